@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- Mshaded-pixels/s of the forward PBR shading pass (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs: set-up, the settle loop, W warm-up steps, the K timed steps, and the line
+(`value`, `ms_per_step` and the roofline derived from the same K steps).  --full adds every other measurement: the cold region, the
+isolated launches, the gather alone (N > 1), whole frames, the extra passes (culling off, 16 / 4 / 0 lights, light statistics) and the
+CPU baseline with its parity check.  --dump-outputs DIR writes what the last timed step returned (dump_outputs) after the timed steps.
 
 Both forms run N ranks, one per GPU: under a launcher (WORLD_SIZE in the environment) this process is one of them; without one
 and N > 1 it starts the N ranks itself (launch_ranks: child processes, before any GPU call), relays rank 0's JSON line and exits
@@ -33,12 +38,12 @@ The JSON line also carries
                (FMA = 2) / kernel_ms / 157.3 TFLOP/s; hbm_frac = real HBM bytes / kernel_ms / 8 TB/s.  The counter inputs are
                STATIC, read from profiles/pmc_latest.json (rocprofv3 --pmc in separate passes, tools/profile_round.sh) and
                profiles/isa_census_latest.json (make census), and labelled so.  Also in the line: the same pass with exact
-               culling off (every pixel lit) and with 16 / 4 / 0 point lights (run after the timed loop; --no-extras
+               culling off (every pixel lit) and with 16 / 4 / 0 point lights (--full only, run after the timed loop; --no-extras
                leaves them out, which is what a rocprofv3 --stats run of this command wants).
   settle       before anything is measured the pass is repeated, untimed, for ARCTIC_BENCH_SETTLE_MS (250): a device that has
                been idle runs its first ~70 ms of load at other clocks than it sustains (0.22 against 0.19 ms per pass).
   cpu_baseline the CPU oracle (scalar C++ port of the same HLSL math) shading a bounded stripe of
-               the SAME G-buffer on this host's cores -- a baseline, not the target.
+               the SAME G-buffer on this host's cores -- a baseline, not the target (--full only).
 """
 import argparse
 import json
@@ -72,18 +77,34 @@ FP32_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: vector FP32 (256 CUs x 4 SI
 # (make -C arctic-renderer_amd/csrc census -> profiles/isa_census_latest.json): the light loop's body exactly, the rest by its static mix.
 CYCLES = {"pk": 4.4, "fast": 2.6, "slow": 4.2, "trans": 8.0}
 SETTLE_MS = float(os.environ.get("ARCTIC_BENCH_SETTLE_MS", "250"))   # untimed: the pass back to back until the device has left its idle clocks
+DUMP_BYTES = 48 << 20         # --dump-outputs: the frame as float32 when it fits in this many bytes, else a seeded sample of its pixels
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def dump_outputs(directory, frame):
+    """--dump-outputs: the RGBA8 frame the last timed step returned (H x W x 4 uint8 on the device), as DIR/frame_rgba8.npy in float32.
+    Whole (H, W, 4) when it fits in DUMP_BYTES; otherwise (n, 4), the pixels at the flat indices
+    np.sort(np.random.default_rng(0).choice(H * W, n, replace=False)) -- the same sample in every run of the same size."""
+    img = frame.cpu().numpy()
+    h, w, c = img.shape
+    if img.size * 4 > DUMP_BYTES:
+        n = DUMP_BYTES // (4 * c)
+        idx = np.sort(np.random.default_rng(0).choice(h * w, n, replace=False))
+        img = img.reshape(h * w, c)[idx]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "frame_rgba8.npy"), img.astype(np.float32))
+
+
 def count_gpus_without_hip():
     """GPUs this process may use, WITHOUT a HIP call (the launcher must not initialise the GPU): the KFD topology's nodes that have SIMDs
     and whose render node this process may open (a lease that restricts devices by cgroup / device-node permissions rather than by
-    environment still lists every GPU in the topology), cut down by the *_VISIBLE_DEVICES lists that are set -- they compose (HIP indexes
-    into what ROCr shows), so the smallest count holds.  0 without an amdgpu compute driver; None when the topology cannot be read: the
-    ranks then fail by themselves, loudly, if a device is missing."""
+    environment still lists every GPU in the topology; one that hides the other GPUs' nodes leaves their properties unreadable: those
+    nodes are not this process's either), cut down by the *_VISIBLE_DEVICES lists that are set -- they compose (HIP indexes
+    into what ROCr shows), so the smallest count holds.  0 without an amdgpu compute driver; None when the topology cannot be read (no
+    node at all): the ranks then fail by themselves, loudly, if a device is missing."""
     listed = []
     for var in ("ROCR_VISIBLE_DEVICES", "HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
         v = os.environ.get(var)
@@ -95,10 +116,14 @@ def count_gpus_without_hip():
         n = 0        # no amdgpu compute driver on this machine at all
     else:
         try:
-            n = 0
+            n, readable = 0, 0
             for node in os.listdir(base):
-                with open(os.path.join(base, node, "properties")) as f:
-                    props = dict(line.split()[:2] for line in f if len(line.split()) >= 2)
+                try:
+                    with open(os.path.join(base, node, "properties")) as f:
+                        props = dict(line.split()[:2] for line in f if len(line.split()) >= 2)
+                except PermissionError:
+                    continue     # in the topology, but not this process's to read
+                readable += 1
                 if int(props.get("simd_count", "0")) <= 0:
                     continue
                 minor = int(props.get("drm_render_minor", "-1"))
@@ -106,6 +131,8 @@ def count_gpus_without_hip():
                 if minor >= 0 and os.path.exists("/dev/dri") and not (os.path.exists(dev) and os.access(dev, os.R_OK | os.W_OK)):
                     continue     # in the topology, but not this process's to open
                 n += 1
+            if readable == 0:
+                n = None
         except (OSError, ValueError):
             n = None
     if listed:
@@ -182,10 +209,15 @@ def main():
     ap.add_argument("--config", type=int, default=3, help="BASELINE.json config number (3 = the metric's config)")
     ap.add_argument("--scale", type=float, default=1.0, help="<1 shrinks the workload (debug only; makes the number invalid)")
     ap.add_argument("--cpu-rows", type=int, default=0, help="rows of the frame the CPU baseline shades (0 = auto)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extra passes (culling off, 16 / 4 / 0 lights, light statistics): "
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed extra passes (culling off, 16 / 4 / 0 lights, light statistics): "
                     "for a rocprofv3 --stats run of this command, whose kernel average should be the timed launches'")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline too: cold region, isolated launches, gather alone, "
+                    "whole frames, extra passes, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the frame the last one returned to DIR/frame_rgba8.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:])      # no launcher around us: be the launcher (no GPU call in this process)
@@ -381,9 +413,9 @@ def main():
         return wall, e0.elapsed_time(e1), first, t_start
 
     # COLD figure first (rounds 1-2 measured this way; kept so that rounds stay comparable from the driver's record alone): the same
-    # W + K steps straight after set-up, before the device has been kept busy for any length of time.
+    # W + K steps straight after set-up, before the device has been kept busy for any length of time (--full).
     cold = None
-    if os.environ.get("ARCTIC_BENCH_COLD", "1") != "0":
+    if args.full and os.environ.get("ARCTIC_BENCH_COLD", "1") != "0":
         c_wall, c_ev, _, _ = timed_region(args.steps, args.warmup)
         if world > 1:
             t = torch.tensor([c_wall], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
@@ -401,17 +433,23 @@ def main():
             for _ in range(50):
                 shade(out_ptrs[0])
             r.flush()
-    # isolated launches, each between its own pair of HIP events (p10/p50/p90 in the line)
-    iters = max(10, min(args.steps, 50))
-    ms = r.time_shade(sc.desc, sc.settings, warmup=20, iters=iters)
-    state["launches"] += 20 + iters
+    # isolated launches, each between its own pair of HIP events (p10/p50/p90 in the line; --full)
+    ms = None
+    if args.full:
+        iters = max(10, min(args.steps, 50))
+        ms = r.time_shade(sc.desc, sc.settings, warmup=20, iters=iters)
+        state["launches"] += 20 + iters
 
     dt, ev_ms, first_timed, t_start = timed_region(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the RGBA8 frame (N > 1: the gathered one on rank 0)
+        dump_outputs(args.dump_outputs, frame if world > 1 else outs[(state["k"] - 1) % n_buf])
     warmup_effective = {"launches": first_timed, "ms": round((t_start - (state["t_first"] or t_start)) * 1e3, 1),
-                        "note": "passes this process had enqueued, and wall time since the first of them, when the timed region began: cold region + settle loop + isolated launches + --warmup"}
+                        "note": "passes this process had enqueued, and wall time since the first of them, when the timed region began: "
+                                + ("cold region + settle loop + isolated launches + --warmup" if args.full else "settle loop + --warmup")}
     kernel_ms = ev_ms / args.steps   # HIP events on the launch stream around the K timed launches
     kernel_ms_source = "HIP events on the launch stream around the K timed steps / K"
-    if world > 1:   # there the span between the events includes the waits for the gathers that free the shard buffers: not kernel time
+    if world > 1 and ms is not None:   # there the span between the events includes the waits for the gathers that free the shard buffers: not kernel time
         kernel_ms = float(np.median(ms))
         kernel_ms_source = "median of this rank's isolated launches (its own shard), each between its own pair of HIP events"
     if world > 1:
@@ -421,7 +459,7 @@ def main():
 
     # outside the timed region: the exchange step alone (gathered bytes / gather time per link)
     gather_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             torch.cuda.synchronize(); dist.barrier()
             t0 = time.perf_counter()
@@ -435,30 +473,31 @@ def main():
         except Exception as exc:   # a measurement extra must never cost the bench line
             log(f"[bench] gather timing skipped: {exc}")
     # whole frames, outside the timed region (shadow raster [only when the sun moves] + visibility prepass of this rank's rows +
-    # shading from the visibility plane [+ gather]): what an application sees, next to the pass the metric is defined on
+    # shading from the visibility plane [+ gather]): what an application sees, next to the pass the metric is defined on (--full)
     whole = {}
-    try:
-        for name, cache in (("static_sun", 1), ("moving_sun", 0)):
-            r.set_option("shadow_cache", cache)
-            for k in range(3 + 20):
-                if k == 3:
-                    r.flush(); torch.cuda.synchronize()
-                    if world > 1:
-                        dist.barrier()
-                    t0 = time.perf_counter()
-                r.render_frame_device(sc.desc, sc.settings, out_ptrs[k % n_buf])
-                if cabi:
-                    r.gather_frame(out_ptrs[k % n_buf], frame_ptr, 0)
-            r.flush(); torch.cuda.synchronize()
-            if world > 1:
-                dist.barrier()
-            whole[name + "_ms"] = round((time.perf_counter() - t0) / 20 * 1e3, 4)
-        r.set_option("shadow_cache", 1)
-        whole["note"] = ("arctic_render_frame_device per rank, 20 frames enqueued back to back (static sun: two frames in flight; moving sun: shadow pass beside the visibility prepass)" + (" + arctic_gather_frame; the shadow map is drawn in light-space row shards "
-                         "and all-gathered when the sun moves" if cabi else "") + "; vertex transform and triangle setup of the whole scene are "
-                         "redundant per rank (DESIGN.md section 5)")
-    except Exception as exc:
-        log(f"[bench] whole-frame timing skipped: {exc}")
+    if args.full:
+        try:
+            for name, cache in (("static_sun", 1), ("moving_sun", 0)):
+                r.set_option("shadow_cache", cache)
+                for k in range(3 + 20):
+                    if k == 3:
+                        r.flush(); torch.cuda.synchronize()
+                        if world > 1:
+                            dist.barrier()
+                        t0 = time.perf_counter()
+                    r.render_frame_device(sc.desc, sc.settings, out_ptrs[k % n_buf])
+                    if cabi:
+                        r.gather_frame(out_ptrs[k % n_buf], frame_ptr, 0)
+                r.flush(); torch.cuda.synchronize()
+                if world > 1:
+                    dist.barrier()
+                whole[name + "_ms"] = round((time.perf_counter() - t0) / 20 * 1e3, 4)
+            r.set_option("shadow_cache", 1)
+            whole["note"] = ("arctic_render_frame_device per rank, 20 frames enqueued back to back (static sun: two frames in flight; moving sun: shadow pass beside the visibility prepass)" + (" + arctic_gather_frame; the shadow map is drawn in light-space row shards "
+                             "and all-gathered when the sun moves" if cabi else "") + "; vertex transform and triangle setup of the whole scene are "
+                             "redundant per rank (DESIGN.md section 5)")
+        except Exception as exc:
+            log(f"[bench] whole-frame timing skipped: {exc}")
     r.set_stream(None)
     # shaded pixels = pixels with geometry (100 % in this scene); counted, not assumed
     _, mat, _, _ = r.read_gbuffer(want=("material",))
@@ -474,7 +513,7 @@ def main():
     n_lights = len(sc.lights)
     extras = {}
     lit_px = None
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         # untimed, after the timed loop.  Light statistics from the counting variant of the kernel:
         r.set_option("count_light_evals", 1)
         r.pass_shade(sc.desc, sc.settings)
@@ -531,7 +570,7 @@ def main():
                 "cold": None if cold is None else dict(cold, frac=round(shaded_local * BYTES_PER_PIXEL / (cold["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)),
                 "kernel_ms": round(kernel_ms, 4),
                 "kernel_ms_source": kernel_ms_source,
-                "isolated_launch_ms_p10_p50_p90": [round(float(np.percentile(ms, q)), 4) for q in (10, 50, 90)],
+                "isolated_launch_ms_p10_p50_p90": None if ms is None else [round(float(np.percentile(ms, q)), 4) for q in (10, 50, 90)],
                 "bytes_per_pixel": BYTES_PER_PIXEL,
                 "rotation": {"sets": len(rotation), "working_set_bytes": working_set,
                              "note": "timed steps rotate over this many handles (own G-buffer, shadow map, textures, output each) when the working set is below "
@@ -566,7 +605,7 @@ def main():
                 roof["valu_flop_frac"] = {"value": round(flops / (kernel_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS, 4), "TFLOPs": round(flops / (kernel_ms * 1e-3) / 1e12, 1),
                                           "peak_TFLOPs": FP32_PEAK_TFLOPS, "flops_per_launch": flops,
                                           "note": "FMA = 2 flops; light loop from its ISA census x executed pair trips, the rest from SQ_INSTS_VALU x the static flop mix of the other code"}
-            else:   # no census / no light statistics (--no-extras) / scalar loop: every non-transcendental instruction at the slow-class cost
+            else:   # no census / no light statistics (--no-extras, or no --full) / scalar loop: every non-transcendental instruction at the slow-class cost
                 cyc = (total - trans) * CYCLES["slow"] + trans * CYCLES["trans"]
                 pricing = {"cycles_per_inst": {"all non-transcendental": CYCLES["slow"], "trans": CYCLES["trans"]}, "source": f"static: {pmc_src}"}
             clk = pmc.get("measured_clock_GHz") or CLOCK_NOMINAL_GHZ
@@ -606,7 +645,7 @@ def main():
                            "note": "one padded shard per rank into rank 0, timed alone (synchronous), outside the timed steps"}},
             "roofline": roof,
         }
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             result["cpu_baseline"] = cpu_baseline(pkg, sc, r, args.cpu_rows)
     for h in rotation[1:]:
         h.close()

@@ -10,7 +10,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -- python3 "$ROOT/bench.py" --no-extras --no-cpu --steps 100 > "$OUT/bench.json" 2> "$OUT/bench.log"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -- python3 "$ROOT/bench.py" --full --no-extras --no-cpu --steps 100 > "$OUT/bench.json" 2> "$OUT/bench.log"
 echo "[profile] kernel trace done"
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" \
