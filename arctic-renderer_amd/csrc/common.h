@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <algorithm>
 
 namespace arctic {
 
@@ -271,7 +272,14 @@ struct ShadeParams {
     unsigned long long *stats;   // STATS kernels only: [0] point-light evaluations, [1] lit pixels, [2] evaluations with n.wi > 0,
                                  // [3] (tile, light) pairs with n.wi <= 0 in every lit lane, [4] tiles with a lit pixel
     unsigned long long *trace;   // ARCTIC_OPT_TILE_TRACE: 4 x u64 per tile (shade.hip: trace_end), or null
-    const uint32_t *tile_order;  // the pass's dispatch order (k_tile_order: strips of 4 tiles, ty << 16 | strip column), n_jobs entries; null: the geometric order
+    // tile_order: the pass's dispatch order (k_tile_order: strips of 4 tiles, ty << 16 | strip column), n_jobs entries; null: the geometric order.
+    // env_tables: image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map), the tables env_light.hip built from the map.  One slot for
+    // both: k_envlit* take the geometric order and never read an order, the other kernels never read the tables.  (Appended as a field of
+    // its own, the pointer grows the block from 392 to 400 bytes -- and that alone reschedules a few instructions of every k_material*.)
+    union {
+        const uint32_t *tile_order;
+        const struct EnvTables *env_tables;
+    };
     uint32_t n_jobs;
     uint32_t pad_o;
     // whole frames without a G-buffer (k_material_vis): the visibility plane and what the prepass left behind
@@ -292,7 +300,44 @@ struct ShadeLaunch {
     uint32_t from_vis;   // 1: k_material_vis (attributes interpolated from the visibility plane) instead of k_material
     uint32_t stats;      // 1: the counting variant (ShadeParams::stats)
     uint32_t tiles_per_wave;   // 0: DEFAULT_TILES_PER_WAVE (ARCTIC_OPT_TILES_PER_WAVE)
+    uint32_t env;        // 1: k_envlit / k_envlit_vis (image-based ambient, ShadeParams::env_tables; geometric tile order, no statistics)
 };
+
+// ---- image-based ambient (ARCTIC_OPT_ENV_LIGHTING, env_light.hip) ------------------------------------------------------
+// The semantics are written once, in include/arctic_hip.h next to the option.  What the shading kernels read, built on the device
+// whenever a map and the option are both present:
+constexpr uint32_t ENV_LEVELS = 6;          // specular levels, roughness k / 5; level 0 is the map itself
+constexpr uint32_t ENV_LUT = 64;            // BRDF table side (n.v x roughness, cell centres)
+constexpr uint32_t ENV_SAMPLES = 512;       // Hammersley samples per prefiltered texel
+constexpr uint32_t ENV_LUT_SAMPLES = 1024;  // ... per BRDF-table cell
+struct EnvTables {
+    float sh[27];                    // E(n) = sum_k sh[3 k + c] Y_k(n): 9 real SH coefficients per channel c, Ramamoorthi-Hanrahan's A_l folded in
+    uint32_t n_levels;               // ENV_LEVELS
+    const float4 *level[ENV_LEVELS]; // RGBA32F equirects, row-major
+    uint32_t w[ENV_LEVELS], h[ENV_LEVELS];
+    const float2 *lut;               // ENV_LUT x ENV_LUT (A, B), row = roughness cell, column = n.v cell
+    uint32_t lut_n, pad;
+};
+// the size of specular level k >= 1 of a W x H map
+inline void env_level_size(uint32_t W, uint32_t H, uint32_t k, uint32_t &w, uint32_t &h) {
+    w = std::max(8u, std::min(W, 512u) >> (k - 1));
+    h = std::max(4u, std::min(H, 256u) >> (k - 1));
+}
+// the box-filtered mip chain the prefilter samples: level m + 1 = max(1, w_m / 2) x max(1, h_m / 2), texel (i, j) = the mean of
+// texels (2i + a, 2j + b), a, b in {0, 1}, clamped to the level's last row / column; down to 1 x 1
+inline uint32_t env_mip_count(uint32_t W, uint32_t H) { uint32_t n = 1; while (W > 1 || H > 1) { W = std::max(1u, W >> 1); H = std::max(1u, H >> 1); ++n; } return n; }
+// device memory of the tables: levels 1..5 back to back, the LUT, the mip chain (levels 1..) of the map, SH partial sums
+struct EnvBuild {
+    const float4 *env; uint32_t W, H;
+    float4 *levels;                  // levels 1..ENV_LEVELS-1, back to back (env_level_size)
+    float2 *lut;
+    float4 *mips;                    // mip levels 1.., back to back
+    double *sh_rows;                 // 27 per map row
+    EnvTables *tables;               // device copy of the struct the kernels read (filled by the host, sh[] by the SH kernel)
+};
+size_t env_levels_bytes(uint32_t W, uint32_t H);
+size_t env_mips_bytes(uint32_t W, uint32_t H);
+hipError_t launch_env_build(const EnvBuild &b, hipStream_t s);
 constexpr uint32_t N_SHADE_STATS = 9;   // [0..4] light statistics, [5..8] shadow-edge statistics of the fast tile (shade.hip)
 constexpr uint32_t DEFAULT_TILES_PER_WAVE = 2;
 // The dispatch order's slots (geometry.hip k_tile_order, shade.hip next_tile): eight lists -- list x = the strips of tile rows ty = x (mod 8) -- of L slots

@@ -207,6 +207,12 @@ struct ArcticRenderer {
     DevBuf &d_shadow_bounds() { return d_shadow_bounds_set[scur]; }
     bool &bounds_valid() { return bounds_valid_set[scur]; }
     uint32_t env_w = 0, env_h = 0;
+    // ARCTIC_OPT_ENV_LIGHTING: the image-based ambient's tables (env_light.hip), built when the map and the option are both there
+    int env_lighting = 0;
+    bool env_built = false;          // the tables belong to the map in d_env
+    DevBuf d_env_levels, d_env_lut, d_env_mips, d_env_sh_rows, d_env_tables;
+    EnvTables env_host = {};         // the device struct's pointers and sizes (its sh[] is written by the device)
+    bool env_active() const { return env_lighting == 1 && env_built; }
     uint32_t n_lights = 0;
     // frame targets
     DevBuf d_vis_set[3], d_p0, d_p1, d_p2, d_p3, d_p4, d_rgba8, d_ldr, d_hdr, d_counter;
@@ -650,11 +656,40 @@ int pass_gbuffer(ArcticRenderer *r, const ArcticScene *sc) {
     return rc != ARCTIC_OK ? rc : resolve_gbuffer(r);
 }
 
+// the image-based ambient's tables from the map in d_env, in stream order on the handle's stream (arctic_create_hdri / arctic_set_option)
+int build_env_tables(ArcticRenderer *r) {
+    const uint32_t W = r->env_w, H = r->env_h;
+    HIPCHECK(r, r->d_env_levels.ensure(env_levels_bytes(W, H)));
+    HIPCHECK(r, r->d_env_lut.ensure((size_t)ENV_LUT * ENV_LUT * sizeof(float2)));
+    HIPCHECK(r, r->d_env_mips.ensure(env_mips_bytes(W, H)));
+    HIPCHECK(r, r->d_env_sh_rows.ensure((size_t)H * 27 * sizeof(double)));
+    HIPCHECK(r, r->d_env_tables.ensure(sizeof(EnvTables)));
+    EnvTables &T = r->env_host;
+    T = EnvTables{};
+    T.n_levels = ENV_LEVELS; T.lut_n = ENV_LUT;
+    T.level[0] = r->d_env.as<float4>(); T.w[0] = W; T.h[0] = H;
+    float4 *lv = r->d_env_levels.as<float4>();
+    for (uint32_t k = 1; k < ENV_LEVELS; ++k) {
+        env_level_size(W, H, k, T.w[k], T.h[k]);
+        T.level[k] = lv; lv += (size_t)T.w[k] * T.h[k];
+    }
+    T.lut = r->d_env_lut.as<float2>();
+    // (the struct goes up in stream order too: the kernels below write its sh[] behind the copy; a pageable source is staged by HIP before the call returns)
+    HIPCHECK(r, hipMemcpyAsync(r->d_env_tables.p, &T, sizeof T, hipMemcpyHostToDevice, r->stream));
+    EnvBuild b = {r->d_env.as<float4>(), W, H, r->d_env_levels.as<float4>(), r->d_env_lut.as<float2>(), r->d_env_mips.as<float4>(),
+                  r->d_env_sh_rows.as<double>(), r->d_env_tables.as<EnvTables>()};
+    HIPCHECK(r, launch_env_build(b, r->stream));
+    r->env_built = true;
+    return ARCTIC_OK;
+}
+
 int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSettings *st, void *d_out, ShadeParams &sp, bool from_vis = false) {
     if (!from_vis && !r->have_gbuffer) {
         if (r->have_vis) { int rc = resolve_gbuffer(r); if (rc != ARCTIC_OK) return rc; }   // frame came from arctic_render_frame
         else return r->fail(ARCTIC_E_STATE, "shade: no G-buffer (run arctic_pass_gbuffer or arctic_write_gbuffer first)");
     }
+    if (r->env_active() && (r->count_evals || r->tile_trace))
+        return r->fail(ARCTIC_E_STATE, "shade: ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply to the image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map)");
     std::memset(&sp, 0, sizeof sp);
     sp.g = r->gbuffer();
     const ArcticRenderer::GeoSet &G = r->geo[r->fwd()];
@@ -694,7 +729,8 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
         sp.trace = r->d_tile_trace.as<unsigned long long>();
     }
     // (the order was built for groups of order_group tiles per wave: a pass that shades another number per wave takes the geometric order)
-    if (!from_vis && r->have_order && r->tile_order && (r->tiles_per_wave == 0 || r->tiles_per_wave == r->order_group)) {
+    if (r->env_active()) sp.env_tables = r->d_env_tables.as<EnvTables>();   // (the geometric order: the tables take the order's slot)
+    else if (!from_vis && r->have_order && r->tile_order && (r->tiles_per_wave == 0 || r->tiles_per_wave == r->order_group)) {
         sp.tile_order = r->d_tile_order.as<uint32_t>(); sp.n_jobs = r->order_slots; sp.tiles_per_wave = r->order_group;
     }
     sp.culling = r->culling;
@@ -724,6 +760,7 @@ hipError_t shade_once(ArcticRenderer *r, const ShadeParams &sp, bool from_vis, b
     L.from_vis = from_vis ? 1u : 0u;
     L.stats = stats ? 1u : 0u;
     L.tiles_per_wave = r->tiles_per_wave;
+    L.env = r->env_active() ? 1u : 0u;
     return launch_shade(sp, L);
 }
 
@@ -882,7 +919,7 @@ void arctic_destroy(ArcticRenderer *r) {
     if (r->own_stream) { (void)hipStreamSynchronize(r->own_stream); (void)hipStreamDestroy(r->own_stream); }
     for (Mesh &m : r->meshes) { if (m.d_vertices) (void)hipFree(m.d_vertices); if (m.d_indices) (void)hipFree(m.d_indices); }
     for (void *p : r->tex_allocs) (void)hipFree(p);
-    DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4,
+    DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4,
                       &r->d_rgba8, &r->d_ldr, &r->d_hdr, &r->d_counter, &r->d_shadow_blocks_set[0], &r->d_shadow_blocks_set[1], &r->d_shadow_bounds_set[0], &r->d_shadow_bounds_set[1], &r->d_staging, &r->d_layout, &r->geo[0].d_xverts, &r->geo[1].d_xverts, &r->geo[2].d_xverts,
                       &r->geo[2].d_recs, &r->geo[2].d_rrecs, &r->geo[2].d_clip_list, &r->geo[2].d_rec_of, &r->geo[2].d_items, &r->tables[2].d,
                       &r->geo[3].d_xverts, &r->geo[3].d_recs, &r->geo[3].d_rrecs, &r->geo[3].d_clip_list, &r->geo[3].d_rec_of, &r->geo[3].d_items, &r->geo[3].d_left, &r->geo[3].d_bin_count, &r->geo[3].d_bin_slots, &r->tables[3].d,
@@ -1063,7 +1100,8 @@ int arctic_create_hdri(ArcticRenderer *r, const float *rgba32f, uint32_t w, uint
     HIPCHECK(r, r->d_env.ensure((size_t)w * h * 16));
     HIPCHECK(r, hipMemcpy(r->d_env.p, rgba32f, (size_t)w * h * 16, hipMemcpyHostToDevice));
     r->env_w = w; r->env_h = h;
-    return ARCTIC_OK;
+    r->env_built = false;   // a new map: new tables (now, or when the option is set)
+    return r->env_lighting == 1 ? build_env_tables(r) : ARCTIC_OK;
 }
 
 int arctic_pass_shadow_map(ArcticRenderer *r, const ArcticScene *scene) {
@@ -1416,6 +1454,21 @@ int arctic_read_tile_order(ArcticRenderer *r, uint32_t *order, uint8_t *tile_cla
     return ARCTIC_OK;
 }
 
+int arctic_read_env_lighting(ArcticRenderer *r, float *sh27, float *lut, uint32_t level, float *texels, uint32_t *dims) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!r->env_built) return r->fail(ARCTIC_E_STATE, "read_env_lighting: no tables (ARCTIC_OPT_ENV_LIGHTING = 1 and an environment map build them)");
+    if (level >= ENV_LEVELS) return r->fail(ARCTIC_E_INVALID, "read_env_lighting: level %u of %u", level, ENV_LEVELS);
+    int rc = select_device(r);
+    if (rc) return rc;
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    const EnvTables &T = r->env_host;
+    if (dims) { dims[0] = T.w[level]; dims[1] = T.h[level]; dims[2] = ENV_LEVELS; dims[3] = ENV_LUT; }
+    if (sh27) HIPCHECK(r, hipMemcpy(sh27, r->d_env_tables.p, 27 * sizeof(float), hipMemcpyDeviceToHost));   // (sh[] is the struct's first member)
+    if (lut) HIPCHECK(r, hipMemcpy(lut, T.lut, (size_t)ENV_LUT * ENV_LUT * sizeof(float2), hipMemcpyDeviceToHost));
+    if (texels) HIPCHECK(r, hipMemcpy(texels, T.level[level], (size_t)T.w[level] * T.h[level] * sizeof(float4), hipMemcpyDeviceToHost));
+    return ARCTIC_OK;
+}
+
 int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
     if (!r) return ARCTIC_E_INVALID;
     switch (option) {
@@ -1474,6 +1527,11 @@ int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
     case ARCTIC_OPT_RASTER_OWNER: r->raster_owner = value < 0 ? -1 : (int)(value & 3); r->shadow_key.clear(); break;
     case ARCTIC_OPT_SHADOW_CACHE: r->shadow_cache = value != 0; r->shadow_key.clear(); break;
     case ARCTIC_OPT_SHADOW_SHARDED: r->shadow_sharded = value != 0; r->shadow_key.clear(); break;
+    case ARCTIC_OPT_ENV_LIGHTING:
+        if (value < 0 || value > 1) return r->fail(ARCTIC_E_INVALID, "ARCTIC_OPT_ENV_LIGHTING: 0 or 1");
+        r->env_lighting = (int)value;
+        if (r->env_lighting == 1 && r->env_w && !r->env_built) { int rc = select_device(r); if (rc) return rc; return build_env_tables(r); }
+        break;
     default: return r->fail(ARCTIC_E_INVALID, "set_option: unknown option %u", option);
     }
     return ARCTIC_OK;

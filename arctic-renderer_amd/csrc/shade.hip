@@ -883,12 +883,15 @@ __device__ __noinline__ f3 sample_environment(const float4 *__restrict__ env, ui
 // gets the same bits whichever of them shades it.
 // LOOP 1: scalar loop.  LOOP 2: two lights at a time in packed fp32.  Both read the lights through the scalar cache.
 // STATS: count lit pixels, evaluated lights, contributing (n.wi > 0) evaluations and wave-wide zero evaluations into sp.stats.
+// get_normal :104-111: rgb with g -> 1 - g, * 2 - 1, then mul(tbn, v), tbn columns t, b, n
+__device__ __forceinline__ f3 get_normal(float nr, float ng, float nb, const float4 &gc, const float4 &gd, const float4 &ge) {
+    const float r = snorm_of_bytes(nr), g = -snorm_of_bytes(ng), b = snorm_of_bytes(nb);   // (1 - g) * 2 - 1 = -(2 g - 1); nr, ng, nb on the 0..255 scale
+    return normalize(mk(fm(ge.y, b, fm(gd.z, g, gc.w * r)), fm(ge.z, b, fm(gd.w, g, gd.x * r)), fm(ge.w, b, fm(ge.x, g, gd.y * r))));
+}
 template <int LOOP, bool STATS>
 __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float ng, float nb, float rough, float metal, f3 base,
                                            const float4 &gc, const float4 &gd, const float4 &ge) {
-    // get_normal :104-111: rgb with g -> 1 - g, * 2 - 1, then mul(tbn, v), tbn columns t, b, n
-    const float r = snorm_of_bytes(nr), g = -snorm_of_bytes(ng), b = snorm_of_bytes(nb);   // (1 - g) * 2 - 1 = -(2 g - 1); nr, ng, nb on the 0..255 scale
-    const f3 n = normalize(mk(fm(ge.y, b, fm(gd.z, g, gc.w * r)), fm(ge.z, b, fm(gd.w, g, gd.x * r)), fm(ge.w, b, fm(ge.x, g, gd.y * r))));
+    const f3 n = get_normal(nr, ng, nb, gc, gd, ge);
     const f3 world = mk(gc.x, gc.y, gc.z);
     const LightArgs la = light_args(sp);   // one batch of scalar loads, in the shadow of the tile's second wave of vector loads
     const f3 wo = normalize(mk(la.eye[0], la.eye[1], la.eye[2]) - world);
@@ -988,6 +991,67 @@ __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float
         }
     }
     return Lo;
+}
+
+// ---- image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1, the k_envlit kernels; semantics in include/arctic_hip.h) ----------------
+// The bracket of   color = Lo (1 - shadow) + ambient [ (1 - F)(1 - metal) base E(n) / pi + P(R, rough) (F0 A + B) ]   from the tables
+// env_light.hip built (EnvTables): E from 27 SH coefficients (scalar loads), P trilinear over the specular levels (bilinear, WRAP;
+// the skybox's direction -> uv mapping), (A, B) bilinear from the clamped 64 x 64 table.  Plain fp32: the per-pixel lookups are
+// smooth functions of the direction (levels >= 1 are prefiltered; level 0 weighs in only below roughness 0.2).
+__device__ __forceinline__ f3 env_level(const EnvTables *T, uint32_t k, float u, float v) {
+    const float4 *img = T->level[k];
+    const uint32_t w = T->w[k], h = T->h[k];
+    int x0, x1, y0, y1;
+    float fx, fy;
+    wrap_axis(u, w, x0, x1, fx);
+    wrap_axis(v, h, y0, y1, fy);
+    const float4 a = img[(size_t)y0 * w + x0], b = img[(size_t)y0 * w + x1], c = img[(size_t)y1 * w + x0], d = img[(size_t)y1 * w + x1];
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+    const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
+    return mk(fm(w11, d.x, fm(w01, c.x, fm(w10, b.x, w00 * a.x))), fm(w11, d.y, fm(w01, c.y, fm(w10, b.y, w00 * a.y))),
+              fm(w11, d.z, fm(w01, c.z, fm(w10, b.z, w00 * a.z))));
+}
+__device__ __forceinline__ f3 env_ambient(const EnvTables *T, f3 n, f3 wo, f3 base, float metal, float rough) {
+    typedef const float __attribute__((address_space(4))) *const_f;   // wave-uniform: the coefficients come through the scalar cache
+    const const_f sh = (const_f)T->sh;
+    // irradiance: real SH basis (env_light.hip sh_basis), A_l folded into the coefficients
+    const float Y[9] = {0.28209479f, 0.48860251f * n.y, 0.48860251f * n.z, 0.48860251f * n.x, 1.09254843f * (n.x * n.y), 1.09254843f * (n.y * n.z),
+                        0.31539157f * (3.0f * (n.z * n.z) - 1.0f), 1.09254843f * (n.x * n.z), 0.54627422f * (n.x * n.x - n.y * n.y)};
+    float E[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float e = sh[c] * Y[0];
+#pragma unroll
+        for (int k = 1; k < 9; ++k) e = fm(sh[3 * k + c], Y[k], e);
+        E[c] = e;
+    }
+    // Fresnel with roughness (per channel)
+    const float ndwo_raw = dot(n, wo), ndwo = fmaxf(ndwo_raw, 0.0f);
+    const f3 F0 = mk(fm(metal, base.x - 0.04f, 0.04f), fm(metal, base.y - 0.04f, 0.04f), fm(metal, base.z - 0.04f, 0.04f));
+    const float om = 1.0f - ndwo, om2 = om * om, p5 = om2 * om2 * om, omr = 1.0f - rough, oml = 1.0f - metal;
+    const f3 F = mk(fm(fmaxf(omr, F0.x) - F0.x, p5, F0.x), fm(fmaxf(omr, F0.y) - F0.y, p5, F0.y), fm(fmaxf(omr, F0.z) - F0.z, p5, F0.z));
+    // (A, B): bilinear, clamped, cell centres
+    const float lx = fminf(fmaxf(ndwo * (float)ENV_LUT - 0.5f, 0.0f), (float)(ENV_LUT - 1)), ly = fminf(fmaxf(rough * (float)ENV_LUT - 0.5f, 0.0f), (float)(ENV_LUT - 1));
+    const uint32_t i0 = (uint32_t)lx, j0 = (uint32_t)ly, i1 = min(i0 + 1u, ENV_LUT - 1), j1 = min(j0 + 1u, ENV_LUT - 1);
+    const float ax = lx - (float)i0, ay = ly - (float)j0;
+    const float2 l00 = T->lut[j0 * ENV_LUT + i0], l10 = T->lut[j0 * ENV_LUT + i1], l01 = T->lut[j1 * ENV_LUT + i0], l11 = T->lut[j1 * ENV_LUT + i1];
+    const float bx = 1.0f - ax, by = 1.0f - ay;
+    const float A = fm(ax * ay, l11.x, fm(bx * ay, l01.x, fm(ax * by, l10.x, (bx * by) * l00.x)));
+    const float B = fm(ax * ay, l11.y, fm(bx * ay, l01.y, fm(ax * by, l10.y, (bx * by) * l00.y)));
+    // P(R, rough): the skybox's mapping of R = 2 (n.wo) n - wo, levels floor(5 r) and the next
+    const float two = 2.0f * ndwo_raw;
+    const f3 R = normalize(mk(fm(two, n.x, -wo.x), fm(two, n.y, -wo.y), fm(two, n.z, -wo.z)));
+    const float u = atan2f(R.z, R.x) * 0.1591f + 0.5f;
+    const float v = -(asinf(fminf(fmaxf(R.y, -1.0f), 1.0f)) * 0.3183f + 0.5f);
+    const float t = rough * (float)(ENV_LEVELS - 1);
+    const uint32_t k0 = min((uint32_t)t, ENV_LEVELS - 1), k1 = min(k0 + 1u, ENV_LEVELS - 1);
+    const float f = t - (float)k0;
+    const f3 P0 = env_level(T, k0, u, v), P1 = env_level(T, k1, u, v);
+    const f3 P = mk(fm(f, P1.x - P0.x, P0.x), fm(f, P1.y - P0.y, P0.y), fm(f, P1.z - P0.z, P0.z));
+    const float kb = oml * INV_PI;
+    return mk(fm((1.0f - F.x) * kb * base.x, E[0], P.x * fm(F0.x, A, B)),
+              fm((1.0f - F.y) * kb * base.y, E[1], P.y * fm(F0.y, A, B)),
+              fm((1.0f - F.z) * kb * base.z, E[2], P.z * fm(F0.z, A, B)));
 }
 
 // ---- ps_main + post_process for one 8x8 tile (one wave): the FAST tile ---------------------------------------------------
@@ -1099,7 +1163,9 @@ __device__ __forceinline__ bool shade_tile_fast(SP sp, KernArgs args, const Args
 
 // ---- the GENERAL tile: ragged tiles at the target's edge, pixels without geometry (skybox), several materials in one tile,
 // materials with images of unequal sizes, the 25-tap shadow test, the debug / timing options --------------------------------
-template <int LOOP, bool STATS, bool LDS_SHADOW, class Second>
+// ENV (k_envlit*): every covered pixel, shadowed or not, loads its second 48 bytes, normal, metalness and roughness and takes the
+// image-based ambient term instead of ambient * base; the light loop is still for lit pixels only.
+template <int LOOP, bool STATS, bool LDS_SHADOW, bool ENV = false, class Second>
 __device__ __forceinline__ void shade_tile(SP sp, const float *lut, float *shadow_tile, uint32_t ty, uint32_t tx,
                                            uint32_t lane, const TileHead &cur, Second second) {
     const uint32_t x = tx * 8 + (lane & 7);
@@ -1168,7 +1234,7 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, float *shado
     // exact culling: see shade_tile_fast
     const bool live = covered && (sp.culling ? lit != 0.0f : true);
     float4 gc, gd, ge;
-    if (live) second(sp.g.c, sp.g.d, sp.g.e, gc, gd, ge);   // second wave of loads: lit pixels only (48 B / pixel, whole 128-byte tile rows)
+    if (ENV ? covered : live) second(sp.g.c, sp.g.d, sp.g.e, gc, gd, ge);   // second wave of loads: lit pixels only (48 B / pixel, whole 128-byte tile rows)
 
     // ---- C: base colour; pixels without geometry: the skybox -----------------------------------------------------------
     if (covered && !plain) base = mk(filt_srgb<0>(pt, lut), filt_srgb<1>(pt, lut), filt_srgb<2>(pt, lut));
@@ -1183,7 +1249,7 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, float *shado
     }
 
     // ---- D: the lights ---------------------------------------------------------------------------------------------
-    if (live) {
+    if (ENV ? covered : live) {
         float nr, ng, nb, rough, metal;
         if (!plain) {
             nr = filt_bytes<0, 3>(pt); ng = filt_bytes<1, 0>(pt); nb = filt_bytes<1, 1>(pt);
@@ -1205,8 +1271,15 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, float *shado
                 todo &= ~__ballot(mine);
             }
         }
-        const f3 Lo = lit_radiance<LOOP, STATS>(sp, lane, nr, ng, nb, rough, metal, base, gc, gd, ge);
-        color = mk(__builtin_fmaf(Lo.x, lit, color.x), __builtin_fmaf(Lo.y, lit, color.y), __builtin_fmaf(Lo.z, lit, color.z));
+        if (ENV) {   // the image-based ambient replaces ambient * base (n, wo: what lit_radiance takes)
+            const f3 n = get_normal(nr, ng, nb, gc, gd, ge);
+            const f3 wo = normalize(mk(sp.eye[0], sp.eye[1], sp.eye[2]) - mk(gc.x, gc.y, gc.z));
+            color = env_ambient(sp.env_tables, n, wo, base, metal, rough) * sp.ambient;
+        }
+        if (!ENV || live) {
+            const f3 Lo = lit_radiance<LOOP, STATS>(sp, lane, nr, ng, nb, rough, metal, base, gc, gd, ge);
+            color = mk(__builtin_fmaf(Lo.x, lit, color.x), __builtin_fmaf(Lo.y, lit, color.y), __builtin_fmaf(Lo.z, lit, color.z));
+        }
     }
 
     // ---- E: post_process + store ---------------------------------------------------------------------------------------
@@ -1340,6 +1413,47 @@ __global__ __launch_bounds__(64 * ARCTIC_WG_WAVES) __attribute__((amdgpu_waves_p
         asm volatile("" : "+s"(args));
         A = args_a(args);                      // (nothing of the block stays in registers across a tile)
         O = order_args(args);
+        if (!next_tile(A, O, blk, k, tx, ty)) break;
+        cur = load_head(A.ga, A.gb, (size_t)ty * A.tiles_x + tx, wave_lane());
+    }
+}
+
+// ---- the image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map) over a resident G-buffer: k_material's walk, every tile through
+// shade_tile<ENV> (the fast tile's early exit for shadowed pixels does not hold here), the geometric order, no statistics, no trace.
+// (A copy of k_material's walk, not a function both kernels share: inlined through one more level, the walk comes out of the compiler
+// with a few instructions of every k_material* rescheduled -- and the default kernels' instructions are kept as they were.)
+template <int LOOP>
+__global__ __launch_bounds__(64 * ARCTIC_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_envlit(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    KernArgs args = kernel_args();
+    const BlockId blk = block_id<ARCTIC_WG_WAVES>();
+    const float *srgb_lut;
+    const unsigned long long *vis_unused;
+    OrderArgs O;
+    ArgsA A = args_a_first(args, srgb_lut, vis_unused, O);
+    O.order = nullptr;   // (the slot holds the environment tables: ShadeParams::env_tables)
+    uint32_t tx, ty, k = 0;
+    if (!next_tile(A, O, blk, k, tx, ty)) return;
+    TileHead cur;
+    {
+        const uint32_t lane = wave_lane();
+        const LutRegs lr = lut_load(srgb_lut, lane);
+        cur = load_head(A.ga, A.gb, (size_t)ty * A.tiles_x + tx, lane);
+        lut_store(lut, lane, lr);
+    }
+#pragma nounroll
+    for (;;) {
+        asm volatile("" : "+s"(args));   // see SP
+        SP sp = *args;
+        const uint32_t lane = wave_lane();
+        const size_t tile = (size_t)ty * A.tiles_x + tx;   // wave-uniform
+        const auto second = [&](const float4 *pc, const float4 *pd, const float4 *pe, float4 &gc, float4 &gd, float4 &ge) {
+            gc = gload_f4(pc + tile * 64, lane * 16u); gd = gload_f4(pd + tile * 64, lane * 16u); ge = gload_f4(pe + tile * 64, lane * 16u);
+        };
+        shade_tile<LOOP, false, false, true>(sp, lut, nullptr, ty, tx, lane, cur, second);
+        if (++k >= A.T) break;
+        asm volatile("" : "+s"(args));
+        A = args_a(args);
         if (!next_tile(A, O, blk, k, tx, ty)) break;
         cur = load_head(A.ga, A.gb, (size_t)ty * A.tiles_x + tx, wave_lane());
     }
@@ -1493,6 +1607,131 @@ __global__ __launch_bounds__(64 * VIS_WG_WAVES) __attribute__((amdgpu_waves_per_
     }
 }
 
+// ---- the image-based ambient over whole frames, straight from the visibility plane: k_material_vis's walk as k_envlit is k_material's
+// (a copy for the same reason)
+template <int LOOP>
+__global__ __launch_bounds__(64 * VIS_WG_WAVES) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_envlit_vis(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    KernArgs args = kernel_args();
+    const BlockId blk = block_id<VIS_WG_WAVES>();
+    const float *srgb_lut;
+    const unsigned long long *vis_plane;
+    OrderArgs O;
+    ArgsA A = args_a_first(args, srgb_lut, vis_plane, O);
+    O.order = nullptr;   // (the slot holds the environment tables)
+    uint32_t tx, ty, k = 0;
+    unsigned long long key = ~0ull;
+    if (!next_tile(A, O, blk, k, tx, ty)) return;
+    {
+        const uint32_t lane = wave_lane();
+        const LutRegs lr = lut_load(srgb_lut, lane);
+        key = vis_plane[((size_t)ty * A.tiles_x + tx) * 64 + lane];
+        lut_store(lut, lane, lr);
+    }
+#pragma nounroll
+    for (;;) {
+    asm volatile("" : "+s"(args));   // see SP
+    SP sp = *args;
+    const uint32_t lane = wave_lane();
+    const int32_t px = (int32_t)(tx * 8 + (lane & 7));
+    const int32_t py = (row_global((int)ty, sp.band_tiles, sp.shard_count, sp.shard_index) + sp.tile_y0) * 8 + (int32_t)(lane >> 3);
+    TileHead cur;
+    cur.a = make_float4(0.0f, 0.0f, 0.0f, 0.0f); cur.b0 = 0.0f; cur.b1 = 0.0f; cur.b2 = __uint_as_float(NO_MATERIAL);
+    float B[3] = {0.0f, 0.0f, 0.0f};
+    uint32_t v0 = 0, v1 = 0, v2 = 0;   // the source triangle's transformed vertices (indices, not pointers: they stay live across the tile)
+    // attribute k of transformed vertex v: XVert::attr at byte 16 + 4k of a 96-byte record.  With compact tables (below 4 GiB each, the
+    // host says) every gather is a wave-uniform base + a 32-bit byte offset: no 64-bit multiply-adds per lane and load
+    const bool compact = sp.compact_tables != 0;
+    if (key != ~0ull && compact) {
+        const uint32_t ri = gload_u32(sp.rec_of, (uint32_t)key << 2);   // low word of the key = order id (k_setup)
+        const uint32_t so = ri << 7;                                     // SetupRec and RasterRec are 128 bytes
+        const float4u qf = gload_f4u(sp.rrecs, so + 96u);                // dz2, inv_area, order id, flags
+        const u4v src = gload_u4u(sp.rrecs, so + 112u);                  // the source triangle's three transformed vertices, its material
+        if (__float_as_uint(qf.w) & RASTER_EXACT_F64) {
+            typedef double d2v __attribute__((ext_vector_type(2)));
+            const auto ld2 = [&](uint32_t o) { return *(const d2v __attribute__((address_space(1))) *)((gchar)sp.rrecs + o); };
+            const auto ld1 = [&](uint32_t o) { return *(const double __attribute__((address_space(1))) *)((gchar)sp.rrecs + o); };
+            const double A0 = ld1(so), C0 = ld1(so + 48u), A2 = ld1(so + 16u), B0 = ld1(so + 24u), B2 = ld1(so + 40u), C2 = ld1(so + 64u);
+            (void)ld2;
+            const float4u s2 = gload_f4u(sp.recs, so + 32u);             // z[2], iw[0..2]
+            const uint32_t fl = __float_as_uint(qf.w);
+            {   // source_barycentrics (edges.h), on the fields just loaded: the same operations in the same order
+#pragma clang fp contract(off)
+                const double x = (double)px, y = (double)py;
+                const float l1 = (float)__builtin_fma(A2, x, __builtin_fma(B2, y, C2)) * qf.y;
+                const float l2 = (float)__builtin_fma(A0, x, __builtin_fma(B0, y, C0)) * qf.y;
+                const float l0 = (1.0f - l1) - l2;
+                const float pw0 = l0 * s2.y, pw1 = l1 * s2.z, pw2 = l2 * s2.w;
+                const float rr = 1.0f / ((pw0 + pw1) + pw2);
+                const float c0 = pw0 * rr, c1 = pw1 * rr, c2 = pw2 * rr;
+                if (__ballot((fl & RASTER_UNIT_BARY) == 0u) == 0ull) {
+                    // every record under the tile is an uncut source triangle (nearly every tile): the rows of its barycentric matrix are
+                    // unit vectors and the products below return c0, c1, c2 themselves -- in source order when set-up exchanged two vertices
+                    const bool swapped = (fl & RASTER_SWAPPED) != 0u;
+                    B[0] = c0; B[1] = swapped ? c2 : c1; B[2] = swapped ? c1 : c2;
+                } else {   // a tile with a cut triangle under it: the product per lane, and the lanes of uncut triangles as above (source_barycentrics' rule: edges.h)
+                    const float4u b0 = gload_f4u(sp.recs, so + 48u), b1 = gload_f4u(sp.recs, so + 64u);   // bary[0][0..2], bary[1][0] | bary[1][1..2], bary[2][0..1]
+                    const float b22 = __uint_as_float(gload_u32(sp.recs, so + 80u));
+                    const bool unit = (fl & RASTER_UNIT_BARY) != 0u, swapped = (fl & RASTER_SWAPPED) != 0u;
+                    const float p0 = (c0 * b0.x + c1 * b0.w) + c2 * b1.z, p1 = (c0 * b0.y + c1 * b1.x) + c2 * b1.w, p2 = (c0 * b0.z + c1 * b1.y) + c2 * b22;
+                    B[0] = unit ? c0 : p0; B[1] = unit ? (swapped ? c2 : c1) : p1; B[2] = unit ? (swapped ? c1 : c2) : p2;
+                }
+            }
+        } else source_barycentrics(sp.recs[ri], sp.rrecs[ri], px, py, B);   // rare: coordinates of 2^24 and more
+        cur.b2 = __uint_as_float(src.w);
+        v0 = src.x; v1 = src.y; v2 = src.z;
+        const uint32_t a0 = v0 * 96u + 16u, a1 = v1 * 96u + 16u, a2 = v2 * 96u + 16u;
+        const float2 u0 = gload_f2(sp.xv, a0), u1 = gload_f2(sp.xv, a1), u2 = gload_f2(sp.xv, a2);                    // attr 0, 1
+        const float4u w0 = gload_f4u(sp.xv, a0 + 56u), w1 = gload_f4u(sp.xv, a1 + 56u), w2 = gload_f4u(sp.xv, a2 + 56u);   // attr 14..17
+        const auto mix = [&](float x0, float x1, float x2) {
+#pragma clang fp contract(off)
+            return (B[0] * x0 + B[1] * x1) + B[2] * x2;   // interpolate_attr (edges.h)
+        };
+        cur.a = make_float4(mix(u0.x, u1.x, u2.x), mix(u0.y, u1.y, u2.y), mix(w0.x, w1.x, w2.x), mix(w0.y, w1.y, w2.y));
+        cur.b0 = mix(w0.z, w1.z, w2.z); cur.b1 = mix(w0.w, w1.w, w2.w);
+    } else if (key != ~0ull) {
+        const uint32_t ri = sp.rec_of[(uint32_t)key];
+        const SetupRec &t = sp.recs[ri];
+        source_barycentrics(t, sp.rrecs[ri], px, py, B);
+        const ObjectRec &ob = sp.objs[t.object];
+        const uint32_t lt = t.src_tri - ob.first_triangle;
+        v0 = ob.first_xvert + ob.indices[3 * lt]; v1 = ob.first_xvert + ob.indices[3 * lt + 1]; v2 = ob.first_xvert + ob.indices[3 * lt + 2];
+        const float *A0 = sp.xv[v0].attr, *A1 = sp.xv[v1].attr, *A2 = sp.xv[v2].attr;
+        cur.a = make_float4(interpolate_attr(B, A0, A1, A2, 0), interpolate_attr(B, A0, A1, A2, 1),
+                            interpolate_attr(B, A0, A1, A2, 14), interpolate_attr(B, A0, A1, A2, 15));
+        cur.b0 = interpolate_attr(B, A0, A1, A2, 16); cur.b1 = interpolate_attr(B, A0, A1, A2, 17);
+        cur.b2 = __uint_as_float(ob.material);
+    }
+    const auto second = [&](const float4 *, const float4 *, const float4 *, float4 &gc, float4 &gd, float4 &ge) {
+        // attribute order (XVert::attr): uv 0-1, t 2-4, b 5-7, n 8-10, world 11-13, light space 14-17; planes as gbuffer_pack
+        const auto mix = [&](float x0, float x1, float x2) {
+#pragma clang fp contract(off)
+            return (B[0] * x0 + B[1] * x1) + B[2] * x2;
+        };
+        if (compact) {
+            const uint32_t a0 = v0 * 96u + 24u, a1 = v1 * 96u + 24u, a2 = v2 * 96u + 24u;   // attr 2..13: three float4 per vertex
+            const float4u p0 = gload_f4u(sp.xv, a0), p1 = gload_f4u(sp.xv, a1), p2 = gload_f4u(sp.xv, a2);                     // attr 2..5
+            const float4u q0 = gload_f4u(sp.xv, a0 + 16u), q1 = gload_f4u(sp.xv, a1 + 16u), q2 = gload_f4u(sp.xv, a2 + 16u);   // attr 6..9
+            const float4u r0 = gload_f4u(sp.xv, a0 + 32u), r1 = gload_f4u(sp.xv, a1 + 32u), r2 = gload_f4u(sp.xv, a2 + 32u);   // attr 10..13
+            gc = make_float4(mix(r0.y, r1.y, r2.y), mix(r0.z, r1.z, r2.z), mix(r0.w, r1.w, r2.w), mix(p0.x, p1.x, p2.x));
+            gd = make_float4(mix(p0.y, p1.y, p2.y), mix(p0.z, p1.z, p2.z), mix(p0.w, p1.w, p2.w), mix(q0.x, q1.x, q2.x));
+            ge = make_float4(mix(q0.y, q1.y, q2.y), mix(q0.z, q1.z, q2.z), mix(q0.w, q1.w, q2.w), mix(r0.x, r1.x, r2.x));
+        } else {
+            const float *A0 = sp.xv[v0].attr, *A1 = sp.xv[v1].attr, *A2 = sp.xv[v2].attr;
+            gc = make_float4(interpolate_attr(B, A0, A1, A2, 11), interpolate_attr(B, A0, A1, A2, 12), interpolate_attr(B, A0, A1, A2, 13), interpolate_attr(B, A0, A1, A2, 2));
+            gd = make_float4(interpolate_attr(B, A0, A1, A2, 3), interpolate_attr(B, A0, A1, A2, 4), interpolate_attr(B, A0, A1, A2, 5), interpolate_attr(B, A0, A1, A2, 6));
+            ge = make_float4(interpolate_attr(B, A0, A1, A2, 7), interpolate_attr(B, A0, A1, A2, 8), interpolate_attr(B, A0, A1, A2, 9), interpolate_attr(B, A0, A1, A2, 10));
+        }
+    };
+    shade_tile<LOOP, false, false, true>(sp, lut, nullptr, ty, tx, lane, cur, second);
+    if (++k >= A.T) break;
+    asm volatile("" : "+s"(args));
+    A = args_a(args);
+    if (!next_tile(A, O, blk, k, tx, ty)) break;
+    key = args->vis[((size_t)ty * A.tiles_x + tx) * 64 + wave_lane()];
+    }
+}
+
 // ---- shadow bounds: the conservative min/max table calculate_lit tests first -------------------------------------------
 // Two launches whenever the shadow map changes (64 MB read once at S = 4000; ~0.02 ms): blocks[j][i] = min/max of the 4x4
 // texel block (i, j) (clamped at the map's edge), then entry (i, j) = blocks (i..i+1, j..j+1): texels [4i, 4i+8) x [4j, 4j+8).
@@ -1534,6 +1773,16 @@ __global__ __launch_bounds__(256) void k_post_process(const float4 *__restrict__
 
 template <int LOOP, bool STATS, bool LDS_SHADOW>
 hipError_t launch_variant(const ShadeParams &sp, const ShadeLaunch &L, dim3 grid) {
+    if (L.env) {   // (geometric order, no statistics, no LDS variant: launch_shade)
+        if (L.from_vis) {
+            if (VIS_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;
+            k_envlit_vis<LOOP><<<grid, 64 * VIS_WG_WAVES, 0, L.stream>>>(sp);
+        } else {
+            if (ARCTIC_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;
+            k_envlit<LOOP><<<grid, 64 * ARCTIC_WG_WAVES, 0, L.stream>>>(sp);
+        }
+        return hipGetLastError();
+    }
     if (L.from_vis) {
         if (VIS_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;   // (block_id, as below)
         k_material_vis<LOOP, STATS, LDS_SHADOW><<<grid, 64 * VIS_WG_WAVES, 0, L.stream>>>(sp);
@@ -1552,6 +1801,7 @@ hipError_t launch_shade(const ShadeParams &sp_in, const ShadeLaunch &L) {
     const uint32_t n_tiles = sp_in.tiles_x * sp_in.tiles_y;
     if (n_tiles == 0) return hipSuccess;
     ShadeParams sp = sp_in;
+    // (the image-based ambient: tiles in the geometric order -- ARCTIC_OPT_TILE_ORDER is a hint --, the order's slot holds the tables)
     // two tiles per wave pay once a frame is several rounds of the chip's wave slots; below ~3 Mpx one tile per wave is faster
     // (tools/experiments/small_frames.py: 1080p pass 0.0638 -> 0.0610 ms, whole frame 0.098 -> 0.084 ms with T = 1; 2688 x 1512: 0.101 against
     // 0.104 ms and 0.142 against 0.153 with T = 2)
@@ -1559,8 +1809,9 @@ hipError_t launch_shade(const ShadeParams &sp_in, const ShadeLaunch &L) {
     const uint32_t bpr = (sp.tiles_x + 3) / 4, groups = (sp.tiles_y + 7) / 8;
     sp.group_stride = (groups + sp.tiles_per_wave - 1) / sp.tiles_per_wave;
     dim3 grid(8 * bpr, sp.group_stride);   // a block shades tiles_per_wave groups of 8 tile rows, group_stride groups apart
-    if (sp.tile_order)                     // ... or tiles_per_wave consecutive slots of the prepass's dispatch order (n_jobs slots, common.h order_slot: a block = one XCD's list)
+    if (sp.tile_order && !L.env)           // ... or tiles_per_wave consecutive slots of the prepass's dispatch order (n_jobs slots, common.h order_slot: a block = one XCD's list)
         grid = dim3((sp.n_jobs + sp.tiles_per_wave - 1) / sp.tiles_per_wave, 1);
+    if (L.env) return L.loop == 2 ? launch_variant<2, false, false>(sp, L, grid) : launch_variant<1, false, false>(sp, L, grid);
     if (sp.debug & 16)   // A/B only: the 25-tap path staged through LDS (a separate instantiation: it costs the default kernels nothing)
         return L.loop == 2 ? launch_variant<2, false, true>(sp, L, grid) : launch_variant<1, false, true>(sp, L, grid);
     if (L.loop == 2) return L.stats ? launch_variant<2, true, false>(sp, L, grid) : launch_variant<2, false, false>(sp, L, grid);

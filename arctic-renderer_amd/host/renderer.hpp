@@ -90,6 +90,13 @@ class Renderer {
     [[nodiscard]] bool create_hdri(float *data, uint32_t width, uint32_t height) { return ok(arctic_create_hdri(m_handle, data, width, height)); }
     void update_lights(std::span<PointLight> point_lights) { (void)ok(arctic_update_lights(m_handle, point_lights.data(), point_lights.size())); }
     [[nodiscard]] bool flush() { return ok(arctic_flush(m_handle)); }
+    // image-based ambient from the HDRI (ARCTIC_OPT_ENV_LIGHTING; no counterpart in the reference, whose ps_main keeps a flat ambient):
+    // false = the reference's ambient * base_color.  Safe to set before or after create_hdri, and without a map at all.
+    [[nodiscard]] bool set_env_lighting(bool on) { return ok(arctic_set_option(m_handle, ARCTIC_OPT_ENV_LIGHTING, on ? 1 : 0)); }
+    // its tables (arctic_read_env_lighting): any pointer may be null; dims = {w, h of `level`, levels, LUT side}
+    [[nodiscard]] bool read_env_lighting(float *sh27, float *lut, uint32_t level, float *texels, uint32_t *dims) {
+        return ok(arctic_read_env_lighting(m_handle, sh27, lut, level, texels, dims));
+    }
 
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }

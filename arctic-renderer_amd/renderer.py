@@ -268,6 +268,23 @@ class Renderer:
         self._check(self.L.arctic_read_cull_counts(self.h, int(shadow_pass), _ptr(out)))
         return out
 
+    def read_env_lighting(self, level=None):
+        """the tables of set_option("env_lighting", 1) (arctic_read_env_lighting): (sh (9, 3) float32 -- E(n) = sum_k sh[k] Y_k(n), A_l
+        folded in --, lut (64, 64, 2) float32 (A, B), row = roughness cell, column = n.v cell, levels: list of (h, w, 4) float32, level 0 =
+        the environment map); level=k returns only that level in the list."""
+        dims = np.zeros(4, np.uint32)
+        self._check(self.L.arctic_read_env_lighting(self.h, None, None, 0, None, _ptr(dims)))
+        n_levels, side = int(dims[2]), int(dims[3])
+        sh, lut = np.empty(27, np.float32), np.empty((side, side, 2), np.float32)
+        self._check(self.L.arctic_read_env_lighting(self.h, _ptr(sh), _ptr(lut), 0, None, None))
+        levels = []
+        for k in (range(n_levels) if level is None else [level]):
+            self._check(self.L.arctic_read_env_lighting(self.h, None, None, k, None, _ptr(dims)))
+            t = np.empty((int(dims[1]), int(dims[0]), 4), np.float32)
+            self._check(self.L.arctic_read_env_lighting(self.h, None, None, k, _ptr(t), None))
+            levels.append(t)
+        return sh.reshape(9, 3), lut, levels
+
     def set_option(self, name, value):
         self._check(self.L.arctic_set_option(self.h, binding.OPTIONS[name], int(value)))
 

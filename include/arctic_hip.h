@@ -339,7 +339,46 @@ int arctic_stats(ArcticRenderer *r, uint64_t *out, uint32_t n);
                                           Where the shadow pass runs with block owners (ARCTIC_OPT_RASTER_OWNER bit 1) the owners merge their bins into the map
                                           this path has drawn into, and blocks with an empty bin have no owner (measured: no faster than the atomic rasteriser) */
 #define ARCTIC_OPT_MARKERS          13 /* 1 = roctx ranges around each pass, named like the reference's Tracy zones (process-wide; libroctx64 is loaded on demand) */
+/* ARCTIC_OPT_ENV_LIGHTING: image-based ambient light from the environment map of arctic_create_hdri (the reference's roadmap item
+ * "IBL with skybox"; forward.hlsl:13,195-206 has the hooks, ps_main :233 still ends in a flat ambient).
+ *   0 (default)  ambient * base_color, as the reference renders.
+ *   1            that term, and only that term, becomes
+ *                  color = Lo (1 - shadow) + ambient [ (1 - F)(1 - metal) base E(n) / pi + P(R, rough) (F0 A + B) ]
+ *                  F  = F0 + (max(1 - rough, F0) - F0)(1 - max(n.wo, 0))^5   (Schlick with roughness, per channel)
+ *                  F0 = lerp(0.04, base, metal),  R = 2 (n.wo) n - wo,  (A, B) = LUT(max(n.wo, 0), rough)
+ *                n, wo, base, metal, rough: exactly what the light loop takes (get_normal, metal-rough .g / .b, sRGB decode, every
+ *                ARCTIC_OPT_SAMPLER mode); ambient (the scene's slider, app.cpp:470) scales the whole bracket.  Shadowed pixels take it too.
+ *                Without an environment map mode 1 renders bit for bit as mode 0, so a host may set it unconditionally.
+ * Direction <-> texel: the skybox's mapping (skybox.hlsl:74-85) with its fp32 constants 0.1591f / 0.3183f and its v flip, so that a mirror
+ * reflects exactly the sky the skybox draws (the unused forward.hlsl:197 variant lacks the flip).  Texel (i, j) of a W x H map:
+ * u = (i + 0.5) / W, v = (j + 0.5) / H, phi = (u - 0.5) / 0.1591f, theta = (0.5 - v) / 0.3183f, direction (cos theta cos phi, sin theta,
+ * cos theta sin phi), solid angle max(cos theta, 0) dphi dtheta with dphi = 1 / (0.1591f W), dtheta = 1 / (0.3183f H).  Because the
+ * constants are rounded the weights sum to 4 pi (1 + 3.5e-4), not 4 pi, and the azimuths overlap by as much at the seam (phi = +-pi, the -x
+ * direction), which is weighed twice: kept, so a constant map c gives E = pi c (1 + 3.5e-4) on average and pi c (1 + 1.1e-3) towards -x.
+ * Tables, built on the device in stream order on the handle's stream when both the map and mode 1 exist -- by arctic_create_hdri or by
+ * arctic_set_option, whichever comes second; never by a frame.  A new map rebuilds them; arctic_resize keeps them:
+ *   E(n)        9 real SH coefficients per channel (basis order 1, y, z, x, xy, yz, 3z^2 - 1, xz, x^2 - y^2 with the usual normalisations),
+ *               projected over the full-resolution map, Ramamoorthi-Hanrahan's A0 = pi, A1 = 2 pi / 3, A2 = pi / 4 folded in.  Summed in
+ *               binary64 in a fixed order (no float atomics): the same map gives the same bits on every handle.
+ *   P(R, r)     6 levels, r_k = k / 5.  Level 0 is the map (bilinear, WRAP, as the skybox samples it); level k >= 1 is an RGBA32F equirect of
+ *               max(8, min(W, 512) >> (k - 1)) x max(4, min(H, 256) >> (k - 1)) texels (~2.7 MB for the stack): Karis' split-sum prefilter
+ *               (N = V = R), 512 Hammersley samples, GGX with alpha = r_k^2, weight n.l, taken from the 2x2 box-filtered mip chain of the map
+ *               (level m + 1 = max(1, w / 2) x max(1, h / 2), texel = mean of (2i + a, 2j + b), clamped to the last row / column) at
+ *               lod = max(0, log2(Omega_s / Omega_p) / 2 + 1), Omega_s = 4 / (512 D), Omega_p = 4 pi / (W H), linear between mip levels.
+ *               GGX frame around n: tangent = normalize(cross(up, n)), up = z unless |n.z| >= 0.999, then x.  At run time P is trilinear:
+ *               levels floor(5 r) and floor(5 r) + 1 (the last one clamped), each bilinear with WRAP.
+ *   (A, B)      64 x 64 RG fp32 at cell centres (n.v, r), 1024 Hammersley samples, Smith-Schlick with k = r^2 / 2 (the IBL form; the direct
+ *               lights keep (r + 1)^2 / 8, on purpose); looked up bilinearly, clamped.
+ * ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply in mode 1 (a shading call then returns ARCTIC_E_STATE), and
+ * ARCTIC_OPT_TILE_ORDER is ignored (the geometric order).  INTEGRATION.md section 5e: what a DX12 host sets. */
+#define ARCTIC_OPT_ENV_LIGHTING     25
 int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value);
+
+/* The tables of ARCTIC_OPT_ENV_LIGHTING (no counterpart in the reference): sh27 = the 27 coefficients of E(n), coefficient k of channel c
+   at 3 k + c (A_l folded in); lut = 64 x 64 x 2 floats, row = roughness cell; texels = specular level `level` (0 = the map), w x h x 4
+   floats; dims = {w, h of that level, levels (6), LUT side (64)}.  Any pointer may be NULL.  ARCTIC_E_STATE when no tables exist.
+   Synchronises. */
+int arctic_read_env_lighting(ArcticRenderer *r, float *sh27, float *lut, uint32_t level, float *texels, uint32_t *dims);
 
 /* The trace of the latest shading pass under ARCTIC_OPT_TILE_TRACE: 4 x uint64 per tile, tile-row major over the handle's tile
    grid (tiles_x x tiles_y, returned too): the 100 MHz reference clock (s_memrealtime) when the tile's wave started, when it ended,
