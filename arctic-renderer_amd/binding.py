@@ -32,6 +32,8 @@ SIGNATURES = {
     "arctic_create_material": (_i32, [_vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _u32, _u32]),
     "arctic_create_mesh": (_i32, [_vp, _vp, _u64, _vp, _u64, _u64]),
     "arctic_update_lights": (_i32, [_vp, _vp, _u64]),
+    "arctic_update_spot_lights": (_i32, [_vp, _vp, _u64]),
+    "arctic_spot_light_constants": (_i32, [_vp, _u64, _vp]),
     "arctic_create_hdri": (_i32, [_vp, _vp, _u32, _u32]),
     "arctic_render_frame": (_i32, [_vp, _scene, _settings, _vp]),
     "arctic_render_frame_device": (_i32, [_vp, _scene, _settings, _vp]),

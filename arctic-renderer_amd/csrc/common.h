@@ -264,13 +264,19 @@ struct ShadeParams {
     const float4 *lights;        // 2 float4 per light, as uploaded
     // ---- block D, byte 192
     float sun_dir[3];
-    uint32_t pad_d0;
+    uint32_t n_spots;            // k_spotlit* only: spot lights at ShadeParams::spots (the slot was padding: the block keeps its size and place)
     float sun_color[3];
     uint32_t pad_d1;
     // ---- the rest: read at the point of use
     const float *srgb_lut;       // 256 floats, sRGB8 -> linear
-    unsigned long long *stats;   // STATS kernels only: [0] point-light evaluations, [1] lit pixels, [2] evaluations with n.wi > 0,
-                                 // [3] (tile, light) pairs with n.wi <= 0 in every lit lane, [4] tiles with a lit pixel
+    // stats: STATS kernels only: [0] point-light evaluations, [1] lit pixels, [2] evaluations with n.wi > 0,
+    //        [3] (tile, light) pairs with n.wi <= 0 in every lit lane, [4] tiles with a lit pixel
+    // spots: k_spotlit* only (they keep no statistics): n_spots lights, SPOT_F4 float4 each (SpotDev).  One slot for both, as tile_order /
+    //        env_tables below share one: a field of its own would grow the block and reschedule instructions of every k_material*.
+    union {
+        unsigned long long *stats;
+        const float4 *spots;
+    };
     unsigned long long *trace;   // ARCTIC_OPT_TILE_TRACE: 4 x u64 per tile (shade.hip: trace_end), or null
     // tile_order: the pass's dispatch order (k_tile_order: strips of 4 tiles, ty << 16 | strip column), n_jobs entries; null: the geometric order.
     // env_tables: image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map), the tables env_light.hip built from the map.  One slot for
@@ -301,7 +307,15 @@ struct ShadeLaunch {
     uint32_t stats;      // 1: the counting variant (ShadeParams::stats)
     uint32_t tiles_per_wave;   // 0: DEFAULT_TILES_PER_WAVE (ARCTIC_OPT_TILES_PER_WAVE)
     uint32_t env;        // 1: k_envlit / k_envlit_vis (image-based ambient, ShadeParams::env_tables; geometric tile order, no statistics)
+    uint32_t spot;       // 1: k_spotlit / k_spotlit_vis with ENV = env (ShadeParams::spots, n_spots; geometric tile order, no statistics)
 };
+
+// ---- spot lights (arctic_update_spot_lights; semantics in include/arctic_hip.h next to the call) ---------------------------------------
+// On the device: 3 float4 per light, {p.xyz, scale} {s.xyz, offset} {rgb, ir2}, s the unit direction, the cone attenuation
+// sat(cd scale + offset)^2 of cd = cos(angle to the axis), the range window sat(1 - (d2 ir2)^2).  Derived by the host (host_math.cpp).
+constexpr uint32_t SPOT_F4 = 3;
+struct SpotDev { float p[3], scale, s[3], offset, c[3], ir2; };
+static_assert(sizeof(SpotDev) == SPOT_F4 * 16, "SpotDev: 3 float4");
 
 // ---- image-based ambient (ARCTIC_OPT_ENV_LIGHTING, env_light.hip) ------------------------------------------------------
 // The semantics are written once, in include/arctic_hip.h next to the option.  What the shading kernels read, built on the device

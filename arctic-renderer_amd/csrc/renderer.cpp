@@ -214,6 +214,9 @@ struct ArcticRenderer {
     EnvTables env_host = {};         // the device struct's pointers and sizes (its sh[] is written by the device)
     bool env_active() const { return env_lighting == 1 && env_built; }
     uint32_t n_lights = 0;
+    // arctic_update_spot_lights: SPOT_F4 float4 per light (common.h SpotDev); a non-empty list sends every tile to k_spotlit*
+    DevBuf d_spots;
+    uint32_t n_spots = 0;
     // frame targets
     DevBuf d_vis_set[3], d_p0, d_p1, d_p2, d_p3, d_p4, d_rgba8, d_ldr, d_hdr, d_counter;
     bool have_gbuffer = false, have_output = false, have_vis = false;   // have_vis: d_vis holds the visibility of the current G-buffer
@@ -690,6 +693,8 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
     }
     if (r->env_active() && (r->count_evals || r->tile_trace))
         return r->fail(ARCTIC_E_STATE, "shade: ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply to the image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map)");
+    if (r->n_spots && (r->count_evals || r->tile_trace))
+        return r->fail(ARCTIC_E_STATE, "shade: ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply with spot lights (arctic_update_spot_lights)");
     std::memset(&sp, 0, sizeof sp);
     sp.g = r->gbuffer();
     const ArcticRenderer::GeoSet &G = r->geo[r->fwd()];
@@ -728,8 +733,10 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
         HIPCHECK(r, hipMemsetAsync(r->d_tile_trace.p, 0, bytes, r->stream));
         sp.trace = r->d_tile_trace.as<unsigned long long>();
     }
+    if (r->n_spots) { sp.spots = r->d_spots.as<float4>(); sp.n_spots = r->n_spots; }   // (the statistics' slot: k_spotlit* keep none)
     // (the order was built for groups of order_group tiles per wave: a pass that shades another number per wave takes the geometric order)
     if (r->env_active()) sp.env_tables = r->d_env_tables.as<EnvTables>();   // (the geometric order: the tables take the order's slot)
+    else if (r->n_spots) {}                                                  // (k_spotlit*: the geometric order)
     else if (!from_vis && r->have_order && r->tile_order && (r->tiles_per_wave == 0 || r->tiles_per_wave == r->order_group)) {
         sp.tile_order = r->d_tile_order.as<uint32_t>(); sp.n_jobs = r->order_slots; sp.tiles_per_wave = r->order_group;
     }
@@ -761,6 +768,7 @@ hipError_t shade_once(ArcticRenderer *r, const ShadeParams &sp, bool from_vis, b
     L.stats = stats ? 1u : 0u;
     L.tiles_per_wave = r->tiles_per_wave;
     L.env = r->env_active() ? 1u : 0u;
+    L.spot = sp.n_spots ? 1u : 0u;
     return launch_shade(sp, L);
 }
 
@@ -820,7 +828,7 @@ bool valid_scene(const ArcticScene *sc) { return sc && (sc->n_objects == 0 || sc
 // =================================================================================================
 extern "C" {
 
-int arctic_version(void) { return 100; }
+int arctic_version(void) { return 200; }
 
 ArcticRenderer *arctic_create(const ArcticCreateInfo *info, char *err, uint64_t err_len) {
     auto say = [&](const char *m) { if (err && err_len) { std::snprintf(err, (size_t)err_len, "%s", m); } };
@@ -919,7 +927,7 @@ void arctic_destroy(ArcticRenderer *r) {
     if (r->own_stream) { (void)hipStreamSynchronize(r->own_stream); (void)hipStreamDestroy(r->own_stream); }
     for (Mesh &m : r->meshes) { if (m.d_vertices) (void)hipFree(m.d_vertices); if (m.d_indices) (void)hipFree(m.d_indices); }
     for (void *p : r->tex_allocs) (void)hipFree(p);
-    DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4,
+    DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_spots, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4,
                       &r->d_rgba8, &r->d_ldr, &r->d_hdr, &r->d_counter, &r->d_shadow_blocks_set[0], &r->d_shadow_blocks_set[1], &r->d_shadow_bounds_set[0], &r->d_shadow_bounds_set[1], &r->d_staging, &r->d_layout, &r->geo[0].d_xverts, &r->geo[1].d_xverts, &r->geo[2].d_xverts,
                       &r->geo[2].d_recs, &r->geo[2].d_rrecs, &r->geo[2].d_clip_list, &r->geo[2].d_rec_of, &r->geo[2].d_items, &r->tables[2].d,
                       &r->geo[3].d_xverts, &r->geo[3].d_recs, &r->geo[3].d_rrecs, &r->geo[3].d_clip_list, &r->geo[3].d_rec_of, &r->geo[3].d_items, &r->geo[3].d_left, &r->geo[3].d_bin_count, &r->geo[3].d_bin_slots, &r->tables[3].d,
@@ -1087,6 +1095,61 @@ int arctic_update_lights(ArcticRenderer *r, const ArcticPointLight *lights, uint
         HIPCHECK(r, hipMemcpy(r->d_light_pairs.p, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice));
     }
     r->n_lights = k;
+    return ARCTIC_OK;
+}
+
+// arctic_update_spot_lights' validation and derivation (include/arctic_hip.h): binary64, each constant rounded once
+int arctic_spot_light_constants(const ArcticSpotLight *lights, uint64_t n, float *out) {
+    if (n && (!lights || !out)) return ARCTIC_E_INVALID;
+    const float PI_F = (float)M_PI;   // "pi": the fp32 value nearest pi (3.14159274)
+    for (uint64_t i = 0; i < n; ++i) {
+        const ArcticSpotLight &l = lights[i];
+        const float *f = l.position;   // 12 floats, no padding
+        for (int k = 0; k < 12; ++k) if (!std::isfinite(f[k])) return ARCTIC_E_INVALID;
+        const double dx = l.direction[0], dy = l.direction[1], dz = l.direction[2];
+        if (dx == 0.0 && dy == 0.0 && dz == 0.0) return ARCTIC_E_INVALID;
+        if (!(l.inner_cone_angle >= 0.0f && l.inner_cone_angle <= l.outer_cone_angle && l.outer_cone_angle > 0.0f && l.outer_cone_angle <= PI_F &&
+              l.range >= 0.0f)) return ARCTIC_E_INVALID;
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const ArcticSpotLight &l = lights[i];
+        const double dx = l.direction[0], dy = l.direction[1], dz = l.direction[2];
+        const double len = std::sqrt(dx * dx + dy * dy + dz * dz);
+        double scale = 0.0, offset = 1.0;
+        if (l.outer_cone_angle != PI_F) {
+            const double co = std::cos((double)l.outer_cone_angle), ci = std::cos((double)l.inner_cone_angle);
+            scale = 1.0 / std::max(1e-3, ci - co);
+            offset = -co * scale;
+        }
+        const double range = l.range;
+        const double ir2 = range > 0.0 ? 1.0 / (range * range) : 0.0;
+        float *o = out + 12 * i;
+        o[0] = l.position[0]; o[1] = l.position[1]; o[2] = l.position[2]; o[3] = (float)scale;
+        o[4] = (float)(dx / len); o[5] = (float)(dy / len); o[6] = (float)(dz / len); o[7] = (float)offset;
+        o[8] = l.color[0]; o[9] = l.color[1]; o[10] = l.color[2]; o[11] = (float)ir2;
+    }
+    return ARCTIC_OK;
+}
+
+int arctic_update_spot_lights(ArcticRenderer *r, const ArcticSpotLight *lights, uint64_t n) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (n && !lights) return r->fail(ARCTIC_E_INVALID, "update_spot_lights: null");
+    std::vector<float> dev((size_t)std::min<uint64_t>(n, r->max_lights) * 12);
+    // (every light given is checked, also those beyond the cap; on failure the handle's list stays as it was)
+    float one[12];
+    for (uint64_t i = 0; i < n; ++i)
+        if (arctic_spot_light_constants(lights + i, 1, one) != ARCTIC_OK)
+            return r->fail(ARCTIC_E_INVALID, "update_spot_lights: light %llu: a NaN or inf field, a zero direction, inner > outer, outer outside (0, pi] or range < 0", (unsigned long long)i);
+    const uint32_t k = (uint32_t)std::min<uint64_t>(n, r->max_lights);
+    int rc = select_device(r);
+    if (rc) return rc;
+    if (k) {
+        (void)arctic_spot_light_constants(lights, k, dev.data());
+        HIPCHECK(r, hipStreamSynchronize(r->stream));   // (a pass in flight may still read the list it replaces)
+        HIPCHECK(r, r->d_spots.ensure((size_t)k * sizeof(SpotDev)));
+        HIPCHECK(r, hipMemcpy(r->d_spots.p, dev.data(), (size_t)k * sizeof(SpotDev), hipMemcpyHostToDevice));
+    }
+    r->n_spots = k;
     return ARCTIC_OK;
 }
 

@@ -888,7 +888,35 @@ __device__ __forceinline__ f3 get_normal(float nr, float ng, float nb, const flo
     const float r = snorm_of_bytes(nr), g = -snorm_of_bytes(ng), b = snorm_of_bytes(nb);   // (1 - g) * 2 - 1 = -(2 g - 1); nr, ng, nb on the 0..255 scale
     return normalize(mk(fm(ge.y, b, fm(gd.z, g, gc.w * r)), fm(ge.z, b, fm(gd.w, g, gd.x * r)), fm(ge.w, b, fm(ge.x, g, gd.y * r))));
 }
-template <int LOOP, bool STATS>
+// SPOT (k_spotlit*): behind the point lights (either loop), the spot lights join the scalar sums through spot_sums.
+// ---- spot lights (arctic_update_spot_lights; semantics in include/arctic_hip.h): one scalar loop, 3 float4 per light through the
+// scalar cache, {p.xyz, scale} {s.xyz, offset} {rgb, ir2} (common.h SpotDev).  The light's colour is scaled by f = att * window and then
+// goes through exactly the point light's arithmetic (light_scalars<true>, the same three multiply-adds per sum): for an omnidirectional
+// light without a range f is exactly 1 (scale 0, offset 1, ir2 0), so it adds the bits a point light at the same place adds.
+// Culling: a light whose n.d <= 0 or f == 0 in every lit lane of the wave is skipped (its term is exactly zero there).
+__device__ __forceinline__ void spot_sums(SP sp, const LoopPix &px, float A[3], float B[3], float C[3]) {
+    const uint32_t n_spots = sp.n_spots;
+    typedef const f4v __attribute__((address_space(4))) *const_f4;   // wave-uniform: scalar loads (see the point loop)
+    const const_f4 L = (const_f4)sp.spots;
+    const bool cull = sp.culling != 0;
+    for (uint32_t i = 0; i < n_spots; ++i) {
+        const f4v a = L[SPOT_F4 * i], b = L[SPOT_F4 * i + 1], c = L[SPOT_F4 * i + 2];
+        const f3 dl = mk(a.x, a.y, a.z) - px.world;
+        const float ndl = dot(px.n, dl);
+        const float d2 = dot(dl, dl), inv = rsq(d2);
+        const float cd = -dot(mk(b.x, b.y, b.z), dl) * inv;
+        const float att = sat(fm(cd, a.w, b.w)), q = d2 * c.w;
+        const float f = (att * att) * sat(1.0f - q * q);
+        if (cull && __ballot(ndl > 0.0f && f > 0.0f) == 0ull) continue;   // wave-uniform
+        const float cr = c.x * f, cg = c.y * f, cb = c.z * f;
+        float s1, s2, s3;
+        light_scalars<true>(px, dl, ndl, s1, s2, s3);
+        A[0] = __builtin_fmaf(cr, s1, A[0]); A[1] = __builtin_fmaf(cg, s1, A[1]); A[2] = __builtin_fmaf(cb, s1, A[2]);
+        B[0] = __builtin_fmaf(cr, s2, B[0]); B[1] = __builtin_fmaf(cg, s2, B[1]); B[2] = __builtin_fmaf(cb, s2, B[2]);
+        C[0] = __builtin_fmaf(cr, s3, C[0]); C[1] = __builtin_fmaf(cg, s3, C[1]); C[2] = __builtin_fmaf(cb, s3, C[2]);
+    }
+}
+template <int LOOP, bool STATS, bool SPOT = false>
 __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float ng, float nb, float rough, float metal, f3 base,
                                            const float4 &gc, const float4 &gd, const float4 &ge) {
     const f3 n = get_normal(nr, ng, nb, gc, gd, ge);
@@ -927,6 +955,7 @@ __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float
             S.b[0] = __builtin_fmaf(lc.x, s2, S.b[0]); S.b[1] = __builtin_fmaf(lc.y, s2, S.b[1]); S.b[2] = __builtin_fmaf(lc.z, s2, S.b[2]);
             S.c[0] = __builtin_fmaf(lc.x, s3, S.c[0]); S.c[1] = __builtin_fmaf(lc.y, s3, S.c[1]); S.c[2] = __builtin_fmaf(lc.z, s3, S.c[2]);
         }
+        if (SPOT) spot_sums(sp, px, S.a, S.b, S.c);
         Lo = resolve_sums(tp, S.a, S.b, S.c);
     } else {
         Sums2 S;
@@ -978,6 +1007,7 @@ __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float
                 Cs[k] = __builtin_fmaf(sun.color[k], s3, S.c[k].x + S.c[k].y);
             }
         }
+        if (SPOT) spot_sums(sp, px, A, Bs, Cs);
         Lo = resolve_sums(tp, A, Bs, Cs);
     }
     if (STATS) {
@@ -1165,7 +1195,8 @@ __device__ __forceinline__ bool shade_tile_fast(SP sp, KernArgs args, const Args
 // materials with images of unequal sizes, the 25-tap shadow test, the debug / timing options --------------------------------
 // ENV (k_envlit*): every covered pixel, shadowed or not, loads its second 48 bytes, normal, metalness and roughness and takes the
 // image-based ambient term instead of ambient * base; the light loop is still for lit pixels only.
-template <int LOOP, bool STATS, bool LDS_SHADOW, bool ENV = false, class Second>
+// SPOT (k_spotlit*): the light loop takes the spot lights too (lit_radiance<SPOT>).
+template <int LOOP, bool STATS, bool LDS_SHADOW, bool ENV = false, bool SPOT = false, class Second>
 __device__ __forceinline__ void shade_tile(SP sp, const float *lut, float *shadow_tile, uint32_t ty, uint32_t tx,
                                            uint32_t lane, const TileHead &cur, Second second) {
     const uint32_t x = tx * 8 + (lane & 7);
@@ -1277,7 +1308,7 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, float *shado
             color = env_ambient(sp.env_tables, n, wo, base, metal, rough) * sp.ambient;
         }
         if (!ENV || live) {
-            const f3 Lo = lit_radiance<LOOP, STATS>(sp, lane, nr, ng, nb, rough, metal, base, gc, gd, ge);
+            const f3 Lo = lit_radiance<LOOP, STATS, SPOT>(sp, lane, nr, ng, nb, rough, metal, base, gc, gd, ge);
             color = mk(__builtin_fmaf(Lo.x, lit, color.x), __builtin_fmaf(Lo.y, lit, color.y), __builtin_fmaf(Lo.z, lit, color.z));
         }
     }
@@ -1418,20 +1449,20 @@ __global__ __launch_bounds__(64 * ARCTIC_WG_WAVES) __attribute__((amdgpu_waves_p
     }
 }
 
-// ---- the image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map) over a resident G-buffer: k_material's walk, every tile through
-// shade_tile<ENV> (the fast tile's early exit for shadowed pixels does not hold here), the geometric order, no statistics, no trace.
-// (A copy of k_material's walk, not a function both kernels share: inlined through one more level, the walk comes out of the compiler
-// with a few instructions of every k_material* rescheduled -- and the default kernels' instructions are kept as they were.)
-template <int LOOP>
-__global__ __launch_bounds__(64 * ARCTIC_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_envlit(const ShadeParams sp_by_value) {
-    __shared__ float lut[256];
+// ---- the general-tile walk over a resident G-buffer, for the opt-in kernels k_envlit and k_spotlit: k_material's walk, every tile through
+// shade_tile<ENV, SPOT> (the fast tile's early exit for shadowed pixels does not hold under ENV, and the fast tile has no spot lights),
+// the geometric order, no statistics, no trace.  (A copy of k_material's walk, not a function k_material shares: inlined through one more
+// level, the walk comes out of the compiler with a few instructions of every k_material* rescheduled -- and the default kernels'
+// instructions are kept as they were.)
+template <int LOOP, bool ENV, bool SPOT>
+__device__ __forceinline__ void walk_general(float *lut) {
     KernArgs args = kernel_args();
     const BlockId blk = block_id<ARCTIC_WG_WAVES>();
     const float *srgb_lut;
     const unsigned long long *vis_unused;
     OrderArgs O;
     ArgsA A = args_a_first(args, srgb_lut, vis_unused, O);
-    O.order = nullptr;   // (the slot holds the environment tables: ShadeParams::env_tables)
+    O.order = nullptr;   // (the geometric order; under ENV the slot holds the environment tables: ShadeParams::env_tables)
     uint32_t tx, ty, k = 0;
     if (!next_tile(A, O, blk, k, tx, ty)) return;
     TileHead cur;
@@ -1450,13 +1481,25 @@ __global__ __launch_bounds__(64 * ARCTIC_WG_WAVES) __attribute__((amdgpu_waves_p
         const auto second = [&](const float4 *pc, const float4 *pd, const float4 *pe, float4 &gc, float4 &gd, float4 &ge) {
             gc = gload_f4(pc + tile * 64, lane * 16u); gd = gload_f4(pd + tile * 64, lane * 16u); ge = gload_f4(pe + tile * 64, lane * 16u);
         };
-        shade_tile<LOOP, false, false, true>(sp, lut, nullptr, ty, tx, lane, cur, second);
+        shade_tile<LOOP, false, false, ENV, SPOT>(sp, lut, nullptr, ty, tx, lane, cur, second);
         if (++k >= A.T) break;
         asm volatile("" : "+s"(args));
         A = args_a(args);
         if (!next_tile(A, O, blk, k, tx, ty)) break;
         cur = load_head(A.ga, A.gb, (size_t)ty * A.tiles_x + tx, wave_lane());
     }
+}
+// the image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map)
+template <int LOOP>
+__global__ __launch_bounds__(64 * ARCTIC_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_envlit(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    walk_general<LOOP, true, false>(lut);
+}
+// spot lights (arctic_update_spot_lights, a non-empty list); ENV: with the image-based ambient as well
+template <int LOOP, bool ENV>
+__global__ __launch_bounds__(64 * ARCTIC_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_spotlit(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    walk_general<LOOP, ENV, true>(lut);
 }
 
 // ---- the same without a G-buffer (whole frames): the tile walk straight from the visibility plane ----------------------
@@ -1607,18 +1650,17 @@ __global__ __launch_bounds__(64 * VIS_WG_WAVES) __attribute__((amdgpu_waves_per_
     }
 }
 
-// ---- the image-based ambient over whole frames, straight from the visibility plane: k_material_vis's walk as k_envlit is k_material's
-// (a copy for the same reason)
-template <int LOOP>
-__global__ __launch_bounds__(64 * VIS_WG_WAVES) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_envlit_vis(const ShadeParams sp_by_value) {
-    __shared__ float lut[256];
+// ---- the general-tile walk over whole frames, straight from the visibility plane (k_envlit_vis, k_spotlit_vis): k_material_vis's walk as
+// walk_general is k_material's (a copy for the same reason)
+template <int LOOP, bool ENV, bool SPOT>
+__device__ __forceinline__ void walk_general_vis(float *lut) {
     KernArgs args = kernel_args();
     const BlockId blk = block_id<VIS_WG_WAVES>();
     const float *srgb_lut;
     const unsigned long long *vis_plane;
     OrderArgs O;
     ArgsA A = args_a_first(args, srgb_lut, vis_plane, O);
-    O.order = nullptr;   // (the slot holds the environment tables)
+    O.order = nullptr;   // (the geometric order; under ENV the slot holds the environment tables)
     uint32_t tx, ty, k = 0;
     unsigned long long key = ~0ull;
     if (!next_tile(A, O, blk, k, tx, ty)) return;
@@ -1723,13 +1765,23 @@ __global__ __launch_bounds__(64 * VIS_WG_WAVES) __attribute__((amdgpu_waves_per_
             ge = make_float4(interpolate_attr(B, A0, A1, A2, 7), interpolate_attr(B, A0, A1, A2, 8), interpolate_attr(B, A0, A1, A2, 9), interpolate_attr(B, A0, A1, A2, 10));
         }
     };
-    shade_tile<LOOP, false, false, true>(sp, lut, nullptr, ty, tx, lane, cur, second);
+    shade_tile<LOOP, false, false, ENV, SPOT>(sp, lut, nullptr, ty, tx, lane, cur, second);
     if (++k >= A.T) break;
     asm volatile("" : "+s"(args));
     A = args_a(args);
     if (!next_tile(A, O, blk, k, tx, ty)) break;
     key = args->vis[((size_t)ty * A.tiles_x + tx) * 64 + wave_lane()];
     }
+}
+template <int LOOP>
+__global__ __launch_bounds__(64 * VIS_WG_WAVES) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_envlit_vis(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    walk_general_vis<LOOP, true, false>(lut);
+}
+template <int LOOP, bool ENV>
+__global__ __launch_bounds__(64 * VIS_WG_WAVES) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_spotlit_vis(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    walk_general_vis<LOOP, ENV, true>(lut);
 }
 
 // ---- shadow bounds: the conservative min/max table calculate_lit tests first -------------------------------------------
@@ -1773,6 +1825,18 @@ __global__ __launch_bounds__(256) void k_post_process(const float4 *__restrict__
 
 template <int LOOP, bool STATS, bool LDS_SHADOW>
 hipError_t launch_variant(const ShadeParams &sp, const ShadeLaunch &L, dim3 grid) {
+    if (L.spot) {   // (geometric order, no statistics, no LDS variant: launch_shade)
+        if (L.from_vis) {
+            if (VIS_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;
+            if (L.env) k_spotlit_vis<LOOP, true><<<grid, 64 * VIS_WG_WAVES, 0, L.stream>>>(sp);
+            else k_spotlit_vis<LOOP, false><<<grid, 64 * VIS_WG_WAVES, 0, L.stream>>>(sp);
+        } else {
+            if (ARCTIC_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;
+            if (L.env) k_spotlit<LOOP, true><<<grid, 64 * ARCTIC_WG_WAVES, 0, L.stream>>>(sp);
+            else k_spotlit<LOOP, false><<<grid, 64 * ARCTIC_WG_WAVES, 0, L.stream>>>(sp);
+        }
+        return hipGetLastError();
+    }
     if (L.env) {   // (geometric order, no statistics, no LDS variant: launch_shade)
         if (L.from_vis) {
             if (VIS_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;
@@ -1801,7 +1865,8 @@ hipError_t launch_shade(const ShadeParams &sp_in, const ShadeLaunch &L) {
     const uint32_t n_tiles = sp_in.tiles_x * sp_in.tiles_y;
     if (n_tiles == 0) return hipSuccess;
     ShadeParams sp = sp_in;
-    // (the image-based ambient: tiles in the geometric order -- ARCTIC_OPT_TILE_ORDER is a hint --, the order's slot holds the tables)
+    // (the image-based ambient and the spot lights: tiles in the geometric order -- ARCTIC_OPT_TILE_ORDER is a hint --, the order's slot
+    // holds the environment tables)
     // two tiles per wave pay once a frame is several rounds of the chip's wave slots; below ~3 Mpx one tile per wave is faster
     // (tools/experiments/small_frames.py: 1080p pass 0.0638 -> 0.0610 ms, whole frame 0.098 -> 0.084 ms with T = 1; 2688 x 1512: 0.101 against
     // 0.104 ms and 0.142 against 0.153 with T = 2)
@@ -1809,9 +1874,9 @@ hipError_t launch_shade(const ShadeParams &sp_in, const ShadeLaunch &L) {
     const uint32_t bpr = (sp.tiles_x + 3) / 4, groups = (sp.tiles_y + 7) / 8;
     sp.group_stride = (groups + sp.tiles_per_wave - 1) / sp.tiles_per_wave;
     dim3 grid(8 * bpr, sp.group_stride);   // a block shades tiles_per_wave groups of 8 tile rows, group_stride groups apart
-    if (sp.tile_order && !L.env)           // ... or tiles_per_wave consecutive slots of the prepass's dispatch order (n_jobs slots, common.h order_slot: a block = one XCD's list)
+    if (sp.tile_order && !L.env && !L.spot) // ... or tiles_per_wave consecutive slots of the prepass's dispatch order (n_jobs slots, common.h order_slot: a block = one XCD's list)
         grid = dim3((sp.n_jobs + sp.tiles_per_wave - 1) / sp.tiles_per_wave, 1);
-    if (L.env) return L.loop == 2 ? launch_variant<2, false, false>(sp, L, grid) : launch_variant<1, false, false>(sp, L, grid);
+    if (L.env || L.spot) return L.loop == 2 ? launch_variant<2, false, false>(sp, L, grid) : launch_variant<1, false, false>(sp, L, grid);
     if (sp.debug & 16)   // A/B only: the 25-tap path staged through LDS (a separate instantiation: it costs the default kernels nothing)
         return L.loop == 2 ? launch_variant<2, false, true>(sp, L, grid) : launch_variant<1, false, true>(sp, L, grid);
     if (L.loop == 2) return L.stats ? launch_variant<2, true, false>(sp, L, grid) : launch_variant<2, false, false>(sp, L, grid);

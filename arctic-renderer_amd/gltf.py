@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .scene import OBJECT_DTYPE, VERTEX_DTYPE
+from .scene import LIGHT_DTYPE, OBJECT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "host", "libarctic_gltf.so")
@@ -38,6 +38,9 @@ def lib():
         L.arctic_gltf_mesh.argtypes = [vp, u64, C.POINTER(vp), u64p, C.POINTER(vp), u64p, u64p]
         L.arctic_gltf_objects.restype, L.arctic_gltf_objects.argtypes = vp, [vp]
         L.arctic_gltf_upload.restype, L.arctic_gltf_upload.argtypes = C.c_int, [vp, vp]
+        for f in ("arctic_gltf_spot_lights", "arctic_gltf_point_lights"):
+            getattr(L, f).restype, getattr(L, f).argtypes = vp, [vp, u64p]
+        L.arctic_gltf_directional_light_count.restype, L.arctic_gltf_directional_light_count.argtypes = u64, [vp]
         L.arctic_png_decode.restype = vp
         L.arctic_png_decode.argtypes = [C.c_char_p, u64, u32p, u32p, C.c_char_p, u64]
         L.arctic_png_free.restype, L.arctic_png_free.argtypes = None, [vp]
@@ -47,10 +50,15 @@ def lib():
 
 class GltfScene:
     """materials: list of (diffuse, normal, metal_rough) uint8 (h, w, 4); meshes: list of (vertices, indices, material);
-    objects: OBJECT_DTYPE array -- the same three things scenes.SyntheticScene carries."""
+    objects: OBJECT_DTYPE array -- the same three things scenes.SyntheticScene carries.  The file's KHR_lights_punctual lights:
+    spot_lights (SPOT_LIGHT_DTYPE, for Renderer.update_spot_lights), point_lights (LIGHT_DTYPE, for update_lights),
+    directional_lights (a count; include/arctic_gltf.h).  upload() uploads no lights."""
 
-    def __init__(self, materials, meshes, objects):
+    def __init__(self, materials, meshes, objects, spot_lights=None, point_lights=None, directional_lights=0):
         self.materials, self.meshes, self.objects = materials, meshes, objects
+        self.spot_lights = np.zeros(0, SPOT_LIGHT_DTYPE) if spot_lights is None else spot_lights
+        self.point_lights = np.zeros(0, LIGHT_DTYPE) if point_lights is None else point_lights
+        self.directional_lights = directional_lights
 
     def upload(self, renderer):
         for d, n, m in self.materials:
@@ -85,7 +93,12 @@ def load(path):
         n_obj = L.arctic_gltf_object_count(h)
         objects = (np.frombuffer(C.string_at(L.arctic_gltf_objects(h), n_obj * OBJECT_DTYPE.itemsize), dtype=OBJECT_DTYPE).copy()
                    if n_obj else np.zeros(0, OBJECT_DTYPE))
-        return GltfScene(materials, meshes, objects)
+        def lights(fn, dtype):
+            n = C.c_uint64()
+            p = fn(h, C.byref(n))
+            return np.frombuffer(C.string_at(p, n.value * dtype.itemsize), dtype=dtype).copy() if n.value else np.zeros(0, dtype)
+        return GltfScene(materials, meshes, objects, lights(L.arctic_gltf_spot_lights, SPOT_LIGHT_DTYPE),
+                         lights(L.arctic_gltf_point_lights, LIGHT_DTYPE), int(L.arctic_gltf_directional_light_count(h)))
     finally:
         L.arctic_gltf_free(h)
 

@@ -493,6 +493,10 @@ struct ArcticGltf {
     std::vector<Material> materials;
     std::vector<Mesh> meshes;
     std::vector<ArcticObject> objects;
+    // KHR_lights_punctual, one entry per (node, light) in the order the node walk meets them
+    std::vector<ArcticSpotLight> spot_lights;     // spot lights, and point lights with a range (outer = pi)
+    std::vector<ArcticPointLight> point_lights;   // point lights without a range
+    uint64_t directional_lights = 0;              // counted, not exported: the sun stays the host's
 };
 
 namespace {
@@ -755,6 +759,69 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
         count_of_mesh.push_back(prims.size());
     }
 
+    // KHR_lights_punctual (no counterpart in the reference, whose load_scene reads no lights): the root's light definitions, checked
+    // against the extension's limits here; the nodes that carry them are met in the walk below
+    struct LightDef { int type = -1; double color[3] = {1.0, 1.0, 1.0}, intensity = 1.0, range = 0.0, inner = 0.0, outer = M_PI / 4.0; };   // type 0 directional, 1 point, 2 spot, -1 unknown (skipped)
+    std::vector<LightDef> light_defs;
+    if (const Json *ext = doc.find("extensions"))
+        if (const Json *khr = ext->find("KHR_lights_punctual")) {
+            const Json &ls = khr->at("lights");
+            if (ls.kind != Json::Array) fail("glTF: KHR_lights_punctual.lights must be an array");
+            for (size_t i = 0; i < ls.size(); ++i) {
+                const Json &l = ls[i];
+                LightDef d;
+                const std::string &type = l.at("type").as_str();
+                d.type = type == "directional" ? 0 : type == "point" ? 1 : type == "spot" ? 2 : -1;
+                if (const Json *c = l.find("color")) {
+                    if (c->size() != 3) fail("glTF: light color must have 3 numbers");
+                    for (int k = 0; k < 3; ++k) d.color[k] = (*c)[k].as_num();
+                }
+                if (const Json *v = l.find("intensity")) d.intensity = v->as_num();
+                if (const Json *v = l.find("range")) { d.range = v->as_num(); if (!(d.range > 0.0) || !std::isfinite(d.range)) fail("glTF: light range must be > 0"); }
+                for (int k = 0; k < 3; ++k) if (!(d.color[k] >= 0.0) || !std::isfinite(d.color[k])) fail("glTF: light color must be finite and >= 0");
+                if (!(d.intensity >= 0.0) || !std::isfinite(d.intensity)) fail("glTF: light intensity must be finite and >= 0");
+                if (d.type == 2) {
+                    if (const Json *sp = l.find("spot")) {
+                        if (const Json *v = sp->find("innerConeAngle")) d.inner = v->as_num();
+                        if (const Json *v = sp->find("outerConeAngle")) d.outer = v->as_num();
+                    }
+                    // the extension: 0 <= inner < outer <= pi / 2 (inner == outer, a hard cone, is accepted: exporters write it for a blend of 0)
+                    if (!(d.inner >= 0.0 && d.inner <= d.outer && d.outer > 0.0 && d.outer <= M_PI / 2.0))
+                        fail("glTF: spot light cone angles outside 0 <= innerConeAngle <= outerConeAngle <= pi/2, outerConeAngle > 0");
+                }
+                light_defs.push_back(d);
+            }
+        }
+    auto emit_light = [&](size_t li, const M4 &m) {
+        if (li >= light_defs.size()) fail("glTF: light index out of range");
+        const LightDef &d = light_defs[li];
+        if (d.type < 0) return;                                   // an unknown type: skipped
+        if (d.type == 0) { ++g->directional_lights; return; }
+        // position = (M (0, 0, 0, 1)).xyz, direction = (M (0, 0, -1, 0)).xyz, M the node's accumulated matrix as the loader gives a mesh
+        const float pos[3] = {m.m[12], m.m[13], m.m[14]};
+        float dir[3] = {-m.m[8], -m.m[9], -m.m[10]};
+        float col[3];
+        for (int k = 0; k < 3; ++k) col[k] = (float)(d.color[k] * d.intensity);
+        if (d.type == 1 && d.range == 0.0) {
+            ArcticPointLight p;
+            std::memset(&p, 0, sizeof p);
+            std::memcpy(p.position, pos, 12); std::memcpy(p.color, col, 12);
+            g->point_lights.push_back(p);
+            return;
+        }
+        const bool finite_dir = std::isfinite(dir[0]) && std::isfinite(dir[1]) && std::isfinite(dir[2]) && (dir[0] != 0.0f || dir[1] != 0.0f || dir[2] != 0.0f);
+        if (d.type == 1 && !finite_dir) { dir[0] = 0.0f; dir[1] = 0.0f; dir[2] = -1.0f; }   // (an omnidirectional light: its direction plays no part)
+        if (!finite_dir && d.type == 2) fail("glTF: a spot light's node has a degenerate transform (no direction)");
+        for (int k = 0; k < 3; ++k) if (!std::isfinite(pos[k]) || !std::isfinite(col[k])) fail("glTF: a light's position or colour is not finite");
+        ArcticSpotLight l;
+        std::memcpy(l.position, pos, 12); std::memcpy(l.direction, dir, 12); std::memcpy(l.color, col, 12);
+        l.range = (float)d.range;
+        if (d.type == 1) { l.inner_cone_angle = 0.0f; l.outer_cone_angle = (float)M_PI; }   // a point light with a range: omnidirectional spot
+        else { l.inner_cone_angle = (float)d.inner; l.outer_cone_angle = (float)d.outer; }
+        if (d.range > 0.0 && !(l.range > 0.0f && std::isfinite(l.range))) fail("glTF: light range outside fp32's range");
+        g->spot_lights.push_back(l);
+    };
+
     // objects (app.cpp:354-382): depth-first from the root with an explicit stack (children are visited last to first),
     // every node matrix transposed by assimp_to_mat4 (app.cpp:540-564) and accumulated as parent * child
     const size_t n_nodes = doc.has("nodes") ? doc.at("nodes").size() : 0;
@@ -784,6 +851,8 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
             trs = mul(it.parent, transpose(node_matrix(n)));
             if (n.has("children")) for (size_t i = 0; i < n.at("children").size(); ++i) children.push_back(Loader::index_of(n.at("children")[i], "node index"));
             if (n.has("mesh")) mesh = (long)Loader::index_of(n.at("mesh"), "mesh index");
+            if (const Json *ext = n.find("extensions"))
+                if (const Json *khr = ext->find("KHR_lights_punctual")) emit_light(Loader::index_of(khr->at("light"), "light index"), trs);
         }
         for (size_t c : children) stack.push_back({(long)c, trs});
         if (mesh >= 0) {
@@ -834,6 +903,15 @@ int arctic_gltf_mesh(const ArcticGltf *g, uint64_t i, const ArcticVertex **verti
     return ARCTIC_OK;
 }
 const ArcticObject *arctic_gltf_objects(const ArcticGltf *g) { return g && !g->objects.empty() ? g->objects.data() : nullptr; }
+const ArcticSpotLight *arctic_gltf_spot_lights(const ArcticGltf *g, uint64_t *n) {
+    if (n) *n = g ? g->spot_lights.size() : 0;
+    return g && !g->spot_lights.empty() ? g->spot_lights.data() : nullptr;
+}
+const ArcticPointLight *arctic_gltf_point_lights(const ArcticGltf *g, uint64_t *n) {
+    if (n) *n = g ? g->point_lights.size() : 0;
+    return g && !g->point_lights.empty() ? g->point_lights.data() : nullptr;
+}
+uint64_t arctic_gltf_directional_light_count(const ArcticGltf *g) { return g ? g->directional_lights : 0; }
 
 int arctic_gltf_upload(const ArcticGltf *g, ArcticRenderer *r) {
     if (!g || !r) return ARCTIC_E_INVALID;

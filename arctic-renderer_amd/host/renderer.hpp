@@ -28,6 +28,7 @@ using Vertex = ArcticVertex;               // position, normal, tangent, bitange
 using Object = ArcticObject;               // trs (column-major mat4), mesh_idx
 struct DirectionalLight { float position[3]; float rotation[2]; float color[3]; };
 using PointLight = ArcticPointLight;       // position, padding0, color, padding1
+using SpotLight = ArcticSpotLight;         // position, range, direction, inner_cone_angle, color, outer_cone_angle (no counterpart in the reference)
 struct Scene {
     Camera camera;
     float ambient;
@@ -89,6 +90,8 @@ class Renderer {
     }
     [[nodiscard]] bool create_hdri(float *data, uint32_t width, uint32_t height) { return ok(arctic_create_hdri(m_handle, data, width, height)); }
     void update_lights(std::span<PointLight> point_lights) { (void)ok(arctic_update_lights(m_handle, point_lights.data(), point_lights.size())); }
+    // spot lights (KHR_lights_punctual's cone and range; include/arctic_hip.h): false = an invalid light, the previous list stays
+    [[nodiscard]] bool update_spot_lights(std::span<SpotLight> spot_lights) { return ok(arctic_update_spot_lights(m_handle, spot_lights.data(), spot_lights.size())); }
     [[nodiscard]] bool flush() { return ok(arctic_flush(m_handle)); }
     // image-based ambient from the HDRI (ARCTIC_OPT_ENV_LIGHTING; no counterpart in the reference, whose ps_main keeps a flat ambient):
     // false = the reference's ambient * base_color.  Safe to set before or after create_hdri, and without a map at all.

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (LIGHT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -141,6 +141,12 @@ class Renderer:
     def update_lights(self, lights):
         l = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
         self._check(self.L.arctic_update_lights(self.h, _ptr(l) if len(l) else None, len(l)))
+
+    def update_spot_lights(self, lights):
+        """replace the handle's spot lights (SPOT_LIGHT_DTYPE records; an empty array clears them).  An invalid light raises
+        ArcticError (ARCTIC_E_INVALID) and leaves the previous list in place."""
+        l = np.ascontiguousarray(lights, dtype=SPOT_LIGHT_DTYPE)
+        self._check(self.L.arctic_update_spot_lights(self.h, _ptr(l) if len(l) else None, len(l)))
 
     def render_frame(self, desc, settings, out=None):
         """returns the (rows, width, 4) uint8 frame (this handle's row shard)."""

@@ -16,7 +16,10 @@ VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("tangent
 OBJECT_DTYPE = np.dtype([("trs", "<f4", 16), ("mesh_idx", "<u8")])
 # scene.hpp:88-94 PointLight (32 B)
 LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("padding0", "<u4"), ("color", "<f4", 3), ("padding1", "<u4")])
-assert VERTEX_DTYPE.itemsize == 56 and OBJECT_DTYPE.itemsize == 72 and LIGHT_DTYPE.itemsize == 32
+# ArcticSpotLight (include/arctic_hip.h): 48 bytes, no padding
+SPOT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("range", "<f4"), ("direction", "<f4", 3), ("inner_cone_angle", "<f4"),
+                             ("color", "<f4", 3), ("outer_cone_angle", "<f4")])
+assert VERTEX_DTYPE.itemsize == 56 and OBJECT_DTYPE.itemsize == 72 and LIGHT_DTYPE.itemsize == 32 and SPOT_LIGHT_DTYPE.itemsize == 48
 
 TM_REINHARD, TM_EXPOSURE, TM_ACES = 0, 1, 2
 

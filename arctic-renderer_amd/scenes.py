@@ -16,7 +16,7 @@ import colorsys
 
 import numpy as np
 
-from .scene import (LIGHT_DTYPE, VERTEX_DTYPE, SceneDesc, make_lights, make_objects, rotation_y, scaling,
+from .scene import (LIGHT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, SceneDesc, make_lights, make_objects, rotation_y, scaling,
                     translation, TM_ACES, TM_REINHARD)
 
 SEED = 0x41524354
@@ -257,6 +257,28 @@ def random_lights(rng, n, lo, hi, intensity=10.0):
     pos = (np.asarray(lo, np.float32) + rng.random((n, 3), dtype=np.float32) * (np.asarray(hi, np.float32) - np.asarray(lo, np.float32)))
     col = np.array([colorsys.hsv_to_rgb(h, 1.0, 1.0) for h in rng.random(n)], np.float32).reshape(n, 3) * intensity
     return make_lights(pos, col)
+
+
+def spot_lights(n, seed=0, lo=(-14.5, 0.5, -6.5), hi=(14.5, 11.5, 6.5), intensity=40.0):
+    """n spot lights (SPOT_LIGHT_DTYPE) aimed at the geometry of the atrium configs (3-5): each hangs in the hall's upper half and points
+    at a random spot of the floor, the walls or the balconies; soft cones (outer 15-45 degrees, inner 0-90 % of it) and a range that
+    reaches its target with room to spare.  A random stream of its own (SEED + 101 + seed): the configs' streams are untouched."""
+    rng = np.random.default_rng(SEED + 101 + seed)
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    out = np.zeros(n, SPOT_LIGHT_DTYPE)
+    for i in range(n):
+        p = lo + rng.random(3) * (hi - lo)
+        p[1] = 0.5 * (lo[1] + hi[1]) + rng.random() * 0.5 * (hi[1] - lo[1])
+        t = lo + rng.random(3) * (hi - lo)
+        t[1] = lo[1] + rng.random() * 0.5 * (hi[1] - lo[1])
+        outer = np.radians(15.0 + 30.0 * rng.random())
+        out[i]["position"] = p
+        out[i]["direction"] = t - p
+        out[i]["outer_cone_angle"] = outer
+        out[i]["inner_cone_angle"] = outer * 0.9 * rng.random()
+        out[i]["range"] = 1.5 * np.linalg.norm(t - p) + 2.0
+        out[i]["color"] = np.array(colorsys.hsv_to_rgb(rng.random(), 0.5, 1.0)) * intensity
+    return out
 
 
 def config1(scale=1.0, tex=None):

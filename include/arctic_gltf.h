@@ -40,6 +40,19 @@ int arctic_gltf_material_image(const ArcticGltf *g, uint64_t i, int k, const uin
 int arctic_gltf_mesh(const ArcticGltf *g, uint64_t i, const ArcticVertex **vertices, uint64_t *n_vertices,
                      const uint32_t **indices, uint64_t *n_indices, uint64_t *material);
 const ArcticObject *arctic_gltf_objects(const ArcticGltf *g);
+/* KHR_lights_punctual (not read by the reference's load_scene): the root's extensions.KHR_lights_punctual.lights, placed by every node whose
+ * extensions.KHR_lights_punctual.light names one, with the node's accumulated matrix M exactly as a mesh on that node gets it
+ * (assimp_to_mat4's transpose included): position = (M (0,0,0,1)).xyz, direction = (M (0,0,-1,0)).xyz.  One entry per (node, light), in
+ * the node walk's order.  Defaults of the extension: color (1,1,1), intensity 1, innerConeAngle 0, outerConeAngle pi/4, no range.
+ * colour = color * intensity (binary64, rounded once).  A spot light -> ArcticSpotLight; a point light without a range -> ArcticPointLight;
+ * a point light with a range -> an omnidirectional ArcticSpotLight (outer = pi, inner = 0), so its range is kept.  Directional lights are
+ * only counted (the sun stays the host's); unknown types are skipped.  A light index out of range, a range <= 0, cone angles outside
+ * 0 <= inner <= outer <= pi/2 (outer > 0; the extension asks inner < outer, equality is accepted), a negative or non-finite colour or
+ * intensity, or a non-numeric field refuse the file.  The arrays live as long as g; n receives the count (NULL result when it is 0).
+ * arctic_gltf_upload uploads no lights: hand them to arctic_update_spot_lights / arctic_update_lights. */
+const ArcticSpotLight *arctic_gltf_spot_lights(const ArcticGltf *g, uint64_t *n);
+const ArcticPointLight *arctic_gltf_point_lights(const ArcticGltf *g, uint64_t *n);
+uint64_t arctic_gltf_directional_light_count(const ArcticGltf *g);
 
 /* convenience: create_material / create_mesh for everything in the file, in order (what load_scene does). */
 int arctic_gltf_upload(const ArcticGltf *g, ArcticRenderer *r);

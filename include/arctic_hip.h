@@ -80,6 +80,17 @@ typedef struct ArcticPointLight {
     uint32_t padding1;
 } ArcticPointLight;
 
+/* A spot light (no counterpart in the reference: its roadmap's "Spotlights"), 48 B, no padding.  The cone and the range follow glTF's
+ * KHR_lights_punctual; see arctic_update_spot_lights for the exact semantics. */
+typedef struct ArcticSpotLight {
+    float position[3];
+    float range;             /* > 0: the KHR window below; 0 = unlimited (KHR: range undefined) */
+    float direction[3];      /* where the light points (glTF: the node's -Z); any finite non-zero length, normalised by the library */
+    float inner_cone_angle;  /* radians, 0 <= inner <= outer */
+    float color[3];          /* linear colour * intensity: the radiance at distance 1 on the axis (glTF: color * intensity in candela) */
+    float outer_cone_angle;  /* radians, 0 < outer <= pi; pi = no cone at all (an omnidirectional light with a range) */
+} ArcticSpotLight;
+
 /* scene.hpp:96-103 Scene; std::vector members flattened to pointer + count.
  * point_lights here is ignored by render_frame exactly as in the reference
  * (renderer.cpp:285-407 uses the buffer last written by update_lights). */
@@ -172,6 +183,32 @@ int arctic_create_mesh(ArcticRenderer *r,
 /* replaces void Renderer::update_lights(span<PointLight>) (renderer.hpp:120,
  * renderer.cpp:585-603): clamps to max_lights like the reference clamps to 16. */
 int arctic_update_lights(ArcticRenderer *r, const ArcticPointLight *lights, uint64_t n);
+
+/* Spot lights (no counterpart in the reference).  Works like arctic_update_lights: replaces the handle's spot list, clamps the count to
+ * max_lights; n = 0 clears the list.  A light with a NaN or inf field, a zero direction, inner > outer, outer outside (0, pi] or range < 0
+ * makes the call return ARCTIC_E_INVALID, and the list the handle had stays as it was.
+ * Per light the host derives, in binary64, each rounded once to fp32:
+ *   s      = normalize(direction)
+ *   scale  = 1 / max(1e-3, cos(inner) - cos(outer)),  offset = -cos(outer) * scale     (KHR_lights_punctual's cone formula)
+ *            outer == pi: scale = 0, offset = 1 (the cone factor is exactly 1)
+ *   ir2    = range > 0 ? 1 / range^2 : 0
+ * A lit pixel at `world`, d = position - world, d2 = |d|^2, inv = rsq(d2), wi = d * inv, takes
+ *   cd       = -dot(s, d) * inv
+ *   att      = sat(cd * scale + offset)^2          (KHR cone attenuation)
+ *   window   = sat(1 - (d2 * ir2)^2)               (KHR range window 1 - (dist / range)^4; with ir2 = 0 it is exactly 1)
+ *   radiance = color * att * window / d2
+ * into the same calculate_outgoing_radiance as a point light's (forward.hlsl:224-231), and the result into Lo.  Lo keeps the factor
+ * (1 - shadow) of the sun's shadow map: a spot light does not light what the sun's shadow covers, exactly like the point lights (and fully
+ * shadowed pixels skip every light).  The ambient term is unchanged, and so is the environment term of ARCTIC_OPT_ENV_LIGHTING = 1, which
+ * combines with spot lights.  An omnidirectional light (outer = pi, range = 0) adds the same bits a point light with its position and
+ * colour adds in the scalar light loop (ARCTIC_OPT_LIGHT_PATH = 1).  An empty list renders exactly as before.
+ * With spot lights every tile goes through the general tile code (kernels k_spotlit / k_spotlit_vis), ARCTIC_OPT_TILE_ORDER is ignored,
+ * and ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE make a shading call return ARCTIC_E_STATE. */
+int arctic_update_spot_lights(ArcticRenderer *r, const ArcticSpotLight *lights, uint64_t n);
+
+/* The per-light constants arctic_update_spot_lights stores on the device, 12 floats per light: position.xyz, scale, s.xyz, offset,
+ * color.rgb, ir2 (semantics above).  ARCTIC_E_INVALID (nothing written) when any light is invalid.  Host only, no handle. */
+int arctic_spot_light_constants(const ArcticSpotLight *lights, uint64_t n, float *out);
 
 /* replaces bool Renderer::create_hdri(float*,w,h) (renderer.hpp:118, renderer.cpp:555-583): RGBA32F equirect
  * environment map.  Pixels without geometry then take it along their view ray (skybox.hlsl:61-90);
