@@ -33,37 +33,6 @@
 #include "edges.h"
 #include "shadow_coords.h"
 
-#ifndef ARCTIC_WG_WAVES
-#define ARCTIC_WG_WAVES 1       // waves per workgroup of k_material, the pass over a G-buffer: 1 (a tile per workgroup; round 5) or 4 (a strip of 4 tiles per workgroup: rounds 1-4).
-#endif                          // A workgroup's slot is held until its LAST wave ends; with tiles of unequal length (shadowed 3 us, lit 13) one-wave workgroups keep
-                                // 5.1 instead of 4.5 waves resident per SIMD.  Round 4 measured them faster with few lights and 1.8 % slower at 64 (with its dispatch order on);
-                                // on round 5's build, order off: 64 / 16 / 0 lights 0.1874 / 0.1273 / 0.0951 -> 0.1857 / 0.1224 / 0.0936 ms (profiles/r5_l_ab_one_wave_workgroups.txt).
-                                // k_material_vis keeps 4 (VIS_WG_WAVES): whole frames are 9 % slower with one.
-#ifndef ARCTIC_VIS_WG_WAVES
-#define ARCTIC_VIS_WG_WAVES 4
-#endif
-constexpr int VIS_WG_WAVES = ARCTIC_VIS_WG_WAVES;   // (2 and 1 measured: whole frames 0.2765 -> 0.2955 / 0.2964 ms, profiles/r5_l_ab_one_wave_workgroups.txt)
-#ifndef ARCTIC_LUT_SHARED
-#define ARCTIC_LUT_SHARED 0     // A/B switch: 1 = each wave of a workgroup loads a quarter of the sRGB table (256 B instead of 1 KiB per wave) and a barrier stands behind the stores
-#endif
-#ifndef ARCTIC_PCF_CANDIDATES
-#define ARCTIC_PCF_CANDIDATES 0   // A/B switch: 1 = the 25 vertical lerps of k_material's PCF taps evaluate three candidate cells and select the RESULT instead of selecting
-                                  // the operands of every lerp (same bits; measured -0.4 % at 0 / 16 lights, nothing at 64: profiles/r5_b_ab_inplace_sums_and_pcf_candidates.txt --
-                                  // and 74 VGPRs once the kernel also carries the D3D-style sampler's taps, a wave per SIMD: off)
-#endif
-#ifndef ARCTIC_PCF_ROW_CANDIDATES
-#define ARCTIC_PCF_ROW_CANDIDATES 0   // A/B switch: 1 = the horizontal lerps of the 25 PCF taps as candidates too (register pressure: see shadow_window)
-#endif
-#ifndef ARCTIC_PIN_SECOND_WAVE
-#define ARCTIC_PIN_SECOND_WAVE 1   // A/B switch: see shade_tile_fast
-#endif
-#ifndef ARCTIC_TILED_FETCH
-#define ARCTIC_TILED_FETCH 1   // A/B switch (instruction census only): 0 = no code for tiled material images (such materials then render wrongly)
-#endif
-#ifndef ARCTIC_EDGE_IN_FAST
-#define ARCTIC_EDGE_IN_FAST 1   // A/B switch (build_tmp variants only): 0 = a tile on a shadow edge goes to the general tile, as in round 3
-#endif
-
 namespace arctic {
 
 namespace {
@@ -292,7 +261,7 @@ __device__ __forceinline__ void fetch_taps_packed(const TexS &d, float u, float 
     if (q8) { asm volatile(""); x = snap256(x); y = snap256(y); }   // (a real branch: one for both axes, nothing for the default sampler)
     axis_split(x, x0, fx);
     axis_split(y, y0, fy);
-    if (ARCTIC_TILED_FETCH && d.tile_row_bytes) {   // (wave-uniform) 4 x 4-texel tiles, common.h TexDesc::tile_row_bytes: four 8-byte loads, a texel of the footprint may sit in the next tile
+    if (d.tile_row_bytes) {   // (wave-uniform) 4 x 4-texel tiles, common.h TexDesc::tile_row_bytes: four 8-byte loads, a texel of the footprint may sit in the next tile
         asm volatile("");
         const uint32_t X = (uint32_t)(x0 + 1), Y = (uint32_t)(y0 + 1), rx = X & 3u, ry = Y & 3u;
         const uint32_t o00 = ((__umul24(Y >> 2, d.tile_row_bytes >> 7) + (X >> 2)) << 7) + ((ry * 4u + rx) << 3);
@@ -378,7 +347,7 @@ __device__ __noinline__ float shadow_generic(const float *__restrict__ map, uint
 // Q8: the D3D-style sampler for the taps (ARCTIC_OPT_SAMPLER bit 2; the oracle's SAMPLER_Q8_SHADOW): every scaled tap coordinate snapped to 1/256
 // texel before it is split into texel and weight.  The window is then the one of the SNAPPED coordinates (a coordinate may snap across an
 // integer); its span is checked like the plain one's, and whatever does not fit takes shadow_generic with the same sampler.
-template <bool CANDIDATES = false, bool Q8 = false>
+template <bool Q8 = false>
 __device__ __forceinline__ float shadow_window(const float *__restrict__ map, uint32_t S, float px, float py, float pz, bool *tapped = nullptr /* statistics: this lane ran the 25 compares */) {
 #pragma clang fp contract(off)
     const float Sf = (float)S;
@@ -398,11 +367,10 @@ __device__ __forceinline__ float shadow_window(const float *__restrict__ map, ui
     if (pz > hi) return 1.0f;
     if (!(pz > lo)) return 0.0f;
     if (tapped) *tapped = true;
-    // The 25 compares, one tap column at a time.  A tap's texels are whichever CELL of the window it falls into, per lane -- selecting the two
-    // operands of every lerp costs four v_cndmask (4.3 issue cycles each) per lerp.  Round 5: each lerp is evaluated in all three candidate
-    // cells instead -- fmaf(t, b - a, a) with the differences b - a formed once per row (the oracle's own subtraction), three fused
-    // multiply-adds at 2.9 cycles -- and the RESULT of the lane's cell is selected (two v_cndmask): the same operations on the same operands
-    // for the cell that counts, so the same bits; 17 issue cycles per lerp instead of 23.
+    // The 25 compares, one tap column at a time.  A tap's texels are whichever CELL of the window it falls into, per lane: the two operands
+    // of every lerp are selected (four v_cndmask per lerp).  (Round 5 measured evaluating each lerp in all three candidate cells and selecting
+    // the RESULT: the same bits, 0.4 % at 0 / 16 lights, nothing at 64, and 74 VGPRs once the D3D-style taps came along.  Measured, removed:
+    // profiles/r5_b_ab_inplace_sums_and_pcf_candidates.txt)
     float fy[5];
     bool r0[5], r1[5];   // row of tap j relative to the window: 0 / 1 / 2
 #pragma unroll
@@ -417,32 +385,14 @@ __device__ __forceinline__ float shadow_window(const float *__restrict__ map, ui
         const float x = scaled(px + (float)(i - 2) * 0.0001f), xf = floorf(x), fx = x - xf;
         const bool c0 = xf == xa, c1 = xf == xa + 1.0f;
         const auto pick = [](bool p0, bool p1, float v0, float v1, float v2) { return p0 ? v0 : (p1 ? v1 : v2); };
-        float h0, h1, h2, h3;
-        if (CANDIDATES && ARCTIC_PCF_ROW_CANDIDATES) {
-            // (the horizontal lerps the same way keep the window's twelve differences alive through all five columns: 76 VGPRs, a wave per SIMD lost)
-            h0 = pick(c0, c1, __builtin_fmaf(fx, w0.y - w0.x, w0.x), __builtin_fmaf(fx, w0.z - w0.y, w0.y), __builtin_fmaf(fx, w0.w - w0.z, w0.z));
-            h1 = pick(c0, c1, __builtin_fmaf(fx, w1.y - w1.x, w1.x), __builtin_fmaf(fx, w1.z - w1.y, w1.y), __builtin_fmaf(fx, w1.w - w1.z, w1.z));
-            h2 = pick(c0, c1, __builtin_fmaf(fx, w2.y - w2.x, w2.x), __builtin_fmaf(fx, w2.z - w2.y, w2.y), __builtin_fmaf(fx, w2.w - w2.z, w2.z));
-            h3 = pick(c0, c1, __builtin_fmaf(fx, w3.y - w3.x, w3.x), __builtin_fmaf(fx, w3.z - w3.y, w3.y), __builtin_fmaf(fx, w3.w - w3.z, w3.z));
-        } else {
-            h0 = lerp_exact(pick(c0, c1, w0.x, w0.y, w0.z), pick(c0, c1, w0.y, w0.z, w0.w), fx);
-            h1 = lerp_exact(pick(c0, c1, w1.x, w1.y, w1.z), pick(c0, c1, w1.y, w1.z, w1.w), fx);
-            h2 = lerp_exact(pick(c0, c1, w2.x, w2.y, w2.z), pick(c0, c1, w2.y, w2.z, w2.w), fx);
-            h3 = lerp_exact(pick(c0, c1, w3.x, w3.y, w3.z), pick(c0, c1, w3.y, w3.z, w3.w), fx);
-        }
-        if (CANDIDATES) {
-            const float e0 = h1 - h0, e1 = h2 - h1, e2 = h3 - h2;   // b - a down the column, for the three cells
+        const float h0 = lerp_exact(pick(c0, c1, w0.x, w0.y, w0.z), pick(c0, c1, w0.y, w0.z, w0.w), fx);
+        const float h1 = lerp_exact(pick(c0, c1, w1.x, w1.y, w1.z), pick(c0, c1, w1.y, w1.z, w1.w), fx);
+        const float h2 = lerp_exact(pick(c0, c1, w2.x, w2.y, w2.z), pick(c0, c1, w2.y, w2.z, w2.w), fx);
+        const float h3 = lerp_exact(pick(c0, c1, w3.x, w3.y, w3.z), pick(c0, c1, w3.y, w3.z, w3.w), fx);
 #pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                const float closest = pick(r0[j], r1[j], __builtin_fmaf(fy[j], e0, h0), __builtin_fmaf(fy[j], e1, h1), __builtin_fmaf(fy[j], e2, h2));
-                shadow += pz > closest ? 1.0f : 0.0f;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                const float closest = lerp_exact(pick(r0[j], r1[j], h0, h1, h2), pick(r0[j], r1[j], h1, h2, h3), fy[j]);
-                shadow += pz > closest ? 1.0f : 0.0f;
-            }
+        for (int j = 0; j < 5; ++j) {
+            const float closest = lerp_exact(pick(r0[j], r1[j], h0, h1, h2), pick(r0[j], r1[j], h1, h2, h3), fy[j]);
+            shadow += pz > closest ? 1.0f : 0.0f;
         }
     }
     return shadow / 25.0f;
@@ -450,58 +400,6 @@ __device__ __forceinline__ float shadow_window(const float *__restrict__ map, ui
 
 // (Round 4 also tried the lane's 4x4 window in LDS -- texel k of lane l at word 64 k + l, a tap = two ds_read2st64_b32 at a computed address, ~290 vector
 // instructions + 58 LDS operations instead of ~425 + 0 -- and measured it slower: profiles/r4_d_ab_window_in_lds.txt; code in commit ec02d97.)
-
-// ---- the LDS variant of the 25-tap path (north_star: "stages ... shadow-map tiles in LDS"; ARCTIC_OPT_DEBUG bit 4 selects the
-// kernels instantiated with it) ----------------------------------------------------------------------------------------------
-// For a tile on a shadow edge: the bounding box of the undecided lanes' footprints (4x4 windows) is staged ONCE per wave in LDS
-// (<= 32 x 32 texels; the lanes of an 8x8 screen tile land within a few texels of each other) and every tap reads its four texels
-// from there with computed addresses -- no selects: per tap 2 ds_read2_b32 + 3 exact lerps + compare, in the oracle's order.
-// Against the register window (4 x 16-byte loads per lane, ~185 v_cndmask to pick texels): measured in DESIGN.md section 4.2.
-constexpr int SHADOW_TILE = 32;   // texels per side of a wave's LDS tile
-__device__ __forceinline__ int wave_min_i32(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
-    return v;
-}
-// returns true when the wave's undecided lanes were handled here (lit updated); false: the caller takes the register path
-__device__ __forceinline__ bool shadow_lds_tile(const ShadowArgs &sa, float *tile /* this wave's SHADOW_TILE^2 floats */, uint32_t lane, bool undecided,
-                                                const float px, const float py, const float pz, float &lit) {
-#pragma clang fp contract(off)
-    const uint32_t S = sa.S;
-    const float Sf = (float)S;
-    const int bx = floor_to_int((px + -0.0002f) * Sf - 0.5f), by = floor_to_int((py + -0.0002f) * Sf - 0.5f);
-    const int ex = floor_to_int((px + 0.0002f) * Sf - 0.5f) + 1, ey = floor_to_int((py + 0.0002f) * Sf - 0.5f) + 1;   // last texel a tap reads
-    const bool ok = bx >= 0 && by >= 0 && ex < (int)S && ey < (int)S;   // no tap wraps (the window test of shadow_window, without its width limit)
-    if (__ballot(undecided && !ok) != 0ull) return false;
-    const int BIG = 1 << 30;
-    const int x0 = wave_min_i32(undecided ? bx : BIG), y0 = wave_min_i32(undecided ? by : BIG);
-    const int x1 = -wave_min_i32(undecided ? -ex : BIG), y1 = -wave_min_i32(undecided ? -ey : BIG);
-    const int W = x1 - x0 + 1, H = y1 - y0 + 1;
-    if (W > SHADOW_TILE || H > SHADOW_TILE) return false;
-    // stage rows y0 .. y1, texels x0 .. x1: two rows per step (lanes 0-31 / 32-63), coalesced along x
-    for (int r = (int)(lane >> 5); r < H; r += 2) {
-        const int c = (int)(lane & 31);
-        if (c < W) tile[r * SHADOW_TILE + c] = sa.map[(size_t)(y0 + r) * S + (size_t)(x0 + c)];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // same wave: LDS operations complete in order
-    if (undecided) {
-        float shadow = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const float x = (px + (float)(i - 2) * 0.0001f) * Sf - 0.5f, xf = floorf(x), fx = x - xf;
-            const int cx = (int)xf - x0;
-#pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                const float y = (py + (float)(j - 2) * 0.0001f) * Sf - 0.5f, yf = floorf(y), fy = y - yf;
-                const float *t0 = tile + ((int)yf - y0) * SHADOW_TILE + cx;
-                const float top = lerp_exact(t0[0], t0[1], fx), bot = lerp_exact(t0[SHADOW_TILE], t0[SHADOW_TILE + 1], fx);
-                shadow += pz > lerp_exact(top, bot, fy) ? 1.0f : 0.0f;
-            }
-        }
-        lit = 1.0f - shadow / 25.0f;
-    }
-    return true;
-}
 
 // 1 - shadow in two steps.  shadow_quick decides from the bounds table where it can (and for every pixel outside the map);
 // returns false for the lanes that need shadow_slow: tiles on a shadow edge, the map's border, maps above 5000^2.
@@ -537,7 +435,7 @@ __device__ __forceinline__ bool shadow_quick(const ShadowArgs &sa, float lsx, fl
 }
 __device__ __forceinline__ float shadow_slow(const ShadowArgs &sa, const ShadowPos &p, bool q8 = false /* wave-uniform */) {
     const uint32_t S = sa.S;
-    if (q8) { asm volatile(""); return 1.0f - (S <= 5000u ? shadow_window<false, true>(sa.map, S, p.px, p.py, p.pz) : shadow_generic(sa.map, S, p.px, p.py, p.pz, true)); }
+    if (q8) { asm volatile(""); return 1.0f - (S <= 5000u ? shadow_window<true>(sa.map, S, p.px, p.py, p.pz) : shadow_generic(sa.map, S, p.px, p.py, p.pz, true)); }
     return 1.0f - (S <= 5000u ? shadow_window(sa.map, S, p.px, p.py, p.pz) : shadow_generic(sa.map, S, p.px, p.py, p.pz));
 }
 
@@ -799,11 +697,7 @@ __device__ __forceinline__ uint32_t rgba8_word_of_exponents(f3 g) {
     asm("v_exp_f32_e64 %0, %6 clamp\n\tv_exp_f32_e64 %1, %7 clamp\n\tv_exp_f32_e64 %2, %8 clamp\n\t"
         "v_fma_f32 %3, %0, %9, 0.5\n\tv_fma_f32 %4, %1, %9, 0.5\n\tv_fma_f32 %5, %2, %9, 0.5"
         : "=&v"(e0), "=&v"(e1), "=&v"(e2), "=&v"(q0), "=&v"(q1), "=&v"(q2) : "v"(g.x), "v"(g.y), "v"(g.z), "s"(255.0f));
-#if ARCTIC_CVT_PK_U8
-    return __builtin_amdgcn_cvt_pk_u8_f32(q2, 2u, __builtin_amdgcn_cvt_pk_u8_f32(q1, 1u, __builtin_amdgcn_cvt_pk_u8_f32(q0, 0u, 0xFF000000u)));
-#else
     return (uint32_t)q0 | ((uint32_t)q1 << 8) | ((uint32_t)q2 << 16) | 0xFF000000u;
-#endif
 }
 
 // first wave of G-buffer loads: what every pixel needs (28 B)
@@ -1092,7 +986,7 @@ __device__ __forceinline__ f3 env_ambient(const EnvTables *T, f3 n, f3 wo, f3 ba
 // that kind (decided wave-wide; the texel loads already issued are then dropped): the caller shades it with shade_tile.
 // `second(pc, pd, pe, gc, gd, ge)` delivers the lit pixels' remaining attributes (world position + tangent frame, packed like the
 // G-buffer planes c, d, e): loaded from the G-buffer, or interpolated on the spot by the visibility-buffer kernel.
-template <int LOOP, bool STATS, bool PCF_CAND, class Second>
+template <int LOOP, bool STATS, class Second>
 __device__ __forceinline__ bool shade_tile_fast(SP sp, KernArgs args, const ArgsA &A, const float *lut, uint32_t ty, uint32_t tx, uint32_t lane, const TileHead &cur, Second second) {
     ArgsB B = args_b(args);   // (the head of the tile is in flight)
     const int32_t row0 = (int32_t)(ty * 8) - (int32_t)B.row0_in_tile;   // the tile's first pixel row in the target (wave-uniform)
@@ -1122,17 +1016,14 @@ __device__ __forceinline__ bool shade_tile_fast(SP sp, KernArgs args, const Args
     if (__ballot(!decided) != 0ull) {   // a tile on a shadow edge (a tenth of the benchmark frame's tiles), or at the map's border
         // Round 4: the 25 taps of the undecided pixels are taken here, with the texel loads above still in flight, instead of handing the
         // tile to the general code, which started over (descriptor, texels, table entry -- three more memory round trips).
-#if !ARCTIC_EDGE_IN_FAST
-        return false;
-#endif
         if (B.sh.S > 5000u) return false;   // (no 4x4 window for such maps: the general tile)
         // the 25-tap code is what would set the kernel's register count: the footprint's texels are given up across it (an empty asm
         // "writes" every component) and asked for again behind it -- cache hits, and such tiles are few
         asm("" : "=v"(pt.r0.x), "=v"(pt.r0.y), "=v"(pt.r0.z), "=v"(pt.r0.w), "=v"(pt.r1.x), "=v"(pt.r1.y), "=v"(pt.r1.z), "=v"(pt.r1.w));
         asm("" : "=v"(pt.w00), "=v"(pt.w10), "=v"(pt.w01), "=v"(pt.w11));
         bool tapped = false;
-        if (q8s) { asm volatile(""); if (!decided) lit = 1.0f - shadow_window<false, true>(B.sh.map, B.sh.S, spos.px, spos.py, spos.pz); }   // (no statistics of this one)
-        else if (!decided) lit = 1.0f - shadow_window<PCF_CAND>(B.sh.map, B.sh.S, spos.px, spos.py, spos.pz, STATS ? &tapped : nullptr);
+        if (q8s) { asm volatile(""); if (!decided) lit = 1.0f - shadow_window<true>(B.sh.map, B.sh.S, spos.px, spos.py, spos.pz); }   // (no statistics of this one)
+        else if (!decided) lit = 1.0f - shadow_window(B.sh.map, B.sh.S, spos.px, spos.py, spos.pz, STATS ? &tapped : nullptr);
         if (STATS) {   // [5] tiles with a pixel the table left undecided, [6] such pixels, [7] tiles that ran the 25 compares, [8] pixels that did
             const unsigned long long und = __ballot(!decided), tap = __ballot(tapped);
             if (wave_lane() == 0) {
@@ -1156,13 +1047,11 @@ __device__ __forceinline__ bool shade_tile_fast(SP sp, KernArgs args, const Args
     if (live) second(C.gc, C.gd, C.ge, gc, gd, ge);   // second wave of loads: lit pixels only (48 B / pixel, whole 128-byte tile rows)
     // ---- C: base colour
     f3 base = mk(filt_srgb<0>(pt, lut), filt_srgb<1>(pt, lut), filt_srgb<2>(pt, lut));
-#if ARCTIC_PIN_SECOND_WAVE
     // Round 5, read off the ISA: the compiler copied components of gc / gd / ge into the register pairs its packed multiplies want RIGHT BEHIND the
     // three loads (s_waitcnt vmcnt(2), (1), (0) + v_mov inside the `live` branch): the wave sat out the whole memory latency there, in front of the
     // twelve table look-ups of the base colour.  The twelve values and a component of the base colour pass through one empty asm statement: whatever
     // the compiler does with the loaded registers, it does behind the base colour.
     asm volatile("" : "+v"(gc.x), "+v"(gc.y), "+v"(gc.z), "+v"(gc.w), "+v"(gd.x), "+v"(gd.y), "+v"(gd.z), "+v"(gd.w), "+v"(ge.x), "+v"(ge.y), "+v"(ge.z), "+v"(ge.w), "+v"(base.x));
-#endif
     // ---- D: the lights.  (The ambient term is formed behind the light loop on either side of the branch: formed in front of it, it
     // would occupy three registers through the loop.)
     EpiArgs E = {C.st, B.out, B.width, B.row0_in_tile, C.ambient};
@@ -1196,8 +1085,8 @@ __device__ __forceinline__ bool shade_tile_fast(SP sp, KernArgs args, const Args
 // ENV (k_envlit*): every covered pixel, shadowed or not, loads its second 48 bytes, normal, metalness and roughness and takes the
 // image-based ambient term instead of ambient * base; the light loop is still for lit pixels only.
 // SPOT (k_spotlit*): the light loop takes the spot lights too (lit_radiance<SPOT>).
-template <int LOOP, bool STATS, bool LDS_SHADOW, bool ENV = false, bool SPOT = false, class Second>
-__device__ __forceinline__ void shade_tile(SP sp, const float *lut, float *shadow_tile, uint32_t ty, uint32_t tx,
+template <int LOOP, bool STATS, bool ENV = false, bool SPOT = false, class Second>
+__device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty, uint32_t tx,
                                            uint32_t lane, const TileHead &cur, Second second) {
     const uint32_t x = tx * 8 + (lane & 7);
     const int32_t y = (int32_t)(ty * 8 + (lane >> 3)) - (int32_t)sp.row0_in_tile;
@@ -1255,8 +1144,7 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, float *shado
         const ShadowArgs sh = shadow_args(sp);
         const bool decided = !covered || shadow_quick(sh, cur.a.z, cur.a.w, cur.b0, cur.b1, spos, lit, q8s);
         if (__ballot(!decided) != 0ull) {   // a tile on a shadow edge (or at the map's border)
-            const bool staged = LDS_SHADOW && !q8s && sh.S <= 5000u && shadow_lds_tile(sh, shadow_tile, lane, !decided, spos.px, spos.py, spos.pz, lit);
-            if (!staged && !decided) lit = shadow_slow(sh, spos, q8s);
+            if (!decided) lit = shadow_slow(sh, spos, q8s);
             // the 25-tap path is what sets the kernel's register count: the texels fetched above are dropped across it and
             // fetched again (cache hits; such tiles are few) instead of being kept alive through it
             fetch_material();
@@ -1364,9 +1252,12 @@ __device__ __forceinline__ void lut_store(float *lut, uint32_t lane, const LutRe
 // dimensional and block b takes the jobs b T ... b T + T - 1 of the list, a job = a strip of 4 horizontally adjacent tiles: the
 // prepass knows which tiles can be lit at all, and deals those evenly over the dispatch, the last stretch excepted.
 // The wave's next tile from job k on: true with (tx, ty) and k = the job taken; false: no more work for this wave.
-// Workgroups of ONE wave (ARCTIC_WG_WAVES == 1): the four tiles of a strip are the blocks b, b + 8, b + 16, b + 24 of a group of 32 -- the
-// same XCD (blocks are dealt round-robin over the 8 XCDs), so what the strip's tiles share still meets in one L2 -- and the strip is
-// block (b >> 5) * 8 + (b & 7) of the 4-wave numbering below.
+// Workgroups of ONE wave (block_id<1>, the passes over a G-buffer): the four tiles of a strip are the blocks b, b + 8, b + 16, b + 24 of a
+// group of 32 -- the same XCD (blocks are dealt round-robin over the 8 XCDs), so what the strip's tiles share still meets in one L2 -- and
+// the strip is block (b >> 5) * 8 + (b & 7) of the 4-wave numbering (block_id<4>, the passes over the visibility plane).  A workgroup's
+// slot is held until its LAST wave ends; with tiles of unequal length (shadowed 3 us, lit 13) one-wave workgroups keep 5.1 instead of 4.5
+// waves resident per SIMD: 64 / 16 / 0 lights 0.1874 / 0.1273 / 0.0951 -> 0.1857 / 0.1224 / 0.0936 ms.  Whole frames are slower with
+// them (0.2765 -> 0.2964 ms; 0.2955 with two waves).  Both measured in profiles/r5_l_ab_one_wave_workgroups.txt.
 struct BlockId { uint32_t x, y, wave; };
 template <int WGW>
 __device__ __forceinline__ BlockId block_id() {
@@ -1393,395 +1284,217 @@ __device__ __forceinline__ bool next_tile(const ArgsA &A, const OrderArgs &O, co
     ty = g * 8 + (b.x & 7u);
     return g < ((A.tiles_y + 7u) >> 3) && ty < A.tiles_y;
 }
-template <int LOOP, bool STATS, bool LDS_SHADOW>
-__global__ __launch_bounds__(64 * ARCTIC_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_material(const ShadeParams sp_by_value) {
+// The walk over a resident G-buffer, the body of every kernel of that pass.  PLAIN (k_material): a tile goes to the fast tile first, the
+// trace and the statistics are there, and the tiles come in the dispatch order when the prepass wrote one.  ENV / SPOT (k_envlit, k_spotlit):
+// every tile goes through shade_tile<ENV, SPOT> (the fast tile's early exit for shadowed pixels does not hold under ENV, and the fast tile
+// has no spot lights), in the geometric order (the order's slot holds the environment tables: ShadeParams::env_tables), with no statistics
+// and no trace.  A macro, not a device function: inlined through one more level, the walk comes out of the compiler with a few instructions
+// of k_material rescheduled.  `lut`: the kernel's sRGB table in LDS.
+#define WALK_GBUFFER(LOOP, STATS, ENV, SPOT)                                                                                                 \
+    constexpr bool PLAIN = !ENV && !SPOT;                                                                                                    \
+    KernArgs args = kernel_args();                                                                                                           \
+    unsigned long long t_entry = PLAIN ? trace_entry() : 0ull;                                                                               \
+    const BlockId blk = block_id<1>();                                                                                                       \
+    const float *srgb_lut;                                                                                                                   \
+    const unsigned long long *vis_unused;                                                                                                    \
+    OrderArgs O;                                                                                                                             \
+    ArgsA A = args_a_first(args, srgb_lut, vis_unused, O);                                                                                   \
+    if (!PLAIN) O.order = nullptr;                                                                                                           \
+    uint32_t tx, ty, k = 0;                                                                                                                  \
+    TileHead cur;                                                                                                                            \
+    if (!next_tile(A, O, blk, k, tx, ty)) return;                                                                                            \
+    {                                                                                                                                        \
+        const uint32_t lane = wave_lane();                                                                                                   \
+        const LutRegs lr = lut_load(srgb_lut, lane);                                       /* an L2 hit: back first ... */                   \
+        cur = load_head(A.ga, A.gb, (size_t)ty * A.tiles_x + tx, lane);                   /* ... while the tile's first bytes travel */      \
+        lut_store(lut, lane, lr);                                                                                                            \
+    }                                                                                                                                        \
+_Pragma("nounroll")                                                                                                                          \
+    for (;;) {                                                                                                                               \
+        asm volatile("" : "+s"(args));   /* see SP */                                                                                        \
+        SP sp = *args;                                                                                                                       \
+        const uint32_t lane = wave_lane();                                                                                                   \
+        const size_t tile = (size_t)ty * A.tiles_x + tx;   /* wave-uniform */                                                                \
+        if (PLAIN) trace_begin(sp, tile, t_entry);                                                                                           \
+        t_entry = 0ull;                                                                                                                      \
+        const auto second = [&](const float4 *pc, const float4 *pd, const float4 *pe, float4 &gc, float4 &gd, float4 &ge) {                  \
+            gc = gload_f4(pc + tile * 64, lane * 16u); gd = gload_f4(pd + tile * 64, lane * 16u); ge = gload_f4(pe + tile * 64, lane * 16u); \
+        };                                                                                                                                   \
+        const bool fast = PLAIN && shade_tile_fast<LOOP, STATS>(sp, args, A, lut, ty, tx, lane, cur, second);                                \
+        if (!fast) shade_tile<LOOP, STATS, ENV, SPOT>(sp, lut, ty, tx, lane, cur, second);                                                   \
+        if (PLAIN) trace_end(sp, A, tile, fast);                                                                                             \
+        if (++k >= A.T) break;                                                                                                               \
+        asm volatile("" : "+s"(args));                                                                                                       \
+        A = args_a(args);                      /* (nothing of the block stays in registers across a tile) */                                 \
+        if (PLAIN) O = order_args(args);                                                                                                     \
+        if (!next_tile(A, O, blk, k, tx, ty)) break;                                                                                         \
+        cur = load_head(A.ga, A.gb, (size_t)ty * A.tiles_x + tx, wave_lane());                                                               \
+    }
+template <int LOOP, bool STATS>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_material(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    __shared__ float shadow_tiles[LDS_SHADOW ? ARCTIC_WG_WAVES : 1][LDS_SHADOW ? SHADOW_TILE * SHADOW_TILE : 1];   // one per wave (the LDS variant of the PCF slow path)
-    KernArgs args = kernel_args();
-    unsigned long long t_entry = trace_entry();
-    const BlockId blk = block_id<ARCTIC_WG_WAVES>();
-    const uint32_t wave = ARCTIC_WG_WAVES == 1 ? 0u : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (of the workgroup: which LDS shadow tile is this wave's)
-    const float *srgb_lut;
-    const unsigned long long *vis_unused;
-    OrderArgs O;
-    ArgsA A = args_a_first(args, srgb_lut, vis_unused, O);
-    uint32_t tx, ty, k = 0;
-    TileHead cur;
-#if ARCTIC_LUT_SHARED && ARCTIC_WG_WAVES == 4
-    {   // a quarter of the table per wave (waves without a tile load theirs too), the barrier behind the head loads' issue
-        const bool has_tile = next_tile(A, O, blk, k, tx, ty);
-        const uint32_t lane = wave_lane();
-        const float q = __uint_as_float(gload_u32(srgb_lut, (blk.wave * 64u + lane) * 4u));
-        if (has_tile) cur = load_head(A.ga, A.gb, (size_t)ty * A.tiles_x + tx, lane);
-        lut[blk.wave * 64u + lane] = q;
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (!has_tile) return;
-    }
-#else
-    if (!next_tile(A, O, blk, k, tx, ty)) return;
-    {
-        const uint32_t lane = wave_lane();
-        const LutRegs lr = lut_load(srgb_lut, lane);                                       // an L2 hit: back first ...
-        cur = load_head(A.ga, A.gb, (size_t)ty * A.tiles_x + tx, lane);                   // ... while the tile's first bytes travel
-        lut_store(lut, lane, lr);
-    }
-#endif
-#pragma nounroll
-    for (;;) {
-        asm volatile("" : "+s"(args));   // see SP
-        SP sp = *args;
-        const uint32_t lane = wave_lane();
-        const size_t tile = (size_t)ty * A.tiles_x + tx;   // wave-uniform
-        trace_begin(sp, tile, t_entry);
-        t_entry = 0ull;
-        const auto second = [&](const float4 *pc, const float4 *pd, const float4 *pe, float4 &gc, float4 &gd, float4 &ge) {
-            gc = gload_f4(pc + tile * 64, lane * 16u); gd = gload_f4(pd + tile * 64, lane * 16u); ge = gload_f4(pe + tile * 64, lane * 16u);
-        };
-        const bool fast = shade_tile_fast<LOOP, STATS, ARCTIC_PCF_CANDIDATES != 0>(sp, args, A, lut, ty, tx, lane, cur, second);
-        if (!fast) shade_tile<LOOP, STATS, LDS_SHADOW>(sp, lut, shadow_tiles[LDS_SHADOW ? wave : 0], ty, tx, lane, cur, second);
-        trace_end(sp, A, tile, fast);
-        if (++k >= A.T) break;
-        asm volatile("" : "+s"(args));
-        A = args_a(args);                      // (nothing of the block stays in registers across a tile)
-        O = order_args(args);
-        if (!next_tile(A, O, blk, k, tx, ty)) break;
-        cur = load_head(A.ga, A.gb, (size_t)ty * A.tiles_x + tx, wave_lane());
-    }
-}
-
-// ---- the general-tile walk over a resident G-buffer, for the opt-in kernels k_envlit and k_spotlit: k_material's walk, every tile through
-// shade_tile<ENV, SPOT> (the fast tile's early exit for shadowed pixels does not hold under ENV, and the fast tile has no spot lights),
-// the geometric order, no statistics, no trace.  (A copy of k_material's walk, not a function k_material shares: inlined through one more
-// level, the walk comes out of the compiler with a few instructions of every k_material* rescheduled -- and the default kernels'
-// instructions are kept as they were.)
-template <int LOOP, bool ENV, bool SPOT>
-__device__ __forceinline__ void walk_general(float *lut) {
-    KernArgs args = kernel_args();
-    const BlockId blk = block_id<ARCTIC_WG_WAVES>();
-    const float *srgb_lut;
-    const unsigned long long *vis_unused;
-    OrderArgs O;
-    ArgsA A = args_a_first(args, srgb_lut, vis_unused, O);
-    O.order = nullptr;   // (the geometric order; under ENV the slot holds the environment tables: ShadeParams::env_tables)
-    uint32_t tx, ty, k = 0;
-    if (!next_tile(A, O, blk, k, tx, ty)) return;
-    TileHead cur;
-    {
-        const uint32_t lane = wave_lane();
-        const LutRegs lr = lut_load(srgb_lut, lane);
-        cur = load_head(A.ga, A.gb, (size_t)ty * A.tiles_x + tx, lane);
-        lut_store(lut, lane, lr);
-    }
-#pragma nounroll
-    for (;;) {
-        asm volatile("" : "+s"(args));   // see SP
-        SP sp = *args;
-        const uint32_t lane = wave_lane();
-        const size_t tile = (size_t)ty * A.tiles_x + tx;   // wave-uniform
-        const auto second = [&](const float4 *pc, const float4 *pd, const float4 *pe, float4 &gc, float4 &gd, float4 &ge) {
-            gc = gload_f4(pc + tile * 64, lane * 16u); gd = gload_f4(pd + tile * 64, lane * 16u); ge = gload_f4(pe + tile * 64, lane * 16u);
-        };
-        shade_tile<LOOP, false, false, ENV, SPOT>(sp, lut, nullptr, ty, tx, lane, cur, second);
-        if (++k >= A.T) break;
-        asm volatile("" : "+s"(args));
-        A = args_a(args);
-        if (!next_tile(A, O, blk, k, tx, ty)) break;
-        cur = load_head(A.ga, A.gb, (size_t)ty * A.tiles_x + tx, wave_lane());
-    }
+    WALK_GBUFFER(LOOP, STATS, false, false);
 }
 // the image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map)
 template <int LOOP>
-__global__ __launch_bounds__(64 * ARCTIC_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_envlit(const ShadeParams sp_by_value) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_envlit(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    walk_general<LOOP, true, false>(lut);
+    WALK_GBUFFER(LOOP, false, true, false);
 }
 // spot lights (arctic_update_spot_lights, a non-empty list); ENV: with the image-based ambient as well
 template <int LOOP, bool ENV>
-__global__ __launch_bounds__(64 * ARCTIC_WG_WAVES) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_spotlit(const ShadeParams sp_by_value) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_spotlit(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    walk_general<LOOP, ENV, true>(lut);
+    WALK_GBUFFER(LOOP, false, ENV, true);
 }
 
 // ---- the same without a G-buffer (whole frames): the tile walk straight from the visibility plane ----------------------
 // arctic_render_frame has no use for the 76 B/pixel G-buffer between its own two kernels: writing it (k_resolve, 630 MB at
-// 4K) and reading it back costs more than interpolating again.  This variant reads the 8-byte visibility key, finds the
+// 4K) and reading it back costs more than interpolating again.  This walk reads the 8-byte visibility key, finds the
 // triangle, and interpolates uv + light-space position for every covered pixel and world position + tangent frame only
 // for the lit ones -- with the very operations of k_resolve (edges.h, fp contraction off), so the pixels are bit-identical
-// to the G-buffer path.  Everything after the attributes is shade_tile, shared.
-template <int LOOP, bool STATS, bool LDS_SHADOW>
-__global__ __launch_bounds__(64 * VIS_WG_WAVES) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_material_vis(const ShadeParams sp_by_value) {
+// to the G-buffer path.  Everything after the attributes is shade_tile_fast / shade_tile, shared.  PLAIN, ENV and SPOT as in
+// WALK_GBUFFER (k_material_vis; k_envlit_vis, k_spotlit_vis), and a macro for the same reason.
+#define WALK_VIS(LOOP, STATS, ENV, SPOT)                                                                                                                            \
+    constexpr bool PLAIN = !ENV && !SPOT;                                                                                                                                            \
+    KernArgs args = kernel_args();                                                                                                                                                   \
+    unsigned long long t_entry = PLAIN ? trace_entry() : 0ull;                                                                                                                       \
+    const BlockId blk = block_id<4>();                                                                                                                                               \
+    const float *srgb_lut;     /* XCD-aware order or the prepass's dispatch order, T tiles per wave, the LUT without a barrier: see WALK_GBUFFER */                                  \
+    const unsigned long long *vis_plane;                                                                                                                                             \
+    OrderArgs O;                                                                                                                                                                     \
+    ArgsA A = args_a_first(args, srgb_lut, vis_plane, O);                                                                                                                            \
+    if (!PLAIN) O.order = nullptr;                                                                                                                                                   \
+    uint32_t tx, ty, k = 0;                                                                                                                                                          \
+    unsigned long long key = ~0ull;                                                                                                                                                  \
+    if (!next_tile(A, O, blk, k, tx, ty)) return;                                                                                                                                    \
+    {                                                                                                                                                                                \
+        const uint32_t lane = wave_lane();                                                                                                                                           \
+        const LutRegs lr = lut_load(srgb_lut, lane);                                                                                                                                 \
+        key = vis_plane[((size_t)ty * A.tiles_x + tx) * 64 + lane];                                                                                                                  \
+        lut_store(lut, lane, lr);                                                                                                                                                    \
+    }                                                                                                                                                                                \
+_Pragma("nounroll")                                                                                                                                                                  \
+    for (;;) {                                                                                                                                                                       \
+        asm volatile("" : "+s"(args));   /* see SP */                                                                                                                                \
+        SP sp = *args;                                                                                                                                                               \
+        const uint32_t lane = wave_lane();                                                                                                                                           \
+        if (PLAIN) trace_begin(sp, (size_t)ty * A.tiles_x + tx, t_entry);                                                                                                            \
+        t_entry = 0ull;                                                                                                                                                              \
+        const int32_t px = (int32_t)(tx * 8 + (lane & 7));                                                                                                                           \
+        const int32_t py = (row_global((int)ty, sp.band_tiles, sp.shard_count, sp.shard_index) + sp.tile_y0) * 8 + (int32_t)(lane >> 3);                                             \
+        TileHead cur;                                                                                                                                                                \
+        cur.a = make_float4(0.0f, 0.0f, 0.0f, 0.0f); cur.b0 = 0.0f; cur.b1 = 0.0f; cur.b2 = __uint_as_float(NO_MATERIAL);                                                            \
+        float B[3] = {0.0f, 0.0f, 0.0f};                                                                                                                                             \
+        uint32_t v0 = 0, v1 = 0, v2 = 0;   /* the source triangle's transformed vertices (indices, not pointers: they stay live across the tile) */                                  \
+        /* attribute k of transformed vertex v: XVert::attr at byte 16 + 4k of a 96-byte record.  With compact tables (below 4 GiB each, the */                                      \
+        /* host says) every gather is a wave-uniform base + a 32-bit byte offset: no 64-bit multiply-adds per lane and load */                                                       \
+        const bool compact = sp.compact_tables != 0;                                                                                                                                 \
+        if (key != ~0ull && compact) {                                                                                                                                               \
+            const uint32_t ri = gload_u32(sp.rec_of, (uint32_t)key << 2);   /* low word of the key = order id (k_setup) */                                                           \
+            const uint32_t so = ri << 7;                                     /* SetupRec and RasterRec are 128 bytes */                                                              \
+            const float4u qf = gload_f4u(sp.rrecs, so + 96u);                /* dz2, inv_area, order id, flags */                                                                    \
+            const u4v src = gload_u4u(sp.rrecs, so + 112u);                  /* the source triangle's three transformed vertices, its material */                                    \
+            if (__float_as_uint(qf.w) & RASTER_EXACT_F64) {                                                                                                                          \
+                typedef double d2v __attribute__((ext_vector_type(2)));                                                                                                              \
+                const auto ld2 = [&](uint32_t o) { return *(const d2v __attribute__((address_space(1))) *)((gchar)sp.rrecs + o); };                                                  \
+                const auto ld1 = [&](uint32_t o) { return *(const double __attribute__((address_space(1))) *)((gchar)sp.rrecs + o); };                                               \
+                const double A0 = ld1(so), C0 = ld1(so + 48u), A2 = ld1(so + 16u), B0 = ld1(so + 24u), B2 = ld1(so + 40u), C2 = ld1(so + 64u);                                       \
+                (void)ld2;                                                                                                                                                           \
+                const float4u s2 = gload_f4u(sp.recs, so + 32u);             /* z[2], iw[0..2] */                                                                                    \
+                const uint32_t fl = __float_as_uint(qf.w);                                                                                                                           \
+                {   /* source_barycentrics (edges.h), on the fields just loaded: the same operations in the same order */                                                            \
+_Pragma("clang fp contract(off)")                                                                                                                                                    \
+                    const double x = (double)px, y = (double)py;                                                                                                                     \
+                    const float l1 = (float)__builtin_fma(A2, x, __builtin_fma(B2, y, C2)) * qf.y;                                                                                   \
+                    const float l2 = (float)__builtin_fma(A0, x, __builtin_fma(B0, y, C0)) * qf.y;                                                                                   \
+                    const float l0 = (1.0f - l1) - l2;                                                                                                                               \
+                    const float pw0 = l0 * s2.y, pw1 = l1 * s2.z, pw2 = l2 * s2.w;                                                                                                   \
+                    const float rr = 1.0f / ((pw0 + pw1) + pw2);                                                                                                                     \
+                    const float c0 = pw0 * rr, c1 = pw1 * rr, c2 = pw2 * rr;                                                                                                         \
+                    if (__ballot((fl & RASTER_UNIT_BARY) == 0u) == 0ull) {                                                                                                           \
+                        /* every record under the tile is an uncut source triangle (nearly every tile): the rows of its barycentric matrix are */                                    \
+                        /* unit vectors and the products below return c0, c1, c2 themselves -- in source order when set-up exchanged two vertices */                                 \
+                        const bool swapped = (fl & RASTER_SWAPPED) != 0u;                                                                                                            \
+                        B[0] = c0; B[1] = swapped ? c2 : c1; B[2] = swapped ? c1 : c2;                                                                                               \
+                    } else {   /* a tile with a cut triangle under it: the product per lane, and the lanes of uncut triangles as above (source_barycentrics' rule: edges.h) */       \
+                        const float4u b0 = gload_f4u(sp.recs, so + 48u), b1 = gload_f4u(sp.recs, so + 64u);   /* bary[0][0..2], bary[1][0] | bary[1][1..2], bary[2][0..1] */         \
+                        const float b22 = __uint_as_float(gload_u32(sp.recs, so + 80u));                                                                                             \
+                        const bool unit = (fl & RASTER_UNIT_BARY) != 0u, swapped = (fl & RASTER_SWAPPED) != 0u;                                                                      \
+                        const float p0 = (c0 * b0.x + c1 * b0.w) + c2 * b1.z, p1 = (c0 * b0.y + c1 * b1.x) + c2 * b1.w, p2 = (c0 * b0.z + c1 * b1.y) + c2 * b22;                     \
+                        B[0] = unit ? c0 : p0; B[1] = unit ? (swapped ? c2 : c1) : p1; B[2] = unit ? (swapped ? c1 : c2) : p2;                                                       \
+                    }                                                                                                                                                                \
+                }                                                                                                                                                                    \
+            } else source_barycentrics(sp.recs[ri], sp.rrecs[ri], px, py, B);   /* rare: coordinates of 2^24 and more */                                                             \
+            cur.b2 = __uint_as_float(src.w);                                                                                                                                         \
+            v0 = src.x; v1 = src.y; v2 = src.z;                                                                                                                                      \
+            const uint32_t a0 = v0 * 96u + 16u, a1 = v1 * 96u + 16u, a2 = v2 * 96u + 16u;                                                                                            \
+            const float2 u0 = gload_f2(sp.xv, a0), u1 = gload_f2(sp.xv, a1), u2 = gload_f2(sp.xv, a2);                    /* attr 0, 1 */                                            \
+            const float4u w0 = gload_f4u(sp.xv, a0 + 56u), w1 = gload_f4u(sp.xv, a1 + 56u), w2 = gload_f4u(sp.xv, a2 + 56u);   /* attr 14..17 */                                     \
+            const auto mix = [&](float x0, float x1, float x2) {                                                                                                                     \
+_Pragma("clang fp contract(off)")                                                                                                                                                    \
+                return (B[0] * x0 + B[1] * x1) + B[2] * x2;   /* interpolate_attr (edges.h) */                                                                                       \
+            };                                                                                                                                                                       \
+            cur.a = make_float4(mix(u0.x, u1.x, u2.x), mix(u0.y, u1.y, u2.y), mix(w0.x, w1.x, w2.x), mix(w0.y, w1.y, w2.y));                                                         \
+            cur.b0 = mix(w0.z, w1.z, w2.z); cur.b1 = mix(w0.w, w1.w, w2.w);                                                                                                          \
+        } else if (key != ~0ull) {                                                                                                                                                   \
+            const uint32_t ri = sp.rec_of[(uint32_t)key];                                                                                                                            \
+            const SetupRec &t = sp.recs[ri];                                                                                                                                         \
+            source_barycentrics(t, sp.rrecs[ri], px, py, B);                                                                                                                         \
+            const ObjectRec &ob = sp.objs[t.object];                                                                                                                                 \
+            const uint32_t lt = t.src_tri - ob.first_triangle;                                                                                                                       \
+            v0 = ob.first_xvert + ob.indices[3 * lt]; v1 = ob.first_xvert + ob.indices[3 * lt + 1]; v2 = ob.first_xvert + ob.indices[3 * lt + 2];                                    \
+            const float *A0 = sp.xv[v0].attr, *A1 = sp.xv[v1].attr, *A2 = sp.xv[v2].attr;                                                                                            \
+            cur.a = make_float4(interpolate_attr(B, A0, A1, A2, 0), interpolate_attr(B, A0, A1, A2, 1),                                                                              \
+                                interpolate_attr(B, A0, A1, A2, 14), interpolate_attr(B, A0, A1, A2, 15));                                                                           \
+            cur.b0 = interpolate_attr(B, A0, A1, A2, 16); cur.b1 = interpolate_attr(B, A0, A1, A2, 17);                                                                              \
+            cur.b2 = __uint_as_float(ob.material);                                                                                                                                   \
+        }                                                                                                                                                                            \
+        const auto second = [&](const float4 *, const float4 *, const float4 *, float4 &gc, float4 &gd, float4 &ge) {                                                                \
+            /* attribute order (XVert::attr): uv 0-1, t 2-4, b 5-7, n 8-10, world 11-13, light space 14-17; planes as gbuffer_pack */                                                \
+            const auto mix = [&](float x0, float x1, float x2) {                                                                                                                     \
+_Pragma("clang fp contract(off)")                                                                                                                                                    \
+                return (B[0] * x0 + B[1] * x1) + B[2] * x2;                                                                                                                          \
+            };                                                                                                                                                                       \
+            if (compact) {                                                                                                                                                           \
+                const uint32_t a0 = v0 * 96u + 24u, a1 = v1 * 96u + 24u, a2 = v2 * 96u + 24u;   /* attr 2..13: three float4 per vertex */                                            \
+                const float4u p0 = gload_f4u(sp.xv, a0), p1 = gload_f4u(sp.xv, a1), p2 = gload_f4u(sp.xv, a2);                     /* attr 2..5 */                                   \
+                const float4u q0 = gload_f4u(sp.xv, a0 + 16u), q1 = gload_f4u(sp.xv, a1 + 16u), q2 = gload_f4u(sp.xv, a2 + 16u);   /* attr 6..9 */                                   \
+                const float4u r0 = gload_f4u(sp.xv, a0 + 32u), r1 = gload_f4u(sp.xv, a1 + 32u), r2 = gload_f4u(sp.xv, a2 + 32u);   /* attr 10..13 */                                 \
+                gc = make_float4(mix(r0.y, r1.y, r2.y), mix(r0.z, r1.z, r2.z), mix(r0.w, r1.w, r2.w), mix(p0.x, p1.x, p2.x));                                                        \
+                gd = make_float4(mix(p0.y, p1.y, p2.y), mix(p0.z, p1.z, p2.z), mix(p0.w, p1.w, p2.w), mix(q0.x, q1.x, q2.x));                                                        \
+                ge = make_float4(mix(q0.y, q1.y, q2.y), mix(q0.z, q1.z, q2.z), mix(q0.w, q1.w, q2.w), mix(r0.x, r1.x, r2.x));                                                        \
+            } else {                                                                                                                                                                 \
+                const float *A0 = sp.xv[v0].attr, *A1 = sp.xv[v1].attr, *A2 = sp.xv[v2].attr;                                                                                        \
+                gc = make_float4(interpolate_attr(B, A0, A1, A2, 11), interpolate_attr(B, A0, A1, A2, 12), interpolate_attr(B, A0, A1, A2, 13), interpolate_attr(B, A0, A1, A2, 2)); \
+                gd = make_float4(interpolate_attr(B, A0, A1, A2, 3), interpolate_attr(B, A0, A1, A2, 4), interpolate_attr(B, A0, A1, A2, 5), interpolate_attr(B, A0, A1, A2, 6));    \
+                ge = make_float4(interpolate_attr(B, A0, A1, A2, 7), interpolate_attr(B, A0, A1, A2, 8), interpolate_attr(B, A0, A1, A2, 9), interpolate_attr(B, A0, A1, A2, 10));   \
+            }                                                                                                                                                                        \
+        };                                                                                                                                                                           \
+        const bool fast = PLAIN && shade_tile_fast<LOOP, STATS>(sp, args, A, lut, ty, tx, lane, cur, second);                                                                        \
+        if (!fast) shade_tile<LOOP, STATS, ENV, SPOT>(sp, lut, ty, tx, lane, cur, second);                                                                                           \
+        if (PLAIN) trace_end(sp, A, (size_t)ty * A.tiles_x + tx, fast);                                                                                                              \
+        if (++k >= A.T) break;                                                                                                                                                       \
+        asm volatile("" : "+s"(args));                                                                                                                                               \
+        A = args_a(args);                                                                                                                                                            \
+        if (PLAIN) O = order_args(args);                                                                                                                                             \
+        if (!next_tile(A, O, blk, k, tx, ty)) break;                                                                                                                                 \
+        key = args->vis[((size_t)ty * A.tiles_x + tx) * 64 + wave_lane()];                                                                                                           \
+    }
+template <int LOOP, bool STATS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_material_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    __shared__ float shadow_tiles[LDS_SHADOW ? VIS_WG_WAVES : 1][LDS_SHADOW ? SHADOW_TILE * SHADOW_TILE : 1];   // one per wave (the LDS variant of the PCF slow path)
-    KernArgs args = kernel_args();
-    unsigned long long t_entry = trace_entry();
-    const BlockId blk = block_id<VIS_WG_WAVES>();
-    const uint32_t wave = VIS_WG_WAVES == 1 ? 0u : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (of the workgroup: which LDS shadow tile is this wave's)
-    const float *srgb_lut;     // XCD-aware order or the prepass's dispatch order, T tiles per wave, the LUT without a barrier: see k_material
-    const unsigned long long *vis_plane;
-    OrderArgs O;
-    ArgsA A = args_a_first(args, srgb_lut, vis_plane, O);
-    uint32_t tx, ty, k = 0;
-    unsigned long long key = ~0ull;
-#if ARCTIC_LUT_SHARED
-    {
-        const bool has_tile = next_tile(A, O, blk, k, tx, ty);
-        const uint32_t lane = wave_lane();
-        const float q = __uint_as_float(gload_u32(srgb_lut, (blk.wave * 64u + lane) * 4u));
-        if (has_tile) key = vis_plane[((size_t)ty * A.tiles_x + tx) * 64 + lane];
-        lut[blk.wave * 64u + lane] = q;
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (!has_tile) return;
-    }
-#else
-    if (!next_tile(A, O, blk, k, tx, ty)) return;
-    {
-        const uint32_t lane = wave_lane();
-        const LutRegs lr = lut_load(srgb_lut, lane);
-        key = vis_plane[((size_t)ty * A.tiles_x + tx) * 64 + lane];
-        lut_store(lut, lane, lr);
-    }
-#endif
-#pragma nounroll
-    for (;;) {
-    asm volatile("" : "+s"(args));   // see SP
-    SP sp = *args;
-    const uint32_t lane = wave_lane();
-    trace_begin(sp, (size_t)ty * A.tiles_x + tx, t_entry);
-    t_entry = 0ull;
-    const int32_t px = (int32_t)(tx * 8 + (lane & 7));
-    const int32_t py = (row_global((int)ty, sp.band_tiles, sp.shard_count, sp.shard_index) + sp.tile_y0) * 8 + (int32_t)(lane >> 3);
-    TileHead cur;
-    cur.a = make_float4(0.0f, 0.0f, 0.0f, 0.0f); cur.b0 = 0.0f; cur.b1 = 0.0f; cur.b2 = __uint_as_float(NO_MATERIAL);
-    float B[3] = {0.0f, 0.0f, 0.0f};
-    uint32_t v0 = 0, v1 = 0, v2 = 0;   // the source triangle's transformed vertices (indices, not pointers: they stay live across the tile)
-    // attribute k of transformed vertex v: XVert::attr at byte 16 + 4k of a 96-byte record.  With compact tables (below 4 GiB each, the
-    // host says) every gather is a wave-uniform base + a 32-bit byte offset: no 64-bit multiply-adds per lane and load
-    const bool compact = sp.compact_tables != 0;
-    if (key != ~0ull && compact) {
-        const uint32_t ri = gload_u32(sp.rec_of, (uint32_t)key << 2);   // low word of the key = order id (k_setup)
-        const uint32_t so = ri << 7;                                     // SetupRec and RasterRec are 128 bytes
-        const float4u qf = gload_f4u(sp.rrecs, so + 96u);                // dz2, inv_area, order id, flags
-        const u4v src = gload_u4u(sp.rrecs, so + 112u);                  // the source triangle's three transformed vertices, its material
-        if (__float_as_uint(qf.w) & RASTER_EXACT_F64) {
-            typedef double d2v __attribute__((ext_vector_type(2)));
-            const auto ld2 = [&](uint32_t o) { return *(const d2v __attribute__((address_space(1))) *)((gchar)sp.rrecs + o); };
-            const auto ld1 = [&](uint32_t o) { return *(const double __attribute__((address_space(1))) *)((gchar)sp.rrecs + o); };
-            const double A0 = ld1(so), C0 = ld1(so + 48u), A2 = ld1(so + 16u), B0 = ld1(so + 24u), B2 = ld1(so + 40u), C2 = ld1(so + 64u);
-            (void)ld2;
-            const float4u s2 = gload_f4u(sp.recs, so + 32u);             // z[2], iw[0..2]
-            const uint32_t fl = __float_as_uint(qf.w);
-            {   // source_barycentrics (edges.h), on the fields just loaded: the same operations in the same order
-#pragma clang fp contract(off)
-                const double x = (double)px, y = (double)py;
-                const float l1 = (float)__builtin_fma(A2, x, __builtin_fma(B2, y, C2)) * qf.y;
-                const float l2 = (float)__builtin_fma(A0, x, __builtin_fma(B0, y, C0)) * qf.y;
-                const float l0 = (1.0f - l1) - l2;
-                const float pw0 = l0 * s2.y, pw1 = l1 * s2.z, pw2 = l2 * s2.w;
-                const float rr = 1.0f / ((pw0 + pw1) + pw2);
-                const float c0 = pw0 * rr, c1 = pw1 * rr, c2 = pw2 * rr;
-                if (__ballot((fl & RASTER_UNIT_BARY) == 0u) == 0ull) {
-                    // every record under the tile is an uncut source triangle (nearly every tile): the rows of its barycentric matrix are
-                    // unit vectors and the products below return c0, c1, c2 themselves -- in source order when set-up exchanged two vertices
-                    const bool swapped = (fl & RASTER_SWAPPED) != 0u;
-                    B[0] = c0; B[1] = swapped ? c2 : c1; B[2] = swapped ? c1 : c2;
-                } else {   // a tile with a cut triangle under it: the product per lane, and the lanes of uncut triangles as above (source_barycentrics' rule: edges.h)
-                    const float4u b0 = gload_f4u(sp.recs, so + 48u), b1 = gload_f4u(sp.recs, so + 64u);   // bary[0][0..2], bary[1][0] | bary[1][1..2], bary[2][0..1]
-                    const float b22 = __uint_as_float(gload_u32(sp.recs, so + 80u));
-                    const bool unit = (fl & RASTER_UNIT_BARY) != 0u, swapped = (fl & RASTER_SWAPPED) != 0u;
-                    const float p0 = (c0 * b0.x + c1 * b0.w) + c2 * b1.z, p1 = (c0 * b0.y + c1 * b1.x) + c2 * b1.w, p2 = (c0 * b0.z + c1 * b1.y) + c2 * b22;
-                    B[0] = unit ? c0 : p0; B[1] = unit ? (swapped ? c2 : c1) : p1; B[2] = unit ? (swapped ? c1 : c2) : p2;
-                }
-            }
-        } else source_barycentrics(sp.recs[ri], sp.rrecs[ri], px, py, B);   // rare: coordinates of 2^24 and more
-        cur.b2 = __uint_as_float(src.w);
-        v0 = src.x; v1 = src.y; v2 = src.z;
-        const uint32_t a0 = v0 * 96u + 16u, a1 = v1 * 96u + 16u, a2 = v2 * 96u + 16u;
-        const float2 u0 = gload_f2(sp.xv, a0), u1 = gload_f2(sp.xv, a1), u2 = gload_f2(sp.xv, a2);                    // attr 0, 1
-        const float4u w0 = gload_f4u(sp.xv, a0 + 56u), w1 = gload_f4u(sp.xv, a1 + 56u), w2 = gload_f4u(sp.xv, a2 + 56u);   // attr 14..17
-        const auto mix = [&](float x0, float x1, float x2) {
-#pragma clang fp contract(off)
-            return (B[0] * x0 + B[1] * x1) + B[2] * x2;   // interpolate_attr (edges.h)
-        };
-        cur.a = make_float4(mix(u0.x, u1.x, u2.x), mix(u0.y, u1.y, u2.y), mix(w0.x, w1.x, w2.x), mix(w0.y, w1.y, w2.y));
-        cur.b0 = mix(w0.z, w1.z, w2.z); cur.b1 = mix(w0.w, w1.w, w2.w);
-    } else if (key != ~0ull) {
-        const uint32_t ri = sp.rec_of[(uint32_t)key];
-        const SetupRec &t = sp.recs[ri];
-        source_barycentrics(t, sp.rrecs[ri], px, py, B);
-        const ObjectRec &ob = sp.objs[t.object];
-        const uint32_t lt = t.src_tri - ob.first_triangle;
-        v0 = ob.first_xvert + ob.indices[3 * lt]; v1 = ob.first_xvert + ob.indices[3 * lt + 1]; v2 = ob.first_xvert + ob.indices[3 * lt + 2];
-        const float *A0 = sp.xv[v0].attr, *A1 = sp.xv[v1].attr, *A2 = sp.xv[v2].attr;
-        cur.a = make_float4(interpolate_attr(B, A0, A1, A2, 0), interpolate_attr(B, A0, A1, A2, 1),
-                            interpolate_attr(B, A0, A1, A2, 14), interpolate_attr(B, A0, A1, A2, 15));
-        cur.b0 = interpolate_attr(B, A0, A1, A2, 16); cur.b1 = interpolate_attr(B, A0, A1, A2, 17);
-        cur.b2 = __uint_as_float(ob.material);
-    }
-    const auto second = [&](const float4 *, const float4 *, const float4 *, float4 &gc, float4 &gd, float4 &ge) {
-        // attribute order (XVert::attr): uv 0-1, t 2-4, b 5-7, n 8-10, world 11-13, light space 14-17; planes as gbuffer_pack
-        const auto mix = [&](float x0, float x1, float x2) {
-#pragma clang fp contract(off)
-            return (B[0] * x0 + B[1] * x1) + B[2] * x2;
-        };
-        if (compact) {
-            const uint32_t a0 = v0 * 96u + 24u, a1 = v1 * 96u + 24u, a2 = v2 * 96u + 24u;   // attr 2..13: three float4 per vertex
-            const float4u p0 = gload_f4u(sp.xv, a0), p1 = gload_f4u(sp.xv, a1), p2 = gload_f4u(sp.xv, a2);                     // attr 2..5
-            const float4u q0 = gload_f4u(sp.xv, a0 + 16u), q1 = gload_f4u(sp.xv, a1 + 16u), q2 = gload_f4u(sp.xv, a2 + 16u);   // attr 6..9
-            const float4u r0 = gload_f4u(sp.xv, a0 + 32u), r1 = gload_f4u(sp.xv, a1 + 32u), r2 = gload_f4u(sp.xv, a2 + 32u);   // attr 10..13
-            gc = make_float4(mix(r0.y, r1.y, r2.y), mix(r0.z, r1.z, r2.z), mix(r0.w, r1.w, r2.w), mix(p0.x, p1.x, p2.x));
-            gd = make_float4(mix(p0.y, p1.y, p2.y), mix(p0.z, p1.z, p2.z), mix(p0.w, p1.w, p2.w), mix(q0.x, q1.x, q2.x));
-            ge = make_float4(mix(q0.y, q1.y, q2.y), mix(q0.z, q1.z, q2.z), mix(q0.w, q1.w, q2.w), mix(r0.x, r1.x, r2.x));
-        } else {
-            const float *A0 = sp.xv[v0].attr, *A1 = sp.xv[v1].attr, *A2 = sp.xv[v2].attr;
-            gc = make_float4(interpolate_attr(B, A0, A1, A2, 11), interpolate_attr(B, A0, A1, A2, 12), interpolate_attr(B, A0, A1, A2, 13), interpolate_attr(B, A0, A1, A2, 2));
-            gd = make_float4(interpolate_attr(B, A0, A1, A2, 3), interpolate_attr(B, A0, A1, A2, 4), interpolate_attr(B, A0, A1, A2, 5), interpolate_attr(B, A0, A1, A2, 6));
-            ge = make_float4(interpolate_attr(B, A0, A1, A2, 7), interpolate_attr(B, A0, A1, A2, 8), interpolate_attr(B, A0, A1, A2, 9), interpolate_attr(B, A0, A1, A2, 10));
-        }
-    };
-    const bool fast = shade_tile_fast<LOOP, STATS, false>(sp, args, A, lut, ty, tx, lane, cur, second);
-    if (!fast) shade_tile<LOOP, STATS, LDS_SHADOW>(sp, lut, shadow_tiles[LDS_SHADOW ? wave : 0], ty, tx, lane, cur, second);
-    trace_end(sp, A, (size_t)ty * A.tiles_x + tx, fast);
-    if (++k >= A.T) break;
-    asm volatile("" : "+s"(args));
-    A = args_a(args);
-    O = order_args(args);
-    if (!next_tile(A, O, blk, k, tx, ty)) break;
-    key = args->vis[((size_t)ty * A.tiles_x + tx) * 64 + wave_lane()];
-    }
-}
-
-// ---- the general-tile walk over whole frames, straight from the visibility plane (k_envlit_vis, k_spotlit_vis): k_material_vis's walk as
-// walk_general is k_material's (a copy for the same reason)
-template <int LOOP, bool ENV, bool SPOT>
-__device__ __forceinline__ void walk_general_vis(float *lut) {
-    KernArgs args = kernel_args();
-    const BlockId blk = block_id<VIS_WG_WAVES>();
-    const float *srgb_lut;
-    const unsigned long long *vis_plane;
-    OrderArgs O;
-    ArgsA A = args_a_first(args, srgb_lut, vis_plane, O);
-    O.order = nullptr;   // (the geometric order; under ENV the slot holds the environment tables)
-    uint32_t tx, ty, k = 0;
-    unsigned long long key = ~0ull;
-    if (!next_tile(A, O, blk, k, tx, ty)) return;
-    {
-        const uint32_t lane = wave_lane();
-        const LutRegs lr = lut_load(srgb_lut, lane);
-        key = vis_plane[((size_t)ty * A.tiles_x + tx) * 64 + lane];
-        lut_store(lut, lane, lr);
-    }
-#pragma nounroll
-    for (;;) {
-    asm volatile("" : "+s"(args));   // see SP
-    SP sp = *args;
-    const uint32_t lane = wave_lane();
-    const int32_t px = (int32_t)(tx * 8 + (lane & 7));
-    const int32_t py = (row_global((int)ty, sp.band_tiles, sp.shard_count, sp.shard_index) + sp.tile_y0) * 8 + (int32_t)(lane >> 3);
-    TileHead cur;
-    cur.a = make_float4(0.0f, 0.0f, 0.0f, 0.0f); cur.b0 = 0.0f; cur.b1 = 0.0f; cur.b2 = __uint_as_float(NO_MATERIAL);
-    float B[3] = {0.0f, 0.0f, 0.0f};
-    uint32_t v0 = 0, v1 = 0, v2 = 0;   // the source triangle's transformed vertices (indices, not pointers: they stay live across the tile)
-    // attribute k of transformed vertex v: XVert::attr at byte 16 + 4k of a 96-byte record.  With compact tables (below 4 GiB each, the
-    // host says) every gather is a wave-uniform base + a 32-bit byte offset: no 64-bit multiply-adds per lane and load
-    const bool compact = sp.compact_tables != 0;
-    if (key != ~0ull && compact) {
-        const uint32_t ri = gload_u32(sp.rec_of, (uint32_t)key << 2);   // low word of the key = order id (k_setup)
-        const uint32_t so = ri << 7;                                     // SetupRec and RasterRec are 128 bytes
-        const float4u qf = gload_f4u(sp.rrecs, so + 96u);                // dz2, inv_area, order id, flags
-        const u4v src = gload_u4u(sp.rrecs, so + 112u);                  // the source triangle's three transformed vertices, its material
-        if (__float_as_uint(qf.w) & RASTER_EXACT_F64) {
-            typedef double d2v __attribute__((ext_vector_type(2)));
-            const auto ld2 = [&](uint32_t o) { return *(const d2v __attribute__((address_space(1))) *)((gchar)sp.rrecs + o); };
-            const auto ld1 = [&](uint32_t o) { return *(const double __attribute__((address_space(1))) *)((gchar)sp.rrecs + o); };
-            const double A0 = ld1(so), C0 = ld1(so + 48u), A2 = ld1(so + 16u), B0 = ld1(so + 24u), B2 = ld1(so + 40u), C2 = ld1(so + 64u);
-            (void)ld2;
-            const float4u s2 = gload_f4u(sp.recs, so + 32u);             // z[2], iw[0..2]
-            const uint32_t fl = __float_as_uint(qf.w);
-            {   // source_barycentrics (edges.h), on the fields just loaded: the same operations in the same order
-#pragma clang fp contract(off)
-                const double x = (double)px, y = (double)py;
-                const float l1 = (float)__builtin_fma(A2, x, __builtin_fma(B2, y, C2)) * qf.y;
-                const float l2 = (float)__builtin_fma(A0, x, __builtin_fma(B0, y, C0)) * qf.y;
-                const float l0 = (1.0f - l1) - l2;
-                const float pw0 = l0 * s2.y, pw1 = l1 * s2.z, pw2 = l2 * s2.w;
-                const float rr = 1.0f / ((pw0 + pw1) + pw2);
-                const float c0 = pw0 * rr, c1 = pw1 * rr, c2 = pw2 * rr;
-                if (__ballot((fl & RASTER_UNIT_BARY) == 0u) == 0ull) {
-                    // every record under the tile is an uncut source triangle (nearly every tile): the rows of its barycentric matrix are
-                    // unit vectors and the products below return c0, c1, c2 themselves -- in source order when set-up exchanged two vertices
-                    const bool swapped = (fl & RASTER_SWAPPED) != 0u;
-                    B[0] = c0; B[1] = swapped ? c2 : c1; B[2] = swapped ? c1 : c2;
-                } else {   // a tile with a cut triangle under it: the product per lane, and the lanes of uncut triangles as above (source_barycentrics' rule: edges.h)
-                    const float4u b0 = gload_f4u(sp.recs, so + 48u), b1 = gload_f4u(sp.recs, so + 64u);   // bary[0][0..2], bary[1][0] | bary[1][1..2], bary[2][0..1]
-                    const float b22 = __uint_as_float(gload_u32(sp.recs, so + 80u));
-                    const bool unit = (fl & RASTER_UNIT_BARY) != 0u, swapped = (fl & RASTER_SWAPPED) != 0u;
-                    const float p0 = (c0 * b0.x + c1 * b0.w) + c2 * b1.z, p1 = (c0 * b0.y + c1 * b1.x) + c2 * b1.w, p2 = (c0 * b0.z + c1 * b1.y) + c2 * b22;
-                    B[0] = unit ? c0 : p0; B[1] = unit ? (swapped ? c2 : c1) : p1; B[2] = unit ? (swapped ? c1 : c2) : p2;
-                }
-            }
-        } else source_barycentrics(sp.recs[ri], sp.rrecs[ri], px, py, B);   // rare: coordinates of 2^24 and more
-        cur.b2 = __uint_as_float(src.w);
-        v0 = src.x; v1 = src.y; v2 = src.z;
-        const uint32_t a0 = v0 * 96u + 16u, a1 = v1 * 96u + 16u, a2 = v2 * 96u + 16u;
-        const float2 u0 = gload_f2(sp.xv, a0), u1 = gload_f2(sp.xv, a1), u2 = gload_f2(sp.xv, a2);                    // attr 0, 1
-        const float4u w0 = gload_f4u(sp.xv, a0 + 56u), w1 = gload_f4u(sp.xv, a1 + 56u), w2 = gload_f4u(sp.xv, a2 + 56u);   // attr 14..17
-        const auto mix = [&](float x0, float x1, float x2) {
-#pragma clang fp contract(off)
-            return (B[0] * x0 + B[1] * x1) + B[2] * x2;   // interpolate_attr (edges.h)
-        };
-        cur.a = make_float4(mix(u0.x, u1.x, u2.x), mix(u0.y, u1.y, u2.y), mix(w0.x, w1.x, w2.x), mix(w0.y, w1.y, w2.y));
-        cur.b0 = mix(w0.z, w1.z, w2.z); cur.b1 = mix(w0.w, w1.w, w2.w);
-    } else if (key != ~0ull) {
-        const uint32_t ri = sp.rec_of[(uint32_t)key];
-        const SetupRec &t = sp.recs[ri];
-        source_barycentrics(t, sp.rrecs[ri], px, py, B);
-        const ObjectRec &ob = sp.objs[t.object];
-        const uint32_t lt = t.src_tri - ob.first_triangle;
-        v0 = ob.first_xvert + ob.indices[3 * lt]; v1 = ob.first_xvert + ob.indices[3 * lt + 1]; v2 = ob.first_xvert + ob.indices[3 * lt + 2];
-        const float *A0 = sp.xv[v0].attr, *A1 = sp.xv[v1].attr, *A2 = sp.xv[v2].attr;
-        cur.a = make_float4(interpolate_attr(B, A0, A1, A2, 0), interpolate_attr(B, A0, A1, A2, 1),
-                            interpolate_attr(B, A0, A1, A2, 14), interpolate_attr(B, A0, A1, A2, 15));
-        cur.b0 = interpolate_attr(B, A0, A1, A2, 16); cur.b1 = interpolate_attr(B, A0, A1, A2, 17);
-        cur.b2 = __uint_as_float(ob.material);
-    }
-    const auto second = [&](const float4 *, const float4 *, const float4 *, float4 &gc, float4 &gd, float4 &ge) {
-        // attribute order (XVert::attr): uv 0-1, t 2-4, b 5-7, n 8-10, world 11-13, light space 14-17; planes as gbuffer_pack
-        const auto mix = [&](float x0, float x1, float x2) {
-#pragma clang fp contract(off)
-            return (B[0] * x0 + B[1] * x1) + B[2] * x2;
-        };
-        if (compact) {
-            const uint32_t a0 = v0 * 96u + 24u, a1 = v1 * 96u + 24u, a2 = v2 * 96u + 24u;   // attr 2..13: three float4 per vertex
-            const float4u p0 = gload_f4u(sp.xv, a0), p1 = gload_f4u(sp.xv, a1), p2 = gload_f4u(sp.xv, a2);                     // attr 2..5
-            const float4u q0 = gload_f4u(sp.xv, a0 + 16u), q1 = gload_f4u(sp.xv, a1 + 16u), q2 = gload_f4u(sp.xv, a2 + 16u);   // attr 6..9
-            const float4u r0 = gload_f4u(sp.xv, a0 + 32u), r1 = gload_f4u(sp.xv, a1 + 32u), r2 = gload_f4u(sp.xv, a2 + 32u);   // attr 10..13
-            gc = make_float4(mix(r0.y, r1.y, r2.y), mix(r0.z, r1.z, r2.z), mix(r0.w, r1.w, r2.w), mix(p0.x, p1.x, p2.x));
-            gd = make_float4(mix(p0.y, p1.y, p2.y), mix(p0.z, p1.z, p2.z), mix(p0.w, p1.w, p2.w), mix(q0.x, q1.x, q2.x));
-            ge = make_float4(mix(q0.y, q1.y, q2.y), mix(q0.z, q1.z, q2.z), mix(q0.w, q1.w, q2.w), mix(r0.x, r1.x, r2.x));
-        } else {
-            const float *A0 = sp.xv[v0].attr, *A1 = sp.xv[v1].attr, *A2 = sp.xv[v2].attr;
-            gc = make_float4(interpolate_attr(B, A0, A1, A2, 11), interpolate_attr(B, A0, A1, A2, 12), interpolate_attr(B, A0, A1, A2, 13), interpolate_attr(B, A0, A1, A2, 2));
-            gd = make_float4(interpolate_attr(B, A0, A1, A2, 3), interpolate_attr(B, A0, A1, A2, 4), interpolate_attr(B, A0, A1, A2, 5), interpolate_attr(B, A0, A1, A2, 6));
-            ge = make_float4(interpolate_attr(B, A0, A1, A2, 7), interpolate_attr(B, A0, A1, A2, 8), interpolate_attr(B, A0, A1, A2, 9), interpolate_attr(B, A0, A1, A2, 10));
-        }
-    };
-    shade_tile<LOOP, false, false, ENV, SPOT>(sp, lut, nullptr, ty, tx, lane, cur, second);
-    if (++k >= A.T) break;
-    asm volatile("" : "+s"(args));
-    A = args_a(args);
-    if (!next_tile(A, O, blk, k, tx, ty)) break;
-    key = args->vis[((size_t)ty * A.tiles_x + tx) * 64 + wave_lane()];
-    }
+    WALK_VIS(LOOP, STATS, false, false);
 }
 template <int LOOP>
-__global__ __launch_bounds__(64 * VIS_WG_WAVES) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_envlit_vis(const ShadeParams sp_by_value) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_envlit_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    walk_general_vis<LOOP, true, false>(lut);
+    WALK_VIS(LOOP, false, true, false);
 }
 template <int LOOP, bool ENV>
-__global__ __launch_bounds__(64 * VIS_WG_WAVES) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_spotlit_vis(const ShadeParams sp_by_value) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_spotlit_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    walk_general_vis<LOOP, ENV, true>(lut);
+    WALK_VIS(LOOP, false, ENV, true);
 }
 
 // ---- shadow bounds: the conservative min/max table calculate_lit tests first -------------------------------------------
@@ -1823,37 +1536,20 @@ __global__ __launch_bounds__(256) void k_post_process(const float4 *__restrict__
     if (ldr) { ldr[i * 3] = l.x; ldr[i * 3 + 1] = l.y; ldr[i * 3 + 2] = l.z; }
 }
 
-template <int LOOP, bool STATS, bool LDS_SHADOW>
+template <int LOOP, bool STATS>
 hipError_t launch_variant(const ShadeParams &sp, const ShadeLaunch &L, dim3 grid) {
-    if (L.spot) {   // (geometric order, no statistics, no LDS variant: launch_shade)
-        if (L.from_vis) {
-            if (VIS_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;
-            if (L.env) k_spotlit_vis<LOOP, true><<<grid, 64 * VIS_WG_WAVES, 0, L.stream>>>(sp);
-            else k_spotlit_vis<LOOP, false><<<grid, 64 * VIS_WG_WAVES, 0, L.stream>>>(sp);
-        } else {
-            if (ARCTIC_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;
-            if (L.env) k_spotlit<LOOP, true><<<grid, 64 * ARCTIC_WG_WAVES, 0, L.stream>>>(sp);
-            else k_spotlit<LOOP, false><<<grid, 64 * ARCTIC_WG_WAVES, 0, L.stream>>>(sp);
-        }
+    if (L.from_vis) {   // four-wave workgroups, a strip of 4 tiles each (block_id<4>)
+        if (L.spot && L.env) k_spotlit_vis<LOOP, true><<<grid, 256, 0, L.stream>>>(sp);
+        else if (L.spot) k_spotlit_vis<LOOP, false><<<grid, 256, 0, L.stream>>>(sp);
+        else if (L.env) k_envlit_vis<LOOP><<<grid, 256, 0, L.stream>>>(sp);
+        else k_material_vis<LOOP, STATS><<<grid, 256, 0, L.stream>>>(sp);
         return hipGetLastError();
     }
-    if (L.env) {   // (geometric order, no statistics, no LDS variant: launch_shade)
-        if (L.from_vis) {
-            if (VIS_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;
-            k_envlit_vis<LOOP><<<grid, 64 * VIS_WG_WAVES, 0, L.stream>>>(sp);
-        } else {
-            if (ARCTIC_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;
-            k_envlit<LOOP><<<grid, 64 * ARCTIC_WG_WAVES, 0, L.stream>>>(sp);
-        }
-        return hipGetLastError();
-    }
-    if (L.from_vis) {
-        if (VIS_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;   // (block_id, as below)
-        k_material_vis<LOOP, STATS, LDS_SHADOW><<<grid, 64 * VIS_WG_WAVES, 0, L.stream>>>(sp);
-        return hipGetLastError();
-    }
-    if (ARCTIC_WG_WAVES == 1) grid.x = (grid.x + 7) / 8 * 32;   // (block_id: four one-wave blocks per strip, a strip's blocks on one XCD)
-    k_material<LOOP, STATS, LDS_SHADOW><<<grid, 64 * ARCTIC_WG_WAVES, 0, L.stream>>>(sp);
+    grid.x = (grid.x + 7) / 8 * 32;   // one-wave workgroups (block_id<1>): four blocks per strip, a strip's blocks on one XCD
+    if (L.spot && L.env) k_spotlit<LOOP, true><<<grid, 64, 0, L.stream>>>(sp);
+    else if (L.spot) k_spotlit<LOOP, false><<<grid, 64, 0, L.stream>>>(sp);
+    else if (L.env) k_envlit<LOOP><<<grid, 64, 0, L.stream>>>(sp);
+    else k_material<LOOP, STATS><<<grid, 64, 0, L.stream>>>(sp);
     return hipGetLastError();
 }
 
@@ -1876,11 +1572,8 @@ hipError_t launch_shade(const ShadeParams &sp_in, const ShadeLaunch &L) {
     dim3 grid(8 * bpr, sp.group_stride);   // a block shades tiles_per_wave groups of 8 tile rows, group_stride groups apart
     if (sp.tile_order && !L.env && !L.spot) // ... or tiles_per_wave consecutive slots of the prepass's dispatch order (n_jobs slots, common.h order_slot: a block = one XCD's list)
         grid = dim3((sp.n_jobs + sp.tiles_per_wave - 1) / sp.tiles_per_wave, 1);
-    if (L.env || L.spot) return L.loop == 2 ? launch_variant<2, false, false>(sp, L, grid) : launch_variant<1, false, false>(sp, L, grid);
-    if (sp.debug & 16)   // A/B only: the 25-tap path staged through LDS (a separate instantiation: it costs the default kernels nothing)
-        return L.loop == 2 ? launch_variant<2, false, true>(sp, L, grid) : launch_variant<1, false, true>(sp, L, grid);
-    if (L.loop == 2) return L.stats ? launch_variant<2, true, false>(sp, L, grid) : launch_variant<2, false, false>(sp, L, grid);
-    return L.stats ? launch_variant<1, true, false>(sp, L, grid) : launch_variant<1, false, false>(sp, L, grid);
+    if (L.loop == 2) return L.stats ? launch_variant<2, true>(sp, L, grid) : launch_variant<2, false>(sp, L, grid);
+    return L.stats ? launch_variant<1, true>(sp, L, grid) : launch_variant<1, false>(sp, L, grid);
 }
 
 hipError_t launch_shadow_bounds(const float *map, uint32_t S, float2 *blocks, float2 *bounds, hipStream_t s) {

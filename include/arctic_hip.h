@@ -302,8 +302,8 @@ int arctic_stats(ArcticRenderer *r, uint64_t *out, uint32_t n);
 #define ARCTIC_OPT_CULLING           3 /* 0 = run the light loop for every covered pixel; 1 (default) = exact culling: fully shadowed pixels skip it
                                           (every term of ps_main carries 1 - shadow, forward.hlsl:222,230) */
 #define ARCTIC_OPT_DEBUG             4 /* timing experiments only: bit 0 skip material textures, bit 1 skip shadow test, bit 2 skip tonemap (wrong images);
-                                          bit 3 shadow test without the min/max table (same image); bit 4 the 25-tap PCF path of tiles on a shadow
-                                          edge reads a per-wave LDS tile instead of a per-lane register window (same image; measured A/B);
+                                          bit 3 shadow test without the min/max table (same image); bit 4 ignored (it selected an LDS variant of the
+                                          25-tap PCF path, measured slower and removed; the image is the same);
                                           bit 5 every triangle through the 64-bit integer rasteriser instead of the binary64 planes (same image: the path
                                           of triangles with snapped coordinates of 2^24 and more); bit 6 whole frames gather records and vertices through 64-bit
                                           pointers (the path of tables of 4 GiB and more) instead of 32-bit offsets (same image); bit 7 arctic_render_frame draws the

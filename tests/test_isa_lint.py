@@ -13,7 +13,7 @@ spec = importlib.util.spec_from_file_location("isa_lint", os.path.join(ROOT, "to
 isa_lint = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(isa_lint)
 
-HEAD = "_ZN6arctic12_GLOBAL__N_110k_materialILi2ELb0ELb0EEEvNS_11ShadeParamsE:\n"
+HEAD = "_ZN6arctic12_GLOBAL__N_110k_materialILi2ELb0EEEvNS_11ShadeParamsE:\n"
 TAIL = "\t.end_amdhsa_kernel\n"
 
 
@@ -105,26 +105,12 @@ def test_shading_kernels_keep_their_register_budgets(shade_isa):
     a day of round 4 saw 82 ... 102 SGPRs)."""
     res = _kernel_resources(shade_isa)
     for loop in (1, 2):
-        k = res[f"_ZN6arctic12_GLOBAL__N_110k_materialILi{loop}ELb0ELb0EEEvNS_11ShadeParamsE"]       # the pass over a G-buffer: 7 waves per SIMD
+        k = res[f"_ZN6arctic12_GLOBAL__N_110k_materialILi{loop}ELb0EEEvNS_11ShadeParamsE"]       # the pass over a G-buffer: 7 waves per SIMD
         assert k["vgprs"] <= 72 and k["sgprs"] <= 96 and k["scratch"] == 0, (loop, k)
         assert k["lds"] <= 20 * 1024, (loop, k)       # 8 workgroups per CU must fit the 160 KiB
     for loop in (1, 2):
-        k = res[f"_ZN6arctic12_GLOBAL__N_114k_material_visILi{loop}ELb0ELb0EEEvNS_11ShadeParamsE"]   # whole frames: 6 waves (7 measured slower, DESIGN 4.2c)
+        k = res[f"_ZN6arctic12_GLOBAL__N_114k_material_visILi{loop}ELb0EEEvNS_11ShadeParamsE"]   # whole frames: 6 waves (7 measured slower, DESIGN 4.2c)
         assert k["vgprs"] <= 80 and k["scratch"] == 0, (loop, k)
-
-
-@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
-@pytest.mark.parametrize("defines", [("-DARCTIC_WG_WAVES=4", "-DARCTIC_EDGE_IN_FAST=0"),
-                                     ("-DARCTIC_LUT_SHARED=1", "-DARCTIC_PCF_CANDIDATES=1", "-DARCTIC_PCF_ROW_CANDIDATES=1", "-DARCTIC_VIS_WG_WAVES=1")],
-                         ids=["four-wave-workgroups+edge-tiles-to-general-tile", "shared-lut+pcf-candidates"])
-def test_ab_switches_still_compile(tmp_path, defines):
-    """the A/B compile switches of shade.hip (measured variants kept behind a default: DESIGN 4.2c, profiles/r4_c_*, r5_a_*, r5_b_*) build for gfx950 with
-    their non-default values -- device code through the backend (register allocation included), nothing is run"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "arctic-renderer_amd", "csrc", "shade.hip")
-    out = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--offload-device-only", "-ffp-contract=off", "-mllvm", "-disable-machine-licm",
-                          *defines, "-c", src, "-o", str(tmp_path / "shade_variant.o")], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-3000:]
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
