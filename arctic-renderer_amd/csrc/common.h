@@ -266,7 +266,7 @@ struct ShadeParams {
     float sun_dir[3];
     uint32_t n_spots;            // k_spotlit* only: spot lights at ShadeParams::spots (the slot was padding: the block keeps its size and place)
     float sun_color[3];
-    uint32_t pad_d1;
+    uint32_t n_cubes;            // k_cubelit* only: shadow-casting point lights at ShadeParams::cubes (the slot was padding, as n_spots' was)
     // ---- the rest: read at the point of use
     const float *srgb_lut;       // 256 floats, sRGB8 -> linear
     // stats: STATS kernels only: [0] point-light evaluations, [1] lit pixels, [2] evaluations with n.wi > 0,
@@ -277,7 +277,13 @@ struct ShadeParams {
         unsigned long long *stats;
         const float4 *spots;
     };
-    unsigned long long *trace;   // ARCTIC_OPT_TILE_TRACE: 4 x u64 per tile (shade.hip: trace_end), or null
+    // trace: ARCTIC_OPT_TILE_TRACE: 4 x u64 per tile (shade.hip: trace_end), or null
+    // cubes: k_cubelit* only (they keep no trace): n_cubes records, CUBE_F4 float4 each (CubeDev), then n_cubes x 6 faces of cube_size^2
+    //        floats (one allocation, arctic_update_point_shadow_lights).  One slot for both, for the reason given at stats / spots.
+    union {
+        unsigned long long *trace;
+        const float4 *cubes;
+    };
     // tile_order: the pass's dispatch order (k_tile_order: strips of 4 tiles, ty << 16 | strip column), n_jobs entries; null: the geometric order.
     // env_tables: image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map), the tables env_light.hip built from the map.  One slot for
     // both: k_envlit* take the geometric order and never read an order, the other kernels never read the tables.  (Appended as a field of
@@ -287,7 +293,7 @@ struct ShadeParams {
         const struct EnvTables *env_tables;
     };
     uint32_t n_jobs;
-    uint32_t pad_o;
+    uint32_t cube_size;          // k_cubelit* only: F, the side of a cube face (ARCTIC_OPT_POINT_SHADOW_SIZE; the slot was padding)
     // whole frames without a G-buffer (k_material_vis): the visibility plane and what the prepass left behind
     const unsigned long long *vis; const SetupRec *recs; const RasterRec *rrecs; const uint32_t *rec_of; const ObjectRec *objs; const XVert *xv;
     // skybox (skybox.hlsl:61-90): environment map for pixels without geometry; env == null -> black
@@ -308,6 +314,7 @@ struct ShadeLaunch {
     uint32_t tiles_per_wave;   // 0: DEFAULT_TILES_PER_WAVE (ARCTIC_OPT_TILES_PER_WAVE)
     uint32_t env;        // 1: k_envlit / k_envlit_vis (image-based ambient, ShadeParams::env_tables; geometric tile order, no statistics)
     uint32_t spot;       // 1: k_spotlit / k_spotlit_vis with ENV = env (ShadeParams::spots, n_spots; geometric tile order, no statistics)
+    uint32_t cube;       // 1: k_cubelit / k_cubelit_vis with ENV = env, spot lights included (ShadeParams::cubes, n_cubes, cube_size; geometric order, no statistics, no trace)
 };
 
 // ---- spot lights (arctic_update_spot_lights; semantics in include/arctic_hip.h next to the call) ---------------------------------------
@@ -316,6 +323,13 @@ struct ShadeLaunch {
 constexpr uint32_t SPOT_F4 = 3;
 struct SpotDev { float p[3], scale, s[3], offset, c[3], ir2; };
 static_assert(sizeof(SpotDev) == SPOT_F4 * 16, "SpotDev: 3 float4");
+
+// ---- shadow-casting point lights (arctic_update_point_shadow_lights; semantics in include/arctic_hip.h next to the call) --------------
+// On the device: 2 float4 per light, {p.xyz, zf / (zf - zn)} {rgb, zn}, the first derived by the host in binary64 and rounded once; behind
+// the n_cubes records the lights' faces, 6 x F x F floats per light in face order (+X, -X, +Y, -Y, +Z, -Z), row-major, row 0 at clip y = +1.
+constexpr uint32_t CUBE_F4 = 2;
+struct CubeDev { float p[3], pz_scale, c[3], zn; };
+static_assert(sizeof(CubeDev) == CUBE_F4 * 16, "CubeDev: 2 float4");
 
 // ---- image-based ambient (ARCTIC_OPT_ENV_LIGHTING, env_light.hip) ------------------------------------------------------
 // The semantics are written once, in include/arctic_hip.h next to the option.  What the shading kernels read, built on the device
@@ -412,6 +426,8 @@ hipError_t launch_gbuffer_tile(GBuffer g, float *attrs, uint32_t *mat, uint32_t 
 void dir_from_rot(const float rot_deg[2], float out[3]);
 void camera_proj_view(const float eye[3], const float rot_deg[2], float aspect, float fov_y_deg, float zn, float zf, float out[16]);
 void sun_proj_view(const float pos[3], const float rot_deg[2], float out[16]);
+// face k (0..5: +X, -X, +Y, -Y, +Z, -Z) of a shadow-casting point light: perspectiveRH_ZO(90 deg, 1, zn, zf) * lookAtRH(p, p + dir_k, up_k)
+void point_shadow_proj_view(const float pos[3], int face, float zn, float zf, float out[16]);
 float srgb8_to_linear(int c);
 void camera_sky_basis(const float rot_deg[2], float aspect, float fov_y_deg, float fwd[3], float right[3], float up[3]);
 

@@ -101,6 +101,33 @@ void sun_proj_view(const float pos[3], const float rot_deg[2], float out[16]) {
     mat_mul(proj, view, out);
 }
 
+// a shadow-casting point light's face k (no counterpart in the reference; include/arctic_hip.h: arctic_point_shadow_matrices):
+// perspectiveRH_ZO(90 deg, 1, zn, zf) * lookAtRH(p, p + dir_k, up_k) with camera_proj_view's helpers and operation order.  Two values are
+// taken exactly: 1 / tan(45 deg) = 1, and lookAtRH's forward (p + dir_k) - p = dir_k -- so the rows s, u, f are signed unit axes, and the
+// entries that are 0 or +-1 by structure are exactly that.
+void point_shadow_proj_view(const float pos[3], int face, float zn, float zf, float out[16]) {
+    static const float dirs[6][3] = {{1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
+    static const float ups[6][3] = {{0, -1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}, {0, -1, 0}, {0, -1, 0}};
+    const float *f = dirs[face], *up = ups[face];
+    float s[3];
+    cross3(f, up, s);
+    normalize3(s);
+    float u[3];
+    cross3(s, f, u);
+    float view[16];
+    view[0] = s[0];  view[4] = s[1];  view[8] = s[2];   view[12] = -dot3(s, pos);
+    view[1] = u[0];  view[5] = u[1];  view[9] = u[2];   view[13] = -dot3(u, pos);
+    view[2] = -f[0]; view[6] = -f[1]; view[10] = -f[2]; view[14] = dot3(f, pos);
+    view[3] = 0.0f;  view[7] = 0.0f;  view[11] = 0.0f;  view[15] = 1.0f;
+    float proj[16] = {0};
+    proj[0] = 1.0f;
+    proj[5] = 1.0f;
+    proj[10] = zf / (zn - zf);
+    proj[11] = -1.0f;
+    proj[14] = -(zf * zn) / (zf - zn);
+    mat_mul(proj, view, out);
+}
+
 // SkyboxPass (skybox_pass.cpp:104-138, skybox.hlsl:61-70): the cube is drawn with proj * mat3(lookAtRH) and its
 // interpolated object-space position is the lookup direction, i.e. the world-space ray through the pixel.  That ray for
 // ndc (x, y) is fwd + x * right + y * up with the camera basis of lookAtRH scaled by the frustum half-extents.

@@ -217,6 +217,15 @@ struct ArcticRenderer {
     // arctic_update_spot_lights: SPOT_F4 float4 per light (common.h SpotDev); a non-empty list sends every tile to k_spotlit*
     DevBuf d_spots;
     uint32_t n_spots = 0;
+    // arctic_update_point_shadow_lights: ONE allocation, n_cubes records (CUBE_F4 float4 each, common.h CubeDev) and behind them n_cubes x 6
+    // faces of cube_size^2 floats; a non-empty list sends every tile to k_cubelit*.  One set of faces: they are drawn on the main stream,
+    // behind the previous frame's shading that reads them (pass_point_shadows)
+    DevBuf d_cubes;
+    uint32_t n_cubes = 0, cube_size = 1024;         // cube_size: ARCTIC_OPT_POINT_SHADOW_SIZE
+    std::vector<ArcticPointShadowLight> cube_lights;   // the list as given: the faces' matrices and the cache key
+    std::vector<uint8_t> cube_key;                  // what the faces were drawn from (render_frame redraws them when it changes; empty: redraw)
+    uint32_t *h_cube_counts = nullptr, *dh_cube_counts = nullptr;   // pinned, mapped: CUBE_COUNT_WORDS per face drawn (run_geometry's DepthTarget)
+    uint32_t cube_count_faces = 0;
     // frame targets
     DevBuf d_vis_set[3], d_p0, d_p1, d_p2, d_p3, d_p4, d_rgba8, d_ldr, d_hdr, d_counter;
     bool have_gbuffer = false, have_output = false, have_vis = false;   // have_vis: d_vis holds the visibility of the current G-buffer
@@ -370,7 +379,7 @@ int alloc_targets(ArcticRenderer *r) {
     HIPCHECK(r, r->d_p4.ensure(px * 12));
     HIPCHECK(r, r->d_rgba8.ensure(out_px * 4));
     HIPCHECK(r, r->d_counter.ensure(8 * N_SHADE_STATS));
-    HIPCHECK(r, r->d_geo_counters.ensure(4 * N_GEO_COUNTERS * 4));   // N_GEO_COUNTERS words per table set
+    HIPCHECK(r, r->d_geo_counters.ensure(5 * N_GEO_COUNTERS * 4));   // N_GEO_COUNTERS words per table set; set 4: the cube faces (CUBE_COUNTER_SET)
     r->have_gbuffer = r->have_output = r->have_vis = r->have_order = false;
     return ARCTIC_OK;
 }
@@ -452,28 +461,44 @@ int upload_pass_tables(ArcticRenderer *r, PassTables &T, DevBuf &d_xverts, hipSt
     return ARCTIC_OK;
 }
 
-// vertex -> clip/setup -> raster, shared by the forward prepass and the shadow pass
-int run_geometry(ArcticRenderer *r, const ArcticScene *sc, bool shadow_pass, hipStream_t stream) {
+// A depth-only target other than the sun's map: one face of a shadow-casting point light (pass_point_shadows).  It is drawn like the
+// sun's map -- front faces culled, depth LESS, cleared to 1.0, small triangles by k_setup -- with the shadow pass's scratch (geo[1],
+// tables[1]), but counts into slots of its own, so that arctic_stats and arctic_read_cull_counts keep describing the sun's pass; and
+// it never takes block owners, a sharded map or k_vertex's block culling (a vertex block's box is made of triangle boxes)
+constexpr uint32_t CUBE_COUNTER_SET = 4;   // its set of N_GEO_COUNTERS device counters
+constexpr uint32_t CUBE_COUNT_WORDS = 8;   // pinned words per face: [0] records, [1] work items, [2] overflow flag, [4] items of the atomic rasteriser (k_raster)
+struct DepthTarget {
+    uint32_t *map;                  // size x size floats
+    uint32_t size;
+    const float *clip_from_world;   // 16 floats, glm memory order
+    uint32_t *h_counts, *dh_counts; // CUBE_COUNT_WORDS pinned words: host and device address
+};
+
+// vertex -> clip/setup -> raster, shared by the forward prepass, the shadow pass and (cube != null) the faces of the point lights
+int run_geometry(ArcticRenderer *r, const ArcticScene *sc, bool shadow_pass, hipStream_t stream, const DepthTarget *cube = nullptr) {
     const int set = shadow_pass ? 1 : r->fwd();
+    const uint32_t cset = cube ? CUBE_COUNTER_SET : (uint32_t)set;   // counter set
     ArcticRenderer::GeoSet &G = r->geo[set];
+    const uint32_t S = cube ? cube->size : r->shadow_size;   // a depth target's side
+    uint32_t *depth_map = cube ? cube->map : r->d_shadow().as<uint32_t>();
     // the pass's target is cleared by the vertex kernel's launch (or by a fill when there is nothing to draw)
-    unsigned long long *clear = shadow_pass ? r->d_shadow().as<unsigned long long>() : r->d_vis().as<unsigned long long>();
+    unsigned long long *clear = shadow_pass ? reinterpret_cast<unsigned long long *>(depth_map) : r->d_vis().as<unsigned long long>();
     const unsigned long long clear_value = shadow_pass ? 0x3F8000003F800000ull : ~0ull;   // depth 1.0 (shadow_map_pass.cpp:124-131) / no triangle
-    const size_t clear_count = shadow_pass ? ((size_t)r->shadow_size * r->shadow_size + 1) / 2 : r->n_tiles() * TILE_PIXELS;
+    const size_t clear_count = shadow_pass ? ((size_t)S * S + 1) / 2 : r->n_tiles() * TILE_PIXELS;
     GeomParams gp;
     std::memset(&gp, 0, sizeof gp);
     sun_proj_view(sc->sun.position, sc->sun.rotation, gp.light_from_world);
     if (shadow_pass) {
-        std::memcpy(gp.clip_from_world, gp.light_from_world, sizeof gp.clip_from_world);
-        gp.vp_w = gp.vp_h = (float)r->shadow_size;
-        gp.sc_x0 = gp.sc_y0 = 0; gp.sc_x1 = gp.sc_y1 = (int32_t)r->shadow_size;
-        if (r->shadow_sharded && r->comm && r->comm_world > 1) {   // this rank's slice of the light-space rows; the all-gather follows the raster
+        std::memcpy(gp.clip_from_world, cube ? cube->clip_from_world : gp.light_from_world, sizeof gp.clip_from_world);
+        gp.vp_w = gp.vp_h = (float)S;
+        gp.sc_x0 = gp.sc_y0 = 0; gp.sc_x1 = gp.sc_y1 = (int32_t)S;
+        if (!cube && r->shadow_sharded && r->comm && r->comm_world > 1) {   // this rank's slice of the light-space rows; the all-gather follows the raster
             const uint32_t per = (r->shadow_size + (uint32_t)r->comm_world - 1) / (uint32_t)r->comm_world;
             gp.sc_y0 = (int32_t)std::min(r->shadow_size, per * (uint32_t)r->comm_rank);
             gp.sc_y1 = (int32_t)std::min(r->shadow_size, per * ((uint32_t)r->comm_rank + 1));
         }
         gp.cull_front = 1;                                       // shadow_map_pass.cpp:96-97
-        gp.tiles_x = (int32_t)((r->shadow_size + 7) / 8); gp.tile_y0 = 0; gp.pitch = (int32_t)r->shadow_size;
+        gp.tiles_x = (int32_t)((S + 7) / 8); gp.tile_y0 = 0; gp.pitch = (int32_t)S;
     } else {
         const ArcticCamera &c = sc->camera;
         camera_proj_view(c.eye, c.rotation, c.aspect, c.fov_y, c.z_near_far[0], c.z_near_far[1], gp.clip_from_world);
@@ -484,14 +509,14 @@ int run_geometry(ArcticRenderer *r, const ArcticScene *sc, bool shadow_pass, hip
         gp.band_tiles = (int32_t)(r->band_rows / TILE); gp.shard_index = (int32_t)r->shard_index; gp.shard_count = (int32_t)r->shard_count;
     }
     gp.raster_flags = ((r->debug & 32) ? 1 : 0) | ((r->debug & 1024) ? 2 : 0);
-    gp.tiles_y = shadow_pass ? (int32_t)((r->shadow_size + 7) / 8) : (int32_t)r->tiles_y;
+    gp.tiles_y = shadow_pass ? (int32_t)((S + 7) / 8) : (int32_t)r->tiles_y;
     // block ownership (ARCTIC_OPT_RASTER_OWNER; default -1 = the choice below): the blocks are written once by their owners, so nothing is cleared
     // the library's choice: the forward pass of a handle that owns 4 Mpx or more -- three launches instead of one cost ~12 us of fixed
     // time, what the atomics cost grows with the pixels.  Whole frames with / without owners: 4K 0.283 / 0.304 ms, one rank of R = 2 at 4K
     // (4.1 Mpx) 0.178 / 0.184, of R = 4 0.136 / 0.130, of R = 8 0.106 / 0.102; config 3 at 1080p 0.113 / 0.114, config 2 (1080p, dense
     // meshes: 14 % of the items beyond their bins) 0.106 / 0.093, config 1 (512^2) 0.064 / 0.038;
     // never the shadow pass (instruction bound, two thirds of its blocks empty: 0.124 -> 0.163 ms)
-    const bool owned = r->raster_owner < 0 ? (!shadow_pass && (uint64_t)r->rows() * r->width >= 4000000ull) : (r->raster_owner & (shadow_pass ? 2 : 1)) != 0;
+    const bool owned = cube ? false : r->raster_owner < 0 ? (!shadow_pass && (uint64_t)r->rows() * r->width >= 4000000ull) : (r->raster_owner & (shadow_pass ? 2 : 1)) != 0;
     // owners beside the small-triangle path: the map is cleared as without owners, k_setup draws the small triangles into it, the owners MERGE their bins into it
     const bool merge = owned && shadow_pass && r->small_triangles && !(r->debug & 32);
     BinTables B{};
@@ -506,23 +531,25 @@ int run_geometry(ArcticRenderer *r, const ArcticScene *sc, bool shadow_pass, hip
         B.count = G.d_bin_count.as<uint32_t>(); B.slots = G.d_bin_slots.as<uint32_t>();
         B.count_all = (r->debug & 512) ? 1u : 0u;
         G.bins_x = B.blocks_x; G.bins_y = B.n_blocks / B.blocks_x;
-    } else G.bins_x = G.bins_y = 0;
+    } else if (!cube) G.bins_x = G.bins_y = 0;
     PassTables &T = r->tables[set];
     uint32_t n_objs, n_xverts, n_src, n_vblocks, n_tblocks;
     int rc = upload_pass_tables(r, T, G.d_xverts, stream, gp, sc, n_objs, n_xverts, n_src, n_vblocks, n_tblocks);
     if (rc != ARCTIC_OK) return rc;
     const GeomParams &d_gp = T.gp;
+    uint32_t *hc = cube ? cube->h_counts : r->h_counts + (shadow_pass ? 2 : 0);   // [0] records, [1] work items of the latest pass into this target
     if (n_objs == 0 || n_src == 0 || n_vblocks == 0) {
-        r->h_counts[shadow_pass ? 2 : 0] = r->h_counts[shadow_pass ? 3 : 1] = 0;
+        hc[0] = hc[1] = 0;
         HIPCHECK(r, launch_fill_u64(clear, clear_value, clear_count, stream));
         return ARCTIC_OK;
     }
     const ObjectRec *objs = T.objs;
-    G.n_tblocks = n_tblocks; G.n_vblocks = n_vblocks; G.cull_counted = (r->debug & 1024) != 0;
-    if (G.cull_counted) HIPCHECK(r, hipMemsetAsync(r->d_geo_counters.as<uint32_t>() + N_GEO_COUNTERS * set + 6, 0, 4, stream));   // (k_vertex counts into it from its first workgroup on)
+    const bool count_culls = (r->debug & 1024) != 0;
+    if (!cube) { G.n_tblocks = n_tblocks; G.n_vblocks = n_vblocks; G.cull_counted = count_culls; }
+    if (count_culls) HIPCHECK(r, hipMemsetAsync(r->d_geo_counters.as<uint32_t>() + N_GEO_COUNTERS * cset + 6, 0, 4, stream));   // (k_vertex counts into it from its first workgroup on)
     HIPCHECK(r, launch_vertex(objs, T.vblock_obj, T.vblock_first, n_vblocks, d_gp, G.d_xverts.as<XVert>(), shadow_pass ? 1 : 0,
-                              r->d_geo_counters.as<uint32_t>() + N_GEO_COUNTERS * set, clear, clear_value, (owned && !merge) ? 0 : clear_count, B.count, owned ? B.n_blocks : 0,
-                              (r->cluster_cull & 2) ? T.vblock_bounds : nullptr, stream));
+                              r->d_geo_counters.as<uint32_t>() + N_GEO_COUNTERS * cset, clear, clear_value, (owned && !merge) ? 0 : clear_count, B.count, owned ? B.n_blocks : 0,
+                              (r->cluster_cull & 2) && !cube ? T.vblock_bounds : nullptr, stream));
     // Record slots: a triangle clipped against 6 planes yields at most 7 triangles, so 7 * n_src slots can never overflow.
     // Records and work items are allocated on the device from two counters (k_setup): no count pass, no scan, and neither
     // count has to come back to the host -- the frame stays asynchronous.
@@ -534,7 +561,7 @@ int run_geometry(ArcticRenderer *r, const ArcticScene *sc, bool shadow_pass, hip
     // work-item table: explicit (record, 16x16 block) pairs.  Its size follows the largest count seen so far (pinned
     // h_counts, refreshed asynchronously each pass) with 4x headroom; an overflow drops work, is flagged by the kernel and
     // reported by the next call that synchronises (arctic_flush / read-backs) -- and the table has grown by then.
-    const uint64_t want = std::max<uint64_t>(r->item_cap_floor, 4ull * r->h_counts[shadow_pass ? 3 : 1]);
+    const uint64_t want = std::max<uint64_t>(r->item_cap_floor, 4ull * hc[1]);
     if (want > G.item_cap) {
         HIPCHECK(r, G.d_items.ensure((size_t)want * 8));
         G.item_cap = (uint32_t)std::min<uint64_t>(want, 0x7FFFFFF0ull);
@@ -544,15 +571,15 @@ int run_geometry(ArcticRenderer *r, const ArcticScene *sc, bool shadow_pass, hip
     HIPCHECK(r, G.d_rrecs.ensure((size_t)n_slots * sizeof(RasterRec)));
     HIPCHECK(r, G.d_rec_of.ensure((size_t)n_src * 8 * 4));
     HIPCHECK(r, G.d_clip_list.ensure((size_t)n_src * 8));
-    uint32_t *counters = r->d_geo_counters.as<uint32_t>() + N_GEO_COUNTERS * set;   // zeroed by k_vertex
+    uint32_t *counters = r->d_geo_counters.as<uint32_t>() + N_GEO_COUNTERS * cset;   // zeroed by k_vertex
     HIPCHECK(r, launch_setup(objs, T.tblock_obj, T.tblock_first, n_tblocks, d_gp, G.d_xverts.as<XVert>(), G.d_recs.as<SetupRec>(),
                              G.d_rrecs.as<RasterRec>(), G.d_rec_of.as<uint32_t>(), G.d_items.as<uint2>(), G.item_cap, n_slots, counters,
                              G.d_clip_list.as<uint2>(), (r->cluster_cull & 1) ? T.tblock_bounds : nullptr,
                              // (block owners STORE their blocks -- that store is the clear --, so nothing may be drawn before them unless they merge)
-                             shadow_pass && (!owned || merge) && r->small_triangles ? r->d_shadow().as<uint32_t>() : nullptr, stream));
+                             shadow_pass && (!owned || merge) && r->small_triangles ? depth_map : nullptr, stream));
     // counts for arctic_stats() and the overflow flag: k_raster stores them into pinned, mapped memory (no copy launches between
     // the kernels); looked at only when the stream has been synchronised
-    uint32_t *dh = r->dh_counts + (shadow_pass ? 2 : 0), *dh_overflow = r->dh_counts + 4 + (shadow_pass ? 1 : 0);
+    uint32_t *dh = cube ? cube->dh_counts : r->dh_counts + (shadow_pass ? 2 : 0), *dh_overflow = cube ? cube->dh_counts + 2 : r->dh_counts + 4 + (shadow_pass ? 1 : 0);
     uint32_t grid = r->raster_blocks[shadow_pass ? 1 : 0];
     const uint2 *draw = G.d_items.as<uint2>();
     if (owned) {
@@ -566,7 +593,7 @@ int run_geometry(ArcticRenderer *r, const ArcticScene *sc, bool shadow_pass, hip
     }
     if (shadow_pass)
         HIPCHECK(r, launch_raster_depth(G.d_recs.as<SetupRec>(), G.d_rrecs.as<RasterRec>(), draw, G.item_cap, counters, grid, d_gp,
-                                        r->d_shadow().as<uint32_t>(), dh, dh_overflow, owned, stream));
+                                        depth_map, dh, dh_overflow, owned, stream));
     else
         HIPCHECK(r, launch_raster_vis(G.d_recs.as<SetupRec>(), G.d_rrecs.as<RasterRec>(), draw, G.item_cap, counters, grid, d_gp,
                                       r->d_vis().as<unsigned long long>(), dh, dh_overflow, owned, stream));
@@ -606,6 +633,33 @@ int pass_shadow_map(ArcticRenderer *r, const ArcticScene *sc, hipStream_t stream
         if (nrc != 0) return r->fail(ARCTIC_E_DEVICE, "ncclAllGather(shadow map): %s", g_rccl.why(nrc));
     }
     return ARCTIC_OK;
+}
+
+// the faces of every shadow-casting point light (arctic_update_point_shadow_lights), 6 per light, each run_geometry's depth-only pass with
+// the face's matrix (host_math.cpp point_shadow_proj_view).  On the pass's stream behind the shadow scratch's guard, like the sun's map:
+// whole frames call it on the main stream, so the faces are redrawn after the previous frame's shading has read them
+float *cube_faces(ArcticRenderer *r) { return reinterpret_cast<float *>(r->d_cubes.as<char>() + (size_t)r->n_cubes * sizeof(CubeDev)); }
+int pass_point_shadows(ArcticRenderer *r, const ArcticScene *sc, hipStream_t stream) {
+    if (!r->n_cubes) return ARCTIC_OK;
+    Range zone("Point Shadow Pass");
+    if (r->shadow_scratch_valid && r->shadow_scratch_stream != stream)   // the previous shadow pass ran on another stream: it owns the scratch until it ends
+        HIPCHECK(r, hipStreamWaitEvent(stream, r->ev_shadow_scratch, 0));
+    const size_t texels = (size_t)r->cube_size * r->cube_size;
+    int rc = ARCTIC_OK;
+    for (uint32_t i = 0; i < r->n_cubes && rc == ARCTIC_OK; ++i) {
+        const ArcticPointShadowLight &l = r->cube_lights[i];
+        for (int k = 0; k < 6 && rc == ARCTIC_OK; ++k) {
+            float m[16];
+            point_shadow_proj_view(l.position, k, l.z_near, l.z_far, m);
+            const size_t j = (size_t)i * 6 + k;
+            const DepthTarget t = {reinterpret_cast<uint32_t *>(cube_faces(r) + j * texels), r->cube_size, m,
+                                   r->h_cube_counts + CUBE_COUNT_WORDS * j, r->dh_cube_counts + CUBE_COUNT_WORDS * j};
+            rc = run_geometry(r, sc, true, stream, &t);
+        }
+    }
+    HIPCHECK(r, hipEventRecord(r->ev_shadow_scratch, stream));
+    r->shadow_scratch_stream = stream; r->shadow_scratch_valid = true;
+    return rc;
 }
 
 // visibility only: vertex -> setup -> raster of the camera view
@@ -695,6 +749,8 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
         return r->fail(ARCTIC_E_STATE, "shade: ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply to the image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map)");
     if (r->n_spots && (r->count_evals || r->tile_trace))
         return r->fail(ARCTIC_E_STATE, "shade: ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply with spot lights (arctic_update_spot_lights)");
+    if (r->n_cubes && (r->count_evals || r->tile_trace))
+        return r->fail(ARCTIC_E_STATE, "shade: ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply with shadow-casting point lights (arctic_update_point_shadow_lights)");
     std::memset(&sp, 0, sizeof sp);
     sp.g = r->gbuffer();
     const ArcticRenderer::GeoSet &G = r->geo[r->fwd()];
@@ -734,9 +790,10 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
         sp.trace = r->d_tile_trace.as<unsigned long long>();
     }
     if (r->n_spots) { sp.spots = r->d_spots.as<float4>(); sp.n_spots = r->n_spots; }   // (the statistics' slot: k_spotlit* keep none)
+    if (r->n_cubes) { sp.cubes = r->d_cubes.as<float4>(); sp.n_cubes = r->n_cubes; sp.cube_size = r->cube_size; }   // (the trace's slot: k_cubelit* keep none)
     // (the order was built for groups of order_group tiles per wave: a pass that shades another number per wave takes the geometric order)
     if (r->env_active()) sp.env_tables = r->d_env_tables.as<EnvTables>();   // (the geometric order: the tables take the order's slot)
-    else if (r->n_spots) {}                                                  // (k_spotlit*: the geometric order)
+    else if (r->n_spots || r->n_cubes) {}                                    // (k_spotlit*, k_cubelit*: the geometric order)
     else if (!from_vis && r->have_order && r->tile_order && (r->tiles_per_wave == 0 || r->tiles_per_wave == r->order_group)) {
         sp.tile_order = r->d_tile_order.as<uint32_t>(); sp.n_jobs = r->order_slots; sp.tiles_per_wave = r->order_group;
     }
@@ -769,6 +826,7 @@ hipError_t shade_once(ArcticRenderer *r, const ShadeParams &sp, bool from_vis, b
     L.tiles_per_wave = r->tiles_per_wave;
     L.env = r->env_active() ? 1u : 0u;
     L.spot = sp.n_spots ? 1u : 0u;
+    L.cube = sp.n_cubes ? 1u : 0u;
     return launch_shade(sp, L);
 }
 
@@ -809,11 +867,30 @@ std::vector<uint8_t> shadow_inputs(const ArcticRenderer *r, const ArcticScene *s
     return k;
 }
 
+// everything the point lights' faces are a function of, as bytes (shadow_inputs' rule)
+std::vector<uint8_t> cube_inputs(const ArcticRenderer *r, const ArcticScene *sc) {
+    std::vector<uint8_t> k;
+    if (!r->n_cubes) return k;
+    auto put = [&](const void *p, size_t n) { const uint8_t *b = static_cast<const uint8_t *>(p); k.insert(k.end(), b, b + n); };
+    const uint64_t head[6] = {r->cube_size, r->n_cubes, (uint64_t)r->meshes.size(), sc->n_objects, (uint64_t)r->cluster_cull, (uint64_t)r->small_triangles};
+    put(head, sizeof head);
+    put(r->cube_lights.data(), r->cube_lights.size() * sizeof(ArcticPointShadowLight));
+    for (uint64_t i = 0; i < sc->n_objects; ++i) { put(sc->objects[i].trs, sizeof sc->objects[i].trs); put(&sc->objects[i].mesh_idx, sizeof sc->objects[i].mesh_idx); }
+    return k;
+}
+
 // after a stream synchronisation: did a rasteriser pass run out of work-item slots?  (k_setup flags it; the table is re-sized
 // from the counts of that very pass, so rendering the frame again succeeds)
 int check_item_overflow(ArcticRenderer *r) {
-    if (!r->h_counts || !(r->h_counts[4] | r->h_counts[5])) return ARCTIC_OK;
-    const uint32_t need = std::max(r->h_counts[1], r->h_counts[3]);
+    bool cube_overflow = false;   // a face of a point light (pass_point_shadows: its own slots)
+    uint32_t need = 0;
+    for (uint32_t j = 0; r->h_cube_counts && j < r->n_cubes * 6; ++j) {
+        uint32_t *c = r->h_cube_counts + CUBE_COUNT_WORDS * j;
+        if (c[2]) { cube_overflow = true; need = std::max(need, c[1]); c[2] = 0; }
+    }
+    if (cube_overflow) r->cube_key.clear();
+    if (!r->h_counts || !(r->h_counts[4] | r->h_counts[5] | (cube_overflow ? 1u : 0u))) return ARCTIC_OK;
+    need = std::max(need, std::max(r->h_counts[1], r->h_counts[3]));
     r->h_counts[4] = r->h_counts[5] = 0;
     r->recs_worst_case = true;   // whichever table it was: the record table takes its worst-case size from now on
     r->have_gbuffer = false; r->have_output = false; r->have_vis = false; r->have_order = false; r->shadow_key.clear();
@@ -828,7 +905,7 @@ bool valid_scene(const ArcticScene *sc) { return sc && (sc->n_objects == 0 || sc
 // =================================================================================================
 extern "C" {
 
-int arctic_version(void) { return 200; }
+int arctic_version(void) { return 300; }
 
 ArcticRenderer *arctic_create(const ArcticCreateInfo *info, char *err, uint64_t err_len) {
     auto say = [&](const char *m) { if (err && err_len) { std::snprintf(err, (size_t)err_len, "%s", m); } };
@@ -914,6 +991,7 @@ void arctic_destroy(ArcticRenderer *r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
     if (r->h_counts) (void)hipHostFree(r->h_counts);
+    if (r->h_cube_counts) (void)hipHostFree(r->h_cube_counts);
     (void)hipStreamSynchronize(r->stream);
     (void)arctic_comm_destroy(r);
     if (r->shadow_stream) { (void)hipStreamSynchronize(r->shadow_stream); (void)hipStreamDestroy(r->shadow_stream); }
@@ -927,7 +1005,7 @@ void arctic_destroy(ArcticRenderer *r) {
     if (r->own_stream) { (void)hipStreamSynchronize(r->own_stream); (void)hipStreamDestroy(r->own_stream); }
     for (Mesh &m : r->meshes) { if (m.d_vertices) (void)hipFree(m.d_vertices); if (m.d_indices) (void)hipFree(m.d_indices); }
     for (void *p : r->tex_allocs) (void)hipFree(p);
-    DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_spots, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4,
+    DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_spots, &r->d_cubes, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4,
                       &r->d_rgba8, &r->d_ldr, &r->d_hdr, &r->d_counter, &r->d_shadow_blocks_set[0], &r->d_shadow_blocks_set[1], &r->d_shadow_bounds_set[0], &r->d_shadow_bounds_set[1], &r->d_staging, &r->d_layout, &r->geo[0].d_xverts, &r->geo[1].d_xverts, &r->geo[2].d_xverts,
                       &r->geo[2].d_recs, &r->geo[2].d_rrecs, &r->geo[2].d_clip_list, &r->geo[2].d_rec_of, &r->geo[2].d_items, &r->tables[2].d,
                       &r->geo[3].d_xverts, &r->geo[3].d_recs, &r->geo[3].d_rrecs, &r->geo[3].d_clip_list, &r->geo[3].d_rec_of, &r->geo[3].d_items, &r->geo[3].d_left, &r->geo[3].d_bin_count, &r->geo[3].d_bin_slots, &r->tables[3].d,
@@ -1153,6 +1231,114 @@ int arctic_update_spot_lights(ArcticRenderer *r, const ArcticSpotLight *lights, 
     return ARCTIC_OK;
 }
 
+// ---- shadow-casting point lights (include/arctic_hip.h) ----------------------------------------------------------------
+namespace {
+bool valid_cube_light(const ArcticPointShadowLight &l) {
+    const float *f = l.position;   // 8 floats, no padding
+    for (int k = 0; k < 8; ++k) if (!std::isfinite(f[k])) return false;
+    return l.z_near > 0.0f && l.z_near < l.z_far;
+}
+// room for k lights with faces of F^2 texels; the faces cleared to 1.0 and the records (binary64, each rounded once) uploaded.  A failed
+// allocation leaves the handle's buffer and list as they were.  The caller has synchronised the stream.
+int cube_store(ArcticRenderer *r, const ArcticPointShadowLight *lights, uint32_t k, uint32_t F) {
+    const size_t rec_bytes = (size_t)k * sizeof(CubeDev), bytes = rec_bytes + (size_t)k * 6 * F * F * 4;
+    if (bytes > r->d_cubes.cap) {
+        void *p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return r->fail(ARCTIC_E_DEVICE, "point shadows: cannot allocate %zu bytes of faces", bytes); }
+        r->d_cubes.release();
+        r->d_cubes.p = p; r->d_cubes.cap = bytes;
+    }
+    if ((size_t)k * 6 > r->cube_count_faces) {   // pinned, mapped counts: 8 words per face
+        uint32_t *h = nullptr, *dh = nullptr;
+        const size_t n = (size_t)std::max<uint32_t>(k, r->max_lights) * 6;
+        if (hipHostMalloc((void **)&h, n * CUBE_COUNT_WORDS * 4, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&dh, h, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            if (h) (void)hipHostFree(h);
+            return r->fail(ARCTIC_E_DEVICE, "point shadows: cannot allocate the pinned counters");
+        }
+        std::memset(h, 0, n * CUBE_COUNT_WORDS * 4);
+        if (r->h_cube_counts) (void)hipHostFree(r->h_cube_counts);
+        r->h_cube_counts = h; r->dh_cube_counts = dh; r->cube_count_faces = (uint32_t)n;
+    }
+    std::vector<CubeDev> dev(k);
+    for (uint32_t i = 0; i < k; ++i) {
+        const ArcticPointShadowLight &l = lights[i];
+        CubeDev &d = dev[i];
+        for (int c = 0; c < 3; ++c) { d.p[c] = l.position[c]; d.c[c] = l.color[c]; }
+        d.pz_scale = (float)((double)l.z_far / ((double)l.z_far - (double)l.z_near));
+        d.zn = l.z_near;
+    }
+    HIPCHECK(r, hipMemcpy(r->d_cubes.p, dev.data(), rec_bytes, hipMemcpyHostToDevice));
+    HIPCHECK(r, launch_fill_u64(reinterpret_cast<unsigned long long *>(r->d_cubes.as<char>() + rec_bytes), 0x3F8000003F800000ull, (size_t)k * 3 * F * F, r->stream));
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    return ARCTIC_OK;
+}
+}  // namespace
+
+int arctic_point_shadow_matrices(const ArcticPointShadowLight *light, float *out96) {
+    if (!light || !out96 || !valid_cube_light(*light)) return ARCTIC_E_INVALID;
+    for (int k = 0; k < 6; ++k) point_shadow_proj_view(light->position, k, light->z_near, light->z_far, out96 + 16 * k);
+    return ARCTIC_OK;
+}
+
+int arctic_update_point_shadow_lights(ArcticRenderer *r, const ArcticPointShadowLight *lights, uint64_t n) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (n && !lights) return r->fail(ARCTIC_E_INVALID, "update_point_shadow_lights: null");
+    // (every light given is checked, also those beyond the cap; on failure the handle's list and faces stay as they were)
+    for (uint64_t i = 0; i < n; ++i)
+        if (!valid_cube_light(lights[i]))
+            return r->fail(ARCTIC_E_INVALID, "update_point_shadow_lights: light %llu: a NaN or inf field, z_near <= 0 or z_far <= z_near", (unsigned long long)i);
+    const uint32_t k = (uint32_t)std::min<uint64_t>(n, r->max_lights);
+    int rc = select_device(r);
+    if (rc) return rc;
+    HIPCHECK(r, hipStreamSynchronize(r->stream));   // (a pass in flight may still read the faces it replaces)
+    if (k) {
+        r->n_cubes = 0;   // (cube_store's layout: records of the new list first)
+        rc = cube_store(r, lights, k, r->cube_size);
+        if (rc != ARCTIC_OK) {   // the previous records and faces are untouched unless the buffer was reused: put the old list back
+            if (!r->cube_lights.empty()) r->n_cubes = (uint32_t)r->cube_lights.size();
+            return rc;
+        }
+    }
+    r->cube_lights.assign(lights, lights + k);
+    r->n_cubes = k;
+    r->cube_key.clear();
+    return ARCTIC_OK;
+}
+
+int arctic_pass_point_shadows(ArcticRenderer *r, const ArcticScene *scene) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "pass_point_shadows: bad scene");
+    int rc = select_device(r);
+    if (rc) return rc;
+    r->cube_key.clear();   // an explicit pass always draws; render_frame's cache starts over
+    return pass_point_shadows(r, scene, r->stream);
+}
+
+int arctic_read_point_shadow(ArcticRenderer *r, uint32_t light, float *faces) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!faces || light >= r->n_cubes) return r->fail(ARCTIC_E_INVALID, "read_point_shadow: null, or light %u of %u", light, r->n_cubes);
+    int rc = select_device(r);
+    if (rc) return rc;
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    if (int ov = check_item_overflow(r)) return ov;
+    const size_t n = (size_t)6 * r->cube_size * r->cube_size;
+    HIPCHECK(r, hipMemcpy(faces, cube_faces(r) + light * n, n * 4, hipMemcpyDeviceToHost));
+    return ARCTIC_OK;
+}
+
+int arctic_write_point_shadow(ArcticRenderer *r, uint32_t light, const float *faces) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!faces || light >= r->n_cubes) return r->fail(ARCTIC_E_INVALID, "write_point_shadow: null, or light %u of %u", light, r->n_cubes);
+    int rc = select_device(r);
+    if (rc) return rc;
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    const size_t n = (size_t)6 * r->cube_size * r->cube_size;
+    HIPCHECK(r, hipMemcpy(cube_faces(r) + light * n, faces, n * 4, hipMemcpyHostToDevice));
+    r->cube_key.clear();
+    return ARCTIC_OK;
+}
+
 int arctic_create_hdri(ArcticRenderer *r, const float *rgba32f, uint32_t w, uint32_t h) {
     if (!r) return ARCTIC_E_INVALID;
     if (!rgba32f || !w || !h) return r->fail(ARCTIC_E_INVALID, "create_hdri: null image or zero size");
@@ -1252,6 +1438,17 @@ int arctic_render_frame_device(ArcticRenderer *r, const ArcticScene *scene, cons
     } else rc = vis_path ? pass_visibility(r, scene, r->stream) : pass_gbuffer(r, scene);
     if (beside) HIPCHECK(r, hipStreamWaitEvent(r->stream, r->ev_shadow, 0));   // the map and its table are complete
     if (rc != ARCTIC_OK) return rc;
+    // the point lights' faces: redrawn when their inputs changed, on the main stream -- behind the previous frame's shading, which reads
+    // the one set of faces, and in front of this frame's
+    if (r->n_cubes) {
+        std::vector<uint8_t> ckey = cube_inputs(r, scene);
+        if (!r->shadow_cache || ckey != r->cube_key) {
+            r->cube_key.clear();
+            rc = pass_point_shadows(r, scene, r->stream);
+            if (rc != ARCTIC_OK) return rc;
+            r->cube_key.swap(ckey);
+        }
+    }
     return pass_shade(r, scene, settings, d_out, vis_path);
 }
 
@@ -1590,6 +1787,19 @@ int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
     case ARCTIC_OPT_RASTER_OWNER: r->raster_owner = value < 0 ? -1 : (int)(value & 3); r->shadow_key.clear(); break;
     case ARCTIC_OPT_SHADOW_CACHE: r->shadow_cache = value != 0; r->shadow_key.clear(); break;
     case ARCTIC_OPT_SHADOW_SHARDED: r->shadow_sharded = value != 0; r->shadow_key.clear(); break;
+    case ARCTIC_OPT_POINT_SHADOW_SIZE: {
+        if (value < 8 || value > 4096 || value % 8 != 0) return r->fail(ARCTIC_E_INVALID, "ARCTIC_OPT_POINT_SHADOW_SIZE: a multiple of 8 in [8, 4096]");
+        if ((uint32_t)value == r->cube_size) break;
+        if (r->n_cubes) {
+            int rc = select_device(r);
+            if (rc) return rc;
+            HIPCHECK(r, hipStreamSynchronize(r->stream));
+            rc = cube_store(r, r->cube_lights.data(), r->n_cubes, (uint32_t)value);
+            if (rc != ARCTIC_OK) return rc;
+        }
+        r->cube_size = (uint32_t)value; r->cube_key.clear();
+        break;
+    }
     case ARCTIC_OPT_ENV_LIGHTING:
         if (value < 0 || value > 1) return r->fail(ARCTIC_E_INVALID, "ARCTIC_OPT_ENV_LIGHTING: 0 or 1");
         r->env_lighting = (int)value;

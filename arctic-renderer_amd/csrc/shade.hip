@@ -810,7 +810,63 @@ __device__ __forceinline__ void spot_sums(SP sp, const LoopPix &px, float A[3], 
         C[0] = __builtin_fmaf(cr, s3, C[0]); C[1] = __builtin_fmaf(cg, s3, C[1]); C[2] = __builtin_fmaf(cb, s3, C[2]);
     }
 }
-template <int LOOP, bool STATS, bool SPOT = false>
+// CUBE (k_cubelit*): behind the spot lights, the shadow-casting point lights join the scalar sums through cube_sums.
+// ---- shadow-casting point lights (arctic_update_point_shadow_lights; semantics in include/arctic_hip.h): one scalar loop, 2 float4 per
+// light through the scalar cache, {p.xyz, zf / (zf - zn)} {rgb, zn} (common.h CubeDev), the faces behind the records.  The colour is scaled
+// by the visibility v of the light's cube (2 x 2 comparison PCF, fp32 weights) and then goes through exactly the point light's arithmetic:
+// where v = 1 the light adds the bits a point light at its place adds, where v = 0 it adds nothing.
+// Lanes with n.d <= 0 read no texel (their term is zero); a light is skipped when no lit lane of the wave has n.d > 0 and v > 0.
+__device__ __forceinline__ float cube_visibility(const float *faces /* this light's 6 faces, wave-uniform */, uint32_t F, f3 d /* world - p */,
+                                                 float pz_scale, float zn) {
+    const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+    float m, sd, ud;
+    uint32_t face;
+    if (ax >= ay && ax >= az) { m = ax; face = d.x >= 0.0f ? 0u : 1u; sd = d.x >= 0.0f ? -d.z : d.z; ud = -d.y; }   // ties: x, then y, then z
+    else if (ay >= az) { m = ay; face = d.y >= 0.0f ? 2u : 3u; sd = d.x; ud = d.y >= 0.0f ? d.z : -d.z; }
+    else { m = az; face = d.z >= 0.0f ? 4u : 5u; sd = d.z >= 0.0f ? d.x : -d.x; ud = -d.y; }
+    if (!(m > zn)) return 1.0f;                                   // inside the near plane: no lookup
+    const float im = 1.0f / m;
+    const float pz = pz_scale * (1.0f - zn * im);
+    if (pz > 1.0f) return 1.0f;                                   // beyond the far plane: outside the map, no shadow (forward.hlsl:76)
+    const float hf = 0.5f * (float)F;
+    const float x = __builtin_fmaf(sd * im, hf, hf - 0.5f), y = __builtin_fmaf(-(ud * im), hf, hf - 0.5f);   // px F - 0.5, py F - 0.5
+    const float x0 = floorf(x), y0 = floorf(y);
+    const float fx = x - x0, fy = y - y0;
+    const int32_t last = (int32_t)F - 1, ix = (int32_t)x0, iy = (int32_t)y0;
+    const uint32_t c0 = (uint32_t)min(max(ix, 0), last), c1 = (uint32_t)min(max(ix + 1, 0), last);
+    const uint32_t r0 = (uint32_t)min(max(iy, 0), last) * F, r1 = (uint32_t)min(max(iy + 1, 0), last) * F;
+    const uint32_t base = face * F * F;                           // < 2^27 texels at F = 4096
+    const float t00 = __uint_as_float(gload_u32(faces, (base + r0 + c0) * 4u)), t10 = __uint_as_float(gload_u32(faces, (base + r0 + c1) * 4u));
+    const float t01 = __uint_as_float(gload_u32(faces, (base + r1 + c0) * 4u)), t11 = __uint_as_float(gload_u32(faces, (base + r1 + c1) * 4u));
+    const float s00 = pz > t00 ? 1.0f : 0.0f, s10 = pz > t10 ? 1.0f : 0.0f, s01 = pz > t01 ? 1.0f : 0.0f, s11 = pz > t11 ? 1.0f : 0.0f;
+    return 1.0f - lerp_exact(lerp_exact(s00, s10, fx), lerp_exact(s01, s11, fx), fy);
+}
+__device__ __forceinline__ void cube_sums(SP sp, const LoopPix &px, float A[3], float B[3], float C[3]) {
+    const uint32_t n_cubes = sp.n_cubes, F = sp.cube_size;
+    typedef const f4v __attribute__((address_space(4))) *const_f4;   // wave-uniform: scalar loads (see the point loop)
+    const const_f4 L = (const_f4)sp.cubes;
+    const float *faces = reinterpret_cast<const float *>(sp.cubes + CUBE_F4 * n_cubes);
+    const bool cull = sp.culling != 0;
+    for (uint32_t i = 0; i < n_cubes; ++i) {
+        const f4v a = L[CUBE_F4 * i], c = L[CUBE_F4 * i + 1];
+        const f3 dl = mk(a.x, a.y, a.z) - px.world;
+        const float ndl = dot(px.n, dl);
+        const bool front = ndl > 0.0f;
+        float v = 1.0f;
+        if (front) v = cube_visibility(faces + (size_t)i * 6 * F * F, F, mk(-dl.x, -dl.y, -dl.z), a.w, c.w);
+        if (cull) {
+            if (__ballot(front && v > 0.0f) == 0ull) continue;   // wave-uniform
+            if (!front || v == 0.0f) continue;                   // this lane's term is exactly zero (the point loop's per-lane skip)
+        }
+        const float cr = c.x * v, cg = c.y * v, cb = c.z * v;
+        float s1, s2, s3;
+        light_scalars<true>(px, dl, ndl, s1, s2, s3);
+        A[0] = __builtin_fmaf(cr, s1, A[0]); A[1] = __builtin_fmaf(cg, s1, A[1]); A[2] = __builtin_fmaf(cb, s1, A[2]);
+        B[0] = __builtin_fmaf(cr, s2, B[0]); B[1] = __builtin_fmaf(cg, s2, B[1]); B[2] = __builtin_fmaf(cb, s2, B[2]);
+        C[0] = __builtin_fmaf(cr, s3, C[0]); C[1] = __builtin_fmaf(cg, s3, C[1]); C[2] = __builtin_fmaf(cb, s3, C[2]);
+    }
+}
+template <int LOOP, bool STATS, bool SPOT = false, bool CUBE = false>
 __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float ng, float nb, float rough, float metal, f3 base,
                                            const float4 &gc, const float4 &gd, const float4 &ge) {
     const f3 n = get_normal(nr, ng, nb, gc, gd, ge);
@@ -850,6 +906,7 @@ __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float
             S.c[0] = __builtin_fmaf(lc.x, s3, S.c[0]); S.c[1] = __builtin_fmaf(lc.y, s3, S.c[1]); S.c[2] = __builtin_fmaf(lc.z, s3, S.c[2]);
         }
         if (SPOT) spot_sums(sp, px, S.a, S.b, S.c);
+        if (CUBE) cube_sums(sp, px, S.a, S.b, S.c);
         Lo = resolve_sums(tp, S.a, S.b, S.c);
     } else {
         Sums2 S;
@@ -902,6 +959,7 @@ __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float
             }
         }
         if (SPOT) spot_sums(sp, px, A, Bs, Cs);
+        if (CUBE) cube_sums(sp, px, A, Bs, Cs);
         Lo = resolve_sums(tp, A, Bs, Cs);
     }
     if (STATS) {
@@ -1084,8 +1142,8 @@ __device__ __forceinline__ bool shade_tile_fast(SP sp, KernArgs args, const Args
 // materials with images of unequal sizes, the 25-tap shadow test, the debug / timing options --------------------------------
 // ENV (k_envlit*): every covered pixel, shadowed or not, loads its second 48 bytes, normal, metalness and roughness and takes the
 // image-based ambient term instead of ambient * base; the light loop is still for lit pixels only.
-// SPOT (k_spotlit*): the light loop takes the spot lights too (lit_radiance<SPOT>).
-template <int LOOP, bool STATS, bool ENV = false, bool SPOT = false, class Second>
+// SPOT (k_spotlit*): the light loop takes the spot lights too (lit_radiance<SPOT>).  CUBE (k_cubelit*): ... and the shadow-casting point lights.
+template <int LOOP, bool STATS, bool ENV = false, bool SPOT = false, bool CUBE = false, class Second>
 __device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty, uint32_t tx,
                                            uint32_t lane, const TileHead &cur, Second second) {
     const uint32_t x = tx * 8 + (lane & 7);
@@ -1196,7 +1254,7 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty,
             color = env_ambient(sp.env_tables, n, wo, base, metal, rough) * sp.ambient;
         }
         if (!ENV || live) {
-            const f3 Lo = lit_radiance<LOOP, STATS, SPOT>(sp, lane, nr, ng, nb, rough, metal, base, gc, gd, ge);
+            const f3 Lo = lit_radiance<LOOP, STATS, SPOT, CUBE>(sp, lane, nr, ng, nb, rough, metal, base, gc, gd, ge);
             color = mk(__builtin_fmaf(Lo.x, lit, color.x), __builtin_fmaf(Lo.y, lit, color.y), __builtin_fmaf(Lo.z, lit, color.z));
         }
     }
@@ -1285,13 +1343,13 @@ __device__ __forceinline__ bool next_tile(const ArgsA &A, const OrderArgs &O, co
     return g < ((A.tiles_y + 7u) >> 3) && ty < A.tiles_y;
 }
 // The walk over a resident G-buffer, the body of every kernel of that pass.  PLAIN (k_material): a tile goes to the fast tile first, the
-// trace and the statistics are there, and the tiles come in the dispatch order when the prepass wrote one.  ENV / SPOT (k_envlit, k_spotlit):
-// every tile goes through shade_tile<ENV, SPOT> (the fast tile's early exit for shadowed pixels does not hold under ENV, and the fast tile
-// has no spot lights), in the geometric order (the order's slot holds the environment tables: ShadeParams::env_tables), with no statistics
+// trace and the statistics are there, and the tiles come in the dispatch order when the prepass wrote one.  ENV / SPOT / CUBE (k_envlit,
+// k_spotlit, k_cubelit): every tile goes through shade_tile<ENV, SPOT, CUBE> (the fast tile's early exit for shadowed pixels does not hold
+// under ENV, and the fast tile has no spot or shadow-casting point lights), in the geometric order (the order's slot holds the environment tables: ShadeParams::env_tables), with no statistics
 // and no trace.  A macro, not a device function: inlined through one more level, the walk comes out of the compiler with a few instructions
 // of k_material rescheduled.  `lut`: the kernel's sRGB table in LDS.
-#define WALK_GBUFFER(LOOP, STATS, ENV, SPOT)                                                                                                 \
-    constexpr bool PLAIN = !ENV && !SPOT;                                                                                                    \
+#define WALK_GBUFFER(LOOP, STATS, ENV, SPOT, CUBE)                                                                                           \
+    constexpr bool PLAIN = !ENV && !SPOT && !CUBE;                                                                                           \
     KernArgs args = kernel_args();                                                                                                           \
     unsigned long long t_entry = PLAIN ? trace_entry() : 0ull;                                                                               \
     const BlockId blk = block_id<1>();                                                                                                       \
@@ -1321,7 +1379,7 @@ _Pragma("nounroll")                                                             
             gc = gload_f4(pc + tile * 64, lane * 16u); gd = gload_f4(pd + tile * 64, lane * 16u); ge = gload_f4(pe + tile * 64, lane * 16u); \
         };                                                                                                                                   \
         const bool fast = PLAIN && shade_tile_fast<LOOP, STATS>(sp, args, A, lut, ty, tx, lane, cur, second);                                \
-        if (!fast) shade_tile<LOOP, STATS, ENV, SPOT>(sp, lut, ty, tx, lane, cur, second);                                                   \
+        if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE>(sp, lut, ty, tx, lane, cur, second);                                             \
         if (PLAIN) trace_end(sp, A, tile, fast);                                                                                             \
         if (++k >= A.T) break;                                                                                                               \
         asm volatile("" : "+s"(args));                                                                                                       \
@@ -1333,19 +1391,25 @@ _Pragma("nounroll")                                                             
 template <int LOOP, bool STATS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_material(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, STATS, false, false);
+    WALK_GBUFFER(LOOP, STATS, false, false, false);
 }
 // the image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map)
 template <int LOOP>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_envlit(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, false, true, false);
+    WALK_GBUFFER(LOOP, false, true, false, false);
 }
 // spot lights (arctic_update_spot_lights, a non-empty list); ENV: with the image-based ambient as well
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_spotlit(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, false, ENV, true);
+    WALK_GBUFFER(LOOP, false, ENV, true, false);
+}
+// shadow-casting point lights (arctic_update_point_shadow_lights, a non-empty list), with the spot list (may be empty); ENV as above
+template <int LOOP, bool ENV>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_cubelit(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    WALK_GBUFFER(LOOP, false, ENV, true, true);
 }
 
 // ---- the same without a G-buffer (whole frames): the tile walk straight from the visibility plane ----------------------
@@ -1353,10 +1417,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 // 4K) and reading it back costs more than interpolating again.  This walk reads the 8-byte visibility key, finds the
 // triangle, and interpolates uv + light-space position for every covered pixel and world position + tangent frame only
 // for the lit ones -- with the very operations of k_resolve (edges.h, fp contraction off), so the pixels are bit-identical
-// to the G-buffer path.  Everything after the attributes is shade_tile_fast / shade_tile, shared.  PLAIN, ENV and SPOT as in
-// WALK_GBUFFER (k_material_vis; k_envlit_vis, k_spotlit_vis), and a macro for the same reason.
-#define WALK_VIS(LOOP, STATS, ENV, SPOT)                                                                                                                            \
-    constexpr bool PLAIN = !ENV && !SPOT;                                                                                                                                            \
+// to the G-buffer path.  Everything after the attributes is shade_tile_fast / shade_tile, shared.  PLAIN, ENV, SPOT and CUBE as in
+// WALK_GBUFFER (k_material_vis; k_envlit_vis, k_spotlit_vis, k_cubelit_vis), and a macro for the same reason.
+#define WALK_VIS(LOOP, STATS, ENV, SPOT, CUBE)                                                                                                                      \
+    constexpr bool PLAIN = !ENV && !SPOT && !CUBE;                                                                                                                                   \
     KernArgs args = kernel_args();                                                                                                                                                   \
     unsigned long long t_entry = PLAIN ? trace_entry() : 0ull;                                                                                                                       \
     const BlockId blk = block_id<4>();                                                                                                                                               \
@@ -1472,7 +1536,7 @@ _Pragma("clang fp contract(off)")                                               
             }                                                                                                                                                                        \
         };                                                                                                                                                                           \
         const bool fast = PLAIN && shade_tile_fast<LOOP, STATS>(sp, args, A, lut, ty, tx, lane, cur, second);                                                                        \
-        if (!fast) shade_tile<LOOP, STATS, ENV, SPOT>(sp, lut, ty, tx, lane, cur, second);                                                                                           \
+        if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE>(sp, lut, ty, tx, lane, cur, second);                                                                                     \
         if (PLAIN) trace_end(sp, A, (size_t)ty * A.tiles_x + tx, fast);                                                                                                              \
         if (++k >= A.T) break;                                                                                                                                                       \
         asm volatile("" : "+s"(args));                                                                                                                                               \
@@ -1484,17 +1548,22 @@ _Pragma("clang fp contract(off)")                                               
 template <int LOOP, bool STATS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_material_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, STATS, false, false);
+    WALK_VIS(LOOP, STATS, false, false, false);
 }
 template <int LOOP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_envlit_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, false, true, false);
+    WALK_VIS(LOOP, false, true, false, false);
 }
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_spotlit_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, false, ENV, true);
+    WALK_VIS(LOOP, false, ENV, true, false);
+}
+template <int LOOP, bool ENV>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_cubelit_vis(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    WALK_VIS(LOOP, false, ENV, true, true);
 }
 
 // ---- shadow bounds: the conservative min/max table calculate_lit tests first -------------------------------------------
@@ -1539,14 +1608,18 @@ __global__ __launch_bounds__(256) void k_post_process(const float4 *__restrict__
 template <int LOOP, bool STATS>
 hipError_t launch_variant(const ShadeParams &sp, const ShadeLaunch &L, dim3 grid) {
     if (L.from_vis) {   // four-wave workgroups, a strip of 4 tiles each (block_id<4>)
-        if (L.spot && L.env) k_spotlit_vis<LOOP, true><<<grid, 256, 0, L.stream>>>(sp);
+        if (L.cube && L.env) k_cubelit_vis<LOOP, true><<<grid, 256, 0, L.stream>>>(sp);
+        else if (L.cube) k_cubelit_vis<LOOP, false><<<grid, 256, 0, L.stream>>>(sp);
+        else if (L.spot && L.env) k_spotlit_vis<LOOP, true><<<grid, 256, 0, L.stream>>>(sp);
         else if (L.spot) k_spotlit_vis<LOOP, false><<<grid, 256, 0, L.stream>>>(sp);
         else if (L.env) k_envlit_vis<LOOP><<<grid, 256, 0, L.stream>>>(sp);
         else k_material_vis<LOOP, STATS><<<grid, 256, 0, L.stream>>>(sp);
         return hipGetLastError();
     }
     grid.x = (grid.x + 7) / 8 * 32;   // one-wave workgroups (block_id<1>): four blocks per strip, a strip's blocks on one XCD
-    if (L.spot && L.env) k_spotlit<LOOP, true><<<grid, 64, 0, L.stream>>>(sp);
+    if (L.cube && L.env) k_cubelit<LOOP, true><<<grid, 64, 0, L.stream>>>(sp);
+    else if (L.cube) k_cubelit<LOOP, false><<<grid, 64, 0, L.stream>>>(sp);
+    else if (L.spot && L.env) k_spotlit<LOOP, true><<<grid, 64, 0, L.stream>>>(sp);
     else if (L.spot) k_spotlit<LOOP, false><<<grid, 64, 0, L.stream>>>(sp);
     else if (L.env) k_envlit<LOOP><<<grid, 64, 0, L.stream>>>(sp);
     else k_material<LOOP, STATS><<<grid, 64, 0, L.stream>>>(sp);
@@ -1570,7 +1643,7 @@ hipError_t launch_shade(const ShadeParams &sp_in, const ShadeLaunch &L) {
     const uint32_t bpr = (sp.tiles_x + 3) / 4, groups = (sp.tiles_y + 7) / 8;
     sp.group_stride = (groups + sp.tiles_per_wave - 1) / sp.tiles_per_wave;
     dim3 grid(8 * bpr, sp.group_stride);   // a block shades tiles_per_wave groups of 8 tile rows, group_stride groups apart
-    if (sp.tile_order && !L.env && !L.spot) // ... or tiles_per_wave consecutive slots of the prepass's dispatch order (n_jobs slots, common.h order_slot: a block = one XCD's list)
+    if (sp.tile_order && !L.env && !L.spot && !L.cube) // ... or tiles_per_wave consecutive slots of the prepass's dispatch order (n_jobs slots, common.h order_slot: a block = one XCD's list)
         grid = dim3((sp.n_jobs + sp.tiles_per_wave - 1) / sp.tiles_per_wave, 1);
     if (L.loop == 2) return L.stats ? launch_variant<2, true>(sp, L, grid) : launch_variant<2, false>(sp, L, grid);
     return L.stats ? launch_variant<1, true>(sp, L, grid) : launch_variant<1, false>(sp, L, grid);

@@ -29,6 +29,7 @@ using Object = ArcticObject;               // trs (column-major mat4), mesh_idx
 struct DirectionalLight { float position[3]; float rotation[2]; float color[3]; };
 using PointLight = ArcticPointLight;       // position, padding0, color, padding1
 using SpotLight = ArcticSpotLight;         // position, range, direction, inner_cone_angle, color, outer_cone_angle (no counterpart in the reference)
+using PointShadowLight = ArcticPointShadowLight;   // position, z_near, color, z_far (no counterpart in the reference)
 struct Scene {
     Camera camera;
     float ambient;
@@ -92,6 +93,15 @@ class Renderer {
     void update_lights(std::span<PointLight> point_lights) { (void)ok(arctic_update_lights(m_handle, point_lights.data(), point_lights.size())); }
     // spot lights (KHR_lights_punctual's cone and range; include/arctic_hip.h): false = an invalid light, the previous list stays
     [[nodiscard]] bool update_spot_lights(std::span<SpotLight> spot_lights) { return ok(arctic_update_spot_lights(m_handle, spot_lights.data(), spot_lights.size())); }
+    // shadow-casting point lights (a cube of six depth maps each; include/arctic_hip.h): false = an invalid light or no memory, the previous list stays
+    [[nodiscard]] bool update_point_shadow_lights(std::span<PointShadowLight> lights) { return ok(arctic_update_point_shadow_lights(m_handle, lights.data(), lights.size())); }
+    [[nodiscard]] bool pass_point_shadows(const ArcticScene &scene) { return ok(arctic_pass_point_shadows(m_handle, &scene)); }
+    // the faces of light `light`: 6 x F x F floats (F = set_point_shadow_size), faces +X, -X, +Y, -Y, +Z, -Z
+    [[nodiscard]] bool read_point_shadow(uint32_t light, float *faces) { return ok(arctic_read_point_shadow(m_handle, light, faces)); }
+    [[nodiscard]] bool write_point_shadow(uint32_t light, const float *faces) { return ok(arctic_write_point_shadow(m_handle, light, faces)); }
+    [[nodiscard]] bool set_point_shadow_size(uint32_t size) { return ok(arctic_set_option(m_handle, ARCTIC_OPT_POINT_SHADOW_SIZE, size)); }
+    // the six face matrices of one light, 16 floats each in glm memory order (host only)
+    [[nodiscard]] static bool point_shadow_matrices(const PointShadowLight &light, float out96[96]) { return arctic_point_shadow_matrices(&light, out96) == ARCTIC_OK; }
     [[nodiscard]] bool flush() { return ok(arctic_flush(m_handle)); }
     // image-based ambient from the HDRI (ARCTIC_OPT_ENV_LIGHTING; no counterpart in the reference, whose ps_main keeps a flat ambient):
     // false = the reference's ambient * base_color.  Safe to set before or after create_hdri, and without a map at all.

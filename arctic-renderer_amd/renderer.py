@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (LIGHT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (LIGHT_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -39,6 +39,7 @@ class Renderer:
         self.width, self.height, self.shadow_size, self.max_lights, self.device = width, height, shadow_size, max_lights, device
         self.row_begin, self.row_end = (row_begin, row_end) if row_end else (0, height)
         self.band_rows, self.shard = band_rows, shard
+        self._options = {}   # what set_option set (read_point_shadow's shape follows "point_shadow_size")
 
     # ---- helpers -------------------------------------------------------------------------------
     @property
@@ -148,6 +149,12 @@ class Renderer:
         l = np.ascontiguousarray(lights, dtype=SPOT_LIGHT_DTYPE)
         self._check(self.L.arctic_update_spot_lights(self.h, _ptr(l) if len(l) else None, len(l)))
 
+    def update_point_shadow_lights(self, lights):
+        """replace the handle's shadow-casting point lights (POINT_SHADOW_LIGHT_DTYPE records; an empty array clears them).  An invalid
+        light raises ArcticError (ARCTIC_E_INVALID) and leaves the previous list and faces in place."""
+        l = np.ascontiguousarray(lights, dtype=POINT_SHADOW_LIGHT_DTYPE)
+        self._check(self.L.arctic_update_point_shadow_lights(self.h, _ptr(l) if len(l) else None, len(l)))
+
     def render_frame(self, desc, settings, out=None):
         """returns the (rows, width, 4) uint8 frame (this handle's row shard)."""
         s, st = self._scene(desc), self._settings(settings)
@@ -165,6 +172,10 @@ class Renderer:
     def pass_shadow_map(self, desc):
         s = self._scene(desc)
         self._check(self.L.arctic_pass_shadow_map(self.h, C.byref(s)))
+
+    def pass_point_shadows(self, desc):
+        s = self._scene(desc)
+        self._check(self.L.arctic_pass_point_shadows(self.h, C.byref(s)))
 
     def pass_gbuffer(self, desc):
         s = self._scene(desc)
@@ -225,6 +236,23 @@ class Renderer:
         if d.shape != (self.shadow_size, self.shadow_size):
             raise ArcticError(-1, "write_shadow_map: wrong shape")
         self._check(self.L.arctic_write_shadow_map(self.h, _ptr(d)))
+
+    def _point_shadow_size(self):
+        return self._options.get("point_shadow_size", 1024)
+
+    def read_point_shadow(self, light):
+        """the 6 faces of shadow-casting point light `light`: (6, F, F) float32, faces +X, -X, +Y, -Y, +Z, -Z"""
+        F = self._point_shadow_size()
+        d = np.empty((6, F, F), np.float32)
+        self._check(self.L.arctic_read_point_shadow(self.h, int(light), _ptr(d)))
+        return d
+
+    def write_point_shadow(self, light, faces):
+        F = self._point_shadow_size()
+        d = np.ascontiguousarray(faces, dtype=np.float32)
+        if d.shape != (6, F, F):
+            raise ArcticError(-1, f"write_point_shadow: expected {(6, F, F)}, got {d.shape}")
+        self._check(self.L.arctic_write_point_shadow(self.h, int(light), _ptr(d)))
 
     def read_output(self, want=("ldr", "hdr", "rgba8")):
         n = (self.rows, self.width)
@@ -293,6 +321,18 @@ class Renderer:
 
     def set_option(self, name, value):
         self._check(self.L.arctic_set_option(self.h, binding.OPTIONS[name], int(value)))
+        self._options[name] = int(value)
+
+
+def point_shadow_matrices(light):
+    """the six face matrices of one shadow-casting point light (a POINT_SHADOW_LIGHT_DTYPE record) exactly as the library builds them:
+    (6, 4, 4) float32, each [col][row] like frame_constants"""
+    l = np.ascontiguousarray(np.asarray(light, dtype=POINT_SHADOW_LIGHT_DTYPE).reshape(1))
+    out = np.empty((6, 4, 4), np.float32)
+    rc = binding.lib().arctic_point_shadow_matrices(_ptr(l), _ptr(out))
+    if rc < 0:
+        raise ArcticError(rc, "point_shadow_matrices: invalid light")
+    return out
 
 
 def frame_constants(desc):

@@ -19,7 +19,10 @@ LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("padding0", "<u4"), ("color", "
 # ArcticSpotLight (include/arctic_hip.h): 48 bytes, no padding
 SPOT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("range", "<f4"), ("direction", "<f4", 3), ("inner_cone_angle", "<f4"),
                              ("color", "<f4", 3), ("outer_cone_angle", "<f4")])
+# ArcticPointShadowLight (include/arctic_hip.h): 32 bytes, no padding
+POINT_SHADOW_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("z_near", "<f4"), ("color", "<f4", 3), ("z_far", "<f4")])
 assert VERTEX_DTYPE.itemsize == 56 and OBJECT_DTYPE.itemsize == 72 and LIGHT_DTYPE.itemsize == 32 and SPOT_LIGHT_DTYPE.itemsize == 48
+assert POINT_SHADOW_LIGHT_DTYPE.itemsize == 32
 
 TM_REINHARD, TM_EXPOSURE, TM_ACES = 0, 1, 2
 

@@ -16,7 +16,7 @@ import colorsys
 
 import numpy as np
 
-from .scene import (LIGHT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, SceneDesc, make_lights, make_objects, rotation_y, scaling,
+from .scene import (LIGHT_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, SceneDesc, make_lights, make_objects, rotation_y, scaling,
                     translation, TM_ACES, TM_REINHARD)
 
 SEED = 0x41524354
@@ -278,6 +278,20 @@ def spot_lights(n, seed=0, lo=(-14.5, 0.5, -6.5), hi=(14.5, 11.5, 6.5), intensit
         out[i]["inner_cone_angle"] = outer * 0.9 * rng.random()
         out[i]["range"] = 1.5 * np.linalg.norm(t - p) + 2.0
         out[i]["color"] = np.array(colorsys.hsv_to_rgb(rng.random(), 0.5, 1.0)) * intensity
+    return out
+
+
+def point_shadow_lights(n, seed=0, lo=(-14.5, 0.5, -6.5), hi=(14.5, 11.5, 6.5), intensity=30.0, z_near=0.05, z_far=40.0):
+    """n shadow-casting point lights (POINT_SHADOW_LIGHT_DTYPE) inside the atrium hall of configs 3-5: uniform in the hall's box, among
+    its columns and balconies, a random hue; near 0.05 and far 40 (the hall's diagonal), so every surface of the hall is inside each
+    cube.  A random stream of its own (SEED + 211 + seed): the configs' streams are untouched."""
+    rng = np.random.default_rng(SEED + 211 + seed)
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    out = np.zeros(n, POINT_SHADOW_LIGHT_DTYPE)
+    for i in range(n):
+        out[i]["position"] = lo + rng.random(3) * (hi - lo)
+        out[i]["color"] = np.array(colorsys.hsv_to_rgb(rng.random(), 0.6, 1.0)) * intensity
+        out[i]["z_near"], out[i]["z_far"] = z_near, z_far
     return out
 
 

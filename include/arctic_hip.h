@@ -91,6 +91,15 @@ typedef struct ArcticSpotLight {
     float outer_cone_angle;  /* radians, 0 < outer <= pi; pi = no cone at all (an omnidirectional light with a range) */
 } ArcticSpotLight;
 
+/* A shadow-casting point light (no counterpart in the reference: its roadmap's "Point light shadows"), 32 B, no padding: a point light
+ * with a cube of six depth maps around it.  See arctic_update_point_shadow_lights for the exact semantics. */
+typedef struct ArcticPointShadowLight {
+    float position[3];
+    float z_near;            /* the cube's near plane, > 0 */
+    float color[3];          /* like ArcticPointLight.color: the radiance at distance 1 */
+    float z_far;             /* the cube's far plane, > z_near; it only limits the shadow (the light itself has no range) */
+} ArcticPointShadowLight;
+
 /* scene.hpp:96-103 Scene; std::vector members flattened to pointer + count.
  * point_lights here is ignored by render_frame exactly as in the reference
  * (renderer.cpp:285-407 uses the buffer last written by update_lights). */
@@ -210,6 +219,40 @@ int arctic_update_spot_lights(ArcticRenderer *r, const ArcticSpotLight *lights, 
  * color.rgb, ir2 (semantics above).  ARCTIC_E_INVALID (nothing written) when any light is invalid.  Host only, no handle. */
 int arctic_spot_light_constants(const ArcticSpotLight *lights, uint64_t n, float *out);
 
+/* Shadow-casting point lights (no counterpart in the reference).  Works like arctic_update_spot_lights: replaces the handle's list and
+ * clamps the count to max_lights; n = 0 clears it.  A light with a NaN or inf field, z_near <= 0 or z_far <= z_near makes the call return
+ * ARCTIC_E_INVALID, an allocation failure ARCTIC_E_DEVICE; either way the list and faces the handle had stay as they were.  A new list
+ * clears its faces to 1.0 and makes the next arctic_render_frame draw them.
+ * Faces.  Light i owns 6 depth maps of F x F floats (F = ARCTIC_OPT_POINT_SHADOW_SIZE), face k = 0..5 looking along +X, -X, +Y, -Y, +Z,
+ * -Z, each row-major with row 0 at clip y = +1, holding z / w of M_k = perspectiveRH_ZO(90 deg, 1, z_near, z_far) * lookAtRH(p, p + dir_k,
+ * up_k), up = (0,-1,0) for +-X and +-Z, (0,0,1) for +Y, (0,0,-1) for -Y (arctic_point_shadow_matrices).  A face is drawn like the sun's
+ * map: every object of the scene, front faces culled, depth LESS, cleared to 1.0.
+ * Lookup, per lit pixel at `world`, d = world - p, m = max(|d.x|, |d.y|, |d.z|): the face is the axis of m (ties go to x, then y, then z)
+ * and its sign;  px = 0.5 + 0.5 (s.d) / m,  py = 0.5 - 0.5 (u.d) / m,  pz = z_far / (z_far - z_near) * (1 - z_near / m), with the face's
+ * lookAt rows  +X: s = -z, u = -y   -X: s = +z, u = -y   +Y: s = +x, u = +z   -Y: s = +x, u = -z   +Z: s = +x, u = -y   -Z: s = -x, u = -y.
+ * If m <= z_near or pz > 1 the light is unshadowed (v = 1) and no texel is read (forward.hlsl:76: outside the map, no shadow).
+ * Otherwise 2 x 2 comparison PCF with CLAMP addressing inside the face: x = px F - 0.5, y = py F - 0.5, the texels floor(x) + {0, 1} by
+ * floor(y) + {0, 1} clamped to [0, F - 1], c = (pz > depth) ? 1 : 0, combined bilinearly with fx = x - floor(x), fy = y - floor(y) as
+ * a + (b - a) t (four equal compares give exactly 0 or 1); v = 1 - that.  fp32 weights in every ARCTIC_OPT_SAMPLER mode; no bias (front-face
+ * culling is the answer to acne, as for the sun, forward.hlsl:81): a closed occluder casts through its far side, a one-sided quad only
+ * when its back faces the light.
+ * The light's term is the point light's (color / |p - world|^2 into calculate_outgoing_radiance, forward.hlsl:224-231) with the colour
+ * scaled by v, added to Lo behind the point and the spot lights.  Lo keeps the sun's (1 - shadow) factor: such a light does not light what
+ * the sun's map covers, and fully sun-shadowed pixels skip every light, exactly like the point and spot lights.  Where v = 1 the light
+ * adds the same bits as a point light with its position and colour (ARCTIC_OPT_LIGHT_PATH = 1); where v = 0 it adds nothing; an empty list
+ * renders exactly as before.
+ * With such lights every tile goes through the general tile code (kernels k_cubelit / k_cubelit_vis, spot lights included),
+ * ARCTIC_OPT_TILE_ORDER is ignored, and ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE make a shading call return ARCTIC_E_STATE.
+ * arctic_render_frame redraws the faces when the lights, F, the objects' transforms or meshes, the mesh count, ARCTIC_OPT_CLUSTER_CULL or
+ * ARCTIC_OPT_SMALL_TRIANGLES changed (every frame with ARCTIC_OPT_SHADOW_CACHE = 0), on the handle's stream in front of the shading pass;
+ * arctic_pass_shade uses the faces in place.  INTEGRATION.md section 5g: what a DX12 host sets. */
+int arctic_update_point_shadow_lights(ArcticRenderer *r, const ArcticPointShadowLight *lights, uint64_t n);
+
+/* The six face matrices M_k of one light (semantics above), 16 floats each in glm memory order (m[col * 4 + row]), faces in order: 96
+ * floats.  fp32, camera_proj_view's helpers and operation order, with 1 / tan(45 deg) and lookAtRH's (p + dir_k) - p taken as exactly 1
+ * and dir_k.  ARCTIC_E_INVALID (nothing written) for an invalid light.  Host only, no handle. */
+int arctic_point_shadow_matrices(const ArcticPointShadowLight *light, float *out96);
+
 /* replaces bool Renderer::create_hdri(float*,w,h) (renderer.hpp:118, renderer.cpp:555-583): RGBA32F equirect
  * environment map.  Pixels without geometry then take it along their view ray (skybox.hlsl:61-90);
  * without a map they are black. */
@@ -236,6 +279,9 @@ int arctic_render_frame_device(ArcticRenderer *r, const ArcticScene *scene,
 /* ShadowMapPass::run (shadow_map_pass.cpp:113-169, depth.hlsl): light-view
  * depth-only raster, front faces culled, into the handle's shadow map. */
 int arctic_pass_shadow_map(ArcticRenderer *r, const ArcticScene *scene);
+
+/* every face of every shadow-casting point light, drawn now (arctic_update_point_shadow_lights) */
+int arctic_pass_point_shadows(ArcticRenderer *r, const ArcticScene *scene);
 
 /* ForwardPass::run's vertex + raster work (forward_pass.cpp:161-226,
  * forward.hlsl:50-66): visibility + G-buffer (the interpolated VSOut). */
@@ -270,6 +316,11 @@ int arctic_write_gbuffer(ArcticRenderer *r, const float *attrs, const uint32_t *
 /* shadow map: shadow_size^2 floats, row-major */
 int arctic_read_shadow_map(ArcticRenderer *r, float *depth);
 int arctic_write_shadow_map(ArcticRenderer *r, const float *depth);
+
+/* the faces of shadow-casting point light `light`: 6 x F x F floats in face order (+X, -X, +Y, -Y, +Z, -Z), each row-major.
+ * ARCTIC_E_INVALID for an index beyond the list.  A write makes the next arctic_render_frame redraw them, as arctic_write_shadow_map does. */
+int arctic_read_point_shadow(ArcticRenderer *r, uint32_t light, float *faces);
+int arctic_write_point_shadow(ArcticRenderer *r, uint32_t light, const float *faces);
 
 /* outputs of the last shade: float LDR (rows*width*3, after tonemap+gamma,
  * before the UNORM8 quantisation), float HDR (rows*width*3, ps_main's colour),
@@ -409,6 +460,8 @@ int arctic_stats(ArcticRenderer *r, uint64_t *out, uint32_t n);
  * ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply in mode 1 (a shading call then returns ARCTIC_E_STATE), and
  * ARCTIC_OPT_TILE_ORDER is ignored (the geometric order).  INTEGRATION.md section 5e: what a DX12 host sets. */
 #define ARCTIC_OPT_ENV_LIGHTING     25
+#define ARCTIC_OPT_POINT_SHADOW_SIZE 26 /* F, the side of each cube face of the shadow-casting point lights: a multiple of 8 in [8, 4096] (default 1024),
+                                          otherwise ARCTIC_E_INVALID.  A change clears the faces to 1.0 and makes the next arctic_render_frame draw them. */
 int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value);
 
 /* The tables of ARCTIC_OPT_ENV_LIGHTING (no counterpart in the reference): sh27 = the 27 coefficients of E(n), coefficient k of channel c
