@@ -206,7 +206,8 @@ __host__ __device__ inline bool shard_row_source(uint32_t y, uint32_t band_rows,
 // (w + 2) x (h + 2) texels, padded texel (X, Y) = image texel ((X - 1) mod w, (Y - 1) mod h).  A bilinear footprint under
 // WRAP addressing starts at image texel (i0, j0) in [-1, w - 1] x [-1, h - 1] and ends one further, i.e. it is padded texels
 // (i0 + 1 .. i0 + 2, j0 + 1 .. j0 + 2): never a wrap test, and the two texels of a row are adjacent -- one footprint = two
-// 16-byte loads instead of twelve 4-byte ones.  Bit 31 of w marks it; descriptors 1 and 2 are then unused.
+// 16-byte loads instead of twelve 4-byte ones.  Bit 31 of w marks it; descriptor 2 is then unused, descriptor 1 is a copy of
+// descriptor 0 or, for a material with a mip chain, its table of levels (MipTable, below).
 struct TexDesc {
     const uint32_t *texels;  // RGBA8 little endian (r = low byte), row-major, tightly packed -- or the packed, bordered image
     uint32_t w, h;           // image size (without the border); w bit 31: packed
@@ -220,6 +221,17 @@ struct TexDesc {
 };
 static_assert(sizeof(TexDesc) == 32, "TexDesc layout (tex_desc loads it with one s_load_dwordx8)");
 constexpr uint32_t TEX_INTERLEAVED = 0x80000000u;
+
+// ---- mip-mapped material textures (ARCTIC_OPT_TEXTURE_MIPS; the semantics are written once, in include/arctic_hip.h next to the option) ----
+// A packed material created under the option owns a CHAIN: one allocation, level 0 (the image uploaded as always, in the layout the tiling
+// option chose) at byte 0, levels 1 .. n - 1 behind it at 256-byte aligned offsets, each a packed image with its own one-texel WRAP border,
+// row-major (texture_mips.hip makes level k + 1 from level k).  The whole chain stays below 2^32 bytes: byte offsets are 32-bit in the kernels.
+// What the kernels see of it: descriptor 3 m + 1 of the material -- unused by packed materials otherwise, a copy of descriptor 3 m with
+// bit 31 of w set -- is a MipTable: texels = a device array of one TexDesc per level (entry 0 = descriptor 3 m), w = the number of levels
+// (>= 1, bit 31 clear), h = 0.  Kernels that do not know of chains never read it.
+constexpr uint32_t MAX_MIP_LEVELS = 16;   // image sides are below 65536
+__host__ __device__ inline uint32_t mip_level_count(uint32_t w, uint32_t h) { uint32_t n = 1; for (uint32_t m = w > h ? w : h; m > 1; m >>= 1) ++n; return n; }
+__host__ __device__ inline uint32_t mip_level_side(uint32_t n, uint32_t k) { return (n >> k) ? (n >> k) : 1u; }
 
 // point light as uploaded (scene.hpp:88-94): float3 pos, pad, float3 color, pad = 2 x float4
 // The kernels' argument block.  The fields are ordered by WHEN a wave of k_material needs them, in 64-byte blocks, so that each
@@ -295,7 +307,13 @@ struct ShadeParams {
     uint32_t n_jobs;
     uint32_t cube_size;          // k_cubelit* only: F, the side of a cube face (ARCTIC_OPT_POINT_SHADOW_SIZE; the slot was padding)
     // whole frames without a G-buffer (k_material_vis): the visibility plane and what the prepass left behind
-    const unsigned long long *vis; const SetupRec *recs; const RasterRec *rrecs; const uint32_t *rec_of; const ObjectRec *objs; const XVert *xv;
+    // lod: k_miplit only (the G-buffer walk reads no visibility plane): the level-of-detail plane of ARCTIC_OPT_TEXTURE_MIPS, one float per pixel,
+    //      tile-major.  One slot for both, for the reason given at stats / spots.
+    union {
+        const unsigned long long *vis;
+        const float *lod;
+    };
+    const SetupRec *recs; const RasterRec *rrecs; const uint32_t *rec_of; const ObjectRec *objs; const XVert *xv;
     // skybox (skybox.hlsl:61-90): environment map for pixels without geometry; env == null -> black
     const float4 *env;                  // RGBA32F equirect, row-major
     uint32_t env_w, env_h;
@@ -314,6 +332,8 @@ struct ShadeLaunch {
     uint32_t tiles_per_wave;   // 0: DEFAULT_TILES_PER_WAVE (ARCTIC_OPT_TILES_PER_WAVE)
     uint32_t env;        // 1: k_envlit / k_envlit_vis (image-based ambient, ShadeParams::env_tables; geometric tile order, no statistics)
     uint32_t spot;       // 1: k_spotlit / k_spotlit_vis with ENV = env (ShadeParams::spots, n_spots; geometric tile order, no statistics)
+    uint32_t mip;        // 1: k_miplit / k_miplit_vis with ENV = env, spot and cube loops compiled in (empty lists loop zero times): trilinear material
+                         //    textures (ARCTIC_OPT_TEXTURE_MIPS; ShadeParams::lod for the G-buffer walk; geometric order, no statistics, no trace)
     uint32_t cube;       // 1: k_cubelit / k_cubelit_vis with ENV = env, spot lights included (ShadeParams::cubes, n_cubes, cube_size; geometric order, no statistics, no trace)
 };
 
@@ -410,6 +430,13 @@ hipError_t launch_resolve(const unsigned long long *vis, const SetupRec *recs, c
                           const GeomParams &gp, uint32_t n_tiles, GBuffer g, const TileHint &hint, hipStream_t s);
 // the shading pass's dispatch order (ShadeParams::tile_order) from the cost classes k_resolve left: lists = scratch of 2 N words, N = ceil(tiles_x / 4) *
 // tiles_y strips; order = order_slots() words; tail_permille: the last part of each list that holds cheap strips only; group = tiles per wave of the pass
+// the same with the level-of-detail plane of ARCTIC_OPT_TEXTURE_MIPS next to the G-buffer (k_resolve_lod): lod = one float per pixel, tile-major
+hipError_t launch_resolve_lod(const unsigned long long *vis, const SetupRec *recs, const RasterRec *rrecs, const uint32_t *rec_of, const ObjectRec *objs, const XVert *xv,
+                              const GeomParams &gp, uint32_t n_tiles, GBuffer g, const TileHint &hint, const TexDesc *tex, uint32_t n_materials, float *lod, hipStream_t s);
+// one float plane between the handle's rows (row-major) and the tile-major layout, as launch_gbuffer_tile does for the G-buffer (texture_mips.hip)
+hipError_t launch_plane_tile(float *tiled, float *rows, uint32_t width, uint32_t n_rows, uint32_t row0_in_tile, uint32_t tiles_x, uint32_t tiles_y, int to_tiled, hipStream_t s);
+// level k + 1 of a material's chain from level k (texture_mips.hip): both packed images with a border; dst row-major
+hipError_t launch_mip_reduce(const TexDesc &src, const TexDesc &dst, const float *srgb_lut, hipStream_t s);
 hipError_t launch_tile_order(const uint8_t *tile_class, uint32_t tiles_x, uint32_t tiles_y, uint32_t tail_permille, uint32_t group, uint32_t *lists, uint32_t *order, hipStream_t s);
 hipError_t launch_fill_u64(unsigned long long *p, unsigned long long v, size_t n, hipStream_t s);
 hipError_t launch_fill_u32(uint32_t *p, uint32_t v, size_t n, hipStream_t s);

@@ -32,6 +32,7 @@
 #include "common.h"
 #include "edges.h"
 #include "shadow_coords.h"
+#include "texture_lod.h"
 
 namespace arctic {
 
@@ -1132,59 +1133,78 @@ __global__ __launch_bounds__(64 * ARCTIC_RASTER_WGW) void k_raster_owned(const R
 // ---------------------------------------------------------------------------------------------
 // resolve: visibility -> interpolated attributes, tile-major G-buffer
 // ---------------------------------------------------------------------------------------------
+// LOD (k_resolve_lod, ARCTIC_OPT_TEXTURE_MIPS): the pixel's level of detail goes into one more plane (texture_lod.h; 0 where nothing is drawn and for
+// materials without a chain).  A compile-time flag on the shared body, a second kernel symbol.
+// The body of k_resolve and k_resolve_lod.  A macro, not a device function (as the tile walks of shade.hip are): inlined through one more level the hint's
+// branches come out of the compiler in another order, and k_resolve is to stay the code it was.
+#define RESOLVE_TILE(LOD)                                                                                                                                       \
+    uint32_t tile = blockIdx.x * 4 + (threadIdx.x >> 6);                                                                                                        \
+    if (tile >= n_tiles) return;                                                                                                                                \
+    uint32_t lane = threadIdx.x & 63;                                                                                                                           \
+    size_t idx = (size_t)tile * 64 + lane;                                                                                                                      \
+    unsigned long long key = vis[idx];                                                                                                                          \
+    float a[18];                                                                                                                                                \
+_Pragma("unroll")                                                                                                                                               \
+    for (int k = 0; k < 18; ++k) a[k] = 0.0f;                                                                                                                   \
+    uint32_t mat = NO_MATERIAL;                                                                                                                                 \
+    float lambda = 0.0f;                                                                                                                                        \
+    if (key != ~0ull) {                                                                                                                                         \
+        const uint32_t ri = rec_of[(uint32_t)key];   /* low word = order id (k_setup) */                                                                        \
+        const SetupRec &t = recs[ri];                                                                                                                           \
+        int32_t tx = (int32_t)(tile % (uint32_t)gp.tiles_x);                                                                                                    \
+        int32_t ty = row_global((int)(tile / (uint32_t)gp.tiles_x), gp.band_tiles, gp.shard_count, gp.shard_index) + gp.tile_y0;                                \
+        int32_t px = tx * 8 + (int32_t)(lane & 7), py = ty * 8 + (int32_t)(lane >> 3);                                                                          \
+        float B[3];                                                                                                                                             \
+        source_barycentrics(t, rrecs[ri], px, py, B);                                                                                                           \
+        const ObjectRec &ob = objs[t.object];                                                                                                                   \
+        uint32_t lt = t.src_tri - ob.first_triangle;                                                                                                            \
+        const float *A0 = xv[ob.first_xvert + ob.indices[3 * lt]].attr;                                                                                         \
+        const float *A1 = xv[ob.first_xvert + ob.indices[3 * lt + 1]].attr;                                                                                     \
+        const float *A2 = xv[ob.first_xvert + ob.indices[3 * lt + 2]].attr;                                                                                     \
+_Pragma("unroll")                                                                                                                                               \
+        for (int k = 0; k < 18; ++k) a[k] = interpolate_attr(B, A0, A1, A2, k);                                                                                 \
+        mat = ob.material;                                                                                                                                      \
+        if (LOD) {                                                                                                                                              \
+            float wf, hf, last;                                                                                                                                 \
+            lambda = mat < n_materials && lod_material(tex, mat, wf, hf, last) ? pixel_lod(t, rrecs[ri], px, py, A0, A1, A2, a[0], a[1], wf, hf, last) : 0.0f;  \
+        }                                                                                                                                                       \
+    }                                                                                                                                                           \
+    if (LOD) lod[idx] = lambda;                                                                                                                                 \
+    {                                                                                                                                                           \
+        float4 A, C, D, E; float B3[3];                                                                                                                         \
+        gbuffer_pack(a, mat, A, B3, C, D, E);                                                                                                                   \
+        g.a[idx] = A; g.c[idx] = C; g.d[idx] = D; g.e[idx] = E;                                                                                                 \
+        g.b[idx * 3] = B3[0]; g.b[idx * 3 + 1] = B3[1]; g.b[idx * 3 + 2] = B3[2];                                                                               \
+    }                                                                                                                                                           \
+    /* The tile's COST CLASS, a hint for the shading pass's dispatch order (k_tile_order; results never depend on it): 1 when a pixel */                        \
+    /* of the tile can be lit at all -- covered, and not decided "every tap shadowed" by the shadow map's min/max table, the first */                           \
+    /* test of the shading kernel itself (shade.hip: shadow_quick) -- or takes the environment lookup; such a tile runs the light loop, */                      \
+    /* tens of times the work of a tile in full shadow.  The light-space position is in registers here: the hint costs one 8-byte load. */                      \
+    if (hint.tile_class) {                                                                                                                                      \
+        bool costly = mat != NO_MATERIAL || hint.sky != 0;                                                                                                      \
+        if (mat != NO_MATERIAL && hint.bounds) {                                                                                                                \
+            ShadowPos p;                                                                                                                                        \
+            shadow_coords(a[14], a[15], a[16], a[17], p);                                                                                                       \
+            uint32_t offset;                                                                                                                                    \
+            if (shadow_table_offset(hint.S, hint.pitch, p, offset)) {                                                                                           \
+                const float2 mm = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(hint.bounds) + offset);                                      \
+                costly = !(p.pz > mm.y);                                                                                                                        \
+            }                                                                                                                                                   \
+        }                                                                                                                                                       \
+        const unsigned long long any = __ballot(costly);                                                                                                        \
+        if (lane == 0) hint.tile_class[tile] = any ? 1 : 0;                                                                                                     \
+    }
 __global__ __launch_bounds__(256) void k_resolve(const unsigned long long *__restrict__ vis, const SetupRec *__restrict__ recs, const RasterRec *__restrict__ rrecs,
                                                  const uint32_t *__restrict__ rec_of, const ObjectRec *__restrict__ objs, const XVert *__restrict__ xv,
                                                  const GeomParams gp, uint32_t n_tiles, GBuffer g, const TileHint hint) {
-    uint32_t tile = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tile >= n_tiles) return;
-    uint32_t lane = threadIdx.x & 63;
-    size_t idx = (size_t)tile * 64 + lane;
-    unsigned long long key = vis[idx];
-    float a[18];
-#pragma unroll
-    for (int k = 0; k < 18; ++k) a[k] = 0.0f;
-    uint32_t mat = NO_MATERIAL;
-    if (key != ~0ull) {
-        const uint32_t ri = rec_of[(uint32_t)key];   // low word = order id (k_setup)
-        const SetupRec &t = recs[ri];
-        int32_t tx = (int32_t)(tile % (uint32_t)gp.tiles_x);
-        int32_t ty = row_global((int)(tile / (uint32_t)gp.tiles_x), gp.band_tiles, gp.shard_count, gp.shard_index) + gp.tile_y0;
-        int32_t px = tx * 8 + (int32_t)(lane & 7), py = ty * 8 + (int32_t)(lane >> 3);
-        float B[3];
-        source_barycentrics(t, rrecs[ri], px, py, B);
-        const ObjectRec &ob = objs[t.object];
-        uint32_t lt = t.src_tri - ob.first_triangle;
-        const float *A0 = xv[ob.first_xvert + ob.indices[3 * lt]].attr;
-        const float *A1 = xv[ob.first_xvert + ob.indices[3 * lt + 1]].attr;
-        const float *A2 = xv[ob.first_xvert + ob.indices[3 * lt + 2]].attr;
-#pragma unroll
-        for (int k = 0; k < 18; ++k) a[k] = interpolate_attr(B, A0, A1, A2, k);
-        mat = ob.material;
-    }
-    {
-        float4 A, C, D, E; float B3[3];
-        gbuffer_pack(a, mat, A, B3, C, D, E);
-        g.a[idx] = A; g.c[idx] = C; g.d[idx] = D; g.e[idx] = E;
-        g.b[idx * 3] = B3[0]; g.b[idx * 3 + 1] = B3[1]; g.b[idx * 3 + 2] = B3[2];
-    }
-    // The tile's COST CLASS, a hint for the shading pass's dispatch order (k_tile_order; results never depend on it): 1 when a pixel
-    // of the tile can be lit at all -- covered, and not decided "every tap shadowed" by the shadow map's min/max table, the first
-    // test of the shading kernel itself (shade.hip: shadow_quick) -- or takes the environment lookup; such a tile runs the light loop,
-    // tens of times the work of a tile in full shadow.  The light-space position is in registers here: the hint costs one 8-byte load.
-    if (hint.tile_class) {
-        bool costly = mat != NO_MATERIAL || hint.sky != 0;
-        if (mat != NO_MATERIAL && hint.bounds) {
-            ShadowPos p;
-            shadow_coords(a[14], a[15], a[16], a[17], p);
-            uint32_t offset;
-            if (shadow_table_offset(hint.S, hint.pitch, p, offset)) {
-                const float2 mm = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(hint.bounds) + offset);
-                costly = !(p.pz > mm.y);
-            }
-        }
-        const unsigned long long any = __ballot(costly);
-        if (lane == 0) hint.tile_class[tile] = any ? 1 : 0;
-    }
+    const TexDesc *tex = nullptr; const uint32_t n_materials = 0; float *lod = nullptr;   // (LOD only)
+    RESOLVE_TILE(false)
+}
+__global__ __launch_bounds__(256) void k_resolve_lod(const unsigned long long *__restrict__ vis, const SetupRec *__restrict__ recs, const RasterRec *__restrict__ rrecs,
+                                                     const uint32_t *__restrict__ rec_of, const ObjectRec *__restrict__ objs, const XVert *__restrict__ xv,
+                                                     const GeomParams gp, uint32_t n_tiles, GBuffer g, const TileHint hint,
+                                                     const TexDesc *__restrict__ tex, uint32_t n_materials, float *__restrict__ lod) {
+    RESOLVE_TILE(true)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1369,6 +1389,12 @@ hipError_t launch_resolve(const unsigned long long *vis, const SetupRec *recs, c
                           const GeomParams &gp, uint32_t n_tiles, GBuffer g, const TileHint &hint, hipStream_t s) {
     if (n_tiles == 0) return hipSuccess;
     k_resolve<<<div_up(n_tiles, 4), 256, 0, s>>>(vis, recs, rrecs, rec_of, objs, xv, gp, n_tiles, g, hint);
+    return hipGetLastError();
+}
+hipError_t launch_resolve_lod(const unsigned long long *vis, const SetupRec *recs, const RasterRec *rrecs, const uint32_t *rec_of, const ObjectRec *objs, const XVert *xv,
+                              const GeomParams &gp, uint32_t n_tiles, GBuffer g, const TileHint &hint, const TexDesc *tex, uint32_t n_materials, float *lod, hipStream_t s) {
+    if (n_tiles == 0) return hipSuccess;
+    k_resolve_lod<<<div_up(n_tiles, 4), 256, 0, s>>>(vis, recs, rrecs, rec_of, objs, xv, gp, n_tiles, g, hint, tex, n_materials, lod);
     return hipGetLastError();
 }
 hipError_t launch_tile_order(const uint8_t *tile_class, uint32_t tiles_x, uint32_t tiles_y, uint32_t tail_permille, uint32_t group, uint32_t *lists, uint32_t *order, hipStream_t s) {

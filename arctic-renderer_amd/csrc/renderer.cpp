@@ -280,6 +280,15 @@ struct ArcticRenderer {
     bool have_order = false;         // d_tile_order belongs to the G-buffer in place
     uint32_t order_group = 0, order_slots = 0;   // ... built for this many tiles per wave, this many slots (common.h order_slot)
     int texture_tiling = -1;         // ARCTIC_OPT_TEXTURE_TILING: materials created from now on: -1 = 4 x 4-texel tiles for images of 2048 texels a side and more, 0 = never, 1 = always
+    // ARCTIC_OPT_TEXTURE_MIPS: materials created under 1 get a chain (chains[m]: the host copy of the material's level descriptors, empty = one level);
+    // at shading time 1 selects k_miplit* once a material has a chain.  d_lod: the level-of-detail plane next to the G-buffer (tile-major, allocated only
+    // under the option); lod_valid: it belongs to the G-buffer in place (k_resolve_lod wrote it, or arctic_write_gbuffer / arctic_write_lod did)
+    int texture_mips = 0;
+    std::vector<std::vector<TexDesc>> chains;
+    uint32_t n_chains = 0;
+    DevBuf d_lod;
+    bool lod_valid = false;
+    bool mips_active() const { return texture_mips == 1 && n_chains != 0; }
     int sampler = 0;                 // ARCTIC_OPT_SAMPLER: bit 0 material footprints, bit 2 PCF taps with coordinates snapped to 1/256 texel (D3D-style 8-bit filter weights)
     int tile_order = 0;              // ARCTIC_OPT_TILE_ORDER: 0 (default since round 5) = the geometric, XCD-aware order of round 3; 1 = the cost-class order of round 4.
                                      // Measured (profiles/r5_a_*): the order gains <= 2 us of the pass, its one-workgroup kernel costs the G-buffer pass 112 us, and handing strips
@@ -377,6 +386,8 @@ int alloc_targets(ArcticRenderer *r) {
     HIPCHECK(r, r->d_p2.ensure(px * 16));
     HIPCHECK(r, r->d_p3.ensure(px * 16));
     HIPCHECK(r, r->d_p4.ensure(px * 12));
+    if (r->texture_mips) HIPCHECK(r, r->d_lod.ensure(px * 4));
+    r->lod_valid = false;
     HIPCHECK(r, r->d_rgba8.ensure(out_px * 4));
     HIPCHECK(r, r->d_counter.ensure(8 * N_SHADE_STATS));
     HIPCHECK(r, r->d_geo_counters.ensure(5 * N_GEO_COUNTERS * 4));   // N_GEO_COUNTERS words per table set; set 4: the cube faces (CUBE_COUNTER_SET)
@@ -697,6 +708,14 @@ int resolve_gbuffer(ArcticRenderer *r) {
             hint.bounds = r->d_shadow_bounds().as<float2>(); hint.S = r->shadow_size; hint.pitch = nb;
         }
     }
+    r->lod_valid = false;
+    if (r->texture_mips) {   // ... with the level-of-detail plane next to it (k_resolve_lod)
+        HIPCHECK(r, r->d_lod.ensure(r->n_tiles() * TILE_PIXELS * 4));
+        HIPCHECK(r, launch_resolve_lod(r->d_vis().as<unsigned long long>(), r->geo[r->fwd()].d_recs.as<SetupRec>(), r->geo[r->fwd()].d_rrecs.as<RasterRec>(), r->geo[r->fwd()].d_rec_of.as<uint32_t>(), r->tables[r->fwd()].objs,
+                                       r->geo[r->fwd()].d_xverts.as<XVert>(), r->tables[r->fwd()].gp, (uint32_t)r->n_tiles(), r->gbuffer(), hint,
+                                       r->d_tex.as<TexDesc>(), (uint32_t)(r->tex.size() / 3), r->d_lod.as<float>(), r->stream));
+        r->lod_valid = true;
+    } else
     HIPCHECK(r, launch_resolve(r->d_vis().as<unsigned long long>(), r->geo[r->fwd()].d_recs.as<SetupRec>(), r->geo[r->fwd()].d_rrecs.as<RasterRec>(), r->geo[r->fwd()].d_rec_of.as<uint32_t>(), r->tables[r->fwd()].objs,
                                r->geo[r->fwd()].d_xverts.as<XVert>(), r->tables[r->fwd()].gp, (uint32_t)r->n_tiles(), r->gbuffer(), hint,
                                r->stream));
@@ -745,6 +764,16 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
         if (r->have_vis) { int rc = resolve_gbuffer(r); if (rc != ARCTIC_OK) return rc; }   // frame came from arctic_render_frame
         else return r->fail(ARCTIC_E_STATE, "shade: no G-buffer (run arctic_pass_gbuffer or arctic_write_gbuffer first)");
     }
+    if (r->mips_active() && (r->count_evals || r->tile_trace))
+        return r->fail(ARCTIC_E_STATE, "shade: ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply to mip-mapped material textures (ARCTIC_OPT_TEXTURE_MIPS = 1 with a chain)");
+    if (!from_vis && r->mips_active() && !r->lod_valid) {   // the G-buffer in place was made with the option off: its plane from the visibility, or zeroes
+        if (r->have_vis) { int rc = resolve_gbuffer(r); if (rc != ARCTIC_OK) return rc; }
+        else {
+            HIPCHECK(r, r->d_lod.ensure(r->n_tiles() * TILE_PIXELS * 4));
+            HIPCHECK(r, hipMemsetAsync(r->d_lod.p, 0, r->n_tiles() * TILE_PIXELS * 4, r->stream));
+            r->lod_valid = true;
+        }
+    }
     if (r->env_active() && (r->count_evals || r->tile_trace))
         return r->fail(ARCTIC_E_STATE, "shade: ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply to the image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map)");
     if (r->n_spots && (r->count_evals || r->tile_trace))
@@ -756,7 +785,9 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
     const ArcticRenderer::GeoSet &G = r->geo[r->fwd()];
     sp.compact_tables = (G.d_recs.cap < (1ull << 32) && G.d_rrecs.cap < (1ull << 32) && G.d_xverts.cap < (1ull << 32) && G.d_rec_of.cap < (1ull << 32) &&
                          r->tables[r->fwd()].d.cap < (1ull << 32) && !(r->debug & 64)) ? 1 : 0;
-    sp.vis = r->d_vis().as<unsigned long long>(); sp.recs = G.d_recs.as<SetupRec>(); sp.rrecs = G.d_rrecs.as<RasterRec>(); sp.rec_of = G.d_rec_of.as<uint32_t>();
+    sp.vis = r->d_vis().as<unsigned long long>();
+    if (!from_vis && r->mips_active()) sp.lod = r->d_lod.as<float>();   // (k_miplit: the G-buffer walk reads no visibility plane, the plane takes its slot)
+    sp.recs = G.d_recs.as<SetupRec>(); sp.rrecs = G.d_rrecs.as<RasterRec>(); sp.rec_of = G.d_rec_of.as<uint32_t>();
     sp.objs = r->tables[r->fwd()].objs; sp.xv = G.d_xverts.as<XVert>();
     sp.tex = r->d_tex.as<TexDesc>();
     sp.n_materials = (uint32_t)(r->tex.size() / 3);
@@ -793,7 +824,7 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
     if (r->n_cubes) { sp.cubes = r->d_cubes.as<float4>(); sp.n_cubes = r->n_cubes; sp.cube_size = r->cube_size; }   // (the trace's slot: k_cubelit* keep none)
     // (the order was built for groups of order_group tiles per wave: a pass that shades another number per wave takes the geometric order)
     if (r->env_active()) sp.env_tables = r->d_env_tables.as<EnvTables>();   // (the geometric order: the tables take the order's slot)
-    else if (r->n_spots || r->n_cubes) {}                                    // (k_spotlit*, k_cubelit*: the geometric order)
+    else if (r->n_spots || r->n_cubes || r->mips_active()) {}                                    // (k_spotlit*, k_cubelit*: the geometric order)
     else if (!from_vis && r->have_order && r->tile_order && (r->tiles_per_wave == 0 || r->tiles_per_wave == r->order_group)) {
         sp.tile_order = r->d_tile_order.as<uint32_t>(); sp.n_jobs = r->order_slots; sp.tiles_per_wave = r->order_group;
     }
@@ -827,6 +858,7 @@ hipError_t shade_once(ArcticRenderer *r, const ShadeParams &sp, bool from_vis, b
     L.env = r->env_active() ? 1u : 0u;
     L.spot = sp.n_spots ? 1u : 0u;
     L.cube = sp.n_cubes ? 1u : 0u;
+    L.mip = r->mips_active() ? 1u : 0u;
     return launch_shade(sp, L);
 }
 
@@ -905,7 +937,7 @@ bool valid_scene(const ArcticScene *sc) { return sc && (sc->n_objects == 0 || sc
 // =================================================================================================
 extern "C" {
 
-int arctic_version(void) { return 300; }
+int arctic_version(void) { return 310; }
 
 ArcticRenderer *arctic_create(const ArcticCreateInfo *info, char *err, uint64_t err_len) {
     auto say = [&](const char *m) { if (err && err_len) { std::snprintf(err, (size_t)err_len, "%s", m); } };
@@ -1005,7 +1037,7 @@ void arctic_destroy(ArcticRenderer *r) {
     if (r->own_stream) { (void)hipStreamSynchronize(r->own_stream); (void)hipStreamDestroy(r->own_stream); }
     for (Mesh &m : r->meshes) { if (m.d_vertices) (void)hipFree(m.d_vertices); if (m.d_indices) (void)hipFree(m.d_indices); }
     for (void *p : r->tex_allocs) (void)hipFree(p);
-    DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_spots, &r->d_cubes, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4,
+    DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_spots, &r->d_cubes, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4, &r->d_lod,
                       &r->d_rgba8, &r->d_ldr, &r->d_hdr, &r->d_counter, &r->d_shadow_blocks_set[0], &r->d_shadow_blocks_set[1], &r->d_shadow_bounds_set[0], &r->d_shadow_bounds_set[1], &r->d_staging, &r->d_layout, &r->geo[0].d_xverts, &r->geo[1].d_xverts, &r->geo[2].d_xverts,
                       &r->geo[2].d_recs, &r->geo[2].d_rrecs, &r->geo[2].d_clip_list, &r->geo[2].d_rec_of, &r->geo[2].d_items, &r->tables[2].d,
                       &r->geo[3].d_xverts, &r->geo[3].d_recs, &r->geo[3].d_rrecs, &r->geo[3].d_clip_list, &r->geo[3].d_rec_of, &r->geo[3].d_items, &r->geo[3].d_left, &r->geo[3].d_bin_count, &r->geo[3].d_bin_slots, &r->tables[3].d,
@@ -1085,6 +1117,7 @@ int arctic_create_material(ArcticRenderer *r, const void *diffuse, uint32_t dw, 
     const void *src[3] = {diffuse, normal, mr};
     const uint32_t w[3] = {dw, nw, mw}, h[3] = {dh, nh, mh};
     TexDesc td[3];
+    std::vector<TexDesc> chain;   // ARCTIC_OPT_TEXTURE_MIPS: one descriptor per level; empty: one level
     // byte offsets into an image are 32-bit in the kernels (shade.hip: saddr loads)
     if ((uint64_t)(dw + 2) * (dh + 2) > (1ull << 29) || (uint64_t)nw * nh > (1ull << 30) || (uint64_t)mw * mh > (1ull << 30))
         return r->fail(ARCTIC_E_CAPACITY, "create_material: image above 2^29 texels");
@@ -1099,6 +1132,17 @@ int arctic_create_material(ArcticRenderer *r, const void *diffuse, uint32_t dw, 
         const uint32_t tpr = (pw + 3) / 4, trows = (ph + 3) / 4;
         size_t n = tiled ? (size_t)tpr * trows * 16 : (size_t)pw * ph;
         if (n > (1ull << 29)) return r->fail(ARCTIC_E_CAPACITY, "create_material: image above 2^29 texels");
+        // ARCTIC_OPT_TEXTURE_MIPS: the chain behind level 0 in the same allocation (common.h), levels 1.. row-major with their own border, at
+        // 256-byte aligned offsets; the whole of it below 2^32 bytes (checked before anything is allocated: the handle stays as it was)
+        const uint32_t levels = r->texture_mips ? mip_level_count(dw, dh) : 1u;
+        std::vector<uint64_t> level_offset(levels, 0);
+        uint64_t chain_bytes = (uint64_t)n * 8;
+        for (uint32_t k = 1; k < levels; ++k) {
+            chain_bytes = (chain_bytes + 255) & ~255ull;
+            level_offset[k] = chain_bytes;
+            chain_bytes += (uint64_t)(mip_level_side(dw, k) + 2) * (mip_level_side(dh, k) + 2) * 8;
+        }
+        if (chain_bytes > (1ull << 32)) return r->fail(ARCTIC_E_CAPACITY, "create_material: the mip chain does not fit in 2^32 bytes (ARCTIC_OPT_TEXTURE_MIPS)");
         std::vector<uint32_t> packed(n * 2);
         const uint8_t *a = static_cast<const uint8_t *>(diffuse), *b = static_cast<const uint8_t *>(normal), *c = static_cast<const uint8_t *>(mr);
         for (uint32_t Y = 0; Y < ph; ++Y) {
@@ -1111,10 +1155,25 @@ int arctic_create_material(ArcticRenderer *r, const void *diffuse, uint32_t dw, 
             }
         }
         void *p = nullptr;
-        HIPCHECK(r, hipMalloc(&p, n * 8));
+        HIPCHECK(r, hipMalloc(&p, (size_t)chain_bytes));
         r->tex_allocs.push_back(p);
         HIPCHECK(r, hipMemcpy(p, packed.data(), n * 8, hipMemcpyHostToDevice));   // synchronous like rhi.cpp:480-519
         for (int i = 0; i < 3; ++i) { td[i] = TexDesc{static_cast<const uint32_t *>(p), dw | TEX_INTERLEAVED, dh, (float)dw, (float)dh, pw, tiled ? tpr * 128u : 0u}; }
+        if (r->texture_mips) {   // level k + 1 from level k on the device (texture_mips.hip), synchronous like the upload; the material's table of levels
+            chain.resize(levels);
+            chain[0] = td[0];
+            for (uint32_t k = 1; k < levels; ++k) {
+                const uint32_t wk = mip_level_side(dw, k), hk = mip_level_side(dh, k);
+                chain[k] = TexDesc{reinterpret_cast<const uint32_t *>(static_cast<const char *>(p) + level_offset[k]), wk | TEX_INTERLEAVED, hk, (float)wk, (float)hk, wk + 2, 0u};
+                HIPCHECK(r, launch_mip_reduce(chain[k - 1], chain[k], r->d_lut.as<float>(), r->stream));
+            }
+            void *table = nullptr;
+            HIPCHECK(r, hipMalloc(&table, levels * sizeof(TexDesc)));
+            r->tex_allocs.push_back(table);
+            HIPCHECK(r, hipMemcpyAsync(table, chain.data(), levels * sizeof(TexDesc), hipMemcpyHostToDevice, r->stream));
+            HIPCHECK(r, hipStreamSynchronize(r->stream));
+            td[1] = TexDesc{static_cast<const uint32_t *>(table), levels, 0u, 0.0f, 0.0f, 0u, 0u};   // the MipTable (common.h)
+        }
     } else {
         for (int i = 0; i < 3; ++i) {
             void *p = nullptr;
@@ -1126,6 +1185,8 @@ int arctic_create_material(ArcticRenderer *r, const void *diffuse, uint32_t dw, 
         }
     }
     r->tex.insert(r->tex.end(), td, td + 3);
+    if (!chain.empty()) ++r->n_chains;
+    r->chains.push_back(std::move(chain));
     HIPCHECK(r, hipStreamSynchronize(r->stream));
     HIPCHECK(r, r->d_tex.ensure(r->tex.size() * sizeof(TexDesc)));
     HIPCHECK(r, hipMemcpy(r->d_tex.p, r->tex.data(), r->tex.size() * sizeof(TexDesc), hipMemcpyHostToDevice));
@@ -1559,10 +1620,82 @@ int arctic_write_gbuffer(ArcticRenderer *r, const float *attrs, const uint32_t *
     HIPCHECK(r, hipMemcpyAsync(d_attrs, attrs, px * 72, hipMemcpyHostToDevice, r->stream));
     HIPCHECK(r, hipMemcpyAsync(d_mat, material, px * 4, hipMemcpyHostToDevice, r->stream));
     HIPCHECK(r, launch_gbuffer_tile(r->gbuffer(), d_attrs, d_mat, r->width, r->rows(), r->row0_in_tile, r->tiles_x, r->tiles_y, 1, r->stream));
+    r->lod_valid = false;
+    if (r->texture_mips) {   // an injected G-buffer has no triangles: its level-of-detail plane is 0 until arctic_write_lod injects one
+        HIPCHECK(r, r->d_lod.ensure(r->n_tiles() * TILE_PIXELS * 4));
+        HIPCHECK(r, hipMemsetAsync(r->d_lod.p, 0, r->n_tiles() * TILE_PIXELS * 4, r->stream));
+        r->lod_valid = true;
+    }
     HIPCHECK(r, hipStreamSynchronize(r->stream));
     r->have_vis = false;
     r->have_gbuffer = true;
     r->have_order = false;   // (a caller's G-buffer comes without cost classes: the geometric order)
+    return ARCTIC_OK;
+}
+
+int arctic_read_lod(ArcticRenderer *r, float *lod) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!lod) return r->fail(ARCTIC_E_INVALID, "read_lod: null");
+    if (!r->texture_mips) return r->fail(ARCTIC_E_STATE, "read_lod: no level-of-detail plane (ARCTIC_OPT_TEXTURE_MIPS is 0)");
+    int rc = select_device(r);
+    if (rc) return rc;
+    if (!r->have_gbuffer || !r->lod_valid) {
+        if (!r->have_vis) return r->fail(ARCTIC_E_STATE, "read_lod: no G-buffer");
+        if ((rc = resolve_gbuffer(r)) != ARCTIC_OK) return rc;   // the frame was shaded from the visibility plane, or resolved with the option off
+    }
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    if (int ov = check_item_overflow(r)) return ov;
+    const size_t px = (size_t)r->rows() * r->width;
+    HIPCHECK(r, r->d_stage.ensure(px * 4));
+    HIPCHECK(r, launch_plane_tile(r->d_lod.as<float>(), r->d_stage.as<float>(), r->width, r->rows(), r->row0_in_tile, r->tiles_x, r->tiles_y, 0, r->stream));
+    HIPCHECK(r, hipMemcpyAsync(lod, r->d_stage.p, px * 4, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    return ARCTIC_OK;
+}
+
+int arctic_write_lod(ArcticRenderer *r, const float *lod) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!lod) return r->fail(ARCTIC_E_INVALID, "write_lod: null");
+    if (!r->texture_mips) return r->fail(ARCTIC_E_STATE, "write_lod: no level-of-detail plane (ARCTIC_OPT_TEXTURE_MIPS is 0)");
+    if (!r->have_gbuffer) return r->fail(ARCTIC_E_STATE, "write_lod: no G-buffer to go with the plane (arctic_pass_gbuffer or arctic_write_gbuffer first)");
+    int rc = select_device(r);
+    if (rc) return rc;
+    const size_t px = (size_t)r->rows() * r->width;
+    HIPCHECK(r, r->d_stage.ensure(px * 4));
+    HIPCHECK(r, r->d_lod.ensure(r->n_tiles() * TILE_PIXELS * 4));
+    HIPCHECK(r, hipMemcpyAsync(r->d_stage.p, lod, px * 4, hipMemcpyHostToDevice, r->stream));
+    HIPCHECK(r, launch_plane_tile(r->d_lod.as<float>(), r->d_stage.as<float>(), r->width, r->rows(), r->row0_in_tile, r->tiles_x, r->tiles_y, 1, r->stream));
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    r->lod_valid = true;
+    return ARCTIC_OK;
+}
+
+int arctic_read_material_mip(ArcticRenderer *r, uint32_t material, uint32_t level, uint8_t *texels, uint32_t dims[2]) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (material >= r->tex.size() / 3) return r->fail(ARCTIC_E_INVALID, "read_material_mip: material %u does not exist", material);
+    const TexDesc &d0 = r->tex[3 * (size_t)material];
+    if (!(d0.w & TEX_INTERLEAVED)) return r->fail(ARCTIC_E_INVALID, "read_material_mip: material %u has images of unequal sizes (no packed image, one level)", material);
+    const std::vector<TexDesc> &chain = r->chains[material];
+    const uint32_t levels = chain.empty() ? 1u : (uint32_t)chain.size();
+    if (level >= levels) return r->fail(ARCTIC_E_INVALID, "read_material_mip: level %u beyond the material's %u", level, levels);
+    const TexDesc &d = chain.empty() ? d0 : chain[level];
+    const uint32_t w = d.w & ~TEX_INTERLEAVED, h = d.h;
+    if (dims) { dims[0] = w; dims[1] = h; }
+    if (!texels) return ARCTIC_OK;   // (the size alone)
+    int rc = select_device(r);
+    if (rc) return rc;
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    // the bordered image as stored (row-major or 4 x 4-texel tiles), unpacked on the host: a test's read-back
+    const uint32_t pw = w + 2, ph = h + 2, tpr = (pw + 3) / 4, trows = (ph + 3) / 4;
+    const size_t bytes = d.tile_row_bytes ? (size_t)tpr * trows * 128 : (size_t)pw * ph * 8;
+    std::vector<uint8_t> img(bytes);
+    HIPCHECK(r, hipMemcpy(img.data(), d.texels, bytes, hipMemcpyDeviceToHost));
+    for (uint32_t y = 0; y < h; ++y)
+        for (uint32_t x = 0; x < w; ++x) {
+            const uint32_t X = x + 1, Y = y + 1;
+            const size_t o = d.tile_row_bytes ? (size_t)(Y >> 2) * d.tile_row_bytes + (size_t)(X >> 2) * 128 + ((Y & 3) * 4 + (X & 3)) * 8 : ((size_t)Y * pw + X) * 8;
+            std::memcpy(texels + ((size_t)y * w + x) * 8, img.data() + o, 8);
+        }
     return ARCTIC_OK;
 }
 
@@ -1769,6 +1902,11 @@ int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
         break;
     case ARCTIC_OPT_TILE_TRACE: r->tile_trace = value != 0; break;
     case ARCTIC_OPT_TEXTURE_TILING: r->texture_tiling = value < 0 ? -1 : (value != 0); break;
+    case ARCTIC_OPT_TEXTURE_MIPS:
+        if (value < 0 || value > 1) return r->fail(ARCTIC_E_INVALID, "ARCTIC_OPT_TEXTURE_MIPS: 0 or 1");
+        if ((int)value != r->texture_mips) r->lod_valid = false;   // (the plane is made with the next G-buffer, or on demand from the visibility in place)
+        r->texture_mips = (int)value;
+        break;
     case ARCTIC_OPT_SAMPLER:
         if (value < 0 || (value & ~5ll)) return r->fail(ARCTIC_E_INVALID, "set_option: sampler is a mask of bit 0 (material footprints) and bit 2 (PCF taps); bit 1 (sRGB decode after filtering) exists in the oracle only");
         r->sampler = (int)value;

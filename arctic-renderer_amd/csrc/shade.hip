@@ -32,6 +32,7 @@
 #include "common.h"
 #include "edges.h"
 #include "shadow_coords.h"
+#include "texture_lod.h"
 
 namespace arctic {
 
@@ -1143,9 +1144,11 @@ __device__ __forceinline__ bool shade_tile_fast(SP sp, KernArgs args, const Args
 // ENV (k_envlit*): every covered pixel, shadowed or not, loads its second 48 bytes, normal, metalness and roughness and takes the
 // image-based ambient term instead of ambient * base; the light loop is still for lit pixels only.
 // SPOT (k_spotlit*): the light loop takes the spot lights too (lit_radiance<SPOT>).  CUBE (k_cubelit*): ... and the shadow-casting point lights.
-template <int LOOP, bool STATS, bool ENV = false, bool SPOT = false, bool CUBE = false, class Second>
+// MIP (k_miplit*, ARCTIC_OPT_TEXTURE_MIPS): the material's eight channels come trilinearly filtered from its chain (mip_material below), fetched
+// BEHIND the shadow test -- nothing of them is live across the 25-tap path, which sets the register count, and nothing is fetched twice.
+template <int LOOP, bool STATS, bool ENV = false, bool SPOT = false, bool CUBE = false, bool MIP = false, class Second>
 __device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty, uint32_t tx,
-                                           uint32_t lane, const TileHead &cur, Second second) {
+                                           uint32_t lane, const TileHead &cur, Second second, float lod = 0.0f /* MIP: the lane's lambda */) {
     const uint32_t x = tx * 8 + (lane & 7);
     const int32_t y = (int32_t)(ty * 8 + (lane >> 3)) - (int32_t)sp.row0_in_tile;
     const bool in_frame = x < sp.width && y >= 0 && y < (int32_t)sp.rows;
@@ -1193,7 +1196,7 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty,
             todo &= ~__ballot(mine);
         }
     };
-    fetch_material();
+    if (!MIP) fetch_material();
 
     // ---- B: shadow test, forward.hlsl:68-96 ----------------------------------------------------------------------
     float lit = 1.0f;
@@ -1205,7 +1208,7 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty,
             if (!decided) lit = shadow_slow(sh, spos, q8s);
             // the 25-tap path is what sets the kernel's register count: the texels fetched above are dropped across it and
             // fetched again (cache hits; such tiles are few) instead of being kept alive through it
-            fetch_material();
+            if (!MIP) fetch_material();
         }
     }
     // exact culling: see shade_tile_fast
@@ -1213,8 +1216,86 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty,
     float4 gc, gd, ge;
     if (ENV ? covered : live) second(sp.g.c, sp.g.d, sp.g.e, gc, gd, ge);   // second wave of loads: lit pixels only (48 B / pixel, whole 128-byte tile rows)
 
+    // ---- MIP: the material through its chain.  ch = {base r, g, b (decoded per texel, then filtered), normal r, g, b on the 0..255 scale, roughness,
+    // metalness}: each level's eight channels by the bilinear rule of mode 0 (the same functions: level 0 alone gives mode 0's bits), the two levels
+    // blended as a + (b - a) f with the full-precision fraction f; f == 0 keeps level l0's bits and fetches nothing of level l1.
+    // lambda differs lane by lane; a level's descriptor is wave-uniform (SGPRs, one s_load_dwordx8 from the material's table of levels): a waterfall
+    // over the levels present in the tile inside the waterfall over its materials, as the mixed-material tile does.  A tile of one material whose
+    // lanes agree on floor(lambda) -- most tiles -- runs two trips: its level and the level above.
+    float ch[8];
+    if (MIP) {
+        const auto filter8 = [&](const Taps &t, float out[8]) {
+            out[0] = filt_srgb<0>(t, lut); out[1] = filt_srgb<1>(t, lut); out[2] = filt_srgb<2>(t, lut);
+            out[3] = filt_bytes<0, 3>(t); out[4] = filt_bytes<1, 0>(t); out[5] = filt_bytes<1, 1>(t);
+            out[6] = filt_unorm<1, 2>(t); out[7] = filt_unorm<1, 3>(t);
+        };
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ch[i] = 0.0f;
+        unsigned long long todo = (sp.debug & 1) ? 0ull : __ballot(covered);
+        if (sp.debug & 1) {   // timing only: no texture traffic (the constants of fetch_material)
+            Taps t;
+            t.r0 = t.r1 = (u4v){0x808080u, 0u, 0x808080u, 0u}; t.w00 = t.w10 = t.w01 = t.w11 = 0.25f;
+            filter8(t, ch);
+        }
+        while (todo) {   // the distinct materials of the tile
+            const uint32_t m = __builtin_amdgcn_readlane(mat, __ffsll((long long)todo) - 1);
+            const bool mine = covered && mat == m;
+            const TexS d0 = tex_desc(sp.tex, m * 3);
+            if (!d0.packed) {   // images of unequal sizes: one level, the cold path of mode 0
+                if (mine) {
+                    Taps t0;
+                    fetch_taps_plain(d0, u, v, t0, q8m);
+                    base = mk(filt_srgb<0>(t0, lut), filt_srgb<1>(t0, lut), filt_srgb<2>(t0, lut));
+                    plain = true;
+                }
+            } else {
+                u8v tv;   // the material's MipTable (common.h): descriptor 3 m + 1
+                asm("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tv) : "s"(sp.tex + (m * 3 + 1)));
+                const uint32_t levels = __builtin_amdgcn_readfirstlane(tv[2]);
+                if (levels & TEX_INTERLEAVED) {   // a packed material without a chain (created with the option off): level 0
+                    if (mine) { Taps t; fetch_taps_packed(d0, u, v, t, q8m); filter8(t, ch); }
+                } else {
+                    // (readfirstlane returns an int: without the casts the low word is sign-extended over the high one)
+                    const TexDesc *table = reinterpret_cast<const TexDesc *>(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane(tv[1]) << 32) |
+                                                                             (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane(tv[0]));
+                    const float last = (float)(levels - 1u);
+                    float lam = lod > 0.0f ? lod : 0.0f;   // (a NaN gives 0; the plane may have been injected: arctic_write_lod)
+                    lam = lam < last ? lam : last;
+                    const float l0f = floorf(lam), f = lam - l0f;
+                    const uint32_t l0 = (uint32_t)l0f, l1 = min(l0 + 1u, levels - 1u);
+#pragma nounroll
+                    for (uint32_t pass = 0; pass < 2; ++pass) {
+                        const uint32_t lev = pass ? l1 : l0;
+                        const bool active = mine && (pass == 0 || f != 0.0f);
+                        unsigned long long td = __ballot(active);
+                        while (td) {   // the distinct levels these lanes ask for
+                            const uint32_t L = __builtin_amdgcn_readlane(lev, __ffsll((long long)td) - 1);
+                            const bool me = active && lev == L;
+                            const TexS dl = tex_desc(table, L);
+                            if (me) {
+                                Taps t;
+                                float r[8];
+                                fetch_taps_packed(dl, u, v, t, q8m);
+                                filter8(t, r);
+                                if (pass == 0) {
+#pragma unroll
+                                    for (int i = 0; i < 8; ++i) ch[i] = r[i];
+                                } else {
+#pragma unroll
+                                    for (int i = 0; i < 8; ++i) ch[i] = fm(r[i] - ch[i], f, ch[i]);
+                                }
+                            }
+                            td &= ~__ballot(me);
+                        }
+                    }
+                }
+            }
+            todo &= ~__ballot(mine);
+        }
+    }
+
     // ---- C: base colour; pixels without geometry: the skybox -----------------------------------------------------------
-    if (covered && !plain) base = mk(filt_srgb<0>(pt, lut), filt_srgb<1>(pt, lut), filt_srgb<2>(pt, lut));
+    if (covered && !plain) base = MIP ? mk(ch[0], ch[1], ch[2]) : mk(filt_srgb<0>(pt, lut), filt_srgb<1>(pt, lut), filt_srgb<2>(pt, lut));
     f3 color = base * sp.ambient;
     if (in_frame && !covered && sp.env) {
         const int gy = (row_global((int)ty, sp.band_tiles, sp.shard_count, sp.shard_index) + sp.tile_y0) * 8 + (int)(lane >> 3);
@@ -1228,7 +1309,8 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty,
     // ---- D: the lights ---------------------------------------------------------------------------------------------
     if (ENV ? covered : live) {
         float nr, ng, nb, rough, metal;
-        if (!plain) {
+        if (!plain && MIP) { nr = ch[3]; ng = ch[4]; nb = ch[5]; rough = ch[6]; metal = ch[7]; }
+        else if (!plain) {
             nr = filt_bytes<0, 3>(pt); ng = filt_bytes<1, 0>(pt); nb = filt_bytes<1, 1>(pt);
             rough = filt_unorm<1, 2>(pt); metal = filt_unorm<1, 3>(pt);   // metal-rough .g, .b (forward.hlsl:117,123)
         }
@@ -1348,8 +1430,8 @@ __device__ __forceinline__ bool next_tile(const ArgsA &A, const OrderArgs &O, co
 // under ENV, and the fast tile has no spot or shadow-casting point lights), in the geometric order (the order's slot holds the environment tables: ShadeParams::env_tables), with no statistics
 // and no trace.  A macro, not a device function: inlined through one more level, the walk comes out of the compiler with a few instructions
 // of k_material rescheduled.  `lut`: the kernel's sRGB table in LDS.
-#define WALK_GBUFFER(LOOP, STATS, ENV, SPOT, CUBE)                                                                                           \
-    constexpr bool PLAIN = !ENV && !SPOT && !CUBE;                                                                                           \
+#define WALK_GBUFFER(LOOP, STATS, ENV, SPOT, CUBE, MIP)                                                                                        \
+    constexpr bool PLAIN = !ENV && !SPOT && !CUBE && !MIP;                                                                                   \
     KernArgs args = kernel_args();                                                                                                           \
     unsigned long long t_entry = PLAIN ? trace_entry() : 0ull;                                                                               \
     const BlockId blk = block_id<1>();                                                                                                       \
@@ -1379,7 +1461,8 @@ _Pragma("nounroll")                                                             
             gc = gload_f4(pc + tile * 64, lane * 16u); gd = gload_f4(pd + tile * 64, lane * 16u); ge = gload_f4(pe + tile * 64, lane * 16u); \
         };                                                                                                                                   \
         const bool fast = PLAIN && shade_tile_fast<LOOP, STATS>(sp, args, A, lut, ty, tx, lane, cur, second);                                \
-        if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE>(sp, lut, ty, tx, lane, cur, second);                                             \
+        if (MIP) { if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE, MIP>(sp, lut, ty, tx, lane, cur, second, sp.lod[tile * 64 + lane]); }  \
+        else if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE>(sp, lut, ty, tx, lane, cur, second);                                        \
         if (PLAIN) trace_end(sp, A, tile, fast);                                                                                             \
         if (++k >= A.T) break;                                                                                                               \
         asm volatile("" : "+s"(args));                                                                                                       \
@@ -1391,25 +1474,33 @@ _Pragma("nounroll")                                                             
 template <int LOOP, bool STATS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_material(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, STATS, false, false, false);
+    WALK_GBUFFER(LOOP, STATS, false, false, false, false);
 }
 // the image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map)
 template <int LOOP>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_envlit(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, false, true, false, false);
+    WALK_GBUFFER(LOOP, false, true, false, false, false);
 }
 // spot lights (arctic_update_spot_lights, a non-empty list); ENV: with the image-based ambient as well
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_spotlit(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, false, ENV, true, false);
+    WALK_GBUFFER(LOOP, false, ENV, true, false, false);
 }
 // shadow-casting point lights (arctic_update_point_shadow_lights, a non-empty list), with the spot list (may be empty); ENV as above
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_cubelit(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, false, ENV, true, true);
+    WALK_GBUFFER(LOOP, false, ENV, true, true, false);
+}
+// trilinear material textures (ARCTIC_OPT_TEXTURE_MIPS = 1 and a material with a chain; ShadeParams::lod = the level-of-detail plane k_resolve_lod wrote or
+// arctic_write_lod injected): every tile through shade_tile<MIP>.  The spot and cube loops are compiled in unconditionally (empty lists loop zero times and
+// leave the sums as they were: the bits of the kernels without them), so that the mode composes with both without a kernel per combination; ENV as above.
+template <int LOOP, bool ENV>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_miplit(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    WALK_GBUFFER(LOOP, false, ENV, true, true, true);
 }
 
 // ---- the same without a G-buffer (whole frames): the tile walk straight from the visibility plane ----------------------
@@ -1419,8 +1510,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 // for the lit ones -- with the very operations of k_resolve (edges.h, fp contraction off), so the pixels are bit-identical
 // to the G-buffer path.  Everything after the attributes is shade_tile_fast / shade_tile, shared.  PLAIN, ENV, SPOT and CUBE as in
 // WALK_GBUFFER (k_material_vis; k_envlit_vis, k_spotlit_vis, k_cubelit_vis), and a macro for the same reason.
-#define WALK_VIS(LOOP, STATS, ENV, SPOT, CUBE)                                                                                                                      \
-    constexpr bool PLAIN = !ENV && !SPOT && !CUBE;                                                                                                                                   \
+#define WALK_VIS(LOOP, STATS, ENV, SPOT, CUBE, MIP)                                                                                                                 \
+    constexpr bool PLAIN = !ENV && !SPOT && !CUBE && !MIP;                                                                                                                           \
     KernArgs args = kernel_args();                                                                                                                                                   \
     unsigned long long t_entry = PLAIN ? trace_entry() : 0ull;                                                                                                                       \
     const BlockId blk = block_id<4>();                                                                                                                                               \
@@ -1536,7 +1627,15 @@ _Pragma("clang fp contract(off)")                                               
             }                                                                                                                                                                        \
         };                                                                                                                                                                           \
         const bool fast = PLAIN && shade_tile_fast<LOOP, STATS>(sp, args, A, lut, ty, tx, lane, cur, second);                                                                        \
-        if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE>(sp, lut, ty, tx, lane, cur, second);                                                                                     \
+        if (MIP) {   /* the pixel's level of detail: the record's own interpolation one pixel to the right and one down (texture_lod.h; the operations of k_resolve_lod) */             \
+            float lambda = 0.0f, wf, hf, last;                                                                                                                                       \
+            const uint32_t mat_ = __float_as_uint(cur.b2);                                                                                                                           \
+            if (key != ~0ull && mat_ < sp.n_materials && lod_material(sp.tex, mat_, wf, hf, last)) {                                                                                 \
+                const uint32_t ri = sp.rec_of[(uint32_t)key];                                                                                                                        \
+                lambda = pixel_lod(sp.recs[ri], sp.rrecs[ri], px, py, sp.xv[v0].attr, sp.xv[v1].attr, sp.xv[v2].attr, cur.a.x, cur.a.y, wf, hf, last);                               \
+            }                                                                                                                                                                        \
+            if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE, MIP>(sp, lut, ty, tx, lane, cur, second, lambda);                                                                    \
+        } else if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE>(sp, lut, ty, tx, lane, cur, second);                                                                              \
         if (PLAIN) trace_end(sp, A, (size_t)ty * A.tiles_x + tx, fast);                                                                                                              \
         if (++k >= A.T) break;                                                                                                                                                       \
         asm volatile("" : "+s"(args));                                                                                                                                               \
@@ -1548,22 +1647,27 @@ _Pragma("clang fp contract(off)")                                               
 template <int LOOP, bool STATS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_material_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, STATS, false, false, false);
+    WALK_VIS(LOOP, STATS, false, false, false, false);
 }
 template <int LOOP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_envlit_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, false, true, false, false);
+    WALK_VIS(LOOP, false, true, false, false, false);
 }
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_spotlit_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, false, ENV, true, false);
+    WALK_VIS(LOOP, false, ENV, true, false, false);
 }
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_cubelit_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, false, ENV, true, true);
+    WALK_VIS(LOOP, false, ENV, true, true, false);
+}
+template <int LOOP, bool ENV>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_miplit_vis(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    WALK_VIS(LOOP, false, ENV, true, true, true);
 }
 
 // ---- shadow bounds: the conservative min/max table calculate_lit tests first -------------------------------------------
@@ -1608,7 +1712,9 @@ __global__ __launch_bounds__(256) void k_post_process(const float4 *__restrict__
 template <int LOOP, bool STATS>
 hipError_t launch_variant(const ShadeParams &sp, const ShadeLaunch &L, dim3 grid) {
     if (L.from_vis) {   // four-wave workgroups, a strip of 4 tiles each (block_id<4>)
-        if (L.cube && L.env) k_cubelit_vis<LOOP, true><<<grid, 256, 0, L.stream>>>(sp);
+        if (L.mip && L.env) k_miplit_vis<LOOP, true><<<grid, 256, 0, L.stream>>>(sp);
+        else if (L.mip) k_miplit_vis<LOOP, false><<<grid, 256, 0, L.stream>>>(sp);
+        else if (L.cube && L.env) k_cubelit_vis<LOOP, true><<<grid, 256, 0, L.stream>>>(sp);
         else if (L.cube) k_cubelit_vis<LOOP, false><<<grid, 256, 0, L.stream>>>(sp);
         else if (L.spot && L.env) k_spotlit_vis<LOOP, true><<<grid, 256, 0, L.stream>>>(sp);
         else if (L.spot) k_spotlit_vis<LOOP, false><<<grid, 256, 0, L.stream>>>(sp);
@@ -1617,7 +1723,9 @@ hipError_t launch_variant(const ShadeParams &sp, const ShadeLaunch &L, dim3 grid
         return hipGetLastError();
     }
     grid.x = (grid.x + 7) / 8 * 32;   // one-wave workgroups (block_id<1>): four blocks per strip, a strip's blocks on one XCD
-    if (L.cube && L.env) k_cubelit<LOOP, true><<<grid, 64, 0, L.stream>>>(sp);
+    if (L.mip && L.env) k_miplit<LOOP, true><<<grid, 64, 0, L.stream>>>(sp);
+    else if (L.mip) k_miplit<LOOP, false><<<grid, 64, 0, L.stream>>>(sp);
+    else if (L.cube && L.env) k_cubelit<LOOP, true><<<grid, 64, 0, L.stream>>>(sp);
     else if (L.cube) k_cubelit<LOOP, false><<<grid, 64, 0, L.stream>>>(sp);
     else if (L.spot && L.env) k_spotlit<LOOP, true><<<grid, 64, 0, L.stream>>>(sp);
     else if (L.spot) k_spotlit<LOOP, false><<<grid, 64, 0, L.stream>>>(sp);
@@ -1643,7 +1751,7 @@ hipError_t launch_shade(const ShadeParams &sp_in, const ShadeLaunch &L) {
     const uint32_t bpr = (sp.tiles_x + 3) / 4, groups = (sp.tiles_y + 7) / 8;
     sp.group_stride = (groups + sp.tiles_per_wave - 1) / sp.tiles_per_wave;
     dim3 grid(8 * bpr, sp.group_stride);   // a block shades tiles_per_wave groups of 8 tile rows, group_stride groups apart
-    if (sp.tile_order && !L.env && !L.spot && !L.cube) // ... or tiles_per_wave consecutive slots of the prepass's dispatch order (n_jobs slots, common.h order_slot: a block = one XCD's list)
+    if (sp.tile_order && !L.env && !L.spot && !L.cube && !L.mip) // ... or tiles_per_wave consecutive slots of the prepass's dispatch order (n_jobs slots, common.h order_slot: a block = one XCD's list)
         grid = dim3((sp.n_jobs + sp.tiles_per_wave - 1) / sp.tiles_per_wave, 1);
     if (L.loop == 2) return L.stats ? launch_variant<2, true>(sp, L, grid) : launch_variant<2, false>(sp, L, grid);
     return L.stats ? launch_variant<1, true>(sp, L, grid) : launch_variant<1, false>(sp, L, grid);

@@ -110,6 +110,16 @@ class Renderer {
     [[nodiscard]] bool read_env_lighting(float *sh27, float *lut, uint32_t level, float *texels, uint32_t *dims) {
         return ok(arctic_read_env_lighting(m_handle, sh27, lut, level, texels, dims));
     }
+    // mip-mapped material textures with trilinear filtering (ARCTIC_OPT_TEXTURE_MIPS; the reference creates one level): set BEFORE create_material -- a
+    // material gets its chain when it is created -- and leave on while rendering.  The DX12 counterpart: MipLevels = 0 and a GenerateMips pass.
+    [[nodiscard]] bool set_texture_mips(bool on) { return ok(arctic_set_option(m_handle, ARCTIC_OPT_TEXTURE_MIPS, on ? 1 : 0)); }
+    // one level of a material's chain, 8 bytes per texel (arctic_read_material_mip); texels may be null: dims = {w, h} alone
+    [[nodiscard]] bool read_material_mip(uint32_t material, uint32_t level, uint8_t *texels, uint32_t dims[2]) {
+        return ok(arctic_read_material_mip(m_handle, material, level, texels, dims));
+    }
+    // the level-of-detail plane next to the G-buffer in place: one float per pixel, row-major over the handle's rows
+    [[nodiscard]] bool read_lod(float *lod) { return ok(arctic_read_lod(m_handle, lod)); }
+    [[nodiscard]] bool write_lod(const float *lod) { return ok(arctic_write_lod(m_handle, lod)); }
 
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }

@@ -226,6 +226,28 @@ class Renderer:
             raise ArcticError(-1, f"write_gbuffer: expected {(self.rows, self.width, 18)}, got {a.shape}")
         self._check(self.L.arctic_write_gbuffer(self.h, _ptr(a), _ptr(m)))
 
+    def read_lod(self):
+        """the level-of-detail plane of the G-buffer in place (set_option("texture_mips", 1)): (rows, width) float32"""
+        lod = np.empty((self.rows, self.width), np.float32)
+        self._check(self.L.arctic_read_lod(self.h, _ptr(lod)))
+        return lod
+
+    def write_lod(self, lod):
+        """inject a level-of-detail plane next to the G-buffer in place (write_gbuffer resets it to 0)"""
+        a = np.ascontiguousarray(lod, dtype=np.float32)
+        if a.shape != (self.rows, self.width):
+            raise ArcticError(-1, f"write_lod: expected {(self.rows, self.width)}, got {a.shape}")
+        self._check(self.L.arctic_write_lod(self.h, _ptr(a)))
+
+    def read_material_mip(self, material, level):
+        """level `level` of a material's chain (arctic_read_material_mip): (h, w, 8) uint8, per texel {diffuse r, g, b, normal r, g, b,
+        metal-rough g, b}; level 0 = the images as uploaded"""
+        dims = np.zeros(2, np.uint32)
+        self._check(self.L.arctic_read_material_mip(self.h, int(material), int(level), None, _ptr(dims)))
+        t = np.empty((int(dims[1]), int(dims[0]), 8), np.uint8)
+        self._check(self.L.arctic_read_material_mip(self.h, int(material), int(level), _ptr(t), _ptr(dims)))
+        return t
+
     def read_shadow_map(self):
         d = np.empty((self.shadow_size, self.shadow_size), np.float32)
         self._check(self.L.arctic_read_shadow_map(self.h, _ptr(d)))

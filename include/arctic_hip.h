@@ -462,7 +462,56 @@ int arctic_stats(ArcticRenderer *r, uint64_t *out, uint32_t n);
 #define ARCTIC_OPT_ENV_LIGHTING     25
 #define ARCTIC_OPT_POINT_SHADOW_SIZE 26 /* F, the side of each cube face of the shadow-casting point lights: a multiple of 8 in [8, 4096] (default 1024),
                                           otherwise ARCTIC_E_INVALID.  A change clears the faces to 1.0 and makes the next arctic_render_frame draw them. */
+/* ARCTIC_OPT_TEXTURE_MIPS: mip-mapped material textures with trilinear filtering (the reference creates one level, rhi.cpp:550, and samples
+ * it with MIN_MAG_MIP_LINEAR: a minified texture aliases, and every pixel's footprint is its own cache lines).
+ *   0 (default)  one level per material, sampled at level 0: as the reference renders, bit for bit, at the same speed.
+ *   1            at the time of arctic_create_material ("from now on", like ARCTIC_OPT_TEXTURE_TILING): a material whose three images have
+ *                equal size gets a full chain, built on the device, synchronously.  Materials with images of unequal sizes, and materials
+ *                created under 0, keep one level and are sampled at level 0 in every mode.
+ *                At shading time, once a material of the handle has a chain: trilinear filtering as below.  With no chain on the handle
+ *                mode 1 shades with the kernels of mode 0.
+ * The chain.  levels = 1 + floor(log2(max(w, h))); level k has w_k = max(1, w >> k), h_k = max(1, h >> k).  Texel (x, y) of level k + 1 is made
+ * from the four texels of level k in columns min(2x, w_k - 1), min(2x + 1, w_k - 1) and rows min(2y, h_k - 1), min(2y + 1, h_k - 1): an odd
+ * side drops its last row / column (it is never read: 2x + 1 <= 2 (w_k >> 1) - 1 < w_k - 1), and a side of 1 repeats its only texel.
+ *   normal .rgb, metal-rough .gb (UNORM8):  (a + b + c + d + 2) >> 2.
+ *   diffuse .rgb (sRGB8):  m = the mean of the four DECODED values, decoded with the 256-entry fp32 table the kernels use (code c ->
+ *     x = c / 255.0f; x <= 0.04045f ? x / 12.92f : powf((x + 0.055f) / 1.055f, 2.4f)), taken in binary64, where the sum of four such values
+ *     is exact.  The stored code is the one whose table value is nearest to m, the lower code on a tie (m against the binary64 midpoints
+ *     of neighbouring table entries: exact again).  Four equal codes give that code back; no pow on the way.
+ *   Level 0 is the image as uploaded (row-major or 4 x 4-texel tiles, ARCTIC_OPT_TEXTURE_TILING); levels 1.. are row-major.  A layout only.
+ *   The chain lives in one allocation of less than 2^32 bytes (8 bytes per texel, a one-texel border per level); a material whose chain
+ *   does not fit fails with ARCTIC_E_CAPACITY and leaves the handle as it was.
+ * The level of detail, per covered pixel (px, py) of a material with a chain: uv00 = the texture coordinates interpolated for the pixel;
+ * uv10, uv01 = the SAME triangle's perspective-correct interpolation evaluated at (px + 1, py) and (px, py + 1), extrapolated past the
+ * triangle's edge where the neighbour is outside it (what a GPU's helper lanes do; never a difference between two triangles).
+ *   rho^2 = max((w du_x)^2 + (h dv_x)^2, (w du_y)^2 + (h dv_y)^2),  du_x = u10 - u00 and so on, w, h the level-0 size;
+ *   lambda = 0.5 log2(rho^2) clamped to [0, levels - 1], a NaN giving 0.  Pixels without geometry and pixels of materials with one level: 0.
+ * arctic_pass_gbuffer leaves lambda in one more plane next to the G-buffer (arctic_read_lod / arctic_write_lod), arctic_render_frame computes
+ * it in the shading kernel with the same operations: the two paths agree bit for bit, as they do in mode 0.
+ * Sampling: l0 = floor(lambda), f = lambda - l0, l1 = min(l0 + 1, levels - 1).  Each of the two levels is sampled by the bilinear rule of
+ * mode 0 with that level's size (texel centres at +0.5, WRAP, sRGB decoded per texel before filtering, ARCTIC_OPT_SAMPLER bit 0 applying to
+ * the bilinear weights); the eight filtered channels (base colour rgb, normal rgb, roughness, metalness) blend as a + (b - a) f in fp32 with
+ * the full-precision f in every sampler mode; ps_main continues unchanged.  f == 0 returns level l0's bits: a plane of zeroes renders the
+ * bits of mode 0.
+ * Composes with ARCTIC_OPT_ENV_LIGHTING, spot lights and shadow-casting point lights.  ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE
+ * do not apply while mode 1 shades with a chain (a shading call then returns ARCTIC_E_STATE), ARCTIC_OPT_TILE_ORDER is ignored (the geometric
+ * order).  Not provided: anisotropic filtering, a LOD bias, chains for the environment map, the shadow maps or materials with images of
+ * unequal sizes, a chain supplied by the caller.  INTEGRATION.md section 5h: what a DX12 host sets. */
+#define ARCTIC_OPT_TEXTURE_MIPS     27
 int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value);
+
+/* Level `level` of a material's chain (ARCTIC_OPT_TEXTURE_MIPS; level 0 = the images as uploaded), for tests: dims = {w, h} of the level,
+   texels = w x h x 8 bytes, row-major, no border, per texel {diffuse r, g, b, normal r, g, b, metal-rough g, b}.  texels may be NULL (the size
+   alone).  ARCTIC_E_INVALID for a material that does not exist or has images of unequal sizes, and for a level beyond the material's
+   (a material without a chain has one).  Synchronises. */
+int arctic_read_material_mip(ArcticRenderer *r, uint32_t material, uint32_t level, uint8_t *texels, uint32_t dims[2]);
+
+/* The level-of-detail plane of the G-buffer in place (ARCTIC_OPT_TEXTURE_MIPS = 1): one float per pixel, row-major over the handle's rows
+   like arctic_read_gbuffer.  arctic_write_gbuffer resets the plane to 0 (an injected G-buffer has no triangles); arctic_write_lod after it
+   injects one (values outside [0, levels - 1] are clamped when they are used, a NaN counts as 0).  ARCTIC_E_STATE with the option off, and
+   without a G-buffer.  Both synchronise. */
+int arctic_read_lod(ArcticRenderer *r, float *lod);
+int arctic_write_lod(ArcticRenderer *r, const float *lod);
 
 /* The tables of ARCTIC_OPT_ENV_LIGHTING (no counterpart in the reference): sh27 = the 27 coefficients of E(n), coefficient k of channel c
    at 3 k + c (A_l folded in); lut = 64 x 64 x 2 floats, row = roughness cell; texels = specular level `level` (0 = the map), w x h x 4
