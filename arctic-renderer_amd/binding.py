@@ -31,6 +31,8 @@ SIGNATURES = {
     "arctic_use_own_stream": (_i32, [_vp]),
     "arctic_create_material": (_i32, [_vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _u32, _u32]),
     "arctic_create_mesh": (_i32, [_vp, _vp, _u64, _vp, _u64, _u64]),
+    "arctic_set_material_extras": (_i32, [_vp, _u64, _vp, _vp, _u32, _u32, _vp, _u32, _u32]),
+    "arctic_check_material_params": (_i32, [_vp]),
     "arctic_update_lights": (_i32, [_vp, _vp, _u64]),
     "arctic_update_spot_lights": (_i32, [_vp, _vp, _u64]),
     "arctic_spot_light_constants": (_i32, [_vp, _u64, _vp]),

@@ -233,6 +233,27 @@ constexpr uint32_t MAX_MIP_LEVELS = 16;   // image sides are below 65536
 __host__ __device__ inline uint32_t mip_level_count(uint32_t w, uint32_t h) { uint32_t n = 1; for (uint32_t m = w > h ? w : h; m > 1; m >>= 1) ++n; return n; }
 __host__ __device__ inline uint32_t mip_level_side(uint32_t n, uint32_t k) { return (n >> k) ? (n >> k) : 1u; }
 
+// ---- glTF material factors, emissive and occlusion (arctic_set_material_extras; the semantics are written once, in include/arctic_hip.h next to the call) ----
+// While a material of the handle is not neutral the texture table is longer: behind the 3 * n_materials descriptors sits ONE MaterialExtra per
+// material (128 bytes = four descriptor slots, so record m is sp.tex + 3 * n_materials + 4 * m), neutral materials included.  ShadeParams does
+// not change: the address follows from ShadeParams::tex and n_materials, and only the k_pbrlit* kernels read it.  The twelve constants come
+// through the scalar unit (one s_load_dwordx8 + one s_load_dwordx4 behind one wait) inside the waterfall over a tile's materials.
+//   FAST (flags bit 2): the material is packed and every image it has is of the packed image's size.  `emissive` then describes ONE image of
+//        4-byte texels {e.r, e.g, e.b, o} (an absent image's bytes are 255) with the packed image's one-texel WRAP border, row-major,
+//        pitch = w + 2: the footprint's first texel and the four weights are those of the material's level 0, the extras cost two 8-byte
+//        loads per lane.  `occlusion` is unused.
+//   otherwise `emissive` / `occlusion` are plain RGBA8 images (TexDesc as for unequal-size materials), each present when its flag bit is set.
+struct MaterialExtra {
+    float base_color[3], metallic, roughness, normal_scale, occlusion_strength, emissive0;   // dwords 0..7  (s_load_dwordx8)
+    float emissive1, emissive2;                                                             // dwords 8..9  (s_load_dwordx4 ...
+    uint32_t flags, pad0;                                                                   // dwords 10..11 ... )
+    uint32_t pad1[4];
+    TexDesc emissive, occlusion;                                                            // bytes 64, 96
+};
+static_assert(sizeof(MaterialExtra) == 128 && offsetof(MaterialExtra, emissive) == 64, "MaterialExtra: four descriptor slots");
+constexpr uint32_t EXTRA_EMISSIVE = 1u, EXTRA_OCCLUSION = 2u, EXTRA_FAST = 4u;
+constexpr uint32_t EXTRA_SLOTS = sizeof(MaterialExtra) / sizeof(TexDesc);
+
 // point light as uploaded (scene.hpp:88-94): float3 pos, pad, float3 color, pad = 2 x float4
 // The kernels' argument block.  The fields are ordered by WHEN a wave of k_material needs them, in 64-byte blocks, so that each
 // phase of a tile is ONE batch of scalar loads behind one wait (shade.hip: args_a / args_b / args_c / args_d) instead of a scalar-cache
@@ -335,6 +356,8 @@ struct ShadeLaunch {
     uint32_t mip;        // 1: k_miplit / k_miplit_vis with ENV = env, spot and cube loops compiled in (empty lists loop zero times): trilinear material
                          //    textures (ARCTIC_OPT_TEXTURE_MIPS; ShadeParams::lod for the G-buffer walk; geometric order, no statistics, no trace)
     uint32_t cube;       // 1: k_cubelit / k_cubelit_vis with ENV = env, spot lights included (ShadeParams::cubes, n_cubes, cube_size; geometric order, no statistics, no trace)
+    uint32_t pbr;        // 1: k_pbrlit / k_pbrlit_vis with ENV = env, MIP = mip, spot and cube loops compiled in: a material of the handle is not neutral
+                         //    (arctic_set_material_extras; MaterialExtra records behind the descriptors of ShadeParams::tex; geometric order, no statistics, no trace)
 };
 
 // ---- spot lights (arctic_update_spot_lights; semantics in include/arctic_hip.h next to the call) ---------------------------------------
@@ -456,6 +479,8 @@ void sun_proj_view(const float pos[3], const float rot_deg[2], float out[16]);
 // face k (0..5: +X, -X, +Y, -Y, +Z, -Z) of a shadow-casting point light: perspectiveRH_ZO(90 deg, 1, zn, zf) * lookAtRH(p, p + dir_k, up_k)
 void point_shadow_proj_view(const float pos[3], int face, float zn, float zf, float out[16]);
 float srgb8_to_linear(int c);
+// arctic_check_material_params: the twelve floats of an ArcticMaterialParams (include/arctic_hip.h) are all finite and in their ranges
+bool material_params_valid(const float p[12]);
 void camera_sky_basis(const float rot_deg[2], float aspect, float fov_y_deg, float fwd[3], float right[3], float up[3]);
 
 }  // namespace arctic

@@ -150,4 +150,13 @@ float srgb8_to_linear(int c) {
     return x <= 0.04045f ? x / 12.92f : std::pow((x + 0.055f) / 1.055f, 2.4f);
 }
 
+// ArcticMaterialParams (include/arctic_hip.h): base_color_factor[3], metallic, roughness in [0, 1]; normal_scale finite; occlusion_strength
+// in [0, 1]; emissive_factor[3] finite and >= 0; reserved[2] zero
+bool material_params_valid(const float p[12]) {
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(p[i])) return false;
+    for (int i : {0, 1, 2, 3, 4, 6}) if (!(p[i] >= 0.0f && p[i] <= 1.0f)) return false;
+    for (int i : {7, 8, 9}) if (!(p[i] >= 0.0f)) return false;
+    return p[10] == 0.0f && p[11] == 0.0f;
+}
+
 }  // namespace arctic

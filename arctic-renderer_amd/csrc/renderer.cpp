@@ -193,6 +193,17 @@ struct ArcticRenderer {
     std::vector<Mesh> meshes;
     std::vector<TexDesc> tex;        // 3 per material (device pointers)
     std::vector<void *> tex_allocs;
+    // arctic_set_material_extras: one entry per material.  While a material is not neutral (n_extras != 0) the device's texture table carries a
+    // MaterialExtra record per material behind the descriptors (common.h) and every shading call takes the k_pbrlit* kernels (has_extras).
+    struct Extras {
+        float p[12] = {1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+        void *d_emissive = nullptr, *d_occlusion = nullptr, *d_fast = nullptr;   // plain RGBA8 images, or the one {e.rgb, o} image of the fast path
+        uint32_t ew = 0, eh = 0, ow = 0, oh = 0;
+        bool neutral = true;
+    };
+    std::vector<Extras> extras;
+    uint32_t n_extras = 0;
+    bool has_extras() const { return n_extras != 0; }
     DevBuf d_tex, d_lut, d_lights, d_light_pairs, d_env;
     // the shadow map, and the min/max of it per 4x4 texel block / per 4x4-aligned 8x8 block (k_shadow_bounds).  Two sets: a frame in
     // flight that redraws the map draws into the other one while the previous frame's shading still reads this one (the second set
@@ -780,6 +791,8 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
         return r->fail(ARCTIC_E_STATE, "shade: ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply with spot lights (arctic_update_spot_lights)");
     if (r->n_cubes && (r->count_evals || r->tile_trace))
         return r->fail(ARCTIC_E_STATE, "shade: ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply with shadow-casting point lights (arctic_update_point_shadow_lights)");
+    if (r->has_extras() && (r->count_evals || r->tile_trace))
+        return r->fail(ARCTIC_E_STATE, "shade: ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply while a material has extras (arctic_set_material_extras)");
     std::memset(&sp, 0, sizeof sp);
     sp.g = r->gbuffer();
     const ArcticRenderer::GeoSet &G = r->geo[r->fwd()];
@@ -824,7 +837,7 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
     if (r->n_cubes) { sp.cubes = r->d_cubes.as<float4>(); sp.n_cubes = r->n_cubes; sp.cube_size = r->cube_size; }   // (the trace's slot: k_cubelit* keep none)
     // (the order was built for groups of order_group tiles per wave: a pass that shades another number per wave takes the geometric order)
     if (r->env_active()) sp.env_tables = r->d_env_tables.as<EnvTables>();   // (the geometric order: the tables take the order's slot)
-    else if (r->n_spots || r->n_cubes || r->mips_active()) {}                                    // (k_spotlit*, k_cubelit*: the geometric order)
+    else if (r->n_spots || r->n_cubes || r->mips_active() || r->has_extras()) {}                                    // (k_spotlit*, k_cubelit*: the geometric order)
     else if (!from_vis && r->have_order && r->tile_order && (r->tiles_per_wave == 0 || r->tiles_per_wave == r->order_group)) {
         sp.tile_order = r->d_tile_order.as<uint32_t>(); sp.n_jobs = r->order_slots; sp.tiles_per_wave = r->order_group;
     }
@@ -859,6 +872,7 @@ hipError_t shade_once(ArcticRenderer *r, const ShadeParams &sp, bool from_vis, b
     L.spot = sp.n_spots ? 1u : 0u;
     L.cube = sp.n_cubes ? 1u : 0u;
     L.mip = r->mips_active() ? 1u : 0u;
+    L.pbr = r->has_extras() ? 1u : 0u;
     return launch_shade(sp, L);
 }
 
@@ -930,6 +944,31 @@ int check_item_overflow(ArcticRenderer *r) {
                    "is incomplete; the tables grow on the next pass -- render the frame again", need, std::max(r->geo[0].item_cap, r->geo[1].item_cap));
 }
 
+// The device's texture table: the 3 * n_materials descriptors and, while a material has extras, one MaterialExtra per material behind them
+// (common.h).  Uploaded whenever either part changes; the caller has drained the stream.
+int upload_tex_table(ArcticRenderer *r) {
+    const size_t n = r->tex.size() / 3, desc_bytes = r->tex.size() * sizeof(TexDesc);
+    std::vector<char> table(desc_bytes + (r->has_extras() ? n * sizeof(MaterialExtra) : 0));
+    std::memcpy(table.data(), r->tex.data(), desc_bytes);
+    for (size_t m = 0; r->has_extras() && m < n; ++m) {
+        const ArcticRenderer::Extras &x = r->extras[m];
+        MaterialExtra e = {};
+        std::memcpy(&e.base_color[0], x.p, 10 * sizeof(float));   // base_color .. emissive2 are the first ten floats of both
+        if (x.d_fast) {
+            const uint32_t w = r->tex[3 * m].w & ~TEX_INTERLEAVED, h = r->tex[3 * m].h;
+            e.flags = EXTRA_FAST | (x.ew ? EXTRA_EMISSIVE : 0u) | (x.ow ? EXTRA_OCCLUSION : 0u);
+            e.emissive = TexDesc{static_cast<const uint32_t *>(x.d_fast), w, h, (float)w, (float)h, w + 2, 0u};
+        } else {
+            if (x.d_emissive) { e.flags |= EXTRA_EMISSIVE; e.emissive = TexDesc{static_cast<const uint32_t *>(x.d_emissive), x.ew, x.eh, (float)x.ew, (float)x.eh, x.ew, 0u}; }
+            if (x.d_occlusion) { e.flags |= EXTRA_OCCLUSION; e.occlusion = TexDesc{static_cast<const uint32_t *>(x.d_occlusion), x.ow, x.oh, (float)x.ow, (float)x.oh, x.ow, 0u}; }
+        }
+        std::memcpy(table.data() + desc_bytes + m * sizeof(MaterialExtra), &e, sizeof e);
+    }
+    HIPCHECK(r, r->d_tex.ensure(std::max<size_t>(48, table.size())));
+    if (!table.empty()) HIPCHECK(r, hipMemcpy(r->d_tex.p, table.data(), table.size(), hipMemcpyHostToDevice));
+    return ARCTIC_OK;
+}
+
 bool valid_scene(const ArcticScene *sc) { return sc && (sc->n_objects == 0 || sc->objects); }
 
 }  // namespace
@@ -937,7 +976,7 @@ bool valid_scene(const ArcticScene *sc) { return sc && (sc->n_objects == 0 || sc
 // =================================================================================================
 extern "C" {
 
-int arctic_version(void) { return 310; }
+int arctic_version(void) { return 320; }
 
 ArcticRenderer *arctic_create(const ArcticCreateInfo *info, char *err, uint64_t err_len) {
     auto say = [&](const char *m) { if (err && err_len) { std::snprintf(err, (size_t)err_len, "%s", m); } };
@@ -1037,6 +1076,7 @@ void arctic_destroy(ArcticRenderer *r) {
     if (r->own_stream) { (void)hipStreamSynchronize(r->own_stream); (void)hipStreamDestroy(r->own_stream); }
     for (Mesh &m : r->meshes) { if (m.d_vertices) (void)hipFree(m.d_vertices); if (m.d_indices) (void)hipFree(m.d_indices); }
     for (void *p : r->tex_allocs) (void)hipFree(p);
+    for (ArcticRenderer::Extras &x : r->extras) for (void *p : {x.d_emissive, x.d_occlusion, x.d_fast}) if (p) (void)hipFree(p);
     DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_spots, &r->d_cubes, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4, &r->d_lod,
                       &r->d_rgba8, &r->d_ldr, &r->d_hdr, &r->d_counter, &r->d_shadow_blocks_set[0], &r->d_shadow_blocks_set[1], &r->d_shadow_bounds_set[0], &r->d_shadow_bounds_set[1], &r->d_staging, &r->d_layout, &r->geo[0].d_xverts, &r->geo[1].d_xverts, &r->geo[2].d_xverts,
                       &r->geo[2].d_recs, &r->geo[2].d_rrecs, &r->geo[2].d_clip_list, &r->geo[2].d_rec_of, &r->geo[2].d_items, &r->tables[2].d,
@@ -1187,10 +1227,68 @@ int arctic_create_material(ArcticRenderer *r, const void *diffuse, uint32_t dw, 
     r->tex.insert(r->tex.end(), td, td + 3);
     if (!chain.empty()) ++r->n_chains;
     r->chains.push_back(std::move(chain));
+    r->extras.emplace_back();
     HIPCHECK(r, hipStreamSynchronize(r->stream));
-    HIPCHECK(r, r->d_tex.ensure(r->tex.size() * sizeof(TexDesc)));
-    HIPCHECK(r, hipMemcpy(r->d_tex.p, r->tex.data(), r->tex.size() * sizeof(TexDesc), hipMemcpyHostToDevice));
+    if (int up = upload_tex_table(r)) return up;
     return (int)(r->tex.size() / 3) - 1;
+}
+
+int arctic_check_material_params(const ArcticMaterialParams *params) {
+    return params && material_params_valid(params->base_color_factor) ? ARCTIC_OK : ARCTIC_E_INVALID;
+}
+
+int arctic_set_material_extras(ArcticRenderer *r, uint64_t material, const ArcticMaterialParams *params, const void *emissive, uint32_t ew, uint32_t eh,
+                               const void *occlusion, uint32_t ow, uint32_t oh) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (material >= r->tex.size() / 3) return r->fail(ARCTIC_E_INVALID, "set_material_extras: material %llu does not exist", (unsigned long long)material);
+    if (params && arctic_check_material_params(params) != ARCTIC_OK)
+        return r->fail(ARCTIC_E_INVALID, "set_material_extras: a field out of range or not finite, or a non-zero reserved field");
+    if ((emissive != nullptr) != (ew != 0 && eh != 0) || (!emissive && (ew | eh)) || (occlusion != nullptr) != (ow != 0 && oh != 0) || (!occlusion && (ow | oh)))
+        return r->fail(ARCTIC_E_INVALID, "set_material_extras: an image with a side of 0, or a size without an image");
+    if ((ew | eh | ow | oh) & 0xFFFF0000u) return r->fail(ARCTIC_E_CAPACITY, "set_material_extras: image side above 65535");
+    if ((uint64_t)ew * eh > (1ull << 30) || (uint64_t)ow * oh > (1ull << 30)) return r->fail(ARCTIC_E_CAPACITY, "set_material_extras: image above 2^30 texels");
+    int rc = select_device(r);
+    if (rc) return rc;
+    ArcticRenderer::Extras nx;
+    if (params) std::memcpy(nx.p, params->base_color_factor, sizeof nx.p);
+    nx.ew = ew; nx.eh = eh; nx.ow = ow; nx.oh = oh;
+    const ArcticRenderer::Extras neutral;
+    nx.neutral = !emissive && !occlusion && std::memcmp(nx.p, neutral.p, sizeof nx.p) == 0;
+    // the new images first: a failed allocation leaves the material as it was
+    const TexDesc &d0 = r->tex[3 * material];
+    const uint32_t mw = d0.w & ~TEX_INTERLEAVED, mh = d0.h;
+    const bool fast = (d0.w & TEX_INTERLEAVED) && (emissive || occlusion) && (!emissive || (ew == mw && eh == mh)) && (!occlusion || (ow == mw && oh == mh));
+    const auto drop = [](ArcticRenderer::Extras &x) { for (void **p : {&x.d_emissive, &x.d_occlusion, &x.d_fast}) if (*p) { (void)hipFree(*p); *p = nullptr; } };
+    const auto upload = [&](void **dst, const void *src, size_t bytes) {
+        if (hipMalloc(dst, bytes) != hipSuccess) { *dst = nullptr; return false; }
+        return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    bool ok = true;
+    if (fast) {   // one image of 4-byte texels {e.r, e.g, e.b, o} with the packed image's one-texel WRAP border (common.h MaterialExtra)
+        const uint32_t pw = mw + 2, ph = mh + 2;
+        std::vector<uint32_t> texels((size_t)pw * ph);
+        const uint8_t *e = static_cast<const uint8_t *>(emissive), *o = static_cast<const uint8_t *>(occlusion);
+        for (uint32_t Y = 0; Y < ph; ++Y) {
+            const size_t sy = (size_t)((Y + mh - 1) % mh) * mw;
+            for (uint32_t X = 0; X < pw; ++X) {
+                const size_t i = sy + (X + mw - 1) % mw;
+                const uint32_t rgb = e ? ((uint32_t)e[4 * i] | ((uint32_t)e[4 * i + 1] << 8) | ((uint32_t)e[4 * i + 2] << 16)) : 0xFFFFFFu;
+                texels[(size_t)Y * pw + X] = rgb | ((o ? (uint32_t)o[4 * i] : 255u) << 24);
+            }
+        }
+        ok = upload(&nx.d_fast, texels.data(), texels.size() * 4);
+    } else {
+        if (emissive) ok = upload(&nx.d_emissive, emissive, (size_t)ew * eh * 4);
+        if (ok && occlusion) ok = upload(&nx.d_occlusion, occlusion, (size_t)ow * oh * 4);
+    }
+    if (!ok) { drop(nx); return r->fail(ARCTIC_E_DEVICE, "set_material_extras: hipMalloc / upload of an image"); }
+    HIPCHECK(r, hipStreamSynchronize(r->stream));   // (a pass in flight may still read the table and the images it replaces)
+    ArcticRenderer::Extras &cur = r->extras[material];
+    const bool table_changes = !(cur.neutral && nx.neutral);
+    r->n_extras += (nx.neutral ? 0u : 1u) - (cur.neutral ? 0u : 1u);
+    drop(cur);
+    cur = nx;
+    return table_changes ? upload_tex_table(r) : ARCTIC_OK;
 }
 
 int arctic_create_mesh(ArcticRenderer *r, const ArcticVertex *vertices, uint64_t n_vertices, const uint32_t *indices,

@@ -289,6 +289,24 @@ __device__ __forceinline__ void fetch_taps_plain(const TexS &d, float u, float v
     t.r0.y = t.r0.w = t.r1.y = t.r1.w = 0u;
     tap_weights(fx, fy, t);
 }
+// the FAST image of a material's extras (common.h MaterialExtra): 4-byte texels {e.r, e.g, e.b, o} with the packed image's one-texel border, row-major.
+// The coordinate arithmetic is fetch_taps_packed's on the same sizes, so the footprint and the four weights are the material's own at level 0;
+// two 8-byte loads (4-byte aligned), the words where filt_srgb / filt_bytes<0, K> look for a plain image's
+typedef uint32_t u2u __attribute__((ext_vector_type(2), aligned(4)));
+__device__ __forceinline__ void fetch_taps_extra(const TexS &d, float u, float v, Taps &t, bool q8 = false) {
+    int x0, y0;
+    float fx, fy;
+    float x = axis_scaled(u, d.wf), y = axis_scaled(v, d.hf);
+    if (q8) { asm volatile(""); x = snap256(x); y = snap256(y); }
+    axis_split(x, x0, fx);
+    axis_split(y, y0, fy);
+    const uint32_t o = ((uint32_t)(__mul24(y0, (int)d.pitch) + x0) + (d.pitch + 1u)) << 2;   // padded texel (x0 + 1, y0 + 1), as fetch_taps_packed
+    const u2u a = *(const u2u __attribute__((address_space(1))) *)((gchar)d.texels + o);
+    const u2u b = *(const u2u __attribute__((address_space(1))) *)((gchar)(d.texels + (size_t)d.pitch * 4u) + o);
+    t.r0 = (u4v){a.x, 0u, a.y, 0u};
+    t.r1 = (u4v){b.x, 0u, b.y, 0u};
+    tap_weights(fx, fy, t);
+}
 // byte k of a word as float: v_cvt_f32_ubyteK, one instruction
 template <int K> __device__ __forceinline__ float ubyte(uint32_t w) { return (float)((w >> (8 * K)) & 0xFFu); }
 // UNORM8 channel (byte K of word W of the texel), bilinear, scaled to [0,1]
@@ -783,6 +801,11 @@ __device__ __forceinline__ f3 get_normal(float nr, float ng, float nb, const flo
     const float r = snorm_of_bytes(nr), g = -snorm_of_bytes(ng), b = snorm_of_bytes(nb);   // (1 - g) * 2 - 1 = -(2 g - 1); nr, ng, nb on the 0..255 scale
     return normalize(mk(fm(ge.y, b, fm(gd.z, g, gc.w * r)), fm(ge.z, b, fm(gd.w, g, gd.x * r)), fm(ge.w, b, fm(ge.x, g, gd.y * r))));
 }
+// PBR (k_pbrlit*): glTF's normalTexture.scale on the tangent-space x and y (scale 1 multiplies exactly: get_normal's bits)
+__device__ __forceinline__ f3 get_normal_scaled(float nr, float ng, float nb, const float4 &gc, const float4 &gd, const float4 &ge, float scale) {
+    const float r = snorm_of_bytes(nr) * scale, g = -snorm_of_bytes(ng) * scale, b = snorm_of_bytes(nb);
+    return normalize(mk(fm(ge.y, b, fm(gd.z, g, gc.w * r)), fm(ge.z, b, fm(gd.w, g, gd.x * r)), fm(ge.w, b, fm(ge.x, g, gd.y * r))));
+}
 // SPOT (k_spotlit*): behind the point lights (either loop), the spot lights join the scalar sums through spot_sums.
 // ---- spot lights (arctic_update_spot_lights; semantics in include/arctic_hip.h): one scalar loop, 3 float4 per light through the
 // scalar cache, {p.xyz, scale} {s.xyz, offset} {rgb, ir2} (common.h SpotDev).  The light's colour is scaled by f = att * window and then
@@ -867,10 +890,10 @@ __device__ __forceinline__ void cube_sums(SP sp, const LoopPix &px, float A[3], 
         C[0] = __builtin_fmaf(cr, s3, C[0]); C[1] = __builtin_fmaf(cg, s3, C[1]); C[2] = __builtin_fmaf(cb, s3, C[2]);
     }
 }
-template <int LOOP, bool STATS, bool SPOT = false, bool CUBE = false>
+template <int LOOP, bool STATS, bool SPOT = false, bool CUBE = false, bool PBR = false>
 __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float ng, float nb, float rough, float metal, f3 base,
-                                           const float4 &gc, const float4 &gd, const float4 &ge) {
-    const f3 n = get_normal(nr, ng, nb, gc, gd, ge);
+                                           const float4 &gc, const float4 &gd, const float4 &ge, float nscale = 1.0f /* PBR: normalTexture.scale */) {
+    const f3 n = PBR ? get_normal_scaled(nr, ng, nb, gc, gd, ge, nscale) : get_normal(nr, ng, nb, gc, gd, ge);
     const f3 world = mk(gc.x, gc.y, gc.z);
     const LightArgs la = light_args(sp);   // one batch of scalar loads, in the shadow of the tile's second wave of vector loads
     const f3 wo = normalize(mk(la.eye[0], la.eye[1], la.eye[2]) - world);
@@ -1146,7 +1169,10 @@ __device__ __forceinline__ bool shade_tile_fast(SP sp, KernArgs args, const Args
 // SPOT (k_spotlit*): the light loop takes the spot lights too (lit_radiance<SPOT>).  CUBE (k_cubelit*): ... and the shadow-casting point lights.
 // MIP (k_miplit*, ARCTIC_OPT_TEXTURE_MIPS): the material's eight channels come trilinearly filtered from its chain (mip_material below), fetched
 // BEHIND the shadow test -- nothing of them is live across the 25-tap path, which sets the register count, and nothing is fetched twice.
-template <int LOOP, bool STATS, bool ENV = false, bool SPOT = false, bool CUBE = false, bool MIP = false, class Second>
+// PBR (k_pbrlit*, arctic_set_material_extras): the material's factors, emissive and occlusion from its MaterialExtra record (common.h), read through
+// the scalar unit in a waterfall over the tile's materials of its own; the two images at level 0 whatever MIP says.  A neutral record multiplies
+// by 1.0f and adds +0.0f: such a pixel keeps the bits the kernel without PBR gives it.
+template <int LOOP, bool STATS, bool ENV = false, bool SPOT = false, bool CUBE = false, bool MIP = false, bool PBR = false, class Second>
 __device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty, uint32_t tx,
                                            uint32_t lane, const TileHead &cur, Second second, float lod = 0.0f /* MIP: the lane's lambda */) {
     const uint32_t x = tx * 8 + (lane & 7);
@@ -1296,7 +1322,50 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty,
 
     // ---- C: base colour; pixels without geometry: the skybox -----------------------------------------------------------
     if (covered && !plain) base = MIP ? mk(ch[0], ch[1], ch[2]) : mk(filt_srgb<0>(pt, lut), filt_srgb<1>(pt, lut), filt_srgb<2>(pt, lut));
+    // ---- PBR: the material's extras.  base' = base * base_color_factor here; the other factors where their channels are formed (D)
+    float x_metal = 1.0f, x_rough = 1.0f, x_nscale = 1.0f, ao = 1.0f;
+    f3 emis = mk(0.0f, 0.0f, 0.0f);
+    if (PBR) {
+        const TexDesc *records = sp.tex + sp.n_materials * 3u;   // behind the descriptors (common.h MaterialExtra)
+        unsigned long long todo = __ballot(covered);
+        while (todo) {   // the distinct materials of the tile: nearly always one trip
+            const uint32_t m = __builtin_amdgcn_readlane(mat, __ffsll((long long)todo) - 1);
+            const bool mine = covered && mat == m;
+            const TexDesc *rec = records + m * EXTRA_SLOTS;
+            u8v ka;   // base_color_factor rgb, metallic, roughness, normal scale, occlusion strength, emissive r
+            u4v kb;   // emissive g, b, flags
+            asm("s_load_dwordx8 %0, %2, 0x0\n\ts_load_dwordx4 %1, %2, 0x20\n\ts_waitcnt lgkmcnt(0)" : "=&s"(ka), "=&s"(kb) : "s"(rec));
+            const uint32_t flags = __builtin_amdgcn_readfirstlane(kb[2]);
+            float er = 1.0f, eg = 1.0f, eb = 1.0f, occ = 1.0f;   // no image: 1
+            if (flags & EXTRA_FAST) {   // (wave-uniform) images of the packed image's size: one 4-byte texel {e.rgb, o}, the material's own footprint
+                const TexS dx = tex_desc(rec, 2);
+                if (mine) {
+                    Taps t;
+                    fetch_taps_extra(dx, u, v, t, q8m);
+                    if (flags & EXTRA_EMISSIVE) { er = filt_srgb<0>(t, lut); eg = filt_srgb<1>(t, lut); eb = filt_srgb<2>(t, lut); }
+                    if (flags & EXTRA_OCCLUSION) occ = filt_unorm<0, 3>(t);
+                }
+            } else {                    // cold: plain RGBA8 images of any size, one at a time
+                if (flags & EXTRA_EMISSIVE) {
+                    const TexS de = tex_desc(rec, 2);
+                    if (mine) { Taps t; fetch_taps_plain(de, u, v, t, q8m); er = filt_srgb<0>(t, lut); eg = filt_srgb<1>(t, lut); eb = filt_srgb<2>(t, lut); }
+                }
+                if (flags & EXTRA_OCCLUSION) {
+                    const TexS dq = tex_desc(rec, 3);
+                    if (mine) { Taps t; fetch_taps_plain(dq, u, v, t, q8m); occ = filt_unorm<0, 0>(t); }
+                }
+            }
+            if (mine) {
+                base = mk(base.x * __uint_as_float(ka[0]), base.y * __uint_as_float(ka[1]), base.z * __uint_as_float(ka[2]));
+                x_metal = __uint_as_float(ka[3]); x_rough = __uint_as_float(ka[4]); x_nscale = __uint_as_float(ka[5]);
+                ao = fm(__uint_as_float(ka[6]), occ - 1.0f, 1.0f);   // 1 + strength (o - 1)
+                emis = mk(er * __uint_as_float(ka[7]), eg * __uint_as_float(kb[0]), eb * __uint_as_float(kb[1]));
+            }
+            todo &= ~__ballot(mine);
+        }
+    }
     f3 color = base * sp.ambient;
+    if (PBR && !ENV) color = color * ao;   // occlusion scales the indirect term only (uncovered lanes: ao = 1, and the skybox replaces the colour below)
     if (in_frame && !covered && sp.env) {
         const int gy = (row_global((int)ty, sp.band_tiles, sp.shard_count, sp.shard_index) + sp.tile_y0) * 8 + (int)(lane >> 3);
         const float nx = __builtin_fmaf((float)x + 0.5f, sp.ndc_sx, -1.0f), ny = __builtin_fmaf(-((float)gy + 0.5f), sp.ndc_sy, 1.0f);
@@ -1330,16 +1399,19 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty,
                 todo &= ~__ballot(mine);
             }
         }
+        if (PBR) { metal = metal * x_metal; rough = rough * x_rough; }
         if (ENV) {   // the image-based ambient replaces ambient * base (n, wo: what lit_radiance takes)
-            const f3 n = get_normal(nr, ng, nb, gc, gd, ge);
+            const f3 n = PBR ? get_normal_scaled(nr, ng, nb, gc, gd, ge, x_nscale) : get_normal(nr, ng, nb, gc, gd, ge);
             const f3 wo = normalize(mk(sp.eye[0], sp.eye[1], sp.eye[2]) - mk(gc.x, gc.y, gc.z));
             color = env_ambient(sp.env_tables, n, wo, base, metal, rough) * sp.ambient;
+            if (PBR) color = color * ao;
         }
         if (!ENV || live) {
-            const f3 Lo = lit_radiance<LOOP, STATS, SPOT, CUBE>(sp, lane, nr, ng, nb, rough, metal, base, gc, gd, ge);
+            const f3 Lo = lit_radiance<LOOP, STATS, SPOT, CUBE, PBR>(sp, lane, nr, ng, nb, rough, metal, base, gc, gd, ge, x_nscale);
             color = mk(__builtin_fmaf(Lo.x, lit, color.x), __builtin_fmaf(Lo.y, lit, color.y), __builtin_fmaf(Lo.z, lit, color.z));
         }
     }
+    if (PBR && covered) color = color + emis;   // emission: no (1 - shadow), no occlusion
 
     // ---- E: post_process + store ---------------------------------------------------------------------------------------
     if (in_frame) store_pixel(store_args(sp), sp.out_rgba8, o, o, color);
@@ -1430,7 +1502,7 @@ __device__ __forceinline__ bool next_tile(const ArgsA &A, const OrderArgs &O, co
 // under ENV, and the fast tile has no spot or shadow-casting point lights), in the geometric order (the order's slot holds the environment tables: ShadeParams::env_tables), with no statistics
 // and no trace.  A macro, not a device function: inlined through one more level, the walk comes out of the compiler with a few instructions
 // of k_material rescheduled.  `lut`: the kernel's sRGB table in LDS.
-#define WALK_GBUFFER(LOOP, STATS, ENV, SPOT, CUBE, MIP)                                                                                        \
+#define WALK_GBUFFER(LOOP, STATS, ENV, SPOT, CUBE, MIP, PBR)                                                                                        \
     constexpr bool PLAIN = !ENV && !SPOT && !CUBE && !MIP;                                                                                   \
     KernArgs args = kernel_args();                                                                                                           \
     unsigned long long t_entry = PLAIN ? trace_entry() : 0ull;                                                                               \
@@ -1461,8 +1533,8 @@ _Pragma("nounroll")                                                             
             gc = gload_f4(pc + tile * 64, lane * 16u); gd = gload_f4(pd + tile * 64, lane * 16u); ge = gload_f4(pe + tile * 64, lane * 16u); \
         };                                                                                                                                   \
         const bool fast = PLAIN && shade_tile_fast<LOOP, STATS>(sp, args, A, lut, ty, tx, lane, cur, second);                                \
-        if (MIP) { if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE, MIP>(sp, lut, ty, tx, lane, cur, second, sp.lod[tile * 64 + lane]); }  \
-        else if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE>(sp, lut, ty, tx, lane, cur, second);                                        \
+        if (MIP) { if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE, MIP, PBR>(sp, lut, ty, tx, lane, cur, second, sp.lod[tile * 64 + lane]); }  \
+        else if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE, false, PBR>(sp, lut, ty, tx, lane, cur, second);                                        \
         if (PLAIN) trace_end(sp, A, tile, fast);                                                                                             \
         if (++k >= A.T) break;                                                                                                               \
         asm volatile("" : "+s"(args));                                                                                                       \
@@ -1474,25 +1546,25 @@ _Pragma("nounroll")                                                             
 template <int LOOP, bool STATS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_material(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, STATS, false, false, false, false);
+    WALK_GBUFFER(LOOP, STATS, false, false, false, false, false);
 }
 // the image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1 with a map)
 template <int LOOP>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_envlit(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, false, true, false, false, false);
+    WALK_GBUFFER(LOOP, false, true, false, false, false, false);
 }
 // spot lights (arctic_update_spot_lights, a non-empty list); ENV: with the image-based ambient as well
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_spotlit(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, false, ENV, true, false, false);
+    WALK_GBUFFER(LOOP, false, ENV, true, false, false, false);
 }
 // shadow-casting point lights (arctic_update_point_shadow_lights, a non-empty list), with the spot list (may be empty); ENV as above
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_cubelit(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, false, ENV, true, true, false);
+    WALK_GBUFFER(LOOP, false, ENV, true, true, false, false);
 }
 // trilinear material textures (ARCTIC_OPT_TEXTURE_MIPS = 1 and a material with a chain; ShadeParams::lod = the level-of-detail plane k_resolve_lod wrote or
 // arctic_write_lod injected): every tile through shade_tile<MIP>.  The spot and cube loops are compiled in unconditionally (empty lists loop zero times and
@@ -1500,7 +1572,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_miplit(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_GBUFFER(LOOP, false, ENV, true, true, true);
+    WALK_GBUFFER(LOOP, false, ENV, true, true, true, false);
+}
+// glTF material factors, emissive and occlusion (arctic_set_material_extras, a material that is not neutral): every tile through shade_tile<PBR>.
+// As in k_miplit the spot and cube loops are compiled in (empty lists loop zero times); ENV and MIP as above.
+template <int LOOP, bool ENV, bool MIP>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_pbrlit(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    WALK_GBUFFER(LOOP, false, ENV, true, true, MIP, true);
 }
 
 // ---- the same without a G-buffer (whole frames): the tile walk straight from the visibility plane ----------------------
@@ -1510,7 +1589,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 // for the lit ones -- with the very operations of k_resolve (edges.h, fp contraction off), so the pixels are bit-identical
 // to the G-buffer path.  Everything after the attributes is shade_tile_fast / shade_tile, shared.  PLAIN, ENV, SPOT and CUBE as in
 // WALK_GBUFFER (k_material_vis; k_envlit_vis, k_spotlit_vis, k_cubelit_vis), and a macro for the same reason.
-#define WALK_VIS(LOOP, STATS, ENV, SPOT, CUBE, MIP)                                                                                                                 \
+#define WALK_VIS(LOOP, STATS, ENV, SPOT, CUBE, MIP, PBR)                                                                                                                 \
     constexpr bool PLAIN = !ENV && !SPOT && !CUBE && !MIP;                                                                                                                           \
     KernArgs args = kernel_args();                                                                                                                                                   \
     unsigned long long t_entry = PLAIN ? trace_entry() : 0ull;                                                                                                                       \
@@ -1634,8 +1713,8 @@ _Pragma("clang fp contract(off)")                                               
                 const uint32_t ri = sp.rec_of[(uint32_t)key];                                                                                                                        \
                 lambda = pixel_lod(sp.recs[ri], sp.rrecs[ri], px, py, sp.xv[v0].attr, sp.xv[v1].attr, sp.xv[v2].attr, cur.a.x, cur.a.y, wf, hf, last);                               \
             }                                                                                                                                                                        \
-            if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE, MIP>(sp, lut, ty, tx, lane, cur, second, lambda);                                                                    \
-        } else if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE>(sp, lut, ty, tx, lane, cur, second);                                                                              \
+            if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE, MIP, PBR>(sp, lut, ty, tx, lane, cur, second, lambda);                                                                    \
+        } else if (!fast) shade_tile<LOOP, STATS, ENV, SPOT, CUBE, false, PBR>(sp, lut, ty, tx, lane, cur, second);                                                                              \
         if (PLAIN) trace_end(sp, A, (size_t)ty * A.tiles_x + tx, fast);                                                                                                              \
         if (++k >= A.T) break;                                                                                                                                                       \
         asm volatile("" : "+s"(args));                                                                                                                                               \
@@ -1647,27 +1726,33 @@ _Pragma("clang fp contract(off)")                                               
 template <int LOOP, bool STATS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_material_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, STATS, false, false, false, false);
+    WALK_VIS(LOOP, STATS, false, false, false, false, false);
 }
 template <int LOOP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_envlit_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, false, true, false, false, false);
+    WALK_VIS(LOOP, false, true, false, false, false, false);
 }
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_spotlit_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, false, ENV, true, false, false);
+    WALK_VIS(LOOP, false, ENV, true, false, false, false);
 }
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_cubelit_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, false, ENV, true, true, false);
+    WALK_VIS(LOOP, false, ENV, true, true, false, false);
 }
 template <int LOOP, bool ENV>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_miplit_vis(const ShadeParams sp_by_value) {
     __shared__ float lut[256];
-    WALK_VIS(LOOP, false, ENV, true, true, true);
+    WALK_VIS(LOOP, false, ENV, true, true, true, false);
+}
+// (the extras' constants and the emission live across the light loop: at the 80 registers of six waves per SIMD three of the eight spilled; five waves)
+template <int LOOP, bool ENV, bool MIP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 6))) void k_pbrlit_vis(const ShadeParams sp_by_value) {
+    __shared__ float lut[256];
+    WALK_VIS(LOOP, false, ENV, true, true, MIP, true);
 }
 
 // ---- shadow bounds: the conservative min/max table calculate_lit tests first -------------------------------------------
@@ -1712,7 +1797,13 @@ __global__ __launch_bounds__(256) void k_post_process(const float4 *__restrict__
 template <int LOOP, bool STATS>
 hipError_t launch_variant(const ShadeParams &sp, const ShadeLaunch &L, dim3 grid) {
     if (L.from_vis) {   // four-wave workgroups, a strip of 4 tiles each (block_id<4>)
-        if (L.mip && L.env) k_miplit_vis<LOOP, true><<<grid, 256, 0, L.stream>>>(sp);
+        if (L.pbr) {
+            if (L.mip && L.env) k_pbrlit_vis<LOOP, true, true><<<grid, 256, 0, L.stream>>>(sp);
+            else if (L.mip) k_pbrlit_vis<LOOP, false, true><<<grid, 256, 0, L.stream>>>(sp);
+            else if (L.env) k_pbrlit_vis<LOOP, true, false><<<grid, 256, 0, L.stream>>>(sp);
+            else k_pbrlit_vis<LOOP, false, false><<<grid, 256, 0, L.stream>>>(sp);
+        }
+        else if (L.mip && L.env) k_miplit_vis<LOOP, true><<<grid, 256, 0, L.stream>>>(sp);
         else if (L.mip) k_miplit_vis<LOOP, false><<<grid, 256, 0, L.stream>>>(sp);
         else if (L.cube && L.env) k_cubelit_vis<LOOP, true><<<grid, 256, 0, L.stream>>>(sp);
         else if (L.cube) k_cubelit_vis<LOOP, false><<<grid, 256, 0, L.stream>>>(sp);
@@ -1723,7 +1814,13 @@ hipError_t launch_variant(const ShadeParams &sp, const ShadeLaunch &L, dim3 grid
         return hipGetLastError();
     }
     grid.x = (grid.x + 7) / 8 * 32;   // one-wave workgroups (block_id<1>): four blocks per strip, a strip's blocks on one XCD
-    if (L.mip && L.env) k_miplit<LOOP, true><<<grid, 64, 0, L.stream>>>(sp);
+    if (L.pbr) {
+        if (L.mip && L.env) k_pbrlit<LOOP, true, true><<<grid, 64, 0, L.stream>>>(sp);
+        else if (L.mip) k_pbrlit<LOOP, false, true><<<grid, 64, 0, L.stream>>>(sp);
+        else if (L.env) k_pbrlit<LOOP, true, false><<<grid, 64, 0, L.stream>>>(sp);
+        else k_pbrlit<LOOP, false, false><<<grid, 64, 0, L.stream>>>(sp);
+    }
+    else if (L.mip && L.env) k_miplit<LOOP, true><<<grid, 64, 0, L.stream>>>(sp);
     else if (L.mip) k_miplit<LOOP, false><<<grid, 64, 0, L.stream>>>(sp);
     else if (L.cube && L.env) k_cubelit<LOOP, true><<<grid, 64, 0, L.stream>>>(sp);
     else if (L.cube) k_cubelit<LOOP, false><<<grid, 64, 0, L.stream>>>(sp);
@@ -1751,7 +1848,7 @@ hipError_t launch_shade(const ShadeParams &sp_in, const ShadeLaunch &L) {
     const uint32_t bpr = (sp.tiles_x + 3) / 4, groups = (sp.tiles_y + 7) / 8;
     sp.group_stride = (groups + sp.tiles_per_wave - 1) / sp.tiles_per_wave;
     dim3 grid(8 * bpr, sp.group_stride);   // a block shades tiles_per_wave groups of 8 tile rows, group_stride groups apart
-    if (sp.tile_order && !L.env && !L.spot && !L.cube && !L.mip) // ... or tiles_per_wave consecutive slots of the prepass's dispatch order (n_jobs slots, common.h order_slot: a block = one XCD's list)
+    if (sp.tile_order && !L.env && !L.spot && !L.cube && !L.mip && !L.pbr) // ... or tiles_per_wave consecutive slots of the prepass's dispatch order (n_jobs slots, common.h order_slot: a block = one XCD's list)
         grid = dim3((sp.n_jobs + sp.tiles_per_wave - 1) / sp.tiles_per_wave, 1);
     if (L.loop == 2) return L.stats ? launch_variant<2, true>(sp, L, grid) : launch_variant<2, false>(sp, L, grid);
     return L.stats ? launch_variant<1, true>(sp, L, grid) : launch_variant<1, false>(sp, L, grid);

@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .scene import LIGHT_DTYPE, OBJECT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE
+from .scene import LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, OBJECT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, neutral_material_params
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "host", "libarctic_gltf.so")
@@ -34,6 +34,7 @@ def lib():
             getattr(L, f).restype, getattr(L, f).argtypes = u64, [vp]
         L.arctic_gltf_material_image.restype = C.c_int
         L.arctic_gltf_material_image.argtypes = [vp, u64, C.c_int, C.POINTER(vp), u32p, u32p]
+        L.arctic_gltf_material_params.restype, L.arctic_gltf_material_params.argtypes = C.c_int, [vp, u64, vp]
         L.arctic_gltf_mesh.restype = C.c_int
         L.arctic_gltf_mesh.argtypes = [vp, u64, C.POINTER(vp), u64p, C.POINTER(vp), u64p, u64p]
         L.arctic_gltf_objects.restype, L.arctic_gltf_objects.argtypes = vp, [vp]
@@ -52,17 +53,30 @@ class GltfScene:
     """materials: list of (diffuse, normal, metal_rough) uint8 (h, w, 4); meshes: list of (vertices, indices, material);
     objects: OBJECT_DTYPE array -- the same three things scenes.SyntheticScene carries.  The file's KHR_lights_punctual lights:
     spot_lights (SPOT_LIGHT_DTYPE, for Renderer.update_spot_lights), point_lights (LIGHT_DTYPE, for update_lights),
-    directional_lights (a count; include/arctic_gltf.h).  upload() uploads no lights."""
+    directional_lights (a count; include/arctic_gltf.h).  upload() uploads no lights.
+    The glTF material model beyond the three images: material_params (MATERIAL_PARAMS_DTYPE, one record per material), emissive_images and
+    occlusion_images (one entry per material: (h, w, 4) uint8 or None).  upload(material_model="gltf") applies them."""
 
-    def __init__(self, materials, meshes, objects, spot_lights=None, point_lights=None, directional_lights=0):
+    def __init__(self, materials, meshes, objects, spot_lights=None, point_lights=None, directional_lights=0, material_params=None,
+                 emissive_images=None, occlusion_images=None):
         self.materials, self.meshes, self.objects = materials, meshes, objects
+        self.material_params = neutral_material_params(len(materials)) if material_params is None else material_params
+        self.emissive_images = [None] * len(materials) if emissive_images is None else emissive_images
+        self.occlusion_images = [None] * len(materials) if occlusion_images is None else occlusion_images
         self.spot_lights = np.zeros(0, SPOT_LIGHT_DTYPE) if spot_lights is None else spot_lights
         self.point_lights = np.zeros(0, LIGHT_DTYPE) if point_lights is None else point_lights
         self.directional_lights = directional_lights
 
-    def upload(self, renderer):
-        for d, n, m in self.materials:
-            renderer.create_material(d, n, m)
+    def upload(self, renderer, material_model="reference"):
+        """material_model "reference": the three images alone, what the reference's load_scene uploads.  "gltf": also the factors, emissive and
+        occlusion of every material that is not neutral (Renderer.set_material_extras)."""
+        if material_model not in ("reference", "gltf"):
+            raise ValueError(f"material_model {material_model!r}: 'reference' or 'gltf'")
+        neutral = neutral_material_params()[0]
+        for k, (d, n, m) in enumerate(self.materials):
+            i = renderer.create_material(d, n, m)
+            if material_model == "gltf" and (self.material_params[k].tobytes() != neutral.tobytes() or self.emissive_images[k] is not None or self.occlusion_images[k] is not None):
+                renderer.set_material_extras(i, self.material_params[k], self.emissive_images[k], self.occlusion_images[k])
         for v, i, mat in self.meshes:
             renderer.create_mesh(v, i, mat)
         return renderer
@@ -75,14 +89,17 @@ def load(path):
     if not h:
         raise ValueError(err.value.decode())
     try:
-        materials = []
+        materials, emissive, occlusion = [], [], []
+        params = np.zeros(L.arctic_gltf_material_count(h), MATERIAL_PARAMS_DTYPE)
         for i in range(L.arctic_gltf_material_count(h)):
             imgs = []
-            for k in range(3):
+            for k in range(5):
                 p, w, hh = C.c_void_p(), C.c_uint32(), C.c_uint32()
                 assert L.arctic_gltf_material_image(h, i, k, C.byref(p), C.byref(w), C.byref(hh)) == 0
-                imgs.append(np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), (hh.value, w.value, 4)).copy())
-            materials.append(tuple(imgs))
+                imgs.append(np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), (hh.value, w.value, 4)).copy() if p.value else None)
+            materials.append(tuple(imgs[:3]))
+            emissive.append(imgs[3]); occlusion.append(imgs[4])
+            assert L.arctic_gltf_material_params(h, i, params[i:i + 1].ctypes.data) == 0
         meshes = []
         for i in range(L.arctic_gltf_mesh_count(h)):
             pv, pi, nv, ni, mat = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -98,7 +115,8 @@ def load(path):
             p = fn(h, C.byref(n))
             return np.frombuffer(C.string_at(p, n.value * dtype.itemsize), dtype=dtype).copy() if n.value else np.zeros(0, dtype)
         return GltfScene(materials, meshes, objects, lights(L.arctic_gltf_spot_lights, SPOT_LIGHT_DTYPE),
-                         lights(L.arctic_gltf_point_lights, LIGHT_DTYPE), int(L.arctic_gltf_directional_light_count(h)))
+                         lights(L.arctic_gltf_point_lights, LIGHT_DTYPE), int(L.arctic_gltf_directional_light_count(h)),
+                         material_params=params, emissive_images=emissive, occlusion_images=occlusion)
     finally:
         L.arctic_gltf_free(h)
 

@@ -484,7 +484,13 @@ Image solid(uint8_t r, uint8_t g, uint8_t b) {   // assets/white.png, assets/nor
     return im;
 }
 
-struct Material { Image img[3]; };
+// img: diffuse, normal, metal-rough (load_scene's three); the glTF material model beyond them: the factors, and the emissive and occlusion
+// images where the file has them (w = 0: absent)
+struct Material {
+    Image img[3];
+    Image emissive, occlusion;
+    ArcticMaterialParams params = {{1.0f, 1.0f, 1.0f}, 1.0f, 1.0f, 1.0f, 1.0f, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f}};
+};
 struct Mesh { std::vector<ArcticVertex> v; std::vector<uint32_t> idx; uint64_t material = 0; };
 
 }  // namespace
@@ -703,6 +709,53 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
             if (const Json *t = pbr->find("metallicRoughnessTexture")) out.img[2] = L.image_of_texture((size_t)t->at("index").as_int());
         }
         if (const Json *t = m.find("normalTexture")) out.img[1] = L.image_of_texture((size_t)t->at("index").as_int());
+        // the rest of glTF's material model (not read by load_scene; applied by the caller: arctic_set_material_extras).  Defaults are glTF's;
+        // a wrong type, a wrong array length, a value out of range or a texture index out of range refuse the file.  texCoord: as above, ignored.
+        {
+            const std::string where = "glTF: material " + std::to_string(i) + ": ";
+            const auto unit = [&](const Json &v, const char *what) {
+                const double x = v.as_num();
+                if (!(x >= 0.0 && x <= 1.0)) fail(where + what + " must be in [0, 1]");
+                return (float)x;
+            };
+            const auto numbers = [&](const Json &v, size_t n, const char *what) -> const Json & {
+                if (v.kind != Json::Array || v.size() != n) fail(where + what + " must be an array of " + std::to_string(n) + " numbers");
+                return v;
+            };
+            const auto object = [&](const Json &v, const char *what) -> const Json & {
+                if (v.kind != Json::Object) fail(where + what + " must be an object");
+                return v;
+            };
+            ArcticMaterialParams &P = out.params;
+            if (const Json *pv = m.find("pbrMetallicRoughness")) {
+                const Json &pbr = object(*pv, "pbrMetallicRoughness");
+                if (const Json *f = pbr.find("baseColorFactor")) for (size_t k = 0; k < 3; ++k) P.base_color_factor[k] = unit(numbers(*f, 4, "baseColorFactor")[k], "baseColorFactor");
+                if (const Json *f = pbr.find("metallicFactor")) P.metallic_factor = unit(*f, "metallicFactor");
+                if (const Json *f = pbr.find("roughnessFactor")) P.roughness_factor = unit(*f, "roughnessFactor");
+            }
+            if (const Json *t = m.find("normalTexture"))
+                if (const Json *sc = object(*t, "normalTexture").find("scale")) {
+                    const double x = sc->as_num();
+                    if (!std::isfinite(x) || !std::isfinite((float)x)) fail(where + "normalTexture.scale must be finite");
+                    P.normal_scale = (float)x;
+                }
+            if (const Json *t = m.find("occlusionTexture")) {
+                out.occlusion = L.image_of_texture(L.index_of(object(*t, "occlusionTexture").at("index"), "occlusionTexture.index"));
+                if (const Json *st = t->find("strength")) P.occlusion_strength = unit(*st, "occlusionTexture.strength");
+            }
+            if (const Json *t = m.find("emissiveTexture")) out.emissive = L.image_of_texture(L.index_of(object(*t, "emissiveTexture").at("index"), "emissiveTexture.index"));
+            double strength = 1.0, emissive[3] = {0.0, 0.0, 0.0};
+            if (const Json *f = m.find("emissiveFactor")) for (size_t k = 0; k < 3; ++k) emissive[k] = numbers(*f, 3, "emissiveFactor")[k].as_num();
+            if (const Json *ex = m.find("extensions"))
+                if (const Json *es = object(*ex, "extensions").find("KHR_materials_emissive_strength"))
+                    if (const Json *v = object(*es, "KHR_materials_emissive_strength").find("emissiveStrength")) strength = v->as_num();
+            if (!(strength >= 0.0) || !std::isfinite(strength)) fail(where + "emissiveStrength must be finite and >= 0");
+            for (int k = 0; k < 3; ++k) {
+                const double e = emissive[k] * strength;   // the strength is folded into the factor (binary64, rounded once)
+                if (!(emissive[k] >= 0.0) || !std::isfinite(e) || !std::isfinite((float)e)) fail(where + "emissiveFactor must be finite and >= 0");
+                P.emissive_factor[k] = (float)e;
+            }
+        }
         g->materials.push_back(std::move(out));
     }
     if (g->materials.empty()) {   // assimp always provides a default material
@@ -890,9 +943,16 @@ uint64_t arctic_gltf_mesh_count(const ArcticGltf *g) { return g ? g->meshes.size
 uint64_t arctic_gltf_object_count(const ArcticGltf *g) { return g ? g->objects.size() : 0; }
 
 int arctic_gltf_material_image(const ArcticGltf *g, uint64_t i, int k, const uint8_t **rgba, uint32_t *w, uint32_t *h) {
-    if (!g || i >= g->materials.size() || k < 0 || k > 2 || !rgba || !w || !h) return ARCTIC_E_INVALID;
-    const Image &im = g->materials[i].img[k];
+    if (!g || i >= g->materials.size() || k < 0 || k > 4 || !rgba || !w || !h) return ARCTIC_E_INVALID;
+    const Material &m = g->materials[i];
+    const Image &im = k == 3 ? m.emissive : k == 4 ? m.occlusion : m.img[k];
+    if (im.w == 0) { *rgba = nullptr; *w = *h = 0; return ARCTIC_OK; }   // (k = 3, 4: the material has no such image)
     *rgba = im.px.data(); *w = im.w; *h = im.h;
+    return ARCTIC_OK;
+}
+int arctic_gltf_material_params(const ArcticGltf *g, uint64_t i, ArcticMaterialParams *out) {
+    if (!g || i >= g->materials.size() || !out) return ARCTIC_E_INVALID;
+    *out = g->materials[i].params;
     return ARCTIC_OK;
 }
 int arctic_gltf_mesh(const ArcticGltf *g, uint64_t i, const ArcticVertex **vertices, uint64_t *n_vertices, const uint32_t **indices,

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/arctic_hip.h"
+#include "../../include/arctic_gltf.h"   // (declarations only: nothing of the loader is linked unless apply_gltf_material_extras is used)
 
 namespace ArcticAMD::Renderer {
 
@@ -30,6 +31,7 @@ struct DirectionalLight { float position[3]; float rotation[2]; float color[3]; 
 using PointLight = ArcticPointLight;       // position, padding0, color, padding1
 using SpotLight = ArcticSpotLight;         // position, range, direction, inner_cone_angle, color, outer_cone_angle (no counterpart in the reference)
 using PointShadowLight = ArcticPointShadowLight;   // position, z_near, color, z_far (no counterpart in the reference)
+using MaterialParams = ArcticMaterialParams;       // glTF's factors: base colour, metallic, roughness, normal scale, occlusion strength, emissive (no counterpart in the reference)
 struct Scene {
     Camera camera;
     float ambient;
@@ -89,6 +91,28 @@ class Renderer {
         return ok(arctic_create_material(m_handle, diffuse_data, diffuse_width, diffuse_height, normal_data, normal_width, normal_height,
                                          metalness_roughness_data, metalness_roughness_width, metalness_roughness_height));
     }
+    // glTF material factors, emissive (sRGB, rgb) and occlusion (linear, R) of a material that exists (include/arctic_hip.h); replaces what it had,
+    // params == nullptr and no images: back to neutral.  false = invalid params / image / index, the material stays as it was
+    [[nodiscard]] bool set_material_extras(MaterialIdx material, const MaterialParams *params, const void *emissive_data = nullptr, uint32_t emissive_width = 0,
+                                           uint32_t emissive_height = 0, const void *occlusion_data = nullptr, uint32_t occlusion_width = 0, uint32_t occlusion_height = 0) {
+        return ok(arctic_set_material_extras(m_handle, material, params, emissive_data, emissive_width, emissive_height, occlusion_data, occlusion_width, occlusion_height));
+    }
+    // the glTF material model of a loaded file on top of arctic_gltf_upload (which stays the reference's load_scene): set_material_extras for every
+    // material of `g` that is not neutral; first_material = the index arctic_gltf_upload's first create_material returned
+    [[nodiscard]] bool apply_gltf_material_extras(const ArcticGltf *g, MaterialIdx first_material = 0) {
+        const MaterialParams neutral = {{1.0f, 1.0f, 1.0f}, 1.0f, 1.0f, 1.0f, 1.0f, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f}};
+        for (uint64_t i = 0; i < arctic_gltf_material_count(g); ++i) {
+            MaterialParams p;
+            const uint8_t *e = nullptr, *o = nullptr;
+            uint32_t ew = 0, eh = 0, ow = 0, oh = 0;
+            if (arctic_gltf_material_params(g, i, &p) != ARCTIC_OK || arctic_gltf_material_image(g, i, 3, &e, &ew, &eh) != ARCTIC_OK ||
+                arctic_gltf_material_image(g, i, 4, &o, &ow, &oh) != ARCTIC_OK) { m_error = "apply_gltf_material_extras: bad glTF handle"; return false; }
+            if (!e && !o && std::memcmp(&p, &neutral, sizeof p) == 0) continue;
+            if (!set_material_extras(first_material + i, &p, e, ew, eh, o, ow, oh)) return false;
+        }
+        return true;
+    }
+    [[nodiscard]] static bool check_material_params(const MaterialParams &params) { return arctic_check_material_params(&params) == ARCTIC_OK; }
     [[nodiscard]] bool create_hdri(float *data, uint32_t width, uint32_t height) { return ok(arctic_create_hdri(m_handle, data, width, height)); }
     void update_lights(std::span<PointLight> point_lights) { (void)ok(arctic_update_lights(m_handle, point_lights.data(), point_lights.size())); }
     // spot lights (KHR_lights_punctual's cone and range; include/arctic_hip.h): false = an invalid light, the previous list stays

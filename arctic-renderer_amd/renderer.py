@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (LIGHT_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -129,6 +129,21 @@ class Renderer:
                 raise ArcticError(-1, "create_material: images must be (h, w, 4) uint8")
         return self._check(self.L.arctic_create_material(self.h, _ptr(d), d.shape[1], d.shape[0], _ptr(n), n.shape[1], n.shape[0],
                                                          _ptr(m), m.shape[1], m.shape[0]))
+
+    def set_material_extras(self, material, params=None, emissive=None, occlusion=None):
+        """glTF factors, emissive and occlusion of one material (include/arctic_hip.h): params = one MATERIAL_PARAMS_DTYPE record or None (the
+        neutral factors), emissive / occlusion = (h, w, 4) uint8 images or None.  Replaces what the material had; all None returns it to
+        neutral.  Invalid params raise ArcticError (ARCTIC_E_INVALID) and leave the material as it was."""
+        p = None if params is None else np.ascontiguousarray(params, dtype=MATERIAL_PARAMS_DTYPE).reshape(1)
+        imgs = []
+        for t in (emissive, occlusion):
+            t = None if t is None else np.ascontiguousarray(t, dtype=np.uint8)
+            if t is not None and (t.ndim != 3 or t.shape[2] != 4):
+                raise ArcticError(-1, "set_material_extras: images must be (h, w, 4) uint8")
+            imgs.append(t)
+        e, o = imgs
+        self._check(self.L.arctic_set_material_extras(self.h, int(material), _ptr(p), _ptr(e), e.shape[1] if e is not None else 0, e.shape[0] if e is not None else 0,
+                                                      _ptr(o), o.shape[1] if o is not None else 0, o.shape[0] if o is not None else 0))
 
     def create_mesh(self, vertices, indices, material_idx):
         v = np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE)
@@ -344,6 +359,12 @@ class Renderer:
     def set_option(self, name, value):
         self._check(self.L.arctic_set_option(self.h, binding.OPTIONS[name], int(value)))
         self._options[name] = int(value)
+
+
+def check_material_params(params):
+    """arctic_check_material_params: True when one MATERIAL_PARAMS_DTYPE record is valid (host only, no handle)"""
+    p = np.ascontiguousarray(params, dtype=MATERIAL_PARAMS_DTYPE).reshape(1)
+    return binding.lib().arctic_check_material_params(p.ctypes.data) == 0
 
 
 def point_shadow_matrices(light):

@@ -23,6 +23,17 @@ SPOT_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("range", "<f4"), ("directi
 POINT_SHADOW_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("z_near", "<f4"), ("color", "<f4", 3), ("z_far", "<f4")])
 assert VERTEX_DTYPE.itemsize == 56 and OBJECT_DTYPE.itemsize == 72 and LIGHT_DTYPE.itemsize == 32 and SPOT_LIGHT_DTYPE.itemsize == 48
 assert POINT_SHADOW_LIGHT_DTYPE.itemsize == 32
+# ArcticMaterialParams (include/arctic_hip.h): 48 bytes, the glTF material factors of Renderer.set_material_extras
+MATERIAL_PARAMS_DTYPE = np.dtype([("base_color_factor", "<f4", 3), ("metallic_factor", "<f4"), ("roughness_factor", "<f4"), ("normal_scale", "<f4"),
+                                  ("occlusion_strength", "<f4"), ("emissive_factor", "<f4", 3), ("reserved", "<f4", 2)])
+assert MATERIAL_PARAMS_DTYPE.itemsize == 48
+
+
+def neutral_material_params(n=1):
+    """n records that change nothing: factors 1, normal scale 1, occlusion strength 1, no emission"""
+    a = np.zeros(n, MATERIAL_PARAMS_DTYPE)
+    a["base_color_factor"], a["metallic_factor"], a["roughness_factor"], a["normal_scale"], a["occlusion_strength"] = 1, 1, 1, 1, 1
+    return a
 
 TM_REINHARD, TM_EXPOSURE, TM_ACES = 0, 1, 2
 

@@ -35,8 +35,17 @@ uint64_t arctic_gltf_material_count(const ArcticGltf *g);
 uint64_t arctic_gltf_mesh_count(const ArcticGltf *g);
 uint64_t arctic_gltf_object_count(const ArcticGltf *g);
 
-/* image k of material i: 0 diffuse, 1 normal, 2 metal-rough; RGBA8, row-major (what stbi_load(..., 4) returns) */
+/* image k of material i: 0 diffuse, 1 normal, 2 metal-rough; RGBA8, row-major (what stbi_load(..., 4) returns).
+ * k = 3 emissive (sRGB, rgb), k = 4 occlusion (linear, R; glTF files often name the metal-rough image here): not read by load_scene.  An
+ * absent image returns ARCTIC_OK with *rgba = NULL, *w = *h = 0. */
 int arctic_gltf_material_image(const ArcticGltf *g, uint64_t i, int k, const uint8_t **rgba, uint32_t *w, uint32_t *h);
+/* The factors of material i as arctic_set_material_extras takes them (not read by load_scene): pbrMetallicRoughness.baseColorFactor (rgb;
+ * alpha ignored), metallicFactor, roughnessFactor, normalTexture.scale, occlusionTexture.strength, and emissiveFactor multiplied by
+ * extensions.KHR_materials_emissive_strength.emissiveStrength (binary64, rounded once).  Defaults are glTF's: 1,1,1 / 1 / 1 / 1 / 1 / 0,0,0
+ * / 1.  A wrong type, a wrong array length, a value outside ArcticMaterialParams' ranges or a texture index out of range refuse the file.
+ * texCoord is ignored as for the other three textures.  arctic_gltf_upload does NOT apply them (it stays load_scene): the caller hands
+ * them, with images 3 and 4, to arctic_set_material_extras for every material that is not neutral. */
+int arctic_gltf_material_params(const ArcticGltf *g, uint64_t i, ArcticMaterialParams *out);
 int arctic_gltf_mesh(const ArcticGltf *g, uint64_t i, const ArcticVertex **vertices, uint64_t *n_vertices,
                      const uint32_t **indices, uint64_t *n_indices, uint64_t *material);
 const ArcticObject *arctic_gltf_objects(const ArcticGltf *g);

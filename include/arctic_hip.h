@@ -189,6 +189,55 @@ int arctic_create_mesh(ArcticRenderer *r,
                        const uint32_t *indices, uint64_t n_indices,
                        uint64_t material_idx);
 
+/* glTF material factors, emissive and occlusion (no counterpart in the reference, whose material is three images).  Per material twelve
+ * floats and two optional images. */
+typedef struct ArcticMaterialParams {   /* 48 bytes */
+    float base_color_factor[3];   /* linear RGB, each in [0, 1] */
+    float metallic_factor;        /* [0, 1] */
+    float roughness_factor;       /* [0, 1] */
+    float normal_scale;           /* finite */
+    float occlusion_strength;     /* [0, 1] */
+    float emissive_factor[3];     /* linear RGB, finite, >= 0 (may exceed 1: emissive strength is pre-multiplied) */
+    float reserved[2];            /* must be 0 */
+} ArcticMaterialParams;
+/* neutral = {1,1,1, 1, 1, 1, 1, 0,0,0, 0,0} and no images.
+ *
+ * arctic_set_material_extras may be called at any time after the material exists; it drains the stream in use first and is synchronous like
+ * arctic_create_material, and it REPLACES what the material had.  params == NULL with no images returns the material to neutral (params ==
+ * NULL with an image: the neutral factors and that image).  emissive_rgba8 is a tightly packed sRGB RGBA8 image of which rgb is used,
+ * occlusion_rgba8 a linear one of which R is used (glTF's convention: it may be the very metal-rough image); NULL, 0, 0 = no image.
+ * ARCTIC_E_INVALID, the material left as it was: a field out of range or not finite, a non-zero reserved field, an image side of 0 with a
+ * non-null pointer (or a null pointer with a non-zero side), a material index that does not exist.  ARCTIC_E_CAPACITY: an image side above 65535.
+ *
+ * For a covered pixel start from what ps_main filters today -- base rgb (decoded per texel, then filtered), the normal-map bytes nr, ng, nb
+ * on the 0..255 scale, rough and metal; ARCTIC_OPT_TEXTURE_MIPS and ARCTIC_OPT_SAMPLER bit 0 apply to these exactly as without extras.  Then
+ *   base'  = base * base_color_factor                      (per channel)
+ *   metal' = metal * metallic_factor      rough' = rough * roughness_factor
+ *   t      = (nr*2/255 - 1, -(ng*2/255 - 1), nb*2/255 - 1) (today's tangent-space normal)
+ *   n'     = normalize(T * t.x*normal_scale + B * t.y*normal_scale + N * t.z)
+ *   o      = occlusion image R, linear, bilinear + WRAP, texel centres at +0.5   (no image: 1)
+ *   ao     = 1 + occlusion_strength * (o - 1)
+ *   e      = emissive image rgb, sRGB-decoded per texel, then filtered the same way      (no image: 1,1,1)
+ *   E      = e * emissive_factor
+ *   A      = ambient * base'     or, with ARCTIC_OPT_ENV_LIGHTING, ambient * ibl(n', wo, base', metal', rough')
+ *   color  = Lo(base', metal', rough', n') * (1 - shadow) + A * ao + E
+ * Lo is every light the handle has (sun, point, spot, shadow-casting point lights), unchanged apart from its inputs.  Occlusion scales the
+ * indirect term only (glTF's rule); emission carries neither (1 - shadow) nor ao: a fully sun-shadowed pixel is A * ao + E, and without
+ * ARCTIC_OPT_ENV_LIGHTING it still never loads its position or tangent frame (exact culling stays).  ARCTIC_OPT_SAMPLER bit 0 applies to
+ * the two images as to the other three; ARCTIC_OPT_HDR16 rounds the final colour, emission included.  The two images are filtered at
+ * LEVEL 0 under both settings of ARCTIC_OPT_TEXTURE_MIPS: they have no chains (yet).
+ *
+ * Nothing changes unless asked: a handle whose materials are all neutral launches exactly the kernels it launched before this call
+ * existed.  While a material is not neutral every tile goes through the general tile code (kernels k_pbrlit / k_pbrlit_vis, spot, cube, ENV
+ * and MIP composing as before); the pixels of a neutral material keep their bits there (the factors multiply by 1.0f and add +0.0f);
+ * ARCTIC_OPT_TILE_ORDER is ignored, and ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE make a shading call return ARCTIC_E_STATE. */
+int arctic_set_material_extras(ArcticRenderer *r, uint64_t material, const ArcticMaterialParams *params,
+                               const void *emissive_rgba8, uint32_t ew, uint32_t eh,
+                               const void *occlusion_rgba8, uint32_t ow, uint32_t oh);
+
+/* The validation arctic_set_material_extras applies to its params: ARCTIC_OK or ARCTIC_E_INVALID (NULL is invalid here).  Host only, no handle. */
+int arctic_check_material_params(const ArcticMaterialParams *params);
+
 /* replaces void Renderer::update_lights(span<PointLight>) (renderer.hpp:120,
  * renderer.cpp:585-603): clamps to max_lights like the reference clamps to 16. */
 int arctic_update_lights(ArcticRenderer *r, const ArcticPointLight *lights, uint64_t n);
