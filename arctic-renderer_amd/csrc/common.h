@@ -471,6 +471,10 @@ hipError_t launch_post_process(const float4 *hdr, uint32_t w, uint32_t h, int32_
                                uint8_t *rgba8, float *ldr, hipStream_t s);
 hipError_t launch_gbuffer_tile(GBuffer g, float *attrs, uint32_t *mat, uint32_t width, uint32_t rows,
                                uint32_t row0_in_tile, uint32_t tiles_x, uint32_t tiles_y, int to_tiled, hipStream_t s);
+// the edge anti-aliasing pass of include/arctic_hip.h (antialias.hip): a row-major RGBA8 image of width x height pixels, 4-byte aligned, into
+// another that does not overlap it; one workgroup per tile of ANTIALIAS_TILE_W x ANTIALIAS_TILE_H pixels
+constexpr uint32_t ANTIALIAS_TILE_W = 64, ANTIALIAS_TILE_H = 16;
+hipError_t launch_antialias(const void *in, void *out, uint32_t width, uint32_t height, hipStream_t s);
 
 // ---- host math (host_math.cpp): glm-equivalent builders, scene.cpp:9-19,41-70 ----------------
 void dir_from_rot(const float rot_deg[2], float out[3]);

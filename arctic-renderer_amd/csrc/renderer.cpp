@@ -240,6 +240,13 @@ struct ArcticRenderer {
     // frame targets
     DevBuf d_vis_set[3], d_p0, d_p1, d_p2, d_p3, d_p4, d_rgba8, d_ldr, d_hdr, d_counter;
     bool have_gbuffer = false, have_output = false, have_vis = false;   // have_vis: d_vis holds the visibility of the current G-buffer
+    // ARCTIC_OPT_ANTIALIAS: with 1 a handle that owns the whole frame shades into d_rgba8 and the edge filter (antialias.hip) writes the
+    // destination -- the caller's buffer or d_aa; output_filtered: the handle's latest RGBA8 output is the one in d_aa
+    int antialias = 0;
+    DevBuf d_aa;
+    bool output_filtered = false;
+    bool aa_active() const { return antialias == 1 && rows() == height; }
+    const void *rgba8_output() const { return output_filtered ? d_aa.p : d_rgba8.p; }
     int light_path = 0;             // ARCTIC_OPT_LIGHT_PATH: 0 automatic, 1 scalar light loop, 2 packed pairs
     bool visbuffer = true;          // arctic_render_frame shades straight from the visibility plane (no G-buffer)
     // per-frame geometry scratch
@@ -403,6 +410,7 @@ int alloc_targets(ArcticRenderer *r) {
     HIPCHECK(r, r->d_counter.ensure(8 * N_SHADE_STATS));
     HIPCHECK(r, r->d_geo_counters.ensure(5 * N_GEO_COUNTERS * 4));   // N_GEO_COUNTERS words per table set; set 4: the cube faces (CUBE_COUNTER_SET)
     r->have_gbuffer = r->have_output = r->have_vis = r->have_order = false;
+    r->output_filtered = false;
     return ARCTIC_OK;
 }
 
@@ -818,7 +826,7 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
     sp.exposure = st->exposure;
     sp.width = r->width; sp.rows = r->rows(); sp.row0_in_tile = r->row0_in_tile;
     sp.tiles_x = r->tiles_x; sp.tiles_y = r->tiles_y;
-    sp.out_rgba8 = static_cast<uint8_t *>(d_out ? d_out : r->d_rgba8.p);
+    sp.out_rgba8 = static_cast<uint8_t *>(d_out && !r->aa_active() ? d_out : r->d_rgba8.p);   // (with the edge filter: always the handle's own, the filter writes d_out)
     size_t out_px = (size_t)r->rows() * r->width;
     if (r->keep_float) {
         HIPCHECK(r, r->d_ldr.ensure(out_px * 12));
@@ -881,13 +889,24 @@ int pass_shade(ArcticRenderer *r, const ArcticScene *sc, const ArcticSettings *s
     ShadeParams sp;
     int rc = fill_shade_params(r, sc, st, d_out, sp, from_vis);
     if (rc != ARCTIC_OK) return rc;
-    for (auto &f : r->inflight)   // a gather of an earlier frame may still be reading this output buffer
-        if (f.ptr && f.ptr == static_cast<const void *>(sp.out_rgba8)) { HIPCHECK(r, hipStreamWaitEvent(r->stream, f.done, 0)); f.ptr = nullptr; }
+    // ARCTIC_OPT_ANTIALIAS: the shading kernels write d_rgba8, the filter the destination
+    const bool aa = r->aa_active();
+    void *aa_out = nullptr;
+    if (aa) {
+        if (!d_out) HIPCHECK(r, r->d_aa.ensure((size_t)r->rows() * r->width * 4));
+        aa_out = d_out ? d_out : r->d_aa.p;
+    }
+    for (auto &f : r->inflight)   // a gather of an earlier frame may still be reading this output buffer (or the one the filter writes)
+        if (f.ptr && (f.ptr == static_cast<const void *>(sp.out_rgba8) || f.ptr == aa_out)) { HIPCHECK(r, hipStreamWaitEvent(r->stream, f.done, 0)); f.ptr = nullptr; }
     if (r->count_evals) {
         sp.stats = r->d_counter.as<unsigned long long>();
         HIPCHECK(r, hipMemsetAsync(r->d_counter.p, 0, 8 * N_SHADE_STATS, r->stream));
     }
     HIPCHECK(r, shade_once(r, sp, from_vis, r->count_evals != 0));
+    if (aa) {
+        Range aa_zone("Anti-aliasing Pass");
+        HIPCHECK(r, launch_antialias(r->d_rgba8.p, aa_out, r->width, r->rows(), r->stream));
+    }
     if (r->count_evals) {
         unsigned long long n[N_SHADE_STATS] = {};
         HIPCHECK(r, hipMemcpyAsync(n, r->d_counter.p, 8 * N_SHADE_STATS, hipMemcpyDeviceToHost, r->stream));
@@ -897,6 +916,7 @@ int pass_shade(ArcticRenderer *r, const ArcticScene *sc, const ArcticSettings *s
         for (int i = 0; i < 4; ++i) r->edge_stats[i] = n[5 + i];
     }
     r->have_output = (d_out == nullptr);
+    r->output_filtered = aa && d_out == nullptr;
     return ARCTIC_OK;
 }
 
@@ -976,7 +996,7 @@ bool valid_scene(const ArcticScene *sc) { return sc && (sc->n_objects == 0 || sc
 // =================================================================================================
 extern "C" {
 
-int arctic_version(void) { return 320; }
+int arctic_version(void) { return 330; }
 
 ArcticRenderer *arctic_create(const ArcticCreateInfo *info, char *err, uint64_t err_len) {
     auto say = [&](const char *m) { if (err && err_len) { std::snprintf(err, (size_t)err_len, "%s", m); } };
@@ -1078,7 +1098,7 @@ void arctic_destroy(ArcticRenderer *r) {
     for (void *p : r->tex_allocs) (void)hipFree(p);
     for (ArcticRenderer::Extras &x : r->extras) for (void *p : {x.d_emissive, x.d_occlusion, x.d_fast}) if (p) (void)hipFree(p);
     DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_spots, &r->d_cubes, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4, &r->d_lod,
-                      &r->d_rgba8, &r->d_ldr, &r->d_hdr, &r->d_counter, &r->d_shadow_blocks_set[0], &r->d_shadow_blocks_set[1], &r->d_shadow_bounds_set[0], &r->d_shadow_bounds_set[1], &r->d_staging, &r->d_layout, &r->geo[0].d_xverts, &r->geo[1].d_xverts, &r->geo[2].d_xverts,
+                      &r->d_rgba8, &r->d_aa, &r->d_ldr, &r->d_hdr, &r->d_counter, &r->d_shadow_blocks_set[0], &r->d_shadow_blocks_set[1], &r->d_shadow_bounds_set[0], &r->d_shadow_bounds_set[1], &r->d_staging, &r->d_layout, &r->geo[0].d_xverts, &r->geo[1].d_xverts, &r->geo[2].d_xverts,
                       &r->geo[2].d_recs, &r->geo[2].d_rrecs, &r->geo[2].d_clip_list, &r->geo[2].d_rec_of, &r->geo[2].d_items, &r->tables[2].d,
                       &r->geo[3].d_xverts, &r->geo[3].d_recs, &r->geo[3].d_rrecs, &r->geo[3].d_clip_list, &r->geo[3].d_rec_of, &r->geo[3].d_items, &r->geo[3].d_left, &r->geo[3].d_bin_count, &r->geo[3].d_bin_slots, &r->tables[3].d,
                       &r->geo[0].d_recs, &r->geo[0].d_rrecs, &r->geo[0].d_clip_list, &r->geo[0].d_rec_of, &r->geo[0].d_items,
@@ -1614,7 +1634,7 @@ int arctic_render_frame_device(ArcticRenderer *r, const ArcticScene *scene, cons
 int arctic_render_frame(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, uint8_t *out_rgba8) {
     int rc = arctic_render_frame_device(r, scene, settings, nullptr);
     if (rc != ARCTIC_OK) return rc;
-    if (out_rgba8) HIPCHECK(r, hipMemcpyAsync(out_rgba8, r->d_rgba8.p, (size_t)r->rows() * r->width * 4, hipMemcpyDeviceToHost, r->stream));
+    if (out_rgba8) HIPCHECK(r, hipMemcpyAsync(out_rgba8, r->rgba8_output(), (size_t)r->rows() * r->width * 4, hipMemcpyDeviceToHost, r->stream));
     HIPCHECK(r, hipStreamSynchronize(r->stream));
     if (int ov = check_item_overflow(r)) return ov;
     return ARCTIC_OK;
@@ -1660,6 +1680,37 @@ int arctic_time_shade(ArcticRenderer *r, const ArcticScene *scene, const ArcticS
     for (uint32_t i = 0; i < iters; ++i) HIPCHECK(r, hipEventElapsedTime(&ms_each[i], ev[2 * i], ev[2 * i + 1]));
     for (auto &e : ev) (void)hipEventDestroy(e);
     r->have_output = true;
+    r->output_filtered = false;   // (the shading kernel alone: d_rgba8 holds what it wrote)
+    return ARCTIC_OK;
+}
+
+int arctic_antialias_device(ArcticRenderer *r, const void *d_in, void *d_out, uint32_t width, uint32_t height) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!d_in || !d_out || !width || !height) return r->fail(ARCTIC_E_INVALID, "antialias: null pointer or zero size");
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
+    const uint64_t bytes = (uint64_t)width * height * 4;
+    if ((a | b) & 3) return r->fail(ARCTIC_E_INVALID, "antialias: RGBA8 images are 4-byte aligned");
+    if (a < b + bytes && b < a + bytes) return r->fail(ARCTIC_E_INVALID, "antialias: the input and the output overlap (the filter reads neighbours: not in place)");
+    int rc = select_device(r);
+    if (rc) return rc;
+    Range zone("Anti-aliasing Pass");
+    HIPCHECK(r, launch_antialias(d_in, d_out, width, height, r->stream));
+    return ARCTIC_OK;
+}
+
+int arctic_antialias(ArcticRenderer *r, const uint8_t *rgba8, uint32_t width, uint32_t height, uint8_t *out) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!rgba8 || !out || !width || !height) return r->fail(ARCTIC_E_INVALID, "antialias: null pointer or zero size");
+    int rc = select_device(r);
+    if (rc) return rc;
+    const size_t n = (size_t)width * height * 4, half = (n + 255) & ~(size_t)255;
+    HIPCHECK(r, hipStreamSynchronize(r->stream));   // (d_stage may move)
+    HIPCHECK(r, r->d_stage.ensure(2 * half));
+    char *d_in = r->d_stage.as<char>(), *d_out = d_in + half;
+    HIPCHECK(r, hipMemcpyAsync(d_in, rgba8, n, hipMemcpyHostToDevice, r->stream));
+    HIPCHECK(r, launch_antialias(d_in, d_out, width, height, r->stream));
+    HIPCHECK(r, hipMemcpyAsync(out, d_out, n, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
     return ARCTIC_OK;
 }
 
@@ -1830,7 +1881,7 @@ int arctic_read_output(ArcticRenderer *r, float *ldr, float *hdr, uint8_t *rgba8
     if (int ov = check_item_overflow(r)) return ov;
     if (ldr) HIPCHECK(r, hipMemcpy(ldr, r->d_ldr.p, px * 12, hipMemcpyDeviceToHost));
     if (hdr) HIPCHECK(r, hipMemcpy(hdr, r->d_hdr.p, px * 12, hipMemcpyDeviceToHost));
-    if (rgba8) HIPCHECK(r, hipMemcpy(rgba8, r->d_rgba8.p, px * 4, hipMemcpyDeviceToHost));
+    if (rgba8) HIPCHECK(r, hipMemcpy(rgba8, r->rgba8_output(), px * 4, hipMemcpyDeviceToHost));
     return ARCTIC_OK;
 }
 
@@ -2036,6 +2087,10 @@ int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
         r->cube_size = (uint32_t)value; r->cube_key.clear();
         break;
     }
+    case ARCTIC_OPT_ANTIALIAS:
+        if (value < 0 || value > 1) return r->fail(ARCTIC_E_INVALID, "ARCTIC_OPT_ANTIALIAS: 0 or 1");
+        r->antialias = (int)value;
+        break;
     case ARCTIC_OPT_ENV_LIGHTING:
         if (value < 0 || value > 1) return r->fail(ARCTIC_E_INVALID, "ARCTIC_OPT_ENV_LIGHTING: 0 or 1");
         r->env_lighting = (int)value;
@@ -2227,7 +2282,7 @@ int arctic_gather_frame(ArcticRenderer *r, const void *d_shard, void *d_frame, i
     if (is_root && !d_frame) return r->fail(ARCTIC_E_INVALID, "gather_frame: the root needs a frame buffer");
     if (!d_shard) {
         if (!r->have_output) return r->fail(ARCTIC_E_STATE, "gather_frame: no shaded output to gather");
-        d_shard = r->d_rgba8.p;
+        d_shard = r->rgba8_output();
     }
     int rc = select_device(r);
     if (rc) return rc;

@@ -144,6 +144,13 @@ class Renderer {
     // the level-of-detail plane next to the G-buffer in place: one float per pixel, row-major over the handle's rows
     [[nodiscard]] bool read_lod(float *lod) { return ok(arctic_read_lod(m_handle, lod)); }
     [[nodiscard]] bool write_lod(const float *lod) { return ok(arctic_write_lod(m_handle, lod)); }
+    // edge anti-aliasing on the RGBA8 output (ARCTIC_OPT_ANTIALIAS; the reference leaves its staircases to the swap chain): a handle that owns the
+    // whole frame then filters every frame it shades; a sharded handle accepts the option and leaves its shard alone -- the root calls
+    // antialias_device on the assembled frame.  The float LDR / HDR planes are never filtered.
+    [[nodiscard]] bool set_antialias(bool on) { return ok(arctic_set_option(m_handle, ARCTIC_OPT_ANTIALIAS, on ? 1 : 0)); }
+    // the filter on any RGBA8 image: host to host (synchronous), or between two device images that do not overlap (asynchronous on the handle's stream)
+    [[nodiscard]] bool antialias(const uint8_t *rgba8, uint32_t width, uint32_t height, uint8_t *out) { return ok(arctic_antialias(m_handle, rgba8, width, height, out)); }
+    [[nodiscard]] bool antialias_device(const void *d_in, void *d_out, uint32_t width, uint32_t height) { return ok(arctic_antialias_device(m_handle, d_in, d_out, width, height)); }
 
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }

@@ -219,6 +219,22 @@ class Renderer:
         self._check(self.L.arctic_post_process(self.h, _ptr(a), w, h, C.byref(st), _ptr(out), _ptr(ldr)))
         return out, ldr
 
+    def antialias(self, img):
+        """the edge anti-aliasing filter of set_option("antialias", 1) (include/arctic_hip.h) on any (h, w, 4) uint8 image, host to host:
+        returns the filtered image.  Works on every handle, whatever its size and options."""
+        a = np.ascontiguousarray(img, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 4 or a.shape[0] == 0 or a.shape[1] == 0:
+            raise ArcticError(-1, "antialias: the image must be (h, w, 4) uint8 with h, w > 0")
+        out = np.empty_like(a)
+        self._check(self.L.arctic_antialias(self.h, _ptr(a), a.shape[1], a.shape[0], _ptr(out)))
+        return out
+
+    def antialias_device(self, d_in_ptr, d_out_ptr, width, height):
+        """the same filter between two RGBA8 device images (int pointers, e.g. torch tensors' .data_ptr()) that do not overlap; asynchronous
+        on the handle's stream.  The root of a sharded frame calls it on the assembled frame."""
+        self._check(self.L.arctic_antialias_device(self.h, C.c_void_p(d_in_ptr) if d_in_ptr else None, C.c_void_p(d_out_ptr) if d_out_ptr else None,
+                                                   int(width), int(height)))
+
     def time_shade(self, desc, settings, warmup=5, iters=20):
         s, st = self._scene(desc), self._settings(settings)
         ms = np.empty(iters, np.float32)

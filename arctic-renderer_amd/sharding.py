@@ -94,14 +94,30 @@ def padded_gather_plan(height, world, band_rows=16):
     return pad, dest
 
 
-def assemble_banded(gathered, height, band_rows=16):
-    """root only: the full frame from interleaved shards (one indexed copy per rank)."""
+def antialias_frame(frame, renderer):
+    """root only: the edge anti-aliasing filter (include/arctic_hip.h, ARCTIC_OPT_ANTIALIAS) on an assembled (height, width, 4) uint8 device
+    frame, through `renderer`'s arctic_antialias_device -- any handle on the frame's device: the sharded handles themselves leave their
+    shards unfiltered, a shard lacks its neighbours' rows.  Returns a new tensor, complete on return (the frame is made on torch's stream,
+    the filter runs on the handle's: both are drained here)."""
+    if not frame.is_cuda or frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 4:
+        raise ValueError("antialias_frame: a (height, width, 4) uint8 device tensor is needed")
+    frame = frame.contiguous()
+    out = torch.empty_like(frame)
+    torch.cuda.current_stream(frame.device).synchronize()
+    renderer.antialias_device(frame.data_ptr(), out.data_ptr(), frame.shape[1], frame.shape[0])
+    renderer.flush()
+    return out
+
+
+def assemble_banded(gathered, height, band_rows=16, antialias=None):
+    """root only: the full frame from interleaved shards (one indexed copy per rank).  antialias: a Renderer whose antialias_device
+    then filters the assembled frame (antialias_frame)."""
     world = len(gathered)
     frame = torch.empty((height,) + tuple(gathered[0].shape[1:]), dtype=gathered[0].dtype, device=gathered[0].device)
     for k, g in enumerate(gathered):
         idx = torch.as_tensor(owned_rows(height, k, world, band_rows), device=g.device)
         frame.index_copy_(0, idx, g)
-    return frame
+    return frame if antialias is None else antialias_frame(frame, antialias)
 
 
 class _Works:
@@ -154,6 +170,8 @@ def _all_equal_rows(shard, world, group):
     return bool(t[0].item() == -t[1].item())
 
 
-def assemble(gathered):
-    """root only: the full frame (height, width, 4) from the per-rank shards."""
-    return torch.cat(gathered, dim=0)
+def assemble(gathered, antialias=None):
+    """root only: the full frame (height, width, 4) from the per-rank shards.  antialias: a Renderer whose antialias_device then filters the
+    assembled frame (antialias_frame)."""
+    frame = torch.cat(gathered, dim=0)
+    return frame if antialias is None else antialias_frame(frame, antialias)

@@ -547,7 +547,57 @@ int arctic_stats(ArcticRenderer *r, uint64_t *out, uint32_t n);
  * order).  Not provided: anisotropic filtering, a LOD bias, chains for the environment map, the shadow maps or materials with images of
  * unequal sizes, a chain supplied by the caller.  INTEGRATION.md section 5h: what a DX12 host sets. */
 #define ARCTIC_OPT_TEXTURE_MIPS     27
+/* ARCTIC_OPT_ANTIALIAS: an edge anti-aliasing pass on the finished RGBA8 image (no counterpart in the reference, which left its staircases to the
+ * swap chain and the display's scaling).  The renderer takes one sample per pixel; this filter is FXAA's structure -- the 3 x 3 orientation
+ * test, a search along the edge with a quarter-gradient stop, the offset 1/2 - d / span and the 0.75 smoothstep^2 sub-pixel term -- restated
+ * in integers, with whole-pixel steps and fixed-point quantities, so that it is DEFINED bit for bit (tests/antialias_reference.py).
+ *   0 (default)  no pass: the image is what it was, byte for byte, at the same speed.
+ *   1            a handle that owns the whole frame applies the filter below to the RGBA8 image of every arctic_pass_shade,
+ *                arctic_render_frame and arctic_render_frame_device: the shading kernels then always write the handle's own RGBA8 buffer and
+ *                the filter writes the destination -- the caller's d_out, or a second buffer of the handle, which arctic_render_frame,
+ *                arctic_read_output and arctic_gather_frame (d_shard = NULL) then read for rgba8.  The float LDR / HDR planes of
+ *                ARCTIC_OPT_KEEP_FLOAT_OUTPUT stay what shading wrote: they are NOT filtered.  arctic_time_shade stays the shading kernel alone.
+ *   any other value: ARCTIC_E_INVALID.
+ * Sharded handles.  A handle that owns only part of the frame (a row range, or interleaved bands of more than one shard) accepts the option and
+ * does NOT apply it: its shard lacks the neighbouring rows.  The root filters the assembled frame with arctic_antialias_device.
+ * The number 5 is the lowest unused one (ARCTIC_OPT_BANDS of the early two-kernel shading pass had it and left with that pass; no library
+ * since has known it); 27 stays the highest.
+ *
+ * The filter.  Input: a W x H RGBA8 image C, row-major.  Addressing: every read at a coordinate outside the image is clamped per axis to
+ * [0, W - 1] x [0, H - 1].  Arithmetic: all integers; nothing below needs more than 32 bits unsigned, or signed for the differences.
+ * Luma: Y(p) = 77 R + 150 G + 29 B, range 0 .. 65280.  Fixed constants: K = 12, T_MIN = 4096.
+ * For each pixel p = (x, y), with N = (x, y - 1), S = (x, y + 1), W = (x - 1, y), E = (x + 1, y) and M = p:
+ *   1. Early exit.  hi / lo are the max / min of Y over {M, N, S, W, E}, and rng = hi - lo.  If rng < max(T_MIN, hi >> 3) the output pixel is
+ *      the input pixel; the rest is skipped.
+ *   2. Orientation, with the corner lumas NW, NE, SW, SE:
+ *        eh = |NW + SW - 2 W| + 2 |N + S - 2 M| + |NE + SE - 2 E|
+ *        ev = |NW + NE - 2 N| + 2 |W + E - 2 M| + |SW + SE - 2 S|
+ *      The edge is horizontal iff eh >= ev.
+ *   3. Side.  (a, b) = (N, S) if horizontal, else (W, E).  ga = |Y(a) - Y(M)|, gb = |Y(b) - Y(M)|, g = max(ga, gb).  The side is a (step -1
+ *      along the normal axis) iff ga >= gb, else b (step +1).  n is that unit step, Ls the side pixel's luma, avg2 = Y(M) + Ls, and t the
+ *      unit step along the edge: (1, 0) if horizontal, else (0, 1).
+ *   4. Search, once per direction s in {-1, +1}.  For i = 1 .. K: q = clamp(p + s i t), e = Y(q) + Y(clamp(q + n)) - avg2.  The first i with
+ *      2 |e| >= g ends the search: d_s = i, e_s = e.  If none ends it, d_s = K and e_s is the e of i = K.
+ *   5. Edge offset.  span = d- + d+, d = min(d-, d+), e_end = e- if d- < d+, else e+.  good = (e_end < 0) != (Y(M) < Ls).
+ *      off_e = good ? floor(128 (span - 2 d) / span) : 0.
+ *   6. Sub-pixel offset.  A = |2 (N + S + E + W) + NW + NE + SW + SE - 12 M| (lumas).  s1 = min(256, floor(256 A / (12 rng))),
+ *      s2 = (s1 s1 (768 - 2 s1)) >> 16,  off_s = (s2 s2 3) >> 10.
+ *   7. Blend.  off = max(off_e, off_s), at most 192.  Cn = C(clamp(p + n)).  For each of R, G, B: out = (C (256 - off) + Cn off + 128) >> 8.
+ *      Alpha is copied from the input pixel.
+ * Not provided: filtering in front of the tonemapper, other thresholds or search lengths (one preset), a halo exchange between shards,
+ * temporal or multi-sample methods.  INTEGRATION.md section 5j: which buffer holds what, and the sharded case. */
+#define ARCTIC_OPT_ANTIALIAS         5
 int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value);
+
+/* The filter of ARCTIC_OPT_ANTIALIAS on any RGBA8 device image of width x height pixels (row-major, tightly packed, 4-byte aligned), whatever
+ * the handle's own size and options: d_in -> d_out, asynchronous on the handle's stream (arctic_flush before another stream reads d_out).
+ * This is what the root of a sharded frame calls on the assembled image.  ARCTIC_E_INVALID: a null pointer, a zero size, a pointer that is
+ * not 4-byte aligned, or d_in / d_out ranges that overlap (a pixel reads its neighbours: the filter cannot run in place). */
+int arctic_antialias_device(ArcticRenderer *r, const void *d_in, void *d_out, uint32_t width, uint32_t height);
+
+/* The same, host to host and synchronous: rgba8 and out are width x height x 4 bytes (they may be the same host buffer); staged through the
+ * handle's staging buffer like arctic_post_process. */
+int arctic_antialias(ArcticRenderer *r, const uint8_t *rgba8, uint32_t width, uint32_t height, uint8_t *out);
 
 /* Level `level` of a material's chain (ARCTIC_OPT_TEXTURE_MIPS; level 0 = the images as uploaded), for tests: dims = {w, h} of the level,
    texels = w x h x 8 bytes, row-major, no border, per texel {diffuse r, g, b, normal r, g, b, metal-rough g, b}.  texels may be NULL (the size
