@@ -31,6 +31,11 @@ SIGNATURES = {
     "arctic_use_own_stream": (_i32, [_vp]),
     "arctic_create_material": (_i32, [_vp, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _u32, _u32]),
     "arctic_create_mesh": (_i32, [_vp, _vp, _u64, _vp, _u64, _u64]),
+    "arctic_set_mesh_skin": (_i32, [_vp, _u64, _vp, _u64, _u32]),
+    "arctic_set_mesh_pose": (_i32, [_vp, _u64, _vp, _u32]),
+    "arctic_read_mesh_vertices": (_i32, [_vp, _u64, _vp, _u64]),
+    "arctic_check_mesh_skin": (_i32, [_vp, _u64, _u32]),
+    "arctic_skin_vertices": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp]),
     "arctic_set_material_extras": (_i32, [_vp, _u64, _vp, _vp, _u32, _u32, _vp, _u32, _u32]),
     "arctic_check_material_params": (_i32, [_vp]),
     "arctic_update_lights": (_i32, [_vp, _vp, _u64]),

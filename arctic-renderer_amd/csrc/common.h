@@ -475,6 +475,11 @@ hipError_t launch_gbuffer_tile(GBuffer g, float *attrs, uint32_t *mat, uint32_t 
 // another that does not overlap it; one workgroup per tile of ANTIALIAS_TILE_W x ANTIALIAS_TILE_H pixels
 constexpr uint32_t ANTIALIAS_TILE_W = 64, ANTIALIAS_TILE_H = 16;
 hipError_t launch_antialias(const void *in, void *out, uint32_t width, uint32_t height, hipStream_t s);
+// skeletal skinning (skin.hip, include/arctic_hip.h: arctic_set_mesh_pose): n_vertices vertices of 14 floats + their 24-byte skin records + n_joints
+// matrices of 16 floats -> out, 14 floats per vertex.  Up to SKIN_LDS_JOINTS joints the kernel stages the joint table in LDS, beyond it gathers from
+// global memory.  Every joint index of `skin` is below n_joints (arctic_set_mesh_skin checked it); all pointers 16-byte aligned
+constexpr uint32_t SKIN_LDS_JOINTS = 256;
+hipError_t launch_skin(const float *vertices, const void *skin, const float *joints, uint32_t n_vertices, uint32_t n_joints, float *out, hipStream_t s);
 
 // ---- host math (host_math.cpp): glm-equivalent builders, scene.cpp:9-19,41-70 ----------------
 void dir_from_rot(const float rot_deg[2], float out[3]);
@@ -486,5 +491,11 @@ float srgb8_to_linear(int c);
 // arctic_check_material_params: the twelve floats of an ArcticMaterialParams (include/arctic_hip.h) are all finite and in their ranges
 bool material_params_valid(const float p[12]);
 void camera_sky_basis(const float rot_deg[2], float aspect, float fov_y_deg, float fwd[3], float right[3], float up[3]);
+// skeletal skinning on the host (include/arctic_hip.h: arctic_check_mesh_skin, arctic_skin_vertices).  skin = n records of 24 bytes {uint16 joints[4];
+// float weights[4]}; mesh_skin_valid: 1 <= n_joints <= 65535, every joint index below it, every weight finite.  skin_vertices_host: the arithmetic
+// of k_skin, operation for operation (in may be out)
+bool mesh_skin_valid(const void *skin, uint64_t n, uint32_t n_joints);
+bool floats_finite(const float *p, uint64_t n);
+void skin_vertices_host(const float *in, const void *skin, uint64_t n, const float *joints, float *out);
 
 }  // namespace arctic

@@ -8,6 +8,8 @@
 // glm's operation order (compiled with -ffp-contract=off so each operation rounds once).
 // Matrices are 16 floats, m[col*4 + row] (glm memory order).
 #include <cmath>
+#include <cstddef>
+#include <cstdint>
 
 #include "common.h"
 
@@ -157,6 +159,45 @@ bool material_params_valid(const float p[12]) {
     for (int i : {0, 1, 2, 3, 4, 6}) if (!(p[i] >= 0.0f && p[i] <= 1.0f)) return false;
     for (int i : {7, 8, 9}) if (!(p[i] >= 0.0f)) return false;
     return p[10] == 0.0f && p[11] == 0.0f;
+}
+
+bool floats_finite(const float *p, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) if (!std::isfinite(p[i])) return false;
+    return true;
+}
+
+namespace {
+struct SkinRec { uint16_t joints[4]; float weights[4]; };   // ArcticSkinVertex
+static_assert(sizeof(SkinRec) == 24, "ArcticSkinVertex is 24 bytes");
+}  // namespace
+
+bool mesh_skin_valid(const void *skin, uint64_t n, uint32_t n_joints) {
+    if (!skin || n == 0 || n_joints == 0 || n_joints > 65535u) return false;
+    const SkinRec *s = static_cast<const SkinRec *>(skin);
+    for (uint64_t v = 0; v < n; ++v)
+        for (int k = 0; k < 4; ++k) if (s[v].joints[k] >= n_joints || !std::isfinite(s[v].weights[k])) return false;
+    return true;
+}
+
+// include/arctic_hip.h, arctic_set_mesh_pose: S = ((w0 J0 + w1 J1) + w2 J2) + w3 J3 per element of rows 0..2, the position through
+// geometry.hip's mat_vec order with w = 1, the three vectors through S's upper 3x3; nothing normalised, the texture coordinates copied
+void skin_vertices_host(const float *in, const void *skin, uint64_t n, const float *joints, float *out) {
+    const SkinRec *s = static_cast<const SkinRec *>(skin);
+    for (uint64_t v = 0; v < n; ++v) {
+        const float *x = in + v * 14;
+        const float *J0 = joints + (size_t)s[v].joints[0] * 16, *J1 = joints + (size_t)s[v].joints[1] * 16;
+        const float *J2 = joints + (size_t)s[v].joints[2] * 16, *J3 = joints + (size_t)s[v].joints[3] * 16;
+        const float w0 = s[v].weights[0], w1 = s[v].weights[1], w2 = s[v].weights[2], w3 = s[v].weights[3];
+        float S[16];
+        for (int e = 0; e < 16; ++e) S[e] = ((w0 * J0[e] + w1 * J1[e]) + w2 * J2[e]) + w3 * J3[e];
+        float y[14];
+        for (int i = 0; i < 3; ++i) {
+            y[i] = ((S[i] * x[0] + S[4 + i] * x[1]) + S[8 + i] * x[2]) + S[12 + i] * 1.0f;
+            for (int k = 1; k < 4; ++k) y[3 * k + i] = (S[i] * x[3 * k] + S[4 + i] * x[3 * k + 1]) + S[8 + i] * x[3 * k + 2];
+        }
+        y[12] = x[12]; y[13] = x[13];
+        for (int k = 0; k < 14; ++k) out[v * 14 + k] = y[k];
+    }
 }
 
 }  // namespace arctic

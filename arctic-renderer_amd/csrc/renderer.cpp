@@ -143,6 +143,32 @@ struct Mesh {
     uint32_t n_vertices = 0, n_indices = 0;
     uint64_t material = 0;
     std::vector<float> tbounds, vbounds;   // cluster_bounds: 6 floats per block of SETUP_THREADS triangles / of 256 vertices
+    // Skeletal skinning (arctic_set_mesh_skin / arctic_set_mesh_pose).  d_skin: one ArcticSkinVertex per vertex; while `posed`, d_posed -- a second
+    // vertex buffer written by k_skin from d_vertices, d_skin and the pose's matrices in d_joints -- is what ObjectRec::vertices points at, and the
+    // mesh's cluster boxes (which bound the bind pose) are replaced by infinite ones.  The matrices travel through a ring of pinned buffers, so
+    // that a pose call neither reads the caller's memory after it returns nor waits for the copy of the pose before it.
+    void *d_skin = nullptr;
+    uint32_t n_joints = 0;
+    float *d_posed = nullptr, *d_joints = nullptr;
+    bool posed = false;
+    static constexpr int POSE_RING = 3;
+    float *h_joints[POSE_RING] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev_joints[POSE_RING] = {nullptr, nullptr, nullptr};
+    bool joints_pending[POSE_RING] = {false, false, false};
+    int joints_turn = 0;
+    uint64_t shape_seq = 0;   // bumped by every successful skin / pose call: part of the shadow caches' keys (shadow_inputs, cube_inputs)
+    const float *vertices_in_use() const { return posed ? d_posed : d_vertices; }
+    void release_pose() {     // (the caller has drained the streams that may read these)
+        if (d_posed) (void)hipFree(d_posed);
+        if (d_joints) (void)hipFree(d_joints);
+        for (int k = 0; k < POSE_RING; ++k) {
+            if (h_joints[k]) (void)hipHostFree(h_joints[k]);
+            if (ev_joints[k]) (void)hipEventDestroy(ev_joints[k]);
+            h_joints[k] = nullptr; ev_joints[k] = nullptr; joints_pending[k] = false;
+        }
+        d_posed = d_joints = nullptr; posed = false;
+    }
+    void release_skin() { release_pose(); if (d_skin) (void)hipFree(d_skin); d_skin = nullptr; n_joints = 0; }
 };
 
 // Object-space boxes for geometry.hip's box_outside, made once per mesh on the host.  tbounds[c] = {min xyz, max xyz} of the positions
@@ -264,6 +290,11 @@ struct ArcticRenderer {
     DevBuf d_geo_counters, d_stage;
     hipStream_t shadow_stream = nullptr;            // arctic_render_frame draws the shadow map here while the main stream runs the visibility prepass
     hipEvent_t ev_fork = nullptr, ev_shadow = nullptr;
+    // Skinning: k_skin runs on the main stream, which has joined every earlier prepass (ev_prepass, ev_shadow) -- so it follows every k_vertex that
+    // still reads the buffer it overwrites.  ev_skin is recorded behind it; the shadow and prepass streams wait for it before their next pass
+    // (skin_seq counts the launches, *_seen what each of those streams has waited for)
+    hipEvent_t ev_skin = nullptr;
+    uint64_t skin_seq = 0, skin_seen_shadow = 0, skin_seen_prepass[2] = {0, 0};
     // The shadow pass has ONE set of scratch (geo[1], tables[1], its four counters) whichever stream it runs on -- the main stream
     // (arctic_pass_shadow_map, a sharded map, debug bit 7) or shadow_stream (whole frames).  ev_shadow_scratch marks the end of the
     // last shadow pass on shadow_scratch_stream; a pass on another stream waits for it first, so two never share the scratch.
@@ -428,7 +459,7 @@ int upload_pass_tables(ArcticRenderer *r, PassTables &T, DevBuf &d_xverts, hipSt
         const Mesh &m = r->meshes[o.mesh_idx];
         ObjectRec rec;
         std::memcpy(rec.trs, o.trs, sizeof rec.trs);
-        rec.vertices = m.d_vertices;
+        rec.vertices = m.vertices_in_use();
         rec.indices = m.d_indices;
         rec.n_vertices = m.n_vertices;
         rec.n_triangles = m.n_indices / 3;
@@ -439,8 +470,14 @@ int upload_pass_tables(ArcticRenderer *r, PassTables &T, DevBuf &d_xverts, hipSt
         uint32_t oi = (uint32_t)objs.size();
         for (uint32_t b = 0; b < rec.n_vertices; b += 256) { vb_obj.push_back(oi); vb_first.push_back(b); }
         for (uint32_t b = 0; b < rec.n_triangles; b += SETUP_THREADS) { tb_obj.push_back(oi); tb_first.push_back(b); }
-        vb_box.insert(vb_box.end(), m.vbounds.begin(), m.vbounds.end());
-        tb_box.insert(tb_box.end(), m.tbounds.begin(), m.tbounds.end());
+        if (m.posed) {   // the boxes bound the bind pose: a posed mesh gets cluster_bounds' "cannot bound" boxes, which are never skipped
+            const float inf = std::numeric_limits<float>::infinity(), open_box[6] = {-inf, -inf, -inf, inf, inf, inf};
+            for (size_t b = 0; b < m.vbounds.size() / 6; ++b) vb_box.insert(vb_box.end(), open_box, open_box + 6);
+            for (size_t b = 0; b < m.tbounds.size() / 6; ++b) tb_box.insert(tb_box.end(), open_box, open_box + 6);
+        } else {
+            vb_box.insert(vb_box.end(), m.vbounds.begin(), m.vbounds.end());
+            tb_box.insert(tb_box.end(), m.tbounds.begin(), m.tbounds.end());
+        }
         xv += rec.n_vertices;
         tri += rec.n_triangles;
         objs.push_back(rec);
@@ -929,7 +966,11 @@ std::vector<uint8_t> shadow_inputs(const ArcticRenderer *r, const ArcticScene *s
     put(head, sizeof head);
     put(sc->sun.position, sizeof sc->sun.position);
     put(sc->sun.rotation, sizeof sc->sun.rotation);
-    for (uint64_t i = 0; i < sc->n_objects; ++i) { put(sc->objects[i].trs, sizeof sc->objects[i].trs); put(&sc->objects[i].mesh_idx, sizeof sc->objects[i].mesh_idx); }
+    for (uint64_t i = 0; i < sc->n_objects; ++i) {
+        put(sc->objects[i].trs, sizeof sc->objects[i].trs); put(&sc->objects[i].mesh_idx, sizeof sc->objects[i].mesh_idx);
+        // the mesh's shape: a skin or pose call changes what the object casts (arctic_set_mesh_pose)
+        if (sc->objects[i].mesh_idx < r->meshes.size()) put(&r->meshes[sc->objects[i].mesh_idx].shape_seq, sizeof(uint64_t));
+    }
     return k;
 }
 
@@ -941,8 +982,18 @@ std::vector<uint8_t> cube_inputs(const ArcticRenderer *r, const ArcticScene *sc)
     const uint64_t head[6] = {r->cube_size, r->n_cubes, (uint64_t)r->meshes.size(), sc->n_objects, (uint64_t)r->cluster_cull, (uint64_t)r->small_triangles};
     put(head, sizeof head);
     put(r->cube_lights.data(), r->cube_lights.size() * sizeof(ArcticPointShadowLight));
-    for (uint64_t i = 0; i < sc->n_objects; ++i) { put(sc->objects[i].trs, sizeof sc->objects[i].trs); put(&sc->objects[i].mesh_idx, sizeof sc->objects[i].mesh_idx); }
+    for (uint64_t i = 0; i < sc->n_objects; ++i) {
+        put(sc->objects[i].trs, sizeof sc->objects[i].trs); put(&sc->objects[i].mesh_idx, sizeof sc->objects[i].mesh_idx);
+        // the mesh's shape: a skin or pose call changes what the object casts (arctic_set_mesh_pose)
+        if (sc->objects[i].mesh_idx < r->meshes.size()) put(&r->meshes[sc->objects[i].mesh_idx].shape_seq, sizeof(uint64_t));
+    }
     return k;
+}
+
+// a stream other than the main one is about to run a prepass: it first waits for the latest k_skin (enqueued on the main stream)
+int wait_skin(ArcticRenderer *r, hipStream_t stream, uint64_t &seen) {
+    if (seen != r->skin_seq) { HIPCHECK(r, hipStreamWaitEvent(stream, r->ev_skin, 0)); seen = r->skin_seq; }
+    return ARCTIC_OK;
 }
 
 // after a stream synchronisation: did a rasteriser pass run out of work-item slots?  (k_setup flags it; the table is re-sized
@@ -996,7 +1047,7 @@ bool valid_scene(const ArcticScene *sc) { return sc && (sc->n_objects == 0 || sc
 // =================================================================================================
 extern "C" {
 
-int arctic_version(void) { return 330; }
+int arctic_version(void) { return 340; }
 
 ArcticRenderer *arctic_create(const ArcticCreateInfo *info, char *err, uint64_t err_len) {
     auto say = [&](const char *m) { if (err && err_len) { std::snprintf(err, (size_t)err_len, "%s", m); } };
@@ -1040,6 +1091,7 @@ ArcticRenderer *arctic_create(const ArcticCreateInfo *info, char *err, uint64_t 
     if ((e = hipEventCreateWithFlags(&r->ev_fork, in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreateWithFlags(&r->ev_shadow, in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreateWithFlags(&r->ev_shadow_scratch, in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = hipEventCreateWithFlags(&r->ev_skin, in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
     // The HIP runtime deals its hardware queues (4 by default, GPU_MAX_HW_QUEUES) to streams in the order they are created, and two
     // streams on one queue do not overlap: the handle's own stream, the shadow stream and the first prepass stream are created here, in
     // that order (with a caller's stream that makes four); the second prepass stream, which only three frames in flight use, is the
@@ -1093,8 +1145,9 @@ void arctic_destroy(ArcticRenderer *r) {
     if (r->ev_fork) (void)hipEventDestroy(r->ev_fork);
     if (r->ev_shadow) (void)hipEventDestroy(r->ev_shadow);
     if (r->ev_shadow_scratch) (void)hipEventDestroy(r->ev_shadow_scratch);
+    if (r->ev_skin) (void)hipEventDestroy(r->ev_skin);
     if (r->own_stream) { (void)hipStreamSynchronize(r->own_stream); (void)hipStreamDestroy(r->own_stream); }
-    for (Mesh &m : r->meshes) { if (m.d_vertices) (void)hipFree(m.d_vertices); if (m.d_indices) (void)hipFree(m.d_indices); }
+    for (Mesh &m : r->meshes) { m.release_skin(); if (m.d_vertices) (void)hipFree(m.d_vertices); if (m.d_indices) (void)hipFree(m.d_indices); }
     for (void *p : r->tex_allocs) (void)hipFree(p);
     for (ArcticRenderer::Extras &x : r->extras) for (void *p : {x.d_emissive, x.d_occlusion, x.d_fast}) if (p) (void)hipFree(p);
     DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_spots, &r->d_cubes, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4, &r->d_lod,
@@ -1144,6 +1197,7 @@ int arctic_set_stream(ArcticRenderer *r, void *hip_stream) {
     //  communication stream -- it is NOT waited for here: it may hold a collective the other ranks have not reached yet)
     if (r->own_stream_is_prepass()) HIPCHECK(r, hipStreamSynchronize(r->own_stream));
     r->stream = static_cast<hipStream_t>(hip_stream);   // NULL = the default stream
+    r->skin_seen_prepass[1] = 0;   // (the second prepass stream may be another one now: it waits for the latest k_skin again)
     return ARCTIC_OK;
 }
 
@@ -1164,6 +1218,7 @@ int arctic_use_own_stream(ArcticRenderer *r) {
         r->own_stream = fresh;
     }
     r->stream = r->own_stream;
+    r->skin_seen_prepass[1] = 0;
     return ARCTIC_OK;
 }
 
@@ -1329,6 +1384,88 @@ int arctic_create_mesh(ArcticRenderer *r, const ArcticVertex *vertices, uint64_t
     HIPCHECK(r, hipMemcpy(m.d_vertices, vertices, n_vertices * sizeof(ArcticVertex), hipMemcpyHostToDevice));
     HIPCHECK(r, hipMemcpy(m.d_indices, indices, n_indices * 4, hipMemcpyHostToDevice));
     return (int)r->meshes.size() - 1;
+}
+
+int arctic_check_mesh_skin(const ArcticSkinVertex *skin, uint64_t n_vertices, uint32_t n_joints) {
+    return mesh_skin_valid(skin, n_vertices, n_joints) ? ARCTIC_OK : ARCTIC_E_INVALID;
+}
+
+int arctic_skin_vertices(const ArcticVertex *in, const ArcticSkinVertex *skin, uint64_t n_vertices, const float *joint_matrices, uint32_t n_joints,
+                         ArcticVertex *out) {
+    if (!in || !out || !joint_matrices || !mesh_skin_valid(skin, n_vertices, n_joints) || !floats_finite(joint_matrices, (uint64_t)n_joints * 16))
+        return ARCTIC_E_INVALID;
+    skin_vertices_host(reinterpret_cast<const float *>(in), skin, n_vertices, joint_matrices, reinterpret_cast<float *>(out));
+    return ARCTIC_OK;
+}
+
+int arctic_set_mesh_skin(ArcticRenderer *r, uint64_t mesh, const ArcticSkinVertex *skin, uint64_t n_vertices, uint32_t n_joints) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (mesh >= r->meshes.size()) return r->fail(ARCTIC_E_INVALID, "set_mesh_skin: mesh %llu does not exist", (unsigned long long)mesh);
+    Mesh &m = r->meshes[mesh];
+    void *d_new = nullptr;
+    int rc = select_device(r);
+    if (rc) return rc;
+    if (skin) {
+        if (n_vertices != m.n_vertices) return r->fail(ARCTIC_E_INVALID, "set_mesh_skin: %llu skin records for a mesh of %u vertices", (unsigned long long)n_vertices, m.n_vertices);
+        if (!mesh_skin_valid(skin, n_vertices, n_joints))
+            return r->fail(ARCTIC_E_INVALID, "set_mesh_skin: n_joints %u outside 1..65535, a joint index at or above it, or a weight that is not finite", n_joints);
+        HIPCHECK(r, hipMalloc(&d_new, n_vertices * sizeof(ArcticSkinVertex)));
+        if (hipMemcpy(d_new, skin, n_vertices * sizeof(ArcticSkinVertex), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); return r->fail(ARCTIC_E_DEVICE, "set_mesh_skin: upload"); }
+    }
+    // what is replaced may still be read: by a k_skin, or -- the posed buffer -- by a prepass; every prepass stream has been joined into the main stream
+    if (m.d_skin) HIPCHECK(r, hipStreamSynchronize(r->stream));
+    m.release_skin();
+    m.d_skin = d_new; m.n_joints = skin ? n_joints : 0;
+    ++m.shape_seq;
+    return ARCTIC_OK;
+}
+
+int arctic_set_mesh_pose(ArcticRenderer *r, uint64_t mesh, const float *joint_matrices, uint32_t n_joints) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (mesh >= r->meshes.size()) return r->fail(ARCTIC_E_INVALID, "set_mesh_pose: mesh %llu does not exist", (unsigned long long)mesh);
+    Mesh &m = r->meshes[mesh];
+    if (!m.d_skin) return r->fail(ARCTIC_E_STATE, "set_mesh_pose: mesh %llu has no skin (arctic_set_mesh_skin)", (unsigned long long)mesh);
+    if (!joint_matrices && n_joints == 0) {   // back to the bind pose: the original buffer and the real cluster boxes (the posed buffer is kept for the next pose)
+        m.posed = false;
+        ++m.shape_seq;
+        return ARCTIC_OK;
+    }
+    if (!joint_matrices || n_joints != m.n_joints) return r->fail(ARCTIC_E_INVALID, "set_mesh_pose: %u joint matrices for a skin of %u joints", n_joints, m.n_joints);
+    if (!floats_finite(joint_matrices, (uint64_t)n_joints * 16)) return r->fail(ARCTIC_E_INVALID, "set_mesh_pose: a matrix element is not finite");
+    int rc = select_device(r);
+    if (rc) return rc;
+    const size_t bytes = (size_t)n_joints * 64;
+    if (!m.d_posed) HIPCHECK(r, hipMalloc((void **)&m.d_posed, (size_t)m.n_vertices * sizeof(ArcticVertex)));
+    if (!m.d_joints) HIPCHECK(r, hipMalloc((void **)&m.d_joints, bytes));
+    const int slot = m.joints_turn;
+    if (!m.h_joints[slot]) HIPCHECK(r, hipHostMalloc((void **)&m.h_joints[slot], bytes));
+    if (!m.ev_joints[slot]) HIPCHECK(r, hipEventCreateWithFlags(&m.ev_joints[slot], hipEventDisableTiming));
+    if (m.joints_pending[slot]) { HIPCHECK(r, hipEventSynchronize(m.ev_joints[slot])); m.joints_pending[slot] = false; }   // (the copy of POSE_RING poses ago)
+    std::memcpy(m.h_joints[slot], joint_matrices, bytes);
+    m.joints_turn = (slot + 1) % Mesh::POSE_RING;
+    // on the main stream: behind every prepass enqueued so far (arctic_render_frame joins its prepass streams into it), so behind every k_vertex
+    // that reads the buffer k_skin overwrites
+    HIPCHECK(r, hipMemcpyAsync(m.d_joints, m.h_joints[slot], bytes, hipMemcpyHostToDevice, r->stream));
+    HIPCHECK(r, hipEventRecord(m.ev_joints[slot], r->stream));
+    m.joints_pending[slot] = true;
+    HIPCHECK(r, launch_skin(m.d_vertices, m.d_skin, m.d_joints, m.n_vertices, n_joints, m.d_posed, r->stream));
+    HIPCHECK(r, hipEventRecord(r->ev_skin, r->stream));
+    ++r->skin_seq;
+    m.posed = true;
+    ++m.shape_seq;
+    return ARCTIC_OK;
+}
+
+int arctic_read_mesh_vertices(ArcticRenderer *r, uint64_t mesh, ArcticVertex *out, uint64_t n_vertices) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (mesh >= r->meshes.size()) return r->fail(ARCTIC_E_INVALID, "read_mesh_vertices: mesh %llu does not exist", (unsigned long long)mesh);
+    const Mesh &m = r->meshes[mesh];
+    if (!out || n_vertices != m.n_vertices) return r->fail(ARCTIC_E_INVALID, "read_mesh_vertices: room for %llu vertices, the mesh has %u", (unsigned long long)n_vertices, m.n_vertices);
+    int rc = select_device(r);
+    if (rc) return rc;
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    HIPCHECK(r, hipMemcpy(out, m.vertices_in_use(), n_vertices * sizeof(ArcticVertex), hipMemcpyDeviceToHost));
+    return ARCTIC_OK;
 }
 
 int arctic_update_lights(ArcticRenderer *r, const ArcticPointLight *lights, uint64_t n) {
@@ -1583,7 +1720,8 @@ int arctic_render_frame_device(ArcticRenderer *r, const ArcticScene *scene, cons
                 HIPCHECK(r, hipEventRecord(r->ev_fork, r->stream));
                 HIPCHECK(r, hipStreamWaitEvent(r->shadow_stream, r->ev_fork, 0));
             }
-            rc = pass_shadow_map(r, scene, r->shadow_stream);
+            rc = wait_skin(r, r->shadow_stream, r->skin_seen_shadow);
+            if (rc == ARCTIC_OK) rc = pass_shadow_map(r, scene, r->shadow_stream);
             if (rc == ARCTIC_OK && !(r->debug & 8)) rc = build_shadow_bounds(r, r->shadow_stream);
             HIPCHECK(r, hipEventRecord(r->ev_shadow, r->shadow_stream));
         } else rc = pass_shadow_map(r, scene, r->stream);
@@ -1611,7 +1749,8 @@ int arctic_render_frame_device(ArcticRenderer *r, const ArcticScene *scene, cons
             else { if (!r->prepass_stream[1]) HIPCHECK(r, hipStreamCreateWithFlags(&r->prepass_stream[1], hipStreamNonBlocking)); ps = r->prepass_stream[1]; }
         }
         if (r->released_valid[r->cur]) HIPCHECK(r, hipStreamWaitEvent(ps, r->ev_released[r->cur], 0));
-        rc = pass_visibility(r, scene, ps);
+        rc = wait_skin(r, ps, r->skin_seen_prepass[turn]);
+        if (rc == ARCTIC_OK) rc = pass_visibility(r, scene, ps);
         HIPCHECK(r, hipEventRecord(r->ev_prepass[turn], ps));
         HIPCHECK(r, hipStreamWaitEvent(r->stream, r->ev_prepass[turn], 0));
     } else rc = vis_path ? pass_visibility(r, scene, r->stream) : pass_gbuffer(r, scene);

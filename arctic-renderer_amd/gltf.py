@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .scene import LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, OBJECT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, neutral_material_params
+from .scene import LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, OBJECT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, neutral_material_params
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "host", "libarctic_gltf.so")
@@ -42,6 +42,14 @@ def lib():
         for f in ("arctic_gltf_spot_lights", "arctic_gltf_point_lights"):
             getattr(L, f).restype, getattr(L, f).argtypes = vp, [vp, u64p]
         L.arctic_gltf_directional_light_count.restype, L.arctic_gltf_directional_light_count.argtypes = u64, [vp]
+        for f in ("arctic_gltf_skin_count", "arctic_gltf_animation_count"):
+            getattr(L, f).restype, getattr(L, f).argtypes = u64, [vp]
+        L.arctic_gltf_skin_joint_count.restype, L.arctic_gltf_skin_joint_count.argtypes = u64, [vp, u64]
+        L.arctic_gltf_animation_duration.restype, L.arctic_gltf_animation_duration.argtypes = C.c_double, [vp, u64]
+        L.arctic_gltf_mesh_skin.restype = C.c_int
+        L.arctic_gltf_mesh_skin.argtypes = [vp, u64, C.POINTER(vp), u64p, C.POINTER(C.c_int64), u32p]
+        L.arctic_gltf_pose.restype, L.arctic_gltf_pose.argtypes = C.c_int, [vp, u64, C.c_int64, C.c_double, vp]
+        L.arctic_gltf_last_error.restype, L.arctic_gltf_last_error.argtypes = C.c_char_p, [vp]
         L.arctic_png_decode.restype = vp
         L.arctic_png_decode.argtypes = [C.c_char_p, u64, u32p, u32p, C.c_char_p, u64]
         L.arctic_png_free.restype, L.arctic_png_free.argtypes = None, [vp]
@@ -55,7 +63,9 @@ class GltfScene:
     spot_lights (SPOT_LIGHT_DTYPE, for Renderer.update_spot_lights), point_lights (LIGHT_DTYPE, for update_lights),
     directional_lights (a count; include/arctic_gltf.h).  upload() uploads no lights.
     The glTF material model beyond the three images: material_params (MATERIAL_PARAMS_DTYPE, one record per material), emissive_images and
-    occlusion_images (one entry per material: (h, w, 4) uint8 or None).  upload(material_model="gltf") applies them."""
+    occlusion_images (one entry per material: (h, w, 4) uint8 or None).  upload(material_model="gltf") applies them.
+    Skins and animations: mesh_skins (one entry per mesh: None, or (SKIN_VERTEX_DTYPE records, skin index, joint count)), skin_joint_counts,
+    animation_durations (seconds, one per animation).  joint_matrices() evaluates a pose, pose() hands it to a renderer."""
 
     def __init__(self, materials, meshes, objects, spot_lights=None, point_lights=None, directional_lights=0, material_params=None,
                  emissive_images=None, occlusion_images=None):
@@ -66,6 +76,43 @@ class GltfScene:
         self.spot_lights = np.zeros(0, SPOT_LIGHT_DTYPE) if spot_lights is None else spot_lights
         self.point_lights = np.zeros(0, LIGHT_DTYPE) if point_lights is None else point_lights
         self.directional_lights = directional_lights
+        self.mesh_skins = [None] * len(meshes)
+        self.skin_joint_counts, self.animation_durations = [], []
+        self._handle = None       # the loader's handle, kept while the scene has skins to pose
+        self._skinned = {}        # id(renderer) -> first_mesh its skins were attached at
+
+    def __del__(self):
+        if getattr(self, "_handle", None):
+            lib().arctic_gltf_free(self._handle)
+            self._handle = None
+
+    def joint_matrices(self, skin, animation=-1, time=0.0):
+        """(n_joints, 16) float32 for Renderer.set_mesh_pose: inverse(global(mesh node)) . global(joint) . inverseBind of the file's skin
+        `skin` under animation `animation` (-1: the rest pose) at `time` seconds (clamped to each sampler's range); computed in binary64 and
+        rounded once (include/arctic_gltf.h: arctic_gltf_pose).  Raises ValueError with the loader's message, e.g. for a CUBICSPLINE sampler."""
+        if not self._handle or not 0 <= skin < len(self.skin_joint_counts):
+            raise ValueError(f"joint_matrices: the scene has no skin {skin}")
+        out = np.empty((self.skin_joint_counts[skin], 16), np.float32)
+        L = lib()
+        if L.arctic_gltf_pose(self._handle, int(skin), int(animation), float(time), out.ctypes.data) != 0:
+            raise ValueError(L.arctic_gltf_last_error(self._handle).decode())
+        return out
+
+    def pose(self, renderer, animation=-1, time=0.0, first_mesh=0):
+        """pose every skinned mesh of the scene on `renderer` (an object with set_mesh_skin / set_mesh_pose, after upload()): attaches the
+        skins the first time it is called for that renderer, then sets each mesh's pose.  first_mesh: the index upload()'s first create_mesh
+        returned (0 for a renderer that held no meshes)."""
+        used = sorted({ms[1] for ms in self.mesh_skins if ms is not None})
+        poses = {k: self.joint_matrices(k, animation, time) for k in used}     # (evaluated first: a refused animation changes nothing)
+        if self._skinned.get(id(renderer)) != first_mesh:
+            for i, ms in enumerate(self.mesh_skins):
+                if ms is not None:
+                    renderer.set_mesh_skin(first_mesh + i, ms[0], ms[2])
+            self._skinned[id(renderer)] = first_mesh
+        for i, ms in enumerate(self.mesh_skins):
+            if ms is not None:
+                renderer.set_mesh_pose(first_mesh + i, poses[ms[1]])
+        return renderer
 
     def upload(self, renderer, material_model="reference"):
         """material_model "reference": the three images alone, what the reference's load_scene uploads.  "gltf": also the factors, emissive and
@@ -114,11 +161,22 @@ def load(path):
             n = C.c_uint64()
             p = fn(h, C.byref(n))
             return np.frombuffer(C.string_at(p, n.value * dtype.itemsize), dtype=dtype).copy() if n.value else np.zeros(0, dtype)
-        return GltfScene(materials, meshes, objects, lights(L.arctic_gltf_spot_lights, SPOT_LIGHT_DTYPE),
-                         lights(L.arctic_gltf_point_lights, LIGHT_DTYPE), int(L.arctic_gltf_directional_light_count(h)),
-                         material_params=params, emissive_images=emissive, occlusion_images=occlusion)
+        scene = GltfScene(materials, meshes, objects, lights(L.arctic_gltf_spot_lights, SPOT_LIGHT_DTYPE),
+                          lights(L.arctic_gltf_point_lights, LIGHT_DTYPE), int(L.arctic_gltf_directional_light_count(h)),
+                          material_params=params, emissive_images=emissive, occlusion_images=occlusion)
+        for i in range(len(meshes)):
+            ps, nv, si, nj = C.c_void_p(), C.c_uint64(), C.c_int64(), C.c_uint32()
+            assert L.arctic_gltf_mesh_skin(h, i, C.byref(ps), C.byref(nv), C.byref(si), C.byref(nj)) == 0
+            if si.value >= 0:
+                scene.mesh_skins[i] = (np.frombuffer(C.string_at(ps, nv.value * SKIN_VERTEX_DTYPE.itemsize), dtype=SKIN_VERTEX_DTYPE).copy(), int(si.value), int(nj.value))
+        scene.skin_joint_counts = [int(L.arctic_gltf_skin_joint_count(h, k)) for k in range(L.arctic_gltf_skin_count(h))]
+        scene.animation_durations = [float(L.arctic_gltf_animation_duration(h, k)) for k in range(L.arctic_gltf_animation_count(h))]
+        if scene.skin_joint_counts:      # arctic_gltf_pose needs the loader's handle: the scene owns it from here on
+            scene._handle, h = h, None
+        return scene
     finally:
-        L.arctic_gltf_free(h)
+        if h:
+            L.arctic_gltf_free(h)
 
 
 def png_decode(data):

@@ -491,7 +491,63 @@ struct Material {
     Image emissive, occlusion;
     ArcticMaterialParams params = {{1.0f, 1.0f, 1.0f}, 1.0f, 1.0f, 1.0f, 1.0f, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f}};
 };
-struct Mesh { std::vector<ArcticVertex> v; std::vector<uint32_t> idx; uint64_t material = 0; };
+// joints / weights: the primitive's JOINTS_0 and WEIGHTS_0 as read (empty: it has none); skin: the file's skin the mesh was met under
+// (-1: none), whose joint count the indices were checked against; node: the node it was met on (the pose is relative to it)
+struct Mesh {
+    std::vector<ArcticVertex> v; std::vector<uint32_t> idx; uint64_t material = 0;
+    std::vector<ArcticSkinVertex> skin_data;
+    long skin = -1, node = -1;
+};
+
+// ---- skins and animations: kept in binary64, evaluated by arctic_gltf_pose
+struct Skin { std::vector<size_t> joints; std::vector<double> inverse_bind; };   // 16 per joint, column-major as in the file
+struct Channel { size_t node = 0; int path = 0 /* 0 translation, 1 rotation, 2 scale */; bool step = false; std::vector<double> times, values; };
+struct Animation { std::vector<Channel> channels; double duration = 0.0; std::string unsupported; /* not empty: posing with it fails with this message */ };
+struct NodeTransform { long parent = -1; bool has_matrix = false; double matrix[16]; double t[3] = {0, 0, 0}, q[4] = {0, 0, 0, 1}, s[3] = {1, 1, 1}; };
+
+struct D4 { double m[16]; };   // m[col * 4 + row]
+D4 d_identity() { D4 r{}; r.m[0] = r.m[5] = r.m[10] = r.m[15] = 1.0; return r; }
+D4 d_mul(const D4 &a, const D4 &b) {
+    D4 r;
+    for (int j = 0; j < 4; ++j)
+        for (int i = 0; i < 4; ++i) {
+            double x = 0.0;
+            for (int k = 0; k < 4; ++k) x += a.m[k * 4 + i] * b.m[j * 4 + k];
+            r.m[j * 4 + i] = x;
+        }
+    return r;
+}
+D4 d_trs(const double *t, const double *q, const double *s) {
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    D4 r = d_identity();
+    r.m[0] = (1 - 2 * (y * y + z * z)) * s[0]; r.m[1] = (2 * (x * y + z * w)) * s[0]; r.m[2] = (2 * (x * z - y * w)) * s[0];
+    r.m[4] = (2 * (x * y - z * w)) * s[1]; r.m[5] = (1 - 2 * (x * x + z * z)) * s[1]; r.m[6] = (2 * (y * z + x * w)) * s[1];
+    r.m[8] = (2 * (x * z + y * w)) * s[2]; r.m[9] = (2 * (y * z - x * w)) * s[2]; r.m[10] = (1 - 2 * (x * x + y * y)) * s[2];
+    r.m[12] = t[0]; r.m[13] = t[1]; r.m[14] = t[2];
+    return r;
+}
+// Gauss-Jordan with partial pivoting; false: singular or not finite
+bool d_inverse(const D4 &a, D4 &out) {
+    double w[4][8];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { w[r][c] = a.m[c * 4 + r]; w[r][4 + c] = r == c ? 1.0 : 0.0; }
+    for (int c = 0; c < 4; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < 4; ++r) if (std::fabs(w[r][c]) > std::fabs(w[piv][c])) piv = r;
+        if (!(std::fabs(w[piv][c]) > 0.0) || !std::isfinite(w[piv][c])) return false;
+        if (piv != c) for (int k = 0; k < 8; ++k) std::swap(w[piv][k], w[c][k]);
+        const double inv = 1.0 / w[c][c];
+        for (int k = 0; k < 8; ++k) w[c][k] *= inv;
+        for (int r = 0; r < 4; ++r) if (r != c) { const double f = w[r][c]; if (f != 0.0) for (int k = 0; k < 8; ++k) w[r][k] -= f * w[c][k]; }
+    }
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { out.m[c * 4 + r] = w[r][4 + c]; if (!std::isfinite(out.m[c * 4 + r])) return false; }
+    return true;
+}
+// a unit quaternion from any four numbers; a zero or non-finite one is the identity rotation
+void q_normalize(double *q) {
+    const double l = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (!(l > 0.0) || !std::isfinite(l)) { q[0] = q[1] = q[2] = 0.0; q[3] = 1.0; return; }
+    for (int k = 0; k < 4; ++k) q[k] /= l;
+}
 
 }  // namespace
 
@@ -503,6 +559,11 @@ struct ArcticGltf {
     std::vector<ArcticSpotLight> spot_lights;     // spot lights, and point lights with a range (outer = pi)
     std::vector<ArcticPointLight> point_lights;   // point lights without a range
     uint64_t directional_lights = 0;              // counted, not exported: the sun stays the host's
+    // skins and animations (not read by the reference's load_scene): arctic_gltf_pose evaluates them
+    std::vector<Skin> skins;
+    std::vector<Animation> animations;
+    std::vector<NodeTransform> nodes;             // filled only when the file has skins
+    mutable std::string pose_error;               // arctic_gltf_last_error
 };
 
 namespace {
@@ -542,7 +603,7 @@ struct Loader {
     std::vector<float> floats(size_t accessor, int n_comp) {
         const Json &a = doc.at("accessors")[accessor];
         if (a.has("sparse")) fail("glTF: sparse accessors are not supported");
-        static const std::map<std::string, int> comps = {{"SCALAR", 1}, {"VEC2", 2}, {"VEC3", 3}, {"VEC4", 4}};
+        static const std::map<std::string, int> comps = {{"SCALAR", 1}, {"VEC2", 2}, {"VEC3", 3}, {"VEC4", 4}, {"MAT4", 16}};
         const auto it = comps.find(a.at("type").as_str());
         if (it == comps.end() || it->second < n_comp) fail("glTF: accessor type mismatch");
         const int file_comp = it->second;
@@ -805,6 +866,25 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
                     for (int c = 0; c < 3; ++c) m.v[v].bitangent[c] = b[c] * tan[v * 4 + 3];
                 }
             } else calc_tangents(m);
+            if (at.has("JOINTS_0") != at.has("WEIGHTS_0")) fail("glTF: JOINTS_0 and WEIGHTS_0 come together");
+            if (at.has("JOINTS_0")) {   // u8 / u16 indices; float or normalised u8 / u16 weights (the specification's list)
+                const size_t ja = Loader::index_of(at.at("JOINTS_0"), "JOINTS_0 accessor"), wa = Loader::index_of(at.at("WEIGHTS_0"), "WEIGHTS_0 accessor");
+                const Json &jacc = doc.at("accessors")[ja], &wacc = doc.at("accessors")[wa];
+                const int64_t jct = jacc.at("componentType").as_int(), wct = wacc.at("componentType").as_int();
+                if (jct != 5121 && jct != 5123) fail("glTF: JOINTS_0 must be unsigned bytes or unsigned shorts");
+                if (jacc.has("normalized") && jacc.at("normalized").b) fail("glTF: JOINTS_0 must not be normalised");
+                if (wct != 5126 && !((wct == 5121 || wct == 5123) && wacc.has("normalized") && wacc.at("normalized").b))
+                    fail("glTF: WEIGHTS_0 must be floats or normalised unsigned bytes / shorts");
+                const std::vector<float> jo = L.floats(ja, 4), we = L.floats(wa, 4);
+                if (jo.size() / 4 != nv || we.size() / 4 != nv) fail("glTF: attribute counts differ");
+                m.skin_data.resize(nv);
+                for (size_t v = 0; v < nv; ++v)
+                    for (int c = 0; c < 4; ++c) {
+                        if (!std::isfinite(we[v * 4 + c])) fail("glTF: a vertex weight is not finite");
+                        m.skin_data[v].joints[c] = (uint16_t)jo[v * 4 + c];   // (0 .. 65535 by the component type)
+                        m.skin_data[v].weights[c] = we[v * 4 + c];
+                    }
+            }
             m.material = p.has("material") ? (uint64_t)p.at("material").as_int() : 0;
             if (m.material >= g->materials.size()) fail("glTF: material index out of range");
             g->meshes.push_back(std::move(m));
@@ -875,6 +955,132 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
         g->spot_lights.push_back(l);
     };
 
+    // skins and animations (no counterpart in the reference).  Everything is checked here, so that arctic_gltf_pose only evaluates: joints are
+    // nodes, inverseBindMatrices (default: identity) has a finite matrix per joint, sampler inputs increase strictly, outputs match them
+    const size_t n_nodes_all = doc.has("nodes") ? doc.at("nodes").size() : 0;
+    const size_t n_skins = doc.has("skins") ? doc.at("skins").size() : 0;
+    for (size_t i = 0; i < n_skins; ++i) {
+        const Json &sk = doc.at("skins")[i];
+        Skin out;
+        const Json &js = sk.at("joints");
+        if (js.kind != Json::Array || js.size() == 0 || js.size() > 65535) fail("glTF: a skin needs 1 .. 65535 joints");
+        for (size_t k = 0; k < js.size(); ++k) {
+            const size_t n = Loader::index_of(js[k], "joint index");
+            if (n >= n_nodes_all) fail("glTF: a skin's joint is not a node");
+            out.joints.push_back(n);
+        }
+        if (sk.has("inverseBindMatrices")) {
+            const size_t acc = Loader::index_of(sk.at("inverseBindMatrices"), "inverseBindMatrices accessor");
+            const Json &a = doc.at("accessors")[acc];
+            if (a.at("type").as_str() != "MAT4" || a.at("componentType").as_int() != 5126) fail("glTF: inverseBindMatrices must be float MAT4");
+            const std::vector<float> m = L.floats(acc, 16);
+            if (m.size() / 16 < out.joints.size()) fail("glTF: inverseBindMatrices has fewer matrices than the skin has joints");
+            for (size_t k = 0; k < out.joints.size() * 16; ++k) {
+                if (!std::isfinite(m[k])) fail("glTF: an inverse bind matrix is not finite");
+                out.inverse_bind.push_back((double)m[k]);
+            }
+        } else
+            for (size_t k = 0; k < out.joints.size(); ++k) { const D4 id = d_identity(); out.inverse_bind.insert(out.inverse_bind.end(), id.m, id.m + 16); }
+        g->skins.push_back(std::move(out));
+    }
+    if (n_skins) {   // the node table arctic_gltf_pose walks: local transforms in binary64 and ONE parent per node
+        g->nodes.resize(n_nodes_all);
+        for (size_t i = 0; i < n_nodes_all; ++i) {
+            const Json &n = doc.at("nodes")[i];
+            NodeTransform &t = g->nodes[i];
+            const auto numbers = [&](const char *key, size_t count, double *out) {
+                const Json &a = n.at(key);
+                if (a.kind != Json::Array || a.size() != count) fail(std::string("glTF: node.") + key + " has the wrong length");
+                for (size_t k = 0; k < count; ++k) { out[k] = a[k].as_num(); if (!std::isfinite(out[k])) fail(std::string("glTF: node.") + key + " is not finite"); }
+            };
+            if (n.has("matrix")) { t.has_matrix = true; numbers("matrix", 16, t.matrix); }
+            if (n.has("translation")) numbers("translation", 3, t.t);
+            if (n.has("rotation")) { numbers("rotation", 4, t.q); q_normalize(t.q); }
+            if (n.has("scale")) numbers("scale", 3, t.s);
+            if (n.has("children"))
+                for (size_t k = 0; k < n.at("children").size(); ++k) {
+                    const size_t c = Loader::index_of(n.at("children")[k], "node index");
+                    if (c >= n_nodes_all) fail("glTF: node index out of range");
+                    if (g->nodes[c].parent >= 0 || c == i) fail("glTF: node graph is not a tree (a node has two parents)");
+                    g->nodes[c].parent = (long)i;
+                }
+        }
+        for (size_t i = 0; i < n_nodes_all; ++i) {   // no cycles: every walk towards the root ends
+            size_t steps = 0;
+            for (long p = g->nodes[i].parent; p >= 0; p = g->nodes[(size_t)p].parent) if (++steps > n_nodes_all) fail("glTF: node graph is not a tree (a cycle)");
+        }
+    }
+    const size_t n_anims = doc.has("animations") ? doc.at("animations").size() : 0;
+    for (size_t i = 0; i < n_anims; ++i) {
+        const Json &an = doc.at("animations")[i];
+        Animation out;
+        const Json &chs = an.at("channels"), &sms = an.at("samplers");
+        if (chs.kind != Json::Array || sms.kind != Json::Array) fail("glTF: animation channels and samplers must be arrays");
+        for (size_t k = 0; k < chs.size(); ++k) {
+            const Json &ch = chs[k];
+            const Json &target = ch.at("target");
+            if (!target.has("node")) continue;   // (the specification: a channel without a target node is ignored)
+            const std::string &path = target.at("path").as_str();
+            const Json &sm = sms[Loader::index_of(ch.at("sampler"), "sampler index")];
+            const std::string interp = sm.has("interpolation") ? sm.at("interpolation").as_str() : std::string("LINEAR");
+            Channel c;
+            c.node = Loader::index_of(target.at("node"), "node index");
+            if (c.node >= n_nodes_all) fail("glTF: an animation targets a node that does not exist");
+            if (path == "weights") { out.unsupported = "animation " + std::to_string(i) + " has a morph-target (weights) channel: not supported"; continue; }
+            if (interp == "CUBICSPLINE") { out.unsupported = "animation " + std::to_string(i) + " uses CUBICSPLINE interpolation: not supported"; continue; }
+            if (interp != "LINEAR" && interp != "STEP") fail("glTF: unknown animation interpolation '" + interp + "'");
+            c.path = path == "translation" ? 0 : path == "rotation" ? 1 : path == "scale" ? 2 : -1;
+            if (c.path < 0) fail("glTF: unknown animation path '" + path + "'");
+            c.step = interp == "STEP";
+            const size_t in_acc = Loader::index_of(sm.at("input"), "sampler input"), out_acc = Loader::index_of(sm.at("output"), "sampler output");
+            if (doc.at("accessors")[in_acc].at("componentType").as_int() != 5126) fail("glTF: sampler input must be float");
+            const std::vector<float> times = L.floats(in_acc, 1);
+            const int comps = c.path == 1 ? 4 : 3;
+            const Json &oa = doc.at("accessors")[out_acc];
+            const int64_t oct = oa.at("componentType").as_int();
+            if (oct != 5126 && !(oa.has("normalized") && oa.at("normalized").b)) fail("glTF: sampler output must be float or normalised integers");
+            if (oa.at("type").as_str() != (comps == 4 ? "VEC4" : "VEC3")) fail("glTF: sampler output has the wrong type for its path");
+            const std::vector<float> values = L.floats(out_acc, comps);
+            if (times.empty()) fail("glTF: an animation sampler has no keyframes");
+            if (values.size() / (size_t)comps != times.size()) fail("glTF: sampler output count does not match its input count");
+            for (size_t j = 0; j < times.size(); ++j) {
+                if (!std::isfinite(times[j]) || times[j] < 0.0f || (j && !(times[j] > times[j - 1]))) fail("glTF: sampler input must be finite, >= 0 and strictly increasing");
+                c.times.push_back((double)times[j]);
+            }
+            for (float v : values) { if (!std::isfinite(v)) fail("glTF: a sampler output is not finite"); c.values.push_back((double)v); }
+            if (c.path == 1) for (size_t j = 0; j < times.size(); ++j) q_normalize(&c.values[j * 4]);
+            out.duration = std::max(out.duration, c.times.back());
+            out.channels.push_back(std::move(c));
+        }
+        g->animations.push_back(std::move(out));
+    }
+    // which skin a loader mesh is met under: the first one stays with the meshes made above (files without skins: nothing changes); the same
+    // glTF mesh under ANOTHER skin becomes a second set of loader meshes, appended behind the file's
+    std::map<std::pair<size_t, size_t>, size_t> skinned_first;   // (glTF mesh, skin) -> first loader mesh
+    const auto attach_skin = [&](size_t mesh, size_t skin, long node) -> size_t {
+        if (skin >= g->skins.size()) fail("glTF: skin index out of range");
+        const auto key = std::make_pair(mesh, skin);
+        const auto it = skinned_first.find(key);
+        if (it != skinned_first.end()) return it->second;
+        size_t first = first_of_mesh[mesh];
+        bool taken = false;
+        for (size_t k = 0; k < count_of_mesh[mesh]; ++k) taken = taken || g->meshes[first + k].skin >= 0;
+        if (taken) {   // the primitives again, for this skin
+            const size_t copy_first = g->meshes.size();
+            for (size_t k = 0; k < count_of_mesh[mesh]; ++k) { Mesh c = g->meshes[first + k]; c.skin = -1; g->meshes.push_back(std::move(c)); }
+            first = copy_first;
+        }
+        for (size_t k = 0; k < count_of_mesh[mesh]; ++k) {
+            Mesh &m = g->meshes[first + k];
+            if (m.skin_data.empty()) continue;   // a primitive without JOINTS_0 stays rigid
+            for (const ArcticSkinVertex &sv : m.skin_data)
+                for (int c = 0; c < 4; ++c) if (sv.joints[c] >= g->skins[skin].joints.size()) fail("glTF: a vertex names a joint the skin does not have");
+            m.skin = (long)skin; m.node = node;
+        }
+        skinned_first[key] = first;
+        return first;
+    };
+
     // objects (app.cpp:354-382): depth-first from the root with an explicit stack (children are visited last to first),
     // every node matrix transposed by assimp_to_mat4 (app.cpp:540-564) and accumulated as parent * child
     const size_t n_nodes = doc.has("nodes") ? doc.at("nodes").size() : 0;
@@ -894,7 +1100,7 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
         stack.pop_back();
         M4 trs;
         std::vector<size_t> children;
-        long mesh = -1;
+        long mesh = -1, skin = -1;
         if (it.node < 0) { trs = mul(it.parent, identity()); children = roots; }
         else {
             if ((size_t)it.node >= n_nodes) fail("glTF: node index out of range");
@@ -904,22 +1110,92 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
             trs = mul(it.parent, transpose(node_matrix(n)));
             if (n.has("children")) for (size_t i = 0; i < n.at("children").size(); ++i) children.push_back(Loader::index_of(n.at("children")[i], "node index"));
             if (n.has("mesh")) mesh = (long)Loader::index_of(n.at("mesh"), "mesh index");
+            if (n.has("skin")) skin = (long)Loader::index_of(n.at("skin"), "skin index");
             if (const Json *ext = n.find("extensions"))
                 if (const Json *khr = ext->find("KHR_lights_punctual")) emit_light(Loader::index_of(khr->at("light"), "light index"), trs);
         }
         for (size_t c : children) stack.push_back({(long)c, trs});
         if (mesh >= 0) {
             if ((size_t)mesh >= n_mesh) fail("glTF: mesh index out of range");
+            const size_t first = skin >= 0 ? attach_skin((size_t)mesh, (size_t)skin, it.node) : first_of_mesh[(size_t)mesh];
             for (size_t k = 0; k < count_of_mesh[(size_t)mesh]; ++k) {
                 ArcticObject o;
                 std::memset(&o, 0, sizeof o);
                 std::memcpy(o.trs, trs.m, sizeof o.trs);
-                o.mesh_idx = first_of_mesh[(size_t)mesh] + k;
+                o.mesh_idx = first + k;
                 g->objects.push_back(o);
             }
         }
     }
     return g;
+}
+
+// channel value at time t (clamped to the sampler's range): STEP holds the earlier keyframe, LINEAR interpolates -- rotations by slerp along
+// the shorter arc, as the specification says (nearly parallel quaternions: a normalised lerp)
+void sample(const Channel &c, double t, double *out) {
+    const int n = c.path == 1 ? 4 : 3;
+    const size_t last = c.times.size() - 1;
+    size_t k = 0;
+    if (t >= c.times[last]) k = last;
+    else if (t > c.times[0]) k = (size_t)(std::upper_bound(c.times.begin(), c.times.end(), t) - c.times.begin()) - 1;
+    const double *a = &c.values[k * (size_t)n];
+    if (k == last || c.step || t <= c.times[k]) { for (int i = 0; i < n; ++i) out[i] = a[i]; return; }
+    const double *b = &c.values[(k + 1) * (size_t)n];
+    const double u = (t - c.times[k]) / (c.times[k + 1] - c.times[k]);
+    if (c.path != 1) { for (int i = 0; i < n; ++i) out[i] = a[i] + (b[i] - a[i]) * u; return; }
+    double d = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3], sign = 1.0;
+    if (d < 0.0) { d = -d; sign = -1.0; }
+    if (d > 1.0 - 1e-12) { for (int i = 0; i < 4; ++i) out[i] = a[i] + (sign * b[i] - a[i]) * u; q_normalize(out); return; }
+    const double th = std::acos(d), sa = std::sin((1.0 - u) * th) / std::sin(th), sb = sign * std::sin(u * th) / std::sin(th);
+    for (int i = 0; i < 4; ++i) out[i] = sa * a[i] + sb * b[i];
+}
+
+// the joint matrices of `skin` under `animation` (-1: the rest pose) at `time`; throws with a message
+void pose(const ArcticGltf &g, uint64_t skin, int64_t animation, double time, float *out) {
+    if (skin >= g.skins.size()) fail("pose: skin index out of range");
+    if (animation < -1 || animation >= (int64_t)g.animations.size()) fail("pose: animation index out of range");
+    if (!std::isfinite(time)) fail("pose: time is not finite");
+    if (!out) fail("pose: null output");
+    const Skin &sk = g.skins[skin];
+    long mesh_node = -1;
+    for (const Mesh &m : g.meshes) if (m.skin == (long)skin) { mesh_node = m.node; break; }
+    std::vector<NodeTransform> nodes = g.nodes;
+    if (animation >= 0) {
+        const Animation &an = g.animations[(size_t)animation];
+        if (!an.unsupported.empty()) fail("pose: " + an.unsupported);
+        for (const Channel &c : an.channels) {
+            NodeTransform &n = nodes[c.node];
+            n.has_matrix = false;   // (an animated node is defined by its translation / rotation / scale)
+            sample(c, time, c.path == 0 ? n.t : c.path == 1 ? n.q : n.s);
+        }
+    }
+    std::vector<D4> global(nodes.size());
+    std::vector<char> done(nodes.size(), 0);
+    const auto global_of = [&](size_t i) -> const D4 & {
+        std::vector<size_t> chain;   // towards the root until a node that is done (load() checked: no cycles)
+        for (long p = (long)i; p >= 0 && !done[(size_t)p]; p = nodes[(size_t)p].parent) chain.push_back((size_t)p);
+        for (size_t k = chain.size(); k-- > 0;) {
+            const size_t n = chain[k];
+            D4 local;
+            if (nodes[n].has_matrix) std::memcpy(local.m, nodes[n].matrix, sizeof local.m);
+            else local = d_trs(nodes[n].t, nodes[n].q, nodes[n].s);
+            global[n] = nodes[n].parent >= 0 ? d_mul(global[(size_t)nodes[n].parent], local) : local;
+            done[n] = 1;
+        }
+        return global[i];
+    };
+    D4 inv_mesh = d_identity();
+    if (mesh_node >= 0 && !d_inverse(global_of((size_t)mesh_node), inv_mesh)) fail("pose: the skinned mesh's node has a singular transform");
+    for (size_t j = 0; j < sk.joints.size(); ++j) {
+        D4 ib;
+        std::memcpy(ib.m, &sk.inverse_bind[j * 16], sizeof ib.m);
+        const D4 m = d_mul(inv_mesh, d_mul(global_of(sk.joints[j]), ib));
+        for (int e = 0; e < 16; ++e) {
+            const float f = (float)m.m[e];   // binary64 throughout, rounded once
+            if (!std::isfinite(f)) fail("pose: a joint matrix is not finite");
+            out[j * 16 + (size_t)e] = f;
+        }
+    }
 }
 
 void say(char *err, uint64_t err_len, const char *m) { if (err && err_len) std::snprintf(err, (size_t)err_len, "%s", m); }
@@ -972,6 +1248,30 @@ const ArcticPointLight *arctic_gltf_point_lights(const ArcticGltf *g, uint64_t *
     return g && !g->point_lights.empty() ? g->point_lights.data() : nullptr;
 }
 uint64_t arctic_gltf_directional_light_count(const ArcticGltf *g) { return g ? g->directional_lights : 0; }
+
+uint64_t arctic_gltf_skin_count(const ArcticGltf *g) { return g ? g->skins.size() : 0; }
+uint64_t arctic_gltf_skin_joint_count(const ArcticGltf *g, uint64_t skin) { return g && skin < g->skins.size() ? g->skins[skin].joints.size() : 0; }
+uint64_t arctic_gltf_animation_count(const ArcticGltf *g) { return g ? g->animations.size() : 0; }
+double arctic_gltf_animation_duration(const ArcticGltf *g, uint64_t animation) { return g && animation < g->animations.size() ? g->animations[animation].duration : -1.0; }
+int arctic_gltf_mesh_skin(const ArcticGltf *g, uint64_t i, const ArcticSkinVertex **skin, uint64_t *n_vertices, int64_t *skin_index, uint32_t *n_joints) {
+    if (!g || i >= g->meshes.size() || !skin || !n_vertices || !skin_index || !n_joints) return ARCTIC_E_INVALID;
+    const Mesh &m = g->meshes[i];
+    if (m.skin < 0) { *skin = nullptr; *n_vertices = 0; *skin_index = -1; *n_joints = 0; return ARCTIC_OK; }
+    *skin = m.skin_data.data(); *n_vertices = m.skin_data.size(); *skin_index = m.skin; *n_joints = (uint32_t)g->skins[(size_t)m.skin].joints.size();
+    return ARCTIC_OK;
+}
+int arctic_gltf_pose(const ArcticGltf *g, uint64_t skin, int64_t animation, double time, float *out) {
+    if (!g) return ARCTIC_E_INVALID;
+    try {
+        pose(*g, skin, animation, time, out);
+        g->pose_error.clear();
+        return ARCTIC_OK;
+    } catch (const std::exception &e) {
+        g->pose_error = e.what();
+        return ARCTIC_E_INVALID;
+    }
+}
+const char *arctic_gltf_last_error(const ArcticGltf *g) { return g ? g->pose_error.c_str() : "null handle"; }
 
 int arctic_gltf_upload(const ArcticGltf *g, ArcticRenderer *r) {
     if (!g || !r) return ARCTIC_E_INVALID;

@@ -31,6 +31,7 @@ struct DirectionalLight { float position[3]; float rotation[2]; float color[3]; 
 using PointLight = ArcticPointLight;       // position, padding0, color, padding1
 using SpotLight = ArcticSpotLight;         // position, range, direction, inner_cone_angle, color, outer_cone_angle (no counterpart in the reference)
 using PointShadowLight = ArcticPointShadowLight;   // position, z_near, color, z_far (no counterpart in the reference)
+using SkinVertex = ArcticSkinVertex;                 // joints[4] (uint16), weights[4]: per-vertex skinning data (no counterpart in the reference)
 using MaterialParams = ArcticMaterialParams;       // glTF's factors: base colour, metallic, roughness, normal scale, occlusion strength, emissive (no counterpart in the reference)
 struct Scene {
     Camera camera;
@@ -112,6 +113,40 @@ class Renderer {
         }
         return true;
     }
+    // skeletal skinning (include/arctic_hip.h; no counterpart in the reference, whose meshes are rigid): a skin -- one SkinVertex per vertex of a
+    // mesh that exists, nullptr detaches it --, then a pose: n_joints matrices of 16 floats in glm memory order, nullptr / 0 = the bind pose.
+    // A pose belongs to the mesh.  false = invalid records / matrices / index (the mesh stays as it was), or a pose without a skin
+    [[nodiscard]] bool set_mesh_skin(MeshIdx mesh, const SkinVertex *skin, uint64_t n_vertices, uint32_t n_joints) {
+        return ok(arctic_set_mesh_skin(m_handle, mesh, skin, n_vertices, n_joints));
+    }
+    [[nodiscard]] bool set_mesh_pose(MeshIdx mesh, const float *joint_matrices, uint32_t n_joints) { return ok(arctic_set_mesh_pose(m_handle, mesh, joint_matrices, n_joints)); }
+    // the vertices the next prepass reads for this mesh, posed or not
+    [[nodiscard]] bool read_mesh_vertices(MeshIdx mesh, Vertex *out, uint64_t n_vertices) { return ok(arctic_read_mesh_vertices(m_handle, mesh, out, n_vertices)); }
+    [[nodiscard]] static bool check_mesh_skin(const SkinVertex *skin, uint64_t n_vertices, uint32_t n_joints) { return arctic_check_mesh_skin(skin, n_vertices, n_joints) == ARCTIC_OK; }
+    [[nodiscard]] static bool skin_vertices(const Vertex *in, const SkinVertex *skin, uint64_t n_vertices, const float *joint_matrices, uint32_t n_joints, Vertex *out) {
+        return arctic_skin_vertices(in, skin, n_vertices, joint_matrices, n_joints, out) == ARCTIC_OK;
+    }
+    // the skins and one pose of a loaded file on top of arctic_gltf_upload: the first call attaches the skin of every skinned loader mesh, every
+    // call sets their poses from animation `animation` (-1: the rest pose) at `time` seconds.  first_mesh = the index arctic_gltf_upload's first
+    // create_mesh returned.  false with the loader's message: e.g. an animation with a CUBICSPLINE sampler (nothing is changed then)
+    [[nodiscard]] bool pose_gltf(const ArcticGltf *g, int64_t animation, double time, MeshIdx first_mesh = 0) {
+        std::vector<std::vector<float>> poses(arctic_gltf_skin_count(g));
+        for (uint64_t k = 0; k < poses.size(); ++k) {
+            poses[k].resize(16 * arctic_gltf_skin_joint_count(g, k));
+            if (arctic_gltf_pose(g, k, animation, time, poses[k].data()) != ARCTIC_OK) { m_error = arctic_gltf_last_error(g); return false; }
+        }
+        const bool attach = !m_gltf_skinned;
+        for (uint64_t i = 0; i < arctic_gltf_mesh_count(g); ++i) {
+            const SkinVertex *skin = nullptr;
+            uint64_t n = 0; int64_t k = -1; uint32_t n_joints = 0;
+            if (arctic_gltf_mesh_skin(g, i, &skin, &n, &k, &n_joints) != ARCTIC_OK) { m_error = "pose_gltf: bad glTF handle"; return false; }
+            if (k < 0) continue;
+            if (attach && !set_mesh_skin(first_mesh + i, skin, n, n_joints)) return false;
+            if (!set_mesh_pose(first_mesh + i, poses[(size_t)k].data(), n_joints)) return false;
+        }
+        m_gltf_skinned = true;
+        return true;
+    }
     [[nodiscard]] static bool check_material_params(const MaterialParams &params) { return arctic_check_material_params(&params) == ARCTIC_OK; }
     [[nodiscard]] bool create_hdri(float *data, uint32_t width, uint32_t height) { return ok(arctic_create_hdri(m_handle, data, width, height)); }
     void update_lights(std::span<PointLight> point_lights) { (void)ok(arctic_update_lights(m_handle, point_lights.data(), point_lights.size())); }
@@ -164,6 +199,7 @@ class Renderer {
     ArcticCreateInfo m_info;
     ArcticRenderer *m_handle = nullptr;
     std::string m_error;
+    bool m_gltf_skinned = false;   // pose_gltf has attached the file's skins
 };
 
 }  // namespace ArcticAMD::Renderer

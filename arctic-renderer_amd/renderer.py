@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -149,6 +149,30 @@ class Renderer:
         v = np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE)
         i = np.ascontiguousarray(indices, dtype=np.uint32).ravel()
         return self._check(self.L.arctic_create_mesh(self.h, _ptr(v), len(v), _ptr(i), len(i), int(material_idx)))
+
+    def set_mesh_skin(self, mesh, skin, n_joints=0):
+        """attach (or replace) the skin of a mesh: one SKIN_VERTEX_DTYPE record per vertex, joint indices below n_joints; None detaches the
+        skin and any pose.  Invalid records raise ArcticError (ARCTIC_E_INVALID) and leave the mesh as it was."""
+        if skin is None:
+            self._check(self.L.arctic_set_mesh_skin(self.h, int(mesh), None, 0, 0))
+            return
+        s = np.ascontiguousarray(skin, dtype=SKIN_VERTEX_DTYPE)
+        self._check(self.L.arctic_set_mesh_skin(self.h, int(mesh), _ptr(s), len(s), int(n_joints)))
+
+    def set_mesh_pose(self, mesh, joint_matrices):
+        """pose a skinned mesh: (n_joints, 16) float32, each matrix in glm memory order ([col][row]; a math matrix M goes in as M.T); None
+        returns the mesh to its bind pose.  Asynchronous on the handle's stream, in order with the frames."""
+        if joint_matrices is None:
+            self._check(self.L.arctic_set_mesh_pose(self.h, int(mesh), None, 0))
+            return
+        j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
+        self._check(self.L.arctic_set_mesh_pose(self.h, int(mesh), _ptr(j), len(j)))
+
+    def read_mesh_vertices(self, mesh, n_vertices):
+        """the vertices the next prepass reads for this mesh, posed or not: n_vertices VERTEX_DTYPE records"""
+        v = np.empty(int(n_vertices), VERTEX_DTYPE)
+        self._check(self.L.arctic_read_mesh_vertices(self.h, int(mesh), _ptr(v), len(v)))
+        return v
 
     def create_hdri(self, rgba32f):
         a = np.ascontiguousarray(rgba32f, dtype=np.float32)
@@ -381,6 +405,27 @@ def check_material_params(params):
     """arctic_check_material_params: True when one MATERIAL_PARAMS_DTYPE record is valid (host only, no handle)"""
     p = np.ascontiguousarray(params, dtype=MATERIAL_PARAMS_DTYPE).reshape(1)
     return binding.lib().arctic_check_material_params(p.ctypes.data) == 0
+
+
+def check_mesh_skin(skin, n_joints):
+    """arctic_check_mesh_skin: True when the SKIN_VERTEX_DTYPE records are valid for n_joints joints (host only, no handle)"""
+    s = np.ascontiguousarray(skin, dtype=SKIN_VERTEX_DTYPE)
+    return binding.lib().arctic_check_mesh_skin(_ptr(s) if len(s) else None, len(s), int(n_joints)) == 0
+
+
+def skin_vertices(vertices, skin, joint_matrices):
+    """arctic_skin_vertices: the skinning arithmetic of include/arctic_hip.h on the host -- the posed VERTEX_DTYPE records.  Invalid input
+    raises ArcticError (ARCTIC_E_INVALID)."""
+    v = np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE)
+    s = np.ascontiguousarray(skin, dtype=SKIN_VERTEX_DTYPE)
+    j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
+    if len(s) != len(v):
+        raise ArcticError(-1, "skin_vertices: one skin record per vertex")
+    out = np.empty_like(v)
+    rc = binding.lib().arctic_skin_vertices(_ptr(v), _ptr(s), len(v), _ptr(j), len(j), _ptr(out))
+    if rc < 0:
+        raise ArcticError(rc, "skin_vertices: invalid skin records or matrices")
+    return out
 
 
 def point_shadow_matrices(light):

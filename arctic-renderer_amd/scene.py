@@ -27,6 +27,9 @@ assert POINT_SHADOW_LIGHT_DTYPE.itemsize == 32
 MATERIAL_PARAMS_DTYPE = np.dtype([("base_color_factor", "<f4", 3), ("metallic_factor", "<f4"), ("roughness_factor", "<f4"), ("normal_scale", "<f4"),
                                   ("occlusion_strength", "<f4"), ("emissive_factor", "<f4", 3), ("reserved", "<f4", 2)])
 assert MATERIAL_PARAMS_DTYPE.itemsize == 48
+# ArcticSkinVertex (include/arctic_hip.h): 24 bytes, the per-vertex joints and weights of Renderer.set_mesh_skin
+SKIN_VERTEX_DTYPE = np.dtype([("joints", "<u2", 4), ("weights", "<f4", 4)])
+assert SKIN_VERTEX_DTYPE.itemsize == 24
 
 
 def neutral_material_params(n=1):

@@ -12,7 +12,7 @@
  *   - node matrices go through assimp_to_mat4 (app.cpp:540-564), which feeds assimp's row-major elements to glm's
  *     column-major constructor, i.e. TRANSPOSES them, and are accumulated as parent * child in that transposed form.
  * Supported: .gltf (JSON) with external or base64 buffers and .glb containers, float / normalised-integer attributes,
- * u8/u16/u32 indices, images by uri or bufferView: PNG (1-16 bit, grey / RGB / palette / alpha, non-interlaced) and
+ * u8/u16/u32 indices, skins and animations (below), images by uri or bufferView: PNG (1-16 bit, grey / RGB / palette / alpha, non-interlaced) and
  * baseline JPEG (8 bit, 1 or 3 components, sampling up to 2x2, restart intervals; float IDCT and replicated chroma, so an
  * LSB or two away from stb_image's integer pipeline).  Not supported: progressive JPEG, sparse accessors, Draco.
  * Nothing here runs on the GPU; parity with assimp's output is unpinned (assimp is not available offline).
@@ -62,6 +62,35 @@ const ArcticObject *arctic_gltf_objects(const ArcticGltf *g);
 const ArcticSpotLight *arctic_gltf_spot_lights(const ArcticGltf *g, uint64_t *n);
 const ArcticPointLight *arctic_gltf_point_lights(const ArcticGltf *g, uint64_t *n);
 uint64_t arctic_gltf_directional_light_count(const ArcticGltf *g);
+
+/* Skins and animations (not read by the reference's load_scene, whose meshes are rigid): JOINTS_0 (u8 / u16) and WEIGHTS_0 (float or
+ * normalised u8 / u16) of a primitive, the file's skins (joints; inverseBindMatrices, identity when absent) and animations (translation /
+ * rotation / scale channels, LINEAR and STEP, rotations by slerp along the shorter arc).  A file without them loads exactly as before: the
+ * same meshes and objects in the same order.  A node's `skin` attaches to the loader meshes of its `mesh`; the same glTF mesh met under a
+ * SECOND skin becomes a second set of loader meshes, appended behind the file's, and its objects name those (met twice under one skin it
+ * stays one set: a pose belongs to the mesh, and it is relative to the first node that carried it).  A primitive without JOINTS_0 stays
+ * rigid under any skin.  Refused files: a joint that is not a node, a vertex that names a joint the skin does not have, JOINTS_0 without
+ * WEIGHTS_0, attribute counts that differ, inverseBindMatrices with fewer matrices than joints or with an element that is not finite, a
+ * weight that is not finite, sampler inputs that are not finite, negative or not strictly increasing, outputs whose count does not match,
+ * a node with two parents (only checked in files that have skins).  A CUBICSPLINE sampler or a `weights` (morph target) channel does NOT
+ * refuse the file: only arctic_gltf_pose with that animation fails.  Keyframe quaternions are normalised when the file is read; one of
+ * length zero is taken as the identity rotation.
+ * arctic_gltf_mesh_skin: the records of loader mesh i as arctic_set_mesh_skin takes them, the skin it belongs to and that skin's joint
+ * count; a rigid mesh returns ARCTIC_OK with *skin = NULL, *skin_index = -1. */
+uint64_t arctic_gltf_skin_count(const ArcticGltf *g);
+uint64_t arctic_gltf_skin_joint_count(const ArcticGltf *g, uint64_t skin);
+uint64_t arctic_gltf_animation_count(const ArcticGltf *g);
+double arctic_gltf_animation_duration(const ArcticGltf *g, uint64_t animation);   /* the latest keyframe of its channels, seconds; -1: no such animation */
+int arctic_gltf_mesh_skin(const ArcticGltf *g, uint64_t i, const ArcticSkinVertex **skin, uint64_t *n_vertices, int64_t *skin_index, uint32_t *n_joints);
+/* The joint matrices of `skin` as arctic_set_mesh_pose takes them (16 floats per joint, glm memory order) into out:
+ *   inverse(global(mesh node)) * global(joint) * inverseBind,   global(n) = global(parent(n)) * local(n)  in glTF's own (untransposed) convention,
+ * evaluated in binary64 and rounded once to fp32.  animation = -1: the rest pose (the nodes as the file has them); otherwise the animation's
+ * channels replace the translation / rotation / scale of the nodes they target at `time` seconds, clamped to each sampler's range.  The mesh
+ * node is the node the skin's first loader mesh was met on (identity when no mesh uses the skin).
+ * ARCTIC_E_INVALID with a message in arctic_gltf_last_error: an index out of range, a time that is not finite, an animation with a
+ * CUBICSPLINE sampler or a morph-target channel, a singular mesh-node transform, a result that is not finite in fp32. */
+int arctic_gltf_pose(const ArcticGltf *g, uint64_t skin, int64_t animation, double time, float *out);
+const char *arctic_gltf_last_error(const ArcticGltf *g);
 
 /* convenience: create_material / create_mesh for everything in the file, in order (what load_scene does). */
 int arctic_gltf_upload(const ArcticGltf *g, ArcticRenderer *r);

@@ -189,6 +189,62 @@ int arctic_create_mesh(ArcticRenderer *r,
                        const uint32_t *indices, uint64_t n_indices,
                        uint64_t material_idx);
 
+/* ---- skeletal skinning (no counterpart in the reference, whose meshes are rigid) --------------------------------------------------------
+ * A mesh may carry a SKIN -- per vertex four joint indices and four weights -- and, with it, a POSE: one matrix per joint.  While a pose is
+ * set, every pass reads a deformed copy of the mesh's vertex buffer, written on the device by one kernel per pose change (skin.hip, k_skin);
+ * the rasterisers, the shadow maps, the cube faces and the shading see an ordinary mesh and are unchanged.
+ *
+ * The arithmetic, defined exactly.  Joint matrices are 16 floats each in glm memory order (m[col * 4 + row]) like ArcticObject::trs.  For a
+ * vertex with joints j0..j3 and weights w0..w3, position (x, y, z) and each of its three vectors v = normal, tangent, bitangent:
+ *   S[e]  = ((w0*J[j0][e] + w1*J[j1][e]) + w2*J[j2][e]) + w3*J[j3][e]          e = 0..15; only rows 0..2 (e % 4 != 3) are used
+ *   pos'  = for i in 0..2: ((S[i]*x + S[4+i]*y) + S[8+i]*z) + S[12+i]*1.0f
+ *   v'    = for i in 0..2:  (S[i]*v.x + S[4+i]*v.y) + S[8+i]*v.z
+ *   uv'   = uv
+ * Every operation is fp32 and rounds once, in the written order, without contraction: numpy in float32 reproduces the result bit for bit
+ * (tests/skin_reference.py), and so does arctic_skin_vertices on the host.  Nothing is normalised here (the vertex kernel normalises the three
+ * vectors as it always has), and the weights are used as given: the library does not renormalise them (weights that do not sum to 1 scale the
+ * vertex).  LIMIT: the vectors go through the upper 3 x 3 of S, not through its inverse transpose.  That is exact for rigid joints and for
+ * uniform scale; under non-uniform scale or shear the normals lean the wrong way.
+ *
+ * A pose belongs to the MESH: every object that uses the mesh shows it.  Two instances in different poses are two meshes.
+ * While a mesh has a pose, the object-space cluster boxes arctic_create_mesh made for ARCTIC_OPT_CLUSTER_CULL do not describe it: the mesh is
+ * then drawn with boxes that are never skipped (it is culled per triangle like any mesh under ARCTIC_OPT_CLUSTER_CULL = 0); the bind pose
+ * gets its real boxes back.  arctic_render_frame's shadow caches (ARCTIC_OPT_SHADOW_CACHE) count every successful skin and pose call of a mesh
+ * the scene uses as a change: the sun's map and the cube faces are redrawn.  Each rank of a sharded frame poses its own copy. */
+typedef struct ArcticSkinVertex {   /* 24 bytes */
+    uint16_t joints[4];   /* every index < n_joints, also in slots whose weight is 0 */
+    float    weights[4];  /* finite; used as given */
+} ArcticSkinVertex;
+
+/* Attaches a skin to an existing mesh, or replaces the one it has (a replaced skin takes its pose with it: the mesh is in its bind pose until the
+ * next arctic_set_mesh_pose).  skin == NULL detaches the skin and any pose.  Synchronous like arctic_create_mesh; replacing or detaching drains
+ * the stream in use first.  ARCTIC_E_INVALID, the mesh left as it was: n_vertices is not the mesh's vertex count, n_joints is 0 or above 65535,
+ * a joint index at or above n_joints, a weight that is not finite, a mesh that does not exist.
+ * A mesh with a skin and no pose renders its own vertices, bit for bit as without the skin. */
+int arctic_set_mesh_skin(ArcticRenderer *r, uint64_t mesh, const ArcticSkinVertex *skin, uint64_t n_vertices, uint32_t n_joints);
+
+/* Poses a skinned mesh: n_joints matrices of 16 floats.  The matrices are copied before the call returns (the caller may free them at once);
+ * the deformation is enqueued on the handle's stream, in order with the passes -- no host synchronisation is needed or made, and a pose set
+ * between two arctic_render_frame calls applies to exactly the frames after it.  NULL, 0 returns the mesh to its bind pose (its original buffer).
+ * ARCTIC_E_STATE: the mesh has no skin.  ARCTIC_E_INVALID, the previous pose kept: n_joints is not the skin's, a matrix element is not finite, a
+ * mesh that does not exist.
+ * Ordering: the kernel runs on the main stream, which every frame's prepass and shadow streams have been joined into, and those streams wait
+ * for it before their next pass; so a frame in flight whose prepass would have run beside the previous frame's shading starts after the pose
+ * instead (what that costs). */
+int arctic_set_mesh_pose(ArcticRenderer *r, uint64_t mesh, const float *joint_matrices, uint32_t n_joints);
+
+/* The vertices the next prepass will read for this mesh, posed or not (tests).  n_vertices must be the mesh's vertex count.  Synchronises. */
+int arctic_read_mesh_vertices(ArcticRenderer *r, uint64_t mesh, ArcticVertex *out, uint64_t n_vertices);
+
+/* The validation arctic_set_mesh_skin applies to the records: ARCTIC_OK or ARCTIC_E_INVALID (NULL and n_vertices = 0 are invalid here).
+ * Host only, no handle. */
+int arctic_check_mesh_skin(const ArcticSkinVertex *skin, uint64_t n_vertices, uint32_t n_joints);
+
+/* The arithmetic above on the host, operation for operation: out[v] = the posed in[v] (out may be in).  ARCTIC_E_INVALID (nothing written):
+ * a null pointer, records arctic_check_mesh_skin refuses, a matrix element that is not finite.  Host only, no handle. */
+int arctic_skin_vertices(const ArcticVertex *in, const ArcticSkinVertex *skin, uint64_t n_vertices,
+                         const float *joint_matrices, uint32_t n_joints, ArcticVertex *out);
+
 /* glTF material factors, emissive and occlusion (no counterpart in the reference, whose material is three images).  Per material twelve
  * floats and two optional images. */
 typedef struct ArcticMaterialParams {   /* 48 bytes */
