@@ -33,6 +33,10 @@ SIGNATURES = {
     "arctic_create_mesh": (_i32, [_vp, _vp, _u64, _vp, _u64, _u64]),
     "arctic_set_mesh_skin": (_i32, [_vp, _u64, _vp, _u64, _u32]),
     "arctic_set_mesh_pose": (_i32, [_vp, _u64, _vp, _u32]),
+    "arctic_set_mesh_morph_targets": (_i32, [_vp, _u64, _vp, _u64, _u32]),
+    "arctic_set_mesh_morph_weights": (_i32, [_vp, _u64, _vp, _u32]),
+    "arctic_check_morph_targets": (_i32, [_vp, _u64, _u32]),
+    "arctic_morph_vertices": (_i32, [_vp, _vp, _u64, _u32, _vp, _vp]),
     "arctic_read_mesh_vertices": (_i32, [_vp, _u64, _vp, _u64]),
     "arctic_check_mesh_skin": (_i32, [_vp, _u64, _u32]),
     "arctic_skin_vertices": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp]),

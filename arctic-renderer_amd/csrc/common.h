@@ -480,6 +480,12 @@ hipError_t launch_antialias(const void *in, void *out, uint32_t width, uint32_t 
 // global memory.  Every joint index of `skin` is below n_joints (arctic_set_mesh_skin checked it); all pointers 16-byte aligned
 constexpr uint32_t SKIN_LDS_JOINTS = 256;
 hipError_t launch_skin(const float *vertices, const void *skin, const float *joints, uint32_t n_vertices, uint32_t n_joints, float *out, hipStream_t s);
+// morph targets (morph.hip, include/arctic_hip.h: arctic_set_mesh_morph_weights): n_vertices vertices of 14 floats + the delta arrays (12 floats per
+// vertex, target-major) of the n_active targets `active` lists -- ascending target index, every weight non-zero and finite, every index below the
+// mesh's target count (the host compacts the list) -> out, 14 floats per vertex.  n_active = 0 copies.  All pointers 16-byte aligned
+struct MorphActive { uint32_t target; float weight; };
+hipError_t launch_morph(const float *vertices, const float *deltas, const MorphActive *active, uint32_t n_active, uint32_t n_vertices, float *out,
+                        hipStream_t s);
 
 // ---- host math (host_math.cpp): glm-equivalent builders, scene.cpp:9-19,41-70 ----------------
 void dir_from_rot(const float rot_deg[2], float out[3]);
@@ -497,5 +503,10 @@ void camera_sky_basis(const float rot_deg[2], float aspect, float fov_y_deg, flo
 bool mesh_skin_valid(const void *skin, uint64_t n, uint32_t n_joints);
 bool floats_finite(const float *p, uint64_t n);
 void skin_vertices_host(const float *in, const void *skin, uint64_t n, const float *joints, float *out);
+// morph targets on the host (include/arctic_hip.h: arctic_check_morph_targets, arctic_morph_vertices).  deltas = n_targets arrays of n records of
+// 12 floats, target-major; morph_targets_valid: n >= 1, 1 <= n_targets <= 65535, every delta finite.  morph_vertices_host: the arithmetic of
+// k_morph, operation for operation -- targets of weight +-0 skipped (in may be out)
+bool morph_targets_valid(const float *deltas, uint64_t n, uint32_t n_targets);
+void morph_vertices_host(const float *in, const float *deltas, uint64_t n, uint32_t n_targets, const float *weights, float *out);
 
 }  // namespace arctic

@@ -200,4 +200,26 @@ void skin_vertices_host(const float *in, const void *skin, uint64_t n, const flo
     }
 }
 
+bool morph_targets_valid(const float *deltas, uint64_t n, uint32_t n_targets) {
+    if (!deltas || n == 0 || n_targets == 0 || n_targets > 65535u) return false;
+    if (n > (UINT64_MAX / 48) / n_targets) return false;   // (the array's byte count fits 64 bits)
+    return floats_finite(deltas, n * n_targets * 12);
+}
+
+// include/arctic_hip.h, arctic_set_mesh_morph_weights: per element m = base, then m = m + w[k] * delta[k][v][e] for the targets of non-zero weight
+// in ascending index -- the product rounds, then the sum; the texture coordinates copied
+void morph_vertices_host(const float *in, const float *deltas, uint64_t n, uint32_t n_targets, const float *weights, float *out) {
+    for (uint64_t v = 0; v < n; ++v) {
+        float m[14];
+        for (int e = 0; e < 14; ++e) m[e] = in[v * 14 + e];
+        for (uint32_t k = 0; k < n_targets; ++k) {
+            const float w = weights[k];
+            if (w == 0.0f) continue;   // (either sign of zero)
+            const float *d = deltas + ((uint64_t)k * n + v) * 12;
+            for (int e = 0; e < 12; ++e) { const float p = w * d[e]; m[e] = m[e] + p; }
+        }
+        for (int e = 0; e < 14; ++e) out[v * 14 + e] = m[e];
+    }
+}
+
 }  // namespace arctic

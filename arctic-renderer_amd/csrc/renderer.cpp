@@ -156,8 +156,34 @@ struct Mesh {
     hipEvent_t ev_joints[POSE_RING] = {nullptr, nullptr, nullptr};
     bool joints_pending[POSE_RING] = {false, false, false};
     int joints_turn = 0;
-    uint64_t shape_seq = 0;   // bumped by every successful skin / pose call: part of the shadow caches' keys (shadow_inputs, cube_inputs)
-    const float *vertices_in_use() const { return posed ? d_posed : d_vertices; }
+    // Morph targets (arctic_set_mesh_morph_targets / arctic_set_mesh_morph_weights).  d_deltas: n_targets arrays of n_vertices records of 12 floats;
+    // while `morphed` (some weight is not zero), d_morphed -- written by k_morph from d_vertices, d_deltas and the compacted {target, weight} list
+    // in d_active -- is what k_skin reads if the mesh is posed and what ObjectRec::vertices points at if it is not.  The list travels through a
+    // ring of pinned buffers like the joint matrices.  morph_weights: the weights in force (all zero after a targets call)
+    float *d_deltas = nullptr, *d_morphed = nullptr;
+    uint32_t n_targets = 0;
+    MorphActive *d_active = nullptr;
+    bool morphed = false;
+    std::vector<float> morph_weights;
+    MorphActive *h_active[POSE_RING] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev_active[POSE_RING] = {nullptr, nullptr, nullptr};
+    bool active_pending[POSE_RING] = {false, false, false};
+    int active_turn = 0;
+    uint64_t shape_seq = 0;   // bumped by every successful skin / pose / morph call: part of the shadow caches' keys (shadow_inputs, cube_inputs)
+    const float *skin_input() const { return morphed ? d_morphed : d_vertices; }                       // morph first, then skin
+    const float *vertices_in_use() const { return posed ? d_posed : skin_input(); }
+    bool deformed() const { return posed || morphed; }                                                 // the cluster boxes do not describe it
+    void release_morph() {    // (the caller has drained the streams that may read these)
+        if (d_deltas) (void)hipFree(d_deltas);
+        if (d_morphed) (void)hipFree(d_morphed);
+        if (d_active) (void)hipFree(d_active);
+        for (int k = 0; k < POSE_RING; ++k) {
+            if (h_active[k]) (void)hipHostFree(h_active[k]);
+            if (ev_active[k]) (void)hipEventDestroy(ev_active[k]);
+            h_active[k] = nullptr; ev_active[k] = nullptr; active_pending[k] = false;
+        }
+        d_deltas = d_morphed = nullptr; d_active = nullptr; n_targets = 0; morphed = false; morph_weights.clear();
+    }
     void release_pose() {     // (the caller has drained the streams that may read these)
         if (d_posed) (void)hipFree(d_posed);
         if (d_joints) (void)hipFree(d_joints);
@@ -470,7 +496,7 @@ int upload_pass_tables(ArcticRenderer *r, PassTables &T, DevBuf &d_xverts, hipSt
         uint32_t oi = (uint32_t)objs.size();
         for (uint32_t b = 0; b < rec.n_vertices; b += 256) { vb_obj.push_back(oi); vb_first.push_back(b); }
         for (uint32_t b = 0; b < rec.n_triangles; b += SETUP_THREADS) { tb_obj.push_back(oi); tb_first.push_back(b); }
-        if (m.posed) {   // the boxes bound the bind pose: a posed mesh gets cluster_bounds' "cannot bound" boxes, which are never skipped
+        if (m.deformed()) {   // the boxes bound the mesh's own shape: a posed or morphed mesh gets cluster_bounds' "cannot bound" boxes, which are never skipped
             const float inf = std::numeric_limits<float>::infinity(), open_box[6] = {-inf, -inf, -inf, inf, inf, inf};
             for (size_t b = 0; b < m.vbounds.size() / 6; ++b) vb_box.insert(vb_box.end(), open_box, open_box + 6);
             for (size_t b = 0; b < m.tbounds.size() / 6; ++b) tb_box.insert(tb_box.end(), open_box, open_box + 6);
@@ -1147,7 +1173,7 @@ void arctic_destroy(ArcticRenderer *r) {
     if (r->ev_shadow_scratch) (void)hipEventDestroy(r->ev_shadow_scratch);
     if (r->ev_skin) (void)hipEventDestroy(r->ev_skin);
     if (r->own_stream) { (void)hipStreamSynchronize(r->own_stream); (void)hipStreamDestroy(r->own_stream); }
-    for (Mesh &m : r->meshes) { m.release_skin(); if (m.d_vertices) (void)hipFree(m.d_vertices); if (m.d_indices) (void)hipFree(m.d_indices); }
+    for (Mesh &m : r->meshes) { m.release_skin(); m.release_morph(); if (m.d_vertices) (void)hipFree(m.d_vertices); if (m.d_indices) (void)hipFree(m.d_indices); }
     for (void *p : r->tex_allocs) (void)hipFree(p);
     for (ArcticRenderer::Extras &x : r->extras) for (void *p : {x.d_emissive, x.d_occlusion, x.d_fast}) if (p) (void)hipFree(p);
     DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_spots, &r->d_cubes, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4, &r->d_lod,
@@ -1448,10 +1474,116 @@ int arctic_set_mesh_pose(ArcticRenderer *r, uint64_t mesh, const float *joint_ma
     HIPCHECK(r, hipMemcpyAsync(m.d_joints, m.h_joints[slot], bytes, hipMemcpyHostToDevice, r->stream));
     HIPCHECK(r, hipEventRecord(m.ev_joints[slot], r->stream));
     m.joints_pending[slot] = true;
-    HIPCHECK(r, launch_skin(m.d_vertices, m.d_skin, m.d_joints, m.n_vertices, n_joints, m.d_posed, r->stream));
+    HIPCHECK(r, launch_skin(m.skin_input(), m.d_skin, m.d_joints, m.n_vertices, n_joints, m.d_posed, r->stream));
     HIPCHECK(r, hipEventRecord(r->ev_skin, r->stream));
     ++r->skin_seq;
     m.posed = true;
+    ++m.shape_seq;
+    return ARCTIC_OK;
+}
+
+int arctic_check_morph_targets(const ArcticMorphDelta *deltas, uint64_t n_vertices, uint32_t n_targets) {
+    return morph_targets_valid(reinterpret_cast<const float *>(deltas), n_vertices, n_targets) ? ARCTIC_OK : ARCTIC_E_INVALID;
+}
+
+int arctic_morph_vertices(const ArcticVertex *in, const ArcticMorphDelta *deltas, uint64_t n_vertices, uint32_t n_targets, const float *weights,
+                          ArcticVertex *out) {
+    if (!in || !out || !weights || !morph_targets_valid(reinterpret_cast<const float *>(deltas), n_vertices, n_targets) || !floats_finite(weights, n_targets))
+        return ARCTIC_E_INVALID;
+    morph_vertices_host(reinterpret_cast<const float *>(in), reinterpret_cast<const float *>(deltas), n_vertices, n_targets, weights, reinterpret_cast<float *>(out));
+    return ARCTIC_OK;
+}
+
+namespace {
+// a posed mesh whose k_skin input has just changed (another blend, or none): the pose again, from the matrices the mesh holds
+int reskin(ArcticRenderer *r, Mesh &m) {
+    if (m.posed) HIPCHECK(r, launch_skin(m.skin_input(), m.d_skin, m.d_joints, m.n_vertices, m.n_joints, m.d_posed, r->stream));
+    return ARCTIC_OK;
+}
+// behind the last deformation kernel of a call: what the shadow and prepass streams wait for (wait_skin)
+int deformed_on_main_stream(ArcticRenderer *r) {
+    HIPCHECK(r, hipEventRecord(r->ev_skin, r->stream));
+    ++r->skin_seq;
+    return ARCTIC_OK;
+}
+}  // namespace
+
+int arctic_set_mesh_morph_targets(ArcticRenderer *r, uint64_t mesh, const ArcticMorphDelta *deltas, uint64_t n_vertices, uint32_t n_targets) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (mesh >= r->meshes.size()) return r->fail(ARCTIC_E_INVALID, "set_mesh_morph_targets: mesh %llu does not exist", (unsigned long long)mesh);
+    Mesh &m = r->meshes[mesh];
+    float *d_new = nullptr;
+    int rc = select_device(r);
+    if (rc) return rc;
+    if (deltas) {
+        if (n_vertices != m.n_vertices) return r->fail(ARCTIC_E_INVALID, "set_mesh_morph_targets: %llu records per target for a mesh of %u vertices", (unsigned long long)n_vertices, m.n_vertices);
+        if (!morph_targets_valid(reinterpret_cast<const float *>(deltas), n_vertices, n_targets))
+            return r->fail(ARCTIC_E_INVALID, "set_mesh_morph_targets: n_targets %u outside 1..65535, or a delta that is not finite", n_targets);
+        const size_t bytes = (size_t)n_targets * n_vertices * sizeof(ArcticMorphDelta);
+        if (hipMalloc((void **)&d_new, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return r->fail(ARCTIC_E_DEVICE, "set_mesh_morph_targets: %u targets x %llu vertices x 48 bytes cannot be allocated", n_targets, (unsigned long long)n_vertices);
+        }
+        if (hipMemcpy(d_new, deltas, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); return r->fail(ARCTIC_E_DEVICE, "set_mesh_morph_targets: upload"); }
+    }
+    // what is replaced may still be read: by a k_morph, a k_skin, or -- the blended buffer -- by a prepass; every prepass stream has been joined
+    // into the main stream
+    const bool was_morphed = m.morphed;
+    if (m.d_deltas && hipStreamSynchronize(r->stream) != hipSuccess) { if (d_new) (void)hipFree(d_new); return r->fail(ARCTIC_E_DEVICE, "set_mesh_morph_targets: hipStreamSynchronize"); }
+    m.release_morph();
+    m.d_deltas = d_new; m.n_targets = deltas ? n_targets : 0;
+    m.morph_weights.assign(m.n_targets, 0.0f);
+    ++m.shape_seq;
+    if (was_morphed && m.posed) {   // the pose stood on the blend that has just gone: once more, on the mesh's own vertices (the stream is drained)
+        if ((rc = reskin(r, m)) != ARCTIC_OK) return rc;
+        return deformed_on_main_stream(r);
+    }
+    return ARCTIC_OK;
+}
+
+int arctic_set_mesh_morph_weights(ArcticRenderer *r, uint64_t mesh, const float *weights, uint32_t n_targets) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (mesh >= r->meshes.size()) return r->fail(ARCTIC_E_INVALID, "set_mesh_morph_weights: mesh %llu does not exist", (unsigned long long)mesh);
+    Mesh &m = r->meshes[mesh];
+    if (!m.d_deltas) return r->fail(ARCTIC_E_STATE, "set_mesh_morph_weights: mesh %llu has no morph targets (arctic_set_mesh_morph_targets)", (unsigned long long)mesh);
+    const bool rest = !weights && n_targets == 0;
+    if (!rest) {
+        if (!weights || n_targets != m.n_targets) return r->fail(ARCTIC_E_INVALID, "set_mesh_morph_weights: %u weights for a mesh of %u targets", n_targets, m.n_targets);
+        if (!floats_finite(weights, n_targets)) return r->fail(ARCTIC_E_INVALID, "set_mesh_morph_weights: a weight is not finite");
+    }
+    int rc = select_device(r);
+    if (rc) return rc;
+    // the targets that take part: non-zero weight (either sign of zero is skipped), ascending index
+    std::vector<MorphActive> active;
+    if (!rest) for (uint32_t k = 0; k < n_targets; ++k) if (weights[k] != 0.0f) active.push_back({k, weights[k]});
+    // Everything below is enqueued on the main stream: behind every prepass enqueued so far (arctic_render_frame joins its prepass streams into
+    // it), so behind every k_vertex and k_skin that reads the buffers k_morph and k_skin overwrite
+    if (active.empty()) {   // the mesh's own vertices again: no blend (the blended buffer is kept for the next call)
+        const bool was_morphed = m.morphed;
+        m.morphed = false;
+        if (was_morphed && m.posed) {
+            if ((rc = reskin(r, m)) != ARCTIC_OK || (rc = deformed_on_main_stream(r)) != ARCTIC_OK) { m.morphed = true; return rc; }
+        }
+    } else {
+        const size_t cap = (size_t)m.n_targets * sizeof(MorphActive), bytes = active.size() * sizeof(MorphActive);
+        if (!m.d_morphed) HIPCHECK(r, hipMalloc((void **)&m.d_morphed, (size_t)m.n_vertices * sizeof(ArcticVertex)));
+        if (!m.d_active) HIPCHECK(r, hipMalloc((void **)&m.d_active, cap));
+        const int slot = m.active_turn;
+        if (!m.h_active[slot]) HIPCHECK(r, hipHostMalloc((void **)&m.h_active[slot], cap));
+        if (!m.ev_active[slot]) HIPCHECK(r, hipEventCreateWithFlags(&m.ev_active[slot], hipEventDisableTiming));
+        if (m.active_pending[slot]) { HIPCHECK(r, hipEventSynchronize(m.ev_active[slot])); m.active_pending[slot] = false; }   // (the copy of POSE_RING calls ago)
+        std::memcpy(m.h_active[slot], active.data(), bytes);
+        m.active_turn = (slot + 1) % Mesh::POSE_RING;
+        HIPCHECK(r, hipMemcpyAsync(m.d_active, m.h_active[slot], bytes, hipMemcpyHostToDevice, r->stream));
+        HIPCHECK(r, hipEventRecord(m.ev_active[slot], r->stream));
+        m.active_pending[slot] = true;
+        HIPCHECK(r, launch_morph(m.d_vertices, m.d_deltas, m.d_active, (uint32_t)active.size(), m.n_vertices, m.d_morphed, r->stream));
+        m.morphed = true;
+        if ((rc = reskin(r, m)) != ARCTIC_OK) return rc;
+        if ((rc = deformed_on_main_stream(r)) != ARCTIC_OK) return rc;
+    }
+    if (rest) m.morph_weights.assign(m.n_targets, 0.0f);
+    else m.morph_weights.assign(weights, weights + n_targets);
     ++m.shape_seq;
     return ARCTIC_OK;
 }

@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from .scene import LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, OBJECT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, neutral_material_params
+from .scene import LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, OBJECT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, neutral_material_params
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "host", "libarctic_gltf.so")
@@ -49,6 +49,8 @@ def lib():
         L.arctic_gltf_mesh_skin.restype = C.c_int
         L.arctic_gltf_mesh_skin.argtypes = [vp, u64, C.POINTER(vp), u64p, C.POINTER(C.c_int64), u32p]
         L.arctic_gltf_pose.restype, L.arctic_gltf_pose.argtypes = C.c_int, [vp, u64, C.c_int64, C.c_double, vp]
+        L.arctic_gltf_mesh_morph.restype, L.arctic_gltf_mesh_morph.argtypes = C.c_int, [vp, u64, C.POINTER(vp), u64p, u32p]
+        L.arctic_gltf_morph_weights.restype, L.arctic_gltf_morph_weights.argtypes = C.c_int, [vp, u64, C.c_int64, C.c_double, vp]
         L.arctic_gltf_last_error.restype, L.arctic_gltf_last_error.argtypes = C.c_char_p, [vp]
         L.arctic_png_decode.restype = vp
         L.arctic_png_decode.argtypes = [C.c_char_p, u64, u32p, u32p, C.c_char_p, u64]
@@ -65,7 +67,9 @@ class GltfScene:
     The glTF material model beyond the three images: material_params (MATERIAL_PARAMS_DTYPE, one record per material), emissive_images and
     occlusion_images (one entry per material: (h, w, 4) uint8 or None).  upload(material_model="gltf") applies them.
     Skins and animations: mesh_skins (one entry per mesh: None, or (SKIN_VERTEX_DTYPE records, skin index, joint count)), skin_joint_counts,
-    animation_durations (seconds, one per animation).  joint_matrices() evaluates a pose, pose() hands it to a renderer."""
+    animation_durations (seconds, one per animation).  joint_matrices() evaluates a pose, pose() hands it to a renderer.
+    Morph targets: mesh_morphs (one entry per mesh: None, or (n_targets, n_vertices) MORPH_DELTA_DTYPE records as
+    Renderer.set_mesh_morph_targets takes them); morph_weights() evaluates a mesh's weights, pose() sets them too."""
 
     def __init__(self, materials, meshes, objects, spot_lights=None, point_lights=None, directional_lights=0, material_params=None,
                  emissive_images=None, occlusion_images=None):
@@ -77,9 +81,10 @@ class GltfScene:
         self.point_lights = np.zeros(0, LIGHT_DTYPE) if point_lights is None else point_lights
         self.directional_lights = directional_lights
         self.mesh_skins = [None] * len(meshes)
+        self.mesh_morphs = [None] * len(meshes)
         self.skin_joint_counts, self.animation_durations = [], []
         self._handle = None       # the loader's handle, kept while the scene has skins to pose
-        self._skinned = {}        # id(renderer) -> first_mesh its skins were attached at
+        self._skinned = {}        # id(renderer) -> first_mesh its skins and morph targets were attached at
 
     def __del__(self):
         if getattr(self, "_handle", None):
@@ -98,17 +103,36 @@ class GltfScene:
             raise ValueError(L.arctic_gltf_last_error(self._handle).decode())
         return out
 
+    def morph_weights(self, mesh, animation=-1, time=0.0):
+        """(n_targets,) float32 for Renderer.set_mesh_morph_weights: the weights of loader mesh `mesh` under animation `animation` (-1: the
+        file's defaults -- node.weights, else mesh.weights, else zeros) at `time` seconds (clamped to the sampler's range); a + (b - a) u in
+        binary64, rounded once (include/arctic_gltf.h: arctic_gltf_morph_weights).  Raises ValueError with the loader's message."""
+        if not self._handle or not 0 <= mesh < len(self.mesh_morphs) or self.mesh_morphs[mesh] is None:
+            raise ValueError(f"morph_weights: mesh {mesh} has no morph targets")
+        out = np.empty(len(self.mesh_morphs[mesh]), np.float32)
+        L = lib()
+        if L.arctic_gltf_morph_weights(self._handle, int(mesh), int(animation), float(time), out.ctypes.data) != 0:
+            raise ValueError(L.arctic_gltf_last_error(self._handle).decode())
+        return out
+
     def pose(self, renderer, animation=-1, time=0.0, first_mesh=0):
-        """pose every skinned mesh of the scene on `renderer` (an object with set_mesh_skin / set_mesh_pose, after upload()): attaches the
-        skins the first time it is called for that renderer, then sets each mesh's pose.  first_mesh: the index upload()'s first create_mesh
+        """pose every skinned mesh and set the weights of every morphed mesh of the scene on `renderer` (an object with set_mesh_skin /
+        set_mesh_pose / set_mesh_morph_targets / set_mesh_morph_weights, after upload()): attaches the skins and the morph targets the first
+        time it is called for that renderer, then sets each mesh's weights and pose.  first_mesh: the index upload()'s first create_mesh
         returned (0 for a renderer that held no meshes)."""
         used = sorted({ms[1] for ms in self.mesh_skins if ms is not None})
         poses = {k: self.joint_matrices(k, animation, time) for k in used}     # (evaluated first: a refused animation changes nothing)
+        weights = {i: self.morph_weights(i, animation, time) for i, mm in enumerate(self.mesh_morphs) if mm is not None}
         if self._skinned.get(id(renderer)) != first_mesh:
             for i, ms in enumerate(self.mesh_skins):
                 if ms is not None:
                     renderer.set_mesh_skin(first_mesh + i, ms[0], ms[2])
+            for i, mm in enumerate(self.mesh_morphs):
+                if mm is not None:
+                    renderer.set_mesh_morph_targets(first_mesh + i, mm)
             self._skinned[id(renderer)] = first_mesh
+        for i, w in weights.items():
+            renderer.set_mesh_morph_weights(first_mesh + i, w)
         for i, ms in enumerate(self.mesh_skins):
             if ms is not None:
                 renderer.set_mesh_pose(first_mesh + i, poses[ms[1]])
@@ -169,9 +193,13 @@ def load(path):
             assert L.arctic_gltf_mesh_skin(h, i, C.byref(ps), C.byref(nv), C.byref(si), C.byref(nj)) == 0
             if si.value >= 0:
                 scene.mesh_skins[i] = (np.frombuffer(C.string_at(ps, nv.value * SKIN_VERTEX_DTYPE.itemsize), dtype=SKIN_VERTEX_DTYPE).copy(), int(si.value), int(nj.value))
+            pd, nt = C.c_void_p(), C.c_uint32()
+            assert L.arctic_gltf_mesh_morph(h, i, C.byref(pd), C.byref(nv), C.byref(nt)) == 0
+            if nt.value:
+                scene.mesh_morphs[i] = np.frombuffer(C.string_at(pd, nt.value * nv.value * MORPH_DELTA_DTYPE.itemsize), dtype=MORPH_DELTA_DTYPE).reshape(nt.value, nv.value).copy()
         scene.skin_joint_counts = [int(L.arctic_gltf_skin_joint_count(h, k)) for k in range(L.arctic_gltf_skin_count(h))]
         scene.animation_durations = [float(L.arctic_gltf_animation_duration(h, k)) for k in range(L.arctic_gltf_animation_count(h))]
-        if scene.skin_joint_counts:      # arctic_gltf_pose needs the loader's handle: the scene owns it from here on
+        if scene.skin_joint_counts or any(mm is not None for mm in scene.mesh_morphs):      # arctic_gltf_pose / arctic_gltf_morph_weights need the loader's handle: the scene owns it from here on
             scene._handle, h = h, None
         return scene
     finally:

@@ -497,11 +497,17 @@ struct Mesh {
     std::vector<ArcticVertex> v; std::vector<uint32_t> idx; uint64_t material = 0;
     std::vector<ArcticSkinVertex> skin_data;
     long skin = -1, node = -1;
+    // morph targets: n_targets arrays of v.size() records, target-major; the node that owns the weights (-1: the mesh is not on a node) and
+    // the weights the file gives it (node.weights, else mesh.weights, else zeros)
+    std::vector<ArcticMorphDelta> morph;
+    uint32_t n_targets = 0;
+    long morph_node = -1;
+    std::vector<float> weights;
 };
 
 // ---- skins and animations: kept in binary64, evaluated by arctic_gltf_pose
 struct Skin { std::vector<size_t> joints; std::vector<double> inverse_bind; };   // 16 per joint, column-major as in the file
-struct Channel { size_t node = 0; int path = 0 /* 0 translation, 1 rotation, 2 scale */; bool step = false; std::vector<double> times, values; };
+struct Channel { size_t node = 0; int path = 0 /* 0 translation, 1 rotation, 2 scale, 3 weights */; int comps = 3 /* values per keyframe */; bool step = false; std::vector<double> times, values; };
 struct Animation { std::vector<Channel> channels; double duration = 0.0; std::string unsupported; /* not empty: posing with it fails with this message */ };
 struct NodeTransform { long parent = -1; bool has_matrix = false; double matrix[16]; double t[3] = {0, 0, 0}, q[4] = {0, 0, 0, 1}, s[3] = {1, 1, 1}; };
 
@@ -599,10 +605,54 @@ struct Loader {
         return buffers[i];
     }
 
-    // accessor -> floats (n_comp per element), converting normalised integers like the glTF spec says
-    std::vector<float> floats(size_t accessor, int n_comp) {
+    // accessor.sparse: `n` elements of `elem` bytes at `values` replace the elements `at` (strictly increasing, each below the accessor's
+    // count).  Everything is checked here: the count against the accessor's, both views against their buffers, the index order
+    struct Sparse { size_t n = 0; std::vector<size_t> at; const uint8_t *values = nullptr; };
+    // an accessor without a bufferView is all zeros (the specification): its count is bounded by nothing in the file, so it is bounded here
+    static constexpr size_t MAX_ZERO_ACCESSOR = (size_t)1 << 26;
+    const uint8_t *view_bytes(const Json &ref, size_t need_count, size_t elem, const char *what) {
+        const Json &bv = doc.at("bufferViews")[index_of(ref.at("bufferView"), "bufferView index")];
+        const std::vector<uint8_t> &buf = buffer(index_of(bv.at("buffer"), "buffer index"));
+        const size_t off_v = bv.has("byteOffset") ? index_of(bv.at("byteOffset"), "byteOffset") : 0, off_a = ref.has("byteOffset") ? index_of(ref.at("byteOffset"), "byteOffset") : 0;
+        check_range(off_v, off_a, buf.size(), what);
+        const size_t off = off_v + off_a;
+        if (need_count > (buf.size() - off) / elem) fail(std::string("glTF: ") + what + " out of bounds");
+        if (bv.has("byteLength")) {   // ... and inside its own view
+            const size_t len = index_of(bv.at("byteLength"), "byteLength");
+            if (off_a > len || need_count > (len - off_a) / elem) fail(std::string("glTF: ") + what + " is longer than its bufferView");
+        }
+        return buf.data() + off;
+    }
+    Sparse sparse_of(const Json &a, size_t count, size_t elem) {
+        Sparse sp;
+        if (!a.has("sparse")) return sp;
+        const Json &s = a.at("sparse");
+        sp.n = index_of(s.at("count"), "sparse count");
+        if (sp.n > count) fail("glTF: sparse count above the accessor's count");
+        if (sp.n == 0) return sp;
+        const Json &si = s.at("indices"), &sv = s.at("values");
+        const int64_t ict = si.at("componentType").as_int();
+        const size_t isize = ict == 5125 ? 4 : ict == 5123 ? 2 : ict == 5121 ? 1 : 0;
+        if (!isize) fail("glTF: sparse indices must be unsigned bytes, shorts or ints");
+        const uint8_t *ip = view_bytes(si, sp.n, isize, "sparse indices");
+        sp.values = view_bytes(sv, sp.n, elem, "sparse values");
+        sp.at.resize(sp.n);
+        for (size_t k = 0; k < sp.n; ++k) {
+            size_t ix;
+            if (isize == 4) { uint32_t u; std::memcpy(&u, ip + k * 4, 4); ix = u; }
+            else if (isize == 2) { uint16_t u; std::memcpy(&u, ip + k * 2, 2); ix = u; }
+            else ix = ip[k];
+            if (ix >= count) fail("glTF: sparse index out of range");
+            if (k && ix <= sp.at[k - 1]) fail("glTF: sparse indices must be strictly increasing");
+            sp.at[k] = ix;
+        }
+        return sp;
+    }
+
+    // accessor -> floats (n_comp per element), converting normalised integers like the glTF spec says.  expect_count: the count the caller
+    // needs (checked before anything is allocated), or SIZE_MAX
+    std::vector<float> floats(size_t accessor, int n_comp, size_t expect_count = SIZE_MAX) {
         const Json &a = doc.at("accessors")[accessor];
-        if (a.has("sparse")) fail("glTF: sparse accessors are not supported");
         static const std::map<std::string, int> comps = {{"SCALAR", 1}, {"VEC2", 2}, {"VEC3", 3}, {"VEC4", 4}, {"MAT4", 16}};
         const auto it = comps.find(a.at("type").as_str());
         if (it == comps.end() || it->second < n_comp) fail("glTF: accessor type mismatch");
@@ -611,30 +661,41 @@ struct Loader {
         const size_t count = index_of(a.at("count"), "accessor count");
         const bool norm = a.has("normalized") && a.at("normalized").b;
         const size_t csize = ct == 5126 || ct == 5125 ? 4 : (ct == 5123 || ct == 5122 ? 2 : 1);
-        const Json &bv = doc.at("bufferViews")[index_of(a.at("bufferView"), "bufferView index")];
-        const std::vector<uint8_t> &buf = buffer(index_of(bv.at("buffer"), "buffer index"));
-        const size_t off_v = bv.has("byteOffset") ? index_of(bv.at("byteOffset"), "byteOffset") : 0, off_a = a.has("byteOffset") ? index_of(a.at("byteOffset"), "byteOffset") : 0;
-        const size_t stride = bv.has("byteStride") ? index_of(bv.at("byteStride"), "byteStride") : csize * file_comp;
         const size_t elem = csize * file_comp;
-        if (stride < elem || stride > 65536) fail("glTF: bad byteStride");
-        check_range(off_v, off_a, buf.size(), "accessor");
-        const size_t off = off_v + off_a;
-        if (count) { if (count - 1 > (buf.size() - off) / stride) fail("glTF: accessor out of bounds"); check_range(off, (count - 1) * stride + elem, buf.size(), "accessor"); }
-        std::vector<float> out(count * (size_t)n_comp);
-        for (size_t i = 0; i < count; ++i)
-            for (int c = 0; c < n_comp; ++c) {
-                const uint8_t *p = &buf[off + (size_t)i * stride + (size_t)c * csize];
-                float v;
-                switch (ct) {
-                case 5126: std::memcpy(&v, p, 4); break;
-                case 5121: v = norm ? *p / 255.0f : (float)*p; break;
-                case 5123: { uint16_t u; std::memcpy(&u, p, 2); v = norm ? u / 65535.0f : (float)u; break; }
-                case 5120: { int8_t s; std::memcpy(&s, p, 1); v = norm ? std::fmax(s / 127.0f, -1.0f) : (float)s; break; }
-                case 5122: { int16_t s; std::memcpy(&s, p, 2); v = norm ? std::fmax(s / 32767.0f, -1.0f) : (float)s; break; }
-                default: fail("glTF: unsupported component type");
-                }
-                out[(size_t)i * n_comp + c] = v;
+        if (expect_count != SIZE_MAX && count != expect_count) fail("glTF: attribute counts differ");
+        if (ct != 5126 && ct != 5121 && ct != 5123 && ct != 5120 && ct != 5122) fail("glTF: unsupported component type");
+        const auto decode = [&](const uint8_t *p) -> float {
+            float v = 0.0f;
+            switch (ct) {
+            case 5126: std::memcpy(&v, p, 4); break;
+            case 5121: v = norm ? *p / 255.0f : (float)*p; break;
+            case 5123: { uint16_t u; std::memcpy(&u, p, 2); v = norm ? u / 65535.0f : (float)u; break; }
+            case 5120: { int8_t s; std::memcpy(&s, p, 1); v = norm ? std::fmax(s / 127.0f, -1.0f) : (float)s; break; }
+            case 5122: { int16_t s; std::memcpy(&s, p, 2); v = norm ? std::fmax(s / 32767.0f, -1.0f) : (float)s; break; }
             }
+            return v;
+        };
+        std::vector<float> out;
+        if (!a.has("bufferView")) {   // no dense base: zeros, which a sparse part may then fill
+            if (!a.has("sparse")) fail("glTF: accessor without a bufferView");
+            if (count > MAX_ZERO_ACCESSOR) fail("glTF: an accessor without a bufferView is too large");
+            out.assign(count * (size_t)n_comp, 0.0f);
+        } else {
+            const Json &bv = doc.at("bufferViews")[index_of(a.at("bufferView"), "bufferView index")];
+            const std::vector<uint8_t> &buf = buffer(index_of(bv.at("buffer"), "buffer index"));
+            const size_t off_v = bv.has("byteOffset") ? index_of(bv.at("byteOffset"), "byteOffset") : 0, off_a = a.has("byteOffset") ? index_of(a.at("byteOffset"), "byteOffset") : 0;
+            const size_t stride = bv.has("byteStride") ? index_of(bv.at("byteStride"), "byteStride") : elem;
+            if (stride < elem || stride > 65536) fail("glTF: bad byteStride");
+            check_range(off_v, off_a, buf.size(), "accessor");
+            const size_t off = off_v + off_a;
+            if (count) { if (count - 1 > (buf.size() - off) / stride) fail("glTF: accessor out of bounds"); check_range(off, (count - 1) * stride + elem, buf.size(), "accessor"); }
+            out.resize(count * (size_t)n_comp);
+            for (size_t i = 0; i < count; ++i)
+                for (int c = 0; c < n_comp; ++c) out[(size_t)i * n_comp + c] = decode(&buf[off + (size_t)i * stride + (size_t)c * csize]);
+        }
+        const Sparse sp = sparse_of(a, count, elem);
+        for (size_t k = 0; k < sp.n; ++k)
+            for (int c = 0; c < n_comp; ++c) out[sp.at[k] * (size_t)n_comp + c] = decode(sp.values + k * elem + (size_t)c * csize);
         return out;
     }
 
@@ -644,19 +705,30 @@ struct Loader {
         const size_t count = index_of(a.at("count"), "accessor count");
         const size_t csize = ct == 5125 ? 4 : ct == 5123 ? 2 : ct == 5121 ? 1 : 0;
         if (!csize || a.at("type").as_str() != "SCALAR") fail("glTF: bad index accessor");
-        const Json &bv = doc.at("bufferViews")[index_of(a.at("bufferView"), "bufferView index")];
-        const std::vector<uint8_t> &buf = buffer(index_of(bv.at("buffer"), "buffer index"));
-        const size_t off_v = bv.has("byteOffset") ? index_of(bv.at("byteOffset"), "byteOffset") : 0, off_a = a.has("byteOffset") ? index_of(a.at("byteOffset"), "byteOffset") : 0;
-        check_range(off_v, off_a, buf.size(), "index accessor");
-        const size_t off = off_v + off_a;
-        if (count > (buf.size() - off) / csize) fail("glTF: index accessor out of bounds");
-        std::vector<uint32_t> out(count);
-        for (size_t i = 0; i < count; ++i) {
-            const uint8_t *p = &buf[off + (size_t)i * csize];
-            if (csize == 4) std::memcpy(&out[(size_t)i], p, 4);
-            else if (csize == 2) { uint16_t u; std::memcpy(&u, p, 2); out[(size_t)i] = u; }
-            else out[(size_t)i] = *p;
+        const auto decode = [&](const uint8_t *p) -> uint32_t {
+            uint32_t v = 0;
+            if (csize == 4) std::memcpy(&v, p, 4);
+            else if (csize == 2) { uint16_t u; std::memcpy(&u, p, 2); v = u; }
+            else v = *p;
+            return v;
+        };
+        std::vector<uint32_t> out;
+        if (!a.has("bufferView")) {
+            if (!a.has("sparse")) fail("glTF: accessor without a bufferView");
+            if (count > MAX_ZERO_ACCESSOR) fail("glTF: an accessor without a bufferView is too large");
+            out.assign(count, 0u);
+        } else {
+            const Json &bv = doc.at("bufferViews")[index_of(a.at("bufferView"), "bufferView index")];
+            const std::vector<uint8_t> &buf = buffer(index_of(bv.at("buffer"), "buffer index"));
+            const size_t off_v = bv.has("byteOffset") ? index_of(bv.at("byteOffset"), "byteOffset") : 0, off_a = a.has("byteOffset") ? index_of(a.at("byteOffset"), "byteOffset") : 0;
+            check_range(off_v, off_a, buf.size(), "index accessor");
+            const size_t off = off_v + off_a;
+            if (count > (buf.size() - off) / csize) fail("glTF: index accessor out of bounds");
+            out.resize(count);
+            for (size_t i = 0; i < count; ++i) out[i] = decode(&buf[off + (size_t)i * csize]);
         }
+        const Sparse sp = sparse_of(a, count, csize);
+        for (size_t k = 0; k < sp.n; ++k) out[sp.at[k]] = decode(sp.values + k * csize);
         return out;
     }
 
@@ -826,11 +898,23 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
     }
 
     // meshes (app.cpp:296-352): one per primitive, in file order; remember where each glTF mesh starts
-    std::vector<size_t> first_of_mesh, count_of_mesh;
+    std::vector<size_t> first_of_mesh, count_of_mesh, targets_of_mesh;
+    std::vector<std::vector<float>> weights_of_mesh;   // mesh.weights, zeros when absent
     const size_t n_mesh = doc.has("meshes") ? doc.at("meshes").size() : 0;
+    const auto weights_array = [&](const Json &w, size_t n_targets, const char *owner) {
+        if (w.kind != Json::Array || w.size() != n_targets) fail(std::string("glTF: ") + owner + ".weights must have one number per morph target");
+        std::vector<float> out(n_targets);
+        for (size_t k = 0; k < n_targets; ++k) {
+            const double x = w[k].as_num();
+            if (!std::isfinite(x) || !std::isfinite((float)x)) fail(std::string("glTF: ") + owner + ".weights is not finite");
+            out[k] = (float)x;
+        }
+        return out;
+    };
     for (size_t i = 0; i < n_mesh; ++i) {
         const Json &prims = doc.at("meshes")[i].at("primitives");
         first_of_mesh.push_back(g->meshes.size());
+        size_t mesh_targets = 0;
         for (size_t k = 0; k < prims.size(); ++k) {
             const Json &p = prims[k];
             if (p.has("mode") && p.at("mode").as_int() != 4) fail("glTF: only triangle lists (mode 4) are supported");
@@ -866,6 +950,60 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
                     for (int c = 0; c < 3; ++c) m.v[v].bitangent[c] = b[c] * tan[v * 4 + 3];
                 }
             } else calc_tangents(m);
+            // morph targets: POSITION / NORMAL / TANGENT displacements, each optional (absent = zero), float VEC3 with the primitive's vertex
+            // count.  The derived parts of a delta are "the value with the target alone at weight 1, minus the base value": with a TANGENT
+            // attribute the bitangent is cross(n + dn, t + dt) * w again; without one, calc_tangents runs on the mesh with the target applied
+            {
+                const Json *tg = p.find("targets");
+                if (tg && tg->kind != Json::Array) fail("glTF: primitive.targets must be an array");
+                const size_t nt = tg ? tg->size() : 0;
+                if (nt > 65535) fail("glTF: more than 65535 morph targets");
+                if (k == 0) mesh_targets = nt;
+                else if (nt != mesh_targets) fail("glTF: the primitives of a mesh have different numbers of morph targets");
+                if (nt && nv > ((size_t)1 << 28) / nt) fail("glTF: morph targets too large (more than 2^28 records)");
+                m.n_targets = (uint32_t)nt;
+                m.morph.resize(nt * nv);
+                std::vector<float> tan_w;   // the handedness of the file's tangents
+                if (nt && at.has("TANGENT")) { const std::vector<float> tan = L.floats((size_t)at.at("TANGENT").as_int(), 4); tan_w.resize(nv); for (size_t v = 0; v < nv; ++v) tan_w[v] = tan[v * 4 + 3]; }
+                for (size_t t = 0; t < nt; ++t) {
+                    const Json &tj = (*tg)[t];
+                    if (tj.kind != Json::Object) fail("glTF: a morph target must be an object");
+                    const auto displacement = [&](const char *name) -> std::vector<float> {
+                        const Json *ref = tj.find(name);
+                        if (!ref) return std::vector<float>(nv * 3, 0.0f);
+                        const size_t acc = Loader::index_of(*ref, "morph target accessor");
+                        const Json &a = doc.at("accessors")[acc];
+                        if (a.at("type").as_str() != "VEC3" || a.at("componentType").as_int() != 5126) fail(std::string("glTF: a morph target's ") + name + " must be float VEC3");
+                        std::vector<float> d = L.floats(acc, 3, nv);
+                        for (float x : d) if (!std::isfinite(x)) fail(std::string("glTF: a morph target's ") + name + " is not finite");
+                        return d;
+                    };
+                    const std::vector<float> dp = displacement("POSITION"), dn = displacement("NORMAL"), dt = displacement("TANGENT");
+                    ArcticMorphDelta *out = &m.morph[t * nv];
+                    Mesh applied;   // without a TANGENT attribute: the mesh with this target alone at weight 1
+                    if (tan_w.empty()) { applied.v = m.v; applied.idx = m.idx; }
+                    for (size_t v = 0; v < nv; ++v) {
+                        ArcticMorphDelta &o = out[v];
+                        std::memcpy(o.position, &dp[v * 3], 12);
+                        std::memcpy(o.normal, &dn[v * 3], 12);
+                        if (!tan_w.empty()) {
+                            std::memcpy(o.tangent, &dt[v * 3], 12);
+                            float n1[3], t1[3], b1[3];
+                            for (int c = 0; c < 3; ++c) { n1[c] = m.v[v].normal[c] + o.normal[c]; t1[c] = m.v[v].tangent[c] + o.tangent[c]; }
+                            cross3(n1, t1, b1);
+                            for (int c = 0; c < 3; ++c) o.bitangent[c] = b1[c] * tan_w[v] - m.v[v].bitangent[c];
+                        } else
+                            for (int c = 0; c < 3; ++c) { applied.v[v].position[c] = m.v[v].position[c] + o.position[c]; applied.v[v].normal[c] = m.v[v].normal[c] + o.normal[c]; }
+                    }
+                    if (tan_w.empty()) {
+                        calc_tangents(applied);
+                        for (size_t v = 0; v < nv; ++v)
+                            for (int c = 0; c < 3; ++c) { out[v].tangent[c] = applied.v[v].tangent[c] - m.v[v].tangent[c]; out[v].bitangent[c] = applied.v[v].bitangent[c] - m.v[v].bitangent[c]; }
+                    }
+                    for (size_t v = 0; v < nv; ++v)
+                        for (int c = 0; c < 3; ++c) if (!std::isfinite(out[v].tangent[c]) || !std::isfinite(out[v].bitangent[c])) fail("glTF: a morph target's derived tangent frame is not finite");
+                }
+            }
             if (at.has("JOINTS_0") != at.has("WEIGHTS_0")) fail("glTF: JOINTS_0 and WEIGHTS_0 come together");
             if (at.has("JOINTS_0")) {   // u8 / u16 indices; float or normalised u8 / u16 weights (the specification's list)
                 const size_t ja = Loader::index_of(at.at("JOINTS_0"), "JOINTS_0 accessor"), wa = Loader::index_of(at.at("WEIGHTS_0"), "WEIGHTS_0 accessor");
@@ -890,6 +1028,9 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
             g->meshes.push_back(std::move(m));
         }
         count_of_mesh.push_back(prims.size());
+        targets_of_mesh.push_back(prims.size() ? mesh_targets : 0);
+        const Json &mj = doc.at("meshes")[i];
+        weights_of_mesh.push_back(mj.has("weights") ? weights_array(mj.at("weights"), targets_of_mesh.back(), "mesh") : std::vector<float>(targets_of_mesh.back(), 0.0f));
     }
 
     // KHR_lights_punctual (no counterpart in the reference, whose load_scene reads no lights): the root's light definitions, checked
@@ -1026,23 +1167,30 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
             Channel c;
             c.node = Loader::index_of(target.at("node"), "node index");
             if (c.node >= n_nodes_all) fail("glTF: an animation targets a node that does not exist");
-            if (path == "weights") { out.unsupported = "animation " + std::to_string(i) + " has a morph-target (weights) channel: not supported"; continue; }
+            size_t channel_targets = 0;   // a weights channel: the target count of the node's mesh
+            if (path == "weights") {
+                const Json &tn = doc.at("nodes")[c.node];
+                if (tn.has("mesh")) { const size_t mi = Loader::index_of(tn.at("mesh"), "mesh index"); if (mi < n_mesh) channel_targets = targets_of_mesh[mi]; }
+                if (!channel_targets) { out.unsupported = "animation " + std::to_string(i) + " has a morph-target (weights) channel on a node whose mesh has no morph targets"; continue; }
+            }
             if (interp == "CUBICSPLINE") { out.unsupported = "animation " + std::to_string(i) + " uses CUBICSPLINE interpolation: not supported"; continue; }
             if (interp != "LINEAR" && interp != "STEP") fail("glTF: unknown animation interpolation '" + interp + "'");
-            c.path = path == "translation" ? 0 : path == "rotation" ? 1 : path == "scale" ? 2 : -1;
+            c.path = path == "translation" ? 0 : path == "rotation" ? 1 : path == "scale" ? 2 : path == "weights" ? 3 : -1;
             if (c.path < 0) fail("glTF: unknown animation path '" + path + "'");
             c.step = interp == "STEP";
             const size_t in_acc = Loader::index_of(sm.at("input"), "sampler input"), out_acc = Loader::index_of(sm.at("output"), "sampler output");
             if (doc.at("accessors")[in_acc].at("componentType").as_int() != 5126) fail("glTF: sampler input must be float");
             const std::vector<float> times = L.floats(in_acc, 1);
-            const int comps = c.path == 1 ? 4 : 3;
+            const int comps = c.path == 1 ? 4 : c.path == 3 ? (int)channel_targets : 3;
+            c.comps = comps;
             const Json &oa = doc.at("accessors")[out_acc];
             const int64_t oct = oa.at("componentType").as_int();
             if (oct != 5126 && !(oa.has("normalized") && oa.at("normalized").b)) fail("glTF: sampler output must be float or normalised integers");
-            if (oa.at("type").as_str() != (comps == 4 ? "VEC4" : "VEC3")) fail("glTF: sampler output has the wrong type for its path");
-            const std::vector<float> values = L.floats(out_acc, comps);
+            if (oa.at("type").as_str() != (c.path == 3 ? "SCALAR" : comps == 4 ? "VEC4" : "VEC3")) fail("glTF: sampler output has the wrong type for its path");
             if (times.empty()) fail("glTF: an animation sampler has no keyframes");
-            if (values.size() / (size_t)comps != times.size()) fail("glTF: sampler output count does not match its input count");
+            // (weights: keyframes x targets scalars, keyframe-major)
+            const std::vector<float> values = L.floats(out_acc, c.path == 3 ? 1 : comps);
+            if (values.size() / (size_t)comps != times.size() || values.size() % (size_t)comps) fail("glTF: sampler output count does not match its input count");
             for (size_t j = 0; j < times.size(); ++j) {
                 if (!std::isfinite(times[j]) || times[j] < 0.0f || (j && !(times[j] > times[j - 1]))) fail("glTF: sampler input must be finite, >= 0 and strictly increasing");
                 c.times.push_back((double)times[j]);
@@ -1078,6 +1226,30 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
             m.skin = (long)skin; m.node = node;
         }
         skinned_first[key] = first;
+        return first;
+    };
+
+    // Morph weights belong to the NODE, a deformation to the mesh here: a glTF mesh with targets gets one set of loader meshes per node it is
+    // met on -- the first node keeps the set made above, every further one a copy appended behind the file's (the mechanism of a second skin)
+    const auto place_morphed = [&](size_t mesh, long skin, long node, const Json &nj) -> size_t {
+        if (skin >= 0 && (size_t)skin >= g->skins.size()) fail("glTF: skin index out of range");
+        size_t first = first_of_mesh[mesh];
+        bool taken = false;
+        for (size_t k = 0; k < count_of_mesh[mesh]; ++k) taken = taken || g->meshes[first + k].morph_node >= 0;
+        if (taken) {
+            const size_t copy_first = g->meshes.size();
+            for (size_t k = 0; k < count_of_mesh[mesh]; ++k) { Mesh c = g->meshes[first + k]; c.skin = -1; c.node = -1; g->meshes.push_back(std::move(c)); }
+            first = copy_first;
+        }
+        const std::vector<float> w = nj.has("weights") ? weights_array(nj.at("weights"), targets_of_mesh[mesh], "node") : weights_of_mesh[mesh];
+        for (size_t k = 0; k < count_of_mesh[mesh]; ++k) {
+            Mesh &m = g->meshes[first + k];
+            m.morph_node = node; m.weights = w;
+            if (skin < 0 || m.skin_data.empty()) continue;
+            for (const ArcticSkinVertex &sv : m.skin_data)
+                for (int c = 0; c < 4; ++c) if (sv.joints[c] >= g->skins[(size_t)skin].joints.size()) fail("glTF: a vertex names a joint the skin does not have");
+            m.skin = skin; m.node = node;
+        }
         return first;
     };
 
@@ -1117,7 +1289,10 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
         for (size_t c : children) stack.push_back({(long)c, trs});
         if (mesh >= 0) {
             if ((size_t)mesh >= n_mesh) fail("glTF: mesh index out of range");
-            const size_t first = skin >= 0 ? attach_skin((size_t)mesh, (size_t)skin, it.node) : first_of_mesh[(size_t)mesh];
+            const Json &nj = doc.at("nodes")[(size_t)it.node];
+            if (!targets_of_mesh[(size_t)mesh] && nj.has("weights") && nj.at("weights").size()) fail("glTF: node.weights on a mesh without morph targets");
+            const size_t first = targets_of_mesh[(size_t)mesh] ? place_morphed((size_t)mesh, skin, it.node, nj)
+                               : skin >= 0 ? attach_skin((size_t)mesh, (size_t)skin, it.node) : first_of_mesh[(size_t)mesh];
             for (size_t k = 0; k < count_of_mesh[(size_t)mesh]; ++k) {
                 ArcticObject o;
                 std::memset(&o, 0, sizeof o);
@@ -1127,13 +1302,15 @@ std::unique_ptr<ArcticGltf> load(const std::string &path) {
             }
         }
     }
+    for (size_t i = 0; i < n_mesh; ++i)   // a mesh with targets that no node carries: the mesh's own weights
+        for (size_t k = 0; k < count_of_mesh[i]; ++k) { Mesh &m = g->meshes[first_of_mesh[i] + k]; if (m.n_targets && m.weights.empty()) m.weights = weights_of_mesh[i]; }
     return g;
 }
 
 // channel value at time t (clamped to the sampler's range): STEP holds the earlier keyframe, LINEAR interpolates -- rotations by slerp along
 // the shorter arc, as the specification says (nearly parallel quaternions: a normalised lerp)
 void sample(const Channel &c, double t, double *out) {
-    const int n = c.path == 1 ? 4 : 3;
+    const int n = c.comps;
     const size_t last = c.times.size() - 1;
     size_t k = 0;
     if (t >= c.times[last]) k = last;
@@ -1164,6 +1341,7 @@ void pose(const ArcticGltf &g, uint64_t skin, int64_t animation, double time, fl
         const Animation &an = g.animations[(size_t)animation];
         if (!an.unsupported.empty()) fail("pose: " + an.unsupported);
         for (const Channel &c : an.channels) {
+            if (c.path == 3) continue;   // (morph weights: morph_weights below)
             NodeTransform &n = nodes[c.node];
             n.has_matrix = false;   // (an animated node is defined by its translation / rotation / scale)
             sample(c, time, c.path == 0 ? n.t : c.path == 1 ? n.q : n.s);
@@ -1195,6 +1373,29 @@ void pose(const ArcticGltf &g, uint64_t skin, int64_t animation, double time, fl
             if (!std::isfinite(f)) fail("pose: a joint matrix is not finite");
             out[j * 16 + (size_t)e] = f;
         }
+    }
+}
+
+// the weights of loader mesh i under `animation` (-1: the file's defaults -- node.weights, else mesh.weights, else zeros) at `time`: a weights
+// channel on the mesh's node replaces them all, a + (b - a) u in binary64 (STEP: a), rounded once; throws with a message
+void morph_weights(const ArcticGltf &g, uint64_t i, int64_t animation, double time, float *out) {
+    if (i >= g.meshes.size()) fail("morph_weights: mesh index out of range");
+    if (animation < -1 || animation >= (int64_t)g.animations.size()) fail("morph_weights: animation index out of range");
+    if (!std::isfinite(time)) fail("morph_weights: time is not finite");
+    const Mesh &m = g.meshes[i];
+    if (!m.n_targets) return;
+    if (!out) fail("morph_weights: null output");
+    std::vector<double> w(m.weights.begin(), m.weights.end());
+    if (animation >= 0) {
+        const Animation &an = g.animations[(size_t)animation];
+        if (!an.unsupported.empty()) fail("morph_weights: " + an.unsupported);
+        for (const Channel &c : an.channels)
+            if (c.path == 3 && m.morph_node >= 0 && c.node == (size_t)m.morph_node && (size_t)c.comps == w.size()) sample(c, time, w.data());
+    }
+    for (size_t k = 0; k < w.size(); ++k) {
+        const float f = (float)w[k];
+        if (!std::isfinite(f)) fail("morph_weights: a weight is not finite");
+        out[k] = f;
     }
 }
 
@@ -1264,6 +1465,24 @@ int arctic_gltf_pose(const ArcticGltf *g, uint64_t skin, int64_t animation, doub
     if (!g) return ARCTIC_E_INVALID;
     try {
         pose(*g, skin, animation, time, out);
+        g->pose_error.clear();
+        return ARCTIC_OK;
+    } catch (const std::exception &e) {
+        g->pose_error = e.what();
+        return ARCTIC_E_INVALID;
+    }
+}
+int arctic_gltf_mesh_morph(const ArcticGltf *g, uint64_t i, const ArcticMorphDelta **deltas, uint64_t *n_vertices, uint32_t *n_targets) {
+    if (!g || i >= g->meshes.size() || !deltas || !n_vertices || !n_targets) return ARCTIC_E_INVALID;
+    const Mesh &m = g->meshes[i];
+    if (!m.n_targets || m.morph.empty()) { *deltas = nullptr; *n_vertices = 0; *n_targets = 0; return ARCTIC_OK; }
+    *deltas = m.morph.data(); *n_vertices = m.v.size(); *n_targets = m.n_targets;
+    return ARCTIC_OK;
+}
+int arctic_gltf_morph_weights(const ArcticGltf *g, uint64_t i, int64_t animation, double time, float *out) {
+    if (!g) return ARCTIC_E_INVALID;
+    try {
+        morph_weights(*g, i, animation, time, out);
         g->pose_error.clear();
         return ARCTIC_OK;
     } catch (const std::exception &e) {

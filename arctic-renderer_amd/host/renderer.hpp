@@ -32,6 +32,7 @@ using PointLight = ArcticPointLight;       // position, padding0, color, padding
 using SpotLight = ArcticSpotLight;         // position, range, direction, inner_cone_angle, color, outer_cone_angle (no counterpart in the reference)
 using PointShadowLight = ArcticPointShadowLight;   // position, z_near, color, z_far (no counterpart in the reference)
 using SkinVertex = ArcticSkinVertex;                 // joints[4] (uint16), weights[4]: per-vertex skinning data (no counterpart in the reference)
+using MorphDelta = ArcticMorphDelta;                 // position, normal, tangent, bitangent deltas: one per vertex per morph target (no counterpart in the reference)
 using MaterialParams = ArcticMaterialParams;       // glTF's factors: base colour, metallic, roughness, normal scale, occlusion strength, emissive (no counterpart in the reference)
 struct Scene {
     Camera camera;
@@ -126,16 +127,44 @@ class Renderer {
     [[nodiscard]] static bool skin_vertices(const Vertex *in, const SkinVertex *skin, uint64_t n_vertices, const float *joint_matrices, uint32_t n_joints, Vertex *out) {
         return arctic_skin_vertices(in, skin, n_vertices, joint_matrices, n_joints, out) == ARCTIC_OK;
     }
+    // morph targets (include/arctic_hip.h): n_targets arrays of n_vertices MorphDelta, target-major, on a mesh that exists (nullptr detaches them;
+    // all weights are zero afterwards), then one weight per target, used as given; nullptr / 0 = the mesh's own vertices.  Weights belong to the
+    // mesh; morph first, then skin.  false = invalid records / weights / index (the mesh stays as it was), or weights without targets
+    [[nodiscard]] bool set_mesh_morph_targets(MeshIdx mesh, const MorphDelta *deltas, uint64_t n_vertices, uint32_t n_targets) {
+        return ok(arctic_set_mesh_morph_targets(m_handle, mesh, deltas, n_vertices, n_targets));
+    }
+    [[nodiscard]] bool set_mesh_morph_weights(MeshIdx mesh, const float *weights, uint32_t n_targets) { return ok(arctic_set_mesh_morph_weights(m_handle, mesh, weights, n_targets)); }
+    [[nodiscard]] static bool check_morph_targets(const MorphDelta *deltas, uint64_t n_vertices, uint32_t n_targets) { return arctic_check_morph_targets(deltas, n_vertices, n_targets) == ARCTIC_OK; }
+    [[nodiscard]] static bool morph_vertices(const Vertex *in, const MorphDelta *deltas, uint64_t n_vertices, uint32_t n_targets, const float *weights, Vertex *out) {
+        return arctic_morph_vertices(in, deltas, n_vertices, n_targets, weights, out) == ARCTIC_OK;
+    }
     // the skins and one pose of a loaded file on top of arctic_gltf_upload: the first call attaches the skin of every skinned loader mesh, every
     // call sets their poses from animation `animation` (-1: the rest pose) at `time` seconds.  first_mesh = the index arctic_gltf_upload's first
     // create_mesh returned.  false with the loader's message: e.g. an animation with a CUBICSPLINE sampler (nothing is changed then)
+    // Morph targets likewise, in front of the skins (morph first, then skin): attached by the first call, their weights set by every call
     [[nodiscard]] bool pose_gltf(const ArcticGltf *g, int64_t animation, double time, MeshIdx first_mesh = 0) {
         std::vector<std::vector<float>> poses(arctic_gltf_skin_count(g));
         for (uint64_t k = 0; k < poses.size(); ++k) {
             poses[k].resize(16 * arctic_gltf_skin_joint_count(g, k));
             if (arctic_gltf_pose(g, k, animation, time, poses[k].data()) != ARCTIC_OK) { m_error = arctic_gltf_last_error(g); return false; }
         }
+        std::vector<std::vector<float>> weights(arctic_gltf_mesh_count(g));   // (evaluated first as well: a refused animation changes nothing)
+        for (uint64_t i = 0; i < weights.size(); ++i) {
+            const MorphDelta *deltas = nullptr;
+            uint64_t n = 0; uint32_t n_targets = 0;
+            if (arctic_gltf_mesh_morph(g, i, &deltas, &n, &n_targets) != ARCTIC_OK) { m_error = "pose_gltf: bad glTF handle"; return false; }
+            weights[i].resize(n_targets);
+            if (n_targets && arctic_gltf_morph_weights(g, i, animation, time, weights[i].data()) != ARCTIC_OK) { m_error = arctic_gltf_last_error(g); return false; }
+        }
         const bool attach = !m_gltf_skinned;
+        for (uint64_t i = 0; i < weights.size(); ++i) {   // morph first, then skin
+            if (weights[i].empty()) continue;
+            const MorphDelta *deltas = nullptr;
+            uint64_t n = 0; uint32_t n_targets = 0;
+            (void)arctic_gltf_mesh_morph(g, i, &deltas, &n, &n_targets);
+            if (attach && !set_mesh_morph_targets(first_mesh + i, deltas, n, n_targets)) return false;
+            if (!set_mesh_morph_weights(first_mesh + i, weights[i].data(), n_targets)) return false;
+        }
         for (uint64_t i = 0; i < arctic_gltf_mesh_count(g); ++i) {
             const SkinVertex *skin = nullptr;
             uint64_t n = 0; int64_t k = -1; uint32_t n_joints = 0;

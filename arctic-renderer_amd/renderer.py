@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -168,8 +168,28 @@ class Renderer:
         j = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1, 16)
         self._check(self.L.arctic_set_mesh_pose(self.h, int(mesh), _ptr(j), len(j)))
 
+    def set_mesh_morph_targets(self, mesh, deltas):
+        """attach (or replace) the morph targets of a mesh: (n_targets, n_vertices) MORPH_DELTA_DTYPE records; None detaches them.  All
+        weights are zero afterwards.  Invalid records raise ArcticError (ARCTIC_E_INVALID) and leave the mesh as it was."""
+        if deltas is None:
+            self._check(self.L.arctic_set_mesh_morph_targets(self.h, int(mesh), None, 0, 0))
+            return
+        d = np.ascontiguousarray(deltas, dtype=MORPH_DELTA_DTYPE)
+        if d.ndim != 2 or d.size == 0:                 # (an empty array is not None: it must not detach)
+            raise ArcticError(-1, "set_mesh_morph_targets: deltas must be (n_targets, n_vertices) records, at least one of each")
+        self._check(self.L.arctic_set_mesh_morph_targets(self.h, int(mesh), _ptr(d), d.shape[1], d.shape[0]))
+
+    def set_mesh_morph_weights(self, mesh, weights):
+        """set the weights of a mesh with morph targets: n_targets float32, used as given; None (or all zeros) returns the mesh to its own
+        vertices.  Asynchronous on the handle's stream, in order with the frames."""
+        if weights is None:
+            self._check(self.L.arctic_set_mesh_morph_weights(self.h, int(mesh), None, 0))
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+        self._check(self.L.arctic_set_mesh_morph_weights(self.h, int(mesh), _ptr(w), len(w)))
+
     def read_mesh_vertices(self, mesh, n_vertices):
-        """the vertices the next prepass reads for this mesh, posed or not: n_vertices VERTEX_DTYPE records"""
+        """the vertices the next prepass reads for this mesh -- posed, else morphed, else its own: n_vertices VERTEX_DTYPE records"""
         v = np.empty(int(n_vertices), VERTEX_DTYPE)
         self._check(self.L.arctic_read_mesh_vertices(self.h, int(mesh), _ptr(v), len(v)))
         return v
@@ -425,6 +445,29 @@ def skin_vertices(vertices, skin, joint_matrices):
     rc = binding.lib().arctic_skin_vertices(_ptr(v), _ptr(s), len(v), _ptr(j), len(j), _ptr(out))
     if rc < 0:
         raise ArcticError(rc, "skin_vertices: invalid skin records or matrices")
+    return out
+
+
+def check_morph_targets(deltas):
+    """arctic_check_morph_targets: True when the (n_targets, n_vertices) MORPH_DELTA_DTYPE records are valid (host only, no handle)"""
+    d = np.ascontiguousarray(deltas, dtype=MORPH_DELTA_DTYPE)
+    if d.ndim != 2:
+        return False
+    return binding.lib().arctic_check_morph_targets(_ptr(d) if d.size else None, d.shape[1], d.shape[0]) == 0
+
+
+def morph_vertices(vertices, deltas, weights):
+    """arctic_morph_vertices: the morph-target arithmetic of include/arctic_hip.h on the host -- the blended VERTEX_DTYPE records for
+    (n_targets, n_vertices) MORPH_DELTA_DTYPE deltas and n_targets weights.  Invalid input raises ArcticError (ARCTIC_E_INVALID)."""
+    v = np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE)
+    d = np.ascontiguousarray(deltas, dtype=MORPH_DELTA_DTYPE)
+    w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+    if d.ndim != 2 or d.shape[1] != len(v) or d.shape[0] != len(w):
+        raise ArcticError(-1, "morph_vertices: deltas must be (n_targets, n_vertices) records, one weight per target")
+    out = np.empty_like(v)
+    rc = binding.lib().arctic_morph_vertices(_ptr(v), _ptr(d), len(v), len(w), _ptr(w), _ptr(out))
+    if rc < 0:
+        raise ArcticError(rc, "morph_vertices: invalid deltas or weights")
     return out
 
 

@@ -30,6 +30,9 @@ assert MATERIAL_PARAMS_DTYPE.itemsize == 48
 # ArcticSkinVertex (include/arctic_hip.h): 24 bytes, the per-vertex joints and weights of Renderer.set_mesh_skin
 SKIN_VERTEX_DTYPE = np.dtype([("joints", "<u2", 4), ("weights", "<f4", 4)])
 assert SKIN_VERTEX_DTYPE.itemsize == 24
+# ArcticMorphDelta (include/arctic_hip.h): 48 bytes, one per vertex per morph target of Renderer.set_mesh_morph_targets
+MORPH_DELTA_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("bitangent", "<f4", 3)])
+assert MORPH_DELTA_DTYPE.itemsize == 48
 
 
 def neutral_material_params(n=1):

@@ -14,7 +14,8 @@
  * Supported: .gltf (JSON) with external or base64 buffers and .glb containers, float / normalised-integer attributes,
  * u8/u16/u32 indices, skins and animations (below), images by uri or bufferView: PNG (1-16 bit, grey / RGB / palette / alpha, non-interlaced) and
  * baseline JPEG (8 bit, 1 or 3 components, sampling up to 2x2, restart intervals; float IDCT and replicated chroma, so an
- * LSB or two away from stb_image's integer pipeline).  Not supported: progressive JPEG, sparse accessors, Draco.
+ * LSB or two away from stb_image's integer pipeline).  Sparse accessors are read everywhere an
+ * accessor is (below).  Not supported: progressive JPEG, Draco.
  * Nothing here runs on the GPU; parity with assimp's output is unpinned (assimp is not available offline).
  */
 #ifndef ARCTIC_GLTF_H
@@ -72,8 +73,8 @@ uint64_t arctic_gltf_directional_light_count(const ArcticGltf *g);
  * rigid under any skin.  Refused files: a joint that is not a node, a vertex that names a joint the skin does not have, JOINTS_0 without
  * WEIGHTS_0, attribute counts that differ, inverseBindMatrices with fewer matrices than joints or with an element that is not finite, a
  * weight that is not finite, sampler inputs that are not finite, negative or not strictly increasing, outputs whose count does not match,
- * a node with two parents (only checked in files that have skins).  A CUBICSPLINE sampler or a `weights` (morph target) channel does NOT
- * refuse the file: only arctic_gltf_pose with that animation fails.  Keyframe quaternions are normalised when the file is read; one of
+ * a node with two parents (only checked in files that have skins).  A CUBICSPLINE sampler, or a `weights` channel on a node whose mesh
+ * has no morph targets, does NOT refuse the file: only arctic_gltf_pose / arctic_gltf_morph_weights with that animation fail.  Keyframe quaternions are normalised when the file is read; one of
  * length zero is taken as the identity rotation.
  * arctic_gltf_mesh_skin: the records of loader mesh i as arctic_set_mesh_skin takes them, the skin it belongs to and that skin's joint
  * count; a rigid mesh returns ARCTIC_OK with *skin = NULL, *skin_index = -1. */
@@ -88,9 +89,35 @@ int arctic_gltf_mesh_skin(const ArcticGltf *g, uint64_t i, const ArcticSkinVerte
  * channels replace the translation / rotation / scale of the nodes they target at `time` seconds, clamped to each sampler's range.  The mesh
  * node is the node the skin's first loader mesh was met on (identity when no mesh uses the skin).
  * ARCTIC_E_INVALID with a message in arctic_gltf_last_error: an index out of range, a time that is not finite, an animation with a
- * CUBICSPLINE sampler or a morph-target channel, a singular mesh-node transform, a result that is not finite in fp32. */
+ * CUBICSPLINE sampler or a weights channel without morph targets, a singular mesh-node transform, a result that is not finite in fp32. */
 int arctic_gltf_pose(const ArcticGltf *g, uint64_t skin, int64_t animation, double time, float *out);
 const char *arctic_gltf_last_error(const ArcticGltf *g);
+
+/* Sparse accessors: accessor.sparse = {count, indices {bufferView, byteOffset, componentType u8 / u16 / u32}, values {bufferView, byteOffset}}
+ * replaces `count` elements of the dense base -- the accessor's bufferView, or zeros when it has none (such an accessor may hold at most 2^26
+ * elements).  Refused: a sparse count above the accessor's, an index at or above the accessor's count, indices that do not increase strictly,
+ * a view too short for its count.
+ *
+ * Morph targets (not read by the reference's load_scene): primitives[].targets with POSITION, NORMAL and TANGENT displacements, each optional
+ * (absent = zero) and each float VEC3 with the primitive's vertex count; every primitive of a mesh has the same number of targets (at most
+ * 65535).  arctic_gltf_mesh_morph gives the records of loader mesh i as arctic_set_mesh_morph_targets takes them (target-major); a mesh
+ * without targets returns ARCTIC_OK with *deltas = NULL, *n_vertices = *n_targets = 0.  The derived parts of a delta follow one rule -- THE
+ * VALUE WITH TARGET k ALONE AT WEIGHT 1, MINUS THE BASE VALUE:
+ *   - primitive with a TANGENT attribute: tangent delta = the file's; bitangent delta = cross(n + dn, t + dt) * w - b, in the loader's fp32 order;
+ *   - primitive without one: the tangents are computed again (aiProcess_CalcTangentSpace as above) on the mesh with target k applied; tangent
+ *     and bitangent deltas are the differences to the base mesh's (a TANGENT displacement in the target is checked and not used).
+ * LIMITS: a target without NORMAL keeps the base normal (normals are not re-derived); the bitangent is blended linearly (arctic_hip.h).
+ * Weights: node.weights overrides mesh.weights, the default is zeros; a length that is not the target count refuses the file.  Weights belong
+ * to the node and a deformation to the loader mesh, so a glTF mesh with targets gets one set of loader meshes per node it is met on: the first
+ * node keeps the file's, every further node a copy appended behind them (as under a second skin).
+ * `weights` animation channels: LINEAR and STEP, output SCALAR (float or normalised integers) with keyframes x targets values.
+ * arctic_gltf_morph_weights: the n_targets weights of loader mesh i into out -- animation = -1: the file's defaults; otherwise a weights channel
+ * on the mesh's node replaces them, a + (b - a) * u with u = (t - t0) / (t1 - t0) in binary64 (STEP: a), time clamped to the sampler's range,
+ * rounded once to fp32.  A mesh without targets: ARCTIC_OK, nothing written.  ARCTIC_E_INVALID with a message in arctic_gltf_last_error: an
+ * index out of range, a time that is not finite, an animation arctic_gltf_pose refuses too.  An animation with joint channels and weights
+ * channels poses both: arctic_gltf_pose reads the former, this call the latter.  arctic_gltf_upload stays load_scene: it attaches nothing. */
+int arctic_gltf_mesh_morph(const ArcticGltf *g, uint64_t i, const ArcticMorphDelta **deltas, uint64_t *n_vertices, uint32_t *n_targets);
+int arctic_gltf_morph_weights(const ArcticGltf *g, uint64_t i, int64_t animation, double time, float *out);
 
 /* convenience: create_material / create_mesh for everything in the file, in order (what load_scene does). */
 int arctic_gltf_upload(const ArcticGltf *g, ArcticRenderer *r);

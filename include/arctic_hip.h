@@ -233,7 +233,7 @@ int arctic_set_mesh_skin(ArcticRenderer *r, uint64_t mesh, const ArcticSkinVerte
  * instead (what that costs). */
 int arctic_set_mesh_pose(ArcticRenderer *r, uint64_t mesh, const float *joint_matrices, uint32_t n_joints);
 
-/* The vertices the next prepass will read for this mesh, posed or not (tests).  n_vertices must be the mesh's vertex count.  Synchronises. */
+/* The vertices the next prepass will read for this mesh -- posed, else morphed, else its own (tests). n_vertices must be the mesh's vertex count.  Synchronises. */
 int arctic_read_mesh_vertices(ArcticRenderer *r, uint64_t mesh, ArcticVertex *out, uint64_t n_vertices);
 
 /* The validation arctic_set_mesh_skin applies to the records: ARCTIC_OK or ARCTIC_E_INVALID (NULL and n_vertices = 0 are invalid here).
@@ -244,6 +244,57 @@ int arctic_check_mesh_skin(const ArcticSkinVertex *skin, uint64_t n_vertices, ui
  * a null pointer, records arctic_check_mesh_skin refuses, a matrix element that is not finite.  Host only, no handle. */
 int arctic_skin_vertices(const ArcticVertex *in, const ArcticSkinVertex *skin, uint64_t n_vertices,
                          const float *joint_matrices, uint32_t n_joints, ArcticVertex *out);
+
+/* ---- morph targets (blend shapes; no counterpart in the reference) -----------------------------------------------------------------------
+ * A mesh may carry n_targets MORPH TARGETS -- per target one ArcticMorphDelta per vertex -- and one WEIGHT per target.  While any weight is not
+ * zero, every pass reads a blended copy of the mesh's vertex buffer, written on the device by one kernel per weights change (morph.hip, k_morph).
+ *
+ * The arithmetic, defined exactly.  With e = the 12 floats of position, normal, tangent and bitangent of vertex v, and k0 < k1 < ... the targets
+ * whose weight is not 0.0f (weights of either sign of zero are skipped), in ascending target index:
+ *   m[e] = base[e];   for k in k0, k1, ...:  m[e] = m[e] + w[k] * delta[k][v][e]
+ *   uv'  = uv
+ * Every operation is fp32: the product rounds once, then the sum rounds once, in the written order, without contraction.  numpy in float32
+ * reproduces the result bit for bit (tests/morph_reference.py), and so does arctic_morph_vertices on the host.  Nothing is normalised here (the
+ * vertex kernel normalises the three vectors as it always has).  Weights are used as given: negative values and values above 1 are legal.
+ * SKIPPING IS PART OF THE DEFINITION, not only an optimisation: "all weights zero" is the mesh's own vertices bit for bit, a -0.0 included (adding
+ * 0 * d would turn it into +0.0), and a target at rest costs no memory traffic.
+ * LIMIT: the bitangent is blended linearly like the other three vectors; it is not recomputed from the blended normal and tangent.  The caller
+ * supplies its delta (the glTF loader's rule: include/arctic_gltf.h).
+ * ORDER WITH A SKIN: morph first, then skin, as glTF specifies.  The buffer the passes read for a morphed and posed mesh is skin(morph(base)),
+ * both steps by their own definitions, so the composition is bit-defined too.
+ *
+ * Like a pose, weights belong to the MESH.  A mesh whose weights are not all zero is drawn with cluster boxes that are never skipped (its real
+ * boxes return when the weights return to zero and there is no pose), and every successful targets or weights call counts as a change for
+ * arctic_render_frame's shadow caches.  Each rank of a sharded frame morphs its own copy. */
+typedef struct ArcticMorphDelta {   /* 48 bytes */
+    float position[3], normal[3], tangent[3], bitangent[3];   /* finite */
+} ArcticMorphDelta;
+
+/* Attaches morph targets to an existing mesh, or replaces the ones it has.  deltas is target-major: deltas[k * n_vertices + v].  deltas == NULL
+ * detaches them (n_vertices and n_targets are then ignored).  Synchronous like arctic_set_mesh_skin; replacing or detaching drains the stream in
+ * use first.  All weights are zero afterwards: the mesh renders its own vertices, or -- if it is posed -- the pose of its own vertices (the pose
+ * is applied again from the matrices the mesh holds).
+ * ARCTIC_E_INVALID, the mesh left as it was: a mesh that does not exist, n_vertices is not the mesh's vertex count, n_targets outside 1..65535,
+ * a delta that is not finite.  ARCTIC_E_DEVICE, the mesh left as it was: the n_targets * n_vertices * 48 bytes cannot be allocated. */
+int arctic_set_mesh_morph_targets(ArcticRenderer *r, uint64_t mesh, const ArcticMorphDelta *deltas, uint64_t n_vertices, uint32_t n_targets);
+
+/* Sets the weights of a mesh with morph targets: n_targets floats.  The weights are copied before the call returns; the blend is enqueued on the
+ * handle's stream, in order with the passes, exactly like arctic_set_mesh_pose -- no host synchronisation, no device drain, and weights set
+ * between two arctic_render_frame calls apply to exactly the frames after them.  NULL, 0, or weights that are all zero, return the mesh to its
+ * own vertices (the blended buffer is kept for the next call; no blend is launched).  If the mesh is posed, the pose is applied again behind the
+ * blend, from the blended buffer and the matrices the mesh holds.
+ * ARCTIC_E_STATE: the mesh has no targets.  ARCTIC_E_INVALID, the previous weights kept: n_targets is not the mesh's, a weight that is not
+ * finite, a mesh that does not exist. */
+int arctic_set_mesh_morph_weights(ArcticRenderer *r, uint64_t mesh, const float *weights, uint32_t n_targets);
+
+/* The validation arctic_set_mesh_morph_targets applies to the records: ARCTIC_OK or ARCTIC_E_INVALID (NULL, n_vertices = 0 and n_targets
+ * outside 1..65535 are invalid here).  Host only, no handle. */
+int arctic_check_morph_targets(const ArcticMorphDelta *deltas, uint64_t n_vertices, uint32_t n_targets);
+
+/* The arithmetic above on the host, operation for operation: out[v] = the blended in[v] (out may be in).  ARCTIC_E_INVALID (nothing written):
+ * a null pointer, records arctic_check_morph_targets refuses, a weight that is not finite.  Host only, no handle. */
+int arctic_morph_vertices(const ArcticVertex *in, const ArcticMorphDelta *deltas, uint64_t n_vertices, uint32_t n_targets,
+                          const float *weights, ArcticVertex *out);
 
 /* glTF material factors, emissive and occlusion (no counterpart in the reference, whose material is three images).  Per material twelve
  * floats and two optional images. */
