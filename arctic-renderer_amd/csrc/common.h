@@ -486,6 +486,13 @@ hipError_t launch_skin(const float *vertices, const void *skin, const float *joi
 struct MorphActive { uint32_t target; float weight; };
 hipError_t launch_morph(const float *vertices, const float *deltas, const MorphActive *active, uint32_t n_active, uint32_t n_vertices, float *out,
                         hipStream_t s);
+// ray queries (trace.hip, include/arctic_hip.h: arctic_trace_rays): n records of 32 bytes (ArcticRay) against the structure of ray_query.h -- n_nodes
+// RayNode, the RayTri they point at, both validated by the host (bvh_validate) -> n records of 16 bytes (ArcticHit); any != 0: any hit.  n < 2^32; all
+// pointers 16-byte aligned.  launch_trace_sun: one any-hit ray per pixel of the G-buffer g from world + bias * n towards minus_sun -> mask, one byte per
+// pixel of the shard's rows x width, row-major: 255 = nothing hit or no geometry, 0 = a triangle hit
+hipError_t launch_trace(const void *rays, uint64_t n, const void *nodes, const void *tris, uint32_t n_nodes, int any, void *hits, hipStream_t s);
+hipError_t launch_trace_sun(GBuffer g, uint32_t tiles_x, uint32_t tiles_y, uint32_t width, uint32_t rows, uint32_t row0_in_tile, float bias, const float minus_sun[3],
+                            const void *nodes, const void *tris, uint32_t n_nodes, uint8_t *mask, hipStream_t s);
 
 // ---- host math (host_math.cpp): glm-equivalent builders, scene.cpp:9-19,41-70 ----------------
 void dir_from_rot(const float rot_deg[2], float out[3]);

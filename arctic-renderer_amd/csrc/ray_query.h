@@ -1,0 +1,179 @@
+// ray_query.h -- ray queries against the scene's triangles (include/arctic_hip.h: arctic_trace_rays and the text in front of it, which is the
+// definition; nothing here restates it, it only carries it out).  ONE copy of the intersection arithmetic and of the walk, compiled for the host
+// (bvh.cpp: the builder, arctic_trace_triangles) and for the device (trace.hip: k_trace, k_trace_sun), both with contraction off.  Plain C++: no
+// HIP type appears here, so the builder and the host walk also compile with a host compiler alone (tests/cpp/bvh_sanitize.cpp).
+#pragma once
+#include <stdint.h>
+#include <stddef.h>
+#include <vector>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define RQ_HD __host__ __device__ __forceinline__
+#else
+#define RQ_HD inline
+#endif
+
+namespace arctic {
+
+// ---- the structure on the device and on the host ------------------------------------------------------------------------------------------
+// Nodes in DEPTH-FIRST order with a SKIP LINK: node i's first child is node i + 1, `skip` is the node behind i's subtree (n_nodes behind the last),
+// so a walk is  i = descend ? i + 1 : skip  -- the index strictly increases, no stack.  leaf = first << 3 | count: count = 0 an interior node,
+// 1..4 a leaf whose triangles are records first .. first + count - 1 (and whose skip is i + 1).  Boxes are exact fp32 unions, no padding.
+struct alignas(16) RayNode { float bmin[3]; uint32_t skip; float bmax[3]; uint32_t leaf; };          // 32 bytes: two 16-byte loads
+struct alignas(16) RayTri { float p0[3], p1[3], p2[3]; uint32_t prim; uint32_t pad[2]; };             // 48 bytes: three 16-byte loads
+static_assert(sizeof(RayNode) == 32 && sizeof(RayTri) == 48, "ray query records");
+struct alignas(16) RayIn { float o[3], t_min, d[3], t_max; };                                         // == ArcticRay
+struct alignas(16) RayOut { float t, u, v; uint32_t prim; };                                          // == ArcticHit
+constexpr uint32_t RAY_NO_PRIM = 0xFFFFFFFFu;
+constexpr uint32_t RAY_LEAF_MAX = 4;
+constexpr uint64_t RAY_MAX_STORED = (1ull << 29) - 1;   // `first` has 29 bits
+
+// the records are READ as whole 16-byte pieces (one vector load each on the device), whatever part of them a path of the walk uses
+typedef float rq_f4 __attribute__((vector_size(16), may_alias));
+RQ_HD uint32_t rq_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
+
+constexpr uint32_t RQ_INF_BITS = 0x7F800000u;
+RQ_HD float rq_inf() { return __builtin_huge_valf(); }
+// min / max as the header defines them: of two equal operands (zeros of either sign included) the FIRST; never applied to a NaN
+RQ_HD float rq_min(float a, float b) { return b < a ? b : a; }
+RQ_HD float rq_max(float a, float b) { return a < b ? b : a; }
+RQ_HD bool rq_finite(float x) { return (__builtin_bit_cast(uint32_t, x) & RQ_INF_BITS) != RQ_INF_BITS; }
+
+// a ray as the walk uses it: the reciprocals are taken once (1.0f / d is the same float wherever it is taken)
+struct RayPrep {
+    float o0, o1, o2, d0, d1, d2;
+    float i0, i1, i2;      // 1.0f / d (unused where d == 0)
+    float n0, n1, n2;      // the same for the NODE test, +inf where d == 0 (see rq_node)
+    float t_min, t_max;
+    bool valid;            // finite origin and direction, direction not zero
+    bool odd;              // some d == 0 or some reciprocal not finite: the node test has to watch for 0 * inf
+};
+RQ_HD RayPrep rq_prepare(const RayIn &r) {
+    RayPrep p;
+    p.o0 = r.o[0]; p.o1 = r.o[1]; p.o2 = r.o[2]; p.d0 = r.d[0]; p.d1 = r.d[1]; p.d2 = r.d[2];
+    p.t_min = r.t_min; p.t_max = r.t_max;
+    p.valid = rq_finite(p.o0) && rq_finite(p.o1) && rq_finite(p.o2) && rq_finite(p.d0) && rq_finite(p.d1) && rq_finite(p.d2) &&
+              !(p.d0 == 0.0f && p.d1 == 0.0f && p.d2 == 0.0f);
+    p.i0 = 1.0f / p.d0; p.i1 = 1.0f / p.d1; p.i2 = 1.0f / p.d2;
+    p.n0 = p.d0 == 0.0f ? rq_inf() : p.i0; p.n1 = p.d1 == 0.0f ? rq_inf() : p.i1; p.n2 = p.d2 == 0.0f ? rq_inf() : p.i2;
+    p.odd = !(rq_finite(p.n0) && rq_finite(p.n1) && rq_finite(p.n2));
+    return p;
+}
+
+// one axis of "ray against box", exactly as defined: false = the box is missed on this axis
+RQ_HD bool rq_axis(float o, float d, float inv, float bmin, float bmax, float &lo, float &hi) {
+    lo = -rq_inf(); hi = rq_inf();
+    if (d == 0.0f) return bmin <= o && o <= bmax;
+    const float l = (bmin - o) * inv, h = (bmax - o) * inv;
+    if (l != l || h != h) return true;   // 0 * inf: a direction component whose reciprocal overflows and an origin in the plane: no constraint
+    lo = rq_min(l, h); hi = rq_max(l, h);
+    return true;
+}
+RQ_HD bool rq_box(const RayPrep &r, float bx0, float by0, float bz0, float bx1, float by1, float bz1, float &tn, float &tf) {
+    float l0, h0, l1, h1, l2, h2;
+    const bool a = rq_axis(r.o0, r.d0, r.i0, bx0, bx1, l0, h0), b = rq_axis(r.o1, r.d1, r.i1, by0, by1, l1, h1), c = rq_axis(r.o2, r.d2, r.i2, bz0, bz1, l2, h2);
+    tn = rq_max(rq_max(l0, l1), l2);
+    tf = rq_min(rq_min(h0, h1), h2);
+    return a && b && c && tn <= tf;
+}
+
+// "ray against triangle", exactly as defined (the caller has excluded triangles with a vertex that is not finite)
+RQ_HD bool rq_triangle(const RayPrep &r, const float *p0, const float *p1, const float *p2, float &t, float &u, float &v) {
+    float tn, tf;
+    if (!rq_box(r, rq_min(rq_min(p0[0], p1[0]), p2[0]), rq_min(rq_min(p0[1], p1[1]), p2[1]), rq_min(rq_min(p0[2], p1[2]), p2[2]),
+                rq_max(rq_max(p0[0], p1[0]), p2[0]), rq_max(rq_max(p0[1], p1[1]), p2[1]), rq_max(rq_max(p0[2], p1[2]), p2[2]), tn, tf)) return false;
+    const float e1x = p1[0] - p0[0], e1y = p1[1] - p0[1], e1z = p1[2] - p0[2];
+    const float e2x = p2[0] - p0[0], e2y = p2[1] - p0[1], e2z = p2[2] - p0[2];
+    const float pvx = r.d1 * e2z - r.d2 * e2y, pvy = r.d2 * e2x - r.d0 * e2z, pvz = r.d0 * e2y - r.d1 * e2x;
+    const float det = (e1x * pvx + e1y * pvy) + e1z * pvz;
+    const float inv = 1.0f / det;
+    const float tvx = r.o0 - p0[0], tvy = r.o1 - p0[1], tvz = r.o2 - p0[2];
+    u = ((tvx * pvx + tvy * pvy) + tvz * pvz) * inv;
+    const float qvx = tvy * e1z - tvz * e1y, qvy = tvz * e1x - tvx * e1z, qvz = tvx * e1y - tvy * e1x;
+    v = ((r.d0 * qvx + r.d1 * qvy) + r.d2 * qvz) * inv;
+    const float tm = ((e2x * qvx + e2y * qvy) + e2z * qvz) * inv;
+    if (!(det != 0.0f && u >= 0.0f && u <= 1.0f && v >= 0.0f && u + v <= 1.0f) || tm != tm) return false;
+    t = rq_min(rq_max(tm, tn), tf);
+    return r.t_min <= t && t <= r.t_max;
+}
+RQ_HD bool rq_finite9(const float *p) {
+    bool ok = true;
+    for (int k = 0; k < 9; ++k) ok = ok && rq_finite(p[k]);
+    return ok;
+}
+
+// The NODE test.  It only has to be CONSERVATIVE: true whenever the node's box, by the definition, is met with
+// max(tn, t_min) <= min(tf, t_max, t_best) -- a needless visit costs time, never a result.  So it may use the hardware's min / max (which differ
+// from the defined ones in the sign of a zero only), takes d == 0 as a reciprocal of +inf (a box the origin is outside of then gives an
+// interval at +-inf, one it is strictly inside of (-inf, +inf)), and folds the ray's own interval in.  ODD rays (RayPrep::odd) can produce
+// 0 * inf = NaN -- origin in a box's plane -- which the definition reads as "no constraint": they take the variant that checks for it.
+template <bool ODD>
+RQ_HD bool rq_node(const RayPrep &r, const rq_f4 &lo, const rq_f4 &hi, float cap) {
+    float l0 = (lo[0] - r.o0) * r.n0, h0 = (hi[0] - r.o0) * r.n0;
+    float l1 = (lo[1] - r.o1) * r.n1, h1 = (hi[1] - r.o1) * r.n1;
+    float l2 = (lo[2] - r.o2) * r.n2, h2 = (hi[2] - r.o2) * r.n2;
+    if (ODD) {
+        if (__builtin_isunordered(l0, h0)) { l0 = -rq_inf(); h0 = rq_inf(); }
+        if (__builtin_isunordered(l1, h1)) { l1 = -rq_inf(); h1 = rq_inf(); }
+        if (__builtin_isunordered(l2, h2)) { l2 = -rq_inf(); h2 = rq_inf(); }
+    }
+    // (fminf / fmaxf drop a NaN operand: a NaN t_min or t_max constrains nothing here, and the triangle test then refuses every hit)
+    const float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(l0, h0), __builtin_fminf(l1, h1)), __builtin_fmaxf(__builtin_fminf(l2, h2), r.t_min));
+    const float tf = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(l0, h0), __builtin_fmaxf(l1, h1)), __builtin_fminf(__builtin_fmaxf(l2, h2), cap));
+    return !(tn > tf);   // strict: a tie must still be found
+}
+
+// The walk: closest hit (ANY = false) or any hit.  `visits`, where given, counts {nodes fetched, triangles tested} (host measurements).
+// Terminates whatever the arrays hold: the index grows by at least one per turn and a leaf has at most 7 turns.
+template <bool ANY, bool ODD>
+RQ_HD RayOut rq_walk(const RayPrep &r, const RayNode *nodes, const RayTri *tris, uint32_t n_nodes, uint64_t *visits = nullptr) {
+    RayOut best = {0.0f, 0.0f, 0.0f, RAY_NO_PRIM};
+    float best_t = rq_inf();
+    uint32_t i = 0;
+    while (i < n_nodes) {
+        const rq_f4 *np = reinterpret_cast<const rq_f4 *>(nodes + i);
+        const rq_f4 lo = np[0], hi = np[1];                    // {bmin.xyz, skip} {bmax.xyz, first << 3 | count}
+        uint32_t next = rq_bits(lo[3]);
+        if (visits) ++visits[0];
+        const float cap = ANY ? r.t_max : __builtin_fminf(r.t_max, best_t);
+        if (rq_node<ODD>(r, lo, hi, cap)) {
+            next = i + 1;
+            const uint32_t leaf = rq_bits(hi[3]), count = leaf & 7u, first = leaf >> 3;
+            for (uint32_t k = 0; k < count; ++k) {
+                const rq_f4 *tp = reinterpret_cast<const rq_f4 *>(tris + first + k);
+                const rq_f4 a = tp[0], b = tp[1], c = tp[2];   // {p0.xyz, p1.x} {p1.yz, p2.xy} {p2.z, prim, -, -}
+                const float p0[3] = {a[0], a[1], a[2]}, p1[3] = {a[3], b[0], b[1]}, p2[3] = {b[2], b[3], c[0]};
+                const uint32_t prim = rq_bits(c[1]);
+                float t, u, v;
+                if (visits) ++visits[1];
+                if (rq_triangle(r, p0, p1, p2, t, u, v)) {
+                    if (ANY) { best.prim = 0u; next = n_nodes; }
+                    else if (t < best_t || (t == best_t && prim < best.prim)) { best_t = t; best.t = t; best.u = u; best.v = v; best.prim = prim; }
+                }
+            }
+        }
+        i = next > i ? next : i + 1;   // (next > i always, in a structure that passed bvh_validate)
+    }
+    return best;
+}
+
+// ---- host side (bvh.cpp) ---------------------------------------------------------------------------------------------------------------------
+struct Bvh {
+    std::vector<RayNode> nodes;
+    std::vector<RayTri> tris;     // reordered by leaf; triangles with a vertex that is not finite are left out
+    uint32_t depth = 0;           // nodes on the longest path from the root (0: no node)
+};
+// tris9: n triangles of 9 floats (world space); prims: their numbers, or null = the array index.  Deterministic: median split on the widest centroid
+// axis, ties by prim.  false: more than RAY_MAX_STORED triangles to store
+bool bvh_build(const float *tris9, uint64_t n, const uint32_t *prims, Bvh &out);
+// every node: index < skip <= n_nodes, first + count <= n_tris, a child's box inside its parent's (what the device walk relies on)
+bool bvh_validate(const Bvh &b);
+// the scene's triangles of one object: p = mat_vec(trs, vertex, 1) exactly as k_vertex writes attr[11..13]; triangles with an index out of range
+// are skipped but numbered.  Appends 9 floats + one prim per kept triangle; returns the next prim
+uint64_t ray_world_triangles(const float *trs, const float *vertices14, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, uint64_t first_prim,
+                             std::vector<float> &tris9, std::vector<uint32_t> &prims);
+void bvh_trace_host(const Bvh &b, const RayIn *rays, uint64_t n, bool any, RayOut *hits, uint64_t *visits /* 2, or null */);
+void brute_trace_host(const float *tris9, uint64_t n_tris, const RayIn *rays, uint64_t n, bool any, RayOut *hits);
+
+}  // namespace arctic

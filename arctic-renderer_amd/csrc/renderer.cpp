@@ -21,6 +21,7 @@
 #include "../../include/arctic_hip.h"
 #include "../../include/arctic_dist.h"
 #include "common.h"
+#include "ray_query.h"
 
 using namespace arctic;
 
@@ -397,6 +398,15 @@ struct ArcticRenderer {
     DevBuf d_staging, d_layout;                       // root: all shards back to back; ranges (2 u32 per rank) + byte offsets (u64 per rank)
     uint32_t layout_world = 0; bool layout_from_comm = false;
     bool shadow_sharded = false;                      // ARCTIC_OPT_SHADOW_SHARDED
+    // Ray queries (arctic_trace_rays, arctic_trace_sun_visibility): the acceleration structure over the scene's world-space triangles, built on the
+    // host (bvh.cpp) from the vertices in use, and cached: ray_key is what it was built from -- ray_inputs(), shadow_inputs' rule -- so a changed
+    // object list, mesh count, pose or weights rebuilds it on the next query.  ray_tris: triangles stored (those that can be hit)
+    struct RayScene {
+        std::vector<uint8_t> key;
+        bool built = false;
+        uint64_t n_tris = 0, n_nodes = 0, builds = 0, depth = 0;
+        DevBuf d_nodes, d_tris, d_rays, d_hits, d_mask;
+    } ray;
     uint32_t *dh_counts = nullptr;  // the device's address of h_counts
     uint32_t *h_counts = nullptr;   // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     std::string err;
@@ -1184,6 +1194,7 @@ void arctic_destroy(ArcticRenderer *r) {
                       &r->geo[1].d_recs, &r->geo[1].d_rrecs, &r->geo[1].d_clip_list, &r->geo[1].d_rec_of, &r->geo[1].d_items, &r->geo[0].d_left, &r->geo[1].d_left, &r->geo[2].d_left, &r->geo[0].d_bin_count, &r->geo[0].d_bin_slots, &r->geo[1].d_bin_count, &r->geo[1].d_bin_slots, &r->geo[2].d_bin_count, &r->geo[2].d_bin_slots, &r->d_geo_counters, &r->d_stage, &r->tables[0].d, &r->tables[1].d};
     for (PassTables &T : r->tables) { if (T.h) (void)hipHostFree(T.h); if (T.copied) (void)hipEventDestroy(T.copied); }
     for (DevBuf *b : bufs) b->release();
+    for (DevBuf *b : {&r->ray.d_nodes, &r->ray.d_tris, &r->ray.d_rays, &r->ray.d_hits, &r->ray.d_mask}) b->release();
     delete r;
 }
 
@@ -2369,6 +2380,127 @@ int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
         break;
     default: return r->fail(ARCTIC_E_INVALID, "set_option: unknown option %u", option);
     }
+    return ARCTIC_OK;
+}
+
+// ---- ray queries (the definition: include/arctic_hip.h; the arithmetic: ray_query.h; the builder: bvh.cpp; the kernels: trace.hip) ----------------
+namespace {
+// everything the structure is a function of, as bytes (shadow_inputs' rule: the objects, the mesh count, the shape of every mesh in use)
+void ray_inputs(const ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_t> &k) {
+    k.clear();
+    auto put = [&](const void *p, size_t n) { const uint8_t *b = static_cast<const uint8_t *>(p); k.insert(k.end(), b, b + n); };
+    const uint64_t head[2] = {(uint64_t)r->meshes.size(), sc->n_objects};
+    put(head, sizeof head);
+    for (uint64_t i = 0; i < sc->n_objects; ++i) {
+        put(sc->objects[i].trs, sizeof sc->objects[i].trs); put(&sc->objects[i].mesh_idx, sizeof sc->objects[i].mesh_idx);
+        if (sc->objects[i].mesh_idx < r->meshes.size()) put(&r->meshes[sc->objects[i].mesh_idx].shape_seq, sizeof(uint64_t));
+    }
+}
+
+// the structure for `sc`, resident on the device: built, validated and uploaded when its inputs changed.  Synchronous (it reads the meshes back).
+int ensure_ray_scene(ArcticRenderer *r, const ArcticScene *sc) {
+    std::vector<uint8_t> key;
+    ray_inputs(r, sc, key);
+    if (r->ray.built && key == r->ray.key) return ARCTIC_OK;
+    // the vertices in use are written by k_morph / k_skin on the main stream; the structure in place may still be read by a query on it
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    std::vector<float> tris9;
+    std::vector<uint32_t> prims;
+    std::vector<std::vector<float>> verts(r->meshes.size());
+    std::vector<std::vector<uint32_t>> inds(r->meshes.size());
+    uint64_t prim = 0;
+    for (uint64_t i = 0; i < sc->n_objects; ++i) {
+        const ArcticObject &o = sc->objects[i];
+        if (o.mesh_idx >= r->meshes.size()) continue;   // (skipped by the passes as well: upload_pass_tables)
+        const Mesh &m = r->meshes[o.mesh_idx];
+        if (prim + m.n_indices / 3 > 0xFFFFFFFEull) return r->fail(ARCTIC_E_CAPACITY, "ray queries: more than 2^32 - 2 triangles in the scene");
+        if (verts[o.mesh_idx].empty()) {
+            verts[o.mesh_idx].resize((size_t)m.n_vertices * 14); inds[o.mesh_idx].resize(m.n_indices);
+            HIPCHECK(r, hipMemcpy(verts[o.mesh_idx].data(), m.vertices_in_use(), (size_t)m.n_vertices * sizeof(ArcticVertex), hipMemcpyDeviceToHost));
+            HIPCHECK(r, hipMemcpy(inds[o.mesh_idx].data(), m.d_indices, (size_t)m.n_indices * 4, hipMemcpyDeviceToHost));
+        }
+        prim = ray_world_triangles(o.trs, verts[o.mesh_idx].data(), m.n_vertices, inds[o.mesh_idx].data(), m.n_indices / 3, prim, tris9, prims);
+    }
+    Bvh b;
+    if (!bvh_build(tris9.data(), prims.size(), prims.data(), b))
+        return r->fail(ARCTIC_E_CAPACITY, "ray queries: %llu triangles to store, the structure holds 2^29 - 1", (unsigned long long)prims.size());
+    if (!bvh_validate(b)) return r->fail(ARCTIC_E_INVALID, "internal: the ray structure failed its validation (%zu nodes, %zu triangles); nothing was uploaded", b.nodes.size(), b.tris.size());
+    r->ray.built = false;
+    HIPCHECK(r, r->ray.d_nodes.ensure(std::max<size_t>(sizeof(RayNode), b.nodes.size() * sizeof(RayNode))));
+    HIPCHECK(r, r->ray.d_tris.ensure(std::max<size_t>(sizeof(RayTri), b.tris.size() * sizeof(RayTri))));
+    if (!b.nodes.empty()) HIPCHECK(r, hipMemcpy(r->ray.d_nodes.p, b.nodes.data(), b.nodes.size() * sizeof(RayNode), hipMemcpyHostToDevice));
+    if (!b.tris.empty()) HIPCHECK(r, hipMemcpy(r->ray.d_tris.p, b.tris.data(), b.tris.size() * sizeof(RayTri), hipMemcpyHostToDevice));
+    r->ray.key.swap(key);
+    r->ray.n_tris = b.tris.size(); r->ray.n_nodes = b.nodes.size(); r->ray.depth = b.depth;
+    ++r->ray.builds;
+    r->ray.built = true;
+    return ARCTIC_OK;
+}
+
+int trace_checks(ArcticRenderer *r, const ArcticScene *sc, const void *rays, uint64_t n, uint32_t flags, const void *hits, const char *who) {
+    if (!valid_scene(sc)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
+    if (flags & ~ARCTIC_TRACE_ANY) return r->fail(ARCTIC_E_INVALID, "%s: flags %#x (ARCTIC_TRACE_ANY or 0; ARCTIC_TRACE_BRUTE belongs to arctic_trace_triangles)", who, flags);
+    if (n && (!rays || !hits)) return r->fail(ARCTIC_E_INVALID, "%s: null rays or hits", who);
+    if (n > 0xFFFFFFFFull) return r->fail(ARCTIC_E_CAPACITY, "%s: %llu rays in one call (2^32 - 1 at most)", who, (unsigned long long)n);
+    return ARCTIC_OK;
+}
+}  // namespace
+
+int arctic_trace_rays_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *d_rays, uint64_t n, uint32_t flags, ArcticHit *d_hits) {
+    if (!r) return ARCTIC_E_INVALID;
+    int rc = trace_checks(r, scene, d_rays, n, flags, d_hits, "trace_rays_device");
+    if (rc) return rc;
+    if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u) return r->fail(ARCTIC_E_INVALID, "trace_rays_device: rays and hits must be 16-byte aligned");
+    if ((rc = select_device(r)) != ARCTIC_OK || (rc = ensure_ray_scene(r, scene)) != ARCTIC_OK) return rc;
+    HIPCHECK(r, launch_trace(d_rays, n, r->ray.d_nodes.p, r->ray.d_tris.p, (uint32_t)r->ray.n_nodes, (flags & ARCTIC_TRACE_ANY) != 0, d_hits, r->stream));
+    return ARCTIC_OK;
+}
+
+int arctic_trace_rays(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits) {
+    if (!r) return ARCTIC_E_INVALID;
+    int rc = trace_checks(r, scene, rays, n, flags, hits, "trace_rays");
+    if (rc) return rc;
+    if ((rc = select_device(r)) != ARCTIC_OK || (rc = ensure_ray_scene(r, scene)) != ARCTIC_OK) return rc;
+    if (n == 0) return ARCTIC_OK;
+    HIPCHECK(r, r->ray.d_rays.ensure(n * sizeof(ArcticRay)));
+    HIPCHECK(r, r->ray.d_hits.ensure(n * sizeof(ArcticHit)));
+    HIPCHECK(r, hipMemcpyAsync(r->ray.d_rays.p, rays, n * sizeof(ArcticRay), hipMemcpyHostToDevice, r->stream));
+    HIPCHECK(r, launch_trace(r->ray.d_rays.p, n, r->ray.d_nodes.p, r->ray.d_tris.p, (uint32_t)r->ray.n_nodes, (flags & ARCTIC_TRACE_ANY) != 0, r->ray.d_hits.p, r->stream));
+    HIPCHECK(r, hipMemcpyAsync(hits, r->ray.d_hits.p, n * sizeof(ArcticHit), hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    return ARCTIC_OK;
+}
+
+int arctic_trace_sun_visibility(ArcticRenderer *r, const ArcticScene *scene, float bias, uint8_t *mask) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "trace_sun_visibility: null scene");
+    if (!std::isfinite(bias)) return r->fail(ARCTIC_E_INVALID, "trace_sun_visibility: the bias is not finite");
+    int rc = select_device(r);
+    if (rc) return rc;
+    if (!r->have_gbuffer) {
+        if (!r->have_vis) return r->fail(ARCTIC_E_STATE, "trace_sun_visibility: no G-buffer (arctic_pass_gbuffer, arctic_write_gbuffer or a frame first)");
+        if ((rc = resolve_gbuffer(r)) != ARCTIC_OK) return rc;   // the frame was shaded from the visibility plane
+    }
+    if ((rc = ensure_ray_scene(r, scene)) != ARCTIC_OK) return rc;
+    float sun[3];
+    dir_from_rot(scene->sun.rotation, sun);
+    const float minus_sun[3] = {-sun[0], -sun[1], -sun[2]};
+    const size_t bytes = (size_t)r->rows() * r->width;
+    HIPCHECK(r, r->ray.d_mask.ensure(std::max<size_t>(bytes, 16)));
+    HIPCHECK(r, launch_trace_sun(r->gbuffer(), r->tiles_x, r->tiles_y, r->width, r->rows(), r->row0_in_tile, bias, minus_sun, r->ray.d_nodes.p, r->ray.d_tris.p,
+                                 (uint32_t)r->ray.n_nodes, r->ray.d_mask.as<uint8_t>(), r->stream));
+    if (mask) {
+        HIPCHECK(r, hipMemcpyAsync(mask, r->ray.d_mask.p, bytes, hipMemcpyDeviceToHost, r->stream));
+        HIPCHECK(r, hipStreamSynchronize(r->stream));
+        if (int ov = check_item_overflow(r)) return ov;
+    }
+    return ARCTIC_OK;
+}
+
+int arctic_ray_scene_info(ArcticRenderer *r, uint64_t *out4) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!out4) return r->fail(ARCTIC_E_INVALID, "ray_scene_info: null");
+    out4[0] = r->ray.n_tris; out4[1] = r->ray.n_nodes; out4[2] = r->ray.builds; out4[3] = r->ray.depth;
     return ARCTIC_OK;
 }
 

@@ -216,6 +216,24 @@ class Renderer {
     [[nodiscard]] bool antialias(const uint8_t *rgba8, uint32_t width, uint32_t height, uint8_t *out) { return ok(arctic_antialias(m_handle, rgba8, width, height, out)); }
     [[nodiscard]] bool antialias_device(const void *d_in, void *d_out, uint32_t width, uint32_t height) { return ok(arctic_antialias_device(m_handle, d_in, d_out, width, height)); }
 
+    // ray queries (include/arctic_hip.h: arctic_trace_rays and the definition in front of it; the reference's roadmap item "Raytracing"): n rays
+    // against the scene's triangles, closest hit or -- ARCTIC_TRACE_ANY -- any hit; host buffers, synchronous.  The handle builds and caches the
+    // acceleration structure; a changed object list, pose or weights rebuilds it on the next query
+    [[nodiscard]] bool trace_rays(const ArcticScene &scene, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits) {
+        return ok(arctic_trace_rays(m_handle, &scene, rays, n, flags, hits));
+    }
+    // the same between device buffers, in stream order on the handle's stream
+    [[nodiscard]] bool trace_rays_device(const ArcticScene &scene, const ArcticRay *d_rays, uint64_t n, uint32_t flags, ArcticHit *d_hits) {
+        return ok(arctic_trace_rays_device(m_handle, &scene, d_rays, n, flags, d_hits));
+    }
+    // one any-hit ray per pixel of the resident G-buffer towards the sun: mask = rows x width bytes, 255 = lit or no geometry, 0 = occluded
+    [[nodiscard]] bool trace_sun_visibility(const ArcticScene &scene, float bias, uint8_t *mask) { return ok(arctic_trace_sun_visibility(m_handle, &scene, bias, mask)); }
+    [[nodiscard]] bool ray_scene_info(uint64_t out4[4]) { return ok(arctic_ray_scene_info(m_handle, out4)); }
+    // the host arbiter: world-space triangles of 9 floats, prim = the array index; ARCTIC_TRACE_BRUTE loops over every triangle (no handle, no GPU)
+    [[nodiscard]] static bool trace_triangles(const float *tris9, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits) {
+        return arctic_trace_triangles(tris9, n_tris, rays, n, flags, hits) == ARCTIC_OK;
+    }
+
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }
 

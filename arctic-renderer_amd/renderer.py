@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (HIT_DTYPE, RAY_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -193,6 +193,38 @@ class Renderer:
         v = np.empty(int(n_vertices), VERTEX_DTYPE)
         self._check(self.L.arctic_read_mesh_vertices(self.h, int(mesh), _ptr(v), len(v)))
         return v
+
+    # ---- ray queries (include/arctic_hip.h: arctic_trace_rays and the definition in front of it) ---------------------------------
+    def trace_rays(self, desc, rays, any_hit=False):
+        """RAY_DTYPE records against the scene's triangles: HIT_DTYPE records, the closest hit of each ray (prim 0xFFFFFFFF: a miss) or, with
+        any_hit, whether anything is hit (prim 0 / 0xFFFFFFFF).  Builds or refreshes the handle's acceleration structure when the scene changed."""
+        s = self._scene(desc)
+        ry = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
+        hits = np.empty(len(ry), HIT_DTYPE)
+        self._check(self.L.arctic_trace_rays(self.h, C.byref(s), _ptr(ry) if len(ry) else None, len(ry), binding.TRACE_ANY if any_hit else 0,
+                                             _ptr(hits) if len(ry) else None))
+        return hits
+
+    def trace_rays_device(self, desc, d_rays_ptr, n, d_hits_ptr, any_hit=False):
+        """the same between device buffers (int pointers, e.g. torch tensors' .data_ptr(); 32 bytes per ray, 16 per hit, 16-byte aligned);
+        asynchronous on the handle's stream."""
+        s = self._scene(desc)
+        self._check(self.L.arctic_trace_rays_device(self.h, C.byref(s), C.c_void_p(d_rays_ptr) if d_rays_ptr else None, int(n),
+                                                    binding.TRACE_ANY if any_hit else 0, C.c_void_p(d_hits_ptr) if d_hits_ptr else None))
+
+    def trace_sun_visibility(self, desc, bias, read=True):
+        """one any-hit ray per pixel of the resident G-buffer towards the sun, from world + bias * n: (rows, width) uint8, 255 = the sun is
+        visible or no geometry, 0 = occluded.  read=False leaves the mask on the device and returns None (timing)."""
+        s = self._scene(desc)
+        mask = np.empty((self.rows, self.width), np.uint8) if read else None
+        self._check(self.L.arctic_trace_sun_visibility(self.h, C.byref(s), float(bias), _ptr(mask)))
+        return mask
+
+    def ray_scene_info(self):
+        """(triangles stored, nodes, builds so far, depth) of the cached acceleration structure"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_ray_scene_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
 
     def create_hdri(self, rgba32f):
         a = np.ascontiguousarray(rgba32f, dtype=np.float32)
@@ -469,6 +501,19 @@ def morph_vertices(vertices, deltas, weights):
     if rc < 0:
         raise ArcticError(rc, "morph_vertices: invalid deltas or weights")
     return out
+
+
+def trace_triangles(triangles, rays, any_hit=False, brute=False):
+    """arctic_trace_triangles: the ray queries of include/arctic_hip.h on the host -- (n, 9) or (n, 3, 3) float32 world-space triangles (prim = the
+    array index) against RAY_DTYPE records: HIT_DTYPE records.  brute: loop over every triangle instead of the acceleration structure."""
+    t = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
+    ry = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
+    hits = np.empty(len(ry), HIT_DTYPE)
+    flags = (binding.TRACE_ANY if any_hit else 0) | (binding.TRACE_BRUTE if brute else 0)
+    rc = binding.lib().arctic_trace_triangles(_ptr(t) if len(t) else None, len(t), _ptr(ry) if len(ry) else None, len(ry), flags, _ptr(hits) if len(ry) else None)
+    if rc < 0:
+        raise ArcticError(rc, "trace_triangles")
+    return hits
 
 
 def point_shadow_matrices(light):

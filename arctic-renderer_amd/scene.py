@@ -33,6 +33,10 @@ assert SKIN_VERTEX_DTYPE.itemsize == 24
 # ArcticMorphDelta (include/arctic_hip.h): 48 bytes, one per vertex per morph target of Renderer.set_mesh_morph_targets
 MORPH_DELTA_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("bitangent", "<f4", 3)])
 assert MORPH_DELTA_DTYPE.itemsize == 48
+# ArcticRay, ArcticHit (include/arctic_hip.h): 32 and 16 bytes, the records of Renderer.trace_rays
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("t_min", "<f4"), ("direction", "<f4", 3), ("t_max", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4")])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 16
 
 
 def neutral_material_params(n=1):
@@ -40,6 +44,15 @@ def neutral_material_params(n=1):
     a = np.zeros(n, MATERIAL_PARAMS_DTYPE)
     a["base_color_factor"], a["metallic_factor"], a["roughness_factor"], a["normal_scale"], a["occlusion_strength"] = 1, 1, 1, 1, 1
     return a
+
+
+def make_rays(origins, directions, t_min=0.0, t_max=np.inf):
+    """n RAY_DTYPE records from (n, 3) origins and directions; t_min / t_max scalars or (n,) arrays"""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    out = np.zeros(len(o), RAY_DTYPE)
+    out["origin"], out["direction"], out["t_min"], out["t_max"] = o, np.asarray(directions, np.float32).reshape(-1, 3), t_min, t_max
+    return out
+
 
 TM_REINHARD, TM_EXPOSURE, TM_ACES = 0, 1, 2
 

@@ -752,6 +752,87 @@ int arctic_read_bin_counts(ArcticRenderer *r, int shadow_pass, uint32_t *out, ui
    k_vertex.  Synchronises.  A measuring aid; no counterpart in the reference (forward_pass.cpp:212-224 draws every object). */
 int arctic_read_cull_counts(ArcticRenderer *r, int shadow_pass, uint32_t *out);
 
+/* ---- ray queries (no counterpart in the reference: its roadmap's "Raytracing") ------------------------------------------------------------------
+ * What does this ray hit?  The handle keeps an acceleration structure over the scene's triangles in world space, built on the host and walked on
+ * the device by ordinary vector code (trace.hip; the MI355X has no ray accelerator).  The answer is DEFINED bit for bit: a walk that prunes gives
+ * exactly what a loop over every triangle gives, numpy in float32 reproduces it (tests/ray_reference.py), and so does arctic_trace_triangles on
+ * the host.  Nothing in the passes uses it (yet): shading, shadow maps and every existing bit are unchanged.
+ *
+ * THE DEFINITION.  Everything is fp32; each operation rounds once, in the written order, without contraction; division is IEEE division.
+ *   min(a, b) = b < a ? b : a      max(a, b) = a < b ? b : a        (of two equal operands, zeros of either sign included, the first)
+ *   cross(a, b)[0] = a[1]*b[2] - a[2]*b[1], cyclically: two rounded products, then the rounded difference
+ *   dot(a, b)      = (a[0]*b[0] + a[1]*b[1]) + a[2]*b[2]
+ * Scene triangles.  The objects in ArcticScene::objects order, each object's triangles in index-buffer order; `prim` is the running index of the
+ *   triangle over the whole scene.  An object whose mesh does not exist has no triangles (the passes skip it too).  The triangle at an index
+ *   out of range is skipped as the rasteriser skips it, and still takes a prim number.  More than 2^32 - 2 triangles: ARCTIC_E_CAPACITY (and the
+ *   structure stores at most 2^29 - 1 triangles that can be hit: ARCTIC_E_CAPACITY as well).  A world vertex is the vertex kernel's transform of
+ *   the mesh's vertices IN USE (posed, else morphed, else its own: arctic_read_mesh_vertices) with w = 1 and M = the object's trs:
+ *     p[i] = ((M[i]*x + M[4+i]*y) + M[8+i]*z) + M[12+i]*1.0f                        i = 0..2: what arctic_read_gbuffer returns as attributes 11..13
+ *   A triangle with a world vertex that is not finite is never hit.
+ * Ray (o, d) against a box (bmin, bmax).  Per axis a:
+ *     d[a] == 0:  the axis contributes (-inf, +inf) when bmin[a] <= o[a] <= bmax[a]; otherwise the box is missed.
+ *     else:       inv = 1.0f / d[a];  l = (bmin[a] - o[a]) * inv;  h = (bmax[a] - o[a]) * inv;  lo = min(l, h);  hi = max(l, h).
+ *                 If l or h is a NaN the axis contributes (-inf, +inf) instead.  (That is 0 * inf: a d[a] so small that inv is infinite, and an
+ *                 origin in one of the box's planes -- the inclusive rule of d[a] == 0.  No other NaN can arise from finite operands.)
+ *     tn = max(max(lo[0], lo[1]), lo[2]);  tf = min(min(hi[0], hi[1]), hi[2]).  The box is met iff no axis missed it and tn <= tf.
+ *   The test is MONOTONE in box inclusion (rounding is monotone, and so is a multiplication by one fixed factor): a ray that meets a box B meets
+ *   every box that contains B, with tn' <= tn and tf' >= tf.  The whole design rests on this.
+ * Ray against triangle (p0, p1, p2).
+ *   1. The triangle's own box: bmin = min(min(p0, p1), p2), bmax = max(max(p0, p1), p2), component-wise.  (tn, tf) is its interval; a box that is
+ *      not met is a miss.
+ *   2. Moeller-Trumbore:  e1 = p1 - p0;  e2 = p2 - p0;  pv = cross(d, e2);  det = dot(e1, pv);  inv = 1.0f / det;  tv = o - p0;
+ *      u = dot(tv, pv) * inv;  qv = cross(tv, e1);  v = dot(d, qv) * inv;  tm = dot(e2, qv) * inv.
+ *      A miss unless  det != 0 && u >= 0 && u <= 1 && v >= 0 && u + v <= 1;  every comparison is false for a NaN, and a NaN tm is a miss too.
+ *   3. t = min(max(tm, tn), tf): Moeller-Trumbore's parameter CLAMPED INTO THE TRIANGLE'S OWN BOX INTERVAL.  A hit iff t_min <= t && t <= t_max.
+ *   Step 3 is what makes a pruned walk EXACTLY equal to the loop over every triangle, with no epsilon anywhere: a hit's t lies inside its
+ *   triangle's interval, so -- by monotonicity -- inside the interval of every box that contains the triangle; a node of the structure with
+ *   max(tn_node, t_min) > min(tf_node, t_max, t_best) therefore holds no hit at or below t_best.  The comparison is strict: a tie must still be found.
+ *   For an axis-aligned triangle (floors, walls) the box has no thickness and t is the slab's value, which is also better conditioned at grazing
+ *   angles than tm.
+ * Closest hit: among all triangles that are hit the smallest t (-0 == +0), among equal t the smallest prim; reported {t, u, v, prim} of that triangle.
+ * Any hit (ARCTIC_TRACE_ANY): only whether a triangle is hit at all: {0, 0, 0, 0}.
+ * A miss is {t = 0, u = 0, v = 0, prim = 0xFFFFFFFF}, under either flag.  A ray whose origin or direction has a component that is not finite, or
+ * whose direction is zero, is a miss, not an error; t_min and t_max are used as given (t_max = +inf: no far limit; a NaN limit admits no hit).
+ * KNOWN LIMITS.  The test is two-sided (no back-face culling).  It is NOT watertight: a ray through a shared edge can slip between the two
+ * triangles' rounded u and v.
+ *
+ * THE STRUCTURE.  A binary tree over the triangles that can be hit, at most 4 per leaf, built deterministically (median split on the widest
+ * centroid axis, ties by prim), boxes the exact fp32 unions -- no padding: the paragraph on step 3 is why none is needed.  Nodes are stored in
+ * depth-first order with a skip link, 32 bytes each; leaf triangles are stored by leaf, pre-transformed, 48 bytes each.  The device walk is
+ * i = descend ? i + 1 : skip[i]: the index strictly increases and the loop ends at the node count -- no stack, and termination by construction.
+ * The host checks every node before anything is uploaded (index < skip <= nodes, first + count <= triangles, a child's box inside its parent's).
+ * The structure is cached in the handle and rebuilt -- synchronously, draining the stream in use, reading deformed meshes back -- by the next
+ * query after the bytes of the objects, the mesh count, or the shape of a mesh in use changed (every successful skin, pose, morph-targets and
+ * weights call counts: the rule of arctic_render_frame's shadow cache).  Each rank of a sharded frame keeps its own full copy. */
+typedef struct ArcticRay { float origin[3]; float t_min; float direction[3]; float t_max; } ArcticRay;   /* 32 bytes */
+typedef struct ArcticHit { float t, u, v; uint32_t prim; } ArcticHit;                                    /* 16 bytes */
+#define ARCTIC_TRACE_ANY   1u   /* any hit instead of the closest */
+#define ARCTIC_TRACE_BRUTE 2u   /* arctic_trace_triangles only: loop over every triangle, no structure */
+
+/* n rays against the scene's triangles: hits[k] answers rays[k].  Host buffers, synchronous.  ARCTIC_E_INVALID: a null scene, null rays or hits
+ * with n > 0, a flag other than ARCTIC_TRACE_ANY.  ARCTIC_E_CAPACITY: n above 2^32 - 1, or a scene too large (above).  n = 0 only builds. */
+int arctic_trace_rays(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits);
+
+/* The same between DEVICE buffers the caller owns (16-byte aligned), stream-ordered on the handle's stream like arctic_render_frame_device: call
+ * arctic_flush() before another stream reads d_hits.  (A rebuild of the structure, when one is due, is synchronous.) */
+int arctic_trace_rays_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *d_rays, uint64_t n, uint32_t flags, ArcticHit *d_hits);
+
+/* One any-hit ray per pixel of the handle's RESIDENT G-buffer (arctic_pass_gbuffer, arctic_write_gbuffer, or the latest frame), towards the sun:
+ *   o[i] = world[i] + bias * n[i]   (the product rounds, then the sum),   d = -sun_dir,   t_min = 0,   t_max = +inf
+ * world and n are attributes 11..13 and 8..10 of arctic_read_gbuffer's order, sun_dir is arctic_frame_constants' sun_dir for `scene`.
+ * mask = rows * width bytes, row-major over the handle's rows like arctic_read_gbuffer: 255 where the sun is visible or the pixel has no
+ * geometry, 0 where a triangle is hit.  mask == NULL leaves the result on the device and does not synchronise (timing).  A sharded handle answers
+ * for its own rows.  ARCTIC_E_STATE without a G-buffer; ARCTIC_E_INVALID for a null scene or a bias that is not finite. */
+int arctic_trace_sun_visibility(ArcticRenderer *r, const ArcticScene *scene, float bias, uint8_t *mask);
+
+/* The host arbiter: the same definition, the same structure and the same walk on the CPU -- or, with ARCTIC_TRACE_BRUTE, the loop over every
+ * triangle.  tris9 = n_tris world-space triangles of 9 floats (p0, p1, p2); prim is the array index.  No handle, no GPU.
+ * ARCTIC_E_INVALID: a null pointer with a non-zero count, an unknown flag.  ARCTIC_E_CAPACITY: n_tris above 2^32 - 2. */
+int arctic_trace_triangles(const float *tris9, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits);
+
+/* The cached structure: out4 = {triangles stored (those that can be hit), nodes, builds so far, depth (nodes on the longest path; 0: empty)}. */
+int arctic_ray_scene_info(ArcticRenderer *r, uint64_t *out4);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row
