@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ARCTIC_HIP_LIBRARY") or os.path.join(HERE, "csrc", "libarctic_hip.so")   # the override is for A/B timing of two builds (tools/experiments)
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "arctic_hip.h")
 
-OPTIONS = {"keep_float_output": 1, "count_light_evals": 2, "culling": 3, "debug": 4, "antialias": 5, "hdr16": 6, "shadow_cache": 9, "visbuffer": 10, "item_table_floor": 11, "light_path": 12, "markers": 13, "shadow_sharded": 14, "frames_in_flight": 15, "tiles_per_wave": 16, "tile_trace": 17, "raster_owner": 18, "tile_order": 19, "order_tail": 20, "sampler": 21, "texture_tiling": 22, "cluster_cull": 23, "small_triangles": 24, "env_lighting": 25, "point_shadow_size": 26, "texture_mips": 27}
+OPTIONS = {"keep_float_output": 1, "count_light_evals": 2, "culling": 3, "debug": 4, "antialias": 5, "hdr16": 6, "ray_refit": 7, "shadow_cache": 9, "visbuffer": 10, "item_table_floor": 11, "light_path": 12, "markers": 13, "shadow_sharded": 14, "frames_in_flight": 15, "tiles_per_wave": 16, "tile_trace": 17, "raster_owner": 18, "tile_order": 19, "order_tail": 20, "sampler": 21, "texture_tiling": 22, "cluster_cull": 23, "small_triangles": 24, "env_lighting": 25, "point_shadow_size": 26, "texture_mips": 27}
 TRACE_ANY, TRACE_BRUTE = 1, 2   # ARCTIC_TRACE_* (include/arctic_hip.h)
 ERRORS = {-1: "ARCTIC_E_INVALID", -2: "ARCTIC_E_DEVICE", -3: "ARCTIC_E_NO_DEVICE", -4: "ARCTIC_E_STATE", -5: "ARCTIC_E_CAPACITY"}
 
@@ -84,6 +84,10 @@ SIGNATURES = {
     "arctic_trace_sun_visibility": (_i32, [_vp, _scene, C.c_float, _vp]),
     "arctic_trace_triangles": (_i32, [_vp, _u64, _vp, _u64, _u32, _vp]),
     "arctic_ray_scene_info": (_i32, [_vp, _vp]),
+    "arctic_ray_refit_info": (_i32, [_vp, _vp]),
+    "arctic_ray_scene_reset": (_i32, [_vp]),
+    "arctic_read_ray_structure": (_i32, [_vp, _vp, _u64, _vp, _u64]),
+    "arctic_refit_triangles": (_i32, [_vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _u64, _vp]),
     "arctic_version": (_i32, []),
     # include/arctic_dist.h: the multi-GPU exchange steps
     "arctic_comm_unique_id": (_i32, [_vp, _vp, _u64]),

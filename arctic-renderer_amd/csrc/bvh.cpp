@@ -6,6 +6,7 @@
 #include "../../include/arctic_hip.h"
 
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 
 namespace arctic {
@@ -130,12 +131,165 @@ uint64_t ray_world_triangles(const float *trs, const float *vertices14, uint32_t
         const uint32_t i[3] = {indices[3 * t], indices[3 * t + 1], indices[3 * t + 2]};
         if (!(i[0] < n_vertices && i[1] < n_vertices && i[2] < n_vertices)) continue;   // geometry.hip: load_indices
         for (int j = 0; j < 3; ++j) {
-            const float *s = vertices14 + (size_t)i[j] * 14;
-            for (int k = 0; k < 3; ++k) tris9.push_back(((trs[k] * s[0] + trs[4 + k] * s[1]) + trs[8 + k] * s[2]) + trs[12 + k] * 1.0f);   // geometry.hip: mat_vec
+            float w[3];
+            rq_world_vertex(trs, 4, vertices14 + (size_t)i[j] * 14, w);   // geometry.hip: mat_vec
+            tris9.insert(tris9.end(), w, w + 3);
         }
         prims.push_back((uint32_t)(first_prim + t));
     }
     return first_prim + n_triangles;
+}
+
+void ray_triangle_sources(uint32_t object, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, std::vector<RefitSource> &out) {
+    for (uint32_t t = 0; t < n_triangles; ++t) {
+        const uint32_t i[3] = {indices[3 * t], indices[3 * t + 1], indices[3 * t + 2]};
+        if (!(i[0] < n_vertices && i[1] < n_vertices && i[2] < n_vertices)) continue;   // (ray_world_triangles' rule)
+        out.push_back(RefitSource{object, i[0], i[1], i[2]});
+    }
+}
+
+namespace {
+// the part of bvh_validate that a refit relies on: indices only, no box (a refitted tree has empty boxes and dead slots)
+bool topology_ok(const Bvh &b) {
+    const uint64_t n = b.nodes.size(), n_tris = b.tris.size();
+    if (n > 0xFFFFFFFFull || n_tris > RAY_MAX_STORED) return false;
+    for (uint64_t i = 0; i < n; ++i) {
+        const RayNode &x = b.nodes[i];
+        if (!(i < x.skip && x.skip <= n)) return false;
+        const uint64_t count = x.leaf & 7u, first = x.leaf >> 3;
+        if (count) {
+            if (count > RAY_LEAF_MAX || first + count > n_tris || x.skip != i + 1) return false;
+        } else {
+            const uint64_t c0 = i + 1;
+            if (c0 >= x.skip) return false;
+            const uint64_t c1 = b.nodes[c0].skip;
+            if (!(c0 < c1 && c1 < x.skip) || b.nodes[c1].skip != x.skip) return false;
+        }
+    }
+    return true;
+}
+void put_box(RayNode &n, const RayBox &x) { for (int a = 0; a < 3; ++a) { n.bmin[a] = x.lo[a]; n.bmax[a] = x.hi[a]; } }
+RayBox get_box(const RayNode &n) { RayBox x; for (int a = 0; a < 3; ++a) { x.lo[a] = n.bmin[a]; x.hi[a] = n.bmax[a]; } return x; }
+}  // namespace
+
+bool bvh_refit(Bvh &b, const float *tris9_now, uint64_t n_now) {
+    if (!topology_ok(b)) return false;
+    for (const RayTri &t : b.tris) if (t.prim >= n_now) return false;
+    for (RayTri &t : b.tris) {
+        float p[9];
+        std::memcpy(p, tris9_now + 9 * (size_t)t.prim, sizeof p);
+        if (!rq_finite9(p)) for (float &x : p) x = rq_dead();
+        std::memcpy(t.p0, p, 12); std::memcpy(t.p1, p + 3, 12); std::memcpy(t.p2, p + 6, 12);
+    }
+    for (size_t i = b.nodes.size(); i-- > 0;) {   // depth-first order: a node's children stand behind it
+        RayNode &n = b.nodes[i];
+        RayBox box = rq_empty_box();
+        const uint32_t count = n.leaf & 7u, first = n.leaf >> 3;
+        if (count) {
+            for (uint32_t k = first; k < first + count; ++k) {
+                float p[9];
+                std::memcpy(p, b.tris[k].p0, 12); std::memcpy(p + 3, b.tris[k].p1, 12); std::memcpy(p + 6, b.tris[k].p2, 12);
+                if (rq_finite9(p)) rq_grow(box, rq_triangle_box(p));
+            }
+        } else {
+            rq_grow(box, get_box(b.nodes[i + 1]));
+            rq_grow(box, get_box(b.nodes[b.nodes[i + 1].skip]));
+        }
+        put_box(n, box);
+    }
+    return true;
+}
+
+// Stage 0 cuts the depth-first array into the maximal subtrees of at most 64 leaves; every later stage does the same to the tree that is left
+// when the roots written so far count as its leaves.  A task's nodes need not be contiguous (they are in stage 0), so they are listed.
+void refit_schedule(const Bvh &b, RefitSchedule &out) {
+    out = RefitSchedule{};
+    const uint32_t n = (uint32_t)b.nodes.size();
+    out.stage_first.push_back(0);
+    if (n == 0) return;
+    std::vector<char> is_input(n, 0);      // a leaf of the tree this stage looks at
+    for (uint32_t i = 0; i < n; ++i) is_input[i] = (b.nodes[i].leaf & 7u) != 0;
+    std::vector<uint32_t> width(n), local(n), height(n);
+    bool stage0 = true;
+    for (;;) {
+        // inputs below every node of the stage's tree (nodes behind an input's subtree root are never looked at)
+        for (uint32_t i = n; i-- > 0;) width[i] = is_input[i] ? 1u : (b.nodes[i].leaf & 7u) ? 0u : width[i + 1] + width[b.nodes[i + 1].skip];
+        std::vector<uint32_t> roots;
+        for (uint32_t i = 0; i < n;) {
+            if (width[i] > REFIT_WAVE) { ++i; continue; }
+            roots.push_back(i);
+            if (stage0 || !is_input[i]) {   // (an input that stands alone has been written already: no task)
+                const size_t base = out.head.size() * REFIT_WAVE;
+                out.inputs.resize(base + REFIT_WAVE, 0u);
+                out.interior.resize(base + REFIT_WAVE, RefitInterior{0u, 0u});
+                uint32_t n_in = 0, n_int = 0, heights = 0;
+                std::vector<uint32_t> inner;
+                for (uint32_t j = i; j < b.nodes[i].skip;) {
+                    if (is_input[j]) { local[j] = n_in; height[j] = 0; out.inputs[base + n_in++] = j; j = b.nodes[j].skip; }
+                    else { inner.push_back(j); ++j; }
+                }
+                for (uint32_t j : inner) local[j] = n_in + n_int++;
+                for (size_t k = inner.size(); k-- > 0;) {   // children first
+                    const uint32_t j = inner[k], c0 = j + 1, c1 = b.nodes[c0].skip;
+                    height[j] = 1 + std::max(height[c0], height[c1]);
+                    heights = std::max(heights, height[j]);
+                    out.interior[base + (local[j] - n_in)] = RefitInterior{j, local[c0] | local[c1] << 8 | height[j] << 16};
+                }
+                out.head.push_back(n_in | n_int << 8 | heights << 16);
+            }
+            i = b.nodes[i].skip;
+        }
+        out.stage_first.push_back((uint32_t)out.head.size());
+        if (roots.size() == 1 && roots[0] == 0) break;
+        std::fill(is_input.begin(), is_input.end(), 0);
+        for (uint32_t r : roots) is_input[r] = 1;
+        stage0 = false;
+    }
+}
+
+bool refit_schedule_validate(const Bvh &b, const RefitSchedule &s) {
+    const uint32_t n = (uint32_t)b.nodes.size();
+    if (s.stage_first.empty() || s.stage_first[0] != 0 || s.stage_first.back() != s.head.size()) return false;
+    if (s.inputs.size() != s.head.size() * REFIT_WAVE || s.interior.size() != s.inputs.size()) return false;
+    if (n == 0) return s.head.empty();
+    std::vector<uint32_t> written(n, 0xFFFFFFFFu);   // the stage that writes each node
+    for (uint32_t st = 0; st + 1 < s.stage_first.size(); ++st) {
+        if (s.stage_first[st] > s.stage_first[st + 1]) return false;
+        for (uint32_t t = s.stage_first[st]; t < s.stage_first[st + 1]; ++t) {
+            const uint32_t n_in = s.head[t] & 255u, n_int = s.head[t] >> 8 & 255u, heights = s.head[t] >> 16;
+            if (n_in == 0 || n_in > REFIT_WAVE || n_int >= REFIT_WAVE || n_int + 1 != n_in || heights >= REFIT_WAVE) return false;
+            for (uint32_t l = 0; l < n_in; ++l) {
+                const uint32_t j = s.inputs[(size_t)t * REFIT_WAVE + l];
+                if (j >= n) return false;
+                if (st == 0) { if (!(b.nodes[j].leaf & 7u) || written[j] != 0xFFFFFFFFu) return false; written[j] = 0; }
+                else if (written[j] >= st) return false;   // (also: never written)
+            }
+            // interiors by height, so that a child's height is known before its parent's is checked
+            for (uint32_t h = 1; h <= heights; ++h)
+                for (uint32_t k = 0; k < n_int; ++k) {
+                    const RefitInterior &e = s.interior[(size_t)t * REFIT_WAVE + k];
+                    if ((e.link >> 16) != h) continue;
+                    const uint32_t a = e.link & 255u, c = e.link >> 8 & 255u;
+                    if (e.node >= n || (b.nodes[e.node].leaf & 7u) || written[e.node] != 0xFFFFFFFFu) return false;
+                    if (a >= n_in + n_int || c >= n_in + n_int || a == n_in + k || c == n_in + k) return false;
+                    // the children named are the node's children, and both are ready in an earlier round
+                    const uint32_t c0 = e.node + 1, c1 = b.nodes[c0].skip;
+                    const uint32_t node_a = a < n_in ? s.inputs[(size_t)t * REFIT_WAVE + a] : s.interior[(size_t)t * REFIT_WAVE + a - n_in].node;
+                    const uint32_t node_c = c < n_in ? s.inputs[(size_t)t * REFIT_WAVE + c] : s.interior[(size_t)t * REFIT_WAVE + c - n_in].node;
+                    if (node_a != c0 || node_c != c1) return false;
+                    const uint32_t ha = a < n_in ? 0u : s.interior[(size_t)t * REFIT_WAVE + a - n_in].link >> 16;
+                    const uint32_t hc = c < n_in ? 0u : s.interior[(size_t)t * REFIT_WAVE + c - n_in].link >> 16;
+                    if (ha >= h || hc >= h) return false;
+                    written[e.node] = st;
+                }
+            for (uint32_t k = 0; k < n_int; ++k) {
+                const uint32_t h = s.interior[(size_t)t * REFIT_WAVE + k].link >> 16;
+                if (h == 0 || h > heights) return false;   // an interior outside every round would never be written
+            }
+        }
+    }
+    for (uint32_t i = 0; i < n; ++i) if (written[i] == 0xFFFFFFFFu) return false;
+    return true;
 }
 
 void bvh_trace_host(const Bvh &b, const RayIn *rays, uint64_t n, bool any, RayOut *hits, uint64_t *visits) {
@@ -168,6 +322,35 @@ void brute_trace_host(const float *tris9, uint64_t n_tris, const RayIn *rays, ui
 }
 
 }  // namespace arctic
+
+extern "C" int arctic_refit_triangles(const float *tris9_build, const float *tris9_now, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits,
+                                      ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap, uint64_t *counts2) {
+    using namespace arctic;
+    static_assert(sizeof(ArcticRayNode) == sizeof(RayNode) && sizeof(ArcticRayTri) == sizeof(RayTri), "the public records are the internal ones");
+    static_assert(offsetof(ArcticRayNode, skip) == offsetof(RayNode, skip) && offsetof(ArcticRayNode, bmax) == offsetof(RayNode, bmax) && offsetof(ArcticRayNode, leaf) == offsetof(RayNode, leaf), "node layout");
+    static_assert(offsetof(ArcticRayTri, p1) == offsetof(RayTri, p1) && offsetof(ArcticRayTri, p2) == offsetof(RayTri, p2) && offsetof(ArcticRayTri, prim) == offsetof(RayTri, prim), "triangle layout");
+    if ((flags & ~(ARCTIC_TRACE_ANY | ARCTIC_TRACE_BRUTE)) || (n_tris && (!tris9_build || !tris9_now)) || (n && (!rays || !hits))) return ARCTIC_E_INVALID;
+    if (n_tris > 0xFFFFFFFEull) return ARCTIC_E_CAPACITY;
+    Bvh b;
+    if (!bvh_build(tris9_build, n_tris, nullptr, b)) return ARCTIC_E_CAPACITY;
+    if (!bvh_validate(b)) return ARCTIC_E_INVALID;
+    // the schedule decides nothing about the result; it is made and checked here so that the host arbiter exercises what the device relies on
+    RefitSchedule sched;
+    refit_schedule(b, sched);
+    if (!refit_schedule_validate(b, sched)) return ARCTIC_E_INVALID;
+    if ((nodes && node_cap < b.nodes.size()) || (tris && tri_cap < b.tris.size())) return ARCTIC_E_CAPACITY;
+    if (!bvh_refit(b, tris9_now, n_tris)) return ARCTIC_E_INVALID;
+    std::vector<RayIn> in(n);
+    std::vector<RayOut> out(n);
+    if (n) std::memcpy(static_cast<void *>(in.data()), rays, n * sizeof(RayIn));
+    if (flags & ARCTIC_TRACE_BRUTE) brute_trace_host(tris9_now, n_tris, in.data(), n, (flags & ARCTIC_TRACE_ANY) != 0, out.data());
+    else bvh_trace_host(b, in.data(), n, (flags & ARCTIC_TRACE_ANY) != 0, out.data(), nullptr);
+    if (n) std::memcpy(static_cast<void *>(hits), out.data(), n * sizeof(RayOut));
+    if (nodes && !b.nodes.empty()) std::memcpy(static_cast<void *>(nodes), b.nodes.data(), b.nodes.size() * sizeof(RayNode));
+    if (tris && !b.tris.empty()) std::memcpy(static_cast<void *>(tris), b.tris.data(), b.tris.size() * sizeof(RayTri));
+    if (counts2) { counts2[0] = b.nodes.size(); counts2[1] = b.tris.size(); }
+    return ARCTIC_OK;
+}
 
 extern "C" int arctic_trace_triangles(const float *tris9, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits) {
     using namespace arctic;

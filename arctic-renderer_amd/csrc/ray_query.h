@@ -103,6 +103,47 @@ RQ_HD bool rq_finite9(const float *p) {
     return ok;
 }
 
+// A world vertex, exactly as defined (and as geometry.hip's mat_vec writes attributes 11..13): m holds the matrix's columns `col` floats apart
+// (an object's trs: 4; the refit's per-object record, which keeps the 12 floats in use: 3), s = the vertex's position
+RQ_HD void rq_world_vertex(const float *m, int col, const float *s, float *out) {
+    for (int k = 0; k < 3; ++k) out[k] = ((m[k] * s[0] + m[col + k] * s[1]) + m[2 * col + k] * s[2]) + m[3 * col + k] * 1.0f;
+}
+
+// ---- refit (include/arctic_hip.h: "a refitted structure") ------------------------------------------------------------------------------------
+// A DEAD slot: nine quiet NaNs.  rq_triangle never reports it, whatever the ray:
+//   some d[a] == 0: rq_axis compares bmin <= o && o <= bmax with bmin = bmax = NaN -- false, the box is missed;
+//   every d[a] != 0: l and h are NaN on every axis, which rq_axis reads as "no constraint", so the box IS met with (-inf, +inf) -- but then
+//     e1 = e2 = NaN, det = NaN, u = NaN, and `det != 0 && u >= 0 && ...` is false because u >= 0 is false for a NaN: a miss.
+constexpr uint32_t RQ_DEAD_BITS = 0x7FC00000u;
+RQ_HD float rq_dead() { return __builtin_bit_cast(float, RQ_DEAD_BITS); }
+// The EMPTY box {+inf, -inf} is the identity of the union below (rq_min(+inf, x) = x, rq_max(-inf, x) = x for every finite x).  Under rq_node it is
+// never pruned: lo - o = +inf and hi - o = -inf, times a factor that is never zero (a valid ray has no infinite d) and never NaN, give {+inf, -inf}
+// in some order on every axis -- also for d == 0, whose factor is +inf --, so every axis contributes (-inf, +inf).  The walk then descends into a
+// subtree that holds dead slots only: time, never a result.
+struct RayBox { float lo[3], hi[3]; };
+RQ_HD RayBox rq_empty_box() { RayBox b; for (int a = 0; a < 3; ++a) { b.lo[a] = rq_inf(); b.hi[a] = -rq_inf(); } return b; }
+RQ_HD void rq_grow(RayBox &b, const RayBox &c) { for (int a = 0; a < 3; ++a) { b.lo[a] = rq_min(b.lo[a], c.lo[a]); b.hi[a] = rq_max(b.hi[a], c.hi[a]); } }
+RQ_HD RayBox rq_triangle_box(const float *p) {   // p: nine finite floats
+    RayBox b;
+    for (int a = 0; a < 3; ++a) { b.lo[a] = rq_min(rq_min(p[a], p[3 + a]), p[6 + a]); b.hi[a] = rq_max(rq_max(p[a], p[3 + a]), p[6 + a]); }
+    return b;
+}
+// The refit's SCHEDULE: tasks of one wave each, in stages; a stage reads only what earlier stages (earlier launches) wrote.  A task owns up to 64
+// INPUT nodes -- stage 0: leaves, whose boxes it forms from their slots; later stages: the roots earlier tasks wrote -- and the up to 63 interior
+// nodes that join them under one root.  Inside the task a node is a local number: input l is l, interior k is n_in + k.  Lane l takes input l,
+// lane k interior k, in the round of its height (1 + the larger of its children's; inputs have height 0).
+constexpr uint32_t REFIT_WAVE = 64;
+struct RefitInterior { uint32_t node; uint32_t link; };   // link = local number of child 0 | child 1 << 8 | height << 16
+struct RefitSchedule {
+    std::vector<uint32_t> head;          // per task: n_in | n_int << 8 | heights << 16
+    std::vector<uint32_t> inputs;        // REFIT_WAVE per task (unused entries: 0)
+    std::vector<RefitInterior> interior; // REFIT_WAVE per task
+    std::vector<uint32_t> stage_first;   // task index where each stage begins, and the task count behind the last
+    uint32_t stages() const { return stage_first.empty() ? 0u : (uint32_t)stage_first.size() - 1; }
+};
+// where a stored slot's vertices come from: the object (the scene's objects order) and the three vertex indices of its mesh
+struct RefitSource { uint32_t object, i0, i1, i2; };
+
 // The NODE test.  It only has to be CONSERVATIVE: true whenever the node's box, by the definition, is met with
 // max(tn, t_min) <= min(tf, t_max, t_best) -- a needless visit costs time, never a result.  So it may use the hardware's min / max (which differ
 // from the defined ones in the sign of a zero only), takes d == 0 as a reciprocal of +inf (a box the origin is outside of then gives an
@@ -158,6 +199,17 @@ RQ_HD RayOut rq_walk(const RayPrep &r, const RayNode *nodes, const RayTri *tris,
     return best;
 }
 
+// what a refit uploads per object: the 12 floats of its trs in use (column c at m[3 c]) and the mesh's vertices in use (14 floats per vertex)
+struct alignas(16) RefitObject { float m[12]; const float *vertices; uint32_t n_vertices, pad; };
+static_assert(sizeof(RefitObject) == 64, "refit object record");
+#if defined(__HIPCC__)
+// ray_refit.hip.  T: the device copies of a RefitSchedule's tables and of the slots' sources; stage_first: the HOST's array of n_stages + 1 task
+// indices.  One launch per stage that has a task, in stream order on s; *launches: how many
+struct RefitTablesDev { const uint32_t *head, *inputs; const RefitInterior *interior; const RefitSource *src; };
+hipError_t launch_ray_refit(const RefitTablesDev &T, const uint32_t *stage_first, uint32_t n_stages, void *nodes, uint32_t n_nodes, void *tris, uint32_t n_slots,
+                            const RefitObject *objs, uint32_t n_objs, hipStream_t s, uint32_t *launches);
+#endif
+
 // ---- host side (bvh.cpp) ---------------------------------------------------------------------------------------------------------------------
 struct Bvh {
     std::vector<RayNode> nodes;
@@ -175,5 +227,14 @@ uint64_t ray_world_triangles(const float *trs, const float *vertices14, uint32_t
                              std::vector<float> &tris9, std::vector<uint32_t> &prims);
 void bvh_trace_host(const Bvh &b, const RayIn *rays, uint64_t n, bool any, RayOut *hits, uint64_t *visits /* 2, or null */);
 void brute_trace_host(const float *tris9, uint64_t n_tris, const RayIn *rays, uint64_t n, bool any, RayOut *hits);
+// ray_world_triangles' bookkeeping for a refit: the source of every triangle it kept, in its order
+void ray_triangle_sources(uint32_t object, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, std::vector<RefitSource> &out);
+// The definition of a refitted structure, on the host, for a tree whose prims are array indices: slot k takes the triangle tris9_now[9 * prim]
+// (dead when not finite), leaf boxes the union of their live slots, interior boxes the union of their children, topology untouched.
+// false (nothing written): a prim at or above n_now, or a tree that fails the topology part of bvh_validate
+bool bvh_refit(Bvh &b, const float *tris9_now, uint64_t n_now);
+// the schedule for b's topology and its check: every node written exactly once, every input written in an earlier stage, every number in range
+void refit_schedule(const Bvh &b, RefitSchedule &out);
+bool refit_schedule_validate(const Bvh &b, const RefitSchedule &s);
 
 }  // namespace arctic

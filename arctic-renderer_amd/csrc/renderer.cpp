@@ -406,6 +406,22 @@ struct ArcticRenderer {
         bool built = false;
         uint64_t n_tris = 0, n_nodes = 0, builds = 0, depth = 0;
         DevBuf d_nodes, d_tris, d_rays, d_hits, d_mask;
+        // ARCTIC_OPT_RAY_REFIT (ray_refit.hip; the definition: include/arctic_hip.h, "a refitted structure").  A full build under the option also
+        // uploads the slots' sources and the refit's schedule (checked on the host first); while `refittable`, a change of the key that keeps the
+        // objects' meshes (built_meshes) is followed on the device: a per-object table through a ring of pinned buffers, then one launch per stage,
+        // all in stream order -- no synchronisation, nothing read back.  Nothing below is allocated while the option is 0
+        int refit_opt = 0;
+        bool refittable = false;
+        uint64_t refits = 0, refit_launches = 0;
+        std::vector<uint64_t> built_meshes;        // every object's mesh_idx at the build
+        std::vector<uint32_t> stage_first;         // RefitSchedule::stage_first of the build
+        DevBuf d_src, d_head, d_inputs, d_interior, d_objs;
+        static constexpr int OBJ_RING = 3;
+        RefitObject *h_objs[OBJ_RING] = {nullptr, nullptr, nullptr};
+        size_t h_objs_cap[OBJ_RING] = {0, 0, 0};
+        hipEvent_t ev_objs[OBJ_RING] = {nullptr, nullptr, nullptr};
+        bool objs_pending[OBJ_RING] = {false, false, false};
+        int objs_turn = 0;
     } ray;
     uint32_t *dh_counts = nullptr;  // the device's address of h_counts
     uint32_t *h_counts = nullptr;   // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
@@ -1194,7 +1210,11 @@ void arctic_destroy(ArcticRenderer *r) {
                       &r->geo[1].d_recs, &r->geo[1].d_rrecs, &r->geo[1].d_clip_list, &r->geo[1].d_rec_of, &r->geo[1].d_items, &r->geo[0].d_left, &r->geo[1].d_left, &r->geo[2].d_left, &r->geo[0].d_bin_count, &r->geo[0].d_bin_slots, &r->geo[1].d_bin_count, &r->geo[1].d_bin_slots, &r->geo[2].d_bin_count, &r->geo[2].d_bin_slots, &r->d_geo_counters, &r->d_stage, &r->tables[0].d, &r->tables[1].d};
     for (PassTables &T : r->tables) { if (T.h) (void)hipHostFree(T.h); if (T.copied) (void)hipEventDestroy(T.copied); }
     for (DevBuf *b : bufs) b->release();
-    for (DevBuf *b : {&r->ray.d_nodes, &r->ray.d_tris, &r->ray.d_rays, &r->ray.d_hits, &r->ray.d_mask}) b->release();
+    for (DevBuf *b : {&r->ray.d_nodes, &r->ray.d_tris, &r->ray.d_rays, &r->ray.d_hits, &r->ray.d_mask, &r->ray.d_src, &r->ray.d_head, &r->ray.d_inputs, &r->ray.d_interior, &r->ray.d_objs}) b->release();
+    for (int k = 0; k < ArcticRenderer::RayScene::OBJ_RING; ++k) {
+        if (r->ray.h_objs[k]) (void)hipHostFree(r->ray.h_objs[k]);
+        if (r->ray.ev_objs[k]) (void)hipEventDestroy(r->ray.ev_objs[k]);
+    }
     delete r;
 }
 
@@ -2378,6 +2398,10 @@ int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
         r->env_lighting = (int)value;
         if (r->env_lighting == 1 && r->env_w && !r->env_built) { int rc = select_device(r); if (rc) return rc; return build_env_tables(r); }
         break;
+    case ARCTIC_OPT_RAY_REFIT:
+        if (value < 0 || value > 1) return r->fail(ARCTIC_E_INVALID, "ARCTIC_OPT_RAY_REFIT: 0 or 1");
+        r->ray.refit_opt = (int)value;   // (in force from the next full build on: a structure built under 0 is not refittable)
+        break;
     default: return r->fail(ARCTIC_E_INVALID, "set_option: unknown option %u", option);
     }
     return ARCTIC_OK;
@@ -2397,11 +2421,61 @@ void ray_inputs(const ArcticRenderer *r, const ArcticScene *sc, std::vector<uint
     }
 }
 
-// the structure for `sc`, resident on the device: built, validated and uploaded when its inputs changed.  Synchronous (it reads the meshes back).
+// may the cached structure follow `sc` by a refit?  Host state only (include/arctic_hip.h: "Eligibility")
+bool ray_refit_eligible(const ArcticRenderer *r, const ArcticScene *sc) {
+    const ArcticRenderer::RayScene &R = r->ray;
+    if (!R.built || !R.refittable || sc->n_objects != R.built_meshes.size()) return false;
+    for (uint64_t i = 0; i < sc->n_objects; ++i)
+        if (sc->objects[i].mesh_idx != R.built_meshes[i] || sc->objects[i].mesh_idx >= r->meshes.size()) return false;
+    return true;
+}
+
+// the refit: the per-object table (trs and vertices in use NOW) through the ring, then the stages.  Everything is enqueued on the handle's stream,
+// behind the k_morph / k_skin that wrote the vertices and behind the queries that still walk the structure in place; nothing waits for the device
+// (the ring's event is that of the copy OBJ_RING refits ago)
+int refit_ray_scene(ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_t> &key) {
+    ArcticRenderer::RayScene &R = r->ray;
+    const size_t n_obj = (size_t)sc->n_objects, bytes = std::max<size_t>(n_obj, 1) * sizeof(RefitObject);
+    const int slot = R.objs_turn;
+    if (R.objs_pending[slot]) { HIPCHECK(r, hipEventSynchronize(R.ev_objs[slot])); R.objs_pending[slot] = false; }
+    if (R.h_objs_cap[slot] < bytes) {
+        if (R.h_objs[slot]) { (void)hipHostFree(R.h_objs[slot]); R.h_objs[slot] = nullptr; R.h_objs_cap[slot] = 0; }
+        HIPCHECK(r, hipHostMalloc((void **)&R.h_objs[slot], bytes));
+        R.h_objs_cap[slot] = bytes;
+    }
+    if (!R.ev_objs[slot]) HIPCHECK(r, hipEventCreateWithFlags(&R.ev_objs[slot], hipEventDisableTiming));
+    for (size_t i = 0; i < n_obj; ++i) {
+        const ArcticObject &o = sc->objects[i];
+        const Mesh &m = r->meshes[o.mesh_idx];   // (ray_refit_eligible: it exists)
+        RefitObject &d = R.h_objs[slot][i];
+        for (int c = 0; c < 4; ++c) for (int k = 0; k < 3; ++k) d.m[3 * c + k] = o.trs[4 * c + k];
+        d.vertices = m.vertices_in_use(); d.n_vertices = m.n_vertices; d.pad = 0;
+    }
+    R.objs_turn = (slot + 1) % ArcticRenderer::RayScene::OBJ_RING;
+    if (n_obj) {
+        HIPCHECK(r, hipMemcpyAsync(R.d_objs.p, R.h_objs[slot], n_obj * sizeof(RefitObject), hipMemcpyHostToDevice, r->stream));
+        HIPCHECK(r, hipEventRecord(R.ev_objs[slot], r->stream));
+        R.objs_pending[slot] = true;
+    }
+    const RefitTablesDev T = {R.d_head.as<uint32_t>(), R.d_inputs.as<uint32_t>(), R.d_interior.as<RefitInterior>(), R.d_src.as<RefitSource>()};
+    uint32_t launches = 0;
+    const hipError_t e = launch_ray_refit(T, R.stage_first.data(), (uint32_t)R.stage_first.size() - 1, R.d_nodes.p, (uint32_t)R.n_nodes, R.d_tris.p, (uint32_t)R.n_tris,
+                                          R.d_objs.as<RefitObject>(), (uint32_t)n_obj, r->stream, &launches);
+    if (e != hipSuccess) { R.built = false; HIPCHECK(r, e); }   // (some stages may have run: the structure is dropped, the next query builds)
+    R.key.swap(key);
+    ++R.refits; R.refit_launches = launches;
+    return ARCTIC_OK;
+}
+
+// the structure for `sc`, resident on the device: built, validated and uploaded when its inputs changed (synchronous: it reads the meshes back) -- or,
+// under ARCTIC_OPT_RAY_REFIT, refitted in stream order when only the geometry moved.
 int ensure_ray_scene(ArcticRenderer *r, const ArcticScene *sc) {
     std::vector<uint8_t> key;
     ray_inputs(r, sc, key);
     if (r->ray.built && key == r->ray.key) return ARCTIC_OK;
+    if (ray_refit_eligible(r, sc)) return refit_ray_scene(r, sc, key);
+    const bool with_refit = r->ray.refit_opt == 1;
+    std::vector<RefitSource> sources;
     // the vertices in use are written by k_morph / k_skin on the main stream; the structure in place may still be read by a query on it
     HIPCHECK(r, hipStreamSynchronize(r->stream));
     std::vector<float> tris9;
@@ -2420,12 +2494,47 @@ int ensure_ray_scene(ArcticRenderer *r, const ArcticScene *sc) {
             HIPCHECK(r, hipMemcpy(inds[o.mesh_idx].data(), m.d_indices, (size_t)m.n_indices * 4, hipMemcpyDeviceToHost));
         }
         prim = ray_world_triangles(o.trs, verts[o.mesh_idx].data(), m.n_vertices, inds[o.mesh_idx].data(), m.n_indices / 3, prim, tris9, prims);
+        if (with_refit) ray_triangle_sources((uint32_t)i, m.n_vertices, inds[o.mesh_idx].data(), m.n_indices / 3, sources);
     }
     Bvh b;
     if (!bvh_build(tris9.data(), prims.size(), prims.data(), b))
         return r->fail(ARCTIC_E_CAPACITY, "ray queries: %llu triangles to store, the structure holds 2^29 - 1", (unsigned long long)prims.size());
     if (!bvh_validate(b)) return r->fail(ARCTIC_E_INVALID, "internal: the ray structure failed its validation (%zu nodes, %zu triangles); nothing was uploaded", b.nodes.size(), b.tris.size());
-    r->ray.built = false;
+    // Refittable: built under the option, no in-range triangle left out for being non-finite (it would have no slot to come back to), every
+    // object's mesh there, and an object index that fits the source records.  The tables: where every stored slot's vertices come from -- copied
+    // from the index buffers read above, found by the slot's prim (ascending in `prims`) -- and the schedule; both checked before anything is uploaded
+    bool refittable = with_refit && b.tris.size() == prims.size() && sources.size() == prims.size() && sc->n_objects <= 0xFFFFFFFFull;
+    for (uint64_t i = 0; refittable && i < sc->n_objects; ++i) refittable = sc->objects[i].mesh_idx < r->meshes.size();
+    std::vector<RefitSource> slot_src;
+    RefitSchedule sched;
+    if (refittable) {
+        slot_src.resize(b.tris.size());
+        for (size_t k = 0; k < b.tris.size(); ++k) {
+            const auto it = std::lower_bound(prims.begin(), prims.end(), b.tris[k].prim);
+            if (it == prims.end() || *it != b.tris[k].prim) return r->fail(ARCTIC_E_INVALID, "internal: a stored triangle's prim %u is not one of the scene's", b.tris[k].prim);
+            const RefitSource &s = slot_src[k] = sources[(size_t)(it - prims.begin())];
+            const uint32_t nv = s.object < sc->n_objects ? r->meshes[sc->objects[s.object].mesh_idx].n_vertices : 0u;
+            if (!(s.i0 < nv && s.i1 < nv && s.i2 < nv)) return r->fail(ARCTIC_E_INVALID, "internal: the refit's source record %zu is out of range; nothing was uploaded", k);
+        }
+        refit_schedule(b, sched);
+        if (!refit_schedule_validate(b, sched)) return r->fail(ARCTIC_E_INVALID, "internal: the refit's schedule failed its validation (%zu nodes, %zu tasks); nothing was uploaded", b.nodes.size(), sched.head.size());
+    }
+    r->ray.built = false; r->ray.refittable = false;
+    if (refittable) {
+        const auto upload = [&](DevBuf &d, const void *p, size_t bytes) -> hipError_t {
+            hipError_t e = d.ensure(std::max<size_t>(bytes, 16));
+            if (e == hipSuccess && bytes) e = hipMemcpy(d.p, p, bytes, hipMemcpyHostToDevice);
+            return e;
+        };
+        HIPCHECK(r, upload(r->ray.d_src, slot_src.data(), slot_src.size() * sizeof(RefitSource)));
+        HIPCHECK(r, upload(r->ray.d_head, sched.head.data(), sched.head.size() * sizeof(uint32_t)));
+        HIPCHECK(r, upload(r->ray.d_inputs, sched.inputs.data(), sched.inputs.size() * sizeof(uint32_t)));
+        HIPCHECK(r, upload(r->ray.d_interior, sched.interior.data(), sched.interior.size() * sizeof(RefitInterior)));
+        HIPCHECK(r, r->ray.d_objs.ensure(std::max<size_t>((size_t)sc->n_objects, 1) * sizeof(RefitObject)));
+        r->ray.stage_first = sched.stage_first;
+        r->ray.built_meshes.resize((size_t)sc->n_objects);
+        for (uint64_t i = 0; i < sc->n_objects; ++i) r->ray.built_meshes[(size_t)i] = sc->objects[i].mesh_idx;
+    }
     HIPCHECK(r, r->ray.d_nodes.ensure(std::max<size_t>(sizeof(RayNode), b.nodes.size() * sizeof(RayNode))));
     HIPCHECK(r, r->ray.d_tris.ensure(std::max<size_t>(sizeof(RayTri), b.tris.size() * sizeof(RayTri))));
     if (!b.nodes.empty()) HIPCHECK(r, hipMemcpy(r->ray.d_nodes.p, b.nodes.data(), b.nodes.size() * sizeof(RayNode), hipMemcpyHostToDevice));
@@ -2433,7 +2542,7 @@ int ensure_ray_scene(ArcticRenderer *r, const ArcticScene *sc) {
     r->ray.key.swap(key);
     r->ray.n_tris = b.tris.size(); r->ray.n_nodes = b.nodes.size(); r->ray.depth = b.depth;
     ++r->ray.builds;
-    r->ray.built = true;
+    r->ray.built = true; r->ray.refittable = refittable;
     return ARCTIC_OK;
 }
 
@@ -2501,6 +2610,33 @@ int arctic_ray_scene_info(ArcticRenderer *r, uint64_t *out4) {
     if (!r) return ARCTIC_E_INVALID;
     if (!out4) return r->fail(ARCTIC_E_INVALID, "ray_scene_info: null");
     out4[0] = r->ray.n_tris; out4[1] = r->ray.n_nodes; out4[2] = r->ray.builds; out4[3] = r->ray.depth;
+    return ARCTIC_OK;
+}
+
+int arctic_ray_refit_info(ArcticRenderer *r, uint64_t *out4) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!out4) return r->fail(ARCTIC_E_INVALID, "ray_refit_info: null");
+    out4[0] = r->ray.refits; out4[1] = r->ray.built && r->ray.refittable ? 1 : 0; out4[2] = r->ray.refit_launches; out4[3] = 0;
+    return ARCTIC_OK;
+}
+
+int arctic_ray_scene_reset(ArcticRenderer *r) {
+    if (!r) return ARCTIC_E_INVALID;
+    r->ray.built = false; r->ray.refittable = false; r->ray.key.clear();   // (the buffers stay: a query in flight may still walk them, and the build reuses them)
+    return ARCTIC_OK;
+}
+
+int arctic_read_ray_structure(ArcticRenderer *r, ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap) {
+    if (!r) return ARCTIC_E_INVALID;
+    static_assert(sizeof(ArcticRayNode) == sizeof(RayNode) && sizeof(ArcticRayTri) == sizeof(RayTri), "the public records are the internal ones");
+    if (!r->ray.built) return r->fail(ARCTIC_E_STATE, "read_ray_structure: no structure (a query builds it)");
+    if ((nodes && node_cap < r->ray.n_nodes) || (tris && tri_cap < r->ray.n_tris))
+        return r->fail(ARCTIC_E_CAPACITY, "read_ray_structure: %llu nodes and %llu triangles", (unsigned long long)r->ray.n_nodes, (unsigned long long)r->ray.n_tris);
+    int rc = select_device(r);
+    if (rc) return rc;
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    if (nodes && r->ray.n_nodes) HIPCHECK(r, hipMemcpy(nodes, r->ray.d_nodes.p, r->ray.n_nodes * sizeof(RayNode), hipMemcpyDeviceToHost));
+    if (tris && r->ray.n_tris) HIPCHECK(r, hipMemcpy(tris, r->ray.d_tris.p, r->ray.n_tris * sizeof(RayTri), hipMemcpyDeviceToHost));
     return ARCTIC_OK;
 }
 

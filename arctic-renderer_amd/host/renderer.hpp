@@ -229,6 +229,19 @@ class Renderer {
     // one any-hit ray per pixel of the resident G-buffer towards the sun: mask = rows x width bytes, 255 = lit or no geometry, 0 = occluded
     [[nodiscard]] bool trace_sun_visibility(const ArcticScene &scene, float bias, uint8_t *mask) { return ok(arctic_trace_sun_visibility(m_handle, &scene, bias, mask)); }
     [[nodiscard]] bool ray_scene_info(uint64_t out4[4]) { return ok(arctic_ray_scene_info(m_handle, out4)); }
+    // ARCTIC_OPT_RAY_REFIT = 1 (set_option): a moved object, a new pose or new weights are followed by a refit of the cached structure on the device, in
+    // stream order, instead of a synchronous rebuild.  out4 = {refits, refittable, launches of the latest refit, 0}; ray_scene_reset drops the
+    // structure so that the next query builds in full -- the remedy once the walk of a refitted tree has become slow
+    [[nodiscard]] bool ray_refit_info(uint64_t out4[4]) { return ok(arctic_ray_refit_info(m_handle, out4)); }
+    [[nodiscard]] bool ray_scene_reset() { return ok(arctic_ray_scene_reset(m_handle)); }
+    [[nodiscard]] bool read_ray_structure(ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap) {
+        return ok(arctic_read_ray_structure(m_handle, nodes, node_cap, tris, tri_cap));
+    }
+    // the refit's host arbiter: build on tris9_build, refit to tris9_now, walk; optionally the refitted structure (no handle, no GPU)
+    [[nodiscard]] static bool refit_triangles(const float *tris9_build, const float *tris9_now, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits,
+                                              ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap, uint64_t *counts2) {
+        return arctic_refit_triangles(tris9_build, tris9_now, n_tris, rays, n, flags, hits, nodes, node_cap, tris, tri_cap, counts2) == ARCTIC_OK;
+    }
     // the host arbiter: world-space triangles of 9 floats, prim = the array index; ARCTIC_TRACE_BRUTE loops over every triangle (no handle, no GPU)
     [[nodiscard]] static bool trace_triangles(const float *tris9, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits) {
         return arctic_trace_triangles(tris9, n_tris, rays, n, flags, hits) == ARCTIC_OK;

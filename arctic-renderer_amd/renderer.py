@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (HIT_DTYPE, RAY_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -225,6 +225,23 @@ class Renderer:
         out = np.zeros(4, np.uint64)
         self._check(self.L.arctic_ray_scene_info(self.h, _ptr(out)))
         return tuple(int(x) for x in out)
+
+    def ray_refit_info(self):
+        """(refits so far, 1 if the cached structure can be refitted, kernel launches of the latest refit, 0): set_option("ray_refit", 1)"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_ray_refit_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    def ray_scene_reset(self):
+        """drop the cached structure: the next query builds in full (a refitted tree that drifted far from the pose it was split for)"""
+        self._check(self.L.arctic_ray_scene_reset(self.h))
+
+    def read_ray_structure(self):
+        """the device's structure as it stands: (RAY_NODE_DTYPE nodes, RAY_TRI_DTYPE leaf triangles).  Synchronises; for tests"""
+        stored, n_nodes, _, _ = self.ray_scene_info()
+        nodes, tris = np.zeros(n_nodes, RAY_NODE_DTYPE), np.zeros(stored, RAY_TRI_DTYPE)
+        self._check(self.L.arctic_read_ray_structure(self.h, _ptr(nodes) if n_nodes else None, n_nodes, _ptr(tris) if stored else None, stored))
+        return nodes, tris
 
     def create_hdri(self, rgba32f):
         a = np.ascontiguousarray(rgba32f, dtype=np.float32)
@@ -501,6 +518,25 @@ def morph_vertices(vertices, deltas, weights):
     if rc < 0:
         raise ArcticError(rc, "morph_vertices: invalid deltas or weights")
     return out
+
+
+def refit_triangles(triangles_build, triangles_now, rays, any_hit=False, brute=False, structure=False):
+    """arctic_refit_triangles: the refit of include/arctic_hip.h on the host -- a structure built on triangles_build, refitted to triangles_now (the
+    same count, prim = the array index), walked: HIT_DTYPE records; structure=True: (hits, RAY_NODE_DTYPE nodes, RAY_TRI_DTYPE leaf triangles)."""
+    a = np.ascontiguousarray(triangles_build, dtype=np.float32).reshape(-1, 9)
+    b = np.ascontiguousarray(triangles_now, dtype=np.float32).reshape(-1, 9)
+    if len(a) != len(b):
+        raise ValueError("refit_triangles: the two triangle lists differ in length")
+    ry = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
+    hits = np.empty(len(ry), HIT_DTYPE)
+    flags = (binding.TRACE_ANY if any_hit else 0) | (binding.TRACE_BRUTE if brute else 0)
+    cap = len(a) if structure else 0
+    nodes, tris, counts = np.zeros(2 * cap, RAY_NODE_DTYPE), np.zeros(cap, RAY_TRI_DTYPE), np.zeros(2, np.uint64)
+    rc = binding.lib().arctic_refit_triangles(_ptr(a) if len(a) else None, _ptr(b) if len(b) else None, len(a), _ptr(ry) if len(ry) else None, len(ry), flags,
+                                              _ptr(hits) if len(ry) else None, _ptr(nodes) if cap else None, len(nodes), _ptr(tris) if cap else None, len(tris), _ptr(counts))
+    if rc < 0:
+        raise ArcticError(rc, "refit_triangles")
+    return (hits, nodes[:int(counts[0])].copy(), tris[:int(counts[1])].copy()) if structure else hits
 
 
 def trace_triangles(triangles, rays, any_hit=False, brute=False):

@@ -37,6 +37,10 @@ assert MORPH_DELTA_DTYPE.itemsize == 48
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("t_min", "<f4"), ("direction", "<f4", 3), ("t_max", "<f4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4")])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 16
+# ArcticRayNode / ArcticRayTri: the ray structure's records as arctic_read_ray_structure and arctic_refit_triangles return them
+RAY_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("skip", "<u4"), ("bmax", "<f4", 3), ("leaf", "<u4")])
+RAY_TRI_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("p2", "<f4", 3), ("prim", "<u4"), ("pad", "<u4", 2)])
+assert RAY_NODE_DTYPE.itemsize == 32 and RAY_TRI_DTYPE.itemsize == 48
 
 
 def neutral_material_params(n=1):

@@ -833,6 +833,55 @@ int arctic_trace_triangles(const float *tris9, uint64_t n_tris, const ArcticRay 
 /* The cached structure: out4 = {triangles stored (those that can be hit), nodes, builds so far, depth (nodes on the longest path; 0: empty)}. */
 int arctic_ray_scene_info(ArcticRenderer *r, uint64_t *out4);
 
+/* ---- refit: the structure follows a scene that MOVES without being rebuilt ------------------------------------------------------------------------
+ * ARCTIC_OPT_RAY_REFIT = 1 (arctic_set_option; default 0: everything above, bit for bit and call for call; any other value: ARCTIC_E_INVALID).
+ * When the geometry moved and the topology stayed, the next query REFITS the cached structure on the device (ray_refit.hip) instead of building
+ * a new one on the host: in stream order on the handle's stream, without synchronising, without reading anything back.  By the paragraph on step 3
+ * a pruned walk equals the loop over every triangle for ANY tree whose boxes contain their triangles, so a refitted tree gives the same bits as a
+ * fresh one; only the speed of the walk can degrade, as the boxes of a tree split for another pose overlap more -- arctic_ray_scene_reset is the
+ * caller's remedy.
+ *
+ * A REFITTED STRUCTURE, defined:
+ * Topology.  The node count, every skip, every leaf word, the order of the slots (the stored triangle records) and every slot's prim are those
+ *   of the last full build.
+ * Slot contents.  Slot k holds the world vertices of its prim, by the formula above ("A world vertex is ...": the same operations, contraction
+ *   off) from the mesh's vertices in use NOW and the object's trs NOW.  If any of the nine floats is not finite the slot is DEAD: nine quiet NaNs
+ *   (0x7FC00000), prim kept.  A dead slot is never hit (the ray against triangle test as written: with a d[a] == 0 its box is missed because
+ *   bmin <= o is false for a NaN; with every d[a] != 0 the box is met with (-inf, +inf), but u is a NaN and u >= 0 is false).  It comes back to
+ *   life at the next refit whose vertices are finite again.
+ * Leaf boxes.  The union (min / max as defined above) of the boxes of the leaf's LIVE triangles; a leaf with none has the EMPTY box
+ *   bmin = +inf, bmax = -inf.
+ * Interior boxes.  The union of the two children's boxes; the empty box is the identity.  The node test only has to stay conservative, and on an
+ *   empty box it is: (+inf - o) and (-inf - o) times a reciprocal that is never zero and never a NaN (zero direction components count as
+ *   +inf) are +inf and -inf in some order, the interval (-inf, +inf) on every axis -- the node is visited, and holds dead slots only.
+ * Zero signs.  min / max of finite values are exact, so a box is the same VALUE in whatever order it is formed; the sign of a zero bound is not
+ *   defined.  Compare boxes by value, triangles by bytes.
+ * Eligibility, decided on the host without synchronising.  The next query refits when ALL hold: the option was 1 at the last full build; that
+ *   build left out no in-range triangle for being non-finite; n_objects and every object's mesh_idx equal that build's; every such mesh still
+ *   exists -- and anything else the structure depends on changed (a trs, a pose, weights).  In every other case it builds in full, as above.  A
+ *   structure built under option 0 is not refittable.  A refit does not count as a build in arctic_ray_scene_info. */
+#define ARCTIC_OPT_RAY_REFIT 7
+typedef struct ArcticRayNode { float bmin[3]; uint32_t skip; float bmax[3]; uint32_t leaf; } ArcticRayNode;                 /* 32 bytes */
+typedef struct ArcticRayTri { float p0[3], p1[3], p2[3]; uint32_t prim; uint32_t pad[2]; } ArcticRayTri;                    /* 48 bytes */
+
+/* out4 = {refits so far, 1 if the cached structure can be refitted, kernel launches of the latest refit, 0}. */
+int arctic_ray_refit_info(ArcticRenderer *r, uint64_t *out4);
+
+/* Drops the cached structure: the next query builds in full (under the option in force then).  For a refitted tree that has drifted far from
+ * the pose it was split for. */
+int arctic_ray_scene_reset(ArcticRenderer *r);
+
+/* The device's nodes and leaf triangles as they stand (for tests; synchronises).  Either pointer may be NULL; counts: arctic_ray_scene_info.
+ * ARCTIC_E_CAPACITY: too little room (nothing written).  ARCTIC_E_STATE: no structure. */
+int arctic_read_ray_structure(ArcticRenderer *r, ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap);
+
+/* The host arbiter of the refit (no handle, no GPU): builds on tris9_build, refits to tris9_now -- n_tris triangles each, prim = the array
+ * index -- by the definition above, walks the refitted tree, and optionally returns it (nodes / tris may be NULL; counts2, if given, receives
+ * {nodes, stored triangles}).  With ARCTIC_TRACE_BRUTE the hits come from the loop over every triangle of tris9_now instead of the walk.  Refuses what
+ * arctic_trace_triangles refuses, and ARCTIC_E_CAPACITY for too little room; a refused call writes nothing. */
+int arctic_refit_triangles(const float *tris9_build, const float *tris9_now, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits,
+                           ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap, uint64_t *counts2);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row
