@@ -200,6 +200,81 @@ bool bvh_refit(Bvh &b, const float *tris9_now, uint64_t n_now) {
     return true;
 }
 
+namespace {
+// is the tree the one Builder::build makes for its slot count?  Node i must cover slots [lo, hi): a leaf of exactly those when hi - lo <= 4, else
+// an interior node whose children cover the two halves.  Iterative, and every index is checked (topology_ok has passed)
+bool builder_topology(const Bvh &b) {
+    struct Item { uint64_t node, lo, hi; };
+    if (b.tris.empty()) return b.nodes.empty();
+    std::vector<Item> todo{{0, 0, b.tris.size()}};
+    uint64_t seen = 0;
+    while (!todo.empty()) {
+        const Item it = todo.back();
+        todo.pop_back();
+        if (it.node >= b.nodes.size()) return false;
+        const RayNode &x = b.nodes[it.node];
+        ++seen;
+        if (it.hi - it.lo <= RAY_LEAF_MAX) {
+            if ((x.leaf & 7u) != it.hi - it.lo || (x.leaf >> 3) != it.lo) return false;
+        } else {
+            if (x.leaf & 7u) return false;
+            const uint64_t mid = it.lo + (it.hi - it.lo) / 2;
+            todo.push_back({b.nodes[it.node + 1].skip, mid, it.hi});
+            todo.push_back({it.node + 1, it.lo, mid});
+        }
+    }
+    return seen == b.nodes.size();
+}
+
+struct SplitRef { float c[3]; uint32_t prim; bool dead; };
+}  // namespace
+
+bool bvh_resplit(Bvh &b, const float *tris9_now, uint64_t n_now) {
+    if (!topology_ok(b) || !builder_topology(b)) return false;
+    for (const RayTri &t : b.tris) if (t.prim >= n_now) return false;
+    std::vector<SplitRef> refs(b.tris.size());
+    for (size_t k = 0; k < refs.size(); ++k) {
+        SplitRef &r = refs[k];
+        r.prim = b.tris[k].prim;
+        const float *p = tris9_now + 9 * (size_t)r.prim;
+        r.dead = !rq_finite9(p);
+        if (r.dead) r.c[0] = r.c[1] = r.c[2] = 0.0f; else rq_centroid(p, r.c);
+    }
+    struct Seg { size_t lo, hi; };
+    std::vector<Seg> todo;
+    if (!refs.empty()) todo.push_back({0, refs.size()});
+    while (!todo.empty()) {
+        const Seg s = todo.back();
+        todo.pop_back();
+        if (s.hi - s.lo <= RAY_LEAF_MAX) {
+            std::sort(refs.begin() + s.lo, refs.begin() + s.hi, [](const SplitRef &x, const SplitRef &y) { return x.prim < y.prim; });
+            continue;
+        }
+        float cmin[3] = {0.0f, 0.0f, 0.0f}, cmax[3] = {0.0f, 0.0f, 0.0f};
+        bool any = false;
+        for (size_t k = s.lo; k < s.hi; ++k) {
+            if (refs[k].dead) continue;
+            for (int a = 0; a < 3; ++a) {
+                cmin[a] = any ? rq_min(cmin[a], refs[k].c[a]) : refs[k].c[a];
+                cmax[a] = any ? rq_max(cmax[a], refs[k].c[a]) : refs[k].c[a];
+            }
+            any = true;
+        }
+        const int axis = any ? rq_split_axis(cmin, cmax) : 0;
+        // the whole segment in the definition's order: live before dead, then the centroid under < (-0 == +0), then the prim
+        std::sort(refs.begin() + s.lo, refs.begin() + s.hi, [axis](const SplitRef &x, const SplitRef &y) {
+            if (x.dead != y.dead) return y.dead;
+            if (!x.dead && x.c[axis] != y.c[axis]) return x.c[axis] < y.c[axis];
+            return x.prim < y.prim;
+        });
+        const size_t mid = s.lo + (s.hi - s.lo) / 2;
+        todo.push_back({s.lo, mid});
+        todo.push_back({mid, s.hi});
+    }
+    for (size_t k = 0; k < refs.size(); ++k) b.tris[k].prim = refs[k].prim;
+    return bvh_refit(b, tris9_now, n_now);
+}
+
 // Stage 0 cuts the depth-first array into the maximal subtrees of at most 64 leaves; every later stage does the same to the tree that is left
 // when the roots written so far count as its leaves.  A task's nodes need not be contiguous (they are in stage 0), so they are listed.
 void refit_schedule(const Bvh &b, RefitSchedule &out) {
@@ -340,6 +415,31 @@ extern "C" int arctic_refit_triangles(const float *tris9_build, const float *tri
     if (!refit_schedule_validate(b, sched)) return ARCTIC_E_INVALID;
     if ((nodes && node_cap < b.nodes.size()) || (tris && tri_cap < b.tris.size())) return ARCTIC_E_CAPACITY;
     if (!bvh_refit(b, tris9_now, n_tris)) return ARCTIC_E_INVALID;
+    std::vector<RayIn> in(n);
+    std::vector<RayOut> out(n);
+    if (n) std::memcpy(static_cast<void *>(in.data()), rays, n * sizeof(RayIn));
+    if (flags & ARCTIC_TRACE_BRUTE) brute_trace_host(tris9_now, n_tris, in.data(), n, (flags & ARCTIC_TRACE_ANY) != 0, out.data());
+    else bvh_trace_host(b, in.data(), n, (flags & ARCTIC_TRACE_ANY) != 0, out.data(), nullptr);
+    if (n) std::memcpy(static_cast<void *>(hits), out.data(), n * sizeof(RayOut));
+    if (nodes && !b.nodes.empty()) std::memcpy(static_cast<void *>(nodes), b.nodes.data(), b.nodes.size() * sizeof(RayNode));
+    if (tris && !b.tris.empty()) std::memcpy(static_cast<void *>(tris), b.tris.data(), b.tris.size() * sizeof(RayTri));
+    if (counts2) { counts2[0] = b.nodes.size(); counts2[1] = b.tris.size(); }
+    return ARCTIC_OK;
+}
+
+extern "C" int arctic_resplit_triangles(const float *tris9_build, const float *tris9_now, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits,
+                                        ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap, uint64_t *counts2) {
+    using namespace arctic;
+    if ((flags & ~(ARCTIC_TRACE_ANY | ARCTIC_TRACE_BRUTE)) || (n_tris && (!tris9_build || !tris9_now)) || (n && (!rays || !hits))) return ARCTIC_E_INVALID;
+    if (n_tris > 0xFFFFFFFEull) return ARCTIC_E_CAPACITY;
+    Bvh b;
+    if (!bvh_build(tris9_build, n_tris, nullptr, b)) return ARCTIC_E_CAPACITY;
+    if (!bvh_validate(b)) return ARCTIC_E_INVALID;
+    RefitSchedule sched;   // (as in arctic_refit_triangles: what the device's refit behind the re-split relies on)
+    refit_schedule(b, sched);
+    if (!refit_schedule_validate(b, sched)) return ARCTIC_E_INVALID;
+    if ((nodes && node_cap < b.nodes.size()) || (tris && tri_cap < b.tris.size())) return ARCTIC_E_CAPACITY;
+    if (!bvh_resplit(b, tris9_now, n_tris)) return ARCTIC_E_INVALID;
     std::vector<RayIn> in(n);
     std::vector<RayOut> out(n);
     if (n) std::memcpy(static_cast<void *>(in.data()), rays, n * sizeof(RayIn));

@@ -199,6 +199,43 @@ RQ_HD RayOut rq_walk(const RayPrep &r, const RayNode *nodes, const RayTri *tris,
     return best;
 }
 
+// ---- re-split (include/arctic_hip.h: "a re-split structure") -----------------------------------------------------------------------------------
+// The builder halves [lo, hi) at lo + (hi - lo) / 2 and stops at hi - lo <= RAY_LEAF_MAX, so the segment that holds slot position p after `level`
+// splits follows from the slot count alone.  A segment that has become a leaf stays as it is at every deeper level.
+RQ_HD void rq_segment(uint32_t n, uint32_t level, uint32_t p, uint32_t &lo, uint32_t &hi) {
+    lo = 0; hi = n;
+    for (uint32_t l = 0; l < level && l < 32u && hi - lo > RAY_LEAF_MAX; ++l) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (p < mid) hi = mid; else lo = mid;
+    }
+}
+// levels at which some segment of n slots is still split (0: the root is a leaf); the halves differ by at most one, so the largest decides
+RQ_HD uint32_t rq_split_levels(uint32_t n) {
+    uint32_t levels = 0;
+    for (uint32_t widest = n; widest > RAY_LEAF_MAX; widest = widest - widest / 2) ++levels;
+    return levels;
+}
+// A finite float as a 32-bit key whose unsigned order is the floats' order under <: -0 counts as +0, so equal floats have equal keys.  Every
+// finite key lies below RQ_KEY_DEAD, which a dead triangle takes on every axis.  rq_key_float: the float a finite key stands for
+constexpr uint32_t RQ_KEY_DEAD = 0xFFFFFFFFu;
+RQ_HD uint32_t rq_float_key(float x) {
+    const uint32_t b = x == 0.0f ? 0u : __builtin_bit_cast(uint32_t, x);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+RQ_HD float rq_key_float(uint32_t k) { return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+// the axis of a segment whose live centroids span [cmin[a], cmax[a]]: the widest fp32 extent under a strict >, the lowest axis on a tie
+RQ_HD int rq_split_axis(const float *cmin, const float *cmax) {
+    int axis = 0;
+    float widest = cmax[0] - cmin[0];
+    for (int a = 1; a < 3; ++a) if (cmax[a] - cmin[a] > widest) { widest = cmax[a] - cmin[a]; axis = a; }
+    return axis;
+}
+// the centroid of a finite triangle: of its box, halves first (the sum of two finite halves is finite)
+RQ_HD void rq_centroid(const float *p, float *c) {
+    const RayBox b = rq_triangle_box(p);
+    for (int a = 0; a < 3; ++a) c[a] = 0.5f * b.lo[a] + 0.5f * b.hi[a];
+}
+
 // what a refit uploads per object: the 12 floats of its trs in use (column c at m[3 c]) and the mesh's vertices in use (14 floats per vertex)
 struct alignas(16) RefitObject { float m[12]; const float *vertices; uint32_t n_vertices, pad; };
 static_assert(sizeof(RefitObject) == 64, "refit object record");
@@ -208,6 +245,12 @@ static_assert(sizeof(RefitObject) == 64, "refit object record");
 struct RefitTablesDev { const uint32_t *head, *inputs; const RefitInterior *interior; const RefitSource *src; };
 hipError_t launch_ray_refit(const RefitTablesDev &T, const uint32_t *stage_first, uint32_t n_stages, void *nodes, uint32_t n_nodes, void *tris, uint32_t n_slots,
                             const RefitObject *objs, uint32_t n_objs, hipStream_t s, uint32_t *launches);
+// ray_resplit.hip.  The slot order of a fresh build of the pose NOW, written into the slots' prims and into src (the device copy of the build's
+// source records), in stream order on s; launch_ray_refit then fills slots and boxes.  ws: ray_resplit_workspace(n_slots) bytes of device memory,
+// 256-byte aligned, the handle's for as long as the structure stands.  *launches: the kernels and fills enqueued here, a radix sort counted as one
+hipError_t ray_resplit_workspace(uint32_t n_slots, size_t *bytes);
+hipError_t launch_ray_resplit(void *ws, size_t ws_bytes, void *tris, uint32_t n_slots, RefitSource *src, const RefitObject *objs, uint32_t n_objs, hipStream_t s,
+                              uint32_t *launches);
 #endif
 
 // ---- host side (bvh.cpp) ---------------------------------------------------------------------------------------------------------------------
@@ -233,6 +276,10 @@ void ray_triangle_sources(uint32_t object, uint32_t n_vertices, const uint32_t *
 // (dead when not finite), leaf boxes the union of their live slots, interior boxes the union of their children, topology untouched.
 // false (nothing written): a prim at or above n_now, or a tree that fails the topology part of bvh_validate
 bool bvh_refit(Bvh &b, const float *tris9_now, uint64_t n_now);
+// The definition of a re-split structure, on the host, for a tree bvh_build made whose prims are array indices: the slots' prims are reordered by
+// the builder's own recursion applied to tris9_now (a triangle that is not finite now orders behind every live one on every axis), then bvh_refit.
+// false (nothing written): what bvh_refit refuses, or a topology that is not the builder's for this slot count
+bool bvh_resplit(Bvh &b, const float *tris9_now, uint64_t n_now);
 // the schedule for b's topology and its check: every node written exactly once, every input written in an earlier stage, every number in range
 void refit_schedule(const Bvh &b, RefitSchedule &out);
 bool refit_schedule_validate(const Bvh &b, const RefitSchedule &s);

@@ -422,6 +422,12 @@ struct ArcticRenderer {
         hipEvent_t ev_objs[OBJ_RING] = {nullptr, nullptr, nullptr};
         bool objs_pending[OBJ_RING] = {false, false, false};
         int objs_turn = 0;
+        // arctic_ray_scene_resplit (ray_resplit.hip; the definition: include/arctic_hip.h, "a re-split structure"): the sorts' workspace, allocated
+        // by the first re-split of a structure of this size and kept; nothing while the call is never made
+        DevBuf d_resplit;
+        size_t resplit_bytes = 0;
+        uint64_t resplit_slots = ~0ull;            // the slot count resplit_bytes was worked out for
+        uint64_t resplits = 0, resplit_launches = 0, resplit_fell_back = 0;
     } ray;
     uint32_t *dh_counts = nullptr;  // the device's address of h_counts
     uint32_t *h_counts = nullptr;   // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
@@ -1210,7 +1216,7 @@ void arctic_destroy(ArcticRenderer *r) {
                       &r->geo[1].d_recs, &r->geo[1].d_rrecs, &r->geo[1].d_clip_list, &r->geo[1].d_rec_of, &r->geo[1].d_items, &r->geo[0].d_left, &r->geo[1].d_left, &r->geo[2].d_left, &r->geo[0].d_bin_count, &r->geo[0].d_bin_slots, &r->geo[1].d_bin_count, &r->geo[1].d_bin_slots, &r->geo[2].d_bin_count, &r->geo[2].d_bin_slots, &r->d_geo_counters, &r->d_stage, &r->tables[0].d, &r->tables[1].d};
     for (PassTables &T : r->tables) { if (T.h) (void)hipHostFree(T.h); if (T.copied) (void)hipEventDestroy(T.copied); }
     for (DevBuf *b : bufs) b->release();
-    for (DevBuf *b : {&r->ray.d_nodes, &r->ray.d_tris, &r->ray.d_rays, &r->ray.d_hits, &r->ray.d_mask, &r->ray.d_src, &r->ray.d_head, &r->ray.d_inputs, &r->ray.d_interior, &r->ray.d_objs}) b->release();
+    for (DevBuf *b : {&r->ray.d_nodes, &r->ray.d_tris, &r->ray.d_rays, &r->ray.d_hits, &r->ray.d_mask, &r->ray.d_src, &r->ray.d_head, &r->ray.d_inputs, &r->ray.d_interior, &r->ray.d_objs, &r->ray.d_resplit}) b->release();
     for (int k = 0; k < ArcticRenderer::RayScene::OBJ_RING; ++k) {
         if (r->ray.h_objs[k]) (void)hipHostFree(r->ray.h_objs[k]);
         if (r->ray.ev_objs[k]) (void)hipEventDestroy(r->ray.ev_objs[k]);
@@ -2432,8 +2438,9 @@ bool ray_refit_eligible(const ArcticRenderer *r, const ArcticScene *sc) {
 
 // the refit: the per-object table (trs and vertices in use NOW) through the ring, then the stages.  Everything is enqueued on the handle's stream,
 // behind the k_morph / k_skin that wrote the vertices and behind the queries that still walk the structure in place; nothing waits for the device
-// (the ring's event is that of the copy OBJ_RING refits ago)
-int refit_ray_scene(ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_t> &key) {
+// (the ring's event is that of the copy OBJ_RING refits ago).  resplit: arctic_ray_scene_resplit -- between the table and the stages the slots are put
+// in the order a fresh build of this pose would give them (ray_resplit.hip), so the stages write that build's structure
+int refit_ray_scene(ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_t> &key, bool resplit = false) {
     ArcticRenderer::RayScene &R = r->ray;
     const size_t n_obj = (size_t)sc->n_objects, bytes = std::max<size_t>(n_obj, 1) * sizeof(RefitObject);
     const int slot = R.objs_turn;
@@ -2458,12 +2465,18 @@ int refit_ray_scene(ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_
         R.objs_pending[slot] = true;
     }
     const RefitTablesDev T = {R.d_head.as<uint32_t>(), R.d_inputs.as<uint32_t>(), R.d_interior.as<RefitInterior>(), R.d_src.as<RefitSource>()};
-    uint32_t launches = 0;
+    uint32_t launches = 0, split_launches = 0;
+    if (resplit) {
+        const hipError_t es = launch_ray_resplit(R.d_resplit.p, R.resplit_bytes, R.d_tris.p, (uint32_t)R.n_tris, R.d_src.as<RefitSource>(), R.d_objs.as<RefitObject>(), (uint32_t)n_obj,
+                                                 r->stream, &split_launches);
+        if (es != hipSuccess) { R.built = false; HIPCHECK(r, es); }   // (the order may be half written: the structure is dropped, the next query builds)
+    }
     const hipError_t e = launch_ray_refit(T, R.stage_first.data(), (uint32_t)R.stage_first.size() - 1, R.d_nodes.p, (uint32_t)R.n_nodes, R.d_tris.p, (uint32_t)R.n_tris,
                                           R.d_objs.as<RefitObject>(), (uint32_t)n_obj, r->stream, &launches);
     if (e != hipSuccess) { R.built = false; HIPCHECK(r, e); }   // (some stages may have run: the structure is dropped, the next query builds)
     R.key.swap(key);
-    ++R.refits; R.refit_launches = launches;
+    if (resplit) { ++R.resplits; R.resplit_launches = (uint64_t)split_launches + launches; }
+    else { ++R.refits; R.refit_launches = launches; }
     return ARCTIC_OK;
 }
 
@@ -2623,6 +2636,36 @@ int arctic_ray_refit_info(ArcticRenderer *r, uint64_t *out4) {
 int arctic_ray_scene_reset(ArcticRenderer *r) {
     if (!r) return ARCTIC_E_INVALID;
     r->ray.built = false; r->ray.refittable = false; r->ray.key.clear();   // (the buffers stay: a query in flight may still walk them, and the build reuses them)
+    return ARCTIC_OK;
+}
+
+int arctic_ray_scene_resplit(ArcticRenderer *r, const ArcticScene *scene) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "ray_scene_resplit: null scene");
+    int rc = select_device(r);
+    if (rc) return rc;
+    ArcticRenderer::RayScene &R = r->ray;
+    if (!ray_refit_eligible(r, scene)) {   // what a reset and the next query's build do (under the option in force now)
+        R.built = false; R.refittable = false; R.key.clear();
+        R.resplit_fell_back = 1;
+        return ensure_ray_scene(r, scene);
+    }
+    if (R.resplit_slots != R.n_tris) {
+        size_t bytes = 0;
+        HIPCHECK(r, ray_resplit_workspace((uint32_t)R.n_tris, &bytes));
+        HIPCHECK(r, R.d_resplit.ensure(std::max<size_t>(bytes, 256)));
+        R.resplit_bytes = bytes; R.resplit_slots = R.n_tris;
+    }
+    std::vector<uint8_t> key;
+    ray_inputs(r, scene, key);
+    R.resplit_fell_back = 0;
+    return refit_ray_scene(r, scene, key, true);
+}
+
+int arctic_ray_resplit_info(ArcticRenderer *r, uint64_t *out4) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!out4) return r->fail(ARCTIC_E_INVALID, "ray_resplit_info: null");
+    out4[0] = r->ray.resplits; out4[1] = r->ray.resplit_launches; out4[2] = r->ray.resplit_fell_back; out4[3] = 0;
     return ARCTIC_OK;
 }
 

@@ -237,6 +237,15 @@ class Renderer {
     [[nodiscard]] bool read_ray_structure(ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap) {
         return ok(arctic_read_ray_structure(m_handle, nodes, node_cap, tris, tri_cap));
     }
+    // the slots of the cached structure in the order a full build of the scene as it is now would give them, then a refit: on the device, in stream
+    // order (falls back to a full build where the structure cannot be refitted).  out4 = {re-splits, launches of the latest, 1 if it fell back, 0}
+    [[nodiscard]] bool ray_scene_resplit(const ArcticScene &scene) { return ok(arctic_ray_scene_resplit(m_handle, &scene)); }
+    [[nodiscard]] bool ray_resplit_info(uint64_t out4[4]) { return ok(arctic_ray_resplit_info(m_handle, out4)); }
+    // the re-split's host arbiter: build on tris9_build, re-split to tris9_now by the definition, walk (no handle, no GPU)
+    [[nodiscard]] static bool resplit_triangles(const float *tris9_build, const float *tris9_now, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits,
+                                                ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap, uint64_t *counts2) {
+        return arctic_resplit_triangles(tris9_build, tris9_now, n_tris, rays, n, flags, hits, nodes, node_cap, tris, tri_cap, counts2) == ARCTIC_OK;
+    }
     // the refit's host arbiter: build on tris9_build, refit to tris9_now, walk; optionally the refitted structure (no handle, no GPU)
     [[nodiscard]] static bool refit_triangles(const float *tris9_build, const float *tris9_now, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits,
                                               ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap, uint64_t *counts2) {

@@ -236,6 +236,18 @@ class Renderer:
         """drop the cached structure: the next query builds in full (a refitted tree that drifted far from the pose it was split for)"""
         self._check(self.L.arctic_ray_scene_reset(self.h))
 
+    def ray_scene_resplit(self, desc):
+        """put the cached structure's slots in the order a full build of the scene as it is NOW would give them, and refit: on the device, in
+        stream order, nothing read back.  Falls back to a full build where the structure cannot be refitted (ray_resplit_info()[2])"""
+        s = self._scene(desc)
+        self._check(self.L.arctic_ray_scene_resplit(self.h, C.byref(s)))
+
+    def ray_resplit_info(self):
+        """(device re-splits so far, launches of the latest, 1 if the latest ray_scene_resplit fell back to a full build, 0)"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_ray_resplit_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
     def read_ray_structure(self):
         """the device's structure as it stands: (RAY_NODE_DTYPE nodes, RAY_TRI_DTYPE leaf triangles).  Synchronises; for tests"""
         stored, n_nodes, _, _ = self.ray_scene_info()
@@ -536,6 +548,25 @@ def refit_triangles(triangles_build, triangles_now, rays, any_hit=False, brute=F
                                               _ptr(hits) if len(ry) else None, _ptr(nodes) if cap else None, len(nodes), _ptr(tris) if cap else None, len(tris), _ptr(counts))
     if rc < 0:
         raise ArcticError(rc, "refit_triangles")
+    return (hits, nodes[:int(counts[0])].copy(), tris[:int(counts[1])].copy()) if structure else hits
+
+
+def resplit_triangles(triangles_build, triangles_now, rays, any_hit=False, brute=False, structure=False):
+    """arctic_resplit_triangles: the re-split of include/arctic_hip.h on the host -- a structure built on triangles_build, its slots reordered by
+    the builder's rule applied to triangles_now, refitted and walked.  Returns what refit_triangles returns."""
+    a = np.ascontiguousarray(triangles_build, dtype=np.float32).reshape(-1, 9)
+    b = np.ascontiguousarray(triangles_now, dtype=np.float32).reshape(-1, 9)
+    if len(a) != len(b):
+        raise ValueError("resplit_triangles: the two triangle lists differ in length")
+    ry = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
+    hits = np.empty(len(ry), HIT_DTYPE)
+    flags = (binding.TRACE_ANY if any_hit else 0) | (binding.TRACE_BRUTE if brute else 0)
+    cap = len(a) if structure else 0
+    nodes, tris, counts = np.zeros(2 * cap, RAY_NODE_DTYPE), np.zeros(cap, RAY_TRI_DTYPE), np.zeros(2, np.uint64)
+    rc = binding.lib().arctic_resplit_triangles(_ptr(a) if len(a) else None, _ptr(b) if len(b) else None, len(a), _ptr(ry) if len(ry) else None, len(ry), flags,
+                                                _ptr(hits) if len(ry) else None, _ptr(nodes) if cap else None, len(nodes), _ptr(tris) if cap else None, len(tris), _ptr(counts))
+    if rc < 0:
+        raise ArcticError(rc, "resplit_triangles")
     return (hits, nodes[:int(counts[0])].copy(), tris[:int(counts[1])].copy()) if structure else hits
 
 

@@ -882,6 +882,46 @@ int arctic_read_ray_structure(ArcticRenderer *r, ArcticRayNode *nodes, uint64_t 
 int arctic_refit_triangles(const float *tris9_build, const float *tris9_now, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits,
                            ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap, uint64_t *counts2);
 
+/* ---- re-split: the structure is split again for the pose the scene has NOW, on the device ------------------------------------------------------
+ * A refit keeps the order of the triangles in the slots from the pose the tree was split for, and the walk of such a tree slows down as the scene
+ * moves on.  arctic_ray_scene_resplit puts the slots in the order a full build of the current pose would give them and refits -- in stream order
+ * on the handle's stream, without synchronising, without reading anything back (ray_resplit.hip).  The builder splits [lo, hi) at
+ * lo + (hi - lo) / 2 and stops at hi - lo <= 4, so the node count, every skip, every leaf word and the depth depend on the NUMBER of stored
+ * triangles alone; the geometry decides only which triangle sits in which slot.
+ *
+ * A RE-SPLIT STRUCTURE, defined:
+ * Topology.  The node count, every skip and every leaf word are those of the last full build; the set of stored triangles (prims) is that build's.
+ * World vertices and centroids.  A stored triangle's world vertices are those of "A world vertex is ..." above, from the mesh's vertices in use
+ *   NOW and the object's trs NOW.  Its centroid is that of its box, per axis c = 0.5f*lo + 0.5f*hi (lo = min, hi = max of the three vertices;
+ *   the products round, then the sum: contraction off).
+ * Dead triangles.  A triangle with a world vertex that is not finite now is DEAD.  On every axis a dead triangle orders behind every live one;
+ *   among dead triangles the order is by prim.
+ * Per segment [lo, hi) of slots, the root's being [0, stored):  hi - lo <= 4 is a LEAF, its slots ordered by prim.  Otherwise the axis is the one
+ *   with the widest centroid extent over the segment's LIVE members, fp32 cmax - cmin under a strict >: on a tie the lowest axis wins; an extent
+ *   that overflows to +inf still orders; a segment with no live member takes axis 0.  The members are ordered by (c[axis], prim) under < on
+ *   floats -- -0 and +0 tie and fall to the prim --, dead members last; with mid = lo + (hi - lo) / 2 the lower mid - lo members form [lo, mid),
+ *   the others [mid, hi), and the rule applies to each half.  (Only the two SETS matter: each half is ordered again by its own rule.)
+ * Slot contents and boxes.  Those of a refit to the current pose ("A REFITTED STRUCTURE" above), dead slots and empty boxes included.
+ * Consequence: with every stored triangle finite now, a re-split structure EQUALS the structure a full build of the current world triangles
+ *   makes (bvh.cpp: bvh_build) -- triangles, skip and leaf compare by bytes, boxes compare by value.
+ * arctic_ray_scene_resplit(r, scene).  When the cached structure could follow `scene` by a refit (Eligibility above: the option was 1 at the last
+ *   full build, and so on) the re-split and the refit are enqueued -- also when nothing moved.  Otherwise the call does what
+ *   arctic_ray_scene_reset and the build of the next query do.  A re-split counts neither as a build in arctic_ray_scene_info nor as a refit in
+ *   arctic_ray_refit_info; later refits keep the order it left.  Its workspace (about 100 bytes per stored triangle) is allocated by the first
+ *   re-split of a structure and kept; a handle that never makes the call allocates nothing and behaves as before.  Each rank of a sharded frame
+ *   re-splits its own copy.  ARCTIC_E_INVALID: a null handle or scene. */
+int arctic_ray_scene_resplit(ArcticRenderer *r, const ArcticScene *scene);
+
+/* out4 = {device re-splits so far, launches of the latest one (its kernels and fills, each radix sort counted as one, and the refit's stages),
+ * 1 if the latest arctic_ray_scene_resplit fell back to a full build on the host, 0}. */
+int arctic_ray_resplit_info(ArcticRenderer *r, uint64_t *out4);
+
+/* The host arbiter of the re-split (no handle, no GPU), shaped like arctic_refit_triangles: builds on tris9_build, re-splits to tris9_now by the
+ * definition above -- carried out directly, dead triangles included, not by a second build --, walks the result and optionally returns it.
+ * With ARCTIC_TRACE_BRUTE the hits come from the loop over every triangle of tris9_now.  The same refusals; a refused call writes nothing. */
+int arctic_resplit_triangles(const float *tris9_build, const float *tris9_now, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits,
+                             ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap, uint64_t *counts2);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row
