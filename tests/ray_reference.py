@@ -11,6 +11,12 @@ ufunc on float32 operands, so each rounds once, in the written order, and nothin
   "open_interval"  t_min < t < t_max instead of <=          "no_clamp"       t = tm, not clamped into the triangle's box interval
   "tie_larger"     among equal t the LARGER prim            "uv_open"        u + v < 1 instead of <=
   "prune_nonstrict" (walk only) a node is skipped when max(tn, t_min) >= min(tf, t_max, t_best)
+  "nan_prunes"     (walk only) a NaN slab product of the NODE test -- 0 * inf: a zero direction component, or one whose reciprocal overflows, and
+                   an origin in the box's plane -- reads as "box missed" instead of "no constraint": what an odd ray meets in a walk that does
+                   not look for the NaN
+
+The generators at the end lay rays out by the WAVE of 64 they fall into on the device, where trace.hip chooses the walk per wave (ray_odd):
+wave_rays, edge_records, subnormal_rays, and soup_gbuffer for the sun's rays.
 """
 import numpy as np
 
@@ -50,7 +56,15 @@ def ray_valid(rays):
     return np.isfinite(o).all(-1) & np.isfinite(d).all(-1) & ~(d == 0).all(-1)
 
 
-def ray_box(o, d, bmin, bmax):
+def ray_odd(rays):
+    """RayPrep::odd of ray_query.h restated: some d == 0, or some float32(1) / d that is not finite -- the rays whose node test can meet 0 * inf.
+    A wave of 64 on the device takes the walk that looks for the NaN when one of its VALID lanes is odd (wave_walks)"""
+    d = rays["direction"]
+    with np.errstate(all="ignore"):
+        return ((d == 0) | ~np.isfinite(F(1.0) / d)).any(-1)
+
+
+def ray_box(o, d, bmin, bmax, nan_prunes=False):
     """o, d, bmin, bmax: sequences of 3 broadcastable float32 arrays -> (met, tn, tf)"""
     los, his, ok = [], [], True
     with np.errstate(all="ignore"):
@@ -58,6 +72,9 @@ def ray_box(o, d, bmin, bmax):
             inv = F(1.0) / d[a]
             l = (bmin[a] - o[a]) * inv
             h = (bmax[a] - o[a]) * inv
+            if nan_prunes:                                          # the defect: d == 0 counts as a reciprocal of +inf, and a NaN product misses
+                n = np.where(d[a] == 0, INF, inv)
+                ok = ok & ~(np.isnan((bmin[a] - o[a]) * n) | np.isnan((bmax[a] - o[a]) * n))
             free = (d[a] == 0) | np.isnan(l) | np.isnan(h)          # d == 0 inside the slab, or 0 * inf: (-inf, +inf)
             ok = ok & ~((d[a] == 0) & ~((bmin[a] <= o[a]) & (o[a] <= bmax[a])))
             los.append(np.where(free, -INF, _min(l, h)))
@@ -205,7 +222,7 @@ def walk(bvh, rays, any_hit=False, defect=None, count_triangles=False):
         visits[act] += 1
         o = [O[act, a] for a in range(3)]
         d = [D[act, a] for a in range(3)]
-        met, tn, tf = ray_box(o, d, [bvh.bmin[i, a] for a in range(3)], [bvh.bmax[i, a] for a in range(3)])
+        met, tn, tf = ray_box(o, d, [bvh.bmin[i, a] for a in range(3)], [bvh.bmax[i, a] for a in range(3)], defect == "nan_prunes")
         with np.errstate(all="ignore"):
             near = _max(tn, TMIN[act])
             far = _min(_min(tf, TMAX[act]), TMAX[act] if any_hit else best_t[act])
@@ -339,3 +356,308 @@ def soup(rng, n_tris, n_rays):
     """-> (tris (n_tris, 9), rays): soup_triangles and soup_rays for them"""
     tris = soup_triangles(rng, n_tris)
     return tris, soup_rays(rng, tris, n_rays)
+
+
+# ---- rays laid out by wave ------------------------------------------------------------------------------------------------------------------
+WAVE = 64
+SUBNORMAL_ODD = (0x00000000, 0x00000001, 0x00200000)                # |d|: zero; the smallest subnormal; 2^-128, the largest whose reciprocal overflows
+SUBNORMAL_PLAIN = (0x00200001, 0x00400000, 0x007FFFFF, 0x00800000)  # one step above it; 2^-127; the largest subnormal; the smallest normal number
+
+
+def wave_walks(rays):
+    """per wave of 64 consecutive rays, the walk trace.hip takes for it -- "odd" when a valid lane is odd, "plain" when it has valid lanes and
+    none is odd, "none" when no lane walks --, computed from ray_odd and ray_valid alone"""
+    valid = ray_valid(rays)
+    odd = valid & ray_odd(rays)
+    return ["odd" if odd[s:s + WAVE].any() else "plain" if valid[s:s + WAVE].any() else "none" for s in range(0, len(rays), WAVE)]
+
+
+def tile_walks(rays, active, rows, width, row0_in_tile=0):
+    """the same for arctic_trace_sun_visibility, whose waves are the 8 x 8 tiles of the handle's rows x width pixels (one ray each, row-major;
+    the first row is row row0_in_tile of its tile row): -> the walks of the tiles, row by row"""
+    valid = ray_valid(rays) & active
+    odd = valid & ray_odd(rays)
+    th, tw = -(-(rows + row0_in_tile) // 8), -(-width // 8)
+    out = []
+    for plane in (valid, odd):
+        full = np.zeros((th * 8, tw * 8), bool)
+        full[row0_in_tile:row0_in_tile + rows, :width] = plane.reshape(rows, width)
+        out.append(full.reshape(th, 8, tw, 8).any((1, 3)).reshape(-1))
+    return ["odd" if o else "plain" if v else "none" for v, o in zip(*out)]
+
+
+EDGE_NAMES = ["d = (0, 0, 0)", "d = (-0, 0, -0)", "o.x = NaN", "o.y = +inf", "o.z = -inf", "d.z = NaN", "d.x = +inf", "d.y = -inf",
+              "t_min = NaN", "t_max = NaN", "t_min = +inf", "t_max = -inf", "t_min > t_max", "t_min = -inf, t_max = +inf"]
+EDGE_INVALID = 8                                                   # records 0..7 are not valid rays; 8..12 are valid and admit no t; 13 admits every t
+
+
+def edge_records(base=None):
+    """the fixed list of bad rays (EDGE_NAMES), each written into a copy of `base` (one ray; default: (1, 1, 0) + t (0.25, 0.5, 1), which is not
+    odd).  Every record but the last is a miss whatever the triangles.  t_min > t_max is 1.5 > 0.5: limits that, swapped, would admit the hit of
+    a ray aimed at a target at t = 1"""
+    base = make_rays([[1, 1, 0]], [[0.25, 0.5, 1]]) if base is None else np.asarray(base, RAY_DTYPE).reshape(1)
+    r = np.repeat(base, len(EDGE_NAMES))
+    r["direction"][0] = (0.0, 0.0, 0.0)
+    r["direction"][1] = (-0.0, 0.0, -0.0)
+    r["origin"][2, 0], r["origin"][3, 1], r["origin"][4, 2] = np.nan, np.inf, -np.inf
+    r["direction"][5, 2], r["direction"][6, 0], r["direction"][7, 1] = np.nan, np.inf, -np.inf
+    r["t_min"][8], r["t_max"][9], r["t_min"][10], r["t_max"][11] = np.nan, np.nan, np.inf, -np.inf
+    r["t_min"][12], r["t_max"][12] = 1.5, 0.5
+    r["t_min"][13], r["t_max"][13] = -np.inf, np.inf
+    return r
+
+
+def _lanes(*parts):
+    out = []
+    for kind, count in parts:
+        out += [kind] * count
+    return out
+
+
+def _with_edges(lanes, edges):
+    lanes = list(lanes)
+    for lane, k in edges.items():
+        lanes[lane] = ("edge", k)
+    return lanes
+
+
+_ALL_EDGES = dict(zip([0, 1, 2, 3, 4, 5, 6, 31, 32, 59, 60, 61, 62, 63], range(14)))
+# a lane is "plain" / "odd" (a ray of that kind from the pool), ("edge", k) (edge record k written over such a ray), or "bad_plain" / "bad_odd"
+# (such a ray made invalid: the former stays not odd, the latter stays odd)
+WAVE_LAYOUTS = {
+    # 9 waves, 529 rays: crosses one 256-thread workgroup boundary
+    1: [_lanes(("plain", 64)),
+        _lanes(("odd", 64)),
+        _lanes(("plain", 63), ("odd", 1)),
+        _lanes(("odd", 1), ("plain", 63)),
+        _with_edges(_lanes(("plain", 64)), {0: 0, 1: 5, 2: 3, 31: 8, 32: 11, 63: 12}),   # invalid odd lanes (d = 0, d.z = NaN) in a plain wave
+        _lanes(("bad_odd", 1), ("bad_plain", 1)) * 32,
+        _lanes(("plain", 64)),
+        _lanes(("plain", 64)),
+        _lanes(("plain", 17))],
+    # every edge record in a plain wave and in an odd wave, and a partial wave that one lane makes odd
+    2: [_with_edges(_lanes(("plain", 64)), _ALL_EDGES),
+        _with_edges(_lanes(("odd", 64)), _ALL_EDGES),
+        _lanes(("plain", 16), ("odd", 1))],
+}
+
+
+def _spoil(ray, k, odd):
+    """one ray made invalid, the k-th way; odd: keep it odd (ray_odd), else keep it not odd"""
+    bad = (np.nan, np.inf, -np.inf)
+    if odd and k % 6 == 4:
+        ray["direction"] = (0.0, 0.0, 0.0)
+    elif odd and k % 6 == 5:
+        ray["direction"][k % 3] = np.nan                            # (1 / NaN is not finite: odd whatever the ray was)
+    elif not odd and k % 6 >= 4:
+        ray["direction"][k % 3] = bad[1 + k % 2]                    # (1 / inf = 0 is finite: not odd)
+    else:
+        ray["origin"][k % 3] = bad[(k // 3) % 3]
+    return ray
+
+
+def vertex_rays(rng, tris, n_rays):
+    """rays that are not odd, aimed from general origins exactly at vertices that two or more triangles share (at any vertex where none is
+    shared) and at points of axis-aligned triangles: the closest hit of such a ray is often shared by several triangles (tied), and the smaller
+    prim has to win"""
+    t = np.ascontiguousarray(tris, F).reshape(-1, 3, 3)
+    v, owner = t.reshape(-1, 3), np.repeat(np.arange(len(t)), 3)
+    uniq, inv = np.unique(v, axis=0, return_inverse=True)
+    inv = inv.reshape(-1)
+    owners = np.zeros(len(uniq), np.int64)
+    np.add.at(owners, np.unique(np.stack([inv, owner], 1), axis=0)[:, 0], 1)
+    shared = uniq[owners >= 2] if (owners >= 2).any() else uniq
+    target = shared[rng.integers(0, len(shared), n_rays)]
+    flat = np.nonzero((t.max(1) == t.min(1)).any(1))[0]             # axis-aligned triangles: those of one shared plane overlap, and tie at the slab's t
+    if len(flat):
+        inside = (t[flat[rng.integers(0, len(flat), n_rays)]] * rng.dirichlet(np.ones(3), n_rays).astype(F)[:, :, None]).sum(1).astype(F)
+        target = np.where((rng.random(n_rays) < 0.5)[:, None], inside, target)
+    off = (rng.uniform(0.5, 3.0, (n_rays, 3)) * rng.choice([-1.0, 1.0], (n_rays, 3))).astype(F)
+    o = (target + off).astype(F)
+    return make_rays(o, (target - o).astype(F), 0.0, np.inf)
+
+
+def planar_rays(rng, tris, n_rays):
+    """odd rays whose origin lies in a plane of a triangle's box on an axis where the direction is zero, or so small that its reciprocal
+    overflows (1e-45): the node test's 0 * inf.  They are aimed at the triangle's vertex in that plane; a third of them run parallel to an axis"""
+    t = np.ascontiguousarray(tris, F).reshape(-1, 3, 3)
+    k, a = rng.integers(0, len(t), n_rays), rng.integers(0, 3, n_rays)
+    upper = rng.integers(0, 2, n_rays).astype(bool)
+    coord = t[k, :, a]
+    vertex = t[k, np.where(upper, coord.argmax(1), coord.argmin(1))]
+    off = (rng.uniform(0.5, 3.0, (n_rays, 3)) * rng.choice([-1.0, 1.0], (n_rays, 3))).astype(F)
+    how = rng.integers(0, 3, n_rays)
+    rows = np.arange(n_rays)
+    off[rows, a] = 0
+    off[how == 2, (a[how == 2] + 1) % 3] = 0                         # parallel to the third axis
+    o = (vertex + off).astype(F)
+    d = (vertex - o).astype(F)
+    assert (d[rows, a] == 0).all()
+    tiny = how == 1
+    d[tiny, a[tiny]] = (F(1e-45) * rng.choice(np.array([-1, 1], F), n_rays))[tiny]
+    return make_rays(o, d, 0.0, np.inf)
+
+
+def wave_pool(rng, tris, prims=None, n_soup=2048, n_vertex=1024, n_planar=192):
+    """the rays wave_rays deals from: soup_rays, vertex_rays and planar_rays, classified once.  SPECIAL among the rays that are not odd: those
+    whose result a walk that prunes at equality changes (defect "prune_nonstrict" in this module's own tree, which is split as the library's
+    is) -- they come first -- and those whose closest hit two triangles share (tied); among the odd rays: those whose result a walk changes
+    that takes a NaN slab product for a miss (defect "nan_prunes") -- they come first -- and the planar_rays"""
+    p = soup_rays(rng, tris, n_soup)
+    p = np.concatenate([p[ray_valid(p)], vertex_rays(rng, tris, n_vertex), planar_rays(rng, tris, n_planar)])
+    odd = ray_odd(p)
+    hit, tie = tied(tris, p)
+    bvh = build_bvh(tris, prims)
+    sensitive = np.zeros(len(p), bool)
+    sensitive[~odd] = walk(bvh, p[~odd])[0] != walk(bvh, p[~odd], defect="prune_nonstrict")[0]
+    sensitive[odd] = walk(bvh, p[odd])[0] != walk(bvh, p[odd], defect="nan_prunes")[0]
+    special = np.where(odd, np.arange(len(p)) >= len(p) - n_planar, tie) | sensitive
+    return dict(rays=p, odd=odd, hit=hit, special=special, first=sensitive)
+
+
+class _Deck:
+    """the rays of one kind (odd, or not) that wave_rays deals from, as three fixed orders of pool indices:
+      any      every ray of the kind that is not special, in the pool's order
+      hitting  those of `any` that hit something, in the pool's order
+      special  the special ones: those whose result the walk's defect changes first, then the others
+    next() goes round  any, special, hitting  and takes the first ray of that order not dealt yet (of `any` where the order is used up), so a
+    third of the lanes are special rays while they last and at least a third hit.  bases: rays that hit, kept back for the edge records"""
+    def __init__(self, pool, ids, n_bases):
+        hit, special, first = pool["hit"], pool["special"], pool["first"]
+        hitting = ids[hit[ids]]
+        self.bases = list(np.concatenate([hitting[~special[hitting]], hitting[special[hitting]]])[:n_bases])   # (not special ones, where there are enough)
+        assert len(self.bases) == n_bases, "the pool is too small"
+        rest = np.setdiff1d(ids, self.bases)
+        plain, chosen = rest[~special[rest]], rest[special[rest]]
+        self.orders = [plain, np.concatenate([chosen[first[chosen]], chosen[~first[chosen]]]), plain[hit[plain]]]
+        self.at, self.dealt, self.turn = [0, 0, 0], set(), 0
+
+    def next(self):
+        for order in (self.turn % 3, 0):
+            ids = self.orders[order]
+            while self.at[order] < len(ids) and ids[self.at[order]] in self.dealt:
+                self.at[order] += 1
+            if self.at[order] < len(ids):
+                self.turn += 1
+                self.dealt.add(ids[self.at[order]])
+                return ids[self.at[order]]
+        raise AssertionError("the pool is too small")
+
+
+def wave_rays(rng, tris, layout, prims=None, pool=None):
+    """rays for the device's waves: a pool (wave_pool; made from rng where none is given) split by ray_odd and dealt into the lanes of
+    WAVE_LAYOUTS[layout] (or of a list of that form) as _Deck describes.  Edge records are written over rays that hit something, so that a walk
+    which ignored the record's defect would report a hit.
+    -> (rays, waves): per wave dict(start, stop, lanes = the layout's lane kinds, edges = {lane: record number}, walk = "plain" / "odd" / "none"
+    as the LAYOUT implies it -- tests check that claim with wave_walks)"""
+    spec = WAVE_LAYOUTS[layout] if isinstance(layout, int) else layout
+    pool = wave_pool(rng, tris, prims) if pool is None else pool
+    p = pool["rays"]
+    n_edge = {False: 0, True: 0}
+    for w in spec:
+        n_edge["odd" in w] += sum(isinstance(l, tuple) for l in w)
+    deck = {o: _Deck(pool, np.nonzero(pool["odd"] == o)[0], n_edge[o]) for o in (False, True)}
+    stronger = lambda a, b: max(a, b, key=["none", "plain", "odd"].index)
+    rays, waves = [], []
+    for w in spec:
+        base_odd = "odd" in w                                        # edge records of an odd wave go over odd rays
+        start, walk = len(rays), "none"
+        for lane, kind in enumerate(w):
+            if isinstance(kind, tuple):
+                r = edge_records(p[deck[base_odd].bases.pop(0)])[kind[1]]
+                if kind[1] >= EDGE_INVALID:
+                    walk = stronger(walk, "odd" if base_odd else "plain")
+            elif kind in ("plain", "odd"):
+                r = p[deck[kind == "odd"].next()].copy()
+                walk = stronger(walk, kind)
+            else:
+                r = _spoil(p[deck[kind == "bad_odd"].next()].copy(), lane // 2, kind == "bad_odd")
+            rays.append(r)
+        waves.append(dict(start=start, stop=len(rays), lanes=list(w), edges={l: k[1] for l, k in enumerate(w) if isinstance(k, tuple)}, walk=walk))
+    assert all(wv["stop"] - wv["start"] == WAVE for wv in waves[:-1])
+    return np.array(rays, RAY_DTYPE), waves
+
+
+def subnormal_rays(tris, seed=5):
+    """rays with ONE direction component at each bit pattern of SUBNORMAL_ODD and SUBNORMAL_PLAIN, of both signs, on each axis; the other two
+    components are general, so such a ray runs (nearly) inside the plane of its origin's coordinate on that axis.  Per axis two triangles -- the
+    one that reaches furthest up that axis, and another whose box has an extent on it where there is one -- and per triangle three origins: in
+    the box's upper plane on that axis, aimed at the vertex there; one ulp above that plane (the triangle is missed; above the furthest one,
+    everything is); strictly inside the box, aimed at a point of the triangle (a hit).
+    -> (plain, odd): two sets, each (rays, pattern): `plain` holds the rays whose reciprocals are all finite, `odd` the others; each is padded to
+    whole waves of 64 with soup rays that are not odd; pattern = |d| 's bits on the axis in question, -1 for a padding ray"""
+    rng = np.random.default_rng(seed)
+    t = np.ascontiguousarray(tris, F).reshape(-1, 3, 3)
+    t = t[np.isfinite(t).all((1, 2))]
+    lo, hi = t.min(1), t.max(1)
+    sets = {False: ([], []), True: ([], [])}
+    for a in range(3):
+        b, c = (a + 1) % 3, (a + 2) % 3
+        top = int(np.argmax(hi[:, a]))
+        wide = np.nonzero((hi[:, a] > lo[:, a]) & (np.arange(len(t)) != top))[0]
+        for k in dict.fromkeys([top] + ([int(wide[rng.integers(len(wide))])] if len(wide) else [])):
+            vertex = t[k][int(np.argmax(t[k][:, a]))]
+            w = np.array([0.5, 0.25, 0.25], F)
+            inner = (t[k] * w[:, None]).sum(0).astype(F)             # a point well inside the triangle
+            for where, target in (("plane", vertex), ("above", vertex), ("inside", inner)):
+                for bits in SUBNORMAL_ODD + SUBNORMAL_PLAIN:
+                    for sign in (0, 0x80000000):
+                        off = rng.uniform(0.75, 2.5, 2).astype(F) * rng.choice(np.array([-1, 1], F), 2)
+                        o, d = target.copy(), np.zeros(3, F)
+                        o[b], o[c] = target[b] + off[0], target[c] + off[1]
+                        d[b], d[c] = target[b] - o[b], target[c] - o[c]
+                        d[a] = np.array([bits | sign], np.uint32).view(F)[0]
+                        if where == "plane":
+                            o[a] = hi[k, a]
+                        elif where == "above":
+                            o[a] = np.nextafter(hi[k, a], INF)
+                        rays, pats = sets[bits in SUBNORMAL_ODD]
+                        rays.append(make_rays([o], [d])[0]); pats.append(bits)
+    pad = soup_rays(rng, t.reshape(-1, 9), 256)
+    pad = pad[ray_valid(pad) & ~ray_odd(pad)]
+    out = []
+    for is_odd in (False, True):
+        rays, pats = sets[is_odd]
+        n_pad = -len(rays) % WAVE
+        out.append((np.concatenate([np.array(rays, RAY_DTYPE), pad[:n_pad]]), np.array(pats + [-1] * n_pad, np.int64)))
+    return out[0], out[1]
+
+
+def soup_gbuffer(rng, tris, height, width, axes=(1, 2)):
+    """a G-buffer to inject for arctic_trace_sun_visibility: (attrs (height, width, 18) float32 with unit normals in 8..10 and world positions in
+    11..13, material (height, width) uint32).  Half of the world positions are random points of the triangles.  The others lie on an edge of a
+    triangle that runs at the triangle's largest or smallest coordinate on one of `axes` -- so the pixel's coordinate on that axis is a plane of
+    that triangle's box and of every box it bounds --, or are such points snapped to multiples of 0.25 on those axes; their normals are +-x, so
+    that a bias keeps them in that plane.  About an eighth of the pixels have no geometry (NO_PRIM as the material), the 8 x 8 tile at (16, 8)
+    and row 20 among them; six covered pixels have a world coordinate that is not finite"""
+    t = np.ascontiguousarray(tris, F).reshape(-1, 3, 3)
+    n = height * width
+    world = (t[rng.integers(0, len(t), n)] * rng.dirichlet(np.ones(3), n).astype(F)[:, :, None]).sum(1).astype(F)
+    nrm = rng.normal(size=(n, 3))
+    nrm = (nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(F)
+    kind = rng.integers(0, 8, n)
+    edges = []                                                       # (triangle, corner i, corner j, axis): an edge at the box's plane on that axis
+    for a in axes:
+        for i, j in ((0, 1), (1, 2), (2, 0)):
+            same = (t[:, i, a] == t[:, j, a]) & ((t[:, i, a] == t[:, :, a].max(1)) | (t[:, i, a] == t[:, :, a].min(1))) & (t[:, :, a].max(1) > t[:, :, a].min(1))
+            edges += [(k, i, j, a) for k in np.nonzero(same)[0]]
+    for px in np.nonzero(kind >= 4)[0]:
+        if kind[px] < 7 and edges:
+            k, i, j, a = edges[rng.integers(len(edges))]
+            lam = F(rng.uniform(0.1, 0.9))
+            world[px] = t[k, i] + lam * (t[k, j] - t[k, i])
+            world[px, a] = t[k, i, a]                                # exactly in the plane
+        else:
+            for a in axes:
+                world[px, a] = np.round(world[px, a] * 4) / 4
+        nrm[px] = (rng.choice([-1.0, 1.0]), 0.0, 0.0)
+    material = np.zeros((height, width), np.uint32)
+    material.reshape(-1)[kind == 0] = NO_PRIM
+    material[8:16, 16:24] = NO_PRIM
+    material[20 % height] = NO_PRIM
+    covered = np.nonzero(material.reshape(-1) != NO_PRIM)[0]
+    for m, px in enumerate(rng.choice(covered, 6, replace=False)):
+        world[px, m % 3] = (np.nan, np.inf, -np.inf)[m // 2]
+    attrs = np.zeros((height, width, 18), F)
+    attrs[..., 8:11], attrs[..., 11:14] = nrm.reshape(height, width, 3), world.reshape(height, width, 3)
+    return attrs, material

@@ -4,11 +4,16 @@ The answer to a ray is DEFINED bit for bit (include/arctic_hip.h, "ray queries";
 tests/test_ray_reference.py), so every comparison here is of bytes: the device's hits against the arbiter's loop over every triangle of the
 scene, for the smallest shapes at which the kernel can still go wrong -- 1, 4 and 5 triangles (one leaf, a full leaf, the first split), 1000 (a
 tree of 511 nodes, depth 9) in one to three objects with transforms of their own; 1, 63, 64, 65, 257 and 1000 rays (a lane, a wave short of one,
-a wave, a wave and a lane, a workgroup and a lane, four workgroups)."""
+a wave, a wave and a lane, a workgroup and a lane, four workgroups).
+
+These rays come from soup_rays, a quarter of which have a zero direction component, so nearly every wave here takes the walk that looks for
+0 * inf.  tests/test_gpu_ray_paths.py has the per-wave cases: waves without such a ray, edge rays, subnormal directions, the sun's grid tails.
+The scenes are tests/ray_scenes.py's, shared with that file."""
 import numpy as np
 import pytest
 
 import ray_reference as R
+from ray_scenes import Scene, soup_meshes, transforms   # noqa: F401 (the refit and re-split tests import the latter two from this module)
 
 pytestmark = pytest.mark.gpu
 
@@ -16,58 +21,6 @@ F = np.float32
 NONE = 0xFFFFFFFF
 TRI_COUNTS = [1, 4, 5, 1000]
 RAY_COUNTS = [1, 63, 64, 65, 257, 1000]
-
-
-def transforms():
-    """three object transforms: one of exactly representable entries (a quarter turn about y, scales 2 / 1 / 0.5, a translation in quarters: the
-    soup's shared edges, grid and axis-aligned planes stay exactly shared, on the grid and axis-aligned in world space), two general ones"""
-    a = np.array([[0, 0, 0.5, 1.5], [0, 1, 0, -0.25], [-2, 0, 0, 2], [0, 0, 0, 1]], np.float64)
-    c, s = np.cos(0.7), np.sin(0.7)
-    b = np.array([[c, -s, 0, -1.3], [s, c, 0, 0.4], [0, 0, 1, 0.9], [0, 0, 0, 1]]) @ np.diag([1.1, 0.8, 1.3, 1.0])
-    c, s = np.cos(-1.9), np.sin(-1.9)
-    d = np.array([[1, 0, 0, 0.2], [0, c, -s, -0.6], [0, s, c, 1.7], [0, 0, 0, 1]]) @ np.diag([0.6, 1.7, 0.9, 1.0])
-    return [m.astype(F) for m in (a, b, d)]
-
-
-def soup_meshes(pkg, rng, n_tris, n_objects):
-    """the soup's triangles as n_objects meshes (three vertices per triangle; vertices of grid triangles repeat the same coordinates, so shared
-    edges stay shared); the second mesh, where there is one, carries a triangle with an index out of range in its middle"""
-    tris = R.soup_triangles(rng, n_tris).reshape(-1, 3, 3)
-    cuts = np.linspace(0, n_tris, n_objects + 1).astype(int)
-    meshes = []
-    for k in range(n_objects):
-        part = tris[cuts[k]:cuts[k + 1]]
-        v = np.zeros(3 * len(part), pkg.scene.VERTEX_DTYPE)
-        v["position"] = part.reshape(-1, 3)
-        v["normal"], v["tangent"], v["bitangent"] = (0, 1, 0), (1, 0, 0), (0, 0, 1)
-        ind = np.arange(3 * len(part), dtype=np.uint32)
-        if k == 1 and len(part) >= 2:
-            mid = 3 * (len(part) // 2)
-            ind = np.concatenate([ind[:mid], np.array([0, 1, 3 * len(part)], np.uint32), ind[mid:]])   # skipped, but it takes a prim number
-        meshes.append((v, ind))
-    return meshes
-
-
-class Scene:
-    def __init__(self, pkg, hip, n_tris):
-        rng = np.random.default_rng(7000 + n_tris)
-        n_objects = {1: 1, 4: 2, 5: 3, 1000: 3}[n_tris]
-        self.meshes = soup_meshes(pkg, rng, n_tris, n_objects)
-        self.desc = pkg.scenes.SceneDesc(camera=dict(eye=(0, 0, 9), rotation=(0, -90), aspect=1.0, fov_y=60.0, z_near_far=(0.1, 50.0)), ambient=0.1,
-                                         sun=pkg.scenes.DEFAULT_SUN, objects=pkg.scene.make_objects([(m, k) for k, m in enumerate(transforms()[:n_objects])]))
-        self.tris, self.prims = R.world_triangles(self.desc.objects, self.meshes)
-        self.n_prims = sum(len(i) // 3 for _, i in self.meshes)
-        self.r = hip.Renderer(64, 64, 64, 16)
-        self.r.create_material(*pkg.scenes.fallback_textures())
-        for v, i in self.meshes:
-            self.r.create_mesh(v, i, 0)
-        self.rays, self.want = {}, {}
-
-    def case(self, n_rays):
-        if n_rays not in self.rays:
-            self.rays[n_rays] = R.soup_rays(np.random.default_rng(9000 + n_rays), self.tris, n_rays)
-            self.want[n_rays] = {a: R.brute(self.tris, self.rays[n_rays], any_hit=a, prims=self.prims) for a in (False, True)}
-        return self.rays[n_rays], self.want[n_rays]
 
 
 @pytest.fixture(scope="module")

@@ -190,3 +190,69 @@ def test_the_run_tells_the_definition_from_each_defect(run, defect):
 def test_the_run_tells_strict_pruning_from_non_strict(run):
     tris, rays, want, bvh = run
     assert R.walk(bvh, rays, defect="prune_nonstrict")[0].tobytes() != want.tobytes()
+
+
+def bits(*patterns):
+    return np.array(patterns, np.uint32).view(F)
+
+
+def test_ray_odd_worked_out_by_hand():
+    """1 / d overflows exactly up to |d| = 2^-128 (bits 0x00200000): 2^128 is one step past the largest float, and 1 / (2^-128 (1 + 2^-21)) rounds
+    to a finite one"""
+    tiny = bits(0x00000001)[0]
+    assert tiny > 0 and tiny / F(2) == 0 and bits(0x007FFFFF)[0] + tiny == bits(0x00800000)[0]      # numpy does not flush subnormals
+    with np.errstate(over="ignore"):
+        assert np.isinf(F(1) / bits(0x00200000)[0]) and F(1) / bits(0x00200001)[0] == bits(0x7F7FFFF8)[0]
+    odd = [0x00000000, 0x00000001, 0x00200000]
+    plain = [0x00200001, 0x00400000, 0x007FFFFF, 0x00800000, 0x3F800000, 0x7F7FFFFF]
+    for pattern, want in [(b, True) for b in odd] + [(b, False) for b in plain]:
+        for sign in (0, 0x80000000):
+            for axis in range(3):
+                d = np.array([1.0, -2.0, 0.5], F)
+                d[axis] = bits(pattern | sign)[0]
+                assert R.ray_odd(R.make_rays([[0, 0, 0]], [d])).tolist() == [want], (hex(pattern | sign), axis)
+    assert bits(0x80000000)[0] == 0 and np.signbit(bits(0x80000000)[0])                             # (-0.0 is among them)
+    # what the limits and the origin hold does not matter; a NaN component is odd (its reciprocal is not finite), an infinite one is not (1 / inf = 0)
+    r = R.make_rays([[np.nan, 0, np.inf]] * 3, [[1, 2, 3], [1, np.nan, 3], [np.inf, 2, -np.inf]], t_min=np.nan, t_max=-np.inf)
+    assert R.ray_odd(r).tolist() == [False, True, False]
+    assert R.ray_odd(R.make_rays([[0, 0, 0]] * 2, [[0, 0, 0], [-0.0, 0.0, -0.0]])).tolist() == [True, True]
+
+
+def test_a_nan_slab_product_is_no_constraint():
+    # d = (0, 0, 1) from the box's plane x = 0: (0 - 0) * inf is NaN.  The definition: no constraint -- a hit; the defect: the root is skipped
+    bvh = R.build_bvh(TRI)
+    assert one(R.walk(bvh, up(0, 1))[0]) == (2.0, 0.0, 0.25, 0) and one(R.walk(bvh, up(0, 1), defect="nan_prunes")[0]) == MISS
+    # the same with a component whose reciprocal overflows
+    tiny = R.make_rays([[0, 1, 0]], [[F(1e-45), 0, 1]])
+    assert one(R.walk(bvh, tiny)[0]) == (2.0, 0.0, 0.25, 0) and one(R.walk(bvh, tiny, defect="nan_prunes")[0]) == MISS
+    # strictly inside the slab, and outside it, there is no NaN: the defect changes nothing
+    for x in (1, -EPS):
+        assert R.walk(bvh, up(x, 1), defect="nan_prunes")[0].tobytes() == R.walk(bvh, up(x, 1))[0].tobytes()
+    # only odd rays can meet it
+    plain = R.make_rays([[0, 1, 0]], [[2.0 ** -126, 2.0 ** -100, 1]])
+    assert not R.ray_odd(plain)[0] and R.walk(bvh, plain, defect="nan_prunes")[0].tobytes() == R.walk(bvh, plain)[0].tobytes()
+
+
+def test_the_run_tells_no_constraint_from_a_nan_that_prunes(run):
+    tris, rays, want, bvh = run
+    got = R.walk(bvh, rays, defect="nan_prunes")[0]
+    differ = (got != want)
+    assert differ.any() and R.ray_odd(rays)[differ].all()                                          # ... and rays that are not odd are not touched
+
+
+def test_edge_records_against_one_triangle():
+    base = R.make_rays([[1, 1, 0]], [[0.25, 0.5, 1]])                                               # reaches z = 2 at (1.5, 2, 2): u = 0.375, v = 0.5
+    assert one(both(TRI, base)) == (2.0, 0.375, 0.5, 0) and not R.ray_odd(base)[0]
+    e = R.edge_records()
+    assert len(e) == len(R.EDGE_NAMES) == 14 and e.tobytes() == R.edge_records(base).tobytes()
+    assert R.ray_valid(e).tolist() == [False] * R.EDGE_INVALID + [True] * 6
+    assert R.ray_odd(e).tolist() == [True, True, False, False, False, True, False, False] + [False] * 6
+    assert np.signbit(e["direction"][1]).tolist() == [True, False, True] and (e["direction"][1] == 0).all()
+    assert e["t_min"][12] > e["t_max"][12]
+    for any_hit in (False, True):
+        got = both(TRI, e, any_hit=any_hit)
+        assert [tuple(h) for h in got[:13].tolist()] == [MISS] * 13
+        assert tuple(got[13].tolist()) == ((0.0, 0.0, 0.0, 0) if any_hit else (2.0, 0.375, 0.5, 0))
+    # swapped limits WOULD admit the hit of a ray aimed at a target at t = 1: the record is not a miss for want of a triangle
+    at_one = R.make_rays([[1, 1, 1.5]], [[0.25, 0.5, 0.5]])
+    assert one(both(TRI, at_one))[0] == 1.0 and one(both(TRI, R.edge_records(at_one)[12:13])) == MISS
