@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ARCTIC_HIP_LIBRARY") or os.path.join(HERE, "csrc", "libarctic_hip.so")   # the override is for A/B timing of two builds (tools/experiments)
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "arctic_hip.h")
 
-OPTIONS = {"keep_float_output": 1, "count_light_evals": 2, "culling": 3, "debug": 4, "antialias": 5, "hdr16": 6, "ray_refit": 7, "shadow_cache": 9, "visbuffer": 10, "item_table_floor": 11, "light_path": 12, "markers": 13, "shadow_sharded": 14, "frames_in_flight": 15, "tiles_per_wave": 16, "tile_trace": 17, "raster_owner": 18, "tile_order": 19, "order_tail": 20, "sampler": 21, "texture_tiling": 22, "cluster_cull": 23, "small_triangles": 24, "env_lighting": 25, "point_shadow_size": 26, "texture_mips": 27}
+OPTIONS = {"keep_float_output": 1, "count_light_evals": 2, "culling": 3, "debug": 4, "antialias": 5, "hdr16": 6, "ray_refit": 7, "light_pair_runs": 8, "shadow_cache": 9, "visbuffer": 10, "item_table_floor": 11, "light_path": 12, "markers": 13, "shadow_sharded": 14, "frames_in_flight": 15, "tiles_per_wave": 16, "tile_trace": 17, "raster_owner": 18, "tile_order": 19, "order_tail": 20, "sampler": 21, "texture_tiling": 22, "cluster_cull": 23, "small_triangles": 24, "env_lighting": 25, "point_shadow_size": 26, "texture_mips": 27}
 TRACE_ANY, TRACE_BRUTE = 1, 2   # ARCTIC_TRACE_* (include/arctic_hip.h)
 ERRORS = {-1: "ARCTIC_E_INVALID", -2: "ARCTIC_E_DEVICE", -3: "ARCTIC_E_NO_DEVICE", -4: "ARCTIC_E_STATE", -5: "ARCTIC_E_CAPACITY"}
 
@@ -44,6 +44,7 @@ SIGNATURES = {
     "arctic_set_material_extras": (_i32, [_vp, _u64, _vp, _vp, _u32, _u32, _vp, _u32, _u32]),
     "arctic_check_material_params": (_i32, [_vp]),
     "arctic_update_lights": (_i32, [_vp, _vp, _u64]),
+    "arctic_light_pair_table": (_i32, [_vp, _u64, _i32, _vp, _vp, _vp]),
     "arctic_update_spot_lights": (_i32, [_vp, _vp, _u64]),
     "arctic_spot_light_constants": (_i32, [_vp, _u64, _vp]),
     "arctic_update_point_shadow_lights": (_i32, [_vp, _vp, _u64]),

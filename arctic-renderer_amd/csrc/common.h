@@ -288,12 +288,15 @@ struct ShadeParams {
     float ambient;
     float inv_gamma;
     float exposure;
-    uint32_t pad_c0;
+    uint32_t pair_runs;          // the runs of light_pairs: where "skip R", "skip G" and "skip B" end, PAIR_RUN_BITS bits each from bit 0 (the general run ends
+                                 // with the table; the slot was padding); 0 = one general run.  A lit tile reads it next to its batch below: one
+                                 // s_load_dword of its own (byte 140 is not adjacent to byte 160), issued with the batch and behind the same wait
     float *out_ldr;              // optional rows*width*3
     float *out_hdr;              // optional rows*width*3
     float eye[3];                // (byte 160: from here to the end of block D is what a lit tile loads in one batch)
     uint32_t n_lights;
     const float4 *light_pairs;   // the lights as pairs, 3 float4 per pair {x0,x1,y0,y1} {z0,z1,r0,r1} {g0,g1,b0,b1}; an odd count is padded with a black light
+                                 // (the order of the pairs: renderer.cpp, light_pair_table)
     const float4 *lights;        // 2 float4 per light, as uploaded
     // ---- block D, byte 192
     float sun_dir[3];
@@ -343,6 +346,7 @@ struct ShadeParams {
     int32_t band_tiles, shard_index, shard_count, tile_y0;   // local tile row -> global row (see row_global)
     int32_t compact_tables;             // 1: the record, vertex and object tables are below 4 GiB each: k_material_vis addresses them with 32-bit byte offsets
 };
+constexpr uint32_t PAIR_RUN_BITS = 10, PAIR_RUN_MAX = (1u << PAIR_RUN_BITS) - 1;   // ShadeParams::pair_runs; a table of more pairs is one general run
 static_assert(offsetof(ShadeParams, tex) == 64 && offsetof(ShadeParams, ambient) == 128 && offsetof(ShadeParams, sun_dir) == 192 &&
               offsetof(ShadeParams, srgb_lut) == 224, "ShadeParams: the blocks k_material loads in one batch each");
 struct ShadeLaunch {
@@ -409,7 +413,7 @@ struct EnvBuild {
 size_t env_levels_bytes(uint32_t W, uint32_t H);
 size_t env_mips_bytes(uint32_t W, uint32_t H);
 hipError_t launch_env_build(const EnvBuild &b, hipStream_t s);
-constexpr uint32_t N_SHADE_STATS = 9;   // [0..4] light statistics, [5..8] shadow-edge statistics of the fast tile (shade.hip)
+constexpr uint32_t N_SHADE_STATS = 10;  // [0..4] light statistics, [5..8] shadow-edge statistics of the fast tile, [9] pair trips in a run that skips a channel (shade.hip)
 constexpr uint32_t DEFAULT_TILES_PER_WAVE = 2;
 // The dispatch order's slots (geometry.hip k_tile_order, shade.hip next_tile): eight lists -- list x = the strips of tile rows ty = x (mod 8) -- of L slots
 // each (the longest list in whole groups), interleaved in groups of `group` slots: slot (q * 8 + x) * group + k = entry q * group + k of list x.  Block b of

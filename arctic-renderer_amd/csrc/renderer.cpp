@@ -301,6 +301,11 @@ struct ArcticRenderer {
     bool aa_active() const { return antialias == 1 && rows() == height; }
     const void *rgba8_output() const { return output_filtered ? d_aa.p : d_rgba8.p; }
     int light_path = 0;             // ARCTIC_OPT_LIGHT_PATH: 0 automatic, 1 scalar light loop, 2 packed pairs
+    // ARCTIC_OPT_LIGHT_PAIR_RUNS: 1 = the pair table of the packed loop is laid out in runs that skip a colour channel (light_pair_table);
+    // 0 = caller order, one general run.  h_lights: the lights as given, so that the option can rebuild the table; pair_runs: ShadeParams::pair_runs
+    int light_pair_runs = 1;
+    std::vector<ArcticPointLight> h_lights;
+    uint32_t pair_runs = 0;
     bool visbuffer = true;          // arctic_render_frame shades straight from the visibility plane (no G-buffer)
     // per-frame geometry scratch
     PassTables tables[4];   // [0], [2], [3] forward pass (one per frame in flight), [1] shadow pass
@@ -911,7 +916,7 @@ int fill_shade_params(ArcticRenderer *r, const ArcticScene *sc, const ArcticSett
     sp.shadow_map = r->shadow_size ? r->d_shadow().as<float>() : nullptr;
     sp.shadow_size = r->shadow_size;
     sp.lights = r->d_lights.as<float4>(); sp.light_pairs = r->d_light_pairs.as<float4>();
-    sp.n_lights = r->n_lights;
+    sp.n_lights = r->n_lights; sp.pair_runs = r->pair_runs;
     std::memcpy(sp.eye, sc->camera.eye, 12);
     dir_from_rot(sc->sun.rotation, sp.sun_dir);     // DirectionalLight::direction(), scene.cpp:56-59
     std::memcpy(sp.sun_color, sc->sun.color, 12);
@@ -1007,7 +1012,7 @@ int pass_shade(ArcticRenderer *r, const ArcticScene *sc, const ArcticSettings *s
         HIPCHECK(r, hipMemcpyAsync(n, r->d_counter.p, 8 * N_SHADE_STATS, hipMemcpyDeviceToHost, r->stream));
         HIPCHECK(r, hipStreamSynchronize(r->stream));
         r->stats[5] = n[0]; r->stats[6] = n[1]; r->stats[7] = n[2];
-        r->light_stats[0] = n[3]; r->light_stats[1] = n[4];
+        r->light_stats[0] = n[3]; r->light_stats[1] = n[4]; r->stats[4] = n[9];
         for (int i = 0; i < 4; ++i) r->edge_stats[i] = n[5 + i];
     }
     r->have_output = (d_out == nullptr);
@@ -1637,6 +1642,82 @@ int arctic_read_mesh_vertices(ArcticRenderer *r, uint64_t mesh, ArcticVertex *ou
     return ARCTIC_OK;
 }
 
+// ---- the pair table of the packed light loop (common.h: ShadeParams::light_pairs, pair_runs; the exactness contract: shade.hip, accumulate_pair) ----
+// A light whose colour channel is +0.0f BY ITS BITS adds +-0 to that channel's three sums; a pair of two such lights needs none of the three
+// packed multiply-adds.  (-0.0f, denormals, NaN and Inf count as non-zero: only +0 leaves the sums' bits alone whatever it is multiplied with.)
+// The table is therefore built from a stable partition of the lights by the lowest zero channel (class 0, 1, 2 = R, G, B; 3 = none), pairs are
+// formed along that sequence -- the odd light at the end of a class pairs with the first light of the next, the black partner of an odd total
+// (mask 7) comes last -- and the pairs are laid out, stably, as four runs: skip R, skip G, skip B, general.  A pair's mask is the AND of its
+// lights' masks; it goes to the run of its lowest set bit, the partner's pair always to the end of the general run (the counting kernels know
+// the partner by its place).  runs = false: caller order, one general run -- the table of earlier builds.
+namespace {
+constexpr uint32_t PAIR_PARTNER = 0xFFFFFFFFu;   // slot of the black partner
+uint32_t zero_channels(const ArcticPointLight &l) {
+    uint32_t m = 0;
+    for (int c = 0; c < 3; ++c) { uint32_t b; std::memcpy(&b, &l.color[c], 4); m |= (b == 0u ? 1u : 0u) << c; }
+    return m;
+}
+uint32_t run_of_mask(uint32_t m) { return m & 1u ? 0u : m & 2u ? 1u : m & 4u ? 2u : 3u; }
+// slots: 2 * n_pairs light indices (pair p = slots[2p], slots[2p + 1]); masks: n_pairs; run_end: where the runs R, G and B end (the general run ends at n_pairs)
+void light_pair_table(const ArcticPointLight *lights, uint32_t k, bool runs, std::vector<uint32_t> &slots, std::vector<uint32_t> &masks, uint32_t run_end[3]) {
+    const uint32_t n_pairs = (k + 1) / 2;
+    std::vector<uint32_t> seq; seq.reserve(2 * (size_t)n_pairs);
+    if (runs && n_pairs <= PAIR_RUN_MAX) {
+        for (uint32_t c = 0; c < 4; ++c)
+            for (uint32_t i = 0; i < k; ++i) if (run_of_mask(zero_channels(lights[i])) == c) seq.push_back(i);
+    } else {
+        runs = false;
+        for (uint32_t i = 0; i < k; ++i) seq.push_back(i);
+    }
+    if (k & 1u) seq.push_back(PAIR_PARTNER);
+    auto mask_of = [&](uint32_t s) { return s == PAIR_PARTNER ? 7u : zero_channels(lights[s]); };
+    slots.clear(); masks.clear();
+    uint32_t end[4] = {0, 0, 0, 0};
+    for (uint32_t c = 0; c < 4; ++c) {
+        for (uint32_t p = 0; p < n_pairs; ++p) {
+            const uint32_t a = seq[2 * p], b = seq[2 * p + 1], m = mask_of(a) & mask_of(b);
+            if ((runs && b != PAIR_PARTNER ? run_of_mask(m) : 3u) != c) continue;
+            slots.push_back(a); slots.push_back(b); masks.push_back(m);
+        }
+        end[c] = (uint32_t)masks.size();
+    }
+    run_end[0] = end[0]; run_end[1] = end[1]; run_end[2] = end[2];
+}
+}   // namespace
+
+// the table as plain numbers (a pure host function: tests/test_light_pair_table.py)
+int arctic_light_pair_table(const ArcticPointLight *lights, uint64_t n, int32_t runs, uint32_t *slots, uint32_t *masks, uint32_t *run_end) {
+    if ((n && !lights) || n > 0x7FFFFFFFull || (n && (!slots || !masks)) || !run_end) return ARCTIC_E_INVALID;
+    std::vector<uint32_t> s, m;
+    light_pair_table(lights, (uint32_t)n, runs != 0, s, m, run_end);
+    if (!s.empty()) std::memcpy(slots, s.data(), s.size() * 4);
+    if (!m.empty()) std::memcpy(masks, m.data(), m.size() * 4);
+    return ARCTIC_OK;
+}
+
+namespace {
+// the handle's lights as pairs for the packed loop; an odd count gets a black partner
+int upload_light_pairs(ArcticRenderer *r) {
+    const ArcticPointLight *lights = r->h_lights.data();
+    const uint32_t k = (uint32_t)r->h_lights.size(), n_pairs = (k + 1) / 2;
+    std::vector<uint32_t> slots, masks;
+    uint32_t run_end[3];
+    light_pair_table(lights, k, r->light_pair_runs != 0, slots, masks, run_end);
+    std::vector<float> pairs((size_t)std::max(1u, n_pairs) * 12, 0.0f);
+    for (uint32_t i = 0; i < 2 * n_pairs; ++i) {
+        float *dst = pairs.data() + (size_t)(i / 2) * 12 + (i & 1);
+        const uint32_t s = slots[i];
+        if (s != PAIR_PARTNER) { dst[0] = lights[s].position[0]; dst[2] = lights[s].position[1]; dst[4] = lights[s].position[2];
+                                 dst[6] = lights[s].color[0]; dst[8] = lights[s].color[1]; dst[10] = lights[s].color[2]; }
+        else { dst[0] = 0.0f; dst[2] = 1.0e6f; dst[4] = 0.0f; dst[6] = dst[8] = dst[10] = 0.0f; }
+    }
+    HIPCHECK(r, r->d_light_pairs.ensure(pairs.size() * 4));
+    HIPCHECK(r, hipMemcpy(r->d_light_pairs.p, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice));
+    r->pair_runs = run_end[0] | run_end[1] << PAIR_RUN_BITS | run_end[2] << (2 * PAIR_RUN_BITS);
+    return ARCTIC_OK;
+}
+}   // namespace
+
 int arctic_update_lights(ArcticRenderer *r, const ArcticPointLight *lights, uint64_t n) {
     if (!r) return ARCTIC_E_INVALID;
     if (n && !lights) return r->fail(ARCTIC_E_INVALID, "update_lights: null");
@@ -1644,19 +1725,9 @@ int arctic_update_lights(ArcticRenderer *r, const ArcticPointLight *lights, uint
     if (rc) return rc;
     uint32_t k = (uint32_t)std::min<uint64_t>(n, r->max_lights);   // renderer.cpp:587-588
     HIPCHECK(r, hipStreamSynchronize(r->stream));
-    if (k) HIPCHECK(r, hipMemcpy(r->d_lights.p, lights, (size_t)k * sizeof(ArcticPointLight), hipMemcpyHostToDevice));
-    {   // the same lights as pairs for the packed loop (common.h: ShadeParams::light_pairs); an odd count gets a black partner
-        const uint32_t n_pairs = (k + 1) / 2;
-        std::vector<float> pairs((size_t)std::max(1u, n_pairs) * 12, 0.0f);
-        for (uint32_t i = 0; i < 2 * n_pairs; ++i) {
-            float *dst = pairs.data() + (size_t)(i / 2) * 12 + (i & 1);
-            if (i < k) { dst[0] = lights[i].position[0]; dst[2] = lights[i].position[1]; dst[4] = lights[i].position[2];
-                         dst[6] = lights[i].color[0]; dst[8] = lights[i].color[1]; dst[10] = lights[i].color[2]; }
-            else { dst[0] = 0.0f; dst[2] = 1.0e6f; dst[4] = 0.0f; dst[6] = dst[8] = dst[10] = 0.0f; }
-        }
-        HIPCHECK(r, r->d_light_pairs.ensure(pairs.size() * 4));
-        HIPCHECK(r, hipMemcpy(r->d_light_pairs.p, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice));
-    }
+    if (k) HIPCHECK(r, hipMemcpy(r->d_lights.p, lights, (size_t)k * sizeof(ArcticPointLight), hipMemcpyHostToDevice));   // (caller order: the scalar loop, the statistics)
+    r->h_lights.assign(lights, lights + k);
+    if ((rc = upload_light_pairs(r)) != ARCTIC_OK) return rc;
     r->n_lights = k;
     return ARCTIC_OK;
 }
@@ -2349,6 +2420,16 @@ int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
         if (value < 0 || value > 2) return r->fail(ARCTIC_E_INVALID, "set_option: light path must be 0..2");
         r->light_path = (int)value;
         break;
+    case ARCTIC_OPT_LIGHT_PAIR_RUNS: {
+        if (value < 0 || value > 1) return r->fail(ARCTIC_E_INVALID, "ARCTIC_OPT_LIGHT_PAIR_RUNS: 0 or 1");
+        if ((int)value == r->light_pair_runs) break;
+        int rc = select_device(r);
+        if (rc) return rc;
+        HIPCHECK(r, hipStreamSynchronize(r->stream));   // (the table in place may be being read)
+        r->light_pair_runs = (int)value;
+        if ((rc = upload_light_pairs(r)) != ARCTIC_OK) return rc;
+        break;
+    }
     case ARCTIC_OPT_ITEM_TABLE_FLOOR:
         if (value < 64 || value > 0x7FFFFFF0ll) return r->fail(ARCTIC_E_INVALID, "set_option: item table floor out of range");
         r->item_cap_floor = (uint32_t)value; r->geo[0].item_cap = r->geo[1].item_cap = r->geo[2].item_cap = r->geo[3].item_cap = 0;

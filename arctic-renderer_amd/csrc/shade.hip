@@ -29,6 +29,7 @@
 // per-channel budget of the output.  The file is compiled with -ffp-contract=off and every fused
 // multiply-add is written out, so k_material and k_material_vis round identically (their images are
 // compared bit for bit).
+#include <type_traits>
 #include "common.h"
 #include "edges.h"
 #include "shadow_coords.h"
@@ -113,10 +114,10 @@ __device__ __forceinline__ EpiArgs epi_args(KernArgs a) {
 __device__ __forceinline__ ShadowArgs shadow_args(SP sp) { ShadowArgs r = {sp.shadow_map, sp.shadow_bounds, sp.shadow_size, sp.bounds_pitch}; return r; }
 __device__ __forceinline__ StoreArgs store_args(SP sp) { StoreArgs r = {sp.hdr16, sp.debug, sp.tm_method, sp.exposure, sp.inv_gamma, sp.out_ldr, sp.out_hdr}; return r; }
 // the lit pixels' constants: eye and the light list (in front of the light loop), the sun (where it is evaluated: behind the packed loop)
-struct LightArgs { float eye[3]; uint32_t n_lights; const float4 *pairs, *lights; };
+struct LightArgs { float eye[3]; uint32_t n_lights; const float4 *pairs, *lights; uint32_t pair_runs; };
 __device__ __forceinline__ LightArgs light_args(SP sp) {
-    LightArgs r = {{sp.eye[0], sp.eye[1], sp.eye[2]}, sp.n_lights, sp.light_pairs, sp.lights};
-    asm volatile("" : "+s"(r.eye[0]), "+s"(r.eye[1]), "+s"(r.eye[2]), "+s"(r.n_lights), "+s"(r.pairs), "+s"(r.lights));
+    LightArgs r = {{sp.eye[0], sp.eye[1], sp.eye[2]}, sp.n_lights, sp.light_pairs, sp.lights, sp.pair_runs};
+    asm volatile("" : "+s"(r.eye[0]), "+s"(r.eye[1]), "+s"(r.eye[2]), "+s"(r.n_lights), "+s"(r.pairs), "+s"(r.lights), "+s"(r.pair_runs));
     return r;
 }
 struct SunArgs { float dir[3], color[3]; };
@@ -627,6 +628,17 @@ __device__ __forceinline__ void wait_and_sub(v2 lx, v2 ly, v2 lz, v2 w_xy, v2 wz
 
 // light_scalars<true> for the two point lights of a pair (d = position - world from wait_and_sub, colours cr, cg, cb in SGPR
 // pairs): lane-wise the same arithmetic as the scalar loop.  nd (n . d of both lights) is returned for the statistics.
+//
+// SKIP = 0, 1, 2 leaves out the three sums of R, G or B: the host puts a pair into such a run only when that channel of BOTH its lights is
+// +0.0f by its bits (renderer.cpp: light_pair_table; ShadeParams::pair_runs).  The contract:
+//   * The skip itself is exact.  The sums start at +0, and (+0) * s is +-0 for every finite s: adding it changes no bit of a sum.
+//   * The table's order is not the caller's: the lights are partitioned by their zero channel and the pairs laid out run by run, so with more
+//     than two lights the SUMMATION ORDER differs from a table in caller order -- and a frame may differ from it in the last bits, the same
+//     kind of difference as between the scalar and the packed loop.
+//   * Up to two point lights, or lights that all have the same zero channels: the table is the one in caller order, the frame bit for bit the
+//     same.  So is a list that arrives ordered by lowest zero channel (R, G, B, none) with an even count in every class but the last.
+// ARCTIC_OPT_LIGHT_PAIR_RUNS = 0 is the table in caller order as one general run (SKIP = 3: all nine sums).
+template <int SKIP>
 __device__ __forceinline__ v2 accumulate_pair(const PackedPix &k, v2 dx, v2 dy, v2 dz, v2 cr, v2 cg, v2 cb, Sums2 &S) {
     const v2 d2 = pk_fma(dz, dz, pk_fma(dy, dy, dx * dx));
     v2 ndx;                                                                     // n.x d.x, in the shadow of the rsq
@@ -648,9 +660,9 @@ __device__ __forceinline__ v2 accumulate_pair(const PackedPix &k, v2 dx, v2 dy, 
     const v2 p5 = m2 * m2 * m;
     const v2 s2 = (sc * ndwi) * rden;
     const v2 s1 = pk_fma(-sc, p5, sc), s3 = s2 * p5;
-    pk_fma_s(cr, s1, S.a[0]); pk_fma_s(cg, s1, S.a[1]); pk_fma_s(cb, s1, S.a[2]);
-    pk_fma_s(cr, s2, S.b[0]); pk_fma_s(cg, s2, S.b[1]); pk_fma_s(cb, s2, S.b[2]);
-    pk_fma_s(cr, s3, S.c[0]); pk_fma_s(cg, s3, S.c[1]); pk_fma_s(cb, s3, S.c[2]);
+    if (SKIP != 0) pk_fma_s(cr, s1, S.a[0]); if (SKIP != 1) pk_fma_s(cg, s1, S.a[1]); if (SKIP != 2) pk_fma_s(cb, s1, S.a[2]);
+    if (SKIP != 0) pk_fma_s(cr, s2, S.b[0]); if (SKIP != 1) pk_fma_s(cg, s2, S.b[1]); if (SKIP != 2) pk_fma_s(cb, s2, S.b[2]);
+    if (SKIP != 0) pk_fma_s(cr, s3, S.c[0]); if (SKIP != 1) pk_fma_s(cg, s3, S.c[1]); if (SKIP != 2) pk_fma_s(cb, s3, S.c[2]);
     return nd;
 }
 
@@ -904,6 +916,7 @@ __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float
     TailPix tp;
     make_pix(n, wo, world, base, metal, rough, px, tp);
     unsigned long long contributing = 0ull, wave_zero = 0ull;   // STATS
+    uint32_t skip_trips = 0;                                    // STATS: trips of this tile in a run that skips a channel
     f3 Lo;
     if (LOOP == 1) {
         Sums S;
@@ -942,9 +955,9 @@ __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float
         // hundreds of cycles after its loads).  Written as asm because the compiler's own version addresses every dword separately
         // (40 scalar instructions per trip) and waits right after issuing.
         const char *lp = reinterpret_cast<const char *>(la.pairs);
-        auto finish = [&](v2 dx, v2 dy, v2 dz, const f4v &Bq, const f4v &C, uint32_t p) {
-            const v2 nd = accumulate_pair(pk, dx, dy, dz, (v2){Bq.z, Bq.w}, (v2){C.x, C.y}, (v2){C.z, C.w}, S);
-            if (STATS) {
+        auto finish = [&](auto skip, v2 dx, v2 dy, v2 dz, const f4v &Bq, const f4v &C, uint32_t p) {
+            const v2 nd = accumulate_pair<decltype(skip)::value>(pk, dx, dy, dz, (v2){Bq.z, Bq.w}, (v2){C.x, C.y}, (v2){C.z, C.w}, S);
+            if (STATS) {   // (the black partner of an odd count is the second light of the LAST pair, whatever the runs)
                 const bool second = 2 * p + 1 < la.n_lights;
                 const unsigned long long m0 = __ballot(nd.x > 0.0f), m1 = second ? __ballot(nd.y > 0.0f) : ~0ull;
                 contributing += __popcll(m0) + (second ? __popcll(m1) : 0);
@@ -952,21 +965,38 @@ __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float
             }
         };
         if (n_pairs) {
+            // The table is four runs of pairs, one after the other: skip R, skip G, skip B, general (ShadeParams::pair_runs; a boundary past the
+            // table cannot happen, the clamp makes that a fact of this code).  Pair p sits in set p & 1 through all of them, and a trip asks for
+            // pair p + 1 whichever run that belongs to: a run boundary adds no wait.
+            const uint32_t run_mask = (1u << PAIR_RUN_BITS) - 1;
+            const uint32_t end_r = min(la.pair_runs & run_mask, n_pairs), end_g = min((la.pair_runs >> PAIR_RUN_BITS) & run_mask, n_pairs),
+                           end_b = min((la.pair_runs >> (2 * PAIR_RUN_BITS)) & run_mask, n_pairs);
+            if (STATS) skip_trips = end_b;   // (the three skip runs are [0, end_b): what the loops below walk with SKIP != 3)
             f4v A0, B0, C0, A1, B1, C1;
-            v2 dx, dy, dz;
+            uint32_t p = 0;
             load_light_pair(lp, A0, B0, C0);
-            for (uint32_t p = 0;;) {
-                wait_and_sub((v2){A0.x, A0.y}, (v2){A0.z, A0.w}, (v2){B0.x, B0.y}, pk.w_xy, pk.wz_a2, dx, dy, dz);   // set 0 has landed
-                if (p + 1 < n_pairs) load_light_pair(lp + 48 * (p + 1), A1, B1, C1);                                  // set 1 in flight
-                finish(dx, dy, dz, B0, C0, p);
-                if (++p == n_pairs) break;
-                wait_and_sub((v2){A1.x, A1.y}, (v2){A1.z, A1.w}, (v2){B1.x, B1.y}, pk.w_xy, pk.wz_a2, dx, dy, dz);
-                if (p + 1 < n_pairs) load_light_pair(lp + 48 * (p + 1), A0, B0, C0);
-                finish(dx, dy, dz, B1, C1, p);
-                if (++p == n_pairs) break;
-            }
+            // one trip: pair p has landed in (A, B, C); pair p + 1 goes in flight into the other set (An, Bn, Cn)
+            auto trip = [&](auto skip, const f4v &A, const f4v &B, const f4v &C, f4v &An, f4v &Bn, f4v &Cn) {
+                v2 dx, dy, dz;
+                wait_and_sub((v2){A.x, A.y}, (v2){A.z, A.w}, (v2){B.x, B.y}, pk.w_xy, pk.wz_a2, dx, dy, dz);
+                if (p + 1 < n_pairs) load_light_pair(lp + 48 * (p + 1), An, Bn, Cn);
+                finish(skip, dx, dy, dz, B, C, p);
+                ++p;
+            };
+            auto run = [&](auto skip, uint32_t end) {
+                if (p < end && (p & 1u)) trip(skip, A1, B1, C1, A0, B0, C0);
+                while (p < end) {
+                    trip(skip, A0, B0, C0, A1, B1, C1);
+                    if (p == end) break;
+                    trip(skip, A1, B1, C1, A0, B0, C0);
+                }
+            };
+            run(std::integral_constant<int, 0>{}, end_r);
+            run(std::integral_constant<int, 1>{}, end_g);
+            run(std::integral_constant<int, 2>{}, end_b);
+            run(std::integral_constant<int, 3>{}, n_pairs);
             // No load is in flight here (the last trip issues none), but only the trip counts say so: a path-insensitive reader of the ISA --
-            // tools/isa_lint.py follows every asm scalar load along every branch to its wait -- sees the loop's exits behind a load of the
+            // tools/isa_lint.py follows every asm scalar load along every branch to its wait -- sees the loops' exits behind a load of the
             // other set.  One scalar instruction per lit tile makes "nothing of a light pair is pending behind the loop" a fact of the code.
             asm volatile("s_waitcnt lgkmcnt(0)");
         }
@@ -994,6 +1024,7 @@ __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float
             atomicAdd(sp.stats + 2, contributing);                                     // ... of which n.wi > 0
             atomicAdd(sp.stats + 3, wave_zero);                                        // (tile, light) pairs with n.wi <= 0 in every lit lane
             atomicAdd(sp.stats + 4, 1ull);                                             // tiles with a lit pixel
+            if (LOOP == 2) atomicAdd(sp.stats + 9, (unsigned long long)skip_trips);                  // (tile, pair) trips of the packed loop in a run that skips a channel
         }
     }
     return Lo;

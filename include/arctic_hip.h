@@ -348,6 +348,11 @@ int arctic_check_material_params(const ArcticMaterialParams *params);
 /* replaces void Renderer::update_lights(span<PointLight>) (renderer.hpp:120,
  * renderer.cpp:585-603): clamps to max_lights like the reference clamps to 16. */
 int arctic_update_lights(ArcticRenderer *r, const ArcticPointLight *lights, uint64_t n);
+/* The pair table the packed light loop walks (ARCTIC_OPT_LIGHT_PAIR_RUNS) as plain numbers, for tests; a pure host function.  slots: 2 * ceil(n / 2)
+ * light indices, pair p = slots[2 p], slots[2 p + 1], 0xFFFFFFFF = the black partner of an odd count; masks: ceil(n / 2), bit c set = channel c of
+ * both lights is +0.0f; run_end: 3 numbers, where the runs "skip R", "skip G" and "skip B" end (the general run ends with the table).  runs = 0: the
+ * table in caller order, one general run. */
+int arctic_light_pair_table(const ArcticPointLight *lights, uint64_t n, int32_t runs, uint32_t *slots, uint32_t *masks, uint32_t *run_end);
 
 /* Spot lights (no counterpart in the reference).  Works like arctic_update_lights: replaces the handle's spot list, clamps the count to
  * max_lights; n = 0 clears the list.  A light with a NaN or inf field, a zero direction, inner > outer, outer outside (0, pi] or range < 0
@@ -489,7 +494,10 @@ int arctic_frame_constants(const ArcticScene *scene, float *proj_view, float *li
 
 /* counters of the last frame: [0] setup triangles (forward), [1] raster work
  * items (forward), [2] setup triangles (shadow), [3] raster work items
- * (shadow), [4] reserved; with ARCTIC_OPT_COUNT_LIGHT_EVALS: [5] point-light
+ * (shadow), [4] with ARCTIC_OPT_COUNT_LIGHT_EVALS: (lit tile, light pair)
+ * trips of the packed light loop that ran in a run which leaves out a colour
+ * channel (ARCTIC_OPT_LIGHT_PAIR_RUNS; 0 with the scalar loop or the option at
+ * 0); with ARCTIC_OPT_COUNT_LIGHT_EVALS: [5] point-light
  * evaluations summed over lit pixels, [6] lit pixels (1 - shadow != 0),
  * [7] evaluations with n.wi > 0 (the others contribute exactly 0,
  * forward.hlsl:191-192), [8] (tile, light) pairs whose n.wi <= 0 in every lit
@@ -520,6 +528,11 @@ int arctic_stats(ArcticRenderer *r, uint64_t *out, uint32_t n);
                                           bit 10 the prepasses count the workgroups ARCTIC_OPT_CLUSTER_CULL skipped (arctic_read_cull_counts; same image) */
 #define ARCTIC_OPT_HDR16             6 /* 1 = round ps_main's colour through binary16 before post_process, like the reference's
                                         R16G16B16A16_FLOAT colour target (forward_pass.cpp:149, renderer.cpp:128-144); default 0 = fp32 */
+#define ARCTIC_OPT_LIGHT_PAIR_RUNS   8 /* 1 (default) = the packed loop walks its pairs in runs that leave out the sums of a colour channel both lights have as +0.0f
+                                          (an exact skip; the lights are regrouped for it, so with more than two lights a frame may differ in the last bits from 0);
+                                          0 = pairs in the caller's order, all sums: a parity aid.  The number is a reused one: ARCTIC_OPT_FUSED (the persistent
+                                          one-kernel shading pass, measured slower and removed) had it; a client that still sets 8 to 0 gets the caller's order, which is
+                                          always a correct image (numbers above 27 are not taken so that the option count stays what the ABI tests pin) */
 #define ARCTIC_OPT_SHADOW_CACHE      9 /* 1 (default) = arctic_render_frame redraws the shadow map only when the sun, the objects or the mesh list changed
                                           (byte-compared); 0 = every frame like the reference (renderer.cpp:300-337).  Same image either way. */
 #define ARCTIC_OPT_FRAMES_IN_FLIGHT  15 /* 2 = arctic_render_frame runs the visibility prepass of a frame on a second stream, into a second set of
