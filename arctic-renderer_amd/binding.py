@@ -92,6 +92,9 @@ SIGNATURES = {
     "arctic_ray_scene_resplit": (_i32, [_vp, _scene]),
     "arctic_ray_resplit_info": (_i32, [_vp, _vp]),
     "arctic_resplit_triangles": (_i32, [_vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "arctic_trace_ambient_occlusion": (_i32, [_vp, _scene, _vp, _vp, _vp]),
+    "arctic_trace_ambient_occlusion_device": (_i32, [_vp, _scene, _vp, _vp, _vp]),
+    "arctic_ambient_occlusion_points": (_i32, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u32, _vp]),
     "arctic_version": (_i32, []),
     # include/arctic_dist.h: the multi-GPU exchange steps
     "arctic_comm_unique_id": (_i32, [_vp, _vp, _u64]),

@@ -22,6 +22,7 @@
 #include "../../include/arctic_dist.h"
 #include "common.h"
 #include "ray_query.h"
+#include "ray_ao.h"
 
 using namespace arctic;
 
@@ -434,6 +435,16 @@ struct ArcticRenderer {
         uint64_t resplit_slots = ~0ull;            // the slot count resplit_bytes was worked out for
         uint64_t resplits = 0, resplit_launches = 0, resplit_fell_back = 0;
     } ray;
+    // Ambient occlusion (arctic_trace_ambient_occlusion, ray_ao.hip): the direction table on the device -- at most 12 KiB, sent from a pinned copy
+    // that is also what the device holds, so an unchanged table is not sent again and the pinned copy is rewritten only after the copy that last
+    // read it has completed --, the hits plane and the result, one byte per pixel of the handle's rows each.  Nothing is allocated before the first call
+    struct AmbientOcclusion {
+        DevBuf d_dirs, d_hits, d_out;
+        float *h_dirs = nullptr;
+        size_t n_floats = 0;                       // what d_dirs holds (0: nothing)
+        hipEvent_t copied = nullptr;
+        bool pending = false;
+    } ao;
     uint32_t *dh_counts = nullptr;  // the device's address of h_counts
     uint32_t *h_counts = nullptr;   // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     std::string err;
@@ -1226,6 +1237,9 @@ void arctic_destroy(ArcticRenderer *r) {
         if (r->ray.h_objs[k]) (void)hipHostFree(r->ray.h_objs[k]);
         if (r->ray.ev_objs[k]) (void)hipEventDestroy(r->ray.ev_objs[k]);
     }
+    for (DevBuf *b : {&r->ao.d_dirs, &r->ao.d_hits, &r->ao.d_out}) b->release();
+    if (r->ao.h_dirs) (void)hipHostFree(r->ao.h_dirs);
+    if (r->ao.copied) (void)hipEventDestroy(r->ao.copied);
     delete r;
 }
 
@@ -2698,6 +2712,63 @@ int arctic_trace_sun_visibility(ArcticRenderer *r, const ArcticScene *scene, flo
         if (int ov = check_item_overflow(r)) return ov;
     }
     return ARCTIC_OK;
+}
+
+namespace {
+// the checks, the G-buffer, the structure, the table and the launches of both ambient-occlusion calls; d_out: the caller's device memory, or null = the handle's own
+int trace_ambient_occlusion(ArcticRenderer *r, const ArcticScene *scene, const ArcticAmbientOcclusion *ao, const float *dirs, uint8_t *d_out, const char *who) {
+    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
+    AoDesc d;
+    if (ao) std::memcpy(&d, ao, sizeof d);
+    if (const char *why = ao_refusal(ao ? &d : nullptr, dirs)) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
+    int rc = select_device(r);
+    if (rc) return rc;
+    if (!r->have_gbuffer && !r->have_vis) return r->fail(ARCTIC_E_STATE, "%s: no G-buffer (arctic_pass_gbuffer, arctic_write_gbuffer or a frame first)", who);
+    if (d.filter && r->rows() != r->height)
+        return r->fail(ARCTIC_E_STATE, "%s: the filter needs the whole frame, this handle owns %u of %u rows (its neighbours' rows are on other shards)", who, r->rows(), r->height);
+    if (!r->have_gbuffer && (rc = resolve_gbuffer(r)) != ARCTIC_OK) return rc;   // the frame was shaded from the visibility plane
+    if ((rc = ensure_ray_scene(r, scene)) != ARCTIC_OK) return rc;
+    ArcticRenderer::AmbientOcclusion &A = r->ao;
+    const size_t n_floats = (size_t)d.pattern * d.pattern * d.n_rays * 3, bytes = (size_t)r->rows() * r->width;
+    if (!A.h_dirs) {
+        HIPCHECK(r, hipHostMalloc((void **)&A.h_dirs, 16 * AO_MAX_RAYS * 3 * sizeof(float)));
+        HIPCHECK(r, hipEventCreateWithFlags(&A.copied, hipEventDisableTiming));
+        HIPCHECK(r, A.d_dirs.ensure(16 * AO_MAX_RAYS * 3 * sizeof(float)));
+    }
+    if (A.n_floats != n_floats || std::memcmp(A.h_dirs, dirs, n_floats * sizeof(float)) != 0) {
+        if (A.pending) { HIPCHECK(r, hipEventSynchronize(A.copied)); A.pending = false; }
+        A.n_floats = 0;
+        std::memcpy(A.h_dirs, dirs, n_floats * sizeof(float));
+        HIPCHECK(r, hipMemcpyAsync(A.d_dirs.p, A.h_dirs, n_floats * sizeof(float), hipMemcpyHostToDevice, r->stream));
+        HIPCHECK(r, hipEventRecord(A.copied, r->stream));
+        A.pending = true; A.n_floats = n_floats;
+    }
+    if (d.filter) HIPCHECK(r, A.d_hits.ensure(std::max<size_t>(bytes, 16)));
+    if (!d_out) { HIPCHECK(r, A.d_out.ensure(std::max<size_t>(bytes, 16))); d_out = A.d_out.as<uint8_t>(); }
+    const GBuffer g = r->gbuffer();
+    // (a band's first row is a multiple of 8 in the frame and in the shard alike, so the shard's row and the frame's agree modulo the pattern)
+    const uint32_t frame_row0 = r->band_rows ? 0u : r->row_begin;
+    HIPCHECK(r, launch_trace_ao(g.b, g.c, g.e, r->tiles_x, r->tiles_y, r->width, r->rows(), r->row0_in_tile, frame_row0, d, A.d_dirs.as<float>(), r->ray.d_nodes.p, r->ray.d_tris.p,
+                                (uint32_t)r->ray.n_nodes, d.filter ? 0 : 1, d.filter ? A.d_hits.as<uint8_t>() : d_out, r->stream));
+    if (d.filter) HIPCHECK(r, launch_ao_filter(g.b, g.c, g.e, r->tiles_x, r->tiles_y, r->width, r->rows(), d, A.d_hits.as<uint8_t>(), d_out, r->stream));
+    return ARCTIC_OK;
+}
+}  // namespace
+
+int arctic_trace_ambient_occlusion(ArcticRenderer *r, const ArcticScene *scene, const ArcticAmbientOcclusion *ao, const float *dirs, uint8_t *out) {
+    if (!r) return ARCTIC_E_INVALID;
+    int rc = trace_ambient_occlusion(r, scene, ao, dirs, nullptr, "trace_ambient_occlusion");
+    if (rc || !out) return rc;
+    HIPCHECK(r, hipMemcpyAsync(out, r->ao.d_out.p, (size_t)r->rows() * r->width, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    if (int ov = check_item_overflow(r)) return ov;
+    return ARCTIC_OK;
+}
+
+int arctic_trace_ambient_occlusion_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticAmbientOcclusion *ao, const float *dirs, uint8_t *d_out) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!d_out) return r->fail(ARCTIC_E_INVALID, "trace_ambient_occlusion_device: null output");
+    return trace_ambient_occlusion(r, scene, ao, dirs, d_out, "trace_ambient_occlusion_device");
 }
 
 int arctic_ray_scene_info(ArcticRenderer *r, uint64_t *out4) {

@@ -256,6 +256,22 @@ class Renderer {
         return arctic_trace_triangles(tris9, n_tris, rays, n, flags, hits) == ARCTIC_OK;
     }
 
+    // ambient occlusion from the resident G-buffer (include/arctic_hip.h: arctic_trace_ambient_occlusion and the definition in front of it): n_rays
+    // any-hit rays of length radius per pixel from dirs (P * P sets of n_rays local directions, z along the normal) -> rows x width bytes of
+    // visibility, 255 = open; out = nullptr leaves it on the device.  The filter (whole frames only) sums over the P x P window of the pattern
+    [[nodiscard]] bool trace_ambient_occlusion(const ArcticScene &scene, const ArcticAmbientOcclusion &ao, const float *dirs, uint8_t *out) {
+        return ok(arctic_trace_ambient_occlusion(m_handle, &scene, &ao, dirs, out));
+    }
+    // the same into device memory the caller owns, in stream order on the handle's stream
+    [[nodiscard]] bool trace_ambient_occlusion_device(const ArcticScene &scene, const ArcticAmbientOcclusion &ao, const float *dirs, uint8_t *d_out) {
+        return ok(arctic_trace_ambient_occlusion_device(m_handle, &scene, &ao, dirs, d_out));
+    }
+    // its host arbiter: hits per point {world3, normal3} with direction set sets[k] (no handle, no GPU)
+    [[nodiscard]] static bool ambient_occlusion_points(const float *tris9, uint64_t n_tris, const float *points6, const uint32_t *sets, uint64_t n_points,
+                                                       const ArcticAmbientOcclusion &ao, const float *dirs, uint32_t flags, uint8_t *hits) {
+        return arctic_ambient_occlusion_points(tris9, n_tris, points6, sets, n_points, &ao, dirs, flags, hits) == ARCTIC_OK;
+    }
+
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }
 

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (AO_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -219,6 +219,25 @@ class Renderer:
         mask = np.empty((self.rows, self.width), np.uint8) if read else None
         self._check(self.L.arctic_trace_sun_visibility(self.h, C.byref(s), float(bias), _ptr(mask)))
         return mask
+
+    # ---- ambient occlusion (include/arctic_hip.h: arctic_trace_ambient_occlusion and the definition in front of it) -------------
+    def trace_ambient_occlusion(self, desc, dirs, n_rays=None, pattern=None, radius=np.inf, bias=1e-3, filter=False, normal_cos=0.9, plane_dist=0.05, read=True):
+        """n_rays any-hit rays of length radius per pixel of the resident G-buffer, from world + bias * m along dirs -- (P * P, n_rays, 3) float32
+        local directions, z along the normal, e.g. ao_directions(n_rays, P); n_rays and pattern default to its shape: (rows, width) uint8
+        visibility, 255 = open or no geometry.  filter: the edge-aware sum over the P x P window (whole frames only).  read=False leaves the
+        result on the device and returns None (timing)."""
+        s = self._scene(desc)
+        ao, d = _ao_arguments(dirs, n_rays, pattern, radius, bias, filter, normal_cos, plane_dist)
+        out = np.empty((self.rows, self.width), np.uint8) if read else None
+        self._check(self.L.arctic_trace_ambient_occlusion(self.h, C.byref(s), _ptr(ao), _ptr(d), _ptr(out)))
+        return out
+
+    def trace_ambient_occlusion_device(self, desc, dirs, d_out_ptr, n_rays=None, pattern=None, radius=np.inf, bias=1e-3, filter=False, normal_cos=0.9, plane_dist=0.05):
+        """the same into device memory the caller owns (an int pointer, e.g. a torch tensor's .data_ptr(); rows * width bytes); asynchronous on
+        the handle's stream."""
+        s = self._scene(desc)
+        ao, d = _ao_arguments(dirs, n_rays, pattern, radius, bias, filter, normal_cos, plane_dist)
+        self._check(self.L.arctic_trace_ambient_occlusion_device(self.h, C.byref(s), _ptr(ao), _ptr(d), C.c_void_p(d_out_ptr) if d_out_ptr else None))
 
     def ray_scene_info(self):
         """(triangles stored, nodes, builds so far, depth) of the cached acceleration structure"""
@@ -581,6 +600,60 @@ def trace_triangles(triangles, rays, any_hit=False, brute=False):
     if rc < 0:
         raise ArcticError(rc, "trace_triangles")
     return hits
+
+
+def _ao_arguments(dirs, n_rays, pattern, radius, bias, filter, normal_cos, plane_dist):
+    """(one AO_DTYPE record, the table as a flat float32 array).  n_rays / pattern: from a (P * P, n_rays, 3) table where not given; the library
+    checks every value"""
+    d = np.ascontiguousarray(dirs, dtype=np.float32)
+    if n_rays is None:
+        n_rays = d.shape[1] if d.ndim == 3 else 0
+    if pattern is None:
+        pattern = {1: 1, 4: 2, 16: 4}.get(d.shape[0] if d.ndim == 3 else 0, 0)
+    if d.size < int(pattern) ** 2 * int(n_rays) * 3:
+        raise ArcticError(-1, "ambient occlusion: the direction table is smaller than pattern * pattern * n_rays * 3 floats")
+    ao = np.zeros(1, AO_DTYPE)
+    ao["n_rays"], ao["pattern"], ao["radius"], ao["bias"] = n_rays, pattern, radius, bias
+    ao["filter"], ao["normal_cos"], ao["plane_dist"] = int(filter), normal_cos, plane_dist
+    return ao, d.reshape(-1)
+
+
+def ambient_occlusion_points(triangles, points, sets, dirs, n_rays=None, pattern=None, radius=np.inf, bias=1e-3, brute=False):
+    """arctic_ambient_occlusion_points: the ambient occlusion of include/arctic_hip.h on the host -- how many of the n_rays rays of each point
+    {world3, normal3} ((n, 6) float32) hit one of the (n, 9) world-space triangles, with direction set sets[k] of dirs: (n,) uint8.  brute: loop
+    over every triangle instead of the acceleration structure."""
+    t = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 6)
+    st = np.ascontiguousarray(sets, dtype=np.uint32).ravel()
+    if len(st) != len(p):
+        raise ArcticError(-1, "ambient_occlusion_points: one set per point")
+    ao, d = _ao_arguments(dirs, n_rays, pattern, radius, bias, False, 0.0, 0.0)
+    hits = np.empty(len(p), np.uint8)
+    rc = binding.lib().arctic_ambient_occlusion_points(_ptr(t) if len(t) else None, len(t), _ptr(p) if len(p) else None, _ptr(st) if len(p) else None, len(p),
+                                                       _ptr(ao), _ptr(d), binding.TRACE_BRUTE if brute else 0, _ptr(hits) if len(p) else None)
+    if rc < 0:
+        raise ArcticError(rc, "ambient_occlusion_points")
+    return hits
+
+
+def ao_directions(n_rays, pattern, seed=0):
+    """a direction table for trace_ambient_occlusion: (P * P, n_rays, 3) float32, cosine-weighted over the hemisphere z > 0, unit length.  One
+    stratified point set -- (k + jitter) / n_rays against the golden-ratio sequence -- per set, each set shifted by its own Cranley-Patterson
+    rotation so that the P * P sets of a window fill each other's gaps.  Deterministic in (n_rays, pattern, seed).  A convenience: the library
+    takes any table."""
+    n, sets = int(n_rays), int(pattern) ** 2
+    rng = np.random.default_rng([int(seed), n, sets])
+    k = np.arange(n, dtype=np.float64)
+    out = np.zeros((sets, n, 3), np.float64)
+    for s in range(sets):
+        u = (k + rng.random(n)) / n                                   # stratified in the radius: one sample per ring of equal projected area
+        v = (k * 0.6180339887498949 + (s + rng.random()) / sets) % 1.0   # the angle: golden-ratio steps, each set turned by its own part of a full turn
+        r, phi = np.sqrt(u) * (1.0 - 1e-6), 2.0 * np.pi * v
+        out[s, :, 0], out[s, :, 1] = r * np.cos(phi), r * np.sin(phi)
+        out[s, :, 2] = np.sqrt(np.maximum(1.0 - r * r, 0.0))
+        out[s] = out[s][rng.permutation(n)]                            # (the order inside a set carries no meaning: ray k of one set is no neighbour of ray k of another)
+    out /= np.linalg.norm(out, axis=-1, keepdims=True)
+    return out.astype(np.float32)
 
 
 def point_shadow_matrices(light):

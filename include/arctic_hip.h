@@ -935,6 +935,72 @@ int arctic_ray_resplit_info(ArcticRenderer *r, uint64_t *out4);
 int arctic_resplit_triangles(const float *tris9_build, const float *tris9_now, uint64_t n_tris, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits,
                              ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap, uint64_t *counts2);
 
+/* ---- ambient occlusion from the resident G-buffer (no counterpart in the reference: its one ambient term is the flat ambient * base_color) ---------
+ * How open is each pixel?  n_rays short any-hit rays per pixel over the hemisphere of its normal, against the structure of the ray queries above
+ * (built, refitted and re-split as described there), walked by ordinary vector code (ray_ao.hip).  The answer is DEFINED bit for bit: numpy in
+ * float32 reproduces it (tests/ao_reference.py), and so does arctic_ambient_occlusion_points on the host.  Nothing in the passes uses the plane:
+ * shading and every existing bit are unchanged; a host multiplies it into its indirect term or bakes it.
+ *
+ * THE DEFINITION.  Everything is fp32, one rounding per operation, in the written order, no contraction; division and square root are IEEE
+ * (correctly rounded); dot, min, max as the ray-query section defines them.
+ * dirs = P*P*n_rays*3 floats: direction k of set s sits at dirs[(s*n_rays + k)*3 ..]: LOCAL directions, z along the normal, used as given -- not
+ *   normalised, no sign check (a table may reach below the horizon, or weight by length through radius); every component must be finite.
+ *   Pixel (x, y) OF THE FRAME uses set (y % P) * P + x % P, so that a P x P window holds every set once and the filter below turns P*P*n_rays
+ *   directions into one estimate.
+ * Per pixel, with world = attributes 11..13 and n = attributes 8..10 of arctic_read_gbuffer's order:
+ *   1. len = sqrt((n0*n0 + n1*n1) + n2*n2);  m[i] = n[i] / len.  The pixel is NOT COVERED if it has no geometry, if len is zero or not finite, or
+ *      if any m[i] is not finite: its hits are 0 and its result is 255.  (The G-buffer's normals are interpolated, so they are not unit vectors;
+ *      the frame below is orthonormal only for one that is.)
+ *   2. The frame, from m alone (Duff et al., "Building an Orthonormal Basis, Revisited", branchless):
+ *        s = copysign(1.0f, m2);  a = -1.0f / (s + m2);  b = (m0*m1)*a;
+ *        t  = { 1.0f + ((s*m0)*m0)*a,  s*b,  (-s)*m0 };     bt = { b,  s + (m1*m1)*a,  -m1 }
+ *      (m2 = -0.0 takes s = -1: a = 1, a frame like any other.)
+ *   3. Ray k, with l = the local direction:  o[i] = world[i] + bias*m[i]  (the product rounds, then the sum);
+ *        d[i] = (t[i]*l0 + bt[i]*l1) + m[i]*l2;   t_min = 0;   t_max = radius;
+ *      any hit, by the ray definition above unchanged.  A ray that is invalid by that definition (a world position that is not finite, a
+ *      direction that comes out zero) is a miss.
+ *   4. hits = the number of the n_rays rays that hit.
+ * Unfiltered result (u8):  (510*(n_rays - hits) + n_rays) / (2*n_rays), integer division: visibility on 0..255, rounded to nearest.
+ * Filtered result for a covered pixel p at frame position (x, y):  the window is the pixels (x+i, y+j) with i, j in [-(P/2), P-1-P/2] -- offsets
+ *   -2..1 for P = 4, -1..0 for P = 2, 0 for P = 1 --, which holds every direction set exactly once.  p itself is always accepted.  Another pixel q
+ *   is accepted iff q lies inside the frame, q is covered, dot(m_p, m_q) >= normal_cos, and fabs(dot(m_p, w_q - w_p)) <= plane_dist, where the
+ *   difference rounds per component first.  With V = the sum of (n_rays - hits_q) over the accepted pixels and T = n_rays * accepted, the result
+ *   is (510*V + T) / (2*T).  A pixel that is not covered gives 255.
+ * Sharded handles.  The pattern uses the row of the FRAME: a handle that owns a row range or interleaved bands returns exactly its rows of the
+ *   whole frame's unfiltered result.  filter = 1 on a handle that does not own the whole frame is refused with ARCTIC_E_STATE and writes nothing
+ *   -- the rule of ARCTIC_OPT_ANTIALIAS: the shard lacks its neighbours' rows.
+ * KNOWN LIMITS.  Those of the ray definition (two-sided, not watertight); the bias is along the shading normal, so a ray of a strongly
+ *   interpolated normal can start below its own surface. */
+typedef struct ArcticAmbientOcclusion {   /* 32 bytes */
+    uint32_t n_rays;      /* rays per pixel, 1..64 */
+    uint32_t pattern;     /* P = 1, 2 or 4: pixel (x, y) OF THE FRAME uses direction set (y % P) * P + x % P */
+    float    radius;      /* every ray's t_max: > 0, +inf allowed */
+    float    bias;        /* finite */
+    uint32_t filter;      /* 0: per-pixel result; 1: reconstruction over the P x P window */
+    float    normal_cos;  /* filter only, finite */
+    float    plane_dist;  /* filter only, >= 0 */
+    uint32_t reserved;    /* 0 */
+} ArcticAmbientOcclusion;
+
+/* The result for every pixel of the handle's RESIDENT G-buffer (arctic_pass_gbuffer, arctic_write_gbuffer, or the latest frame): rows*width
+ * bytes, row-major over the handle's rows like arctic_trace_sun_visibility.  out == NULL leaves the result on the device and does not
+ * synchronise (timing).  Once the handle is warm a call allocates nothing; the table is sent again only when its bytes changed.
+ * Refusals, in this order; a refused call writes nothing.  ARCTIC_E_INVALID: a null scene, ao or dirs; n_rays outside 1..64; pattern not 1, 2 or
+ * 4; radius not > 0 (a NaN included); a bias that is not finite; filter > 1 or reserved != 0; with the filter on, a normal_cos that is not finite
+ * or a plane_dist that is negative or a NaN; a direction component that is not finite.  ARCTIC_E_STATE: no G-buffer; the filter on a shard. */
+int arctic_trace_ambient_occlusion(ArcticRenderer *r, const ArcticScene *scene, const ArcticAmbientOcclusion *ao, const float *dirs, uint8_t *out);
+
+/* The same into DEVICE memory the caller owns (rows*width bytes), stream-ordered on the handle's stream: call arctic_flush() before another
+ * stream reads d_out.  dirs stays a host pointer.  ARCTIC_E_INVALID also for a null d_out. */
+int arctic_trace_ambient_occlusion_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticAmbientOcclusion *ao, const float *dirs, uint8_t *d_out);
+
+/* The host arbiter (no handle, no GPU): hits[k] for point k = {world3, normal3} of points6, using direction set sets[k] -- steps 1 to 4 above,
+ * 0 for a point that is not covered; filter, normal_cos and plane_dist are checked and otherwise unused.  tris9 as in arctic_trace_triangles;
+ * flags: 0 (the structure and the walk of the device) or ARCTIC_TRACE_BRUTE (the loop over every triangle).  Refuses what the call above refuses
+ * with ARCTIC_E_INVALID, and an unknown flag, a null pointer with a non-zero count and a sets[k] >= P*P; ARCTIC_E_CAPACITY: n_tris above 2^32 - 2. */
+int arctic_ambient_occlusion_points(const float *tris9, uint64_t n_tris, const float *points6, const uint32_t *sets, uint64_t n_points,
+                                    const ArcticAmbientOcclusion *ao, const float *dirs, uint32_t flags, uint8_t *hits);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row
