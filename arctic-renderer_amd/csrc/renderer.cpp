@@ -21,6 +21,7 @@
 #include "../../include/arctic_hip.h"
 #include "../../include/arctic_dist.h"
 #include "common.h"
+#include "device_resources.h"
 #include "ray_query.h"
 #include "ray_ao.h"
 
@@ -107,30 +108,12 @@ struct Rccl {
 };
 Rccl g_rccl;
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
-        size_t want = bytes + bytes / 4 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T *as() const { return static_cast<T *>(p); }
-};
-
 // per-pass host->device tables (frame constants, object records, block tables): written into pinned memory and sent with
 // ONE asynchronous copy; the pinned buffer is reused only after the copy that last read it has completed (event), so
 // uploading never waits for the kernels of the previous pass or frame.
 struct PassTables {
-    void *h = nullptr;          // pinned staging
-    size_t h_cap = 0;
+    UploadRing<1> staging;      // pinned staging
     DevBuf d;                   // device arena
-    hipEvent_t copied = nullptr;
-    bool pending = false;
     std::vector<char> last;     // what the device arena holds: an unchanged object list is not uploaded again
     GeomParams gp;              // this pass's frame constants (kernel argument, by value)
     // device views into the arena (valid after upload)
@@ -140,8 +123,7 @@ struct PassTables {
 };
 
 struct Mesh {
-    float *d_vertices = nullptr;
-    uint32_t *d_indices = nullptr;
+    DevBuf d_vertices, d_indices;
     uint32_t n_vertices = 0, n_indices = 0;
     uint64_t material = 0;
     std::vector<float> tbounds, vbounds;   // cluster_bounds: 6 floats per block of SETUP_THREADS triangles / of 256 vertices
@@ -149,54 +131,35 @@ struct Mesh {
     // vertex buffer written by k_skin from d_vertices, d_skin and the pose's matrices in d_joints -- is what ObjectRec::vertices points at, and the
     // mesh's cluster boxes (which bound the bind pose) are replaced by infinite ones.  The matrices travel through a ring of pinned buffers, so
     // that a pose call neither reads the caller's memory after it returns nor waits for the copy of the pose before it.
-    void *d_skin = nullptr;
+    DevBuf d_skin;
     uint32_t n_joints = 0;
-    float *d_posed = nullptr, *d_joints = nullptr;
+    DevBuf d_posed, d_joints;
     bool posed = false;
     static constexpr int POSE_RING = 3;
-    float *h_joints[POSE_RING] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_joints[POSE_RING] = {nullptr, nullptr, nullptr};
-    bool joints_pending[POSE_RING] = {false, false, false};
-    int joints_turn = 0;
+    UploadRing<POSE_RING> joints_ring;
     // Morph targets (arctic_set_mesh_morph_targets / arctic_set_mesh_morph_weights).  d_deltas: n_targets arrays of n_vertices records of 12 floats;
     // while `morphed` (some weight is not zero), d_morphed -- written by k_morph from d_vertices, d_deltas and the compacted {target, weight} list
     // in d_active -- is what k_skin reads if the mesh is posed and what ObjectRec::vertices points at if it is not.  The list travels through a
     // ring of pinned buffers like the joint matrices.  morph_weights: the weights in force (all zero after a targets call)
-    float *d_deltas = nullptr, *d_morphed = nullptr;
+    DevBuf d_deltas, d_morphed;
     uint32_t n_targets = 0;
-    MorphActive *d_active = nullptr;
+    DevBuf d_active;
     bool morphed = false;
     std::vector<float> morph_weights;
-    MorphActive *h_active[POSE_RING] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_active[POSE_RING] = {nullptr, nullptr, nullptr};
-    bool active_pending[POSE_RING] = {false, false, false};
-    int active_turn = 0;
+    UploadRing<POSE_RING> active_ring;
     uint64_t shape_seq = 0;   // bumped by every successful skin / pose / morph call: part of the shadow caches' keys (shadow_inputs, cube_inputs)
-    const float *skin_input() const { return morphed ? d_morphed : d_vertices; }                       // morph first, then skin
-    const float *vertices_in_use() const { return posed ? d_posed : skin_input(); }
+    const float *skin_input() const { return (morphed ? d_morphed : d_vertices).as<float>(); }          // morph first, then skin
+    const float *vertices_in_use() const { return posed ? d_posed.as<float>() : skin_input(); }
     bool deformed() const { return posed || morphed; }                                                 // the cluster boxes do not describe it
     void release_morph() {    // (the caller has drained the streams that may read these)
-        if (d_deltas) (void)hipFree(d_deltas);
-        if (d_morphed) (void)hipFree(d_morphed);
-        if (d_active) (void)hipFree(d_active);
-        for (int k = 0; k < POSE_RING; ++k) {
-            if (h_active[k]) (void)hipHostFree(h_active[k]);
-            if (ev_active[k]) (void)hipEventDestroy(ev_active[k]);
-            h_active[k] = nullptr; ev_active[k] = nullptr; active_pending[k] = false;
-        }
-        d_deltas = d_morphed = nullptr; d_active = nullptr; n_targets = 0; morphed = false; morph_weights.clear();
+        d_deltas.release(); d_morphed.release(); d_active.release(); active_ring.release();
+        n_targets = 0; morphed = false; morph_weights.clear();
     }
     void release_pose() {     // (the caller has drained the streams that may read these)
-        if (d_posed) (void)hipFree(d_posed);
-        if (d_joints) (void)hipFree(d_joints);
-        for (int k = 0; k < POSE_RING; ++k) {
-            if (h_joints[k]) (void)hipHostFree(h_joints[k]);
-            if (ev_joints[k]) (void)hipEventDestroy(ev_joints[k]);
-            h_joints[k] = nullptr; ev_joints[k] = nullptr; joints_pending[k] = false;
-        }
-        d_posed = d_joints = nullptr; posed = false;
+        d_posed.release(); d_joints.release(); joints_ring.release();
+        posed = false;
     }
-    void release_skin() { release_pose(); if (d_skin) (void)hipFree(d_skin); d_skin = nullptr; n_joints = 0; }
+    void release_skin() { release_pose(); d_skin.release(); n_joints = 0; }
 };
 
 // Object-space boxes for geometry.hip's box_outside, made once per mesh on the host.  tbounds[c] = {min xyz, max xyz} of the positions
@@ -239,19 +202,18 @@ void cluster_bounds(const ArcticVertex *v, uint32_t n_vertices, const uint32_t *
 
 struct ArcticRenderer {
     int device = 0;
-    hipStream_t stream = nullptr;       // the stream every pass is enqueued on (own_stream unless the caller set one)
-    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;       // the stream every pass is enqueued on (own_stream unless the caller set one); not owned
     uint32_t width = 0, height = 0, shadow_size = 0, max_lights = 0, row_begin = 0, row_end = 0;
     uint32_t tiles_x = 0, tiles_y = 0, tile_y0 = 0, row0_in_tile = 0;
     uint32_t band_rows = 0, shard_index = 0, shard_count = 1, owned_rows = 0;   // interleaved shard (band_rows > 0)
     std::vector<Mesh> meshes;
     std::vector<TexDesc> tex;        // 3 per material (device pointers)
-    std::vector<void *> tex_allocs;
+    std::vector<DevBuf> tex_allocs;
     // arctic_set_material_extras: one entry per material.  While a material is not neutral (n_extras != 0) the device's texture table carries a
     // MaterialExtra record per material behind the descriptors (common.h) and every shading call takes the k_pbrlit* kernels (has_extras).
     struct Extras {
         float p[12] = {1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
-        void *d_emissive = nullptr, *d_occlusion = nullptr, *d_fast = nullptr;   // plain RGBA8 images, or the one {e.rgb, o} image of the fast path
+        DevBuf d_emissive, d_occlusion, d_fast;   // plain RGBA8 images, or the one {e.rgb, o} image of the fast path
         uint32_t ew = 0, eh = 0, ow = 0, oh = 0;
         bool neutral = true;
     };
@@ -265,7 +227,7 @@ struct ArcticRenderer {
     DevBuf d_shadow_set[2], d_shadow_blocks_set[2], d_shadow_bounds_set[2];
     bool bounds_valid_set[2] = {false, false};   // false whenever the map has been written since its table was built
     int scur = 0;
-    hipEvent_t ev_shadow_released[2] = {nullptr, nullptr};   // like ev_released, for the shadow-map sets
+    Event ev_shadow_released[2];   // like ev_released, for the shadow-map sets
     bool shadow_released_valid[2] = {false, false};
     DevBuf &d_shadow() { return d_shadow_set[scur]; }
     DevBuf &d_shadow_blocks() { return d_shadow_blocks_set[scur]; }
@@ -289,7 +251,9 @@ struct ArcticRenderer {
     uint32_t n_cubes = 0, cube_size = 1024;         // cube_size: ARCTIC_OPT_POINT_SHADOW_SIZE
     std::vector<ArcticPointShadowLight> cube_lights;   // the list as given: the faces' matrices and the cache key
     std::vector<uint8_t> cube_key;                  // what the faces were drawn from (render_frame redraws them when it changes; empty: redraw)
-    uint32_t *h_cube_counts = nullptr, *dh_cube_counts = nullptr;   // pinned, mapped: CUBE_COUNT_WORDS per face drawn (run_geometry's DepthTarget)
+    PinnedBuf cube_counts;                          // pinned, mapped: CUBE_COUNT_WORDS per face drawn (run_geometry's DepthTarget)
+    uint32_t *h_cube_counts() const { return cube_counts.as<uint32_t>(); }
+    uint32_t *dh_cube_counts() const { return cube_counts.dev<uint32_t>(); }
     uint32_t cube_count_faces = 0;
     // frame targets
     DevBuf d_vis_set[3], d_p0, d_p1, d_p2, d_p3, d_p4, d_rgba8, d_ldr, d_hdr, d_counter;
@@ -321,17 +285,17 @@ struct ArcticRenderer {
         uint32_t n_tblocks = 0, n_vblocks = 0; bool cull_counted = false;   // the latest pass's workgroups (arctic_read_cull_counts)
     } geo[4];   // indexed like tables
     DevBuf d_geo_counters, d_stage;
-    hipStream_t shadow_stream = nullptr;            // arctic_render_frame draws the shadow map here while the main stream runs the visibility prepass
-    hipEvent_t ev_fork = nullptr, ev_shadow = nullptr;
+    // shadow_stream (below): arctic_render_frame draws the shadow map there while the main stream runs the visibility prepass
+    Event ev_fork, ev_shadow;
     // Skinning: k_skin runs on the main stream, which has joined every earlier prepass (ev_prepass, ev_shadow) -- so it follows every k_vertex that
     // still reads the buffer it overwrites.  ev_skin is recorded behind it; the shadow and prepass streams wait for it before their next pass
     // (skin_seq counts the launches, *_seen what each of those streams has waited for)
-    hipEvent_t ev_skin = nullptr;
+    Event ev_skin;
     uint64_t skin_seq = 0, skin_seen_shadow = 0, skin_seen_prepass[2] = {0, 0};
     // The shadow pass has ONE set of scratch (geo[1], tables[1], its four counters) whichever stream it runs on -- the main stream
     // (arctic_pass_shadow_map, a sharded map, debug bit 7) or shadow_stream (whole frames).  ev_shadow_scratch marks the end of the
     // last shadow pass on shadow_scratch_stream; a pass on another stream waits for it first, so two never share the scratch.
-    hipEvent_t ev_shadow_scratch = nullptr;
+    Event ev_shadow_scratch;
     hipStream_t shadow_scratch_stream = nullptr;
     bool shadow_scratch_valid = false;
     // Frames in flight (arctic_render_frame, ARCTIC_OPT_FRAMES_IN_FLIGHT = 2): the visibility prepass of frame k + 1 runs on
@@ -343,8 +307,7 @@ struct ArcticRenderer {
     // sets the prepasses of two consecutive frames are independent of each other as well, and a small frame -- whose prepass is a
     // chain of launches longer than its shading -- is bound by neither chain alone.
     int frames_in_flight = 2, frames_in_flight_opt = 0 /* ARCTIC_OPT_FRAMES_IN_FLIGHT; 0: by the target's size (alloc_targets) */, cur = 0, prepass_turn = 0;
-    hipStream_t prepass_stream[2] = {nullptr, nullptr};
-    hipEvent_t ev_prepass[2] = {nullptr, nullptr}, ev_released[3] = {nullptr, nullptr, nullptr};
+    Event ev_prepass[2], ev_released[3];   // (prepass_stream[2]: below)
     bool released_valid[3] = {false, false, false};
     DevBuf &d_vis() { return d_vis_set[cur]; }
     int fwd() const { return cur ? cur + 1 : 0; }      // index of the current forward set in tables / geo
@@ -390,14 +353,14 @@ struct ArcticRenderer {
     // main stream with events, the shard layout of every rank (all-gathered once at arctic_comm_init)
     Rccl::Comm comm = nullptr;
     int comm_rank = 0, comm_world = 1;
-    hipStream_t comm_stream = nullptr;
+    hipStream_t comm_stream = nullptr;   // the handle's own stream, borrowed, or comm_stream_owned (below)
     bool comm_stream_borrowed = false;   // the communication stream is the handle's own stream, idle because the caller brought its stream (one stream -- one hardware queue -- fewer)
     // ONE role per stream: own_stream is the main stream, or -- the caller brought its own -- EITHER the exchange's stream (borrowed by
     // arctic_comm_init) OR the second prepass stream of three frames in flight, never both: a gather queued in front of a prepass would
     // stall it behind the other ranks, and synchronising a prepass stream must never wait for an unmatched collective.
     bool own_stream_is_prepass() const { return stream != own_stream && !comm_stream_borrowed; }
-    hipEvent_t ev_main = nullptr;
-    struct InFlight { const void *ptr = nullptr; hipEvent_t done = nullptr; } inflight[4];   // gathers that still read a shard buffer
+    Event ev_main;
+    struct InFlight { const void *ptr = nullptr; Event done; } inflight[4];   // gathers that still read a shard buffer
     std::vector<uint32_t> peer_rows, peer_ranges;    // rows of every rank's shard; [begin, end) of every rank (row-range shards)
     std::vector<uint64_t> peer_offset;               // byte offset of every rank's shard in the root's staging buffer (arctic_exchange_plan)
     uint64_t staging_bytes = 0;
@@ -423,11 +386,7 @@ struct ArcticRenderer {
         std::vector<uint32_t> stage_first;         // RefitSchedule::stage_first of the build
         DevBuf d_src, d_head, d_inputs, d_interior, d_objs;
         static constexpr int OBJ_RING = 3;
-        RefitObject *h_objs[OBJ_RING] = {nullptr, nullptr, nullptr};
-        size_t h_objs_cap[OBJ_RING] = {0, 0, 0};
-        hipEvent_t ev_objs[OBJ_RING] = {nullptr, nullptr, nullptr};
-        bool objs_pending[OBJ_RING] = {false, false, false};
-        int objs_turn = 0;
+        UploadRing<OBJ_RING> objs_ring;
         // arctic_ray_scene_resplit (ray_resplit.hip; the definition: include/arctic_hip.h, "a re-split structure"): the sorts' workspace, allocated
         // by the first re-split of a structure of this size and kept; nothing while the call is never made
         DevBuf d_resplit;
@@ -440,13 +399,16 @@ struct ArcticRenderer {
     // read it has completed --, the hits plane and the result, one byte per pixel of the handle's rows each.  Nothing is allocated before the first call
     struct AmbientOcclusion {
         DevBuf d_dirs, d_hits, d_out;
-        float *h_dirs = nullptr;
+        UploadRing<1> dirs_ring;                   // its one pinned slot keeps the table last sent
         size_t n_floats = 0;                       // what d_dirs holds (0: nothing)
-        hipEvent_t copied = nullptr;
-        bool pending = false;
     } ao;
-    uint32_t *dh_counts = nullptr;  // the device's address of h_counts
-    uint32_t *h_counts = nullptr;   // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
+    PinnedBuf counts;               // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
+    uint32_t *h_counts() const { return counts.as<uint32_t>(); }
+    uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts
+    // The streams the handle created, declared LAST: members are destroyed in reverse order, so every stream is waited for and gone before any
+    // buffer, pinned slot or event above -- which its work may still touch -- is released.  (arctic_create makes them in the order its comment
+    // gives; comm_stream_owned: the exchange's stream when it is not the borrowed own_stream.)
+    Stream own_stream, shadow_stream, prepass_stream[2], comm_stream_owned;
     std::string err;
 
     int fail(int code, const char *fmt, ...) {
@@ -534,7 +496,7 @@ int upload_pass_tables(ArcticRenderer *r, PassTables &T, DevBuf &d_xverts, hipSt
         ObjectRec rec;
         std::memcpy(rec.trs, o.trs, sizeof rec.trs);
         rec.vertices = m.vertices_in_use();
-        rec.indices = m.d_indices;
+        rec.indices = m.d_indices.as<uint32_t>();
         rec.n_vertices = m.n_vertices;
         rec.n_triangles = m.n_indices / 3;
         rec.first_xvert = (uint32_t)xv;
@@ -575,20 +537,12 @@ int upload_pass_tables(ArcticRenderer *r, PassTables &T, DevBuf &d_xverts, hipSt
     if (!vb_box.empty()) std::memcpy(h + o_vb, vb_box.data(), vb_box.size() * 4);
     if (!tb_box.empty()) std::memcpy(h + o_tb, tb_box.data(), tb_box.size() * 4);
     if (!(T.d.p && stage == T.last)) {
-        if (T.pending) { HIPCHECK(r, hipEventSynchronize(T.copied)); T.pending = false; }
-        if (total > T.h_cap) {
-            if (T.h) HIPCHECK(r, hipHostFree(T.h));
-            T.h = nullptr; T.h_cap = 0;
-            HIPCHECK(r, hipHostMalloc(&T.h, total * 2));
-            T.h_cap = total * 2;
-        }
-        if (!T.copied) HIPCHECK(r, hipEventCreateWithFlags(&T.copied, hipEventDisableTiming));
+        char *pinned = nullptr;
+        HIPCHECK(r, T.staging.stage(T.staging.slot[0].h.cap < total ? total * 2 : total, &pinned));   // (a slot that has to grow gets twice the table)
         T.last.clear();
         HIPCHECK(r, T.d.ensure(total));
-        std::memcpy(T.h, h, total);
-        HIPCHECK(r, hipMemcpyAsync(T.d.p, T.h, total, hipMemcpyHostToDevice, stream));
-        HIPCHECK(r, hipEventRecord(T.copied, stream));
-        T.pending = true;
+        std::memcpy(pinned, h, total);
+        HIPCHECK(r, T.staging.send(T.d.p, total, stream));
         T.last.swap(stage);
     }
     const char *d = T.d.as<char>();
@@ -678,7 +632,7 @@ int run_geometry(ArcticRenderer *r, const ArcticScene *sc, bool shadow_pass, hip
     int rc = upload_pass_tables(r, T, G.d_xverts, stream, gp, sc, n_objs, n_xverts, n_src, n_vblocks, n_tblocks);
     if (rc != ARCTIC_OK) return rc;
     const GeomParams &d_gp = T.gp;
-    uint32_t *hc = cube ? cube->h_counts : r->h_counts + (shadow_pass ? 2 : 0);   // [0] records, [1] work items of the latest pass into this target
+    uint32_t *hc = cube ? cube->h_counts : r->h_counts() + (shadow_pass ? 2 : 0);   // [0] records, [1] work items of the latest pass into this target
     if (n_objs == 0 || n_src == 0 || n_vblocks == 0) {
         hc[0] = hc[1] = 0;
         HIPCHECK(r, launch_fill_u64(clear, clear_value, clear_count, stream));
@@ -720,7 +674,7 @@ int run_geometry(ArcticRenderer *r, const ArcticScene *sc, bool shadow_pass, hip
                              shadow_pass && (!owned || merge) && r->small_triangles ? depth_map : nullptr, stream));
     // counts for arctic_stats() and the overflow flag: k_raster stores them into pinned, mapped memory (no copy launches between
     // the kernels); looked at only when the stream has been synchronised
-    uint32_t *dh = cube ? cube->dh_counts : r->dh_counts + (shadow_pass ? 2 : 0), *dh_overflow = cube ? cube->dh_counts + 2 : r->dh_counts + 4 + (shadow_pass ? 1 : 0);
+    uint32_t *dh = cube ? cube->dh_counts : r->dh_counts() + (shadow_pass ? 2 : 0), *dh_overflow = cube ? cube->dh_counts + 2 : r->dh_counts() + 4 + (shadow_pass ? 1 : 0);
     uint32_t grid = r->raster_blocks[shadow_pass ? 1 : 0];
     const uint2 *draw = G.d_items.as<uint2>();
     if (owned) {
@@ -730,7 +684,7 @@ int run_geometry(ArcticRenderer *r, const ArcticScene *sc, bool shadow_pass, hip
         // late: it only sizes the grid) a launch of 64 workgroups, else the whole persistent grid -- the kernel shortens its chunks
         // so that every resident wave gets one (a grid cut to the item count measured slower: config 1, half of whose items are left)
         draw = G.d_left.as<uint2>();
-        if (r->h_counts[6 + (shadow_pass ? 1 : 0)] <= 64) grid = std::min<uint32_t>(grid, 64);
+        if (r->h_counts()[6 + (shadow_pass ? 1 : 0)] <= 64) grid = std::min<uint32_t>(grid, 64);
     }
     if (shadow_pass)
         HIPCHECK(r, launch_raster_depth(G.d_recs.as<SetupRec>(), G.d_rrecs.as<RasterRec>(), draw, G.item_cap, counters, grid, d_gp,
@@ -794,7 +748,7 @@ int pass_point_shadows(ArcticRenderer *r, const ArcticScene *sc, hipStream_t str
             point_shadow_proj_view(l.position, k, l.z_near, l.z_far, m);
             const size_t j = (size_t)i * 6 + k;
             const DepthTarget t = {reinterpret_cast<uint32_t *>(cube_faces(r) + j * texels), r->cube_size, m,
-                                   r->h_cube_counts + CUBE_COUNT_WORDS * j, r->dh_cube_counts + CUBE_COUNT_WORDS * j};
+                                   r->h_cube_counts() + CUBE_COUNT_WORDS * j, r->dh_cube_counts() + CUBE_COUNT_WORDS * j};
             rc = run_geometry(r, sc, true, stream, &t);
         }
     }
@@ -1075,14 +1029,14 @@ int wait_skin(ArcticRenderer *r, hipStream_t stream, uint64_t &seen) {
 int check_item_overflow(ArcticRenderer *r) {
     bool cube_overflow = false;   // a face of a point light (pass_point_shadows: its own slots)
     uint32_t need = 0;
-    for (uint32_t j = 0; r->h_cube_counts && j < r->n_cubes * 6; ++j) {
-        uint32_t *c = r->h_cube_counts + CUBE_COUNT_WORDS * j;
+    for (uint32_t j = 0; r->h_cube_counts() && j < r->n_cubes * 6; ++j) {
+        uint32_t *c = r->h_cube_counts() + CUBE_COUNT_WORDS * j;
         if (c[2]) { cube_overflow = true; need = std::max(need, c[1]); c[2] = 0; }
     }
     if (cube_overflow) r->cube_key.clear();
-    if (!r->h_counts || !(r->h_counts[4] | r->h_counts[5] | (cube_overflow ? 1u : 0u))) return ARCTIC_OK;
-    need = std::max(need, std::max(r->h_counts[1], r->h_counts[3]));
-    r->h_counts[4] = r->h_counts[5] = 0;
+    if (!r->h_counts() || !(r->h_counts()[4] | r->h_counts()[5] | (cube_overflow ? 1u : 0u))) return ARCTIC_OK;
+    need = std::max(need, std::max(r->h_counts()[1], r->h_counts()[3]));
+    r->h_counts()[4] = r->h_counts()[5] = 0;
     r->recs_worst_case = true;   // whichever table it was: the record table takes its worst-case size from now on
     r->have_gbuffer = false; r->have_output = false; r->have_vis = false; r->have_order = false; r->shadow_key.clear();
     return r->fail(ARCTIC_E_CAPACITY, "a rasteriser table overflowed (%u work items needed, %u slots; or more than 2 records per source triangle): the last frame "
@@ -1102,10 +1056,10 @@ int upload_tex_table(ArcticRenderer *r) {
         if (x.d_fast) {
             const uint32_t w = r->tex[3 * m].w & ~TEX_INTERLEAVED, h = r->tex[3 * m].h;
             e.flags = EXTRA_FAST | (x.ew ? EXTRA_EMISSIVE : 0u) | (x.ow ? EXTRA_OCCLUSION : 0u);
-            e.emissive = TexDesc{static_cast<const uint32_t *>(x.d_fast), w, h, (float)w, (float)h, w + 2, 0u};
+            e.emissive = TexDesc{x.d_fast.as<const uint32_t>(), w, h, (float)w, (float)h, w + 2, 0u};
         } else {
-            if (x.d_emissive) { e.flags |= EXTRA_EMISSIVE; e.emissive = TexDesc{static_cast<const uint32_t *>(x.d_emissive), x.ew, x.eh, (float)x.ew, (float)x.eh, x.ew, 0u}; }
-            if (x.d_occlusion) { e.flags |= EXTRA_OCCLUSION; e.occlusion = TexDesc{static_cast<const uint32_t *>(x.d_occlusion), x.ow, x.oh, (float)x.ow, (float)x.oh, x.ow, 0u}; }
+            if (x.d_emissive) { e.flags |= EXTRA_EMISSIVE; e.emissive = TexDesc{x.d_emissive.as<const uint32_t>(), x.ew, x.eh, (float)x.ew, (float)x.eh, x.ew, 0u}; }
+            if (x.d_occlusion) { e.flags |= EXTRA_OCCLUSION; e.occlusion = TexDesc{x.d_occlusion.as<const uint32_t>(), x.ow, x.oh, (float)x.ow, (float)x.oh, x.ow, 0u}; }
         }
         std::memcpy(table.data() + desc_bytes + m * sizeof(MaterialExtra), &e, sizeof e);
     }
@@ -1159,33 +1113,32 @@ ArcticRenderer *arctic_create(const ArcticCreateInfo *info, char *err, uint64_t 
     // (ev_main and the gather's events, which RCCL's transfers to other devices follow, keep the default.)
     const unsigned in_device_event = hipEventDisableTiming | hipEventDisableSystemFence;
     if ((e = hipSetDevice(r->device)) != hipSuccess) return bail("hipSetDevice", e);
-    if ((e = hipStreamCreateWithFlags(&r->own_stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
+    if ((e = r->own_stream.create(hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
     r->stream = r->own_stream;
-    if ((e = hipStreamCreateWithFlags(&r->shadow_stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
-    if ((e = hipEventCreateWithFlags(&r->ev_fork, in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreateWithFlags(&r->ev_shadow, in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreateWithFlags(&r->ev_shadow_scratch, in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreateWithFlags(&r->ev_skin, in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = r->shadow_stream.create(hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
+    if ((e = r->ev_fork.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = r->ev_shadow.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = r->ev_shadow_scratch.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = r->ev_skin.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
     // The HIP runtime deals its hardware queues (4 by default, GPU_MAX_HW_QUEUES) to streams in the order they are created, and two
     // streams on one queue do not overlap: the handle's own stream, the shadow stream and the first prepass stream are created here, in
     // that order (with a caller's stream that makes four); the second prepass stream, which only three frames in flight use, is the
     // handle's own stream when the caller brought one (it is idle then), else created when first needed (second_prepass_stream)
-    if ((e = hipStreamCreateWithFlags(&r->prepass_stream[0], hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
+    if ((e = r->prepass_stream[0].create(hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
     for (int k = 0; k < 2; ++k)
-        if ((e = hipEventCreateWithFlags(&r->ev_prepass[k], in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
-    for (hipEvent_t &ev : r->ev_released)
-        if ((e = hipEventCreateWithFlags(&ev, in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
-    for (hipEvent_t &ev : r->ev_shadow_released)
-        if ((e = hipEventCreateWithFlags(&ev, in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+        if ((e = r->ev_prepass[k].create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    for (Event &ev : r->ev_released)
+        if ((e = ev.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    for (Event &ev : r->ev_shadow_released)
+        if ((e = ev.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
     {
         hipDeviceProp_t prop;
         if ((e = hipGetDeviceProperties(&prop, r->device)) != hipSuccess) return bail("hipGetDeviceProperties", e);
         r->cu_count = (uint32_t)std::max(1, prop.multiProcessorCount);
         r->raster_blocks[0] = raster_grid_blocks(false, r->cu_count);
         r->raster_blocks[1] = raster_grid_blocks(true, r->cu_count);
-        if ((e = hipHostMalloc((void **)&r->h_counts, 64, hipHostMallocMapped)) != hipSuccess) return bail("hipHostMalloc", e);
-        std::memset(r->h_counts, 0, 64);
-        if ((e = hipHostGetDevicePointer((void **)&r->dh_counts, r->h_counts, 0)) != hipSuccess) return bail("hipHostGetDevicePointer", e);
+        if ((e = r->counts.alloc(64, hipHostMallocMapped)) != hipSuccess) return bail("hipHostMalloc", e);
+        std::memset(r->h_counts(), 0, 64);
     }
     float lut[256];
     for (int i = 0; i < 256; ++i) lut[i] = srgb8_to_linear(i);
@@ -1204,42 +1157,16 @@ ArcticRenderer *arctic_create(const ArcticCreateInfo *info, char *err, uint64_t 
     return r;
 }
 
+// Nothing is released by name here: once the streams are idle the handle's members release themselves (device_resources.h), the streams first
+// (ArcticRenderer declares them last).
 void arctic_destroy(ArcticRenderer *r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
-    if (r->h_counts) (void)hipHostFree(r->h_counts);
-    if (r->h_cube_counts) (void)hipHostFree(r->h_cube_counts);
     (void)hipStreamSynchronize(r->stream);
+    if (r->shadow_stream) (void)hipStreamSynchronize(r->shadow_stream);
+    for (hipStream_t ps : r->prepass_stream) if (ps) (void)hipStreamSynchronize(ps);
+    if (r->own_stream) (void)hipStreamSynchronize(r->own_stream);
     (void)arctic_comm_destroy(r);
-    if (r->shadow_stream) { (void)hipStreamSynchronize(r->shadow_stream); (void)hipStreamDestroy(r->shadow_stream); }
-    for (hipStream_t ps : r->prepass_stream) if (ps) { (void)hipStreamSynchronize(ps); (void)hipStreamDestroy(ps); }
-    for (hipEvent_t ev : r->ev_prepass) if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : r->ev_released) if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : r->ev_shadow_released) if (ev) (void)hipEventDestroy(ev);
-    if (r->ev_fork) (void)hipEventDestroy(r->ev_fork);
-    if (r->ev_shadow) (void)hipEventDestroy(r->ev_shadow);
-    if (r->ev_shadow_scratch) (void)hipEventDestroy(r->ev_shadow_scratch);
-    if (r->ev_skin) (void)hipEventDestroy(r->ev_skin);
-    if (r->own_stream) { (void)hipStreamSynchronize(r->own_stream); (void)hipStreamDestroy(r->own_stream); }
-    for (Mesh &m : r->meshes) { m.release_skin(); m.release_morph(); if (m.d_vertices) (void)hipFree(m.d_vertices); if (m.d_indices) (void)hipFree(m.d_indices); }
-    for (void *p : r->tex_allocs) (void)hipFree(p);
-    for (ArcticRenderer::Extras &x : r->extras) for (void *p : {x.d_emissive, x.d_occlusion, x.d_fast}) if (p) (void)hipFree(p);
-    DevBuf *bufs[] = {&r->d_tex, &r->d_lut, &r->d_lights, &r->d_light_pairs, &r->d_spots, &r->d_cubes, &r->d_shadow_set[0], &r->d_shadow_set[1], &r->d_env, &r->d_env_levels, &r->d_env_lut, &r->d_env_mips, &r->d_env_sh_rows, &r->d_env_tables, &r->d_vis_set[0], &r->d_vis_set[1], &r->d_vis_set[2], &r->d_p0, &r->d_p1, &r->d_p2, &r->d_p3, &r->d_p4, &r->d_lod,
-                      &r->d_rgba8, &r->d_aa, &r->d_ldr, &r->d_hdr, &r->d_counter, &r->d_shadow_blocks_set[0], &r->d_shadow_blocks_set[1], &r->d_shadow_bounds_set[0], &r->d_shadow_bounds_set[1], &r->d_staging, &r->d_layout, &r->geo[0].d_xverts, &r->geo[1].d_xverts, &r->geo[2].d_xverts,
-                      &r->geo[2].d_recs, &r->geo[2].d_rrecs, &r->geo[2].d_clip_list, &r->geo[2].d_rec_of, &r->geo[2].d_items, &r->tables[2].d,
-                      &r->geo[3].d_xverts, &r->geo[3].d_recs, &r->geo[3].d_rrecs, &r->geo[3].d_clip_list, &r->geo[3].d_rec_of, &r->geo[3].d_items, &r->geo[3].d_left, &r->geo[3].d_bin_count, &r->geo[3].d_bin_slots, &r->tables[3].d,
-                      &r->geo[0].d_recs, &r->geo[0].d_rrecs, &r->geo[0].d_clip_list, &r->geo[0].d_rec_of, &r->geo[0].d_items,
-                      &r->geo[1].d_recs, &r->geo[1].d_rrecs, &r->geo[1].d_clip_list, &r->geo[1].d_rec_of, &r->geo[1].d_items, &r->geo[0].d_left, &r->geo[1].d_left, &r->geo[2].d_left, &r->geo[0].d_bin_count, &r->geo[0].d_bin_slots, &r->geo[1].d_bin_count, &r->geo[1].d_bin_slots, &r->geo[2].d_bin_count, &r->geo[2].d_bin_slots, &r->d_geo_counters, &r->d_stage, &r->tables[0].d, &r->tables[1].d};
-    for (PassTables &T : r->tables) { if (T.h) (void)hipHostFree(T.h); if (T.copied) (void)hipEventDestroy(T.copied); }
-    for (DevBuf *b : bufs) b->release();
-    for (DevBuf *b : {&r->ray.d_nodes, &r->ray.d_tris, &r->ray.d_rays, &r->ray.d_hits, &r->ray.d_mask, &r->ray.d_src, &r->ray.d_head, &r->ray.d_inputs, &r->ray.d_interior, &r->ray.d_objs, &r->ray.d_resplit}) b->release();
-    for (int k = 0; k < ArcticRenderer::RayScene::OBJ_RING; ++k) {
-        if (r->ray.h_objs[k]) (void)hipHostFree(r->ray.h_objs[k]);
-        if (r->ray.ev_objs[k]) (void)hipEventDestroy(r->ray.ev_objs[k]);
-    }
-    for (DevBuf *b : {&r->ao.d_dirs, &r->ao.d_hits, &r->ao.d_out}) b->release();
-    if (r->ao.h_dirs) (void)hipHostFree(r->ao.h_dirs);
-    if (r->ao.copied) (void)hipEventDestroy(r->ao.copied);
     delete r;
 }
 
@@ -1294,10 +1221,11 @@ int arctic_use_own_stream(ArcticRenderer *r) {
         // passes queued behind those would stall until they do -- and becomes its owner; the passes get a fresh stream (ordered against earlier
         // gathers the way they always are: by the events of the shard buffers they write, pass_shade).  The new stream goes into a local first: a
         // failed creation leaves the handle exactly as it was.
-        hipStream_t fresh = nullptr;
-        HIPCHECK(r, hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking));
+        Stream fresh;
+        HIPCHECK(r, fresh.create(hipStreamNonBlocking));
         r->comm_stream_borrowed = false;   // comm_stream == the old own_stream: owned by the exchange from here on (destroyed with the communicator)
-        r->own_stream = fresh;
+        r->comm_stream_owned = std::move(r->own_stream);
+        r->own_stream = std::move(fresh);
     }
     r->stream = r->own_stream;
     r->skin_seen_prepass[1] = 0;
@@ -1351,9 +1279,10 @@ int arctic_create_material(ArcticRenderer *r, const void *diffuse, uint32_t dw, 
                 packed[2 * o + 1] = (uint32_t)b[4 * i + 1] | ((uint32_t)b[4 * i + 2] << 8) | ((uint32_t)c[4 * i + 1] << 16) | ((uint32_t)c[4 * i + 2] << 24);
             }
         }
-        void *p = nullptr;
-        HIPCHECK(r, hipMalloc(&p, (size_t)chain_bytes));
-        r->tex_allocs.push_back(p);
+        DevBuf image;
+        HIPCHECK(r, image.alloc_exact((size_t)chain_bytes));
+        void *const p = image.p;
+        r->tex_allocs.push_back(std::move(image));
         HIPCHECK(r, hipMemcpy(p, packed.data(), n * 8, hipMemcpyHostToDevice));   // synchronous like rhi.cpp:480-519
         for (int i = 0; i < 3; ++i) { td[i] = TexDesc{static_cast<const uint32_t *>(p), dw | TEX_INTERLEAVED, dh, (float)dw, (float)dh, pw, tiled ? tpr * 128u : 0u}; }
         if (r->texture_mips) {   // level k + 1 from level k on the device (texture_mips.hip), synchronous like the upload; the material's table of levels
@@ -1364,19 +1293,21 @@ int arctic_create_material(ArcticRenderer *r, const void *diffuse, uint32_t dw, 
                 chain[k] = TexDesc{reinterpret_cast<const uint32_t *>(static_cast<const char *>(p) + level_offset[k]), wk | TEX_INTERLEAVED, hk, (float)wk, (float)hk, wk + 2, 0u};
                 HIPCHECK(r, launch_mip_reduce(chain[k - 1], chain[k], r->d_lut.as<float>(), r->stream));
             }
-            void *table = nullptr;
-            HIPCHECK(r, hipMalloc(&table, levels * sizeof(TexDesc)));
-            r->tex_allocs.push_back(table);
+            DevBuf levels_table;
+            HIPCHECK(r, levels_table.alloc_exact(levels * sizeof(TexDesc)));
+            void *const table = levels_table.p;
+            r->tex_allocs.push_back(std::move(levels_table));
             HIPCHECK(r, hipMemcpyAsync(table, chain.data(), levels * sizeof(TexDesc), hipMemcpyHostToDevice, r->stream));
             HIPCHECK(r, hipStreamSynchronize(r->stream));
             td[1] = TexDesc{static_cast<const uint32_t *>(table), levels, 0u, 0.0f, 0.0f, 0u, 0u};   // the MipTable (common.h)
         }
     } else {
         for (int i = 0; i < 3; ++i) {
-            void *p = nullptr;
             size_t bytes = (size_t)w[i] * h[i] * 4;
-            HIPCHECK(r, hipMalloc(&p, bytes));
-            r->tex_allocs.push_back(p);
+            DevBuf image;
+            HIPCHECK(r, image.alloc_exact(bytes));
+            void *const p = image.p;
+            r->tex_allocs.push_back(std::move(image));
             HIPCHECK(r, hipMemcpy(p, src[i], bytes, hipMemcpyHostToDevice));
             td[i] = TexDesc{static_cast<const uint32_t *>(p), w[i], h[i], (float)w[i], (float)h[i], w[i], 0u};
         }
@@ -1415,10 +1346,8 @@ int arctic_set_material_extras(ArcticRenderer *r, uint64_t material, const Arcti
     const TexDesc &d0 = r->tex[3 * material];
     const uint32_t mw = d0.w & ~TEX_INTERLEAVED, mh = d0.h;
     const bool fast = (d0.w & TEX_INTERLEAVED) && (emissive || occlusion) && (!emissive || (ew == mw && eh == mh)) && (!occlusion || (ow == mw && oh == mh));
-    const auto drop = [](ArcticRenderer::Extras &x) { for (void **p : {&x.d_emissive, &x.d_occlusion, &x.d_fast}) if (*p) { (void)hipFree(*p); *p = nullptr; } };
-    const auto upload = [&](void **dst, const void *src, size_t bytes) {
-        if (hipMalloc(dst, bytes) != hipSuccess) { *dst = nullptr; return false; }
-        return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    const auto upload = [&](DevBuf &dst, const void *src, size_t bytes) {
+        return dst.alloc_exact(bytes) == hipSuccess && hipMemcpy(dst.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
     };
     bool ok = true;
     if (fast) {   // one image of 4-byte texels {e.r, e.g, e.b, o} with the packed image's one-texel WRAP border (common.h MaterialExtra)
@@ -1433,18 +1362,17 @@ int arctic_set_material_extras(ArcticRenderer *r, uint64_t material, const Arcti
                 texels[(size_t)Y * pw + X] = rgb | ((o ? (uint32_t)o[4 * i] : 255u) << 24);
             }
         }
-        ok = upload(&nx.d_fast, texels.data(), texels.size() * 4);
+        ok = upload(nx.d_fast, texels.data(), texels.size() * 4);
     } else {
-        if (emissive) ok = upload(&nx.d_emissive, emissive, (size_t)ew * eh * 4);
-        if (ok && occlusion) ok = upload(&nx.d_occlusion, occlusion, (size_t)ow * oh * 4);
+        if (emissive) ok = upload(nx.d_emissive, emissive, (size_t)ew * eh * 4);
+        if (ok && occlusion) ok = upload(nx.d_occlusion, occlusion, (size_t)ow * oh * 4);
     }
-    if (!ok) { drop(nx); return r->fail(ARCTIC_E_DEVICE, "set_material_extras: hipMalloc / upload of an image"); }
+    if (!ok) return r->fail(ARCTIC_E_DEVICE, "set_material_extras: hipMalloc / upload of an image");
     HIPCHECK(r, hipStreamSynchronize(r->stream));   // (a pass in flight may still read the table and the images it replaces)
     ArcticRenderer::Extras &cur = r->extras[material];
     const bool table_changes = !(cur.neutral && nx.neutral);
     r->n_extras += (nx.neutral ? 0u : 1u) - (cur.neutral ? 0u : 1u);
-    drop(cur);
-    cur = nx;
+    cur = std::move(nx);   // (the images it replaces go with the assignment)
     return table_changes ? upload_tex_table(r) : ARCTIC_OK;
 }
 
@@ -1457,14 +1385,15 @@ int arctic_create_mesh(ArcticRenderer *r, const ArcticVertex *vertices, uint64_t
     if (n_vertices > 0x7FFFFFFFull || n_indices > 0xFFFFFFF0ull) return r->fail(ARCTIC_E_CAPACITY, "create_mesh: mesh too large");
     int rc = select_device(r);
     if (rc) return rc;
-    Mesh m;
-    HIPCHECK(r, hipMalloc((void **)&m.d_vertices, n_vertices * sizeof(ArcticVertex)));
-    if (hipMalloc((void **)&m.d_indices, n_indices * 4) != hipSuccess) { (void)hipFree(m.d_vertices); return r->fail(ARCTIC_E_DEVICE, "create_mesh: hipMalloc indices"); }
-    m.n_vertices = (uint32_t)n_vertices; m.n_indices = (uint32_t)n_indices; m.material = material_idx;
-    cluster_bounds(vertices, m.n_vertices, indices, m.n_indices, m.tbounds, m.vbounds);
-    r->meshes.push_back(m);
-    HIPCHECK(r, hipMemcpy(m.d_vertices, vertices, n_vertices * sizeof(ArcticVertex), hipMemcpyHostToDevice));
-    HIPCHECK(r, hipMemcpy(m.d_indices, indices, n_indices * 4, hipMemcpyHostToDevice));
+    Mesh fresh;
+    HIPCHECK(r, fresh.d_vertices.alloc_exact(n_vertices * sizeof(ArcticVertex)));
+    if (fresh.d_indices.alloc_exact(n_indices * 4) != hipSuccess) return r->fail(ARCTIC_E_DEVICE, "create_mesh: hipMalloc indices");
+    fresh.n_vertices = (uint32_t)n_vertices; fresh.n_indices = (uint32_t)n_indices; fresh.material = material_idx;
+    cluster_bounds(vertices, fresh.n_vertices, indices, fresh.n_indices, fresh.tbounds, fresh.vbounds);
+    r->meshes.push_back(std::move(fresh));
+    const Mesh &m = r->meshes.back();
+    HIPCHECK(r, hipMemcpy(m.d_vertices.p, vertices, n_vertices * sizeof(ArcticVertex), hipMemcpyHostToDevice));
+    HIPCHECK(r, hipMemcpy(m.d_indices.p, indices, n_indices * 4, hipMemcpyHostToDevice));
     return (int)r->meshes.size() - 1;
 }
 
@@ -1484,20 +1413,20 @@ int arctic_set_mesh_skin(ArcticRenderer *r, uint64_t mesh, const ArcticSkinVerte
     if (!r) return ARCTIC_E_INVALID;
     if (mesh >= r->meshes.size()) return r->fail(ARCTIC_E_INVALID, "set_mesh_skin: mesh %llu does not exist", (unsigned long long)mesh);
     Mesh &m = r->meshes[mesh];
-    void *d_new = nullptr;
+    DevBuf d_new;
     int rc = select_device(r);
     if (rc) return rc;
     if (skin) {
         if (n_vertices != m.n_vertices) return r->fail(ARCTIC_E_INVALID, "set_mesh_skin: %llu skin records for a mesh of %u vertices", (unsigned long long)n_vertices, m.n_vertices);
         if (!mesh_skin_valid(skin, n_vertices, n_joints))
             return r->fail(ARCTIC_E_INVALID, "set_mesh_skin: n_joints %u outside 1..65535, a joint index at or above it, or a weight that is not finite", n_joints);
-        HIPCHECK(r, hipMalloc(&d_new, n_vertices * sizeof(ArcticSkinVertex)));
-        if (hipMemcpy(d_new, skin, n_vertices * sizeof(ArcticSkinVertex), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); return r->fail(ARCTIC_E_DEVICE, "set_mesh_skin: upload"); }
+        HIPCHECK(r, d_new.alloc_exact(n_vertices * sizeof(ArcticSkinVertex)));
+        if (hipMemcpy(d_new.p, skin, n_vertices * sizeof(ArcticSkinVertex), hipMemcpyHostToDevice) != hipSuccess) return r->fail(ARCTIC_E_DEVICE, "set_mesh_skin: upload");
     }
     // what is replaced may still be read: by a k_skin, or -- the posed buffer -- by a prepass; every prepass stream has been joined into the main stream
     if (m.d_skin) HIPCHECK(r, hipStreamSynchronize(r->stream));
     m.release_skin();
-    m.d_skin = d_new; m.n_joints = skin ? n_joints : 0;
+    m.d_skin = std::move(d_new); m.n_joints = skin ? n_joints : 0;
     ++m.shape_seq;
     return ARCTIC_OK;
 }
@@ -1517,20 +1446,15 @@ int arctic_set_mesh_pose(ArcticRenderer *r, uint64_t mesh, const float *joint_ma
     int rc = select_device(r);
     if (rc) return rc;
     const size_t bytes = (size_t)n_joints * 64;
-    if (!m.d_posed) HIPCHECK(r, hipMalloc((void **)&m.d_posed, (size_t)m.n_vertices * sizeof(ArcticVertex)));
-    if (!m.d_joints) HIPCHECK(r, hipMalloc((void **)&m.d_joints, bytes));
-    const int slot = m.joints_turn;
-    if (!m.h_joints[slot]) HIPCHECK(r, hipHostMalloc((void **)&m.h_joints[slot], bytes));
-    if (!m.ev_joints[slot]) HIPCHECK(r, hipEventCreateWithFlags(&m.ev_joints[slot], hipEventDisableTiming));
-    if (m.joints_pending[slot]) { HIPCHECK(r, hipEventSynchronize(m.ev_joints[slot])); m.joints_pending[slot] = false; }   // (the copy of POSE_RING poses ago)
-    std::memcpy(m.h_joints[slot], joint_matrices, bytes);
-    m.joints_turn = (slot + 1) % Mesh::POSE_RING;
+    if (!m.d_posed) HIPCHECK(r, m.d_posed.alloc_exact((size_t)m.n_vertices * sizeof(ArcticVertex)));
+    if (!m.d_joints) HIPCHECK(r, m.d_joints.alloc_exact(bytes));
+    float *h_joints = nullptr;
+    HIPCHECK(r, m.joints_ring.stage(bytes, &h_joints));   // (waits for the copy of POSE_RING poses ago at most)
+    std::memcpy(h_joints, joint_matrices, bytes);
     // on the main stream: behind every prepass enqueued so far (arctic_render_frame joins its prepass streams into it), so behind every k_vertex
     // that reads the buffer k_skin overwrites
-    HIPCHECK(r, hipMemcpyAsync(m.d_joints, m.h_joints[slot], bytes, hipMemcpyHostToDevice, r->stream));
-    HIPCHECK(r, hipEventRecord(m.ev_joints[slot], r->stream));
-    m.joints_pending[slot] = true;
-    HIPCHECK(r, launch_skin(m.skin_input(), m.d_skin, m.d_joints, m.n_vertices, n_joints, m.d_posed, r->stream));
+    HIPCHECK(r, m.joints_ring.send(m.d_joints.p, bytes, r->stream));
+    HIPCHECK(r, launch_skin(m.skin_input(), m.d_skin.p, m.d_joints.as<float>(), m.n_vertices, n_joints, m.d_posed.as<float>(), r->stream));
     HIPCHECK(r, hipEventRecord(r->ev_skin, r->stream));
     ++r->skin_seq;
     m.posed = true;
@@ -1553,7 +1477,7 @@ int arctic_morph_vertices(const ArcticVertex *in, const ArcticMorphDelta *deltas
 namespace {
 // a posed mesh whose k_skin input has just changed (another blend, or none): the pose again, from the matrices the mesh holds
 int reskin(ArcticRenderer *r, Mesh &m) {
-    if (m.posed) HIPCHECK(r, launch_skin(m.skin_input(), m.d_skin, m.d_joints, m.n_vertices, m.n_joints, m.d_posed, r->stream));
+    if (m.posed) HIPCHECK(r, launch_skin(m.skin_input(), m.d_skin.p, m.d_joints.as<float>(), m.n_vertices, m.n_joints, m.d_posed.as<float>(), r->stream));
     return ARCTIC_OK;
 }
 // behind the last deformation kernel of a call: what the shadow and prepass streams wait for (wait_skin)
@@ -1568,7 +1492,7 @@ int arctic_set_mesh_morph_targets(ArcticRenderer *r, uint64_t mesh, const Arctic
     if (!r) return ARCTIC_E_INVALID;
     if (mesh >= r->meshes.size()) return r->fail(ARCTIC_E_INVALID, "set_mesh_morph_targets: mesh %llu does not exist", (unsigned long long)mesh);
     Mesh &m = r->meshes[mesh];
-    float *d_new = nullptr;
+    DevBuf d_new;
     int rc = select_device(r);
     if (rc) return rc;
     if (deltas) {
@@ -1576,18 +1500,18 @@ int arctic_set_mesh_morph_targets(ArcticRenderer *r, uint64_t mesh, const Arctic
         if (!morph_targets_valid(reinterpret_cast<const float *>(deltas), n_vertices, n_targets))
             return r->fail(ARCTIC_E_INVALID, "set_mesh_morph_targets: n_targets %u outside 1..65535, or a delta that is not finite", n_targets);
         const size_t bytes = (size_t)n_targets * n_vertices * sizeof(ArcticMorphDelta);
-        if (hipMalloc((void **)&d_new, bytes) != hipSuccess) {
+        if (d_new.alloc_exact(bytes) != hipSuccess) {
             (void)hipGetLastError();
             return r->fail(ARCTIC_E_DEVICE, "set_mesh_morph_targets: %u targets x %llu vertices x 48 bytes cannot be allocated", n_targets, (unsigned long long)n_vertices);
         }
-        if (hipMemcpy(d_new, deltas, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_new); return r->fail(ARCTIC_E_DEVICE, "set_mesh_morph_targets: upload"); }
+        if (hipMemcpy(d_new.p, deltas, bytes, hipMemcpyHostToDevice) != hipSuccess) return r->fail(ARCTIC_E_DEVICE, "set_mesh_morph_targets: upload");
     }
     // what is replaced may still be read: by a k_morph, a k_skin, or -- the blended buffer -- by a prepass; every prepass stream has been joined
     // into the main stream
     const bool was_morphed = m.morphed;
-    if (m.d_deltas && hipStreamSynchronize(r->stream) != hipSuccess) { if (d_new) (void)hipFree(d_new); return r->fail(ARCTIC_E_DEVICE, "set_mesh_morph_targets: hipStreamSynchronize"); }
+    if (m.d_deltas && hipStreamSynchronize(r->stream) != hipSuccess) return r->fail(ARCTIC_E_DEVICE, "set_mesh_morph_targets: hipStreamSynchronize");
     m.release_morph();
-    m.d_deltas = d_new; m.n_targets = deltas ? n_targets : 0;
+    m.d_deltas = std::move(d_new); m.n_targets = deltas ? n_targets : 0;
     m.morph_weights.assign(m.n_targets, 0.0f);
     ++m.shape_seq;
     if (was_morphed && m.posed) {   // the pose stood on the blend that has just gone: once more, on the mesh's own vertices (the stream is drained)
@@ -1622,18 +1546,13 @@ int arctic_set_mesh_morph_weights(ArcticRenderer *r, uint64_t mesh, const float 
         }
     } else {
         const size_t cap = (size_t)m.n_targets * sizeof(MorphActive), bytes = active.size() * sizeof(MorphActive);
-        if (!m.d_morphed) HIPCHECK(r, hipMalloc((void **)&m.d_morphed, (size_t)m.n_vertices * sizeof(ArcticVertex)));
-        if (!m.d_active) HIPCHECK(r, hipMalloc((void **)&m.d_active, cap));
-        const int slot = m.active_turn;
-        if (!m.h_active[slot]) HIPCHECK(r, hipHostMalloc((void **)&m.h_active[slot], cap));
-        if (!m.ev_active[slot]) HIPCHECK(r, hipEventCreateWithFlags(&m.ev_active[slot], hipEventDisableTiming));
-        if (m.active_pending[slot]) { HIPCHECK(r, hipEventSynchronize(m.ev_active[slot])); m.active_pending[slot] = false; }   // (the copy of POSE_RING calls ago)
-        std::memcpy(m.h_active[slot], active.data(), bytes);
-        m.active_turn = (slot + 1) % Mesh::POSE_RING;
-        HIPCHECK(r, hipMemcpyAsync(m.d_active, m.h_active[slot], bytes, hipMemcpyHostToDevice, r->stream));
-        HIPCHECK(r, hipEventRecord(m.ev_active[slot], r->stream));
-        m.active_pending[slot] = true;
-        HIPCHECK(r, launch_morph(m.d_vertices, m.d_deltas, m.d_active, (uint32_t)active.size(), m.n_vertices, m.d_morphed, r->stream));
+        if (!m.d_morphed) HIPCHECK(r, m.d_morphed.alloc_exact((size_t)m.n_vertices * sizeof(ArcticVertex)));
+        if (!m.d_active) HIPCHECK(r, m.d_active.alloc_exact(cap));
+        MorphActive *h_active = nullptr;
+        HIPCHECK(r, m.active_ring.stage(cap, &h_active));   // (waits for the copy of POSE_RING calls ago at most)
+        std::memcpy(h_active, active.data(), bytes);
+        HIPCHECK(r, m.active_ring.send(m.d_active.p, bytes, r->stream));
+        HIPCHECK(r, launch_morph(m.d_vertices.as<float>(), m.d_deltas.as<float>(), m.d_active.as<MorphActive>(), (uint32_t)active.size(), m.n_vertices, m.d_morphed.as<float>(), r->stream));
         m.morphed = true;
         if ((rc = reskin(r, m)) != ARCTIC_OK) return rc;
         if ((rc = deformed_on_main_stream(r)) != ARCTIC_OK) return rc;
@@ -1813,22 +1732,19 @@ bool valid_cube_light(const ArcticPointShadowLight &l) {
 int cube_store(ArcticRenderer *r, const ArcticPointShadowLight *lights, uint32_t k, uint32_t F) {
     const size_t rec_bytes = (size_t)k * sizeof(CubeDev), bytes = rec_bytes + (size_t)k * 6 * F * F * 4;
     if (bytes > r->d_cubes.cap) {
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return r->fail(ARCTIC_E_DEVICE, "point shadows: cannot allocate %zu bytes of faces", bytes); }
-        r->d_cubes.release();
-        r->d_cubes.p = p; r->d_cubes.cap = bytes;
+        DevBuf fresh;
+        if (fresh.alloc_exact(bytes) != hipSuccess) { (void)hipGetLastError(); return r->fail(ARCTIC_E_DEVICE, "point shadows: cannot allocate %zu bytes of faces", bytes); }
+        r->d_cubes = std::move(fresh);
     }
     if ((size_t)k * 6 > r->cube_count_faces) {   // pinned, mapped counts: 8 words per face
-        uint32_t *h = nullptr, *dh = nullptr;
+        PinnedBuf fresh;
         const size_t n = (size_t)std::max<uint32_t>(k, r->max_lights) * 6;
-        if (hipHostMalloc((void **)&h, n * CUBE_COUNT_WORDS * 4, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void **)&dh, h, 0) != hipSuccess) {
+        if (fresh.alloc(n * CUBE_COUNT_WORDS * 4, hipHostMallocMapped) != hipSuccess) {
             (void)hipGetLastError();
-            if (h) (void)hipHostFree(h);
             return r->fail(ARCTIC_E_DEVICE, "point shadows: cannot allocate the pinned counters");
         }
-        std::memset(h, 0, n * CUBE_COUNT_WORDS * 4);
-        if (r->h_cube_counts) (void)hipHostFree(r->h_cube_counts);
-        r->h_cube_counts = h; r->dh_cube_counts = dh; r->cube_count_faces = (uint32_t)n;
+        std::memset(fresh.p, 0, n * CUBE_COUNT_WORDS * 4);
+        r->cube_counts = std::move(fresh); r->cube_count_faces = (uint32_t)n;
     }
     std::vector<CubeDev> dev(k);
     for (uint32_t i = 0; i < k; ++i) {
@@ -2000,7 +1916,7 @@ int arctic_render_frame_device(ArcticRenderer *r, const ArcticScene *scene, cons
         hipStream_t ps = r->prepass_stream[0];
         if (turn) {
             if (r->own_stream_is_prepass()) ps = r->own_stream;
-            else { if (!r->prepass_stream[1]) HIPCHECK(r, hipStreamCreateWithFlags(&r->prepass_stream[1], hipStreamNonBlocking)); ps = r->prepass_stream[1]; }
+            else { if (!r->prepass_stream[1]) HIPCHECK(r, r->prepass_stream[1].create(hipStreamNonBlocking)); ps = r->prepass_stream[1]; }
         }
         if (r->released_valid[r->cur]) HIPCHECK(r, hipStreamWaitEvent(ps, r->ev_released[r->cur], 0));
         rc = wait_skin(r, ps, r->skin_seen_prepass[turn]);
@@ -2062,8 +1978,8 @@ int arctic_time_shade(ArcticRenderer *r, const ArcticScene *scene, const ArcticS
     ShadeParams sp;
     if ((rc = fill_shade_params(r, scene, settings, nullptr, sp)) != ARCTIC_OK) return rc;
     for (uint32_t i = 0; i < warmup; ++i) HIPCHECK(r, shade_once(r, sp, false, false));
-    std::vector<hipEvent_t> ev(2 * (size_t)iters);
-    for (auto &e : ev) HIPCHECK(r, hipEventCreate(&e));
+    std::vector<Event> ev(2 * (size_t)iters);
+    for (auto &e : ev) HIPCHECK(r, e.create(hipEventDefault));
     for (uint32_t i = 0; i < iters; ++i) {
         HIPCHECK(r, hipEventRecord(ev[2 * i], r->stream));
         HIPCHECK(r, shade_once(r, sp, false, false));
@@ -2071,7 +1987,6 @@ int arctic_time_shade(ArcticRenderer *r, const ArcticScene *scene, const ArcticS
     }
     HIPCHECK(r, hipStreamSynchronize(r->stream));
     for (uint32_t i = 0; i < iters; ++i) HIPCHECK(r, hipEventElapsedTime(&ms_each[i], ev[2 * i], ev[2 * i + 1]));
-    for (auto &e : ev) (void)hipEventDestroy(e);
     r->have_output = true;
     r->output_filtered = false;   // (the shading kernel alone: d_rgba8 holds what it wrote)
     return ARCTIC_OK;
@@ -2290,8 +2205,8 @@ int arctic_frame_constants(const ArcticScene *scene, float *proj_view, float *li
 int arctic_stats(ArcticRenderer *r, uint64_t *out, uint32_t n) {
     if (!r || !out) return ARCTIC_E_INVALID;
     if (select_device(r) == ARCTIC_OK) (void)hipStreamSynchronize(r->stream);
-    if (r->h_counts) for (int i = 0; i < 4; ++i) r->stats[i] = r->h_counts[i];
-    for (uint32_t i = 0; i < n && i < 16; ++i) out[i] = i < 8 ? r->stats[i] : i < 10 ? r->light_stats[i - 8] : i < 12 ? (r->h_counts ? r->h_counts[6 + (i - 10)] : 0) : r->edge_stats[i - 12];
+    if (r->h_counts()) for (int i = 0; i < 4; ++i) r->stats[i] = r->h_counts()[i];
+    for (uint32_t i = 0; i < n && i < 16; ++i) out[i] = i < 8 ? r->stats[i] : i < 10 ? r->light_stats[i - 8] : i < 12 ? (r->h_counts() ? r->h_counts()[6 + (i - 10)] : 0) : r->edge_stats[i - 12];
     return ARCTIC_OK;
 }
 
@@ -2538,27 +2453,16 @@ bool ray_refit_eligible(const ArcticRenderer *r, const ArcticScene *sc) {
 int refit_ray_scene(ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_t> &key, bool resplit = false) {
     ArcticRenderer::RayScene &R = r->ray;
     const size_t n_obj = (size_t)sc->n_objects, bytes = std::max<size_t>(n_obj, 1) * sizeof(RefitObject);
-    const int slot = R.objs_turn;
-    if (R.objs_pending[slot]) { HIPCHECK(r, hipEventSynchronize(R.ev_objs[slot])); R.objs_pending[slot] = false; }
-    if (R.h_objs_cap[slot] < bytes) {
-        if (R.h_objs[slot]) { (void)hipHostFree(R.h_objs[slot]); R.h_objs[slot] = nullptr; R.h_objs_cap[slot] = 0; }
-        HIPCHECK(r, hipHostMalloc((void **)&R.h_objs[slot], bytes));
-        R.h_objs_cap[slot] = bytes;
-    }
-    if (!R.ev_objs[slot]) HIPCHECK(r, hipEventCreateWithFlags(&R.ev_objs[slot], hipEventDisableTiming));
+    RefitObject *h_objs = nullptr;
+    HIPCHECK(r, R.objs_ring.stage(bytes, &h_objs));   // (a slot grows to fit)
     for (size_t i = 0; i < n_obj; ++i) {
         const ArcticObject &o = sc->objects[i];
         const Mesh &m = r->meshes[o.mesh_idx];   // (ray_refit_eligible: it exists)
-        RefitObject &d = R.h_objs[slot][i];
+        RefitObject &d = h_objs[i];
         for (int c = 0; c < 4; ++c) for (int k = 0; k < 3; ++k) d.m[3 * c + k] = o.trs[4 * c + k];
         d.vertices = m.vertices_in_use(); d.n_vertices = m.n_vertices; d.pad = 0;
     }
-    R.objs_turn = (slot + 1) % ArcticRenderer::RayScene::OBJ_RING;
-    if (n_obj) {
-        HIPCHECK(r, hipMemcpyAsync(R.d_objs.p, R.h_objs[slot], n_obj * sizeof(RefitObject), hipMemcpyHostToDevice, r->stream));
-        HIPCHECK(r, hipEventRecord(R.ev_objs[slot], r->stream));
-        R.objs_pending[slot] = true;
-    }
+    HIPCHECK(r, R.objs_ring.send(R.d_objs.p, n_obj * sizeof(RefitObject), r->stream));   // (no object: nothing is sent, the ring moves on)
     const RefitTablesDev T = {R.d_head.as<uint32_t>(), R.d_inputs.as<uint32_t>(), R.d_interior.as<RefitInterior>(), R.d_src.as<RefitSource>()};
     uint32_t launches = 0, split_launches = 0;
     if (resplit) {
@@ -2599,7 +2503,7 @@ int ensure_ray_scene(ArcticRenderer *r, const ArcticScene *sc) {
         if (verts[o.mesh_idx].empty()) {
             verts[o.mesh_idx].resize((size_t)m.n_vertices * 14); inds[o.mesh_idx].resize(m.n_indices);
             HIPCHECK(r, hipMemcpy(verts[o.mesh_idx].data(), m.vertices_in_use(), (size_t)m.n_vertices * sizeof(ArcticVertex), hipMemcpyDeviceToHost));
-            HIPCHECK(r, hipMemcpy(inds[o.mesh_idx].data(), m.d_indices, (size_t)m.n_indices * 4, hipMemcpyDeviceToHost));
+            HIPCHECK(r, hipMemcpy(inds[o.mesh_idx].data(), m.d_indices.p, (size_t)m.n_indices * 4, hipMemcpyDeviceToHost));
         }
         prim = ray_world_triangles(o.trs, verts[o.mesh_idx].data(), m.n_vertices, inds[o.mesh_idx].data(), m.n_indices / 3, prim, tris9, prims);
         if (with_refit) ray_triangle_sources((uint32_t)i, m.n_vertices, inds[o.mesh_idx].data(), m.n_indices / 3, sources);
@@ -2730,18 +2634,15 @@ int trace_ambient_occlusion(ArcticRenderer *r, const ArcticScene *scene, const A
     if ((rc = ensure_ray_scene(r, scene)) != ARCTIC_OK) return rc;
     ArcticRenderer::AmbientOcclusion &A = r->ao;
     const size_t n_floats = (size_t)d.pattern * d.pattern * d.n_rays * 3, bytes = (size_t)r->rows() * r->width;
-    if (!A.h_dirs) {
-        HIPCHECK(r, hipHostMalloc((void **)&A.h_dirs, 16 * AO_MAX_RAYS * 3 * sizeof(float)));
-        HIPCHECK(r, hipEventCreateWithFlags(&A.copied, hipEventDisableTiming));
-        HIPCHECK(r, A.d_dirs.ensure(16 * AO_MAX_RAYS * 3 * sizeof(float)));
-    }
-    if (A.n_floats != n_floats || std::memcmp(A.h_dirs, dirs, n_floats * sizeof(float)) != 0) {
-        if (A.pending) { HIPCHECK(r, hipEventSynchronize(A.copied)); A.pending = false; }
+    const size_t table_bytes = 16 * AO_MAX_RAYS * 3 * sizeof(float);   // the largest table: the slot and d_dirs are made once
+    if (A.n_floats != n_floats || std::memcmp(A.dirs_ring.slot[0].h.p, dirs, n_floats * sizeof(float)) != 0) {   // (n_floats != 0: an empty A holds no table)
+        float *h_dirs = nullptr;
+        HIPCHECK(r, A.dirs_ring.stage(table_bytes, &h_dirs));
+        HIPCHECK(r, A.d_dirs.ensure(table_bytes));
         A.n_floats = 0;
-        std::memcpy(A.h_dirs, dirs, n_floats * sizeof(float));
-        HIPCHECK(r, hipMemcpyAsync(A.d_dirs.p, A.h_dirs, n_floats * sizeof(float), hipMemcpyHostToDevice, r->stream));
-        HIPCHECK(r, hipEventRecord(A.copied, r->stream));
-        A.pending = true; A.n_floats = n_floats;
+        std::memcpy(h_dirs, dirs, n_floats * sizeof(float));
+        HIPCHECK(r, A.dirs_ring.send(A.d_dirs.p, n_floats * sizeof(float), r->stream));
+        A.n_floats = n_floats;
     }
     if (d.filter) HIPCHECK(r, A.d_hits.ensure(std::max<size_t>(bytes, 16)));
     if (!d_out) { HIPCHECK(r, A.d_out.ensure(std::max<size_t>(bytes, 16))); d_out = A.d_out.as<uint8_t>(); }
@@ -2970,10 +2871,10 @@ int arctic_comm_init(ArcticRenderer *r, const void *id_bytes, int rank, int worl
         if (!r->comm_stream) {
             // (the runtime deals few hardware queues to many streams, and two streams on one queue do not overlap: DESIGN.md 4.3)
             if (r->stream != r->own_stream) { r->comm_stream = r->own_stream; r->comm_stream_borrowed = true; }
-            else HIPCHECK(r, hipStreamCreateWithFlags(&r->comm_stream, hipStreamNonBlocking));
+            else { HIPCHECK(r, r->comm_stream_owned.create(hipStreamNonBlocking)); r->comm_stream = r->comm_stream_owned; }
         }
-        if (!r->ev_main) HIPCHECK(r, hipEventCreateWithFlags(&r->ev_main, hipEventDisableTiming));
-        for (auto &f : r->inflight) if (!f.done) HIPCHECK(r, hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
+        HIPCHECK(r, r->ev_main.ensure(hipEventDisableTiming));
+        for (auto &f : r->inflight) HIPCHECK(r, f.done.ensure(hipEventDisableTiming));
         // every rank's shard layout: {row_begin, row_end, rows, band_rows} all-gathered once (the root places shards of unequal size)
         HIPCHECK(r, tmp.ensure((size_t)world * 16));
         const uint32_t mine[4] = {r->band_rows ? 0u : r->row_begin, r->band_rows ? 0u : r->row_end, r->rows(), r->band_rows};
@@ -2986,7 +2887,6 @@ int arctic_comm_init(ArcticRenderer *r, const void *id_bytes, int rank, int worl
         return comm_adopt_layout(r, all.data(), world);
     };
     rc = finish();
-    tmp.release();
     if (rc != ARCTIC_OK) {
         const std::string why = r->err;
         (void)arctic_comm_destroy(r);
@@ -3002,9 +2902,10 @@ int arctic_comm_destroy(ArcticRenderer *r) {
     if (r->comm) { (void)g_rccl.CommDestroy(r->comm); r->comm = nullptr; }
     r->comm_rank = 0; r->comm_world = 1;
     if (r->layout_from_comm) { r->layout_world = 0; r->layout_from_comm = false; }
-    for (auto &f : r->inflight) { if (f.done) (void)hipEventDestroy(f.done); f.done = nullptr; f.ptr = nullptr; }
-    if (r->ev_main) { (void)hipEventDestroy(r->ev_main); r->ev_main = nullptr; }
-    if (r->comm_stream) { if (!r->comm_stream_borrowed) (void)hipStreamDestroy(r->comm_stream); r->comm_stream = nullptr; r->comm_stream_borrowed = false; }
+    for (auto &f : r->inflight) { f.done.release(); f.ptr = nullptr; }
+    r->ev_main.release();
+    r->comm_stream_owned.release();   // (nothing when the stream was borrowed: own_stream stays the handle's)
+    r->comm_stream = nullptr; r->comm_stream_borrowed = false;
     return ARCTIC_OK;
 }
 
