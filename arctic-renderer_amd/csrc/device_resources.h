@@ -1,5 +1,5 @@
-// device_resources.h -- owners of what the HIP runtime hands out: device memory, pinned memory, events, streams, and the ring of pinned
-// slots that host tables travel through.  Host only, nothing of the project: every type is move-only and its destructor releases what it
+// device_resources.h -- owners of what the HIP runtime hands out: device memory, pinned memory, events, streams, the ring of pinned
+// slots that host tables travel through, and the marks that order one stream behind another.  Host only, nothing of the project: every type is move-only and its destructor releases what it
 // holds, so a handle (renderer.cpp) frees nothing by hand -- its members go in reverse order of declaration, a local owner on a failure path
 // goes with its scope.  The owners make exactly the runtime calls the code they replace made; none of them synchronises behind the caller's
 // back except Stream, whose release waits for the stream before it destroys it.
@@ -7,6 +7,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstddef>
+#include <cstdint>
 #include <utility>
 
 namespace arctic {
@@ -131,6 +132,82 @@ template <int N> struct UploadRing {
 
 private:
     static void take(Slot &a, Slot &b) { a.h = std::move(b.h); a.copied = std::move(b.copied); a.pending = std::exchange(b.pending, false); }
+};
+
+// A mark: one event that knows what it stands for -- whether anything has been recorded on it since it was made or forgotten, on which stream,
+// and how many times.  The rules of cross-stream ordering are kept here, once, not at every site:
+//   never recorded                          nothing to wait for
+//   recorded on the waiting stream itself   nothing to wait for (stream order does it)
+//   wait_once                               one wait per recording and waiter (`seen` is the waiter's: the generation it has waited for)
+// `recorded` is apart from `on` because nullptr is a real stream, the default one.  forget: the caller has drained the streams, what was recorded
+// is complete; the generation goes on counting, so no waiter's `seen` can match a later recording by accident.
+struct StreamMark {
+    Event ev;
+    bool recorded = false;
+    hipStream_t on = nullptr;
+    uint64_t generation = 0;
+    StreamMark() = default;
+    StreamMark(StreamMark &&o) noexcept
+        : ev(std::move(o.ev)), recorded(std::exchange(o.recorded, false)), on(std::exchange(o.on, nullptr)), generation(std::exchange(o.generation, 0)) {}
+    StreamMark &operator=(StreamMark &&o) noexcept {
+        if (this != &o) { ev = std::move(o.ev); recorded = std::exchange(o.recorded, false); on = std::exchange(o.on, nullptr); generation = std::exchange(o.generation, 0); }
+        return *this;
+    }
+    hipError_t create(unsigned flags) { forget(); return ev.create(flags); }
+    hipError_t ensure(unsigned flags) { return ev.ensure(flags); }
+    void release() { ev.release(); forget(); }
+    void forget() { recorded = false; on = nullptr; }
+    hipError_t record(hipStream_t stream) {
+        hipError_t e = hipEventRecord(ev, stream);
+        if (e == hipSuccess) { recorded = true; on = stream; ++generation; }
+        return e;
+    }
+    hipError_t wait(hipStream_t stream) const { return !recorded || stream == on ? hipSuccess : hipStreamWaitEvent(stream, ev, 0); }
+    hipError_t wait_once(hipStream_t stream, uint64_t &seen) const {   // (a refused wait leaves `seen` as it was: the next call waits again)
+        if (seen == generation) return hipSuccess;
+        hipError_t e = wait(stream);
+        if (e == hipSuccess) seen = generation;
+        return e;
+    }
+};
+
+// Who still reads this buffer: N slots of {buffer, mark recorded behind its reader}.
+//   claim(ptr, drain, mark)  the slot that holds `ptr`, else a free one, else -- none free -- `drain` is waited for, every slot is cleared and slot 0
+//                            taken; `mark` is the slot's, for the caller to record behind the reader it enqueues
+//   wait_for(ptr, stream)    a slot holds `ptr`: `stream` waits for its mark and the slot is free again; else nothing
+template <int N> struct ReaderTable {
+    struct Slot { const void *ptr = nullptr; StreamMark done; };
+    Slot slot[N];
+    ReaderTable() = default;
+    ReaderTable(ReaderTable &&o) noexcept { for (int k = 0; k < N; ++k) take(slot[k], o.slot[k]); }
+    ReaderTable &operator=(ReaderTable &&o) noexcept { if (this != &o) for (int k = 0; k < N; ++k) take(slot[k], o.slot[k]); return *this; }
+    hipError_t ensure(unsigned flags) {
+        for (Slot &s : slot) { hipError_t e = s.done.ensure(flags); if (e != hipSuccess) return e; }
+        return hipSuccess;
+    }
+    void release() { for (Slot &s : slot) { s.done.release(); s.ptr = nullptr; } }
+    hipError_t wait_for(const void *ptr, hipStream_t stream) {
+        for (Slot &s : slot)
+            if (ptr && s.ptr == ptr) { hipError_t e = s.done.wait(stream); if (e != hipSuccess) return e; s.ptr = nullptr; }
+        return hipSuccess;
+    }
+    hipError_t claim(const void *ptr, hipStream_t drain, StreamMark *&mark) {
+        Slot *found = nullptr;
+        for (Slot &s : slot) if (s.ptr == ptr) found = &s;
+        if (!found) for (Slot &s : slot) if (!s.ptr) { found = &s; break; }
+        if (!found) {
+            hipError_t e = hipStreamSynchronize(drain);
+            if (e != hipSuccess) return e;
+            for (Slot &s : slot) s.ptr = nullptr;
+            found = &slot[0];
+        }
+        found->ptr = ptr;
+        mark = &found->done;
+        return hipSuccess;
+    }
+
+private:
+    static void take(Slot &a, Slot &b) { a.ptr = std::exchange(b.ptr, nullptr); a.done = std::move(b.done); }
 };
 
 }  // namespace arctic

@@ -227,8 +227,7 @@ struct ArcticRenderer {
     DevBuf d_shadow_set[2], d_shadow_blocks_set[2], d_shadow_bounds_set[2];
     bool bounds_valid_set[2] = {false, false};   // false whenever the map has been written since its table was built
     int scur = 0;
-    Event ev_shadow_released[2];   // like ev_released, for the shadow-map sets
-    bool shadow_released_valid[2] = {false, false};
+    StreamMark shadow_set_released[2];   // like vis_set_released, for the shadow-map sets
     DevBuf &d_shadow() { return d_shadow_set[scur]; }
     DevBuf &d_shadow_blocks() { return d_shadow_blocks_set[scur]; }
     DevBuf &d_shadow_bounds() { return d_shadow_bounds_set[scur]; }
@@ -286,29 +285,27 @@ struct ArcticRenderer {
     } geo[4];   // indexed like tables
     DevBuf d_geo_counters, d_stage;
     // shadow_stream (below): arctic_render_frame draws the shadow map there while the main stream runs the visibility prepass
-    Event ev_fork, ev_shadow;
-    // Skinning: k_skin runs on the main stream, which has joined every earlier prepass (ev_prepass, ev_shadow) -- so it follows every k_vertex that
-    // still reads the buffer it overwrites.  ev_skin is recorded behind it; the shadow and prepass streams wait for it before their next pass
-    // (skin_seq counts the launches, *_seen what each of those streams has waited for)
-    Event ev_skin;
-    uint64_t skin_seq = 0, skin_seen_shadow = 0, skin_seen_prepass[2] = {0, 0};
+    // (the marks -- device_resources.h StreamMark -- keep the rules: never recorded or recorded on the waiting stream itself, nothing to wait for)
+    StreamMark shadow_fork, shadow_drawn;
+    // Skinning: k_skin runs on the main stream, which has joined every earlier prepass (prepass_done, shadow_drawn) -- so it follows every k_vertex that
+    // still reads the buffer it overwrites.  `deformed` is recorded behind it; the shadow and prepass streams wait for it before their next pass,
+    // once per recording (*_seen: the generation each of those streams has waited for)
+    StreamMark deformed;
+    uint64_t skin_seen_shadow = 0, skin_seen_prepass[2] = {0, 0};
     // The shadow pass has ONE set of scratch (geo[1], tables[1], its four counters) whichever stream it runs on -- the main stream
-    // (arctic_pass_shadow_map, a sharded map, debug bit 7) or shadow_stream (whole frames).  ev_shadow_scratch marks the end of the
-    // last shadow pass on shadow_scratch_stream; a pass on another stream waits for it first, so two never share the scratch.
-    Event ev_shadow_scratch;
-    hipStream_t shadow_scratch_stream = nullptr;
-    bool shadow_scratch_valid = false;
+    // (arctic_pass_shadow_map, a sharded map, debug bit 7) or shadow_stream (whole frames).  shadow_scratch_free marks the end of the
+    // last shadow pass; a pass on another stream waits for it first, so two never share the scratch.
+    StreamMark shadow_scratch_free;
     // Frames in flight (arctic_render_frame, ARCTIC_OPT_FRAMES_IN_FLIGHT = 2): the visibility prepass of frame k + 1 runs on
     // prepass_stream while the main stream still shades frame k, so there are two sets of what the prepass writes and the
     // shading reads -- visibility plane, vertex / record / item tables, object tables -- and `cur` names the set of the latest frame
-    // (the one the pass-level calls and arctic_read_gbuffer see).  ev_released[s]: everything enqueued on the main stream up to
+    // (the one the pass-level calls and arctic_read_gbuffer see).  vis_set_released[s]: everything enqueued on the main stream up to
     // the moment the handle moved on from set s; the next prepass into s waits for it.
     // Up to three sets (the reference keeps 3 frames in flight, rhi.hpp:25) and two prepass streams used alternately: with three
     // sets the prepasses of two consecutive frames are independent of each other as well, and a small frame -- whose prepass is a
     // chain of launches longer than its shading -- is bound by neither chain alone.
     int frames_in_flight = 2, frames_in_flight_opt = 0 /* ARCTIC_OPT_FRAMES_IN_FLIGHT; 0: by the target's size (alloc_targets) */, cur = 0, prepass_turn = 0;
-    Event ev_prepass[2], ev_released[3];   // (prepass_stream[2]: below)
-    bool released_valid[3] = {false, false, false};
+    StreamMark prepass_done[2], vis_set_released[3];   // (prepass_stream[2]: below)
     DevBuf &d_vis() { return d_vis_set[cur]; }
     int fwd() const { return cur ? cur + 1 : 0; }      // index of the current forward set in tables / geo
     bool recs_worst_case = false;   // record table at 7 per source triangle (after an overflow of the 2-per-triangle table)
@@ -359,8 +356,8 @@ struct ArcticRenderer {
     // arctic_comm_init) OR the second prepass stream of three frames in flight, never both: a gather queued in front of a prepass would
     // stall it behind the other ranks, and synchronising a prepass stream must never wait for an unmatched collective.
     bool own_stream_is_prepass() const { return stream != own_stream && !comm_stream_borrowed; }
-    Event ev_main;
-    struct InFlight { const void *ptr = nullptr; Event done; } inflight[4];   // gathers that still read a shard buffer
+    StreamMark shaded;                // the main stream, where a gather starts
+    ReaderTable<4> shard_readers;     // gathers that still read a shard buffer
     std::vector<uint32_t> peer_rows, peer_ranges;    // rows of every rank's shard; [begin, end) of every rank (row-range shards)
     std::vector<uint64_t> peer_offset;               // byte offset of every rank's shard in the root's staging buffer (arctic_exchange_plan)
     uint64_t staging_bytes = 0;
@@ -465,7 +462,7 @@ int alloc_targets(ArcticRenderer *r) {
     // their shading (tools/experiments/in_flight.py, 2 / 3 in flight: 1080p config 2 0.077 / 0.065 ms, config 3 at 1080p 0.094 / 0.088,
     // config 1 0.030 / 0.026; 4K 0.278 / 0.284)
     if (r->frames_in_flight_opt == 0) { r->frames_in_flight = (uint64_t)r->rows() * r->width < 3000000ull ? 3 : 2; r->cur = 0; }
-    r->released_valid[0] = r->released_valid[1] = r->released_valid[2] = false;   // (callers synchronise before they resize)
+    for (StreamMark &m : r->vis_set_released) m.forget();   // (callers synchronise before they resize)
     HIPCHECK(r, r->d_p0.ensure(px * 16));
     HIPCHECK(r, r->d_p1.ensure(px * 16));
     HIPCHECK(r, r->d_p2.ensure(px * 16));
@@ -711,11 +708,9 @@ int pass_shadow_map(ArcticRenderer *r, const ArcticScene *sc, hipStream_t stream
     if (r->shadow_size == 0) return ARCTIC_OK;
     Range zone("Shadow Map Pass");
     r->bounds_valid() = false;
-    if (r->shadow_scratch_valid && r->shadow_scratch_stream != stream)   // the previous shadow pass ran on another stream: it owns the scratch until it ends
-        HIPCHECK(r, hipStreamWaitEvent(stream, r->ev_shadow_scratch, 0));
+    HIPCHECK(r, r->shadow_scratch_free.wait(stream));   // the previous shadow pass ran on another stream: it owns the scratch until it ends
     int rc = run_geometry(r, sc, true, stream);
-    HIPCHECK(r, hipEventRecord(r->ev_shadow_scratch, stream));
-    r->shadow_scratch_stream = stream; r->shadow_scratch_valid = true;
+    HIPCHECK(r, r->shadow_scratch_free.record(stream));
     if (rc != ARCTIC_OK) return rc;
     if (r->shadow_sharded && r->comm && r->comm_world > 1) {
         // every rank has drawn ceil(S / world) rows of the map: one in-place all-gather (the send buffer is this rank's slice of the
@@ -737,8 +732,7 @@ float *cube_faces(ArcticRenderer *r) { return reinterpret_cast<float *>(r->d_cub
 int pass_point_shadows(ArcticRenderer *r, const ArcticScene *sc, hipStream_t stream) {
     if (!r->n_cubes) return ARCTIC_OK;
     Range zone("Point Shadow Pass");
-    if (r->shadow_scratch_valid && r->shadow_scratch_stream != stream)   // the previous shadow pass ran on another stream: it owns the scratch until it ends
-        HIPCHECK(r, hipStreamWaitEvent(stream, r->ev_shadow_scratch, 0));
+    HIPCHECK(r, r->shadow_scratch_free.wait(stream));   // the previous shadow pass ran on another stream: it owns the scratch until it ends
     const size_t texels = (size_t)r->cube_size * r->cube_size;
     int rc = ARCTIC_OK;
     for (uint32_t i = 0; i < r->n_cubes && rc == ARCTIC_OK; ++i) {
@@ -752,8 +746,7 @@ int pass_point_shadows(ArcticRenderer *r, const ArcticScene *sc, hipStream_t str
             rc = run_geometry(r, sc, true, stream, &t);
         }
     }
-    HIPCHECK(r, hipEventRecord(r->ev_shadow_scratch, stream));
-    r->shadow_scratch_stream = stream; r->shadow_scratch_valid = true;
+    HIPCHECK(r, r->shadow_scratch_free.record(stream));
     return rc;
 }
 
@@ -961,8 +954,8 @@ int pass_shade(ArcticRenderer *r, const ArcticScene *sc, const ArcticSettings *s
         if (!d_out) HIPCHECK(r, r->d_aa.ensure((size_t)r->rows() * r->width * 4));
         aa_out = d_out ? d_out : r->d_aa.p;
     }
-    for (auto &f : r->inflight)   // a gather of an earlier frame may still be reading this output buffer (or the one the filter writes)
-        if (f.ptr && (f.ptr == static_cast<const void *>(sp.out_rgba8) || f.ptr == aa_out)) { HIPCHECK(r, hipStreamWaitEvent(r->stream, f.done, 0)); f.ptr = nullptr; }
+    HIPCHECK(r, r->shard_readers.wait_for(sp.out_rgba8, r->stream));   // a gather of an earlier frame may still be reading this output buffer ...
+    HIPCHECK(r, r->shard_readers.wait_for(aa_out, r->stream));         // ... or the one the filter writes
     if (r->count_evals) {
         sp.stats = r->d_counter.as<unsigned long long>();
         HIPCHECK(r, hipMemsetAsync(r->d_counter.p, 0, 8 * N_SHADE_STATS, r->stream));
@@ -985,6 +978,16 @@ int pass_shade(ArcticRenderer *r, const ArcticScene *sc, const ArcticSettings *s
     return ARCTIC_OK;
 }
 
+// the tail of every cache key (shadow_inputs, cube_inputs, ray_inputs): per object its transform, its mesh and -- the mesh exists -- the mesh's
+// shape: a skin, pose or morph call changes what the object casts (arctic_set_mesh_pose)
+void put_objects(const ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_t> &k) {
+    auto put = [&](const void *p, size_t n) { const uint8_t *b = static_cast<const uint8_t *>(p); k.insert(k.end(), b, b + n); };
+    for (uint64_t i = 0; i < sc->n_objects; ++i) {
+        put(sc->objects[i].trs, sizeof sc->objects[i].trs); put(&sc->objects[i].mesh_idx, sizeof sc->objects[i].mesh_idx);
+        if (sc->objects[i].mesh_idx < r->meshes.size()) put(&r->meshes[sc->objects[i].mesh_idx].shape_seq, sizeof(uint64_t));
+    }
+}
+
 // everything the shadow map is a function of, as bytes (compared exactly, not hashed)
 std::vector<uint8_t> shadow_inputs(const ArcticRenderer *r, const ArcticScene *sc) {
     std::vector<uint8_t> k;
@@ -994,11 +997,7 @@ std::vector<uint8_t> shadow_inputs(const ArcticRenderer *r, const ArcticScene *s
     put(head, sizeof head);
     put(sc->sun.position, sizeof sc->sun.position);
     put(sc->sun.rotation, sizeof sc->sun.rotation);
-    for (uint64_t i = 0; i < sc->n_objects; ++i) {
-        put(sc->objects[i].trs, sizeof sc->objects[i].trs); put(&sc->objects[i].mesh_idx, sizeof sc->objects[i].mesh_idx);
-        // the mesh's shape: a skin or pose call changes what the object casts (arctic_set_mesh_pose)
-        if (sc->objects[i].mesh_idx < r->meshes.size()) put(&r->meshes[sc->objects[i].mesh_idx].shape_seq, sizeof(uint64_t));
-    }
+    put_objects(r, sc, k);
     return k;
 }
 
@@ -1010,17 +1009,13 @@ std::vector<uint8_t> cube_inputs(const ArcticRenderer *r, const ArcticScene *sc)
     const uint64_t head[6] = {r->cube_size, r->n_cubes, (uint64_t)r->meshes.size(), sc->n_objects, (uint64_t)r->cluster_cull, (uint64_t)r->small_triangles};
     put(head, sizeof head);
     put(r->cube_lights.data(), r->cube_lights.size() * sizeof(ArcticPointShadowLight));
-    for (uint64_t i = 0; i < sc->n_objects; ++i) {
-        put(sc->objects[i].trs, sizeof sc->objects[i].trs); put(&sc->objects[i].mesh_idx, sizeof sc->objects[i].mesh_idx);
-        // the mesh's shape: a skin or pose call changes what the object casts (arctic_set_mesh_pose)
-        if (sc->objects[i].mesh_idx < r->meshes.size()) put(&r->meshes[sc->objects[i].mesh_idx].shape_seq, sizeof(uint64_t));
-    }
+    put_objects(r, sc, k);
     return k;
 }
 
 // a stream other than the main one is about to run a prepass: it first waits for the latest k_skin (enqueued on the main stream)
 int wait_skin(ArcticRenderer *r, hipStream_t stream, uint64_t &seen) {
-    if (seen != r->skin_seq) { HIPCHECK(r, hipStreamWaitEvent(stream, r->ev_skin, 0)); seen = r->skin_seq; }
+    HIPCHECK(r, r->deformed.wait_once(stream, seen));
     return ARCTIC_OK;
 }
 
@@ -1110,27 +1105,27 @@ ArcticRenderer *arctic_create(const ArcticCreateInfo *info, char *err, uint64_t 
     // The events below order streams of THIS device among each other (prepass / shadow pass / shading of frames in flight); nothing waits for them on the
     // host or on another device.  Without the system-scope fence HIP otherwise puts around every record and wait -- a cache write-back and invalidate between
     // two shading kernels -- a 4K frame takes 0.256 instead of 0.261 ms, one rank of 8's 0.065 instead of 0.069 (round 5, tools/experiments/cull_ab.py's loop).
-    // (ev_main and the gather's events, which RCCL's transfers to other devices follow, keep the default.)
+    // (`shaded` and the gather's marks, which RCCL's transfers to other devices follow, keep the default.)
     const unsigned in_device_event = hipEventDisableTiming | hipEventDisableSystemFence;
     if ((e = hipSetDevice(r->device)) != hipSuccess) return bail("hipSetDevice", e);
     if ((e = r->own_stream.create(hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
     r->stream = r->own_stream;
     if ((e = r->shadow_stream.create(hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
-    if ((e = r->ev_fork.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = r->ev_shadow.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = r->ev_shadow_scratch.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = r->ev_skin.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = r->shadow_fork.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = r->shadow_drawn.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = r->shadow_scratch_free.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = r->deformed.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
     // The HIP runtime deals its hardware queues (4 by default, GPU_MAX_HW_QUEUES) to streams in the order they are created, and two
     // streams on one queue do not overlap: the handle's own stream, the shadow stream and the first prepass stream are created here, in
     // that order (with a caller's stream that makes four); the second prepass stream, which only three frames in flight use, is the
     // handle's own stream when the caller brought one (it is idle then), else created when first needed (second_prepass_stream)
     if ((e = r->prepass_stream[0].create(hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
     for (int k = 0; k < 2; ++k)
-        if ((e = r->ev_prepass[k].create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
-    for (Event &ev : r->ev_released)
-        if ((e = ev.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
-    for (Event &ev : r->ev_shadow_released)
-        if ((e = ev.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+        if ((e = r->prepass_done[k].create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    for (StreamMark &m : r->vis_set_released)
+        if ((e = m.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
+    for (StreamMark &m : r->shadow_set_released)
+        if ((e = m.create(in_device_event)) != hipSuccess) return bail("hipEventCreate", e);
     {
         hipDeviceProp_t prop;
         if ((e = hipGetDeviceProperties(&prop, r->device)) != hipSuccess) return bail("hipGetDeviceProperties", e);
@@ -1184,13 +1179,21 @@ int arctic_resize(ArcticRenderer *r, uint32_t width, uint32_t height) {
     return alloc_targets(r);
 }
 
+namespace {
+// the main stream and whatever runs prepasses for it: what arctic_flush and a change of the frames in flight wait for
+int drain_frame_streams(ArcticRenderer *r) {
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    for (hipStream_t ps : r->prepass_stream) if (ps) HIPCHECK(r, hipStreamSynchronize(ps));   // (joined into the main stream by every frame; after a failed frame they may not be)
+    if (r->own_stream_is_prepass()) HIPCHECK(r, hipStreamSynchronize(r->own_stream));         // (the second prepass stream of a handle on a caller's stream)
+    return ARCTIC_OK;
+}
+}  // namespace
+
 int arctic_flush(ArcticRenderer *r) {
     if (!r) return ARCTIC_E_INVALID;
     int rc = select_device(r);
     if (rc) return rc;
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    for (hipStream_t ps : r->prepass_stream) if (ps) HIPCHECK(r, hipStreamSynchronize(ps));   // (joined into the main stream by every frame; after a failed frame they may not be)
-    if (r->own_stream_is_prepass()) HIPCHECK(r, hipStreamSynchronize(r->own_stream));         // (the second prepass stream of a handle on a caller's stream)
+    if ((rc = drain_frame_streams(r)) != ARCTIC_OK) return rc;
     HIPCHECK(r, hipStreamSynchronize(r->shadow_stream));
     if (r->comm_stream) HIPCHECK(r, hipStreamSynchronize(r->comm_stream));
     if (int ov = check_item_overflow(r)) return ov;
@@ -1455,8 +1458,7 @@ int arctic_set_mesh_pose(ArcticRenderer *r, uint64_t mesh, const float *joint_ma
     // that reads the buffer k_skin overwrites
     HIPCHECK(r, m.joints_ring.send(m.d_joints.p, bytes, r->stream));
     HIPCHECK(r, launch_skin(m.skin_input(), m.d_skin.p, m.d_joints.as<float>(), m.n_vertices, n_joints, m.d_posed.as<float>(), r->stream));
-    HIPCHECK(r, hipEventRecord(r->ev_skin, r->stream));
-    ++r->skin_seq;
+    HIPCHECK(r, r->deformed.record(r->stream));
     m.posed = true;
     ++m.shape_seq;
     return ARCTIC_OK;
@@ -1482,8 +1484,7 @@ int reskin(ArcticRenderer *r, Mesh &m) {
 }
 // behind the last deformation kernel of a call: what the shadow and prepass streams wait for (wait_skin)
 int deformed_on_main_stream(ArcticRenderer *r) {
-    HIPCHECK(r, hipEventRecord(r->ev_skin, r->stream));
-    ++r->skin_seq;
+    HIPCHECK(r, r->deformed.record(r->stream));
     return ARCTIC_OK;
 }
 }  // namespace
@@ -1881,21 +1882,20 @@ int arctic_render_frame_device(ArcticRenderer *r, const ArcticScene *scene, cons
         r->shadow_key.clear();
         if (beside) {
             if (shadow_in_flight) {
-                HIPCHECK(r, hipEventRecord(r->ev_shadow_released[r->scur], r->stream));
-                r->shadow_released_valid[r->scur] = true;
+                HIPCHECK(r, r->shadow_set_released[r->scur].record(r->stream));
                 r->scur ^= 1;
                 HIPCHECK(r, r->d_shadow().ensure(shadow_alloc_bytes(r)));   // first use of the second map (cleared by the pass itself)
-                if (r->shadow_released_valid[r->scur]) HIPCHECK(r, hipStreamWaitEvent(r->shadow_stream, r->ev_shadow_released[r->scur], 0));
+                HIPCHECK(r, r->shadow_set_released[r->scur].wait(r->shadow_stream));
             } else {
-                HIPCHECK(r, hipEventRecord(r->ev_fork, r->stream));
-                HIPCHECK(r, hipStreamWaitEvent(r->shadow_stream, r->ev_fork, 0));
+                HIPCHECK(r, r->shadow_fork.record(r->stream));
+                HIPCHECK(r, r->shadow_fork.wait(r->shadow_stream));
             }
             rc = wait_skin(r, r->shadow_stream, r->skin_seen_shadow);
             if (rc == ARCTIC_OK) rc = pass_shadow_map(r, scene, r->shadow_stream);
             if (rc == ARCTIC_OK && !(r->debug & 8)) rc = build_shadow_bounds(r, r->shadow_stream);
-            HIPCHECK(r, hipEventRecord(r->ev_shadow, r->shadow_stream));
+            HIPCHECK(r, r->shadow_drawn.record(r->shadow_stream));
         } else rc = pass_shadow_map(r, scene, r->stream);
-        if (rc != ARCTIC_OK) { if (beside) (void)hipStreamWaitEvent(r->stream, r->ev_shadow, 0); return rc; }
+        if (rc != ARCTIC_OK) { if (beside) (void)r->shadow_drawn.wait(r->stream); return rc; }
         r->shadow_key.swap(key);
     }
     // whole frames skip the G-buffer: the shading pass interpolates from the visibility plane (k_material_vis), bit-identical
@@ -1907,8 +1907,7 @@ int arctic_render_frame_device(ArcticRenderer *r, const ArcticScene *scene, cons
     // frame's shading and precede this one's, a prepass running ahead would only compete with it)
     const bool in_flight = vis_path && r->frames_in_flight > 1 && (!redraw || shadow_in_flight);
     if (in_flight) {
-        HIPCHECK(r, hipEventRecord(r->ev_released[r->cur], r->stream));   // everything that reads or writes the set being left is enqueued by now
-        r->released_valid[r->cur] = true;
+        HIPCHECK(r, r->vis_set_released[r->cur].record(r->stream));   // everything that reads or writes the set being left is enqueued by now
         r->cur = (r->cur + 1) % r->frames_in_flight;
         r->have_vis = r->have_gbuffer = r->have_order = false;            // of the set entered: overwritten now
         // consecutive prepasses on alternate streams when there are three sets (they overlap then); with two, one stream as before
@@ -1918,13 +1917,13 @@ int arctic_render_frame_device(ArcticRenderer *r, const ArcticScene *scene, cons
             if (r->own_stream_is_prepass()) ps = r->own_stream;
             else { if (!r->prepass_stream[1]) HIPCHECK(r, r->prepass_stream[1].create(hipStreamNonBlocking)); ps = r->prepass_stream[1]; }
         }
-        if (r->released_valid[r->cur]) HIPCHECK(r, hipStreamWaitEvent(ps, r->ev_released[r->cur], 0));
+        HIPCHECK(r, r->vis_set_released[r->cur].wait(ps));
         rc = wait_skin(r, ps, r->skin_seen_prepass[turn]);
         if (rc == ARCTIC_OK) rc = pass_visibility(r, scene, ps);
-        HIPCHECK(r, hipEventRecord(r->ev_prepass[turn], ps));
-        HIPCHECK(r, hipStreamWaitEvent(r->stream, r->ev_prepass[turn], 0));
+        HIPCHECK(r, r->prepass_done[turn].record(ps));
+        HIPCHECK(r, r->prepass_done[turn].wait(r->stream));
     } else rc = vis_path ? pass_visibility(r, scene, r->stream) : pass_gbuffer(r, scene);
-    if (beside) HIPCHECK(r, hipStreamWaitEvent(r->stream, r->ev_shadow, 0));   // the map and its table are complete
+    if (beside) HIPCHECK(r, r->shadow_drawn.wait(r->stream));   // the map and its table are complete
     if (rc != ARCTIC_OK) return rc;
     // the point lights' faces: redrawn when their inputs changed, on the main stream -- behind the previous frame's shading, which reads
     // the one set of faces, and in front of this frame's
@@ -2333,11 +2332,9 @@ int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
         r->frames_in_flight_opt = (int)value;
         if (value == 0) value = (uint64_t)r->rows() * r->width < 3000000ull ? 3 : 2;
         if ((int)value != r->frames_in_flight) {   // the sets change roles: nothing may be in flight, and `cur` must name a set that exists
-            HIPCHECK(r, hipStreamSynchronize(r->stream));
-            for (hipStream_t ps : r->prepass_stream) if (ps) HIPCHECK(r, hipStreamSynchronize(ps));
-            if (r->own_stream_is_prepass()) HIPCHECK(r, hipStreamSynchronize(r->own_stream));
+            if (int rc = drain_frame_streams(r)) return rc;
             if (r->cur >= (int)value) { r->cur = 0; r->have_vis = r->have_gbuffer = r->have_order = false; }
-            r->released_valid[0] = r->released_valid[1] = r->released_valid[2] = false;
+            for (StreamMark &m : r->vis_set_released) m.forget();
         }
         r->frames_in_flight = (int)value;
         break;
@@ -2431,10 +2428,7 @@ void ray_inputs(const ArcticRenderer *r, const ArcticScene *sc, std::vector<uint
     auto put = [&](const void *p, size_t n) { const uint8_t *b = static_cast<const uint8_t *>(p); k.insert(k.end(), b, b + n); };
     const uint64_t head[2] = {(uint64_t)r->meshes.size(), sc->n_objects};
     put(head, sizeof head);
-    for (uint64_t i = 0; i < sc->n_objects; ++i) {
-        put(sc->objects[i].trs, sizeof sc->objects[i].trs); put(&sc->objects[i].mesh_idx, sizeof sc->objects[i].mesh_idx);
-        if (sc->objects[i].mesh_idx < r->meshes.size()) put(&r->meshes[sc->objects[i].mesh_idx].shape_seq, sizeof(uint64_t));
-    }
+    put_objects(r, sc, k);
 }
 
 // may the cached structure follow `sc` by a refit?  Host state only (include/arctic_hip.h: "Eligibility")
@@ -2873,8 +2867,8 @@ int arctic_comm_init(ArcticRenderer *r, const void *id_bytes, int rank, int worl
             if (r->stream != r->own_stream) { r->comm_stream = r->own_stream; r->comm_stream_borrowed = true; }
             else { HIPCHECK(r, r->comm_stream_owned.create(hipStreamNonBlocking)); r->comm_stream = r->comm_stream_owned; }
         }
-        HIPCHECK(r, r->ev_main.ensure(hipEventDisableTiming));
-        for (auto &f : r->inflight) HIPCHECK(r, f.done.ensure(hipEventDisableTiming));
+        HIPCHECK(r, r->shaded.ensure(hipEventDisableTiming));
+        HIPCHECK(r, r->shard_readers.ensure(hipEventDisableTiming));
         // every rank's shard layout: {row_begin, row_end, rows, band_rows} all-gathered once (the root places shards of unequal size)
         HIPCHECK(r, tmp.ensure((size_t)world * 16));
         const uint32_t mine[4] = {r->band_rows ? 0u : r->row_begin, r->band_rows ? 0u : r->row_end, r->rows(), r->band_rows};
@@ -2902,8 +2896,8 @@ int arctic_comm_destroy(ArcticRenderer *r) {
     if (r->comm) { (void)g_rccl.CommDestroy(r->comm); r->comm = nullptr; }
     r->comm_rank = 0; r->comm_world = 1;
     if (r->layout_from_comm) { r->layout_world = 0; r->layout_from_comm = false; }
-    for (auto &f : r->inflight) { f.done.release(); f.ptr = nullptr; }
-    r->ev_main.release();
+    r->shard_readers.release();
+    r->shaded.release();
     r->comm_stream_owned.release();   // (nothing when the stream was borrowed: own_stream stays the handle's)
     r->comm_stream = nullptr; r->comm_stream_borrowed = false;
     return ARCTIC_OK;
@@ -2922,8 +2916,8 @@ int arctic_gather_frame(ArcticRenderer *r, const void *d_shard, void *d_frame, i
     int rc = select_device(r);
     if (rc) return rc;
     const size_t row_bytes = (size_t)r->width * 4;
-    HIPCHECK(r, hipEventRecord(r->ev_main, r->stream));               // after the shading that produced the shard ...
-    HIPCHECK(r, hipStreamWaitEvent(r->comm_stream, r->ev_main, 0));   // ... on the communication stream, beside the next frame
+    HIPCHECK(r, r->shaded.record(r->stream));        // after the shading that produced the shard ...
+    HIPCHECK(r, r->shaded.wait(r->comm_stream));     // ... on the communication stream, beside the next frame
     const uint8_t *src = static_cast<const uint8_t *>(d_shard);
     if (r->comm_world > 1) {
         // the transfers of this rank, straight from the plan (arctic_exchange_transfers: what the CPU tests check for worlds 2..8)
@@ -2950,12 +2944,9 @@ int arctic_gather_frame(ArcticRenderer *r, const void *d_shard, void *d_frame, i
         HIPCHECK(r, launch_place_rows(src, static_cast<uint8_t *>(d_frame), r->width, r->height, r->band_rows, (uint32_t)r->comm_world,
                                       layout_ranges(r), layout_offsets(r), r->comm_stream));
     // whoever writes this shard buffer next waits for the transfers that still read it
-    ArcticRenderer::InFlight *slot = nullptr;
-    for (auto &f : r->inflight) if (f.ptr == d_shard) slot = &f;
-    if (!slot) for (auto &f : r->inflight) if (!f.ptr) { slot = &f; break; }
-    if (!slot) { HIPCHECK(r, hipStreamSynchronize(r->comm_stream)); for (auto &f : r->inflight) f.ptr = nullptr; slot = &r->inflight[0]; }
-    slot->ptr = d_shard;
-    HIPCHECK(r, hipEventRecord(slot->done, r->comm_stream));
+    StreamMark *gathered = nullptr;
+    HIPCHECK(r, r->shard_readers.claim(d_shard, r->comm_stream, gathered));
+    HIPCHECK(r, gathered->record(r->comm_stream));
     return ARCTIC_OK;
 }
 

@@ -20,7 +20,7 @@ enum Kind { DEVICE, PINNED, EVENT, STREAM, N_KINDS };
 struct Call { std::string fn; void *handle; size_t arg; void *stream; const void *src; };
 std::vector<Call> calls;
 std::set<void *> live[N_KINDS];
-int double_releases = 0, refuse_device = 0, refuse_pinned = 0, refuse_alias = 0;
+int double_releases = 0, refuse_device = 0, refuse_pinned = 0, refuse_alias = 0, refuse_wait = 0;
 
 void *make(Kind k, size_t bytes) { void *p = std::malloc(bytes ? bytes : 1); live[k].insert(p); return p; }
 void drop(Kind k, void *p) { if (live[k].erase(p)) std::free(p); else ++double_releases; }
@@ -46,6 +46,10 @@ hipError_t hipHostGetDevicePointer(void **d, void *h, unsigned) {
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned flags) { *e = static_cast<hipEvent_t>(make(EVENT, 1)); calls.push_back({"hipEventCreateWithFlags", *e, flags, nullptr, nullptr}); return hipSuccess; }
 hipError_t hipEventDestroy(hipEvent_t e) { calls.push_back({"hipEventDestroy", e, 0, nullptr, nullptr}); drop(EVENT, e); return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { calls.push_back({"hipEventRecord", e, 0, s, nullptr}); return live[EVENT].count(e) ? hipSuccess : hipErrorInvalidHandle; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned flags) {
+    if (refused(refuse_wait)) { calls.push_back({"hipStreamWaitEvent!", e, flags, s, nullptr}); return hipErrorInvalidValue; }
+    calls.push_back({"hipStreamWaitEvent", e, flags, s, nullptr}); return live[EVENT].count(e) ? hipSuccess : hipErrorInvalidHandle;
+}
 hipError_t hipEventSynchronize(hipEvent_t e) { calls.push_back({"hipEventSynchronize", e, 0, nullptr, nullptr}); return live[EVENT].count(e) ? hipSuccess : hipErrorInvalidHandle; }
 hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind, hipStream_t s) {
     calls.push_back({"hipMemcpyAsync", dst, n, s, src}); std::memcpy(dst, src, n); return hipSuccess;   // (a real copy: the sanitizer sees a slot or a destination that is too small)
@@ -162,7 +166,7 @@ void ring_of_one() {
     done(name);
 }
 
-struct Holder { DevBuf d; PinnedBuf p; Event e; UploadRing<3> ring; int tag = 0; };
+struct Holder { DevBuf d; PinnedBuf p; Event e; UploadRing<3> ring; StreamMark mark; ReaderTable<4> readers; int tag = 0; };
 
 void moved_in_a_vector() {
     const char *name = "move-vector-growth";
@@ -176,6 +180,11 @@ void moved_in_a_vector() {
         at = calls.size();
         CHECK(v[0].e.ensure(hipEventDisableTiming) == hipSuccess && calls.size() == at);   // created already: nothing
         CHECK(v[0].ring.stage(64, &h) == hipSuccess && v[0].ring.send(dst.data(), 64, nullptr) == hipSuccess);
+        hipStream_t on = reinterpret_cast<hipStream_t>(&failures);
+        StreamMark *claimed = nullptr;
+        CHECK(v[0].mark.create(hipEventDisableTiming) == hipSuccess && v[0].mark.record(on) == hipSuccess);
+        CHECK(v[0].readers.ensure(hipEventDisableTiming) == hipSuccess && v[0].readers.claim(dst.data(), nullptr, claimed) == hipSuccess && claimed->record(on) == hipSuccess);
+        const hipEvent_t mark_ev = v[0].mark.ev, reader_ev = claimed->ev;
         v[0].tag = 42;
         void *d = v[0].d.p, *p = v[0].p.p;
         hipEvent_t e = v[0].e;
@@ -186,10 +195,15 @@ void moved_in_a_vector() {
         CHECK(calls.size() == n_calls);                               // ... without a runtime call
         CHECK(v[0].tag == 42 && v[0].d.p == d && v[0].d.cap == 381 && v[0].p.p == p && v[0].p.d == p && v[0].p.cap == 64 && v[0].e == e);
         CHECK(v[0].ring.turn == 1 && v[0].ring.slot[0].pending && v[0].ring.slot[0].h.p == h && !v[0].ring.slot[1].pending);
+        CHECK(v[0].mark.ev == mark_ev && v[0].mark.recorded && v[0].mark.on == on && v[0].mark.generation == 1);
+        CHECK(v[0].readers.slot[0].ptr == dst.data() && v[0].readers.slot[0].done.ev == reader_ev && v[0].readers.slot[0].done.recorded && !v[0].readers.slot[1].ptr);
         CHECK(alive() == n_alive && live[DEVICE].size() == n_dev && live[PINNED].size() == n_pin && live[EVENT].size() == n_ev);
         at = calls.size();
         CHECK(v[0].ring.send(dst.data(), 0, nullptr) == hipSuccess && v[0].ring.send(dst.data(), 0, nullptr) == hipSuccess);
         CHECK(v[0].ring.stage(64, &h) == hipSuccess && since(at) == "hipEventSynchronize");   // the pending slot is still waited for after the move
+        at = calls.size();
+        CHECK(v[0].mark.wait(nullptr) == hipSuccess && v[0].readers.wait_for(dst.data(), nullptr) == hipSuccess && since(at) == "hipStreamWaitEvent hipStreamWaitEvent");
+        CHECK(calls[at].handle == mark_ev && calls[at + 1].handle == reader_ev);   // the mark and the claimed slot are still waited for after the move
         v.clear();
         CHECK(alive() == 0);
     }
@@ -247,6 +261,221 @@ void streams_and_events() {
     CHECK(alive() == 0 && double_releases == 0 && since(calls.size() - 3) == "hipStreamSynchronize hipStreamDestroy hipEventDestroy");   // a scope's end does the same
     done(name);
 }
+
+// two streams that exist (the default stream, nullptr, is the third one the cases use)
+struct TwoStreams {
+    Stream a, b;
+    bool make() { return a.create(hipStreamNonBlocking) == hipSuccess && b.create(hipStreamNonBlocking) == hipSuccess; }
+};
+bool waited(size_t at, hipStream_t stream, hipEvent_t ev) {   // exactly one call since `at`: `stream` waits for `ev`
+    return calls.size() == at + 1 && calls[at].fn == "hipStreamWaitEvent" && calls[at].stream == stream && calls[at].handle == ev && calls[at].arg == 0;
+}
+
+void marks() {
+    const char *name = "mark-never-recorded-never-waited-for";
+    {
+        TwoStreams s;
+        StreamMark m, empty;
+        uint64_t seen = 0;
+        CHECK(s.make() && m.create(hipEventDisableTiming) == hipSuccess && calls.back().fn == "hipEventCreateWithFlags" && calls.back().arg == hipEventDisableTiming);
+        size_t at = calls.size();
+        CHECK(m.wait(s.a) == hipSuccess && m.wait(nullptr) == hipSuccess && m.wait_once(s.a, seen) == hipSuccess && m.wait_once(nullptr, seen) == hipSuccess);
+        CHECK(empty.wait(s.a) == hipSuccess && empty.wait_once(nullptr, seen) == hipSuccess);
+        CHECK(calls.size() == at && seen == 0 && !m.recorded && m.generation == 0);
+        CHECK(m.ensure(hipEventDisableTiming) == hipSuccess && calls.size() == at);   // created already: nothing
+    }
+    CHECK(alive() == 0 && double_releases == 0);
+    done(name);
+    name = "mark-same-stream-elided-others-wait";
+    {
+        TwoStreams s;
+        CHECK(s.make());
+        const hipStream_t recorded_on[2] = {nullptr, s.a};   // the default stream is a stream like any other
+        for (hipStream_t on : recorded_on) {
+            StreamMark m;
+            CHECK(m.create(hipEventDisableTiming) == hipSuccess);
+            size_t at = calls.size();
+            CHECK(m.record(on) == hipSuccess && since(at) == "hipEventRecord" && calls[at].handle == m.ev.e && calls[at].stream == on);
+            CHECK(m.recorded && m.on == on && m.generation == 1);
+            at = calls.size();
+            CHECK(m.wait(on) == hipSuccess && calls.size() == at);                    // same stream: stream order does it
+            CHECK(m.wait(s.b) == hipSuccess && waited(at, s.b, m.ev));
+            const hipStream_t other = on ? nullptr : static_cast<hipStream_t>(s.a);
+            at = calls.size();
+            CHECK(m.wait(other) == hipSuccess && waited(at, other, m.ev));
+            at = calls.size();                                                        // two passes on one stream, then one on another (the shadow scratch)
+            CHECK(m.wait(on) == hipSuccess && m.record(on) == hipSuccess && m.wait(on) == hipSuccess && m.record(on) == hipSuccess && since(at) == "hipEventRecord hipEventRecord");
+            CHECK(m.wait(s.b) == hipSuccess && m.record(s.b) == hipSuccess && since(at + 2) == "hipStreamWaitEvent hipEventRecord" && calls[at + 2].stream == s.b && m.on == s.b);
+            at = calls.size();
+            CHECK(m.wait(s.b) == hipSuccess && calls.size() == at && m.wait(on) == hipSuccess && waited(at, on, m.ev));
+        }
+    }
+    CHECK(alive() == 0 && double_releases == 0);
+    done(name);
+    name = "mark-forget";
+    {
+        TwoStreams s;
+        StreamMark m;
+        CHECK(s.make() && m.create(0) == hipSuccess && m.record(s.a) == hipSuccess);
+        const hipEvent_t ev = m.ev;
+        size_t at = calls.size();
+        m.forget();
+        CHECK(m.wait(s.b) == hipSuccess && m.wait(nullptr) == hipSuccess && calls.size() == at && m.ev == ev && m.generation == 1);   // no runtime call, the event is kept
+        CHECK(m.record(nullptr) == hipSuccess && m.generation == 2);
+        at = calls.size();
+        CHECK(m.wait(nullptr) == hipSuccess && calls.size() == at && m.wait(s.b) == hipSuccess && waited(at, s.b, ev));
+        at = calls.size();
+        m.release();                                                                   // release forgets as well
+        CHECK(since(at) == "hipEventDestroy" && !m.recorded && !m.ev && m.wait(s.b) == hipSuccess && calls.size() == at + 1);
+    }
+    CHECK(alive() == 0 && double_releases == 0);
+    done(name);
+    name = "mark-generations";
+    {
+        TwoStreams s;
+        StreamMark m;
+        uint64_t seen_a = 0, seen_b = 0;
+        CHECK(s.make() && m.create(hipEventDisableTiming) == hipSuccess);
+        for (uint64_t g = 1; g <= 3; ++g) {   // each waiter waits once per record, however often it asks
+            CHECK(m.record(nullptr) == hipSuccess && m.generation == g);
+            size_t at = calls.size();
+            CHECK(m.wait_once(s.a, seen_a) == hipSuccess && waited(at, s.a, m.ev) && seen_a == g);
+            CHECK(m.wait_once(s.a, seen_a) == hipSuccess && calls.size() == at + 1);
+            if (g == 2) continue;             // waiter b misses a generation: it waits once for the latest
+            at = calls.size();
+            CHECK(m.wait_once(s.b, seen_b) == hipSuccess && waited(at, s.b, m.ev) && seen_b == g);
+            CHECK(m.wait_once(s.b, seen_b) == hipSuccess && m.wait_once(s.a, seen_a) == hipSuccess && calls.size() == at + 1);
+        }
+        seen_b = 0;                           // the waiter is another stream now (arctic_set_stream): it waits again, once
+        size_t at = calls.size();
+        CHECK(m.wait_once(s.b, seen_b) == hipSuccess && waited(at, s.b, m.ev) && seen_b == 3 && m.wait_once(s.b, seen_b) == hipSuccess && calls.size() == at + 1);
+        refuse_wait = 1;                      // a refused wait leaves `seen` as it was: the next call waits again
+        CHECK(m.record(nullptr) == hipSuccess);
+        at = calls.size();
+        CHECK(m.wait_once(s.a, seen_a) == hipErrorInvalidValue && seen_a == 3 && since(at) == "hipStreamWaitEvent!");
+        at = calls.size();
+        CHECK(m.wait_once(s.a, seen_a) == hipSuccess && waited(at, s.a, m.ev) && seen_a == 4);
+        seen_a = 0;                           // a waiter on the recording stream itself: nothing to wait for, and it has seen the generation
+        at = calls.size();
+        CHECK(m.wait_once(nullptr, seen_a) == hipSuccess && calls.size() == at && seen_a == 4);
+        StreamMark never;                     // a waiter reset to 0 waits again only if something was ever recorded
+        uint64_t seen = 0;
+        CHECK(never.create(0) == hipSuccess);
+        at = calls.size();
+        CHECK(never.wait_once(s.a, seen) == hipSuccess && calls.size() == at && seen == 0);
+    }
+    CHECK(alive() == 0 && double_releases == 0);
+    done(name);
+}
+
+// the sets of frames in flight.  A frame enters set k % 3 (its prepass stream waits for the set's mark) and leaves it when the next frame starts
+// (the main stream records the mark): renderer.cpp's "record the set left, advance, wait on the set entered" with the frame's own record put
+// first.  (The renderer's very first frame also records the set it starts in, which no frame has drawn into.)
+void ring_of_marks() {
+    const char *name = "mark-ring-of-three-sets";
+    {
+        TwoStreams s;
+        Stream main_stream;
+        StreamMark released[3];
+        CHECK(s.make() && main_stream.create(hipStreamNonBlocking) == hipSuccess);
+        for (StreamMark &m : released) CHECK(m.create(hipEventDisableTiming) == hipSuccess);
+        size_t record_of[3] = {0, 0, 0};   // index in `calls` of the set's latest record
+        for (int pass = 0; pass < 2; ++pass) {
+            for (int frame = 0; frame < (pass ? 3 : 7); ++frame) {
+                const int set = frame % 3;
+                const hipStream_t ps = frame & 1 ? s.b : s.a;
+                size_t at = calls.size();
+                CHECK(released[set].wait(ps) == hipSuccess);
+                if (frame < 3) CHECK(calls.size() == at);   // nothing has left this set (again, after forget): nothing to wait for
+                else {
+                    CHECK(waited(at, ps, released[set].ev));
+                    // the mark's latest record is the one made when this set was left three frames earlier, and nothing has been recorded on it since
+                    CHECK(calls[record_of[set]].fn == "hipEventRecord" && calls[record_of[set]].handle == released[set].ev.e && released[set].generation == (uint64_t)(frame / 3));
+                    for (size_t i = record_of[set] + 1; i < at; ++i) CHECK(!(calls[i].fn == "hipEventRecord" && calls[i].handle == released[set].ev.e));
+                }
+                record_of[set] = calls.size();
+                CHECK(released[set].record(main_stream) == hipSuccess && calls[record_of[set]].stream == main_stream);
+            }
+            size_t at = calls.size();
+            for (StreamMark &m : released) m.forget();      // the streams were drained (a resize, another number of frames in flight)
+            CHECK(calls.size() == at);
+        }
+        // the renderer's own order from a fresh handle: record the set left, advance, wait on the set entered
+        StreamMark fresh[3];
+        for (StreamMark &m : fresh) CHECK(m.create(hipEventDisableTiming) == hipSuccess);
+        int cur = 0;
+        for (int frame = 0; frame < 4; ++frame) {
+            CHECK(fresh[cur].record(main_stream) == hipSuccess);
+            cur = (cur + 1) % 3;
+            size_t at = calls.size();
+            CHECK(fresh[cur].wait(s.a) == hipSuccess && (frame < 2 ? calls.size() == at : waited(at, s.a, fresh[cur].ev)));
+        }
+    }
+    CHECK(alive() == 0 && double_releases == 0);
+    done(name);
+}
+
+void reader_table() {
+    const char *name = "reader-table";
+    char buf[6] = {};
+    {
+        TwoStreams s;
+        ReaderTable<4> t;
+        StreamMark *m = nullptr, *again = nullptr;
+        CHECK(s.make());
+        size_t at = calls.size();
+        CHECK(t.ensure(hipEventDisableTiming) == hipSuccess && since(at) == "hipEventCreateWithFlags hipEventCreateWithFlags hipEventCreateWithFlags hipEventCreateWithFlags");
+        CHECK(t.ensure(hipEventDisableTiming) == hipSuccess && calls.size() == at + 4);
+        at = calls.size();
+        CHECK(t.wait_for(&buf[0], s.a) == hipSuccess && t.wait_for(nullptr, s.a) == hipSuccess && calls.size() == at);   // nobody reads it: nothing
+        CHECK(t.claim(&buf[0], s.b, m) == hipSuccess && m == &t.slot[0].done && m->record(s.b) == hipSuccess);
+        CHECK(t.claim(&buf[1], s.b, m) == hipSuccess && m == &t.slot[1].done && m->record(s.b) == hipSuccess);
+        CHECK(t.claim(&buf[0], s.b, again) == hipSuccess && again == &t.slot[0].done && again->record(s.b) == hipSuccess);   // the same buffer: its slot again
+        CHECK(since(at) == "hipEventRecord hipEventRecord hipEventRecord" && t.slot[0].done.generation == 2 && !t.slot[2].ptr);
+        at = calls.size();
+        CHECK(t.wait_for(&buf[5], s.a) == hipSuccess && calls.size() == at);                                  // an unknown buffer: nothing
+        CHECK(t.wait_for(&buf[0], s.a) == hipSuccess && waited(at, s.a, t.slot[0].done.ev) && !t.slot[0].ptr);   // a known one: one wait, and the slot is free
+        CHECK(t.wait_for(&buf[0], s.a) == hipSuccess && calls.size() == at + 1);
+        CHECK(t.claim(&buf[2], s.b, m) == hipSuccess && m == &t.slot[0].done);                                // the first free slot
+        CHECK(t.claim(&buf[3], s.b, m) == hipSuccess && m == &t.slot[2].done && t.claim(&buf[4], s.b, m) == hipSuccess && m == &t.slot[3].done);
+        CHECK(calls.size() == at + 1);                                                                        // (claiming alone calls nothing)
+        at = calls.size();
+        CHECK(t.claim(&buf[5], s.b, m) == hipSuccess && since(at) == "hipStreamSynchronize" && calls[at].handle == s.b.s);   // a fifth buffer: the readers' stream is drained, once
+        CHECK(m == &t.slot[0].done && t.slot[0].ptr == &buf[5] && !t.slot[1].ptr && !t.slot[2].ptr && !t.slot[3].ptr);
+        refuse_wait = 1;                                                                                      // a refused wait keeps the slot
+        CHECK(m->record(s.b) == hipSuccess && t.wait_for(&buf[5], s.a) == hipErrorInvalidValue && t.slot[0].ptr == &buf[5]);
+        ReaderTable<4> moved = std::move(t);
+        CHECK(!t.slot[0].ptr && !t.slot[0].done.ev && !t.slot[0].done.recorded && moved.slot[0].ptr == &buf[5] && moved.slot[0].done.recorded);
+        at = calls.size();
+        CHECK(t.wait_for(&buf[5], s.a) == hipSuccess && calls.size() == at && moved.wait_for(&buf[5], s.a) == hipSuccess && waited(at, s.a, moved.slot[0].done.ev));
+        at = calls.size();
+        moved.release(); moved.release();
+        CHECK(since(at) == "hipEventDestroy hipEventDestroy hipEventDestroy hipEventDestroy" && !moved.slot[0].ptr);
+    }
+    CHECK(alive() == 0 && double_releases == 0);
+    done(name);
+    name = "mark-moves-and-release";
+    {
+        TwoStreams s;
+        StreamMark a, b;
+        CHECK(s.make() && a.create(hipEventDisableTiming) == hipSuccess && b.create(hipEventDisableTiming) == hipSuccess && a.record(s.a) == hipSuccess);
+        const hipEvent_t ev = a.ev;
+        StreamMark c = std::move(a);
+        CHECK(!a.ev && !a.recorded && a.on == nullptr && a.generation == 0 && c.ev == ev && c.recorded && c.on == s.a && c.generation == 1);
+        size_t at = calls.size();
+        CHECK(a.wait(s.b) == hipSuccess && calls.size() == at);     // a moved-from mark is empty: nothing to wait for
+        b = std::move(c);                                            // move assignment releases what it held
+        CHECK(since(at) == "hipEventDestroy" && live[EVENT].size() == 1 && b.ev == ev && b.recorded && !c.ev && !c.recorded);
+        at = calls.size();
+        CHECK(b.wait(s.b) == hipSuccess && waited(at, s.b, ev));
+        at = calls.size();
+        CHECK(b.create(hipEventDisableTiming) == hipSuccess && since(at) == "hipEventDestroy hipEventCreateWithFlags" && !b.recorded);   // made again: never recorded
+        b.release(); b.release(); a.release();
+        CHECK(since(at + 2) == "hipEventDestroy" && live[EVENT].empty());
+    }
+    CHECK(alive() == 0 && double_releases == 0);
+    done(name);
+}
 }  // namespace
 
 int main() {
@@ -256,6 +485,9 @@ int main() {
     moved_in_a_vector();
     refused_allocations();
     streams_and_events();
+    marks();
+    ring_of_marks();
+    reader_table();
     const char *name = "all-released-once";
     if (alive() != 0 || double_releases != 0) { std::printf("BAD %s: %zu handles alive, %d released twice\n", name, alive(), double_releases); ++failures; }
     else done(name);

@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "arctic-renderer_amd", "csrc")
 HIP_INCLUDE = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
 CASES = ("devbuf-ensure-and-exact", "ring3-seven-uploads", "ring1-waits-only-when-pending", "ring-slot-grows-and-is-kept", "move-vector-growth",
-         "failed-allocation-leaves-empty", "stream-waits-then-goes-once", "all-released-once")
+         "failed-allocation-leaves-empty", "stream-waits-then-goes-once", "mark-never-recorded-never-waited-for", "mark-same-stream-elided-others-wait",
+         "mark-forget", "mark-generations", "mark-ring-of-three-sets", "reader-table", "mark-moves-and-release", "all-released-once")
 
 
 def test_owners_under_sanitizers():
@@ -46,6 +47,14 @@ def test_renderer_releases_nothing_by_hand():
     body = m.group(1)
     assert "delete r;" in body and "arctic_comm_destroy(r)" in body
     assert not re.search(r"\bd_\w+", body), body
+    # ... and orders its streams through marks only (device_resources.h StreamMark, ReaderTable): no wait of its own, no record but the timing
+    # events of arctic_time_shade, none of the companion state the marks replaced
+    assert "hipStreamWaitEvent" not in text
+    timing = re.search(r"^int arctic_time_shade\(.*?^\}\n", text, flags=re.S | re.M)
+    assert timing, "arctic_time_shade not found"
+    assert "hipEventRecord" in timing.group(0) and "hipEventRecord" not in text.replace(timing.group(0), "")
+    for gone in ("released_valid", "shadow_released_valid", "shadow_scratch_stream", "shadow_scratch_valid", "skin_seq"):
+        assert gone not in text, gone
     # the header the owners live in stays free of the project: nothing but the HIP runtime's API and the standard library
     header = open(os.path.join(CSRC, "device_resources.h")).read()
     assert re.findall(r'#include\s+"([^"]+)"', header) == []

@@ -354,7 +354,51 @@ def test_frames_in_flight_alternating_poses(pkg, hip, in_flight):
     h.close()
 
 
-# ---- skin state ----------------------------------------------------------------------------------------------------------------------------
+def test_frames_in_flight_on_a_callers_stream(pkg, hip):
+    """a handle on a caller's stream with three frames in flight: its own stream serves as the second prepass stream.  Eight frames without a flush,
+    a new pose before every second one, the sun moved on frames 2, 3 and 6 (the other shadow map, drawn on the shadow stream behind the latest
+    k_skin); after frame 4 the handle goes back to its own stream, so the second prepass stream is another one and waits for the latest k_skin
+    again.  Every frame is the frame of a handle with one frame in flight on its own stream that is given the same calls."""
+    import torch
+    bar = Bar(pkg, 3)
+    scene = make_scene(pkg, bar)
+    poses = [bar.pose(30.0), bar.pose(-30.0, move=(0.0, 0.5, 0.0)), bar.pose(15.0), bar.pose(-45.0, move=(0.0, 0.3, 0.0))]
+    descs, sun = [], pkg.scenes.DEFAULT_SUN
+    for k in range(8):                                                                # the camera moves a little as well: no frame is a repeat
+        d = copy.deepcopy(scene[2])
+        d.camera["eye"] = (0.05 * k, 2.5, 7.0)
+        if k in (2, 3, 6):
+            sun = dict(sun, rotation=(-70.0 + 4.0 * k, 12.0 + 3.0 * k))
+        d.sun = sun
+        descs.append(d)
+    stream = torch.cuda.Stream()
+    r = handle(hip, scene, frames_in_flight=3)
+    r.set_mesh_skin(0, bar.skin, 3)
+    r.set_stream(stream.cuda_stream)
+    outs = [torch.empty((H, W, 4), dtype=torch.uint8, device="cuda") for _ in range(8)]
+    torch.cuda.synchronize()
+    for k in range(8):
+        if k % 2 == 0:
+            r.set_mesh_pose(0, poses[k // 2])
+        r.render_frame_device(descs[k], SETTINGS, outs[k].data_ptr())
+        if k == 4:
+            r.set_stream(None)
+    r.flush()
+    got = [o.cpu().numpy() for o in outs]
+    r.close()
+    h = handle(hip, scene, frames_in_flight=1)
+    h.set_mesh_skin(0, bar.skin, 3)
+    for k in range(8):
+        if k % 2 == 0:
+            h.set_mesh_pose(0, poses[k // 2])
+        np.testing.assert_array_equal(got[k], h.render_frame(descs[k], SETTINGS), err_msg=f"frame {k}")
+    h.close()
+    for k in range(7):
+        assert not np.array_equal(got[k], got[k + 1]), f"frames {k} and {k + 1} are the same"
+    assert all((g[..., :3] != 0).any() for g in got)
+
+
+# ---- skin state----------------------------------------------------------------------------------------------------------------------------
 def test_a_skin_without_a_pose_changes_nothing(pkg, hip):
     bar = Bar(pkg, 3)
     scene = make_scene(pkg, bar)
