@@ -95,6 +95,13 @@ SIGNATURES = {
     "arctic_trace_ambient_occlusion": (_i32, [_vp, _scene, _vp, _vp, _vp]),
     "arctic_trace_ambient_occlusion_device": (_i32, [_vp, _scene, _vp, _vp, _vp]),
     "arctic_ambient_occlusion_points": (_i32, [_vp, _u64, _vp, _vp, _u64, _vp, _vp, _u32, _vp]),
+    "arctic_hit_attributes": (_i32, [_vp, _scene, _vp, _u64, _vp, _vp]),
+    "arctic_interpolate_hits": (_i32, [_vp, _u64, _vp, _u64, _vp, _vp, _u32, _u64, _vp, _u64, _vp, _vp]),
+    "arctic_shade_hits": (_i32, [_vp, _scene, _vp, _vp, _u64, _u32, _vp]),
+    "arctic_shade_hits_device": (_i32, [_vp, _scene, _vp, _vp, _u64, _u32, _vp]),
+    "arctic_trace_reflections": (_i32, [_vp, _scene, C.c_float, _vp]),
+    "arctic_trace_reflections_device": (_i32, [_vp, _scene, C.c_float, _vp]),
+    "arctic_hit_shading_info": (_i32, [_vp, _vp]),
     "arctic_version": (_i32, []),
     # include/arctic_dist.h: the multi-GPU exchange steps
     "arctic_comm_unique_id": (_i32, [_vp, _vp, _u64]),

@@ -24,6 +24,7 @@
 #include "device_resources.h"
 #include "ray_query.h"
 #include "ray_ao.h"
+#include "hit_shade.h"
 
 using namespace arctic;
 
@@ -226,6 +227,7 @@ struct ArcticRenderer {
     // is allocated when that first happens); `scur` names the map of the latest frame, the one every other call sees
     DevBuf d_shadow_set[2], d_shadow_blocks_set[2], d_shadow_bounds_set[2];
     bool bounds_valid_set[2] = {false, false};   // false whenever the map has been written since its table was built
+    bool shadow_written_set[2] = {false, false}; // the map has been drawn (pass_shadow_map) or written (arctic_write_shadow_map): arctic_shade_hits asks
     int scur = 0;
     StreamMark shadow_set_released[2];   // like vis_set_released, for the shadow-map sets
     DevBuf &d_shadow() { return d_shadow_set[scur]; }
@@ -399,6 +401,19 @@ struct ArcticRenderer {
         UploadRing<1> dirs_ring;                   // its one pinned slot keeps the table last sent
         size_t n_floats = 0;                       // what d_dirs holds (0: nothing)
     } ao;
+    // Hit attributes (arctic_hit_attributes, hit_shade.hip): the prim-indexed source table -- where every triangle of the scene, in the ray queries'
+    // numbering, takes its vertices from; it depends on the topology alone, so it is made again only behind a full build of the structure
+    // (sources_of: RayScene::builds then) --, the per-object records of a call, which travel through a ring of pinned buffers like the refit's, and
+    // the host forms' buffers.  Nothing is allocated before the first call of arctic_hit_attributes, arctic_shade_hits or arctic_trace_reflections
+    struct HitScene {
+        DevBuf d_src, d_objs, d_hits, d_attrs, d_material;
+        DevBuf d_rays, d_color;                    // arctic_shade_hits' host form, and the reflection plane's rays, hits (d_hits) and result
+        uint64_t n_prims = 0, sources_of = ~0ull, tables_made = 0;
+        static constexpr int OBJ_RING = 3;
+        UploadRing<OBJ_RING> objs_ring;
+        size_t device_bytes() const { return d_src.cap + d_objs.cap + d_hits.cap + d_attrs.cap + d_material.cap + d_rays.cap + d_color.cap; }
+        size_t pinned_bytes() const { size_t b = 0; for (const auto &s : objs_ring.slot) b += s.h.cap; return b; }
+    } hit;
     PinnedBuf counts;               // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts
@@ -712,6 +727,7 @@ int pass_shadow_map(ArcticRenderer *r, const ArcticScene *sc, hipStream_t stream
     int rc = run_geometry(r, sc, true, stream);
     HIPCHECK(r, r->shadow_scratch_free.record(stream));
     if (rc != ARCTIC_OK) return rc;
+    r->shadow_written_set[r->scur] = true;
     if (r->shadow_sharded && r->comm && r->comm_world > 1) {
         // every rank has drawn ceil(S / world) rows of the map: one in-place all-gather (the send buffer is this rank's slice of the
         // receive buffer) completes it everywhere, on the pass's stream -- the shading pass needs it next
@@ -2174,6 +2190,7 @@ int arctic_write_shadow_map(ArcticRenderer *r, const float *depth) {
     HIPCHECK(r, hipStreamSynchronize(r->stream));
     HIPCHECK(r, hipMemcpy(r->d_shadow().p, depth, (size_t)r->shadow_size * r->shadow_size * 4, hipMemcpyHostToDevice));
     r->shadow_key.clear(); r->bounds_valid() = false;
+    r->shadow_written_set[r->scur] = true;
     return ARCTIC_OK;
 }
 
@@ -2730,6 +2747,185 @@ int arctic_read_ray_structure(ArcticRenderer *r, ArcticRayNode *nodes, uint64_t 
     return ARCTIC_OK;
 }
 
+// ---- hit attributes (the definition: include/arctic_hip.h; the arithmetic: hit_attributes.h; the kernel: hit_shade.hip) ---------------------------
+namespace {
+// the structure for `sc`, the source table of its topology and this call's object records, all on the device; enqueues on the handle's stream
+int ensure_hit_scene(ArcticRenderer *r, const ArcticScene *sc) {
+    int rc = ensure_ray_scene(r, sc);
+    if (rc) return rc;
+    ArcticRenderer::HitScene &H = r->hit;
+    if (H.sources_of != r->ray.builds) {   // (a refit and a re-split keep the objects' meshes, and a mesh keeps its index buffer)
+        HIPCHECK(r, hipStreamSynchronize(r->stream));   // a call in flight may still read the table in place
+        std::vector<HitSource> sources;
+        std::vector<std::vector<uint32_t>> inds(r->meshes.size());
+        for (uint64_t i = 0; i < sc->n_objects; ++i) {
+            const ArcticObject &o = sc->objects[i];
+            if (o.mesh_idx >= r->meshes.size()) continue;   // (no triangles: ensure_ray_scene)
+            const Mesh &m = r->meshes[o.mesh_idx];
+            std::vector<uint32_t> &ix = inds[o.mesh_idx];
+            if (ix.empty() && m.n_indices) {
+                ix.resize(m.n_indices);
+                HIPCHECK(r, hipMemcpy(ix.data(), m.d_indices.p, (size_t)m.n_indices * 4, hipMemcpyDeviceToHost));
+            }
+            hit_triangle_sources((uint32_t)i, m.n_vertices, ix.data(), m.n_indices / 3, sources);   // (at most 2^32 - 2 in all: ensure_ray_scene)
+        }
+        HIPCHECK(r, H.d_src.ensure(std::max<size_t>(sources.size(), 1) * sizeof(HitSource)));
+        if (!sources.empty()) HIPCHECK(r, hipMemcpy(H.d_src.p, sources.data(), sources.size() * sizeof(HitSource), hipMemcpyHostToDevice));
+        H.n_prims = sources.size();
+        H.sources_of = r->ray.builds;
+        ++H.tables_made;
+    }
+    const size_t n_obj = (size_t)sc->n_objects, bytes = std::max<size_t>(n_obj, 1) * sizeof(HitObject);
+    HitObject *h_objs = nullptr;
+    HIPCHECK(r, H.objs_ring.stage(bytes, &h_objs));
+    HIPCHECK(r, H.d_objs.ensure(bytes));
+    for (size_t i = 0; i < n_obj; ++i) {
+        const ArcticObject &o = sc->objects[i];
+        HitObject &d = h_objs[i];
+        std::memcpy(d.trs, o.trs, sizeof d.trs);
+        const bool there = o.mesh_idx < r->meshes.size();   // (an object without a mesh has no prim: its record is never read)
+        d.vertices = there ? r->meshes[o.mesh_idx].vertices_in_use() : nullptr;
+        d.n_vertices = there ? r->meshes[o.mesh_idx].n_vertices : 0u;
+        d.material = there ? (uint32_t)r->meshes[o.mesh_idx].material : HIT_NO_MATERIAL;
+    }
+    HIPCHECK(r, H.objs_ring.send(H.d_objs.p, n_obj * sizeof(HitObject), r->stream));
+    return ARCTIC_OK;
+}
+}  // namespace
+
+int arctic_hit_attributes(ArcticRenderer *r, const ArcticScene *scene, const ArcticHit *hits, uint64_t n, float *attrs, uint32_t *material) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "hit_attributes: null scene");
+    if (n && (!hits || !attrs || !material)) return r->fail(ARCTIC_E_INVALID, "hit_attributes: null hits, attrs or material");
+    if (n > 0xFFFFFFFFull) return r->fail(ARCTIC_E_CAPACITY, "hit_attributes: %llu hits in one call (2^32 - 1 at most)", (unsigned long long)n);
+    int rc;
+    if ((rc = select_device(r)) != ARCTIC_OK || (rc = ensure_hit_scene(r, scene)) != ARCTIC_OK) return rc;
+    if (n == 0) return ARCTIC_OK;
+    ArcticRenderer::HitScene &H = r->hit;
+    float lpv[16];
+    sun_proj_view(scene->sun.position, scene->sun.rotation, lpv);
+    HIPCHECK(r, H.d_hits.ensure(n * sizeof(ArcticHit)));
+    HIPCHECK(r, H.d_attrs.ensure(n * HIT_ATTRS * sizeof(float)));
+    HIPCHECK(r, H.d_material.ensure(n * sizeof(uint32_t)));
+    HIPCHECK(r, hipMemcpyAsync(H.d_hits.p, hits, n * sizeof(ArcticHit), hipMemcpyHostToDevice, r->stream));
+    HIPCHECK(r, launch_hit_attributes(H.d_hits.p, n, H.d_src.as<HitSource>(), (uint32_t)H.n_prims, H.d_objs.as<HitObject>(), lpv, H.d_attrs.as<float>(),
+                                      H.d_material.as<uint32_t>(), r->stream));
+    HIPCHECK(r, hipMemcpyAsync(attrs, H.d_attrs.p, n * HIT_ATTRS * sizeof(float), hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(r, hipMemcpyAsync(material, H.d_material.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    return ARCTIC_OK;
+}
+
+// ---- hit shading and the reflection plane (include/arctic_hip.h; the kernels: hit_shade.hip) -------------------------------------------------------
+namespace {
+// the sun's map as k_shade_hits needs it: whole, and drawn or written at least once
+int sun_map_ready(ArcticRenderer *r, const char *who) {
+    if (r->shadow_size && r->shadow_sharded)
+        return r->fail(ARCTIC_E_STATE, "%s: the sun's map is sharded (ARCTIC_OPT_SHADOW_SHARDED): a hit may lie in rows this handle never draws", who);
+    if (r->shadow_size && !r->shadow_written_set[r->scur])
+        return r->fail(ARCTIC_E_STATE, "%s: the sun's map was never drawn or written (arctic_pass_shadow_map, arctic_write_shadow_map or a frame first)", who);
+    return ARCTIC_OK;
+}
+// what both forms of arctic_shade_hits refuse before the device is touched
+int shade_checks(ArcticRenderer *r, const ArcticScene *sc, const void *rays, const void *hits, uint64_t n, uint32_t flags, const void *out, const char *who) {
+    if (!valid_scene(sc)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
+    if (flags) return r->fail(ARCTIC_E_INVALID, "%s: flags %#x (0)", who, flags);
+    if (n && (!rays || !hits || !out)) return r->fail(ARCTIC_E_INVALID, "%s: null rays, hits or output", who);
+    if (n > 0xFFFFFFFFull) return r->fail(ARCTIC_E_CAPACITY, "%s: %llu rays in one call (2^32 - 1 at most)", who, (unsigned long long)n);
+    return sun_map_ready(r, who);
+}
+// the structure, the tables and the launch: device pointers throughout
+int shade_hits(ArcticRenderer *r, const ArcticScene *sc, const void *d_rays, const void *d_hits, uint64_t n, float4 *d_out) {
+    int rc = ensure_hit_scene(r, sc);
+    if (rc || n == 0) return rc;
+    HitShadeParams p = {};
+    p.src = r->hit.d_src.as<HitSource>(); p.objs = r->hit.d_objs.as<HitObject>(); p.n_prims = (uint32_t)r->hit.n_prims;
+    p.tex = r->d_tex.as<TexDesc>(); p.srgb_lut = r->d_lut.as<float>();
+    p.shadow_map = r->shadow_size ? r->d_shadow().as<float>() : nullptr; p.shadow_size = r->shadow_size;
+    p.lights = r->d_lights.as<float4>(); p.n_lights = r->n_lights;
+    p.env = r->env_w ? r->d_env.as<float4>() : nullptr; p.env_w = r->env_w; p.env_h = r->env_h;
+    p.ambient = sc->ambient;
+    dir_from_rot(sc->sun.rotation, p.sun_dir);
+    std::memcpy(p.sun_color, sc->sun.color, sizeof p.sun_color);
+    sun_proj_view(sc->sun.position, sc->sun.rotation, p.lpv);
+    HIPCHECK(r, launch_shade_hits(d_rays, d_hits, n, p, d_out, r->stream));
+    return ARCTIC_OK;
+}
+}  // namespace
+
+int arctic_shade_hits_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *d_rays, const ArcticHit *d_hits, uint64_t n, uint32_t flags, float *d_rgba32f) {
+    if (!r) return ARCTIC_E_INVALID;
+    int rc = shade_checks(r, scene, d_rays, d_hits, n, flags, d_rgba32f, "shade_hits_device");
+    if (rc) return rc;
+    if (((uintptr_t)d_rays | (uintptr_t)d_hits | (uintptr_t)d_rgba32f) & 15u) return r->fail(ARCTIC_E_INVALID, "shade_hits_device: rays, hits and output must be 16-byte aligned");
+    if ((rc = select_device(r)) != ARCTIC_OK) return rc;
+    return shade_hits(r, scene, d_rays, d_hits, n, reinterpret_cast<float4 *>(d_rgba32f));
+}
+
+int arctic_shade_hits(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *rays, const ArcticHit *hits, uint64_t n, uint32_t flags, float *rgba32f) {
+    if (!r) return ARCTIC_E_INVALID;
+    int rc = shade_checks(r, scene, rays, hits, n, flags, rgba32f, "shade_hits");
+    if (rc) return rc;
+    if ((rc = select_device(r)) != ARCTIC_OK) return rc;
+    ArcticRenderer::HitScene &H = r->hit;
+    if (n) {
+        HIPCHECK(r, H.d_rays.ensure(n * sizeof(ArcticRay)));
+        HIPCHECK(r, H.d_hits.ensure(n * sizeof(ArcticHit)));
+        HIPCHECK(r, H.d_color.ensure(n * 16));
+        HIPCHECK(r, hipMemcpyAsync(H.d_rays.p, rays, n * sizeof(ArcticRay), hipMemcpyHostToDevice, r->stream));
+        HIPCHECK(r, hipMemcpyAsync(H.d_hits.p, hits, n * sizeof(ArcticHit), hipMemcpyHostToDevice, r->stream));
+    }
+    if ((rc = shade_hits(r, scene, H.d_rays.p, H.d_hits.p, n, H.d_color.as<float4>())) != ARCTIC_OK || n == 0) return rc;
+    HIPCHECK(r, hipMemcpyAsync(rgba32f, H.d_color.p, n * 16, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    return ARCTIC_OK;
+}
+
+namespace {
+// the checks, the G-buffer and the three launches of both reflection calls; d_out: the caller's device memory, or null = the handle's own
+int trace_reflections(ArcticRenderer *r, const ArcticScene *scene, float bias, float4 *d_out, const char *who) {
+    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
+    if (!std::isfinite(bias)) return r->fail(ARCTIC_E_INVALID, "%s: the bias is not finite", who);
+    const uint64_t n = (uint64_t)r->rows() * r->width;
+    if (!r->have_gbuffer && !r->have_vis) return r->fail(ARCTIC_E_STATE, "%s: no G-buffer (arctic_pass_gbuffer, arctic_write_gbuffer or a frame first)", who);
+    int rc = sun_map_ready(r, who);
+    if (rc || (rc = select_device(r)) != ARCTIC_OK) return rc;
+    if (!r->have_gbuffer && (rc = resolve_gbuffer(r)) != ARCTIC_OK) return rc;   // the frame was shaded from the visibility plane
+    if ((rc = ensure_ray_scene(r, scene)) != ARCTIC_OK) return rc;
+    ArcticRenderer::HitScene &H = r->hit;
+    HIPCHECK(r, H.d_rays.ensure(std::max<uint64_t>(n, 1) * sizeof(ArcticRay)));
+    HIPCHECK(r, H.d_hits.ensure(std::max<uint64_t>(n, 1) * sizeof(ArcticHit)));
+    if (!d_out) { HIPCHECK(r, H.d_color.ensure(std::max<uint64_t>(n, 1) * 16)); d_out = H.d_color.as<float4>(); }
+    const GBuffer g = r->gbuffer();
+    HIPCHECK(r, launch_reflect_rays(g.b, g.c, g.e, r->tiles_x, r->tiles_y, r->width, r->rows(), r->row0_in_tile, scene->camera.eye, bias, H.d_rays.p, r->stream));
+    HIPCHECK(r, launch_trace(H.d_rays.p, n, r->ray.d_nodes.p, r->ray.d_tris.p, (uint32_t)r->ray.n_nodes, 0, H.d_hits.p, r->stream));
+    return shade_hits(r, scene, H.d_rays.p, H.d_hits.p, n, d_out);
+}
+}  // namespace
+
+int arctic_trace_reflections(ArcticRenderer *r, const ArcticScene *scene, float bias, float *rgba32f) {
+    if (!r) return ARCTIC_E_INVALID;
+    int rc = trace_reflections(r, scene, bias, nullptr, "trace_reflections");
+    if (rc || !rgba32f) return rc;
+    HIPCHECK(r, hipMemcpyAsync(rgba32f, r->hit.d_color.p, (size_t)r->rows() * r->width * 16, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    if (int ov = check_item_overflow(r)) return ov;
+    return ARCTIC_OK;
+}
+
+int arctic_trace_reflections_device(ArcticRenderer *r, const ArcticScene *scene, float bias, float *d_rgba32f) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!d_rgba32f || ((uintptr_t)d_rgba32f & 15u)) return r->fail(ARCTIC_E_INVALID, "trace_reflections_device: the output is null or not 16-byte aligned");
+    return trace_reflections(r, scene, bias, reinterpret_cast<float4 *>(d_rgba32f), "trace_reflections_device");
+}
+
+int arctic_hit_shading_info(ArcticRenderer *r, uint64_t *out4) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!out4) return r->fail(ARCTIC_E_INVALID, "hit_shading_info: null");
+    out4[0] = r->hit.device_bytes(); out4[1] = r->hit.pinned_bytes(); out4[2] = r->hit.n_prims; out4[3] = r->hit.tables_made;
+    return ARCTIC_OK;
+}
+
 // ---- multi-GPU exchange steps (include/arctic_dist.h) ------------------------------------------------------------------------
 // the plan, as pure host functions (no device, no handle): everything below is built on them
 int arctic_exchange_plan(uint32_t width, uint32_t height, uint32_t band_rows, uint32_t world, const uint32_t *row_ranges,
@@ -2825,7 +3021,7 @@ int comm_adopt_layout(ArcticRenderer *r, const uint32_t *all, int world) {
             HIPCHECK(r, hipStreamSynchronize(r->stream));
             HIPCHECK(r, b.ensure(need));
             HIPCHECK(r, launch_fill_u32(b.as<uint32_t>(), 0x3F800000u, (need - 8) / 4, r->stream));
-            r->shadow_key.clear(); r->bounds_valid_set[s] = false;
+            r->shadow_key.clear(); r->bounds_valid_set[s] = false; r->shadow_written_set[s] = false;
         }
     }
     return ARCTIC_OK;

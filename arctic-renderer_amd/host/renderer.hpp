@@ -271,6 +271,32 @@ class Renderer {
                                                        const ArcticAmbientOcclusion &ao, const float *dirs, uint32_t flags, uint8_t *hits) {
         return arctic_ambient_occlusion_points(tris9, n_tris, points6, sets, n_points, &ao, dirs, flags, hits) == ARCTIC_OK;
     }
+    // what is AT a hit (include/arctic_hip.h: arctic_hit_attributes and the definition in front of it): the interpolated vertex output -- 18 floats in
+    // arctic_read_gbuffer's order -- and the material of every hit record; host buffers, synchronous
+    [[nodiscard]] bool hit_attributes(const ArcticScene &scene, const ArcticHit *hits, uint64_t n, float *attrs, uint32_t *material) {
+        return ok(arctic_hit_attributes(m_handle, &scene, hits, n, attrs, material));
+    }
+    // its host arbiter for one object of the scene (no handle, no GPU); hits of other objects are left as they are
+    [[nodiscard]] static bool interpolate_hits(const ArcticVertex *vertices, uint64_t n_vertices, const uint32_t *indices, uint64_t n_indices, const float *trs,
+                                               const float *light_proj_view, uint32_t material, uint64_t first_prim, const ArcticHit *hits, uint64_t n, float *attrs,
+                                               uint32_t *material_out) {
+        return arctic_interpolate_hits(vertices, n_vertices, indices, n_indices, trs, light_proj_view, material, first_prim, hits, n, attrs, material_out) == ARCTIC_OK;
+    }
+    // the forward pixel at every hit, seen from the ray's origin: rgba32f = n x {r, g, b, a}, a = 1 at a hit; a miss takes the environment map, a = 0
+    [[nodiscard]] bool shade_hits(const ArcticScene &scene, const ArcticRay *rays, const ArcticHit *hits, uint64_t n, float *rgba32f) {
+        return ok(arctic_shade_hits(m_handle, &scene, rays, hits, n, 0, rgba32f));
+    }
+    // the same between device buffers, in stream order on the handle's stream
+    [[nodiscard]] bool shade_hits_device(const ArcticScene &scene, const ArcticRay *d_rays, const ArcticHit *d_hits, uint64_t n, float *d_rgba32f) {
+        return ok(arctic_shade_hits_device(m_handle, &scene, d_rays, d_hits, n, 0, d_rgba32f));
+    }
+    // one mirror ray per pixel of the resident G-buffer, its closest hit shaded: rows x width x {r, g, b, a}; rgba32f = nullptr leaves it on the device
+    [[nodiscard]] bool trace_reflections(const ArcticScene &scene, float bias, float *rgba32f) { return ok(arctic_trace_reflections(m_handle, &scene, bias, rgba32f)); }
+    [[nodiscard]] bool trace_reflections_device(const ArcticScene &scene, float bias, float *d_rgba32f) {
+        return ok(arctic_trace_reflections_device(m_handle, &scene, bias, d_rgba32f));
+    }
+    // {device bytes, pinned host bytes, prims in the source table, times the table was made}: all 0 until the first of the calls above
+    [[nodiscard]] bool hit_shading_info(uint64_t out4[4]) { return ok(arctic_hit_shading_info(m_handle, out4)); }
 
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }

@@ -239,6 +239,57 @@ class Renderer:
         ao, d = _ao_arguments(dirs, n_rays, pattern, radius, bias, filter, normal_cos, plane_dist)
         self._check(self.L.arctic_trace_ambient_occlusion_device(self.h, C.byref(s), _ptr(ao), _ptr(d), C.c_void_p(d_out_ptr) if d_out_ptr else None))
 
+    # ---- what is at a hit (include/arctic_hip.h: arctic_hit_attributes and the text in front of it) ---------------------------------------
+    def hit_attributes(self, desc, hits):
+        """HIT_DTYPE records (trace_rays' answer, or hand-made) -> ((n, 18) float32 attributes in read_gbuffer's order, (n,) uint32 materials):
+        the interpolated vertex output at each hit; material 0xFFFFFFFF and zeros for a miss or a prim the scene does not have."""
+        s = self._scene(desc)
+        h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).ravel()
+        attrs, material = np.empty((len(h), 18), np.float32), np.empty(len(h), np.uint32)
+        p = (lambda a: _ptr(a) if len(h) else None)
+        self._check(self.L.arctic_hit_attributes(self.h, C.byref(s), p(h), len(h), p(attrs), p(material)))
+        return attrs, material
+
+    def shade_hits(self, desc, rays, hits):
+        """RAY_DTYPE records and their HIT_DTYPE records -> (n, 4) float32: the forward pixel at each hit seen from the ray's origin, a = 1; for
+        a miss the environment map along the ray (black without one), a = 0."""
+        s = self._scene(desc)
+        ry = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
+        h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).ravel()
+        if len(h) != len(ry):
+            raise ArcticError(-1, "shade_hits: one hit per ray")
+        out = np.empty((len(ry), 4), np.float32)
+        p = (lambda a: _ptr(a) if len(ry) else None)
+        self._check(self.L.arctic_shade_hits(self.h, C.byref(s), p(ry), p(h), len(ry), 0, p(out)))
+        return out
+
+    def shade_hits_device(self, desc, d_rays_ptr, d_hits_ptr, n, d_rgba_ptr):
+        """the same between device buffers (int pointers; 32 bytes per ray, 16 per hit, 16 per result, 16-byte aligned); asynchronous on the
+        handle's stream."""
+        s = self._scene(desc)
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_shade_hits_device(self.h, C.byref(s), vp(d_rays_ptr), vp(d_hits_ptr), int(n), 0, vp(d_rgba_ptr)))
+
+    def trace_reflections(self, desc, bias, read=True):
+        """one mirror ray per pixel of the resident G-buffer, from world + bias * m, its closest hit shaded: (rows, width, 4) float32, a = 1 where
+        the reflection shows geometry.  read=False leaves the plane on the device and returns None (timing)."""
+        s = self._scene(desc)
+        out = np.empty((self.rows, self.width, 4), np.float32) if read else None
+        self._check(self.L.arctic_trace_reflections(self.h, C.byref(s), float(bias), _ptr(out)))
+        return out
+
+    def trace_reflections_device(self, desc, bias, d_rgba_ptr):
+        """the same into device memory the caller owns (an int pointer; rows * width * 16 bytes, 16-byte aligned); asynchronous on the handle's stream."""
+        s = self._scene(desc)
+        self._check(self.L.arctic_trace_reflections_device(self.h, C.byref(s), float(bias), C.c_void_p(d_rgba_ptr) if d_rgba_ptr else None))
+
+    def hit_shading_info(self):
+        """(device bytes, pinned host bytes, prims in the source table, times the table was made) held for hit_attributes, shade_hits and
+        trace_reflections: all 0 until the first of them"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_hit_shading_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
     def ray_scene_info(self):
         """(triangles stored, nodes, builds so far, depth) of the cached acceleration structure"""
         out = np.zeros(4, np.uint64)
@@ -600,6 +651,23 @@ def trace_triangles(triangles, rays, any_hit=False, brute=False):
     if rc < 0:
         raise ArcticError(rc, "trace_triangles")
     return hits
+
+
+def interpolate_hits(vertices, indices, trs, light_proj_view, material, first_prim, hits, attrs, material_out):
+    """arctic_interpolate_hits: the hit attributes of include/arctic_hip.h on the host, for ONE object -- its mesh (VERTEX_DTYPE records, uint32
+    indices), its trs and the sun's matrix (16 floats each, [col][row]), the mesh's material, the prim of its first triangle.  Fills attrs
+    ((n, 18) float32) and material_out ((n,) uint32) IN PLACE for the hits whose prim is one of the object's; the others are left as they are."""
+    v = np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE).ravel()
+    ix = np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+    m, l = np.ascontiguousarray(trs, dtype=np.float32).reshape(16), np.ascontiguousarray(light_proj_view, dtype=np.float32).reshape(16)
+    h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).ravel()
+    assert attrs.dtype == np.float32 and attrs.flags.c_contiguous and attrs.shape == (len(h), 18)
+    assert material_out.dtype == np.uint32 and material_out.flags.c_contiguous and material_out.shape == (len(h),)
+    rc = binding.lib().arctic_interpolate_hits(_ptr(v) if len(v) else None, len(v), _ptr(ix) if len(ix) else None, len(ix), _ptr(m), _ptr(l), int(material),
+                                               int(first_prim), _ptr(h) if len(h) else None, len(h), _ptr(attrs) if len(h) else None,
+                                               _ptr(material_out) if len(h) else None)
+    if rc < 0:
+        raise ArcticError(rc, "interpolate_hits")
 
 
 def _ao_arguments(dirs, n_rays, pattern, radius, bias, filter, normal_cos, plane_dist):

@@ -1001,6 +1001,91 @@ int arctic_trace_ambient_occlusion_device(ArcticRenderer *r, const ArcticScene *
 int arctic_ambient_occlusion_points(const float *tris9, uint64_t n_tris, const float *points6, const uint32_t *sets, uint64_t n_points,
                                     const ArcticAmbientOcclusion *ao, const float *dirs, uint32_t flags, uint8_t *hits);
 
+/* ---- what is AT a hit: attributes, shading, and a reflection plane (no counterpart in the reference: its roadmap's "Raytracing") ---------------------
+ * A ray query answers {t, u, v, prim}.  The three layers below turn that into the interpolated vertex output at the hit, into the colour the
+ * forward pass would give that point seen along the ray, and into a plane of mirror reflections of the resident G-buffer.  Each is usable alone.
+ * Nothing in the passes uses them: shading, shadow maps and every existing bit are unchanged, and a handle that never makes these calls
+ * allocates nothing for them.
+ *
+ * 1. HIT ATTRIBUTES, DEFINED bit for bit: numpy in float32 reproduces them (tests/hit_reference.py), and so does arctic_interpolate_hits on the host.
+ * Everything is fp32; each operation rounds once, in the written order, without contraction; division and square root are IEEE.
+ * prim -> source.  `prim` is the running triangle index of the ray-query definition above: the objects in ArcticScene::objects order, each
+ *   object's triangles in index-buffer order, an object whose mesh does not exist having none.  The result is material = 0xFFFFFFFF and eighteen
+ *   zeros for prim == 0xFFFFFFFF (a miss), for a prim at or above the scene's count, and for the triangle with an index out of range, which is
+ *   skipped but numbered.  Otherwise material is the mesh's material, as arctic_read_gbuffer reports it.
+ * Per vertex, exactly what the vertex kernel writes, from the mesh's vertices IN USE (posed, else morphed, else its own) and the object's trs NOW:
+ *     world[i] = ((M[i]*x + M[4+i]*y) + M[8+i]*z) + M[12+i]*1.0f         i = 0..3, M = trs (i = 3 is the w the next product takes: 1 for an affine trs)
+ *     t, b, n  = the stored tangent, bitangent, normal, each times  inv = 1.0f / sqrt((v0*v0 + v1*v1) + v2*v2)  -- NOT transformed by trs
+ *     light_space[i] = ((L[i]*world0 + L[4+i]*world1) + L[8+i]*world2) + L[12+i]*world3,   L = arctic_frame_constants' light_proj_view for `scene`
+ *     uv = the stored texture coordinates
+ * Interpolation.  w0 = (1.0f - u) - v.  Each of the 18 attributes -- arctic_read_gbuffer's order: uv2, t3, b3, n3, world3, light_space4 -- is
+ *     (w0*a0 + u*a1) + v*a2      a0, a1, a2 = the attribute at the triangle's first, second, third index
+ *   u and v are used as given (not clamped); t is not used.  A NaN u or v propagates: the attributes it reaches are NaNs, of a sign and payload
+ *   that are not defined -- compare those as NaNs, everything else by bytes.
+ * The handle keeps a table, indexed by prim, of where every triangle takes its vertices from.  It depends on the topology alone, is made by the
+ * first of these calls behind the ray structure and made again only behind a full build of it: the calls keep working, without a rebuild, after a
+ * refit and after arctic_ray_scene_resplit. */
+
+/* attrs[18 k ..] and material[k] for hits[k].  Host buffers, synchronous; builds or refreshes the ray structure like arctic_trace_rays.
+ * ARCTIC_E_INVALID: a null scene, a null pointer with n > 0.  ARCTIC_E_CAPACITY: n above 2^32 - 1, or a scene too large (above). */
+int arctic_hit_attributes(ArcticRenderer *r, const ArcticScene *scene, const ArcticHit *hits, uint64_t n, float *attrs, uint32_t *material);
+
+/* The host arbiter (no handle, no GPU) for ONE object: its mesh (n_indices / 3 triangles), its trs (16 floats), the sun's matrix (16 floats) and
+ * the mesh's material.  The object's triangles are prims first_prim .. first_prim + n_indices / 3 - 1; a hit whose prim lies there gets its
+ * attributes and material (eighteen zeros and 0xFFFFFFFF for the triangle with an index out of range), every other hit's entries are LEFT AS THEY
+ * ARE -- so a caller fills the outputs with zeros and 0xFFFFFFFF and chains the scene's objects.  ARCTIC_E_INVALID: a null pointer with a non-zero
+ * count, null trs or matrix.  ARCTIC_E_CAPACITY: more than 2^32 - 1 vertices, prims beyond 2^32 - 2. */
+int arctic_interpolate_hits(const ArcticVertex *vertices, uint64_t n_vertices, const uint32_t *indices, uint64_t n_indices, const float *trs,
+                            const float *light_proj_view, uint32_t material, uint64_t first_prim, const ArcticHit *hits, uint64_t n, float *attrs,
+                            uint32_t *material_out);
+
+/* 2. HIT SHADING (hit_shade.hip: k_shade_hits).  rgba32f[4 k ..] for ray k and its hit:
+ * A hit (a prim that resolves, above):  rgb = ps_main (forward.hlsl:208-235) on the attributes of layer 1 with eye := rays[k].origin, so
+ *   wo = normalize(origin - world);  a = 1.  The material's textures are sampled at LEVEL 0 with the default sampler -- full-fp32 bilinear
+ *   weights, WRAP, sRGB decoded per texel before filtering -- whatever ARCTIC_OPT_SAMPLER says.  calculate_shadow takes its 25 taps on the
+ *   handle's resident sun map (shadow_size == 0: shadow 0).  The point lights are those last given to arctic_update_lights, in caller order;
+ *   ambient and sun come from `scene`.  A back face is shaded with the stored frame, without a flip.  The hit's t is not used.
+ * A miss or a prim that does not resolve:  with an environment map (arctic_create_hdri), its level 0 along d / |d| under the skybox's mapping
+ *   (uv = (atan2(d.z, d.x) * 0.1591f + 0.5, -(asin(d.y) * 0.3183f + 0.5)), bilinear, WRAP), a = 0.  Without a map, or for a direction that is
+ *   zero or has a component that is not finite: {0, 0, 0, 0}.
+ * Held to the shading pass's standing bar against float64 (tests/test_gpu_hit_shading.py), not defined bit for bit.
+ * OUT OF SCOPE at hits: spot lights, shadow-casting point lights, image-based ambient (ARCTIC_OPT_ENV_LIGHTING), material extras
+ *   (arctic_set_material_extras) and mip chains (ARCTIC_OPT_TEXTURE_MIPS) do not take part; a handle that has them still answers ARCTIC_OK with
+ *   the base model above.
+ * Refusals, before the device is touched; a refused call writes nothing.  ARCTIC_E_INVALID: a null scene, flags != 0, a null pointer with n > 0.
+ *   ARCTIC_E_CAPACITY: n above 2^32 - 1 (or a scene too large).  ARCTIC_E_STATE: the handle has a sun map (shadow_size != 0) that was never
+ *   drawn or written, or that is sharded (ARCTIC_OPT_SHADOW_SHARDED). */
+int arctic_shade_hits(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *rays, const ArcticHit *hits, uint64_t n, uint32_t flags, float *rgba32f);
+
+/* The same between DEVICE buffers the caller owns (16-byte aligned), stream-ordered on the handle's stream like arctic_trace_rays_device: call
+ * arctic_flush() before another stream reads d_rgba32f.  ARCTIC_E_INVALID also for a pointer that is not 16-byte aligned. */
+int arctic_shade_hits_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *d_rays, const ArcticHit *d_hits, uint64_t n, uint32_t flags,
+                             float *d_rgba32f);
+
+/* 3. THE REFLECTION PLANE.  One mirror ray per pixel of the handle's RESIDENT G-buffer (arctic_pass_gbuffer, arctic_write_gbuffer, or the latest
+ * frame), its closest hit shaded by layer 2: three launches over buffers the handle owns (k_reflect_rays, the ray queries' walk, k_shade_hits).
+ * Per pixel, with world = attributes 11..13, n = attributes 8..10 and eye = scene->camera.eye; fp32, one rounding per operation, no contraction:
+ *   m = n / len as in step 1 of the ambient occlusion.  A pixel without geometry or NOT COVERED by that step has no ray.
+ *   i[j] = world[j] - eye[j];   k = dot(m, i)  (the ray queries' dot);   k >= 0 (the surface faces away): no ray.
+ *   d[j] = i[j] - (2.0f*k)*m[j];   o[j] = world[j] + bias*m[j]  (the product rounds, then the sum);   t_min = 0;   t_max = +inf
+ *   The result is layer 2's for that ray and its closest hit.  A pixel without a ray is {0, 0, 0, 0}: it stands in the ray buffer as the
+ *   all-zero record, whose direction is zero.  So a = 1 where the reflection shows geometry, 0 elsewhere.
+ * The normal is the INTERPOLATED VERTEX NORMAL, as in the ambient occlusion, not the normal-mapped one.
+ * rgba32f = rows * width * 4 floats, row-major over the handle's rows like arctic_trace_sun_visibility; a sharded handle answers for its own
+ * rows.  rgba32f == NULL leaves the plane on the device and does not synchronise (timing).
+ * ARCTIC_E_INVALID: a null scene, a bias that is not finite.  ARCTIC_E_STATE: no G-buffer; the sun map's states of layer 2. */
+int arctic_trace_reflections(ArcticRenderer *r, const ArcticScene *scene, float bias, float *rgba32f);
+
+/* The same into DEVICE memory the caller owns (rows * width * 16 bytes, 16-byte aligned), stream-ordered on the handle's stream.
+ * ARCTIC_E_INVALID also for a null or misaligned d_rgba32f. */
+int arctic_trace_reflections_device(ArcticRenderer *r, const ArcticScene *scene, float bias, float *d_rgba32f);
+
+/* What the three layers hold on this handle: out4 = {bytes of device memory (the source table, the object records, the host forms' buffers and
+ * the plane's rays, hits and colours, at their capacities), bytes of pinned host memory (the object records' ring), prims in the source table,
+ * times the source table was made}.  {0, 0, 0, 0} until the first arctic_hit_attributes, arctic_shade_hits(_device) or
+ * arctic_trace_reflections(_device) that passes its checks.  Touches no device. */
+int arctic_hit_shading_info(ArcticRenderer *r, uint64_t *out4);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row
