@@ -1,6 +1,6 @@
 // device_resources.h -- owners of what the HIP runtime hands out: device memory, pinned memory, events, streams, the ring of pinned
 // slots that host tables travel through, and the marks that order one stream behind another.  Host only, nothing of the project: every type is move-only and its destructor releases what it
-// holds, so a handle (renderer.cpp) frees nothing by hand -- its members go in reverse order of declaration, a local owner on a failure path
+// holds, so a handle (renderer_state.h) frees nothing by hand -- its members go in reverse order of declaration, a local owner on a failure path
 // goes with its scope.  The owners make exactly the runtime calls the code they replace made; none of them synchronises behind the caller's
 // back except Stream, whose release waits for the stream before it destroys it.
 #pragma once

@@ -1,4 +1,7 @@
 // renderer.cpp -- the C-ABI of include/arctic_hip.h: resource ownership + frame graph on one HIP stream.
+// The units of the C-ABI: renderer.cpp -- create, destroy and resize, streams, resources, the passes and frames, options, the debug read-backs;
+// ray_calls.cpp -- queries, refit and re-split, sun visibility, ambient occlusion, hit attributes and shading, reflections; exchange_calls.cpp --
+// the multi-GPU exchange (include/arctic_dist.h).  The handle they share: renderer_state.h.
 //
 // Plays the role of Arctic::Renderer::Renderer (reference src/renderer/renderer.{hpp,cpp}) for
 // the hot path only: create_material/create_mesh/update_lights upload resources
@@ -7,9 +10,7 @@
 // (RHI, descriptor heaps, barriers, swapchain) is replaced by plain device allocations and
 // stream order.  No CPU fallback: every entry point needs a HIP device.
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
-#include <dlfcn.h>
 
 #include <cstdlib>
 #include <cstring>
@@ -22,146 +23,15 @@
 #include "../../include/arctic_dist.h"
 #include "common.h"
 #include "device_resources.h"
-#include "ray_query.h"
-#include "ray_ao.h"
-#include "hit_shade.h"
+#include "renderer_state.h"
 
 using namespace arctic;
 
-namespace {
-
-// Optional profiler ranges named like the reference's Tracy zones ("Shadow Map Pass", "Forward Pass": shadow_map_pass.cpp:116,
-// forward_pass.cpp:164): roctx is loaded at run time only when ARCTIC_OPT_MARKERS is set, so the library has no link-time
-// dependency on it.  Host-side ranges around the enqueue of each pass (rocprofv3 --marker-trace shows them).
-struct Markers {
-    int (*push)(const char *) = nullptr;
-    int (*pop)() = nullptr;
-    bool tried = false, on = false;
-    void enable(bool want) {
-        on = want;
-        if (want && !tried) {
-            tried = true;
-            void *h = dlopen("libroctx64.so", RTLD_NOW | RTLD_LOCAL);
-            if (!h) h = dlopen("/opt/rocm/lib/libroctx64.so", RTLD_NOW | RTLD_LOCAL);
-            if (h) {
-                push = reinterpret_cast<int (*)(const char *)>(dlsym(h, "roctxRangePushA"));
-                pop = reinterpret_cast<int (*)()>(dlsym(h, "roctxRangePop"));
-            }
-        }
-    }
-    bool available() const { return push && pop; }
-};
+namespace arctic {
 Markers g_markers;
-struct Range {
-    bool live;
-    explicit Range(const char *name) : live(g_markers.on && g_markers.available()) { if (live) g_markers.push(name); }
-    ~Range() { if (live) g_markers.pop(); }
-};
+}  // namespace arctic
 
-
-// RCCL, loaded at run time like roctx (arctic_dist.h): the few entry points the exchange steps use.  Types are declared here
-// the way rccl.h declares them (opaque communicator, 128-byte id by value, int enums) so the library needs no RCCL headers.
-struct Rccl {
-    struct UniqueId { char internal[ARCTIC_COMM_ID_BYTES]; };
-    typedef void *Comm;
-    static constexpr int Uint8 = 1, Uint32 = 3, Float32 = 7;   // ncclDataType_t (rccl.h:459-466)
-    int (*GetUniqueId)(UniqueId *) = nullptr;
-    int (*CommInitRank)(Comm *, int, UniqueId, int) = nullptr;
-    int (*CommDestroy)(Comm) = nullptr;
-    int (*AllGather)(const void *, void *, size_t, int, Comm, hipStream_t) = nullptr;
-    int (*Send)(const void *, size_t, int, int, Comm, hipStream_t) = nullptr;
-    int (*Recv)(void *, size_t, int, int, Comm, hipStream_t) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    const char *(*GetErrorString)(int) = nullptr;
-    bool tried = false;
-    bool load() {
-        if (!tried) {
-            tried = true;
-            // an RCCL the process has loaded already (a host that also runs torch.distributed: PyTorch-ROCm brings its own librccl.so.1)
-            // is the one to use -- ONE library instance with two communicators, not two RCCL builds side by side on the same devices
-            // ARCTIC_RCCL_LIB (honoured only when set): the library that provides the nccl* entry points instead -- the test suite's
-            // loopback communicator (tests/cpp/loopback_rccl.cpp: ranks = threads of one process on one GPU, where RCCL refuses two
-            // ranks per device), so that the R > 1 branch of the exchange runs where no second GPU exists.  No fallback when it is set.
-            const char *override_lib = std::getenv("ARCTIC_RCCL_LIB");
-            const bool overridden = override_lib && *override_lib;
-            void *h = overridden ? dlopen(override_lib, RTLD_NOW | RTLD_LOCAL) : dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);
-            if (overridden && !h) return false;
-            if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);
-            if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-            if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-            if (!h) h = dlopen("/opt/rocm/lib/librccl.so", RTLD_NOW | RTLD_LOCAL);
-            if (h) {
-                GetUniqueId = reinterpret_cast<decltype(GetUniqueId)>(dlsym(h, "ncclGetUniqueId"));
-                CommInitRank = reinterpret_cast<decltype(CommInitRank)>(dlsym(h, "ncclCommInitRank"));
-                CommDestroy = reinterpret_cast<decltype(CommDestroy)>(dlsym(h, "ncclCommDestroy"));
-                AllGather = reinterpret_cast<decltype(AllGather)>(dlsym(h, "ncclAllGather"));
-                Send = reinterpret_cast<decltype(Send)>(dlsym(h, "ncclSend"));
-                Recv = reinterpret_cast<decltype(Recv)>(dlsym(h, "ncclRecv"));
-                GroupStart = reinterpret_cast<decltype(GroupStart)>(dlsym(h, "ncclGroupStart"));
-                GroupEnd = reinterpret_cast<decltype(GroupEnd)>(dlsym(h, "ncclGroupEnd"));
-                GetErrorString = reinterpret_cast<decltype(GetErrorString)>(dlsym(h, "ncclGetErrorString"));
-            }
-        }
-        return GetUniqueId && CommInitRank && CommDestroy && AllGather && Send && Recv && GroupStart && GroupEnd;
-    }
-    const char *why(int rc) const { return GetErrorString ? GetErrorString(rc) : "RCCL error"; }
-};
-Rccl g_rccl;
-
-// per-pass host->device tables (frame constants, object records, block tables): written into pinned memory and sent with
-// ONE asynchronous copy; the pinned buffer is reused only after the copy that last read it has completed (event), so
-// uploading never waits for the kernels of the previous pass or frame.
-struct PassTables {
-    UploadRing<1> staging;      // pinned staging
-    DevBuf d;                   // device arena
-    std::vector<char> last;     // what the device arena holds: an unchanged object list is not uploaded again
-    GeomParams gp;              // this pass's frame constants (kernel argument, by value)
-    // device views into the arena (valid after upload)
-    const ObjectRec *objs = nullptr;
-    const uint32_t *vblock_obj = nullptr, *vblock_first = nullptr, *tblock_obj = nullptr, *tblock_first = nullptr;
-    const float *vblock_bounds = nullptr, *tblock_bounds = nullptr;   // 6 floats per block (cluster_bounds)
-};
-
-struct Mesh {
-    DevBuf d_vertices, d_indices;
-    uint32_t n_vertices = 0, n_indices = 0;
-    uint64_t material = 0;
-    std::vector<float> tbounds, vbounds;   // cluster_bounds: 6 floats per block of SETUP_THREADS triangles / of 256 vertices
-    // Skeletal skinning (arctic_set_mesh_skin / arctic_set_mesh_pose).  d_skin: one ArcticSkinVertex per vertex; while `posed`, d_posed -- a second
-    // vertex buffer written by k_skin from d_vertices, d_skin and the pose's matrices in d_joints -- is what ObjectRec::vertices points at, and the
-    // mesh's cluster boxes (which bound the bind pose) are replaced by infinite ones.  The matrices travel through a ring of pinned buffers, so
-    // that a pose call neither reads the caller's memory after it returns nor waits for the copy of the pose before it.
-    DevBuf d_skin;
-    uint32_t n_joints = 0;
-    DevBuf d_posed, d_joints;
-    bool posed = false;
-    static constexpr int POSE_RING = 3;
-    UploadRing<POSE_RING> joints_ring;
-    // Morph targets (arctic_set_mesh_morph_targets / arctic_set_mesh_morph_weights).  d_deltas: n_targets arrays of n_vertices records of 12 floats;
-    // while `morphed` (some weight is not zero), d_morphed -- written by k_morph from d_vertices, d_deltas and the compacted {target, weight} list
-    // in d_active -- is what k_skin reads if the mesh is posed and what ObjectRec::vertices points at if it is not.  The list travels through a
-    // ring of pinned buffers like the joint matrices.  morph_weights: the weights in force (all zero after a targets call)
-    DevBuf d_deltas, d_morphed;
-    uint32_t n_targets = 0;
-    DevBuf d_active;
-    bool morphed = false;
-    std::vector<float> morph_weights;
-    UploadRing<POSE_RING> active_ring;
-    uint64_t shape_seq = 0;   // bumped by every successful skin / pose / morph call: part of the shadow caches' keys (shadow_inputs, cube_inputs)
-    const float *skin_input() const { return (morphed ? d_morphed : d_vertices).as<float>(); }          // morph first, then skin
-    const float *vertices_in_use() const { return posed ? d_posed.as<float>() : skin_input(); }
-    bool deformed() const { return posed || morphed; }                                                 // the cluster boxes do not describe it
-    void release_morph() {    // (the caller has drained the streams that may read these)
-        d_deltas.release(); d_morphed.release(); d_active.release(); active_ring.release();
-        n_targets = 0; morphed = false; morph_weights.clear();
-    }
-    void release_pose() {     // (the caller has drained the streams that may read these)
-        d_posed.release(); d_joints.release(); joints_ring.release();
-        posed = false;
-    }
-    void release_skin() { release_pose(); d_skin.release(); n_joints = 0; }
-};
+namespace {
 
 // Object-space boxes for geometry.hip's box_outside, made once per mesh on the host.  tbounds[c] = {min xyz, max xyz} of the positions
 // the triangles [c * SETUP_THREADS, (c + 1) * SETUP_THREADS) use -- one workgroup of k_setup --, vbounds[b] = the union of the boxes
@@ -201,249 +71,7 @@ void cluster_bounds(const ArcticVertex *v, uint32_t n_vertices, const uint32_t *
 
 }  // namespace
 
-struct ArcticRenderer {
-    int device = 0;
-    hipStream_t stream = nullptr;       // the stream every pass is enqueued on (own_stream unless the caller set one); not owned
-    uint32_t width = 0, height = 0, shadow_size = 0, max_lights = 0, row_begin = 0, row_end = 0;
-    uint32_t tiles_x = 0, tiles_y = 0, tile_y0 = 0, row0_in_tile = 0;
-    uint32_t band_rows = 0, shard_index = 0, shard_count = 1, owned_rows = 0;   // interleaved shard (band_rows > 0)
-    std::vector<Mesh> meshes;
-    std::vector<TexDesc> tex;        // 3 per material (device pointers)
-    std::vector<DevBuf> tex_allocs;
-    // arctic_set_material_extras: one entry per material.  While a material is not neutral (n_extras != 0) the device's texture table carries a
-    // MaterialExtra record per material behind the descriptors (common.h) and every shading call takes the k_pbrlit* kernels (has_extras).
-    struct Extras {
-        float p[12] = {1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
-        DevBuf d_emissive, d_occlusion, d_fast;   // plain RGBA8 images, or the one {e.rgb, o} image of the fast path
-        uint32_t ew = 0, eh = 0, ow = 0, oh = 0;
-        bool neutral = true;
-    };
-    std::vector<Extras> extras;
-    uint32_t n_extras = 0;
-    bool has_extras() const { return n_extras != 0; }
-    DevBuf d_tex, d_lut, d_lights, d_light_pairs, d_env;
-    // the shadow map, and the min/max of it per 4x4 texel block / per 4x4-aligned 8x8 block (k_shadow_bounds).  Two sets: a frame in
-    // flight that redraws the map draws into the other one while the previous frame's shading still reads this one (the second set
-    // is allocated when that first happens); `scur` names the map of the latest frame, the one every other call sees
-    DevBuf d_shadow_set[2], d_shadow_blocks_set[2], d_shadow_bounds_set[2];
-    bool bounds_valid_set[2] = {false, false};   // false whenever the map has been written since its table was built
-    bool shadow_written_set[2] = {false, false}; // the map has been drawn (pass_shadow_map) or written (arctic_write_shadow_map): arctic_shade_hits asks
-    int scur = 0;
-    StreamMark shadow_set_released[2];   // like vis_set_released, for the shadow-map sets
-    DevBuf &d_shadow() { return d_shadow_set[scur]; }
-    DevBuf &d_shadow_blocks() { return d_shadow_blocks_set[scur]; }
-    DevBuf &d_shadow_bounds() { return d_shadow_bounds_set[scur]; }
-    bool &bounds_valid() { return bounds_valid_set[scur]; }
-    uint32_t env_w = 0, env_h = 0;
-    // ARCTIC_OPT_ENV_LIGHTING: the image-based ambient's tables (env_light.hip), built when the map and the option are both there
-    int env_lighting = 0;
-    bool env_built = false;          // the tables belong to the map in d_env
-    DevBuf d_env_levels, d_env_lut, d_env_mips, d_env_sh_rows, d_env_tables;
-    EnvTables env_host = {};         // the device struct's pointers and sizes (its sh[] is written by the device)
-    bool env_active() const { return env_lighting == 1 && env_built; }
-    uint32_t n_lights = 0;
-    // arctic_update_spot_lights: SPOT_F4 float4 per light (common.h SpotDev); a non-empty list sends every tile to k_spotlit*
-    DevBuf d_spots;
-    uint32_t n_spots = 0;
-    // arctic_update_point_shadow_lights: ONE allocation, n_cubes records (CUBE_F4 float4 each, common.h CubeDev) and behind them n_cubes x 6
-    // faces of cube_size^2 floats; a non-empty list sends every tile to k_cubelit*.  One set of faces: they are drawn on the main stream,
-    // behind the previous frame's shading that reads them (pass_point_shadows)
-    DevBuf d_cubes;
-    uint32_t n_cubes = 0, cube_size = 1024;         // cube_size: ARCTIC_OPT_POINT_SHADOW_SIZE
-    std::vector<ArcticPointShadowLight> cube_lights;   // the list as given: the faces' matrices and the cache key
-    std::vector<uint8_t> cube_key;                  // what the faces were drawn from (render_frame redraws them when it changes; empty: redraw)
-    PinnedBuf cube_counts;                          // pinned, mapped: CUBE_COUNT_WORDS per face drawn (run_geometry's DepthTarget)
-    uint32_t *h_cube_counts() const { return cube_counts.as<uint32_t>(); }
-    uint32_t *dh_cube_counts() const { return cube_counts.dev<uint32_t>(); }
-    uint32_t cube_count_faces = 0;
-    // frame targets
-    DevBuf d_vis_set[3], d_p0, d_p1, d_p2, d_p3, d_p4, d_rgba8, d_ldr, d_hdr, d_counter;
-    bool have_gbuffer = false, have_output = false, have_vis = false;   // have_vis: d_vis holds the visibility of the current G-buffer
-    // ARCTIC_OPT_ANTIALIAS: with 1 a handle that owns the whole frame shades into d_rgba8 and the edge filter (antialias.hip) writes the
-    // destination -- the caller's buffer or d_aa; output_filtered: the handle's latest RGBA8 output is the one in d_aa
-    int antialias = 0;
-    DevBuf d_aa;
-    bool output_filtered = false;
-    bool aa_active() const { return antialias == 1 && rows() == height; }
-    const void *rgba8_output() const { return output_filtered ? d_aa.p : d_rgba8.p; }
-    int light_path = 0;             // ARCTIC_OPT_LIGHT_PATH: 0 automatic, 1 scalar light loop, 2 packed pairs
-    // ARCTIC_OPT_LIGHT_PAIR_RUNS: 1 = the pair table of the packed loop is laid out in runs that skip a colour channel (light_pair_table);
-    // 0 = caller order, one general run.  h_lights: the lights as given, so that the option can rebuild the table; pair_runs: ShadeParams::pair_runs
-    int light_pair_runs = 1;
-    std::vector<ArcticPointLight> h_lights;
-    uint32_t pair_runs = 0;
-    bool visbuffer = true;          // arctic_render_frame shades straight from the visibility plane (no G-buffer)
-    // per-frame geometry scratch
-    PassTables tables[4];   // [0], [2], [3] forward pass (one per frame in flight), [1] shadow pass
-    // transformed vertices, records, work items: one set per pass ([0] forward, [1] shadow), so that the two prepasses of a frame
-    // can run side by side (arctic_render_frame) and the forward pass's records outlive a shadow pass (k_resolve, k_material_vis)
-    struct GeoSet {
-        DevBuf d_xverts, d_recs, d_rrecs, d_clip_list, d_rec_of, d_items;
-        DevBuf d_left;                     // ... and the work items the bins did not take (same capacity as d_items), for the atomic rasteriser
-        DevBuf d_bin_count, d_bin_slots;   // block ownership (common.h: BinTables): a counter and BIN_SLOTS record indices per 16x16 block of the target
-        uint32_t item_cap = 0;      // entries of d_items (work-item table of the rasteriser)
-        uint32_t bins_x = 0, bins_y = 0;   // blocks of the latest owned pass (arctic_read_bin_counts)
-        uint32_t n_tblocks = 0, n_vblocks = 0; bool cull_counted = false;   // the latest pass's workgroups (arctic_read_cull_counts)
-    } geo[4];   // indexed like tables
-    DevBuf d_geo_counters, d_stage;
-    // shadow_stream (below): arctic_render_frame draws the shadow map there while the main stream runs the visibility prepass
-    // (the marks -- device_resources.h StreamMark -- keep the rules: never recorded or recorded on the waiting stream itself, nothing to wait for)
-    StreamMark shadow_fork, shadow_drawn;
-    // Skinning: k_skin runs on the main stream, which has joined every earlier prepass (prepass_done, shadow_drawn) -- so it follows every k_vertex that
-    // still reads the buffer it overwrites.  `deformed` is recorded behind it; the shadow and prepass streams wait for it before their next pass,
-    // once per recording (*_seen: the generation each of those streams has waited for)
-    StreamMark deformed;
-    uint64_t skin_seen_shadow = 0, skin_seen_prepass[2] = {0, 0};
-    // The shadow pass has ONE set of scratch (geo[1], tables[1], its four counters) whichever stream it runs on -- the main stream
-    // (arctic_pass_shadow_map, a sharded map, debug bit 7) or shadow_stream (whole frames).  shadow_scratch_free marks the end of the
-    // last shadow pass; a pass on another stream waits for it first, so two never share the scratch.
-    StreamMark shadow_scratch_free;
-    // Frames in flight (arctic_render_frame, ARCTIC_OPT_FRAMES_IN_FLIGHT = 2): the visibility prepass of frame k + 1 runs on
-    // prepass_stream while the main stream still shades frame k, so there are two sets of what the prepass writes and the
-    // shading reads -- visibility plane, vertex / record / item tables, object tables -- and `cur` names the set of the latest frame
-    // (the one the pass-level calls and arctic_read_gbuffer see).  vis_set_released[s]: everything enqueued on the main stream up to
-    // the moment the handle moved on from set s; the next prepass into s waits for it.
-    // Up to three sets (the reference keeps 3 frames in flight, rhi.hpp:25) and two prepass streams used alternately: with three
-    // sets the prepasses of two consecutive frames are independent of each other as well, and a small frame -- whose prepass is a
-    // chain of launches longer than its shading -- is bound by neither chain alone.
-    int frames_in_flight = 2, frames_in_flight_opt = 0 /* ARCTIC_OPT_FRAMES_IN_FLIGHT; 0: by the target's size (alloc_targets) */, cur = 0, prepass_turn = 0;
-    StreamMark prepass_done[2], vis_set_released[3];   // (prepass_stream[2]: below)
-    DevBuf &d_vis() { return d_vis_set[cur]; }
-    int fwd() const { return cur ? cur + 1 : 0; }      // index of the current forward set in tables / geo
-    bool recs_worst_case = false;   // record table at 7 per source triangle (after an overflow of the 2-per-triangle table)
-    uint32_t item_cap_floor = 1u << 22;   // its smallest size (ARCTIC_OPT_ITEM_TABLE_FLOOR; tests shrink it to reach the overflow path)
-    uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t edge_stats[4] = {0, 0, 0, 0};   // stats[12..15]: fast tiles the shadow table left undecided, their undecided pixels, tiles / pixels that ran the 25 compares
-    uint64_t light_stats[2] = {0, 0};   // stats[8], [9]: (tile, light) pairs with n.wi <= 0 in every lit lane; tiles with a lit pixel
-    int keep_float = 0, count_evals = 0, culling = 1, debug = 0, hdr16 = 0, tile_trace = 0;
-    uint32_t tiles_per_wave = 0;     // ARCTIC_OPT_TILES_PER_WAVE (0 = the library's default)
-    // The shading pass's dispatch order (round 4): k_resolve leaves a cost class per tile next to the G-buffer (can a pixel of the tile be
-    // lit at all?), k_tile_order turns the classes into the order in which arctic_pass_shade hands out its strips of 4 tiles.  A hint:
-    // a stale or missing order changes the pass's time, never its image.
-    DevBuf d_tile_class, d_order_lists, d_tile_order;
-    bool have_order = false;         // d_tile_order belongs to the G-buffer in place
-    uint32_t order_group = 0, order_slots = 0;   // ... built for this many tiles per wave, this many slots (common.h order_slot)
-    int texture_tiling = -1;         // ARCTIC_OPT_TEXTURE_TILING: materials created from now on: -1 = 4 x 4-texel tiles for images of 2048 texels a side and more, 0 = never, 1 = always
-    // ARCTIC_OPT_TEXTURE_MIPS: materials created under 1 get a chain (chains[m]: the host copy of the material's level descriptors, empty = one level);
-    // at shading time 1 selects k_miplit* once a material has a chain.  d_lod: the level-of-detail plane next to the G-buffer (tile-major, allocated only
-    // under the option); lod_valid: it belongs to the G-buffer in place (k_resolve_lod wrote it, or arctic_write_gbuffer / arctic_write_lod did)
-    int texture_mips = 0;
-    std::vector<std::vector<TexDesc>> chains;
-    uint32_t n_chains = 0;
-    DevBuf d_lod;
-    bool lod_valid = false;
-    bool mips_active() const { return texture_mips == 1 && n_chains != 0; }
-    int sampler = 0;                 // ARCTIC_OPT_SAMPLER: bit 0 material footprints, bit 2 PCF taps with coordinates snapped to 1/256 texel (D3D-style 8-bit filter weights)
-    int tile_order = 0;              // ARCTIC_OPT_TILE_ORDER: 0 (default since round 5) = the geometric, XCD-aware order of round 3; 1 = the cost-class order of round 4.
-                                     // Measured (profiles/r5_a_*): the order gains <= 2 us of the pass, its one-workgroup kernel costs the G-buffer pass 112 us, and handing strips
-                                     // out by cost instead of by XCD row costs the pass 83 MB of fabric reads per launch (L2 hits 2.33 M -> 1.73 M: neighbouring strips no longer meet in one L2)
-    uint32_t order_tail = 60;        // ARCTIC_OPT_ORDER_TAIL: the last part of the order (per mille) that holds cheap strips only
-    DevBuf d_tile_trace;             // ARCTIC_OPT_TILE_TRACE: 4 x u64 per tile of the latest shading pass
-    int cluster_cull = 3;            // ARCTIC_OPT_CLUSTER_CULL: bit 0 k_setup skips clusters, bit 1 k_vertex skips vertex blocks, that cannot touch the pass's pixels
-    int small_triangles = 1;         // ARCTIC_OPT_SMALL_TRIANGLES: 1 = the shadow pass's k_setup draws triangles with a small bounding box itself (geometry.hip: draw_small)
-    int raster_owner = -1;           // ARCTIC_OPT_RASTER_OWNER: bit 0 forward pass, bit 1 shadow pass: the blocks of the target are written once by owner waves
-                                     // (k_bin + k_raster_owned) instead of per-pixel atomics; -1: the library's choice
-    uint32_t raster_blocks[2] = {2048, 2048};  // persistent grid of k_raster: [0] forward pass, [1] shadow pass
-    // render_frame re-renders the shadow map only when its inputs changed (sun, objects, meshes): the reference redraws it
-    // every frame (renderer.cpp:300-337), but a depth map of unchanged geometry from an unchanged light is the same map
-    std::vector<uint8_t> shadow_key; bool shadow_cache = true;
-    uint32_t cu_count = 256;
-    // multi-GPU exchange (arctic_dist.h): an RCCL communicator owned by the handle, a communication stream ordered against the
-    // main stream with events, the shard layout of every rank (all-gathered once at arctic_comm_init)
-    Rccl::Comm comm = nullptr;
-    int comm_rank = 0, comm_world = 1;
-    hipStream_t comm_stream = nullptr;   // the handle's own stream, borrowed, or comm_stream_owned (below)
-    bool comm_stream_borrowed = false;   // the communication stream is the handle's own stream, idle because the caller brought its stream (one stream -- one hardware queue -- fewer)
-    // ONE role per stream: own_stream is the main stream, or -- the caller brought its own -- EITHER the exchange's stream (borrowed by
-    // arctic_comm_init) OR the second prepass stream of three frames in flight, never both: a gather queued in front of a prepass would
-    // stall it behind the other ranks, and synchronising a prepass stream must never wait for an unmatched collective.
-    bool own_stream_is_prepass() const { return stream != own_stream && !comm_stream_borrowed; }
-    StreamMark shaded;                // the main stream, where a gather starts
-    ReaderTable<4> shard_readers;     // gathers that still read a shard buffer
-    std::vector<uint32_t> peer_rows, peer_ranges;    // rows of every rank's shard; [begin, end) of every rank (row-range shards)
-    std::vector<uint64_t> peer_offset;               // byte offset of every rank's shard in the root's staging buffer (arctic_exchange_plan)
-    uint64_t staging_bytes = 0;
-    DevBuf d_staging, d_layout;                       // root: all shards back to back; ranges (2 u32 per rank) + byte offsets (u64 per rank)
-    uint32_t layout_world = 0; bool layout_from_comm = false;
-    bool shadow_sharded = false;                      // ARCTIC_OPT_SHADOW_SHARDED
-    // Ray queries (arctic_trace_rays, arctic_trace_sun_visibility): the acceleration structure over the scene's world-space triangles, built on the
-    // host (bvh.cpp) from the vertices in use, and cached: ray_key is what it was built from -- ray_inputs(), shadow_inputs' rule -- so a changed
-    // object list, mesh count, pose or weights rebuilds it on the next query.  ray_tris: triangles stored (those that can be hit)
-    struct RayScene {
-        std::vector<uint8_t> key;
-        bool built = false;
-        uint64_t n_tris = 0, n_nodes = 0, builds = 0, depth = 0;
-        DevBuf d_nodes, d_tris, d_rays, d_hits, d_mask;
-        // ARCTIC_OPT_RAY_REFIT (ray_refit.hip; the definition: include/arctic_hip.h, "a refitted structure").  A full build under the option also
-        // uploads the slots' sources and the refit's schedule (checked on the host first); while `refittable`, a change of the key that keeps the
-        // objects' meshes (built_meshes) is followed on the device: a per-object table through a ring of pinned buffers, then one launch per stage,
-        // all in stream order -- no synchronisation, nothing read back.  Nothing below is allocated while the option is 0
-        int refit_opt = 0;
-        bool refittable = false;
-        uint64_t refits = 0, refit_launches = 0;
-        std::vector<uint64_t> built_meshes;        // every object's mesh_idx at the build
-        std::vector<uint32_t> stage_first;         // RefitSchedule::stage_first of the build
-        DevBuf d_src, d_head, d_inputs, d_interior, d_objs;
-        static constexpr int OBJ_RING = 3;
-        UploadRing<OBJ_RING> objs_ring;
-        // arctic_ray_scene_resplit (ray_resplit.hip; the definition: include/arctic_hip.h, "a re-split structure"): the sorts' workspace, allocated
-        // by the first re-split of a structure of this size and kept; nothing while the call is never made
-        DevBuf d_resplit;
-        size_t resplit_bytes = 0;
-        uint64_t resplit_slots = ~0ull;            // the slot count resplit_bytes was worked out for
-        uint64_t resplits = 0, resplit_launches = 0, resplit_fell_back = 0;
-    } ray;
-    // Ambient occlusion (arctic_trace_ambient_occlusion, ray_ao.hip): the direction table on the device -- at most 12 KiB, sent from a pinned copy
-    // that is also what the device holds, so an unchanged table is not sent again and the pinned copy is rewritten only after the copy that last
-    // read it has completed --, the hits plane and the result, one byte per pixel of the handle's rows each.  Nothing is allocated before the first call
-    struct AmbientOcclusion {
-        DevBuf d_dirs, d_hits, d_out;
-        UploadRing<1> dirs_ring;                   // its one pinned slot keeps the table last sent
-        size_t n_floats = 0;                       // what d_dirs holds (0: nothing)
-    } ao;
-    // Hit attributes (arctic_hit_attributes, hit_shade.hip): the prim-indexed source table -- where every triangle of the scene, in the ray queries'
-    // numbering, takes its vertices from; it depends on the topology alone, so it is made again only behind a full build of the structure
-    // (sources_of: RayScene::builds then) --, the per-object records of a call, which travel through a ring of pinned buffers like the refit's, and
-    // the host forms' buffers.  Nothing is allocated before the first call of arctic_hit_attributes, arctic_shade_hits or arctic_trace_reflections
-    struct HitScene {
-        DevBuf d_src, d_objs, d_hits, d_attrs, d_material;
-        DevBuf d_rays, d_color;                    // arctic_shade_hits' host form, and the reflection plane's rays, hits (d_hits) and result
-        uint64_t n_prims = 0, sources_of = ~0ull, tables_made = 0;
-        static constexpr int OBJ_RING = 3;
-        UploadRing<OBJ_RING> objs_ring;
-        size_t device_bytes() const { return d_src.cap + d_objs.cap + d_hits.cap + d_attrs.cap + d_material.cap + d_rays.cap + d_color.cap; }
-        size_t pinned_bytes() const { size_t b = 0; for (const auto &s : objs_ring.slot) b += s.h.cap; return b; }
-    } hit;
-    PinnedBuf counts;               // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
-    uint32_t *h_counts() const { return counts.as<uint32_t>(); }
-    uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts
-    // The streams the handle created, declared LAST: members are destroyed in reverse order, so every stream is waited for and gone before any
-    // buffer, pinned slot or event above -- which its work may still touch -- is released.  (arctic_create makes them in the order its comment
-    // gives; comm_stream_owned: the exchange's stream when it is not the borrowed own_stream.)
-    Stream own_stream, shadow_stream, prepass_stream[2], comm_stream_owned;
-    std::string err;
-
-    int fail(int code, const char *fmt, ...) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        err = buf;
-        return code;
-    }
-    uint32_t rows() const { return band_rows ? owned_rows : row_end - row_begin; }
-    size_t n_tiles() const { return (size_t)tiles_x * tiles_y; }
-    GBuffer gbuffer() const { return GBuffer{d_p0.as<float4>(), d_p4.as<float>(), d_p1.as<float4>(), d_p2.as<float4>(), d_p3.as<float4>()}; }
-};
-
-#define HIPCHECK(r, expr)                                                                            \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) return (r)->fail(ARCTIC_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-namespace {
+namespace arctic {   // (renderer_state.h: other units call these)
 
 // bytes of a shadow-map buffer: S rows, or -- with a communicator -- world * ceil(S / world) rows, the room the in-place all-gather
 // of a sharded map writes (ARCTIC_OPT_SHADOW_SHARDED); + 8: the map is cleared in 8-byte words.  ONE definition for every place
@@ -458,6 +86,10 @@ int select_device(ArcticRenderer *r) {
     HIPCHECK(r, hipSetDevice(r->device));
     return ARCTIC_OK;
 }
+
+}  // namespace arctic
+
+namespace {
 
 int alloc_targets(ArcticRenderer *r) {
     r->shadow_key.clear();   // buffers may move: render_frame redraws the shadow map
@@ -776,6 +408,8 @@ int pass_visibility(ArcticRenderer *r, const ArcticScene *sc, hipStream_t stream
     return ARCTIC_OK;
 }
 
+}  // namespace
+namespace arctic {   // (renderer_state.h: other units call it)
 // visibility -> the 76 B/pixel G-buffer.  Valid while the records of the forward pass are still in place.
 int resolve_gbuffer(ArcticRenderer *r) {
     Range zone("Forward Pass: G-buffer");
@@ -819,6 +453,8 @@ int resolve_gbuffer(ArcticRenderer *r) {
     r->have_gbuffer = true;
     return ARCTIC_OK;
 }
+}  // namespace arctic
+namespace {
 
 int pass_gbuffer(ArcticRenderer *r, const ArcticScene *sc) {
     int rc = pass_visibility(r, sc, r->stream);
@@ -994,6 +630,8 @@ int pass_shade(ArcticRenderer *r, const ArcticScene *sc, const ArcticSettings *s
     return ARCTIC_OK;
 }
 
+}  // namespace
+namespace arctic {   // (renderer_state.h: other units call it)
 // the tail of every cache key (shadow_inputs, cube_inputs, ray_inputs): per object its transform, its mesh and -- the mesh exists -- the mesh's
 // shape: a skin, pose or morph call changes what the object casts (arctic_set_mesh_pose)
 void put_objects(const ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_t> &k) {
@@ -1003,6 +641,8 @@ void put_objects(const ArcticRenderer *r, const ArcticScene *sc, std::vector<uin
         if (sc->objects[i].mesh_idx < r->meshes.size()) put(&r->meshes[sc->objects[i].mesh_idx].shape_seq, sizeof(uint64_t));
     }
 }
+}  // namespace arctic
+namespace {
 
 // everything the shadow map is a function of, as bytes (compared exactly, not hashed)
 std::vector<uint8_t> shadow_inputs(const ArcticRenderer *r, const ArcticScene *sc) {
@@ -1035,6 +675,8 @@ int wait_skin(ArcticRenderer *r, hipStream_t stream, uint64_t &seen) {
     return ARCTIC_OK;
 }
 
+}  // namespace
+namespace arctic {   // (renderer_state.h: other units call it)
 // after a stream synchronisation: did a rasteriser pass run out of work-item slots?  (k_setup flags it; the table is re-sized
 // from the counts of that very pass, so rendering the frame again succeeds)
 int check_item_overflow(ArcticRenderer *r) {
@@ -1053,6 +695,8 @@ int check_item_overflow(ArcticRenderer *r) {
     return r->fail(ARCTIC_E_CAPACITY, "a rasteriser table overflowed (%u work items needed, %u slots; or more than 2 records per source triangle): the last frame "
                    "is incomplete; the tables grow on the next pass -- render the frame again", need, std::max(r->geo[0].item_cap, r->geo[1].item_cap));
 }
+}  // namespace arctic
+namespace {
 
 // The device's texture table: the 3 * n_materials descriptors and, while a material has extras, one MaterialExtra per material behind them
 // (common.h).  Uploaded whenever either part changes; the caller has drained the stream.
@@ -1079,9 +723,10 @@ int upload_tex_table(ArcticRenderer *r) {
     return ARCTIC_OK;
 }
 
-bool valid_scene(const ArcticScene *sc) { return sc && (sc->n_objects == 0 || sc->objects); }
-
 }  // namespace
+namespace arctic {   // (renderer_state.h: other units call it)
+bool valid_scene(const ArcticScene *sc) { return sc && (sc->n_objects == 0 || sc->objects); }
+}  // namespace arctic
 
 // =================================================================================================
 extern "C" {
@@ -2434,727 +2079,6 @@ int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
         break;
     default: return r->fail(ARCTIC_E_INVALID, "set_option: unknown option %u", option);
     }
-    return ARCTIC_OK;
-}
-
-// ---- ray queries (the definition: include/arctic_hip.h; the arithmetic: ray_query.h; the builder: bvh.cpp; the kernels: trace.hip) ----------------
-namespace {
-// everything the structure is a function of, as bytes (shadow_inputs' rule: the objects, the mesh count, the shape of every mesh in use)
-void ray_inputs(const ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_t> &k) {
-    k.clear();
-    auto put = [&](const void *p, size_t n) { const uint8_t *b = static_cast<const uint8_t *>(p); k.insert(k.end(), b, b + n); };
-    const uint64_t head[2] = {(uint64_t)r->meshes.size(), sc->n_objects};
-    put(head, sizeof head);
-    put_objects(r, sc, k);
-}
-
-// may the cached structure follow `sc` by a refit?  Host state only (include/arctic_hip.h: "Eligibility")
-bool ray_refit_eligible(const ArcticRenderer *r, const ArcticScene *sc) {
-    const ArcticRenderer::RayScene &R = r->ray;
-    if (!R.built || !R.refittable || sc->n_objects != R.built_meshes.size()) return false;
-    for (uint64_t i = 0; i < sc->n_objects; ++i)
-        if (sc->objects[i].mesh_idx != R.built_meshes[i] || sc->objects[i].mesh_idx >= r->meshes.size()) return false;
-    return true;
-}
-
-// the refit: the per-object table (trs and vertices in use NOW) through the ring, then the stages.  Everything is enqueued on the handle's stream,
-// behind the k_morph / k_skin that wrote the vertices and behind the queries that still walk the structure in place; nothing waits for the device
-// (the ring's event is that of the copy OBJ_RING refits ago).  resplit: arctic_ray_scene_resplit -- between the table and the stages the slots are put
-// in the order a fresh build of this pose would give them (ray_resplit.hip), so the stages write that build's structure
-int refit_ray_scene(ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_t> &key, bool resplit = false) {
-    ArcticRenderer::RayScene &R = r->ray;
-    const size_t n_obj = (size_t)sc->n_objects, bytes = std::max<size_t>(n_obj, 1) * sizeof(RefitObject);
-    RefitObject *h_objs = nullptr;
-    HIPCHECK(r, R.objs_ring.stage(bytes, &h_objs));   // (a slot grows to fit)
-    for (size_t i = 0; i < n_obj; ++i) {
-        const ArcticObject &o = sc->objects[i];
-        const Mesh &m = r->meshes[o.mesh_idx];   // (ray_refit_eligible: it exists)
-        RefitObject &d = h_objs[i];
-        for (int c = 0; c < 4; ++c) for (int k = 0; k < 3; ++k) d.m[3 * c + k] = o.trs[4 * c + k];
-        d.vertices = m.vertices_in_use(); d.n_vertices = m.n_vertices; d.pad = 0;
-    }
-    HIPCHECK(r, R.objs_ring.send(R.d_objs.p, n_obj * sizeof(RefitObject), r->stream));   // (no object: nothing is sent, the ring moves on)
-    const RefitTablesDev T = {R.d_head.as<uint32_t>(), R.d_inputs.as<uint32_t>(), R.d_interior.as<RefitInterior>(), R.d_src.as<RefitSource>()};
-    uint32_t launches = 0, split_launches = 0;
-    if (resplit) {
-        const hipError_t es = launch_ray_resplit(R.d_resplit.p, R.resplit_bytes, R.d_tris.p, (uint32_t)R.n_tris, R.d_src.as<RefitSource>(), R.d_objs.as<RefitObject>(), (uint32_t)n_obj,
-                                                 r->stream, &split_launches);
-        if (es != hipSuccess) { R.built = false; HIPCHECK(r, es); }   // (the order may be half written: the structure is dropped, the next query builds)
-    }
-    const hipError_t e = launch_ray_refit(T, R.stage_first.data(), (uint32_t)R.stage_first.size() - 1, R.d_nodes.p, (uint32_t)R.n_nodes, R.d_tris.p, (uint32_t)R.n_tris,
-                                          R.d_objs.as<RefitObject>(), (uint32_t)n_obj, r->stream, &launches);
-    if (e != hipSuccess) { R.built = false; HIPCHECK(r, e); }   // (some stages may have run: the structure is dropped, the next query builds)
-    R.key.swap(key);
-    if (resplit) { ++R.resplits; R.resplit_launches = (uint64_t)split_launches + launches; }
-    else { ++R.refits; R.refit_launches = launches; }
-    return ARCTIC_OK;
-}
-
-// the structure for `sc`, resident on the device: built, validated and uploaded when its inputs changed (synchronous: it reads the meshes back) -- or,
-// under ARCTIC_OPT_RAY_REFIT, refitted in stream order when only the geometry moved.
-int ensure_ray_scene(ArcticRenderer *r, const ArcticScene *sc) {
-    std::vector<uint8_t> key;
-    ray_inputs(r, sc, key);
-    if (r->ray.built && key == r->ray.key) return ARCTIC_OK;
-    if (ray_refit_eligible(r, sc)) return refit_ray_scene(r, sc, key);
-    const bool with_refit = r->ray.refit_opt == 1;
-    std::vector<RefitSource> sources;
-    // the vertices in use are written by k_morph / k_skin on the main stream; the structure in place may still be read by a query on it
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    std::vector<float> tris9;
-    std::vector<uint32_t> prims;
-    std::vector<std::vector<float>> verts(r->meshes.size());
-    std::vector<std::vector<uint32_t>> inds(r->meshes.size());
-    uint64_t prim = 0;
-    for (uint64_t i = 0; i < sc->n_objects; ++i) {
-        const ArcticObject &o = sc->objects[i];
-        if (o.mesh_idx >= r->meshes.size()) continue;   // (skipped by the passes as well: upload_pass_tables)
-        const Mesh &m = r->meshes[o.mesh_idx];
-        if (prim + m.n_indices / 3 > 0xFFFFFFFEull) return r->fail(ARCTIC_E_CAPACITY, "ray queries: more than 2^32 - 2 triangles in the scene");
-        if (verts[o.mesh_idx].empty()) {
-            verts[o.mesh_idx].resize((size_t)m.n_vertices * 14); inds[o.mesh_idx].resize(m.n_indices);
-            HIPCHECK(r, hipMemcpy(verts[o.mesh_idx].data(), m.vertices_in_use(), (size_t)m.n_vertices * sizeof(ArcticVertex), hipMemcpyDeviceToHost));
-            HIPCHECK(r, hipMemcpy(inds[o.mesh_idx].data(), m.d_indices.p, (size_t)m.n_indices * 4, hipMemcpyDeviceToHost));
-        }
-        prim = ray_world_triangles(o.trs, verts[o.mesh_idx].data(), m.n_vertices, inds[o.mesh_idx].data(), m.n_indices / 3, prim, tris9, prims);
-        if (with_refit) ray_triangle_sources((uint32_t)i, m.n_vertices, inds[o.mesh_idx].data(), m.n_indices / 3, sources);
-    }
-    Bvh b;
-    if (!bvh_build(tris9.data(), prims.size(), prims.data(), b))
-        return r->fail(ARCTIC_E_CAPACITY, "ray queries: %llu triangles to store, the structure holds 2^29 - 1", (unsigned long long)prims.size());
-    if (!bvh_validate(b)) return r->fail(ARCTIC_E_INVALID, "internal: the ray structure failed its validation (%zu nodes, %zu triangles); nothing was uploaded", b.nodes.size(), b.tris.size());
-    // Refittable: built under the option, no in-range triangle left out for being non-finite (it would have no slot to come back to), every
-    // object's mesh there, and an object index that fits the source records.  The tables: where every stored slot's vertices come from -- copied
-    // from the index buffers read above, found by the slot's prim (ascending in `prims`) -- and the schedule; both checked before anything is uploaded
-    bool refittable = with_refit && b.tris.size() == prims.size() && sources.size() == prims.size() && sc->n_objects <= 0xFFFFFFFFull;
-    for (uint64_t i = 0; refittable && i < sc->n_objects; ++i) refittable = sc->objects[i].mesh_idx < r->meshes.size();
-    std::vector<RefitSource> slot_src;
-    RefitSchedule sched;
-    if (refittable) {
-        slot_src.resize(b.tris.size());
-        for (size_t k = 0; k < b.tris.size(); ++k) {
-            const auto it = std::lower_bound(prims.begin(), prims.end(), b.tris[k].prim);
-            if (it == prims.end() || *it != b.tris[k].prim) return r->fail(ARCTIC_E_INVALID, "internal: a stored triangle's prim %u is not one of the scene's", b.tris[k].prim);
-            const RefitSource &s = slot_src[k] = sources[(size_t)(it - prims.begin())];
-            const uint32_t nv = s.object < sc->n_objects ? r->meshes[sc->objects[s.object].mesh_idx].n_vertices : 0u;
-            if (!(s.i0 < nv && s.i1 < nv && s.i2 < nv)) return r->fail(ARCTIC_E_INVALID, "internal: the refit's source record %zu is out of range; nothing was uploaded", k);
-        }
-        refit_schedule(b, sched);
-        if (!refit_schedule_validate(b, sched)) return r->fail(ARCTIC_E_INVALID, "internal: the refit's schedule failed its validation (%zu nodes, %zu tasks); nothing was uploaded", b.nodes.size(), sched.head.size());
-    }
-    r->ray.built = false; r->ray.refittable = false;
-    if (refittable) {
-        const auto upload = [&](DevBuf &d, const void *p, size_t bytes) -> hipError_t {
-            hipError_t e = d.ensure(std::max<size_t>(bytes, 16));
-            if (e == hipSuccess && bytes) e = hipMemcpy(d.p, p, bytes, hipMemcpyHostToDevice);
-            return e;
-        };
-        HIPCHECK(r, upload(r->ray.d_src, slot_src.data(), slot_src.size() * sizeof(RefitSource)));
-        HIPCHECK(r, upload(r->ray.d_head, sched.head.data(), sched.head.size() * sizeof(uint32_t)));
-        HIPCHECK(r, upload(r->ray.d_inputs, sched.inputs.data(), sched.inputs.size() * sizeof(uint32_t)));
-        HIPCHECK(r, upload(r->ray.d_interior, sched.interior.data(), sched.interior.size() * sizeof(RefitInterior)));
-        HIPCHECK(r, r->ray.d_objs.ensure(std::max<size_t>((size_t)sc->n_objects, 1) * sizeof(RefitObject)));
-        r->ray.stage_first = sched.stage_first;
-        r->ray.built_meshes.resize((size_t)sc->n_objects);
-        for (uint64_t i = 0; i < sc->n_objects; ++i) r->ray.built_meshes[(size_t)i] = sc->objects[i].mesh_idx;
-    }
-    HIPCHECK(r, r->ray.d_nodes.ensure(std::max<size_t>(sizeof(RayNode), b.nodes.size() * sizeof(RayNode))));
-    HIPCHECK(r, r->ray.d_tris.ensure(std::max<size_t>(sizeof(RayTri), b.tris.size() * sizeof(RayTri))));
-    if (!b.nodes.empty()) HIPCHECK(r, hipMemcpy(r->ray.d_nodes.p, b.nodes.data(), b.nodes.size() * sizeof(RayNode), hipMemcpyHostToDevice));
-    if (!b.tris.empty()) HIPCHECK(r, hipMemcpy(r->ray.d_tris.p, b.tris.data(), b.tris.size() * sizeof(RayTri), hipMemcpyHostToDevice));
-    r->ray.key.swap(key);
-    r->ray.n_tris = b.tris.size(); r->ray.n_nodes = b.nodes.size(); r->ray.depth = b.depth;
-    ++r->ray.builds;
-    r->ray.built = true; r->ray.refittable = refittable;
-    return ARCTIC_OK;
-}
-
-int trace_checks(ArcticRenderer *r, const ArcticScene *sc, const void *rays, uint64_t n, uint32_t flags, const void *hits, const char *who) {
-    if (!valid_scene(sc)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
-    if (flags & ~ARCTIC_TRACE_ANY) return r->fail(ARCTIC_E_INVALID, "%s: flags %#x (ARCTIC_TRACE_ANY or 0; ARCTIC_TRACE_BRUTE belongs to arctic_trace_triangles)", who, flags);
-    if (n && (!rays || !hits)) return r->fail(ARCTIC_E_INVALID, "%s: null rays or hits", who);
-    if (n > 0xFFFFFFFFull) return r->fail(ARCTIC_E_CAPACITY, "%s: %llu rays in one call (2^32 - 1 at most)", who, (unsigned long long)n);
-    return ARCTIC_OK;
-}
-}  // namespace
-
-int arctic_trace_rays_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *d_rays, uint64_t n, uint32_t flags, ArcticHit *d_hits) {
-    if (!r) return ARCTIC_E_INVALID;
-    int rc = trace_checks(r, scene, d_rays, n, flags, d_hits, "trace_rays_device");
-    if (rc) return rc;
-    if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u) return r->fail(ARCTIC_E_INVALID, "trace_rays_device: rays and hits must be 16-byte aligned");
-    if ((rc = select_device(r)) != ARCTIC_OK || (rc = ensure_ray_scene(r, scene)) != ARCTIC_OK) return rc;
-    HIPCHECK(r, launch_trace(d_rays, n, r->ray.d_nodes.p, r->ray.d_tris.p, (uint32_t)r->ray.n_nodes, (flags & ARCTIC_TRACE_ANY) != 0, d_hits, r->stream));
-    return ARCTIC_OK;
-}
-
-int arctic_trace_rays(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *rays, uint64_t n, uint32_t flags, ArcticHit *hits) {
-    if (!r) return ARCTIC_E_INVALID;
-    int rc = trace_checks(r, scene, rays, n, flags, hits, "trace_rays");
-    if (rc) return rc;
-    if ((rc = select_device(r)) != ARCTIC_OK || (rc = ensure_ray_scene(r, scene)) != ARCTIC_OK) return rc;
-    if (n == 0) return ARCTIC_OK;
-    HIPCHECK(r, r->ray.d_rays.ensure(n * sizeof(ArcticRay)));
-    HIPCHECK(r, r->ray.d_hits.ensure(n * sizeof(ArcticHit)));
-    HIPCHECK(r, hipMemcpyAsync(r->ray.d_rays.p, rays, n * sizeof(ArcticRay), hipMemcpyHostToDevice, r->stream));
-    HIPCHECK(r, launch_trace(r->ray.d_rays.p, n, r->ray.d_nodes.p, r->ray.d_tris.p, (uint32_t)r->ray.n_nodes, (flags & ARCTIC_TRACE_ANY) != 0, r->ray.d_hits.p, r->stream));
-    HIPCHECK(r, hipMemcpyAsync(hits, r->ray.d_hits.p, n * sizeof(ArcticHit), hipMemcpyDeviceToHost, r->stream));
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    return ARCTIC_OK;
-}
-
-int arctic_trace_sun_visibility(ArcticRenderer *r, const ArcticScene *scene, float bias, uint8_t *mask) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "trace_sun_visibility: null scene");
-    if (!std::isfinite(bias)) return r->fail(ARCTIC_E_INVALID, "trace_sun_visibility: the bias is not finite");
-    int rc = select_device(r);
-    if (rc) return rc;
-    if (!r->have_gbuffer) {
-        if (!r->have_vis) return r->fail(ARCTIC_E_STATE, "trace_sun_visibility: no G-buffer (arctic_pass_gbuffer, arctic_write_gbuffer or a frame first)");
-        if ((rc = resolve_gbuffer(r)) != ARCTIC_OK) return rc;   // the frame was shaded from the visibility plane
-    }
-    if ((rc = ensure_ray_scene(r, scene)) != ARCTIC_OK) return rc;
-    float sun[3];
-    dir_from_rot(scene->sun.rotation, sun);
-    const float minus_sun[3] = {-sun[0], -sun[1], -sun[2]};
-    const size_t bytes = (size_t)r->rows() * r->width;
-    HIPCHECK(r, r->ray.d_mask.ensure(std::max<size_t>(bytes, 16)));
-    HIPCHECK(r, launch_trace_sun(r->gbuffer(), r->tiles_x, r->tiles_y, r->width, r->rows(), r->row0_in_tile, bias, minus_sun, r->ray.d_nodes.p, r->ray.d_tris.p,
-                                 (uint32_t)r->ray.n_nodes, r->ray.d_mask.as<uint8_t>(), r->stream));
-    if (mask) {
-        HIPCHECK(r, hipMemcpyAsync(mask, r->ray.d_mask.p, bytes, hipMemcpyDeviceToHost, r->stream));
-        HIPCHECK(r, hipStreamSynchronize(r->stream));
-        if (int ov = check_item_overflow(r)) return ov;
-    }
-    return ARCTIC_OK;
-}
-
-namespace {
-// the checks, the G-buffer, the structure, the table and the launches of both ambient-occlusion calls; d_out: the caller's device memory, or null = the handle's own
-int trace_ambient_occlusion(ArcticRenderer *r, const ArcticScene *scene, const ArcticAmbientOcclusion *ao, const float *dirs, uint8_t *d_out, const char *who) {
-    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
-    AoDesc d;
-    if (ao) std::memcpy(&d, ao, sizeof d);
-    if (const char *why = ao_refusal(ao ? &d : nullptr, dirs)) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
-    int rc = select_device(r);
-    if (rc) return rc;
-    if (!r->have_gbuffer && !r->have_vis) return r->fail(ARCTIC_E_STATE, "%s: no G-buffer (arctic_pass_gbuffer, arctic_write_gbuffer or a frame first)", who);
-    if (d.filter && r->rows() != r->height)
-        return r->fail(ARCTIC_E_STATE, "%s: the filter needs the whole frame, this handle owns %u of %u rows (its neighbours' rows are on other shards)", who, r->rows(), r->height);
-    if (!r->have_gbuffer && (rc = resolve_gbuffer(r)) != ARCTIC_OK) return rc;   // the frame was shaded from the visibility plane
-    if ((rc = ensure_ray_scene(r, scene)) != ARCTIC_OK) return rc;
-    ArcticRenderer::AmbientOcclusion &A = r->ao;
-    const size_t n_floats = (size_t)d.pattern * d.pattern * d.n_rays * 3, bytes = (size_t)r->rows() * r->width;
-    const size_t table_bytes = 16 * AO_MAX_RAYS * 3 * sizeof(float);   // the largest table: the slot and d_dirs are made once
-    if (A.n_floats != n_floats || std::memcmp(A.dirs_ring.slot[0].h.p, dirs, n_floats * sizeof(float)) != 0) {   // (n_floats != 0: an empty A holds no table)
-        float *h_dirs = nullptr;
-        HIPCHECK(r, A.dirs_ring.stage(table_bytes, &h_dirs));
-        HIPCHECK(r, A.d_dirs.ensure(table_bytes));
-        A.n_floats = 0;
-        std::memcpy(h_dirs, dirs, n_floats * sizeof(float));
-        HIPCHECK(r, A.dirs_ring.send(A.d_dirs.p, n_floats * sizeof(float), r->stream));
-        A.n_floats = n_floats;
-    }
-    if (d.filter) HIPCHECK(r, A.d_hits.ensure(std::max<size_t>(bytes, 16)));
-    if (!d_out) { HIPCHECK(r, A.d_out.ensure(std::max<size_t>(bytes, 16))); d_out = A.d_out.as<uint8_t>(); }
-    const GBuffer g = r->gbuffer();
-    // (a band's first row is a multiple of 8 in the frame and in the shard alike, so the shard's row and the frame's agree modulo the pattern)
-    const uint32_t frame_row0 = r->band_rows ? 0u : r->row_begin;
-    HIPCHECK(r, launch_trace_ao(g.b, g.c, g.e, r->tiles_x, r->tiles_y, r->width, r->rows(), r->row0_in_tile, frame_row0, d, A.d_dirs.as<float>(), r->ray.d_nodes.p, r->ray.d_tris.p,
-                                (uint32_t)r->ray.n_nodes, d.filter ? 0 : 1, d.filter ? A.d_hits.as<uint8_t>() : d_out, r->stream));
-    if (d.filter) HIPCHECK(r, launch_ao_filter(g.b, g.c, g.e, r->tiles_x, r->tiles_y, r->width, r->rows(), d, A.d_hits.as<uint8_t>(), d_out, r->stream));
-    return ARCTIC_OK;
-}
-}  // namespace
-
-int arctic_trace_ambient_occlusion(ArcticRenderer *r, const ArcticScene *scene, const ArcticAmbientOcclusion *ao, const float *dirs, uint8_t *out) {
-    if (!r) return ARCTIC_E_INVALID;
-    int rc = trace_ambient_occlusion(r, scene, ao, dirs, nullptr, "trace_ambient_occlusion");
-    if (rc || !out) return rc;
-    HIPCHECK(r, hipMemcpyAsync(out, r->ao.d_out.p, (size_t)r->rows() * r->width, hipMemcpyDeviceToHost, r->stream));
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    if (int ov = check_item_overflow(r)) return ov;
-    return ARCTIC_OK;
-}
-
-int arctic_trace_ambient_occlusion_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticAmbientOcclusion *ao, const float *dirs, uint8_t *d_out) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!d_out) return r->fail(ARCTIC_E_INVALID, "trace_ambient_occlusion_device: null output");
-    return trace_ambient_occlusion(r, scene, ao, dirs, d_out, "trace_ambient_occlusion_device");
-}
-
-int arctic_ray_scene_info(ArcticRenderer *r, uint64_t *out4) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!out4) return r->fail(ARCTIC_E_INVALID, "ray_scene_info: null");
-    out4[0] = r->ray.n_tris; out4[1] = r->ray.n_nodes; out4[2] = r->ray.builds; out4[3] = r->ray.depth;
-    return ARCTIC_OK;
-}
-
-int arctic_ray_refit_info(ArcticRenderer *r, uint64_t *out4) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!out4) return r->fail(ARCTIC_E_INVALID, "ray_refit_info: null");
-    out4[0] = r->ray.refits; out4[1] = r->ray.built && r->ray.refittable ? 1 : 0; out4[2] = r->ray.refit_launches; out4[3] = 0;
-    return ARCTIC_OK;
-}
-
-int arctic_ray_scene_reset(ArcticRenderer *r) {
-    if (!r) return ARCTIC_E_INVALID;
-    r->ray.built = false; r->ray.refittable = false; r->ray.key.clear();   // (the buffers stay: a query in flight may still walk them, and the build reuses them)
-    return ARCTIC_OK;
-}
-
-int arctic_ray_scene_resplit(ArcticRenderer *r, const ArcticScene *scene) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "ray_scene_resplit: null scene");
-    int rc = select_device(r);
-    if (rc) return rc;
-    ArcticRenderer::RayScene &R = r->ray;
-    if (!ray_refit_eligible(r, scene)) {   // what a reset and the next query's build do (under the option in force now)
-        R.built = false; R.refittable = false; R.key.clear();
-        R.resplit_fell_back = 1;
-        return ensure_ray_scene(r, scene);
-    }
-    if (R.resplit_slots != R.n_tris) {
-        size_t bytes = 0;
-        HIPCHECK(r, ray_resplit_workspace((uint32_t)R.n_tris, &bytes));
-        HIPCHECK(r, R.d_resplit.ensure(std::max<size_t>(bytes, 256)));
-        R.resplit_bytes = bytes; R.resplit_slots = R.n_tris;
-    }
-    std::vector<uint8_t> key;
-    ray_inputs(r, scene, key);
-    R.resplit_fell_back = 0;
-    return refit_ray_scene(r, scene, key, true);
-}
-
-int arctic_ray_resplit_info(ArcticRenderer *r, uint64_t *out4) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!out4) return r->fail(ARCTIC_E_INVALID, "ray_resplit_info: null");
-    out4[0] = r->ray.resplits; out4[1] = r->ray.resplit_launches; out4[2] = r->ray.resplit_fell_back; out4[3] = 0;
-    return ARCTIC_OK;
-}
-
-int arctic_read_ray_structure(ArcticRenderer *r, ArcticRayNode *nodes, uint64_t node_cap, ArcticRayTri *tris, uint64_t tri_cap) {
-    if (!r) return ARCTIC_E_INVALID;
-    static_assert(sizeof(ArcticRayNode) == sizeof(RayNode) && sizeof(ArcticRayTri) == sizeof(RayTri), "the public records are the internal ones");
-    if (!r->ray.built) return r->fail(ARCTIC_E_STATE, "read_ray_structure: no structure (a query builds it)");
-    if ((nodes && node_cap < r->ray.n_nodes) || (tris && tri_cap < r->ray.n_tris))
-        return r->fail(ARCTIC_E_CAPACITY, "read_ray_structure: %llu nodes and %llu triangles", (unsigned long long)r->ray.n_nodes, (unsigned long long)r->ray.n_tris);
-    int rc = select_device(r);
-    if (rc) return rc;
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    if (nodes && r->ray.n_nodes) HIPCHECK(r, hipMemcpy(nodes, r->ray.d_nodes.p, r->ray.n_nodes * sizeof(RayNode), hipMemcpyDeviceToHost));
-    if (tris && r->ray.n_tris) HIPCHECK(r, hipMemcpy(tris, r->ray.d_tris.p, r->ray.n_tris * sizeof(RayTri), hipMemcpyDeviceToHost));
-    return ARCTIC_OK;
-}
-
-// ---- hit attributes (the definition: include/arctic_hip.h; the arithmetic: hit_attributes.h; the kernel: hit_shade.hip) ---------------------------
-namespace {
-// the structure for `sc`, the source table of its topology and this call's object records, all on the device; enqueues on the handle's stream
-int ensure_hit_scene(ArcticRenderer *r, const ArcticScene *sc) {
-    int rc = ensure_ray_scene(r, sc);
-    if (rc) return rc;
-    ArcticRenderer::HitScene &H = r->hit;
-    if (H.sources_of != r->ray.builds) {   // (a refit and a re-split keep the objects' meshes, and a mesh keeps its index buffer)
-        HIPCHECK(r, hipStreamSynchronize(r->stream));   // a call in flight may still read the table in place
-        std::vector<HitSource> sources;
-        std::vector<std::vector<uint32_t>> inds(r->meshes.size());
-        for (uint64_t i = 0; i < sc->n_objects; ++i) {
-            const ArcticObject &o = sc->objects[i];
-            if (o.mesh_idx >= r->meshes.size()) continue;   // (no triangles: ensure_ray_scene)
-            const Mesh &m = r->meshes[o.mesh_idx];
-            std::vector<uint32_t> &ix = inds[o.mesh_idx];
-            if (ix.empty() && m.n_indices) {
-                ix.resize(m.n_indices);
-                HIPCHECK(r, hipMemcpy(ix.data(), m.d_indices.p, (size_t)m.n_indices * 4, hipMemcpyDeviceToHost));
-            }
-            hit_triangle_sources((uint32_t)i, m.n_vertices, ix.data(), m.n_indices / 3, sources);   // (at most 2^32 - 2 in all: ensure_ray_scene)
-        }
-        HIPCHECK(r, H.d_src.ensure(std::max<size_t>(sources.size(), 1) * sizeof(HitSource)));
-        if (!sources.empty()) HIPCHECK(r, hipMemcpy(H.d_src.p, sources.data(), sources.size() * sizeof(HitSource), hipMemcpyHostToDevice));
-        H.n_prims = sources.size();
-        H.sources_of = r->ray.builds;
-        ++H.tables_made;
-    }
-    const size_t n_obj = (size_t)sc->n_objects, bytes = std::max<size_t>(n_obj, 1) * sizeof(HitObject);
-    HitObject *h_objs = nullptr;
-    HIPCHECK(r, H.objs_ring.stage(bytes, &h_objs));
-    HIPCHECK(r, H.d_objs.ensure(bytes));
-    for (size_t i = 0; i < n_obj; ++i) {
-        const ArcticObject &o = sc->objects[i];
-        HitObject &d = h_objs[i];
-        std::memcpy(d.trs, o.trs, sizeof d.trs);
-        const bool there = o.mesh_idx < r->meshes.size();   // (an object without a mesh has no prim: its record is never read)
-        d.vertices = there ? r->meshes[o.mesh_idx].vertices_in_use() : nullptr;
-        d.n_vertices = there ? r->meshes[o.mesh_idx].n_vertices : 0u;
-        d.material = there ? (uint32_t)r->meshes[o.mesh_idx].material : HIT_NO_MATERIAL;
-    }
-    HIPCHECK(r, H.objs_ring.send(H.d_objs.p, n_obj * sizeof(HitObject), r->stream));
-    return ARCTIC_OK;
-}
-}  // namespace
-
-int arctic_hit_attributes(ArcticRenderer *r, const ArcticScene *scene, const ArcticHit *hits, uint64_t n, float *attrs, uint32_t *material) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "hit_attributes: null scene");
-    if (n && (!hits || !attrs || !material)) return r->fail(ARCTIC_E_INVALID, "hit_attributes: null hits, attrs or material");
-    if (n > 0xFFFFFFFFull) return r->fail(ARCTIC_E_CAPACITY, "hit_attributes: %llu hits in one call (2^32 - 1 at most)", (unsigned long long)n);
-    int rc;
-    if ((rc = select_device(r)) != ARCTIC_OK || (rc = ensure_hit_scene(r, scene)) != ARCTIC_OK) return rc;
-    if (n == 0) return ARCTIC_OK;
-    ArcticRenderer::HitScene &H = r->hit;
-    float lpv[16];
-    sun_proj_view(scene->sun.position, scene->sun.rotation, lpv);
-    HIPCHECK(r, H.d_hits.ensure(n * sizeof(ArcticHit)));
-    HIPCHECK(r, H.d_attrs.ensure(n * HIT_ATTRS * sizeof(float)));
-    HIPCHECK(r, H.d_material.ensure(n * sizeof(uint32_t)));
-    HIPCHECK(r, hipMemcpyAsync(H.d_hits.p, hits, n * sizeof(ArcticHit), hipMemcpyHostToDevice, r->stream));
-    HIPCHECK(r, launch_hit_attributes(H.d_hits.p, n, H.d_src.as<HitSource>(), (uint32_t)H.n_prims, H.d_objs.as<HitObject>(), lpv, H.d_attrs.as<float>(),
-                                      H.d_material.as<uint32_t>(), r->stream));
-    HIPCHECK(r, hipMemcpyAsync(attrs, H.d_attrs.p, n * HIT_ATTRS * sizeof(float), hipMemcpyDeviceToHost, r->stream));
-    HIPCHECK(r, hipMemcpyAsync(material, H.d_material.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    return ARCTIC_OK;
-}
-
-// ---- hit shading and the reflection plane (include/arctic_hip.h; the kernels: hit_shade.hip) -------------------------------------------------------
-namespace {
-// the sun's map as k_shade_hits needs it: whole, and drawn or written at least once
-int sun_map_ready(ArcticRenderer *r, const char *who) {
-    if (r->shadow_size && r->shadow_sharded)
-        return r->fail(ARCTIC_E_STATE, "%s: the sun's map is sharded (ARCTIC_OPT_SHADOW_SHARDED): a hit may lie in rows this handle never draws", who);
-    if (r->shadow_size && !r->shadow_written_set[r->scur])
-        return r->fail(ARCTIC_E_STATE, "%s: the sun's map was never drawn or written (arctic_pass_shadow_map, arctic_write_shadow_map or a frame first)", who);
-    return ARCTIC_OK;
-}
-// what both forms of arctic_shade_hits refuse before the device is touched
-int shade_checks(ArcticRenderer *r, const ArcticScene *sc, const void *rays, const void *hits, uint64_t n, uint32_t flags, const void *out, const char *who) {
-    if (!valid_scene(sc)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
-    if (flags) return r->fail(ARCTIC_E_INVALID, "%s: flags %#x (0)", who, flags);
-    if (n && (!rays || !hits || !out)) return r->fail(ARCTIC_E_INVALID, "%s: null rays, hits or output", who);
-    if (n > 0xFFFFFFFFull) return r->fail(ARCTIC_E_CAPACITY, "%s: %llu rays in one call (2^32 - 1 at most)", who, (unsigned long long)n);
-    return sun_map_ready(r, who);
-}
-// the structure, the tables and the launch: device pointers throughout
-int shade_hits(ArcticRenderer *r, const ArcticScene *sc, const void *d_rays, const void *d_hits, uint64_t n, float4 *d_out) {
-    int rc = ensure_hit_scene(r, sc);
-    if (rc || n == 0) return rc;
-    HitShadeParams p = {};
-    p.src = r->hit.d_src.as<HitSource>(); p.objs = r->hit.d_objs.as<HitObject>(); p.n_prims = (uint32_t)r->hit.n_prims;
-    p.tex = r->d_tex.as<TexDesc>(); p.srgb_lut = r->d_lut.as<float>();
-    p.shadow_map = r->shadow_size ? r->d_shadow().as<float>() : nullptr; p.shadow_size = r->shadow_size;
-    p.lights = r->d_lights.as<float4>(); p.n_lights = r->n_lights;
-    p.env = r->env_w ? r->d_env.as<float4>() : nullptr; p.env_w = r->env_w; p.env_h = r->env_h;
-    p.ambient = sc->ambient;
-    dir_from_rot(sc->sun.rotation, p.sun_dir);
-    std::memcpy(p.sun_color, sc->sun.color, sizeof p.sun_color);
-    sun_proj_view(sc->sun.position, sc->sun.rotation, p.lpv);
-    HIPCHECK(r, launch_shade_hits(d_rays, d_hits, n, p, d_out, r->stream));
-    return ARCTIC_OK;
-}
-}  // namespace
-
-int arctic_shade_hits_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *d_rays, const ArcticHit *d_hits, uint64_t n, uint32_t flags, float *d_rgba32f) {
-    if (!r) return ARCTIC_E_INVALID;
-    int rc = shade_checks(r, scene, d_rays, d_hits, n, flags, d_rgba32f, "shade_hits_device");
-    if (rc) return rc;
-    if (((uintptr_t)d_rays | (uintptr_t)d_hits | (uintptr_t)d_rgba32f) & 15u) return r->fail(ARCTIC_E_INVALID, "shade_hits_device: rays, hits and output must be 16-byte aligned");
-    if ((rc = select_device(r)) != ARCTIC_OK) return rc;
-    return shade_hits(r, scene, d_rays, d_hits, n, reinterpret_cast<float4 *>(d_rgba32f));
-}
-
-int arctic_shade_hits(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *rays, const ArcticHit *hits, uint64_t n, uint32_t flags, float *rgba32f) {
-    if (!r) return ARCTIC_E_INVALID;
-    int rc = shade_checks(r, scene, rays, hits, n, flags, rgba32f, "shade_hits");
-    if (rc) return rc;
-    if ((rc = select_device(r)) != ARCTIC_OK) return rc;
-    ArcticRenderer::HitScene &H = r->hit;
-    if (n) {
-        HIPCHECK(r, H.d_rays.ensure(n * sizeof(ArcticRay)));
-        HIPCHECK(r, H.d_hits.ensure(n * sizeof(ArcticHit)));
-        HIPCHECK(r, H.d_color.ensure(n * 16));
-        HIPCHECK(r, hipMemcpyAsync(H.d_rays.p, rays, n * sizeof(ArcticRay), hipMemcpyHostToDevice, r->stream));
-        HIPCHECK(r, hipMemcpyAsync(H.d_hits.p, hits, n * sizeof(ArcticHit), hipMemcpyHostToDevice, r->stream));
-    }
-    if ((rc = shade_hits(r, scene, H.d_rays.p, H.d_hits.p, n, H.d_color.as<float4>())) != ARCTIC_OK || n == 0) return rc;
-    HIPCHECK(r, hipMemcpyAsync(rgba32f, H.d_color.p, n * 16, hipMemcpyDeviceToHost, r->stream));
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    return ARCTIC_OK;
-}
-
-namespace {
-// the checks, the G-buffer and the three launches of both reflection calls; d_out: the caller's device memory, or null = the handle's own
-int trace_reflections(ArcticRenderer *r, const ArcticScene *scene, float bias, float4 *d_out, const char *who) {
-    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
-    if (!std::isfinite(bias)) return r->fail(ARCTIC_E_INVALID, "%s: the bias is not finite", who);
-    const uint64_t n = (uint64_t)r->rows() * r->width;
-    if (!r->have_gbuffer && !r->have_vis) return r->fail(ARCTIC_E_STATE, "%s: no G-buffer (arctic_pass_gbuffer, arctic_write_gbuffer or a frame first)", who);
-    int rc = sun_map_ready(r, who);
-    if (rc || (rc = select_device(r)) != ARCTIC_OK) return rc;
-    if (!r->have_gbuffer && (rc = resolve_gbuffer(r)) != ARCTIC_OK) return rc;   // the frame was shaded from the visibility plane
-    if ((rc = ensure_ray_scene(r, scene)) != ARCTIC_OK) return rc;
-    ArcticRenderer::HitScene &H = r->hit;
-    HIPCHECK(r, H.d_rays.ensure(std::max<uint64_t>(n, 1) * sizeof(ArcticRay)));
-    HIPCHECK(r, H.d_hits.ensure(std::max<uint64_t>(n, 1) * sizeof(ArcticHit)));
-    if (!d_out) { HIPCHECK(r, H.d_color.ensure(std::max<uint64_t>(n, 1) * 16)); d_out = H.d_color.as<float4>(); }
-    const GBuffer g = r->gbuffer();
-    HIPCHECK(r, launch_reflect_rays(g.b, g.c, g.e, r->tiles_x, r->tiles_y, r->width, r->rows(), r->row0_in_tile, scene->camera.eye, bias, H.d_rays.p, r->stream));
-    HIPCHECK(r, launch_trace(H.d_rays.p, n, r->ray.d_nodes.p, r->ray.d_tris.p, (uint32_t)r->ray.n_nodes, 0, H.d_hits.p, r->stream));
-    return shade_hits(r, scene, H.d_rays.p, H.d_hits.p, n, d_out);
-}
-}  // namespace
-
-int arctic_trace_reflections(ArcticRenderer *r, const ArcticScene *scene, float bias, float *rgba32f) {
-    if (!r) return ARCTIC_E_INVALID;
-    int rc = trace_reflections(r, scene, bias, nullptr, "trace_reflections");
-    if (rc || !rgba32f) return rc;
-    HIPCHECK(r, hipMemcpyAsync(rgba32f, r->hit.d_color.p, (size_t)r->rows() * r->width * 16, hipMemcpyDeviceToHost, r->stream));
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    if (int ov = check_item_overflow(r)) return ov;
-    return ARCTIC_OK;
-}
-
-int arctic_trace_reflections_device(ArcticRenderer *r, const ArcticScene *scene, float bias, float *d_rgba32f) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!d_rgba32f || ((uintptr_t)d_rgba32f & 15u)) return r->fail(ARCTIC_E_INVALID, "trace_reflections_device: the output is null or not 16-byte aligned");
-    return trace_reflections(r, scene, bias, reinterpret_cast<float4 *>(d_rgba32f), "trace_reflections_device");
-}
-
-int arctic_hit_shading_info(ArcticRenderer *r, uint64_t *out4) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!out4) return r->fail(ARCTIC_E_INVALID, "hit_shading_info: null");
-    out4[0] = r->hit.device_bytes(); out4[1] = r->hit.pinned_bytes(); out4[2] = r->hit.n_prims; out4[3] = r->hit.tables_made;
-    return ARCTIC_OK;
-}
-
-// ---- multi-GPU exchange steps (include/arctic_dist.h) ------------------------------------------------------------------------
-// the plan, as pure host functions (no device, no handle): everything below is built on them
-int arctic_exchange_plan(uint32_t width, uint32_t height, uint32_t band_rows, uint32_t world, const uint32_t *row_ranges,
-                         uint32_t *rows, uint64_t *offset, uint64_t *total_bytes) {
-    if (!rows || !offset || world == 0 || width == 0 || height == 0) return ARCTIC_E_INVALID;
-    if (row_ranges) {
-        if (band_rows) return ARCTIC_E_INVALID;
-        for (uint32_t k = 0; k < world; ++k) {
-            if (row_ranges[2 * k] > row_ranges[2 * k + 1] || row_ranges[2 * k + 1] > height) return ARCTIC_E_INVALID;
-            rows[k] = row_ranges[2 * k + 1] - row_ranges[2 * k];
-        }
-    } else {
-        if (!band_rows) return ARCTIC_E_INVALID;
-        // band b -> rank b % world: full bands each, and the frame's last (possibly short) band to whoever it falls to
-        const uint32_t n_bands = (height + band_rows - 1) / band_rows, last_rows = height - (n_bands - 1) * band_rows;
-        for (uint32_t k = 0; k < world; ++k) {
-            const uint32_t mine = n_bands / world + (k < n_bands % world ? 1u : 0u);
-            rows[k] = mine * band_rows;
-            if (mine && (n_bands - 1) % world == k) rows[k] -= band_rows - last_rows;
-        }
-    }
-    uint64_t off = 0;
-    for (uint32_t k = 0; k < world; ++k) { offset[k] = off; off += (uint64_t)rows[k] * width * 4; }
-    if (total_bytes) *total_bytes = off;
-    return ARCTIC_OK;
-}
-
-int arctic_exchange_row_source(uint32_t y, uint32_t height, uint32_t band_rows, uint32_t world, const uint32_t *row_ranges,
-                               uint32_t *owner, uint32_t *local_row) {
-    if (!owner || !local_row || world == 0 || y >= height || (!row_ranges && !band_rows) || (row_ranges && band_rows)) return ARCTIC_E_INVALID;
-    return shard_row_source(y, band_rows, world, row_ranges, *owner, *local_row) ? 0 : 1;
-}
-
-int arctic_exchange_transfers(uint32_t width, uint32_t world, int32_t rank, int32_t root, const uint32_t *rows, const uint64_t *offset,
-                              ArcticTransfer *out, uint32_t cap) {
-    if (!rows || !offset || !out || world == 0 || rank < 0 || root < 0 || (uint32_t)rank >= world || (uint32_t)root >= world) return ARCTIC_E_INVALID;
-    uint32_t n = 0;
-    const uint64_t row_bytes = (uint64_t)width * 4;
-    if (rank != root) {
-        if (rows[rank]) { if (n >= cap) return ARCTIC_E_CAPACITY; out[n++] = ArcticTransfer{root, 1, 0, rows[rank] * row_bytes}; }
-        return (int)n;
-    }
-    for (uint32_t k = 0; k < world; ++k) {
-        if ((int32_t)k == root || !rows[k]) continue;
-        if (n >= cap) return ARCTIC_E_CAPACITY;
-        out[n++] = ArcticTransfer{(int32_t)k, 0, offset[k], rows[k] * row_bytes};
-    }
-    return (int)n;
-}
-
-namespace {
-
-// rows of every rank's shard and where each shard starts in a staging buffer that holds them back to back; uploaded to d_layout
-int upload_layout(ArcticRenderer *r, uint32_t world, const uint32_t *ranges /* 2 * world, or null: interleaved bands */, bool from_comm) {
-    std::vector<uint32_t> rows(world, 0), rg(2 * (size_t)world, 0);
-    std::vector<uint64_t> off(world, 0);
-    uint64_t total = 0;
-    if (ranges) std::memcpy(rg.data(), ranges, (size_t)world * 8);
-    else if (!r->band_rows || r->shard_count != world) return r->fail(ARCTIC_E_INVALID, "frame layout: interleaved bands need band_rows > 0 and shard_count == world");
-    if (arctic_exchange_plan(r->width, r->height, ranges ? 0u : r->band_rows, world, ranges, rows.data(), off.data(), &total) != ARCTIC_OK)
-        return r->fail(ARCTIC_E_INVALID, "frame layout: bad row ranges");
-    const size_t ranges_bytes = (((size_t)world * 8) + 15) / 16 * 16;
-    HIPCHECK(r, r->d_layout.ensure(ranges_bytes + (size_t)world * 8));
-    HIPCHECK(r, hipMemcpyAsync(r->d_layout.p, rg.data(), (size_t)world * 8, hipMemcpyHostToDevice, r->stream));
-    HIPCHECK(r, hipMemcpyAsync(r->d_layout.as<char>() + ranges_bytes, off.data(), (size_t)world * 8, hipMemcpyHostToDevice, r->stream));
-    HIPCHECK(r, hipStreamSynchronize(r->stream));   // the host vectors go out of scope
-    r->peer_rows = rows; r->peer_offset = off; r->staging_bytes = total; r->peer_ranges = ranges ? rg : std::vector<uint32_t>();
-    r->layout_world = world; r->layout_from_comm = from_comm;
-    return ARCTIC_OK;
-}
-const uint32_t *layout_ranges(const ArcticRenderer *r) { return r->d_layout.as<uint32_t>(); }
-const unsigned long long *layout_offsets(const ArcticRenderer *r) {
-    return reinterpret_cast<const unsigned long long *>(r->d_layout.as<char>() + (((size_t)r->layout_world * 8) + 15) / 16 * 16);
-}
-
-// the second half of arctic_comm_init, free of RCCL calls (unit-testable through arctic_comm_init's error paths): `all` holds every
-// rank's {row_begin, row_end, rows, band_rows}; checks them against this handle's sharding, uploads the layout, grows the shadow maps
-int comm_adopt_layout(ArcticRenderer *r, const uint32_t *all, int world) {
-    std::vector<uint32_t> ranges(2 * (size_t)world);
-    for (int k = 0; k < world; ++k) {
-        if (all[4 * k + 3] != r->band_rows) return r->fail(ARCTIC_E_INVALID, "comm_init: rank %d shards the frame differently (band_rows %u vs %u)", k, all[4 * k + 3], r->band_rows);
-        ranges[2 * k] = all[4 * k]; ranges[2 * k + 1] = all[4 * k + 1];
-    }
-    int rc = upload_layout(r, (uint32_t)world, r->band_rows ? nullptr : ranges.data(), true);
-    if (rc != ARCTIC_OK) return rc;
-    for (int k = 0; k < world; ++k)
-        if (r->peer_rows[(size_t)k] != all[4 * k + 2]) return r->fail(ARCTIC_E_INVALID, "comm_init: rank %d reports %u rows, the layout gives it %u", k, all[4 * k + 2], r->peer_rows[(size_t)k]);
-    if (r->shadow_size) {   // room for the in-place all-gather of a sharded shadow map, in BOTH map sets (frames in flight flip between them)
-        const size_t need = shadow_alloc_bytes(r);
-        for (int s = 0; s < 2; ++s) {
-            DevBuf &b = r->d_shadow_set[s];
-            if (!b.p || b.cap >= need) continue;   // (the second set is allocated, at this size, when first used)
-            HIPCHECK(r, hipStreamSynchronize(r->stream));
-            HIPCHECK(r, b.ensure(need));
-            HIPCHECK(r, launch_fill_u32(b.as<uint32_t>(), 0x3F800000u, (need - 8) / 4, r->stream));
-            r->shadow_key.clear(); r->bounds_valid_set[s] = false; r->shadow_written_set[s] = false;
-        }
-    }
-    return ARCTIC_OK;
-}
-
-}  // namespace
-
-int arctic_comm_unique_id(void *id_out, char *err, uint64_t err_len) {
-    auto say = [&](const char *m) { if (err && err_len) std::snprintf(err, (size_t)err_len, "%s", m); return ARCTIC_E_DEVICE; };
-    if (!id_out) return ARCTIC_E_INVALID;
-    if (!g_rccl.load()) return say("arctic_comm_unique_id: librccl.so could not be loaded");
-    Rccl::UniqueId id;
-    const int rc = g_rccl.GetUniqueId(&id);
-    if (rc != 0) return say(g_rccl.why(rc));
-    std::memcpy(id_out, id.internal, ARCTIC_COMM_ID_BYTES);
-    return ARCTIC_OK;
-}
-
-int arctic_comm_init(ArcticRenderer *r, const void *id_bytes, int rank, int world) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!id_bytes || world < 1 || rank < 0 || rank >= world) return r->fail(ARCTIC_E_INVALID, "comm_init: bad id / rank / world");
-    if (r->comm) return r->fail(ARCTIC_E_STATE, "comm_init: the handle already has a communicator");
-    if (r->band_rows && ((uint32_t)world != r->shard_count || (uint32_t)rank != r->shard_index))
-        return r->fail(ARCTIC_E_INVALID, "comm_init: rank %d of %d does not match the handle's shard %u of %u", rank, world, r->shard_index, r->shard_count);
-    int rc = select_device(r);
-    if (rc) return rc;
-    if (!g_rccl.load()) return r->fail(ARCTIC_E_DEVICE, "comm_init: librccl.so could not be loaded");
-    Rccl::UniqueId id;
-    std::memcpy(id.internal, id_bytes, ARCTIC_COMM_ID_BYTES);
-    int nrc = g_rccl.CommInitRank(&r->comm, world, id, rank);
-    if (nrc != 0) { r->comm = nullptr; return r->fail(ARCTIC_E_DEVICE, "ncclCommInitRank: %s", g_rccl.why(nrc)); }
-    r->comm_rank = rank; r->comm_world = world;
-    // From here on the handle owns a communicator: any failure below gives it back (arctic_comm_destroy) before returning, so the
-    // handle is never left half initialised (comm set, no layout) and arctic_comm_init can be called again.
-    DevBuf tmp;
-    const auto finish = [&]() -> int {
-        if (!r->comm_stream) {
-            // (the runtime deals few hardware queues to many streams, and two streams on one queue do not overlap: DESIGN.md 4.3)
-            if (r->stream != r->own_stream) { r->comm_stream = r->own_stream; r->comm_stream_borrowed = true; }
-            else { HIPCHECK(r, r->comm_stream_owned.create(hipStreamNonBlocking)); r->comm_stream = r->comm_stream_owned; }
-        }
-        HIPCHECK(r, r->shaded.ensure(hipEventDisableTiming));
-        HIPCHECK(r, r->shard_readers.ensure(hipEventDisableTiming));
-        // every rank's shard layout: {row_begin, row_end, rows, band_rows} all-gathered once (the root places shards of unequal size)
-        HIPCHECK(r, tmp.ensure((size_t)world * 16));
-        const uint32_t mine[4] = {r->band_rows ? 0u : r->row_begin, r->band_rows ? 0u : r->row_end, r->rows(), r->band_rows};
-        HIPCHECK(r, hipMemcpyAsync(tmp.as<char>() + (size_t)rank * 16, mine, 16, hipMemcpyHostToDevice, r->comm_stream));
-        const int arc = g_rccl.AllGather(tmp.as<char>() + (size_t)rank * 16, tmp.p, 4, Rccl::Uint32, r->comm, r->comm_stream);
-        if (arc != 0) return r->fail(ARCTIC_E_DEVICE, "ncclAllGather(layout): %s", g_rccl.why(arc));
-        std::vector<uint32_t> all((size_t)world * 4);
-        HIPCHECK(r, hipMemcpyAsync(all.data(), tmp.p, (size_t)world * 16, hipMemcpyDeviceToHost, r->comm_stream));
-        HIPCHECK(r, hipStreamSynchronize(r->comm_stream));
-        return comm_adopt_layout(r, all.data(), world);
-    };
-    rc = finish();
-    if (rc != ARCTIC_OK) {
-        const std::string why = r->err;
-        (void)arctic_comm_destroy(r);
-        r->err = why;
-        return rc;
-    }
-    return ARCTIC_OK;
-}
-
-int arctic_comm_destroy(ArcticRenderer *r) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (r->comm_stream) (void)hipStreamSynchronize(r->comm_stream);
-    if (r->comm) { (void)g_rccl.CommDestroy(r->comm); r->comm = nullptr; }
-    r->comm_rank = 0; r->comm_world = 1;
-    if (r->layout_from_comm) { r->layout_world = 0; r->layout_from_comm = false; }
-    r->shard_readers.release();
-    r->shaded.release();
-    r->comm_stream_owned.release();   // (nothing when the stream was borrowed: own_stream stays the handle's)
-    r->comm_stream = nullptr; r->comm_stream_borrowed = false;
-    return ARCTIC_OK;
-}
-
-int arctic_gather_frame(ArcticRenderer *r, const void *d_shard, void *d_frame, int root) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!r->comm || !r->layout_from_comm) return r->fail(ARCTIC_E_STATE, "gather_frame: no communicator (arctic_comm_init)");
-    if (root < 0 || root >= r->comm_world) return r->fail(ARCTIC_E_INVALID, "gather_frame: bad root");
-    const bool is_root = r->comm_rank == root;
-    if (is_root && !d_frame) return r->fail(ARCTIC_E_INVALID, "gather_frame: the root needs a frame buffer");
-    if (!d_shard) {
-        if (!r->have_output) return r->fail(ARCTIC_E_STATE, "gather_frame: no shaded output to gather");
-        d_shard = r->rgba8_output();
-    }
-    int rc = select_device(r);
-    if (rc) return rc;
-    const size_t row_bytes = (size_t)r->width * 4;
-    HIPCHECK(r, r->shaded.record(r->stream));        // after the shading that produced the shard ...
-    HIPCHECK(r, r->shaded.wait(r->comm_stream));     // ... on the communication stream, beside the next frame
-    const uint8_t *src = static_cast<const uint8_t *>(d_shard);
-    if (r->comm_world > 1) {
-        // the transfers of this rank, straight from the plan (arctic_exchange_transfers: what the CPU tests check for worlds 2..8)
-        std::vector<ArcticTransfer> xfers((size_t)r->comm_world);
-        const int n_x = arctic_exchange_transfers(r->width, (uint32_t)r->comm_world, r->comm_rank, root, r->peer_rows.data(), r->peer_offset.data(),
-                                                  xfers.data(), (uint32_t)xfers.size());
-        if (n_x < 0) return r->fail(ARCTIC_E_STATE, "gather_frame: no transfer plan");
-        if (is_root) HIPCHECK(r, r->d_staging.ensure((size_t)r->staging_bytes));
-        int nrc = g_rccl.GroupStart();
-        if (nrc != 0) return r->fail(ARCTIC_E_DEVICE, "ncclGroupStart: %s", g_rccl.why(nrc));
-        for (int i = 0; i < n_x && nrc == 0; ++i) {
-            const ArcticTransfer &t = xfers[(size_t)i];
-            nrc = t.is_send ? g_rccl.Send(src, (size_t)t.bytes, Rccl::Uint8, t.peer, r->comm, r->comm_stream)
-                            : g_rccl.Recv(r->d_staging.as<char>() + t.staging_offset, (size_t)t.bytes, Rccl::Uint8, t.peer, r->comm, r->comm_stream);
-        }
-        const int erc = g_rccl.GroupEnd();
-        if (nrc != 0 || erc != 0) return r->fail(ARCTIC_E_DEVICE, "ncclSend/ncclRecv(frame shards): %s", g_rccl.why(nrc ? nrc : erc));
-        if (is_root) {
-            HIPCHECK(r, hipMemcpyAsync(r->d_staging.as<char>() + r->peer_offset[(size_t)root], src, (size_t)r->rows() * row_bytes, hipMemcpyDeviceToDevice, r->comm_stream));
-            src = r->d_staging.as<uint8_t>();
-        }
-    }
-    if (is_root)
-        HIPCHECK(r, launch_place_rows(src, static_cast<uint8_t *>(d_frame), r->width, r->height, r->band_rows, (uint32_t)r->comm_world,
-                                      layout_ranges(r), layout_offsets(r), r->comm_stream));
-    // whoever writes this shard buffer next waits for the transfers that still read it
-    StreamMark *gathered = nullptr;
-    HIPCHECK(r, r->shard_readers.claim(d_shard, r->comm_stream, gathered));
-    HIPCHECK(r, gathered->record(r->comm_stream));
-    return ARCTIC_OK;
-}
-
-int arctic_assemble_frame(ArcticRenderer *r, const void *d_staging, void *d_frame, uint32_t world, const uint32_t *row_ranges) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!d_staging || !d_frame || world == 0) return r->fail(ARCTIC_E_INVALID, "assemble_frame: null buffer or world == 0");
-    int rc = select_device(r);
-    if (rc) return rc;
-    if (r->layout_from_comm && (uint32_t)r->comm_world != world) return r->fail(ARCTIC_E_STATE, "assemble_frame: the handle's communicator has another world size");
-    if (!r->layout_from_comm && (rc = upload_layout(r, world, row_ranges, false)) != ARCTIC_OK) return rc;
-    HIPCHECK(r, launch_place_rows(static_cast<const uint8_t *>(d_staging), static_cast<uint8_t *>(d_frame), r->width, r->height,
-                                  row_ranges ? 0u : r->band_rows, world, layout_ranges(r), layout_offsets(r), r->stream));
     return ARCTIC_OK;
 }
 

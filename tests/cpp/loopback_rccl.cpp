@@ -1,4 +1,4 @@
-// loopback_rccl.cpp -- TEST DOUBLE for the nine RCCL entry points libarctic_hip.so resolves (csrc/renderer.cpp: struct Rccl), so that
+// loopback_rccl.cpp -- TEST DOUBLE for the nine RCCL entry points libarctic_hip.so resolves (csrc/renderer_state.h: struct Rccl; its one instance: csrc/exchange_calls.cpp), so that
 // the R > 1 branch of the exchange (arctic_comm_init's layout all-gather, arctic_gather_frame's grouped send / recv, the sharded shadow
 // map's in-place all-gather) can be EXECUTED on one GPU: RCCL itself refuses two ranks on one device, and the pool hands out one GPU.
 // Ranks = threads of one process, each driving its own handle; a "communicator" is a rendezvous in host memory, a transfer a

@@ -1,6 +1,6 @@
 """The owning resource types of arctic-renderer_amd/csrc/device_resources.h on a machine without a GPU: the sequence of runtime calls each owner makes and
 that everything is released exactly once -- over a fake runtime, under the address and undefined-behaviour sanitizers, in a program of its own
-(tests/cpp/resources_sanitize.cpp) -- and that renderer.cpp releases nothing by hand any more."""
+(tests/cpp/resources_sanitize.cpp) -- and that the host units of the handle (renderer_state.h and whatever includes it) release nothing by hand any more."""
 import os
 import re
 import shutil
@@ -38,21 +38,24 @@ def test_owners_under_sanitizers():
 
 
 def test_renderer_releases_nothing_by_hand():
-    """renderer.cpp holds what the runtime gave it in owners only: no release call of its own, and arctic_destroy names no buffer"""
-    text = open(os.path.join(CSRC, "renderer.cpp")).read()
+    """the handle's units -- renderer_state.h and every host unit that includes it -- hold what the runtime gave them in owners only: no release call
+    of their own, and arctic_destroy names no buffer"""
+    units = sorted(n for n in os.listdir(CSRC) if n.endswith(".cpp") and re.search(r'#include\s+"renderer_state\.h"', open(os.path.join(CSRC, n)).read()))
+    assert {"renderer.cpp", "ray_calls.cpp", "exchange_calls.cpp"} <= set(units), units
+    text = "".join(open(os.path.join(CSRC, n)).read() for n in ["renderer_state.h"] + units)
     for call in ("hipFree", "hipHostFree", "hipEventDestroy", "hipStreamDestroy"):
         assert not re.search(r"\b" + call + r"\b", text), call
-    m = re.search(r"^void arctic_destroy\(ArcticRenderer \*r\) \{\n(.*?)^\}\n", text, flags=re.S | re.M)
-    assert m, "arctic_destroy not found"
-    body = m.group(1)
+    m = re.findall(r"^void arctic_destroy\(ArcticRenderer \*r\) \{\n(.*?)^\}\n", text, flags=re.S | re.M)
+    assert len(m) == 1, "arctic_destroy not found (once)"
+    body = m[0]
     assert "delete r;" in body and "arctic_comm_destroy(r)" in body
     assert not re.search(r"\bd_\w+", body), body
-    # ... and orders its streams through marks only (device_resources.h StreamMark, ReaderTable): no wait of its own, no record but the timing
+    # ... and order their streams through marks only (device_resources.h StreamMark, ReaderTable): no wait of their own, no record but the timing
     # events of arctic_time_shade, none of the companion state the marks replaced
     assert "hipStreamWaitEvent" not in text
-    timing = re.search(r"^int arctic_time_shade\(.*?^\}\n", text, flags=re.S | re.M)
-    assert timing, "arctic_time_shade not found"
-    assert "hipEventRecord" in timing.group(0) and "hipEventRecord" not in text.replace(timing.group(0), "")
+    timing = re.findall(r"^int arctic_time_shade\(.*?^\}\n", text, flags=re.S | re.M)
+    assert len(timing) == 1, "arctic_time_shade not found (once)"
+    assert "hipEventRecord" in timing[0] and "hipEventRecord" not in text.replace(timing[0], "")
     for gone in ("released_valid", "shadow_released_valid", "shadow_scratch_stream", "shadow_scratch_valid", "skin_seq"):
         assert gone not in text, gone
     # the header the owners live in stays free of the project: nothing but the HIP runtime's API and the standard library

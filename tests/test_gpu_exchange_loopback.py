@@ -23,7 +23,7 @@ def build():
 
 
 def test_loopback_communicator_builds_and_exports_what_the_library_resolves():
-    """(CPU) the nine entry points of csrc/renderer.cpp: struct Rccl"""
+    """(CPU) the nine entry points of csrc/renderer_state.h: struct Rccl"""
     import ctypes
     build()
     L = ctypes.CDLL(LIB)
