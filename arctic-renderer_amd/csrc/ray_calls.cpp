@@ -1,9 +1,10 @@
 // ray_calls.cpp -- the ray family of the C-ABI (include/arctic_hip.h): ray queries, refit and re-split of their structure, sun visibility, ambient
-// occlusion, hit attributes, hit shading and the reflection plane.
+// occlusion, hit attributes, hit shading, the reflection plane, and the composition of the two planes into the shaded frame.
 //
-// Owns, of the handle (renderer_state.h): ArcticRenderer::RayScene, AmbientOcclusion and HitScene -- nothing outside this unit touches them but
+// Owns, of the handle (renderer_state.h): ArcticRenderer::RayScene, AmbientOcclusion, HitScene and Compose -- nothing outside this unit touches them but
 // arctic_set_option, which writes RayScene::refit_opt.  Reads, of the handle's other state: the G-buffer planes (resolved here from the visibility
-// plane when a frame was shaded from it), the shadow map, the lights, the textures, the environment and the meshes.  Enqueues on r->stream only.
+// plane when a frame was shaded from it), the shadow map, the lights, the textures, the environment, the meshes and -- the composition -- the float
+// HDR plane of the latest shading.  Enqueues on r->stream only.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -13,6 +14,7 @@
 #include "ray_query.h"
 #include "ray_ao.h"
 #include "hit_shade.h"
+#include "compose.h"
 
 namespace {
 
@@ -500,6 +502,118 @@ int arctic_hit_shading_info(ArcticRenderer *r, uint64_t *out4) {
     if (!r) return ARCTIC_E_INVALID;
     if (!out4) return r->fail(ARCTIC_E_INVALID, "hit_shading_info: null");
     out4[0] = r->hit.device_bytes(); out4[1] = r->hit.pinned_bytes(); out4[2] = r->hit.n_prims; out4[3] = r->hit.tables_made;
+    return ARCTIC_OK;
+}
+
+// ---- the composition (the definition: include/arctic_hip.h; the arithmetic: compose.h; the kernel: compose.hip) -----------------------------------
+namespace {
+// what both calls refuse with ARCTIC_E_INVALID for the composition's own sake; ao, refl: the planes k_compose will read
+int compose_checks(ArcticRenderer *r, const ArcticScene *sc, const ArcticSettings *st, const ArcticRayCompose *c, const void *ao, const void *refl, ComposeDesc &d, const char *who) {
+    if (!valid_scene(sc) || !st) return r->fail(ARCTIC_E_INVALID, "%s: null scene or settings", who);
+    if (c) std::memcpy(&d, c, sizeof d);
+    const char *why = compose_refusal(c ? &d : nullptr);
+    if (why || (why = compose_plane_refusal(d, ao, refl, 16u)) != nullptr) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
+    return ARCTIC_OK;
+}
+// ... and with ARCTIC_E_STATE, in the header's order: no side effect
+int compose_states(ArcticRenderer *r, const ComposeDesc &d, const char *who) {
+    int rc = gbuffer_refusal(r, who);
+    if (rc) return rc;
+    if (!r->keep_float) return r->fail(ARCTIC_E_STATE, "%s: the float HDR plane needs ARCTIC_OPT_KEEP_FLOAT_OUTPUT", who);
+    if (!r->hdr_valid) return r->fail(ARCTIC_E_STATE, "%s: nothing shaded since ARCTIC_OPT_KEEP_FLOAT_OUTPUT was turned on or since the last resize (arctic_pass_shade or a frame first)", who);
+    if (r->hdr16) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_OPT_HDR16 = 1: the HDR plane is rounded through binary16", who);
+    if (d.flags & COMPOSE_AO) {
+        const char *why = r->env_lighting == 1 ? "ARCTIC_OPT_ENV_LIGHTING is on" : r->texture_mips == 1 ? "ARCTIC_OPT_TEXTURE_MIPS = 1" : r->has_extras() ? "a material is not neutral (arctic_set_material_extras)" : nullptr;
+        if (why) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_COMPOSE_AO: %s, so the frame's ambient term is not ambient * base_color at level 0", who, why);
+    }
+    return ARCTIC_OK;
+}
+// the G-buffer, the handle's buffers and the launch: device pointers throughout; d_out: the caller's RGBA8, or null = the handle's own
+int compose_planes(ArcticRenderer *r, const ArcticScene *sc, const ArcticSettings *st, const ComposeDesc &d, const uint8_t *d_ao, const float *d_refl, uint8_t *d_out) {
+    int rc = gbuffer_in_place(r);
+    if (rc) return rc;
+    ArcticRenderer::Compose &K = r->compose;
+    const uint64_t n = (uint64_t)r->rows() * r->width;
+    if (!d_out) HIPCHECK(r, K.d_rgba8.ensure(std::max<uint64_t>(n, 1) * 4));
+    HIPCHECK(r, K.d_ldr.ensure(std::max<uint64_t>(n, 1) * 12));
+    HIPCHECK(r, K.d_hdr.ensure(std::max<uint64_t>(n, 1) * 12));
+    const GBuffer g = r->gbuffer();
+    ComposeParams p = {};
+    p.plane_a = g.a; p.plane_b = g.b; p.plane_c = g.c; p.plane_e = g.e;
+    p.tex = r->d_tex.as<TexDesc>(); p.srgb_lut = r->d_lut.as<float>();
+    p.hdr = r->d_hdr.as<float>();
+    p.ao = (d.flags & COMPOSE_AO) ? d_ao : nullptr; p.refl = (d.flags & COMPOSE_REFLECTIONS) ? d_refl : nullptr;
+    p.out_rgba8 = reinterpret_cast<uint32_t *>(d_out ? d_out : K.d_rgba8.as<uint8_t>()); p.out_ldr = K.d_ldr.as<float>(); p.out_hdr = K.d_hdr.as<float>();
+    p.tiles_x = r->tiles_x; p.tiles_y = r->tiles_y; p.width = r->width; p.rows = r->rows(); p.row0_in_tile = r->row0_in_tile;
+    p.n_materials = (uint32_t)(r->tex.size() / 3); p.flags = d.flags;
+    p.tm = st->tm_method; p.inv_gamma = 1.0f / st->gamma; p.exposure = st->exposure;
+    p.ao_strength = d.ao_strength; p.reflection_strength = d.reflection_strength; p.ambient = sc->ambient;
+    std::memcpy(p.eye, sc->camera.eye, sizeof p.eye);
+    HIPCHECK(r, launch_compose(p, r->stream));
+    K.pixels = n; K.own_rgba8 = d_out == nullptr; ++K.launches;
+    return ARCTIC_OK;
+}
+}  // namespace
+
+int arctic_compose_planes_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticRayCompose *compose,
+                                 const uint8_t *d_ao_u8, const float *d_reflection_rgba32f, uint8_t *d_out_rgba8) {
+    if (!r) return ARCTIC_E_INVALID;
+    ComposeDesc d;
+    int rc = compose_checks(r, scene, settings, compose, d_ao_u8, d_reflection_rgba32f, d, "compose_planes_device");
+    if (rc) return rc;
+    if (d_out_rgba8 && ((uintptr_t)d_out_rgba8 & 3u)) return r->fail(ARCTIC_E_INVALID, "compose_planes_device: the output is not 4-byte aligned");
+    if ((rc = compose_states(r, d, "compose_planes_device")) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
+    return compose_planes(r, scene, settings, d, d_ao_u8, d_reflection_rgba32f, d_out_rgba8);
+}
+
+int arctic_pass_ray_effects(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticRayCompose *compose,
+                            const ArcticAmbientOcclusion *ao, const float *dirs, uint8_t *d_out_rgba8) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "pass_ray_effects";
+    alignas(16) static const char own_plane[16] = {};   // (the planes are the handle's own: never null, always aligned)
+    ComposeDesc d;
+    int rc = compose_checks(r, scene, settings, compose, own_plane, own_plane, d, who);
+    if (rc) return rc;
+    if (d_out_rgba8 && ((uintptr_t)d_out_rgba8 & 3u)) return r->fail(ARCTIC_E_INVALID, "%s: the output is not 4-byte aligned", who);
+    // every refusal of the two tracing calls, in front of the first launch (the calls below make them again, in their own words, to no effect)
+    AoDesc a = {};
+    if (d.flags & COMPOSE_AO) {
+        if (ao) std::memcpy(&a, ao, sizeof a);
+        if (const char *why = ao_refusal(ao ? &a : nullptr, dirs)) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
+    }
+    if ((d.flags & COMPOSE_REFLECTIONS) && !std::isfinite(d.reflection_bias)) return r->fail(ARCTIC_E_INVALID, "%s: the reflection bias is not finite", who);
+    if ((rc = compose_states(r, d, who)) != ARCTIC_OK) return rc;
+    if ((d.flags & COMPOSE_AO) && a.filter && r->rows() != r->height)
+        return r->fail(ARCTIC_E_STATE, "%s: the filter needs the whole frame, this handle owns %u of %u rows (its neighbours' rows are on other shards)", who, r->rows(), r->height);
+    if ((d.flags & COMPOSE_REFLECTIONS) && (rc = sun_map_ready(r, who)) != ARCTIC_OK) return rc;
+    if ((rc = select_device(r)) != ARCTIC_OK) return rc;
+    if ((d.flags & COMPOSE_AO) && (rc = trace_ambient_occlusion(r, scene, ao, dirs, nullptr, who)) != ARCTIC_OK) return rc;
+    if ((d.flags & COMPOSE_REFLECTIONS) && (rc = trace_reflections(r, scene, d.reflection_bias, nullptr, who)) != ARCTIC_OK) return rc;
+    if ((rc = compose_planes(r, scene, settings, d, r->ao.d_out.as<uint8_t>(), r->hit.d_color.as<float>(), d_out_rgba8)) != ARCTIC_OK) return rc;
+    ++r->compose.passes;
+    return ARCTIC_OK;
+}
+
+int arctic_read_composed(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8) {
+    if (!r) return ARCTIC_E_INVALID;
+    const ArcticRenderer::Compose &K = r->compose;
+    const uint64_t n = (uint64_t)r->rows() * r->width;
+    if (!K.pixels || K.pixels != n) return r->fail(ARCTIC_E_STATE, "read_composed: nothing composed yet, or not since the last resize");
+    if (rgba8 && !K.own_rgba8) return r->fail(ARCTIC_E_STATE, "read_composed: the latest composition wrote the caller's RGBA8 buffer, not the handle's");
+    int rc = select_device(r);
+    if (rc) return rc;
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    if (int ov = check_item_overflow(r)) return ov;
+    if (ldr_rgb) HIPCHECK(r, hipMemcpy(ldr_rgb, K.d_ldr.p, n * 12, hipMemcpyDeviceToHost));
+    if (hdr_rgb) HIPCHECK(r, hipMemcpy(hdr_rgb, K.d_hdr.p, n * 12, hipMemcpyDeviceToHost));
+    if (rgba8) HIPCHECK(r, hipMemcpy(rgba8, K.d_rgba8.p, n * 4, hipMemcpyDeviceToHost));
+    return ARCTIC_OK;
+}
+
+int arctic_compose_info(ArcticRenderer *r, uint64_t *out4) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!out4) return r->fail(ARCTIC_E_INVALID, "compose_info: null");
+    out4[0] = r->compose.device_bytes(); out4[1] = r->compose.launches; out4[2] = r->compose.passes; out4[3] = 0;
     return ARCTIC_OK;
 }
 

@@ -121,6 +121,8 @@ int alloc_targets(ArcticRenderer *r) {
     HIPCHECK(r, r->d_counter.ensure(8 * N_SHADE_STATS));
     HIPCHECK(r, r->d_geo_counters.ensure(5 * N_GEO_COUNTERS * 4));   // N_GEO_COUNTERS words per table set; set 4: the cube faces (CUBE_COUNTER_SET)
     r->have_gbuffer = r->have_output = r->have_vis = r->have_order = false;
+    r->hdr_valid = false;
+    r->compose.pixels = 0;   // (arctic_read_composed: nothing composed at this size yet)
     r->output_filtered = false;
     return ARCTIC_OK;
 }
@@ -626,6 +628,7 @@ int pass_shade(ArcticRenderer *r, const ArcticScene *sc, const ArcticSettings *s
         for (int i = 0; i < 4; ++i) r->edge_stats[i] = n[5 + i];
     }
     r->have_output = (d_out == nullptr);
+    r->hdr_valid = r->keep_float != 0;   // (sp.out_hdr: this pass wrote d_hdr, or it did not)
     r->output_filtered = aa && d_out == nullptr;
     return ARCTIC_OK;
 }
@@ -691,7 +694,7 @@ int check_item_overflow(ArcticRenderer *r) {
     need = std::max(need, std::max(r->h_counts()[1], r->h_counts()[3]));
     r->h_counts()[4] = r->h_counts()[5] = 0;
     r->recs_worst_case = true;   // whichever table it was: the record table takes its worst-case size from now on
-    r->have_gbuffer = false; r->have_output = false; r->have_vis = false; r->have_order = false; r->shadow_key.clear();
+    r->have_gbuffer = false; r->have_output = false; r->hdr_valid = false; r->have_vis = false; r->have_order = false; r->shadow_key.clear();
     return r->fail(ARCTIC_E_CAPACITY, "a rasteriser table overflowed (%u work items needed, %u slots; or more than 2 records per source triangle): the last frame "
                    "is incomplete; the tables grow on the next pass -- render the frame again", need, std::max(r->geo[0].item_cap, r->geo[1].item_cap));
 }
@@ -1648,6 +1651,7 @@ int arctic_time_shade(ArcticRenderer *r, const ArcticScene *scene, const ArcticS
     HIPCHECK(r, hipStreamSynchronize(r->stream));
     for (uint32_t i = 0; i < iters; ++i) HIPCHECK(r, hipEventElapsedTime(&ms_each[i], ev[2 * i], ev[2 * i + 1]));
     r->have_output = true;
+    r->hdr_valid = r->keep_float != 0;
     r->output_filtered = false;   // (the shading kernel alone: d_rgba8 holds what it wrote)
     return ARCTIC_OK;
 }
@@ -1983,7 +1987,7 @@ int arctic_read_env_lighting(ArcticRenderer *r, float *sh27, float *lut, uint32_
 int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
     if (!r) return ARCTIC_E_INVALID;
     switch (option) {
-    case ARCTIC_OPT_KEEP_FLOAT_OUTPUT: r->keep_float = value != 0; break;
+    case ARCTIC_OPT_KEEP_FLOAT_OUTPUT: r->hdr_valid = r->hdr_valid && r->keep_float && value != 0; r->keep_float = value != 0; break;   // (turned on: the HDR plane is the next shading's)
     case ARCTIC_OPT_COUNT_LIGHT_EVALS: r->count_evals = value != 0; break;
     case ARCTIC_OPT_CULLING: r->culling = value != 0; break;
     case ARCTIC_OPT_DEBUG: r->debug = (int)value; break;

@@ -1,5 +1,5 @@
 // renderer_state.h -- the handle of the C-ABI, declared once for the host units that implement it: renderer.cpp (create, destroy and resize,
-// streams, resources, the passes and frames, options, the debug read-backs), ray_calls.cpp (the ray family) and exchange_calls.cpp (the
+// streams, resources, the passes and frames, options, the debug read-backs), ray_calls.cpp (the ray family and the composition) and exchange_calls.cpp (the
 // multi-GPU exchange).  Also the few helpers one of those units defines and another calls.  Host only.
 #pragma once
 #include <algorithm>
@@ -212,6 +212,7 @@ struct ArcticRenderer {
     // frame targets
     DevBuf d_vis_set[3], d_p0, d_p1, d_p2, d_p3, d_p4, d_rgba8, d_ldr, d_hdr, d_counter;
     bool have_gbuffer = false, have_output = false, have_vis = false;   // have_vis: d_vis holds the visibility of the current G-buffer
+    bool hdr_valid = false;          // d_hdr holds the latest shading's colours: set where the shading pass is enqueued under ARCTIC_OPT_KEEP_FLOAT_OUTPUT, cleared by a resize and when the option is turned on (arctic_compose_planes_device asks)
     // ARCTIC_OPT_ANTIALIAS: with 1 a handle that owns the whole frame shades into d_rgba8 and the edge filter (antialias.hip) writes the
     // destination -- the caller's buffer or d_aa; output_filtered: the handle's latest RGBA8 output is the one in d_aa
     int antialias = 0;
@@ -368,6 +369,15 @@ struct ArcticRenderer {
         size_t device_bytes() const { return d_src.cap + d_objs.cap + d_hits.cap + d_attrs.cap + d_material.cap + d_rays.cap + d_color.cap; }
         size_t pinned_bytes() const { size_t b = 0; for (const auto &s : objs_ring.slot) b += s.h.cap; return b; }
     } hit;
+    // The composition (arctic_compose_planes_device, arctic_pass_ray_effects; compose.hip): the composed RGBA8, float LDR and float HDR of the handle's
+    // rows.  Nothing is allocated before the first call that passes its checks.  pixels: rows * width of the latest composition (0: none; a resize
+    // makes the handle's differ); own_rgba8: that call wrote d_rgba8, not the caller's buffer
+    struct Compose {
+        DevBuf d_rgba8, d_ldr, d_hdr;
+        uint64_t pixels = 0, launches = 0, passes = 0;
+        bool own_rgba8 = false;
+        size_t device_bytes() const { return d_rgba8.cap + d_ldr.cap + d_hdr.cap; }
+    } compose;
     PinnedBuf counts;               // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts

@@ -298,6 +298,30 @@ class Renderer {
     // {device bytes, pinned host bytes, prims in the source table, times the table was made}: all 0 until the first of the calls above
     [[nodiscard]] bool hit_shading_info(uint64_t out4[4]) { return ok(arctic_hit_shading_info(m_handle, out4)); }
 
+    // occlusion and reflections composed into the shaded frame, in front of the tonemapper (include/arctic_hip.h: arctic_compose_planes_device and the
+    // definition in front of it; needs ARCTIC_OPT_KEEP_FLOAT_OUTPUT and a shading pass): device planes the caller owns -- a plane whose flag is absent
+    // may be nullptr -- into d_out_rgba8 or, nullptr, the handle's own buffers (read_composed); in stream order on the handle's stream
+    [[nodiscard]] bool compose_planes_device(const ArcticScene &scene, const ArcticSettings &settings, const ArcticRayCompose &compose, const uint8_t *d_ao_u8,
+                                             const float *d_reflection_rgba32f, uint8_t *d_out_rgba8) {
+        return ok(arctic_compose_planes_device(m_handle, &scene, &settings, &compose, d_ao_u8, d_reflection_rgba32f, d_out_rgba8));
+    }
+    // the one call: the ambient occlusion (ao, dirs: as trace_ambient_occlusion takes them; nullptr without ARCTIC_COMPOSE_AO), the reflection plane at
+    // compose.reflection_bias, then the composition
+    [[nodiscard]] bool pass_ray_effects(const ArcticScene &scene, const ArcticSettings &settings, const ArcticRayCompose &compose, const ArcticAmbientOcclusion *ao,
+                                        const float *dirs, uint8_t *d_out_rgba8) {
+        return ok(arctic_pass_ray_effects(m_handle, &scene, &settings, &compose, ao, dirs, d_out_rgba8));
+    }
+    // the latest composition, shaped like read_output; any pointer may be nullptr
+    [[nodiscard]] bool read_composed(float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8) { return ok(arctic_read_composed(m_handle, ldr_rgb, hdr_rgb, rgba8)); }
+    // its host arbiter: the composed HDR colour of n pixels from channels sampled already (no handle, no GPU)
+    [[nodiscard]] static bool compose_pixels(const ArcticRayCompose &compose, const float *eye3, float ambient, uint64_t n, const float *hdr3, const float *base3,
+                                             const float *metal, const float *rough, const float *normal3, const float *world3, const uint8_t *ao, const float *refl4,
+                                             const uint8_t *geometry, float *out_hdr3) {
+        return arctic_compose_pixels(&compose, eye3, ambient, n, hdr3, base3, metal, rough, normal3, world3, ao, refl4, geometry, out_hdr3) == ARCTIC_OK;
+    }
+    // {device bytes, launches of the composition kernel, pass_ray_effects calls, 0}: all 0 until the first call that passes its checks
+    [[nodiscard]] bool compose_info(uint64_t out4[4]) { return ok(arctic_compose_info(m_handle, out4)); }
+
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }
 

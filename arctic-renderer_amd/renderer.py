@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (AO_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (AO_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -288,6 +288,46 @@ class Renderer:
         trace_reflections: all 0 until the first of them"""
         out = np.zeros(4, np.uint64)
         self._check(self.L.arctic_hit_shading_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    # ---- occlusion and reflections composed into the shaded frame (include/arctic_hip.h: arctic_compose_planes_device and the definition) -------
+    def compose_planes_device(self, desc, settings, d_ao_ptr=None, d_reflection_ptr=None, ao_strength=1.0, reflection_strength=1.0, d_out_ptr=None, flags=None):
+        """fold device planes the caller owns (int pointers: rows * width bytes of visibility, rows * width * 16 bytes of RGBA32F, 16-byte aligned)
+        into the float HDR colour of the latest shading (set_option("keep_float_output", 1)), then tonemap; flags default to the planes given.
+        The result stays on the device -- d_out_ptr (rows * width * 4 bytes) or the handle's own buffers: read_composed(); asynchronous on the
+        handle's stream."""
+        s, st = self._scene(desc), self._settings(settings)
+        if flags is None:
+            flags = (binding.COMPOSE_AO if d_ao_ptr else 0) | (binding.COMPOSE_REFLECTIONS if d_reflection_ptr else 0)
+        c = _compose_arguments(flags, ao_strength, reflection_strength, 0.0)
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_compose_planes_device(self.h, C.byref(s), C.byref(st), _ptr(c), vp(d_ao_ptr), vp(d_reflection_ptr), vp(d_out_ptr)))
+
+    def pass_ray_effects(self, desc, settings, dirs=None, reflection_bias=None, ao_strength=1.0, reflection_strength=1.0, d_out_ptr=None, read=True, n_rays=None,
+                         pattern=None, radius=np.inf, bias=1e-3, filter=False, normal_cos=0.9, plane_dist=0.05):
+        """the one call: the ambient occlusion (dirs and its parameters as trace_ambient_occlusion takes them; None: no occlusion), the reflection
+        plane (reflection_bias; None: no reflections), then the composition into the latest shading's HDR colour and the tonemapper:
+        (rows, width, 4) uint8.  read=False or a d_out_ptr leaves the result on the device and returns None."""
+        s, st = self._scene(desc), self._settings(settings)
+        flags = (binding.COMPOSE_AO if dirs is not None else 0) | (binding.COMPOSE_REFLECTIONS if reflection_bias is not None else 0)
+        c = _compose_arguments(flags, ao_strength, reflection_strength, 0.0 if reflection_bias is None else reflection_bias)
+        ao, d = _ao_arguments(dirs, n_rays, pattern, radius, bias, filter, normal_cos, plane_dist) if dirs is not None else (None, None)
+        self._check(self.L.arctic_pass_ray_effects(self.h, C.byref(s), C.byref(st), _ptr(c), _ptr(ao), _ptr(d), C.c_void_p(d_out_ptr) if d_out_ptr else None))
+        return self.read_composed(want=("rgba8",))[2] if read and not d_out_ptr else None
+
+    def read_composed(self, want=("ldr", "hdr", "rgba8")):
+        """the latest composition, shaped like read_output: (ldr, hdr, rgba8), None for what was not asked for"""
+        n = (self.rows, self.width)
+        ldr = np.empty(n + (3,), np.float32) if "ldr" in want else None
+        hdr = np.empty(n + (3,), np.float32) if "hdr" in want else None
+        rgba = np.empty(n + (4,), np.uint8) if "rgba8" in want else None
+        self._check(self.L.arctic_read_composed(self.h, _ptr(ldr), _ptr(hdr), _ptr(rgba)))
+        return ldr, hdr, rgba
+
+    def compose_info(self):
+        """(device bytes, launches of the composition kernel, pass_ray_effects calls, 0) held for the composition: all 0 until the first call"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_compose_info(self.h, _ptr(out)))
         return tuple(int(x) for x in out)
 
     def ray_scene_info(self):
@@ -702,6 +742,36 @@ def ambient_occlusion_points(triangles, points, sets, dirs, n_rays=None, pattern
     if rc < 0:
         raise ArcticError(rc, "ambient_occlusion_points")
     return hits
+
+
+def _compose_arguments(flags, ao_strength, reflection_strength, reflection_bias):
+    """one COMPOSE_DTYPE record; the library checks every value"""
+    c = np.zeros(1, COMPOSE_DTYPE)
+    c["flags"], c["ao_strength"], c["reflection_strength"], c["reflection_bias"] = flags, ao_strength, reflection_strength, reflection_bias
+    return c
+
+
+def compose_pixels(hdr, base, metal, rough, normal, world, geometry, eye, ambient, ao=None, refl=None, ao_strength=1.0, reflection_strength=1.0, flags=None):
+    """arctic_compose_pixels: the composition of include/arctic_hip.h on the host, in front of the tonemapper -- (n, 3) float32 composed HDR colours
+    from (n, 3) hdr, the sampled channels base (n, 3), metal, rough (n,), the G-buffer's normal and world (n, 3), geometry (n,) bool, ao (n,) uint8
+    and refl (n, 4) float32; flags default to the planes given."""
+    f = lambda a, k: np.ascontiguousarray(a, dtype=np.float32).reshape((-1, k) if k > 1 else (-1,))
+    h, b, m, r, nr, w = f(hdr, 3), f(base, 3), f(metal, 1), f(rough, 1), f(normal, 3), f(world, 3)
+    g = np.ascontiguousarray(np.asarray(geometry) != 0, dtype=np.uint8).ravel()
+    a = None if ao is None else np.ascontiguousarray(ao, dtype=np.uint8).ravel()
+    rf = None if refl is None else f(refl, 4)
+    n = len(h)
+    if any(len(x) != n for x in (b, m, r, nr, w, g)) or (a is not None and len(a) != n) or (rf is not None and len(rf) != n):
+        raise ArcticError(-1, "compose_pixels: one entry of every array per pixel")
+    if flags is None:
+        flags = (binding.COMPOSE_AO if a is not None else 0) | (binding.COMPOSE_REFLECTIONS if rf is not None else 0)
+    c = _compose_arguments(flags, ao_strength, reflection_strength, 0.0)
+    e = np.ascontiguousarray(eye, dtype=np.float32).reshape(3)
+    out = np.empty((n, 3), np.float32)
+    rc = binding.lib().arctic_compose_pixels(_ptr(c), _ptr(e), float(ambient), n, _ptr(h), _ptr(b), _ptr(m), _ptr(r), _ptr(nr), _ptr(w), _ptr(a), _ptr(rf), _ptr(g), _ptr(out))
+    if rc < 0:
+        raise ArcticError(rc, "compose_pixels")
+    return out
 
 
 def ao_directions(n_rays, pattern, seed=0):

@@ -939,7 +939,7 @@ int arctic_resplit_triangles(const float *tris9_build, const float *tris9_now, u
  * How open is each pixel?  n_rays short any-hit rays per pixel over the hemisphere of its normal, against the structure of the ray queries above
  * (built, refitted and re-split as described there), walked by ordinary vector code (ray_ao.hip).  The answer is DEFINED bit for bit: numpy in
  * float32 reproduces it (tests/ao_reference.py), and so does arctic_ambient_occlusion_points on the host.  Nothing in the passes uses the plane:
- * shading and every existing bit are unchanged; a host multiplies it into its indirect term or bakes it.
+ * shading and every existing bit are unchanged; arctic_compose_planes_device and arctic_pass_ray_effects (below) fold it into the shaded frame.
  *
  * THE DEFINITION.  Everything is fp32, one rounding per operation, in the written order, no contraction; division and square root are IEEE
  * (correctly rounded); dot, min, max as the ray-query section defines them.
@@ -1005,7 +1005,7 @@ int arctic_ambient_occlusion_points(const float *tris9, uint64_t n_tris, const f
  * A ray query answers {t, u, v, prim}.  The three layers below turn that into the interpolated vertex output at the hit, into the colour the
  * forward pass would give that point seen along the ray, and into a plane of mirror reflections of the resident G-buffer.  Each is usable alone.
  * Nothing in the passes uses them: shading, shadow maps and every existing bit are unchanged, and a handle that never makes these calls
- * allocates nothing for them.
+ * allocates nothing for them; arctic_compose_planes_device and arctic_pass_ray_effects (below) fold the reflection plane into the shaded frame.
  *
  * 1. HIT ATTRIBUTES, DEFINED bit for bit: numpy in float32 reproduces them (tests/hit_reference.py), and so does arctic_interpolate_hits on the host.
  * Everything is fp32; each operation rounds once, in the written order, without contraction; division and square root are IEEE.
@@ -1085,6 +1085,90 @@ int arctic_trace_reflections_device(ArcticRenderer *r, const ArcticScene *scene,
  * times the source table was made}.  {0, 0, 0, 0} until the first arctic_hit_attributes, arctic_shade_hits(_device) or
  * arctic_trace_reflections(_device) that passes its checks.  Touches no device. */
 int arctic_hit_shading_info(ArcticRenderer *r, uint64_t *out4);
+
+/* ---- occlusion and reflections composed into the shaded frame (no counterpart in the reference: the last stage of its roadmap's "Raytracing") -------
+ * The ambient occlusion's byte plane and the reflection plane above, folded into the frame the shading pass left, IN FRONT OF the tonemapper: one
+ * streaming kernel (compose.hip: k_compose) over the handle's rows, and the one call that traces both planes and composes them.  Nothing in the
+ * passes changes: a handle that never makes these calls renders the same bytes and allocates nothing for them.
+ *
+ * THE DEFINITION.  Everything is fp32.  For every pixel of the handle's rows:
+ *   hdr  = the float HDR colour the last shading left (what arctic_read_output returns as hdr_rgb; needs ARCTIC_OPT_KEEP_FLOAT_OUTPUT);
+ *   the resident G-buffer: uv = attributes 0..1, n = attributes 8..10, world = attributes 11..13 of arctic_read_gbuffer's order, and material;
+ *   ao   = a byte, visibility on 0..255 (arctic_trace_ambient_occlusion's result);   refl = four floats (arctic_trace_reflections' result).
+ * A pixel without geometry (material == 0xFFFFFFFF, or an index the handle has no material for -- the shading pass's own test):  C = hdr.
+ * Otherwise base, metal, rough = the material's channels at uv, sampled exactly as layer 2 of the hit shading samples them: level 0, the default
+ *   sampler (full-fp32 bilinear weights, WRAP, sRGB decoded per texel before filtering), all three image layouts, whatever ARCTIC_OPT_SAMPLER says.
+ * Occlusion (ARCTIC_COMPOSE_AO):
+ *     vis = ao / 255;   ka = 1 - ao_strength * (1 - vis);   C = hdr + (ambient * base) * (ka - 1)          ambient = scene->ambient
+ *   This scales ps_main's ambient term (forward.hlsl:233) by ka and touches nothing that carries 1 - shadow.  ao == 255 or ao_strength == 0 adds
+ *   an exact zero.
+ * Reflection (ARCTIC_COMPOSE_REFLECTIONS), present only where refl.a > 0:
+ *     m  = n / len as in step 1 of the ambient occlusion: the INTERPOLATED VERTEX NORMAL the mirror ray used, not the normal-mapped one;
+ *     wo = normalize(eye - world)   (eye = scene->camera.eye);      c = max(dot(m, wo), 0);
+ *     F0 = 0.04 + (base - 0.04) * metal;      F = F0 + (1 - F0) * (1 - c)^5;
+ *     g  = (1 - rough)^2      -- a single mirror ray stands for the specular lobe only as far as the surface is smooth;
+ *     C += reflection_strength * refl.a * g * F * refl.rgb
+ *   The term is a SELECT, not a product by zero: where refl.a is 0 (or a NaN), or the pixel is NOT COVERED by the occlusion's step 1, nothing of
+ *   m or refl.rgb is looked at -- a NaN there does not reach C.
+ * Tonemap.  post_process (post_process.hlsl:59-93) of C under `settings` gives the float LDR colour and RGBA8, by the operations arctic_post_process
+ *   carries out.
+ * Not defined bit for bit (the sampler, a fifth power, the tonemapper): held to the shading pass's two standing bars against float64,
+ *   |hdr - want| / (|want| + 1e-3) <= 1e-4 and |ldr - want| <= 1e-4 (tests/test_gpu_compose.py).
+ * That the HDR plane and the resident G-buffer belong to the same frame is the caller's business when the passes are driven one by one; after
+ *   arctic_render_frame it holds by construction (the G-buffer is resolved on demand from the frame's visibility plane).
+ * ARCTIC_OPT_ANTIALIAS is not applied to the composed image: a caller runs arctic_antialias_device on it.
+ * Sharded handles compose their own rows: the kernel needs no neighbours.
+ * Refusals, in this order, before the device is touched; a refused call writes nothing.
+ *   ARCTIC_E_INVALID: a null scene, settings or block; flags 0 or with unknown bits; ao_strength outside [0, 1] or a NaN; reflection_strength
+ *     negative or not finite; reserved != 0; a null plane that a flag needs, or a float plane that is not 16-byte aligned (the byte plane may be
+ *     at any address).
+ *   ARCTIC_E_STATE: no G-buffer; ARCTIC_OPT_KEEP_FLOAT_OUTPUT off, or no shading since it was turned on or since the last resize;
+ *     ARCTIC_OPT_HDR16 = 1; with ARCTIC_COMPOSE_AO: ARCTIC_OPT_ENV_LIGHTING on, ARCTIC_OPT_TEXTURE_MIPS = 1, or a material that is not neutral
+ *     (arctic_set_material_extras) -- the ambient term of such a frame is not ambient * base at level 0, and the occlusion would scale something the
+ *     frame does not hold; it is refused, not approximated. */
+#define ARCTIC_COMPOSE_AO          1u
+#define ARCTIC_COMPOSE_REFLECTIONS 2u
+typedef struct ArcticRayCompose {   /* 32 bytes */
+    uint32_t flags;                /* ARCTIC_COMPOSE_AO | ARCTIC_COMPOSE_REFLECTIONS, at least one */
+    float    ao_strength;          /* 0..1: 0 leaves the frame as it is, 1 takes the ambient term of a closed pixel (ao = 0) away */
+    float    reflection_strength;  /* >= 0, finite */
+    float    reflection_bias;      /* arctic_pass_ray_effects only: the bias of arctic_trace_reflections */
+    uint32_t reserved[4];          /* 0 */
+} ArcticRayCompose;
+
+/* k_compose alone, on DEVICE planes the caller owns: d_ao_u8 (rows*width bytes) and d_reflection_rgba32f (rows*width*16 bytes, 16-byte aligned),
+ * row-major over the handle's rows; a plane whose flag is absent may be NULL.  d_out_rgba8: rows*width*4 bytes of device memory (4-byte aligned: ARCTIC_E_INVALID otherwise), or NULL = the
+ * handle's own buffer (arctic_read_composed).  The float LDR and the composed HDR go to the handle's own buffers.  Stream-ordered on the handle's
+ * stream: call arctic_flush() before another stream reads d_out_rgba8.  Once the handle is warm a call allocates nothing. */
+int arctic_compose_planes_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticRayCompose *compose,
+                                 const uint8_t *d_ao_u8, const float *d_reflection_rgba32f, uint8_t *d_out_rgba8);
+
+/* The one call.  With ARCTIC_COMPOSE_AO: arctic_trace_ambient_occlusion_device with `ao` and `dirs` as that call takes them, into the handle's own
+ * plane.  With ARCTIC_COMPOSE_REFLECTIONS: arctic_trace_reflections_device with the bias compose->reflection_bias, into the handle's own plane.
+ * Then k_compose on those planes.  Byte for byte what the three public calls give when made by hand.  ao and dirs may be NULL without
+ * ARCTIC_COMPOSE_AO.  Every refusal of the three calls is unchanged (the occlusion's filter on a shard and the sun map's states of the hit shading
+ * among them), and all of them come before anything is enqueued: a refused call writes nothing. */
+int arctic_pass_ray_effects(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticRayCompose *compose,
+                            const ArcticAmbientOcclusion *ao, const float *dirs, uint8_t *d_out_rgba8);
+
+/* The last composed planes, shaped like arctic_read_output: rows*width*3 floats, rows*width*3 floats, rows*width*4 bytes; any may be NULL.
+ * Synchronises.  ARCTIC_E_STATE: nothing composed yet (or not since the last resize); rgba8 asked for when the last call wrote the caller's
+ * buffer. */
+int arctic_read_composed(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8);
+
+/* The host arbiter (no handle, no GPU): the composed HDR colour of n pixels from channels the caller has sampled already -- the definition's two
+ * terms by the very functions the kernel runs, without the sampler and without the tonemapper.  Per pixel k: hdr3, base3, metal, rough, the G-buffer's
+ * normal3 (not normalised: step 1 is carried out here) and world3, ao, refl4, and geometry[k] != 0 where the pixel has geometry.  ao may be NULL
+ * without ARCTIC_COMPOSE_AO, refl4 without ARCTIC_COMPOSE_REFLECTIONS.  The same ARCTIC_E_INVALID refusals (the float plane needs no alignment
+ * beyond a float's), also for a null eye3 and a null array with n > 0; a refused call writes nothing. */
+int arctic_compose_pixels(const ArcticRayCompose *compose, const float *eye3, float ambient, uint64_t n, const float *hdr3, const float *base3,
+                          const float *metal, const float *rough, const float *normal3, const float *world3, const uint8_t *ao, const float *refl4,
+                          const uint8_t *geometry, float *out_hdr3);
+
+/* What the composition holds on this handle: out4 = {bytes of device memory (the composed RGBA8, LDR and HDR buffers, at their capacities),
+ * launches of k_compose, calls of arctic_pass_ray_effects that passed their checks, 0}.  {0, 0, 0, 0} until the first call that passes its checks.
+ * Touches no device. */
+int arctic_compose_info(ArcticRenderer *r, uint64_t *out4);
 
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
