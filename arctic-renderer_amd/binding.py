@@ -108,6 +108,13 @@ SIGNATURES = {
     "arctic_read_composed": (_i32, [_vp, _vp, _vp, _vp]),
     "arctic_compose_pixels": (_i32, [_vp, _vp, C.c_float, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "arctic_compose_info": (_i32, [_vp, _vp]),
+    "arctic_accumulate_ambient_occlusion_device": (_i32, [_vp, _scene, _vp, _vp, _vp]),
+    "arctic_accumulate_ambient_occlusion": (_i32, [_vp, _scene, _vp, _vp, _vp]),
+    "arctic_ao_history_reset": (_i32, [_vp]),
+    "arctic_read_ao_history": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "arctic_ao_history_info": (_i32, [_vp, _vp]),
+    "arctic_accumulate_pixels": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_pass_ray_effects_temporal": (_i32, [_vp, _scene, _settings, _vp, _vp, _vp, _vp, _vp]),
     "arctic_version": (_i32, []),
     # include/arctic_dist.h: the multi-GPU exchange steps
     "arctic_comm_unique_id": (_i32, [_vp, _vp, _u64]),

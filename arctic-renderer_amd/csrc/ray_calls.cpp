@@ -1,8 +1,8 @@
 // ray_calls.cpp -- the ray family of the C-ABI (include/arctic_hip.h): ray queries, refit and re-split of their structure, sun visibility, ambient
-// occlusion, hit attributes, hit shading, the reflection plane, and the composition of the two planes into the shaded frame.
+// occlusion and its temporal accumulation, hit attributes, hit shading, the reflection plane, and the composition of the two planes into the shaded frame.
 //
-// Owns, of the handle (renderer_state.h): ArcticRenderer::RayScene, AmbientOcclusion, HitScene and Compose -- nothing outside this unit touches them but
-// arctic_set_option, which writes RayScene::refit_opt.  Reads, of the handle's other state: the G-buffer planes (resolved here from the visibility
+// Owns, of the handle (renderer_state.h): ArcticRenderer::RayScene, AmbientOcclusion, AoHistory, HitScene and Compose -- nothing outside this unit touches
+// them but arctic_set_option, which writes RayScene::refit_opt, and a resize, which empties the history.  Reads, of the handle's other state: the G-buffer planes (resolved here from the visibility
 // plane when a frame was shaded from it), the shadow map, the lights, the textures, the environment, the meshes and -- the composition -- the float
 // HDR plane of the latest shading.  Enqueues on r->stream only.
 #include <algorithm>
@@ -15,6 +15,7 @@
 #include "ray_ao.h"
 #include "hit_shade.h"
 #include "compose.h"
+#include "ao_history.h"
 
 namespace {
 
@@ -614,6 +615,141 @@ int arctic_compose_info(ArcticRenderer *r, uint64_t *out4) {
     if (!r) return ARCTIC_E_INVALID;
     if (!out4) return r->fail(ARCTIC_E_INVALID, "compose_info: null");
     out4[0] = r->compose.device_bytes(); out4[1] = r->compose.launches; out4[2] = r->compose.passes; out4[3] = 0;
+    return ARCTIC_OK;
+}
+
+// ---- temporal accumulation of the occlusion plane (the definition: include/arctic_hip.h; the arithmetic: ao_history.h; the kernel: ao_history.hip) --
+namespace {
+// what the calls refuse with ARCTIC_E_INVALID for the accumulation's own sake; in, out: the planes k_ao_accumulate will read and write
+int accumulate_checks(ArcticRenderer *r, const ArcticScene *sc, const ArcticAoHistory *hist, const void *in, const void *out, AoHistoryDesc &d, const char *who) {
+    if (!valid_scene(sc)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
+    if (!hist || !in || !out) return r->fail(ARCTIC_E_INVALID, "%s: null parameters or plane", who);
+    std::memcpy(&d, hist, sizeof d);
+    if (const char *why = ao_history_refusal(&d)) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
+    return ARCTIC_OK;
+}
+// ... and with ARCTIC_E_STATE: no side effect
+int accumulate_states(ArcticRenderer *r, const char *who) {
+    int rc = gbuffer_refusal(r, who);
+    if (rc) return rc;
+    if (r->rows() != r->height)
+        return r->fail(ARCTIC_E_STATE, "%s: the history's taps need the whole frame, this handle owns %u of %u rows (its neighbours' rows are on other shards)", who, r->rows(), r->height);
+    return ARCTIC_OK;
+}
+// the G-buffer, the history sets and the launch: device pointers throughout.  The handle's state moves only behind a launch that was enqueued
+int accumulate_planes(ArcticRenderer *r, const ArcticScene *sc, const AoHistoryDesc &d, const uint8_t *d_in, uint8_t *d_out) {
+    int rc = gbuffer_in_place(r);
+    if (rc) return rc;
+    ArcticRenderer::AoHistory &A = r->ao_history;
+    const size_t plane = std::max<size_t>(r->n_tiles(), 1) * TILE_PIXELS * 16;
+    for (DevBuf *b : {&A.d_a[0], &A.d_a[1], &A.d_b[0], &A.d_b[1]})
+        if (b->cap < plane) HIPCHECK(r, b->alloc_exact(plane));   // (no headroom: the four planes are 64 bytes per pixel as the header says, 531 MB at 4K)
+    const bool have = A.valid && A.width == r->width && A.height == r->height;
+    const int from = A.cur, to = A.cur ^ 1;
+    const GBuffer g = r->gbuffer();
+    AoHistoryParams p = {};
+    p.plane_b = g.b; p.plane_c = g.c; p.plane_e = g.e;
+    p.prev_a = have ? A.d_a[from].p : nullptr; p.prev_b = have ? A.d_b[from].p : nullptr;
+    p.next_a = A.d_a[to].p; p.next_b = A.d_b[to].p;
+    p.ao_in = d_in; p.ao_out = d_out;
+    p.tiles_x = r->tiles_x; p.tiles_y = r->tiles_y; p.width = r->width; p.rows = r->rows();
+    p.d = d;
+    if (have) std::memcpy(p.P, A.proj_view, sizeof p.P);
+    HIPCHECK(r, launch_ao_accumulate(p, r->stream));
+    const ArcticCamera &c = sc->camera;
+    camera_proj_view(c.eye, c.rotation, c.aspect, c.fov_y, c.z_near_far[0], c.z_near_far[1], A.proj_view);
+    A.cur = to; A.valid = true; A.width = r->width; A.height = r->height;
+    ++A.launches; ++A.calls;
+    return ARCTIC_OK;
+}
+}  // namespace
+
+int arctic_accumulate_ambient_occlusion_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticAoHistory *hist, const uint8_t *d_ao_in_u8, uint8_t *d_ao_out_u8) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "accumulate_ambient_occlusion_device";
+    AoHistoryDesc d;
+    int rc = accumulate_checks(r, scene, hist, d_ao_in_u8, d_ao_out_u8, d, who);
+    if (rc || (rc = accumulate_states(r, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
+    return accumulate_planes(r, scene, d, d_ao_in_u8, d_ao_out_u8);
+}
+
+int arctic_accumulate_ambient_occlusion(ArcticRenderer *r, const ArcticScene *scene, const ArcticAoHistory *hist, const uint8_t *ao_in, uint8_t *ao_out) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "accumulate_ambient_occlusion";
+    AoHistoryDesc d;
+    int rc = accumulate_checks(r, scene, hist, ao_in, ao_out, d, who);
+    if (rc || (rc = accumulate_states(r, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
+    const size_t bytes = (size_t)r->rows() * r->width;
+    HIPCHECK(r, r->d_stage.ensure(std::max<size_t>(bytes, 16)));
+    HIPCHECK(r, hipMemcpyAsync(r->d_stage.p, ao_in, bytes, hipMemcpyHostToDevice, r->stream));
+    if ((rc = accumulate_planes(r, scene, d, r->d_stage.as<uint8_t>(), r->d_stage.as<uint8_t>())) != ARCTIC_OK) return rc;
+    return read_back(r, ao_out, r->d_stage, bytes, FROM_FRAME);
+}
+
+int arctic_ao_history_reset(ArcticRenderer *r) {
+    if (!r) return ARCTIC_E_INVALID;
+    r->ao_history.valid = false;   // (the planes stay: a call in flight may still write them, and the next call reuses them)
+    r->ao_history.calls = 0;
+    return ARCTIC_OK;
+}
+
+int arctic_read_ao_history(ArcticRenderer *r, float *value, float *count, float *world3, float *normal3) {
+    if (!r) return ARCTIC_E_INVALID;
+    const ArcticRenderer::AoHistory &A = r->ao_history;
+    if (!A.valid || A.width != r->width || A.height != r->height || r->rows() != r->height)
+        return r->fail(ARCTIC_E_STATE, "read_ao_history: the history is empty (no call yet, or none since the last reset or resize)");
+    int rc = select_device(r);
+    if (rc) return rc;
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    const size_t n = r->n_tiles() * TILE_PIXELS;
+    std::vector<float> a(n * 4), b(n * 4);
+    HIPCHECK(r, hipMemcpy(a.data(), A.d_a[A.cur].p, n * 16, hipMemcpyDeviceToHost));
+    HIPCHECK(r, hipMemcpy(b.data(), A.d_b[A.cur].p, n * 16, hipMemcpyDeviceToHost));
+    for (uint32_t y = 0; y < r->height; ++y)
+        for (uint32_t x = 0; x < r->width; ++x) {
+            const size_t q = ((size_t)(y / TILE) * r->tiles_x + x / TILE) * TILE_PIXELS + (y % TILE) * TILE + x % TILE, o = (size_t)y * r->width + x;
+            if (value) value[o] = a[4 * q + 3];
+            if (count) count[o] = b[4 * q + 3];
+            for (int i = 0; i < 3; ++i) {
+                if (world3) world3[3 * o + i] = a[4 * q + i];
+                if (normal3) normal3[3 * o + i] = b[4 * q + i];
+            }
+        }
+    return ARCTIC_OK;
+}
+
+int arctic_ao_history_info(ArcticRenderer *r, uint64_t *out4) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!out4) return r->fail(ARCTIC_E_INVALID, "ao_history_info: null");
+    out4[0] = r->ao_history.device_bytes(); out4[1] = r->ao_history.launches; out4[2] = r->ao_history.calls; out4[3] = 0;
+    return ARCTIC_OK;
+}
+
+int arctic_pass_ray_effects_temporal(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticRayCompose *compose,
+                                     const ArcticAmbientOcclusion *ao, const float *dirs, const ArcticAoHistory *hist, uint8_t *d_out_rgba8) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "pass_ray_effects_temporal";
+    alignas(16) static const char own_plane[16] = {};   // (the planes are the handle's own: never null, always aligned)
+    ComposeDesc d;
+    int rc = compose_checks(r, scene, settings, compose, own_plane, own_plane, d, who);
+    if (rc) return rc;
+    if (!(d.flags & COMPOSE_AO)) return r->fail(ARCTIC_E_INVALID, "%s: ARCTIC_COMPOSE_AO is not set: there is nothing to accumulate (arctic_pass_ray_effects)", who);
+    if (d_out_rgba8 && ((uintptr_t)d_out_rgba8 & 3u)) return r->fail(ARCTIC_E_INVALID, "%s: the output is not 4-byte aligned", who);
+    // every refusal of the calls below, in front of the first launch (they make them again, in their own words, to no effect)
+    AoDesc a = {};
+    if (ao) std::memcpy(&a, ao, sizeof a);
+    if (const char *why = ao_refusal(ao ? &a : nullptr, dirs)) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
+    AoHistoryDesc h;
+    if ((rc = accumulate_checks(r, scene, hist, own_plane, own_plane, h, who)) != ARCTIC_OK) return rc;
+    if ((d.flags & COMPOSE_REFLECTIONS) && !std::isfinite(d.reflection_bias)) return r->fail(ARCTIC_E_INVALID, "%s: the reflection bias is not finite", who);
+    if ((rc = compose_states(r, d, who)) != ARCTIC_OK || (rc = accumulate_states(r, who)) != ARCTIC_OK) return rc;
+    if ((d.flags & COMPOSE_REFLECTIONS) && (rc = sun_map_ready(r, who)) != ARCTIC_OK) return rc;
+    if ((rc = select_device(r)) != ARCTIC_OK) return rc;
+    if ((rc = trace_ambient_occlusion(r, scene, ao, dirs, nullptr, who)) != ARCTIC_OK) return rc;
+    if ((rc = accumulate_planes(r, scene, h, r->ao.d_out.as<uint8_t>(), r->ao.d_out.as<uint8_t>())) != ARCTIC_OK) return rc;
+    if ((d.flags & COMPOSE_REFLECTIONS) && (rc = trace_reflections(r, scene, d.reflection_bias, nullptr, who)) != ARCTIC_OK) return rc;
+    if ((rc = compose_planes(r, scene, settings, d, r->ao.d_out.as<uint8_t>(), r->hit.d_color.as<float>(), d_out_rgba8)) != ARCTIC_OK) return rc;
+    ++r->compose.passes;
     return ARCTIC_OK;
 }
 

@@ -123,6 +123,7 @@ int alloc_targets(ArcticRenderer *r) {
     r->have_gbuffer = r->have_output = r->have_vis = r->have_order = false;
     r->hdr_valid = false;
     r->compose.pixels = 0;   // (arctic_read_composed: nothing composed at this size yet)
+    r->ao_history.valid = false;   // (the occlusion's history is empty after a resize)
     r->output_filtered = false;
     return ARCTIC_OK;
 }

@@ -378,6 +378,19 @@ struct ArcticRenderer {
         bool own_rgba8 = false;
         size_t device_bytes() const { return d_rgba8.cap + d_ldr.cap + d_hdr.cap; }
     } compose;
+    // The temporal accumulation of the occlusion plane (arctic_accumulate_ambient_occlusion_device; ao_history.hip): two sets of the two history
+    // planes, tile-major like the G-buffer (n_tiles * 64 float4 each) -- a call reads set `cur` and writes the other, then `cur` moves.  Nothing is
+    // allocated before the first call that passes its checks.  valid: H is not empty (cleared by arctic_ao_history_reset and by a resize);
+    // proj_view, width, height: those of the call that wrote set `cur`
+    struct AoHistory {
+        DevBuf d_a[2], d_b[2];
+        int cur = 0;
+        bool valid = false;
+        float proj_view[16] = {};
+        uint32_t width = 0, height = 0;
+        uint64_t launches = 0, calls = 0;
+        size_t device_bytes() const { return d_a[0].cap + d_a[1].cap + d_b[0].cap + d_b[1].cap; }
+    } ao_history;
     PinnedBuf counts;               // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts

@@ -321,6 +321,35 @@ class Renderer {
     }
     // {device bytes, launches of the composition kernel, pass_ray_effects calls, 0}: all 0 until the first call that passes its checks
     [[nodiscard]] bool compose_info(uint64_t out4[4]) { return ok(arctic_compose_info(m_handle, out4)); }
+    // temporal accumulation of the occlusion plane (include/arctic_hip.h: arctic_accumulate_ambient_occlusion_device and the definition in front of it):
+    // the device byte plane d_ao_in_u8 blended into the handle's history, reprojected through the previous call's camera, into d_ao_out_u8 (it may be
+    // the same plane); in stream order on the handle's stream
+    [[nodiscard]] bool accumulate_ambient_occlusion_device(const ArcticScene &scene, const ArcticAoHistory &hist, const uint8_t *d_ao_in_u8, uint8_t *d_ao_out_u8) {
+        return ok(arctic_accumulate_ambient_occlusion_device(m_handle, &scene, &hist, d_ao_in_u8, d_ao_out_u8));
+    }
+    // the host form, synchronous
+    [[nodiscard]] bool accumulate_ambient_occlusion(const ArcticScene &scene, const ArcticAoHistory &hist, const uint8_t *ao_in, uint8_t *ao_out) {
+        return ok(arctic_accumulate_ambient_occlusion(m_handle, &scene, &hist, ao_in, ao_out));
+    }
+    // empties the history; frees nothing
+    [[nodiscard]] bool ao_history_reset() { return ok(arctic_ao_history_reset(m_handle)); }
+    // the history the last call wrote, row-major; any pointer may be nullptr
+    [[nodiscard]] bool read_ao_history(float *value, float *count, float *world3, float *normal3) { return ok(arctic_read_ao_history(m_handle, value, count, world3, normal3)); }
+    // {device bytes, launches of k_ao_accumulate, calls since the last reset, 0}
+    [[nodiscard]] bool ao_history_info(uint64_t out4[4]) { return ok(arctic_ao_history_info(m_handle, out4)); }
+    // its host arbiter: n pixels against a previous history given as row-major arrays (no handle, no GPU)
+    [[nodiscard]] static bool accumulate_pixels(const ArcticAoHistory &hist, uint64_t n, const float *world3, const float *normal3, const uint8_t *geometry, const uint8_t *cur,
+                                                const float *prev_proj_view, uint32_t width, uint32_t height, const float *prev_value, const float *prev_count,
+                                                const float *prev_world3, const float *prev_normal3, uint8_t *out_u8, float *out_value, float *out_count,
+                                                float *out_world3, float *out_normal3) {
+        return arctic_accumulate_pixels(&hist, n, world3, normal3, geometry, cur, prev_proj_view, width, height, prev_value, prev_count, prev_world3, prev_normal3, out_u8,
+                                        out_value, out_count, out_world3, out_normal3) == ARCTIC_OK;
+    }
+    // pass_ray_effects with the accumulation between the occlusion and the composition (compose.flags must hold ARCTIC_COMPOSE_AO)
+    [[nodiscard]] bool pass_ray_effects_temporal(const ArcticScene &scene, const ArcticSettings &settings, const ArcticRayCompose &compose, const ArcticAmbientOcclusion &ao,
+                                                 const float *dirs, const ArcticAoHistory &hist, uint8_t *d_out_rgba8) {
+        return ok(arctic_pass_ray_effects_temporal(m_handle, &scene, &settings, &compose, &ao, dirs, &hist, d_out_rgba8));
+    }
 
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }

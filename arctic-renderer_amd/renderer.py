@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (AO_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -329,6 +329,61 @@ class Renderer:
         out = np.zeros(4, np.uint64)
         self._check(self.L.arctic_compose_info(self.h, _ptr(out)))
         return tuple(int(x) for x in out)
+
+    # ---- temporal accumulation of the occlusion plane (include/arctic_hip.h: arctic_accumulate_ambient_occlusion_device and the definition) ------
+    def accumulate_ambient_occlusion_device(self, desc, d_ao_in_ptr, d_ao_out_ptr, max_history=32.0, normal_cos=0.9, plane_dist=0.05, min_weight=0.0, hist=None):
+        """blend the device byte plane d_ao_in_ptr (an int pointer; rows * width bytes) into the handle's history, reprojected through the previous
+        call's camera, and write the accumulated plane to d_ao_out_ptr (it may be the same plane); desc's camera is kept for the next call.
+        hist: an AO_HISTORY_DTYPE record instead of the four parameters.  Asynchronous on the handle's stream."""
+        s = self._scene(desc)
+        h = _ao_history_arguments(max_history, normal_cos, plane_dist, min_weight) if hist is None else hist
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_accumulate_ambient_occlusion_device(self.h, C.byref(s), _ptr(h), vp(d_ao_in_ptr), vp(d_ao_out_ptr)))
+
+    def accumulate_ambient_occlusion(self, desc, ao, max_history=32.0, normal_cos=0.9, plane_dist=0.05, min_weight=0.0, hist=None):
+        """the same from and to host memory: (rows, width) uint8 -> (rows, width) uint8; synchronous"""
+        s = self._scene(desc)
+        h = _ao_history_arguments(max_history, normal_cos, plane_dist, min_weight) if hist is None else hist
+        a = np.ascontiguousarray(ao, dtype=np.uint8)
+        if a.shape != (self.rows, self.width):
+            raise ArcticError(-1, f"accumulate_ambient_occlusion: expected {(self.rows, self.width)}, got {a.shape}")
+        out = np.empty_like(a)
+        self._check(self.L.arctic_accumulate_ambient_occlusion(self.h, C.byref(s), _ptr(h), _ptr(a), _ptr(out)))
+        return out
+
+    def ao_history_reset(self):
+        """empty the history: the next accumulation is a first call.  Frees nothing."""
+        self._check(self.L.arctic_ao_history_reset(self.h))
+
+    def read_ao_history(self, want=("value", "count", "world", "normal")):
+        """the history the last accumulation wrote: (value, count, world, normal) -- (rows, width) float32 twice, (rows, width, 3) float32 twice; None
+        for what was not asked for.  ArcticError (STATE) while the history is empty."""
+        n = (self.rows, self.width)
+        value = np.empty(n, np.float32) if "value" in want else None
+        count = np.empty(n, np.float32) if "count" in want else None
+        world = np.empty(n + (3,), np.float32) if "world" in want else None
+        normal = np.empty(n + (3,), np.float32) if "normal" in want else None
+        self._check(self.L.arctic_read_ao_history(self.h, _ptr(value), _ptr(count), _ptr(world), _ptr(normal)))
+        return value, count, world, normal
+
+    def ao_history_info(self):
+        """(device bytes of the two history sets, launches of the accumulation kernel, calls since the last reset, 0): all 0 until the first call"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_ao_history_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    def pass_ray_effects_temporal(self, desc, settings, dirs, reflection_bias=None, ao_strength=1.0, reflection_strength=1.0, d_out_ptr=None, read=True, n_rays=None,
+                                  pattern=None, radius=np.inf, bias=1e-3, filter=False, normal_cos=0.9, plane_dist=0.05, max_history=32.0, history_normal_cos=0.9,
+                                  history_plane_dist=0.05, min_weight=0.0):
+        """pass_ray_effects with the accumulation between the occlusion and the composition: (rows, width, 4) uint8.  read=False or a d_out_ptr
+        leaves the result on the device and returns None."""
+        s, st = self._scene(desc), self._settings(settings)
+        flags = (binding.COMPOSE_AO if dirs is not None else 0) | (binding.COMPOSE_REFLECTIONS if reflection_bias is not None else 0)
+        c = _compose_arguments(flags, ao_strength, reflection_strength, 0.0 if reflection_bias is None else reflection_bias)
+        ao, d = _ao_arguments(dirs, n_rays, pattern, radius, bias, filter, normal_cos, plane_dist) if dirs is not None else (None, None)
+        h = _ao_history_arguments(max_history, history_normal_cos, history_plane_dist, min_weight)
+        self._check(self.L.arctic_pass_ray_effects_temporal(self.h, C.byref(s), C.byref(st), _ptr(c), _ptr(ao), _ptr(d), _ptr(h), C.c_void_p(d_out_ptr) if d_out_ptr else None))
+        return self.read_composed(want=("rgba8",))[2] if read and not d_out_ptr else None
 
     def ray_scene_info(self):
         """(triangles stored, nodes, builds so far, depth) of the cached acceleration structure"""
@@ -771,6 +826,42 @@ def compose_pixels(hdr, base, metal, rough, normal, world, geometry, eye, ambien
     rc = binding.lib().arctic_compose_pixels(_ptr(c), _ptr(e), float(ambient), n, _ptr(h), _ptr(b), _ptr(m), _ptr(r), _ptr(nr), _ptr(w), _ptr(a), _ptr(rf), _ptr(g), _ptr(out))
     if rc < 0:
         raise ArcticError(rc, "compose_pixels")
+    return out
+
+
+def _ao_history_arguments(max_history, normal_cos, plane_dist, min_weight):
+    """one AO_HISTORY_DTYPE record; the library checks every value"""
+    h = np.zeros(1, AO_HISTORY_DTYPE)
+    h["max_history"], h["normal_cos"], h["plane_dist"], h["min_weight"] = max_history, normal_cos, plane_dist, min_weight
+    return h
+
+
+def accumulate_pixels(world, normal, geometry, cur, prev_proj_view=None, width=1, height=1, prev=None, max_history=32.0, normal_cos=0.9, plane_dist=0.05, min_weight=0.0,
+                      hist=None):
+    """arctic_accumulate_pixels: the temporal accumulation of include/arctic_hip.h on the host, for n pixels in any order -- world, normal (n, 3),
+    geometry (n,) bool, cur (n,) uint8; prev_proj_view: the previous call's (4, 4) matrix as frame_constants gives it, None = an empty history;
+    prev: (value, count, world, normal) of the previous call's width x height frame, as read_ao_history returns them.  Returns (byte (n,) uint8,
+    value (n,), N (n,), world (n, 3), normal (n, 3)): the output and the history entry written."""
+    f = lambda a, k: np.ascontiguousarray(a, dtype=np.float32).reshape((-1, k) if k > 1 else (-1,))
+    w, nr = f(world, 3), f(normal, 3)
+    g = np.ascontiguousarray(np.asarray(geometry) != 0, dtype=np.uint8).ravel()
+    c = np.ascontiguousarray(cur, dtype=np.uint8).ravel()
+    n = len(w)
+    if any(len(x) != n for x in (nr, g, c)):
+        raise ArcticError(-1, "accumulate_pixels: one entry of every array per pixel")
+    h = _ao_history_arguments(max_history, normal_cos, plane_dist, min_weight) if hist is None else hist
+    P = None if prev_proj_view is None else np.ascontiguousarray(prev_proj_view, dtype=np.float32).reshape(16)
+    pv = pc = pw = pn = None
+    if P is not None:
+        pv, pc, pw, pn = f(prev[0], 1), f(prev[1], 1), f(prev[2], 3), f(prev[3], 3)
+        if any(len(x) != int(width) * int(height) for x in (pv, pc, pw, pn)):
+            raise ArcticError(-1, "accumulate_pixels: the previous history is not width * height entries")
+    out = np.empty(n, np.uint8), np.empty(n, np.float32), np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+    p = (lambda a: _ptr(a) if n else None)
+    rc = binding.lib().arctic_accumulate_pixels(_ptr(h), n, p(w), p(nr), p(g), p(c), _ptr(P), int(width), int(height), _ptr(pv), _ptr(pc), _ptr(pw), _ptr(pn),
+                                                *[p(o) for o in out])
+    if rc < 0:
+        raise ArcticError(rc, "accumulate_pixels")
     return out
 
 

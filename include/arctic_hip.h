@@ -1170,6 +1170,93 @@ int arctic_compose_pixels(const ArcticRayCompose *compose, const float *eye3, fl
  * Touches no device. */
 int arctic_compose_info(ArcticRenderer *r, uint64_t *out4);
 
+/* ---- temporal accumulation of the ambient occlusion's byte plane (no counterpart in the reference) --------------------------------------------------
+ * One occlusion ray per pixel gives 0 or 255; these calls carry the estimate from frame to frame: reproject it through the PREVIOUS call's camera,
+ * reject history that belongs to another surface, blend the new byte into it.  A caller who turns the direction table every frame
+ * (ao_directions(n, P, seed = frame)) gets the quality of tens of rays per pixel for one ray and one streaming kernel (ao_history.hip:
+ * k_ao_accumulate).  Nothing in the passes or in the other ray calls changes: a handle that never makes these calls renders the same bytes and
+ * allocates nothing for them.
+ *
+ * THE DEFINITION.  Bit for bit, like the occlusion itself: fp32 throughout, one rounding per operation in the written order, no contraction,
+ * IEEE division and square root.
+ * STATE.  The handle keeps a history H of its frame: per pixel {world3, value} and {m3, count}, two float4 planes, 32 bytes per pixel, and TWO sets
+ *   of them (a call reads one and writes the other): 64 bytes per pixel, 531 MB at 3840 x 2160, allocated by the first call that passes its checks
+ *   (arctic_ao_history_info).  It also keeps the proj_view (16 floats, arctic_frame_constants' layout [col][row]) and the frame size of the call
+ *   that wrote H.  H is EMPTY before the first call, after arctic_ao_history_reset and after arctic_resize.
+ * INPUTS.  The resident G-buffer (n = attributes 8..10, world = attributes 11..13, material), `scene` (its camera gives THIS call's proj_view, kept
+ *   for the next call), the current byte plane ao_in, and ArcticAoHistory.
+ * PER PIXEL p.  cur = (float)ao_in[p];  W, H = the frame's width and height as floats.
+ *   1. m_p = n / len as in step 1 of the ambient occlusion, w_p = world.  No geometry (material == 0xFFFFFFFF) or NOT COVERED by that step:
+ *      the output byte is 255 and the entry written is all zero (count 0: never accepted as a tap).
+ *   2. H is empty:  N = 1, value = cur.
+ *   3. Otherwise reproject with the PREVIOUS call's matrix P (the vertex kernel's product order, setup_triangle's projection):
+ *        c[i] = ((P[i]*w0 + P[4+i]*w1) + P[8+i]*w2) + P[12+i]
+ *        reject everything unless c3 > 0 and c0, c1, c3 are finite;
+ *        iw = 1 / c3;  nx = c0*iw;  ny = c1*iw;  sx = (nx + 1) * (0.5*W);  sy = (1 - ny) * (0.5*H)
+ *        gx = sx - 0.5;  gy = sy - 0.5;  ix = floor(gx);  iy = floor(gy);  ax = gx - ix;  ay = gy - iy
+ *        reject everything, tested in float before any conversion, unless -1 <= ix <= W-1 and -1 <= iy <= H-1.
+ *      "Reject everything": N = 1, value = cur, as in step 5.
+ *   4. The four taps (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1), in this order, weigh (1-ax)*(1-ay), ax*(1-ay), (1-ax)*ay, ax*ay.
+ *      A tap q is ACCEPTED iff it lies inside the frame, count_q > 0 and the occlusion filter's test holds on the STORED m_q, w_q of the previous
+ *      call:  dot(m_p, m_q) >= normal_cos  and  |dot(m_p, w_q - w_p)| <= plane_dist.
+ *      A rejected tap's weight is 0 and its history is not looked at -- a SELECT, not a product by zero: a NaN there does not reach the result.
+ *        S = ((k0 + k1) + k2) + k3;   V, C = the same ordered sums of k*value_q and k*count_q.
+ *   5. !(S > min_weight):  N = 1, value = cur.
+ *   6. Otherwise  hv = V / S;  hn = C / S;  N = min(hn + 1, max_history);  a = 1 / N;  value = hv + (cur - hv) * a.
+ *   7. The output byte is (uint8)min(max(floor(value + 0.5), 0), 255); the entry written is {w_p, value}, {m_p, N}.
+ * KNOWN LIMITS, stated and not worked around.  There are no per-object motion vectors: a moving object is handled only as far as the two
+ *   rejections catch it.  Only the occlusion plane is accumulated; the mirror reflection is one deterministic ray per pixel and is not.
+ * Refusals, in this order; a refused call writes nothing and leaves H as it was.
+ *   ARCTIC_E_INVALID: a null scene, hist or plane; max_history outside [1, 65536] or a NaN; normal_cos not finite; plane_dist negative or a NaN;
+ *     min_weight outside [0, 1) or a NaN; reserved != 0.
+ *   ARCTIC_E_STATE: no G-buffer; a handle that does not own the whole frame (the rule of the occlusion's filter: the taps' rows are elsewhere). */
+typedef struct ArcticAoHistory {   /* 32 bytes */
+    float    max_history;   /* N's cap: 1 <= max_history <= 65536, finite; 1 = no accumulation */
+    float    normal_cos;    /* the acceptance test's bound on dot(m_p, m_q), finite */
+    float    plane_dist;    /* the acceptance test's bound on |dot(m_p, w_q - w_p)|, >= 0 */
+    float    min_weight;    /* history is used only if the accepted taps' weight S > min_weight; in [0, 1) */
+    uint32_t reserved[4];   /* 0 */
+} ArcticAoHistory;
+
+/* One call of the definition on DEVICE planes the caller owns, rows*width bytes each, row-major.  d_ao_in_u8 == d_ao_out_u8 is allowed (a pixel
+ * reads only its own current byte); the planes may not overlap otherwise.  Stream-ordered on the handle's stream.  The first call that passes its
+ * checks allocates the two history sets (64 bytes per pixel); from then on a call allocates nothing and does not synchronise. */
+int arctic_accumulate_ambient_occlusion_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticAoHistory *hist, const uint8_t *d_ao_in_u8,
+                                               uint8_t *d_ao_out_u8);
+
+/* The host form: ao_in and ao_out are rows*width bytes of host memory (they may be the same).  Synchronous. */
+int arctic_accumulate_ambient_occlusion(ArcticRenderer *r, const ArcticScene *scene, const ArcticAoHistory *hist, const uint8_t *ao_in, uint8_t *ao_out);
+
+/* Empties H (the next call is a first call) and sets the calls counter to 0.  Frees nothing, touches no device. */
+int arctic_ao_history_reset(ArcticRenderer *r);
+
+/* The history the last call WROTE, row-major: value and count rows*width floats, world3 and normal3 (the stored m) rows*width*3 floats.  Any
+ * pointer may be NULL.  Synchronises.  ARCTIC_E_STATE while H is empty. */
+int arctic_read_ao_history(ArcticRenderer *r, float *value, float *count, float *world3, float *normal3);
+
+/* What the accumulation holds on this handle: out4 = {bytes of device memory (the two history sets, at their capacities), launches of
+ * k_ao_accumulate, calls since the last reset, 0}.  {0, 0, 0, 0} until the first call that passes its checks.  Touches no device. */
+int arctic_ao_history_info(ArcticRenderer *r, uint64_t *out4);
+
+/* The host arbiter (no handle, no GPU): the definition for n pixels in any order, by the very functions the kernel runs.  Per pixel k: world3,
+ * normal3 (not normalised: step 1 is carried out here), geometry[k] != 0 where the pixel has geometry, and cur[k], its current byte.
+ * prev_proj_view: the previous call's matrix, NULL = the history is empty; width, height: the frame (1..16384 each); prev_value, prev_count,
+ * prev_world3, prev_normal3: the previous history as arctic_read_ao_history returns it (ignored while prev_proj_view is NULL).  Outputs: the byte
+ * (required with n > 0), and -- each may be NULL -- value, N, and the stored w_p and m_p (all zero for step 1's pixels).  No output may overlap
+ * the previous history.  The same ARCTIC_E_INVALID refusals, also for a frame size out of range and a null array that is needed. */
+int arctic_accumulate_pixels(const ArcticAoHistory *hist, uint64_t n, const float *world3, const float *normal3, const uint8_t *geometry, const uint8_t *cur,
+                             const float *prev_proj_view, uint32_t width, uint32_t height, const float *prev_value, const float *prev_count,
+                             const float *prev_world3, const float *prev_normal3, uint8_t *out_u8, float *out_value, float *out_count, float *out_world3,
+                             float *out_normal3);
+
+/* arctic_pass_ray_effects with the accumulation between the occlusion and k_compose: arctic_trace_ambient_occlusion_device into the handle's own
+ * plane, arctic_accumulate_ambient_occlusion_device on that plane in place, the reflection plane if ARCTIC_COMPOSE_REFLECTIONS is set, then
+ * k_compose.  Requires ARCTIC_COMPOSE_AO (ARCTIC_E_INVALID without it).  Byte for byte the public calls made by hand.  Every refusal of those calls
+ * is unchanged and comes before anything is enqueued: a refused call writes nothing and leaves H as it was.  arctic_pass_ray_effects itself is
+ * what it was. */
+int arctic_pass_ray_effects_temporal(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticRayCompose *compose,
+                                     const ArcticAmbientOcclusion *ao, const float *dirs, const ArcticAoHistory *hist, uint8_t *d_out_rgba8);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row

@@ -11,7 +11,7 @@ import tempfile
 
 EXACT = ["-ffp-contract=off"]
 FLAGS = {"shade": EXACT + ["-mllvm", "-disable-machine-licm"], "env_light": [], "exchange": [], "antialias": []}
-DEFAULT = ["shade", "geometry", "trace", "ray_refit", "ray_resplit", "ray_ao", "hit_shade", "skin", "morph", "antialias", "texture_mips", "env_light", "exchange"]
+DEFAULT = ["shade", "geometry", "trace", "ray_refit", "ray_resplit", "ray_ao", "hit_shade", "compose", "skin", "morph", "antialias", "texture_mips", "env_light", "exchange"]
 
 
 def isa(tree, name, out):
