@@ -76,6 +76,7 @@ SIGNATURES = {
     "arctic_read_cull_counts": (_i32, [_vp, _i32, _vp]),
     "arctic_owner_grid": (_i32, [_u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp]),
     "arctic_owner_visit": (_i32, [_u32, _u32, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "arctic_cluster_bounds": (_i32, [_vp, _u64, _vp, _u64, _vp, _vp]),
     "arctic_set_option": (_i32, [_vp, _u32, _i64]),
     "arctic_read_env_lighting": (_i32, [_vp, _vp, _vp, _u32, _vp, _vp]),
     "arctic_read_material_mip": (_i32, [_vp, _u32, _u32, _vp, _vp]),

@@ -435,7 +435,7 @@ hipError_t launch_vertex(const ObjectRec *objs, const uint32_t *block_obj, const
                          uint32_t n_blocks, const GeomParams &gp, XVert *xv, int clip_only, uint32_t *counters /*zeroed here for k_setup*/,
                          unsigned long long *clear, unsigned long long clear_value, size_t clear_count /*the pass's target, cleared in the same launch*/,
                          uint32_t *zero, size_t zero_count /*the bin counters of an owned raster, zeroed in the same launch*/,
-                         const float *block_bounds /*6 floats per block: object-space box of every cluster that uses a vertex of the block, or null (no culling)*/, hipStream_t s);
+                         const float *block_bounds /*6 floats per block: the union of the object-space boxes of the clusters that read a vertex of the block (renderer.cpp: cluster_bounds), or null (no culling)*/, hipStream_t s);
 hipError_t launch_setup(const ObjectRec *objs, const uint32_t *block_obj, const uint32_t *block_first, uint32_t n_blocks,
                         const GeomParams &gp, const XVert *xv, SetupRec *recs, RasterRec *rrecs, uint32_t *rec_of /*8 per source triangle*/,
                         uint2 *items, uint32_t item_cap, uint32_t rec_cap, uint32_t *counters /*records, items, overflow, clip-list length: zeroed by launch_vertex*/,

@@ -230,14 +230,22 @@ __device__ __forceinline__ void normalize3(const float *v, float *o) {
 // Cluster culling (round 5; no counterpart in the reference, which hands every triangle to the hardware's own clipper and culler,
 // forward_pass.cpp:212-224).  bb = {min xyz, max xyz} in object space of the positions a workgroup's triangles use (renderer.cpp:
 // cluster_bounds).  True only when NO triangle with its vertices in the box can touch a pixel this pass keeps: all eight corners, transformed
-// with the products k_vertex uses, lie beyond ONE plane -- near, far, or a side of the scissor rectangle `strict` pixels further out -- by more
+// with the products k_vertex uses, lie beyond ONE plane -- near, far, or a side of the scissor rectangle one pixel further out -- by more
 // than the rounding those two products can accumulate (E x the sum of the magnitudes of their terms; the products' own bound is ~5e-7 of
 // it).  The planes are half-spaces of clip space (x - x_l w < 0 ...), so no corner needs w > 0: whatever part of a triangle is drawn has
 // w > 0 (setup_triangle, the clipper's near plane) and lies in the same half-space, i.e. projects outside the scissor.  A lane takes corner
 // lane & 7; every wave of the workgroup reaches the same answer from the same numbers.  NaN or infinite bounds (renderer.cpp stores
 // them for clusters it cannot bound) compare false everywhere: never culled.
-// strict = 2 for k_vertex's vertex blocks, whose boxes contain the boxes of every cluster that uses one of their vertices: a block is
-// skipped only if each of those clusters is skipped by k_setup's test with strict = 1 (twice the margins on a larger box).
+// strict = 1 for k_setup's clusters, strict = 2 for k_vertex's vertex blocks: the SAME planes, twice the rounding margin E.  A block's box
+// contains the box of every cluster that reads one of its vertices (cluster_bounds makes it as their union; tests/test_cluster_bounds.py
+// holds the host to that), and with one set of planes the test is monotone: if a box B is beyond a plane with strict = 2, every box b inside
+// B is beyond it with strict = 1.  The corners of b are convex combinations of B's and a plane's left-hand side is affine in the corner, so it
+// is past B's threshold at b's corners too; the threshold is E x ac(box), ac does not decrease with the box, and the factor 2 on E is more than
+// the two evaluations' roundings (5e-7 ac each) can differ by.  So a block is skipped only if k_setup skips every cluster that would read its
+// vertices.  The scissor's sides are moved out by the same one pixel for both: planes `strict` pixels out, as they were, are two half-spaces
+// through the eye of which neither holds the other -- in front of the eye the one further out is the smaller, BEHIND the eye it is the larger --
+// so a box with a corner behind the eye in the pixel-wide wedge between them was skipped as a block and kept as a cluster
+// (tests/test_gpu_cluster_cull.py: test_reused_handles_box_through_the_eye_plane).
 __device__ __forceinline__ bool box_outside(const float *__restrict__ bb, const float *__restrict__ trs, const GeomParams &gp, float strict) {
     const uint32_t k = threadIdx.x & 7u;
     const float lo0 = bb[0], lo1 = bb[1], lo2 = bb[2], hi0 = bb[3], hi1 = bb[4], hi2 = bb[5];
@@ -252,8 +260,8 @@ __device__ __forceinline__ bool box_outside(const float *__restrict__ bb, const 
     for (int i = 0; i < 4; ++i) ac[i] = ((fabsf(c[i]) * aw[0] + fabsf(c[4 + i]) * aw[1]) + fabsf(c[8 + i]) * aw[2]) + fabsf(c[12 + i]) * aw[3];
     const float E = 4.0e-6f * strict, ex = E * ac[0], ey = E * ac[1], ez = E * ac[2], ew = E * ac[3];
     const float hx = 0.5f * gp.vp_w, hy = 0.5f * gp.vp_h;   // setup_triangle: X = (x / w + 1) hx, Y = (1 - y / w) hy
-    const float xl = ((float)gp.sc_x0 - strict) / hx - 1.0f, xr = ((float)gp.sc_x1 + strict) / hx - 1.0f;
-    const float yt = 1.0f - ((float)gp.sc_y0 - strict) / hy, yb = 1.0f - ((float)gp.sc_y1 + strict) / hy;
+    const float xl = ((float)gp.sc_x0 - 1.0f) / hx - 1.0f, xr = ((float)gp.sc_x1 + 1.0f) / hx - 1.0f;
+    const float yt = 1.0f - ((float)gp.sc_y0 - 1.0f) / hy, yb = 1.0f - ((float)gp.sc_y1 + 1.0f) / hy;
     const bool in_near = !(clip[2] < -ez), in_far = !(clip[2] - clip[3] > ez + ew);
     const bool in_left = !(clip[0] - xl * clip[3] < -(ex + fabsf(xl) * ew)), in_right = !(clip[0] - xr * clip[3] > ex + fabsf(xr) * ew);
     const bool in_top = !(clip[1] - yt * clip[3] > ey + fabsf(yt) * ew), in_bottom = !(clip[1] - yb * clip[3] < -(ey + fabsf(yb) * ew));
@@ -273,7 +281,8 @@ __global__ __launch_bounds__(256) void k_vertex(const ObjectRec *__restrict__ ob
     if (blockIdx.x == 0 && threadIdx.x < N_GEO_COUNTERS && !((gp.raster_flags & 2) && threadIdx.x == 6)) counters[threadIdx.x] = 0;
     const ObjectRec &ob = objs[block_obj[blockIdx.x]];
     uint32_t vi = block_first[blockIdx.x] + threadIdx.x;
-    // vertices only triangles of culled clusters use are not transformed: nothing will read them (box_outside)
+    // a skipped block's vertices are not transformed and their XVert slots keep whatever they held: every cluster that reads one of them is
+    // skipped by k_setup, because the block's box contains that cluster's box (box_outside's comment; renderer.cpp: cluster_bounds)
     const bool outside = bounds && box_outside(bounds + 6u * blockIdx.x, ob.trs, gp, 2.0f);   // (by every lane: the corners are spread over them)
     const bool live = vi < ob.n_vertices && !outside;
     if (outside && (gp.raster_flags & 2) && threadIdx.x == 0) atomicAdd(&counters[6], 1u);

@@ -33,40 +33,45 @@ Markers g_markers;
 
 namespace {
 
-// Object-space boxes for geometry.hip's box_outside, made once per mesh on the host.  tbounds[c] = {min xyz, max xyz} of the positions
-// the triangles [c * SETUP_THREADS, (c + 1) * SETUP_THREADS) use -- one workgroup of k_setup --, vbounds[b] = the union of the boxes
-// of every TRIANGLE that uses one of the vertices [256 b, 256 b + 256) -- one workgroup of k_vertex: a vertex may be skipped only when
-// all its triangles are.  Triangles with an index out of range draw nothing (load_indices) and bound nothing; a block that holds a
-// position that is not finite, or no triangle at all, gets an infinite box (never culled).
+// Object-space boxes for geometry.hip's box_outside, made once per mesh on the host (arctic_cluster_bounds is this function).
+// tbounds[c] = {min xyz, max xyz} of the positions the valid triangles [c * SETUP_THREADS, (c + 1) * SETUP_THREADS) use -- one workgroup of
+// k_setup.  vbounds[b] = the union of tbounds[t / SETUP_THREADS] over every valid triangle t that uses one of the vertices [256 b, 256 b + 256)
+// -- one workgroup of k_vertex --, made in a second pass over the finished tbounds: a vertex block's box CONTAINS the box of every cluster
+// that reads one of its vertices, which is what lets k_vertex skip it (box_outside's comment has the argument).  The union of the boxes of
+// those TRIANGLES alone is smaller than their clusters' boxes and is not enough.
+// Triangles with an index out of range draw nothing (load_indices) and bound nothing.  A cluster with a position that is not finite, or with no
+// valid triangle, gets an infinite box (never culled); a block that touches such a cluster, or that no valid triangle uses, gets one too.
 void cluster_bounds(const ArcticVertex *v, uint32_t n_vertices, const uint32_t *ind, uint32_t n_indices, std::vector<float> &tb, std::vector<float> &vb) {
     const uint32_t n_tri = n_indices / 3, n_tb = (n_tri + SETUP_THREADS - 1) / SETUP_THREADS, n_vb = (n_vertices + 255) / 256;
     const float inf = std::numeric_limits<float>::infinity();
     tb.assign((size_t)n_tb * 6, 0.0f); vb.assign((size_t)n_vb * 6, 0.0f);
     for (uint32_t b = 0; b < n_tb; ++b) for (int k = 0; k < 3; ++k) { tb[6 * b + k] = inf; tb[6 * b + 3 + k] = -inf; }
     for (uint32_t b = 0; b < n_vb; ++b) for (int k = 0; k < 3; ++k) { vb[6 * b + k] = inf; vb[6 * b + 3 + k] = -inf; }
-    std::vector<char> bad_t(n_tb, 0), bad_v(n_vb, 0);
-    for (uint32_t t = 0; t < n_tri; ++t) {
-        const uint32_t i[3] = {ind[3 * t], ind[3 * t + 1], ind[3 * t + 2]};
-        if (!(i[0] < n_vertices && i[1] < n_vertices && i[2] < n_vertices)) continue;
-        float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
-        bool finite = true;
-        for (int j = 0; j < 3; ++j) for (int k = 0; k < 3; ++k) {
-            const float p = v[i[j]].position[k];
-            finite = finite && std::isfinite(p);
-            lo[k] = std::min(lo[k], p); hi[k] = std::max(hi[k], p);
-        }
-        const auto grow = [&](std::vector<float> &box, std::vector<char> &bad, uint32_t b) {
-            if (!finite) bad[b] = 1;
-            for (int k = 0; k < 3; ++k) { box[6 * b + k] = std::min(box[6 * b + k], lo[k]); box[6 * b + 3 + k] = std::max(box[6 * b + 3 + k], hi[k]); }
-        };
-        grow(tb, bad_t, t / SETUP_THREADS);
-        for (int j = 0; j < 3; ++j) if (j == 0 || (i[j] / 256 != i[0] / 256 && (j == 1 || i[j] / 256 != i[1] / 256))) grow(vb, bad_v, i[j] / 256);
-    }
-    const auto finish = [&](std::vector<float> &box, const std::vector<char> &bad, uint32_t n) {
-        for (uint32_t b = 0; b < n; ++b)
-            if (bad[b] || !(box[6 * b] <= box[6 * b + 3])) for (int k = 0; k < 3; ++k) { box[6 * b + k] = -inf; box[6 * b + 3 + k] = inf; }
+    const auto valid = [&](uint32_t t) { return ind[3 * t] < n_vertices && ind[3 * t + 1] < n_vertices && ind[3 * t + 2] < n_vertices; };
+    const auto open_unless_bounded = [&](std::vector<float> &box, uint32_t b, bool bad) {   // (an untouched box still has min = inf > max = -inf)
+        if (bad || !(box[6 * b] <= box[6 * b + 3])) for (int k = 0; k < 3; ++k) { box[6 * b + k] = -inf; box[6 * b + 3 + k] = inf; }
     };
-    finish(tb, bad_t, n_tb); finish(vb, bad_v, n_vb);
+    std::vector<char> bad_t(n_tb, 0);
+    for (uint32_t t = 0; t < n_tri; ++t) {
+        if (!valid(t)) continue;
+        const uint32_t c = t / SETUP_THREADS;
+        for (int j = 0; j < 3; ++j) for (int k = 0; k < 3; ++k) {
+            const float p = v[ind[3 * t + j]].position[k];
+            if (!std::isfinite(p)) bad_t[c] = 1;
+            tb[6 * c + k] = std::min(tb[6 * c + k], p); tb[6 * c + 3 + k] = std::max(tb[6 * c + 3 + k], p);
+        }
+    }
+    for (uint32_t c = 0; c < n_tb; ++c) open_unless_bounded(tb, c, bad_t[c] != 0);
+    // second pass: every box of tb is now final, finite or {-inf, inf}; min / max carry an infinite box into the block's
+    for (uint32_t t = 0; t < n_tri; ++t) {
+        if (!valid(t)) continue;
+        const uint32_t c = t / SETUP_THREADS;
+        for (int j = 0; j < 3; ++j) {
+            const uint32_t b = ind[3 * t + j] / 256;
+            for (int k = 0; k < 3; ++k) { vb[6 * b + k] = std::min(vb[6 * b + k], tb[6 * c + k]); vb[6 * b + 3 + k] = std::max(vb[6 * b + 3 + k], tb[6 * c + 3 + k]); }
+        }
+    }
+    for (uint32_t b = 0; b < n_vb; ++b) open_unless_bounded(vb, b, false);
 }
 
 }  // namespace
@@ -206,7 +211,7 @@ int upload_pass_tables(ArcticRenderer *r, PassTables &T, DevBuf &d_xverts, hipSt
 // A depth-only target other than the sun's map: one face of a shadow-casting point light (pass_point_shadows).  It is drawn like the
 // sun's map -- front faces culled, depth LESS, cleared to 1.0, small triangles by k_setup -- with the shadow pass's scratch (geo[1],
 // tables[1]), but counts into slots of its own, so that arctic_stats and arctic_read_cull_counts keep describing the sun's pass; and
-// it never takes block owners, a sharded map or k_vertex's block culling (a vertex block's box is made of triangle boxes)
+// it never takes block owners, a sharded map or k_vertex's block culling (left off while a vertex block's box was made of triangle boxes, ADVICE.md, and not measured with it since)
 constexpr uint32_t CUBE_COUNTER_SET = 4;   // its set of N_GEO_COUNTERS device counters
 constexpr uint32_t CUBE_COUNT_WORDS = 8;   // pinned words per face: [0] records, [1] work items, [2] overflow flag, [4] items of the atomic rasteriser (k_raster)
 struct DepthTarget {
@@ -1902,6 +1907,19 @@ int arctic_owner_visit(uint32_t width, uint32_t height, uint32_t row_begin, uint
         int lrow;
         local_tile_rows[j] = owner_tile_row(*block_row, j, (int)tile_y0, (int)tiles_y, bt, (int)shard_count, (int)shard_index, lrow) ? lrow : -1;
     }
+    return ARCTIC_OK;
+}
+
+// the culling boxes of a mesh as plain numbers (a pure host function: the very cluster_bounds arctic_create_mesh keeps the handle's boxes from;
+// tests/test_cluster_bounds.py holds it to its definition and to "a vertex block's box contains its clusters' boxes")
+int arctic_cluster_bounds(const ArcticVertex *vertices, uint64_t n_vertices, const uint32_t *indices, uint64_t n_indices, float *tbounds_out, float *vbounds_out) {
+    if ((!vertices && n_vertices) || (!indices && n_indices) || n_indices % 3 != 0) return ARCTIC_E_INVALID;
+    if (n_vertices > 0x7FFFFFFFull || n_indices > 0xFFFFFFF0ull) return ARCTIC_E_CAPACITY;   // (arctic_create_mesh's limits)
+    std::vector<float> tb, vb;
+    cluster_bounds(vertices, (uint32_t)n_vertices, indices, (uint32_t)n_indices, tb, vb);
+    if ((!tbounds_out && !tb.empty()) || (!vbounds_out && !vb.empty())) return ARCTIC_E_INVALID;
+    if (!tb.empty()) std::memcpy(tbounds_out, tb.data(), tb.size() * sizeof(float));
+    if (!vb.empty()) std::memcpy(vbounds_out, vb.data(), vb.size() * sizeof(float));
     return ARCTIC_OK;
 }
 

@@ -114,6 +114,11 @@ class Renderer {
         }
         return true;
     }
+    // the culling boxes create_mesh keeps for a mesh (arctic_cluster_bounds: host only, no handle): ceil(n_indices / 3 / 256) cluster boxes and
+    // ceil(n_vertices / 256) vertex-block boxes of six floats, each block's box containing the boxes of the clusters that read its vertices
+    [[nodiscard]] static bool cluster_bounds(const Vertex *vertices, uint64_t n_vertices, const uint32_t *indices, uint64_t n_indices, float *tbounds_out, float *vbounds_out) {
+        return arctic_cluster_bounds(vertices, n_vertices, indices, n_indices, tbounds_out, vbounds_out) == ARCTIC_OK;
+    }
     // skeletal skinning (include/arctic_hip.h; no counterpart in the reference, whose meshes are rigid): a skin -- one SkinVertex per vertex of a
     // mesh that exists, nullptr detaches it --, then a pose: n_joints matrices of 16 floats in glm memory order, nullptr / 0 = the bind pose.
     // A pose belongs to the mesh.  false = invalid records / matrices / index (the mesh stays as it was), or a pose without a skin

@@ -896,6 +896,19 @@ def point_shadow_matrices(light):
     return out
 
 
+def cluster_bounds(vertices, indices):
+    """arctic_cluster_bounds: the culling boxes create_mesh keeps for this mesh, on the host -- (tbounds (ceil(triangles / 256), 6), vbounds
+    (ceil(vertices / 256), 6)) float32, {min xyz, max xyz} each; every vertex block's box contains the boxes of the clusters that read it"""
+    v = np.ascontiguousarray(vertices, dtype=VERTEX_DTYPE)
+    i = np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+    tb, vb = np.empty(((len(i) // 3 + 255) // 256, 6), np.float32), np.empty(((len(v) + 255) // 256, 6), np.float32)
+    rc = binding.lib().arctic_cluster_bounds(_ptr(v) if len(v) else None, len(v), _ptr(i) if len(i) else None, len(i), _ptr(tb) if len(tb) else None,
+                                             _ptr(vb) if len(vb) else None)
+    if rc < 0:
+        raise ArcticError(rc, "cluster_bounds")
+    return tb, vb
+
+
 def frame_constants(desc):
     """proj_view, light_proj_view ([col][row]) and sun_dir exactly as the library builds them."""
     s = desc.fill(CScene())

@@ -1267,6 +1267,20 @@ int arctic_owner_grid(uint32_t width, uint32_t height, uint32_t row_begin, uint3
 int arctic_owner_visit(uint32_t width, uint32_t height, uint32_t row_begin, uint32_t row_end, uint32_t band_rows, uint32_t shard_index, uint32_t shard_count,
                        uint32_t grid_row, uint32_t *block_row, int32_t *local_tile_rows);
 
+/* The object-space boxes of ARCTIC_OPT_CLUSTER_CULL as plain numbers -- a pure host function, no device, no handle: the function
+   arctic_create_mesh makes a mesh's boxes with.  Triangle t is indices[3 t .. 3 t + 2]; it is VALID when its three indices are below n_vertices
+   (any other triangle draws nothing and bounds nothing).  A box is six floats {min x, min y, min z, max x, max y, max z}; the infinite box is
+   {-inf, -inf, -inf, inf, inf, inf} and is never skipped.
+     tbounds_out: ceil(n_indices / 3 / 256) boxes.  Box c bounds the positions of the valid triangles 256 c .. 256 c + 255 (a cluster: one workgroup
+       of the set-up kernel).  Infinite if one of those positions is not finite, or if the cluster has no valid triangle.
+     vbounds_out: ceil(n_vertices / 256) boxes.  Box b is the union of tbounds[t / 256] over every valid triangle t that uses one of the vertices
+       256 b .. 256 b + 255 (a vertex block: one workgroup of the vertex kernel) -- so it CONTAINS the box of every cluster that reads one of the
+       block's vertices, and is infinite when one of them is.  Infinite as well if no valid triangle uses the block.
+   min and max of floats round nothing: both tables are exact.  An empty index list or vertex list is accepted (no clusters / no blocks).
+   ARCTIC_E_INVALID (nothing written): a null array with a count above 0, an index count that is no multiple of 3, a null output for a table that
+   is not empty.  ARCTIC_E_CAPACITY (nothing written): more than 2^31 - 1 vertices or 2^32 - 16 indices, arctic_create_mesh's limits. */
+int arctic_cluster_bounds(const ArcticVertex *vertices, uint64_t n_vertices, const uint32_t *indices, uint64_t n_indices, float *tbounds_out, float *vbounds_out);
+
 /* library/ABI version: major*10000 + minor*100 + patch */
 int arctic_version(void);
 

@@ -12,6 +12,8 @@ import copy
 import numpy as np
 import pytest
 
+import cluster_cull_cases as CC
+
 pytestmark = pytest.mark.gpu
 
 COUNT = 1024     # ARCTIC_OPT_DEBUG bit 10: count what was skipped
@@ -181,3 +183,188 @@ def test_option_is_validated(pkg, hip):
     with pytest.raises(hip.ArcticError):
         r.cull_counts(False)                # nothing counted yet
     r.close()
+
+
+# ---- reused handles: what a skipped vertex block leaves in its slots is an EARLIER pass's coordinates --------------------------------------
+# The tests above make a fresh handle per camera (a skipped block's slots then hold nothing plausible, or the very values the unculled run left in
+# recycled memory) or move a quad of 6 pixels.  Here three handles -- cluster_cull 0, 1 and 3 -- live through a whole sequence of cameras or suns
+# that differ by large steps, with meshes of many clusters and blocks that span hundreds of pixels, as generated and with their triangles
+# permuted: a block skipped while a kept cluster still reads it shows the previous camera's triangle (tests/test_cluster_bounds.py counts, on
+# the CPU, how many such reads each sequence has under a rule that allows them).  Everything is compared bit for bit with the cull-0 handle.
+CULLS = (0, 1, 3)
+
+
+class Mismatches:
+    """every comparison of a sequence, so that a failure names each step and how many elements differ"""
+
+    def __init__(self):
+        self.found = []
+
+    def compare(self, where, want, got):
+        for name, a, b in zip(("plane 0", "plane 1", "plane 2", "plane 3"), want, got):
+            assert a.shape == b.shape
+            n = int((a != b).sum())
+            if n:
+                self.found.append(f"{where}, {name}: {n} of {a.size} elements differ")
+
+    def check(self):
+        for line in self.found:
+            print(line)
+        assert not self.found, f"{len(self.found)} comparisons differ from the unculled handle's; the first: {self.found[0]}"
+
+
+def _planes(r, want=("attrs", "material", "depth", "tri")):
+    return [np.ascontiguousarray(x).view(np.uint32).copy() for x in r.read_gbuffer(want=want) if x is not None]
+
+
+@pytest.fixture(scope="module")
+def hall(pkg):
+    sc = pkg.scenes.config3(scale=0.5)
+    return {False: sc, True: CC.permuted_scene(sc)}
+
+
+def _handles(hip, sc, **options):
+    out = []
+    for cull in CULLS:
+        r = sc.upload(hip.Renderer(sc.width, sc.height, sc.shadow_size, sc.max_lights))
+        for k, v in dict(options, cluster_cull=cull, debug=COUNT).items():
+            r.set_option(k, v)
+        out.append(r)
+    return out
+
+
+@pytest.mark.parametrize("permute", [False, True], ids=["as-generated", "permuted"])
+def test_reused_handles_small_quad(pkg, hip, permute):
+    """one 48 x 48 quad that fills camera A's frame (18 clusters, 10 vertex blocks), pass_gbuffer on the same table set for A, A tilted up, A, A
+    raised, A, A raised and moved back: all four planes of the G-buffer"""
+    S = pkg.scenes
+    mats = S.make_material_textures(np.random.default_rng(7), 64)
+    v, i = CC.permuted_meshes([CC.big_quad(S)])[0] if permute else CC.big_quad(S)
+    rs = [hip.Renderer(CC.QUAD_W, CC.QUAD_H, 0, 16) for _ in CULLS]
+    for r, cull in zip(rs, CULLS):
+        r.create_material(*mats); r.create_mesh(v, i, 0)
+        r.set_option("cluster_cull", cull); r.set_option("debug", COUNT)
+    m = Mismatches()
+    for k, cam in enumerate(CC.QUAD_CAMERAS):
+        desc = CC.quad_desc(S, cam)
+        out = []
+        for r in rs:
+            r.pass_gbuffer(desc)
+            out.append(_planes(r))
+        drawn = float((out[0][3] != 0xFFFFFFFF).mean())
+        assert drawn > (0.75 if cam is CC.CAMERA_A else 0.05), (k, drawn)         # A sees the whole quad (0.82 of its frame); every other camera still sees part of it
+        for cull, got in zip(CULLS[1:], out[1:]):
+            m.compare(f"camera {k}, cluster_cull {cull}", out[0], got)
+        n = rs[2].cull_counts(False)
+        print(f"camera {k}: {drawn:.2f} of the frame drawn; cluster_cull 3 skips {n[1]} of {n[0]} clusters and {n[3]} of {n[2]} vertex blocks")
+        if cam is CC.CAMERA_A:
+            assert n[1] == 0 and n[3] == 0
+        elif not permute:      # (a block of the permuted quad is read by every cluster: its box is the quad's, and the quad is in view)
+            assert n[3] >= 1 and n[1] >= 1, (k, n)
+    for r in rs:
+        r.close()
+    m.check()
+
+
+@pytest.mark.parametrize("in_flight", [1, 2, 3])
+@pytest.mark.parametrize("permute", [False, True], ids=["as-generated", "permuted"])
+def test_reused_handles_whole_frames(pkg, hip, hall, permute, in_flight):
+    """config 3 at 0.5, render_frame three times per camera -- so that every table set of the frames in flight has held the previous camera --
+    for the camera turned on the spot by large steps: the RGBA8 frame each time, the triangle and depth planes after each camera's last frame;
+    the second camera both through the visibility path (which reads the transformed vertices' attributes as well) and through the G-buffer"""
+    sc = hall[permute]
+    rs = _handles(hip, sc, frames_in_flight=in_flight, visbuffer=1)
+    m = Mismatches()
+    for k, rot in enumerate(CC.FRAME_ROTATIONS):
+        desc = CC.with_camera_rotation(sc.desc, rot)
+        for vis in ((1, 0) if k == 1 else (1,)):
+            for r in rs:
+                r.set_option("visbuffer", vis)
+            for rep in range(3):
+                frames = [r.render_frame(desc, sc.settings).copy() for r in rs]
+                for cull, got in zip(CULLS[1:], frames[1:]):
+                    m.compare(f"camera {k} {rot}, visbuffer {vis}, frame {rep}, cluster_cull {cull}: rgba8", [frames[0]], [got])
+            out = [_planes(r, want=("depth", "tri")) for r in rs]
+            for cull, got in zip(CULLS[1:], out[1:]):
+                m.compare(f"camera {k} {rot}, visbuffer {vis}, cluster_cull {cull}: depth / tri", out[0], got)
+            assert (out[0][1] != 0xFFFFFFFF).mean() > 0.3      # (the camera turned up sees the sky through the ceiling's opening)
+        for r in rs:
+            r.set_option("visbuffer", 1)
+        n = rs[2].cull_counts(False)
+        print(f"camera {k} {rot}: cluster_cull 3 skips {n[1]} of {n[0]} clusters and {n[3]} of {n[2]} vertex blocks")
+        assert n[3] >= 1 and n[1] >= 1, (k, n)
+    for r in rs:
+        r.close()
+    m.check()
+
+
+@pytest.mark.parametrize("permute", [False, True], ids=["as-generated", "permuted"])
+def test_reused_handles_sun_pass(pkg, hip, hall, permute):
+    """the sun's pass for a sun whose frustum holds the hall, then two turned far away, then the first again: the shadow map's bits.  Then the
+    same once more with a shadow-casting point light whose six faces are drawn in front of every sun's pass: they share the pass's vertex buffer
+    and are drawn without block culling, so a skipped block's slots then hold the last face's coordinates"""
+    sc = hall[permute]
+    rs = _handles(hip, sc)
+    m = Mismatches()
+    for faces in (False, True):
+        if faces:
+            for r in rs:
+                r.set_option("point_shadow_size", 64)
+                r.update_point_shadow_lights(pkg.scenes.point_shadow_lights(1, seed=5))
+        for k, rot in enumerate(CC.SUN_ROTATIONS):
+            desc = CC.with_sun_rotation(sc.desc, rot)
+            out = []
+            for r in rs:
+                if faces:
+                    r.pass_point_shadows(desc)
+                r.pass_shadow_map(desc)
+                out.append([r.read_shadow_map().view(np.uint32).copy()])
+            for cull, got in zip(CULLS[1:], out[1:]):
+                m.compare(f"sun {k} {rot}, cube faces {faces}, cluster_cull {cull}: shadow map", out[0], got)
+            n = rs[2].cull_counts(True)
+            print(f"sun {k} {rot}, cube faces {faces}: {float((out[0][0] != 0x3F800000).mean()):.2f} of the map drawn; cluster_cull 3 skips {n[1]} of {n[0]} clusters and "
+                  f"{n[3]} of {n[2]} vertex blocks")
+            if k in (1, 2):
+                assert n[3] >= 1 and n[1] >= 1, (k, n)
+                assert (out[0][0] != 0x3F800000).any()
+    for r in rs:
+        r.close()
+    m.check()
+
+
+def test_reused_handles_box_through_the_eye_plane(pkg, hip):
+    """a wall of ONE cluster and ONE vertex block (the same box) beside the eye, reaching far behind it; the camera looks at it, then turns in
+    steps of 0.02 degrees through the directions at which the box's far corner, behind the eye, passes the side planes of box_outside --
+    looking at the wall again before every step, so that its slots hold on-screen coordinates.  A block skipped while its cluster is kept
+    draws the wall as the previous camera saw it."""
+    S = pkg.scenes
+    mats = S.make_material_textures(np.random.default_rng(7), 64)
+    v, i = CC.wall(S)
+    rs = [hip.Renderer(CC.QUAD_W, CC.QUAD_H, 0, 16) for _ in CULLS]
+    for r, cull in zip(rs, CULLS):
+        r.create_material(*mats); r.create_mesh(v, i, 0)
+        r.set_option("cluster_cull", cull); r.set_option("debug", COUNT)
+    m = Mismatches()
+    states = []
+    for k, rot in enumerate(CC.WALL_SWEEP):
+        for step, rotation in (("wall in view", CC.WALL_VISIBLE), ("turned", rot)):
+            desc = CC.quad_desc(S, CC.wall_camera(rotation))
+            out = []
+            for r in rs:
+                r.pass_gbuffer(desc)
+                out.append(_planes(r))
+            for cull, got in zip(CULLS[1:], out[1:]):
+                m.compare(f"camera {k} {rotation} ({step}), cluster_cull {cull}", out[0], got)
+            n = rs[2].cull_counts(False)
+            if step == "turned":
+                states.append((int(n[3]), int(n[1])))
+            else:
+                assert (out[0][3] != 0xFFFFFFFF).mean() > 0.1 and n[1] == 0 and n[3] == 0
+    for r in rs:
+        r.close()
+    print("vertex block skipped / cluster skipped per camera of the sweep:", " ".join(f"{b}{c}" for b, c in states))
+    for line in m.found:
+        print(line)
+    assert all(c >= b for b, c in states), states              # never a block without its cluster
+    assert (1, 1) in states and (0, 0) in states, states        # the sweep crosses the planes
+    m.check()
