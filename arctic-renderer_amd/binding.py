@@ -116,6 +116,15 @@ SIGNATURES = {
     "arctic_ao_history_info": (_i32, [_vp, _vp]),
     "arctic_accumulate_pixels": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "arctic_pass_ray_effects_temporal": (_i32, [_vp, _scene, _settings, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_motion_vectors_device": (_i32, [_vp, _scene, _vp, _vp]),
+    "arctic_motion_vectors": (_i32, [_vp, _scene, _vp, _vp, _vp, _vp]),
+    "arctic_motion_reset": (_i32, [_vp]),
+    "arctic_motion_info": (_i32, [_vp, _vp]),
+    "arctic_motion_pixels": (_i32, [_u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _u32, _vp, _vp]),
+    "arctic_accumulate_ambient_occlusion_motion_device": (_i32, [_vp, _scene, _vp, _vp, _vp, _vp]),
+    "arctic_accumulate_ambient_occlusion_motion": (_i32, [_vp, _scene, _vp, _vp, _vp, _vp]),
+    "arctic_accumulate_pixels_motion": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_pass_ray_effects_motion": (_i32, [_vp, _scene, _settings, _vp, _vp, _vp, _vp, _vp]),
     "arctic_version": (_i32, []),
     # include/arctic_dist.h: the multi-GPU exchange steps
     "arctic_comm_unique_id": (_i32, [_vp, _vp, _u64]),

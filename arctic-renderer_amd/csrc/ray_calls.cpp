@@ -16,6 +16,7 @@
 #include "hit_shade.h"
 #include "compose.h"
 #include "ao_history.h"
+#include "motion.h"
 
 namespace {
 
@@ -636,8 +637,9 @@ int accumulate_states(ArcticRenderer *r, const char *who) {
         return r->fail(ARCTIC_E_STATE, "%s: the history's taps need the whole frame, this handle owns %u of %u rows (its neighbours' rows are on other shards)", who, r->rows(), r->height);
     return ARCTIC_OK;
 }
-// the G-buffer, the history sets and the launch: device pointers throughout.  The handle's state moves only behind a launch that was enqueued
-int accumulate_planes(ArcticRenderer *r, const ArcticScene *sc, const AoHistoryDesc &d, const uint8_t *d_in, uint8_t *d_out) {
+// the G-buffer, the history sets and the launch: device pointers throughout.  The handle's state moves only behind a launch that was enqueued.
+// d_prev_world4: the motion form (k_ao_accumulate_motion reads that plane); null: the plain one (k_ao_accumulate).  Both share the history
+int accumulate_planes(ArcticRenderer *r, const ArcticScene *sc, const AoHistoryDesc &d, const uint8_t *d_in, uint8_t *d_out, const void *d_prev_world4 = nullptr) {
     int rc = gbuffer_in_place(r);
     if (rc) return rc;
     ArcticRenderer::AoHistory &A = r->ao_history;
@@ -655,7 +657,7 @@ int accumulate_planes(ArcticRenderer *r, const ArcticScene *sc, const AoHistoryD
     p.tiles_x = r->tiles_x; p.tiles_y = r->tiles_y; p.width = r->width; p.rows = r->rows();
     p.d = d;
     if (have) std::memcpy(p.P, A.proj_view, sizeof p.P);
-    HIPCHECK(r, launch_ao_accumulate(p, r->stream));
+    HIPCHECK(r, d_prev_world4 ? launch_ao_accumulate_motion(p, d_prev_world4, r->stream) : launch_ao_accumulate(p, r->stream));
     const ArcticCamera &c = sc->camera;
     camera_proj_view(c.eye, c.rotation, c.aspect, c.fov_y, c.z_near_far[0], c.z_near_far[1], A.proj_view);
     A.cur = to; A.valid = true; A.width = r->width; A.height = r->height;
@@ -747,6 +749,207 @@ int arctic_pass_ray_effects_temporal(ArcticRenderer *r, const ArcticScene *scene
     if ((rc = select_device(r)) != ARCTIC_OK) return rc;
     if ((rc = trace_ambient_occlusion(r, scene, ao, dirs, nullptr, who)) != ARCTIC_OK) return rc;
     if ((rc = accumulate_planes(r, scene, h, r->ao.d_out.as<uint8_t>(), r->ao.d_out.as<uint8_t>())) != ARCTIC_OK) return rc;
+    if ((d.flags & COMPOSE_REFLECTIONS) && (rc = trace_reflections(r, scene, d.reflection_bias, nullptr, who)) != ARCTIC_OK) return rc;
+    if ((rc = compose_planes(r, scene, settings, d, r->ao.d_out.as<uint8_t>(), r->hit.d_color.as<float>(), d_out_rgba8)) != ARCTIC_OK) return rc;
+    ++r->compose.passes;
+    return ARCTIC_OK;
+}
+
+// ---- motion vectors and the accumulation that uses them (the definition: include/arctic_hip.h; the arithmetic: motion.h; the kernels: motion.hip) ---
+namespace {
+// what the motion calls refuse, in the header's order: no side effect
+int motion_refusal(ArcticRenderer *r, const ArcticScene *sc, const void *prev_world4, const char *who) {
+    if (!valid_scene(sc) || !prev_world4) return r->fail(ARCTIC_E_INVALID, "%s: null scene or prev_world4 plane", who);
+    if (!r->have_vis) return r->fail(ARCTIC_E_STATE, "%s: no visibility plane (arctic_pass_gbuffer or a frame first; arctic_write_gbuffer leaves none)", who);
+    return ARCTIC_OK;
+}
+// The table, k_motion, the snapshots, then M becomes this call's scene: device pointers throughout, everything enqueued on the handle's stream.
+// Whatever can fail is done in front of the first launch; the handle's state moves only behind the launches
+int motion_planes(ArcticRenderer *r, const ArcticScene *sc, float4 *d_pw, float2 *d_vel, float *d_bary, uint4 *d_src) {
+    ArcticRenderer::Motion &M = r->motion;
+    const bool have = M.valid && M.width == r->width && M.height == r->height;
+    if (M.shapes.size() < r->meshes.size()) M.shapes.resize(r->meshes.size());
+    HIPCHECK(r, M.written.ensure(hipEventDisableTiming));
+    HIPCHECK(r, M.written.wait(r->stream));   // (recorded on another stream: arctic_set_stream came in between; on this one: stream order does it)
+    // the table, in the prepass's order: the scene's objects whose mesh exists
+    size_t n_tab = 0;
+    for (uint64_t i = 0; i < sc->n_objects; ++i) n_tab += sc->objects[i].mesh_idx < r->meshes.size() ? 1 : 0;
+    const size_t bytes = std::max<size_t>(n_tab, 1) * sizeof(MotionObject);
+    MotionObject *h_objs = nullptr;
+    HIPCHECK(r, M.objs_ring.stage(bytes, &h_objs));
+    HIPCHECK(r, M.d_objs.ensure(bytes));
+    std::vector<uint64_t> to_snap;   // the meshes whose snapshot this call writes: deformed, and not stamped with the shape they have
+    size_t k = 0;
+    for (uint64_t i = 0; i < sc->n_objects; ++i) {
+        const ArcticObject &o = sc->objects[i];
+        if (o.mesh_idx >= r->meshes.size()) continue;
+        const Mesh &m = r->meshes[o.mesh_idx];
+        ArcticRenderer::Motion::Shape &S = M.shapes[o.mesh_idx];
+        MotionObject &d = h_objs[k++];
+        d = MotionObject{};
+        d.n_vertices = m.n_vertices; d.scene_object = (uint32_t)std::min<uint64_t>(i, 0xFFFFFFFEull);
+        // step 3: M is not empty, the previous call's list had this entry, and it named the same mesh (which that call therefore saw)
+        if (have && i < M.objects.size() && M.objects[i].mesh == o.mesh_idx && S.seen_call == M.call_id) {
+            std::memcpy(d.prev_trs, M.objects[i].trs, sizeof d.prev_trs);
+            if (S.seq_at_call == m.shape_seq) { d.prev = m.vertices_in_use(); d.stride = 14; }             // the shape has not moved since
+            else if (S.rigid_at_call) { d.prev = m.d_vertices.as<float>(); d.stride = 14; }               // it was the mesh's own buffer then
+            else if (S.d_snap && S.stamp == S.seq_at_call && S.n_vertices == m.n_vertices) { d.prev = S.d_snap.as<float>(); d.stride = 4; }
+            d.has_prev = d.prev != nullptr;
+        }
+        if (m.deformed() && !(S.d_snap && S.stamp == m.shape_seq && S.n_vertices == m.n_vertices) && std::find(to_snap.begin(), to_snap.end(), o.mesh_idx) == to_snap.end())
+            to_snap.push_back(o.mesh_idx);
+    }
+    for (uint64_t mi : to_snap) {   // (a snapshot is made once per mesh: its size never changes, so the buffer a table entry above points at stays)
+        ArcticRenderer::Motion::Shape &S = M.shapes[mi];
+        const Mesh &m = r->meshes[mi];
+        if (!S.d_snap || S.n_vertices != m.n_vertices) {
+            S.stamp = ~0ull;
+            HIPCHECK(r, S.d_snap.alloc_exact(std::max<size_t>(m.n_vertices, 1) * 16));
+            S.n_vertices = m.n_vertices;
+        }
+    }
+    HIPCHECK(r, M.objs_ring.send(M.d_objs.p, n_tab * sizeof(MotionObject), r->stream));
+    const int f = r->fwd();
+    MotionParams p = {};
+    p.vis = r->d_vis().as<unsigned long long>();
+    p.recs = r->geo[f].d_recs.as<SetupRec>(); p.rrecs = r->geo[f].d_rrecs.as<RasterRec>(); p.rec_of = r->geo[f].d_rec_of.as<uint32_t>();
+    p.objs = r->tables[f].objs; p.mobjs = M.d_objs.as<MotionObject>();
+    p.n_objs = (uint32_t)n_tab; p.n_tiles = (uint32_t)r->n_tiles(); p.width = r->width; p.height = r->height; p.rows = r->rows(); p.row0_in_tile = r->row0_in_tile;
+    p.gp = r->tables[f].gp;
+    if (have) std::memcpy(p.P, M.proj_view, sizeof p.P);
+    p.prev_world4 = d_pw; p.velocity2 = d_vel; p.bary3 = d_bary; p.source4 = d_src;
+    HIPCHECK(r, launch_motion(p, r->stream));
+    ++M.launches;
+    M.valid = false;   // (until the snapshots below are enqueued too: a failure between leaves M empty, never half this call's)
+    for (uint64_t mi : to_snap) {
+        ArcticRenderer::Motion::Shape &S = M.shapes[mi];
+        const Mesh &m = r->meshes[mi];
+        HIPCHECK(r, launch_motion_snapshot(m.vertices_in_use(), m.n_vertices, S.d_snap.p, r->stream));
+        S.stamp = m.shape_seq;
+        ++M.snapshot_launches;
+    }
+    HIPCHECK(r, M.written.record(r->stream));
+    // M becomes this call's scene
+    ++M.call_id;
+    M.objects.resize((size_t)sc->n_objects);
+    for (uint64_t i = 0; i < sc->n_objects; ++i) {
+        const ArcticObject &o = sc->objects[i];
+        M.objects[(size_t)i].mesh = o.mesh_idx;
+        std::memcpy(M.objects[(size_t)i].trs, o.trs, sizeof o.trs);
+        if (o.mesh_idx >= r->meshes.size()) continue;
+        const Mesh &m = r->meshes[o.mesh_idx];
+        ArcticRenderer::Motion::Shape &S = M.shapes[o.mesh_idx];
+        S.seq_at_call = m.shape_seq; S.rigid_at_call = !m.deformed(); S.seen_call = M.call_id;
+    }
+    const ArcticCamera &c = sc->camera;
+    camera_proj_view(c.eye, c.rotation, c.aspect, c.fov_y, c.z_near_far[0], c.z_near_far[1], M.proj_view);
+    M.width = r->width; M.height = r->height; M.valid = true;
+    ++M.calls;
+    return ARCTIC_OK;
+}
+}  // namespace
+
+int arctic_motion_vectors_device(ArcticRenderer *r, const ArcticScene *scene, float *d_prev_world4, float *d_velocity2) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "motion_vectors_device";
+    if (((uintptr_t)d_prev_world4 & 15u) || ((uintptr_t)d_velocity2 & 7u)) return r->fail(ARCTIC_E_INVALID, "%s: prev_world4 must be 16-byte aligned, velocity2 8-byte aligned", who);
+    int rc = motion_refusal(r, scene, d_prev_world4, who);
+    if (rc || (rc = select_device(r)) != ARCTIC_OK) return rc;
+    return motion_planes(r, scene, reinterpret_cast<float4 *>(d_prev_world4), reinterpret_cast<float2 *>(d_velocity2), nullptr, nullptr);
+}
+
+int arctic_motion_vectors(ArcticRenderer *r, const ArcticScene *scene, float *prev_world4, float *velocity2, float *bary3, uint32_t *source4) {
+    if (!r) return ARCTIC_E_INVALID;
+    alignas(16) static const char own_plane[16] = {};   // (the plane k_motion writes is the handle's own: never null)
+    int rc = motion_refusal(r, scene, own_plane, "motion_vectors");
+    if (rc || (rc = select_device(r)) != ARCTIC_OK) return rc;
+    ArcticRenderer::Motion &M = r->motion;
+    const size_t n = std::max<size_t>((size_t)r->rows() * r->width, 1);
+    HIPCHECK(r, M.d_pw.ensure(n * 16));
+    if (velocity2) HIPCHECK(r, M.d_vel.ensure(n * 8));
+    if (bary3) HIPCHECK(r, M.d_bary.ensure(n * 12));
+    if (source4) HIPCHECK(r, M.d_src.ensure(n * 16));
+    if ((rc = motion_planes(r, scene, M.d_pw.as<float4>(), velocity2 ? M.d_vel.as<float2>() : nullptr, bary3 ? M.d_bary.as<float>() : nullptr,
+                            source4 ? M.d_src.as<uint4>() : nullptr)) != ARCTIC_OK) return rc;
+    const size_t px = (size_t)r->rows() * r->width;
+    if (prev_world4) HIPCHECK(r, hipMemcpyAsync(prev_world4, M.d_pw.p, px * 16, hipMemcpyDeviceToHost, r->stream));
+    if (velocity2) HIPCHECK(r, hipMemcpyAsync(velocity2, M.d_vel.p, px * 8, hipMemcpyDeviceToHost, r->stream));
+    if (bary3) HIPCHECK(r, hipMemcpyAsync(bary3, M.d_bary.p, px * 12, hipMemcpyDeviceToHost, r->stream));
+    if (source4) HIPCHECK(r, hipMemcpyAsync(source4, M.d_src.p, px * 16, hipMemcpyDeviceToHost, r->stream));
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    return check_item_overflow(r);
+}
+
+int arctic_motion_reset(ArcticRenderer *r) {
+    if (!r) return ARCTIC_E_INVALID;
+    r->motion.valid = false;   // (the snapshots and the table stay: a call in flight may still read them, and the next call reuses them)
+    r->motion.calls = 0;
+    return ARCTIC_OK;
+}
+
+int arctic_motion_info(ArcticRenderer *r, uint64_t *out4) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!out4) return r->fail(ARCTIC_E_INVALID, "motion_info: null");
+    out4[0] = r->motion.device_bytes(); out4[1] = r->motion.launches; out4[2] = r->motion.snapshot_launches; out4[3] = r->motion.calls;
+    return ARCTIC_OK;
+}
+
+int arctic_accumulate_ambient_occlusion_motion_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticAoHistory *hist, const float *d_prev_world4,
+                                                      const uint8_t *d_ao_in_u8, uint8_t *d_ao_out_u8) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "accumulate_ambient_occlusion_motion_device";
+    AoHistoryDesc d;
+    int rc = accumulate_checks(r, scene, hist, d_ao_in_u8, d_ao_out_u8, d, who);
+    if (rc) return rc;
+    if (!d_prev_world4 || ((uintptr_t)d_prev_world4 & 15u)) return r->fail(ARCTIC_E_INVALID, "%s: the prev_world4 plane is null or not 16-byte aligned", who);
+    if ((rc = accumulate_states(r, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
+    return accumulate_planes(r, scene, d, d_ao_in_u8, d_ao_out_u8, d_prev_world4);
+}
+
+int arctic_accumulate_ambient_occlusion_motion(ArcticRenderer *r, const ArcticScene *scene, const ArcticAoHistory *hist, const float *prev_world4, const uint8_t *ao_in,
+                                               uint8_t *ao_out) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "accumulate_ambient_occlusion_motion";
+    AoHistoryDesc d;
+    int rc = accumulate_checks(r, scene, hist, ao_in, ao_out, d, who);
+    if (rc) return rc;
+    if (!prev_world4) return r->fail(ARCTIC_E_INVALID, "%s: null prev_world4 plane", who);
+    if ((rc = accumulate_states(r, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
+    const size_t px = (size_t)r->rows() * r->width;
+    HIPCHECK(r, r->d_stage.ensure(std::max<size_t>(px, 16)));
+    HIPCHECK(r, r->motion.d_plane.ensure(std::max<size_t>(px, 1) * 16));
+    HIPCHECK(r, hipMemcpyAsync(r->d_stage.p, ao_in, px, hipMemcpyHostToDevice, r->stream));
+    HIPCHECK(r, hipMemcpyAsync(r->motion.d_plane.p, prev_world4, px * 16, hipMemcpyHostToDevice, r->stream));
+    if ((rc = accumulate_planes(r, scene, d, r->d_stage.as<uint8_t>(), r->d_stage.as<uint8_t>(), r->motion.d_plane.p)) != ARCTIC_OK) return rc;
+    return read_back(r, ao_out, r->d_stage, px, FROM_FRAME);
+}
+
+int arctic_pass_ray_effects_motion(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticRayCompose *compose,
+                                   const ArcticAmbientOcclusion *ao, const float *dirs, const ArcticAoHistory *hist, uint8_t *d_out_rgba8) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "pass_ray_effects_motion";
+    alignas(16) static const char own_plane[16] = {};   // (the planes are the handle's own: never null, always aligned)
+    ComposeDesc d;
+    int rc = compose_checks(r, scene, settings, compose, own_plane, own_plane, d, who);
+    if (rc) return rc;
+    if (!(d.flags & COMPOSE_AO)) return r->fail(ARCTIC_E_INVALID, "%s: ARCTIC_COMPOSE_AO is not set: there is nothing to accumulate (arctic_pass_ray_effects)", who);
+    if (d_out_rgba8 && ((uintptr_t)d_out_rgba8 & 3u)) return r->fail(ARCTIC_E_INVALID, "%s: the output is not 4-byte aligned", who);
+    // every refusal of the calls below, in front of the first launch (they make them again, in their own words, to no effect)
+    AoDesc a = {};
+    if (ao) std::memcpy(&a, ao, sizeof a);
+    if (const char *why = ao_refusal(ao ? &a : nullptr, dirs)) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
+    AoHistoryDesc h;
+    if ((rc = accumulate_checks(r, scene, hist, own_plane, own_plane, h, who)) != ARCTIC_OK) return rc;
+    if ((d.flags & COMPOSE_REFLECTIONS) && !std::isfinite(d.reflection_bias)) return r->fail(ARCTIC_E_INVALID, "%s: the reflection bias is not finite", who);
+    if ((rc = motion_refusal(r, scene, own_plane, who)) != ARCTIC_OK) return rc;
+    if ((rc = compose_states(r, d, who)) != ARCTIC_OK || (rc = accumulate_states(r, who)) != ARCTIC_OK) return rc;
+    if ((d.flags & COMPOSE_REFLECTIONS) && (rc = sun_map_ready(r, who)) != ARCTIC_OK) return rc;
+    if ((rc = select_device(r)) != ARCTIC_OK) return rc;
+    ArcticRenderer::Motion &M = r->motion;
+    HIPCHECK(r, M.d_plane.ensure(std::max<size_t>((size_t)r->rows() * r->width, 1) * 16));
+    if ((rc = motion_planes(r, scene, M.d_plane.as<float4>(), nullptr, nullptr, nullptr)) != ARCTIC_OK) return rc;
+    if ((rc = trace_ambient_occlusion(r, scene, ao, dirs, nullptr, who)) != ARCTIC_OK) return rc;
+    if ((rc = accumulate_planes(r, scene, h, r->ao.d_out.as<uint8_t>(), r->ao.d_out.as<uint8_t>(), M.d_plane.p)) != ARCTIC_OK) return rc;
     if ((d.flags & COMPOSE_REFLECTIONS) && (rc = trace_reflections(r, scene, d.reflection_bias, nullptr, who)) != ARCTIC_OK) return rc;
     if ((rc = compose_planes(r, scene, settings, d, r->ao.d_out.as<uint8_t>(), r->hit.d_color.as<float>(), d_out_rgba8)) != ARCTIC_OK) return rc;
     ++r->compose.passes;

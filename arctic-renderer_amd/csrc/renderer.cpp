@@ -129,6 +129,7 @@ int alloc_targets(ArcticRenderer *r) {
     r->hdr_valid = false;
     r->compose.pixels = 0;   // (arctic_read_composed: nothing composed at this size yet)
     r->ao_history.valid = false;   // (the occlusion's history is empty after a resize)
+    r->motion.valid = false;       // (... and so is what the previous motion call saw)
     r->output_filtered = false;
     return ARCTIC_OK;
 }

@@ -391,7 +391,41 @@ struct ArcticRenderer {
         uint64_t launches = 0, calls = 0;
         size_t device_bytes() const { return d_a[0].cap + d_a[1].cap + d_b[0].cap + d_b[1].cap; }
     } ao_history;
-    PinnedBuf counts;               // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
+    // Motion vectors (arctic_motion_vectors_device; motion.hip): the state M of include/arctic_hip.h -- what the previous motion call saw.  Per entry of
+    // that call's object list its mesh and trs; that call's proj_view and frame size; per mesh (`shapes`, by mesh handle) where its vertices lay:
+    // nothing for a mesh that was not deformed (its own buffer never changes), else a float4 snapshot written by k_motion_snapshot at the END of the
+    // call that saw the pose, behind k_motion, which may still read the pose before it from the same buffer.  seq_at_call, rigid_at_call, seen_call:
+    // the mesh's shape_seq, !deformed() and the call's number when a call last used the mesh.  The per-object table of a call travels through a
+    // ring of pinned buffers like HitScene's.  d_pw .. d_src: the host form's planes; d_plane: the one call's.  `written`: recorded behind every
+    // call, waited for by the next one if the handle's stream has changed in between.  Nothing is allocated before the first call that passes
+    // its checks; valid: M is not empty (cleared by arctic_motion_reset and by a resize)
+    struct Motion {
+        struct PrevObject { uint64_t mesh; float trs[16]; };
+        struct Shape {
+            DevBuf d_snap;
+            uint32_t n_vertices = 0;            // what d_snap holds room for
+            uint64_t stamp = ~0ull;             // the shape_seq d_snap was written at (~0: never)
+            uint64_t seq_at_call = 0, seen_call = 0;
+            bool rigid_at_call = true;
+        };
+        bool valid = false;
+        std::vector<PrevObject> objects;
+        float proj_view[16] = {};
+        uint32_t width = 0, height = 0;
+        std::vector<Shape> shapes;
+        DevBuf d_objs;
+        static constexpr int OBJ_RING = 3;
+        UploadRing<OBJ_RING> objs_ring;
+        DevBuf d_pw, d_vel, d_bary, d_src, d_plane;
+        StreamMark written;
+        uint64_t launches = 0, snapshot_launches = 0, calls = 0, call_id = 0;
+        size_t device_bytes() const {
+            size_t b = d_objs.cap + d_pw.cap + d_vel.cap + d_bary.cap + d_src.cap + d_plane.cap;
+            for (const Shape &s : shapes) b += s.d_snap.cap;
+            return b;
+        }
+    } motion;
+    PinnedBuf counts;              // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts
     // The streams the handle created, declared LAST: members are destroyed in reverse order, so every stream is waited for and gone before any

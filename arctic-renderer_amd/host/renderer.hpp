@@ -355,6 +355,48 @@ class Renderer {
                                                  const float *dirs, const ArcticAoHistory &hist, uint8_t *d_out_rgba8) {
         return ok(arctic_pass_ray_effects_temporal(m_handle, &scene, &settings, &compose, &ao, dirs, &hist, d_out_rgba8));
     }
+    // motion vectors (include/arctic_hip.h: arctic_motion_vectors_device and the definition in front of it): where every pixel's surface point lay at
+    // the previous motion call, into device planes the caller owns (rows*width float4; rows*width float2, may be nullptr); once per frame, after the
+    // frame's pose / trs have been set and drawn; in stream order on the handle's stream
+    [[nodiscard]] bool motion_vectors_device(const ArcticScene &scene, float *d_prev_world4, float *d_velocity2) {
+        return ok(arctic_motion_vectors_device(m_handle, &scene, d_prev_world4, d_velocity2));
+    }
+    // the host form, synchronous, with the barycentrics and the source triangle of every pixel; any pointer may be nullptr
+    [[nodiscard]] bool motion_vectors(const ArcticScene &scene, float *prev_world4, float *velocity2, float *bary3, uint32_t *source4) {
+        return ok(arctic_motion_vectors(m_handle, &scene, prev_world4, velocity2, bary3, source4));
+    }
+    // forgets what the previous motion call saw; frees nothing
+    [[nodiscard]] bool motion_reset() { return ok(arctic_motion_reset(m_handle)); }
+    // {device bytes, launches of k_motion, launches of k_motion_snapshot, calls since the last reset}
+    [[nodiscard]] bool motion_info(uint64_t out4[4]) { return ok(arctic_motion_info(m_handle, out4)); }
+    // its host arbiter (no handle, no GPU)
+    [[nodiscard]] static bool motion_pixels(uint64_t n, const float *bary3, const uint32_t *object, const float *prev_pos9, const int32_t *pixel_xy, const float *prev_trs,
+                                            uint64_t n_objects, const float *prev_proj_view, uint32_t width, uint32_t height, float *prev_world4, float *velocity2) {
+        return arctic_motion_pixels(n, bary3, object, prev_pos9, pixel_xy, prev_trs, n_objects, prev_proj_view, width, height, prev_world4, velocity2) == ARCTIC_OK;
+    }
+    // the accumulation with the history fetched where each pixel's point WAS (d_prev_world4: the plane motion_vectors_device wrote for this frame);
+    // shares the history with accumulate_ambient_occlusion_device
+    [[nodiscard]] bool accumulate_ambient_occlusion_motion_device(const ArcticScene &scene, const ArcticAoHistory &hist, const float *d_prev_world4, const uint8_t *d_ao_in_u8,
+                                                                  uint8_t *d_ao_out_u8) {
+        return ok(arctic_accumulate_ambient_occlusion_motion_device(m_handle, &scene, &hist, d_prev_world4, d_ao_in_u8, d_ao_out_u8));
+    }
+    // the host form, synchronous
+    [[nodiscard]] bool accumulate_ambient_occlusion_motion(const ArcticScene &scene, const ArcticAoHistory &hist, const float *prev_world4, const uint8_t *ao_in, uint8_t *ao_out) {
+        return ok(arctic_accumulate_ambient_occlusion_motion(m_handle, &scene, &hist, prev_world4, ao_in, ao_out));
+    }
+    // its host arbiter: accumulate_pixels with the prev_world4 array
+    [[nodiscard]] static bool accumulate_pixels_motion(const ArcticAoHistory &hist, uint64_t n, const float *world3, const float *prev_world4, const float *normal3,
+                                                       const uint8_t *geometry, const uint8_t *cur, const float *prev_proj_view, uint32_t width, uint32_t height,
+                                                       const float *prev_value, const float *prev_count, const float *prev_world3, const float *prev_normal3, uint8_t *out_u8,
+                                                       float *out_value, float *out_count, float *out_world3, float *out_normal3) {
+        return arctic_accumulate_pixels_motion(&hist, n, world3, prev_world4, normal3, geometry, cur, prev_proj_view, width, height, prev_value, prev_count, prev_world3,
+                                               prev_normal3, out_u8, out_value, out_count, out_world3, out_normal3) == ARCTIC_OK;
+    }
+    // pass_ray_effects_temporal with the motion vectors in front of the occlusion and the accumulation's motion form
+    [[nodiscard]] bool pass_ray_effects_motion(const ArcticScene &scene, const ArcticSettings &settings, const ArcticRayCompose &compose, const ArcticAmbientOcclusion &ao,
+                                               const float *dirs, const ArcticAoHistory &hist, uint8_t *d_out_rgba8) {
+        return ok(arctic_pass_ray_effects_motion(m_handle, &scene, &settings, &compose, &ao, dirs, &hist, d_out_rgba8));
+    }
 
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }

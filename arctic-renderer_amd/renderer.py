@@ -385,6 +385,72 @@ class Renderer:
         self._check(self.L.arctic_pass_ray_effects_temporal(self.h, C.byref(s), C.byref(st), _ptr(c), _ptr(ao), _ptr(d), _ptr(h), C.c_void_p(d_out_ptr) if d_out_ptr else None))
         return self.read_composed(want=("rgba8",))[2] if read and not d_out_ptr else None
 
+    # ---- motion vectors and the accumulation that uses them (include/arctic_hip.h: arctic_motion_vectors_device and the definition) -------------
+    def motion_vectors_device(self, desc, d_prev_world4_ptr, d_velocity2_ptr=None):
+        """where every pixel's surface point lay at the previous motion call, into device planes the caller owns (int pointers: rows * width
+        float4 {previous world position, flag}, and rows * width float2 offsets to where it was on the screen, or None).  desc: the scene
+        that was drawn; it is what the next call compares against -- once per frame.  Asynchronous on the handle's stream."""
+        s = self._scene(desc)
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_motion_vectors_device(self.h, C.byref(s), vp(d_prev_world4_ptr), vp(d_velocity2_ptr)))
+
+    def motion_vectors(self, desc, want=("prev_world", "velocity", "bary", "source")):
+        """the same to host memory, with the kernel's two further outputs: (prev_world (rows, width, 4) float32, velocity (rows, width, 2)
+        float32, bary (rows, width, 3) float32, source (rows, width, 4) uint32 = {object, i0, i1, i2}); None for what was not asked for.
+        Synchronous."""
+        n = (self.rows, self.width)
+        pw = np.empty(n + (4,), np.float32) if "prev_world" in want else None
+        vel = np.empty(n + (2,), np.float32) if "velocity" in want else None
+        bary = np.empty(n + (3,), np.float32) if "bary" in want else None
+        src = np.empty(n + (4,), np.uint32) if "source" in want else None
+        s = self._scene(desc)
+        self._check(self.L.arctic_motion_vectors(self.h, C.byref(s), _ptr(pw), _ptr(vel), _ptr(bary), _ptr(src)))
+        return pw, vel, bary, src
+
+    def motion_reset(self):
+        """forget what the previous motion call saw: the next call is a first call.  Frees nothing."""
+        self._check(self.L.arctic_motion_reset(self.h))
+
+    def motion_info(self):
+        """(device bytes, launches of k_motion, launches of k_motion_snapshot, calls since the last reset): all 0 until the first call"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_motion_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    def accumulate_ambient_occlusion_motion_device(self, desc, d_prev_world4_ptr, d_ao_in_ptr, d_ao_out_ptr, max_history=32.0, normal_cos=0.9, plane_dist=0.05, min_weight=0.0,
+                                                   hist=None):
+        """accumulate_ambient_occlusion_device with the history fetched where each pixel's point WAS: d_prev_world4_ptr is the plane
+        motion_vectors_device wrote for this frame.  Shares the history with the plain call.  Asynchronous on the handle's stream."""
+        s = self._scene(desc)
+        h = _ao_history_arguments(max_history, normal_cos, plane_dist, min_weight) if hist is None else hist
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_accumulate_ambient_occlusion_motion_device(self.h, C.byref(s), _ptr(h), vp(d_prev_world4_ptr), vp(d_ao_in_ptr), vp(d_ao_out_ptr)))
+
+    def accumulate_ambient_occlusion_motion(self, desc, prev_world4, ao, max_history=32.0, normal_cos=0.9, plane_dist=0.05, min_weight=0.0, hist=None):
+        """the same from and to host memory: (rows, width, 4) float32 and (rows, width) uint8 -> (rows, width) uint8; synchronous"""
+        s = self._scene(desc)
+        h = _ao_history_arguments(max_history, normal_cos, plane_dist, min_weight) if hist is None else hist
+        a = np.ascontiguousarray(ao, dtype=np.uint8)
+        pw = np.ascontiguousarray(prev_world4, dtype=np.float32)
+        if a.shape != (self.rows, self.width) or pw.shape != (self.rows, self.width, 4):
+            raise ArcticError(-1, f"accumulate_ambient_occlusion_motion: expected {(self.rows, self.width)} and {(self.rows, self.width, 4)}, got {a.shape} and {pw.shape}")
+        out = np.empty_like(a)
+        self._check(self.L.arctic_accumulate_ambient_occlusion_motion(self.h, C.byref(s), _ptr(h), _ptr(pw), _ptr(a), _ptr(out)))
+        return out
+
+    def pass_ray_effects_motion(self, desc, settings, dirs, reflection_bias=None, ao_strength=1.0, reflection_strength=1.0, d_out_ptr=None, read=True, n_rays=None,
+                                pattern=None, radius=np.inf, bias=1e-3, filter=False, normal_cos=0.9, plane_dist=0.05, max_history=32.0, history_normal_cos=0.9,
+                                history_plane_dist=0.05, min_weight=0.0):
+        """pass_ray_effects_temporal with the motion vectors in front of the occlusion and the accumulation's motion form: (rows, width, 4)
+        uint8.  read=False or a d_out_ptr leaves the result on the device and returns None."""
+        s, st = self._scene(desc), self._settings(settings)
+        flags = (binding.COMPOSE_AO if dirs is not None else 0) | (binding.COMPOSE_REFLECTIONS if reflection_bias is not None else 0)
+        c = _compose_arguments(flags, ao_strength, reflection_strength, 0.0 if reflection_bias is None else reflection_bias)
+        ao, d = _ao_arguments(dirs, n_rays, pattern, radius, bias, filter, normal_cos, plane_dist) if dirs is not None else (None, None)
+        h = _ao_history_arguments(max_history, history_normal_cos, history_plane_dist, min_weight)
+        self._check(self.L.arctic_pass_ray_effects_motion(self.h, C.byref(s), C.byref(st), _ptr(c), _ptr(ao), _ptr(d), _ptr(h), C.c_void_p(d_out_ptr) if d_out_ptr else None))
+        return self.read_composed(want=("rgba8",))[2] if read and not d_out_ptr else None
+
     def ray_scene_info(self):
         """(triangles stored, nodes, builds so far, depth) of the cached acceleration structure"""
         out = np.zeros(4, np.uint64)
@@ -862,6 +928,55 @@ def accumulate_pixels(world, normal, geometry, cur, prev_proj_view=None, width=1
                                                 *[p(o) for o in out])
     if rc < 0:
         raise ArcticError(rc, "accumulate_pixels")
+    return out
+
+
+def motion_pixels(bary, obj, prev_pos, pixel_xy, prev_trs, prev_proj_view=None, width=1, height=1):
+    """arctic_motion_pixels: steps 3 to 5 of the motion vectors of include/arctic_hip.h on the host, for n pixels in any order -- bary (n, 3),
+    obj (n,) uint32 (0xFFFFFFFF: no geometry), prev_pos (n, 3, 3) the previous object-space positions of the pixel's three vertices, pixel_xy
+    (n, 2) int32, prev_trs (n_objects, 16) the previous call's trs by object; prev_proj_view: the previous call's (4, 4) matrix, None = M is
+    empty.  Returns (prev_world4 (n, 4), velocity2 (n, 2)) float32."""
+    b = np.ascontiguousarray(bary, dtype=np.float32).reshape(-1, 3)
+    o = np.ascontiguousarray(obj, dtype=np.uint32).ravel()
+    q = np.ascontiguousarray(prev_pos, dtype=np.float32).reshape(-1, 9)
+    xy = np.ascontiguousarray(pixel_xy, dtype=np.int32).reshape(-1, 2)
+    t = np.ascontiguousarray(prev_trs, dtype=np.float32).reshape(-1, 16)
+    n = len(b)
+    if any(len(x) != n for x in (o, q, xy)):
+        raise ArcticError(-1, "motion_pixels: one entry of every array per pixel")
+    P = None if prev_proj_view is None else np.ascontiguousarray(prev_proj_view, dtype=np.float32).reshape(16)
+    pw, vel = np.empty((n, 4), np.float32), np.empty((n, 2), np.float32)
+    p = (lambda a: _ptr(a) if len(a) else None)
+    rc = binding.lib().arctic_motion_pixels(n, p(b), p(o), p(q), p(xy), p(t), len(t), _ptr(P), int(width), int(height), p(pw), p(vel))
+    if rc < 0:
+        raise ArcticError(rc, "motion_pixels")
+    return pw, vel
+
+
+def accumulate_pixels_motion(world, prev_world4, normal, geometry, cur, prev_proj_view=None, width=1, height=1, prev=None, max_history=32.0, normal_cos=0.9, plane_dist=0.05,
+                             min_weight=0.0, hist=None):
+    """arctic_accumulate_pixels_motion: accumulate_pixels with one more input, prev_world4 (n, 4) -- every pixel's previous point and flag as
+    motion_vectors gives them.  Returns what accumulate_pixels returns."""
+    f = lambda a, k: np.ascontiguousarray(a, dtype=np.float32).reshape((-1, k) if k > 1 else (-1,))
+    w, pw4, nr = f(world, 3), f(prev_world4, 4), f(normal, 3)
+    g = np.ascontiguousarray(np.asarray(geometry) != 0, dtype=np.uint8).ravel()
+    c = np.ascontiguousarray(cur, dtype=np.uint8).ravel()
+    n = len(w)
+    if any(len(x) != n for x in (pw4, nr, g, c)):
+        raise ArcticError(-1, "accumulate_pixels_motion: one entry of every array per pixel")
+    h = _ao_history_arguments(max_history, normal_cos, plane_dist, min_weight) if hist is None else hist
+    P = None if prev_proj_view is None else np.ascontiguousarray(prev_proj_view, dtype=np.float32).reshape(16)
+    pv = pc = pw = pn = None
+    if P is not None:
+        pv, pc, pw, pn = f(prev[0], 1), f(prev[1], 1), f(prev[2], 3), f(prev[3], 3)
+        if any(len(x) != int(width) * int(height) for x in (pv, pc, pw, pn)):
+            raise ArcticError(-1, "accumulate_pixels_motion: the previous history is not width * height entries")
+    out = np.empty(n, np.uint8), np.empty(n, np.float32), np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+    p = (lambda a: _ptr(a) if n else None)
+    rc = binding.lib().arctic_accumulate_pixels_motion(_ptr(h), n, p(w), p(pw4), p(nr), p(g), p(c), _ptr(P), int(width), int(height), _ptr(pv), _ptr(pc), _ptr(pw), _ptr(pn),
+                                                       *[p(o) for o in out])
+    if rc < 0:
+        raise ArcticError(rc, "accumulate_pixels_motion")
     return out
 
 

@@ -1205,7 +1205,8 @@ int arctic_compose_info(ArcticRenderer *r, uint64_t *out4);
  *   6. Otherwise  hv = V / S;  hn = C / S;  N = min(hn + 1, max_history);  a = 1 / N;  value = hv + (cur - hv) * a.
  *   7. The output byte is (uint8)min(max(floor(value + 0.5), 0), 255); the entry written is {w_p, value}, {m_p, N}.
  * KNOWN LIMITS, stated and not worked around.  There are no per-object motion vectors: a moving object is handled only as far as the two
- *   rejections catch it.  Only the occlusion plane is accumulated; the mirror reflection is one deterministic ray per pixel and is not.
+ *   rejections catch it (the motion form below, arctic_accumulate_ambient_occlusion_motion_device, is the call that has them).  Only the occlusion
+ *   plane is accumulated; the mirror reflection is one deterministic ray per pixel and is not.
  * Refusals, in this order; a refused call writes nothing and leaves H as it was.
  *   ARCTIC_E_INVALID: a null scene, hist or plane; max_history outside [1, 65536] or a NaN; normal_cos not finite; plane_dist negative or a NaN;
  *     min_weight outside [0, 1) or a NaN; reserved != 0.
@@ -1256,6 +1257,103 @@ int arctic_accumulate_pixels(const ArcticAoHistory *hist, uint64_t n, const floa
  * what it was. */
 int arctic_pass_ray_effects_temporal(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticRayCompose *compose,
                                      const ArcticAmbientOcclusion *ao, const float *dirs, const ArcticAoHistory *hist, uint8_t *d_out_rgba8);
+
+/* ---- per-pixel motion vectors, and the accumulation that uses them (no counterpart in the reference) ------------------------------------------------
+ * "Where was this surface point in the previous frame": for every pixel of the current visibility plane the world position its surface point had
+ * at the PREVIOUS motion call -- through that call's trs and that call's pose or morph weights -- and the offset on the screen to where it was
+ * seen then.  It is what lets the occlusion's history follow an object that moves (a changed trs, arctic_set_mesh_pose,
+ * arctic_set_mesh_morph_weights), and what temporal anti-aliasing or motion blur would read first.  Nothing in the passes or in the other calls
+ * changes: a handle that never makes these calls renders the same bytes and allocates nothing for them.
+ *
+ * THE DEFINITION.  Bit for bit: fp32 throughout, one rounding per operation in the written order, no contraction, IEEE division.
+ * STATE.  The handle keeps M, what the previous motion call saw: per entry o of that call's object list its mesh handle and the 16 floats of its
+ *   trs; that call's proj_view (arctic_frame_constants' layout [col][row]) and the frame size; and per mesh the object-space positions its vertices
+ *   in use held when that call was enqueued.  A mesh that was neither posed nor morphed then needs nothing (its own vertices never change); any other
+ *   gets a snapshot, one float4 {x, y, z, 0} per vertex, written by k_motion_snapshot at the END of the call in stream order behind k_motion, and only
+ *   when the mesh's shape has changed since the snapshot was last written -- one buffer per mesh: a call reads pose N-1 from it, then overwrites it
+ *   with pose N.  M is EMPTY before the first call, after arctic_motion_reset and after arctic_resize.
+ * INPUTS.  The visibility plane of the current frame with the records of its prepass -- exactly what resolves the G-buffer --, so after
+ *   arctic_pass_gbuffer or a frame; and `scene`, the scene that was DRAWN (its objects give this call's trs and meshes, its camera this call's
+ *   proj_view: both kept for the next call).
+ * PER PIXEL p = (px, py), in the frame's coordinates whatever rows the handle owns.  A pixel reads no neighbour.
+ *   1. No triangle covers p:  prev_world4 = {0, 0, 0, 0}, velocity2 = {0, 0}, bary3 = {0, 0, 0}, source4 = {0xFFFFFFFF, 0, 0, 0}.
+ *   2. Otherwise B = the perspective-correct barycentrics of p in its SOURCE triangle, the three weights every one of the 18 attributes of
+ *      arctic_read_gbuffer is interpolated with; o = the triangle's entry in the scene's object list; i0, i1, i2 = its three indices into the
+ *      mesh's vertices.  bary3 = B, source4 = {o, i0, i1, i2}.
+ *   3. Entry o HAS A PREVIOUS iff M is not empty, o is below the previous call's object count, and that call's entry o named the same mesh.
+ *      Without a previous:  prev_world4 = {0, 0, 0, 0}, velocity2 = {0, 0}.
+ *   4. X_k = prev_trs[o] * (prevpos[i_k], 1), rows 0..2, in the vertex kernel's product order:
+ *        X_k[j] = ((T[j]*x + T[4+j]*y) + T[8+j]*z) + T[12+j]*1
+ *      pw[j] = (B0*X_0[j] + B1*X_1[j]) + B2*X_2[j], the attributes' order.   prev_world4 = {pw, flag}.
+ *   5. The velocity, through the PREVIOUS call's matrix P (the accumulation's operations up to sx, sy):
+ *        c[i] = ((P[i]*pw0 + P[4+i]*pw1) + P[8+i]*pw2) + P[12+i]
+ *        c3 > 0 and c0, c1, c3 finite:  iw = 1 / c3;  nx = c0*iw;  ny = c1*iw;  sx = (nx + 1) * (0.5*W);  sy = (1 - ny) * (0.5*H);
+ *          velocity2 = {sx - (px + 0.5), sy - (py + 0.5)}, flag = 2.
+ *        otherwise:  velocity2 = {0, 0}, flag = 1.
+ *      The vector points from this pixel's centre to where the point WAS: the offset a consumer adds to fetch history.
+ *   The flag (prev_world4's w): 0 = nothing known, 1 = the previous point alone, 2 = the point and its velocity.
+ * WHAT FOLLOWS.  With no trs, pose or weights changed since the previous call, pw equals the G-buffer's world (attributes 11..13) bit for bit.
+ * An object whose mesh does not exist and a triangle with an index out of range never reach a pixel (the prepass skips both); every index is
+ *   bounded by the mesh's vertex count before a position is read.
+ * Refusals, in this order; a refused call writes nothing and leaves M as it was.
+ *   ARCTIC_E_INVALID: a null handle, scene or prev_world4 plane (the device form: also a prev_world4 that is not 16-byte aligned, a velocity2
+ *     that is not 8-byte aligned).
+ *   ARCTIC_E_STATE: no visibility plane -- nothing drawn yet, or the G-buffer in place was written by arctic_write_gbuffer. */
+
+/* One call of the definition into DEVICE planes the caller owns, row-major, in the handle's own rows: rows*width float4 (prev_world4) and
+ * rows*width float2 (velocity2, may be NULL).  Stream-ordered on the handle's stream.  The per-object table of the call travels through a ring of
+ * pinned buffers; a warm call on a scene without a posed or morphed mesh allocates nothing and does not synchronise.  After enqueueing, M is this
+ * call's scene: make the call ONCE per frame, after the frame's pose / trs have been set and drawn. */
+int arctic_motion_vectors_device(ArcticRenderer *r, const ArcticScene *scene, float *d_prev_world4, float *d_velocity2);
+
+/* The host form: the same kernel into host memory, with its two further outputs -- bary3 (rows*width*3 floats) and source4 (rows*width*4
+ * uint32: {o, i0, i1, i2}) -- which let a caller restate the pass without a rasteriser of its own.  Any pointer may be NULL.  Synchronous. */
+int arctic_motion_vectors(ArcticRenderer *r, const ArcticScene *scene, float *prev_world4, float *velocity2, float *bary3, uint32_t *source4);
+
+/* Empties M (the next call is a first call) and sets the calls counter to 0.  Frees nothing, touches no device. */
+int arctic_motion_reset(ArcticRenderer *r);
+
+/* What the motion calls hold on this handle: out4 = {bytes of device memory (the snapshots, the table, and the planes of the host form and of
+ * arctic_pass_ray_effects_motion, at their capacities), launches of k_motion, launches of k_motion_snapshot, calls since the last reset}.
+ * {0, 0, 0, 0} until the first call that passes its checks.  Touches no device. */
+int arctic_motion_info(ArcticRenderer *r, uint64_t *out4);
+
+/* The host arbiter (no handle, no GPU): steps 3 to 5 for n pixels in any order, by the very functions the kernel runs.  Per pixel k: bary3 (B),
+ * object[k] (its entry o; 0xFFFFFFFF = no geometry), prev_pos9 (the previous object-space positions of its three vertices, x y z each), and
+ * pixel_xy (px, py).  prev_trs: n_objects x 16 floats, the previous call's trs by entry (an object[k] at or above n_objects has no previous);
+ * prev_proj_view: the previous call's matrix, NULL = M is empty; width, height: the frame (1..16384 each).  Outputs: prev_world4 (n*4 floats,
+ * required with n > 0) and velocity2 (n*2 floats, may be NULL).  ARCTIC_E_INVALID: a frame size out of range, a null array that is needed. */
+int arctic_motion_pixels(uint64_t n, const float *bary3, const uint32_t *object, const float *prev_pos9, const int32_t *pixel_xy, const float *prev_trs,
+                         uint64_t n_objects, const float *prev_proj_view, uint32_t width, uint32_t height, float *prev_world4, float *velocity2);
+
+/* THE ACCUMULATION WITH MOTION.  arctic_accumulate_ambient_occlusion_device's definition with two changes, pw_p and flag_p being pixel p's entry
+ * of a prev_world4 plane (row-major, rows*width float4, as arctic_motion_vectors_device writes it):
+ *   Step 3 reprojects pw_p in place of w_p; unless flag_p >= 1 (a NaN is not) it rejects everything.
+ *   Step 4's plane test is |dot(m_p, w_q - pw_p)| <= plane_dist: both positions lie in the previous frame.
+ * The normal test and the entry written ({w_p, value}, {m_p, N}) are unchanged, so both calls share H and may be mixed from frame to frame (the
+ * launches arctic_ao_history_info counts are those of either kernel, k_ao_accumulate or k_ao_accumulate_motion).  The refusals are the plain
+ * call's, plus ARCTIC_E_INVALID for a null prev_world4 plane (the device form: or one that is not 16-byte aligned).
+ * KNOWN LIMIT, stated and not worked around: a surface that ROTATES between frames is tested with this frame's normal m_p against the stored m_q
+ * of the previous frame; normal_cos is what tolerates that. */
+int arctic_accumulate_ambient_occlusion_motion_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticAoHistory *hist, const float *d_prev_world4,
+                                                      const uint8_t *d_ao_in_u8, uint8_t *d_ao_out_u8);
+
+/* The host form: prev_world4 is rows*width*4 floats, ao_in and ao_out rows*width bytes of host memory (they may be the same).  Synchronous. */
+int arctic_accumulate_ambient_occlusion_motion(ArcticRenderer *r, const ArcticScene *scene, const ArcticAoHistory *hist, const float *prev_world4, const uint8_t *ao_in,
+                                               uint8_t *ao_out);
+
+/* Its host arbiter: arctic_accumulate_pixels with one more input array, prev_world4 (n*4 floats: pw and the flag of every pixel). */
+int arctic_accumulate_pixels_motion(const ArcticAoHistory *hist, uint64_t n, const float *world3, const float *prev_world4, const float *normal3, const uint8_t *geometry,
+                                    const uint8_t *cur, const float *prev_proj_view, uint32_t width, uint32_t height, const float *prev_value, const float *prev_count,
+                                    const float *prev_world3, const float *prev_normal3, uint8_t *out_u8, float *out_value, float *out_count, float *out_world3,
+                                    float *out_normal3);
+
+/* arctic_pass_ray_effects_temporal with two differences: arctic_motion_vectors_device goes into a plane the handle owns, in front of the occlusion,
+ * and the accumulation is the motion form on that plane.  Byte for byte the public calls made by hand.  Every refusal of those calls comes before
+ * anything is enqueued: a refused call writes nothing and leaves H and M as they were.  arctic_pass_ray_effects and
+ * arctic_pass_ray_effects_temporal are what they were. */
+int arctic_pass_ray_effects_motion(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticRayCompose *compose,
+                                   const ArcticAmbientOcclusion *ao, const float *dirs, const ArcticAoHistory *hist, uint8_t *d_out_rgba8);
 
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
