@@ -17,6 +17,7 @@ HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "arctic_hip.h")
 OPTIONS = {"keep_float_output": 1, "count_light_evals": 2, "culling": 3, "debug": 4, "antialias": 5, "hdr16": 6, "ray_refit": 7, "light_pair_runs": 8, "shadow_cache": 9, "visbuffer": 10, "item_table_floor": 11, "light_path": 12, "markers": 13, "shadow_sharded": 14, "frames_in_flight": 15, "tiles_per_wave": 16, "tile_trace": 17, "raster_owner": 18, "tile_order": 19, "order_tail": 20, "sampler": 21, "texture_tiling": 22, "cluster_cull": 23, "small_triangles": 24, "env_lighting": 25, "point_shadow_size": 26, "texture_mips": 27}
 TRACE_ANY, TRACE_BRUTE = 1, 2   # ARCTIC_TRACE_* (include/arctic_hip.h)
 COMPOSE_AO, COMPOSE_REFLECTIONS = 1, 2   # ARCTIC_COMPOSE_*
+TAA_LUMA_WEIGHT, TAA_SOURCE_COMPOSED = 1, 2   # ARCTIC_TAA_*
 ERRORS = {-1: "ARCTIC_E_INVALID", -2: "ARCTIC_E_DEVICE", -3: "ARCTIC_E_NO_DEVICE", -4: "ARCTIC_E_STATE", -5: "ARCTIC_E_CAPACITY"}
 
 _vp, _u32, _u64, _i32, _i64 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_int64
@@ -125,6 +126,15 @@ SIGNATURES = {
     "arctic_accumulate_ambient_occlusion_motion": (_i32, [_vp, _scene, _vp, _vp, _vp, _vp]),
     "arctic_accumulate_pixels_motion": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "arctic_pass_ray_effects_motion": (_i32, [_vp, _scene, _settings, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_set_camera_jitter": (_i32, [_vp, C.c_float, C.c_float]),
+    "arctic_jitter_proj_view": (_i32, [_vp, _u32, _u32, C.c_float, C.c_float]),
+    "arctic_taa_resolve_device": (_i32, [_vp, _settings, _vp, _vp, _vp, _vp]),
+    "arctic_taa_resolve": (_i32, [_vp, _settings, _vp, _vp, _vp, _vp]),
+    "arctic_pass_taa": (_i32, [_vp, _scene, _settings, _vp, _vp]),
+    "arctic_taa_reset": (_i32, [_vp]),
+    "arctic_read_taa": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "arctic_taa_info": (_i32, [_vp, _vp]),
+    "arctic_taa_pixels": (_i32, [_vp, _u64, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "arctic_version": (_i32, []),
     # include/arctic_dist.h: the multi-GPU exchange steps
     "arctic_comm_unique_id": (_i32, [_vp, _vp, _u64]),

@@ -130,6 +130,7 @@ int alloc_targets(ArcticRenderer *r) {
     r->compose.pixels = 0;   // (arctic_read_composed: nothing composed at this size yet)
     r->ao_history.valid = false;   // (the occlusion's history is empty after a resize)
     r->motion.valid = false;       // (... and so is what the previous motion call saw)
+    r->taa.valid = false;          // (... and the anti-aliasing's T; the camera jitter stays)
     r->output_filtered = false;
     return ARCTIC_OK;
 }
@@ -250,6 +251,8 @@ int run_geometry(ArcticRenderer *r, const ArcticScene *sc, bool shadow_pass, hip
     } else {
         const ArcticCamera &c = sc->camera;
         camera_proj_view(c.eye, c.rotation, c.aspect, c.fov_y, c.z_near_far[0], c.z_near_far[1], gp.clip_from_world);
+        // arctic_set_camera_jitter: the matrix that is DRAWN, from here on (the cluster culling below tests against it); with (0, 0) it is not touched
+        if (r->taa.jitter[0] != 0.0f || r->taa.jitter[1] != 0.0f) (void)arctic_jitter_proj_view(gp.clip_from_world, r->width, r->height, r->taa.jitter[0], r->taa.jitter[1]);
         gp.vp_w = (float)r->width; gp.vp_h = (float)r->height;
         gp.sc_x0 = 0; gp.sc_x1 = (int32_t)r->width; gp.sc_y0 = (int32_t)r->row_begin; gp.sc_y1 = (int32_t)r->row_end;
         gp.cull_front = 0;                                       // forward_pass.cpp:143-144

@@ -425,7 +425,24 @@ struct ArcticRenderer {
             return b;
         }
     } motion;
-    PinnedBuf counts;              // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
+    // Temporal anti-aliasing (arctic_taa_resolve_device, arctic_set_camera_jitter; taa.hip): the state T of include/arctic_hip.h -- two sets of one
+    // float4 plane {r, g, b, N}, tile-major like the G-buffer (n_tiles * 64 float4 each): a call reads set `cur` and writes the other, then `cur`
+    // moves.  d_rgba8, d_ldr: the tonemapped result of the handle's rows; d_color, d_vel: the host form's planes, d_vel also arctic_pass_taa's
+    // (its prev_world4 goes into Motion::d_plane).  `written`: recorded behind every call, waited for by the next one if the handle's stream has
+    // changed in between.  Nothing is allocated before the first call that passes its checks; valid: T is not empty (cleared by
+    // arctic_taa_reset and by a resize); width, height: those of the call that wrote set `cur`; own_rgba8: that call wrote d_rgba8, not the
+    // caller's buffer.  jitter: arctic_set_camera_jitter's, in pixels -- host state alone, read by run_geometry's forward branch
+    struct Taa {
+        DevBuf d_t[2], d_rgba8, d_ldr, d_color, d_vel;
+        int cur = 0;
+        bool valid = false, own_rgba8 = false;
+        uint32_t width = 0, height = 0;
+        float jitter[2] = {0.0f, 0.0f};
+        StreamMark written;
+        uint64_t launches = 0, calls = 0;
+        size_t device_bytes() const { return d_t[0].cap + d_t[1].cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_vel.cap; }
+    } taa;
+    PinnedBuf counts;             // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts
     // The streams the handle created, declared LAST: members are destroyed in reverse order, so every stream is waited for and gone before any

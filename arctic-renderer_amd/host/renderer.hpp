@@ -398,6 +398,37 @@ class Renderer {
         return ok(arctic_pass_ray_effects_motion(m_handle, &scene, &settings, &compose, &ao, dirs, &hist, d_out_rgba8));
     }
 
+    // temporal anti-aliasing (include/arctic_hip.h: arctic_set_camera_jitter, arctic_taa_resolve_device and the definition in front of it).
+    // The forward prepass's sub-pixel offset in pixels, each in [-1, 1]; (0, 0), the default, changes nothing
+    [[nodiscard]] bool set_camera_jitter(float jx, float jy) { return ok(arctic_set_camera_jitter(m_handle, jx, jy)); }
+    // the same offset applied to a [col][row] matrix on the host: what a host that draws with its own projection feeds it
+    [[nodiscard]] static bool jitter_proj_view(float *proj_view16, uint32_t width, uint32_t height, float jx, float jy) {
+        return arctic_jitter_proj_view(proj_view16, width, height, jx, jy) == ARCTIC_OK;
+    }
+    // the resolve on device planes (nullptr: the handle's HDR plane, zero velocity, the handle's own output); stream-ordered
+    [[nodiscard]] bool taa_resolve_device(const ArcticSettings &settings, const ArcticTaa &taa, const float *d_hdr_rgb32f, const float *d_velocity2, uint8_t *d_out_rgba8) {
+        return ok(arctic_taa_resolve_device(m_handle, &settings, &taa, d_hdr_rgb32f, d_velocity2, d_out_rgba8));
+    }
+    // the same from and to host memory; synchronous
+    [[nodiscard]] bool taa_resolve(const ArcticSettings &settings, const ArcticTaa &taa, const float *hdr_rgb32f, const float *velocity2, uint8_t *out_rgba8) {
+        return ok(arctic_taa_resolve(m_handle, &settings, &taa, hdr_rgb32f, velocity2, out_rgba8));
+    }
+    // the frame's ONE motion call, then the resolve on the handle's HDR plane
+    [[nodiscard]] bool pass_taa(const ArcticScene &scene, const ArcticSettings &settings, const ArcticTaa &taa, uint8_t *d_out_rgba8) {
+        return ok(arctic_pass_taa(m_handle, &scene, &settings, &taa, d_out_rgba8));
+    }
+    // empties the history; frees nothing
+    [[nodiscard]] bool taa_reset() { return ok(arctic_taa_reset(m_handle)); }
+    // what the latest resolve left, row-major; any pointer may be nullptr
+    [[nodiscard]] bool read_taa(float *ldr_rgb, float *hdr_rgb, float *count, uint8_t *rgba8) { return ok(arctic_read_taa(m_handle, ldr_rgb, hdr_rgb, count, rgba8)); }
+    // {device bytes, launches of k_taa_resolve, calls since the last reset, 0}
+    [[nodiscard]] bool taa_info(uint64_t out4[4]) { return ok(arctic_taa_info(m_handle, out4)); }
+    // the host arbiter: steps 1 to 6 for n pixels, no handle, no GPU
+    [[nodiscard]] static bool taa_pixels(const ArcticTaa &taa, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *cur_rgb, const float *velocity2,
+                                         const float *prev_rgbn, float *out_rgbn) {
+        return arctic_taa_pixels(&taa, n, pixel_xy, width, height, cur_rgb, velocity2, prev_rgbn, out_rgbn) == ARCTIC_OK;
+    }
+
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }
 

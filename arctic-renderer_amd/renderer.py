@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -450,6 +450,64 @@ class Renderer:
         h = _ao_history_arguments(max_history, history_normal_cos, history_plane_dist, min_weight)
         self._check(self.L.arctic_pass_ray_effects_motion(self.h, C.byref(s), C.byref(st), _ptr(c), _ptr(ao), _ptr(d), _ptr(h), C.c_void_p(d_out_ptr) if d_out_ptr else None))
         return self.read_composed(want=("rgba8",))[2] if read and not d_out_ptr else None
+
+    # ---- temporal anti-aliasing (include/arctic_hip.h: arctic_set_camera_jitter, arctic_taa_resolve_device and the definition) --------------------
+    def set_camera_jitter(self, jx, jy):
+        """the forward prepass's sub-pixel offset in pixels, each in [-1, 1]: a point at screen position s is drawn at s + (jx, jy).  (0, 0), the
+        default, changes nothing.  Kept across resize."""
+        self._check(self.L.arctic_set_camera_jitter(self.h, float(jx), float(jy)))
+
+    def taa_resolve_device(self, settings, d_hdr_ptr=None, d_velocity2_ptr=None, d_out_ptr=None, jitter=(0.0, 0.0), max_history=8.0, min_weight=0.0, flags=0, taa=None):
+        """blend a device HDR plane (an int pointer: rows * width * 3 floats; None: the handle's own, the latest shading's or -- flags &
+        TAA_SOURCE_COMPOSED -- the latest composition's) into the handle's history, fetched where d_velocity2_ptr (rows * width float2; None: zero)
+        and this frame's jitter say, then tonemap.  The result stays on the device -- d_out_ptr (rows * width * 4 bytes) or the handle's own
+        buffers: read_taa().  taa: a TAA_DTYPE record instead of the parameters.  Asynchronous on the handle's stream."""
+        st = self._settings(settings)
+        t = _taa_arguments(flags, max_history, min_weight, jitter) if taa is None else taa
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_taa_resolve_device(self.h, C.byref(st), _ptr(t), vp(d_hdr_ptr), vp(d_velocity2_ptr), vp(d_out_ptr)))
+
+    def taa_resolve(self, settings, hdr=None, velocity2=None, jitter=(0.0, 0.0), max_history=8.0, min_weight=0.0, flags=0, taa=None, read=True):
+        """the same from and to host memory: hdr (rows, width, 3) float32 or None, velocity2 (rows, width, 2) float32 or None -> (rows, width, 4)
+        uint8 (read=False: None, the result stays in the handle's buffers); synchronous"""
+        st = self._settings(settings)
+        t = _taa_arguments(flags, max_history, min_weight, jitter) if taa is None else taa
+        c = None if hdr is None else np.ascontiguousarray(hdr, dtype=np.float32)
+        v = None if velocity2 is None else np.ascontiguousarray(velocity2, dtype=np.float32)
+        if (c is not None and c.shape != (self.rows, self.width, 3)) or (v is not None and v.shape != (self.rows, self.width, 2)):
+            raise ArcticError(-1, f"taa_resolve: expected {(self.rows, self.width, 3)} and {(self.rows, self.width, 2)}")
+        out = np.empty((self.rows, self.width, 4), np.uint8) if read else None
+        self._check(self.L.arctic_taa_resolve(self.h, C.byref(st), _ptr(t), _ptr(c), _ptr(v), _ptr(out)))
+        return out
+
+    def pass_taa(self, desc, settings, d_out_ptr=None, jitter=(0.0, 0.0), max_history=8.0, min_weight=0.0, flags=0, taa=None, read=True):
+        """the one call: the frame's ONE motion call into planes the handle owns, then the resolve on the handle's HDR plane: (rows, width, 4)
+        uint8.  read=False or a d_out_ptr leaves the result on the device and returns None."""
+        s, st = self._scene(desc), self._settings(settings)
+        t = _taa_arguments(flags, max_history, min_weight, jitter) if taa is None else taa
+        self._check(self.L.arctic_pass_taa(self.h, C.byref(s), C.byref(st), _ptr(t), C.c_void_p(d_out_ptr) if d_out_ptr else None))
+        return self.read_taa(want=("rgba8",))[3] if read and not d_out_ptr else None
+
+    def taa_reset(self):
+        """empty the history: the next resolve is a first call.  Frees nothing."""
+        self._check(self.L.arctic_taa_reset(self.h))
+
+    def read_taa(self, want=("ldr", "hdr", "count", "rgba8")):
+        """what the latest resolve left, row-major: (ldr (rows, width, 3), hdr (rows, width, 3), count (rows, width) float32, rgba8 (rows, width,
+        4) uint8); None for what was not asked for.  ArcticError (STATE) while the history is empty."""
+        n = (self.rows, self.width)
+        ldr = np.empty(n + (3,), np.float32) if "ldr" in want else None
+        hdr = np.empty(n + (3,), np.float32) if "hdr" in want else None
+        count = np.empty(n, np.float32) if "count" in want else None
+        rgba = np.empty(n + (4,), np.uint8) if "rgba8" in want else None
+        self._check(self.L.arctic_read_taa(self.h, _ptr(ldr), _ptr(hdr), _ptr(count), _ptr(rgba)))
+        return ldr, hdr, count, rgba
+
+    def taa_info(self):
+        """(device bytes, launches of k_taa_resolve, calls since the last reset, 0): all 0 until the first call"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_taa_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
 
     def ray_scene_info(self):
         """(triangles stored, nodes, builds so far, depth) of the cached acceleration structure"""
@@ -978,6 +1036,59 @@ def accumulate_pixels_motion(world, prev_world4, normal, geometry, cur, prev_pro
     if rc < 0:
         raise ArcticError(rc, "accumulate_pixels_motion")
     return out
+
+
+def _taa_arguments(flags, max_history, min_weight, jitter):
+    """one TAA_DTYPE record; the library checks every value"""
+    t = np.zeros(1, TAA_DTYPE)
+    t["flags"], t["max_history"], t["min_weight"], t["jitter"] = flags, max_history, min_weight, jitter
+    return t
+
+
+def taa_pixels(pixel_xy, cur, velocity2=None, prev=None, jitter=(0.0, 0.0), max_history=8.0, min_weight=0.0, flags=0, taa=None):
+    """arctic_taa_pixels: steps 1 to 6 of the resolve of include/arctic_hip.h on the host, for n pixels in any order -- pixel_xy (n, 2) int32, cur
+    the WHOLE frame's colour (height, width, 3), velocity2 (n, 2) or None = zero, prev the whole frame's previous {r, g, b, N} (height, width, 4)
+    or None = an empty history.  Returns (n, 4) float32 {out, N}."""
+    xy = np.ascontiguousarray(pixel_xy, dtype=np.int32).reshape(-1, 2)
+    c = np.ascontiguousarray(cur, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ArcticError(-1, "taa_pixels: cur is the whole frame, (height, width, 3)")
+    height, width = c.shape[:2]
+    n = len(xy)
+    v = None if velocity2 is None else np.ascontiguousarray(velocity2, dtype=np.float32).reshape(-1, 2)
+    pv = None if prev is None else np.ascontiguousarray(prev, dtype=np.float32)
+    if (v is not None and len(v) != n) or (pv is not None and pv.shape != (height, width, 4)):
+        raise ArcticError(-1, "taa_pixels: one velocity per pixel, and the previous history is (height, width, 4)")
+    t = _taa_arguments(flags, max_history, min_weight, jitter) if taa is None else taa
+    out = np.empty((n, 4), np.float32)
+    rc = binding.lib().arctic_taa_pixels(_ptr(t), n, _ptr(xy) if n else None, int(width), int(height), _ptr(c), _ptr(v) if n else None, _ptr(pv), _ptr(out) if n else None)
+    if rc < 0:
+        raise ArcticError(rc, "taa_pixels")
+    return out
+
+
+def jitter_proj_view(m, w, h, jx, jy):
+    """arctic_jitter_proj_view: the (4, 4) [col][row] matrix m with the sub-pixel offset (jx, jy) pixels of a w x h frame applied -- the matrix
+    the forward prepass draws with under set_camera_jitter(jx, jy).  Returns a new (4, 4) float32 array."""
+    out = np.array(m, dtype=np.float32).reshape(16).copy()
+    rc = binding.lib().arctic_jitter_proj_view(_ptr(out), int(w), int(h), float(jx), float(jy))
+    if rc < 0:
+        raise ArcticError(rc, "jitter_proj_view")
+    return out.reshape(4, 4)
+
+
+def taa_jitter(frame, period=8):
+    """the sample offset of frame `frame`: point number frame % period + 1 of the Halton sequence in bases (2, 3), minus 0.5 in each coordinate --
+    (jx, jy) in [-0.5, 0.5) pixels, for set_camera_jitter and for the resolve's `jitter`"""
+    def halton(i, base):
+        f, x = 1.0, 0.0
+        while i > 0:
+            f /= base
+            x += f * (i % base)
+            i //= base
+        return x
+    i = int(frame) % int(period) + 1
+    return halton(i, 2) - 0.5, halton(i, 3) - 0.5
 
 
 def ao_directions(n_rays, pattern, seed=0):

@@ -1355,6 +1355,111 @@ int arctic_accumulate_pixels_motion(const ArcticAoHistory *hist, uint64_t n, con
 int arctic_pass_ray_effects_motion(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticRayCompose *compose,
                                    const ArcticAmbientOcclusion *ao, const float *dirs, const ArcticAoHistory *hist, uint8_t *d_out_rgba8);
 
+/* ---- temporal anti-aliasing: camera jitter and a history resolve (no counterpart in the reference) ------------------------------------------------
+ * The frame is point-sampled at pixel centres.  Two pieces turn a sequence of frames into an anti-aliased one: a sub-pixel offset of the sample
+ * position that changes from frame to frame, and a resolve in front of the tonemapper that blends each frame's float HDR colour into a history
+ * fetched where the surface point WAS (velocity2 of arctic_motion_vectors_device).  Nothing in the passes or in the other calls changes: a handle
+ * that never makes these calls renders the same bytes and allocates nothing for them.
+ *
+ * THE JITTER.  ArcticCamera is byte-compatible with the reference and has no room for it, so the handle keeps it. */
+
+/* Sets the handle's camera jitter (jx, jy), in pixels; both finite and in [-1, 1], else ARCTIC_E_INVALID.  The default is (0, 0).  It applies to
+ * the forward prepass only (arctic_pass_gbuffer, and so arctic_render_frame): the matrix that is drawn is arctic_jitter_proj_view of the
+ * camera's, and the cluster culling tests against that matrix.  The shadow pass, the cube faces, arctic_frame_constants, the motion calls and the
+ * occlusion history keep the unjittered matrix.  arctic_resize keeps the jitter.  With (0, 0) arctic_jitter_proj_view is NOT CALLED: the matrix,
+ * and so every byte of every path, is what it was.  Touches no device.
+ * KNOWN LIMIT, stated and not worked around: the occlusion history and k_motion reproject through unjittered matrices, so under jitter their
+ * screen positions are off by less than one pixel from the drawn samples.  velocity2 of a still scene is -j, and the resolve's step 3 adds j back. */
+int arctic_set_camera_jitter(ArcticRenderer *r, float jx, float jy);
+
+/* A pure host function (no device, no handle), the one the forward prepass calls: in arctic_frame_constants' layout [col][row], for c = 0..3
+ *     m[4c+0] = m[4c+0] + kx * m[4c+3]          m[4c+1] = m[4c+1] - ky * m[4c+3]          kx = (2*jx)/W,  ky = (2*jy)/H
+ * in fp32, one rounding per operation.  A point the unjittered matrix puts at screen position s is drawn at s + j.  ARCTIC_E_INVALID (nothing
+ * written): a null matrix, a frame size outside 1..16384, a jitter that is not finite or outside [-1, 1]. */
+int arctic_jitter_proj_view(float *proj_view16, uint32_t width, uint32_t height, float jx, float jy);
+
+/* THE RESOLVE: THE DEFINITION.  Bit for bit: fp32 throughout, one rounding per operation in the written order, no contraction, IEEE division.
+ * min(a, b) is (b < a) ? b : a and max(a, b) is (a < b) ? b : a.
+ * STATE.  T is one float4 plane per pixel, {r, g, b, N}: the resolved HDR colour and the number of frames it stands for.  There are TWO SETS, and
+ *   a call reads one and writes the other: 32 bytes per pixel, allocated by the first call that passes its checks.  T is EMPTY before the first
+ *   call, after arctic_taa_reset and after arctic_resize.
+ * INPUTS.  The current HDR colour plane C (rows x width x 3 floats, row-major); optionally velocity2 as arctic_motion_vectors_device writes it
+ *   (NULL: all zero); and ArcticTaa.  The resolve reads NO G-BUFFER: it works after every shading variant (image-based ambient, mip chains,
+ *   material extras, spot and cube lights) and refuses none of them.
+ * PER PIXEL p = (px, py); W and H are the frame size as floats.
+ *   1. c = C[p].  The neighbourhood box: for dy = -1, 0, 1 and dx = -1, 0, 1, in that order, q = (clamp(px+dx, 0, W-1), clamp(py+dy, 0, H-1));
+ *      lo and hi start at the first C[q] and fold per channel, lo = (x < lo) ? x : lo and hi = (x > hi) ? x : hi: a NaN neighbour is ignored.
+ *   2. T is empty:  N = 1, out = c.
+ *   3. Otherwise v = velocity2[p], or (0, 0).  hx = ((px + 0.5) + vx) + jx, hy likewise, j being ArcticTaa::jitter.  gx = hx - 0.5;
+ *      ix = floor(gx); ax = gx - ix; y likewise.  Reject everything (N = 1, out = c) unless hx and hy are finite, -1 <= ix <= W-1 and
+ *      -1 <= iy <= H-1, tested in float before any conversion.
+ *   4. Four taps (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1) with the weights (1-ax)(1-ay), ax(1-ay), (1-ax)ay, ax*ay.  A tap is accepted iff
+ *      it lies inside the frame and its stored N_q > 0; a rejected tap is a SELECT: its weight is 0 and its history is not looked at.
+ *      S = ((k0 + k1) + k2) + k3; R, G, B and Cn are the same ordered sums of k*r_q, k*g_q, k*b_q and k*N_q.
+ *      If !(S > min_weight):  N = 1, out = c.
+ *   5. Otherwise h = {R, G, B} / S and hn = Cn / S, then the clamp, per channel with selects: h = (h < lo) ? lo : h, then h = (h > hi) ? hi : h.
+ *   6. N = min(hn + 1, max_history); a = 1 / N.
+ *      Without ARCTIC_TAA_LUMA_WEIGHT:  out = h + (c - h) * a.
+ *      With it:  wc = 1 / (1 + max(max(max(c.r, c.g), c.b), 0)), wh the same of h;  kc = a * wc;  kh = (1 - a) * wh;
+ *        out = (c*kc + h*kh) / (kc + kh)  -- which keeps one HDR sample from owning an edge.
+ *   7. Store {out, N}.  Then post_process of `out` under `settings`, as k_compose carries it out: float LDR and RGBA8.
+ *   {out, N} is defined bit for bit; the tonemapped planes are held to the project's standing bar (1e-4 of the float64 post_process).
+ * WHAT FOLLOWS.  On a still scene drawn with jitter j, velocity2 is -j and step 3 lands on the pixel's own centre: with max_history at or above
+ *   the frame count and no luma weight, `out` is the running mean of the frames.
+ * KNOWN LIMITS, stated and not worked around.  A pixel without geometry has velocity2 = 0, so the sky is not reprojected under camera rotation;
+ *   the box clamp bounds what it keeps.  There is no sharpening, no motion blur, and a shard cannot resolve (no halo exchange).
+ * Refusals, in this order; every refusal comes before anything is enqueued, and a refused call writes nothing and leaves T as it was.
+ *   ARCTIC_E_INVALID: a null handle, settings or ArcticTaa; unknown flag bits; a field outside the ranges below, or a NaN; a device plane that
+ *     is misaligned: 4 bytes for C and RGBA8, 8 bytes for velocity2.
+ *   ARCTIC_E_STATE: a handle that does not own the whole frame (the taps' rows are elsewhere); and, with a NULL colour plane:
+ *     ARCTIC_OPT_KEEP_FLOAT_OUTPUT off; no shading since it was turned on or since the last resize; under ARCTIC_TAA_SOURCE_COMPOSED no
+ *     composition since the last resize; ARCTIC_OPT_HDR16 = 1. */
+#define ARCTIC_TAA_LUMA_WEIGHT      1u
+#define ARCTIC_TAA_SOURCE_COMPOSED  2u   /* C = the latest composition's HDR plane instead of the latest shading's */
+typedef struct ArcticTaa {               /* 32 bytes */
+    uint32_t flags;
+    float max_history;                   /* 1..65536, finite; 1 = no accumulation */
+    float min_weight;                    /* [0, 1) */
+    float jitter[2];                     /* THIS frame's jitter, pixels, finite, |j| <= 1 */
+    uint32_t reserved[3];                /* 0 */
+} ArcticTaa;
+
+/* One call of the definition on DEVICE planes, in the handle's rows.  d_hdr_rgb32f: rows*width*3 floats, NULL = the handle's own plane (the
+ * latest shading's, or under ARCTIC_TAA_SOURCE_COMPOSED the latest composition's); d_velocity2: rows*width float2, NULL = zero; d_out_rgba8:
+ * rows*width*4 bytes, NULL = the handle's own buffer (arctic_read_taa).  No plane may alias another.  Stream-ordered on the handle's stream; a
+ * warm call allocates nothing and does not synchronise. */
+int arctic_taa_resolve_device(ArcticRenderer *r, const ArcticSettings *settings, const ArcticTaa *taa, const float *d_hdr_rgb32f, const float *d_velocity2,
+                              uint8_t *d_out_rgba8);
+
+/* The host form: the same kernel from and to host memory (any pointer but settings and taa may be NULL, with the meanings above; a NULL output:
+ * the result stays in the handle's buffers).  Synchronous. */
+int arctic_taa_resolve(ArcticRenderer *r, const ArcticSettings *settings, const ArcticTaa *taa, const float *hdr_rgb32f, const float *velocity2, uint8_t *out_rgba8);
+
+/* The one call: arctic_motion_vectors_device into planes the handle owns, then the resolve on the handle's HDR plane with that velocity2.  Byte
+ * for byte the two calls made by hand.  It is the frame's ONE motion call: a caller who also wants arctic_pass_ray_effects_motion drives the
+ * calls by hand and shares the planes.  Every refusal of both calls comes before anything is enqueued. */
+int arctic_pass_taa(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticTaa *taa, uint8_t *d_out_rgba8);
+
+/* Empties T (the next call is a first call) and sets the calls counter to 0.  Frees nothing, touches no device. */
+int arctic_taa_reset(ArcticRenderer *r);
+
+/* What the latest resolve left, row-major whatever the layout on the device: float LDR and the resolved HDR colour (rows*width*3 floats each), N
+ * (rows*width floats) and the handle's own RGBA8.  Any pointer may be NULL.  Synchronises.  ARCTIC_E_STATE while T is empty, and for rgba8 when
+ * the latest resolve wrote the caller's buffer. */
+int arctic_read_taa(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, float *count, uint8_t *rgba8);
+
+/* What the calls hold on this handle: out4 = {bytes of device memory, launches of k_taa_resolve, calls since the last reset, 0}.  All 0 until the
+ * first call that passes its checks.  Touches no device. */
+int arctic_taa_info(ArcticRenderer *r, uint64_t *out4);
+
+/* The host arbiter (no handle, no GPU): steps 1 to 6 for n pixels in any order, by the very functions the kernel runs.  pixel_xy: (px, py) per
+ * pixel, inside the frame; cur_rgb: the WHOLE frame's C (height*width*3 floats, row-major); velocity2: n*2 floats, one per listed pixel, or NULL
+ * = zero; prev_rgbn: the whole frame's previous T (height*width*4 floats, row-major) or NULL = T is empty; out_rgbn: n*4 floats {out, N}.
+ * ARCTIC_E_INVALID (nothing written): what the resolve refuses of ArcticTaa, a frame size outside 1..16384, a pixel outside the frame, a null
+ * array that is needed. */
+int arctic_taa_pixels(const ArcticTaa *taa, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *cur_rgb, const float *velocity2,
+                      const float *prev_rgbn, float *out_rgbn);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row
