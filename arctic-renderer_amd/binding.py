@@ -18,6 +18,7 @@ OPTIONS = {"keep_float_output": 1, "count_light_evals": 2, "culling": 3, "debug"
 TRACE_ANY, TRACE_BRUTE = 1, 2   # ARCTIC_TRACE_* (include/arctic_hip.h)
 COMPOSE_AO, COMPOSE_REFLECTIONS = 1, 2   # ARCTIC_COMPOSE_*
 TAA_LUMA_WEIGHT, TAA_SOURCE_COMPOSED = 1, 2   # ARCTIC_TAA_*
+MB_DITHER, MB_SOURCE_COMPOSED, MB_SOURCE_TAA = 1, 2, 4   # ARCTIC_MB_*
 ERRORS = {-1: "ARCTIC_E_INVALID", -2: "ARCTIC_E_DEVICE", -3: "ARCTIC_E_NO_DEVICE", -4: "ARCTIC_E_STATE", -5: "ARCTIC_E_CAPACITY"}
 
 _vp, _u32, _u64, _i32, _i64 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_int64
@@ -135,6 +136,14 @@ SIGNATURES = {
     "arctic_read_taa": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "arctic_taa_info": (_i32, [_vp, _vp]),
     "arctic_taa_pixels": (_i32, [_vp, _u64, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "arctic_motion_blur_device": (_i32, [_vp, _settings, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_motion_blur": (_i32, [_vp, _settings, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_depth_plane_device": (_i32, [_vp, _vp]),
+    "arctic_pass_motion_blur": (_i32, [_vp, _scene, _settings, _vp, _vp]),
+    "arctic_read_motion_blur": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_motion_blur_info": (_i32, [_vp, _vp]),
+    "arctic_motion_blur_prepare": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_motion_blur_pixels": (_i32, [_vp, _u64, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "arctic_version": (_i32, []),
     # include/arctic_dist.h: the multi-GPU exchange steps
     "arctic_comm_unique_id": (_i32, [_vp, _vp, _u64]),

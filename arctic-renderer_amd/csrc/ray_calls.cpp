@@ -1,8 +1,8 @@
 // ray_calls.cpp -- the ray family of the C-ABI (include/arctic_hip.h): ray queries, refit and re-split of their structure, sun visibility, ambient
 // occlusion and its temporal accumulation, hit attributes, hit shading, the reflection plane, the composition of the two planes into the shaded frame,
-// the motion vectors, and the temporal anti-aliasing resolve that reads them.
+// the motion vectors, the temporal anti-aliasing resolve that reads them, and the motion blur.
 //
-// Owns, of the handle (renderer_state.h): ArcticRenderer::RayScene, AmbientOcclusion, AoHistory, HitScene, Compose, Motion and Taa -- nothing outside this unit touches
+// Owns, of the handle (renderer_state.h): ArcticRenderer::RayScene, AmbientOcclusion, AoHistory, HitScene, Compose, Motion, Taa and MotionBlur -- nothing outside this unit touches
 // them but arctic_set_option, which writes RayScene::refit_opt, run_geometry, which reads Taa::jitter, and a resize, which empties the histories.  Reads, of the handle's other state: the G-buffer planes (resolved here from the visibility
 // plane when a frame was shaded from it), the shadow map, the lights, the textures, the environment, the meshes and -- the composition -- the float
 // HDR plane of the latest shading.  Enqueues on r->stream only.
@@ -19,6 +19,7 @@
 #include "ao_history.h"
 #include "motion.h"
 #include "taa.h"
+#include "motion_blur.h"
 
 namespace {
 
@@ -1014,6 +1015,7 @@ int taa_planes(ArcticRenderer *r, const ArcticSettings *st, const TaaDesc &d, co
     HIPCHECK(r, launch_taa_resolve(p, r->stream));
     HIPCHECK(r, T.written.record(r->stream));
     T.cur = to; T.valid = true; T.width = r->width; T.height = r->height; T.own_rgba8 = d_out == nullptr;
+    T.by_pass = false;   // (arctic_pass_taa sets it behind this)
     ++T.launches; ++T.calls;
     return ARCTIC_OK;
 }
@@ -1062,7 +1064,9 @@ int arctic_pass_taa(ArcticRenderer *r, const ArcticScene *scene, const ArcticSet
     HIPCHECK(r, r->motion.d_plane.ensure(px * 16));
     HIPCHECK(r, r->taa.d_vel.ensure(px * 8));
     if ((rc = motion_planes(r, scene, r->motion.d_plane.as<float4>(), r->taa.d_vel.as<float2>(), nullptr, nullptr)) != ARCTIC_OK) return rc;
-    return taa_planes(r, settings, d, nullptr, r->taa.d_vel.p, d_out_rgba8);
+    if ((rc = taa_planes(r, settings, d, nullptr, r->taa.d_vel.p, d_out_rgba8)) != ARCTIC_OK) return rc;
+    r->taa.by_pass = true;   // (Taa::d_vel is this frame's velocity2: arctic_pass_motion_blur under ARCTIC_MB_SOURCE_TAA reads it)
+    return ARCTIC_OK;
 }
 
 int arctic_taa_reset(ArcticRenderer *r) {
@@ -1102,6 +1106,177 @@ int arctic_taa_info(ArcticRenderer *r, uint64_t *out4) {
     if (!r) return ARCTIC_E_INVALID;
     if (!out4) return r->fail(ARCTIC_E_INVALID, "taa_info: null");
     out4[0] = r->taa.device_bytes(); out4[1] = r->taa.launches; out4[2] = r->taa.calls; out4[3] = 0;
+    return ARCTIC_OK;
+}
+
+// ---- motion blur (the definition: include/arctic_hip.h; the arithmetic: motion_blur.h; the kernels: motion_blur.hip) ------------------------------
+namespace {
+// what the calls refuse with ARCTIC_E_INVALID, in the header's order; color, vel, depth, out: the planes the kernels will read and write (null
+// colour, depth, output: the handle's own, zero, the handle's own); align: whether they are device planes, whose alignment the loads and stores need
+int mb_checks(ArcticRenderer *r, const ArcticSettings *st, const ArcticMotionBlur *mb, const void *color, const void *vel, const void *depth, const void *out, bool align,
+              MotionBlurDesc &d, const char *who) {
+    if (!st || !mb) return r->fail(ARCTIC_E_INVALID, "%s: null settings or parameters", who);
+    std::memcpy(&d, mb, sizeof d);
+    if (const char *why = motion_blur_refusal(&d)) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
+    if (!vel) return r->fail(ARCTIC_E_INVALID, "%s: null velocity2", who);
+    if (align && ((((uintptr_t)color | (uintptr_t)depth | (uintptr_t)out) & 3u) || ((uintptr_t)vel & 7u)))
+        return r->fail(ARCTIC_E_INVALID, "%s: the colour plane, the depth and the output must be 4-byte aligned, velocity2 8-byte aligned", who);
+    return ARCTIC_OK;
+}
+// T is not empty: arctic_read_taa's condition
+bool taa_holds_a_frame(const ArcticRenderer *r) { return r->taa.valid && r->taa.width == r->width && r->taa.height == r->height; }
+// ... and with ARCTIC_E_STATE: no side effect.  own_color: the colour plane is the handle's (d.flags says which)
+int mb_states(ArcticRenderer *r, const MotionBlurDesc &d, bool own_color, const char *who) {
+    if (r->rows() != r->height)
+        return r->fail(ARCTIC_E_STATE, "%s: the gather's taps need the whole frame, this handle owns %u of %u rows (its neighbours' rows are on other shards)", who, r->rows(), r->height);
+    if (!own_color) return ARCTIC_OK;
+    if (d.flags & MB_SOURCE_TAA) {
+        if (!taa_holds_a_frame(r)) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_MB_SOURCE_TAA: the anti-aliasing's history is empty (no resolve yet, or none since the last reset or resize)", who);
+        return ARCTIC_OK;
+    }
+    TaaDesc t = {};
+    t.flags = (d.flags & MB_SOURCE_COMPOSED) ? TAA_SOURCE_COMPOSED : 0u;
+    return taa_states(r, t, true, who);
+}
+// the handle's buffers and the three launches: device pointers throughout.  d_color: null = the handle's own plane, per d.flags; d_depth: null =
+// zero; d_out: the caller's RGBA8, or null = the handle's own.  The handle's state moves only behind launches that were enqueued
+int mb_planes(ArcticRenderer *r, const ArcticSettings *st, const MotionBlurDesc &d, const float *d_color, const void *d_vel, const float *d_depth, uint8_t *d_out) {
+    ArcticRenderer::MotionBlur &B = r->motion_blur;
+    const uint64_t n = std::max<uint64_t>((uint64_t)r->rows() * r->width, 1), tiles = std::max<uint64_t>(r->n_tiles(), 1);
+    HIPCHECK(r, B.d_prep.ensure(n * 8));
+    HIPCHECK(r, B.d_tile.ensure(tiles * 8));
+    HIPCHECK(r, B.d_neighbour.ensure(tiles * 8));
+    HIPCHECK(r, B.d_hdr.ensure(n * 12));
+    if (!d_out) HIPCHECK(r, B.d_rgba8.ensure(n * 4));
+    HIPCHECK(r, B.d_ldr.ensure(n * 12));
+    HIPCHECK(r, B.written.ensure(hipEventDisableTiming));
+    HIPCHECK(r, B.written.wait(r->stream));   // (recorded on another stream: arctic_set_stream came in between; on this one: stream order does it)
+    MotionBlurParams p = {};
+    if (d_color) p.color = d_color;
+    else if (d.flags & MB_SOURCE_TAA) {
+        HIPCHECK(r, r->taa.written.wait(r->stream));   // (the resolve that wrote T, if the stream has changed since)
+        p.color = r->taa.d_t[r->taa.cur].p; p.color_taa = true;
+    } else p.color = (d.flags & MB_SOURCE_COMPOSED) ? r->compose.d_hdr.as<float>() : r->d_hdr.as<float>();
+    p.velocity = d_vel; p.depth = d_depth;
+    p.prep = B.d_prep.p; p.tile_max = B.d_tile.p; p.neighbour_max = B.d_neighbour.p;
+    p.out_hdr = B.d_hdr.as<float>(); p.out_rgba8 = reinterpret_cast<uint32_t *>(d_out ? d_out : B.d_rgba8.as<uint8_t>()); p.out_ldr = B.d_ldr.as<float>();
+    p.tiles_x = r->tiles_x; p.tiles_y = r->tiles_y; p.width = r->width; p.rows = r->rows();
+    p.tm = st->tm_method; p.inv_gamma = 1.0f / st->gamma; p.exposure = st->exposure;
+    p.d = d;
+    B.valid = false;   // (until all three are enqueued: a failure between leaves nothing to read, never half this call's)
+    HIPCHECK(r, launch_mb_tile_max(p, r->stream));
+    HIPCHECK(r, launch_mb_neighbour_max(p, r->stream));
+    HIPCHECK(r, launch_motion_blur(p, r->stream));
+    HIPCHECK(r, B.written.record(r->stream));
+    B.valid = true; B.width = r->width; B.height = r->height; B.own_rgba8 = d_out == nullptr;
+    ++B.launches; ++B.calls;
+    return ARCTIC_OK;
+}
+// arctic_depth_plane_device behind its refusals
+int mb_depth_plane(ArcticRenderer *r, float *d_depth) {
+    HIPCHECK(r, launch_mb_depth(r->d_vis().as<unsigned long long>(), d_depth, r->tiles_x, r->tiles_y, r->width, r->rows(), r->row0_in_tile, r->stream));
+    return ARCTIC_OK;
+}
+}  // namespace
+
+int arctic_motion_blur_device(ArcticRenderer *r, const ArcticSettings *settings, const ArcticMotionBlur *mb, const float *d_hdr_rgb32f, const float *d_velocity2,
+                              const float *d_depth, uint8_t *d_out_rgba8) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "motion_blur_device";
+    MotionBlurDesc d;
+    int rc = mb_checks(r, settings, mb, d_hdr_rgb32f, d_velocity2, d_depth, d_out_rgba8, true, d, who);
+    if (rc || (rc = mb_states(r, d, d_hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
+    return mb_planes(r, settings, d, d_hdr_rgb32f, d_velocity2, d_depth, d_out_rgba8);
+}
+
+int arctic_motion_blur(ArcticRenderer *r, const ArcticSettings *settings, const ArcticMotionBlur *mb, const float *hdr_rgb32f, const float *velocity2, const float *depth,
+                       uint8_t *out_rgba8) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "motion_blur";
+    MotionBlurDesc d;
+    int rc = mb_checks(r, settings, mb, hdr_rgb32f, velocity2, depth, out_rgba8, false, d, who);
+    if (rc || (rc = mb_states(r, d, hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
+    ArcticRenderer::MotionBlur &B = r->motion_blur;
+    const size_t px = (size_t)r->rows() * r->width;
+    HIPCHECK(r, B.written.ensure(hipEventDisableTiming));
+    HIPCHECK(r, B.written.wait(r->stream));   // (the copies below overwrite planes the previous call read)
+    if (hdr_rgb32f) {
+        HIPCHECK(r, B.d_color.ensure(std::max<size_t>(px, 1) * 12));
+        HIPCHECK(r, hipMemcpyAsync(B.d_color.p, hdr_rgb32f, px * 12, hipMemcpyHostToDevice, r->stream));
+    }
+    HIPCHECK(r, B.d_vel.ensure(std::max<size_t>(px, 1) * 8));
+    HIPCHECK(r, hipMemcpyAsync(B.d_vel.p, velocity2, px * 8, hipMemcpyHostToDevice, r->stream));
+    if (depth) {
+        HIPCHECK(r, B.d_depth.ensure(std::max<size_t>(px, 1) * 4));
+        HIPCHECK(r, hipMemcpyAsync(B.d_depth.p, depth, px * 4, hipMemcpyHostToDevice, r->stream));
+    }
+    if ((rc = mb_planes(r, settings, d, hdr_rgb32f ? B.d_color.as<float>() : nullptr, B.d_vel.p, depth ? B.d_depth.as<float>() : nullptr, nullptr)) != ARCTIC_OK) return rc;
+    if (out_rgba8) return read_back(r, out_rgba8, B.d_rgba8, px * 4, hdr_rgb32f == nullptr);
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    return hdr_rgb32f ? ARCTIC_OK : check_item_overflow(r);
+}
+
+int arctic_depth_plane_device(ArcticRenderer *r, float *d_depth) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "depth_plane_device";
+    if (!d_depth || ((uintptr_t)d_depth & 3u)) return r->fail(ARCTIC_E_INVALID, "%s: the plane is null or not 4-byte aligned", who);
+    if (!r->have_vis) return r->fail(ARCTIC_E_STATE, "%s: no visibility plane (arctic_pass_gbuffer or a frame first; arctic_write_gbuffer leaves none)", who);
+    int rc = select_device(r);
+    if (rc) return rc;
+    return mb_depth_plane(r, d_depth);
+}
+
+int arctic_pass_motion_blur(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticMotionBlur *mb, uint8_t *d_out_rgba8) {
+    if (!r) return ARCTIC_E_INVALID;
+    const char *who = "pass_motion_blur";
+    alignas(16) static const char own_plane[16] = {};   // (the planes are the handle's own: never null, always aligned)
+    MotionBlurDesc d;
+    int rc = mb_checks(r, settings, mb, nullptr, own_plane, nullptr, d_out_rgba8, true, d, who);
+    // every refusal of the motion call and of the depth plane, in front of the first launch
+    if (rc || (rc = motion_refusal(r, scene, own_plane, who)) != ARCTIC_OK || (rc = mb_states(r, d, true, who)) != ARCTIC_OK) return rc;
+    const bool from_taa = (d.flags & MB_SOURCE_TAA) != 0;
+    if (from_taa && !r->taa.by_pass)
+        return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_MB_SOURCE_TAA: the handle's latest anti-aliasing call was not arctic_pass_taa, so it holds no velocity2 of this frame", who);
+    if ((rc = select_device(r)) != ARCTIC_OK) return rc;
+    ArcticRenderer::MotionBlur &B = r->motion_blur;
+    const size_t px = std::max<size_t>((size_t)r->rows() * r->width, 1);
+    HIPCHECK(r, B.written.ensure(hipEventDisableTiming));
+    HIPCHECK(r, B.written.wait(r->stream));   // (the motion call and the depth below overwrite planes the previous call read)
+    HIPCHECK(r, B.d_depth.ensure(px * 4));
+    const void *d_vel = r->taa.d_vel.p;
+    if (!from_taa) {
+        HIPCHECK(r, r->motion.d_plane.ensure(px * 16));
+        HIPCHECK(r, B.d_vel.ensure(px * 8));
+        if ((rc = motion_planes(r, scene, r->motion.d_plane.as<float4>(), B.d_vel.as<float2>(), nullptr, nullptr)) != ARCTIC_OK) return rc;
+        d_vel = B.d_vel.p;
+    }
+    if ((rc = mb_depth_plane(r, B.d_depth.as<float>())) != ARCTIC_OK) return rc;
+    return mb_planes(r, settings, d, nullptr, d_vel, B.d_depth.as<float>(), d_out_rgba8);
+}
+
+int arctic_read_motion_blur(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, float *tile_max2, float *neighbour_max2, float *prepared2) {
+    if (!r) return ARCTIC_E_INVALID;
+    const ArcticRenderer::MotionBlur &B = r->motion_blur;
+    if (!B.valid || B.width != r->width || B.height != r->height || r->rows() != r->height)
+        return r->fail(ARCTIC_E_STATE, "read_motion_blur: nothing blurred yet, or not since the last resize");
+    if (rgba8 && !B.own_rgba8) return r->fail(ARCTIC_E_STATE, "read_motion_blur: the latest call wrote the caller's RGBA8 buffer, not the handle's");
+    int rc = select_device(r);
+    if (rc) return rc;
+    HIPCHECK(r, hipStreamSynchronize(r->stream));
+    const size_t px = (size_t)r->rows() * r->width, tiles = r->n_tiles();
+    if (ldr_rgb) HIPCHECK(r, hipMemcpy(ldr_rgb, B.d_ldr.p, px * 12, hipMemcpyDeviceToHost));
+    if (hdr_rgb) HIPCHECK(r, hipMemcpy(hdr_rgb, B.d_hdr.p, px * 12, hipMemcpyDeviceToHost));
+    if (rgba8) HIPCHECK(r, hipMemcpy(rgba8, B.d_rgba8.p, px * 4, hipMemcpyDeviceToHost));
+    if (tile_max2) HIPCHECK(r, hipMemcpy(tile_max2, B.d_tile.p, tiles * 8, hipMemcpyDeviceToHost));
+    if (neighbour_max2) HIPCHECK(r, hipMemcpy(neighbour_max2, B.d_neighbour.p, tiles * 8, hipMemcpyDeviceToHost));
+    if (prepared2) HIPCHECK(r, hipMemcpy(prepared2, B.d_prep.p, px * 8, hipMemcpyDeviceToHost));
+    return ARCTIC_OK;
+}
+
+int arctic_motion_blur_info(ArcticRenderer *r, uint64_t *out4) {
+    if (!r) return ARCTIC_E_INVALID;
+    if (!out4) return r->fail(ARCTIC_E_INVALID, "motion_blur_info: null");
+    out4[0] = r->motion_blur.device_bytes(); out4[1] = r->motion_blur.launches; out4[2] = r->motion_blur.calls; out4[3] = 0;
     return ARCTIC_OK;
 }
 

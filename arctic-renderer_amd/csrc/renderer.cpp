@@ -131,6 +131,7 @@ int alloc_targets(ArcticRenderer *r) {
     r->ao_history.valid = false;   // (the occlusion's history is empty after a resize)
     r->motion.valid = false;       // (... and so is what the previous motion call saw)
     r->taa.valid = false;          // (... and the anti-aliasing's T; the camera jitter stays)
+    r->motion_blur.valid = false;  // (... and what the latest motion blur left)
     r->output_filtered = false;
     return ARCTIC_OK;
 }

@@ -436,12 +436,27 @@ struct ArcticRenderer {
         DevBuf d_t[2], d_rgba8, d_ldr, d_color, d_vel;
         int cur = 0;
         bool valid = false, own_rgba8 = false;
+        bool by_pass = false;   // the call that wrote set `cur` was arctic_pass_taa: d_vel holds that frame's velocity2 (arctic_pass_motion_blur reads it)
         uint32_t width = 0, height = 0;
         float jitter[2] = {0.0f, 0.0f};
         StreamMark written;
         uint64_t launches = 0, calls = 0;
         size_t device_bytes() const { return d_t[0].cap + d_t[1].cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_vel.cap; }
     } taa;
+    // Motion blur (arctic_motion_blur_device; motion_blur.hip): d_prep is P of include/arctic_hip.h (float2 per pixel, row-major), d_tile and
+    // d_neighbour the two maxima (float2 per tile), d_hdr the blurred colour, d_rgba8 and d_ldr its tonemapped planes; d_color, d_vel, d_depth:
+    // the host form's planes, d_vel and d_depth also arctic_pass_motion_blur's (its prev_world4 goes into Motion::d_plane).  `written`: recorded
+    // behind every call, waited for by the next one if the handle's stream has changed in between.  Nothing is allocated before the first call
+    // that passes its checks; valid: the planes hold a call's result at width x height (cleared by a resize); own_rgba8: that call wrote
+    // d_rgba8, not the caller's buffer
+    struct MotionBlur {
+        DevBuf d_prep, d_tile, d_neighbour, d_hdr, d_rgba8, d_ldr, d_color, d_vel, d_depth;
+        bool valid = false, own_rgba8 = false;
+        uint32_t width = 0, height = 0;
+        StreamMark written;
+        uint64_t launches = 0, calls = 0;
+        size_t device_bytes() const { return d_prep.cap + d_tile.cap + d_neighbour.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_vel.cap + d_depth.cap; }
+    } motion_blur;
     PinnedBuf counts;             // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts

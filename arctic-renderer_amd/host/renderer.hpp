@@ -429,6 +429,38 @@ class Renderer {
         return arctic_taa_pixels(&taa, n, pixel_xy, width, height, cur_rgb, velocity2, prev_rgbn, out_rgbn) == ARCTIC_OK;
     }
 
+    // motion blur (include/arctic_hip.h: arctic_motion_blur_device and the definition in front of it).  The blur on device planes (nullptr: the
+    // handle's HDR plane per mb.flags, depth 0, the handle's own output; d_velocity2 is required); stream-ordered
+    [[nodiscard]] bool motion_blur_device(const ArcticSettings &settings, const ArcticMotionBlur &mb, const float *d_hdr_rgb32f, const float *d_velocity2, const float *d_depth,
+                                          uint8_t *d_out_rgba8) {
+        return ok(arctic_motion_blur_device(m_handle, &settings, &mb, d_hdr_rgb32f, d_velocity2, d_depth, d_out_rgba8));
+    }
+    // the same from and to host memory; synchronous
+    [[nodiscard]] bool motion_blur(const ArcticSettings &settings, const ArcticMotionBlur &mb, const float *hdr_rgb32f, const float *velocity2, const float *depth, uint8_t *out_rgba8) {
+        return ok(arctic_motion_blur(m_handle, &settings, &mb, hdr_rgb32f, velocity2, depth, out_rgba8));
+    }
+    // the visibility plane's depth as a row-major float plane on the device: arctic_read_gbuffer's depth
+    [[nodiscard]] bool depth_plane_device(float *d_depth) { return ok(arctic_depth_plane_device(m_handle, d_depth)); }
+    // the motion call, the depth, then the blur on the handle's planes; under ARCTIC_MB_SOURCE_TAA no motion call: pass_taa's velocity plane
+    [[nodiscard]] bool pass_motion_blur(const ArcticScene &scene, const ArcticSettings &settings, const ArcticMotionBlur &mb, uint8_t *d_out_rgba8) {
+        return ok(arctic_pass_motion_blur(m_handle, &scene, &settings, &mb, d_out_rgba8));
+    }
+    // what the latest blur left, row-major; any pointer may be nullptr
+    [[nodiscard]] bool read_motion_blur(float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, float *tile_max2, float *neighbour_max2, float *prepared2) {
+        return ok(arctic_read_motion_blur(m_handle, ldr_rgb, hdr_rgb, rgba8, tile_max2, neighbour_max2, prepared2));
+    }
+    // {device bytes, launches of k_motion_blur, calls, 0}
+    [[nodiscard]] bool motion_blur_info(uint64_t out4[4]) { return ok(arctic_motion_blur_info(m_handle, out4)); }
+    // the host arbiters: steps 1 to 3 of a whole frame, and step 4 for n pixels; no handle, no GPU
+    [[nodiscard]] static bool motion_blur_prepare(const ArcticMotionBlur &mb, uint32_t width, uint32_t height, const float *velocity2, const float *depth, float *tile_max2,
+                                                  float *neighbour_max2, float *prepared2) {
+        return arctic_motion_blur_prepare(&mb, width, height, velocity2, depth, tile_max2, neighbour_max2, prepared2) == ARCTIC_OK;
+    }
+    [[nodiscard]] static bool motion_blur_pixels(const ArcticMotionBlur &mb, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *rgb,
+                                                 const float *prepared2, const float *neighbour_max2, float *out_rgb) {
+        return arctic_motion_blur_pixels(&mb, n, pixel_xy, width, height, rgb, prepared2, neighbour_max2, out_rgb) == ARCTIC_OK;
+    }
+
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }
 

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, MOTION_BLUR_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -507,6 +507,68 @@ class Renderer:
         """(device bytes, launches of k_taa_resolve, calls since the last reset, 0): all 0 until the first call"""
         out = np.zeros(4, np.uint64)
         self._check(self.L.arctic_taa_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    # ---- motion blur (include/arctic_hip.h: arctic_motion_blur_device and the definition in front of it) ------------------------------------------
+    def motion_blur_device(self, settings, d_hdr_ptr=None, d_velocity2_ptr=None, d_depth_ptr=None, d_out_ptr=None, shutter=1.0, max_radius=16.0, samples=15, depth_extent=0.05,
+                           flags=0, mb=None):
+        """blur a device HDR plane (an int pointer: rows * width * 3 floats; None: the handle's own, per flags -- the latest shading's, under
+        MB_SOURCE_COMPOSED the composition's, under MB_SOURCE_TAA the anti-aliasing's history) along d_velocity2_ptr (rows * width float2,
+        required), ordered by d_depth_ptr (rows * width floats; None: depth 0), then tonemap.  The result stays on the device -- d_out_ptr (rows *
+        width * 4 bytes) or the handle's own buffers: read_motion_blur().  mb: a MOTION_BLUR_DTYPE record instead of the parameters.
+        Asynchronous on the handle's stream."""
+        st = self._settings(settings)
+        m = _motion_blur_arguments(flags, shutter, max_radius, samples, depth_extent) if mb is None else mb
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_motion_blur_device(self.h, C.byref(st), _ptr(m), vp(d_hdr_ptr), vp(d_velocity2_ptr), vp(d_depth_ptr), vp(d_out_ptr)))
+
+    def motion_blur(self, settings, hdr=None, velocity2=None, depth=None, shutter=1.0, max_radius=16.0, samples=15, depth_extent=0.05, flags=0, mb=None, read=True):
+        """the same from and to host memory: hdr (rows, width, 3) float32 or None, velocity2 (rows, width, 2) float32, depth (rows, width) float32 or
+        None -> (rows, width, 4) uint8 (read=False: None, the result stays in the handle's buffers); synchronous"""
+        st = self._settings(settings)
+        m = _motion_blur_arguments(flags, shutter, max_radius, samples, depth_extent) if mb is None else mb
+        c = None if hdr is None else np.ascontiguousarray(hdr, dtype=np.float32)
+        v = None if velocity2 is None else np.ascontiguousarray(velocity2, dtype=np.float32)
+        z = None if depth is None else np.ascontiguousarray(depth, dtype=np.float32)
+        n = (self.rows, self.width)
+        if (c is not None and c.shape != n + (3,)) or (v is not None and v.shape != n + (2,)) or (z is not None and z.shape != n):
+            raise ArcticError(-1, f"motion_blur: expected {n + (3,)}, {n + (2,)} and {n}")
+        out = np.empty(n + (4,), np.uint8) if read else None
+        self._check(self.L.arctic_motion_blur(self.h, C.byref(st), _ptr(m), _ptr(c), _ptr(v), _ptr(z), _ptr(out)))
+        return out
+
+    def depth_plane_device(self, d_depth_ptr):
+        """the visibility plane's depth of the handle's rows into a device plane (an int pointer: rows * width floats): read_gbuffer's depth.
+        Asynchronous on the handle's stream."""
+        self._check(self.L.arctic_depth_plane_device(self.h, C.c_void_p(d_depth_ptr) if d_depth_ptr else None))
+
+    def pass_motion_blur(self, desc, settings, d_out_ptr=None, shutter=1.0, max_radius=16.0, samples=15, depth_extent=0.05, flags=0, mb=None, read=True):
+        """the one call: the motion vectors and the depth into planes the handle owns, then the blur of the handle's HDR plane: (rows, width, 4)
+        uint8.  Under MB_SOURCE_TAA no motion call: the velocity plane of the latest pass_taa.  read=False or a d_out_ptr leaves the result on
+        the device and returns None."""
+        s, st = self._scene(desc), self._settings(settings)
+        m = _motion_blur_arguments(flags, shutter, max_radius, samples, depth_extent) if mb is None else mb
+        self._check(self.L.arctic_pass_motion_blur(self.h, C.byref(s), C.byref(st), _ptr(m), C.c_void_p(d_out_ptr) if d_out_ptr else None))
+        return self.read_motion_blur(want=("rgba8",))[2] if read and not d_out_ptr else None
+
+    def read_motion_blur(self, want=("ldr", "hdr", "rgba8", "tile_max", "neighbour_max", "prepared")):
+        """what the latest blur left, row-major: (ldr (rows, width, 3), hdr (rows, width, 3) float32, rgba8 (rows, width, 4) uint8, tile_max and
+        neighbour_max (tiles_y, tiles_x, 2), prepared (rows, width, 2) float32 {l, z}); None for what was not asked for"""
+        n = (self.rows, self.width)
+        t = ((self.rows + 7) // 8, (self.width + 7) // 8, 2)
+        ldr = np.empty(n + (3,), np.float32) if "ldr" in want else None
+        hdr = np.empty(n + (3,), np.float32) if "hdr" in want else None
+        rgba = np.empty(n + (4,), np.uint8) if "rgba8" in want else None
+        tile = np.empty(t, np.float32) if "tile_max" in want else None
+        nb = np.empty(t, np.float32) if "neighbour_max" in want else None
+        prep = np.empty(n + (2,), np.float32) if "prepared" in want else None
+        self._check(self.L.arctic_read_motion_blur(self.h, _ptr(ldr), _ptr(hdr), _ptr(rgba), _ptr(tile), _ptr(nb), _ptr(prep)))
+        return ldr, hdr, rgba, tile, nb, prep
+
+    def motion_blur_info(self):
+        """(device bytes, launches of k_motion_blur, calls, 0): all 0 until the first call"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_motion_blur_info(self.h, _ptr(out)))
         return tuple(int(x) for x in out)
 
     def ray_scene_info(self):
@@ -1064,6 +1126,52 @@ def taa_pixels(pixel_xy, cur, velocity2=None, prev=None, jitter=(0.0, 0.0), max_
     rc = binding.lib().arctic_taa_pixels(_ptr(t), n, _ptr(xy) if n else None, int(width), int(height), _ptr(c), _ptr(v) if n else None, _ptr(pv), _ptr(out) if n else None)
     if rc < 0:
         raise ArcticError(rc, "taa_pixels")
+    return out
+
+
+def _motion_blur_arguments(flags, shutter, max_radius, samples, depth_extent):
+    """one MOTION_BLUR_DTYPE record; the library checks every value"""
+    m = np.zeros(1, MOTION_BLUR_DTYPE)
+    m["flags"], m["shutter"], m["max_radius"], m["samples"], m["depth_extent"] = flags, shutter, max_radius, samples, depth_extent
+    return m
+
+
+def motion_blur_prepare(velocity2, depth=None, shutter=1.0, max_radius=16.0, samples=15, depth_extent=0.05, flags=0, mb=None):
+    """arctic_motion_blur_prepare: steps 1 to 3 of the motion blur of include/arctic_hip.h on the host, for a whole frame -- velocity2 (height,
+    width, 2), depth (height, width) or None = 0.  Returns (tile_max2, neighbour_max2) of shape (tiles_y, tiles_x, 2) and P (height, width, 2)."""
+    v = np.ascontiguousarray(velocity2, dtype=np.float32)
+    if v.ndim != 3 or v.shape[2] != 2:
+        raise ArcticError(-1, "motion_blur_prepare: velocity2 is the whole frame, (height, width, 2)")
+    height, width = v.shape[:2]
+    z = None if depth is None else np.ascontiguousarray(depth, dtype=np.float32)
+    if z is not None and z.shape != (height, width):
+        raise ArcticError(-1, "motion_blur_prepare: depth is (height, width)")
+    m = _motion_blur_arguments(flags, shutter, max_radius, samples, depth_extent) if mb is None else mb
+    t = ((height + 7) // 8, (width + 7) // 8, 2)
+    tile, nb, prep = np.empty(t, np.float32), np.empty(t, np.float32), np.empty((height, width, 2), np.float32)
+    rc = binding.lib().arctic_motion_blur_prepare(_ptr(m), int(width), int(height), _ptr(v), _ptr(z), _ptr(tile), _ptr(nb), _ptr(prep))
+    if rc < 0:
+        raise ArcticError(rc, "motion_blur_prepare")
+    return tile, nb, prep
+
+
+def motion_blur_pixels(pixel_xy, rgb, prepared, neighbour_max, shutter=1.0, max_radius=16.0, samples=15, depth_extent=0.05, flags=0, mb=None):
+    """arctic_motion_blur_pixels: step 4 of the motion blur on the host, for n pixels in any order -- pixel_xy (n, 2) int32, rgb the WHOLE frame's
+    colour (height, width, 3), prepared and neighbour_max as motion_blur_prepare returns them.  Returns (n, 3) float32."""
+    xy = np.ascontiguousarray(pixel_xy, dtype=np.int32).reshape(-1, 2)
+    c = np.ascontiguousarray(rgb, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ArcticError(-1, "motion_blur_pixels: rgb is the whole frame, (height, width, 3)")
+    height, width = c.shape[:2]
+    p, nb = np.ascontiguousarray(prepared, dtype=np.float32), np.ascontiguousarray(neighbour_max, dtype=np.float32)
+    if p.shape != (height, width, 2) or nb.shape != ((height + 7) // 8, (width + 7) // 8, 2):
+        raise ArcticError(-1, "motion_blur_pixels: prepared is (height, width, 2), neighbour_max (tiles_y, tiles_x, 2)")
+    m = _motion_blur_arguments(flags, shutter, max_radius, samples, depth_extent) if mb is None else mb
+    n = len(xy)
+    out = np.empty((n, 3), np.float32)
+    rc = binding.lib().arctic_motion_blur_pixels(_ptr(m), n, _ptr(xy) if n else None, int(width), int(height), _ptr(c), _ptr(p), _ptr(nb), _ptr(out) if n else None)
+    if rc < 0:
+        raise ArcticError(rc, "motion_blur_pixels")
     return out
 
 

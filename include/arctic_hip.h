@@ -1262,7 +1262,7 @@ int arctic_pass_ray_effects_temporal(ArcticRenderer *r, const ArcticScene *scene
  * "Where was this surface point in the previous frame": for every pixel of the current visibility plane the world position its surface point had
  * at the PREVIOUS motion call -- through that call's trs and that call's pose or morph weights -- and the offset on the screen to where it was
  * seen then.  It is what lets the occlusion's history follow an object that moves (a changed trs, arctic_set_mesh_pose,
- * arctic_set_mesh_morph_weights), and what temporal anti-aliasing or motion blur would read first.  Nothing in the passes or in the other calls
+ * arctic_set_mesh_morph_weights), and what temporal anti-aliasing and the motion blur (below) read first.  Nothing in the passes or in the other calls
  * changes: a handle that never makes these calls renders the same bytes and allocates nothing for them.
  *
  * THE DEFINITION.  Bit for bit: fp32 throughout, one rounding per operation in the written order, no contraction, IEEE division.
@@ -1407,7 +1407,7 @@ int arctic_jitter_proj_view(float *proj_view16, uint32_t width, uint32_t height,
  * WHAT FOLLOWS.  On a still scene drawn with jitter j, velocity2 is -j and step 3 lands on the pixel's own centre: with max_history at or above
  *   the frame count and no luma weight, `out` is the running mean of the frames.
  * KNOWN LIMITS, stated and not worked around.  A pixel without geometry has velocity2 = 0, so the sky is not reprojected under camera rotation;
- *   the box clamp bounds what it keeps.  There is no sharpening, no motion blur, and a shard cannot resolve (no halo exchange).
+ *   the box clamp bounds what it keeps.  There is no sharpening (the motion blur is a stage of its own behind the resolve, below), and a shard cannot resolve (no halo exchange).
  * Refusals, in this order; every refusal comes before anything is enqueued, and a refused call writes nothing and leaves T as it was.
  *   ARCTIC_E_INVALID: a null handle, settings or ArcticTaa; unknown flag bits; a field outside the ranges below, or a NaN; a device plane that
  *     is misaligned: 4 bytes for C and RGBA8, 8 bytes for velocity2.
@@ -1459,6 +1459,110 @@ int arctic_taa_info(ArcticRenderer *r, uint64_t *out4);
  * array that is needed. */
 int arctic_taa_pixels(const ArcticTaa *taa, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *cur_rgb, const float *velocity2,
                       const float *prev_rgbn, float *out_rgbn);
+
+/* ---- motion blur: tile velocity maxima and a depth-aware gather (no counterpart in the reference) -------------------------------------------------
+ * A fast object is smeared over the path it covered while the shutter was open: the reconstruction filter of McGuire et al., "A Reconstruction
+ * Filter for Plausible Motion Blur" (2012) -- tile maximum, neighbourhood maximum, and a depth-aware gather with cone and cylinder weights --
+ * restated so that it is defined bit for bit like every stage in front of the tonemapper here.  It reads the float HDR colour (the shading's, the
+ * composition's, or the anti-aliasing's history), velocity2 of arctic_motion_vectors_device and the prepass depth.  Nothing in the passes or in
+ * the other calls changes: a handle that never makes these calls renders the same bytes and allocates nothing for them.
+ *
+ * THE DEFINITION.  Bit for bit: fp32 throughout, one rounding per operation in the written order, no contraction, IEEE division and square root.
+ * min(a, b) is (b < a) ? b : a and max(a, b) is (a < b) ? b : a.  clamp01(x) = !(x > 0) ? 0 : (x > 1 ? 1 : x): a NaN gives 0.
+ * INPUTS.  C: the HDR colour, rows x width x 3 floats, row-major.  velocity2 as arctic_motion_vectors_device writes it (REQUIRED).  Depth: rows x
+ *   width floats, smaller means nearer, in the units arctic_read_gbuffer returns (arctic_depth_plane_device); NULL: every pixel has depth 0.
+ *   W and H are the frame size; a tile is 8 x 8 pixels, tile(p) = (px / 8, py / 8), and the tile grid is ceil(W / 8) x ceil(H / 8).
+ *   1. HALF VELOCITY.  h_p = velocity2[p] * (0.5 * shutter) per component.  If either component of h_p is not finite, h_p = (0, 0).
+ *      len = sqrt(hx*hx + hy*hy).  If len > max_radius:  s = max_radius / len,  h_p = h_p * s.  l2_p = hx*hx + hy*hy of the final h_p, and
+ *      l_p = max(sqrt(l2_p), 0.5).  The prepared plane is P[p] = {l_p, z_p} (float2, row-major), z_p the pixel's depth.
+ *   2. TILE MAXIMUM.  tile_max2[tile] = the h_p with the largest l2_p over the tile's pixels inside the frame; among equals the pixel with the
+ *      lowest lane index (py & 7) * 8 + (px & 7) wins.
+ *   3. NEIGHBOURHOOD MAXIMUM.  Rt = ceil(max_radius / 8) tiles.  neighbour_max2[(tx, ty)] = the tile_max2 with the largest hx*hx + hy*hy among
+ *      the tiles (tx+dx, ty+dy), |dx|, |dy| <= Rt, that lie inside the tile grid, visited row-major (dy outer); the first among equals wins.
+ *   4. THE GATHER, for pixel p = (px, py) with d = neighbour_max2[tile(p)] and dl = sqrt(dx*dx + dy*dy):
+ *      If !(dl > 0.5):  out = C[p], bit for bit -- tiles that nothing fast can reach are copied.
+ *      Otherwise w = 1 / l_p, acc = C[p] * w, and for i = 0 .. samples-1 in order:
+ *        o = ((B[py & 3][px & 3] + 0.5) / 16) - 0.5 under ARCTIC_MB_DITHER, else 0; B is the 4 x 4 Bayer matrix with the rows
+ *          {0, 8, 2, 10}, {12, 4, 14, 6}, {3, 11, 1, 9}, {15, 7, 13, 5}.
+ *        t = (((i + 0.5) + o) / samples) * 2 - 1.   sx = (px + 0.5) + t*dx, sy = (py + 0.5) + t*dy;  qx = floor(sx), qy = floor(sy).
+ *        The tap is inside iff 0 <= qx <= W-1 and 0 <= qy <= H-1, tested in float before any conversion; a NaN fails.
+ *        dist = |t| * dl.  With {l_q, z_q} = P[q]:
+ *          f = clamp01(1 - (z_q - z_p) / depth_extent)          b = clamp01(1 - (z_p - z_q) / depth_extent)
+ *          cone(l) = clamp01(1 - dist / l)
+ *          cyl(l) = 1 - (s*s) * (3 - 2*s)  with  s = clamp01((dist - 0.95*l) / (0.1*l))
+ *          a = (f * cone(l_q) + b * cone(l_p)) + (cyl(l_q) * cyl(l_p)) * 2
+ *        A tap outside the frame is a SELECT with weight 0: nothing of it is read.  A tap whose a is not > 0 is a SELECT too: its colour does
+ *        not enter, so a NaN colour never spreads through a zero weight.  Otherwise w = w + a and acc = acc + C[q] * a per channel.
+ *      out = acc / w.
+ *   5. Store out (float3, row-major).  Then post_process of `out` under `settings`, as k_compose and k_taa_resolve carry it out: float LDR and
+ *      RGBA8.  tile_max2, neighbour_max2, P and out are defined bit for bit; the tonemapped planes are held to the project's standing bar (1e-4
+ *      of the float64 post_process).
+ * KNOWN LIMITS, stated and not worked around.  The depth is the prepass's non-linear depth, so depth_extent is in those units.  The sky has
+ *   velocity2 = 0.  Only whole frames are handled: a shard's taps lie on other ranks, so a shard is refused as the resolve refuses it.  The
+ *   minimum length 0.5 lets a still pixel inside a fast tile's window take up to one pixel of its neighbour along d: the paper's behaviour.
+ * Refusals, in this order; every refusal comes before anything is enqueued, and a refused call writes nothing.
+ *   ARCTIC_E_INVALID: a null handle, settings or ArcticMotionBlur; unknown flag bits, or both source flags; a field outside the ranges below,
+ *     or a NaN; a null velocity2; a device plane that is misaligned: 4 bytes for C, the depth and RGBA8, 8 bytes for velocity2.
+ *   ARCTIC_E_STATE: a handle that does not own the whole frame; and, with a NULL colour plane: under ARCTIC_MB_SOURCE_TAA an empty T
+ *     (arctic_read_taa's condition) -- nothing else, the history is float whatever made it --, otherwise what arctic_taa_resolve_device refuses
+ *     of the handle's HDR plane: ARCTIC_OPT_KEEP_FLOAT_OUTPUT off; no shading since it was turned on or since the last resize; under
+ *     ARCTIC_MB_SOURCE_COMPOSED no composition since the last resize; ARCTIC_OPT_HDR16 = 1. */
+#define ARCTIC_MB_DITHER           1u   /* the taps of a pixel are offset by its entry of the Bayer matrix */
+#define ARCTIC_MB_SOURCE_COMPOSED  2u   /* a NULL colour = the latest composition's HDR plane instead of the latest shading's */
+#define ARCTIC_MB_SOURCE_TAA       4u   /* a NULL colour = the anti-aliasing's history T; excludes ARCTIC_MB_SOURCE_COMPOSED */
+typedef struct ArcticMotionBlur {       /* 32 bytes */
+    uint32_t flags;
+    float shutter;                      /* [0, 4], finite: the fraction of the frame interval that is exposed */
+    float max_radius;                   /* [1, 64], finite: pixels */
+    uint32_t samples;                   /* 1..64: taps per pixel */
+    float depth_extent;                 /* > 0, finite: the soft extent of the depth comparison */
+    uint32_t reserved[3];               /* 0 */
+} ArcticMotionBlur;
+
+/* One call of the definition on DEVICE planes of a handle that owns the whole frame: k_mb_tile_max, k_mb_neighbour_max, k_motion_blur.
+ * d_hdr_rgb32f: rows*width*3 floats, NULL = the handle's own plane per `flags`; d_velocity2: rows*width float2, required; d_depth: rows*width
+ * floats, NULL = depth 0; d_out_rgba8: rows*width*4 bytes, NULL = the handle's own buffer (arctic_read_motion_blur).  No plane may alias
+ * another.  Stream-ordered on the handle's stream; a warm call allocates nothing and does not synchronise. */
+int arctic_motion_blur_device(ArcticRenderer *r, const ArcticSettings *settings, const ArcticMotionBlur *mb, const float *d_hdr_rgb32f, const float *d_velocity2,
+                              const float *d_depth, uint8_t *d_out_rgba8);
+
+/* The host form: the same kernels from and to host memory (hdr_rgb32f, depth and out_rgba8 may be NULL, with the meanings above; a NULL output:
+ * the result stays in the handle's buffers).  Synchronous. */
+int arctic_motion_blur(ArcticRenderer *r, const ArcticSettings *settings, const ArcticMotionBlur *mb, const float *hdr_rgb32f, const float *velocity2,
+                       const float *depth, uint8_t *out_rgba8);
+
+/* The visibility plane's depth of the handle's rows as a device plane: d_depth, rows*width floats, row-major, 4-byte aligned -- the values
+ * arctic_read_gbuffer returns as `depth`, a pixel without geometry 1.0.  Stream-ordered.  ARCTIC_E_INVALID: a null handle or plane, or a
+ * misaligned one.  ARCTIC_E_STATE: no visibility plane (arctic_pass_gbuffer or a frame first; arctic_write_gbuffer leaves none). */
+int arctic_depth_plane_device(ArcticRenderer *r, float *d_depth);
+
+/* The one call: arctic_motion_vectors_device, then arctic_depth_plane_device, then the blur of the handle's HDR plane, all on planes the handle
+ * owns.  Byte for byte the calls made by hand.  It is then the frame's ONE motion call.  Under ARCTIC_MB_SOURCE_TAA it makes NO motion call:
+ * it reads the velocity plane the latest arctic_pass_taa left in the handle, and returns ARCTIC_E_STATE unless the handle's latest
+ * anti-aliasing call since the last resize or reset was arctic_pass_taa.  So blur behind anti-aliasing is: render, arctic_pass_taa,
+ * arctic_pass_motion_blur with the flag -- and the frame still has one motion call.  Every refusal of every step comes before anything is
+ * enqueued. */
+int arctic_pass_motion_blur(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticMotionBlur *mb, uint8_t *d_out_rgba8);
+
+/* What the latest blur left, row-major: float LDR and the blurred HDR colour (rows*width*3 floats each), the handle's own RGBA8, tile_max2 and
+ * neighbour_max2 (one float2 per tile of the tile grid, row-major) and P (rows*width float2).  Any pointer may be NULL.  Synchronises.
+ * ARCTIC_E_STATE before the first call and after a resize, and for rgba8 when the latest call wrote the caller's buffer. */
+int arctic_read_motion_blur(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, float *tile_max2, float *neighbour_max2, float *prepared2);
+
+/* What the calls hold on this handle: out4 = {bytes of device memory, launches of k_motion_blur, calls, 0}.  All 0 until the first call that
+ * passes its checks.  Touches no device. */
+int arctic_motion_blur_info(ArcticRenderer *r, uint64_t *out4);
+
+/* The host arbiters (no handle, no GPU), by the very functions the kernels run.  arctic_motion_blur_prepare: steps 1 to 3 of a WHOLE frame --
+ * velocity2 (height*width*2 floats), depth (height*width floats or NULL = 0) in; tile_max2, neighbour_max2 (2 floats per tile) and prepared2
+ * (P: height*width*2 floats) out.  arctic_motion_blur_pixels: step 4 for n pixels in any order -- pixel_xy: (px, py) per pixel, inside the frame;
+ * rgb: the WHOLE frame's C (height*width*3 floats, row-major); prepared2 and neighbour_max2 as the first writes them; out_rgb: n*3 floats.
+ * ARCTIC_E_INVALID (nothing written): what the blur refuses of ArcticMotionBlur, a frame size outside 1..16384, a pixel outside the frame, a
+ * null array that is needed. */
+int arctic_motion_blur_prepare(const ArcticMotionBlur *mb, uint32_t width, uint32_t height, const float *velocity2, const float *depth, float *tile_max2,
+                               float *neighbour_max2, float *prepared2);
+int arctic_motion_blur_pixels(const ArcticMotionBlur *mb, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *rgb,
+                              const float *prepared2, const float *neighbour_max2, float *out_rgb);
 
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
