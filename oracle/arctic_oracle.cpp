@@ -363,6 +363,8 @@ struct Oracle {
     int hdr16 = 0;        // 1: ps_main's colour passes through binary16 (the reference's RGBA16F target) before post_process
     int precision = 64;   // arithmetic of the BRDF/tonemap: 64 = float64 (parity arbiter), 32 = literal fp32 (CPU baseline)
     int sampler_mode = 0; // SAMPLER_* bits: variants of what the reference leaves to the D3D12 sampler hardware (default: none)
+    bool has_proj_view = false;   // oracle_set_proj_view: pass_gbuffer draws with proj_view in place of the camera's matrix, and nothing
+    M4 proj_view{};               // else reads it (shadow pass, light-space position, the eye of the shading and the sky ray keep the camera)
     std::string err;
     uint32_t rows() const { return row_end - row_begin; }
 };
@@ -435,7 +437,7 @@ void pass_gbuffer(Oracle &o, const Scene &sc) {
     o.src_tri.assign(npx, 0xFFFFFFFFu);
     o.matid.assign(npx, 0xFFFFFFFFu);
     o.attrs.assign(npx * 18, 0.0f);
-    M4 pv = camera_proj_view(sc.camera), lpv = sun_proj_view(sc.sun);
+    M4 pv = o.has_proj_view ? o.proj_view : camera_proj_view(sc.camera), lpv = sun_proj_view(sc.sun);
     uint32_t rec = 0;
     process_geometry(o, sc, pv, lpv, (float)o.width, (float)o.height, 0, (int)o.row_begin, (int)W, (int)o.row_end, CULL_BACK,
         [&](const SetupTri &t, const VSOut *const *tv) {
@@ -1050,6 +1052,15 @@ int oracle_set_sampler_mode(void *h, int mode) {
     Oracle *o = static_cast<Oracle *>(h);
     if (!o || mode < 0 || mode > 7) return -1;
     o->sampler_mode = mode;
+    return 0;
+}
+// the matrix of the forward prepass ([col][row], 16 floats) in place of camera_proj_view(scene.camera); NULL: the camera's again (the default).
+// Test infrastructure for a jittered prepass: the caller computes the matrix, the oracle only draws with it.
+int oracle_set_proj_view(void *h, const float *m16_or_null) {
+    Oracle *o = static_cast<Oracle *>(h);
+    if (!o) return -1;
+    o->has_proj_view = m16_or_null != nullptr;
+    if (m16_or_null) std::memcpy(&o->proj_view, m16_or_null, sizeof(M4));
     return 0;
 }
 int oracle_hardware_threads(void) { return (int)std::thread::hardware_concurrency(); }

@@ -89,6 +89,7 @@ def lib():
         L.oracle_set_precision.argtypes = [vp, i32]
         L.oracle_set_sampler_mode.argtypes = [vp, i32]
         L.oracle_set_hdr16.argtypes = [vp, i32]
+        L.oracle_set_proj_view.argtypes = [vp, vp]
         L.oracle_create_hdri.argtypes = [vp, vp, u32, u32]
         L.oracle_sky_ray.argtypes = [vp, C.POINTER(Camera), u32, u32, vp]
         L.oracle_sky_ray.restype = None
@@ -134,6 +135,17 @@ class Oracle:
     def set_hdr16(self, on):
         """route ps_main's colour through binary16 like the reference's RGBA16F target (forward_pass.cpp:149)."""
         assert self.L.oracle_set_hdr16(self.h, int(on)) == 0
+        return self
+
+    def set_proj_view(self, m):
+        """the forward prepass (pass_gbuffer, and so render_frame) draws with m ([col][row], as frame_constants returns it) in place of the
+        camera's proj_view; None: the camera's again.  Nothing else reads it: the shadow pass, the light-space position, the eye of the
+        shading and the sky ray keep the camera -- what arctic_set_camera_jitter's "the forward prepass only" says."""
+        if m is None:
+            assert self.L.oracle_set_proj_view(self.h, None) == 0
+            return self
+        a = _f32(m).reshape(16)
+        assert self.L.oracle_set_proj_view(self.h, _ptr(a)) == 0
         return self
 
     def create_hdri(self, rgba32f):

@@ -19,10 +19,13 @@ pytestmark = pytest.mark.gpu
 COUNT = 1024     # ARCTIC_OPT_DEBUG bit 10: count what was skipped
 
 
-def prepass(hip, sc, cull, desc=None, frame=True, **kw):
+def prepass(hip, sc, cull, desc=None, frame=True, jitter=None, **kw):
+    """jitter: arctic_set_camera_jitter's (jx, jy) before anything is drawn; None: the call is never made"""
     desc = desc or sc.desc
     r = sc.upload(hip.Renderer(sc.width, sc.height, sc.shadow_size, sc.max_lights, **kw))
     r.set_option("cluster_cull", cull)
+    if jitter is not None:
+        r.set_camera_jitter(*jitter)
     r.set_option("debug", COUNT)
     if sc.shadow_size:
         r.pass_shadow_map(desc)
@@ -106,25 +109,40 @@ def test_shards(pkg, hip, kw):
         assert c[0][1] == whole[0][1]
 
 
+SWEEP_W, SWEEP_H = 256, 144
+SWEEP_CAMERA = dict(eye=(0.0, 0.0, 3.0), rotation=(0.0, -90.0), aspect=SWEEP_W / SWEEP_H, fov_y=45.0, z_near_far=(0.1, 50.0))      # looks down -z
+SWEEP_SIDES = ("right", "left", "top", "bottom")
+SWEEP_STEPS = tuple(np.linspace(-2.5, 2.5, 11))
+
+
+def sweep_offsets(steps=None):
+    """[(side, d, translation)] of test_objects_on_the_scissors_sides: the quad of CC.small_quad with its near edge d pixels inside (negative) /
+    outside each side of the frame (steps: {side: the values of d}, default SWEEP_STEPS for every side), then through the near plane, the far
+    plane and behind the camera (side "depth", d = None)"""
+    w, h = SWEEP_W, SWEEP_H
+    # where does the quad's plane meet the frustum's sides?  half-extent of the view at the quad's distance
+    half_h = 3.0 * np.tan(np.radians(22.5)); half_w = half_h * w / h
+    px = 2 * half_w / w
+    offsets = []
+    for name, side, centre in (("right", "x", half_w), ("left", "x", -half_w), ("top", "y", half_h), ("bottom", "y", -half_h)):
+        for d in (steps or {}).get(name, SWEEP_STEPS):
+            t = centre + np.sign(centre) * (0.05 + d * px)      # the quad's near edge d pixels inside (negative) / outside the side
+            offsets.append((name, float(d), (t, 0.0, 0.0) if side == "x" else (0.0, t, 0.0)))
+    for z in (3.0 - 0.1 + 1e-4, 3.0 - 0.1 - 1e-4, 3.0 - 0.1, 3.0 - 50.0 + 1e-3, 3.0 - 50.0 - 1e-3, 3.0 + 5.0):      # at the near plane, the far plane, behind the camera
+        offsets.append(("depth", None, (0.0, 0.0, z)))
+    return offsets
+
+
 def test_objects_on_the_scissors_sides(pkg, hip):
     """one small dense quad (several clusters) moved across every side of the frame in steps of a fraction of a pixel, and through the near and the
     far plane: whatever is skipped, the image's bits are those of the unculled prepass"""
     S = pkg.scenes
     rng = np.random.default_rng(7)
     mats = [S.make_material_textures(rng, 64)]
-    meshes = [S.quad((-0.05, -0.05, 0.0), (0.1, 0, 0), (0, 0.1, 0), 24, 24) + (0,)]      # 1152 triangles: 5 clusters, strips of the quad
-    w, h = 256, 144
-    cam = dict(eye=(0.0, 0.0, 3.0), rotation=(0.0, -90.0), aspect=w / h, fov_y=45.0, z_near_far=(0.1, 50.0))      # looks down -z
-    # where does the quad's plane meet the frustum's sides?  half-extent of the view at the quad's distance
-    half_h = 3.0 * np.tan(np.radians(22.5)); half_w = half_h * w / h
-    px = 2 * half_w / w
-    offsets = []
-    for side, centre in (("x", half_w), ("x", -half_w), ("y", half_h), ("y", -half_h)):
-        for d in np.linspace(-2.5, 2.5, 11):
-            t = centre + np.sign(centre) * (0.05 + d * px)      # the quad's near edge d pixels inside (negative) / outside the side
-            offsets.append((t, 0.0, 0.0) if side == "x" else (0.0, t, 0.0))
-    for z in (3.0 - 0.1 + 1e-4, 3.0 - 0.1 - 1e-4, 3.0 - 0.1, 3.0 - 50.0 + 1e-3, 3.0 - 50.0 - 1e-3, 3.0 + 5.0):      # at the near plane, the far plane, behind the camera
-        offsets.append((0.0, 0.0, z))
+    meshes = [CC.small_quad(S) + (0,)]      # 1152 triangles: 5 clusters, strips of the quad
+    w, h = SWEEP_W, SWEEP_H
+    cam = SWEEP_CAMERA
+    offsets = [off for _, _, off in sweep_offsets()]
     hits = seen = 0
     ra, rb = [hip.Renderer(w, h, 0, 16) for _ in range(2)]
     for r, cull in ((ra, 0), (rb, 3)):

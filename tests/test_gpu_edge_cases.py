@@ -24,7 +24,9 @@ def camera_scene(pkg, objects, w, h, lights=None):
                        point_lights=lights)
 
 
-def both(pkg, oracle, hip, w, h, shadow, mats, meshes, objs, lights, settings=(0, 2.2, 1.0)):
+def both(pkg, oracle, hip, w, h, shadow, mats, meshes, objs, lights, settings=(0, 2.2, 1.0), jitter=None, options=None, desc=None):
+    """jitter (jx, jy): the device draws under arctic_set_camera_jitter, the oracle with the matrix tests/taa_reference.py makes of its own
+    camera matrix and the frame's size; options: arctic_set_option pairs for the device; desc: a scene in place of camera_scene's"""
     outs = []
     for cls in (oracle.Oracle, hip.Renderer):
         r = cls(w, h, shadow, 16)
@@ -35,7 +37,14 @@ def both(pkg, oracle, hip, w, h, shadow, mats, meshes, objs, lights, settings=(0
         r.update_lights(lights)
         if cls is hip.Renderer:
             r.set_option("keep_float_output", 1)
-        desc = camera_scene(pkg, pkg.scene.make_objects(objs), w, h, lights)
+            for name, value in (options or {}).items():
+                r.set_option(name, value)
+        desc = desc or camera_scene(pkg, pkg.scene.make_objects(objs), w, h, lights)
+        if jitter is not None and cls is hip.Renderer:
+            r.set_camera_jitter(*jitter)
+        elif jitter is not None:
+            import taa_reference
+            r.set_proj_view(taa_reference.jitter_proj_view(oracle.frame_constants(desc)[0], w, h, *jitter))
         img = r.render_frame(desc, settings)
         outs.append((img, r.read_output()[0], r.read_gbuffer(), r))
     return outs
@@ -84,6 +93,13 @@ def test_triangles_beyond_the_binary64_range_take_the_integer_rasteriser(pkg, or
     """the rasteriser evaluates edge functions as binary64 planes when every snapped coordinate is below 2^24 (exact), in
     64-bit integers otherwise: a 3840-pixel-wide target with triangles clipped at the +-64 w guard band reaches
     64 * 1920 * 256 = 2^24.9, next to ordinary triangles in the same frame -- both paths in one item stream."""
+    outs = both(pkg, oracle, hip, *guard_band_scene(pkg))
+    assert (outs[0][2][1] != 0xFFFFFFFF).mean() > 0.5
+    check(outs)
+
+
+def guard_band_scene(pkg):
+    """both()'s arguments from the width on: the 3840 x 64 frame of the test above"""
     rng = np.random.default_rng(19)
     mats = [pkg.scenes.make_material_textures(rng, 16)]
     pts = [(-50000, -40000, -6), (50000, -40000, -6), (0, 60000, -6),     # NDC +-140: cut at the guard band on both sides
@@ -92,9 +108,7 @@ def test_triangles_beyond_the_binary64_range_take_the_integer_rasteriser(pkg, or
            (100, -1, 1), (140, -1, 1), (120, 1, 1)]                        # ordinary, near the right edge of the wide frame
     idx = list(range(12))
     lights = pkg.scenes.random_lights(rng, 2, (-2, -2, 0.5), (2, 2, 3))
-    outs = both(pkg, oracle, hip, 3840, 64, 128, mats, [(tri_mesh(pkg, pts), idx, 0)], [(np.eye(4), 0)], lights)
-    assert (outs[0][2][1] != 0xFFFFFFFF).mean() > 0.5
-    check(outs)
+    return 3840, 64, 128, mats, [(tri_mesh(pkg, pts), idx, 0)], [(np.eye(4), 0)], lights
 
 
 def test_one_texel_textures_and_wrapping_uv(pkg, oracle, hip):
@@ -198,8 +212,24 @@ def test_large_light_and_material_tables(pkg, oracle, hip, n_mat, n_lights):
 def test_record_table_overflow_is_reported_and_recovers(pkg, oracle, hip):
     """the setup-record table starts at 2 records per source triangle; a scene whose triangles are nearly all clipped into
     three (one vertex behind the camera, one beyond the far plane) overflows it: loud error, then the worst-case table."""
-    rng = np.random.default_rng(5)
     n = 6000
+    v, idx, mats, desc, n_recs, ref = clipped_scene(pkg, oracle, n)
+    assert n_recs > 2 * n + 4096, f"the test scene does not overflow the record table ({n_recs} records)"
+    r = hip.Renderer(160, 96, 0, 16); r.create_material(*mats[0]); r.create_mesh(v, idx, 0)
+    with pytest.raises(hip.ArcticError) as e:
+        r.render_frame(desc, (0, 2.2, 1.0))
+    assert e.value.code == -5
+    img = r.render_frame(desc, (0, 2.2, 1.0))
+    assert int(r.stats()[0]) == n_recs
+    d = np.abs(img.astype(np.int16) - ref.astype(np.int16))
+    assert d.max() <= 1 and (d != 0).mean() < 2e-3 and (img[..., :3].sum(-1) > 0).mean() > 0.2
+    r.close()
+
+
+def clipped_scene(pkg, oracle, n):
+    """(vertices, indices, materials, desc, the oracle's record count, the oracle's frame) of the test above: n triangles at 160 x 96, nearly
+    all clipped into three.  2 n + 4096 records are the table's first size: n = 6000 overflows it, n = 1200 does not."""
+    rng = np.random.default_rng(5)
     pts = np.zeros((n, 3, 3), np.float32)
     cx, cy = rng.uniform(-1.5, 1.5, n), rng.uniform(-1.0, 1.0, n)
     pts[:, 0] = np.stack([cx - 0.2, cy - 0.2, np.full(n, 9.0)], -1)        # behind the eye (z = 4, looking down -z)
@@ -223,16 +253,7 @@ def test_record_table_overflow_is_reported_and_recovers(pkg, oracle, hip):
             best = (int(o.stats()[0]), idx, ref)
         o.close()
     n_recs, idx, ref = best
-    assert n_recs > 2 * n + 4096, f"the test scene does not overflow the record table ({n_recs} records)"
-    r = hip.Renderer(160, 96, 0, 16); r.create_material(*mats[0]); r.create_mesh(v, idx, 0)
-    with pytest.raises(hip.ArcticError) as e:
-        r.render_frame(desc, (0, 2.2, 1.0))
-    assert e.value.code == -5
-    img = r.render_frame(desc, (0, 2.2, 1.0))
-    assert int(r.stats()[0]) == n_recs
-    d = np.abs(img.astype(np.int16) - ref.astype(np.int16))
-    assert d.max() <= 1 and (d != 0).mean() < 2e-3 and (img[..., :3].sum(-1) > 0).mean() > 0.2
-    r.close()
+    return v, idx, mats, desc, n_recs, ref
 
 
 def test_profiler_markers_option(pkg, hip):

@@ -197,10 +197,11 @@ def test_trilinear_matches_float64(pkg, oracle, hip, sampler):
 
 
 # ---- 7: the plane against float64 ------------------------------------------------------------------------------------------------------
-def _lod_reference(pkg, sc, r, tri, mat):
+def _lod_reference(pkg, sc, r, tri, mat, pv=None):
     """lambda per pixel in binary64 from the visibility's triangle ids, the scene's vertices and the camera: the finite-difference definition
-    of include/arctic_hip.h on the triangle's projective interpolation (vertices snapped to 1/256 pixel as set-up snaps them)"""
-    pv = pkg.renderer.frame_constants(sc.desc)[0].astype(np.float64)      # [col][row]
+    of include/arctic_hip.h on the triangle's projective interpolation (vertices snapped to 1/256 pixel as set-up snaps them).  pv: the matrix
+    the prepass drew with, [col][row], where that is not the camera's (arctic_set_camera_jitter)"""
+    pv = (pkg.renderer.frame_constants(sc.desc)[0] if pv is None else np.asarray(pv).reshape(4, 4)).astype(np.float64)      # [col][row]
     H, W = tri.shape
     lam = np.zeros((H, W)); rho2 = np.zeros((H, W)); uv00 = np.zeros((H, W, 2))
     first = 0
@@ -236,11 +237,11 @@ def _lod_reference(pkg, sc, r, tri, mat):
     return lam, rho2, uv00
 
 
-def _lod_error(pkg, sc, r):
+def _lod_error(pkg, sc, r, pv=None):
     r.pass_gbuffer(sc.desc)
     got = r.read_lod().astype(np.float64)
     attrs, mat, _, tri = r.read_gbuffer()
-    want, rho2, uv00 = _lod_reference(pkg, sc, r, tri, mat)
+    want, rho2, uv00 = _lod_reference(pkg, sc, r, tri, mat, pv)
     cov = mat != NO_MAT
     assert np.all(got[~cov] == 0.0)
     # the reference sees the triangles the device drew: its uv00 is the G-buffer's (clipped triangles excepted: their ids are sub-triangles of the source)
