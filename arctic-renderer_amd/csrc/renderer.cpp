@@ -132,6 +132,7 @@ int alloc_targets(ArcticRenderer *r) {
     r->motion.valid = false;       // (... and so is what the previous motion call saw)
     r->taa.valid = false;          // (... and the anti-aliasing's T; the camera jitter stays)
     r->motion_blur.valid = false;  // (... and what the latest motion blur left)
+    r->dof.valid = false;          // (... and the latest depth of field)
     r->output_filtered = false;
     return ARCTIC_OK;
 }

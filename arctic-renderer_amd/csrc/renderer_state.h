@@ -457,6 +457,22 @@ struct ArcticRenderer {
         uint64_t launches = 0, calls = 0;
         size_t device_bytes() const { return d_prep.cap + d_tile.cap + d_neighbour.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_vel.cap + d_depth.cap; }
     } motion_blur;
+    // Depth of field (arctic_dof_device; dof.hip): d_prep is P of include/arctic_hip.h (float2 per pixel, row-major), d_tile and d_neighbour
+    // the two maxima (one float per tile), d_hdr the gathered colour, d_rgba8 and d_ldr its tonemapped planes; d_color, d_depth: the host
+    // form's planes, d_depth also arctic_pass_dof's; d_taps: the tap table, which travels through taps_ring, whose one pinned slot keeps the
+    // table last sent (n_taps float2; 0: nothing).  `written`: recorded behind every call, waited for by the next one if the handle's stream
+    // has changed in between.  Nothing is allocated before the first call that passes its checks; valid: the planes hold a call's result at
+    // width x height (cleared by a resize); own_rgba8: that call wrote d_rgba8, not the caller's buffer
+    struct Dof {
+        DevBuf d_prep, d_tile, d_neighbour, d_hdr, d_rgba8, d_ldr, d_color, d_depth, d_taps;
+        UploadRing<1> taps_ring;
+        uint32_t n_taps = 0;
+        bool valid = false, own_rgba8 = false;
+        uint32_t width = 0, height = 0;
+        StreamMark written;
+        uint64_t launches = 0, calls = 0;
+        size_t device_bytes() const { return d_prep.cap + d_tile.cap + d_neighbour.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_depth.cap + d_taps.cap; }
+    } dof;
     PinnedBuf counts;             // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts

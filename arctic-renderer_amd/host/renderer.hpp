@@ -461,6 +461,39 @@ class Renderer {
         return arctic_motion_blur_pixels(&mb, n, pixel_xy, width, height, rgb, prepared2, neighbour_max2, out_rgb) == ARCTIC_OK;
     }
 
+    // depth of field (include/arctic_hip.h: arctic_dof_device and the definition in front of it).  The gather on device planes (nullptr: the
+    // handle's HDR plane per dof.flags, the handle's own output; d_depth is required; taps2: dof.samples float2 in host memory); stream-ordered
+    [[nodiscard]] bool dof_device(const ArcticSettings &settings, const ArcticDof &dof, const float *d_hdr_rgb32f, const float *d_depth, const float *taps2, uint8_t *d_out_rgba8) {
+        return ok(arctic_dof_device(m_handle, &settings, &dof, d_hdr_rgb32f, d_depth, taps2, d_out_rgba8));
+    }
+    // the same from and to host memory; synchronous
+    [[nodiscard]] bool dof(const ArcticSettings &settings, const ArcticDof &dof, const float *hdr_rgb32f, const float *depth, const float *taps2, uint8_t *out_rgba8) {
+        return ok(arctic_dof(m_handle, &settings, &dof, hdr_rgb32f, depth, taps2, out_rgba8));
+    }
+    // the depth, then the gather of the handle's planes under the scene's camera planes (dof.z_near == dof.z_far == 0)
+    [[nodiscard]] bool pass_dof(const ArcticScene &scene, const ArcticSettings &settings, const ArcticDof &dof, const float *taps2, uint8_t *d_out_rgba8) {
+        return ok(arctic_pass_dof(m_handle, &scene, &settings, &dof, taps2, d_out_rgba8));
+    }
+    // what the latest call left, row-major; any pointer may be nullptr
+    [[nodiscard]] bool read_dof(float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, float *tile_max, float *neighbour_max, float *prepared2) {
+        return ok(arctic_read_dof(m_handle, ldr_rgb, hdr_rgb, rgba8, tile_max, neighbour_max, prepared2));
+    }
+    // {device bytes, launches of k_dof_gather, calls, 0}
+    [[nodiscard]] bool dof_info(uint64_t out4[4]) { return ok(arctic_dof_info(m_handle, out4)); }
+    // autofocus: the view distance of one pixel of the resident visibility plane; synchronises
+    [[nodiscard]] bool dof_focus_at(float z_near, float z_far, uint32_t px, uint32_t py, float *distance) { return ok(arctic_dof_focus_at(m_handle, z_near, z_far, px, py, distance)); }
+    // the host arbiters and the thin lens: no handle, no GPU
+    [[nodiscard]] static bool dof_prepare(const ArcticDof &dof, uint32_t width, uint32_t height, const float *depth, float *tile_max, float *neighbour_max, float *prepared2) {
+        return arctic_dof_prepare(&dof, width, height, depth, tile_max, neighbour_max, prepared2) == ARCTIC_OK;
+    }
+    [[nodiscard]] static bool dof_pixels(const ArcticDof &dof, const float *taps2, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *rgb,
+                                         const float *prepared2, const float *neighbour_max, float *out_rgb) {
+        return arctic_dof_pixels(&dof, taps2, n, pixel_xy, width, height, rgb, prepared2, neighbour_max, out_rgb) == ARCTIC_OK;
+    }
+    [[nodiscard]] static bool dof_coc_scale(float f_number, float focal_length_mm, float sensor_height_mm, float focus_distance, uint32_t height_px, float *out) {
+        return arctic_dof_coc_scale(f_number, focal_length_mm, sensor_height_mm, focus_distance, height_px, out) == ARCTIC_OK;
+    }
+
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }
 

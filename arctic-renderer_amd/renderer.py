@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, MOTION_BLUR_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, MOTION_BLUR_DTYPE, DOF_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -570,6 +570,72 @@ class Renderer:
         out = np.zeros(4, np.uint64)
         self._check(self.L.arctic_motion_blur_info(self.h, _ptr(out)))
         return tuple(int(x) for x in out)
+
+    # ---- depth of field (include/arctic_hip.h: arctic_dof_device and the definition in front of it) ------------------------------------------------
+    def dof_device(self, settings, d_hdr_ptr=None, d_depth_ptr=None, taps=None, d_out_ptr=None, focus_distance=5.0, coc_scale=8.0, max_radius=16.0, samples=16,
+                   depth_extent=0.5, z_near=0.1, z_far=1000.0, flags=0, dof=None):
+        """spread a device HDR plane (an int pointer: rows * width * 3 floats; None: the handle's own, per flags -- the latest shading's, under
+        DOF_SOURCE_COMPOSED the composition's, under DOF_SOURCE_TAA the anti-aliasing's history, under DOF_SOURCE_MOTION_BLUR the latest motion
+        blur's output) over each pixel's circle of confusion, from d_depth_ptr (rows * width floats, required) and the tap table `taps` ((samples,
+        2) float32 in the unit disc; None: dof_taps(samples)), then tonemap.  The result stays on the device -- d_out_ptr (rows * width * 4
+        bytes) or the handle's own buffers: read_dof().  dof: a DOF_DTYPE record instead of the parameters.  Asynchronous on the handle's stream."""
+        st = self._settings(settings)
+        m = _dof_arguments(flags, focus_distance, coc_scale, max_radius, samples, depth_extent, z_near, z_far) if dof is None else dof
+        t = _dof_table(taps, m)
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_dof_device(self.h, C.byref(st), _ptr(m), vp(d_hdr_ptr), vp(d_depth_ptr), _ptr(t), vp(d_out_ptr)))
+
+    def dof(self, settings, hdr=None, depth=None, taps=None, focus_distance=5.0, coc_scale=8.0, max_radius=16.0, samples=16, depth_extent=0.5, z_near=0.1, z_far=1000.0,
+            flags=0, dof=None, read=True):
+        """the same from and to host memory: hdr (rows, width, 3) float32 or None, depth (rows, width) float32 -> (rows, width, 4) uint8
+        (read=False: None, the result stays in the handle's buffers); synchronous"""
+        st = self._settings(settings)
+        m = _dof_arguments(flags, focus_distance, coc_scale, max_radius, samples, depth_extent, z_near, z_far) if dof is None else dof
+        t = _dof_table(taps, m)
+        c = None if hdr is None else np.ascontiguousarray(hdr, dtype=np.float32)
+        z = None if depth is None else np.ascontiguousarray(depth, dtype=np.float32)
+        n = (self.rows, self.width)
+        if (c is not None and c.shape != n + (3,)) or (z is not None and z.shape != n):
+            raise ArcticError(-1, f"dof: expected {n + (3,)} and {n}")
+        out = np.empty(n + (4,), np.uint8) if read else None
+        self._check(self.L.arctic_dof(self.h, C.byref(st), _ptr(m), _ptr(c), _ptr(z), _ptr(t), _ptr(out)))
+        return out
+
+    def pass_dof(self, desc, settings, d_out_ptr=None, taps=None, focus_distance=5.0, coc_scale=8.0, max_radius=16.0, samples=16, depth_extent=0.5, flags=0, dof=None, read=True):
+        """the one call: the depth into a plane the handle owns, then the gather of the handle's HDR plane per flags, under the scene's camera
+        planes (the record's z_near and z_far stay 0): (rows, width, 4) uint8.  read=False or a d_out_ptr leaves the result on the device and
+        returns None."""
+        s, st = self._scene(desc), self._settings(settings)
+        m = _dof_arguments(flags, focus_distance, coc_scale, max_radius, samples, depth_extent, 0.0, 0.0) if dof is None else dof
+        t = _dof_table(taps, m)
+        self._check(self.L.arctic_pass_dof(self.h, C.byref(s), C.byref(st), _ptr(m), _ptr(t), C.c_void_p(d_out_ptr) if d_out_ptr else None))
+        return self.read_dof(want=("rgba8",))[2] if read and not d_out_ptr else None
+
+    def read_dof(self, want=("ldr", "hdr", "rgba8", "tile_max", "neighbour_max", "prepared")):
+        """what the latest depth-of-field call left, row-major: (ldr (rows, width, 3), hdr (rows, width, 3) float32, rgba8 (rows, width, 4) uint8,
+        tile_max and neighbour_max (tiles_y, tiles_x), prepared (rows, width, 2) float32 {s, zv}); None for what was not asked for"""
+        n = (self.rows, self.width)
+        t = ((self.rows + 7) // 8, (self.width + 7) // 8)
+        ldr = np.empty(n + (3,), np.float32) if "ldr" in want else None
+        hdr = np.empty(n + (3,), np.float32) if "hdr" in want else None
+        rgba = np.empty(n + (4,), np.uint8) if "rgba8" in want else None
+        tile = np.empty(t, np.float32) if "tile_max" in want else None
+        nb = np.empty(t, np.float32) if "neighbour_max" in want else None
+        prep = np.empty(n + (2,), np.float32) if "prepared" in want else None
+        self._check(self.L.arctic_read_dof(self.h, _ptr(ldr), _ptr(hdr), _ptr(rgba), _ptr(tile), _ptr(nb), _ptr(prep)))
+        return ldr, hdr, rgba, tile, nb, prep
+
+    def dof_info(self):
+        """(device bytes, launches of k_dof_gather, calls, 0): all 0 until the first call"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_dof_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    def dof_focus_at(self, px, py, z_near, z_far):
+        """autofocus: the view distance of pixel (px, py) of the handle's rows in the resident visibility plane; synchronous"""
+        out = C.c_float(0.0)
+        self._check(self.L.arctic_dof_focus_at(self.h, float(z_near), float(z_far), int(px), int(py), C.byref(out)))
+        return float(out.value)
 
     def ray_scene_info(self):
         """(triangles stored, nodes, builds so far, depth) of the cached acceleration structure"""
@@ -1172,6 +1238,81 @@ def motion_blur_pixels(pixel_xy, rgb, prepared, neighbour_max, shutter=1.0, max_
     rc = binding.lib().arctic_motion_blur_pixels(_ptr(m), n, _ptr(xy) if n else None, int(width), int(height), _ptr(c), _ptr(p), _ptr(nb), _ptr(out) if n else None)
     if rc < 0:
         raise ArcticError(rc, "motion_blur_pixels")
+    return out
+
+
+def _dof_arguments(flags, focus_distance, coc_scale, max_radius, samples, depth_extent, z_near, z_far):
+    """one DOF_DTYPE record; the library checks every value"""
+    m = np.zeros(1, DOF_DTYPE)
+    m["flags"], m["focus_distance"], m["coc_scale"], m["max_radius"], m["samples"], m["depth_extent"] = flags, focus_distance, coc_scale, max_radius, samples, depth_extent
+    m["z_near"], m["z_far"] = z_near, z_far
+    return m
+
+
+def _dof_table(taps, m):
+    """the tap table of a call: the caller's as contiguous float32, or Vogel's spiral for the record's sample count"""
+    if taps is None:
+        n = int(m["samples"][0])
+        return dof_taps(n) if 1 <= n <= 64 else np.zeros((1, 2), np.float32)     # (the library refuses the count)
+    t = np.ascontiguousarray(taps, dtype=np.float32)
+    if t.ndim != 2 or t.shape[1] != 2 or len(t) < int(m["samples"][0]):
+        raise ArcticError(-1, "dof: taps is (samples, 2)")
+    return t
+
+
+def dof_taps(samples):
+    """a tap table for depth of field: (samples, 2) float32 in the unit disc, Vogel's spiral -- tap i at the radius sqrt((i + 0.5) / samples) and
+    the angle i times the golden angle -- computed in float64 and cast.  A convenience: the library takes any table inside the disc."""
+    n = int(samples)
+    i = np.arange(n, dtype=np.float64)
+    r, phi = np.sqrt((i + 0.5) / n), i * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi)], -1).astype(np.float32)
+
+
+def dof_coc_scale(f_number, focal_length_mm, sensor_height_mm, focus_distance, height_px):
+    """arctic_dof_coc_scale: the thin lens' radius of the circle of confusion at infinite distance, in pixels -- ArcticDof's coc_scale"""
+    out = C.c_float(0.0)
+    rc = binding.lib().arctic_dof_coc_scale(float(f_number), float(focal_length_mm), float(sensor_height_mm), float(focus_distance), int(height_px), C.byref(out))
+    if rc < 0:
+        raise ArcticError(rc, "dof_coc_scale")
+    return float(out.value)
+
+
+def dof_prepare(depth, focus_distance=5.0, coc_scale=8.0, max_radius=16.0, samples=16, depth_extent=0.5, z_near=0.1, z_far=1000.0, flags=0, dof=None):
+    """arctic_dof_prepare: steps 1 to 3 of depth of field of include/arctic_hip.h on the host, for a whole frame -- depth (height, width).
+    Returns (tile_max, neighbour_max) of shape (tiles_y, tiles_x) and P (height, width, 2)."""
+    z = np.ascontiguousarray(depth, dtype=np.float32)
+    if z.ndim != 2:
+        raise ArcticError(-1, "dof_prepare: depth is the whole frame, (height, width)")
+    height, width = z.shape
+    m = _dof_arguments(flags, focus_distance, coc_scale, max_radius, samples, depth_extent, z_near, z_far) if dof is None else dof
+    t = ((height + 7) // 8, (width + 7) // 8)
+    tile, nb, prep = np.empty(t, np.float32), np.empty(t, np.float32), np.empty((height, width, 2), np.float32)
+    rc = binding.lib().arctic_dof_prepare(_ptr(m), int(width), int(height), _ptr(z), _ptr(tile), _ptr(nb), _ptr(prep))
+    if rc < 0:
+        raise ArcticError(rc, "dof_prepare")
+    return tile, nb, prep
+
+
+def dof_pixels(pixel_xy, rgb, prepared, neighbour_max, taps=None, focus_distance=5.0, coc_scale=8.0, max_radius=16.0, samples=16, depth_extent=0.5, z_near=0.1, z_far=1000.0,
+               flags=0, dof=None):
+    """arctic_dof_pixels: step 4 of depth of field on the host, for n pixels in any order -- pixel_xy (n, 2) int32, rgb the WHOLE frame's colour
+    (height, width, 3), prepared and neighbour_max as dof_prepare returns them, taps (samples, 2) or None = dof_taps(samples).  Returns (n, 3) float32."""
+    xy = np.ascontiguousarray(pixel_xy, dtype=np.int32).reshape(-1, 2)
+    c = np.ascontiguousarray(rgb, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ArcticError(-1, "dof_pixels: rgb is the whole frame, (height, width, 3)")
+    height, width = c.shape[:2]
+    p, nb = np.ascontiguousarray(prepared, dtype=np.float32), np.ascontiguousarray(neighbour_max, dtype=np.float32)
+    if p.shape != (height, width, 2) or nb.shape != ((height + 7) // 8, (width + 7) // 8):
+        raise ArcticError(-1, "dof_pixels: prepared is (height, width, 2), neighbour_max (tiles_y, tiles_x)")
+    m = _dof_arguments(flags, focus_distance, coc_scale, max_radius, samples, depth_extent, z_near, z_far) if dof is None else dof
+    t = _dof_table(taps, m)
+    n = len(xy)
+    out = np.empty((n, 3), np.float32)
+    rc = binding.lib().arctic_dof_pixels(_ptr(m), _ptr(t), n, _ptr(xy) if n else None, int(width), int(height), _ptr(c), _ptr(p), _ptr(nb), _ptr(out) if n else None)
+    if rc < 0:
+        raise ArcticError(rc, "dof_pixels")
     return out
 
 

@@ -52,6 +52,9 @@ assert TAA_DTYPE.itemsize == 32
 # ArcticMotionBlur: the parameters of the motion blur (arctic_motion_blur_device)
 MOTION_BLUR_DTYPE = np.dtype([("flags", "<u4"), ("shutter", "<f4"), ("max_radius", "<f4"), ("samples", "<u4"), ("depth_extent", "<f4"), ("reserved", "<u4", 3)])
 assert MOTION_BLUR_DTYPE.itemsize == 32
+# ArcticDof: the parameters of depth of field (arctic_dof_device)
+DOF_DTYPE = np.dtype([("flags", "<u4"), ("focus_distance", "<f4"), ("coc_scale", "<f4"), ("max_radius", "<f4"), ("samples", "<u4"), ("depth_extent", "<f4"), ("z_near", "<f4"), ("z_far", "<f4")])
+assert DOF_DTYPE.itemsize == 32
 # ArcticRayNode / ArcticRayTri: the ray structure's records as arctic_read_ray_structure and arctic_refit_triangles return them
 RAY_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("skip", "<u4"), ("bmax", "<f4", 3), ("leaf", "<u4")])
 RAY_TRI_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("p2", "<f4", 3), ("prim", "<u4"), ("pad", "<u4", 2)])

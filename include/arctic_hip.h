@@ -1564,6 +1564,122 @@ int arctic_motion_blur_prepare(const ArcticMotionBlur *mb, uint32_t width, uint3
 int arctic_motion_blur_pixels(const ArcticMotionBlur *mb, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *rgb,
                               const float *prepared2, const float *neighbour_max2, float *out_rgb);
 
+/* ---- depth of field: circle-of-confusion tile maxima and a disc gather (no counterpart in the reference) -------------------------------------------
+ * The lens of the camera stage whose shutter is the motion blur above: a pixel away from the focus plane is spread over a disc whose radius
+ * follows the thin lens, in front of the tonemapper and BEHIND the motion blur.  It reads the float HDR colour (the shading's, the
+ * composition's, the anti-aliasing's history or the motion blur's output) and the prepass depth, nothing else.  Nothing in the passes or in the
+ * other calls changes: a handle that never makes these calls renders the same bytes and allocates nothing for them.
+ *
+ * THE DEFINITION.  Bit for bit: fp32 throughout, one rounding per operation in the written order, no contraction, IEEE division and square root.
+ * min, max and clamp01 are the motion blur's.  |x| clears the sign bit.
+ * INPUTS.  C: the HDR colour, rows x width x 3 floats, row-major.  Depth: rows x width floats as arctic_depth_plane_device writes them
+ *   (REQUIRED: without a depth there is nothing to focus on).  taps2: `samples` float2 offsets in the unit disc, HOST memory in every form of
+ *   the call, as the occlusion's direction table is; renderer.py's dof_taps gives Vogel's spiral.  W and H are the frame size; a tile is 8 x 8
+ *   pixels, tile(p) = (px / 8, py / 8), and the tile grid is ceil(W / 8) x ceil(H / 8).
+ *   1. VIEW DISTANCE AND SIGNED RADIUS.  With n = z_near, f = z_far and d = depth[p]:  den = f - d * (f - n);  zv = (n * f) / den if den > 0,
+ *      else zv = f (a NaN fails the test).  This inverts the camera's projection as the library draws it (perspectiveRH_ZO: a point at the
+ *      distance `dist` along the view axis has the depth f / (f - n) * (1 - n / dist)), so zv is that distance; a pixel without geometry
+ *      (depth 1.0) has zv = f up to rounding.
+ *      s = coc_scale * (1 - focus_distance / zv): negative in front of the focus plane.  If s is not finite, s = 0.  Then
+ *      s = min(max(s, -max_radius), max_radius).  a_p = max(|s_p|, A0) with A0 = 0.5641896f, which is 1 / sqrt(pi): a sharp pixel's disc has
+ *      the area of one pixel.  The prepared plane is P[p] = {s_p, zv_p} (float2, row-major).
+ *   2. TILE MAXIMUM.  tile_max[tile] = the largest |s_p| over the tile's pixels inside the frame: one float per tile.
+ *   3. NEIGHBOURHOOD MAXIMUM.  Rt = ceil(max_radius / 8) tiles.  neighbour_max[(tx, ty)] = the largest tile_max among the tiles
+ *      (tx+dx, ty+dy), |dx|, |dy| <= Rt, that lie inside the tile grid.
+ *   4. THE GATHER, for pixel p = (px, py) with R = neighbour_max[tile(p)]:
+ *      If !(R > 0.5):  out = C[p], bit for bit -- tiles that nothing out of focus can reach are copied.
+ *      Otherwise k = (R * R) / samples, w = 0.31830987f / (a_p * a_p), acc = C[p] * w, entered = false, and for i = 0 .. samples-1 in order,
+ *      with u = taps2[i]:
+ *        ox = u.x * R, oy = u.y * R.   qx = floor((px + 0.5) + ox), qy = floor((py + 0.5) + oy).
+ *        The tap is inside iff 0 <= qx <= W-1 and 0 <= qy <= H-1, tested in float before any conversion; a NaN fails.
+ *        dist = sqrt(ox*ox + oy*oy).  With {s_q, z_q} = P[q] and a_q = max(|s_q|, A0):
+ *          behind = clamp01((z_q - z_p) / depth_extent)
+ *          e = a_q - behind * (a_q - min(a_q, a_p))
+ *          cover = clamp01(e - dist)
+ *          a = (cover * k) / (a_q * a_q)
+ *        A tap behind the centre cannot spread further than the centre's own disc, so a blurred background does not bleed onto a sharp
+ *        foreground; a blurred foreground does spread over a sharp background.  A tap stands for R*R*pi / samples of area and a disc of radius
+ *        a_q has the density 1 / (pi * a_q * a_q): that is a; the centre is one pixel of area at its own density: that is the first w.
+ *        A tap outside the frame is a SELECT: nothing of it is read.  A tap whose a is not > 0 is a SELECT too: its colour does not enter,
+ *        so a NaN colour never spreads through a zero weight.  Otherwise w = w + a, acc = acc + C[q] * a per channel, entered = true.
+ *      out = entered ? acc / w : C[p].  The second select makes "a pixel that nothing covers keeps its bits" exact.
+ *   5. Store out (float3, row-major).  Then post_process of `out` under `settings`, as k_motion_blur carries it out: float LDR and RGBA8.
+ *      tile_max, neighbour_max, P and out are defined bit for bit; the tonemapped planes are held to the project's standing bar (1e-4 of the
+ *      float64 post_process).
+ * KNOWN LIMITS, stated and not worked around.  The gather radius is the tile neighbourhood's, so a mildly blurred pixel near a strongly
+ *   blurred one is sampled sparsely.  Weights are normalised, not alpha-composited.  The sky sits at about z_far.  Only whole frames are
+ *   handled: a shard's taps lie on other ranks, so a shard is refused as the motion blur refuses it.
+ * Refusals, in this order; every refusal comes before anything is enqueued, and a refused call writes nothing.
+ *   ARCTIC_E_INVALID: a null handle, settings or ArcticDof; unknown flag bits, or more than one source flag; a field outside the ranges
+ *     below, or a NaN; a null depth; a null taps2, a tap with a component that is not finite or with x*x + y*y > 1 in fp32; a device plane
+ *     that is misaligned: 4 bytes for C, the depth and RGBA8.
+ *   ARCTIC_E_STATE: a handle that does not own the whole frame; and, with a NULL colour plane: under ARCTIC_DOF_SOURCE_MOTION_BLUR no motion
+ *     blur since the last resize (arctic_read_motion_blur's condition); under ARCTIC_DOF_SOURCE_TAA and ARCTIC_DOF_SOURCE_COMPOSED, and with
+ *     no flag, what the motion blur refuses under ARCTIC_MB_SOURCE_TAA, ARCTIC_MB_SOURCE_COMPOSED and with no flag. */
+#define ARCTIC_DOF_SOURCE_COMPOSED     1u   /* a NULL colour = the latest composition's HDR plane instead of the latest shading's */
+#define ARCTIC_DOF_SOURCE_TAA          2u   /* a NULL colour = the anti-aliasing's history T */
+#define ARCTIC_DOF_SOURCE_MOTION_BLUR  4u   /* a NULL colour = the latest motion blur's HDR output; at most one of the three */
+typedef struct ArcticDof {                  /* 32 bytes */
+    uint32_t flags;
+    float focus_distance;                   /* > 0, finite: the view distance that is sharp */
+    float coc_scale;                        /* [0, 4096], finite: pixels of radius at infinite distance (arctic_dof_coc_scale) */
+    float max_radius;                       /* [1, 64]: pixels */
+    uint32_t samples;                       /* 1..64: taps per pixel */
+    float depth_extent;                     /* > 0, finite: the soft extent of the occlusion test, in view distance */
+    float z_near;                           /* > 0: the camera's planes, as the frame was drawn with */
+    float z_far;                            /* > z_near, finite */
+} ArcticDof;
+
+/* One call of the definition on DEVICE planes of a handle that owns the whole frame: k_dof_prepare, k_dof_neighbour_max, k_dof_gather.
+ * d_hdr_rgb32f: rows*width*3 floats, NULL = the handle's own plane per `flags`; d_depth: rows*width floats, required; taps2: samples float2
+ * in HOST memory, read before the call returns and sent through the handle's staged-upload ring when it differs from the table last sent;
+ * d_out_rgba8: rows*width*4 bytes, NULL = the handle's own buffer (arctic_read_dof).  No plane may alias another.  Stream-ordered on the
+ * handle's stream; a warm call allocates nothing and does not synchronise. */
+int arctic_dof_device(ArcticRenderer *r, const ArcticSettings *settings, const ArcticDof *dof, const float *d_hdr_rgb32f, const float *d_depth, const float *taps2,
+                      uint8_t *d_out_rgba8);
+
+/* The host form: the same kernels from and to host memory (hdr_rgb32f and out_rgba8 may be NULL, with the meanings above; a NULL output: the
+ * result stays in the handle's buffers).  Synchronous. */
+int arctic_dof(ArcticRenderer *r, const ArcticSettings *settings, const ArcticDof *dof, const float *hdr_rgb32f, const float *depth, const float *taps2, uint8_t *out_rgba8);
+
+/* The one call: arctic_depth_plane_device into a plane the handle owns, then the gather of the handle's HDR plane per `flags`.  Byte for
+ * byte the calls made by hand.  The block's z_near and z_far must both be 0 -- the call takes scene->camera.z_near_far, the planes the frame
+ * was drawn with -- and only this call accepts zeros there.  Behind the motion blur: render, arctic_pass_motion_blur, arctic_pass_dof with
+ * ARCTIC_DOF_SOURCE_MOTION_BLUR.  Every refusal of every step comes before anything is enqueued. */
+int arctic_pass_dof(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticDof *dof, const float *taps2, uint8_t *d_out_rgba8);
+
+/* What the latest call left, row-major: float LDR and the HDR colour (rows*width*3 floats each), the handle's own RGBA8, tile_max and
+ * neighbour_max (one float per tile of the tile grid, row-major) and P (rows*width float2).  Any pointer may be NULL.  Synchronises.
+ * ARCTIC_E_STATE before the first call and after a resize, and for rgba8 when the latest call wrote the caller's buffer. */
+int arctic_read_dof(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, float *tile_max, float *neighbour_max, float *prepared2);
+
+/* What the calls hold on this handle: out4 = {bytes of device memory, launches of k_dof_gather, calls, 0}.  All 0 until the first call that
+ * passes its checks.  Touches no device. */
+int arctic_dof_info(ArcticRenderer *r, uint64_t *out4);
+
+/* The host arbiters (no handle, no GPU), by the very functions the kernels run.  arctic_dof_prepare: steps 1 to 3 of a WHOLE frame -- depth
+ * (height*width floats) in; tile_max, neighbour_max (1 float per tile) and prepared2 (P: height*width*2 floats) out.  arctic_dof_pixels: step
+ * 4 for n pixels in any order -- taps2: samples float2; pixel_xy: (px, py) per pixel, inside the frame; rgb: the WHOLE frame's C
+ * (height*width*3 floats, row-major); prepared2 and neighbour_max as the first writes them; out_rgb: n*3 floats.  ARCTIC_E_INVALID (nothing
+ * written): what the gather refuses of ArcticDof and of taps2, a frame size outside 1..16384, a pixel outside the frame, a null array that is
+ * needed. */
+int arctic_dof_prepare(const ArcticDof *dof, uint32_t width, uint32_t height, const float *depth, float *tile_max, float *neighbour_max, float *prepared2);
+int arctic_dof_pixels(const ArcticDof *dof, const float *taps2, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *rgb,
+                      const float *prepared2, const float *neighbour_max, float *out_rgb);
+
+/* The thin lens in pixels -- a pure host function, no handle: the radius of the circle of confusion of a point at infinite distance, which is
+ * ArcticDof::coc_scale.  In fp32, in this order, with focus_distance in metres:  fl = focal_length_mm * 0.001;
+ * c = (fl * fl) / (f_number * (focus_distance - fl))  [the diameter on the sensor, metres];
+ * *out = ((0.5 * c) / (sensor_height_mm * 0.001)) * height_px.  A point at the distance D then has the radius *out * |1 - focus_distance / D|:
+ * step 1's s.  ARCTIC_E_INVALID (nothing written): a null out; f_number, focal_length_mm or sensor_height_mm not finite and above 0;
+ * height_px outside 1..16384; focus_distance not finite or not above fl; a result that is not finite. */
+int arctic_dof_coc_scale(float f_number, float focal_length_mm, float sensor_height_mm, float focus_distance, uint32_t height_px, float *out);
+
+/* Autofocus: step 1's zv of pixel (px, py) of the handle's rows (py counts from the handle's first row) of the resident visibility plane,
+ * under the planes z_near and z_far.  Synchronises.  ARCTIC_E_INVALID: a null handle or distance, planes outside ArcticDof's ranges, a pixel
+ * outside the handle's rows.  ARCTIC_E_STATE: no visibility plane (arctic_depth_plane_device's condition). */
+int arctic_dof_focus_at(ArcticRenderer *r, float z_near, float z_far, uint32_t px, uint32_t py, float *distance);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row
