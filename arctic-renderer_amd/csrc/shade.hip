@@ -1033,22 +1033,53 @@ __device__ __forceinline__ f3 lit_radiance(SP sp, uint32_t lane, float nr, float
 // ---- image-based ambient (ARCTIC_OPT_ENV_LIGHTING = 1, the k_envlit kernels; semantics in include/arctic_hip.h) ----------------
 // The bracket of   color = Lo (1 - shadow) + ambient [ (1 - F)(1 - metal) base E(n) / pi + P(R, rough) (F0 A + B) ]   from the tables
 // env_light.hip built (EnvTables): E from 27 SH coefficients (scalar loads), P trilinear over the specular levels (bilinear, WRAP;
-// the skybox's direction -> uv mapping), (A, B) bilinear from the clamped 64 x 64 table.  Plain fp32: the per-pixel lookups are
-// smooth functions of the direction (levels >= 1 are prefiltered; level 0 weighs in only below roughness 0.2).
-__device__ __forceinline__ f3 env_level(const EnvTables *T, uint32_t k, float u, float v) {
+// the skybox's direction -> uv mapping), (A, B) bilinear from the clamped 64 x 64 table.  E, F and (A, B) are plain fp32: smooth
+// functions of n and n.wo.  The lookup coordinates of P are binary64 from the G-buffer's own numbers (env_reflection), like the
+// skybox's: level 0 is the raw map, and an equirect's azimuth near a pole is x / z of R, which fp32 n and wo carry to 1e-6 only.
+// Measured (tests/test_gpu_env_shapes.py) on a 2048 x 1024 map with up to a factor 16 between neighbouring texels, float LDR:
+// fp32 coordinates were off by up to 4.6e-2 within a texel of the poles, 6.4 % of the test's pixels above the 1e-4 bar; binary64 ones
+// by 6.1e-5 at the most.  On a 128 x 64 map 2.2e-4 before, 2.4e-6 now.
+__device__ __forceinline__ f3 env_level(const EnvTables *T, uint32_t k, double u, double v) {
     const float4 *img = T->level[k];
     const uint32_t w = T->w[k], h = T->h[k];
     int x0, x1, y0, y1;
     float fx, fy;
-    wrap_axis(u, w, x0, x1, fx);
-    wrap_axis(v, h, y0, y1, fy);
+    wrap_axis64(u, w, x0, x1, fx);
+    wrap_axis64(v, h, y0, y1, fy);
     const float4 a = img[(size_t)y0 * w + x0], b = img[(size_t)y0 * w + x1], c = img[(size_t)y1 * w + x0], d = img[(size_t)y1 * w + x1];
     const float gx = 1.0f - fx, gy = 1.0f - fy;
     const float w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
     return mk(fm(w11, d.x, fm(w01, c.x, fm(w10, b.x, w00 * a.x))), fm(w11, d.y, fm(w01, c.y, fm(w10, b.y, w00 * a.y))),
               fm(w11, d.z, fm(w01, c.z, fm(w10, b.z, w00 * a.z))));
 }
-__device__ __forceinline__ f3 env_ambient(const EnvTables *T, f3 n, f3 wo, f3 base, float metal, float rough) {
+// P(R, rough) for a direction R of any length: the skybox's mapping, levels floor(5 r) and the next.  Out of line: binary64 atan2 and
+// asin need registers the tile code around the call has not got.
+__device__ __noinline__ f3 env_specular64(const EnvTables *T, double x, double y, double z, float rough) {
+    const double inv = 1.0 / sqrt(x * x + y * y + z * z);
+    const double u = atan2(z * inv, x * inv) * (double)0.1591f + 0.5;
+    const double v = -(asin(fmin(fmax(y * inv, -1.0), 1.0)) * (double)0.3183f + 0.5);
+    const float t = rough * (float)(ENV_LEVELS - 1);
+    const uint32_t k0 = min((uint32_t)t, ENV_LEVELS - 1), k1 = min(k0 + 1u, ENV_LEVELS - 1);
+    const float f = t - (float)k0;
+    const f3 P0 = env_level(T, k0, u, v), P1 = env_level(T, k1, u, v);
+    return mk(fm(f, P1.x - P0.x, P0.x), fm(f, P1.y - P0.y, P0.y), fm(f, P1.z - P0.z, P0.z));
+}
+// R = 2 (n.wo) n - wo (from the raw dot) in binary64.  cr, cg, cb: the normal-map channels on the 0..255 scale, ns: the scale of the
+// tangent-space x and y (get_normal / get_normal_scaled); gc, gd, ge: the G-buffer planes (world position, tangent frame)
+__device__ __forceinline__ f3 env_reflection(const EnvTables *T, float cr, float cg, float cb, float ns, const float4 &gc, const float4 &gd, const float4 &ge,
+                                             float ex, float ey, float ez, float rough) {
+    const double r = ((double)cr * (2.0 / 255.0) - 1.0) * ns, g = -((double)cg * (2.0 / 255.0) - 1.0) * ns, b = (double)cb * (2.0 / 255.0) - 1.0;
+    double nx = (double)ge.y * b + ((double)gd.z * g + (double)gc.w * r), ny = (double)ge.z * b + ((double)gd.w * g + (double)gd.x * r),
+           nz = (double)ge.w * b + ((double)ge.x * g + (double)gd.y * r);
+    const double ni = 1.0 / sqrt(nx * nx + ny * ny + nz * nz);
+    nx *= ni; ny *= ni; nz *= ni;
+    double wx = (double)ex - gc.x, wy = (double)ey - gc.y, wz = (double)ez - gc.z;
+    const double wi = 1.0 / sqrt(wx * wx + wy * wy + wz * wz);
+    wx *= wi; wy *= wi; wz *= wi;
+    const double two = 2.0 * (nx * wx + ny * wy + nz * wz);
+    return env_specular64(T, two * nx - wx, two * ny - wy, two * nz - wz, rough);
+}
+__device__ __forceinline__ f3 env_ambient(const EnvTables *T, f3 n, f3 wo, f3 P, f3 base, float metal, float rough) {
     typedef const float __attribute__((address_space(4))) *const_f;   // wave-uniform: the coefficients come through the scalar cache
     const const_f sh = (const_f)T->sh;
     // irradiance: real SH basis (env_light.hip sh_basis), A_l folded into the coefficients
@@ -1075,16 +1106,6 @@ __device__ __forceinline__ f3 env_ambient(const EnvTables *T, f3 n, f3 wo, f3 ba
     const float bx = 1.0f - ax, by = 1.0f - ay;
     const float A = fm(ax * ay, l11.x, fm(bx * ay, l01.x, fm(ax * by, l10.x, (bx * by) * l00.x)));
     const float B = fm(ax * ay, l11.y, fm(bx * ay, l01.y, fm(ax * by, l10.y, (bx * by) * l00.y)));
-    // P(R, rough): the skybox's mapping of R = 2 (n.wo) n - wo, levels floor(5 r) and the next
-    const float two = 2.0f * ndwo_raw;
-    const f3 R = normalize(mk(fm(two, n.x, -wo.x), fm(two, n.y, -wo.y), fm(two, n.z, -wo.z)));
-    const float u = atan2f(R.z, R.x) * 0.1591f + 0.5f;
-    const float v = -(asinf(fminf(fmaxf(R.y, -1.0f), 1.0f)) * 0.3183f + 0.5f);
-    const float t = rough * (float)(ENV_LEVELS - 1);
-    const uint32_t k0 = min((uint32_t)t, ENV_LEVELS - 1), k1 = min(k0 + 1u, ENV_LEVELS - 1);
-    const float f = t - (float)k0;
-    const f3 P0 = env_level(T, k0, u, v), P1 = env_level(T, k1, u, v);
-    const f3 P = mk(fm(f, P1.x - P0.x, P0.x), fm(f, P1.y - P0.y, P0.y), fm(f, P1.z - P0.z, P0.z));
     const float kb = oml * INV_PI;
     return mk(fm((1.0f - F.x) * kb * base.x, E[0], P.x * fm(F0.x, A, B)),
               fm((1.0f - F.y) * kb * base.y, E[1], P.y * fm(F0.y, A, B)),
@@ -1434,7 +1455,8 @@ __device__ __forceinline__ void shade_tile(SP sp, const float *lut, uint32_t ty,
         if (ENV) {   // the image-based ambient replaces ambient * base (n, wo: what lit_radiance takes)
             const f3 n = PBR ? get_normal_scaled(nr, ng, nb, gc, gd, ge, x_nscale) : get_normal(nr, ng, nb, gc, gd, ge);
             const f3 wo = normalize(mk(sp.eye[0], sp.eye[1], sp.eye[2]) - mk(gc.x, gc.y, gc.z));
-            color = env_ambient(sp.env_tables, n, wo, base, metal, rough) * sp.ambient;
+            const f3 P = env_reflection(sp.env_tables, nr, ng, nb, PBR ? x_nscale : 1.0f, gc, gd, ge, sp.eye[0], sp.eye[1], sp.eye[2], rough);
+            color = env_ambient(sp.env_tables, n, wo, P, base, metal, rough) * sp.ambient;
             if (PBR) color = color * ao;
         }
         if (!ENV || live) {

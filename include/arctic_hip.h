@@ -623,7 +623,8 @@ int arctic_stats(ArcticRenderer *r, uint64_t *out, uint32_t n);
  *               (level m + 1 = max(1, w / 2) x max(1, h / 2), texel = mean of (2i + a, 2j + b), clamped to the last row / column) at
  *               lod = max(0, log2(Omega_s / Omega_p) / 2 + 1), Omega_s = 4 / (512 D), Omega_p = 4 pi / (W H), linear between mip levels.
  *               GGX frame around n: tangent = normalize(cross(up, n)), up = z unless |n.z| >= 0.999, then x.  At run time P is trilinear:
- *               levels floor(5 r) and floor(5 r) + 1 (the last one clamped), each bilinear with WRAP.
+ *               levels floor(5 r) and floor(5 r) + 1 (the last one clamped), each bilinear with WRAP.  R and its texel coordinates are
+ *               binary64 from the pixel's attributes (tangent frame, normal texel, eye - world), the filter weights and the blend fp32.
  *   (A, B)      64 x 64 RG fp32 at cell centres (n.v, r), 1024 Hammersley samples, Smith-Schlick with k = r^2 / 2 (the IBL form; the direct
  *               lights keep (r + 1)^2 / 8, on purpose); looked up bilinearly, clamped.
  * ARCTIC_OPT_COUNT_LIGHT_EVALS and ARCTIC_OPT_TILE_TRACE do not apply in mode 1 (a shading call then returns ARCTIC_E_STATE), and

@@ -107,8 +107,9 @@ def level_size(W, H, k):
     return max(8, min(W, 512) >> (k - 1)), max(4, min(H, 256) >> (k - 1))
 
 
-def prefilter_level(env, k):
-    """(h, w, 3) float64: specular level k >= 1 of the map"""
+def prefilter_level(env, k, texels=None):
+    """(h, w, 3) float64: specular level k >= 1 of the map; texels = a list of (row, column) pairs of the level: only those texels,
+    (len(texels), 3), the same numbers the whole level holds there"""
     H_, W_ = env.shape[:2]
     w, h = level_size(W_, H_, k)
     mips = mip_chain(env)
@@ -116,6 +117,9 @@ def prefilter_level(env, k):
     alpha = r * r
     a2 = alpha * alpha
     n, _ = texel_dirs(w, h)
+    if texels is not None:
+        rc = np.asarray(texels, np.int64).reshape(-1, 2)
+        n = n[rc[:, 0], rc[:, 1]]
     n = n.reshape(-1, 3)
     x1, x2 = hammersley(SAMPLES)
     out = np.zeros((n.shape[0], 3))
@@ -140,7 +144,7 @@ def prefilter_level(env, k):
             c += sample_uv(mips[m], u, v) * wgt[..., None]
         keep = (nl > 0).astype(np.float64) * nl
         out[s0:s0 + 256] = np.einsum("psc,ps->pc", c, keep) / keep.sum(1)[:, None]
-    return out.reshape(h, w, 3)
+    return out if texels is not None else out.reshape(h, w, 3)
 
 
 def brdf_lut():

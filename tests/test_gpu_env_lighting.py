@@ -229,6 +229,10 @@ def test_full_size_frame_is_finite(pkg, hip):
     _, hdr1, _ = r.read_output()
     assert np.isfinite(hdr1).all()
     assert not np.array_equal(img1, ref0)
+    # 2048 x 1024: eight trips per thread in k_env_sh_rows, four in k_env_sh_final
+    sh = r.read_env_lighting(level=ER.LEVELS - 1)[0]
+    want = ER.sh_project(sc.environment)
+    assert np.abs(sh - want).max() <= 1e-6 * np.abs(want[0]).max(), np.abs(sh - want).max()
     r.set_option("env_lighting", 0)
     np.testing.assert_array_equal(r.render_frame(sc.desc, sc.settings), ref0)
     r.close()
