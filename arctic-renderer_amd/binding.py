@@ -20,6 +20,7 @@ COMPOSE_AO, COMPOSE_REFLECTIONS = 1, 2   # ARCTIC_COMPOSE_*
 TAA_LUMA_WEIGHT, TAA_SOURCE_COMPOSED = 1, 2   # ARCTIC_TAA_*
 MB_DITHER, MB_SOURCE_COMPOSED, MB_SOURCE_TAA = 1, 2, 4   # ARCTIC_MB_*
 DOF_SOURCE_COMPOSED, DOF_SOURCE_TAA, DOF_SOURCE_MOTION_BLUR = 1, 2, 4   # ARCTIC_DOF_*
+BLOOM_SOURCE_COMPOSED, BLOOM_SOURCE_TAA, BLOOM_SOURCE_MOTION_BLUR, BLOOM_SOURCE_DOF = 1, 2, 4, 8   # ARCTIC_BLOOM_*
 ERRORS = {-1: "ARCTIC_E_INVALID", -2: "ARCTIC_E_DEVICE", -3: "ARCTIC_E_NO_DEVICE", -4: "ARCTIC_E_STATE", -5: "ARCTIC_E_CAPACITY"}
 
 _vp, _u32, _u64, _i32, _i64 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_int64
@@ -154,6 +155,13 @@ SIGNATURES = {
     "arctic_dof_pixels": (_i32, [_vp, _vp, _u64, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "arctic_dof_coc_scale": (_i32, [C.c_float, C.c_float, C.c_float, C.c_float, _u32, _vp]),
     "arctic_dof_focus_at": (_i32, [_vp, C.c_float, C.c_float, _u32, _u32, _vp]),
+    "arctic_bloom_device": (_i32, [_vp, _settings, _vp, _vp, _vp]),
+    "arctic_bloom": (_i32, [_vp, _settings, _vp, _vp, _vp]),
+    "arctic_read_bloom": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_bloom_info": (_i32, [_vp, _vp]),
+    "arctic_bloom_layout": (_i32, [_u32, _u32, _u32, _vp]),
+    "arctic_bloom_pyramid": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp]),
+    "arctic_bloom_pixels": (_i32, [_vp, _u64, _vp, _u32, _u32, _vp, _vp, _vp]),
     "arctic_version": (_i32, []),
     # include/arctic_dist.h: the multi-GPU exchange steps
     "arctic_comm_unique_id": (_i32, [_vp, _vp, _u64]),

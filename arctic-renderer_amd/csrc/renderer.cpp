@@ -133,6 +133,7 @@ int alloc_targets(ArcticRenderer *r) {
     r->taa.valid = false;          // (... and the anti-aliasing's T; the camera jitter stays)
     r->motion_blur.valid = false;  // (... and what the latest motion blur left)
     r->dof.valid = false;          // (... and the latest depth of field)
+    r->bloom.valid = false;        // (... and the latest bloom)
     r->output_filtered = false;
     return ARCTIC_OK;
 }

@@ -473,6 +473,19 @@ struct ArcticRenderer {
         uint64_t launches = 0, calls = 0;
         size_t device_bytes() const { return d_prep.cap + d_tile.cap + d_neighbour.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_depth.cap + d_taps.cap; }
     } dof;
+    // Bloom (arctic_bloom_device; bloom.hip, owned by bloom_calls.cpp): d_down and d_up are the two pyramids of include/arctic_hip.h as
+    // arctic_bloom_layout packs them, sized for 8 levels whatever a call asks for; d_hdr the composite, d_rgba8 and d_ldr its tonemapped planes;
+    // d_color: the host form's plane.  `written`: recorded behind every call, waited for by the next one if the handle's stream has changed in
+    // between.  Nothing is allocated before the first call that passes its checks; valid: the planes hold a call's result at width x height
+    // with `levels` levels (cleared by a resize); own_rgba8: that call wrote d_rgba8, not the caller's buffer
+    struct Bloom {
+        DevBuf d_down, d_up, d_hdr, d_rgba8, d_ldr, d_color;
+        bool valid = false, own_rgba8 = false;
+        uint32_t width = 0, height = 0, levels = 0;
+        StreamMark written;
+        uint64_t launches = 0, calls = 0;
+        size_t device_bytes() const { return d_down.cap + d_up.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap; }
+    } bloom;
     PinnedBuf counts;             // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts

@@ -494,6 +494,31 @@ class Renderer {
         return arctic_dof_coc_scale(f_number, focal_length_mm, sensor_height_mm, focus_distance, height_px, out) == ARCTIC_OK;
     }
 
+    // bloom (include/arctic_hip.h: arctic_bloom_device and the definition in front of it).  The pyramid and the composite on device planes
+    // (nullptr: the handle's HDR plane per bloom.flags, the handle's own output); stream-ordered
+    [[nodiscard]] bool bloom_device(const ArcticSettings &settings, const ArcticBloom &bloom, const float *d_hdr_rgb32f, uint8_t *d_out_rgba8) {
+        return ok(arctic_bloom_device(m_handle, &settings, &bloom, d_hdr_rgb32f, d_out_rgba8));
+    }
+    // the same from and to host memory; synchronous
+    [[nodiscard]] bool bloom(const ArcticSettings &settings, const ArcticBloom &bloom, const float *hdr_rgb32f, uint8_t *out_rgba8) {
+        return ok(arctic_bloom(m_handle, &settings, &bloom, hdr_rgb32f, out_rgba8));
+    }
+    // what the latest call left, row-major, the pyramids as bloom_layout packs them; any pointer may be nullptr
+    [[nodiscard]] bool read_bloom(float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, float *down, float *up) {
+        return ok(arctic_read_bloom(m_handle, ldr_rgb, hdr_rgb, rgba8, down, up));
+    }
+    // {device bytes, launches of k_bloom_composite, calls, 0}
+    [[nodiscard]] bool bloom_info(uint64_t out4[4]) { return ok(arctic_bloom_info(m_handle, out4)); }
+    // the layout (out: 3 * levels + 2 numbers) and the host arbiters: no handle, no GPU
+    [[nodiscard]] static bool bloom_layout(uint32_t width, uint32_t height, uint32_t levels, uint64_t *out) { return arctic_bloom_layout(width, height, levels, out) == ARCTIC_OK; }
+    [[nodiscard]] static bool bloom_pyramid(const ArcticBloom &bloom, uint32_t width, uint32_t height, const float *rgb, float *down, float *up) {
+        return arctic_bloom_pyramid(&bloom, width, height, rgb, down, up) == ARCTIC_OK;
+    }
+    [[nodiscard]] static bool bloom_pixels(const ArcticBloom &bloom, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *rgb, const float *up1,
+                                           float *out_rgb) {
+        return arctic_bloom_pixels(&bloom, n, pixel_xy, width, height, rgb, up1, out_rgb) == ARCTIC_OK;
+    }
+
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }
 

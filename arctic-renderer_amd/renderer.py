@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, MOTION_BLUR_DTYPE, DOF_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, MOTION_BLUR_DTYPE, DOF_DTYPE, BLOOM_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -636,6 +636,50 @@ class Renderer:
         out = C.c_float(0.0)
         self._check(self.L.arctic_dof_focus_at(self.h, float(z_near), float(z_far), int(px), int(py), C.byref(out)))
         return float(out.value)
+
+    # ---- bloom (include/arctic_hip.h: arctic_bloom_device and the definition in front of it) --------------------------------------------------------
+    def bloom_device(self, settings, d_hdr_ptr=None, d_out_ptr=None, threshold=1.0, soft_knee=0.5, clamp_max=65504.0, intensity=0.5, spread=1.0, levels=5, flags=0, bloom=None):
+        """bloom of a device HDR plane (an int pointer: rows * width * 3 floats; None: the handle's own, per flags -- the latest shading's, under
+        BLOOM_SOURCE_COMPOSED the composition's, under BLOOM_SOURCE_TAA the anti-aliasing's history, under BLOOM_SOURCE_MOTION_BLUR the latest
+        motion blur's and under BLOOM_SOURCE_DOF the latest depth of field's output): prefilter, `levels` levels down, up again, composite,
+        tonemap.  The result stays on the device -- d_out_ptr (rows * width * 4 bytes) or the handle's own buffers: read_bloom().  bloom: a
+        BLOOM_DTYPE record instead of the parameters.  Asynchronous on the handle's stream."""
+        st = self._settings(settings)
+        m = _bloom_arguments(flags, threshold, soft_knee, clamp_max, intensity, spread, levels) if bloom is None else bloom
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_bloom_device(self.h, C.byref(st), _ptr(m), vp(d_hdr_ptr), vp(d_out_ptr)))
+
+    def bloom(self, settings, hdr=None, threshold=1.0, soft_knee=0.5, clamp_max=65504.0, intensity=0.5, spread=1.0, levels=5, flags=0, bloom=None, read=True):
+        """the same from and to host memory: hdr (rows, width, 3) float32 or None -> (rows, width, 4) uint8 (read=False: None, the result stays
+        in the handle's buffers); synchronous"""
+        st = self._settings(settings)
+        m = _bloom_arguments(flags, threshold, soft_knee, clamp_max, intensity, spread, levels) if bloom is None else bloom
+        c = None if hdr is None else np.ascontiguousarray(hdr, dtype=np.float32)
+        n = (self.rows, self.width)
+        if c is not None and c.shape != n + (3,):
+            raise ArcticError(-1, f"bloom: expected {n + (3,)}")
+        out = np.empty(n + (4,), np.uint8) if read else None
+        self._check(self.L.arctic_bloom(self.h, C.byref(st), _ptr(m), _ptr(c), _ptr(out)))
+        return out
+
+    def read_bloom(self, levels, want=("ldr", "hdr", "rgba8", "down", "up")):
+        """what the latest bloom call left: (ldr (rows, width, 3), hdr (rows, width, 3) float32, rgba8 (rows, width, 4) uint8, down: the list of
+        D_1 .. D_L as (H_k, W_k, 3) arrays, up: the list of U_1 .. U_{L-1}); None for what was not asked for.  levels: that call's"""
+        n = (self.rows, self.width)
+        lay = bloom_layout(self.width, self.rows, levels)
+        ldr = np.empty(n + (3,), np.float32) if "ldr" in want else None
+        hdr = np.empty(n + (3,), np.float32) if "hdr" in want else None
+        rgba = np.empty(n + (4,), np.uint8) if "rgba8" in want else None
+        down = np.empty(max(lay["down_floats"], 1), np.float32) if "down" in want else None
+        up = np.empty(max(lay["up_floats"], 1), np.float32) if "up" in want else None
+        self._check(self.L.arctic_read_bloom(self.h, _ptr(ldr), _ptr(hdr), _ptr(rgba), _ptr(down), _ptr(up)))
+        return ldr, hdr, rgba, _bloom_split(down, lay, levels), _bloom_split(up, lay, levels - 1)
+
+    def bloom_info(self):
+        """(device bytes, launches of k_bloom_composite, calls, 0): all 0 until the first call"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_bloom_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
 
     def ray_scene_info(self):
         """(triangles stored, nodes, builds so far, depth) of the cached acceleration structure"""
@@ -1313,6 +1357,70 @@ def dof_pixels(pixel_xy, rgb, prepared, neighbour_max, taps=None, focus_distance
     rc = binding.lib().arctic_dof_pixels(_ptr(m), _ptr(t), n, _ptr(xy) if n else None, int(width), int(height), _ptr(c), _ptr(p), _ptr(nb), _ptr(out) if n else None)
     if rc < 0:
         raise ArcticError(rc, "dof_pixels")
+    return out
+
+
+def _bloom_arguments(flags, threshold, soft_knee, clamp_max, intensity, spread, levels):
+    """one BLOOM_DTYPE record; the library checks every value"""
+    m = np.zeros(1, BLOOM_DTYPE)
+    m["flags"], m["threshold"], m["soft_knee"], m["clamp_max"], m["intensity"], m["spread"], m["levels"] = flags, threshold, soft_knee, clamp_max, intensity, spread, levels
+    return m
+
+
+def _bloom_split(packed, lay, count):
+    """the first `count` levels of a packed pyramid as (H_k, W_k, 3) views"""
+    if packed is None:
+        return None
+    return [packed[o:o + h * w * 3].reshape(h, w, 3) for (w, h), o in zip(lay["sizes"][:count], lay["offsets"][:count])]
+
+
+def bloom_layout(width, height, levels):
+    """arctic_bloom_layout: the pyramid of a width x height frame -- {"sizes": [(W_k, H_k)], "offsets": [floats from the start of `down` to D_k;
+    U_k lies at the same offset of `up`], "down_floats", "up_floats"}"""
+    n = int(levels)
+    out = np.zeros(3 * max(min(n, 8), 1) + 2, np.uint64)
+    rc = binding.lib().arctic_bloom_layout(int(width), int(height), n, _ptr(out))
+    if rc < 0:
+        raise ArcticError(rc, "bloom_layout")
+    return {"sizes": [(int(out[3 * k]), int(out[3 * k + 1])) for k in range(n)], "offsets": [int(out[3 * k + 2]) for k in range(n)],
+            "down_floats": int(out[3 * n]), "up_floats": int(out[3 * n + 1])}
+
+
+def bloom_pyramid(rgb, threshold=1.0, soft_knee=0.5, clamp_max=65504.0, intensity=0.5, spread=1.0, levels=5, flags=0, bloom=None):
+    """arctic_bloom_pyramid: steps 1 to 3 of bloom of include/arctic_hip.h on the host, for a whole frame -- rgb (height, width, 3).  Returns
+    (down, up): the lists of D_1 .. D_L and U_1 .. U_{L-1} as (H_k, W_k, 3) float32 arrays."""
+    c = np.ascontiguousarray(rgb, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ArcticError(-1, "bloom_pyramid: rgb is the whole frame, (height, width, 3)")
+    height, width = c.shape[:2]
+    m = _bloom_arguments(flags, threshold, soft_knee, clamp_max, intensity, spread, levels) if bloom is None else bloom
+    n = int(m["levels"][0])
+    lay = bloom_layout(width, height, n) if 1 <= n <= 8 and 1 <= width <= 16384 and 1 <= height <= 16384 else None     # (the library refuses the rest)
+    down = np.empty(max(lay["down_floats"], 1) if lay else 1, np.float32)
+    up = np.empty(max(lay["up_floats"], 1) if lay else 1, np.float32)
+    rc = binding.lib().arctic_bloom_pyramid(_ptr(m), int(width), int(height), _ptr(c), _ptr(down), _ptr(up))
+    if rc < 0:
+        raise ArcticError(rc, "bloom_pyramid")
+    return _bloom_split(down, lay, n), _bloom_split(up, lay, n - 1)
+
+
+def bloom_pixels(pixel_xy, rgb, up1, threshold=1.0, soft_knee=0.5, clamp_max=65504.0, intensity=0.5, spread=1.0, levels=5, flags=0, bloom=None):
+    """arctic_bloom_pixels: step 4 of bloom on the host, for n pixels in any order -- pixel_xy (n, 2) int32, rgb the WHOLE frame's colour
+    (height, width, 3), up1: U_1 ((height + 1) // 2, (width + 1) // 2, 3); D_1 when levels = 1.  Returns (n, 3) float32."""
+    xy = np.ascontiguousarray(pixel_xy, dtype=np.int32).reshape(-1, 2)
+    c = np.ascontiguousarray(rgb, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ArcticError(-1, "bloom_pixels: rgb is the whole frame, (height, width, 3)")
+    height, width = c.shape[:2]
+    u = np.ascontiguousarray(up1, dtype=np.float32)
+    if u.shape != ((height + 1) // 2, (width + 1) // 2, 3):
+        raise ArcticError(-1, "bloom_pixels: up1 is ((height + 1) // 2, (width + 1) // 2, 3)")
+    m = _bloom_arguments(flags, threshold, soft_knee, clamp_max, intensity, spread, levels) if bloom is None else bloom
+    n = len(xy)
+    out = np.empty((n, 3), np.float32)
+    rc = binding.lib().arctic_bloom_pixels(_ptr(m), n, _ptr(xy) if n else None, int(width), int(height), _ptr(c), _ptr(u), _ptr(out) if n else None)
+    if rc < 0:
+        raise ArcticError(rc, "bloom_pixels")
     return out
 
 

@@ -55,6 +55,9 @@ assert MOTION_BLUR_DTYPE.itemsize == 32
 # ArcticDof: the parameters of depth of field (arctic_dof_device)
 DOF_DTYPE = np.dtype([("flags", "<u4"), ("focus_distance", "<f4"), ("coc_scale", "<f4"), ("max_radius", "<f4"), ("samples", "<u4"), ("depth_extent", "<f4"), ("z_near", "<f4"), ("z_far", "<f4")])
 assert DOF_DTYPE.itemsize == 32
+# ArcticBloom: the parameters of bloom (arctic_bloom_device)
+BLOOM_DTYPE = np.dtype([("flags", "<u4"), ("threshold", "<f4"), ("soft_knee", "<f4"), ("clamp_max", "<f4"), ("intensity", "<f4"), ("spread", "<f4"), ("levels", "<u4"), ("reserved", "<u4")])
+assert BLOOM_DTYPE.itemsize == 32
 # ArcticRayNode / ArcticRayTri: the ray structure's records as arctic_read_ray_structure and arctic_refit_triangles return them
 RAY_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("skip", "<u4"), ("bmax", "<f4", 3), ("leaf", "<u4")])
 RAY_TRI_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("p2", "<f4", 3), ("prim", "<u4"), ("pad", "<u4", 2)])

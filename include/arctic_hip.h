@@ -1681,6 +1681,106 @@ int arctic_dof_coc_scale(float f_number, float focal_length_mm, float sensor_hei
  * outside the handle's rows.  ARCTIC_E_STATE: no visibility plane (arctic_depth_plane_device's condition). */
 int arctic_dof_focus_at(ArcticRenderer *r, float z_near, float z_far, uint32_t px, uint32_t py, float *distance);
 
+/* ---- bloom: a thresholded mip pyramid composed in front of the tonemapper (no counterpart in the reference) ----------------------------------------
+ * The glow of the lens: what is brighter than a threshold is spread over a pyramid of ever coarser planes and added back, the LAST stage in
+ * front of the tonemapper, BEHIND the depth of field.  The filters are Jimenez's ("Next Generation Post Processing in Call of Duty: Advanced
+ * Warfare", 2014): a 13-tap downsample with Karis' luminance weights on the first level, and a 3 x 3 tent on the way up -- restated on integer
+ * texels so that they are defined bit for bit like every stage in front of the tonemapper here.  It reads the float HDR colour (the shading's,
+ * the composition's, the anti-aliasing's history, the motion blur's or the depth of field's output), nothing else.  Nothing in the passes or
+ * in the other calls changes: a handle that never makes these calls renders the same bytes and allocates nothing for them.
+ *
+ * THE DEFINITION.  Bit for bit: fp32 throughout, one rounding per operation in the written order, no contraction, IEEE division.
+ * min and max are the motion blur's.  Every clamp(i, lo, hi) of an index is an integer clamp.
+ * INPUTS.  C: the HDR colour, rows x width x 3 floats, row-major.  The frame is W x H.  Level sizes: W_0 = W, H_0 = H,
+ *   W_k = (W_{k-1} + 1) / 2, H_k = (H_{k-1} + 1) / 2 in integer division; a level of 1 x 1 is valid, and so is every level below it.
+ *   `levels` is L, 1..8.  Every plane of the pyramid is row-major float3.
+ *   1. PREFILTER, per pixel q of the frame.  Per channel x = C[q] > 0 ? min(C[q], clamp_max) : 0 -- a NaN fails the test and becomes 0, +inf
+ *      becomes clamp_max, a negative value becomes 0.  br = max(x.r, max(x.g, x.b)).  knee = threshold * soft_knee.
+ *      t = br - (threshold - knee).  t = min(max(t, 0), 2 * knee).  soft = (t * t) / (4 * knee + 1e-5f).  m = max(soft, br - threshold).
+ *      contrib = min(m / max(br, 1e-5f), 1).  b[q] = x * contrib per channel.
+ *   2. DOWN(S, Ws, Hs) at destination pixel (x, y).  The footprint is S~(i, j) = S[clamp(2x - 2 + i, 0, Ws - 1), clamp(2y - 2 + j, 0, Hs - 1)],
+ *      i, j = 0..5.  Box(a, b) = ((S~(a,b) + S~(a+1,b)) + (S~(a,b+1) + S~(a+1,b+1))) * 0.25.
+ *      Group(a, b) = ((Box(a,b) + Box(a+2,b)) + (Box(a,b+2) + Box(a+2,b+2))) * 0.25.
+ *      G0 = Group(1,1), G1 = Group(0,0), G2 = Group(2,0), G3 = Group(0,2), G4 = Group(2,2): the 13 bilinear taps of Jimenez's downsample on
+ *      integer texels, 36 texels and 13 distinct boxes.
+ *      Plain form: out = G0 * 0.5 + ((G1 + G2) + (G3 + G4)) * 0.125.
+ *      Karis form, for the first level only, to suppress fireflies: l_g = (0.2126f * G.r + 0.7152f * G.g) + 0.0722f * G.b;
+ *      w_0 = 0.5f / (1 + l_0), w_g = 0.125f / (1 + l_g) for g = 1..4; num = w_0 * G0 + ((w_1 * G1 + w_2 * G2) + (w_3 * G3 + w_4 * G4));
+ *      den = w_0 + ((w_1 + w_2) + (w_3 + w_4)); out = num / den.
+ *      D_1 = DOWN_karis(b, W, H), and D_k = DOWN(D_{k-1}, W_{k-1}, H_{k-1}) for k = 2..L.
+ *   3. UP(T, Wt, Ht) at destination pixel (x, y) of the next finer level.  With h = x >> 1: even x has base = h - 2 and
+ *      wx = (0.0625f, 0.3125f, 0.4375f, 0.1875f); odd x has base = h - 1 and wx = (0.1875f, 0.4375f, 0.3125f, 0.0625f).  The same rule
+ *      applies in y.  This is the 3 x 3 tent of bilinear taps one coarse texel apart, restated; its weights are exact sixteenths.
+ *      T~(i, j) = T[clamp(bx + i, 0, Wt - 1), clamp(by + j, 0, Ht - 1)], i, j = 0..3.
+ *      r_j = (wx0 * T~(0,j) + wx1 * T~(1,j)) + (wx2 * T~(2,j) + wx3 * T~(3,j)).  out = (wy0 * r_0 + wy1 * r_1) + (wy2 * r_2 + wy3 * r_3).
+ *      U_L = D_L.  For k = L-1 .. 1, U_k = D_k + spread * UP(U_{k+1}) at level k's size.
+ *   4. COMPOSITE, per pixel p.  B = UP(U_1, W_1, H_1) at the frame's size.  a = intensity * B per channel.  out = a > 0 ? C[p] + a : C[p].
+ *      The composite is a SELECT, so a pixel that no bloom reaches keeps its bits, a NaN included.
+ *   5. Store out (float3, row-major).  Then post_process of `out` under `settings`, exactly as k_dof_gather carries it out: float LDR and
+ *      RGBA8.  The D_k, U_k and out are defined bit for bit; the tonemapped planes are held to the project's standing bar (1e-4 of the
+ *      float64 post_process).
+ * EXACT PROPERTIES.  Every D_k and U_k is finite and >= 0 whatever C holds: step 1 removes NaN, infinity and negatives, and everything after
+ *   it is a bounded sum.  If every pixel has br <= threshold - knee, every plane is +0 and out equals C by bits.
+ * KNOWN LIMITS, stated and not worked around.  The footprint is corner-centred, so a single pixel's glow is not symmetric about it.  There is
+ *   no lens dirt and no per-level tint.  Only whole frames are handled: a shard's footprint lies on other ranks, so a shard is refused as the
+ *   blur and the lens refuse it.
+ * Refusals, in this order; every refusal comes before anything is enqueued, and a refused call writes nothing.
+ *   ARCTIC_E_INVALID: a null handle, settings or ArcticBloom; unknown flag bits, or more than one source flag; a field outside the ranges
+ *     below, or a NaN; reserved != 0; a device plane that is misaligned: 4 bytes for C and RGBA8.
+ *   ARCTIC_E_STATE: a handle that does not own the whole frame; and, with a NULL colour plane: under ARCTIC_BLOOM_SOURCE_DOF no depth of field
+ *     since the last resize (arctic_read_dof's condition); under the other three flags and with no flag, what arctic_dof_device refuses under
+ *     ARCTIC_DOF_SOURCE_MOTION_BLUR, ARCTIC_DOF_SOURCE_TAA, ARCTIC_DOF_SOURCE_COMPOSED and with no flag. */
+#define ARCTIC_BLOOM_SOURCE_COMPOSED     1u   /* a NULL colour = the latest composition's HDR plane instead of the latest shading's */
+#define ARCTIC_BLOOM_SOURCE_TAA          2u   /* a NULL colour = the anti-aliasing's history T */
+#define ARCTIC_BLOOM_SOURCE_MOTION_BLUR  4u   /* a NULL colour = the latest motion blur's HDR output */
+#define ARCTIC_BLOOM_SOURCE_DOF          8u   /* a NULL colour = the latest depth of field's HDR output; at most one of the four */
+#define ARCTIC_BLOOM_MAX_LEVELS          8u
+typedef struct ArcticBloom {                  /* 32 bytes */
+    uint32_t flags;
+    float threshold;                          /* [0, 65504], finite: the brightness where the glow begins */
+    float soft_knee;                          /* [0, 1]: the part of the threshold below it over which the glow fades in */
+    float clamp_max;                          /* (0, 65504]: no channel enters the pyramid above it */
+    float intensity;                          /* [0, 16]: the composite's factor */
+    float spread;                             /* [0, 1]: what every coarser level adds to the next finer one */
+    uint32_t levels;                          /* 1..8: L */
+    uint32_t reserved;                        /* must be 0 */
+} ArcticBloom;
+
+/* One call of the definition on DEVICE planes of a handle that owns the whole frame: k_bloom_down_first, L-1 times k_bloom_down, L-1 times
+ * k_bloom_up, k_bloom_composite -- 2L launches.  d_hdr_rgb32f: rows*width*3 floats, NULL = the handle's own plane per `flags`;
+ * d_out_rgba8: rows*width*4 bytes, NULL = the handle's own buffer (arctic_read_bloom).  No plane may alias another.  Stream-ordered on the
+ * handle's stream; a warm call allocates nothing and does not synchronise. */
+int arctic_bloom_device(ArcticRenderer *r, const ArcticSettings *settings, const ArcticBloom *bloom, const float *d_hdr_rgb32f, uint8_t *d_out_rgba8);
+
+/* The host form: the same kernels from and to host memory (hdr_rgb32f and out_rgba8 may be NULL, with the meanings above; a NULL output: the
+ * result stays in the handle's buffers).  Synchronous. */
+int arctic_bloom(ArcticRenderer *r, const ArcticSettings *settings, const ArcticBloom *bloom, const float *hdr_rgb32f, uint8_t *out_rgba8);
+
+/* What the latest call left, row-major: float LDR and `out` (rows*width*3 floats each), the handle's own RGBA8, and the two pyramids as
+ * arctic_bloom_layout packs them for that call's `levels`: `down` holds D_1 .. D_L and `up` holds U_1 .. U_{L-1} (U_L is D_L; nothing is
+ * written to `up` when L = 1).  Any pointer may be NULL.  Synchronises.  ARCTIC_E_STATE before the first call and after a resize, and for
+ * rgba8 when the latest call wrote the caller's buffer. */
+int arctic_read_bloom(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, float *down, float *up);
+
+/* What the calls hold on this handle: out4 = {bytes of device memory, launches of k_bloom_composite, calls, 0}.  All 0 until the first call
+ * that passes its checks.  Touches no device. */
+int arctic_bloom_info(ArcticRenderer *r, uint64_t *out4);
+
+/* The pyramid's layout -- a pure host function, no handle.  out: 3 * levels + 2 numbers: {W_k, H_k, offset_k} for k = 1 .. levels, where
+ * offset_k counts FLOATS from the start of `down` to D_k (the levels are packed in level order, W_k * H_k * 3 floats each), then the floats
+ * of `down` and the floats of `up`.  U_k lies at offset_k of `up`.  ARCTIC_E_INVALID (nothing written): a null out, a frame size outside
+ * 1..16384, levels outside 1..8. */
+int arctic_bloom_layout(uint32_t width, uint32_t height, uint32_t levels, uint64_t *out);
+
+/* The host arbiters (no handle, no GPU), by the very functions the kernels run.  arctic_bloom_pyramid: steps 1 to 3 of a WHOLE frame -- rgb
+ * (height*width*3 floats) in; `down` and `up` out, as arctic_bloom_layout packs them (`up` may be NULL when levels = 1).
+ * arctic_bloom_pixels: step 4 for n pixels in any order -- pixel_xy: (px, py) per pixel, inside the frame; rgb: the WHOLE frame's C; up1: U_1
+ * (H_1*W_1*3 floats; D_1 when levels = 1); out_rgb: n*3 floats.  ARCTIC_E_INVALID (nothing written): what the call refuses of ArcticBloom, a
+ * frame size outside 1..16384, a pixel outside the frame, a null array that is needed. */
+int arctic_bloom_pyramid(const ArcticBloom *bloom, uint32_t width, uint32_t height, const float *rgb, float *down, float *up);
+int arctic_bloom_pixels(const ArcticBloom *bloom, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *rgb, const float *up1,
+                        float *out_rgb);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row
