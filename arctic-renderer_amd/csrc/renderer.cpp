@@ -134,6 +134,7 @@ int alloc_targets(ArcticRenderer *r) {
     r->motion_blur.valid = false;  // (... and what the latest motion blur left)
     r->dof.valid = false;          // (... and the latest depth of field)
     r->bloom.valid = false;        // (... and the latest bloom)
+    r->exposure.valid = r->exposure.planes = false;   // (... and the exposure's adaptation and planes)
     r->output_filtered = false;
     return ARCTIC_OK;
 }

@@ -486,6 +486,20 @@ struct ArcticRenderer {
         uint64_t launches = 0, calls = 0;
         size_t device_bytes() const { return d_down.cap + d_up.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap; }
     } bloom;
+    // Auto-exposure (arctic_exposure_device; exposure.hip, owned by exposure_calls.cpp): d_partials is the meter's table T[G][256] of
+    // include/arctic_hip.h, d_hist the histogram H, d_state the 32-byte state record; d_hdr the exposed frame, d_rgba8 and d_ldr its tonemapped
+    // planes (never allocated under ARCTIC_EXPOSURE_METER_ONLY); d_color: the host form's plane.  `written`: recorded behind every call, waited
+    // for by the next one if the handle's stream has changed in between.  Nothing is allocated before the first call that passes its checks;
+    // valid: d_state and d_hist hold a metering call's result at width x height (cleared by a resize and by arctic_exposure_reset: the next
+    // resolve ignores what the record holds); planes: the output planes hold an applying call's; own_rgba8: that call wrote d_rgba8
+    struct Exposure {
+        DevBuf d_partials, d_hist, d_state, d_hdr, d_rgba8, d_ldr, d_color;
+        bool valid = false, planes = false, own_rgba8 = false;
+        uint32_t width = 0, height = 0;
+        StreamMark written;
+        uint64_t launches = 0, calls = 0, meters = 0;
+        size_t device_bytes() const { return d_partials.cap + d_hist.cap + d_state.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap; }
+    } exposure;
     PinnedBuf counts;             // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts

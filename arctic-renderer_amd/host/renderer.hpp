@@ -519,6 +519,33 @@ class Renderer {
         return arctic_bloom_pixels(&bloom, n, pixel_xy, width, height, rgb, up1, out_rgb) == ARCTIC_OK;
     }
 
+    // auto-exposure (include/arctic_hip.h: arctic_exposure_device and the definition in front of it).  Meter, resolve and apply on device planes
+    // (nullptr: the handle's HDR plane per exposure.flags, the handle's own output); stream-ordered, nothing is read back
+    [[nodiscard]] bool exposure_device(const ArcticSettings &settings, const ArcticExposure &exposure, const float *d_hdr_rgb32f, uint8_t *d_out_rgba8) {
+        return ok(arctic_exposure_device(m_handle, &settings, &exposure, d_hdr_rgb32f, d_out_rgba8));
+    }
+    // the same from and to host memory; synchronous
+    [[nodiscard]] bool exposure(const ArcticSettings &settings, const ArcticExposure &exposure, const float *hdr_rgb32f, uint8_t *out_rgba8) {
+        return ok(arctic_exposure(m_handle, &settings, &exposure, hdr_rgb32f, out_rgba8));
+    }
+    // what the latest calls left; any pointer may be nullptr
+    [[nodiscard]] bool read_exposure(float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, uint32_t *hist256, ArcticExposureState *state) {
+        return ok(arctic_read_exposure(m_handle, ldr_rgb, hdr_rgb, rgba8, hist256, state));
+    }
+    [[nodiscard]] bool exposure_reset() { return ok(arctic_exposure_reset(m_handle)); }
+    // {device bytes, launches of k_exposure_apply, calls, launches of k_exposure_meter}
+    [[nodiscard]] bool exposure_info(uint64_t out4[4]) { return ok(arctic_exposure_info(m_handle, out4)); }
+    // the meter's geometry (out: 3 numbers), the per-call rate and the host arbiters: no handle, no GPU
+    [[nodiscard]] static bool exposure_layout(uint32_t width, uint32_t height, uint64_t *out3) { return arctic_exposure_layout(width, height, out3) == ARCTIC_OK; }
+    [[nodiscard]] static float exposure_rate(float dt, float speed) { return arctic_exposure_rate(dt, speed); }
+    [[nodiscard]] static bool exposure_histogram(const ArcticExposure &exposure, uint32_t width, uint32_t height, const float *rgb, uint32_t *hist256) {
+        return arctic_exposure_histogram(&exposure, width, height, rgb, hist256) == ARCTIC_OK;
+    }
+    [[nodiscard]] static bool exposure_resolve(const ArcticExposure &exposure, const uint32_t *hist256, const ArcticExposureState *previous, ArcticExposureState *state) {
+        return arctic_exposure_resolve(&exposure, hist256, previous, state) == ARCTIC_OK;
+    }
+    [[nodiscard]] static bool exposure_pixels(uint64_t n, const float *rgb, float exposure, float *out_rgb) { return arctic_exposure_pixels(n, rgb, exposure, out_rgb) == ARCTIC_OK; }
+
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }
 

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, MOTION_BLUR_DTYPE, DOF_DTYPE, BLOOM_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, MOTION_BLUR_DTYPE, DOF_DTYPE, BLOOM_DTYPE, EXPOSURE_DTYPE, EXPOSURE_STATE_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -679,6 +679,53 @@ class Renderer:
         """(device bytes, launches of k_bloom_composite, calls, 0): all 0 until the first call"""
         out = np.zeros(4, np.uint64)
         self._check(self.L.arctic_bloom_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    # ---- auto-exposure (include/arctic_hip.h: arctic_exposure_device and the definition in front of it) ---------------------------------------------
+    def exposure_device(self, settings, d_hdr_ptr=None, d_out_ptr=None, exposure=None, **kw):
+        """auto-exposure of a device HDR plane (an int pointer: rows * width * 3 floats; None: the handle's own, per flags -- the latest shading's,
+        or the plane EXPOSURE_SOURCE_COMPOSED, _TAA, _MOTION_BLUR, _DOF or _BLOOM names): meter, resolve, apply, tonemap.  The result stays on
+        the device -- d_out_ptr (rows * width * 4 bytes) or the handle's own buffers: read_exposure().  exposure: an EXPOSURE_DTYPE record
+        instead of the parameters of exposure_arguments().  Asynchronous on the handle's stream; nothing is read back."""
+        st = self._settings(settings)
+        m = exposure_arguments(**kw) if exposure is None else exposure
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_exposure_device(self.h, C.byref(st), _ptr(m), vp(d_hdr_ptr), vp(d_out_ptr)))
+
+    def exposure(self, settings, hdr=None, exposure=None, read=True, **kw):
+        """the same from and to host memory: hdr (rows, width, 3) float32 or None -> (rows, width, 4) uint8 (read=False or EXPOSURE_METER_ONLY:
+        None, the result stays in the handle's buffers); synchronous"""
+        st = self._settings(settings)
+        m = exposure_arguments(**kw) if exposure is None else exposure
+        c = None if hdr is None else np.ascontiguousarray(hdr, dtype=np.float32)
+        n = (self.rows, self.width)
+        if c is not None and c.shape != n + (3,):
+            raise ArcticError(-1, f"exposure: expected {n + (3,)}")
+        read = read and not (int(m["flags"][0]) & binding.EXPOSURE_METER_ONLY)
+        out = np.empty(n + (4,), np.uint8) if read else None
+        self._check(self.L.arctic_exposure(self.h, C.byref(st), _ptr(m), _ptr(c), _ptr(out)))
+        return out
+
+    def read_exposure(self, want=("ldr", "hdr", "rgba8", "hist", "state")):
+        """what the latest calls left: (ldr (rows, width, 3), hdr (rows, width, 3) float32, rgba8 (rows, width, 4) uint8, hist (256,) uint32,
+        state: one EXPOSURE_STATE_DTYPE record); None for what was not asked for"""
+        n = (self.rows, self.width)
+        ldr = np.empty(n + (3,), np.float32) if "ldr" in want else None
+        hdr = np.empty(n + (3,), np.float32) if "hdr" in want else None
+        rgba = np.empty(n + (4,), np.uint8) if "rgba8" in want else None
+        hist = np.empty(256, np.uint32) if "hist" in want else None
+        state = np.zeros(1, EXPOSURE_STATE_DTYPE) if "state" in want else None
+        self._check(self.L.arctic_read_exposure(self.h, _ptr(ldr), _ptr(hdr), _ptr(rgba), _ptr(hist), _ptr(state)))
+        return ldr, hdr, rgba, hist, state
+
+    def exposure_reset(self):
+        """forget the adaptation: the next metering call starts from an invalid state"""
+        self._check(self.L.arctic_exposure_reset(self.h))
+
+    def exposure_info(self):
+        """(device bytes, launches of k_exposure_apply, calls, launches of k_exposure_meter): all 0 until the first call"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_exposure_info(self.h, _ptr(out)))
         return tuple(int(x) for x in out)
 
     def ray_scene_info(self):
@@ -1421,6 +1468,76 @@ def bloom_pixels(pixel_xy, rgb, up1, threshold=1.0, soft_knee=0.5, clamp_max=655
     rc = binding.lib().arctic_bloom_pixels(_ptr(m), n, _ptr(xy) if n else None, int(width), int(height), _ptr(c), _ptr(u), _ptr(out) if n else None)
     if rc < 0:
         raise ArcticError(rc, "bloom_pixels")
+    return out
+
+
+def exposure_arguments(flags=0, low=0.5, high=0.95, key_value=0.18, min_exposure=1.0 / 1024.0, max_exposure=1024.0, rate_up=1.0, rate_down=1.0, fallback_exposure=1.0,
+                       window=(0, 0, 0, 0), low_q16=None, high_q16=None):
+    """one EXPOSURE_DTYPE record; low, high: the percentile band as fractions (floored to 1/65536), or low_q16, high_q16 as they are; the
+    library checks every value"""
+    m = np.zeros(1, EXPOSURE_DTYPE)
+    m["flags"] = flags
+    m["low_q16"] = int(low * 65536.0) if low_q16 is None else low_q16
+    m["high_q16"] = int(high * 65536.0) if high_q16 is None else high_q16
+    m["key_value"], m["min_exposure"], m["max_exposure"], m["rate_up"], m["rate_down"], m["fallback_exposure"] = key_value, min_exposure, max_exposure, rate_up, rate_down, fallback_exposure
+    m["window"][0] = window
+    return m
+
+
+def exposure_layout(width, height):
+    """arctic_exposure_layout: the meter's launch geometry for a width x height frame -- {"groups": G, "pixels_per_trip": the pixels a workgroup
+    takes per trip of its loop, "table_bytes": the bytes of T[G][256]}"""
+    out = np.zeros(3, np.uint64)
+    rc = binding.lib().arctic_exposure_layout(int(width), int(height), _ptr(out))
+    if rc < 0:
+        raise ArcticError(rc, "exposure_layout")
+    return {"groups": int(out[0]), "pixels_per_trip": int(out[1]), "table_bytes": int(out[2])}
+
+
+def exposure_rate(dt, speed):
+    """arctic_exposure_rate: 1 - exp(-dt * speed) as a float in [0, 1], the per-call rate of an adaptation of `speed` per second"""
+    return float(binding.lib().arctic_exposure_rate(float(dt), float(speed)))
+
+
+def exposure_histogram(rgb, exposure=None, **kw):
+    """arctic_exposure_histogram: step 1 of auto-exposure of include/arctic_hip.h on the host, for a whole frame -- rgb (height, width, 3).
+    Returns H, (256,) uint32."""
+    c = np.ascontiguousarray(rgb, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ArcticError(-1, "exposure_histogram: rgb is the whole frame, (height, width, 3)")
+    m = exposure_arguments(**kw) if exposure is None else exposure
+    hist = np.empty(256, np.uint32)
+    rc = binding.lib().arctic_exposure_histogram(_ptr(m), int(c.shape[1]), int(c.shape[0]), _ptr(c), _ptr(hist))
+    if rc < 0:
+        raise ArcticError(rc, "exposure_histogram")
+    return hist
+
+
+def exposure_resolve(hist, previous=None, exposure=None, **kw):
+    """arctic_exposure_resolve: step 2 on the host -- hist (256,) uint32 and the state in front of the call (an EXPOSURE_STATE_DTYPE record, or
+    None: invalid).  Returns the state behind it, one EXPOSURE_STATE_DTYPE record."""
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    if h.shape != (256,):
+        raise ArcticError(-1, "exposure_resolve: hist is (256,)")
+    m = exposure_arguments(**kw) if exposure is None else exposure
+    prev = None if previous is None else np.ascontiguousarray(previous, dtype=EXPOSURE_STATE_DTYPE).reshape(1)
+    out = np.zeros(1, EXPOSURE_STATE_DTYPE)
+    rc = binding.lib().arctic_exposure_resolve(_ptr(m), _ptr(h), _ptr(prev), _ptr(out))
+    if rc < 0:
+        raise ArcticError(rc, "exposure_resolve")
+    return out
+
+
+def exposure_pixels(rgb, e):
+    """arctic_exposure_pixels: step 3's multiply on the host -- rgb (..., 3) float32 and the exposure E.  Returns an array of rgb's shape."""
+    c = np.ascontiguousarray(rgb, dtype=np.float32)
+    if c.ndim < 1 or c.shape[-1] != 3:
+        raise ArcticError(-1, "exposure_pixels: rgb is (..., 3)")
+    out = np.empty_like(c)
+    n = c.size // 3
+    rc = binding.lib().arctic_exposure_pixels(n, _ptr(c) if n else None, float(e), _ptr(out) if n else None)
+    if rc < 0:
+        raise ArcticError(rc, "exposure_pixels")
     return out
 
 

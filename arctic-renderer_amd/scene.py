@@ -58,6 +58,12 @@ assert DOF_DTYPE.itemsize == 32
 # ArcticBloom: the parameters of bloom (arctic_bloom_device)
 BLOOM_DTYPE = np.dtype([("flags", "<u4"), ("threshold", "<f4"), ("soft_knee", "<f4"), ("clamp_max", "<f4"), ("intensity", "<f4"), ("spread", "<f4"), ("levels", "<u4"), ("reserved", "<u4")])
 assert BLOOM_DTYPE.itemsize == 32
+# ArcticExposure: the parameters of auto-exposure (arctic_exposure_device), and ArcticExposureState: what it keeps on the device
+EXPOSURE_DTYPE = np.dtype([("flags", "<u4"), ("low_q16", "<u4"), ("high_q16", "<u4"), ("key_value", "<f4"), ("min_exposure", "<f4"), ("max_exposure", "<f4"), ("rate_up", "<f4"),
+                           ("rate_down", "<f4"), ("fallback_exposure", "<f4"), ("window", "<u4", 4), ("reserved", "<u4")])
+assert EXPOSURE_DTYPE.itemsize == 56
+EXPOSURE_STATE_DTYPE = np.dtype([("adapted_key", "<f8"), ("exposure", "<f4"), ("luminance", "<f4"), ("metered", "<u4"), ("valid", "<u4"), ("frames", "<u4"), ("reserved", "<u4")])
+assert EXPOSURE_STATE_DTYPE.itemsize == 32
 # ArcticRayNode / ArcticRayTri: the ray structure's records as arctic_read_ray_structure and arctic_refit_triangles return them
 RAY_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("skip", "<u4"), ("bmax", "<f4", 3), ("leaf", "<u4")])
 RAY_TRI_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("p2", "<f4", 3), ("prim", "<u4"), ("pad", "<u4", 2)])

@@ -1781,6 +1781,131 @@ int arctic_bloom_pyramid(const ArcticBloom *bloom, uint32_t width, uint32_t heig
 int arctic_bloom_pixels(const ArcticBloom *bloom, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *rgb, const float *up1,
                         float *out_rgb);
 
+/* ---- auto-exposure: a luminance histogram, eye adaptation and the exposed frame in front of the tonemapper (no counterpart in the reference) -----
+ * The meter of the chain: the frame's luminance is binned into a 256-bin histogram, a percentile band of it gives a mean log luminance, the
+ * mean is adapted over time, and the frame is multiplied by the exposure E that maps the adapted luminance to `key_value` -- the LAST stage in
+ * front of the tonemapper, BEHIND bloom.  It reads the float HDR colour (the shading's, the composition's, the anti-aliasing's history, the
+ * motion blur's, the depth of field's or bloom's output), nothing else.  The histogram, the adapted state and E stay in device memory: the
+ * three launches of a call are stream-ordered and nothing is read back.  Nothing in the passes or in the other calls changes: a handle that
+ * never makes these calls renders the same bytes and allocates nothing for them.
+ *
+ * THE DEFINITION.  Bit for bit: fp32 unless marked binary64, one rounding per operation in the written order, no contraction, IEEE division.
+ * There is no transcendental in it: the logarithm and its inverse are the float's own bit pattern.  min and max are the motion blur's.
+ * INPUTS.  C: the HDR colour, rows x width x 3 floats, row-major.  The frame is W x H.  The metering window is [x0, x1) x [y0, y1): the
+ *   record's `window`, or the whole frame when all four are zero.  The state record (ArcticExposureState) of the handle, valid or not.
+ *   1. METER, per pixel q inside the window.  Per channel x = C[q] > 0 ? min(C[q], 65504.0f) : 0 -- a NaN fails the test and becomes 0, +inf
+ *      becomes 65504, a negative value becomes 0.  l = (0.2126f * x.r + 0.7152f * x.g) + 0.0722f * x.b.  key = bits(l) >> 20: the sign is 0, so
+ *      keys are monotone in l, 8 keys per octave.  bin = clamp(key - 888, 0, 255) as an integer clamp; 888 = (127 - 16) * 8.  Bin 0 is "black",
+ *      everything below 1.125 * 2^-16; bin 255 ends just under 2^16, which 65504 cannot exceed.  H[bin] += 1, H being uint32[256]: the counts
+ *      are integers, so H does not depend on the order of the additions or on the launch geometry.
+ *   2. RESOLVE.  Under ARCTIC_EXPOSURE_SKIP_BLACK H' is H with H'[0] = 0, otherwise H' = H.  N = sum H' in uint64.
+ *      lo = (N * low_q16) >> 16 and hi = (N * high_q16) >> 16.  P_0 = 0, P_{b+1} = P_b + H'[b].
+ *      c_b = max(0, min(P_{b+1}, hi) - max(P_b, lo)): the pixels of bin b whose rank lies in [lo, hi).  M = sum c_b and S = sum b * c_b, uint64.
+ *      If M == 0 there is no measurement: adapted_key, luminance, valid and frames of the state are left as they are (an invalid state stays
+ *      invalid, with adapted_key = 0 and luminance = 0), metered = 0, and E = min(max(fallback_exposure, min_exposure), max_exposure).
+ *      Otherwise, in binary64: m = (double)S / (double)M and a_t = m + 888.5.  If the state is invalid or ARCTIC_EXPOSURE_RESET is set, a = a_t
+ *      and frames = 1.  Else rate = a_t > a_prev ? rate_up : rate_down, a = a_prev + (a_t - a_prev) * (double)rate -- two roundings, no fma --
+ *      and frames += 1.  L = float_from_bits((uint32)(a * 1048576.0)): the product is exact and the cast truncates; L is the float whose key is
+ *      the adapted mean key, at the middle of its bin.  E = min(max(key_value / L, min_exposure), max_exposure).
+ *      The state becomes {adapted_key = a, exposure = E, luminance = L, metered = M saturated at 2^32 - 1, valid = 1, frames, reserved = 0}.
+ *   3. APPLY, per pixel of the WHOLE frame, not the window.  out = C * E per channel: one multiply; a NaN stays a NaN, a -0 stays a -0.
+ *      Store out (float3, row-major).  Then post_process of `out` under `settings`, exactly as k_bloom_composite ends: float LDR and RGBA8.
+ *      settings->exposure keeps its meaning for tm_exposure and is independent of E.
+ *   H, the state and out are defined bit for bit; the tonemapped planes are held to the project's standing bar (1e-4 of the float64
+ *   post_process of the kernel's own out, RGBA8 within one step).
+ * EXACT PROPERTIES.  (i) H sums to the window's pixel count whatever C holds.  (ii) Scaling a frame by 2^k shifts every key by 8k; when no
+ *   pixel touches bin 0, bin 255 or the 65504 clamp before or after and ARCTIC_EXPOSURE_RESET is set, a_t shifts by 8k (exactly when M is a
+ *   power of two, else to the last place of the binary64 division), L scales by exactly 2^k, E by exactly 2^-k, and out is the same bytes.  (iii) A constant grey l inside the range gives |L / l - 1| <= 1/16: L is the
+ *   middle of l's bin.  (iv) The state after n calls on one frame is binary64 arithmetic; a moves monotonically towards a_t.
+ * KNOWN LIMITS, stated and not worked around.  The logarithm is piecewise linear, at most 0.0861 octaves off log2; with the bin's half width
+ *   L lies within 2^(2 * 0.0861 + 1/16) = 1.177 of the true geometric mean of the band.  Adaptation is linear in the key domain at the
+ *   caller's per-frame rates (arctic_exposure_rate is the convenience).  Metering is uniform inside the window.  Bloom's threshold is applied
+ *   in front of this stage, so it sees unexposed radiance.  Only whole frames are handled: a shard is refused as the blur, the lens and bloom
+ *   refuse it.
+ * FLAGS.  ARCTIC_EXPOSURE_HOLD: no meter and no resolve, the E the latest metering call left is applied with one launch.
+ *   ARCTIC_EXPOSURE_METER_ONLY: no apply, and no output plane is allocated or written -- for a host that feeds E to its own tonemapper.
+ * Refusals, in this order; every refusal comes before anything is enqueued, and a refused call writes nothing, the state included.
+ *   ARCTIC_E_INVALID: a null handle, settings or ArcticExposure; unknown flag bits, or more than one source flag; ARCTIC_EXPOSURE_HOLD
+ *     together with ARCTIC_EXPOSURE_METER_ONLY or ARCTIC_EXPOSURE_RESET; a field outside the ranges below, or a NaN; a window that is neither
+ *     all zero nor inside the frame; reserved != 0; a device plane that is misaligned: 4 bytes for C and RGBA8.
+ *   ARCTIC_E_STATE: a handle that does not own the whole frame; with a NULL colour plane: under ARCTIC_EXPOSURE_SOURCE_BLOOM no bloom since
+ *     the last resize (arctic_read_bloom's condition); under the other four flags and with no flag, what arctic_bloom_device refuses under
+ *     ARCTIC_BLOOM_SOURCE_DOF, _MOTION_BLUR, _TAA, _COMPOSED and with no flag; and under ARCTIC_EXPOSURE_HOLD: no metering call since the
+ *     handle was created, since arctic_exposure_reset or since the last resize. */
+#define ARCTIC_EXPOSURE_SOURCE_COMPOSED     1u   /* a NULL colour = the latest composition's HDR plane instead of the latest shading's */
+#define ARCTIC_EXPOSURE_SOURCE_TAA          2u   /* a NULL colour = the anti-aliasing's history T */
+#define ARCTIC_EXPOSURE_SOURCE_MOTION_BLUR  4u   /* a NULL colour = the latest motion blur's HDR output */
+#define ARCTIC_EXPOSURE_SOURCE_DOF          8u   /* a NULL colour = the latest depth of field's HDR output */
+#define ARCTIC_EXPOSURE_SOURCE_BLOOM        16u  /* a NULL colour = the latest bloom's HDR output; at most one of the five */
+#define ARCTIC_EXPOSURE_SKIP_BLACK          32u  /* bin 0 does not count */
+#define ARCTIC_EXPOSURE_RESET               64u  /* this call adapts at once: a = a_t */
+#define ARCTIC_EXPOSURE_HOLD                128u /* apply the held E; nothing is metered */
+#define ARCTIC_EXPOSURE_METER_ONLY          256u /* meter and resolve; nothing is applied */
+typedef struct ArcticExposure {                  /* 56 bytes */
+    uint32_t flags;
+    uint32_t low_q16;                            /* 0 <= low_q16 < high_q16 <= 65536: the percentile band in 1/65536 */
+    uint32_t high_q16;
+    float key_value;                             /* (0, 65504]: the mid grey the mean luminance is mapped to, exposure compensation folded in */
+    float min_exposure;                          /* 0 < min_exposure <= max_exposure <= 65504 */
+    float max_exposure;
+    float rate_up;                               /* [0, 1]: the part of the way a moves per call when a_t lies above it */
+    float rate_down;                             /* [0, 1]: ... and when it does not */
+    float fallback_exposure;                     /* (0, 65504]: E of a call that measured nothing */
+    uint32_t window[4];                          /* x0, y0, x1, y1; all zero = the whole frame; else x0 < x1 <= W, y0 < y1 <= H */
+    uint32_t reserved;                           /* must be 0 */
+} ArcticExposure;
+typedef struct ArcticExposureState {             /* 32 bytes, on the device */
+    double adapted_key;                          /* a */
+    float exposure;                              /* E of the latest metering call */
+    float luminance;                             /* L */
+    uint32_t metered;                            /* M of the latest metering call, saturated */
+    uint32_t valid;                              /* a and L hold a measurement */
+    uint32_t frames;                             /* measurements folded into a since it last began at a_t */
+    uint32_t reserved;
+} ArcticExposureState;
+
+/* One call of the definition on DEVICE planes of a handle that owns the whole frame: k_exposure_meter, k_exposure_resolve, k_exposure_apply
+ * (HOLD: the last alone; METER_ONLY: the first two).  d_hdr_rgb32f: rows*width*3 floats, NULL = the handle's own plane per `flags`;
+ * d_out_rgba8: rows*width*4 bytes, NULL = the handle's own buffer (arctic_read_exposure).  No plane may alias another.  Stream-ordered on
+ * the handle's stream; a warm call allocates nothing and does not synchronise. */
+int arctic_exposure_device(ArcticRenderer *r, const ArcticSettings *settings, const ArcticExposure *exposure, const float *d_hdr_rgb32f, uint8_t *d_out_rgba8);
+
+/* The host form: the same kernels from and to host memory (hdr_rgb32f and out_rgba8 may be NULL, with the meanings above; a NULL output: the
+ * result stays in the handle's buffers).  Synchronous. */
+int arctic_exposure(ArcticRenderer *r, const ArcticSettings *settings, const ArcticExposure *exposure, const float *hdr_rgb32f, uint8_t *out_rgba8);
+
+/* What the latest calls left: float LDR and `out` (rows*width*3 floats each) and the handle's own RGBA8 of the latest call that applied; H
+ * (256 counts) and the state record of the latest call that metered.  Any pointer may be NULL.  Synchronises.  ARCTIC_E_STATE: nothing of
+ * what is asked for since the handle was created, arctic_exposure_reset or the last resize; and for rgba8 when the latest call wrote the
+ * caller's buffer. */
+int arctic_read_exposure(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, uint32_t *hist256, ArcticExposureState *state);
+
+/* Forgets the adaptation: the next metering call starts from an invalid state, and ARCTIC_EXPOSURE_HOLD is refused until then.  Nothing is
+ * enqueued and nothing freed. */
+int arctic_exposure_reset(ArcticRenderer *r);
+
+/* What the calls hold on this handle: out4 = {bytes of device memory, launches of k_exposure_apply, calls, launches of k_exposure_meter}.
+ * All 0 until the first call that passes its checks.  Touches no device. */
+int arctic_exposure_info(ArcticRenderer *r, uint64_t *out4);
+
+/* The meter's launch geometry -- a pure host function, no handle.  out3 = {G: the workgroups of k_exposure_meter and the rows of its partials
+ * table T[G][256], the pixels a workgroup takes per trip of its loop, the bytes of T}.  ARCTIC_E_INVALID (nothing written): a null out3, a
+ * frame size outside 1..16384. */
+int arctic_exposure_layout(uint32_t width, uint32_t height, uint64_t *out3);
+
+/* The per-call rate of an adaptation of `speed` per second over a frame of dt seconds: 1 - exp(-dt * speed) as a float, clamped to [0, 1]
+ * (a NaN: 0).  A pure host function. */
+float arctic_exposure_rate(float dt, float speed);
+
+/* The host arbiters (no handle, no GPU), by the very functions the kernels run.  arctic_exposure_histogram: step 1 of a WHOLE frame -- rgb
+ * (height*width*3 floats) in, H (256 counts) out.  arctic_exposure_resolve: step 2 -- H and the state in front of the call (NULL: invalid) in,
+ * the state behind it out.  arctic_exposure_pixels: step 3's multiply for n pixels -- rgb and out_rgb: n*3 floats.  ARCTIC_E_INVALID
+ * (nothing written): what the call refuses of ArcticExposure (arctic_exposure_resolve takes any window a frame of 16384 x 16384 admits), a
+ * frame size outside 1..16384, a null array that is needed. */
+int arctic_exposure_histogram(const ArcticExposure *exposure, uint32_t width, uint32_t height, const float *rgb, uint32_t *hist256);
+int arctic_exposure_resolve(const ArcticExposure *exposure, const uint32_t *hist256, const ArcticExposureState *previous, ArcticExposureState *state);
+int arctic_exposure_pixels(uint64_t n, const float *rgb, float exposure, float *out_rgb);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row
