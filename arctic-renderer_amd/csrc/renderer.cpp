@@ -135,6 +135,7 @@ int alloc_targets(ArcticRenderer *r) {
     r->dof.valid = false;          // (... and the latest depth of field)
     r->bloom.valid = false;        // (... and the latest bloom)
     r->exposure.valid = r->exposure.planes = false;   // (... and the exposure's adaptation and planes)
+    r->fog.valid = false;          // (... and the latest fog)
     r->output_filtered = false;
     return ARCTIC_OK;
 }

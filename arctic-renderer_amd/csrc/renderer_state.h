@@ -500,6 +500,22 @@ struct ArcticRenderer {
         uint64_t launches = 0, calls = 0, meters = 0;
         size_t device_bytes() const { return d_partials.cap + d_hist.cap + d_state.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap; }
     } exposure;
+    // Volumetric fog (arctic_fog_device; fog.hip, owned by fog_calls.cpp): d_hdr is the fogged colour when the caller passes no HDR plane of its
+    // own, d_rgba8 and d_ldr its tonemapped planes; d_color, d_depth: the host form's planes, d_depth also arctic_pass_fog's; d_offsets: the 16
+    // offsets, which travel through offsets_ring, whose one pinned slot keeps the table last sent (have_offsets: it holds one).  `written`:
+    // recorded behind every call, waited for by the next one if the handle's stream has changed in between.  Nothing is allocated before the
+    // first call that passes its checks; valid: the planes hold a call's result at width x height (cleared by a resize); own_hdr, own_rgba8:
+    // that call wrote d_hdr / d_rgba8, not the caller's planes
+    struct Fog {
+        DevBuf d_hdr, d_rgba8, d_ldr, d_color, d_depth, d_offsets;
+        UploadRing<1> offsets_ring;
+        bool have_offsets = false;
+        bool valid = false, own_hdr = false, own_rgba8 = false;
+        uint32_t width = 0, height = 0;
+        StreamMark written;
+        uint64_t launches = 0, calls = 0, uploads = 0;
+        size_t device_bytes() const { return d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_depth.cap + d_offsets.cap; }
+    } fog;
     PinnedBuf counts;             // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts

@@ -546,6 +546,34 @@ class Renderer {
     }
     [[nodiscard]] static bool exposure_pixels(uint64_t n, const float *rgb, float exposure, float *out_rgb) { return arctic_exposure_pixels(n, rgb, exposure, out_rgb) == ARCTIC_OK; }
 
+    // volumetric fog (include/arctic_hip.h: arctic_fog_device and the definition in front of it).  The march on device planes (nullptr: the
+    // handle's HDR plane per fog.flags, every depth 1.0, the handle's own outputs; offsets16: 16 floats in host memory or nullptr); stream-ordered
+    [[nodiscard]] bool fog_device(const ArcticSettings &settings, const ArcticFog &fog, const ArcticFogView &view, const float *offsets16, const float *d_hdr_rgb32f,
+                                  const float *d_depth, float *d_out_hdr_rgb32f, uint8_t *d_out_rgba8) {
+        return ok(arctic_fog_device(m_handle, &settings, &fog, &view, offsets16, d_hdr_rgb32f, d_depth, d_out_hdr_rgb32f, d_out_rgba8));
+    }
+    // the same from and to host memory; synchronous
+    [[nodiscard]] bool fog(const ArcticSettings &settings, const ArcticFog &fog, const ArcticFogView &view, const float *offsets16, const float *hdr_rgb32f, const float *depth,
+                           float *out_hdr_rgb32f, uint8_t *out_rgba8) {
+        return ok(arctic_fog(m_handle, &settings, &fog, &view, offsets16, hdr_rgb32f, depth, out_hdr_rgb32f, out_rgba8));
+    }
+    // the scene's view record, the depth plane, then the march of the handle's planes
+    [[nodiscard]] bool pass_fog(const ArcticScene &scene, const ArcticSettings &settings, const ArcticFog &fog, const float *offsets16, uint8_t *d_out_rgba8) {
+        return ok(arctic_pass_fog(m_handle, &scene, &settings, &fog, offsets16, d_out_rgba8));
+    }
+    // what the latest call left, row-major; any pointer may be nullptr
+    [[nodiscard]] bool read_fog(float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8) { return ok(arctic_read_fog(m_handle, ldr_rgb, hdr_rgb, rgba8)); }
+    // {device bytes, launches of k_fog_march, calls, uploads of the offset table}
+    [[nodiscard]] bool fog_info(uint64_t out4[4]) { return ok(arctic_fog_info(m_handle, out4)); }
+    // the view record of a scene and the host arbiter: no handle, no GPU
+    [[nodiscard]] static bool fog_view(const ArcticScene &scene, uint32_t width, uint32_t height, ArcticFogView *out) { return arctic_fog_view(&scene, width, height, out) == ARCTIC_OK; }
+    [[nodiscard]] static bool fog_pixels(const ArcticFog &fog, const ArcticFogView &view, const float *offsets16, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height,
+                                         const float *rgb, const float *depth, const float *shadow, uint32_t S, float *out_rgb, float *terms2) {
+        return arctic_fog_pixels(&fog, &view, offsets16, n, pixel_xy, width, height, rgb, depth, shadow, S, out_rgb, terms2) == ARCTIC_OK;
+    }
+    [[nodiscard]] static float fog_exp2(float x) { return arctic_fog_exp2(x); }
+    [[nodiscard]] static bool fog_exp2_poly(uint64_t n, const float *f, float *p) { return arctic_fog_exp2_poly(n, f, p) == ARCTIC_OK; }
+
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }
 

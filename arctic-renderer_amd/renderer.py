@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, MOTION_BLUR_DTYPE, DOF_DTYPE, BLOOM_DTYPE, EXPOSURE_DTYPE, EXPOSURE_STATE_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, MOTION_BLUR_DTYPE, DOF_DTYPE, BLOOM_DTYPE, EXPOSURE_DTYPE, EXPOSURE_STATE_DTYPE, FOG_DTYPE, FOG_VIEW_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -726,6 +726,60 @@ class Renderer:
         """(device bytes, launches of k_exposure_apply, calls, launches of k_exposure_meter): all 0 until the first call"""
         out = np.zeros(4, np.uint64)
         self._check(self.L.arctic_exposure_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    # ---- volumetric fog (include/arctic_hip.h: arctic_fog_device and the definition in front of it) -------------------------------------------------
+    def fog_device(self, settings, view, d_hdr_ptr=None, d_depth_ptr=None, d_out_hdr_ptr=None, d_out_ptr=None, offsets=None, fog=None, **kw):
+        """march a device HDR plane (an int pointer: rows * width * 3 floats; None: the handle's own -- the latest shading's, under
+        FOG_SOURCE_COMPOSED the composition's) through the fog under `view` (a FOG_VIEW_DTYPE record: fog_view()), from d_depth_ptr (rows * width
+        floats; None: every depth 1.0) and the handle's current sun map, then tonemap.  The result stays on the device -- d_out_hdr_ptr (rows *
+        width * 3 floats) and d_out_ptr (rows * width * 4 bytes), or the handle's own buffers: read_fog().  offsets: 16 floats in [0, 1) or None
+        (all 0.5); fog: a FOG_DTYPE record instead of the parameters of fog_arguments().  Asynchronous on the handle's stream."""
+        st = self._settings(settings)
+        m = fog_arguments(**kw) if fog is None else fog
+        t = _fog_offsets(offsets)
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_fog_device(self.h, C.byref(st), _ptr(m), _ptr(view), _ptr(t), vp(d_hdr_ptr), vp(d_depth_ptr), vp(d_out_hdr_ptr), vp(d_out_ptr)))
+
+    def fog(self, settings, view, hdr=None, depth=None, offsets=None, fog=None, read=True, **kw):
+        """the same from and to host memory: hdr (rows, width, 3) float32 or None, depth (rows, width) float32 or None -> (hdr (rows, width, 3)
+        float32, rgba8 (rows, width, 4) uint8) (read=False: None, the result stays in the handle's buffers); synchronous"""
+        st = self._settings(settings)
+        m = fog_arguments(**kw) if fog is None else fog
+        t = _fog_offsets(offsets)
+        c = None if hdr is None else np.ascontiguousarray(hdr, dtype=np.float32)
+        z = None if depth is None else np.ascontiguousarray(depth, dtype=np.float32)
+        n = (self.rows, self.width)
+        if (c is not None and c.shape != n + (3,)) or (z is not None and z.shape != n):
+            raise ArcticError(-1, f"fog: expected {n + (3,)} and {n}")
+        out_hdr = np.empty(n + (3,), np.float32) if read else None
+        out = np.empty(n + (4,), np.uint8) if read else None
+        self._check(self.L.arctic_fog(self.h, C.byref(st), _ptr(m), _ptr(view), _ptr(t), _ptr(c), _ptr(z), _ptr(out_hdr), _ptr(out)))
+        return (out_hdr, out) if read else None
+
+    def pass_fog(self, desc, settings, d_out_ptr=None, offsets=None, fog=None, read=True, **kw):
+        """the one call: fog_view of the scene, the depth into a plane the handle owns, then the march of the handle's HDR plane per flags:
+        (rows, width, 4) uint8.  read=False or a d_out_ptr leaves the result on the device and returns None."""
+        s, st = self._scene(desc), self._settings(settings)
+        m = fog_arguments(**kw) if fog is None else fog
+        t = _fog_offsets(offsets)
+        self._check(self.L.arctic_pass_fog(self.h, C.byref(s), C.byref(st), _ptr(m), _ptr(t), C.c_void_p(d_out_ptr) if d_out_ptr else None))
+        return self.read_fog(want=("rgba8",))[2] if read and not d_out_ptr else None
+
+    def read_fog(self, want=("ldr", "hdr", "rgba8")):
+        """what the latest fog call left, row-major: (ldr (rows, width, 3), hdr (rows, width, 3) float32, rgba8 (rows, width, 4) uint8); None for
+        what was not asked for"""
+        n = (self.rows, self.width)
+        ldr = np.empty(n + (3,), np.float32) if "ldr" in want else None
+        hdr = np.empty(n + (3,), np.float32) if "hdr" in want else None
+        rgba = np.empty(n + (4,), np.uint8) if "rgba8" in want else None
+        self._check(self.L.arctic_read_fog(self.h, _ptr(ldr), _ptr(hdr), _ptr(rgba)))
+        return ldr, hdr, rgba
+
+    def fog_info(self):
+        """(device bytes, launches of k_fog_march, calls, uploads of the offset table): all 0 until the first call"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_fog_info(self.h, _ptr(out)))
         return tuple(int(x) for x in out)
 
     def ray_scene_info(self):
@@ -1538,6 +1592,80 @@ def exposure_pixels(rgb, e):
     rc = binding.lib().arctic_exposure_pixels(n, _ptr(c) if n else None, float(e), _ptr(out) if n else None)
     if rc < 0:
         raise ArcticError(rc, "exposure_pixels")
+    return out
+
+
+def fog_arguments(flags=0, density=0.05, anisotropy=0.5, max_distance=100.0, steps=32, bias=0.002, scatter_color=(1.0, 1.0, 1.0), ambient_color=(0.0, 0.0, 0.0)):
+    """one FOG_DTYPE record; scatter_color is the single-scattering albedo times the sun's radiance; the library checks every value"""
+    m = np.zeros(1, FOG_DTYPE)
+    m["flags"], m["density"], m["anisotropy"], m["max_distance"], m["steps"], m["bias"] = flags, density, anisotropy, max_distance, steps, bias
+    m["scatter_color"][0], m["ambient_color"][0] = scatter_color, ambient_color
+    return m
+
+
+def _fog_offsets(offsets):
+    """the offset table of a call: None (every entry 0.5) or 16 contiguous float32"""
+    if offsets is None:
+        return None
+    t = np.ascontiguousarray(offsets, dtype=np.float32).ravel()
+    if t.size != 16:
+        raise ArcticError(-1, "fog: offsets is 16 floats")
+    return t
+
+
+def fog_offsets(seed=0):
+    """an offset table for the fog: the 16 strata (i + 0.5) / 16 in an order shuffled by `seed`, so that the 4 x 4 pixels of a block start their
+    march at 16 different depths.  A convenience: the library takes any table in [0, 1)."""
+    return ((np.random.default_rng(seed).permutation(16) + 0.5) / 16.0).astype(np.float32)
+
+
+def fog_view(desc, width, height):
+    """arctic_fog_view: the FOG_VIEW_DTYPE record of a scene's camera and sun for a width x height frame"""
+    s = desc.fill(CScene())
+    out = np.zeros(1, FOG_VIEW_DTYPE)
+    rc = binding.lib().arctic_fog_view(C.byref(s), int(width), int(height), _ptr(out))
+    if rc < 0:
+        raise ArcticError(rc, "fog_view")
+    return out
+
+
+def fog_pixels(pixel_xy, rgb, view, depth=None, shadow=None, offsets=None, fog=None, terms=False, **kw):
+    """arctic_fog_pixels: the fog on the host, for n pixels in any order -- pixel_xy (n, 2) int32, rgb the WHOLE frame's colour (height, width,
+    3), view a FOG_VIEW_DTYPE record, depth (height, width) or None, shadow (S, S) or None.  Returns (n, 3) float32, with terms=True also
+    (n, 2) {T, I}."""
+    xy = np.ascontiguousarray(pixel_xy, dtype=np.int32).reshape(-1, 2)
+    c = np.ascontiguousarray(rgb, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ArcticError(-1, "fog_pixels: rgb is the whole frame, (height, width, 3)")
+    height, width = c.shape[:2]
+    z = None if depth is None else np.ascontiguousarray(depth, dtype=np.float32)
+    sm = None if shadow is None else np.ascontiguousarray(shadow, dtype=np.float32)
+    if (z is not None and z.shape != (height, width)) or (sm is not None and (sm.ndim != 2 or sm.shape[0] != sm.shape[1])):
+        raise ArcticError(-1, "fog_pixels: depth is (height, width), shadow (S, S)")
+    m = fog_arguments(**kw) if fog is None else fog
+    t = _fog_offsets(offsets)
+    n = len(xy)
+    out = np.empty((n, 3), np.float32)
+    tm = np.empty((n, 2), np.float32) if terms else None
+    rc = binding.lib().arctic_fog_pixels(_ptr(m), _ptr(view), _ptr(t), n, _ptr(xy) if n else None, int(width), int(height), _ptr(c), _ptr(z), _ptr(sm),
+                                         0 if sm is None else int(sm.shape[0]), _ptr(out) if n else None, _ptr(tm) if terms and n else None)
+    if rc < 0:
+        raise ArcticError(rc, "fog_pixels")
+    return (out, tm) if terms else out
+
+
+def fog_exp2(x):
+    """arctic_fog_exp2: the fog's 2^x for x <= 0, as the kernel evaluates it"""
+    return float(binding.lib().arctic_fog_exp2(float(x)))
+
+
+def fog_exp2_poly(f):
+    """arctic_fog_exp2_poly: the polynomial of fog_exp2 for an array of f in [0, 1]"""
+    a = np.ascontiguousarray(f, dtype=np.float32).ravel()
+    out = np.empty_like(a)
+    rc = binding.lib().arctic_fog_exp2_poly(len(a), _ptr(a) if len(a) else None, _ptr(out) if len(a) else None)
+    if rc < 0:
+        raise ArcticError(rc, "fog_exp2_poly")
     return out
 
 

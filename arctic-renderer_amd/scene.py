@@ -64,6 +64,13 @@ EXPOSURE_DTYPE = np.dtype([("flags", "<u4"), ("low_q16", "<u4"), ("high_q16", "<
 assert EXPOSURE_DTYPE.itemsize == 56
 EXPOSURE_STATE_DTYPE = np.dtype([("adapted_key", "<f8"), ("exposure", "<f4"), ("luminance", "<f4"), ("metered", "<u4"), ("valid", "<u4"), ("frames", "<u4"), ("reserved", "<u4")])
 assert EXPOSURE_STATE_DTYPE.itemsize == 32
+# ArcticFog: the parameters of volumetric fog (arctic_fog_device), and ArcticFogView: the camera's rays and the sun's map per frame (arctic_fog_view)
+FOG_DTYPE = np.dtype([("flags", "<u4"), ("density", "<f4"), ("anisotropy", "<f4"), ("max_distance", "<f4"), ("steps", "<u4"), ("bias", "<f4"), ("scatter_color", "<f4", 3),
+                      ("ambient_color", "<f4", 3), ("reserved", "<u4")])
+assert FOG_DTYPE.itemsize == 52
+FOG_VIEW_DTYPE = np.dtype([("eye", "<f4", 3), ("z_near", "<f4"), ("ray00", "<f4", 3), ("z_far", "<f4"), ("ray_dx", "<f4", 3), ("pad0", "<f4"), ("ray_dy", "<f4", 3), ("pad1", "<f4"),
+                           ("sun_dir", "<f4", 3), ("pad2", "<f4"), ("light", "<f4", (3, 4))])
+assert FOG_VIEW_DTYPE.itemsize == 128
 # ArcticRayNode / ArcticRayTri: the ray structure's records as arctic_read_ray_structure and arctic_refit_triangles return them
 RAY_NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("skip", "<u4"), ("bmax", "<f4", 3), ("leaf", "<u4")])
 RAY_TRI_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("p2", "<f4", 3), ("prim", "<u4"), ("pad", "<u4", 2)])

@@ -1906,6 +1906,120 @@ int arctic_exposure_histogram(const ArcticExposure *exposure, uint32_t width, ui
 int arctic_exposure_resolve(const ArcticExposure *exposure, const uint32_t *hist256, const ArcticExposureState *previous, ArcticExposureState *state);
 int arctic_exposure_pixels(uint64_t n, const float *rgb, float exposure, float *out_rgb);
 
+/* ---- Volumetric fog: sun shafts marched through the sun's shadow map (no counterpart in the reference) ------------------------------------------
+ * The first stage behind the shading or the composition and in front of the anti-aliasing: a homogeneous participating medium lit by the sun.
+ * Every pixel's view ray is marched from the eye to its surface in `steps` samples; each sample asks the sun's shadow map whether it is lit.
+ * The stages behind it have no flag for it: the calls take an optional caller-owned HDR output plane, and that plane is chained into
+ * arctic_taa_resolve_device, arctic_motion_blur_device and the rest through their explicit colour argument.
+ *
+ * THE DEFINITION.  Bit for bit: fp32, one rounding per operation in the written order, no contraction (no fma), IEEE division and square root,
+ * no library transcendental.  min(a, b) is b < a ? b : a.
+ * INPUTS.  C: the float HDR colour, row-major, 3 floats per pixel.  depth: the prepass depth plane (arctic_depth_plane_device), one float per
+ *   pixel; a NULL plane means every depth is 1.0.  The sun's map: S x S floats, row-major; S = 0 means no map, and every sample is lit.
+ *   offsets16: a caller's HOST table of 16 floats in [0, 1), interleaved over 4 x 4 pixels: pixel (px, py) uses entry (py & 3) * 4 + (px & 3);
+ *   NULL means every entry is 0.5.  The two records below; N = steps, g = anisotropy.
+ * 1. RAY.  fx = px + 0.5, fy = py + 0.5.  Per component D = (ray00 + fx * ray_dx) + fy * ray_dy.  len = sqrt((D.x*D.x + D.y*D.y) + D.z*D.z).
+ *   zv = the depth of field's view distance of `depth` under z_near and z_far: den = z_far - depth * (z_far - z_near), zv = den > 0 ?
+ *   (z_near * z_far) / den : z_far, so a NaN depth gives z_far.  z_end = min(zv, max_distance).  dz = z_end / (float)N.
+ * 2. EXTINCTION.  x = -((density * 1.442695f) * len) * dz.  a = fog_exp2(x).  T_0 = 1, and T_{k+1} = T_k * a.
+ *   fog_exp2(x) for x <= 0: x = x > -126 ? x : -126 (a NaN becomes -126); n = floor(x); f = x - n, which lies in [0, 1], and 1 is reached
+ *   after rounding; p = Horner from the top with separate multiply and add, ((((((c6 * f + c5) * f + c4) * f + c3) * f + c2) * f + c1) * f + c0,
+ *   c0..c6 = 0x1p+0, 0x1.62e428p-1, 0x1.ebfdf2p-3, 0x1.c67f5p-5, 0x1.3d54d8p-7, 0x1.44d4d2p-10, 0x1.ca8f0ap-13;
+ *   r = float_from_bits(bits(p) + (n << 23)) in two's complement; a = min(r, 1.0f).  Over every float f of [0, 1] p differs from 2^f by at most
+ *   8.4e-8 relative and lies in [1, 2]; the test holds 1.2e-7 and 1 <= p < 4, which the bit addition needs (tests/test_fog_reference.py).
+ * 3. MARCH, for k = 0 .. N-1.  z = ((float)k + offset) * dz.  Per component P = eye + D * z.
+ *   u = ((light[0][0]*P.x + light[0][1]*P.y) + light[0][2]*P.z) + light[0][3]; v and w likewise from rows 1 and 2.
+ *   tu = floor(u * (float)S), tv = floor(v * (float)S).  The sample is inside when tu >= 0 && tu <= S-1 && tv >= 0 && tv <= S-1 && !(w > 1.0f);
+ *   a NaN fails, and nothing is read.  Inside: V_k = (w - bias > map[tv][tu]) ? 0 : 1.  Outside, or with S = 0: V_k = 1.
+ *   I = I + V_k * (T_k - T_{k+1}), as a select on V_k, in order of k from I = 0.
+ * 4. PHASE AND OUTPUT.  cos_t = -((D.x*sun_dir.x + D.y*sun_dir.y) + D.z*sun_dir.z) / len.  q = (1 + g*g) - (2*g) * cos_t.
+ *   ph = ((1 - g*g) * 0.07957747f) / (q * sqrt(q)) (Henyey-Greenstein).  T = T_N.  If !(T < 1.0f): out = C by bits -- zero density, zero
+ *   length and a NaN T.  Otherwise per channel out = (C * T + (scatter_color * ph) * I) + ambient_color * (1 - T).
+ *   Then the tonemapper of `out` exactly as k_dof_gather carries it out: float HDR, float LDR and RGBA8.
+ * EXACT PROPERTIES.  a <= 1, so the T_k never rise and every term of I is >= 0.  0 <= I <= 1 - T up to the sum's rounding.  Density 0 returns
+ *   C by bits, NaN and -0 included (for a finite len).  A NaN in C stays in its own pixel: the stage reads no neighbour.  No lookup is made
+ *   outside the map for any light rows or any view record.
+ * KNOWN LIMITS, stated and not worked around.  Homogeneous medium.  Single scattering from the sun only: point, spot and cube-shadow lights do
+ *   not light the fog.  One nearest-texel compare per sample.  The ray ignores the anti-aliasing's sub-pixel jitter.  Whole frames only: a
+ *   shard is refused with ARCTIC_E_STATE.  ARCTIC_OPT_HDR16 is refused (ARCTIC_E_STATE) when the colour is the handle's.
+ * REFUSALS, all ARCTIC_E_INVALID, in this order, and every refusal comes before anything is enqueued: a null argument; unknown flag bits; a
+ *   field out of range or NaN; reserved != 0 or a pad that is not 0; a view record that is not finite or has z_near >= z_far (or z_near <= 0);
+ *   an offset outside [0, 1); a misaligned plane.  Then ARCTIC_E_STATE: a shard; with a NULL colour no float HDR plane of this size (or none
+ *   composed under the flag); a sun map (shadow_size != 0) that is sharded or was never drawn or written, the rule of arctic_shade_hits.  A
+ *   refused call writes nothing and leaves the counters and buffers as they were. */
+#define ARCTIC_FOG_SOURCE_COMPOSED 1u                /* a NULL colour = the composition's HDR plane, not the shading's */
+typedef struct ArcticFog {                       /* 52 bytes */
+    uint32_t flags;
+    float density;                               /* [0, 64]: sigma, the extinction per world unit */
+    float anisotropy;                            /* [-0.95, 0.95]: g of the phase function; above 0 scatters forward */
+    float max_distance;                          /* (0, 65504]: the march ends here, in view distance */
+    uint32_t steps;                              /* 1..128: N */
+    float bias;                                  /* [0, 1]: in shadow-map depth */
+    float scatter_color[3];                      /* [0, 65504]: the single-scattering albedo times the sun's radiance; the caller sets it */
+    float ambient_color[3];                      /* [0, 65504]: what the medium emits or in-scatters from the sky */
+    uint32_t reserved;                           /* must be 0 */
+} ArcticFog;
+typedef struct ArcticFogView {                   /* 128 bytes; every field finite, the pads 0, 0 < z_near < z_far */
+    float eye[3];
+    float z_near;
+    float ray00[3];                              /* the ray of the frame's corner (0, 0), at view distance 1 */
+    float z_far;
+    float ray_dx[3];                             /* ... and what a pixel to the right adds */
+    float pad0;
+    float ray_dy[3];                             /* ... and a pixel down */
+    float pad1;
+    float sun_dir[3];                            /* the direction in which the light travels, of length 1 */
+    float pad2;
+    float light[3][4];                           /* three affine rows: a world point to the map's (u, v, depth) */
+} ArcticFogView;
+
+/* The view record of a scene's camera and sun for a width x height frame -- a pure host function, no handle.  The formulas are those of the
+ * camera's and the sun's matrices (perspectiveRH_ZO * lookAtRH, orthoRH_ZO(-16, 16, -16, 16, 0.1, 50) * lookAtRH) on the fp32 direction the
+ * library derives from the rotations, evaluated in binary64 and rounded once to fp32.  D at view distance 1 is f + x_ndc * aspect *
+ * tan(fov_y / 2) * s + y_ndc * tan(fov_y / 2) * u with x_ndc = 2 fx / width - 1 and y_ndc = 1 - 2 fy / height, which falls as py rises.
+ * light row 0 is 0.5 * clip_x + 0.5, row 1 is 0.5 - 0.5 * clip_y, row 2 is clip_z.  ARCTIC_E_INVALID (nothing written): a null pointer, a
+ * frame size outside 1..16384, a scene whose record is not finite or has not 0 < z_near < z_far. */
+int arctic_fog_view(const ArcticScene *scene, uint32_t width, uint32_t height, ArcticFogView *out);
+
+/* One call of the definition on DEVICE planes of a handle that owns the whole frame: k_fog_march, one launch.  d_hdr_rgb32f: rows*width*3
+ * floats, NULL = the shading's plane (the composition's under ARCTIC_FOG_SOURCE_COMPOSED), which needs ARCTIC_OPT_KEEP_FLOAT_OUTPUT; d_depth:
+ * rows*width floats or NULL; d_out_hdr_rgb32f (rows*width*3 floats) and d_out_rgba8 (rows*width*4 bytes): NULL = the handle's own
+ * (arctic_read_fog).  offsets16 is a HOST pointer; the table is sent again only when it differs from the one last sent.  It reads the
+ * handle's current sun map.  No plane may alias another.  Stream-ordered on the handle's stream; a warm call allocates nothing and does not
+ * synchronise. */
+int arctic_fog_device(ArcticRenderer *r, const ArcticSettings *settings, const ArcticFog *fog, const ArcticFogView *view, const float *offsets16, const float *d_hdr_rgb32f,
+                      const float *d_depth, float *d_out_hdr_rgb32f, uint8_t *d_out_rgba8);
+
+/* The host form: the same kernel from and to host memory (every plane may be NULL, with the meanings above; a NULL output: the result stays in
+ * the handle's buffers).  Synchronous. */
+int arctic_fog(ArcticRenderer *r, const ArcticSettings *settings, const ArcticFog *fog, const ArcticFogView *view, const float *offsets16, const float *hdr_rgb32f,
+               const float *depth, float *out_hdr_rgb32f, uint8_t *out_rgba8);
+
+/* The one call: arctic_fog_view of the scene at the handle's size, then arctic_depth_plane_device into a plane the handle owns, then the march
+ * of the handle's HDR plane per fog->flags into the handle's HDR plane and d_out_rgba8 (NULL: the handle's own).  Its bytes equal the same
+ * calls made by hand.  Also ARCTIC_E_INVALID for a null scene or one that arctic_fog_view refuses, ARCTIC_E_STATE without a visibility plane;
+ * every refusal comes before anything is enqueued. */
+int arctic_pass_fog(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticFog *fog, const float *offsets16, uint8_t *d_out_rgba8);
+
+/* What the latest call left: float LDR and `out` (rows*width*3 floats each) and RGBA8, the latter two when that call wrote the handle's own.
+ * Any pointer may be NULL.  Synchronises.  ARCTIC_E_STATE: no fog since the handle was created or the last resize; hdr_rgb or rgba8 when the
+ * latest call wrote the caller's plane. */
+int arctic_read_fog(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8);
+
+/* What the calls hold on this handle: out4 = {bytes of device memory, launches of k_fog_march, calls, uploads of the offset table}.  All 0 until
+ * the first call that passes its checks.  Touches no device. */
+int arctic_fog_info(ArcticRenderer *r, uint64_t *out4);
+
+/* The host arbiter (no handle, no GPU), by the very functions the kernel runs: steps 1 to 4 for n pixels in any order.  pixel_xy: n int2; rgb:
+ * the WHOLE frame's colour (height*width*3 floats); depth: height*width floats or NULL; shadow: S*S floats (S = 0: none); out_rgb: n*3 floats;
+ * terms2: NULL or n float2 {T, I}.  ARCTIC_E_INVALID (nothing written): what the calls refuse of the records and the table, a frame size
+ * outside 1..16384 or S above 16384, a pixel outside the frame, a null array that is needed.
+ * arctic_fog_exp2 is step 2's function and arctic_fog_exp2_poly its polynomial p of n values f, for the test that measures them. */
+int arctic_fog_pixels(const ArcticFog *fog, const ArcticFogView *view, const float *offsets16, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height,
+                      const float *rgb, const float *depth, const float *shadow, uint32_t S, float *out_rgb, float *terms2);
+float arctic_fog_exp2(float x);
+int arctic_fog_exp2_poly(uint64_t n, const float *f, float *p);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row
