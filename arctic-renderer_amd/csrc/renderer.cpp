@@ -136,6 +136,7 @@ int alloc_targets(ArcticRenderer *r) {
     r->bloom.valid = false;        // (... and the latest bloom)
     r->exposure.valid = r->exposure.planes = false;   // (... and the exposure's adaptation and planes)
     r->fog.valid = false;          // (... and the latest fog)
+    r->taa_upscale.valid = false;  // (... and the upscaler's U)
     r->output_filtered = false;
     return ARCTIC_OK;
 }

@@ -516,6 +516,22 @@ struct ArcticRenderer {
         uint64_t launches = 0, calls = 0, uploads = 0;
         size_t device_bytes() const { return d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_depth.cap + d_offsets.cap; }
     } fog;
+    // Temporal upscaling (arctic_taa_upscale_device; taa_upscale.hip, owned by taa_upscale_calls.cpp): the state U of include/arctic_hip.h -- two
+    // sets of one float4 plane {r, g, b, N} per OUTPUT pixel, tile-major in 8 x 8 output tiles: a call reads set `cur` and writes the other,
+    // then `cur` moves.  d_rgba8, d_ldr: the tonemapped result at the output size; d_color, d_vel: the host form's input planes, d_vel also
+    // arctic_pass_taa_upscale's (its prev_world4 goes into Motion::d_plane).  `written`: recorded behind every call, waited for by the next one
+    // if the handle's stream has changed in between.  Nothing is allocated before the first call that passes its checks; valid: U is not empty
+    // (cleared by arctic_taa_upscale_reset and by a resize); in_width, in_height, out_width, out_height: those of the call that wrote set
+    // `cur`; own_rgba8: that call wrote d_rgba8, not the caller's buffer.  Apart from T: neither stage touches the other's state
+    struct TaaUpscale {
+        DevBuf d_u[2], d_rgba8, d_ldr, d_color, d_vel;
+        int cur = 0;
+        bool valid = false, own_rgba8 = false;
+        uint32_t in_width = 0, in_height = 0, out_width = 0, out_height = 0;
+        StreamMark written;
+        uint64_t launches = 0, calls = 0;
+        size_t device_bytes() const { return d_u[0].cap + d_u[1].cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_vel.cap; }
+    } taa_upscale;
     PinnedBuf counts;             // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts

@@ -574,6 +574,37 @@ class Renderer {
     [[nodiscard]] static float fog_exp2(float x) { return arctic_fog_exp2(x); }
     [[nodiscard]] static bool fog_exp2_poly(uint64_t n, const float *f, float *p) { return arctic_fog_exp2_poly(n, f, p) == ARCTIC_OK; }
 
+    // temporal upscaling (include/arctic_hip.h: arctic_taa_upscale_device and the definition in front of it).  The handle's jittered frame into a
+    // history of upscale.out_width x out_height on device planes (nullptr: the handle's HDR plane per upscale.flags, zero velocity, the handle's
+    // own output); stream-ordered
+    [[nodiscard]] bool taa_upscale_device(const ArcticSettings &settings, const ArcticTaaUpscale &upscale, const float *d_hdr_rgb32f, const float *d_velocity2, uint8_t *d_out_rgba8) {
+        return ok(arctic_taa_upscale_device(m_handle, &settings, &upscale, d_hdr_rgb32f, d_velocity2, d_out_rgba8));
+    }
+    // the same from and to host memory; synchronous
+    [[nodiscard]] bool taa_upscale(const ArcticSettings &settings, const ArcticTaaUpscale &upscale, const float *hdr_rgb32f, const float *velocity2, uint8_t *out_rgba8) {
+        return ok(arctic_taa_upscale(m_handle, &settings, &upscale, hdr_rgb32f, velocity2, out_rgba8));
+    }
+    // the frame's one motion call into planes the handle owns, then the upscale of the handle's HDR plane
+    [[nodiscard]] bool pass_taa_upscale(const ArcticScene &scene, const ArcticSettings &settings, const ArcticTaaUpscale &upscale, uint8_t *d_out_rgba8) {
+        return ok(arctic_pass_taa_upscale(m_handle, &scene, &settings, &upscale, d_out_rgba8));
+    }
+    // the next call is a first call
+    [[nodiscard]] bool taa_upscale_reset() { return ok(arctic_taa_upscale_reset(m_handle)); }
+    // what the latest call left, row-major at the output size; any pointer may be nullptr
+    [[nodiscard]] bool read_taa_upscale(float *ldr_rgb, float *hdr_rgb, float *count, uint8_t *rgba8) { return ok(arctic_read_taa_upscale(m_handle, ldr_rgb, hdr_rgb, count, rgba8)); }
+    // the accumulated HDR colour as a row-major device plane of the output size: the next stage's explicit colour, on a handle of that size
+    [[nodiscard]] bool taa_upscale_hdr_device(float *d_hdr_rgb32f) { return ok(arctic_taa_upscale_hdr_device(m_handle, d_hdr_rgb32f)); }
+    // {device bytes, launches of k_taa_upscale, calls since the last reset, W | H << 32}
+    [[nodiscard]] bool taa_upscale_info(uint64_t out4[4]) { return ok(arctic_taa_upscale_info(m_handle, out4)); }
+    // the host arbiter and the jitter sequence: no handle, no GPU
+    [[nodiscard]] static bool taa_upscale_pixels(const ArcticTaaUpscale &upscale, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *cur_rgb,
+                                                 const float *velocity2, const float *prev_rgbn, float *out_rgbn) {
+        return arctic_taa_upscale_pixels(&upscale, n, pixel_xy, width, height, cur_rgb, velocity2, prev_rgbn, out_rgbn) == ARCTIC_OK;
+    }
+    [[nodiscard]] static bool taa_upscale_jitter(uint32_t index, uint32_t w, uint32_t W, uint32_t h, uint32_t H, float out2[2]) {
+        return arctic_taa_upscale_jitter(index, w, W, h, H, out2) == ARCTIC_OK;
+    }
+
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }
 

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, MOTION_BLUR_DTYPE, DOF_DTYPE, BLOOM_DTYPE, EXPOSURE_DTYPE, EXPOSURE_STATE_DTYPE, FOG_DTYPE, FOG_VIEW_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, TAA_UPSCALE_DTYPE, MOTION_BLUR_DTYPE, DOF_DTYPE, BLOOM_DTYPE, EXPOSURE_DTYPE, EXPOSURE_STATE_DTYPE, FOG_DTYPE, FOG_VIEW_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -782,6 +782,66 @@ class Renderer:
         self._check(self.L.arctic_fog_info(self.h, _ptr(out)))
         return tuple(int(x) for x in out)
 
+    # ---- temporal upscaling (include/arctic_hip.h: arctic_taa_upscale_device and the definition in front of it) ------------------------------------
+    def taa_upscale_device(self, settings, out_size, d_hdr_ptr=None, d_velocity2_ptr=None, d_out_ptr=None, upscale=None, **kw):
+        """accumulate a device HDR plane of the handle's size (an int pointer: rows * width * 3 floats; None: the handle's own, the latest
+        shading's or -- flags & TAA_UPSCALE_SOURCE_COMPOSED -- the latest composition's) into the handle's history of out_size = (W, H), fetched
+        where d_velocity2_ptr (rows * width float2; None: zero) and this frame's jitter say, then tonemap.  The result stays on the device --
+        d_out_ptr (H * W * 4 bytes) or the handle's own buffers: read_taa_upscale().  upscale: a TAA_UPSCALE_DTYPE record instead of the
+        parameters of taa_upscale_arguments().  Asynchronous on the handle's stream."""
+        st = self._settings(settings)
+        t = taa_upscale_arguments(out_size, **kw) if upscale is None else upscale
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_taa_upscale_device(self.h, C.byref(st), _ptr(t), vp(d_hdr_ptr), vp(d_velocity2_ptr), vp(d_out_ptr)))
+
+    def taa_upscale(self, settings, out_size, hdr=None, velocity2=None, upscale=None, read=True, **kw):
+        """the same from and to host memory: hdr (rows, width, 3) float32 or None, velocity2 (rows, width, 2) float32 or None -> (H, W, 4) uint8
+        (read=False: None, the result stays in the handle's buffers); synchronous"""
+        st = self._settings(settings)
+        t = taa_upscale_arguments(out_size, **kw) if upscale is None else upscale
+        c = None if hdr is None else np.ascontiguousarray(hdr, dtype=np.float32)
+        v = None if velocity2 is None else np.ascontiguousarray(velocity2, dtype=np.float32)
+        if (c is not None and c.shape != (self.rows, self.width, 3)) or (v is not None and v.shape != (self.rows, self.width, 2)):
+            raise ArcticError(-1, f"taa_upscale: expected {(self.rows, self.width, 3)} and {(self.rows, self.width, 2)}")
+        out = np.empty((int(t["out_height"][0]), int(t["out_width"][0]), 4), np.uint8) if read else None
+        self._check(self.L.arctic_taa_upscale(self.h, C.byref(st), _ptr(t), _ptr(c), _ptr(v), _ptr(out)))
+        return out
+
+    def pass_taa_upscale(self, desc, settings, out_size, d_out_ptr=None, upscale=None, read=True, **kw):
+        """the one call: the frame's ONE motion call into planes the handle owns, then the upscale of the handle's HDR plane: (H, W, 4) uint8.
+        read=False or a d_out_ptr leaves the result on the device and returns None."""
+        s, st = self._scene(desc), self._settings(settings)
+        t = taa_upscale_arguments(out_size, **kw) if upscale is None else upscale
+        self._check(self.L.arctic_pass_taa_upscale(self.h, C.byref(s), C.byref(st), _ptr(t), C.c_void_p(d_out_ptr) if d_out_ptr else None))
+        return self.read_taa_upscale(want=("rgba8",))[3] if read and not d_out_ptr else None
+
+    def taa_upscale_reset(self):
+        """empty the upscaler's history: the next call is a first call.  Frees nothing."""
+        self._check(self.L.arctic_taa_upscale_reset(self.h))
+
+    def read_taa_upscale(self, want=("ldr", "hdr", "count", "rgba8")):
+        """what the latest upscale left, row-major at its output size: (ldr (H, W, 3), hdr (H, W, 3), count (H, W) float32, rgba8 (H, W, 4)
+        uint8); None for what was not asked for.  ArcticError (STATE) while the history is empty."""
+        size = self.taa_upscale_info()[3]
+        n = (size >> 32, size & 0xFFFFFFFF)
+        ldr = np.empty(n + (3,), np.float32) if "ldr" in want else None
+        hdr = np.empty(n + (3,), np.float32) if "hdr" in want else None
+        count = np.empty(n, np.float32) if "count" in want else None
+        rgba = np.empty(n + (4,), np.uint8) if "rgba8" in want else None
+        self._check(self.L.arctic_read_taa_upscale(self.h, _ptr(ldr), _ptr(hdr), _ptr(count), _ptr(rgba)))
+        return ldr, hdr, count, rgba
+
+    def taa_upscale_hdr_device(self, d_hdr_ptr):
+        """the accumulated HDR colour of the latest upscale into a device plane (an int pointer: H * W * 3 floats, row-major): the explicit
+        colour argument of bloom_device, exposure_device and the rest on a handle of the output size.  Asynchronous on the handle's stream."""
+        self._check(self.L.arctic_taa_upscale_hdr_device(self.h, C.c_void_p(d_hdr_ptr) if d_hdr_ptr else None))
+
+    def taa_upscale_info(self):
+        """(device bytes, launches of k_taa_upscale, calls since the last reset, W | H << 32 of the history): all 0 until the first call"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_taa_upscale_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
     def ray_scene_info(self):
         """(triangles stored, nodes, builds so far, depth) of the cached acceleration structure"""
         out = np.zeros(4, np.uint64)
@@ -1337,6 +1397,48 @@ def taa_pixels(pixel_xy, cur, velocity2=None, prev=None, jitter=(0.0, 0.0), max_
     rc = binding.lib().arctic_taa_pixels(_ptr(t), n, _ptr(xy) if n else None, int(width), int(height), _ptr(c), _ptr(v) if n else None, _ptr(pv), _ptr(out) if n else None)
     if rc < 0:
         raise ArcticError(rc, "taa_pixels")
+    return out
+
+
+def taa_upscale_arguments(out_size, jitter=(0.0, 0.0), max_history=32.0, min_weight=0.0, sharpness=1.0, confidence_floor=2.0 ** -6, flags=0):
+    """one TAA_UPSCALE_DTYPE record for an output of out_size = (W, H); the library checks every value"""
+    t = np.zeros(1, TAA_UPSCALE_DTYPE)
+    t["flags"], t["max_history"], t["min_weight"], t["jitter"], t["sharpness"], t["confidence_floor"] = flags, max_history, min_weight, jitter, sharpness, confidence_floor
+    t["out_width"], t["out_height"] = int(out_size[0]), int(out_size[1])
+    return t
+
+
+def taa_upscale_pixels(pixel_xy, cur, out_size, velocity2=None, prev=None, upscale=None, **kw):
+    """arctic_taa_upscale_pixels: steps 1 to 6 of the upscaler of include/arctic_hip.h on the host, for n OUTPUT pixels in any order -- pixel_xy
+    (n, 2) int32 inside out_size = (W, H), cur the WHOLE input frame's colour (height, width, 3), velocity2 the whole input frame's (height,
+    width, 2) or None = zero, prev the whole previous {r, g, b, N} (H, W, 4) or None = an empty history.  Returns (n, 4) float32 {out, N}."""
+    xy = np.ascontiguousarray(pixel_xy, dtype=np.int32).reshape(-1, 2)
+    c = np.ascontiguousarray(cur, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ArcticError(-1, "taa_upscale_pixels: cur is the whole input frame, (height, width, 3)")
+    height, width = c.shape[:2]
+    n = len(xy)
+    t = taa_upscale_arguments(out_size, **kw) if upscale is None else upscale
+    v = None if velocity2 is None else np.ascontiguousarray(velocity2, dtype=np.float32)
+    pv = None if prev is None else np.ascontiguousarray(prev, dtype=np.float32)
+    if (v is not None and v.shape != (height, width, 2)) or (pv is not None and pv.shape != (int(t["out_height"][0]), int(t["out_width"][0]), 4)):
+        raise ArcticError(-1, "taa_upscale_pixels: velocity2 is (height, width, 2), and the previous history is (H, W, 4)")
+    out = np.empty((n, 4), np.float32)
+    rc = binding.lib().arctic_taa_upscale_pixels(_ptr(t), n, _ptr(xy) if n else None, int(width), int(height), _ptr(c), _ptr(v), _ptr(pv), _ptr(out) if n else None)
+    if rc < 0:
+        raise ArcticError(rc, "taa_upscale_pixels")
+    return out
+
+
+def taa_upscale_jitter(index, in_size, out_size, exact=False):
+    """arctic_taa_upscale_jitter: the jitter (jx, jy) of frame `index` for an upscale from in_size = (w, h) to out_size = (W, H), as two
+    float32 -- Halton(2, 3) minus one half with period 8 * ceil(W / w) * ceil(H / h), or, exact=True and a ratio of 1, 2 or 4 on both axes,
+    the s * s phases that put every output pixel's centre on a sample once.  For set_camera_jitter and the upscaler's `jitter`."""
+    out = np.zeros(2, np.float32)
+    i = (int(index) & 0x7FFFFFFF) | (binding.TAA_UPSCALE_JITTER_EXACT if exact else 0)
+    rc = binding.lib().arctic_taa_upscale_jitter(i, int(in_size[0]), int(out_size[0]), int(in_size[1]), int(out_size[1]), _ptr(out))
+    if rc < 0:
+        raise ArcticError(rc, "taa_upscale_jitter")
     return out
 
 

@@ -49,6 +49,10 @@ assert AO_HISTORY_DTYPE.itemsize == 32
 # ArcticTaa: the parameters of the temporal anti-aliasing resolve (arctic_taa_resolve_device)
 TAA_DTYPE = np.dtype([("flags", "<u4"), ("max_history", "<f4"), ("min_weight", "<f4"), ("jitter", "<f4", 2), ("reserved", "<u4", 3)])
 assert TAA_DTYPE.itemsize == 32
+# ArcticTaaUpscale: the parameters of the temporal upscaler (arctic_taa_upscale_device)
+TAA_UPSCALE_DTYPE = np.dtype([("flags", "<u4"), ("max_history", "<f4"), ("min_weight", "<f4"), ("jitter", "<f4", 2), ("sharpness", "<f4"), ("confidence_floor", "<f4"),
+                              ("out_width", "<u4"), ("out_height", "<u4"), ("reserved", "<u4", 3)])
+assert TAA_UPSCALE_DTYPE.itemsize == 48
 # ArcticMotionBlur: the parameters of the motion blur (arctic_motion_blur_device)
 MOTION_BLUR_DTYPE = np.dtype([("flags", "<u4"), ("shutter", "<f4"), ("max_radius", "<f4"), ("samples", "<u4"), ("depth_extent", "<f4"), ("reserved", "<u4", 3)])
 assert MOTION_BLUR_DTYPE.itemsize == 32

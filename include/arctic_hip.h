@@ -2020,6 +2020,135 @@ int arctic_fog_pixels(const ArcticFog *fog, const ArcticFogView *view, const flo
 float arctic_fog_exp2(float x);
 int arctic_fog_exp2_poly(uint64_t n, const float *f, float *p);
 
+/* ---- Temporal upscaling: low-resolution jittered frames into a larger history (no counterpart in the reference) ----------------------------------
+ * Every stage behind the shading runs at the handle's frame size, and the ray stages' cost scales with the pixel count.  This stage lets a
+ * caller trace and shade w x h pixels and show W x H: it accumulates the handle's jittered frames into a history of the OUTPUT size, in front
+ * of the tonemapper.  It is the resolve above (arctic_taa_resolve_device) with three differences: the history lives on a larger grid, each
+ * frame's sample carries a confidence that falls with its distance from the output pixel's centre, and the box comes from the input pixels
+ * around the nearest sample.  Nothing in the passes or in the other calls changes: a handle that never makes these calls renders the same
+ * bytes and allocates nothing for them.
+ *
+ * THE UPSCALER: THE DEFINITION.  Bit for bit: fp32 throughout, one rounding per operation in the written order, no contraction, IEEE division.
+ * min(a, b) is (b < a) ? b : a and max(a, b) is (a < b) ? b : a.
+ * SIZES.  The input is the handle's frame, w x h.  The output is W x H = out_width x out_height with w <= W <= 4w, h <= H <= 4h and both in
+ *   1..16384; the two axes may have different ratios.  rx = (float)w / (float)W, ry = (float)h / (float)H.
+ * STATE.  U is one float4 {r, g, b, N} per OUTPUT pixel: the accumulated HDR colour and the confidence it stands for.  There are TWO SETS, and a
+ *   call reads one and writes the other: 32 bytes per output pixel, tile-major like T, allocated by the first call that passes its checks and
+ *   re-allocated when W x H changes.  U is EMPTY before the first call, after arctic_taa_upscale_reset, after arctic_resize and after a change
+ *   of W x H.  U is not T: this stage and the resolve never touch each other's state.
+ * INPUTS.  The handle-size HDR colour plane C (h x w x 3 floats, row-major), exactly as the resolve takes it; optionally the handle-size
+ *   velocity2 (NULL: all zero), in INPUT pixels as arctic_motion_vectors_device writes it; and ArcticTaaUpscale, j being its jitter in INPUT pixels.
+ * PER OUTPUT PIXEL p = (px, py), x written out and y likewise:
+ *   1. THE NEAREST SAMPLE.  ux = (px + 0.5) * rx is the pixel's centre in input pixels.  Input pixel q's centre shows the unjittered position
+ *      (q + 0.5) - j, so the sample nearest to p is qx = clamp(floor(ux + jx), 0, w-1) -- the floor of the ROUNDED sum, clamped in float before
+ *      the conversion.  Its offset in OUTPUT pixels: Dx = (((qx + 0.5) - jx) - ux) / rx.
+ *   2. c = C[q].  The box lo, hi over the 3 x 3 INPUT pixels around q is the resolve's step 1 with q in the place of p: dy then dx from -1 to
+ *      1, clamped at the input frame's edge, lo = (x < lo) ? x : lo and hi = (x > hi) ? x : hi, so a NaN neighbour is ignored.
+ *   3. THE CONFIDENCE of this frame's sample for this pixel: beta = max(0, 1 - sharpness * (Dx*Dx + Dy*Dy)).
+ *   4. U is empty:  out = c, N = max(beta, confidence_floor).  This is also what every rejection below gives.
+ *   5. Otherwise v = velocity2[q], or (0, 0).  hx = ((px + 0.5) + vx / rx) + jx / rx.  From here the resolve's steps 3 to 5 ON THE OUTPUT
+ *      GRID: gx = hx - 0.5; ix = floor(gx); ax = gx - ix; reject unless hx and hy are finite, -1 <= ix <= W-1 and -1 <= iy <= H-1, tested in
+ *      float before any conversion.  Four taps (ix, iy), (ix+1, iy), (ix, iy+1), (ix+1, iy+1) of U with the weights (1-ax)(1-ay), ax(1-ay),
+ *      (1-ax)ay, ax*ay; a tap is accepted iff it lies inside the OUTPUT frame and its stored N_q > 0; a rejected tap is a SELECT: its weight is
+ *      0 and its history is not looked at.  S = ((k0 + k1) + k2) + k3; R, G, B and Cn the same ordered sums of k*r_q, k*g_q, k*b_q, k*N_q.
+ *      If !(S > min_weight): reject.  h = {R, G, B} / S and hn = Cn / S, then, unless ARCTIC_TAA_UPSCALE_NO_CLAMP, per channel
+ *      h = (h < lo) ? lo : h, then h = (h > hi) ? hi : h.  (NO_CLAMP is meant for still scenes and ground-truth accumulation.)
+ *   6. N = min(hn + beta, max_history); a = beta / N.
+ *      beta == 0 is a SELECT: out = h -- a NaN in c does not enter a pixel that this frame does not sample.
+ *      Otherwise, if hn + beta == beta (the history's confidence vanishes beside the sample's, which only a history that has seen nothing
+ *      but confidence_floor does): a SELECT too, out = c.  At ratio 1 it never fires: every stored N is 1 or more there.
+ *      Otherwise the resolve's step 6 with this a.  Without ARCTIC_TAA_UPSCALE_LUMA_WEIGHT: out = h + (c - h) * a.  With it:
+ *      wc = 1 / (1 + max(max(max(c.r, c.g), c.b), 0)), wh the same of h; kc = a * wc; kh = (1 - a) * wh; out = (c*kc + h*kh) / (kc + kh).
+ *   7. Store {out, N}.  Then post_process of `out` under `settings`, as k_taa_resolve carries it out: float LDR and RGBA8, row-major at W x H.
+ *   {out, N} is defined bit for bit; the tonemapped planes are held to the project's standing bar (1e-4 of the float64 post_process).
+ * WHAT FOLLOWS, each a test.
+ *   P1.  With W = w, H = h, sharpness = 0, |j| < 0.5 and no NO_CLAMP, {out, N} is the resolve's (arctic_taa_pixels) by bytes: rx = 1, q = p,
+ *     beta = 1, and v / 1 and j / 1 are v and j.  (floor(ux + jx) is px as long as the sum does not round up to px + 1: |j| <= 0.499 does at
+ *     every frame size.)
+ *   P2.  With U empty every output pixel is C[q], the nearest sample; no output byte is left unwritten for any size pair.
+ *   P3.  A still scene (velocity2 = -j), a power-of-two integer ratio s, NO_CLAMP, sharpness >= 1, confidence_floor <= 2^-25 and the s*s
+ *     jitters of arctic_taa_upscale_jitter's exact sequence: every D is a whole number of output pixels, so beta is 1 where the sample lies
+ *     on the pixel's centre and 0 elsewhere; hx is px + 0.5 exactly.  After s*s frames `out` is, for every output pixel, the colour sampled
+ *     at its own centre, by bits -- the frame point-sampled at W x H -- and after k*s*s frames it still is, with N = min(k, max_history).
+ *   P4.  A NaN, infinite or far-out-of-frame velocity rejects that pixel alone.  A NaN in C[q'] enters, through c, only the pixels whose q is
+ *     q' (the box ignores it); what a history that holds a NaN does is the resolve's: a tap's weight times it.  Nothing is read outside a
+ *     plane for any record that passes the checks.
+ * KNOWN LIMITS, stated and not worked around.  The motion blur and the depth of field read the low-resolution handle's depth and velocity, so
+ *   they run IN FRONT of the upscaler, on its input.  There is no LOD bias for ARCTIC_OPT_TEXTURE_MIPS at the reduced size.  The sky is not
+ *   reprojected under camera rotation (the resolve's limit).  A shard cannot upscale.
+ * Refusals, in this order; every refusal comes before anything is enqueued, and a refused call writes nothing and leaves U as it was.
+ *   ARCTIC_E_INVALID: a null handle, settings or ArcticTaaUpscale; unknown flag bits; a field outside the ranges below, or a NaN; reserved
+ *     words that are not 0; an output size outside 1..16384, below the handle's or above four times it; a device plane that is misaligned:
+ *     4 bytes for C and RGBA8, 8 bytes for velocity2.
+ *   ARCTIC_E_STATE: a handle that does not own the whole frame; and, with a NULL colour plane, the resolve's four conditions:
+ *     ARCTIC_OPT_KEEP_FLOAT_OUTPUT off; no shading since it was turned on or since the last resize; under ARCTIC_TAA_UPSCALE_SOURCE_COMPOSED
+ *     no composition since the last resize; ARCTIC_OPT_HDR16 = 1. */
+#define ARCTIC_TAA_UPSCALE_LUMA_WEIGHT      1u
+#define ARCTIC_TAA_UPSCALE_SOURCE_COMPOSED  2u   /* C = the latest composition's HDR plane instead of the latest shading's */
+#define ARCTIC_TAA_UPSCALE_NO_CLAMP         4u   /* step 5 without the clamp to the box */
+typedef struct ArcticTaaUpscale {        /* 48 bytes */
+    uint32_t flags;
+    float max_history;                   /* 1..65536, finite */
+    float min_weight;                    /* [0, 1) */
+    float jitter[2];                     /* THIS frame's jitter, INPUT pixels, finite, |j| <= 1 */
+    float sharpness;                     /* [0, 65536]; 0: every frame counts fully for every pixel */
+    float confidence_floor;              /* (0, 1]: the N of a pixel that only a distant sample has reached */
+    uint32_t out_width;                  /* W */
+    uint32_t out_height;                 /* H */
+    uint32_t reserved[3];                /* 0 */
+} ArcticTaaUpscale;
+
+/* One call of the definition on DEVICE planes of a handle that owns the whole frame: k_taa_upscale, one launch.  d_hdr_rgb32f: h*w*3 floats,
+ * NULL = the handle's own plane (the latest shading's, or under ARCTIC_TAA_UPSCALE_SOURCE_COMPOSED the latest composition's); d_velocity2:
+ * h*w float2, NULL = zero; d_out_rgba8: H*W*4 bytes, NULL = the handle's own buffer (arctic_read_taa_upscale).  No plane may alias another.
+ * Stream-ordered on the handle's stream; a warm call allocates nothing and does not synchronise. */
+int arctic_taa_upscale_device(ArcticRenderer *r, const ArcticSettings *settings, const ArcticTaaUpscale *upscale, const float *d_hdr_rgb32f, const float *d_velocity2,
+                              uint8_t *d_out_rgba8);
+
+/* The host form: the same kernel from and to host memory (any pointer but settings and upscale may be NULL, with the meanings above; a NULL
+ * output: the result stays in the handle's buffers).  Synchronous. */
+int arctic_taa_upscale(ArcticRenderer *r, const ArcticSettings *settings, const ArcticTaaUpscale *upscale, const float *hdr_rgb32f, const float *velocity2, uint8_t *out_rgba8);
+
+/* The one call: arctic_motion_vectors_device into planes the handle owns, then the upscale of the handle's HDR plane with that velocity2.  Byte
+ * for byte the two calls made by hand.  It is the frame's ONE motion call.  Every refusal of both calls comes before anything is enqueued. */
+int arctic_pass_taa_upscale(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticTaaUpscale *upscale, uint8_t *d_out_rgba8);
+
+/* Empties U (the next call is a first call) and sets the calls counter to 0.  Frees nothing, touches no device. */
+int arctic_taa_upscale_reset(ArcticRenderer *r);
+
+/* What the latest call left, row-major at W x H whatever the layout on the device: float LDR and the accumulated HDR colour (H*W*3 floats
+ * each), N (H*W floats) and the handle's own RGBA8 (H*W*4 bytes).  Any pointer may be NULL.  Synchronises.  ARCTIC_E_STATE while U is empty,
+ * and for rgba8 when the latest call wrote the caller's buffer. */
+int arctic_read_taa_upscale(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, float *count, uint8_t *rgba8);
+
+/* The accumulated HDR colour of the latest call as a DEVICE plane of the output size, row-major, H*W*3 floats (4-byte aligned): what the stages
+ * behind the upscaler take as their explicit colour argument -- arctic_bloom_device, arctic_exposure_device and the rest on a handle of the
+ * OUTPUT size.  One small launch (k_taa_upscale_hdr), stream-ordered on the handle's stream, allocates nothing.  ARCTIC_E_INVALID: a null or
+ * misaligned plane.  ARCTIC_E_STATE while U is empty.  It does not count as a call or a launch of arctic_taa_upscale_info. */
+int arctic_taa_upscale_hdr_device(ArcticRenderer *r, float *d_hdr_rgb32f);
+
+/* What the calls hold on this handle: out4 = {bytes of device memory, launches of k_taa_upscale, calls since the last reset, W | H << 32 of the
+ * history (0 before the first call)}.  All 0 until the first call that passes its checks.  Touches no device. */
+int arctic_taa_upscale_info(ArcticRenderer *r, uint64_t *out4);
+
+/* The host arbiter (no handle, no GPU): steps 1 to 6 for n OUTPUT pixels in any order, by the very function the kernel runs.  pixel_xy:
+ * (px, py) per pixel, inside the output frame; width, height: the INPUT frame; cur_rgb: the whole input frame's C (height*width*3 floats);
+ * velocity2: the whole input frame's (height*width*2 floats) or NULL = zero; prev_rgbn: the whole previous U (H*W*4 floats, row-major) or NULL
+ * = U is empty; out_rgbn: n*4 floats {out, N}.  ARCTIC_E_INVALID (nothing written): what the calls refuse of ArcticTaaUpscale and of the
+ * sizes, a pixel outside the output frame, a null array that is needed. */
+int arctic_taa_upscale_pixels(const ArcticTaaUpscale *upscale, uint64_t n, const int32_t *pixel_xy, uint32_t width, uint32_t height, const float *cur_rgb,
+                              const float *velocity2, const float *prev_rgbn, float *out_rgbn);
+
+/* The jitter of frame `index` for an upscale from w x h to W x H -- a pure host function; set it with arctic_set_camera_jitter and pass it in
+ * ArcticTaaUpscale::jitter.  In fp32, one rounding per operation:
+ *   Without ARCTIC_TAA_UPSCALE_JITTER_EXACT in `index`: L = 8 * ceil(W / w) * ceil(H / h); i = index % L + 1; out2 = {halton(i, 2) - 0.5,
+ *     halton(i, 3) - 0.5}, halton(i, b): f = 1, x = 0; while i > 0: f = f / b; x = x + f * (float)(i % b); i = i / b.
+ *   With it (the sequence of P3), for W = s*w and H = s*h with s = 1, 2 or 4 alone: i = (index & 0x7FFFFFFF) % (s*s); kx = i % s, ky = i / s;
+ *     out2 = {0.5 - (kx + 0.5) / s, 0.5 - (ky + 0.5) / s}: phase i puts the centres of the output pixels (s*qx + kx, s*qy + ky) on samples.
+ * ARCTIC_E_INVALID (nothing written): a null pointer, sizes outside what the upscaler takes, the flag with any other ratio. */
+#define ARCTIC_TAA_UPSCALE_JITTER_EXACT 0x80000000u
+int arctic_taa_upscale_jitter(uint32_t index, uint32_t w, uint32_t W, uint32_t h, uint32_t H, float *out2);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row

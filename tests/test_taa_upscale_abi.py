@@ -1,0 +1,180 @@
+"""The temporal upscaler on a machine without a GPU: the entry points (header, binding, C++ mirror, python wrappers), the record's layout, the
+definition in the header in front of the calls, the build rules, the kernel's resource figures, every refusal that needs no device -- in the
+header's order, the output untouched -- and the pure host calls working with no device."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "arctic-renderer_amd", "csrc")
+ENTRY_POINTS = {"arctic_taa_upscale_device": 6, "arctic_taa_upscale": 6, "arctic_pass_taa_upscale": 5, "arctic_taa_upscale_reset": 1, "arctic_read_taa_upscale": 5,
+                "arctic_taa_upscale_hdr_device": 2, "arctic_taa_upscale_info": 2, "arctic_taa_upscale_pixels": 9, "arctic_taa_upscale_jitter": 6}
+MODULE_LEVEL = ("taa_upscale_pixels", "taa_upscale_jitter")
+NO_HANDLE = ("arctic_taa_upscale_pixels", "arctic_taa_upscale_jitter")
+FIELDS = ["flags", "max_history", "min_weight", "jitter[2]", "sharpness", "confidence_floor", "out_width", "out_height", "reserved[3]"]
+HAVE_HIPCC = shutil.which("hipcc") is not None or os.path.exists("/opt/rocm/bin/hipcc")
+INVALID = -1
+F = np.float32
+
+
+@pytest.fixture(scope="module")
+def lib(pkg):
+    from importlib import import_module
+    b = import_module("arctic_renderer_amd.binding")
+    if not os.path.exists(b.LIB_PATH):
+        import __graft_entry__ as entry
+        entry.build()
+    return b
+
+
+def test_entry_points_binding_and_mirror(pkg, lib):
+    text = open(os.path.join(ROOT, "include", "arctic_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    L = lib.lib()
+    for name, arity in ENTRY_POINTS.items():
+        m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", header)
+        assert m and len(m.group(1).split(",")) == arity, name
+        assert name in lib.header_symbols() and hasattr(L, name)
+        res, args = lib.SIGNATURES[name]
+        assert res is C.c_int32 and len(args) == arity
+    exported = subprocess.check_output(["nm", "-D", "--defined-only", lib.LIB_PATH], text=True) if shutil.which("nm") else None
+    if exported is not None:
+        for name in ENTRY_POINTS:
+            assert re.search(r" T " + name + r"$", exported, re.M), name
+    hpp = open(os.path.join(ROOT, "arctic-renderer_amd", "host", "renderer.hpp")).read()
+    for method in [n[len("arctic_"):] for n in ENTRY_POINTS]:
+        assert re.search(r"\[\[nodiscard\]\]\s+(static\s+)?bool\s+" + method + r"\s*\(", hpp), method
+        assert hasattr(pkg.renderer, method) if method in MODULE_LEVEL else hasattr(pkg.renderer.Renderer, method), method
+    # the record: 48 bytes, a multiple of 16, the fields where the header puts them, the flags
+    m = re.search(r"typedef struct ArcticTaaUpscale \{(.*?)\} ArcticTaaUpscale;", header, re.S)
+    assert [f.split()[-1] for f in m.group(1).split(";") if f.strip()] == FIELDS
+    dt = pkg.scene.TAA_UPSCALE_DTYPE
+    assert dt.itemsize == 48 and dt.itemsize % 16 == 0
+    assert [dt.fields[n][1] for n in ("flags", "max_history", "min_weight", "jitter", "sharpness", "confidence_floor", "out_width", "out_height", "reserved")] == [0, 4, 8, 12, 20, 24, 28, 32, 36]
+    for name, value in (("LUMA_WEIGHT", "1u"), ("SOURCE_COMPOSED", "2u"), ("NO_CLAMP", "4u"), ("JITTER_EXACT", "0x80000000u")):
+        assert re.search(r"#define ARCTIC_TAA_UPSCALE_" + name + r"\s+" + value, header), name
+    assert (lib.TAA_UPSCALE_LUMA_WEIGHT, lib.TAA_UPSCALE_SOURCE_COMPOSED, lib.TAA_UPSCALE_NO_CLAMP, lib.TAA_UPSCALE_JITTER_EXACT) == (1, 2, 4, 0x80000000)
+    # the first five fields lie where ArcticTaa's do: the two stages' records start alike
+    assert [dt.fields[n][1] for n in ("flags", "max_history", "min_weight", "jitter")] == [pkg.scene.TAA_DTYPE.fields[n][1] for n in ("flags", "max_history", "min_weight", "jitter")]
+    # the definition stands in the header, in front of the calls
+    for phrase in ("rx = (float)w / (float)W", "TWO SETS", "32 bytes per output pixel", "tile-major like T", "re-allocated when W x H changes", "after arctic_taa_upscale_reset, after arctic_resize",
+                   "U is not T", "ux = (px + 0.5) * rx", "qx = clamp(floor(ux + jx), 0, w-1)", "Dx = (((qx + 0.5) - jx) - ux) / rx", "a NaN neighbour is ignored",
+                   "beta = max(0, 1 - sharpness * (Dx*Dx + Dy*Dy))", "out = c, N = max(beta, confidence_floor)", "hx = ((px + 0.5) + vx / rx) + jx / rx",
+                   "tested in\n *      float before any conversion", "a rejected tap is a SELECT", "S = ((k0 + k1) + k2) + k3", "If !(S > min_weight): reject",
+                   "h = (h < lo) ? lo : h, then h = (h > hi) ? hi : h", "N = min(hn + beta, max_history); a = beta / N", "beta == 0 is a SELECT: out = h",
+                   "if hn + beta == beta", "out = h + (c - h) * a", "out = (c*kc + h*kh) / (kc + kh)", "as k_taa_resolve carries it out", "P1.", "P2.", "P3.", "P4.",
+                   "IN FRONT of the upscaler", "no LOD bias", "A shard cannot upscale", "leaves U as it was", "every refusal comes before anything is enqueued",
+                   "the frame's ONE motion call", "f = f / b; x = x + f * (float)(i % b)", "out2 = {0.5 - (kx + 0.5) / s, 0.5 - (ky + 0.5) / s}"):
+        assert phrase in text, phrase
+    assert text.index("N = min(hn + beta, max_history)") < text.index("int arctic_taa_upscale_device(") < text.index("int arctic_pass_taa_upscale(") < text.index("int arctic_taa_upscale_pixels(")
+    assert text.index("int arctic_fog_pixels(") < text.index("typedef struct ArcticTaaUpscale")
+    for name in ("README.md", "DESIGN.md", "INTEGRATION.md"):
+        assert "arctic_taa_upscale_device" in open(os.path.join(ROOT, name)).read(), name
+    assert "taa_upscale_time.py" in open(os.path.join(ROOT, "tools", "README.md")).read()
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    assert "\n## 6y." in design and "**Not provided.**" in design.split("\n## 6y.")[1].split("\n## 7.")[0]
+    make = open(os.path.join(CSRC, "Makefile")).read()
+    assert re.search(r"^taa_upscale\.o: taa_upscale\.hip.*taa\.h.*taa_upscale\.h.*post_process\.h.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\) ", make, flags=re.M) and "asm-taa-upscale:" in make
+    assert re.search(r"^taa_upscale_host\.o: taa_upscale\.cpp.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\) ", make, flags=re.M)
+    assert re.search(r"^taa_upscale_calls\.o: taa_upscale_calls\.cpp.*renderer_state\.h", make, flags=re.M)
+    assert "taa_upscale.o taa_upscale_calls.o taa_upscale_host.o" in make
+    # one copy of the arithmetic: the kernel and the arbiter call taa_upscale.h's function, which stands on taa.h; one copy of the tonemapper
+    for unit in ("taa_upscale.hip", "taa_upscale.cpp"):
+        assert "taa_upscale_pixel(" in open(os.path.join(CSRC, unit)).read(), unit
+    shared = open(os.path.join(CSRC, "taa_upscale.h")).read()
+    assert '#include "taa.h"' in shared and "taa_luma_weight(" in shared and "static_assert(TAA_UPSCALE_FOOTPRINT == 11" in shared
+    kernel = open(os.path.join(CSRC, "taa_upscale.hip")).read()
+    assert '#include "post_process.h"' in kernel and "rrt_odt" not in kernel
+
+
+def record(pkg, **kw):
+    return pkg.renderer.taa_upscale_arguments(kw.pop("out_size", (4, 4)), **kw)
+
+
+def test_refusals_of_the_host_functions_and_of_a_null_handle(pkg, lib):
+    L = lib.lib()
+    R = pkg.renderer
+    cur = np.zeros((2, 2, 3), F)
+    assert R.taa_upscale_pixels(np.zeros((0, 2)), cur, (4, 4)).shape == (0, 4)
+    # every refusal of the record, in the header's order; nothing is written
+    bads = (dict(flags=8), dict(flags=0x80000000), dict(max_history=0.5), dict(max_history=65536.5), dict(max_history=np.nan), dict(min_weight=1.0), dict(min_weight=-1e-9),
+            dict(jitter=(1.5, 0)), dict(jitter=(0, np.nan)), dict(sharpness=-1e-9), dict(sharpness=65537.0), dict(sharpness=np.nan), dict(sharpness=np.inf),
+            dict(confidence_floor=0.0), dict(confidence_floor=1.0001), dict(confidence_floor=np.nan), dict(out_size=(1, 4)), dict(out_size=(4, 9)), dict(out_size=(0, 4)),
+            dict(out_size=(9, 4)))
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    xy = np.zeros((1, 2), np.int32)
+    for bad in bads:
+        out = np.full((1, 4), 77.0, F)
+        t = record(pkg, **dict(bad))
+        assert L.arctic_taa_upscale_pixels(p(t), 1, p(xy), 2, 2, p(cur), None, None, p(out)) == INVALID and (out == 77.0).all(), bad
+        with pytest.raises(R.ArcticError):
+            R.taa_upscale_pixels([[0, 0]], cur, **dict(dict(out_size=(4, 4)), **bad))
+    t = record(pkg)
+    t["reserved"][0, 2] = 1
+    out = np.full((1, 4), 77.0, F)
+    assert L.arctic_taa_upscale_pixels(p(t), 1, p(xy), 2, 2, p(cur), None, None, p(out)) == INVALID and (out == 77.0).all()
+    for bad_xy in ([[4, 0]], [[0, 4]], [[-1, 0]]):
+        with pytest.raises(R.ArcticError):
+            R.taa_upscale_pixels(bad_xy, cur, (4, 4))
+    with pytest.raises(R.ArcticError):
+        R.taa_upscale_pixels([[0, 0]], cur, (4, 4), velocity2=np.zeros((1, 2)))
+    with pytest.raises(R.ArcticError):
+        R.taa_upscale_pixels([[0, 0]], cur, (4, 4), prev=np.zeros((2, 2, 4)))
+    # the pure host calls work with no device: the limits of every range pass
+    got = R.taa_upscale_pixels([[3, 3]], cur, (8, 8), max_history=65536.0, min_weight=0.999, jitter=(-1.0, 1.0), sharpness=65536.0, confidence_floor=1.0, flags=7)
+    assert got.tolist() == [[0.0, 0.0, 0.0, 1.0]]
+    assert R.taa_upscale_jitter(0, (2, 2), (8, 8)).tolist() == [0.0, float(F(1.0) / F(3.0) - F(0.5))]
+    assert R.taa_upscale_jitter(3, (2, 2), (4, 4), exact=True).tolist() == [-0.25, -0.25]
+    # a null handle, before any device is touched
+    for name, arity in ENTRY_POINTS.items():
+        if name not in NO_HANDLE:
+            assert getattr(L, name)(*([None] * arity)) == INVALID, name
+
+
+def test_the_refusals_come_in_the_headers_order():
+    """taa_upscale_refusal names the first fault of a record that has several: flags, max_history, min_weight, jitter, sharpness,
+    confidence_floor, reserved, then the sizes -- read off the source, whose order the calls share"""
+    source = open(os.path.join(CSRC, "taa_upscale.cpp")).read()
+    body = source.split("const char *taa_upscale_refusal(")[1].split("\n}\n")[0]
+    order = [body.index(s) for s in ('"null parameters"', '"flags have unknown bits"', '"max_history outside', '"min_weight outside', '"jitter outside', '"sharpness outside',
+                                     '"confidence_floor outside', '"reserved not 0"', '"the output size must lie')]
+    assert order == sorted(order)
+    calls = open(os.path.join(CSRC, "taa_upscale_calls.cpp")).read()
+    for entry in ("arctic_taa_upscale_device", "arctic_taa_upscale"):
+        body = calls.split("int " + entry + "(")[1].split("\n}\n")[0]
+        assert body.index("upscale_checks(") < body.index("upscale_states(") < body.index("select_device(") < body.index("upscale_planes(")
+    body = calls.split("int arctic_pass_taa_upscale(")[1].split("\n}\n")[0]
+    assert body.index("upscale_checks(") < body.index("valid_scene(") < body.index("have_vis") < body.index("upscale_states(") < body.index("select_device(") < body.index("arctic_motion_vectors_device(")
+    checks = calls.split("int upscale_checks(")[1].split("\n}\n")[0]
+    assert checks.index("null settings or parameters") < checks.index("taa_upscale_refusal(") < checks.index("4-byte aligned")
+    states = calls.split("int upscale_states(")[1].split("\n}\n")[0]
+    assert states.index("r->rows() != r->height") < states.index("keep_float") < states.index("hdr_valid") < states.index("SOURCE_COMPOSED") < states.index("hdr16")
+
+
+@pytest.mark.skipif(not HAVE_HIPCC, reason="no hipcc")
+def test_the_kernel_uses_no_scratch_no_stack_and_one_footprint_of_lds(tmp_path):
+    """k_taa_upscale: no scratch, no stack frame and no call, 8 waves per SIMD, and four footprints of 11 x 11 x 3 floats of LDS per workgroup
+    (5808 bytes).  The compiler's figures when this was written: 61 VGPRs and 50 SGPRs -- the bound below is what 8 waves per SIMD need, the
+    figures DESIGN.md 6y quotes are checked against the compiler's"""
+    log = subprocess.run(["make", "-C", CSRC, "asm-taa-upscale", f"OUT={tmp_path}"], capture_output=True, text=True, check=True)
+    remarks = log.stdout + log.stderr
+    names = re.findall(r"Function Name: (\S+)", remarks)
+    grab = lambda what: [int(x) for x in re.findall(what + r": (\d+)", remarks)]
+    r = dict(vgprs=grab(r" VGPRs"), sgprs=grab(r"TotalSGPRs"), scratch=grab(r"ScratchSize \[bytes/lane\]"), lds=grab(r"LDS Size \[bytes/block\]"), waves=grab(r"Occupancy \[waves/SIMD\]"))
+    assert len(names) == 2 and "k_taa_upscaleE" in names[0] and "k_taa_upscale_hdrE" in names[1], names      # (the second only untiles U's colour)
+    assert r["scratch"] == [0, 0] and r["lds"] == [4 * 11 * 11 * 3 * 4, 0] and r["waves"] == [8, 8] and r["vgprs"][0] <= 64, r
+    assert "Dynamic Stack: True" not in remarks
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    assert f"k_taa_upscale: {r['vgprs'][0]} VGPRs, {r['sgprs'][0]} SGPRs, scratch 0, {r['lds'][0]} bytes of LDS per workgroup, 8 waves per SIMD" in design, r
+    frame = []
+    for line in open(str(tmp_path / "taa_upscale-hip-amdgcn-amd-amdhsa-gfx950.s")):
+        m = re.match(r"\s+\.amdhsa_(private_segment_fixed_size|uses_dynamic_stack) (\d+)", line)
+        if m:
+            frame.append(int(m.group(2)))
+        assert "swappc" not in line
+    assert frame == [0, 0, 0, 0], frame
