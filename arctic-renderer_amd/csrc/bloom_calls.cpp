@@ -1,6 +1,6 @@
 // bloom_calls.cpp -- bloom's calls of the C-ABI (include/arctic_hip.h: arctic_bloom_device and the definition in front of it; the arithmetic:
 // bloom.h; the kernels: bloom.hip; the arbiters and the layout: bloom.cpp).  Of the handle (renderer_state.h) it owns ArcticRenderer::Bloom and
-// reads, of the stages in front of it, only what says whether their planes hold a frame of this size.
+// reads its colour plane through post_source.cpp, which knows the stages in front of it.
 #include <cstdint>
 #include <cstring>
 
@@ -19,33 +19,18 @@ int bloom_checks(ArcticRenderer *r, const ArcticSettings *st, const ArcticBloom 
     if (align && (((uintptr_t)color | (uintptr_t)out) & 3u)) return r->fail(ARCTIC_E_INVALID, "%s: the colour plane and the output must be 4-byte aligned", who);
     return ARCTIC_OK;
 }
-// ... and with ARCTIC_E_STATE: no side effect.  own_color: the colour plane is the handle's (d.flags says which).  The conditions are those of
-// the stage's own read call (the lens, the blur), of the history and of the float HDR plane, as the depth of field asks them of the same sources
+// which plane a NULL colour means under the record's flags (they exclude each other), and the public name of the flag that says so
+SourceFlag bloom_source(uint32_t flags) {
+    if (flags & BLOOM_SOURCE_DOF) return {HdrSource::Dof, "ARCTIC_BLOOM_SOURCE_DOF"};
+    if (flags & BLOOM_SOURCE_MOTION_BLUR) return {HdrSource::MotionBlur, "ARCTIC_BLOOM_SOURCE_MOTION_BLUR"};
+    if (flags & BLOOM_SOURCE_TAA) return {HdrSource::Taa, "ARCTIC_BLOOM_SOURCE_TAA"};
+    return {(flags & BLOOM_SOURCE_COMPOSED) ? HdrSource::Composed : HdrSource::Shaded, "ARCTIC_BLOOM_SOURCE_COMPOSED"};
+}
+// ... and with ARCTIC_E_STATE: no side effect.  own_color: the colour plane is the handle's (d.flags says which)
 int bloom_states(ArcticRenderer *r, const BloomDesc &d, bool own_color, const char *who) {
     if (r->rows() != r->height)
         return r->fail(ARCTIC_E_STATE, "%s: the pyramid's footprints need the whole frame, this handle owns %u of %u rows (its neighbours' rows are on other shards)", who, r->rows(), r->height);
-    if (!own_color) return ARCTIC_OK;
-    if (d.flags & BLOOM_SOURCE_DOF) {
-        const ArcticRenderer::Dof &D = r->dof;
-        if (!D.valid || D.width != r->width || D.height != r->height) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_BLOOM_SOURCE_DOF: no depth of field yet, or not since the last resize", who);
-        return ARCTIC_OK;
-    }
-    if (d.flags & BLOOM_SOURCE_MOTION_BLUR) {
-        const ArcticRenderer::MotionBlur &B = r->motion_blur;
-        if (!B.valid || B.width != r->width || B.height != r->height) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_BLOOM_SOURCE_MOTION_BLUR: nothing blurred yet, or not since the last resize", who);
-        return ARCTIC_OK;
-    }
-    if (d.flags & BLOOM_SOURCE_TAA) {
-        if (!(r->taa.valid && r->taa.width == r->width && r->taa.height == r->height))
-            return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_BLOOM_SOURCE_TAA: the anti-aliasing's history is empty (no resolve yet, or none since the last reset or resize)", who);
-        return ARCTIC_OK;
-    }
-    if (!r->keep_float) return r->fail(ARCTIC_E_STATE, "%s: the float HDR plane needs ARCTIC_OPT_KEEP_FLOAT_OUTPUT", who);
-    if (!r->hdr_valid) return r->fail(ARCTIC_E_STATE, "%s: nothing shaded since ARCTIC_OPT_KEEP_FLOAT_OUTPUT was turned on or since the last resize (arctic_pass_shade or a frame first)", who);
-    if ((d.flags & BLOOM_SOURCE_COMPOSED) && (!r->compose.pixels || r->compose.pixels != (uint64_t)r->rows() * r->width))
-        return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_BLOOM_SOURCE_COMPOSED: nothing composed yet, or not since the last resize", who);
-    if (r->hdr16) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_OPT_HDR16 = 1: the HDR plane is rounded through binary16", who);
-    return ARCTIC_OK;
+    return own_color ? source_refusal(r, bloom_source(d.flags), who) : ARCTIC_OK;
 }
 // the handle's buffers and the 2 L launches: device pointers throughout.  d_color: null = the handle's own plane, per d.flags; d_out: the caller's
 // RGBA8, or null = the handle's own.  The pyramids are sized for 8 levels, so a record with other levels allocates nothing.  The handle's state
@@ -61,18 +46,10 @@ int bloom_planes(ArcticRenderer *r, const ArcticSettings *st, const BloomDesc &d
     HIPCHECK(r, B.d_ldr.ensure(n * 12));
     HIPCHECK(r, B.written.ensure(hipEventDisableTiming));
     HIPCHECK(r, B.written.wait(r->stream));   // (recorded on another stream: arctic_set_stream came in between; on this one: stream order does it)
+    SourcePlane source = {d_color, false};
+    if (!d_color) { if (int rc = source_plane(r, bloom_source(d.flags).source, source)) return rc; }
     BloomParams p = {};
-    if (d_color) p.color = d_color;
-    else if (d.flags & BLOOM_SOURCE_TAA) {
-        HIPCHECK(r, r->taa.written.wait(r->stream));   // (the resolve that wrote T, if the stream has changed since)
-        p.color = r->taa.d_t[r->taa.cur].p; p.color_taa = true;
-    } else if (d.flags & BLOOM_SOURCE_DOF) {
-        HIPCHECK(r, r->dof.written.wait(r->stream));   // (... the lens, likewise)
-        p.color = r->dof.d_hdr.as<float>();
-    } else if (d.flags & BLOOM_SOURCE_MOTION_BLUR) {
-        HIPCHECK(r, r->motion_blur.written.wait(r->stream));   // (... and the blur)
-        p.color = r->motion_blur.d_hdr.as<float>();
-    } else p.color = (d.flags & BLOOM_SOURCE_COMPOSED) ? r->compose.d_hdr.as<float>() : r->d_hdr.as<float>();
+    p.color = source.color; p.color_taa = source.color_taa;
     p.down = B.d_down.as<float>(); p.up = B.d_up.as<float>();
     p.out_hdr = B.d_hdr.as<float>(); p.out_rgba8 = reinterpret_cast<uint32_t *>(d_out ? d_out : B.d_rgba8.as<uint8_t>()); p.out_ldr = B.d_ldr.as<float>();
     p.tiles_x = r->tiles_x; p.width = r->width; p.rows = r->rows();
@@ -108,22 +85,15 @@ int arctic_bloom(ArcticRenderer *r, const ArcticSettings *settings, const Arctic
     if (rc || (rc = bloom_states(r, d, hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
     ArcticRenderer::Bloom &B = r->bloom;
     const size_t px = (size_t)r->rows() * r->width;
-    if (hdr_rgb32f) {
-        HIPCHECK(r, B.written.ensure(hipEventDisableTiming));
-        HIPCHECK(r, B.written.wait(r->stream));   // (the copy below overwrites a plane the previous call read)
-        HIPCHECK(r, B.d_color.ensure(std::max<size_t>(px, 1) * 12));
-        HIPCHECK(r, hipMemcpyAsync(B.d_color.p, hdr_rgb32f, px * 12, hipMemcpyHostToDevice, r->stream));
-    }
+    if (hdr_rgb32f && (rc = upload_plane(r, B.written, B.d_color, hdr_rgb32f, px, 12)) != ARCTIC_OK) return rc;
     if ((rc = bloom_planes(r, settings, d, hdr_rgb32f ? B.d_color.as<float>() : nullptr, nullptr)) != ARCTIC_OK) return rc;
-    if (out_rgba8) HIPCHECK(r, hipMemcpyAsync(out_rgba8, B.d_rgba8.p, px * 4, hipMemcpyDeviceToHost, r->stream));
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    return hdr_rgb32f ? ARCTIC_OK : check_item_overflow(r);
+    return read_back(r, out_rgba8, B.d_rgba8, px * 4, hdr_rgb32f == nullptr);
 }
 
 int arctic_read_bloom(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, float *down, float *up) {
     if (!r) return ARCTIC_E_INVALID;
     const ArcticRenderer::Bloom &B = r->bloom;
-    if (!B.valid || B.width != r->width || B.height != r->height || r->rows() != r->height)
+    if (!B.holds(*r) || r->rows() != r->height)
         return r->fail(ARCTIC_E_STATE, "read_bloom: no bloom yet, or not since the last resize");
     if (rgba8 && !B.own_rgba8) return r->fail(ARCTIC_E_STATE, "read_bloom: the latest call wrote the caller's RGBA8 buffer, not the handle's");
     int rc = select_device(r);

@@ -1,6 +1,6 @@
 // exposure_calls.cpp -- auto-exposure's calls of the C-ABI (include/arctic_hip.h: arctic_exposure_device and the definition in front of it; the
 // arithmetic: exposure.h; the kernels: exposure.hip; the arbiters and the layout: exposure.cpp).  Of the handle (renderer_state.h) it owns
-// ArcticRenderer::Exposure and reads, of the stages in front of it, only what says whether their planes hold a frame of this size.
+// ArcticRenderer::Exposure and reads its colour plane through post_source.cpp, which knows the stages in front of it.
 #include <cstdint>
 #include <cstring>
 
@@ -19,43 +19,20 @@ int exposure_checks(ArcticRenderer *r, const ArcticSettings *st, const ArcticExp
     if (align && (((uintptr_t)color | (uintptr_t)out) & 3u)) return r->fail(ARCTIC_E_INVALID, "%s: the colour plane and the output must be 4-byte aligned", who);
     return ARCTIC_OK;
 }
-// ... and with ARCTIC_E_STATE: no side effect.  own_color: the colour plane is the handle's (d.flags says which).  The conditions are those of
-// each stage's own read call, as bloom asks them of the same sources
+// which plane a NULL colour means under the record's flags (the sources exclude each other), and the public name of the flag that says so
+SourceFlag exposure_source(uint32_t flags) {
+    if (flags & EXPOSURE_SOURCE_BLOOM) return {HdrSource::Bloom, "ARCTIC_EXPOSURE_SOURCE_BLOOM"};
+    if (flags & EXPOSURE_SOURCE_DOF) return {HdrSource::Dof, "ARCTIC_EXPOSURE_SOURCE_DOF"};
+    if (flags & EXPOSURE_SOURCE_MOTION_BLUR) return {HdrSource::MotionBlur, "ARCTIC_EXPOSURE_SOURCE_MOTION_BLUR"};
+    if (flags & EXPOSURE_SOURCE_TAA) return {HdrSource::Taa, "ARCTIC_EXPOSURE_SOURCE_TAA"};
+    return {(flags & EXPOSURE_SOURCE_COMPOSED) ? HdrSource::Composed : HdrSource::Shaded, "ARCTIC_EXPOSURE_SOURCE_COMPOSED"};
+}
+// ... and with ARCTIC_E_STATE: no side effect.  own_color: the colour plane is the handle's (d.flags says which)
 int exposure_states(ArcticRenderer *r, const ExposureDesc &d, bool own_color, const char *who) {
     if (r->rows() != r->height)
         return r->fail(ARCTIC_E_STATE, "%s: the meter needs the whole frame, this handle owns %u of %u rows (the others are on other shards)", who, r->rows(), r->height);
-    const ArcticRenderer::Exposure &X = r->exposure;
-    const auto source = [&]() -> int {
-        if (!own_color) return ARCTIC_OK;
-        if (d.flags & EXPOSURE_SOURCE_BLOOM) {
-            const ArcticRenderer::Bloom &B = r->bloom;
-            if (!B.valid || B.width != r->width || B.height != r->height) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_EXPOSURE_SOURCE_BLOOM: no bloom yet, or not since the last resize", who);
-            return ARCTIC_OK;
-        }
-        if (d.flags & EXPOSURE_SOURCE_DOF) {
-            const ArcticRenderer::Dof &D = r->dof;
-            if (!D.valid || D.width != r->width || D.height != r->height) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_EXPOSURE_SOURCE_DOF: no depth of field yet, or not since the last resize", who);
-            return ARCTIC_OK;
-        }
-        if (d.flags & EXPOSURE_SOURCE_MOTION_BLUR) {
-            const ArcticRenderer::MotionBlur &B = r->motion_blur;
-            if (!B.valid || B.width != r->width || B.height != r->height) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_EXPOSURE_SOURCE_MOTION_BLUR: nothing blurred yet, or not since the last resize", who);
-            return ARCTIC_OK;
-        }
-        if (d.flags & EXPOSURE_SOURCE_TAA) {
-            if (!(r->taa.valid && r->taa.width == r->width && r->taa.height == r->height))
-                return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_EXPOSURE_SOURCE_TAA: the anti-aliasing's history is empty (no resolve yet, or none since the last reset or resize)", who);
-            return ARCTIC_OK;
-        }
-        if (!r->keep_float) return r->fail(ARCTIC_E_STATE, "%s: the float HDR plane needs ARCTIC_OPT_KEEP_FLOAT_OUTPUT", who);
-        if (!r->hdr_valid) return r->fail(ARCTIC_E_STATE, "%s: nothing shaded since ARCTIC_OPT_KEEP_FLOAT_OUTPUT was turned on or since the last resize (arctic_pass_shade or a frame first)", who);
-        if ((d.flags & EXPOSURE_SOURCE_COMPOSED) && (!r->compose.pixels || r->compose.pixels != (uint64_t)r->rows() * r->width))
-            return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_EXPOSURE_SOURCE_COMPOSED: nothing composed yet, or not since the last resize", who);
-        if (r->hdr16) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_OPT_HDR16 = 1: the HDR plane is rounded through binary16", who);
-        return ARCTIC_OK;
-    };
-    if (int rc = source()) return rc;
-    if ((d.flags & EXPOSURE_HOLD) && !(X.valid && X.width == r->width && X.height == r->height))
+    if (own_color) { if (int rc = source_refusal(r, exposure_source(d.flags), who)) return rc; }
+    if ((d.flags & EXPOSURE_HOLD) && !r->exposure.holds(*r))
         return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_EXPOSURE_HOLD: no exposure is held (no metering call yet, or none since arctic_exposure_reset or the last resize)", who);
     return ARCTIC_OK;
 }
@@ -76,21 +53,10 @@ int exposure_planes(ArcticRenderer *r, const ArcticSettings *st, const ExposureD
     }
     HIPCHECK(r, X.written.ensure(hipEventDisableTiming));
     HIPCHECK(r, X.written.wait(r->stream));   // (recorded on another stream: arctic_set_stream came in between; on this one: stream order does it)
+    SourcePlane source = {d_color, false};
+    if (!d_color) { if (int rc = source_plane(r, exposure_source(d.flags).source, source)) return rc; }
     ExposureParams p = {};
-    if (d_color) p.color = d_color;
-    else if (d.flags & EXPOSURE_SOURCE_TAA) {
-        HIPCHECK(r, r->taa.written.wait(r->stream));   // (the resolve that wrote T, if the stream has changed since)
-        p.color = r->taa.d_t[r->taa.cur].p; p.color_taa = true;
-    } else if (d.flags & EXPOSURE_SOURCE_BLOOM) {
-        HIPCHECK(r, r->bloom.written.wait(r->stream));   // (... bloom, likewise)
-        p.color = r->bloom.d_hdr.as<float>();
-    } else if (d.flags & EXPOSURE_SOURCE_DOF) {
-        HIPCHECK(r, r->dof.written.wait(r->stream));   // (... the lens)
-        p.color = r->dof.d_hdr.as<float>();
-    } else if (d.flags & EXPOSURE_SOURCE_MOTION_BLUR) {
-        HIPCHECK(r, r->motion_blur.written.wait(r->stream));   // (... and the blur)
-        p.color = r->motion_blur.d_hdr.as<float>();
-    } else p.color = (d.flags & EXPOSURE_SOURCE_COMPOSED) ? r->compose.d_hdr.as<float>() : r->d_hdr.as<float>();
+    p.color = source.color; p.color_taa = source.color_taa;
     p.partials = X.d_partials.as<uint32_t>(); p.hist = X.d_hist.as<uint32_t>(); p.state = X.d_state.as<ExposureState>();
     if (apply) { p.out_hdr = X.d_hdr.as<float>(); p.out_rgba8 = reinterpret_cast<uint32_t *>(d_out ? d_out : X.d_rgba8.as<uint8_t>()); p.out_ldr = X.d_ldr.as<float>(); }
     p.tiles_x = r->tiles_x; p.width = r->width; p.rows = r->rows();
@@ -132,23 +98,16 @@ int arctic_exposure(ArcticRenderer *r, const ArcticSettings *settings, const Arc
     if (rc || (rc = exposure_states(r, d, hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
     ArcticRenderer::Exposure &X = r->exposure;
     const size_t px = (size_t)r->rows() * r->width;
-    if (hdr_rgb32f) {
-        HIPCHECK(r, X.written.ensure(hipEventDisableTiming));
-        HIPCHECK(r, X.written.wait(r->stream));   // (the copy below overwrites a plane the previous call read)
-        HIPCHECK(r, X.d_color.ensure(std::max<size_t>(px, 1) * 12));
-        HIPCHECK(r, hipMemcpyAsync(X.d_color.p, hdr_rgb32f, px * 12, hipMemcpyHostToDevice, r->stream));
-    }
+    if (hdr_rgb32f && (rc = upload_plane(r, X.written, X.d_color, hdr_rgb32f, px, 12)) != ARCTIC_OK) return rc;
     if ((rc = exposure_planes(r, settings, d, hdr_rgb32f ? X.d_color.as<float>() : nullptr, nullptr)) != ARCTIC_OK) return rc;
-    if (out_rgba8 && !(d.flags & EXPOSURE_METER_ONLY)) HIPCHECK(r, hipMemcpyAsync(out_rgba8, X.d_rgba8.p, px * 4, hipMemcpyDeviceToHost, r->stream));
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    return hdr_rgb32f ? ARCTIC_OK : check_item_overflow(r);
+    return read_back(r, (d.flags & EXPOSURE_METER_ONLY) ? nullptr : out_rgba8, X.d_rgba8, px * 4, hdr_rgb32f == nullptr);   // (a metering call has no planes)
 }
 
 int arctic_read_exposure(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, uint32_t *hist256, ArcticExposureState *state) {
     if (!r) return ARCTIC_E_INVALID;
     const ArcticRenderer::Exposure &X = r->exposure;
-    const bool size = X.width == r->width && X.height == r->height && r->rows() == r->height;
-    if ((hist256 || state) && !(X.valid && size)) return r->fail(ARCTIC_E_STATE, "read_exposure: nothing metered yet, or not since arctic_exposure_reset or the last resize");
+    const bool whole = r->rows() == r->height, size = X.width == r->width && X.height == r->height && whole;
+    if ((hist256 || state) && !(X.holds(*r) && whole)) return r->fail(ARCTIC_E_STATE, "read_exposure: nothing metered yet, or not since arctic_exposure_reset or the last resize");
     if ((ldr_rgb || hdr_rgb || rgba8) && !(X.planes && size)) return r->fail(ARCTIC_E_STATE, "read_exposure: no exposed frame yet, or not since the last resize");
     if (rgba8 && !X.own_rgba8) return r->fail(ARCTIC_E_STATE, "read_exposure: the latest call wrote the caller's RGBA8 buffer, not the handle's");
     int rc = select_device(r);

@@ -27,18 +27,14 @@ int fog_checks(ArcticRenderer *r, const ArcticSettings *st, const ArcticFog *fog
         return r->fail(ARCTIC_E_INVALID, "%s: the colour plane, the depth and the outputs must be 4-byte aligned", who);
     return ARCTIC_OK;
 }
+// which plane a NULL colour means under the record's flags
+SourceFlag fog_source(uint32_t flags) { return {(flags & FOG_SOURCE_COMPOSED) ? HdrSource::Composed : HdrSource::Shaded, "ARCTIC_FOG_SOURCE_COMPOSED"}; }
 // ... and with ARCTIC_E_STATE: no side effect.  own_color: the colour plane is the handle's (d.flags says which).  The sun's map under the rule of
 // arctic_shade_hits: whole, and drawn or written at least once
 int fog_states(ArcticRenderer *r, const FogDesc &d, bool own_color, const char *who) {
     if (r->rows() != r->height)
         return r->fail(ARCTIC_E_STATE, "%s: whole frames only, this handle owns %u of %u rows (the others are on other shards)", who, r->rows(), r->height);
-    if (own_color) {
-        if (!r->keep_float) return r->fail(ARCTIC_E_STATE, "%s: the float HDR plane needs ARCTIC_OPT_KEEP_FLOAT_OUTPUT", who);
-        if (!r->hdr_valid) return r->fail(ARCTIC_E_STATE, "%s: nothing shaded since ARCTIC_OPT_KEEP_FLOAT_OUTPUT was turned on or since the last resize (arctic_pass_shade or a frame first)", who);
-        if ((d.flags & FOG_SOURCE_COMPOSED) && (!r->compose.pixels || r->compose.pixels != (uint64_t)r->rows() * r->width))
-            return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_FOG_SOURCE_COMPOSED: nothing composed yet, or not since the last resize", who);
-        if (r->hdr16) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_OPT_HDR16 = 1: the HDR plane is rounded through binary16", who);
-    }
+    if (own_color) { if (int rc = source_refusal(r, fog_source(d.flags), who)) return rc; }
     if (r->shadow_size && r->shadow_sharded)
         return r->fail(ARCTIC_E_STATE, "%s: the sun's map is sharded (ARCTIC_OPT_SHADOW_SHARDED): a sample may lie in rows this handle never draws", who);
     if (r->shadow_size && !r->shadow_written_set[r->scur])
@@ -70,8 +66,10 @@ int fog_planes(ArcticRenderer *r, const ArcticSettings *st, const FogDesc &d, co
         F.have_offsets = true;
         ++F.uploads;
     }
+    SourcePlane source = {d_color, false};
+    if (!d_color) { if (int rc = source_plane(r, fog_source(d.flags).source, source)) return rc; }
     FogParams p = {};
-    p.color = d_color ? d_color : (d.flags & FOG_SOURCE_COMPOSED) ? r->compose.d_hdr.as<float>() : r->d_hdr.as<float>();
+    p.color = static_cast<const float *>(source.color);
     p.depth = d_depth;
     p.map = r->shadow_size ? r->d_shadow().as<float>() : nullptr; p.S = r->shadow_size;
     p.offsets = F.d_offsets.as<float>();
@@ -141,21 +139,11 @@ int arctic_fog(ArcticRenderer *r, const ArcticSettings *settings, const ArcticFo
     if (rc || (rc = fog_states(r, d, hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
     ArcticRenderer::Fog &F = r->fog;
     const size_t px = (size_t)r->rows() * r->width;
-    HIPCHECK(r, F.written.ensure(hipEventDisableTiming));
-    HIPCHECK(r, F.written.wait(r->stream));   // (the copies below overwrite planes the previous call read)
-    if (hdr_rgb32f) {
-        HIPCHECK(r, F.d_color.ensure(std::max<size_t>(px, 1) * 12));
-        HIPCHECK(r, hipMemcpyAsync(F.d_color.p, hdr_rgb32f, px * 12, hipMemcpyHostToDevice, r->stream));
-    }
-    if (depth) {
-        HIPCHECK(r, F.d_depth.ensure(std::max<size_t>(px, 1) * 4));
-        HIPCHECK(r, hipMemcpyAsync(F.d_depth.p, depth, px * 4, hipMemcpyHostToDevice, r->stream));
-    }
+    if (hdr_rgb32f && (rc = upload_plane(r, F.written, F.d_color, hdr_rgb32f, px, 12)) != ARCTIC_OK) return rc;
+    if (depth && (rc = upload_plane(r, F.written, F.d_depth, depth, px, 4)) != ARCTIC_OK) return rc;
     if ((rc = fog_planes(r, settings, d, v, offsets16, hdr_rgb32f ? F.d_color.as<float>() : nullptr, depth ? F.d_depth.as<float>() : nullptr, nullptr, nullptr)) != ARCTIC_OK) return rc;
     if (out_hdr_rgb32f) HIPCHECK(r, hipMemcpyAsync(out_hdr_rgb32f, F.d_hdr.p, px * 12, hipMemcpyDeviceToHost, r->stream));
-    if (out_rgba8) HIPCHECK(r, hipMemcpyAsync(out_rgba8, F.d_rgba8.p, px * 4, hipMemcpyDeviceToHost, r->stream));
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    return hdr_rgb32f ? ARCTIC_OK : check_item_overflow(r);
+    return read_back(r, out_rgba8, F.d_rgba8, px * 4, hdr_rgb32f == nullptr);
 }
 
 int arctic_pass_fog(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticFog *fog, const float *offsets16, uint8_t *d_out_rgba8) {
@@ -182,7 +170,7 @@ int arctic_pass_fog(ArcticRenderer *r, const ArcticScene *scene, const ArcticSet
 int arctic_read_fog(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8) {
     if (!r) return ARCTIC_E_INVALID;
     const ArcticRenderer::Fog &F = r->fog;
-    if (!F.valid || F.width != r->width || F.height != r->height || r->rows() != r->height)
+    if (!F.holds(*r) || r->rows() != r->height)
         return r->fail(ARCTIC_E_STATE, "read_fog: no fog yet, or not since the last resize");
     if (hdr_rgb && !F.own_hdr) return r->fail(ARCTIC_E_STATE, "read_fog: the latest call wrote the caller's HDR plane, not the handle's");
     if (rgba8 && !F.own_rgba8) return r->fail(ARCTIC_E_STATE, "read_fog: the latest call wrote the caller's RGBA8 buffer, not the handle's");

@@ -1,11 +1,13 @@
 // ray_calls.cpp -- the ray family of the C-ABI (include/arctic_hip.h): ray queries, refit and re-split of their structure, sun visibility, ambient
 // occlusion and its temporal accumulation, hit attributes, hit shading, the reflection plane, the composition of the two planes into the shaded frame,
-// the motion vectors, the temporal anti-aliasing resolve that reads them, the motion blur, and depth of field.
+// and the motion vectors with the accumulation that uses them.  The post stages that read these planes are units of their own (renderer_state.h).
 //
-// Owns, of the handle (renderer_state.h): ArcticRenderer::RayScene, AmbientOcclusion, AoHistory, HitScene, Compose, Motion, Taa, MotionBlur and Dof -- nothing outside this unit touches
-// them but arctic_set_option, which writes RayScene::refit_opt, run_geometry, which reads Taa::jitter, and a resize, which empties the histories.  Reads, of the handle's other state: the G-buffer planes (resolved here from the visibility
-// plane when a frame was shaded from it), the shadow map, the lights, the textures, the environment, the meshes and -- the composition -- the float
-// HDR plane of the latest shading.  Enqueues on r->stream only.
+// Owns, of the handle (renderer_state.h): ArcticRenderer::RayScene, AmbientOcclusion, AoHistory, HitScene, Compose and Motion -- nothing outside this
+// unit touches them but arctic_set_option, which writes RayScene::refit_opt, a resize, which empties the histories, the post stages' one calls,
+// which make the motion call through motion_refusal and motion_planes into Motion::d_plane, and post_source.cpp, which reads Compose's HDR plane.
+// Reads, of the handle's other state: the G-buffer planes (resolved here from the visibility plane when a frame was shaded from it), the shadow
+// map, the lights, the textures, the environment, the meshes and -- the composition -- the float HDR plane of the latest shading.  Enqueues on
+// r->stream only.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -18,9 +20,6 @@
 #include "compose.h"
 #include "ao_history.h"
 #include "motion.h"
-#include "taa.h"
-#include "motion_blur.h"
-#include "dof.h"
 
 namespace {
 
@@ -32,15 +31,6 @@ int gbuffer_refusal(ArcticRenderer *r, const char *who) {
 }
 // ... and gbuffer_in_place, behind it: the planes are resolved now when the frame was shaded from the visibility plane
 int gbuffer_in_place(ArcticRenderer *r) { return r->have_gbuffer ? ARCTIC_OK : resolve_gbuffer(r); }
-
-// The host forms' tail: the result to the caller's memory, then the stream is drained.  FROM_FRAME: the result was made from the G-buffer of a
-// frame, so the call also reports a rasteriser table that overflowed under that frame (check_item_overflow)
-constexpr bool FROM_FRAME = true;
-int read_back(ArcticRenderer *r, void *out, const DevBuf &d, size_t bytes, bool from_frame = false) {
-    HIPCHECK(r, hipMemcpyAsync(out, d.p, bytes, hipMemcpyDeviceToHost, r->stream));
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    return from_frame ? check_item_overflow(r) : ARCTIC_OK;
-}
 
 }  // namespace
 
@@ -525,9 +515,7 @@ int compose_checks(ArcticRenderer *r, const ArcticScene *sc, const ArcticSetting
 int compose_states(ArcticRenderer *r, const ComposeDesc &d, const char *who) {
     int rc = gbuffer_refusal(r, who);
     if (rc) return rc;
-    if (!r->keep_float) return r->fail(ARCTIC_E_STATE, "%s: the float HDR plane needs ARCTIC_OPT_KEEP_FLOAT_OUTPUT", who);
-    if (!r->hdr_valid) return r->fail(ARCTIC_E_STATE, "%s: nothing shaded since ARCTIC_OPT_KEEP_FLOAT_OUTPUT was turned on or since the last resize (arctic_pass_shade or a frame first)", who);
-    if (r->hdr16) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_OPT_HDR16 = 1: the HDR plane is rounded through binary16", who);
+    if ((rc = source_refusal(r, {HdrSource::Shaded, ""}, who)) != ARCTIC_OK) return rc;   // (the float HDR plane of the latest shading: post_source.cpp)
     if (d.flags & COMPOSE_AO) {
         const char *why = r->env_lighting == 1 ? "ARCTIC_OPT_ENV_LIGHTING is on" : r->texture_mips == 1 ? "ARCTIC_OPT_TEXTURE_MIPS = 1" : r->has_extras() ? "a material is not neutral (arctic_set_material_extras)" : nullptr;
         if (why) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_COMPOSE_AO: %s, so the frame's ambient term is not ambient * base_color at level 0", who, why);
@@ -760,7 +748,8 @@ int arctic_pass_ray_effects_temporal(ArcticRenderer *r, const ArcticScene *scene
 }
 
 // ---- motion vectors and the accumulation that uses them (the definition: include/arctic_hip.h; the arithmetic: motion.h; the kernels: motion.hip) ---
-namespace {
+}  // extern "C"
+namespace arctic {   // (renderer_state.h: arctic_pass_taa and arctic_pass_motion_blur call these)
 // what the motion calls refuse, in the header's order: no side effect
 int motion_refusal(ArcticRenderer *r, const ArcticScene *sc, const void *prev_world4, const char *who) {
     if (!valid_scene(sc) || !prev_world4) return r->fail(ARCTIC_E_INVALID, "%s: null scene or prev_world4 plane", who);
@@ -851,7 +840,8 @@ int motion_planes(ArcticRenderer *r, const ArcticScene *sc, float4 *d_pw, float2
     ++M.calls;
     return ARCTIC_OK;
 }
-}  // namespace
+}  // namespace arctic
+extern "C" {
 
 int arctic_motion_vectors_device(ArcticRenderer *r, const ArcticScene *scene, float *d_prev_world4, float *d_velocity2) {
     if (!r) return ARCTIC_E_INVALID;
@@ -957,508 +947,6 @@ int arctic_pass_ray_effects_motion(ArcticRenderer *r, const ArcticScene *scene, 
     if ((d.flags & COMPOSE_REFLECTIONS) && (rc = trace_reflections(r, scene, d.reflection_bias, nullptr, who)) != ARCTIC_OK) return rc;
     if ((rc = compose_planes(r, scene, settings, d, r->ao.d_out.as<uint8_t>(), r->hit.d_color.as<float>(), d_out_rgba8)) != ARCTIC_OK) return rc;
     ++r->compose.passes;
-    return ARCTIC_OK;
-}
-
-// ---- temporal anti-aliasing (the definition: include/arctic_hip.h; the arithmetic: taa.h; the kernel: taa.hip) -----------------------------------
-int arctic_set_camera_jitter(ArcticRenderer *r, float jx, float jy) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!(jx >= -1.0f && jx <= 1.0f && jy >= -1.0f && jy <= 1.0f)) return r->fail(ARCTIC_E_INVALID, "set_camera_jitter: both offsets must be finite and in [-1, 1] pixels");
-    r->taa.jitter[0] = jx; r->taa.jitter[1] = jy;
-    return ARCTIC_OK;
-}
-
-namespace {
-// what the calls refuse with ARCTIC_E_INVALID, in the header's order; color, vel, out: the planes k_taa_resolve will read and write (null: the
-// handle's own, zero, the handle's own); align: whether they are device planes, whose alignment the kernel's loads and stores need
-int taa_checks(ArcticRenderer *r, const ArcticSettings *st, const ArcticTaa *taa, const void *color, const void *vel, const void *out, bool align, TaaDesc &d, const char *who) {
-    if (!st || !taa) return r->fail(ARCTIC_E_INVALID, "%s: null settings or parameters", who);
-    std::memcpy(&d, taa, sizeof d);
-    if (const char *why = taa_refusal(&d)) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
-    if (align && ((((uintptr_t)color | (uintptr_t)out) & 3u) || ((uintptr_t)vel & 7u)))
-        return r->fail(ARCTIC_E_INVALID, "%s: the colour plane and the output must be 4-byte aligned, velocity2 8-byte aligned", who);
-    return ARCTIC_OK;
-}
-// ... and with ARCTIC_E_STATE: no side effect.  own_color: the colour plane is the handle's (d.flags says which)
-int taa_states(ArcticRenderer *r, const TaaDesc &d, bool own_color, const char *who) {
-    if (r->rows() != r->height)
-        return r->fail(ARCTIC_E_STATE, "%s: the history's taps need the whole frame, this handle owns %u of %u rows (its neighbours' rows are on other shards)", who, r->rows(), r->height);
-    if (!own_color) return ARCTIC_OK;
-    if (!r->keep_float) return r->fail(ARCTIC_E_STATE, "%s: the float HDR plane needs ARCTIC_OPT_KEEP_FLOAT_OUTPUT", who);
-    if (!r->hdr_valid) return r->fail(ARCTIC_E_STATE, "%s: nothing shaded since ARCTIC_OPT_KEEP_FLOAT_OUTPUT was turned on or since the last resize (arctic_pass_shade or a frame first)", who);
-    if ((d.flags & TAA_SOURCE_COMPOSED) && (!r->compose.pixels || r->compose.pixels != (uint64_t)r->rows() * r->width))
-        return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_TAA_SOURCE_COMPOSED: nothing composed yet, or not since the last resize", who);
-    if (r->hdr16) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_OPT_HDR16 = 1: the HDR plane is rounded through binary16", who);
-    return ARCTIC_OK;
-}
-// the two sets of T, the handle's buffers and the launch: device pointers throughout.  d_color: null = the handle's own plane, per d.flags;
-// d_vel: null = zero; d_out: the caller's RGBA8, or null = the handle's own.  The handle's state moves only behind a launch that was enqueued
-int taa_planes(ArcticRenderer *r, const ArcticSettings *st, const TaaDesc &d, const float *d_color, const void *d_vel, uint8_t *d_out) {
-    ArcticRenderer::Taa &T = r->taa;
-    const uint64_t n = (uint64_t)r->rows() * r->width;
-    const size_t plane = std::max<size_t>(r->n_tiles(), 1) * TILE_PIXELS * 16;
-    for (DevBuf *b : {&T.d_t[0], &T.d_t[1]})
-        if (b->cap < plane) HIPCHECK(r, b->alloc_exact(plane));   // (no headroom: the two sets are 32 bytes per pixel as the header says)
-    if (!d_out) HIPCHECK(r, T.d_rgba8.ensure(std::max<uint64_t>(n, 1) * 4));
-    HIPCHECK(r, T.d_ldr.ensure(std::max<uint64_t>(n, 1) * 12));
-    HIPCHECK(r, T.written.ensure(hipEventDisableTiming));
-    HIPCHECK(r, T.written.wait(r->stream));   // (recorded on another stream: arctic_set_stream came in between; on this one: stream order does it)
-    const bool have = T.valid && T.width == r->width && T.height == r->height;
-    const int from = T.cur, to = T.cur ^ 1;
-    TaaParams p = {};
-    p.color = d_color ? d_color : (d.flags & TAA_SOURCE_COMPOSED) ? r->compose.d_hdr.as<float>() : r->d_hdr.as<float>();
-    p.velocity = d_vel;
-    p.prev = have ? T.d_t[from].p : nullptr; p.next = T.d_t[to].p;
-    p.out_rgba8 = reinterpret_cast<uint32_t *>(d_out ? d_out : T.d_rgba8.as<uint8_t>()); p.out_ldr = T.d_ldr.as<float>();
-    p.tiles_x = r->tiles_x; p.tiles_y = r->tiles_y; p.width = r->width; p.rows = r->rows();
-    p.tm = st->tm_method; p.inv_gamma = 1.0f / st->gamma; p.exposure = st->exposure;
-    p.d = d;
-    HIPCHECK(r, launch_taa_resolve(p, r->stream));
-    HIPCHECK(r, T.written.record(r->stream));
-    T.cur = to; T.valid = true; T.width = r->width; T.height = r->height; T.own_rgba8 = d_out == nullptr;
-    T.by_pass = false;   // (arctic_pass_taa sets it behind this)
-    ++T.launches; ++T.calls;
-    return ARCTIC_OK;
-}
-}  // namespace
-
-int arctic_taa_resolve_device(ArcticRenderer *r, const ArcticSettings *settings, const ArcticTaa *taa, const float *d_hdr_rgb32f, const float *d_velocity2, uint8_t *d_out_rgba8) {
-    if (!r) return ARCTIC_E_INVALID;
-    const char *who = "taa_resolve_device";
-    TaaDesc d;
-    int rc = taa_checks(r, settings, taa, d_hdr_rgb32f, d_velocity2, d_out_rgba8, true, d, who);
-    if (rc || (rc = taa_states(r, d, d_hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
-    return taa_planes(r, settings, d, d_hdr_rgb32f, d_velocity2, d_out_rgba8);
-}
-
-int arctic_taa_resolve(ArcticRenderer *r, const ArcticSettings *settings, const ArcticTaa *taa, const float *hdr_rgb32f, const float *velocity2, uint8_t *out_rgba8) {
-    if (!r) return ARCTIC_E_INVALID;
-    const char *who = "taa_resolve";
-    TaaDesc d;
-    int rc = taa_checks(r, settings, taa, hdr_rgb32f, velocity2, out_rgba8, false, d, who);
-    if (rc || (rc = taa_states(r, d, hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
-    ArcticRenderer::Taa &T = r->taa;
-    const size_t px = (size_t)r->rows() * r->width;
-    if (hdr_rgb32f) {
-        HIPCHECK(r, T.d_color.ensure(std::max<size_t>(px, 1) * 12));
-        HIPCHECK(r, hipMemcpyAsync(T.d_color.p, hdr_rgb32f, px * 12, hipMemcpyHostToDevice, r->stream));
-    }
-    if (velocity2) {
-        HIPCHECK(r, T.d_vel.ensure(std::max<size_t>(px, 1) * 8));
-        HIPCHECK(r, hipMemcpyAsync(T.d_vel.p, velocity2, px * 8, hipMemcpyHostToDevice, r->stream));
-    }
-    if ((rc = taa_planes(r, settings, d, hdr_rgb32f ? T.d_color.as<float>() : nullptr, velocity2 ? T.d_vel.p : nullptr, nullptr)) != ARCTIC_OK) return rc;
-    if (out_rgba8) return read_back(r, out_rgba8, T.d_rgba8, px * 4, hdr_rgb32f == nullptr);
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    return hdr_rgb32f ? ARCTIC_OK : check_item_overflow(r);
-}
-
-int arctic_pass_taa(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticTaa *taa, uint8_t *d_out_rgba8) {
-    if (!r) return ARCTIC_E_INVALID;
-    const char *who = "pass_taa";
-    alignas(16) static const char own_plane[16] = {};   // (the planes are the handle's own: never null, always aligned)
-    TaaDesc d;
-    int rc = taa_checks(r, settings, taa, nullptr, nullptr, d_out_rgba8, true, d, who);
-    // every refusal of the motion call, in front of the first launch (the call below makes them again, to no effect)
-    if (rc || (rc = motion_refusal(r, scene, own_plane, who)) != ARCTIC_OK || (rc = taa_states(r, d, true, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
-    const size_t px = std::max<size_t>((size_t)r->rows() * r->width, 1);
-    HIPCHECK(r, r->motion.d_plane.ensure(px * 16));
-    HIPCHECK(r, r->taa.d_vel.ensure(px * 8));
-    if ((rc = motion_planes(r, scene, r->motion.d_plane.as<float4>(), r->taa.d_vel.as<float2>(), nullptr, nullptr)) != ARCTIC_OK) return rc;
-    if ((rc = taa_planes(r, settings, d, nullptr, r->taa.d_vel.p, d_out_rgba8)) != ARCTIC_OK) return rc;
-    r->taa.by_pass = true;   // (Taa::d_vel is this frame's velocity2: arctic_pass_motion_blur under ARCTIC_MB_SOURCE_TAA reads it)
-    return ARCTIC_OK;
-}
-
-int arctic_taa_reset(ArcticRenderer *r) {
-    if (!r) return ARCTIC_E_INVALID;
-    r->taa.valid = false;   // (the planes stay: a call in flight may still write them, and the next call reuses them)
-    r->taa.calls = 0;
-    return ARCTIC_OK;
-}
-
-int arctic_read_taa(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, float *count, uint8_t *rgba8) {
-    if (!r) return ARCTIC_E_INVALID;
-    const ArcticRenderer::Taa &T = r->taa;
-    if (!T.valid || T.width != r->width || T.height != r->height || r->rows() != r->height)
-        return r->fail(ARCTIC_E_STATE, "read_taa: T is empty (no call yet, or none since the last reset or resize)");
-    if (rgba8 && !T.own_rgba8) return r->fail(ARCTIC_E_STATE, "read_taa: the latest resolve wrote the caller's RGBA8 buffer, not the handle's");
-    int rc = select_device(r);
-    if (rc) return rc;
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    const size_t px = (size_t)r->rows() * r->width;
-    if (ldr_rgb) HIPCHECK(r, hipMemcpy(ldr_rgb, T.d_ldr.p, px * 12, hipMemcpyDeviceToHost));
-    if (rgba8) HIPCHECK(r, hipMemcpy(rgba8, T.d_rgba8.p, px * 4, hipMemcpyDeviceToHost));
-    if (hdr_rgb || count) {
-        const size_t n = r->n_tiles() * TILE_PIXELS;
-        std::vector<float> t(n * 4);
-        HIPCHECK(r, hipMemcpy(t.data(), T.d_t[T.cur].p, n * 16, hipMemcpyDeviceToHost));
-        for (uint32_t y = 0; y < r->height; ++y)
-            for (uint32_t x = 0; x < r->width; ++x) {
-                const size_t q = ((size_t)(y / TILE) * r->tiles_x + x / TILE) * TILE_PIXELS + (y % TILE) * TILE + x % TILE, o = (size_t)y * r->width + x;
-                if (count) count[o] = t[4 * q + 3];
-                if (hdr_rgb) for (int i = 0; i < 3; ++i) hdr_rgb[3 * o + i] = t[4 * q + i];
-            }
-    }
-    return ARCTIC_OK;
-}
-
-int arctic_taa_info(ArcticRenderer *r, uint64_t *out4) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!out4) return r->fail(ARCTIC_E_INVALID, "taa_info: null");
-    out4[0] = r->taa.device_bytes(); out4[1] = r->taa.launches; out4[2] = r->taa.calls; out4[3] = 0;
-    return ARCTIC_OK;
-}
-
-// ---- motion blur (the definition: include/arctic_hip.h; the arithmetic: motion_blur.h; the kernels: motion_blur.hip) ------------------------------
-namespace {
-// what the calls refuse with ARCTIC_E_INVALID, in the header's order; color, vel, depth, out: the planes the kernels will read and write (null
-// colour, depth, output: the handle's own, zero, the handle's own); align: whether they are device planes, whose alignment the loads and stores need
-int mb_checks(ArcticRenderer *r, const ArcticSettings *st, const ArcticMotionBlur *mb, const void *color, const void *vel, const void *depth, const void *out, bool align,
-              MotionBlurDesc &d, const char *who) {
-    if (!st || !mb) return r->fail(ARCTIC_E_INVALID, "%s: null settings or parameters", who);
-    std::memcpy(&d, mb, sizeof d);
-    if (const char *why = motion_blur_refusal(&d)) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
-    if (!vel) return r->fail(ARCTIC_E_INVALID, "%s: null velocity2", who);
-    if (align && ((((uintptr_t)color | (uintptr_t)depth | (uintptr_t)out) & 3u) || ((uintptr_t)vel & 7u)))
-        return r->fail(ARCTIC_E_INVALID, "%s: the colour plane, the depth and the output must be 4-byte aligned, velocity2 8-byte aligned", who);
-    return ARCTIC_OK;
-}
-// T is not empty: arctic_read_taa's condition
-bool taa_holds_a_frame(const ArcticRenderer *r) { return r->taa.valid && r->taa.width == r->width && r->taa.height == r->height; }
-// ... and with ARCTIC_E_STATE: no side effect.  own_color: the colour plane is the handle's (d.flags says which)
-int mb_states(ArcticRenderer *r, const MotionBlurDesc &d, bool own_color, const char *who) {
-    if (r->rows() != r->height)
-        return r->fail(ARCTIC_E_STATE, "%s: the gather's taps need the whole frame, this handle owns %u of %u rows (its neighbours' rows are on other shards)", who, r->rows(), r->height);
-    if (!own_color) return ARCTIC_OK;
-    if (d.flags & MB_SOURCE_TAA) {
-        if (!taa_holds_a_frame(r)) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_MB_SOURCE_TAA: the anti-aliasing's history is empty (no resolve yet, or none since the last reset or resize)", who);
-        return ARCTIC_OK;
-    }
-    TaaDesc t = {};
-    t.flags = (d.flags & MB_SOURCE_COMPOSED) ? TAA_SOURCE_COMPOSED : 0u;
-    return taa_states(r, t, true, who);
-}
-// the handle's buffers and the three launches: device pointers throughout.  d_color: null = the handle's own plane, per d.flags; d_depth: null =
-// zero; d_out: the caller's RGBA8, or null = the handle's own.  The handle's state moves only behind launches that were enqueued
-int mb_planes(ArcticRenderer *r, const ArcticSettings *st, const MotionBlurDesc &d, const float *d_color, const void *d_vel, const float *d_depth, uint8_t *d_out) {
-    ArcticRenderer::MotionBlur &B = r->motion_blur;
-    const uint64_t n = std::max<uint64_t>((uint64_t)r->rows() * r->width, 1), tiles = std::max<uint64_t>(r->n_tiles(), 1);
-    HIPCHECK(r, B.d_prep.ensure(n * 8));
-    HIPCHECK(r, B.d_tile.ensure(tiles * 8));
-    HIPCHECK(r, B.d_neighbour.ensure(tiles * 8));
-    HIPCHECK(r, B.d_hdr.ensure(n * 12));
-    if (!d_out) HIPCHECK(r, B.d_rgba8.ensure(n * 4));
-    HIPCHECK(r, B.d_ldr.ensure(n * 12));
-    HIPCHECK(r, B.written.ensure(hipEventDisableTiming));
-    HIPCHECK(r, B.written.wait(r->stream));   // (recorded on another stream: arctic_set_stream came in between; on this one: stream order does it)
-    MotionBlurParams p = {};
-    if (d_color) p.color = d_color;
-    else if (d.flags & MB_SOURCE_TAA) {
-        HIPCHECK(r, r->taa.written.wait(r->stream));   // (the resolve that wrote T, if the stream has changed since)
-        p.color = r->taa.d_t[r->taa.cur].p; p.color_taa = true;
-    } else p.color = (d.flags & MB_SOURCE_COMPOSED) ? r->compose.d_hdr.as<float>() : r->d_hdr.as<float>();
-    p.velocity = d_vel; p.depth = d_depth;
-    p.prep = B.d_prep.p; p.tile_max = B.d_tile.p; p.neighbour_max = B.d_neighbour.p;
-    p.out_hdr = B.d_hdr.as<float>(); p.out_rgba8 = reinterpret_cast<uint32_t *>(d_out ? d_out : B.d_rgba8.as<uint8_t>()); p.out_ldr = B.d_ldr.as<float>();
-    p.tiles_x = r->tiles_x; p.tiles_y = r->tiles_y; p.width = r->width; p.rows = r->rows();
-    p.tm = st->tm_method; p.inv_gamma = 1.0f / st->gamma; p.exposure = st->exposure;
-    p.d = d;
-    B.valid = false;   // (until all three are enqueued: a failure between leaves nothing to read, never half this call's)
-    HIPCHECK(r, launch_mb_tile_max(p, r->stream));
-    HIPCHECK(r, launch_mb_neighbour_max(p, r->stream));
-    HIPCHECK(r, launch_motion_blur(p, r->stream));
-    HIPCHECK(r, B.written.record(r->stream));
-    B.valid = true; B.width = r->width; B.height = r->height; B.own_rgba8 = d_out == nullptr;
-    ++B.launches; ++B.calls;
-    return ARCTIC_OK;
-}
-// arctic_depth_plane_device behind its refusals
-int mb_depth_plane(ArcticRenderer *r, float *d_depth) {
-    HIPCHECK(r, launch_mb_depth(r->d_vis().as<unsigned long long>(), d_depth, r->tiles_x, r->tiles_y, r->width, r->rows(), r->row0_in_tile, r->stream));
-    return ARCTIC_OK;
-}
-}  // namespace
-
-int arctic_motion_blur_device(ArcticRenderer *r, const ArcticSettings *settings, const ArcticMotionBlur *mb, const float *d_hdr_rgb32f, const float *d_velocity2,
-                              const float *d_depth, uint8_t *d_out_rgba8) {
-    if (!r) return ARCTIC_E_INVALID;
-    const char *who = "motion_blur_device";
-    MotionBlurDesc d;
-    int rc = mb_checks(r, settings, mb, d_hdr_rgb32f, d_velocity2, d_depth, d_out_rgba8, true, d, who);
-    if (rc || (rc = mb_states(r, d, d_hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
-    return mb_planes(r, settings, d, d_hdr_rgb32f, d_velocity2, d_depth, d_out_rgba8);
-}
-
-int arctic_motion_blur(ArcticRenderer *r, const ArcticSettings *settings, const ArcticMotionBlur *mb, const float *hdr_rgb32f, const float *velocity2, const float *depth,
-                       uint8_t *out_rgba8) {
-    if (!r) return ARCTIC_E_INVALID;
-    const char *who = "motion_blur";
-    MotionBlurDesc d;
-    int rc = mb_checks(r, settings, mb, hdr_rgb32f, velocity2, depth, out_rgba8, false, d, who);
-    if (rc || (rc = mb_states(r, d, hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
-    ArcticRenderer::MotionBlur &B = r->motion_blur;
-    const size_t px = (size_t)r->rows() * r->width;
-    HIPCHECK(r, B.written.ensure(hipEventDisableTiming));
-    HIPCHECK(r, B.written.wait(r->stream));   // (the copies below overwrite planes the previous call read)
-    if (hdr_rgb32f) {
-        HIPCHECK(r, B.d_color.ensure(std::max<size_t>(px, 1) * 12));
-        HIPCHECK(r, hipMemcpyAsync(B.d_color.p, hdr_rgb32f, px * 12, hipMemcpyHostToDevice, r->stream));
-    }
-    HIPCHECK(r, B.d_vel.ensure(std::max<size_t>(px, 1) * 8));
-    HIPCHECK(r, hipMemcpyAsync(B.d_vel.p, velocity2, px * 8, hipMemcpyHostToDevice, r->stream));
-    if (depth) {
-        HIPCHECK(r, B.d_depth.ensure(std::max<size_t>(px, 1) * 4));
-        HIPCHECK(r, hipMemcpyAsync(B.d_depth.p, depth, px * 4, hipMemcpyHostToDevice, r->stream));
-    }
-    if ((rc = mb_planes(r, settings, d, hdr_rgb32f ? B.d_color.as<float>() : nullptr, B.d_vel.p, depth ? B.d_depth.as<float>() : nullptr, nullptr)) != ARCTIC_OK) return rc;
-    if (out_rgba8) return read_back(r, out_rgba8, B.d_rgba8, px * 4, hdr_rgb32f == nullptr);
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    return hdr_rgb32f ? ARCTIC_OK : check_item_overflow(r);
-}
-
-int arctic_depth_plane_device(ArcticRenderer *r, float *d_depth) {
-    if (!r) return ARCTIC_E_INVALID;
-    const char *who = "depth_plane_device";
-    if (!d_depth || ((uintptr_t)d_depth & 3u)) return r->fail(ARCTIC_E_INVALID, "%s: the plane is null or not 4-byte aligned", who);
-    if (!r->have_vis) return r->fail(ARCTIC_E_STATE, "%s: no visibility plane (arctic_pass_gbuffer or a frame first; arctic_write_gbuffer leaves none)", who);
-    int rc = select_device(r);
-    if (rc) return rc;
-    return mb_depth_plane(r, d_depth);
-}
-
-int arctic_pass_motion_blur(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticMotionBlur *mb, uint8_t *d_out_rgba8) {
-    if (!r) return ARCTIC_E_INVALID;
-    const char *who = "pass_motion_blur";
-    alignas(16) static const char own_plane[16] = {};   // (the planes are the handle's own: never null, always aligned)
-    MotionBlurDesc d;
-    int rc = mb_checks(r, settings, mb, nullptr, own_plane, nullptr, d_out_rgba8, true, d, who);
-    // every refusal of the motion call and of the depth plane, in front of the first launch
-    if (rc || (rc = motion_refusal(r, scene, own_plane, who)) != ARCTIC_OK || (rc = mb_states(r, d, true, who)) != ARCTIC_OK) return rc;
-    const bool from_taa = (d.flags & MB_SOURCE_TAA) != 0;
-    if (from_taa && !r->taa.by_pass)
-        return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_MB_SOURCE_TAA: the handle's latest anti-aliasing call was not arctic_pass_taa, so it holds no velocity2 of this frame", who);
-    if ((rc = select_device(r)) != ARCTIC_OK) return rc;
-    ArcticRenderer::MotionBlur &B = r->motion_blur;
-    const size_t px = std::max<size_t>((size_t)r->rows() * r->width, 1);
-    HIPCHECK(r, B.written.ensure(hipEventDisableTiming));
-    HIPCHECK(r, B.written.wait(r->stream));   // (the motion call and the depth below overwrite planes the previous call read)
-    HIPCHECK(r, B.d_depth.ensure(px * 4));
-    const void *d_vel = r->taa.d_vel.p;
-    if (!from_taa) {
-        HIPCHECK(r, r->motion.d_plane.ensure(px * 16));
-        HIPCHECK(r, B.d_vel.ensure(px * 8));
-        if ((rc = motion_planes(r, scene, r->motion.d_plane.as<float4>(), B.d_vel.as<float2>(), nullptr, nullptr)) != ARCTIC_OK) return rc;
-        d_vel = B.d_vel.p;
-    }
-    if ((rc = mb_depth_plane(r, B.d_depth.as<float>())) != ARCTIC_OK) return rc;
-    return mb_planes(r, settings, d, nullptr, d_vel, B.d_depth.as<float>(), d_out_rgba8);
-}
-
-int arctic_read_motion_blur(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, float *tile_max2, float *neighbour_max2, float *prepared2) {
-    if (!r) return ARCTIC_E_INVALID;
-    const ArcticRenderer::MotionBlur &B = r->motion_blur;
-    if (!B.valid || B.width != r->width || B.height != r->height || r->rows() != r->height)
-        return r->fail(ARCTIC_E_STATE, "read_motion_blur: nothing blurred yet, or not since the last resize");
-    if (rgba8 && !B.own_rgba8) return r->fail(ARCTIC_E_STATE, "read_motion_blur: the latest call wrote the caller's RGBA8 buffer, not the handle's");
-    int rc = select_device(r);
-    if (rc) return rc;
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    const size_t px = (size_t)r->rows() * r->width, tiles = r->n_tiles();
-    if (ldr_rgb) HIPCHECK(r, hipMemcpy(ldr_rgb, B.d_ldr.p, px * 12, hipMemcpyDeviceToHost));
-    if (hdr_rgb) HIPCHECK(r, hipMemcpy(hdr_rgb, B.d_hdr.p, px * 12, hipMemcpyDeviceToHost));
-    if (rgba8) HIPCHECK(r, hipMemcpy(rgba8, B.d_rgba8.p, px * 4, hipMemcpyDeviceToHost));
-    if (tile_max2) HIPCHECK(r, hipMemcpy(tile_max2, B.d_tile.p, tiles * 8, hipMemcpyDeviceToHost));
-    if (neighbour_max2) HIPCHECK(r, hipMemcpy(neighbour_max2, B.d_neighbour.p, tiles * 8, hipMemcpyDeviceToHost));
-    if (prepared2) HIPCHECK(r, hipMemcpy(prepared2, B.d_prep.p, px * 8, hipMemcpyDeviceToHost));
-    return ARCTIC_OK;
-}
-
-int arctic_motion_blur_info(ArcticRenderer *r, uint64_t *out4) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!out4) return r->fail(ARCTIC_E_INVALID, "motion_blur_info: null");
-    out4[0] = r->motion_blur.device_bytes(); out4[1] = r->motion_blur.launches; out4[2] = r->motion_blur.calls; out4[3] = 0;
-    return ARCTIC_OK;
-}
-
-// ---- depth of field (the definition: include/arctic_hip.h; the arithmetic: dof.h; the kernels: dof.hip) ----------------------------------------------
-namespace {
-// what the calls refuse with ARCTIC_E_INVALID, in the header's order; color, depth, out: the planes the kernels will read and write (null colour,
-// output: the handle's own); align: whether they are device planes, whose alignment the loads and stores need; zero_planes: arctic_pass_dof's block
-int dof_checks(ArcticRenderer *r, const ArcticSettings *st, const ArcticDof *dof, const void *color, const void *depth, const float *taps2, const void *out, bool align,
-               bool zero_planes, DofDesc &d, const char *who) {
-    if (!st || !dof) return r->fail(ARCTIC_E_INVALID, "%s: null settings or parameters", who);
-    std::memcpy(&d, dof, sizeof d);
-    if (const char *why = dof_refusal(&d, zero_planes)) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
-    if (!depth) return r->fail(ARCTIC_E_INVALID, "%s: null depth", who);
-    if (const char *why = dof_taps_refusal(&d, taps2)) return r->fail(ARCTIC_E_INVALID, "%s: %s", who, why);
-    if (align && (((uintptr_t)color | (uintptr_t)depth | (uintptr_t)out) & 3u))
-        return r->fail(ARCTIC_E_INVALID, "%s: the colour plane, the depth and the output must be 4-byte aligned", who);
-    return ARCTIC_OK;
-}
-// ... and with ARCTIC_E_STATE: no side effect.  own_color: the colour plane is the handle's (d.flags says which)
-int dof_states(ArcticRenderer *r, const DofDesc &d, bool own_color, const char *who) {
-    if (r->rows() != r->height)
-        return r->fail(ARCTIC_E_STATE, "%s: the gather's taps need the whole frame, this handle owns %u of %u rows (its neighbours' rows are on other shards)", who, r->rows(), r->height);
-    if (!own_color) return ARCTIC_OK;
-    if (d.flags & DOF_SOURCE_MOTION_BLUR) {
-        const ArcticRenderer::MotionBlur &B = r->motion_blur;
-        if (!B.valid || B.width != r->width || B.height != r->height)
-            return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_DOF_SOURCE_MOTION_BLUR: nothing blurred yet, or not since the last resize", who);
-        return ARCTIC_OK;
-    }
-    MotionBlurDesc m = {};
-    m.flags = (d.flags & DOF_SOURCE_TAA) ? MB_SOURCE_TAA : (d.flags & DOF_SOURCE_COMPOSED) ? MB_SOURCE_COMPOSED : 0u;
-    return mb_states(r, m, true, who);
-}
-// the handle's buffers, the tap table and the three launches: device pointers throughout but taps2.  d_color: null = the handle's own plane, per
-// d.flags; d_out: the caller's RGBA8, or null = the handle's own.  The handle's state moves only behind launches that were enqueued
-int dof_planes(ArcticRenderer *r, const ArcticSettings *st, const DofDesc &d, const float *d_color, const float *d_depth, const float *taps2, uint8_t *d_out) {
-    ArcticRenderer::Dof &D = r->dof;
-    const uint64_t n = std::max<uint64_t>((uint64_t)r->rows() * r->width, 1), tiles = std::max<uint64_t>(r->n_tiles(), 1);
-    const size_t table_bytes = DOF_MAX_SAMPLES * 2 * sizeof(float);   // the largest table: the slot and d_taps are made once
-    HIPCHECK(r, D.d_prep.ensure(n * 8));
-    HIPCHECK(r, D.d_tile.ensure(tiles * 4));
-    HIPCHECK(r, D.d_neighbour.ensure(tiles * 4));
-    HIPCHECK(r, D.d_hdr.ensure(n * 12));
-    if (!d_out) HIPCHECK(r, D.d_rgba8.ensure(n * 4));
-    HIPCHECK(r, D.d_ldr.ensure(n * 12));
-    HIPCHECK(r, D.d_taps.ensure(table_bytes));
-    HIPCHECK(r, D.written.ensure(hipEventDisableTiming));
-    HIPCHECK(r, D.written.wait(r->stream));   // (recorded on another stream: arctic_set_stream came in between; on this one: stream order does it)
-    if (D.n_taps != d.samples || std::memcmp(D.taps_ring.slot[0].h.p, taps2, (size_t)d.samples * 8) != 0) {   // (n_taps != 0: an empty D holds no table)
-        float *h_taps = nullptr;
-        HIPCHECK(r, D.taps_ring.stage(table_bytes, &h_taps));
-        D.n_taps = 0;
-        std::memcpy(h_taps, taps2, (size_t)d.samples * 8);
-        HIPCHECK(r, D.taps_ring.send(D.d_taps.p, (size_t)d.samples * 8, r->stream));
-        D.n_taps = d.samples;
-    }
-    DofParams p = {};
-    if (d_color) p.color = d_color;
-    else if (d.flags & DOF_SOURCE_TAA) {
-        HIPCHECK(r, r->taa.written.wait(r->stream));   // (the resolve that wrote T, if the stream has changed since)
-        p.color = r->taa.d_t[r->taa.cur].p; p.color_taa = true;
-    } else if (d.flags & DOF_SOURCE_MOTION_BLUR) {
-        HIPCHECK(r, r->motion_blur.written.wait(r->stream));   // (... the blur, likewise)
-        p.color = r->motion_blur.d_hdr.as<float>();
-    } else p.color = (d.flags & DOF_SOURCE_COMPOSED) ? r->compose.d_hdr.as<float>() : r->d_hdr.as<float>();
-    p.depth = d_depth; p.taps = D.d_taps.as<float>();
-    p.prep = D.d_prep.p; p.tile_max = D.d_tile.as<float>(); p.neighbour_max = D.d_neighbour.as<float>();
-    p.out_hdr = D.d_hdr.as<float>(); p.out_rgba8 = reinterpret_cast<uint32_t *>(d_out ? d_out : D.d_rgba8.as<uint8_t>()); p.out_ldr = D.d_ldr.as<float>();
-    p.tiles_x = r->tiles_x; p.tiles_y = r->tiles_y; p.width = r->width; p.rows = r->rows();
-    p.tm = st->tm_method; p.inv_gamma = 1.0f / st->gamma; p.exposure = st->exposure;
-    p.d = d;
-    D.valid = false;   // (until all three are enqueued: a failure between leaves nothing to read, never half this call's)
-    HIPCHECK(r, launch_dof_prepare(p, r->stream));
-    HIPCHECK(r, launch_dof_neighbour_max(p, r->stream));
-    HIPCHECK(r, launch_dof_gather(p, r->stream));
-    HIPCHECK(r, D.written.record(r->stream));
-    D.valid = true; D.width = r->width; D.height = r->height; D.own_rgba8 = d_out == nullptr;
-    ++D.launches; ++D.calls;
-    return ARCTIC_OK;
-}
-}  // namespace
-
-int arctic_dof_device(ArcticRenderer *r, const ArcticSettings *settings, const ArcticDof *dof, const float *d_hdr_rgb32f, const float *d_depth, const float *taps2,
-                      uint8_t *d_out_rgba8) {
-    if (!r) return ARCTIC_E_INVALID;
-    const char *who = "dof_device";
-    DofDesc d;
-    int rc = dof_checks(r, settings, dof, d_hdr_rgb32f, d_depth, taps2, d_out_rgba8, true, false, d, who);
-    if (rc || (rc = dof_states(r, d, d_hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
-    return dof_planes(r, settings, d, d_hdr_rgb32f, d_depth, taps2, d_out_rgba8);
-}
-
-int arctic_dof(ArcticRenderer *r, const ArcticSettings *settings, const ArcticDof *dof, const float *hdr_rgb32f, const float *depth, const float *taps2, uint8_t *out_rgba8) {
-    if (!r) return ARCTIC_E_INVALID;
-    const char *who = "dof";
-    DofDesc d;
-    int rc = dof_checks(r, settings, dof, hdr_rgb32f, depth, taps2, out_rgba8, false, false, d, who);
-    if (rc || (rc = dof_states(r, d, hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
-    ArcticRenderer::Dof &D = r->dof;
-    const size_t px = (size_t)r->rows() * r->width;
-    HIPCHECK(r, D.written.ensure(hipEventDisableTiming));
-    HIPCHECK(r, D.written.wait(r->stream));   // (the copies below overwrite planes the previous call read)
-    if (hdr_rgb32f) {
-        HIPCHECK(r, D.d_color.ensure(std::max<size_t>(px, 1) * 12));
-        HIPCHECK(r, hipMemcpyAsync(D.d_color.p, hdr_rgb32f, px * 12, hipMemcpyHostToDevice, r->stream));
-    }
-    HIPCHECK(r, D.d_depth.ensure(std::max<size_t>(px, 1) * 4));
-    HIPCHECK(r, hipMemcpyAsync(D.d_depth.p, depth, px * 4, hipMemcpyHostToDevice, r->stream));
-    if ((rc = dof_planes(r, settings, d, hdr_rgb32f ? D.d_color.as<float>() : nullptr, D.d_depth.as<float>(), taps2, nullptr)) != ARCTIC_OK) return rc;
-    if (out_rgba8) return read_back(r, out_rgba8, D.d_rgba8, px * 4, hdr_rgb32f == nullptr);
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    return hdr_rgb32f ? ARCTIC_OK : check_item_overflow(r);
-}
-
-int arctic_pass_dof(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticDof *dof, const float *taps2, uint8_t *d_out_rgba8) {
-    if (!r) return ARCTIC_E_INVALID;
-    const char *who = "pass_dof";
-    alignas(16) static const char own_plane[16] = {};   // (the depth is the handle's own: never null, always aligned)
-    DofDesc d;
-    int rc = dof_checks(r, settings, dof, nullptr, own_plane, taps2, d_out_rgba8, true, true, d, who);
-    if (rc) return rc;
-    if (!valid_scene(scene)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
-    d.z_near = scene->camera.z_near_far[0]; d.z_far = scene->camera.z_near_far[1];
-    if (const char *why = dof_refusal(&d, false)) return r->fail(ARCTIC_E_INVALID, "%s: the scene's camera: %s", who, why);
-    // the depth plane's refusal, in front of the first launch
-    if (!r->have_vis) return r->fail(ARCTIC_E_STATE, "%s: no visibility plane (arctic_pass_gbuffer or a frame first; arctic_write_gbuffer leaves none)", who);
-    if ((rc = dof_states(r, d, true, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
-    ArcticRenderer::Dof &D = r->dof;
-    const size_t px = std::max<size_t>((size_t)r->rows() * r->width, 1);
-    HIPCHECK(r, D.written.ensure(hipEventDisableTiming));
-    HIPCHECK(r, D.written.wait(r->stream));   // (the depth below overwrites a plane the previous call read)
-    HIPCHECK(r, D.d_depth.ensure(px * 4));
-    if ((rc = mb_depth_plane(r, D.d_depth.as<float>())) != ARCTIC_OK) return rc;
-    return dof_planes(r, settings, d, nullptr, D.d_depth.as<float>(), taps2, d_out_rgba8);
-}
-
-int arctic_read_dof(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8, float *tile_max, float *neighbour_max, float *prepared2) {
-    if (!r) return ARCTIC_E_INVALID;
-    const ArcticRenderer::Dof &D = r->dof;
-    if (!D.valid || D.width != r->width || D.height != r->height || r->rows() != r->height)
-        return r->fail(ARCTIC_E_STATE, "read_dof: no depth of field yet, or not since the last resize");
-    if (rgba8 && !D.own_rgba8) return r->fail(ARCTIC_E_STATE, "read_dof: the latest call wrote the caller's RGBA8 buffer, not the handle's");
-    int rc = select_device(r);
-    if (rc) return rc;
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    const size_t px = (size_t)r->rows() * r->width, tiles = r->n_tiles();
-    if (ldr_rgb) HIPCHECK(r, hipMemcpy(ldr_rgb, D.d_ldr.p, px * 12, hipMemcpyDeviceToHost));
-    if (hdr_rgb) HIPCHECK(r, hipMemcpy(hdr_rgb, D.d_hdr.p, px * 12, hipMemcpyDeviceToHost));
-    if (rgba8) HIPCHECK(r, hipMemcpy(rgba8, D.d_rgba8.p, px * 4, hipMemcpyDeviceToHost));
-    if (tile_max) HIPCHECK(r, hipMemcpy(tile_max, D.d_tile.p, tiles * 4, hipMemcpyDeviceToHost));
-    if (neighbour_max) HIPCHECK(r, hipMemcpy(neighbour_max, D.d_neighbour.p, tiles * 4, hipMemcpyDeviceToHost));
-    if (prepared2) HIPCHECK(r, hipMemcpy(prepared2, D.d_prep.p, px * 8, hipMemcpyDeviceToHost));
-    return ARCTIC_OK;
-}
-
-int arctic_dof_info(ArcticRenderer *r, uint64_t *out4) {
-    if (!r) return ARCTIC_E_INVALID;
-    if (!out4) return r->fail(ARCTIC_E_INVALID, "dof_info: null");
-    out4[0] = r->dof.device_bytes(); out4[1] = r->dof.launches; out4[2] = r->dof.calls; out4[3] = 0;
-    return ARCTIC_OK;
-}
-
-int arctic_dof_focus_at(ArcticRenderer *r, float z_near, float z_far, uint32_t px, uint32_t py, float *distance) {
-    if (!r) return ARCTIC_E_INVALID;
-    const char *who = "dof_focus_at";
-    if (!distance) return r->fail(ARCTIC_E_INVALID, "%s: null distance", who);
-    if (!(z_near > 0.0f) || !(z_far > z_near && rq_finite(z_far))) return r->fail(ARCTIC_E_INVALID, "%s: z_near not above 0, or z_far not finite and above it", who);
-    if (px >= r->width || py >= r->rows()) return r->fail(ARCTIC_E_INVALID, "%s: pixel (%u, %u) is outside the handle's %u x %u pixels", who, px, py, r->width, r->rows());
-    if (!r->have_vis) return r->fail(ARCTIC_E_STATE, "%s: no visibility plane (arctic_pass_gbuffer or a frame first; arctic_write_gbuffer leaves none)", who);
-    int rc = select_device(r);
-    if (rc) return rc;
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    // the plane is tile-major, as k_mb_depth reads it
-    const uint32_t yy = py + r->row0_in_tile;
-    const size_t at = ((size_t)(yy / 8) * r->tiles_x + px / 8) * 64 + (yy % 8) * 8 + px % 8;
-    unsigned long long key = 0;
-    HIPCHECK(r, hipMemcpy(&key, r->d_vis().as<unsigned long long>() + at, sizeof key, hipMemcpyDeviceToHost));
-    uint32_t bits = (uint32_t)(key >> 32);
-    float depth = 1.0f;
-    if (key != ~0ull) std::memcpy(&depth, &bits, sizeof depth);
-    *distance = dof_view_distance_host(z_near, z_far, depth);
     return ARCTIC_OK;
 }
 

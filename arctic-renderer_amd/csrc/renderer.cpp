@@ -1,7 +1,9 @@
 // renderer.cpp -- the C-ABI of include/arctic_hip.h: resource ownership + frame graph on one HIP stream.
 // The units of the C-ABI: renderer.cpp -- create, destroy and resize, streams, resources, the passes and frames, options, the debug read-backs;
-// ray_calls.cpp -- queries, refit and re-split, sun visibility, ambient occlusion, hit attributes and shading, reflections; exchange_calls.cpp --
-// the multi-GPU exchange (include/arctic_dist.h).  The handle they share: renderer_state.h.
+// ray_calls.cpp -- queries, refit and re-split, sun visibility, ambient occlusion, hit attributes and shading, reflections, the composition, the
+// motion vectors; exchange_calls.cpp -- the multi-GPU exchange (include/arctic_dist.h); taa_calls.cpp, motion_blur_calls.cpp, dof_calls.cpp,
+// bloom_calls.cpp, exposure_calls.cpp, fog_calls.cpp, taa_upscale_calls.cpp -- one post stage each; post_source.cpp -- what those stages share.
+// The handle they share: renderer_state.h.
 //
 // Plays the role of Arctic::Renderer::Renderer (reference src/renderer/renderer.{hpp,cpp}) for
 // the hot path only: create_material/create_mesh/update_lights upload resources

@@ -1,6 +1,8 @@
 // renderer_state.h -- the handle of the C-ABI, declared once for the host units that implement it: renderer.cpp (create, destroy and resize,
-// streams, resources, the passes and frames, options, the debug read-backs), ray_calls.cpp (the ray family and the composition) and exchange_calls.cpp (the
-// multi-GPU exchange).  Also the few helpers one of those units defines and another calls.  Host only.
+// streams, resources, the passes and frames, options, the debug read-backs), ray_calls.cpp (the ray family, the composition, the motion vectors),
+// exchange_calls.cpp (the multi-GPU exchange), one unit per post stage -- taa_calls.cpp, motion_blur_calls.cpp, dof_calls.cpp, bloom_calls.cpp,
+// exposure_calls.cpp, fog_calls.cpp, taa_upscale_calls.cpp -- and post_source.cpp (what those stages' calls share).  Also the few helpers one of
+// those units defines and another calls.  Host only.
 #pragma once
 #include <algorithm>
 #include <cstdarg>
@@ -442,6 +444,7 @@ struct ArcticRenderer {
         StreamMark written;
         uint64_t launches = 0, calls = 0;
         size_t device_bytes() const { return d_t[0].cap + d_t[1].cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_vel.cap; }
+        bool holds(const ArcticRenderer &r) const { return valid && width == r.width && height == r.height; }   // the stage holds a result of the handle's frame size: the one spelling, on every stage below
     } taa;
     // Motion blur (arctic_motion_blur_device; motion_blur.hip): d_prep is P of include/arctic_hip.h (float2 per pixel, row-major), d_tile and
     // d_neighbour the two maxima (float2 per tile), d_hdr the blurred colour, d_rgba8 and d_ldr its tonemapped planes; d_color, d_vel, d_depth:
@@ -456,6 +459,7 @@ struct ArcticRenderer {
         StreamMark written;
         uint64_t launches = 0, calls = 0;
         size_t device_bytes() const { return d_prep.cap + d_tile.cap + d_neighbour.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_vel.cap + d_depth.cap; }
+        bool holds(const ArcticRenderer &r) const { return valid && width == r.width && height == r.height; }
     } motion_blur;
     // Depth of field (arctic_dof_device; dof.hip): d_prep is P of include/arctic_hip.h (float2 per pixel, row-major), d_tile and d_neighbour
     // the two maxima (one float per tile), d_hdr the gathered colour, d_rgba8 and d_ldr its tonemapped planes; d_color, d_depth: the host
@@ -472,6 +476,7 @@ struct ArcticRenderer {
         StreamMark written;
         uint64_t launches = 0, calls = 0;
         size_t device_bytes() const { return d_prep.cap + d_tile.cap + d_neighbour.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_depth.cap + d_taps.cap; }
+        bool holds(const ArcticRenderer &r) const { return valid && width == r.width && height == r.height; }
     } dof;
     // Bloom (arctic_bloom_device; bloom.hip, owned by bloom_calls.cpp): d_down and d_up are the two pyramids of include/arctic_hip.h as
     // arctic_bloom_layout packs them, sized for 8 levels whatever a call asks for; d_hdr the composite, d_rgba8 and d_ldr its tonemapped planes;
@@ -485,6 +490,7 @@ struct ArcticRenderer {
         StreamMark written;
         uint64_t launches = 0, calls = 0;
         size_t device_bytes() const { return d_down.cap + d_up.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap; }
+        bool holds(const ArcticRenderer &r) const { return valid && width == r.width && height == r.height; }
     } bloom;
     // Auto-exposure (arctic_exposure_device; exposure.hip, owned by exposure_calls.cpp): d_partials is the meter's table T[G][256] of
     // include/arctic_hip.h, d_hist the histogram H, d_state the 32-byte state record; d_hdr the exposed frame, d_rgba8 and d_ldr its tonemapped
@@ -499,6 +505,7 @@ struct ArcticRenderer {
         StreamMark written;
         uint64_t launches = 0, calls = 0, meters = 0;
         size_t device_bytes() const { return d_partials.cap + d_hist.cap + d_state.cap + d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap; }
+        bool holds(const ArcticRenderer &r) const { return valid && width == r.width && height == r.height; }
     } exposure;
     // Volumetric fog (arctic_fog_device; fog.hip, owned by fog_calls.cpp): d_hdr is the fogged colour when the caller passes no HDR plane of its
     // own, d_rgba8 and d_ldr its tonemapped planes; d_color, d_depth: the host form's planes, d_depth also arctic_pass_fog's; d_offsets: the 16
@@ -515,6 +522,7 @@ struct ArcticRenderer {
         StreamMark written;
         uint64_t launches = 0, calls = 0, uploads = 0;
         size_t device_bytes() const { return d_hdr.cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_depth.cap + d_offsets.cap; }
+        bool holds(const ArcticRenderer &r) const { return valid && width == r.width && height == r.height; }
     } fog;
     // Temporal upscaling (arctic_taa_upscale_device; taa_upscale.hip, owned by taa_upscale_calls.cpp): the state U of include/arctic_hip.h -- two
     // sets of one float4 plane {r, g, b, N} per OUTPUT pixel, tile-major in 8 x 8 output tiles: a call reads set `cur` and writes the other,
@@ -531,6 +539,7 @@ struct ArcticRenderer {
         StreamMark written;
         uint64_t launches = 0, calls = 0;
         size_t device_bytes() const { return d_u[0].cap + d_u[1].cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_vel.cap; }
+        bool holds(const ArcticRenderer &r) const { return valid && in_width == r.width && in_height == r.height; }   // ... at any output size
     } taa_upscale;
     PinnedBuf counts;             // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
@@ -563,13 +572,30 @@ struct ArcticRenderer {
 
 namespace arctic {
 
-// Helpers that cross a unit boundary: defined in renderer.cpp, called from ray_calls.cpp or exchange_calls.cpp as well (their comments are at
-// the definitions).  dir_from_rot and sun_proj_view, which the ray family also calls, are host_math.cpp's (common.h).
+// Helpers that cross a unit boundary: defined in renderer.cpp, called from the other units as well (their comments are at the definitions).
+// dir_from_rot and sun_proj_view, which the ray family also calls, are host_math.cpp's (common.h).
 size_t shadow_alloc_bytes(const ArcticRenderer *r);
 int select_device(ArcticRenderer *r);
 int resolve_gbuffer(ArcticRenderer *r);
 void put_objects(const ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_t> &k);
 int check_item_overflow(ArcticRenderer *r);
 bool valid_scene(const ArcticScene *sc);
+
+// ... defined in ray_calls.cpp: the motion call behind its refusals, as arctic_pass_taa and arctic_pass_motion_blur make it; in
+// motion_blur_calls.cpp: arctic_depth_plane_device behind its refusals, as arctic_pass_dof makes it
+int motion_refusal(ArcticRenderer *r, const ArcticScene *sc, const void *prev_world4, const char *who);
+int motion_planes(ArcticRenderer *r, const ArcticScene *sc, float4 *d_pw, float2 *d_vel, float *d_bary, uint4 *d_src);
+int mb_depth_plane(ArcticRenderer *r, float *d_depth);
+
+// ... defined in post_source.cpp.  The planes a NULL colour pointer can mean to a post stage; each stage maps its own flag bits to one of them
+enum class HdrSource { Shaded, Composed, Taa, MotionBlur, Dof, Bloom };
+struct SourceFlag { HdrSource source; const char *flag; };   // flag: the public name of the flag that chose it, for the refusals' texts
+struct SourcePlane { const void *color; bool color_taa; };   // color_taa: the history's tile-major float4 plane, not rows * width * 3 floats
+int source_refusal(ArcticRenderer *r, SourceFlag s, const char *who);
+int source_plane(ArcticRenderer *r, HdrSource source, SourcePlane &plane);
+// the host forms' two ends
+int upload_plane(ArcticRenderer *r, StreamMark &written, DevBuf &d, const void *plane, size_t px, size_t bytes_per_pixel);
+constexpr bool FROM_FRAME = true;
+int read_back(ArcticRenderer *r, void *out, const DevBuf &d, size_t bytes, bool from_frame = false);
 
 }  // namespace arctic

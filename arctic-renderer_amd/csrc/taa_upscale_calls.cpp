@@ -23,22 +23,13 @@ int upscale_checks(ArcticRenderer *r, const ArcticSettings *st, const ArcticTaaU
         return r->fail(ARCTIC_E_INVALID, "%s: the colour plane and the output must be 4-byte aligned, velocity2 8-byte aligned", who);
     return ARCTIC_OK;
 }
+// which plane a NULL colour means under the record's flags
+SourceFlag upscale_source(uint32_t flags) { return {(flags & TAA_UPSCALE_SOURCE_COMPOSED) ? HdrSource::Composed : HdrSource::Shaded, "ARCTIC_TAA_UPSCALE_SOURCE_COMPOSED"}; }
 // ... and with ARCTIC_E_STATE: no side effect.  own_color: the colour plane is the handle's (d.flags says which)
 int upscale_states(ArcticRenderer *r, const TaaUpscaleDesc &d, bool own_color, const char *who) {
     if (r->rows() != r->height)
         return r->fail(ARCTIC_E_STATE, "%s: the samples' boxes need the whole frame, this handle owns %u of %u rows (its neighbours' rows are on other shards)", who, r->rows(), r->height);
-    if (!own_color) return ARCTIC_OK;
-    if (!r->keep_float) return r->fail(ARCTIC_E_STATE, "%s: the float HDR plane needs ARCTIC_OPT_KEEP_FLOAT_OUTPUT", who);
-    if (!r->hdr_valid) return r->fail(ARCTIC_E_STATE, "%s: nothing shaded since ARCTIC_OPT_KEEP_FLOAT_OUTPUT was turned on or since the last resize (arctic_pass_shade or a frame first)", who);
-    if ((d.flags & TAA_UPSCALE_SOURCE_COMPOSED) && (!r->compose.pixels || r->compose.pixels != (uint64_t)r->rows() * r->width))
-        return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_TAA_UPSCALE_SOURCE_COMPOSED: nothing composed yet, or not since the last resize", who);
-    if (r->hdr16) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_OPT_HDR16 = 1: the HDR plane is rounded through binary16", who);
-    return ARCTIC_OK;
-}
-// U holds a call's result of this handle's frame size
-bool upscale_holds(const ArcticRenderer *r) {
-    const ArcticRenderer::TaaUpscale &U = r->taa_upscale;
-    return U.valid && U.in_width == r->width && U.in_height == r->height;
+    return own_color ? source_refusal(r, upscale_source(d.flags), who) : ARCTIC_OK;
 }
 // the two sets of U, the handle's buffers and the launch: device pointers throughout.  d_color: null = the handle's own plane, per d.flags;
 // d_vel: null = zero; d_out: the caller's RGBA8, or null = the handle's own.  The handle's state moves only behind a launch that was enqueued
@@ -56,10 +47,12 @@ int upscale_planes(ArcticRenderer *r, const ArcticSettings *st, const TaaUpscale
     HIPCHECK(r, U.d_ldr.ensure(n * 12));
     HIPCHECK(r, U.written.ensure(hipEventDisableTiming));
     HIPCHECK(r, U.written.wait(r->stream));   // (recorded on another stream: arctic_set_stream came in between; on this one: stream order does it)
-    const bool have = upscale_holds(r) && U.out_width == d.out_width && U.out_height == d.out_height;
+    const bool have = U.holds(*r) && U.out_width == d.out_width && U.out_height == d.out_height;
     const int from = U.cur, to = U.cur ^ 1;
+    SourcePlane source = {d_color, false};
+    if (!d_color) { if (int rc = source_plane(r, upscale_source(d.flags).source, source)) return rc; }
     TaaUpscaleParams p = {};
-    p.color = d_color ? d_color : (d.flags & TAA_UPSCALE_SOURCE_COMPOSED) ? r->compose.d_hdr.as<float>() : r->d_hdr.as<float>();
+    p.color = static_cast<const float *>(source.color);
     p.velocity = d_vel;
     p.prev = have ? U.d_u[from].p : nullptr; p.next = U.d_u[to].p;
     p.out_rgba8 = reinterpret_cast<uint32_t *>(d_out ? d_out : U.d_rgba8.as<uint8_t>()); p.out_ldr = U.d_ldr.as<float>();
@@ -92,20 +85,10 @@ int arctic_taa_upscale(ArcticRenderer *r, const ArcticSettings *settings, const 
     if (rc || (rc = upscale_states(r, d, hdr_rgb32f == nullptr, who)) != ARCTIC_OK || (rc = select_device(r)) != ARCTIC_OK) return rc;
     ArcticRenderer::TaaUpscale &U = r->taa_upscale;
     const size_t px = (size_t)r->rows() * r->width;
-    HIPCHECK(r, U.written.ensure(hipEventDisableTiming));
-    HIPCHECK(r, U.written.wait(r->stream));   // (the copies below overwrite planes the previous call read)
-    if (hdr_rgb32f) {
-        HIPCHECK(r, U.d_color.ensure(std::max<size_t>(px, 1) * 12));
-        HIPCHECK(r, hipMemcpyAsync(U.d_color.p, hdr_rgb32f, px * 12, hipMemcpyHostToDevice, r->stream));
-    }
-    if (velocity2) {
-        HIPCHECK(r, U.d_vel.ensure(std::max<size_t>(px, 1) * 8));
-        HIPCHECK(r, hipMemcpyAsync(U.d_vel.p, velocity2, px * 8, hipMemcpyHostToDevice, r->stream));
-    }
+    if (hdr_rgb32f && (rc = upload_plane(r, U.written, U.d_color, hdr_rgb32f, px, 12)) != ARCTIC_OK) return rc;
+    if (velocity2 && (rc = upload_plane(r, U.written, U.d_vel, velocity2, px, 8)) != ARCTIC_OK) return rc;
     if ((rc = upscale_planes(r, settings, d, hdr_rgb32f ? U.d_color.as<float>() : nullptr, velocity2 ? U.d_vel.p : nullptr, nullptr)) != ARCTIC_OK) return rc;
-    if (out_rgba8) HIPCHECK(r, hipMemcpyAsync(out_rgba8, U.d_rgba8.p, (size_t)d.out_width * d.out_height * 4, hipMemcpyDeviceToHost, r->stream));
-    HIPCHECK(r, hipStreamSynchronize(r->stream));
-    return hdr_rgb32f ? ARCTIC_OK : check_item_overflow(r);
+    return read_back(r, out_rgba8, U.d_rgba8, (size_t)d.out_width * d.out_height * 4, hdr_rgb32f == nullptr);
 }
 
 int arctic_pass_taa_upscale(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticTaaUpscale *upscale, uint8_t *d_out_rgba8) {
@@ -138,7 +121,7 @@ int arctic_taa_upscale_reset(ArcticRenderer *r) {
 int arctic_read_taa_upscale(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, float *count, uint8_t *rgba8) {
     if (!r) return ARCTIC_E_INVALID;
     const ArcticRenderer::TaaUpscale &U = r->taa_upscale;
-    if (!upscale_holds(r) || r->rows() != r->height)
+    if (!U.holds(*r) || r->rows() != r->height)
         return r->fail(ARCTIC_E_STATE, "read_taa_upscale: U is empty (no call yet, or none since the last reset or resize)");
     if (rgba8 && !U.own_rgba8) return r->fail(ARCTIC_E_STATE, "read_taa_upscale: the latest call wrote the caller's RGBA8 buffer, not the handle's");
     int rc = select_device(r);
@@ -166,7 +149,7 @@ int arctic_taa_upscale_hdr_device(ArcticRenderer *r, float *d_hdr_rgb32f) {
     if (!r) return ARCTIC_E_INVALID;
     if (!d_hdr_rgb32f || ((uintptr_t)d_hdr_rgb32f & 3u)) return r->fail(ARCTIC_E_INVALID, "taa_upscale_hdr_device: the plane is null or not 4-byte aligned");
     ArcticRenderer::TaaUpscale &U = r->taa_upscale;
-    if (!upscale_holds(r) || r->rows() != r->height)
+    if (!U.holds(*r) || r->rows() != r->height)
         return r->fail(ARCTIC_E_STATE, "taa_upscale_hdr_device: U is empty (no call yet, or none since the last reset or resize)");
     int rc = select_device(r);
     if (rc) return rc;

@@ -153,7 +153,11 @@ def test_the_refusals_come_in_the_headers_order():
     checks = calls.split("int upscale_checks(")[1].split("\n}\n")[0]
     assert checks.index("null settings or parameters") < checks.index("taa_upscale_refusal(") < checks.index("4-byte aligned")
     states = calls.split("int upscale_states(")[1].split("\n}\n")[0]
-    assert states.index("r->rows() != r->height") < states.index("keep_float") < states.index("hdr_valid") < states.index("SOURCE_COMPOSED") < states.index("hdr16")
+    assert states.index("r->rows() != r->height") < states.index("source_refusal(r, upscale_source(d.flags), who)")
+    assert "TAA_UPSCALE_SOURCE_COMPOSED) ? HdrSource::Composed : HdrSource::Shaded" in calls.split("SourceFlag upscale_source(")[1].split("\n")[0]
+    shared = open(os.path.join(CSRC, "post_source.cpp")).read()                  # the source's refusals: stated once for every post stage
+    source = shared.split("int source_refusal(")[1].split("\n}\n")[0]
+    assert source.index("keep_float") < source.index("hdr_valid") < source.index("HdrSource::Composed &&") < source.index("hdr16")
 
 
 @pytest.mark.skipif(not HAVE_HIPCC, reason="no hipcc")
