@@ -24,6 +24,7 @@ BLOOM_SOURCE_COMPOSED, BLOOM_SOURCE_TAA, BLOOM_SOURCE_MOTION_BLUR, BLOOM_SOURCE_
 EXPOSURE_SOURCE_COMPOSED, EXPOSURE_SOURCE_TAA, EXPOSURE_SOURCE_MOTION_BLUR, EXPOSURE_SOURCE_DOF, EXPOSURE_SOURCE_BLOOM = 1, 2, 4, 8, 16   # ARCTIC_EXPOSURE_*
 EXPOSURE_SKIP_BLACK, EXPOSURE_RESET, EXPOSURE_HOLD, EXPOSURE_METER_ONLY = 32, 64, 128, 256
 FOG_SOURCE_COMPOSED = 1   # ARCTIC_FOG_*
+GI_SOURCE_COMPOSED = 1   # ARCTIC_GI_*
 TAA_UPSCALE_LUMA_WEIGHT, TAA_UPSCALE_SOURCE_COMPOSED, TAA_UPSCALE_NO_CLAMP, TAA_UPSCALE_JITTER_EXACT = 1, 2, 4, 0x80000000   # ARCTIC_TAA_UPSCALE_*
 ERRORS = {-1: "ARCTIC_E_INVALID", -2: "ARCTIC_E_DEVICE", -3: "ARCTIC_E_NO_DEVICE", -4: "ARCTIC_E_STATE", -5: "ARCTIC_E_CAPACITY"}
 
@@ -194,6 +195,22 @@ SIGNATURES = {
     "arctic_taa_upscale_info": (_i32, [_vp, _vp]),
     "arctic_taa_upscale_pixels": (_i32, [_vp, _u64, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "arctic_taa_upscale_jitter": (_i32, [_u32, _u32, _u32, _u32, _u32, _vp]),
+    "arctic_trace_gi": (_i32, [_vp, _scene, _vp, _vp, _vp]),
+    "arctic_trace_gi_device": (_i32, [_vp, _scene, _vp, _vp, _vp]),
+    "arctic_gi_rays": (_i32, [_vp, _vp, _vp, _u32, _vp]),
+    "arctic_read_gi_estimate": (_i32, [_vp, _vp, _vp]),
+    "arctic_gi_info": (_i32, [_vp, _vp]),
+    "arctic_accumulate_gi_device": (_i32, [_vp, _scene, _vp, _vp, _vp]),
+    "arctic_accumulate_gi": (_i32, [_vp, _scene, _vp, _vp, _vp]),
+    "arctic_gi_history_reset": (_i32, [_vp]),
+    "arctic_read_gi_history": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "arctic_gi_compose_device": (_i32, [_vp, _scene, _settings, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_read_gi": (_i32, [_vp, _vp, _vp, _vp]),
+    "arctic_pass_gi": (_i32, [_vp, _scene, _settings, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_gi_accumulate_pixels": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_gi_compose_pixels": (_i32, [_vp, C.c_float, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "arctic_gi_points": (_i32, [_vp, _vp, _u64, _vp, _vp, _u32, _vp]),
+    "arctic_gi_estimate_pixels": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "arctic_version": (_i32, []),
     # include/arctic_dist.h: the multi-GPU exchange steps
     "arctic_comm_unique_id": (_i32, [_vp, _vp, _u64]),

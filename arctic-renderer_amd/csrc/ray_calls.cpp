@@ -21,7 +21,7 @@
 #include "ao_history.h"
 #include "motion.h"
 
-namespace {
+namespace arctic {   // (renderer_state.h: gi_calls.cpp calls these as well)
 
 // "The call needs a G-buffer", in two steps: ambient occlusion and the reflections have a refusal of their own between them, and no call
 // resolves anything in front of a refusal.  gbuffer_refusal: the refusal alone, no side effect ...
@@ -31,8 +31,12 @@ int gbuffer_refusal(ArcticRenderer *r, const char *who) {
 }
 // ... and gbuffer_in_place, behind it: the planes are resolved now when the frame was shaded from the visibility plane
 int gbuffer_in_place(ArcticRenderer *r) { return r->have_gbuffer ? ARCTIC_OK : resolve_gbuffer(r); }
+// what keeps a call from correcting the frame's ambient term (ARCTIC_COMPOSE_AO; the indirect light's ambient_scale)
+const char *ambient_term_refusal(const ArcticRenderer *r) {
+    return r->env_lighting == 1 ? "ARCTIC_OPT_ENV_LIGHTING is on" : r->texture_mips == 1 ? "ARCTIC_OPT_TEXTURE_MIPS = 1" : r->has_extras() ? "a material is not neutral (arctic_set_material_extras)" : nullptr;
+}
 
-}  // namespace
+}  // namespace arctic
 
 extern "C" {
 
@@ -88,7 +92,9 @@ int refit_ray_scene(ArcticRenderer *r, const ArcticScene *sc, std::vector<uint8_
     else { ++R.refits; R.refit_launches = launches; }
     return ARCTIC_OK;
 }
-
+}  // namespace
+}  // extern "C"
+namespace arctic {   // (renderer_state.h)
 // the structure for `sc`, resident on the device: built, validated and uploaded when its inputs changed (synchronous: it reads the meshes back) -- or,
 // under ARCTIC_OPT_RAY_REFIT, refitted in stream order when only the geometry moved.
 int ensure_ray_scene(ArcticRenderer *r, const ArcticScene *sc) {
@@ -167,6 +173,9 @@ int ensure_ray_scene(ArcticRenderer *r, const ArcticScene *sc) {
     r->ray.built = true; r->ray.refittable = refittable;
     return ARCTIC_OK;
 }
+}  // namespace arctic
+extern "C" {
+namespace {
 
 int trace_checks(ArcticRenderer *r, const ArcticScene *sc, const void *rays, uint64_t n, uint32_t flags, const void *hits, const char *who) {
     if (!valid_scene(sc)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
@@ -399,7 +408,8 @@ int arctic_hit_attributes(ArcticRenderer *r, const ArcticScene *scene, const Arc
 }
 
 // ---- hit shading and the reflection plane (include/arctic_hip.h; the kernels: hit_shade.hip) -------------------------------------------------------
-namespace {
+}  // extern "C"
+namespace arctic {   // (renderer_state.h: gi_calls.cpp runs the hit shading between kernels of its own)
 // the sun's map as k_shade_hits needs it: whole, and drawn or written at least once
 int sun_map_ready(ArcticRenderer *r, const char *who) {
     if (r->shadow_size && r->shadow_sharded)
@@ -407,14 +417,6 @@ int sun_map_ready(ArcticRenderer *r, const char *who) {
     if (r->shadow_size && !r->shadow_written_set[r->scur])
         return r->fail(ARCTIC_E_STATE, "%s: the sun's map was never drawn or written (arctic_pass_shadow_map, arctic_write_shadow_map or a frame first)", who);
     return ARCTIC_OK;
-}
-// what both forms of arctic_shade_hits refuse before the device is touched
-int shade_checks(ArcticRenderer *r, const ArcticScene *sc, const void *rays, const void *hits, uint64_t n, uint32_t flags, const void *out, const char *who) {
-    if (!valid_scene(sc)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
-    if (flags) return r->fail(ARCTIC_E_INVALID, "%s: flags %#x (0)", who, flags);
-    if (n && (!rays || !hits || !out)) return r->fail(ARCTIC_E_INVALID, "%s: null rays, hits or output", who);
-    if (n > 0xFFFFFFFFull) return r->fail(ARCTIC_E_CAPACITY, "%s: %llu rays in one call (2^32 - 1 at most)", who, (unsigned long long)n);
-    return sun_map_ready(r, who);
 }
 // the structure, the tables and the launch: device pointers throughout
 int shade_hits(ArcticRenderer *r, const ArcticScene *sc, const void *d_rays, const void *d_hits, uint64_t n, float4 *d_out) {
@@ -432,6 +434,17 @@ int shade_hits(ArcticRenderer *r, const ArcticScene *sc, const void *d_rays, con
     sun_proj_view(sc->sun.position, sc->sun.rotation, p.lpv);
     HIPCHECK(r, launch_shade_hits(d_rays, d_hits, n, p, d_out, r->stream));
     return ARCTIC_OK;
+}
+}  // namespace arctic
+extern "C" {
+namespace {
+// what both forms of arctic_shade_hits refuse before the device is touched
+int shade_checks(ArcticRenderer *r, const ArcticScene *sc, const void *rays, const void *hits, uint64_t n, uint32_t flags, const void *out, const char *who) {
+    if (!valid_scene(sc)) return r->fail(ARCTIC_E_INVALID, "%s: null scene", who);
+    if (flags) return r->fail(ARCTIC_E_INVALID, "%s: flags %#x (0)", who, flags);
+    if (n && (!rays || !hits || !out)) return r->fail(ARCTIC_E_INVALID, "%s: null rays, hits or output", who);
+    if (n > 0xFFFFFFFFull) return r->fail(ARCTIC_E_CAPACITY, "%s: %llu rays in one call (2^32 - 1 at most)", who, (unsigned long long)n);
+    return sun_map_ready(r, who);
 }
 }  // namespace
 
@@ -517,8 +530,7 @@ int compose_states(ArcticRenderer *r, const ComposeDesc &d, const char *who) {
     if (rc) return rc;
     if ((rc = source_refusal(r, {HdrSource::Shaded, ""}, who)) != ARCTIC_OK) return rc;   // (the float HDR plane of the latest shading: post_source.cpp)
     if (d.flags & COMPOSE_AO) {
-        const char *why = r->env_lighting == 1 ? "ARCTIC_OPT_ENV_LIGHTING is on" : r->texture_mips == 1 ? "ARCTIC_OPT_TEXTURE_MIPS = 1" : r->has_extras() ? "a material is not neutral (arctic_set_material_extras)" : nullptr;
-        if (why) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_COMPOSE_AO: %s, so the frame's ambient term is not ambient * base_color at level 0", who, why);
+        if (const char *why = ambient_term_refusal(r)) return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_COMPOSE_AO: %s, so the frame's ambient term is not ambient * base_color at level 0", who, why);
     }
     return ARCTIC_OK;
 }
@@ -544,7 +556,7 @@ int compose_planes(ArcticRenderer *r, const ArcticScene *sc, const ArcticSetting
     p.ao_strength = d.ao_strength; p.reflection_strength = d.reflection_strength; p.ambient = sc->ambient;
     std::memcpy(p.eye, sc->camera.eye, sizeof p.eye);
     HIPCHECK(r, launch_compose(p, r->stream));
-    K.pixels = n; K.own_rgba8 = d_out == nullptr; ++K.launches;
+    K.pixels = n; K.own_rgba8 = d_out == nullptr; K.flags = d.flags; ++K.launches;
     return ARCTIC_OK;
 }
 }  // namespace

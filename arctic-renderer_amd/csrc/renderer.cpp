@@ -139,6 +139,7 @@ int alloc_targets(ArcticRenderer *r) {
     r->exposure.valid = r->exposure.planes = false;   // (... and the exposure's adaptation and planes)
     r->fog.valid = false;          // (... and the latest fog)
     r->taa_upscale.valid = false;  // (... and the upscaler's U)
+    r->gi.pixels = r->gi.composed = 0; r->gi.hist_valid = false;   // (... and the latest indirect light, its history and its composition)
     r->output_filtered = false;
     return ARCTIC_OK;
 }

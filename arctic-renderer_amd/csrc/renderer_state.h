@@ -1,8 +1,9 @@
 // renderer_state.h -- the handle of the C-ABI, declared once for the host units that implement it: renderer.cpp (create, destroy and resize,
 // streams, resources, the passes and frames, options, the debug read-backs), ray_calls.cpp (the ray family, the composition, the motion vectors),
 // exchange_calls.cpp (the multi-GPU exchange), one unit per post stage -- taa_calls.cpp, motion_blur_calls.cpp, dof_calls.cpp, bloom_calls.cpp,
-// exposure_calls.cpp, fog_calls.cpp, taa_upscale_calls.cpp -- and post_source.cpp (what those stages' calls share).  Also the few helpers one of
-// those units defines and another calls.  Host only.
+// exposure_calls.cpp, fog_calls.cpp, taa_upscale_calls.cpp --, post_source.cpp (what those stages' calls share) and gi_calls.cpp (the indirect diffuse
+// light, which runs the ray family's walk and hit shading between kernels of its own).  Also the few helpers one of those units defines and another
+// calls.  Host only.
 #pragma once
 #include <algorithm>
 #include <cstdarg>
@@ -378,6 +379,7 @@ struct ArcticRenderer {
         DevBuf d_rgba8, d_ldr, d_hdr;
         uint64_t pixels = 0, launches = 0, passes = 0;
         bool own_rgba8 = false;
+        uint32_t flags = 0;   // the latest composition's (arctic_gi_compose_device asks whether it has scaled the ambient term already)
         size_t device_bytes() const { return d_rgba8.cap + d_ldr.cap + d_hdr.cap; }
     } compose;
     // The temporal accumulation of the occlusion plane (arctic_accumulate_ambient_occlusion_device; ao_history.hip): two sets of the two history
@@ -541,7 +543,34 @@ struct ArcticRenderer {
         size_t device_bytes() const { return d_u[0].cap + d_u[1].cap + d_rgba8.cap + d_ldr.cap + d_color.cap + d_vel.cap; }
         bool holds(const ArcticRenderer &r) const { return valid && in_width == r.width && in_height == r.height; }   // ... at any output size
     } taa_upscale;
-    PinnedBuf counts;             // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
+    // Indirect diffuse light (arctic_trace_gi; gi.hip, owned by gi_calls.cpp): the direction table on the device -- at most 3 KiB, sent from a
+    // pinned copy that is also what the device holds, like the occlusion's --, the float4 sum S and the estimate E of the handle's rows.  The
+    // rays, hits and colours of a round are HitScene's (the reflection plane's buffers), so a handle that traces both holds them once.  Nothing
+    // is allocated before the first call that passes its checks.  pixels: rows * width of the latest estimate (0: none; a resize makes the
+    // handle's differ); own_estimate: that call wrote d_estimate, not the caller's plane.  The accumulation (k_gi_accumulate): two sets of three
+    // history planes, tile-major like the occlusion's (n_tiles * 64 float4 each, 96 bytes per pixel) -- a call reads set `hist_cur` and writes the
+    // other, then it moves; hist_valid: the history is not empty (cleared by arctic_gi_history_reset and by a resize); proj_view, hist_width,
+    // hist_height: those of the call that wrote set `hist_cur`.  The composition (k_gi_compose): d_hdr, d_ldr, d_rgba8 of the handle's rows;
+    // composed: rows * width of the latest one; own_hdr, own_rgba8: it wrote the handle's planes, not the caller's
+    struct Gi {
+        DevBuf d_dirs, d_sum, d_estimate;
+        UploadRing<1> dirs_ring;                   // its one pinned slot keeps the table last sent
+        size_t n_floats = 0;                       // what d_dirs holds (0: nothing)
+        uint64_t pixels = 0, launches = 0, calls = 0;
+        bool own_estimate = false;
+        DevBuf d_hist[2][3];
+        int hist_cur = 0;
+        bool hist_valid = false;
+        float proj_view[16] = {};
+        uint32_t hist_width = 0, hist_height = 0;
+        uint64_t hist_calls = 0;
+        DevBuf d_hdr, d_ldr, d_rgba8;
+        uint64_t composed = 0, passes = 0;
+        bool own_hdr = false, own_rgba8 = false;
+        size_t history_bytes() const { size_t b = 0; for (const auto &set : d_hist) for (const DevBuf &d : set) b += d.cap; return b; }
+        size_t device_bytes() const { return d_dirs.cap + d_sum.cap + d_estimate.cap + history_bytes() + d_hdr.cap + d_ldr.cap + d_rgba8.cap; }
+    } gi;
+    PinnedBuf counts;            // pinned, mapped: [0] records, [1] work items (forward), [2], [3] the same for the shadow pass, [4], [5] item-table overflow flags, [6], [7] work items drawn by the atomic rasteriser (forward, shadow)
     uint32_t *h_counts() const { return counts.as<uint32_t>(); }
     uint32_t *dh_counts() const { return counts.dev<uint32_t>(); }   // the device's address of h_counts
     // The streams the handle created, declared LAST: members are destroyed in reverse order, so every stream is waited for and gone before any
@@ -586,6 +615,16 @@ bool valid_scene(const ArcticScene *sc);
 int motion_refusal(ArcticRenderer *r, const ArcticScene *sc, const void *prev_world4, const char *who);
 int motion_planes(ArcticRenderer *r, const ArcticScene *sc, float4 *d_pw, float2 *d_vel, float *d_bary, uint4 *d_src);
 int mb_depth_plane(ArcticRenderer *r, float *d_depth);
+// ... defined in ray_calls.cpp as well, called by gi_calls.cpp (the indirect light is traced and shaded by the ray family's own steps): "the call
+// needs a G-buffer" in its two steps, the structure of the ray queries for a scene, the sun's map as k_shade_hits needs it, the shading of n
+// device rays and hits
+int gbuffer_refusal(ArcticRenderer *r, const char *who);
+int gbuffer_in_place(ArcticRenderer *r);
+int ensure_ray_scene(ArcticRenderer *r, const ArcticScene *sc);
+int sun_map_ready(ArcticRenderer *r, const char *who);
+int shade_hits(ArcticRenderer *r, const ArcticScene *sc, const void *d_rays, const void *d_hits, uint64_t n, float4 *d_out);
+// ... and why the frame's ambient term is not the flat ambient * base_color at level 0 that a correction of it assumes (null: it is)
+const char *ambient_term_refusal(const ArcticRenderer *r);
 
 // ... defined in post_source.cpp.  The planes a NULL colour pointer can mean to a post stage; each stage maps its own flag bits to one of them
 enum class HdrSource { Shaded, Composed, Taa, MotionBlur, Dof, Bloom };

@@ -605,6 +605,63 @@ class Renderer {
         return arctic_taa_upscale_jitter(index, w, W, h, H, out2) == ARCTIC_OK;
     }
 
+    // indirect diffuse light (include/arctic_hip.h: arctic_trace_gi and the definition in front of it): gi.n_rays rounds of one closest-hit ray per
+    // pixel of the resident G-buffer from dirs (P * P sets of n_rays local directions, z along the normal: cosine-weighted for an irradiance
+    // estimate), each shaded at its hit or by the environment map -> rows x width float4 {mean colour, rays}; rgba32f = nullptr leaves it on the
+    // device.  The filter (whole frames only) sums over the P x P window of the pattern
+    [[nodiscard]] bool trace_gi(const ArcticScene &scene, const ArcticGi &gi, const float *dirs, float *rgba32f) { return ok(arctic_trace_gi(m_handle, &scene, &gi, dirs, rgba32f)); }
+    // the same into device memory the caller owns, in stream order on the handle's stream
+    [[nodiscard]] bool trace_gi_device(const ArcticScene &scene, const ArcticGi &gi, const float *dirs, float *d_rgba32f) {
+        return ok(arctic_trace_gi_device(m_handle, &scene, &gi, dirs, d_rgba32f));
+    }
+    // round `round`'s ray records, for tests
+    [[nodiscard]] bool gi_rays(const ArcticGi &gi, const float *dirs, uint32_t round, ArcticRay *rays) { return ok(arctic_gi_rays(m_handle, &gi, dirs, round, rays)); }
+    // the latest call's sum and estimate planes; either may be nullptr
+    [[nodiscard]] bool read_gi_estimate(float *sum_rgba32f, float *estimate_rgba32f) { return ok(arctic_read_gi_estimate(m_handle, sum_rgba32f, estimate_rgba32f)); }
+    // {device bytes of the table, S and E, launches of the stage's own kernels, tracing calls, 0}
+    [[nodiscard]] bool gi_info(uint64_t out4[4]) { return ok(arctic_gi_info(m_handle, out4)); }
+    // the temporal accumulation of E: the device plane d_gi_in blended into the handle's history, reprojected through the previous call's camera, into
+    // d_gi_out (it may be the same plane); in stream order.  accumulate_gi: the host form, synchronous
+    [[nodiscard]] bool accumulate_gi_device(const ArcticScene &scene, const ArcticGiHistory &hist, const float *d_gi_in_rgba32f, float *d_gi_out_rgba32f) {
+        return ok(arctic_accumulate_gi_device(m_handle, &scene, &hist, d_gi_in_rgba32f, d_gi_out_rgba32f));
+    }
+    [[nodiscard]] bool accumulate_gi(const ArcticScene &scene, const ArcticGiHistory &hist, const float *gi_in_rgba32f, float *gi_out_rgba32f) {
+        return ok(arctic_accumulate_gi(m_handle, &scene, &hist, gi_in_rgba32f, gi_out_rgba32f));
+    }
+    [[nodiscard]] bool gi_history_reset() { return ok(arctic_gi_history_reset(m_handle)); }
+    [[nodiscard]] bool read_gi_history(float *acc3, float *count, float *world3, float *normal3) { return ok(arctic_read_gi_history(m_handle, acc3, count, world3, normal3)); }
+    // the composition: C (nullptr: the handle's shaded or composed plane) + the ambient correction + base * E (nullptr: the handle's estimate), then the
+    // tonemapper, into the caller's planes or (nullptr) the handle's own: read_gi
+    [[nodiscard]] bool gi_compose_device(const ArcticScene &scene, const ArcticSettings &settings, const ArcticGiCompose &compose, const float *d_hdr_rgb32f,
+                                         const float *d_gi_rgba32f, float *d_out_hdr_rgb32f, uint8_t *d_out_rgba8) {
+        return ok(arctic_gi_compose_device(m_handle, &scene, &settings, &compose, d_hdr_rgb32f, d_gi_rgba32f, d_out_hdr_rgb32f, d_out_rgba8));
+    }
+    [[nodiscard]] bool read_gi(float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8) { return ok(arctic_read_gi(m_handle, ldr_rgb, hdr_rgb, rgba8)); }
+    // the one call: trace, accumulate when hist is given, compose
+    [[nodiscard]] bool pass_gi(const ArcticScene &scene, const ArcticSettings &settings, const ArcticGi &gi, const float *dirs, const ArcticGiHistory *hist,
+                               const ArcticGiCompose &compose, uint8_t *d_out_rgba8) {
+        return ok(arctic_pass_gi(m_handle, &scene, &settings, &gi, dirs, hist, &compose, d_out_rgba8));
+    }
+    // the host arbiters: no handle, no GPU
+    [[nodiscard]] static bool gi_accumulate_pixels(const ArcticGiHistory &hist, uint64_t n, const float *world3, const float *normal3, const uint8_t *geometry, const float *cur4,
+                                                   const float *prev_proj_view, uint32_t width, uint32_t height, const float *prev_acc3, const float *prev_count,
+                                                   const float *prev_world3, const float *prev_normal3, float *out4, float *out_acc3, float *out_count, float *out_world3,
+                                                   float *out_normal3) {
+        return arctic_gi_accumulate_pixels(&hist, n, world3, normal3, geometry, cur4, prev_proj_view, width, height, prev_acc3, prev_count, prev_world3, prev_normal3, out4,
+                                           out_acc3, out_count, out_world3, out_normal3) == ARCTIC_OK;
+    }
+    [[nodiscard]] static bool gi_compose_pixels(const ArcticGiCompose &compose, float ambient, uint64_t n, const float *hdr3, const float *base3, const float *metal,
+                                                const float *gi4, const uint8_t *geometry, float *out_hdr3) {
+        return arctic_gi_compose_pixels(&compose, ambient, n, hdr3, base3, metal, gi4, geometry, out_hdr3) == ARCTIC_OK;
+    }
+    [[nodiscard]] static bool gi_points(const float *points6, const uint32_t *sets, uint64_t n_points, const ArcticGi &gi, const float *dirs, uint32_t round, ArcticRay *rays) {
+        return arctic_gi_points(points6, sets, n_points, &gi, dirs, round, rays) == ARCTIC_OK;
+    }
+    [[nodiscard]] static bool gi_estimate_pixels(const ArcticGi &gi, uint32_t width, uint32_t height, const ArcticRay *rays, const float *colors4, const float *normal3,
+                                                 const float *world3, const uint8_t *geometry, float *sum4, float *estimate4) {
+        return arctic_gi_estimate_pixels(&gi, width, height, rays, colors4, normal3, world3, geometry, sum4, estimate4) == ARCTIC_OK;
+    }
+
     const std::string &last_error() const { return m_error; }
     ArcticRenderer *handle() const { return m_handle; }
 

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding
-from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, TAA_UPSCALE_DTYPE, MOTION_BLUR_DTYPE, DOF_DTYPE, BLOOM_DTYPE, EXPOSURE_DTYPE, EXPOSURE_STATE_DTYPE, FOG_DTYPE, FOG_VIEW_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
+from .scene import (AO_DTYPE, AO_HISTORY_DTYPE, GI_DTYPE, GI_HISTORY_DTYPE, GI_COMPOSE_DTYPE, COMPOSE_DTYPE, HIT_DTYPE, RAY_DTYPE, RAY_NODE_DTYPE, RAY_TRI_DTYPE, LIGHT_DTYPE, MATERIAL_PARAMS_DTYPE, MORPH_DELTA_DTYPE, POINT_SHADOW_LIGHT_DTYPE, SKIN_VERTEX_DTYPE, SPOT_LIGHT_DTYPE, TAA_DTYPE, TAA_UPSCALE_DTYPE, MOTION_BLUR_DTYPE, DOF_DTYPE, BLOOM_DTYPE, EXPOSURE_DTYPE, EXPOSURE_STATE_DTYPE, FOG_DTYPE, FOG_VIEW_DTYPE, VERTEX_DTYPE, CCreateInfo, CScene, CSettings)
 
 
 class ArcticError(RuntimeError):
@@ -238,6 +238,98 @@ class Renderer:
         s = self._scene(desc)
         ao, d = _ao_arguments(dirs, n_rays, pattern, radius, bias, filter, normal_cos, plane_dist)
         self._check(self.L.arctic_trace_ambient_occlusion_device(self.h, C.byref(s), _ptr(ao), _ptr(d), C.c_void_p(d_out_ptr) if d_out_ptr else None))
+
+    # ---- indirect diffuse light (include/arctic_hip.h: arctic_trace_gi and the definition in front of it) -------------------------------------
+    def trace_gi(self, desc, dirs, n_rays=None, pattern=None, max_distance=np.inf, bias=1e-3, clamp_max=65504.0, filter=False, normal_cos=0.9, plane_dist=0.05, read=True):
+        """n_rays rounds of one closest-hit ray per pixel of the resident G-buffer, from world + bias * m along dirs -- (P * P, n_rays, 3) float32
+        local directions, z along the normal, e.g. gi_directions(n_rays, P); n_rays and pattern default to its shape --, each shaded at its hit
+        (shade_hits) or by the environment map: (rows, width, 4) float32 {mean colour, rays}.  filter: the sum over the P x P window (whole
+        frames only).  read=False leaves the plane on the device and returns None (timing)."""
+        s = self._scene(desc)
+        gi, d = gi_arguments(dirs, n_rays, pattern, max_distance, bias, clamp_max, filter, normal_cos, plane_dist)
+        out = np.empty((self.rows, self.width, 4), np.float32) if read else None
+        self._check(self.L.arctic_trace_gi(self.h, C.byref(s), _ptr(gi), _ptr(d), _ptr(out)))
+        return out
+
+    def trace_gi_device(self, desc, dirs, d_rgba_ptr, **kw):
+        """the same into device memory the caller owns (an int pointer; rows * width * 16 bytes, 16-byte aligned); asynchronous on the handle's stream."""
+        s = self._scene(desc)
+        gi, d = gi_arguments(dirs, **kw)
+        self._check(self.L.arctic_trace_gi_device(self.h, C.byref(s), _ptr(gi), _ptr(d), C.c_void_p(d_rgba_ptr) if d_rgba_ptr else None))
+
+    def gi_rays(self, dirs, round, **kw):
+        """round `round`'s ray records of the resident G-buffer: (rows, width) RAY_DTYPE, the all-zero record where a pixel has no ray (tests)"""
+        gi, d = gi_arguments(dirs, **kw)
+        out = np.empty((self.rows, self.width), RAY_DTYPE)
+        self._check(self.L.arctic_gi_rays(self.h, _ptr(gi), _ptr(d), int(round), _ptr(out)))
+        return out
+
+    def read_gi_estimate(self, want=("sum", "estimate")):
+        """the latest trace_gi's planes as they stand on the device: {"sum": S, "estimate": E}, (rows, width, 4) float32 each"""
+        out = {k: np.empty((self.rows, self.width, 4), np.float32) for k in want}
+        self._check(self.L.arctic_read_gi_estimate(self.h, _ptr(out.get("sum")), _ptr(out.get("estimate"))))
+        return out
+
+    def gi_info(self):
+        """(device bytes of the table, S, E, the history and the composition's planes, launches of the stage's own kernels, tracing calls, bytes of
+        the history alone): all 0 until the first call"""
+        out = np.zeros(4, np.uint64)
+        self._check(self.L.arctic_gi_info(self.h, _ptr(out)))
+        return tuple(int(x) for x in out)
+
+    def accumulate_gi_device(self, desc, d_in_ptr, d_out_ptr, max_history=32.0, normal_cos=0.9, plane_dist=0.05, min_weight=0.0, hist=None):
+        """blend a device plane of E (an int pointer: rows * width float4, 16-byte aligned) into the handle's history, reprojected through the
+        previous call's camera, into d_out_ptr ({acc, N}; it may be the same plane).  Asynchronous on the handle's stream."""
+        s = self._scene(desc)
+        h = gi_history_arguments(max_history, normal_cos, plane_dist, min_weight) if hist is None else hist
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_accumulate_gi_device(self.h, C.byref(s), _ptr(h), vp(d_in_ptr), vp(d_out_ptr)))
+
+    def accumulate_gi(self, desc, gi, max_history=32.0, normal_cos=0.9, plane_dist=0.05, min_weight=0.0, hist=None):
+        """the same from and to host memory: (rows, width, 4) float32 E -> (rows, width, 4) {acc, N}; synchronous"""
+        s = self._scene(desc)
+        h = gi_history_arguments(max_history, normal_cos, plane_dist, min_weight) if hist is None else hist
+        a = np.ascontiguousarray(gi, dtype=np.float32)
+        if a.shape != (self.rows, self.width, 4):
+            raise ArcticError(-1, "accumulate_gi: the plane is not (rows, width, 4)")
+        out = np.empty_like(a)
+        self._check(self.L.arctic_accumulate_gi(self.h, C.byref(s), _ptr(h), _ptr(a), _ptr(out)))
+        return out
+
+    def gi_history_reset(self):
+        self._check(self.L.arctic_gi_history_reset(self.h))
+
+    def read_gi_history(self):
+        """the current history, row-major: {"acc": (h, w, 3), "count": (h, w), "world": (h, w, 3), "normal": (h, w, 3)} float32"""
+        n = (self.height, self.width)
+        out = dict(acc=np.empty(n + (3,), np.float32), count=np.empty(n, np.float32), world=np.empty(n + (3,), np.float32), normal=np.empty(n + (3,), np.float32))
+        self._check(self.L.arctic_read_gi_history(self.h, _ptr(out["acc"]), _ptr(out["count"]), _ptr(out["world"]), _ptr(out["normal"])))
+        return out
+
+    def gi_compose_device(self, desc, settings, d_hdr_ptr=None, d_gi_ptr=None, d_out_hdr_ptr=None, d_out_ptr=None, gi_strength=1.0, ambient_scale=1.0, flags=0, compose=None):
+        """fold the indirect light into an HDR plane in front of the tonemapper: C (an int pointer: rows * width * 3 floats; None: the handle's
+        shaded plane, under GI_SOURCE_COMPOSED the composed one) + (ambient * base) * (ambient_scale - 1) + gi_strength * (1 - metal) * base * E
+        (d_gi_ptr: rows * width float4; None: the handle's estimate).  The result stays on the device -- the caller's planes or the handle's
+        own: read_gi().  Asynchronous on the handle's stream."""
+        s, st = self._scene(desc), self._settings(settings)
+        c = gi_compose_arguments(gi_strength, ambient_scale, flags) if compose is None else compose
+        vp = (lambda x: C.c_void_p(x) if x else None)
+        self._check(self.L.arctic_gi_compose_device(self.h, C.byref(s), C.byref(st), _ptr(c), vp(d_hdr_ptr), vp(d_gi_ptr), vp(d_out_hdr_ptr), vp(d_out_ptr)))
+
+    def read_gi(self, want=("ldr", "hdr", "rgba8")):
+        """the latest composition's planes the handle owns: {"ldr", "hdr": (rows, width, 3) float32, "rgba8": (rows, width, 4) uint8}"""
+        n = (self.rows, self.width)
+        out = {k: np.empty(n + ((4,) if k == "rgba8" else (3,)), np.uint8 if k == "rgba8" else np.float32) for k in want}
+        self._check(self.L.arctic_read_gi(self.h, _ptr(out.get("ldr")), _ptr(out.get("hdr")), _ptr(out.get("rgba8"))))
+        return out
+
+    def pass_gi(self, desc, settings, dirs, d_out_ptr=None, hist=None, compose=None, **kw):
+        """the one call: trace_gi (keywords as it takes them), accumulate when hist (a GI_HISTORY_DTYPE record, e.g. gi_history_arguments()) is
+        given, compose (a GI_COMPOSE_DTYPE record; default gi_strength 1, ambient_scale 1).  Asynchronous on the handle's stream."""
+        s, st = self._scene(desc), self._settings(settings)
+        gi, d = gi_arguments(dirs, **kw)
+        c = gi_compose_arguments() if compose is None else compose
+        self._check(self.L.arctic_pass_gi(self.h, C.byref(s), C.byref(st), _ptr(gi), _ptr(d), _ptr(hist), _ptr(c), C.c_void_p(d_out_ptr) if d_out_ptr else None))
 
     # ---- what is at a hit (include/arctic_hip.h: arctic_hit_attributes and the text in front of it) ---------------------------------------
     def hit_attributes(self, desc, hits):
@@ -1256,6 +1348,116 @@ def ambient_occlusion_points(triangles, points, sets, dirs, n_rays=None, pattern
     return hits
 
 
+def gi_arguments(dirs, n_rays=None, pattern=None, max_distance=np.inf, bias=1e-3, clamp_max=65504.0, filter=False, normal_cos=0.9, plane_dist=0.05):
+    """(one GI_DTYPE record, the table as a flat float32 array).  n_rays / pattern: from a (P * P, n_rays, 3) table where not given; the library
+    checks every value"""
+    d = np.ascontiguousarray(dirs, dtype=np.float32)
+    if n_rays is None:
+        n_rays = d.shape[1] if d.ndim == 3 else 0
+    if pattern is None:
+        pattern = {1: 1, 4: 2, 16: 4}.get(d.shape[0] if d.ndim == 3 else 0, 0)
+    if d.size < int(pattern) ** 2 * int(n_rays) * 3:
+        raise ArcticError(-1, "indirect light: the direction table is smaller than pattern * pattern * n_rays * 3 floats")
+    gi = np.zeros(1, GI_DTYPE)
+    gi["n_rays"], gi["pattern"], gi["max_distance"], gi["bias"], gi["clamp_max"] = n_rays, pattern, max_distance, bias, clamp_max
+    gi["filter"], gi["normal_cos"], gi["plane_dist"] = int(filter), normal_cos, plane_dist
+    return gi, d.reshape(-1)
+
+
+def gi_history_arguments(max_history=32.0, normal_cos=0.9, plane_dist=0.05, min_weight=0.0):
+    """one GI_HISTORY_DTYPE record; the library checks every value"""
+    h = np.zeros(1, GI_HISTORY_DTYPE)
+    h["max_history"], h["normal_cos"], h["plane_dist"], h["min_weight"] = max_history, normal_cos, plane_dist, min_weight
+    return h
+
+
+def gi_compose_arguments(gi_strength=1.0, ambient_scale=1.0, flags=0):
+    """one GI_COMPOSE_DTYPE record; the library checks every value"""
+    c = np.zeros(1, GI_COMPOSE_DTYPE)
+    c["flags"], c["gi_strength"], c["ambient_scale"] = flags, gi_strength, ambient_scale
+    return c
+
+
+def gi_accumulate_pixels(world, normal, geometry, cur, prev_proj_view=None, width=1, height=1, prev=None, hist=None, **kw):
+    """arctic_gi_accumulate_pixels: stage 5 on the host for n pixels in any order -- world, normal (n, 3), geometry (n,), cur (n, 4) = E;
+    prev_proj_view: the previous call's (4, 4) matrix, None = the history is empty; prev = (acc (w * h, 3), count, world, normal) row-major.
+    Returns (out (n, 4) = {acc, N}, acc (n, 3), count (n,), world (n, 3), normal (n, 3)) float32."""
+    f = lambda a, k: np.ascontiguousarray(a, dtype=np.float32).reshape(-1, k) if k > 1 else np.ascontiguousarray(a, dtype=np.float32).ravel()
+    w, nr, c = f(world, 3), f(normal, 3), f(cur, 4)
+    g = np.ascontiguousarray(geometry, dtype=np.uint8).ravel()
+    n = len(w)
+    if any(len(x) != n for x in (nr, g, c)):
+        raise ArcticError(-1, "gi_accumulate_pixels: one entry of every array per pixel")
+    h = gi_history_arguments(**kw) if hist is None else hist
+    P = None if prev_proj_view is None else np.ascontiguousarray(prev_proj_view, dtype=np.float32).reshape(16)
+    pa = pc = pw = pn = None
+    if P is not None:
+        pa, pc, pw, pn = f(prev[0], 3), f(prev[1], 1), f(prev[2], 3), f(prev[3], 3)
+        if any(len(x) != int(width) * int(height) for x in (pa, pc, pw, pn)):
+            raise ArcticError(-1, "gi_accumulate_pixels: the previous history is not width * height entries")
+    out = np.empty((n, 4), np.float32), np.empty((n, 3), np.float32), np.empty(n, np.float32), np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+    p = (lambda a: _ptr(a) if n else None)
+    rc = binding.lib().arctic_gi_accumulate_pixels(_ptr(h), n, p(w), p(nr), p(g), p(c), _ptr(P), int(width), int(height), _ptr(pa), _ptr(pc), _ptr(pw), _ptr(pn),
+                                                   *[p(o) for o in out])
+    if rc < 0:
+        raise ArcticError(rc, "gi_accumulate_pixels")
+    return out
+
+
+def gi_compose_pixels(hdr, base, metal, gi, geometry, ambient, gi_strength=1.0, ambient_scale=1.0, flags=0, compose=None):
+    """arctic_gi_compose_pixels: stage 6's two terms on the host, on channels sampled already: hdr, base (n, 3), metal (n,), gi (n, 4) = E,
+    geometry (n,) -> (n, 3) float32"""
+    h, b = (np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3) for a in (hdr, base))
+    m, e = np.ascontiguousarray(metal, dtype=np.float32).ravel(), np.ascontiguousarray(gi, dtype=np.float32).reshape(-1, 4)
+    g = np.ascontiguousarray(geometry, dtype=np.uint8).ravel()
+    n = len(h)
+    if any(len(x) != n for x in (b, m, e, g)):
+        raise ArcticError(-1, "gi_compose_pixels: one entry of every array per pixel")
+    c = gi_compose_arguments(gi_strength, ambient_scale, flags) if compose is None else compose
+    out = np.empty((n, 3), np.float32)
+    p = (lambda a: _ptr(a) if n else None)
+    rc = binding.lib().arctic_gi_compose_pixels(_ptr(c), float(ambient), n, p(h), p(b), p(m), p(e), p(g), p(out))
+    if rc < 0:
+        raise ArcticError(rc, "gi_compose_pixels")
+    return out
+
+
+def gi_points(points, sets, dirs, round, **kw):
+    """arctic_gi_points: round `round`'s ray of each point {world3, normal3} ((n, 6) float32) with direction set sets[k] of dirs: (n,) RAY_DTYPE,
+    the all-zero record for a point that is not covered.  No handle, no GPU."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 6)
+    st = np.ascontiguousarray(sets, dtype=np.uint32).ravel()
+    if len(st) != len(p):
+        raise ArcticError(-1, "gi_points: one set per point")
+    gi, d = gi_arguments(dirs, **kw)
+    rays = np.empty(len(p), RAY_DTYPE)
+    rc = binding.lib().arctic_gi_points(_ptr(p) if len(p) else None, _ptr(st) if len(p) else None, len(p), _ptr(gi), _ptr(d), int(round), _ptr(rays) if len(p) else None)
+    if rc < 0:
+        raise ArcticError(rc, "gi_points")
+    return rays
+
+
+def gi_estimate_pixels(rays, colors, normal=None, world=None, geometry=None, gi=None, **kw):
+    """arctic_gi_estimate_pixels: stages 3 and 4 on the host.  rays (n_rays, h, w) RAY_DTYPE and colors (n_rays, h, w, 4) float32, round after
+    round; with the filter normal and world (h, w, 3) and geometry (h, w) as well: -> (S, E), (h, w, 4) float32 each.  gi: a GI_DTYPE record,
+    or keywords as trace_gi takes them (n_rays and pattern included: no table is read)."""
+    ry = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+    n_rays, h, w = ry.shape
+    c = np.ascontiguousarray(colors, dtype=np.float32).reshape(n_rays, h, w, 4)
+    if gi is None:
+        P = int(kw.pop("pattern", 1))
+        kw.pop("n_rays", None)   # (the rounds given are the rounds summed)
+        gi, _ = gi_arguments(np.zeros((P * P, n_rays, 3), np.float32), n_rays=n_rays, pattern=P, **kw)
+    f3 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(h, w, 3)
+    nm, wd = f3(normal), f3(world)
+    geo = None if geometry is None else np.ascontiguousarray(geometry, dtype=np.uint8).reshape(h, w)
+    S, E = np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32)
+    rc = binding.lib().arctic_gi_estimate_pixels(_ptr(gi), w, h, _ptr(ry), _ptr(c), _ptr(nm), _ptr(wd), _ptr(geo), _ptr(S), _ptr(E))
+    if rc < 0:
+        raise ArcticError(rc, "gi_estimate_pixels")
+    return S, E
+
+
 def _compose_arguments(flags, ao_strength, reflection_strength, reflection_bias):
     """one COMPOSE_DTYPE record; the library checks every value"""
     c = np.zeros(1, COMPOSE_DTYPE)
@@ -1813,6 +2015,13 @@ def ao_directions(n_rays, pattern, seed=0):
         out[s] = out[s][rng.permutation(n)]                            # (the order inside a set carries no meaning: ray k of one set is no neighbour of ray k of another)
     out /= np.linalg.norm(out, axis=-1, keepdims=True)
     return out.astype(np.float32)
+
+
+gi_directions = ao_directions
+"""gi_directions(n_rays, pattern, seed=0): the direction table trace_gi expects -- ao_directions' table, under the name of its use here.  The table
+MUST be cosine-weighted over the hemisphere z > 0, as this one is, for the mean of the rays' radiance to be the irradiance over pi: the estimate
+weights every ray alike, so the cosine of the rendering equation has to be in the density the directions were drawn from.  The library takes any
+table; with a uniform one the result is a mean radiance, not an irradiance."""
 
 
 def point_shadow_matrices(light):

@@ -40,6 +40,14 @@ assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 16
 # ArcticAmbientOcclusion (include/arctic_hip.h)
 AO_DTYPE = np.dtype([("n_rays", "<u4"), ("pattern", "<u4"), ("radius", "<f4"), ("bias", "<f4"), ("filter", "<u4"), ("normal_cos", "<f4"), ("plane_dist", "<f4"), ("reserved", "<u4")])
 assert AO_DTYPE.itemsize == 32
+# ArcticGi (include/arctic_hip.h)
+GI_DTYPE = np.dtype([("n_rays", "<u4"), ("pattern", "<u4"), ("max_distance", "<f4"), ("bias", "<f4"), ("clamp_max", "<f4"), ("filter", "<u4"), ("normal_cos", "<f4"), ("plane_dist", "<f4"),
+                     ("reserved", "<u4", 4)])
+assert GI_DTYPE.itemsize == 48
+# ArcticGiHistory (ArcticAoHistory's fields) and ArcticGiCompose
+GI_HISTORY_DTYPE = np.dtype([("max_history", "<f4"), ("normal_cos", "<f4"), ("plane_dist", "<f4"), ("min_weight", "<f4"), ("reserved", "<u4", 4)])
+GI_COMPOSE_DTYPE = np.dtype([("flags", "<u4"), ("gi_strength", "<f4"), ("ambient_scale", "<f4"), ("reserved", "<u4", 5)])
+assert GI_HISTORY_DTYPE.itemsize == 32 and GI_COMPOSE_DTYPE.itemsize == 32
 # ArcticRayCompose (include/arctic_hip.h)
 COMPOSE_DTYPE = np.dtype([("flags", "<u4"), ("ao_strength", "<f4"), ("reflection_strength", "<f4"), ("reflection_bias", "<f4"), ("reserved", "<u4", 4)])
 assert COMPOSE_DTYPE.itemsize == 32

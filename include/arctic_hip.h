@@ -2149,6 +2149,180 @@ int arctic_taa_upscale_pixels(const ArcticTaaUpscale *upscale, uint64_t n, const
 #define ARCTIC_TAA_UPSCALE_JITTER_EXACT 0x80000000u
 int arctic_taa_upscale_jitter(uint32_t index, uint32_t w, uint32_t W, uint32_t h, uint32_t H, float *out2);
 
+/* ---- Indirect diffuse light: one bounce from the resident G-buffer (no counterpart in the reference: its one ambient term is the flat ambient * base_color) --
+ * What light arrives at each pixel from the rest of the scene?  n_rays rays per pixel over the hemisphere of its normal, each walked to its
+ * CLOSEST hit and shaded there by layer 2 of the hit section (arctic_shade_hits), a miss taking the environment map; the mean of those colours
+ * is the estimate E.  With a COSINE-WEIGHTED direction table the mean of the radiance is the irradiance over pi, which is what a diffuse surface
+ * multiplies its base colour by.  Nothing in the passes uses the plane: shading and every existing bit are unchanged, and a handle that never
+ * makes these calls allocates nothing for them.
+ *
+ * THE DEFINITION.  Everything is fp32, one rounding per operation, in the written order, no contraction; division and square root are IEEE
+ * (correctly rounded).  dirs has the ambient occlusion's layout, P*P*n_rays*3 floats, direction k of set s at dirs[(s*n_rays + k)*3 ..], used as
+ * given; pixel (x, y) OF THE FRAME uses set (y % P) * P + x % P.  The work is done in n_rays ROUNDS k = 0 .. n_rays-1 over the reflection plane's
+ * own buffers (one ray, one hit and one colour per pixel: 64 bytes, once, not n_rays times); S and E are row-major float4 planes.
+ *   1. Rays (k_gi_rays, round k).  Per pixel, with world = attributes 11..13 and n = attributes 8..10: steps 1 to 3 of the ambient occlusion
+ *      unchanged -- m, the frame t and bt, o[i] = world[i] + bias*m[i], d[i] = (t[i]*l0 + bt[i]*l1) + m[i]*l2 with l = direction k of the pixel's
+ *      set -- and t_min = 0, t_max = max_distance.  A pixel without geometry, or one NOT COVERED by step 1, gets the all-zero record, as in the
+ *      reflection plane.  A pixel HAD A RAY in the round iff its record's t_max > 0.
+ *   2. Radiance.  The ray queries' closest-hit walk and layer 2's k_shade_hits on those records, unchanged: a hit gives the forward pixel there
+ *      seen from the ray's origin, a miss the environment map along d, or zeros without a map.  OUT OF SCOPE at the hits, as in layer 2: spot
+ *      lights, shadow-casting point lights, image-based ambient, material extras and mip chains do not take part.
+ *   3. Sum (k_gi_add, round k).  Each channel l of the round's colour is sanitised by selects:  L = l > clamp_max ? clamp_max : (l > 0 ? l : 0)
+ *      -- a NaN becomes 0, +inf becomes clamp_max, a negative becomes 0.  For a pixel that had a ray,
+ *      S[p] = {S.r + L.r, S.g + L.g, S.b + L.b, S.cnt + 1};  round 0 starts from {0, 0, 0, 0} (it stores, it does not add), so the plane needs
+ *      no clearing; a pixel without a ray keeps its S (in round 0: zeros).
+ *   4. Estimate (k_gi_estimate).  Unfiltered:  E = {S.r / S.cnt, S.g / S.cnt, S.b / S.cnt, S.cnt} where S.cnt > 0, else {0, 0, 0, 0}.
+ *      Filtered (filter = 1), for a covered pixel p: the ambient occlusion filter's window, pixel order (rows of the window outside, columns
+ *      inside) and acceptance test -- p itself always accepted; another pixel q accepted iff inside the frame, covered,
+ *      dot(m_p, m_q) >= normal_cos and fabs(dot(m_p, w_q - w_p)) <= plane_dist.  A = {0, 0, 0, 0};  for every accepted pixel q IN WINDOW ORDER,
+ *      p at its own place:  A = {A.r + S_q.r, A.g + S_q.g, A.b + S_q.b, A.cnt + S_q.cnt};  E = A's estimate by the unfiltered formula, so E.a is
+ *      the accepted ray count.  A rejected pixel's S is not looked at (a select, not a product by zero: a NaN there stays there).  A pixel that
+ *      is not covered gives {0, 0, 0, 0}.
+ * Sharded handles.  The pattern uses the row of the FRAME; filter = 1 on a handle that does not own the whole frame is refused with
+ *   ARCTIC_E_STATE, by the occlusion's rule.
+ * KNOWN LIMITS.  Those of the ray definition and of layer 2; the normal is the interpolated vertex normal; one bounce: the radiance at a hit holds
+ *   the flat ambient term there, not a second bounce.  The calls use the reflection plane's rays, hits and colours as a round's scratch: a
+ *   reflection plane left on the device (arctic_trace_reflections with a NULL output) is overwritten. */
+typedef struct ArcticGi {   /* 48 bytes */
+    uint32_t n_rays;       /* rays per pixel = rounds, 1..16 */
+    uint32_t pattern;      /* P = 1, 2 or 4: pixel (x, y) OF THE FRAME uses direction set (y % P) * P + x % P */
+    float    max_distance; /* every ray's t_max: > 0, +inf allowed */
+    float    bias;         /* finite */
+    float    clamp_max;    /* the upper bound of a sanitised channel: > 0, finite */
+    uint32_t filter;       /* 0: per-pixel estimate; 1: the sum over the P x P window */
+    float    normal_cos;   /* filter only, finite */
+    float    plane_dist;   /* filter only, >= 0 */
+    uint32_t reserved[4];  /* 0 */
+} ArcticGi;
+
+/* E for every pixel of the handle's RESIDENT G-buffer: rows * width * 4 floats, row-major over the handle's rows like arctic_trace_reflections.
+ * rgba32f == NULL leaves the plane on the device and does not synchronise (timing).  Once the handle is warm a call allocates nothing; the
+ * table is sent again only when its bytes changed.
+ * Refusals, in this order; a refused call writes nothing and enqueues nothing.  ARCTIC_E_INVALID: a null scene, gi or dirs; n_rays outside
+ * 1..16; pattern not 1, 2 or 4; max_distance not > 0 (a NaN included); a bias that is not finite; a clamp_max that is not > 0 and finite;
+ * filter > 1 or a reserved word != 0; with the filter on, a normal_cos that is not finite or a plane_dist that is negative or a NaN; a direction
+ * component that is not finite.  ARCTIC_E_STATE: no G-buffer; the sun map's states of layer 2; the filter on a shard. */
+int arctic_trace_gi(ArcticRenderer *r, const ArcticScene *scene, const ArcticGi *gi, const float *dirs, float *rgba32f);
+
+/* The same into DEVICE memory the caller owns (rows * width * 16 bytes, 16-byte aligned), stream-ordered on the handle's stream.  dirs stays a host
+ * pointer.  ARCTIC_E_INVALID also, first, for a null or misaligned d_rgba32f. */
+int arctic_trace_gi_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticGi *gi, const float *dirs, float *d_rgba32f);
+
+/* For tests: the records of round `round` (stage 1 alone), rows * width of them, row-major.  Needs no scene.  ARCTIC_E_INVALID: what the call
+ * above refuses for gi and dirs, then a round >= n_rays or a null output.  ARCTIC_E_STATE: no G-buffer. */
+int arctic_gi_rays(ArcticRenderer *r, const ArcticGi *gi, const float *dirs, uint32_t round, ArcticRay *rays);
+
+/* The latest arctic_trace_gi(_device)'s S and E as they stand on the device (either may be NULL).  ARCTIC_E_STATE: nothing traced yet, or not since
+ * the last resize; E asked for when the latest call wrote the caller's plane. */
+int arctic_read_gi_estimate(ArcticRenderer *r, float *sum_rgba32f, float *estimate_rgba32f);
+
+/* out4 = {bytes of device memory held for the table, S, E, the history and the composition's planes (the rays, hits and colours are the reflection
+ * plane's: arctic_hit_shading_info), launches of this section's own kernels so far, tracing calls so far, bytes of the history alone}.
+ * {0, 0, 0, 0} until the first call that passes its checks. */
+int arctic_gi_info(ArcticRenderer *r, uint64_t *out4);
+
+/* 5. TEMPORAL ACCUMULATION of E (k_gi_accumulate).  Steps 1 to 6 of arctic_accumulate_ambient_occlusion_device's definition word for word, with
+ * `value` a three-channel colour: the reprojection of the pixel's world position through the PREVIOUS call's proj_view, the four taps, the
+ * acceptance of a tap q on its STORED m_q and w_q, the weights w_q, S = the accepted weights' sum, min_weight, N = min(hn + 1, max_history) and
+ * a = 1 / N are all unchanged.  What changes:  V becomes three ordered sums, V_c = ((k0*acc_c,0 + k1*acc_c,1) + k2*acc_c,2) + k3*acc_c,3 over the
+ * accepted taps;  hv_c = V_c / S;  acc_c = hv_c + (cur_c - hv_c) * a, with cur = E.rgb of the plane given.  A pixel whose E.a is 0 is treated as
+ * NOT COVERED: its output is {0, 0, 0, 0} and the entry written is all zero.  The output is {acc.rgb, N}; without an accepted history
+ * (S <= min_weight, or the first call) it is {E.rgb, 1}.
+ * The history is three float4 planes per pixel -- {w, N}, {m, 0}, {acc, 0} -- in two sets, tile-major like the occlusion's: 96 bytes per pixel,
+ * allocated by the first call, reported by arctic_gi_info, emptied by arctic_gi_history_reset and by a resize.  It is this section's own: the
+ * occlusion's history is not touched.  Whole frames only (ARCTIC_E_STATE on a shard, by the occlusion's rule).
+ * KNOWN LIMITS.  The plain form's: the reprojection follows the camera alone, so a moving or deforming object drags its history until the normal
+ *   and plane tests reject it; the motion-vector form (arctic_accumulate_ambient_occlusion_motion_device's) is OUT OF SCOPE here.  Light that
+ *   changes is followed at the rate 1 / max_history. */
+typedef struct ArcticGiHistory {   /* 32 bytes: ArcticAoHistory's fields and refusals */
+    float    max_history;  /* in [1, 65536] */
+    float    normal_cos;   /* finite */
+    float    plane_dist;   /* >= 0 */
+    float    min_weight;   /* in [0, 1) */
+    uint32_t reserved[4];  /* 0 */
+} ArcticGiHistory;
+
+/* d_gi_in_rgba32f (E: rows * width float4, row-major, 16-byte aligned, e.g. arctic_trace_gi_device's output) blended into the handle's history,
+ * the result {acc, N} into d_gi_out_rgba32f (it may be the same plane); stream-ordered on the handle's stream.
+ * Refusals, in this order; a refused call writes nothing.  ARCTIC_E_INVALID: a null scene; null parameters or plane; a plane that is not 16-byte
+ * aligned; max_history outside [1, 65536]; a normal_cos that is not finite; a plane_dist that is negative or a NaN; min_weight outside [0, 1);
+ * reserved != 0.  ARCTIC_E_STATE: no G-buffer; a handle that does not own the whole frame. */
+int arctic_accumulate_gi_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticGiHistory *hist, const float *d_gi_in_rgba32f, float *d_gi_out_rgba32f);
+
+/* The same from and to host memory; synchronous. */
+int arctic_accumulate_gi(ArcticRenderer *r, const ArcticScene *scene, const ArcticGiHistory *hist, const float *gi_in_rgba32f, float *gi_out_rgba32f);
+
+/* Empties the history (the next call is a first call); frees nothing. */
+int arctic_gi_history_reset(ArcticRenderer *r);
+
+/* The current history, row-major (any pointer may be NULL): acc3 and world3 and normal3 = height * width * 3 floats, count = height * width.
+ * ARCTIC_E_STATE: the history is empty. */
+int arctic_read_gi_history(ArcticRenderer *r, float *acc3, float *count, float *world3, float *normal3);
+
+/* 6. COMPOSITION (k_gi_compose, a kernel and a call of its own: arctic_compose_planes_device is what it was).  Per pixel WITH GEOMETRY (a material
+ * the handle has), with base, metal sampled exactly as k_compose samples them (level 0, the default sampler, the G-buffer's uv and material):
+ *   C = the HDR colour: the caller's plane (rows * width * 3 floats, row-major), or with NULL the handle's shaded plane, or under
+ *       ARCTIC_GI_SOURCE_COMPOSED the composed one -- the refusals of those sources are the post stages' (ARCTIC_OPT_KEEP_FLOAT_OUTPUT, ...).
+ *   Ambient correction:   C_c = C_c + (ambient * base_c) * (ambient_scale - 1)      -- the occlusion's form with ka = ambient_scale:
+ *       ambient_scale = 1 adds an exact zero, ambient_scale = 0 takes the flat ambient term out, so that E replaces it.
+ *   Where E.a > 0 (a select; E.rgb is not looked at elsewhere):   C_c = C_c + (gi_strength * (1 - metal)) * (base_c * E_c)
+ *   then the shared tonemapper to float LDR and RGBA8.  A pixel without geometry keeps its C.
+ * E is the caller's plane (arctic_trace_gi_device's or arctic_accumulate_gi_device's output) or, with NULL, the handle's own estimate.  Written:
+ * the handle's own HDR, LDR and RGBA8 planes (arctic_read_gi), or the caller's d_out_hdr_rgb32f / d_out_rgba8.  The later stages take the
+ * result through their explicit colour argument, as they take the fog's: there is no *_SOURCE_GI flag.  Shards compose their own rows.
+ * Indirect SPECULAR light is out of scope: the reflection plane is that term.
+ * Refusals, in this order; a refused call writes nothing.  ARCTIC_E_INVALID: a null scene or settings; null parameters; unknown flag bits; a
+ * gi_strength that is negative or not finite; ambient_scale outside [0, 1]; reserved != 0; a misaligned plane (E: 16 bytes, the others 4).
+ * ARCTIC_E_STATE: no G-buffer; with a NULL C the source's states; with a NULL E no estimate on the handle; with ambient_scale != 1 what refuses
+ * ARCTIC_COMPOSE_AO (ARCTIC_OPT_ENV_LIGHTING, ARCTIC_OPT_TEXTURE_MIPS = 1, a material that is not neutral), and with ARCTIC_GI_SOURCE_COMPOSED
+ * a latest composition that had ARCTIC_COMPOSE_AO: it has scaled the term already. */
+#define ARCTIC_GI_SOURCE_COMPOSED 1u   /* a NULL colour plane means the composed HDR plane, not the shaded one */
+typedef struct ArcticGiCompose {   /* 32 bytes */
+    uint32_t flags;         /* 0 or ARCTIC_GI_SOURCE_COMPOSED */
+    float    gi_strength;   /* >= 0, finite */
+    float    ambient_scale; /* in [0, 1]: what is left of the flat ambient term */
+    uint32_t reserved[5];   /* 0 */
+} ArcticGiCompose;
+
+int arctic_gi_compose_device(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticGiCompose *compose, const float *d_hdr_rgb32f,
+                             const float *d_gi_rgba32f, float *d_out_hdr_rgb32f, uint8_t *d_out_rgba8);
+
+/* What the latest composition left in the handle's own planes (any pointer may be NULL).  ARCTIC_E_STATE: nothing composed yet, or not since the
+ * last resize; a plane asked for that the latest call wrote into the caller's memory instead. */
+int arctic_read_gi(ArcticRenderer *r, float *ldr_rgb, float *hdr_rgb, uint8_t *rgba8);
+
+/* The one call: arctic_trace_gi into the handle's own estimate, arctic_accumulate_gi_device on that plane in place when hist != NULL, then
+ * arctic_gi_compose_device with a NULL colour and the handle's estimate -- byte for byte the calls made by hand.  Every refusal of the three comes
+ * before anything is enqueued, in the order: gi and dirs, hist, compose (ARCTIC_E_INVALID); then the states of the trace, of the accumulation and
+ * of the composition (ARCTIC_E_STATE). */
+int arctic_pass_gi(ArcticRenderer *r, const ArcticScene *scene, const ArcticSettings *settings, const ArcticGi *gi, const float *dirs, const ArcticGiHistory *hist,
+                   const ArcticGiCompose *compose, uint8_t *d_out_rgba8);
+
+/* The host arbiters (no handle, no GPU), running the functions the kernels run.  arctic_gi_points: round `round`'s record for point k =
+ * {world3, normal3} of points6, which has geometry, using direction set sets[k]; the all-zero record for a point that is not covered.  Refuses
+ * what arctic_trace_gi refuses for gi and dirs, a round >= n_rays, a null pointer with a non-zero count and a sets[k] >= P*P. */
+int arctic_gi_points(const float *points6, const uint32_t *sets, uint64_t n_points, const ArcticGi *gi, const float *dirs, uint32_t round, ArcticRay *rays);
+
+/* Stages 3 and 4 for a whole frame of width x height pixels: rays and colors4 hold n_rays rounds of width*height records / float4 colours, round
+ * after round; normal3, world3 (attributes 8..10 and 11..13) and geometry (0: none) are read with the filter on only and may be NULL without it.
+ * sum4 and estimate4 receive S and E.  Refuses what arctic_trace_gi refuses for gi, a width or height of 0 or above 16384 and a null pointer. */
+int arctic_gi_estimate_pixels(const ArcticGi *gi, uint32_t width, uint32_t height, const ArcticRay *rays, const float *colors4, const float *normal3,
+                              const float *world3, const uint8_t *geometry, float *sum4, float *estimate4);
+
+/* Stage 5 for n pixels in any order, shaped like arctic_accumulate_pixels: cur4 = the pixels' E; prev_proj_view = the previous call's matrix
+ * (NULL: the history is empty) and the previous history as row-major arrays of a width x height frame; out4 = {acc, N}, and the entry written
+ * (any of the four may be NULL).  Refuses what arctic_accumulate_gi_device refuses for hist, a width or height of 0 or above 16384, a matrix
+ * without its four arrays, and a null array with n > 0. */
+int arctic_gi_accumulate_pixels(const ArcticGiHistory *hist, uint64_t n, const float *world3, const float *normal3, const uint8_t *geometry, const float *cur4,
+                                const float *prev_proj_view, uint32_t width, uint32_t height, const float *prev_acc3, const float *prev_count,
+                                const float *prev_world3, const float *prev_normal3, float *out4, float *out_acc3, float *out_count, float *out_world3,
+                                float *out_normal3);
+
+/* Stage 6's two terms for n pixels on channels sampled already, like arctic_compose_pixels: out_hdr3 = C after the ambient correction and the
+ * indirect term.  Refuses what arctic_gi_compose_device refuses for compose, and a null array with n > 0. */
+int arctic_gi_compose_pixels(const ArcticGiCompose *compose, float ambient, uint64_t n, const float *hdr3, const float *base3, const float *metal, const float *gi4,
+                             const uint8_t *geometry, float *out_hdr3);
+
 /* The owner grid of a forward prepass as plain numbers -- pure host functions, no device, no handle (the library's kernels use the
    same definitions).  A handle created with these sizes (row range [row_begin, row_end), or -- band_rows > 0 -- the interleaved
    shard shard_index of shard_count) launches grid[0] x grid[1] owner waves, one per 16x16 block; arctic_owner_visit: grid row
