@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ARCTIC_HIP_LIBRARY") or os.path.join(HERE, "csrc", "libarctic_hip.so")   # the override is for A/B timing of two builds (tools/experiments)
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "arctic_hip.h")
 
-OPTIONS = {"keep_float_output": 1, "count_light_evals": 2, "culling": 3, "debug": 4, "antialias": 5, "hdr16": 6, "ray_refit": 7, "light_pair_runs": 8, "shadow_cache": 9, "visbuffer": 10, "item_table_floor": 11, "light_path": 12, "markers": 13, "shadow_sharded": 14, "frames_in_flight": 15, "tiles_per_wave": 16, "tile_trace": 17, "raster_owner": 18, "tile_order": 19, "order_tail": 20, "sampler": 21, "texture_tiling": 22, "cluster_cull": 23, "small_triangles": 24, "env_lighting": 25, "point_shadow_size": 26, "texture_mips": 27}
+OPTIONS = {"keep_float_output": 1, "count_light_evals": 2, "culling": 3, "debug": 4, "antialias": 5, "hdr16": 6, "ray_refit": 7, "light_pair_runs": 8, "shadow_cache": 9, "visbuffer": 10, "item_table_floor": 11, "light_path": 12, "markers": 13, "shadow_sharded": 14, "frames_in_flight": 15, "tiles_per_wave": 16, "tile_trace": 17, "raster_owner": 18, "tile_order": 19, "order_tail": 20, "sampler": 21, "texture_tiling": 22, "cluster_cull": 23, "small_triangles": 24, "env_lighting": 25, "point_shadow_size": 26, "texture_mips": 27, "hit_model": 0}
 TRACE_ANY, TRACE_BRUTE = 1, 2   # ARCTIC_TRACE_* (include/arctic_hip.h)
 COMPOSE_AO, COMPOSE_REFLECTIONS = 1, 2   # ARCTIC_COMPOSE_*
 TAA_LUMA_WEIGHT, TAA_SOURCE_COMPOSED = 1, 2   # ARCTIC_TAA_*

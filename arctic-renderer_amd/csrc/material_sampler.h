@@ -1,7 +1,8 @@
 // material_sampler.h -- a material's channels at one texture coordinate: the sampler ps_main uses by default (MIN_MAG_MIP_LINEAR + WRAP at level 0,
 // texel centres at +0.5, full fp32 weights, sRGB decoded per texel before filtering), for one pixel at a time and all three image layouts of
-// common.h TexDesc.  ONE copy, included by hit_shade.hip (k_shade_hits) and compose.hip (k_compose); every descriptor and texel is a vector load,
-// per lane.  Device compilation only; compile with contraction off.
+// common.h TexDesc.  ONE copy, included by hit_shade.hip (k_shade_hits), hit_shade_ext.hip (k_shade_hits_ext, which also takes the material's
+// extras: sample_extras below), compose.hip (k_compose) and gi.hip; every descriptor and texel is a vector load, per lane.  Device compilation only;
+// compile with contraction off.
 #pragma once
 #include "common.h"
 #include "ray_query.h"
@@ -93,6 +94,54 @@ __device__ __forceinline__ Channels sample_material(const TexDesc *__restrict__ 
         c.metal = hs_filter(w, hs_byte(t[0], 2), hs_byte(t[1], 2), hs_byte(t[2], 2), hs_byte(t[3], 2)) * (1.0f / 255.0f);
     }
     return c;
+}
+
+// ---- glTF material extras at the same coordinate (common.h MaterialExtra, include/arctic_hip.h next to arctic_set_material_extras; k_shade_hits_ext) ----
+// records = the descriptors' end, tex + 3 n_materials: record m is four descriptor slots from records + 4 m.  The twelve constants are three
+// 16-byte vector loads per lane; the images are taken at level 0 under the sampler above, in both storage layouts:
+//   EXTRA_FAST  one image of 4-byte texels {e.r, e.g, e.b, o} with the packed image's one-texel WRAP border, row-major: the footprint's first
+//               texel and weights are hs_fetch_packed's on the same sizes, i.e. the material's own at level 0
+//   otherwise   two plain RGBA8 images (hs_fetch_plain), each present when its flag bit is set; occlusion is .r
+// An absent image reads as 1.  ao = 1 + strength (o - 1);  emis = e * emissive_factor with e sRGB-decoded per texel before filtering
+struct ExtraChannels { float base[3], metal, rough, nscale, ao, emis[3]; };
+__device__ __forceinline__ ExtraChannels sample_extras(const TexDesc *__restrict__ records, const float *__restrict__ lut, uint32_t mat, float u, float v) {
+    const TexDesc *rec = records + EXTRA_SLOTS * mat;
+    const rq_f4 *p = reinterpret_cast<const rq_f4 *>(rec);
+    const rq_f4 k0 = p[0], k1 = p[1], k2 = p[2];   // base rgb, metallic | roughness, normal scale, occlusion strength, emissive r | emissive g, b, flags
+    const uint32_t flags = rq_bits(k2[2]);
+    float e[3] = {1.0f, 1.0f, 1.0f}, occ = 1.0f;
+    if (flags & EXTRA_FAST) {
+        const TexDesc d = load_desc(rec, 2u);
+        int x0, y0;
+        float fx, fy;
+        hs_axis(u, d.wf, (int)(d.w & ~TEX_INTERLEAVED), x0, fx);
+        hs_axis(v, d.hf, (int)d.h, y0, fy);
+        const uint32_t o = (uint32_t)(y0 + 1) * d.pitch + (uint32_t)(x0 + 1);   // padded texel (x0 + 1, y0 + 1): never a wrap test
+        const uint32_t t[4] = {d.texels[o], d.texels[o + 1u], d.texels[o + d.pitch], d.texels[o + d.pitch + 1u]};
+        const Weights w = hs_weights(fx, fy);
+        if (flags & EXTRA_EMISSIVE) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) e[k] = hs_filter(w, lut[(t[0] >> (8 * k)) & 0xFFu], lut[(t[1] >> (8 * k)) & 0xFFu], lut[(t[2] >> (8 * k)) & 0xFFu], lut[(t[3] >> (8 * k)) & 0xFFu]);
+        }
+        if (flags & EXTRA_OCCLUSION) occ = hs_filter(w, hs_byte(t[0], 3), hs_byte(t[1], 3), hs_byte(t[2], 3), hs_byte(t[3], 3)) * (1.0f / 255.0f);
+    } else {
+        uint32_t t[4];
+        if (flags & EXTRA_EMISSIVE) {
+            const Weights w = hs_fetch_plain(load_desc(rec, 2u), u, v, t);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) e[k] = hs_filter(w, lut[(t[0] >> (8 * k)) & 0xFFu], lut[(t[1] >> (8 * k)) & 0xFFu], lut[(t[2] >> (8 * k)) & 0xFFu], lut[(t[3] >> (8 * k)) & 0xFFu]);
+        }
+        if (flags & EXTRA_OCCLUSION) {
+            const Weights w = hs_fetch_plain(load_desc(rec, 3u), u, v, t);
+            occ = hs_filter(w, hs_byte(t[0], 0), hs_byte(t[1], 0), hs_byte(t[2], 0), hs_byte(t[3], 0)) * (1.0f / 255.0f);
+        }
+    }
+    ExtraChannels x;
+    x.base[0] = k0[0]; x.base[1] = k0[1]; x.base[2] = k0[2];
+    x.metal = k0[3]; x.rough = k1[0]; x.nscale = k1[1];
+    x.ao = __builtin_fmaf(k1[2], occ - 1.0f, 1.0f);
+    x.emis[0] = e[0] * k1[3]; x.emis[1] = e[1] * k2[0]; x.emis[2] = e[2] * k2[1];
+    return x;
 }
 
 }  // namespace

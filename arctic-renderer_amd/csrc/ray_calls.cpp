@@ -17,6 +17,7 @@
 #include "ray_query.h"
 #include "ray_ao.h"
 #include "hit_shade.h"
+#include "hit_shade_ext.h"
 #include "compose.h"
 #include "ao_history.h"
 #include "motion.h"
@@ -410,15 +411,19 @@ int arctic_hit_attributes(ArcticRenderer *r, const ArcticScene *scene, const Arc
 // ---- hit shading and the reflection plane (include/arctic_hip.h; the kernels: hit_shade.hip) -------------------------------------------------------
 }  // extern "C"
 namespace arctic {   // (renderer_state.h: gi_calls.cpp runs the hit shading between kernels of its own)
-// the sun's map as k_shade_hits needs it: whole, and drawn or written at least once
+// the sun's map as k_shade_hits (and k_shade_hits_ext) needs it: whole, and drawn or written at least once
 int sun_map_ready(ArcticRenderer *r, const char *who) {
     if (r->shadow_size && r->shadow_sharded)
         return r->fail(ARCTIC_E_STATE, "%s: the sun's map is sharded (ARCTIC_OPT_SHADOW_SHARDED): a hit may lie in rows this handle never draws", who);
     if (r->shadow_size && !r->shadow_written_set[r->scur])
         return r->fail(ARCTIC_E_STATE, "%s: the sun's map was never drawn or written (arctic_pass_shadow_map, arctic_write_shadow_map or a frame first)", who);
+    // ... and, under ARCTIC_OPT_HIT_MODEL = 1, the cube lights' faces as k_shade_hits_ext needs them: drawn or written since the list was set
+    if (r->hit_model == 1 && r->n_cubes && !r->cube_faces_filled)
+        return r->fail(ARCTIC_E_STATE, "%s: ARCTIC_OPT_HIT_MODEL = 1 and the shadow-casting point lights' faces were neither drawn nor written since the list was set "
+                       "(arctic_pass_point_shadows, arctic_write_point_shadow or a frame first)", who);
     return ARCTIC_OK;
 }
-// the structure, the tables and the launch: device pointers throughout
+// the structure, the tables and the launch: device pointers throughout.  Every caller has asked sun_map_ready in front of its first launch
 int shade_hits(ArcticRenderer *r, const ArcticScene *sc, const void *d_rays, const void *d_hits, uint64_t n, float4 *d_out) {
     int rc = ensure_hit_scene(r, sc);
     if (rc || n == 0) return rc;
@@ -432,6 +437,16 @@ int shade_hits(ArcticRenderer *r, const ArcticScene *sc, const void *d_rays, con
     dir_from_rot(sc->sun.rotation, p.sun_dir);
     std::memcpy(p.sun_color, sc->sun.color, sizeof p.sun_color);
     sun_proj_view(sc->sun.position, sc->sun.rotation, p.lpv);
+    if (r->hit_model == 1) {   // the same block, and the handle's other tables as they stand (hit_shade_ext.h)
+        HitShadeExtParams q = {};
+        q.base = p;
+        if (r->n_spots) { q.spots = r->d_spots.as<float4>(); q.n_spots = r->n_spots; }
+        if (r->n_cubes) { q.cubes = r->d_cubes.as<float4>(); q.n_cubes = r->n_cubes; q.cube_size = r->cube_size; }
+        if (r->has_extras()) q.extras = p.tex + r->tex.size();   // one MaterialExtra per material behind the 3 n_materials descriptors (common.h)
+        if (r->env_active()) q.env_tables = r->d_env_tables.as<EnvTables>();
+        HIPCHECK(r, launch_shade_hits_ext(d_rays, d_hits, n, q, d_out, r->stream));
+        return ARCTIC_OK;
+    }
     HIPCHECK(r, launch_shade_hits(d_rays, d_hits, n, p, d_out, r->stream));
     return ARCTIC_OK;
 }

@@ -416,6 +416,7 @@ int pass_point_shadows(ArcticRenderer *r, const ArcticScene *sc, hipStream_t str
         }
     }
     HIPCHECK(r, r->shadow_scratch_free.record(stream));
+    if (rc == ARCTIC_OK) r->cube_faces_filled = true;
     return rc;
 }
 
@@ -1473,6 +1474,7 @@ int arctic_update_point_shadow_lights(ArcticRenderer *r, const ArcticPointShadow
     r->cube_lights.assign(lights, lights + k);
     r->n_cubes = k;
     r->cube_key.clear();
+    r->cube_faces_filled = false;   // (cleared to 1.0: nothing has been drawn into them)
     return ARCTIC_OK;
 }
 
@@ -1506,6 +1508,7 @@ int arctic_write_point_shadow(ArcticRenderer *r, uint32_t light, const float *fa
     const size_t n = (size_t)6 * r->cube_size * r->cube_size;
     HIPCHECK(r, hipMemcpy(cube_faces(r) + light * n, faces, n * 4, hipMemcpyHostToDevice));
     r->cube_key.clear();
+    r->cube_faces_filled = true;
     return ARCTIC_OK;
 }
 
@@ -2097,9 +2100,13 @@ int arctic_set_option(ArcticRenderer *r, uint32_t option, int64_t value) {
             rc = cube_store(r, r->cube_lights.data(), r->n_cubes, (uint32_t)value);
             if (rc != ARCTIC_OK) return rc;
         }
-        r->cube_size = (uint32_t)value; r->cube_key.clear();
+        r->cube_size = (uint32_t)value; r->cube_key.clear(); r->cube_faces_filled = false;
         break;
     }
+    case ARCTIC_OPT_HIT_MODEL:
+        if (value < 0 || value > 1) return r->fail(ARCTIC_E_INVALID, "ARCTIC_OPT_HIT_MODEL: 0 or 1");
+        r->hit_model = (int)value;
+        break;
     case ARCTIC_OPT_ANTIALIAS:
         if (value < 0 || value > 1) return r->fail(ARCTIC_E_INVALID, "ARCTIC_OPT_ANTIALIAS: 0 or 1");
         r->antialias = (int)value;

@@ -206,6 +206,8 @@ struct ArcticRenderer {
     // behind the previous frame's shading that reads them (pass_point_shadows)
     DevBuf d_cubes;
     uint32_t n_cubes = 0, cube_size = 1024;         // cube_size: ARCTIC_OPT_POINT_SHADOW_SIZE
+    bool cube_faces_filled = false;                 // the faces have been drawn (pass_point_shadows) or written (arctic_write_point_shadow) since the list or F was set: shade_hits asks under hit_model 1
+    int hit_model = 0;                              // ARCTIC_OPT_HIT_MODEL: 0 = k_shade_hits, 1 = k_shade_hits_ext (hit_shade_ext.hip)
     std::vector<ArcticPointShadowLight> cube_lights;   // the list as given: the faces' matrices and the cache key
     std::vector<uint8_t> cube_key;                  // what the faces were drawn from (render_frame redraws them when it changes; empty: redraw)
     PinnedBuf cube_counts;                          // pinned, mapped: CUBE_COUNT_WORDS per face drawn (run_geometry's DepthTarget)

@@ -287,6 +287,9 @@ class Renderer {
                                                uint32_t *material_out) {
         return arctic_interpolate_hits(vertices, n_vertices, indices, n_indices, trs, light_proj_view, material, first_prim, hits, n, attrs, material_out) == ARCTIC_OK;
     }
+    // which pixel the hit shading below -- and with it the reflection plane, the ray effects and the indirect light -- evaluates (ARCTIC_OPT_HIT_MODEL):
+    // 0 (default) the base model; 1 also spot lights, shadow-casting point lights, image-based ambient and material extras, at level 0
+    [[nodiscard]] bool set_hit_model(int model) { return ok(arctic_set_option(m_handle, ARCTIC_OPT_HIT_MODEL, model)); }
     // the forward pixel at every hit, seen from the ray's origin: rgba32f = n x {r, g, b, a}, a = 1 at a hit; a miss takes the environment map, a = 0
     [[nodiscard]] bool shade_hits(const ArcticScene &scene, const ArcticRay *rays, const ArcticHit *hits, uint64_t n, float *rgba32f) {
         return ok(arctic_shade_hits(m_handle, &scene, rays, hits, n, 0, rgba32f));

@@ -342,9 +342,15 @@ class Renderer:
         self._check(self.L.arctic_hit_attributes(self.h, C.byref(s), p(h), len(h), p(attrs), p(material)))
         return attrs, material
 
+    def set_hit_model(self, model):
+        """ARCTIC_OPT_HIT_MODEL (the same as set_option("hit_model", model)): 0 = the base model at ray hits, 1 = with spot lights,
+        shadow-casting point lights, image-based ambient and material extras.  shade_hits, trace_reflections, pass_ray_effects, trace_gi and
+        pass_gi follow it.  Any other value raises ArcticError (ARCTIC_E_INVALID)."""
+        self.set_option("hit_model", model)
+
     def shade_hits(self, desc, rays, hits):
         """RAY_DTYPE records and their HIT_DTYPE records -> (n, 4) float32: the forward pixel at each hit seen from the ray's origin, a = 1; for
-        a miss the environment map along the ray (black without one), a = 0."""
+        a miss the environment map along the ray (black without one), a = 0.  Which pixel: set_hit_model."""
         s = self._scene(desc)
         ry = np.ascontiguousarray(rays, dtype=RAY_DTYPE).ravel()
         h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).ravel()

@@ -1052,10 +1052,36 @@ int arctic_interpolate_hits(const ArcticVertex *vertices, uint64_t n_vertices, c
  * Held to the shading pass's standing bar against float64 (tests/test_gpu_hit_shading.py), not defined bit for bit.
  * OUT OF SCOPE at hits: spot lights, shadow-casting point lights, image-based ambient (ARCTIC_OPT_ENV_LIGHTING), material extras
  *   (arctic_set_material_extras) and mip chains (ARCTIC_OPT_TEXTURE_MIPS) do not take part; a handle that has them still answers ARCTIC_OK with
- *   the base model above.
+ *   the base model above.  That is ARCTIC_OPT_HIT_MODEL = 0, the default.
+ * ARCTIC_OPT_HIT_MODEL = 1 (hit_shade_ext.hip: k_shade_hits_ext) shades the hit with the forward pass's whole pixel, each part by the definition
+ *   that stands next to its call or option above, with eye := rays[k].origin, one light at a time in the caller's order:
+ *     Lo    = sun + sum(point) + sum(spot: colour att window / d2) + sum(cube: colour v / d2)
+ *     rgb   = Lo (1 - shadow) + A ao + E,      A = ambient * base'  or, with image-based ambient active, ambient * ibl(n', wo, base', metal', rough')
+ *   material extras (only while a material of the handle is not neutral): the factors on base, metal and rough, normal_scale on the tangent-space x
+ *     and y, E = the sRGB-decoded emissive image * emissive_factor -- not multiplied by (1 - shadow) --, ao = 1 + occlusion_strength (o - 1) on the
+ *     ambient term only; both images bilinear with WRAP at level 0, whichever way the handle stores them.
+ *   spot lights (arctic_update_spot_lights) behind the point lights: att = sat(cd scale + offset)^2, window = sat(1 - (d2 ir2)^2).
+ *   shadow-casting point lights (arctic_update_point_shadow_lights) behind the spots: the face of the largest |d| (ties x, then y, then z), the
+ *     lookAt rows above, four clamped texels, compare then bilinear, v = 1 inside the near and beyond the far plane; their sum stands under the
+ *     sun's (1 - shadow) like every other light's.
+ *   image-based ambient, when ARCTIC_OPT_ENV_LIGHTING = 1 and a map are both there: the bracket of that option from the resident tables in place of
+ *     ambient * base; never multiplied by the sun's shadow.
+ *   Mip chains STAY OUT under both values: a hit has no pixel footprint, so every image is sampled at level 0; so do ARCTIC_OPT_SAMPLER's modes.
+ *   A hit AT the ray's origin (world == origin by bits: t = 0 on a surface the origin lies on) has wo = 0 / 0 under both models, and its colour is
+ *   not a number wherever wo is used: the base model does not use it where the sun's shadow is total, the image-based ambient always does.
+ *   Alpha, misses and invalid directions are those of the base model.  A handle with no spot light, no shadow-casting point light, only neutral
+ *   materials and no active image-based ambient gets the base model's bytes.  Every consumer of the hit shading follows the option:
+ *   arctic_shade_hits(_device), arctic_trace_reflections(_device), arctic_pass_ray_effects*, arctic_trace_gi, arctic_pass_gi.  Held to the same bar
+ *   against float64 (tests/test_gpu_hit_model.py).  A handle that never sets the option allocates nothing for it.
  * Refusals, before the device is touched; a refused call writes nothing.  ARCTIC_E_INVALID: a null scene, flags != 0, a null pointer with n > 0.
  *   ARCTIC_E_CAPACITY: n above 2^32 - 1 (or a scene too large).  ARCTIC_E_STATE: the handle has a sun map (shadow_size != 0) that was never
- *   drawn or written, or that is sharded (ARCTIC_OPT_SHADOW_SHARDED). */
+ *   drawn or written, or that is sharded (ARCTIC_OPT_SHADOW_SHARDED); under ARCTIC_OPT_HIT_MODEL = 1 also a non-empty list of shadow-casting
+ *   point lights whose faces were neither drawn (arctic_pass_point_shadows, a frame) nor written (arctic_write_point_shadow) since the list or
+ *   ARCTIC_OPT_POINT_SHADOW_SIZE was set.  That state is ONE flag for the whole list, like the sun map's: arctic_write_point_shadow of one light
+ *   sets it for all (the others' faces are then the cleared 1.0: everything lit), and a drawn face whose rasteriser table overflowed (the
+ *   ARCTIC_E_CAPACITY of the next synchronising call) still counts as drawn -- render again, as that error says. */
+#define ARCTIC_OPT_HIT_MODEL         0 /* 0 (default) = the base model at hits (k_shade_hits); 1 = the extended model above; anything else: ARCTIC_E_INVALID.
+                                          (Its number is 0: 1 .. 27 are taken -- 14 in arctic_dist.h -- and 0 was the free one that is not above them.) */
 int arctic_shade_hits(ArcticRenderer *r, const ArcticScene *scene, const ArcticRay *rays, const ArcticHit *hits, uint64_t n, uint32_t flags, float *rgba32f);
 
 /* The same between DEVICE buffers the caller owns (16-byte aligned), stream-ordered on the handle's stream like arctic_trace_rays_device: call
